@@ -1,9 +1,14 @@
 #!/usr/bin/env python
 """bench.py -- Mdisparities/s of the CStereoMatching hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: either as above -- bench.py then starts N ranks itself through torch.distributed.run on 127.0.0.1 -- or
    python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run sets up, warms up, times the K steps and prints the result line (headline figure, ms_per_step, config).
+--full adds everything else this file measures: the stage split, one pair alone, the PCIe and filter timings, the
+roofline (with its rocprofv3 --pmc passes), the NCC kernel alone, the C++ adapter and the CPU baseline.
+--dump-outputs DIR writes what the timed path computed in its last step (see dump_outputs).
 
 A "step" is one pass of the hot path (ConstructPyrm -> MatchOneLayer x PyrmNum, both directions ->
 DisparityToCloud) over a batch of --inflight (3) stereo pairs per GPU, inputs already resident in HBM, followed (N > 1)
@@ -43,11 +48,17 @@ def main():
                     help="c2 (default): BASELINE configs[1], weak scaling; c4: BASELINE configs[3] = the 10-pair C3 rig sharded pair %% N over "
                          "the N GPUs with the RCCL gather of all ten clouds in every step, STRONG scaling (c4s: the same at the shipped scale)")
     ap.add_argument("--inflight", type=int, default=3, help="pairs in flight per GPU (contexts run concurrently by rsm_run_pairs)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: stage split, one pair alone, PCIe and filter timings, roofline, NCC kernel alone, "
+                         "C++ adapter, CPU baseline (the options below that name one of these act only with --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed in the last step as DIR/<name>.npy (float64 / float32, "
+                         "at most 64 MB in all: a fixed, seeded sample of a larger output)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--opt", action="append", default=[], help="rsm_set_option name=value (tuning knobs)")
     ap.add_argument("--stage-events", type=int, default=0, help="1: per-stage events inside the timed region too")
     ap.add_argument("--measure-traffic", type=int, default=1,
-                    help="1 (default, N = 1): two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) of one pair in a child process give "
+                    help="1 (default, N = 1, --full): two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) of one pair in a child process give "
                          "roofline.traffic; 0: quote profiles/pmc_traffic.json while it still describes this kernel source")
     ap.add_argument("--adapter-inflight", type=int, default=0,
                     help="pairs in flight inside the C++ adapter's MatchAll (0: three more than --inflight: a slot's pair is uploading, being filtered or downloading part of the time; measured on C2 with 36 pairs, plain / with the filter inside: 5 slots 302 / 210, 6 303 / 219, 7 301 / 210 Mdisp/s)")
@@ -62,6 +73,10 @@ def main():
                          "and out, no RCCL): an auxiliary PCIe-inclusive figure, not the driver's scaling run")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.one_process and args.dump_outputs:
+        ap.error("--dump-outputs times the resident-input path; --one-process has no such path")
 
     if args.one_process:
         raise SystemExit(one_process(args))
@@ -102,12 +117,20 @@ def main():
     dev = torch.device("cuda", local_rank)
     ctxs, cfgs, keep = [], [], []
     jobs = None
+
+    def make_all(pairs):
+        # the seeded inputs of several pairs at once (numpy leaves the GIL in most of it): the same arrays, a third of the time
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(max(1, min(len(pairs), 8))) as ex:
+            return dict(zip(pairs, ex.map(lambda p: make(pair=p), pairs)))
+
     if rig:
         mine = [p for p in range(N_RIG) if p % world == rank]          # pair % n_gpus -> 2,2,1,1,1,1,1,1 at N = 8
         F = max(1, min(args.inflight, len(mine)))
         jobs = [[] for _ in range(F)]                                   # context i matches its pairs one after the other
+        made = make_all(mine)
         for j, p in enumerate(mine):
-            cfgp = make(pair=p)
+            cfgp = made[p]
             t_img = [torch.from_numpy(np.ascontiguousarray(cfgp.image[v])).to(dev) for v in range(2)]
             t_msk = [torch.from_numpy(np.ascontiguousarray(cfgp.mask[v])).to(dev) for v in range(2)]
             jobs[j % F].append((p, cfgp, t_img, t_msk))                 # the inputs of every local pair stay resident in HBM
@@ -126,8 +149,9 @@ def main():
             cfgs.append(make(pair=0))
     else:
         F = max(1, args.inflight)
+        made = make_all([rank * F + i for i in range(F)])
         for i in range(F):  # a differently-seeded pair per rank and slot, uploaded once, outside the timed region
-            cfg = make(pair=rank * F + i)
+            cfg = made[rank * F + i]
             c = Context(local_rank)
             for o in args.opt:
                 k, v = o.split("=")
@@ -300,14 +324,19 @@ def main():
             a["ms"] += v["ms"]; a["launches"] += v["launches"]; a["bytes"] += v["bytes"]
     for c in ctxs:
         c.profile_enable(False)
-    ctx.profile_enable(1)
-    ctx.run_pair()  # the stage split: one pair alone, untimed
-    fence()
-    stage_prof = ctx.profile_get()
-    ctx.profile_enable(False)
+    if args.dump_outputs:   # before anything else runs on these contexts: their results are still the last timed step's
+        pair_of = [(jobs[i][-1][0] if jobs[i] else None) for i in range(len(ctxs))] if rig else [rank * F + i for i in range(len(ctxs))]
+        dump_outputs(args.dump_outputs, [(p, c) for p, c in zip(pair_of, ctxs) if p is not None], n_pairs_total)
+    stage_prof = None
+    if args.full:
+        ctx.profile_enable(1)
+        ctx.run_pair()  # the stage split: one pair alone, untimed
+        fence()
+        stage_prof = ctx.profile_get()
+        ctx.profile_enable(False)
 
     single = None
-    if world == 1 and rank == 0:
+    if args.full and world == 1 and rank == 0:
         # one context alone, same workload, same run: what ONE pair costs with the GPU to itself (BASELINE configs[1]
         # is a single pair), and the host-buffer boundary (rsm_upload_pair / rsm_download_pair over PCIe) beside it
         ks = max(2, args.steps // 2)
@@ -358,9 +387,24 @@ def main():
     else:
         v_total = float(v_top)
 
-    if rank == 0:
+    if rank == 0:   # the result line of every run
         ms_per_step = dt / args.steps * 1e3
         value = v_total / (dt / args.steps) / 1e6
+        out = {
+            "metric": "Mdisparities/s per GPU (11x11 NCC, 128 disp)" if args.config == "c2" else "Mdisparities/s",
+            "value": round(value, 3), "unit": "Mdisparities/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "ms_per_pair": round(ms_per_step / F, 3), "higher_is_better": True,
+            "scaling": "strong" if rig else "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+            "config": {"workload": ("C4_rig10_" + cfg.name.rsplit("_p", 1)[0]) if rig else cfg.name, "width": cfg.width, "height": cfg.height,
+                       "pyr_levels": cfg.pyr_levels,
+                       "ncc_window": 2 * cfg.radius + 1, "offset": cfg.offset, "pairs_per_gpu": F, "pairs_in_flight": F,
+                       "v_top_per_pair": int(res.v_top), "n_points_last": int(res.n_points),
+                       "parallelism": ("pairs sharded one process per GPU + fan-in gather of the clouds to rank 0, overlapped with the next step, through %s"
+                                       % ("rsm_comm / rsm_gather_clouds (the library's own RCCL path)" if transport == "rccl" else
+                                          "torch.distributed (%s)" % backend)) if world > 1 else "single GPU",
+                       "transport": transport if exchange else None, "transport_note": transport_note},
+        }
+    if rank == 0 and args.full:
         # ---- roofline of the dominant kernel: the top level's Jacobi sweep (k_refine_sweep<1>, one launch per sweep)
         # (hipEvents recorded by the library right around every 8th k_refine_sweep<1> launch, on its own stream)
         # which kernel carries the top level's sweeps: k_refine_skew<T,1> (T time-skewed sweeps per launch, the default
@@ -407,41 +451,27 @@ def main():
         alone_ms = alone["ms"] / max(1, alone["launches"])
         alone_gbs = (alone["bytes"] / max(1, alone["launches"])) / (alone_ms * 1e-3) / 1e9 if alone_ms > 0 else 0.0
         total_alg_bytes = sum(v["bytes"] for k, v in stage_prof.items() if k not in ("refine_light_top", "refine_skew_top"))
-        out = {
-            "metric": "Mdisparities/s per GPU (11x11 NCC, 128 disp)" if args.config == "c2" else "Mdisparities/s",
-            "value": round(value, 3), "unit": "Mdisparities/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "ms_per_pair": round(ms_per_step / F, 3), "higher_is_better": True,
-            "scaling": "strong" if rig else "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": ("C4_rig10_" + cfg.name.rsplit("_p", 1)[0]) if rig else cfg.name, "width": cfg.width, "height": cfg.height,
-                       "pyr_levels": cfg.pyr_levels,
-                       "ncc_window": 2 * cfg.radius + 1, "offset": cfg.offset, "pairs_per_gpu": F, "pairs_in_flight": F,
-                       "v_top_per_pair": int(res.v_top), "n_points_last": int(res.n_points),
-                       "parallelism": ("pairs sharded one process per GPU + fan-in gather of the clouds to rank 0, overlapped with the next step, through %s"
-                                       % ("rsm_comm / rsm_gather_clouds (the library's own RCCL path)" if transport == "rccl" else
-                                          "torch.distributed (%s)" % backend)) if world > 1 else "single GPU",
-                       "transport": transport if exchange else None, "transport_note": transport_note},
-            "roofline": {"bound": "hbm", "kernel": kname,
-                         "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
-                         # the same launch priced on its MEASURED HBM bytes (PMC): how close the kernel runs to the
-                         # memory system's rate, as opposed to how many of those bytes the algorithm needs
-                         "traffic_GBps": round(traffic / (avg_ms * 1e-3) / 1e9, 1) if traffic and avg_ms > 0 else None,
-                         "traffic_frac": round(traffic / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if traffic and avg_ms > 0 else None,
-                         "avg_launch_ms": round(avg_ms, 5),
-                         "alone": {"avg_launch_ms": round(alone_ms, 5), "achieved": round(alone_gbs, 2),
-                                   "frac": round(alone_gbs / HBM_PEAK_GBS, 4),
-                                   "note": "one pair in flight (untimed extra run): no other pair's kernels beside the launch"},
-                         "launches_timed_per_step": launches // args.steps // F, "concurrent_pairs": F,
-                         "sweeps_per_launch": spl,
-                         # the first sweeps of the level (cache still filling) run one per launch in k_refine_sweep<1>
-                         "single_sweep_kernel": {"kernel": "k_refine_sweep<1>", "avg_launch_ms": round(prof_acc["refine_light_top"]["ms"] / max(1, prof_acc["refine_light_top"]["launches"]), 5),
-                                                 "alone_avg_launch_ms": round(stage_prof["refine_light_top"]["ms"] / max(1, stage_prof["refine_light_top"]["launches"]), 5)} if multi else None,
-                         "sweeps_per_step": stage_prof["refine_sweep_top"]["launches"],
-                         "algorithmic_bytes_per_launch": bytes_per_launch,
-                         "whole_pair_algorithmic_GB": round(total_alg_bytes / 1e9, 3),
-                         "whole_pair_frac": round(total_alg_bytes * F / (dt / args.steps) / 1e9 / HBM_PEAK_GBS, 4)},
-            "stage_ms_per_step": stage_ms,
-        }
+        out["roofline"] = {"bound": "hbm", "kernel": kname,
+                           "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                           "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
+                           # the same launch priced on its MEASURED HBM bytes (PMC): how close the kernel runs to the
+                           # memory system's rate, as opposed to how many of those bytes the algorithm needs
+                           "traffic_GBps": round(traffic / (avg_ms * 1e-3) / 1e9, 1) if traffic and avg_ms > 0 else None,
+                           "traffic_frac": round(traffic / (avg_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4) if traffic and avg_ms > 0 else None,
+                           "avg_launch_ms": round(avg_ms, 5),
+                           "alone": {"avg_launch_ms": round(alone_ms, 5), "achieved": round(alone_gbs, 2),
+                                     "frac": round(alone_gbs / HBM_PEAK_GBS, 4),
+                                     "note": "one pair in flight (untimed extra run): no other pair's kernels beside the launch"},
+                           "launches_timed_per_step": launches // args.steps // F, "concurrent_pairs": F,
+                           "sweeps_per_launch": spl,
+                           # the first sweeps of the level (cache still filling) run one per launch in k_refine_sweep<1>
+                           "single_sweep_kernel": {"kernel": "k_refine_sweep<1>", "avg_launch_ms": round(prof_acc["refine_light_top"]["ms"] / max(1, prof_acc["refine_light_top"]["launches"]), 5),
+                                                   "alone_avg_launch_ms": round(stage_prof["refine_light_top"]["ms"] / max(1, stage_prof["refine_light_top"]["launches"]), 5)} if multi else None,
+                           "sweeps_per_step": stage_prof["refine_sweep_top"]["launches"],
+                           "algorithmic_bytes_per_launch": bytes_per_launch,
+                           "whole_pair_algorithmic_GB": round(total_alg_bytes / 1e9, 3),
+                           "whole_pair_frac": round(total_alg_bytes * F / (dt / args.steps) / 1e9 / HBM_PEAK_GBS, 4)}
+        out["stage_ms_per_step"] = stage_ms
         out["roofline"]["traffic_source"] = traffic_source  # measured = this run's own --pmc passes; quoted = profiles/pmc_traffic.json
         valu = traffic_detail.pop("valu", None) if isinstance(traffic_detail, dict) else None
         scalar = traffic_detail.pop("scalar", None) if isinstance(traffic_detail, dict) else None
@@ -484,6 +514,7 @@ def main():
                                    ("%.0f %%" % (100 * fr["scalar"])) if fr.get("scalar") is not None else "?",
                                    ("%.0f %%" % (100 * fr["lds"])) if fr.get("lds") is not None else "?",
                                    ("%.0f %%" % (100 * parked)) if parked is not None else "?"))
+    if rank == 0:
         if rig:
             # BASELINE configs[3]: the SAME ten pairs at every N (strong scaling): pair p on rank p % N; a step
             # = all ten pairs matched once + (N > 1) the RCCL fan-in of the ten clouds to rank 0; 10 pairs on 8 GPUs cap at 5x
@@ -503,7 +534,7 @@ def main():
             out["value_single_pair_pcie_inclusive_pinned"] = round(res.v_top / (single + h2d + d2h_pinned) / 1e6, 3)
             out["filter_ms"] = round(filt[0] * 1e3, 2)
             out["filter_points"] = {"in": int(n_pts), "kept": int(filt[1])}
-        if world == 1 and args.config in ("c2", "c5"):
+        if args.full and world == 1 and args.config in ("c2", "c5"):
             # the NCC kernel alone (pixel x candidate evaluations per second) at SURVEY 8(d)'s two points, two launches each
             out["ncc_kernel"] = {}
             for r_, cands in ((5, 129), (7, 257)):
@@ -511,7 +542,7 @@ def main():
                 px = (cfg.width - 2 * r_) * (cfg.height - 2 * r_)
                 out["ncc_kernel"]["%dx%d_%d" % (2 * r_ + 1, 2 * r_ + 1, cands)] = {
                     "ms_per_launch": round(ms, 3), "MDE_per_s": round(px * cands / ms / 1e3, 1)}
-        if world == 1 and args.config in ("c2", "c3", "c5") and args.adapter_pairs > 0 and not rig:
+        if args.full and world == 1 and args.config in ("c2", "c3", "c5") and args.adapter_pairs > 0 and not rig:
             # the drop-in as a maintainer integrates it: the compiled C++ adapter's MatchAll (include/rsm_stereo_adapter.hpp),
             # host images in, InsertPoint stream out, PCIe included -- never `value`
             try:
@@ -530,7 +561,7 @@ def main():
                 out["adapter_fp64_points"] = ab["fp64"]
             except Exception as e:  # noqa: BLE001
                 out["adapter"] = {"error": "%s: %s" % (type(e).__name__, str(e)[:300])}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(synth)
         print(json.dumps(out), flush=True)
     for c in ctxs:
@@ -794,6 +825,40 @@ def adapter_bench(cfgs, n_pairs, inflight, v_top):
         return res
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
+
+
+DUMP_BYTES = 60 * 1000 * 1000   # --dump-outputs: all pairs of all ranks together stay under 64 MB
+
+
+def dump_outputs(path, pairs, n_pairs_total):
+    """--dump-outputs DIR: the arrays rsm_download_pair hands a caller of the timed path, for every (pair id, context) of this
+    rank, as the last timed step left them:
+      pair<p>_disparity0 / _disparity1  float64 H x W (NOMATCH = -10000), flattened
+      pair<p>_xyz                       float64 n_points x 3 (InsertPoint order)
+      pair<p>_bgr                       float32 n_points x 3 (the uint8 colours)
+      pair<p>_info                      float64 [n_points, v_top, margin[0] (6 values), margin[1] (6 values)]
+    Each pair gets an equal share of DUMP_BYTES.  A longer array is replaced by a fixed sample of its rows (pixels or
+    points): the row indices np.random.default_rng(crc32(file name)).choice(rows, k, replace=False), sorted -- the same
+    indices for the same shape in every run, so two builds compare output for output."""
+    import zlib
+    os.makedirs(path, exist_ok=True)
+    # rows of k per pair: two disparity samples (8 B), xyz (24 B) and bgr (12 B)
+    k = max(1, DUMP_BYTES // max(1, n_pairs_total) // (2 * 8 + 24 + 12))
+
+    def save(name, a):
+        if a.shape[0] > k:
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(a.shape[0], k, replace=False))
+            a = a[idx]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+
+    for p, c in pairs:
+        r = c.download_pair()
+        for v in range(2):
+            save("pair%d_disparity%d" % (p, v), np.asarray(r.disparity[v], np.float64).reshape(-1))
+        save("pair%d_xyz" % p, np.asarray(r.xyz, np.float64))
+        save("pair%d_bgr" % p, np.asarray(r.bgr, np.float32))
+        np.save(os.path.join(path, "pair%d_info.npy" % p),
+                np.array([r.n_points, r.v_top] + list(r.margin[0]) + list(r.margin[1]), np.float64))
 
 
 def kernel_src_sha():

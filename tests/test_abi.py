@@ -91,38 +91,6 @@ def test_header_is_plain_c():
     assert r.returncode == 0, r.stderr
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/reconstruction"), reason="reference headers only exist in the build container")
-@pytest.mark.parametrize("pcl", [False, True])
-def test_cpp_adapter_compiles_against_the_reference_headers(tmp_path, pcl):
-    """The cv::Mat-facing shim (include/CStereoMatchingMI355.hpp) against the reference's own vendored headers, with and
-    without IS_PCL (SharedInclude.h defines it; the InsertPoint / filter calls are behind it, CStereoMatching.cpp:30,750).
-    The marshalling itself is plain C++ and is RUN by tests/test_gpu_cpp_adapter.py."""
-    if not os.path.isdir("/root/reference"):
-        pytest.skip("the reference checkout exists only in the build container")
-    src = tmp_path / "adapter_check.cpp"
-    src.write_text('#define __declspec(x)\n#define _Longlong long long\n#include "SharedInclude.h"\n'
-                   + ('' if pcl else '#undef IS_PCL\n') +
-                   '#include "CStereoMatching.h"\n#include "CStereoMatchingMI355.hpp"\n'
-                   'bool f(CStereoMatching &sm) { RsmStereoMI355 g(0); return g.MatchPair(sm, 0) && g.LastStatus() == 0; }\n'
-                   # the whole loop as INTEGRATION.md 2 writes it: a member function, so the lambda may call the private Rectify
-                   'void CStereoMatching::MatchAllLayer() {\n'
-                   '    static RsmStereoMI355 gpu(0, 3);\n'
-                   '    RsmCvTraits::rectify() = [](CStereoMatching &s, int CamPair) { s.Rectify(CamPair, s.Q); };\n'
-                   '    std::vector<int> status(m_data->m_CampairNum);\n'
-                   '    if (gpu.MatchAll(*this, m_data->m_CampairNum, status.data()) != m_data->m_CampairNum) printf("rsm: %s\\n", gpu.LastError());\n'
-                   '}\n'
-                   # the several-GPU form (every visible device, three pairs in flight on each) and the loop with the filter on the GPU
-                   'int g(CStereoMatching &sm, int n) {\n'
-                   '    static RsmStereoMI355 gpu(RsmStereoMI355::AllDevices(), 3);\n'
-                   '    RsmCvTraits::filtered_sink() = [](CStereoMatching &, int, const rsm_point16 *, const float *, int64_t, int64_t) {};\n'
-                   '    return gpu.MatchAll(sm, n) + gpu.MatchAllFiltered(sm, n);\n'
-                   '}\n')
-    r = subprocess.run(["g++", "-std=c++11", "-fsyntax-only", "-w", "-I/root/reference/include",
-                        "-I/root/reference/reconstruction", "-I" + os.path.join(ROOT, "include"), str(src)],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-
-
 def test_mock_adapter_program_builds_and_links(tmp_path):
     """tests/cpp/mock_adapter.cpp (the traits-based adapter with mock types) compiles with plain g++ and links against
     the C-ABI library; it is executed on the GPU box."""

@@ -104,7 +104,7 @@ def test_bench_runs_with_two_ranks_on_the_gloo_stand_in(launcher):
     env = dict(os.environ, RSM_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    tail = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--config", "c2s"]
+    tail = [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--config", "c2s", "--full"]
     if launcher == "self":
         cmd = [sys.executable] + tail
     else:
@@ -117,6 +117,33 @@ def test_bench_runs_with_two_ranks_on_the_gloo_stand_in(launcher):
     d = json.loads(lines[-1])
     assert d["n_gpus"] == 2 and d["value"] > 0 and d["scaling"] == "weak" and "roofline" in d
     assert d["config"]["pairs_per_gpu"] == 3  # bench.py's default --inflight
+
+
+def test_bench_plain_run_and_its_dumped_outputs(ctx, tmp_path):
+    """A plain run (no --full) prints the headline line and nothing that takes runs of its own; --dump-outputs writes the
+    last timed step's arrays (float32 / float64, 64 MB at most), and pair 0's equal the same pair matched on its own here."""
+    import bench
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "RSM_BENCH_BACKEND", "RSM_BENCH_SELF_GATHER")}
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--inflight", "2",
+                        "--config", "c2s", "--dump-outputs", str(out)], capture_output=True, text=True, env=env, cwd=ROOT, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["value"] > 0 and d["ms_per_step"] > 0 and d["higher_is_better"] is True
+    assert d["unit"] == "Mdisparities/s" and d["dtype"] == "f64" and d["metric"]
+    assert not {"roofline", "stage_ms_per_step", "value_single_pair", "ncc_kernel", "adapter", "cpu_baseline"} & set(d)
+    names = sorted(os.listdir(out))
+    assert names == sorted("pair%d_%s.npy" % (p, n) for p in (0, 1) for n in ("disparity0", "disparity1", "xyz", "bgr", "info"))
+    assert sum(os.path.getsize(out / n) for n in names) <= 64 * 1000 * 1000
+    assert all(np.load(out / n).dtype in (np.float32, np.float64) for n in names)
+    ctx.match_pair(synth.config_c2_sample(pair=0))
+    mine = tmp_path / "mine"
+    bench.dump_outputs(str(mine), [(0, ctx)], 2)
+    assert np.load(out / "pair0_info.npy")[1] == d["config"]["v_top_per_pair"]
+    for n in sorted(os.listdir(mine)):
+        assert np.array_equal(np.load(out / n), np.load(mine / n), equal_nan=True), n
 
 
 def test_bench_gathers_through_the_librarys_own_rccl_path():

@@ -6,7 +6,7 @@ export OMP_NUM_THREADS=16 OMP_WAIT_POLICY=passive
 export TMPDIR=/tmp
 out=$PWD/gpurun_out/prof_$tag
 rm -rf $out; mkdir -p $out
-rocprofv3 --kernel-trace --stats -d $out -o $tag -- python bench.py --no-cpu-baseline "$@" > $out/bench_stdout.log 2>&1
+rocprofv3 --kernel-trace --stats -d $out -o $tag -- python bench.py --full --no-cpu-baseline "$@" > $out/bench_stdout.log 2>&1
 echo "rocprof rc=$?" >> $out/bench_stdout.log
 f=$(find $out -name "*kernel_stats.csv" | head -1)
 [ -n "$f" ] && head -40 "$f"

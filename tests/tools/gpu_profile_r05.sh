@@ -4,9 +4,9 @@
 export OMP_NUM_THREADS=16 OMP_WAIT_POLICY=passive TMPDIR=/tmp
 root=$PWD
 out=$root/gpurun_out/prof_r05; rm -rf $out; mkdir -p $out
-python -u bench.py > $out/r05_bench.log 2> $out/r05_bench.err; echo "bench rc=$?"; tail -1 $out/r05_bench.log | cut -c1-260
+python -u bench.py --full > $out/r05_bench.log 2> $out/r05_bench.err; echo "bench rc=$?"; tail -1 $out/r05_bench.log | cut -c1-260
 for c in c3 c5 c4; do
-  timeout 600 python -u bench.py --no-cpu-baseline --measure-traffic 0 --config $c --steps 5 --warmup 1 > $out/r05_bench_$c.log 2> $out/r05_bench_$c.err; echo "$c rc=$?"; tail -1 $out/r05_bench_$c.log | cut -c1-200
+  timeout 600 python -u bench.py --full --no-cpu-baseline --measure-traffic 0 --config $c --steps 5 --warmup 1 > $out/r05_bench_$c.log 2> $out/r05_bench_$c.err; echo "$c rc=$?"; tail -1 $out/r05_bench_$c.log | cut -c1-200
 done
 python tests/tools/gpu_ncc_micro.py > $out/r05_ncc_micro.log 2>&1; tail -6 $out/r05_ncc_micro.log
 bash tests/tools/gpu_stats_inflight.sh r05 > $out/r05_stats_inflight.log 2>&1; cp gpurun_out/stats_r05/r05_kernel_stats.csv $out/ 2>/dev/null; cp gpurun_out/stats_r05/bench_under_rocprof.log $out/r05_bench_under_rocprof.log 2>/dev/null; head -12 $out/r05_stats_inflight.log

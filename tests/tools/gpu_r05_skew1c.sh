@@ -3,7 +3,7 @@
 cp reconstruction_amd/librsm_mi355.so /tmp/shipped.so
 for v in reconstruction_amd/variants/v_*.so; do
   cp $v reconstruction_amd/librsm_mi355.so; echo "== $(cat ${v%.so}.txt)"
-  python -u bench.py --no-cpu-baseline --measure-traffic 0 --adapter-pairs 0 --steps 2 --warmup 1 --inflight 1 --opt refine_skew_variant=64 2>&1 | python -c "
+  python -u bench.py --full --no-cpu-baseline --measure-traffic 0 --adapter-pairs 0 --steps 2 --warmup 1 --inflight 1 --opt refine_skew_variant=64 2>&1 | python -c "
 import sys,json
 n=0
 for l in sys.stdin:

@@ -3,7 +3,7 @@
 cp reconstruction_amd/librsm_mi355.so /tmp/keep.so
 for n in "$@"; do
   cp tests/_ab/$n.so reconstruction_amd/librsm_mi355.so
-  python -u bench.py --no-cpu-baseline --adapter-pairs 0 --steps 8 --warmup 2 $BENCH_OPTS 2>/dev/null | python -c "
+  python -u bench.py --full --no-cpu-baseline --adapter-pairs 0 --steps 8 --warmup 2 $BENCH_OPTS 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']
 print('[$n]', 'value', d['value'], 'single', d['ms_single_pair'], 'skew alone', r['alone']['avg_launch_ms'], 'in flight', r['avg_launch_ms'], 'traffic', r['traffic'], json.dumps(r['valu']))"

@@ -7,6 +7,7 @@ echo "pytest rc=$?" >> gpurun_out/pytest.log
 grep -E "passed|failed|rc=" gpurun_out/pytest.log | tail -3
 shift
 if [ -n "$1" ]; then
+  set -- --full "$@"
   timeout 900 python -u bench.py "$@" > gpurun_out/bench.log 2>&1; echo "bench rc=$?" >> gpurun_out/bench.log
   tail -5 gpurun_out/bench.log
 fi

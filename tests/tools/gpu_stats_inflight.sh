@@ -3,7 +3,7 @@
 export TMPDIR=/tmp
 root=$PWD; tag=${1:-r04}; shift; out=$root/gpurun_out/stats_$tag; rm -rf $out; mkdir -p $out
 cd /tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -o s -- python $root/bench.py --no-cpu-baseline --measure-traffic 0 --adapter-pairs 0 "$@" > $out/bench_under_rocprof.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats -o s -- python $root/bench.py --full --no-cpu-baseline --measure-traffic 0 --adapter-pairs 0 "$@" > $out/bench_under_rocprof.log 2>&1
 cd $root
 f=$(find $out/stats -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" $out/${tag}_kernel_stats.csv
 rm -rf $out/stats

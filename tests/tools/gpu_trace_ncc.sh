@@ -3,7 +3,7 @@
 export TMPDIR=/tmp
 root=$PWD; out=$root/gpurun_out/trace_ncc; rm -rf $out; mkdir -p $out
 cd /tmp
-rocprofv3 --kernel-trace -d $out -o tr -- python $root/bench.py --no-cpu-baseline --steps 1 --warmup 0 --inflight 1 "$@" > $out/stdout.log 2>&1
+rocprofv3 --kernel-trace -d $out -o tr -- python $root/bench.py --full --no-cpu-baseline --steps 1 --warmup 0 --inflight 1 "$@" > $out/stdout.log 2>&1
 cd $root
 python - <<PY
 import sqlite3, glob
