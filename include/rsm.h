@@ -233,9 +233,14 @@ int rsm_gather_plan(int rank, int world, int root, int n_local, const int *pair_
  *   "no_exact" = 1         (timing A/B only) skip the reference-order re-evaluation of near-tie pixels
  *   "refine_skew_from" / "refine_skew_T" / "refine_skew_min_px" / "refine_skew_waves" / "refine_skew_rows"   time-skewed refine
  *                          sweeps (k_refine_skew): T (2..4, default 4) sweeps per launch from that sweep of a level on (default
- *                          22; 0 = never) at levels with at least min_px margin pixels per direction (default 1 M: the two
+ *                          4; 0 = never) at levels with at least min_px margin pixels per direction (default 1 M: the two
  *                          largest levels of a 12 MP pair; a level narrower than 80 columns never), aiming at `waves` workgroups
  *                          (default 2560: two rounds of the 1280 a chip holds) or `rows` rows per chunk
+ *   "refine_rekey_until"   a time-skewed launch that starts before this sweep (default 22; 0 = never, the schedule then wants
+ *                          refine_skew_from = 22) is preceded by a re-key pass (k_refine_rekey): each live pixel's data-term cache
+ *                          holds its current key and the neighbour key on the side the state is nearest to, so the early launches
+ *                          miss at the settled rate.  "refine_rekey_side" = 1 installs the other neighbour instead (tests: a wrong
+ *                          prediction costs misses, never bits)
  *   "refine_skew_uw"       columns a strip of that kernel owns: 0 (default) = 66 - 2T, all that its last sweep can compute from 64
  *                          lanes; an even number below that (e.g. 56: every strip starts on a 128-byte line of the cache ways) for A/B
  *   "refine_skew_waves_alone"  the workgroups a time-skewed launch aims at while no other context of the device is inside

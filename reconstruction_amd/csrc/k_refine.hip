@@ -19,7 +19,8 @@
 // written as separate 16-bit halves.
 //
 // This file: the first sweep (k_refine_first), the single sweep (k_refine_sweep, used while the cache fills and on the small
-// levels), the scatter of a time-skewed launch's update list (k_refine_apply), and the test entries.  The settled sweeps of
+// levels), the re-key pass in front of the early time-skewed launches (k_refine_rekey), the scatter of a time-skewed launch's
+// update list (k_refine_apply), and the test entries.  The settled sweeps of
 // the large levels run T per launch in k_refine_skew.hip.
 #include "refine_common.h"
 
@@ -279,6 +280,95 @@ __global__ __launch_bounds__(256) void k_refine_sweep(StageArgs a) {
         out[pix] = (mode[i] == 0) ? col[i + 1] /* .cpp:655 */
                                   : refine_update(mode[i], col[i + 1], dE[i], dW[i], col[i], col[i + 2], pwp[i], delta[i], a.ws, s_exp);
     }
+}
+
+// Re-key (before an early time-skewed launch, after k_refine_apply): for every live interior pixel of the current state f64_a
+// the way of its key k = iMatch - x = int(d - 1.5) holds k, and the other way holds the neighbour key on the side of k's interval
+// the state is nearest to (a.flag3 = 1: the other side -- a deliberately wrong prediction, tests only).  k + 1 and k - 1 share a
+// way, so only one of them can be resident; what the early sweeps need next is the near one (tests/tools/simulate_rekey.py:
+// the rare-row fraction of a T = 4 launch from sweep 4 drops from 0.80 to 0.01).  Nothing but exact data terms is written, so
+// the sweeps' results do not depend on it.  The entries to compute are compacted per wave through an LDS list over RK_PPT rows
+// and served a lane each while the list is long, four lanes each for the last 16 or fewer (as k_refine_sweep serves misses):
+// a few scattered entries do not run the data-term routine in every wave.
+#define RK_PPT 8                // vertically adjacent pixels per thread
+#define RKW_CAP (2 * 64 * RK_PPT) // both ways of every pixel of a wave
+__global__ __launch_bounds__(256) void k_refine_rekey(StageArgs a) {
+    __shared__ uint32_t s_list[4][RKW_CAP]; // slot of the pixel (lane * RK_PPT + i) | key << 16
+    const DirArgs &d = a.d[blockIdx.z];
+    const int W = a.W, H = a.H;
+    const int x = d.own.XL + 1 + blockIdx.x * 256 + (int)threadIdx.x;
+    const int y0 = d.own.YL + 1 + blockIdx.y * RK_PPT;
+    const int ylast = d.own.YR - 1;
+    if (y0 > ylast) return; // uniform
+    const bool colok = x <= d.own.XR - 1;
+    const int xs = colok ? x : d.own.XL + 1;
+    const bool wrong = a.flag3 == 1;
+    double dc[RK_PPT];
+    uint32_t kk[RK_PPT];
+#pragma unroll
+    for (int i = 0; i < RK_PPT; i++) {
+        const size_t pix = (size_t)min(y0 + i, ylast) * W + xs;
+        dc[i] = d.f64_a[pix];
+        kk[i] = d.rf_key[pix];
+    }
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int xw0 = d.own.XL + 1 + blockIdx.x * 256 + wid * 64; // column of this wave's lane 0
+    const unsigned long long below = (1ull << lane) - 1ull;
+    int n = 0; // entries of this wave (uniform)
+#pragma unroll
+    for (int i = 0; i < RK_PPT; i++) {
+        const bool lv = colok && (y0 + i <= ylast) && dc[i] != (double)NOMATCH; // .cpp:613
+        const double v = dc[i] - 1.5;
+        const int rel = (int)v; // .cpp:625 (iMatch - x)
+        const double centre = rel > 0 ? rel + 0.5 : (rel < 0 ? rel - 0.5 : 0.0); // (int() truncates: key 0's interval is (-1, 1))
+        const int nb = ((v > centre) != wrong) ? rel + 1 : rel - 1;
+        const bool n0 = lv && (int)(int16_t)(kk[i] >> ((rel & 1) << 4)) != rel;
+        const bool n1 = lv && (int)(int16_t)(kk[i] >> ((nb & 1) << 4)) != nb;
+        const uint32_t slot = (uint32_t)(lane * RK_PPT + i);
+        const unsigned long long m0 = __ballot(n0);
+        if (n0) s_list[wid][n + __popcll(m0 & below)] = slot | ((uint32_t)(rel & 0xffff) << 16);
+        n += __popcll(m0);
+        const unsigned long long m1 = __ballot(n1);
+        if (n1) s_list[wid][n + __popcll(m1 & below)] = slot | ((uint32_t)(nb & 0xffff) << 16);
+        n += __popcll(m1);
+    }
+    if (!n) return; // wave-uniform; no workgroup barrier follows
+    __builtin_amdgcn_wave_barrier();
+    for (int done = 0; done < n;) { // uniform
+        if (n - done > 16) { // a lane per entry
+            const int e = done + lane;
+            if (e < n) {
+                const uint32_t en = s_list[wid][e];
+                const int slot = en & 0xffff, r = (int)(int16_t)(en >> 16);
+                const int ex = xw0 + slot / RK_PPT, ey = y0 + slot % RK_PPT;
+                double p, q;
+                refine_data_term_packed(d.img4_own, d.img4_oth, W, H, ex, ey, r + ex, p, q);
+                rf_store(d, a.rf_stride, (size_t)ey * W + ex, r, p, q);
+            }
+            done += 64;
+        } else { // four lanes per entry
+            const int e = done + (lane >> 2);
+            const bool ok = e < n;
+            const uint32_t en = s_list[wid][ok ? e : done];
+            const int slot = en & 0xffff, r = (int)(int16_t)(en >> 16);
+            const int ex = xw0 + slot / RK_PPT, ey = y0 + slot % RK_PPT;
+            double p, q;
+            refine_data_term_quad(d.img4_own, d.img4_oth, W, H, ex, ey, r + ex, lane & 3, p, q);
+            if (ok && (lane & 3) == 0) rf_store(d, a.rf_stride, (size_t)ey * W + ex, r, p, q);
+            done += 16;
+        }
+    }
+}
+
+// the re-key pass over the interior of the current state a.d[].f64_a (a.flag3 = 1: the mispredicting side, tests)
+void launch_refine_rekey(const StageArgs &a, hipStream_t st) {
+    int rows = 0, cols = 0;
+    for (int v = 0; v < a.ndir; v++) {
+        rows = max(rows, a.d[v].own.YR - a.d[v].own.YL - 1);
+        cols = max(cols, a.d[v].own.XR - a.d[v].own.XL - 1);
+    }
+    if (rows <= 0 || cols <= 0) return;
+    hipLaunchKernelGGL(k_refine_rekey, dim3((cols + 255) / 256, (rows + RK_PPT - 1) / RK_PPT, a.ndir), dim3(256), 0, st, a);
 }
 
 // scatters the update list of the k_refine_skew launch a.flag3 into the cache and clears the other counter set

@@ -145,7 +145,11 @@ struct rsm_ctx {
     int opt_heavy_min_px = 400000; // ... from this many margin pixels on (smaller levels are launch-bound themselves)
     int opt_heavy_lanes = 2;     // 2: the single-sweep part and the time-skewed part of a level's refine take turns separately (lanes 0 / 1)
     int opt_heavy_exclusive = 1; // refine sections of contexts sharing a GPU take turns (heavy_begin): 1 = the top level's, 2 = every large level's, 0 = none
-    int opt_refine_skew_from = 22; // first sweep of a level that may run in the time-skewed kernel (k_refine_skew; 0: never): before that too many pixels still miss the data-term cache for its lane-serial miss service
+    int opt_refine_skew_from = 4;  // first sweep of a level that may run in the time-skewed kernel (k_refine_skew; 0: never): 22 without the re-key below -- before
+                                   // that too many pixels still miss the data-term cache for its lane-serial miss service
+    int opt_refine_rekey_until = 22; // a time-skewed launch that starts before this sweep is preceded by k_refine_rekey (both cache ways set for the current
+                                     // state: the key and its nearer neighbour), which keeps the early launches' misses at the settled rate (0: never)
+    int opt_refine_rekey_side = 0;   // 1: k_refine_rekey installs the FARTHER neighbour (a wrong prediction: tests)
     int opt_refine_prefill = 1;    // k_refine_first also fills the second cache way with the neighbour iMatch its update points to
     int opt_refine_skew_T = 4;     // sweeps per time-skewed launch (2..4)
     int opt_refine_skew_min_px = 1000000; // ... at levels with at least this many margin pixels per direction (smaller levels: the 4T-step pipeline fill of a chunk eats the gain)
@@ -416,6 +420,8 @@ static int ensure_workspace(rsm_ctx *c, const rsm_pair_in *in) {
     DALLOC(c, c->rf_list, std::max(2 * px + 64, 2 * SETB_SCRATCH(in->width)));
     DALLOC(c, c->tie_list, 2 * px + 64);
     DALLOC(c, c->wrow, NCC_WROW_INTS((size_t)in->height)); // per (direction, row) counters and the row kernels' row lists (rsm_dev.h)
+    // (a shard that fills drops further records: the entries stay in the launch's LDS copy, and a later sweep that needs one misses
+    // again -- costs time, never bits.  With the re-key in front of the early launches they list about as few as the settled ones.)
     c->upd_cap = (int)std::min<size_t>(65536, std::max<size_t>(1024, px / 8));
     DALLOC(c, c->upd_list, (size_t)RF_UPD_SHARDS * c->upd_cap);
     DALLOC(c, c->upd_list2, (size_t)RF_UPD_SHARDS * c->upd_cap);
@@ -531,6 +537,8 @@ extern "C" int rsm_set_option(rsm_ctx *c, const char *name, long long value) {
     else if (!strcmp(name, "no_exact")) c->opt_no_exact = value != 0;
     else if (!strcmp(name, "refine_skew_from")) c->opt_refine_skew_from = (int)std::max(0LL, std::min(value, 100000LL));
     else if (!strcmp(name, "refine_prefill")) c->opt_refine_prefill = value != 0;
+    else if (!strcmp(name, "refine_rekey_until")) c->opt_refine_rekey_until = (int)std::max(0LL, std::min(value, 100000LL));
+    else if (!strcmp(name, "refine_rekey_side")) c->opt_refine_rekey_side = value != 0;
     else if (!strcmp(name, "refine_split")) c->opt_refine_split = (int)std::max(0LL, std::min(value, 2LL)); // 2: also with pairs in flight (A/B)
     else if (!strcmp(name, "refine_skew_T")) c->opt_refine_skew_T = (int)std::max(2LL, std::min(value, 4LL));
     else if (!strcmp(name, "refine_skew_min_px")) c->opt_refine_skew_min_px = (int)std::max(0LL, std::min(value, 2000000000LL));
@@ -693,15 +701,31 @@ static int refine_sweeps(rsm_ctx *c, StageArgs &a, double *const bufA[2], double
             c->prof_launches[stg] += 1;
             c->prof_bytes[stg] += (skewT ? (double)skewT : 1.0) * level_bytes();
         }
+        // an early time-skewed launch: k_refine_rekey first sets both cache ways for the state it starts from (the previous
+        // launch's cache updates are in: k_refine_apply runs behind every skewed launch on the same stream)
+        const bool rekey = skewT && t < c->opt_refine_rekey_until;
         if (skewT && split_now) { // the two directions as two launch chains: one's tail runs beside the other's head
             StageArgs a0 = a, a1 = a;
             a0.ndir = a1.ndir = 1;
             a1.d[0] = a.d[1];
             a1.upd_list = c->upd_list2;
             a1.upd_cnt = c->upd_cnt2;
+            if (rekey) {
+                StageArgs r0 = a0, r1 = a1;
+                r0.flag3 = r1.flag3 = c->opt_refine_rekey_side;
+                launch_refine_rekey(r0, st);
+                launch_refine_rekey(r1, c->stream2);
+            }
             launch_refine_skew(a0, skewT, st, e0, e1); // (e0 / e1: only under refine_split = 2, an A/B mode)
             launch_refine_skew(a1, skewT, c->stream2, nullptr, nullptr);
-        } else if (skewT) launch_refine_skew(a, skewT, st, e0, e1);
+        } else if (skewT) {
+            if (rekey) {
+                StageArgs r = a;
+                r.flag3 = c->opt_refine_rekey_side;
+                launch_refine_rekey(r, st);
+            }
+            launch_refine_skew(a, skewT, st, e0, e1);
+        }
         else launch_refine_sweep(a, st, e0, e1);
         launches += skewT ? skewT : 1;
         curB = !curB;

@@ -121,6 +121,7 @@ void launch_refine_init(const StageArgs &a, hipStream_t st);   // d16_in -> f64_
 void launch_refine_sweep(const StageArgs &a, hipStream_t st, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 // T (2..4) sweeps f64_a -> f64_b in one time-skewed launch (a.flag3 = launch index, a.skew_rows, a.skew_uw) + the cache-update launch
 void launch_refine_apply(const StageArgs &a, hipStream_t st); // k_refine.hip
+void launch_refine_rekey(const StageArgs &a, hipStream_t st); // k_refine.hip: both cache ways for the state a.d[].f64_a (k_refine_rekey)
 void launch_refine_skew(const StageArgs &a, int T, hipStream_t st, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr); // k_refine_skew.hip
 int refine_skew_strips(const Mg &m, int T, int uw); // strips of 64 lanes a direction's interior takes (k_refine_skew.hip)
 bool refine_skew_fits(const StageArgs &a);          // the kernel's flat over-reads stay inside the level
