@@ -428,6 +428,26 @@ int rsm_filter_last_normals_info(rsm_ctx *ctx, int64_t info[2]);
 int rsm_filter_last_cloud_host(rsm_ctx *ctx, const rsm_filter_params *params, rsm_point16 *h_points, float *h_normals,
                                int64_t max_points, int64_t *n_kept, double *stats);
 
+/* ---- moving-least-squares smoothing (CCloudOptimization::run, CCloudOptimization.cpp:348-389) ----------- */
+typedef struct rsm_mls_params {
+    double search_radius;   /* m_mls_radius (CReconstruction.cpp:18: 2.5); the weight's Gaussian uses radius^2 */
+    int polynomial_order;   /* 1 as .cpp:360; 2 = PCL's default; 0 = no polynomial fit (plane projection) */
+} rsm_mls_params;
+/* pcl::MovingLeastSquares (computeMLSPointNormal, upsampling NONE, normals computed) restated from PCL 1.7.2 (csrc/k_mls.hip):
+ * every finite point with at least 3 finite points (itself included) within the radius is projected onto the local plane,
+ * moved by the polynomial fit's height and given the fit's normal -- not renormalised, as PCL 1.7.2 leaves it -- then the normal
+ * is negated when its float dot product with the point's reference normal is < 0 (.cpp:378-385; a NaN reference never flips).
+ * RSM_E_INVALID: radius not finite or not > 0, order outside 0..2, n < 0 or above INT32_MAX, a NULL output pointer.
+ * host buffers: xyz n*3, ref_normals n*4 (nx,ny,nz,curvature as rsm_filter_cloud returns them) or NULL = no flip;
+ * out_xyz 3*n, out_normals 4*n (nx,ny,nz,curvature), src_index n; *n_out = points emitted, in input order */
+int rsm_mls_cloud(rsm_ctx *ctx, const float *xyz, int64_t n, const float *ref_normals, const rsm_mls_params *p,
+                  float *out_xyz, float *out_normals, int32_t *src_index, int64_t *n_out);
+/* the same on DEVICE buffers of rsm_point16 records -- what rsm_filter_last_cloud leaves for each pair, concatenated,
+ * or what rsm_gather_clouds delivers at the root (no normals there: pass NULL) */
+int rsm_mls_cloud_device(rsm_ctx *ctx, const rsm_point16 *d_points, int64_t n, const float *d_ref_normals,
+                         const rsm_mls_params *p, float *d_out_xyz, float *d_out_normals, int32_t *d_src_index,
+                         int64_t *n_out);
+
 /* ---- kernel microbenchmark (MDE/s: pixel x candidate NCC evaluations) -------------------- */
 /* Runs the NCC interval-argmax kernel `iters` times on a resident level-sized problem with
  * `cands` candidates per pixel and returns average milliseconds per launch. */

@@ -1,10 +1,13 @@
-"""python -m reconstruction_amd <config.yml> [--device N] [--out cloud.ply]
+"""python -m reconstruction_amd <config.yml> [--device N] [--out cloud.ply] [--filter] [--mls [--mls-out bigcloud.ply]]
 
 The command-line shape of the reference's main() (reconstruction/main.cpp:5-23) for the part this package covers:
 CReconstrction::Init (configuration + calibration, CReconstruction.cpp:5-19) -> CStereoMatching::MatchAllLayer
 (Rectify, pyramid, matching, refinement, cloud; on the MI355X) -> per pair CCloudOptimization::filter's outlier removal
-and normals (--filter; CCloudOptimization.cpp:82-121, on the GPU) -> the merged point cloud as a PLY file.
-CCloudOptimization::run (MLS, Poisson meshing, texture; main.cpp:19) is outside this package: feed the PLY to it.
+and normals (--filter; CCloudOptimization.cpp:82-121, on the GPU) -> the merged point cloud as a PLY file -> with --mls
+(implies --filter) the moving-least-squares block of CCloudOptimization::run (CCloudOptimization.cpp:348-389, on the GPU):
+the smoothed, oriented cloud as bigcloud.ply (pcl::PointNormal, savePLYFileBinary), what the mesher reads.
+The rest of CCloudOptimization::run (Poisson meshing, texture: external executables; main.cpp:19) is outside this
+package: feed bigcloud.ply to it.
 Needs an MI355X; there is no CPU path.
 """
 from __future__ import annotations
@@ -41,8 +44,14 @@ def main(argv=None) -> int:
     ap.add_argument("--filter", action="store_true",
                     help="per-pair StatisticalOutlierRemoval (k=100, 1 sigma) as CCloudOptimization::filter (CReconstruction.cpp:18)")
     ap.add_argument("--mls-radius", type=float, default=2.5,
-                    help="search radius of the per-pair normals, in scene units (m_mls_radius; CReconstruction.cpp:18 passes 2.5)")
+                    help="search radius of the per-pair normals and of the MLS, in scene units (m_mls_radius; CReconstruction.cpp:18 passes 2.5)")
+    ap.add_argument("--mls", action="store_true",
+                    help="after the filter (implied), CCloudOptimization::run's MLS over the merged cloud (order 1, normals flipped to the "
+                         "filter's; CCloudOptimization.cpp:348-389) -> bigcloud.ply")
+    ap.add_argument("--mls-out", default=None, help="path of the MLS cloud (default: bigcloud.ply next to the --out PLY)")
     args = ap.parse_args(argv)
+    if args.mls:
+        args.filter = True
 
     from .config import load_config
     try:
@@ -80,6 +89,15 @@ def main(argv=None) -> int:
     out = args.out or (name if name.lower().endswith(".ply") else name + ".ply")
     write_ply(out, xyz, bgr, normals if args.filter else None)
     print("%d points -> %s" % (len(xyz), out))
+    if args.mls:
+        import os
+        from . import write_ply_pointnormal
+        t1 = time.perf_counter()
+        mxyz, mnrm, _ = sink.run()
+        big = args.mls_out or os.path.join(os.path.dirname(os.path.abspath(out)), "bigcloud.ply")
+        write_ply_pointnormal(big, mxyz, mnrm)                     # savePLYFileBinary("tmp\\bigcloud.ply"), .cpp:389
+        print("MLS time: %.3f s" % (time.perf_counter() - t1))
+        print("%d points -> %s" % (len(mxyz), big))
     return 0
 
 

@@ -57,6 +57,11 @@ class FilterParams(C.Structure):
     _fields_ = [("sor_mean_k", C.c_int), ("sor_std_mul", C.c_double), ("normal_radius", C.c_double), ("cam_center", C.c_float * 3)]
 
 
+class MlsParams(C.Structure):
+    """rsm_mls_params (include/rsm.h)."""
+    _fields_ = [("search_radius", C.c_double), ("polynomial_order", C.c_int)]
+
+
 class RectifyIn(C.Structure):
     _fields_ = [("K", (C.c_double * 9) * 2), ("E", (C.c_double * 12) * 2),
                 ("origin_width", C.c_int), ("origin_height", C.c_int), ("lowest_width", C.c_int),
@@ -83,6 +88,7 @@ EXPORTS = [
     "rsm_pack_cloud16", "rsm_comm_unique_id", "rsm_comm_create", "rsm_comm_destroy", "rsm_comm_last_error",
     "rsm_gather_clouds", "rsm_gather_counts", "rsm_gather_meta_fill", "rsm_gather_plan", "rsm_comm_create_transport",
     "rsm_filter_cloud", "rsm_filter_last_cloud", "rsm_host_alloc", "rsm_host_free", "rsm_host_register", "rsm_host_unregister",
+    "rsm_mls_cloud", "rsm_mls_cloud_device",
 ]
 
 _lib = None
@@ -116,5 +122,9 @@ def load():
     lib.rsm_comm_last_error.argtypes = [C.c_void_p]
     lib.rsm_comm_destroy.restype = None
     lib.rsm_comm_destroy.argtypes = [C.c_void_p]
+    lib.rsm_mls_cloud.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(MlsParams), C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.POINTER(C.c_int64)]
+    lib.rsm_mls_cloud_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(MlsParams), C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
     _lib = lib
     return lib

@@ -19,7 +19,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from ._lib import Boundary, FilterParams, NOMATCH, PairIn, PairOut, RectifyIn, RectifyOut, RsmError  # noqa: F401
+from ._lib import Boundary, FilterParams, MlsParams, NOMATCH, PairIn, PairOut, RectifyIn, RectifyOut, RsmError  # noqa: F401
 
 
 class _Pinned:
@@ -99,6 +99,22 @@ def write_ply(path, xyz, bgr, normals=None):
     st = _lib.load().rsm_write_ply(str(path).encode(), _p(xyz), _p(bgr), C.c_int64(len(xyz)))
     if st != 0:
         raise RsmError(st, "rsm_write_ply(%s)" % path)
+
+
+def write_ply_pointnormal(path, xyz, normals):
+    """tmp\\bigcloud.ply of CCloudOptimization::run (CCloudOptimization.cpp:389): pcl::io::savePLYFileBinary of a
+    pcl::PointCloud<pcl::PointNormal> -- binary little-endian, float x y z normal_x normal_y normal_z curvature per vertex.
+    normals: [n,4] (nx, ny, nz, curvature) as mls_cloud returns them.  Host-only."""
+    xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+    nrm = np.ascontiguousarray(normals, np.float32).reshape(-1, 4)
+    assert len(xyz) == len(nrm)
+    rec = np.empty((len(xyz), 7), "<f4")
+    rec[:, :3], rec[:, 3:] = xyz, nrm
+    with open(path, "wb") as f:
+        f.write(("ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n"
+                 "property float normal_x\nproperty float normal_y\nproperty float normal_z\nproperty float curvature\nend_header\n"
+                 % len(xyz)).encode())
+        f.write(rec.tobytes())
 
 
 @dataclass
@@ -393,6 +409,45 @@ class Context:
         self._chk(self._lib.rsm_filter_last_cloud(self._h, C.byref(prm), C.c_void_p(points_ptr or None), C.c_void_p(normals_ptr or None),
                                                   C.c_int64(max_points), C.byref(m), st))
         return int(m.value), dict(mean=st[0], stddev=st[1], threshold=st[2], exhaustive=int(st[3]))
+
+    # ---- moving-least-squares smoothing (CCloudOptimization::run, CloudOptimization/CCloudOptimization.cpp:348-389) ----
+    @staticmethod
+    def _mls_params(radius, order):
+        prm = MlsParams()
+        prm.search_radius, prm.polynomial_order = float(radius), int(order)
+        return prm
+
+    def mls_cloud(self, xyz, radius=2.5, order=1, ref_normals=None):
+        """pcl::MovingLeastSquares (normals on, polynomial `order`, no upsampling) on a host cloud (n x 3, float32); with
+        ref_normals ([n,4] or [n,3]: the filter's normals) each output normal is negated where it disagrees with its
+        input point's (.cpp:378-385).  Returns (xyz float32 [m,3], normals float32 [m,4] = nx, ny, nz, curvature,
+        src_index int32 [m]) in input order."""
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        n = len(xyz)
+        ref = None
+        if ref_normals is not None:
+            r = np.asarray(ref_normals, np.float32).reshape(n, -1)
+            ref = np.zeros((n, 4), np.float32)
+            ref[:, :min(4, r.shape[1])] = r[:, :4]
+        oxyz = np.zeros((max(n, 1), 3), np.float32)
+        onrm = np.zeros((max(n, 1), 4), np.float32)
+        oidx = np.zeros(max(n, 1), np.int32)
+        m = C.c_int64()
+        prm = self._mls_params(radius, order)
+        self._chk(self._lib.rsm_mls_cloud(self._h, _p(xyz), C.c_int64(n), None if ref is None else _p(ref), C.byref(prm), _p(oxyz),
+                                          _p(onrm), _p(oidx), C.byref(m)))
+        k = int(m.value)
+        return oxyz[:k].copy(), onrm[:k].copy(), oidx[:k].copy()
+
+    def mls_cloud_device(self, points_ptr, n, ref_normals_ptr, out_xyz_ptr, out_normals_ptr, src_index_ptr, radius=2.5, order=1):
+        """rsm_mls_cloud_device on device buffers (addresses): n rsm_point16 records in, n float4 reference normals (or 0 / None:
+        no flip); outputs of capacity n.  Returns the number of points emitted."""
+        m = C.c_int64()
+        prm = self._mls_params(radius, order)
+        self._chk(self._lib.rsm_mls_cloud_device(self._h, C.c_void_p(points_ptr or None), C.c_int64(n), C.c_void_p(ref_normals_ptr or None),
+                                                 C.byref(prm), C.c_void_p(out_xyz_ptr or None), C.c_void_p(out_normals_ptr or None),
+                                                 C.c_void_p(src_index_ptr or None), C.byref(m)))
+        return int(m.value)
 
     @property
     def n_points(self):
@@ -789,8 +844,9 @@ class CloudOptimization:
     """The part of CCloudOptimization (CloudOptimization/CCloudOptimization.cpp) that sits on the stereo path:
     Init (:40-57: only the per-pair filter's parameters are used), InsertPoint (:59-62), filter(idx) (:64-147: the
     StatisticalOutlierRemoval + NormalEstimation + normal flip of :82-121 on the GPU; the mesh / texture tooling
-    after :123 is Windows executables and out of scope).  `cloud_normals` accumulates what the reference's global
-    `*cloud_normals += *cloud_normal` (:123) does: per pair (xyz float32 [m,3], normals float32 [m,4])."""
+    after :123 is Windows executables and out of scope), run() (:348-389: MLS over the merged cloud + the normal flip
+    on the GPU; meshing and texturing after :389 are external executables).  `cloud_normals` accumulates what the
+    reference's global `*cloud_normals += *cloud_normal` (:123) does: per pair (xyz float32 [m,3], normals float32 [m,4])."""
 
     def __init__(self, ctx: Context | None = None, device: int = 0):
         self._ctx = ctx or Context(device)
@@ -802,6 +858,7 @@ class CloudOptimization:
 
     def Init(self, sor_meank, sor_stdThres, outrem_neighbor, outrem_radius, mls_radius, ImageData, isdelete_=False):
         self.m_sor_meank, self.m_sor_stdThres, self.m_mls_radius = sor_meank, sor_stdThres, mls_radius
+        self.isdelete = bool(isdelete_)
         self.m_ImageData = ImageData
         self.CamCenter = [np.asarray(c[0].CamCenter if c[0].CamCenter is not None else np.zeros(3), np.float32).ravel()
                           for c in ImageData.cam]
@@ -822,3 +879,20 @@ class CloudOptimization:
         self.stats.append(st)
         self._pts = []   # cloud_in->clear(), :145
         self._bgr = None
+
+    def run(self):
+        """The MLS block of CCloudOptimization::run (:348-389) with isdelete = false (CReconstruction.cpp:18): the pairs'
+        filtered clouds concatenated in pair order (copyPointCloud, :353), MovingLeastSquares with m_mls_radius, polynomial
+        order 1 and normals (:355-364), each normal negated where it disagrees with its input point's filter normal
+        (:378-385).  Stores and returns cloud_ms_normals = (xyz float32 [m,3], normals float32 [m,4], src_index int32 [m]);
+        write_ply_pointnormal writes it as savePLYFileBinary does (:389)."""
+        if getattr(self, "isdelete", False):
+            raise ValueError("CloudOptimization.run: isdelete = true selects the multi-view duplicate deletion (CCloudOptimization.cpp:152-346), "
+                             "a branch the reference never takes (CReconstruction.cpp:18 passes false); it is not implemented")
+        if self.cloud_normals:
+            xyz = np.concatenate([c[0] for c in self.cloud_normals]).astype(np.float32)
+            ref = np.concatenate([c[1] for c in self.cloud_normals]).astype(np.float32)
+        else:
+            xyz, ref = np.zeros((0, 3), np.float32), np.zeros((0, 4), np.float32)
+        self.cloud_ms_normals = self._ctx.mls_cloud(xyz, self.m_mls_radius, 1, ref)
+        return self.cloud_ms_normals

@@ -21,6 +21,7 @@
 //   radius search: cell edge = radius, the 27 cells cover the ball.
 #include "../../include/rsm.h"
 #include "rsm_dev.h"
+#include "cloud_grid.h"
 
 #include <cstring>
 #include <string.h>
@@ -40,20 +41,7 @@
 static inline size_t filter_max_cells(int64_t n) {
     return (size_t)std::min<int64_t>(FILTER_MAX_CELLS, std::max<int64_t>(1 << 16, 8 * n));
 }
-// Grid in KEY order: axis "x" is the fastest digit of the cell key, and it is the WORLD axis with the most cells (p0) --
-// a depth map is a sheet in a deep box, so the rows of cells along its depth hold a handful of points each and the
-// per-row table + short search inside the row (table kind 2) stays cheap when the cells are too many for a table.
-struct FGrid {
-    float ox, oy, oz, inv_h;
-    int nx, ny, nz;
-    int p0, p1, p2; // world axis (0 = x, 1 = y, 2 = z) of key axis x, y, z
-};
-__device__ __forceinline__ float pick_axis(int a, float x, float y, float z) { return a == 0 ? x : (a == 1 ? y : z); }
 
-__device__ __forceinline__ float fdist2(float ax, float ay, float az, float bx, float by, float bz) {
-    const float dx = ax - bx, dy = ay - by, dz = az - bz;
-    return (dx * dx + dy * dy) + dz * dz;
-}
 // sqrtf, correctly rounded, for the k-nearest sums (PCL adds sqrt of the float32 squared distances): the compiler's own sequence --
 // v_sqrt_f32 (1 ulp), the two neighbouring floats, an fma residual each, two selects -- WITHOUT its input scaling for
 // denormals and its zero / infinity test (8 of 17 instructions): the same bits for every x in [2^-96, FLT_MAX] and for 0
@@ -85,16 +73,6 @@ void launch_sqrt_check(unsigned int first, long long n, unsigned long long *mism
     if (n > 0) hipLaunchKernelGGL(k_sqrt_check, dim3(8192), dim3(256), 0, st, first, n, mismatches);
 }
 
-__device__ __forceinline__ int cell_of(float v, float o, float inv_h, int n) {
-    const int c = (int)floorf((v - o) * inv_h);
-    return min(max(c, 0), n - 1);
-}
-// cell of a world point, in key order
-__device__ __forceinline__ void grid_cell(const FGrid &g, float x, float y, float z, int &ix, int &iy, int &iz) {
-    ix = cell_of(pick_axis(g.p0, x, y, z), g.ox, g.inv_h, g.nx);
-    iy = cell_of(pick_axis(g.p1, x, y, z), g.oy, g.inv_h, g.ny);
-    iz = cell_of(pick_axis(g.p2, x, y, z), g.oz, g.inv_h, g.nz);
-}
 
 __global__ void k_cell_keys(const float *__restrict__ xyz, int64_t n, FGrid g, unsigned long long *__restrict__ keys,
                             unsigned int *__restrict__ vals) {
@@ -119,15 +97,6 @@ __global__ void k_gather_sorted(const float *__restrict__ xyz, const unsigned in
     sxyz[j] = make_float4(xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2], __uint_as_float(i));
 }
 
-__device__ __forceinline__ int lower_bound_key(const unsigned long long *__restrict__ keys, int n, unsigned long long k) {
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (keys[mid] < k) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
 
 // cell table: (first, one-past-last) sorted index of every cell's points; (0, 0) for an empty cell
 // div = 1: per cell; div = nx: per (y, z) row of cells (a deep or thick cloud has too many cells for a table of them)
@@ -147,25 +116,6 @@ __device__ __forceinline__ int lower_bound_key_in(const unsigned long long *__re
     return lo;
 }
 
-// the 9 contiguous ranges of the sorted array that hold the 27 cells around p (binary search on the keys; used by the
-// normals and by the k-nearest search when the grid has too many cells for a table)
-__device__ __forceinline__ void ranges9(const unsigned long long *__restrict__ keys, int n, const FGrid &g, float px, float py,
-                                        float pz, int (&rs)[9], int (&re)[9]) {
-    int ix, iy, iz;
-    grid_cell(g, px, py, pz, ix, iy, iz);
-    const int x0 = max(ix - 1, 0), x1 = min(ix + 1, g.nx - 1);
-#pragma unroll
-    for (int t = 0; t < 9; t++) {
-        const int yy = iy + t % 3 - 1, zz = iz + t / 3 - 1;
-        if (yy < 0 || yy >= g.ny || zz < 0 || zz >= g.nz) {
-            rs[t] = re[t] = 0;
-            continue;
-        }
-        const unsigned long long base = ((unsigned long long)zz * g.ny + yy) * g.nx;
-        rs[t] = lower_bound_key(keys, n, base + x0);
-        re[t] = lower_bound_key(keys, n, base + x1 + 1);
-    }
-}
 
 #define KNN_C 32    // registers per lane for the candidates within h
 #define KNN_CAP (64 * KNN_C)
@@ -1210,67 +1160,6 @@ __global__ void k_compact_kept(const float *__restrict__ xyz, const unsigned int
     kept_index[o] = (int32_t)i;
 }
 
-// ---- eigen33 / computeRoots of PCL's common/impl/eigen.hpp (smallest eigenvalue and its vector), in double
-__device__ __forceinline__ void pcl_roots2(double b, double c, double *r) {
-    r[0] = 0.0;
-    double d = b * b - 4.0 * c;
-    if (d < 0.0) d = 0.0;
-    const double sd = sqrt(d);
-    r[2] = 0.5 * (b + sd);
-    r[1] = 0.5 * (b - sd);
-}
-__device__ void pcl_plane_from_cov(const double *cov, double *nrm, double *curvature) {
-    double scale = 0.0;
-    for (int i = 0; i < 9; i++) scale = fmax(scale, fabs(cov[i]));
-    if (scale <= 2.2250738585072014e-308) scale = 1.0;
-    double m[9];
-    for (int i = 0; i < 9; i++) m[i] = cov[i] / scale;
-    double r[3];
-    const double c0 = m[0] * m[4] * m[8] + 2.0 * m[1] * m[2] * m[5] - m[0] * m[5] * m[5] - m[4] * m[2] * m[2] - m[8] * m[1] * m[1];
-    const double c1 = m[0] * m[4] - m[1] * m[1] + m[0] * m[8] - m[2] * m[2] + m[4] * m[8] - m[5] * m[5];
-    const double c2 = m[0] + m[4] + m[8];
-    if (fabs(c0) < 2.220446049250313e-16) {
-        pcl_roots2(c2, c1, r);
-    } else {
-        const double s_inv3 = 1.0 / 3.0, s_sqrt3 = sqrt(3.0);
-        const double c2_over_3 = c2 * s_inv3;
-        double a_over_3 = (c1 - c2 * c2_over_3) * s_inv3;
-        if (a_over_3 > 0.0) a_over_3 = 0.0;
-        const double half_b = 0.5 * (c0 + c2_over_3 * (2.0 * c2_over_3 * c2_over_3 - c1));
-        double q = half_b * half_b + a_over_3 * a_over_3 * a_over_3;
-        if (q > 0.0) q = 0.0;
-        const double rho = sqrt(-a_over_3);
-        const double theta = atan2(sqrt(-q), half_b) * s_inv3;
-        const double ct = cos(theta), st = sin(theta);
-        r[0] = c2_over_3 + 2.0 * rho * ct;
-        r[1] = c2_over_3 - rho * (ct + s_sqrt3 * st);
-        r[2] = c2_over_3 - rho * (ct - s_sqrt3 * st);
-        if (r[0] >= r[1]) { const double t = r[0]; r[0] = r[1]; r[1] = t; }
-        if (r[1] >= r[2]) {
-            const double t = r[1]; r[1] = r[2]; r[2] = t;
-            if (r[0] >= r[1]) { const double u = r[0]; r[0] = r[1]; r[1] = u; }
-        }
-        if (r[0] <= 0.0) pcl_roots2(c2, c1, r);
-    }
-    const double ev = r[0] * scale;
-    m[0] -= r[0];
-    m[4] -= r[0];
-    m[8] -= r[0];
-    const double v1[3] = {m[1] * m[5] - m[2] * m[4], m[2] * m[3] - m[0] * m[5], m[0] * m[4] - m[1] * m[3]};
-    const double v2[3] = {m[1] * m[8] - m[2] * m[7], m[2] * m[6] - m[0] * m[8], m[0] * m[7] - m[1] * m[6]};
-    const double v3[3] = {m[4] * m[8] - m[5] * m[7], m[5] * m[6] - m[3] * m[8], m[3] * m[7] - m[4] * m[6]};
-    const double l1 = v1[0] * v1[0] + v1[1] * v1[1] + v1[2] * v1[2];
-    const double l2 = v2[0] * v2[0] + v2[1] * v2[1] + v2[2] * v2[2];
-    const double l3 = v3[0] * v3[0] + v3[1] * v3[1] + v3[2] * v3[2];
-    const double *v = v3;
-    double l = l3;
-    if (l1 >= l2 && l1 >= l3) { v = v1; l = l1; }
-    else if (l2 >= l1 && l2 >= l3) { v = v2; l = l2; }
-    const double s = sqrt(l);
-    for (int i = 0; i < 3; i++) nrm[i] = v[i] / s;
-    const double tr = cov[0] + cov[4] + cov[8];
-    *curvature = (tr != 0.0) ? fabs(ev / tr) : 0.0;
-}
 
 // computePointNormal's covariance from the nine sums, the plane, flipNormalTowardsViewpoint(origin) + the turn toward CamCenter
 __device__ float4 normal_from_sums(double a0, double a1, double a2, double a3, double a4, double a5, double a6, double a7, double a8, int cnt, const float4 p,
@@ -1498,6 +1387,7 @@ size_t filter_arena_bytes(int64_t n) { // upper bound of one filter call's scrat
     return (size_t)n * 112 + (filter_max_cells(n) + 64) * sizeof(int2) + std::min<size_t>((size_t)64 << 20, ((size_t)32 << 20) + (size_t)n * 16) /* sort / scan temporaries, the exhaustive search's 16 MB of histograms */;
 }
 void *filter_arena_alloc(FilterArena *a, size_t bytes) { return a->get<char>(bytes); }
+void *filter_arena_host(FilterArena *a) { return a->h_pinned; } // (the first 3 * 8192 floats stage the filter's samples: free outside its call)
 
 namespace {
 // robust grid: extents from the 1 % .. 99 % quantiles of a sample (far outliers must not set the cell size)
@@ -1526,19 +1416,11 @@ bool sample_extent(FilterArena *A, const float *d_xyz, int64_t n, hipStream_t st
 }
 } // namespace
 
-struct FilterGridDev {
-    unsigned long long *keys = nullptr;
-    unsigned int *vals = nullptr; // original index of every sorted point
-    float4 *sxyz = nullptr;
-    int2 *table = nullptr; // (first, one past last) sorted index per cell (table_kind 1) or per (y, z) row of cells (2)
-    int table_kind = 0;    // 0: none, binary search on all keys
-    FGrid g{};
-};
 
 // sorts the n points of d_xyz by the key of a grid with cell edge h over the box [bb_lo, bb_hi] (points outside fall
 // into the border cells: clamping is non-expansive, so two points within h of each other still sit in adjacent cells);
 // nv = finite points (they sort first).  Arena space stays allocated until the caller releases its mark.
-static int build_grid(FilterArena *A, const float *d_xyz, int64_t n, int64_t nv, float h, const float bb_lo[3], const float bb_hi[3],
+int build_grid(FilterArena *A, const float *d_xyz, int64_t n, int64_t nv, float h, const float bb_lo[3], const float bb_hi[3],
                       hipStream_t st, FilterGridDev &G) {
     G.g.inv_h = 1.0f / h;
     auto dim = [&](int a) { return (int)std::min<double>(1 << 20, std::max<double>(1.0, floor((double)(bb_hi[a] - bb_lo[a]) / h) + 1.0)); };
@@ -1577,6 +1459,28 @@ static int build_grid(FilterArena *A, const float *d_xyz, int64_t n, int64_t nv,
         if (hipMemsetAsync(G.table, 0, sizeof(int2) * nc, st) != hipSuccess) return RSM_E_HIP;
         hipLaunchKernelGGL(k_cell_table, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, st, k2, (int)nv,
                            (unsigned long long)(G.table_kind == 1 ? 1 : G.g.nx), G.table);
+    }
+    return RSM_OK;
+}
+
+// the bounding box and the finite-point count the filter computes first (k_bbox), for the other cloud steps (k_mls.hip)
+int cloud_bbox(FilterArena *A, const float *d_xyz, int64_t n, hipStream_t st, float lo[3], float hi[3], int64_t *nv) {
+    *nv = 0;
+    for (int a = 0; a < 3; a++) lo[a] = hi[a] = 0.0f;
+    if (n <= 0) return RSM_OK;
+    if (!A->h_pinned) return RSM_E_STATE;
+    unsigned int *d_bb = A->get<unsigned int>(8);
+    if (!d_bb) return RSM_E_NOMEM;
+    unsigned int *h_bb = (unsigned int *)((char *)A->h_pinned + 3 * 8192 * sizeof(float));
+    const unsigned int init[7] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u, 0u};
+    memcpy(h_bb, init, sizeof init);
+    if (hipMemcpyAsync(d_bb, h_bb, sizeof init, hipMemcpyHostToDevice, st) != hipSuccess) return RSM_E_HIP;
+    hipLaunchKernelGGL(k_bbox, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 1024)), dim3(256), 0, st, d_xyz, n, d_bb);
+    if (hipMemcpyAsync(h_bb, d_bb, sizeof init, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return RSM_E_HIP;
+    *nv = h_bb[6];
+    for (int a = 0; a < 3 && *nv; a++) {
+        lo[a] = ord_to_float(h_bb[a]);
+        hi[a] = ord_to_float(h_bb[3 + a]);
     }
     return RSM_OK;
 }

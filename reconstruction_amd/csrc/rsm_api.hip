@@ -1989,6 +1989,65 @@ extern "C" int rsm_filter_last_cloud_host(rsm_ctx *c, const rsm_filter_params *p
     return RSM_OK;
 }
 
+// ---- moving-least-squares smoothing (CCloudOptimization::run, CloudOptimization/CCloudOptimization.cpp:348-389) -----------
+static int mls_args_ok(rsm_ctx *c, int64_t n, const rsm_mls_params *p, const void *out_xyz, const void *out_nrm, const void *src_index,
+                       const int64_t *n_out) {
+    return c && p && n_out && out_xyz && out_nrm && src_index && n >= 0 && n <= (int64_t)INT32_MAX && std::isfinite(p->search_radius) &&
+           p->search_radius > 0.0 && p->polynomial_order >= 0 && p->polynomial_order <= 2;
+}
+// (re)sizes the context's filter arena for an MLS call on n points plus `own` bytes of the caller's
+static int mls_reserve(rsm_ctx *c, int64_t n, size_t own) {
+    if (!c->filt_arena) c->filt_arena = filter_arena_create();
+    if (filter_arena_reserve(c->filt_arena, own + 4096 + mls_arena_bytes(n)) != RSM_OK)
+        return set_err(c, RSM_E_NOMEM, "mls: no device memory for %lld points", (long long)n);
+    return RSM_OK;
+}
+
+extern "C" int rsm_mls_cloud_device(rsm_ctx *c, const rsm_point16 *d_points, int64_t n, const float *d_ref_normals, const rsm_mls_params *p,
+                                    float *d_out_xyz, float *d_out_normals, int32_t *d_src_index, int64_t *n_out) {
+    if (!mls_args_ok(c, n, p, d_out_xyz, d_out_normals, d_src_index, n_out) || (n > 0 && !d_points)) return RSM_E_INVALID;
+    *n_out = 0;
+    if (n == 0) return RSM_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    int s = mls_reserve(c, n, sizeof(float) * 3 * (size_t)n);
+    if (s != RSM_OK) return s;
+    float *dx = (float *)filter_arena_alloc(c->filt_arena, sizeof(float) * 3 * (size_t)n);
+    if (!dx) return set_err(c, RSM_E_NOMEM, "mls: arena too small");
+    launch_point16_xyz(d_points, n, dx, c->stream);
+    s = mls_cloud_device(c->filt_arena, dx, n, (const float4 *)d_ref_normals, p->search_radius, p->polynomial_order, d_out_xyz, d_out_normals,
+                         d_src_index, n_out, c->stream);
+    if (s != RSM_OK) return set_err(c, s, "mls failed");
+    return RSM_OK;
+}
+
+extern "C" int rsm_mls_cloud(rsm_ctx *c, const float *xyz, int64_t n, const float *ref_normals, const rsm_mls_params *p, float *out_xyz,
+                             float *out_normals, int32_t *src_index, int64_t *n_out) {
+    if (!mls_args_ok(c, n, p, out_xyz, out_normals, src_index, n_out) || (n > 0 && !xyz)) return RSM_E_INVALID;
+    *n_out = 0;
+    if (n == 0) return RSM_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t bx = sizeof(float) * 3 * (size_t)n, bn = sizeof(float) * 4 * (size_t)n, bi = sizeof(int32_t) * (size_t)n;
+    int s = mls_reserve(c, n, 2 * bx + (ref_normals ? bn : 0) + bn + bi + 5 * 256);
+    if (s != RSM_OK) return s;
+    FilterArena *A = c->filt_arena;
+    float *dx = (float *)filter_arena_alloc(A, bx), *dox = (float *)filter_arena_alloc(A, bx), *don = (float *)filter_arena_alloc(A, bn);
+    int32_t *doi = (int32_t *)filter_arena_alloc(A, bi);
+    float *dr = ref_normals ? (float *)filter_arena_alloc(A, bn) : nullptr;
+    if (!dx || !dox || !don || !doi || (ref_normals && !dr)) return set_err(c, RSM_E_NOMEM, "mls: arena too small");
+    HIPCHK(c, hipMemcpyAsync(dx, xyz, bx, hipMemcpyHostToDevice, c->stream));
+    if (dr) HIPCHK(c, hipMemcpyAsync(dr, ref_normals, bn, hipMemcpyHostToDevice, c->stream));
+    s = mls_cloud_device(A, dx, n, (const float4 *)dr, p->search_radius, p->polynomial_order, dox, don, doi, n_out, c->stream);
+    if (s != RSM_OK) return set_err(c, s, "mls failed");
+    const size_t m = (size_t)*n_out;
+    if (m > 0) {
+        HIPCHK(c, hipMemcpyAsync(out_xyz, dox, sizeof(float) * 3 * m, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(out_normals, don, sizeof(float) * 4 * m, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(src_index, doi, sizeof(int32_t) * m, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return RSM_OK;
+}
+
 // ---- PLY writer (CStereoMatching.cpp:723-729, 754-756) ----------------------------------------------
 extern "C" int rsm_write_ply(const char *path, const double *xyz, const uint8_t *bgr, int64_t n) {
     if (!path || n < 0 || (n > 0 && (!xyz || !bgr))) return RSM_E_INVALID;

@@ -157,6 +157,7 @@ void filter_arena_destroy(FilterArena *a);
 size_t filter_arena_bytes(int64_t n);                      // scratch one filter call needs for n points
 int filter_arena_reserve(FilterArena *a, size_t bytes);    // makes room, rewinds the arena
 void *filter_arena_alloc(FilterArena *a, size_t bytes);    // caller buffers that live across the call (nullptr: full)
+void *filter_arena_host(FilterArena *a);                   // its small pinned host block (after a reserve; 64 bytes are free for a caller)
 // The cloud as the depth map it is (rsm_filter_last_cloud): which pixels of the top level's margin box emitted a point (k_cloud's
 // flags + per-row offsets: point index = compaction order), the fp64 points, and the geometry that bounds how far a point outside
 // a pixel window can be (k_filter.hip: k_sor_window).  R_final must be a rotation (the caller checks).
@@ -182,3 +183,10 @@ int filter_cloud_device(FilterArena *a, const float *d_xyz, int64_t n, int mean_
                         double stats[4], hipStream_t st, const FilterLattice *pre = nullptr);
 void launch_f64_to_f32x3(const double *src, int64_t n, float *dst, hipStream_t st);
 void launch_pack_filtered16(const double *xyz, const uint8_t *bgr, const int32_t *kept, int64_t m, void *dst16, hipStream_t st);
+
+// moving-least-squares smoothing (k_mls.hip; CCloudOptimization::run, CCloudOptimization.cpp:348-389) of n float xyz points, on the
+// filter's arena: d_ref (optional) n float4 normals to agree with; outputs in input order, *n_out of them (one host round trip)
+size_t mls_arena_bytes(int64_t n); // scratch one call needs for n points (callers add their own buffers)
+int mls_cloud_device(FilterArena *a, const float *d_xyz, int64_t n, const float4 *d_ref, double radius, int order, float *d_oxyz, float *d_onrm,
+                     int32_t *d_oidx, int64_t *n_out, hipStream_t st);
+void launch_point16_xyz(const void *rec, int64_t n, float *xyz, hipStream_t st); // rsm_point16 records -> n x 3 float
