@@ -448,6 +448,32 @@ int rsm_mls_cloud_device(rsm_ctx *ctx, const rsm_point16 *d_points, int64_t n, c
                          const rsm_mls_params *p, float *d_out_xyz, float *d_out_normals, int32_t *d_src_index,
                          int64_t *n_out);
 
+/* ---- multi-view duplicate deletion (the isdelete branch of CCloudOptimization::run, CCloudOptimization.cpp:152-346) */
+/* One pair of the rig as CCloudOptimization::filter(i) leaves it (.cpp:66-71) after Rectify and MatchAllLayer.  Host pointers. */
+typedef struct rsm_dedup_view {
+    double P[2][12];          /* cam[i][k].P, 3x4 row-major, k = 0 (left), 1 (right): R[i][k] / T[i][k] are its columns as float */
+    float cam_center[3];      /* cam[i][0].CamCenter */
+    rsm_boundary bound0;      /* cam[i][0].bound (MatchAllLayer's top-level margin); width or height <= 0: the pair owns no buckets */
+    int width, height;        /* the rectified top level of both views */
+    const uint8_t *image[2];  /* cam[i][k].image, BGR 8UC3, stride 3 * width */
+    const uint8_t *mask[2];   /* cam[i][k].mask, 8UC1, stride width */
+} rsm_dedup_view;
+/* Every point goes to the left view of the pair its normal faces best, is bucketed by the pixel it projects to, and each bucket
+ * whose left-mask pixel is 255 keeps one point per surface layer (the reference's rules, quirks included: DESIGN 9 f6).
+ * index (capacity n) receives indicesptr -- indices into the input, in the reference's (pair, row, column) visiting order --
+ * and *n_out its length; stats = {s1 (outside the bound), s2 (left mask 0), count0 (right-mask misses), buckets visited}.
+ * host buffers: xyz n*3 float, normals4 n*4 float (the filter's normals after their flip: nx, ny, nz, curvature).
+ * RSM_E_INVALID: a NULL output, n < 0 or above INT32_MAX, n > 0 with n_pairs < 1, a NULL image or mask, a bound whose width /
+ * height disagree with XL..XR / YL..YR, a bound outside its image or closer than 2 px to its edge (the 5x5 windows). */
+int rsm_dedup_cloud(rsm_ctx *ctx, const float *xyz, const float *normals4, int64_t n, const rsm_dedup_view *views, int n_pairs,
+                    int32_t *index, int64_t *n_out, int64_t stats[4]);
+/* the same on DEVICE buffers: n rsm_point16 records and n float4 normals (what rsm_filter_last_cloud leaves per pair, concatenated);
+ * d_index (capacity n) as above; d_out_points / d_out_normals (capacity n each, may be NULL) receive the kept records and their
+ * normals, in d_index order -- the input of rsm_mls_cloud_device.  The views' images stay host pointers. */
+int rsm_dedup_cloud_device(rsm_ctx *ctx, const rsm_point16 *d_points, const float *d_normals4, int64_t n, const rsm_dedup_view *views,
+                           int n_pairs, int32_t *d_index, rsm_point16 *d_out_points, float *d_out_normals, int64_t *n_out,
+                           int64_t stats[4]);
+
 /* ---- kernel microbenchmark (MDE/s: pixel x candidate NCC evaluations) -------------------- */
 /* Runs the NCC interval-argmax kernel `iters` times on a resident level-sized problem with
  * `cands` candidates per pixel and returns average milliseconds per launch. */

@@ -1,11 +1,12 @@
-"""python -m reconstruction_amd <config.yml> [--device N] [--out cloud.ply] [--filter] [--mls [--mls-out bigcloud.ply]]
+"""python -m reconstruction_amd <config.yml> [--device N] [--out cloud.ply] [--filter] [--mls [--isdelete] [--mls-out bigcloud.ply]]
 
 The command-line shape of the reference's main() (reconstruction/main.cpp:5-23) for the part this package covers:
 CReconstrction::Init (configuration + calibration, CReconstruction.cpp:5-19) -> CStereoMatching::MatchAllLayer
 (Rectify, pyramid, matching, refinement, cloud; on the MI355X) -> per pair CCloudOptimization::filter's outlier removal
 and normals (--filter; CCloudOptimization.cpp:82-121, on the GPU) -> the merged point cloud as a PLY file -> with --mls
 (implies --filter) the moving-least-squares block of CCloudOptimization::run (CCloudOptimization.cpp:348-389, on the GPU):
-the smoothed, oriented cloud as bigcloud.ply (pcl::PointNormal, savePLYFileBinary), what the mesher reads.
+the smoothed, oriented cloud as bigcloud.ply (pcl::PointNormal, savePLYFileBinary), what the mesher reads; --isdelete runs the
+multi-view duplicate deletion before it (CCloudOptimization.cpp:152-346, on the GPU).
 The rest of CCloudOptimization::run (Poisson meshing, texture: external executables; main.cpp:19) is outside this
 package: feed bigcloud.ply to it.
 Needs an MI355X; there is no CPU path.
@@ -49,7 +50,12 @@ def main(argv=None) -> int:
                     help="after the filter (implied), CCloudOptimization::run's MLS over the merged cloud (order 1, normals flipped to the "
                          "filter's; CCloudOptimization.cpp:348-389) -> bigcloud.ply")
     ap.add_argument("--mls-out", default=None, help="path of the MLS cloud (default: bigcloud.ply next to the --out PLY)")
+    ap.add_argument("--isdelete", action="store_true",
+                    help="with --mls: the multi-view duplicate deletion before the MLS (Init's isdelete = true; CCloudOptimization.cpp:"
+                         "152-346): one point per surface layer per pixel of the view each point faces best")
     args = ap.parse_args(argv)
+    if args.isdelete and not args.mls:
+        ap.error("--isdelete needs --mls (it selects the points the MLS reads)")
     if args.mls:
         args.filter = True
 
@@ -65,7 +71,7 @@ def main(argv=None) -> int:
     if args.filter:
         from . import CloudOptimization
         sink = CloudOptimization(sm._ctx)
-        sink.Init(100, 1, 50, 2, args.mls_radius, data, False)    # CReconstruction.cpp:18
+        sink.Init(100, 1, 50, 2, args.mls_radius, data, args.isdelete)    # CReconstruction.cpp:18 (isdelete false there)
     else:
         sink = CloudSink()
     sm.Init(data, sink, args.radius, args.ws)
@@ -93,7 +99,15 @@ def main(argv=None) -> int:
         import os
         from . import write_ply_pointnormal
         t1 = time.perf_counter()
-        mxyz, mnrm, _ = sink.run()
+        try:
+            mxyz, mnrm, _ = sink.run()
+        except ValueError as e:                                    # --isdelete on pre-rectified input (no P)
+            print(e)
+            return 1
+        if args.isdelete and sm.Verbose >= 1:
+            st = sink.dedup_stats
+            print("s1: %d s2: %d" % (st["s1"], st["s2"]))           # .cpp:194
+            print("%d of %d points kept" % (len(sink.indicesptr), len(xyz)))
         big = args.mls_out or os.path.join(os.path.dirname(os.path.abspath(out)), "bigcloud.ply")
         write_ply_pointnormal(big, mxyz, mnrm)                     # savePLYFileBinary("tmp\\bigcloud.ply"), .cpp:389
         print("MLS time: %.3f s" % (time.perf_counter() - t1))

@@ -62,6 +62,12 @@ class MlsParams(C.Structure):
     _fields_ = [("search_radius", C.c_double), ("polynomial_order", C.c_int)]
 
 
+class DedupView(C.Structure):
+    """rsm_dedup_view (include/rsm.h): one pair of the rig for the duplicate deletion (host pointers)."""
+    _fields_ = [("P", (C.c_double * 12) * 2), ("cam_center", C.c_float * 3), ("bound0", Boundary), ("width", C.c_int),
+                ("height", C.c_int), ("image", C.c_void_p * 2), ("mask", C.c_void_p * 2)]
+
+
 class RectifyIn(C.Structure):
     _fields_ = [("K", (C.c_double * 9) * 2), ("E", (C.c_double * 12) * 2),
                 ("origin_width", C.c_int), ("origin_height", C.c_int), ("lowest_width", C.c_int),
@@ -88,7 +94,7 @@ EXPORTS = [
     "rsm_pack_cloud16", "rsm_comm_unique_id", "rsm_comm_create", "rsm_comm_destroy", "rsm_comm_last_error",
     "rsm_gather_clouds", "rsm_gather_counts", "rsm_gather_meta_fill", "rsm_gather_plan", "rsm_comm_create_transport",
     "rsm_filter_cloud", "rsm_filter_last_cloud", "rsm_host_alloc", "rsm_host_free", "rsm_host_register", "rsm_host_unregister",
-    "rsm_mls_cloud", "rsm_mls_cloud_device",
+    "rsm_mls_cloud", "rsm_mls_cloud_device", "rsm_dedup_cloud", "rsm_dedup_cloud_device",
 ]
 
 _lib = None
@@ -126,5 +132,9 @@ def load():
                                   C.c_void_p, C.POINTER(C.c_int64)]
     lib.rsm_mls_cloud_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(MlsParams), C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+    lib.rsm_dedup_cloud.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(DedupView), C.c_int, C.c_void_p,
+                                    C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.rsm_dedup_cloud_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(DedupView), C.c_int, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     _lib = lib
     return lib

@@ -19,7 +19,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from ._lib import Boundary, FilterParams, MlsParams, NOMATCH, PairIn, PairOut, RectifyIn, RectifyOut, RsmError  # noqa: F401
+from ._lib import Boundary, DedupView, FilterParams, MlsParams, NOMATCH, PairIn, PairOut, RectifyIn, RectifyOut, RsmError  # noqa: F401
 
 
 class _Pinned:
@@ -448,6 +448,61 @@ class Context:
                                                  C.byref(prm), C.c_void_p(out_xyz_ptr or None), C.c_void_p(out_normals_ptr or None),
                                                  C.c_void_p(src_index_ptr or None), C.byref(m)))
         return int(m.value)
+
+    # ---- multi-view duplicate deletion (CCloudOptimization::run's isdelete branch, CloudOptimization/CCloudOptimization.cpp:152-346) ----
+    @staticmethod
+    def dedup_views(cams):
+        """rsm_dedup_view per pair from cam[i][0..1] (Camera objects: P, image, mask, CamCenter, and bound on the left view, as
+        Rectify and MatchAllLayer leave them).  Returns (ctypes array, arrays to keep alive during the call)."""
+        views = (DedupView * max(1, len(cams)))()
+        keep = []
+        for i, pair in enumerate(cams):
+            v = views[i]
+            shape = None
+            for k in range(2):
+                v.P[k][:] = np.asarray(pair[k].P, np.float64).reshape(3, 4).ravel().tolist()
+                img, msk = _u8(pair[k].image), _u8(pair[k].mask)
+                if img.ndim != 3 or img.shape[2] != 3 or msk.shape != img.shape[:2] or (shape is not None and msk.shape != shape):
+                    raise ValueError("dedup: pair %d view %d: image %s / mask %s do not form one rectified pair" % (i, k, img.shape, msk.shape))
+                shape = msk.shape
+                keep += [img, msk]
+                v.image[k], v.mask[k] = img.ctypes.data, msk.ctypes.data
+            v.cam_center[:] = np.asarray(pair[0].CamCenter, np.float32).ravel()[:3].tolist()
+            v.bound0 = _bd(pair[0].bound)
+            v.height, v.width = shape
+        return views, keep
+
+    @staticmethod
+    def _dedup_stats(st):
+        return dict(s1=int(st[0]), s2=int(st[1]), count0=int(st[2]), visited=int(st[3]))
+
+    def dedup_cloud(self, xyz, normals, cams):
+        """The isdelete branch on a host cloud: xyz [n,3] float32 and the filter's normals [n,4] (or [n,3]) of the pairs' filtered
+        clouds in pair order, cams = m_ImageData.cam.  Returns (indicesptr int32 [m], stats dict s1 / s2 / count0 / visited)."""
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        n = len(xyz)
+        nr = np.asarray(normals, np.float32).reshape(n, -1)
+        nrm = np.zeros((n, 4), np.float32)
+        nrm[:, :min(4, nr.shape[1])] = nr[:, :4]
+        views, keep = self.dedup_views(cams)
+        idx = np.zeros(max(n, 1), np.int32)
+        m = C.c_int64()
+        st = (C.c_int64 * 4)()
+        self._chk(self._lib.rsm_dedup_cloud(self._h, _p(xyz), _p(nrm), C.c_int64(n), views, C.c_int(len(cams)), _p(idx), C.byref(m), st))
+        del keep
+        return idx[:int(m.value)].copy(), self._dedup_stats(st)
+
+    def dedup_cloud_device(self, points_ptr, normals_ptr, n, cams, index_ptr, out_points_ptr=None, out_normals_ptr=None):
+        """rsm_dedup_cloud_device on device buffers (addresses): n rsm_point16 records and n float4 normals in; indicesptr (capacity
+        n) and, when given, the kept records / normals out.  Returns (m, stats dict)."""
+        views, keep = self.dedup_views(cams)
+        m = C.c_int64()
+        st = (C.c_int64 * 4)()
+        self._chk(self._lib.rsm_dedup_cloud_device(self._h, C.c_void_p(points_ptr or None), C.c_void_p(normals_ptr or None), C.c_int64(n), views,
+                                                   C.c_int(len(cams)), C.c_void_p(index_ptr or None), C.c_void_p(out_points_ptr or None),
+                                                   C.c_void_p(out_normals_ptr or None), C.byref(m), st))
+        del keep
+        return int(m.value), self._dedup_stats(st)
 
     @property
     def n_points(self):
@@ -881,18 +936,27 @@ class CloudOptimization:
         self._bgr = None
 
     def run(self):
-        """The MLS block of CCloudOptimization::run (:348-389) with isdelete = false (CReconstruction.cpp:18): the pairs'
-        filtered clouds concatenated in pair order (copyPointCloud, :353), MovingLeastSquares with m_mls_radius, polynomial
-        order 1 and normals (:355-364), each normal negated where it disagrees with its input point's filter normal
-        (:378-385).  Stores and returns cloud_ms_normals = (xyz float32 [m,3], normals float32 [m,4], src_index int32 [m]);
-        write_ply_pointnormal writes it as savePLYFileBinary does (:389)."""
-        if getattr(self, "isdelete", False):
-            raise ValueError("CloudOptimization.run: isdelete = true selects the multi-view duplicate deletion (CCloudOptimization.cpp:152-346), "
-                             "a branch the reference never takes (CReconstruction.cpp:18 passes false); it is not implemented")
+        """The MLS block of CCloudOptimization::run (:348-389): the pairs' filtered clouds concatenated in pair order (copyPointCloud,
+        :353), MovingLeastSquares with m_mls_radius, polynomial order 1 and normals (:355-364), each normal negated where it disagrees
+        with its input point's filter normal (:378-385).  With isdelete (Init's isdelete_) the multi-view duplicate deletion
+        (:152-346) runs first on the GPU and the MLS reads cloud_normals[indicesptr] (:352); self.indicesptr and self.dedup_stats
+        keep what it did.  Stores and returns cloud_ms_normals = (xyz float32 [m,3], normals float32 [m,4], src_index int32 [m] into
+        the merged cloud: indicesptr[idx_in_orig] with isdelete); write_ply_pointnormal writes it as savePLYFileBinary does (:389)."""
         if self.cloud_normals:
             xyz = np.concatenate([c[0] for c in self.cloud_normals]).astype(np.float32)
             ref = np.concatenate([c[1] for c in self.cloud_normals]).astype(np.float32)
         else:
             xyz, ref = np.zeros((0, 3), np.float32), np.zeros((0, 4), np.float32)
-        self.cloud_ms_normals = self._ctx.mls_cloud(xyz, self.m_mls_radius, 1, ref)
+        if getattr(self, "isdelete", False):
+            cams = self.m_ImageData.cam
+            if any(c.P is None or c.image is None or c.mask is None for pair in cams for c in pair[:2]) or \
+                    any(pair[0].bound is None or pair[0].CamCenter is None for pair in cams):
+                raise ValueError("CloudOptimization.run: isdelete = true (the multi-view duplicate deletion, CCloudOptimization.cpp:152-346) "
+                                 "needs every camera's P, image and mask and the left views' bound and CamCenter, as Rectify and "
+                                 "MatchAllLayer leave them; pre-rectified input carries no P")
+            self.indicesptr, self.dedup_stats = self._ctx.dedup_cloud(xyz, ref, cams)
+            ox, on, oi = self._ctx.mls_cloud(xyz[self.indicesptr], self.m_mls_radius, 1, ref[self.indicesptr])
+            self.cloud_ms_normals = (ox, on, self.indicesptr[oi])
+        else:
+            self.cloud_ms_normals = self._ctx.mls_cloud(xyz, self.m_mls_radius, 1, ref)
         return self.cloud_ms_normals

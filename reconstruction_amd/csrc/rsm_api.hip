@@ -2048,6 +2048,64 @@ extern "C" int rsm_mls_cloud(rsm_ctx *c, const float *xyz, int64_t n, const floa
     return RSM_OK;
 }
 
+// ---- multi-view duplicate deletion (the isdelete branch of CCloudOptimization::run, CCloudOptimization.cpp:152-346) ----------------
+static int dedup_args_ok(rsm_ctx *c, int64_t n, const rsm_dedup_view *v, int np, const void *index, const int64_t *n_out, const int64_t *stats) {
+    if (!c || !index || !n_out || !stats || n < 0 || n > (int64_t)INT32_MAX) return 0;
+    if (n > 0 && (np < 1 || !v)) return 0;
+    return np < 1 || (v && dedup_views_ok(v, np));
+}
+static int dedup_reserve(rsm_ctx *c, const rsm_dedup_view *v, int np, int64_t n, size_t own) {
+    if (!c->filt_arena) c->filt_arena = filter_arena_create();
+    if (filter_arena_reserve(c->filt_arena, own + 4096 + dedup_arena_bytes(v, np, n)) != RSM_OK)
+        return set_err(c, RSM_E_NOMEM, "dedup: no device memory for %lld points", (long long)n);
+    return RSM_OK;
+}
+
+extern "C" int rsm_dedup_cloud_device(rsm_ctx *c, const rsm_point16 *d_points, const float *d_normals4, int64_t n, const rsm_dedup_view *views,
+                                      int n_pairs, int32_t *d_index, rsm_point16 *d_out_points, float *d_out_normals, int64_t *n_out,
+                                      int64_t stats[4]) {
+    if (!dedup_args_ok(c, n, views, n_pairs, d_index, n_out, stats) || (n > 0 && (!d_points || !d_normals4))) return RSM_E_INVALID;
+    *n_out = 0;
+    for (int t = 0; t < 4; t++) stats[t] = 0;
+    if (n == 0) return RSM_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    int s = dedup_reserve(c, views, n_pairs, n, 0);
+    if (s != RSM_OK) return s;
+    s = dedup_cloud_device(c->filt_arena, (const float *)d_points, 4, (const float4 *)d_normals4, n, views, n_pairs, d_index, n_out, stats, c->stream);
+    if (s != RSM_OK) return set_err(c, s, "dedup failed");
+    if (*n_out > 0 && (d_out_points || d_out_normals)) {
+        launch_dedup_gather(d_points, d_normals4, d_index, *n_out, d_out_points, d_out_normals, c->stream);
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipGetLastError());
+    }
+    return RSM_OK;
+}
+
+extern "C" int rsm_dedup_cloud(rsm_ctx *c, const float *xyz, const float *normals4, int64_t n, const rsm_dedup_view *views, int n_pairs,
+                               int32_t *index, int64_t *n_out, int64_t stats[4]) {
+    if (!dedup_args_ok(c, n, views, n_pairs, index, n_out, stats) || (n > 0 && (!xyz || !normals4))) return RSM_E_INVALID;
+    *n_out = 0;
+    for (int t = 0; t < 4; t++) stats[t] = 0;
+    if (n == 0) return RSM_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t bx = sizeof(float) * 3 * (size_t)n, bn = sizeof(float) * 4 * (size_t)n, bi = sizeof(int32_t) * (size_t)n;
+    int s = dedup_reserve(c, views, n_pairs, n, bx + bn + bi + 3 * 256);
+    if (s != RSM_OK) return s;
+    FilterArena *A = c->filt_arena;
+    float *dx = (float *)filter_arena_alloc(A, bx), *dn = (float *)filter_arena_alloc(A, bn);
+    int32_t *di = (int32_t *)filter_arena_alloc(A, bi);
+    if (!dx || !dn || !di) return set_err(c, RSM_E_NOMEM, "dedup: arena too small");
+    HIPCHK(c, hipMemcpyAsync(dx, xyz, bx, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(dn, normals4, bn, hipMemcpyHostToDevice, c->stream));
+    s = dedup_cloud_device(A, dx, 3, (const float4 *)dn, n, views, n_pairs, di, n_out, stats, c->stream);
+    if (s != RSM_OK) return set_err(c, s, "dedup failed");
+    if (*n_out > 0) {
+        HIPCHK(c, hipMemcpyAsync(index, di, sizeof(int32_t) * (size_t)*n_out, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return RSM_OK;
+}
+
 // ---- PLY writer (CStereoMatching.cpp:723-729, 754-756) ----------------------------------------------
 extern "C" int rsm_write_ply(const char *path, const double *xyz, const uint8_t *bgr, int64_t n) {
     if (!path || n < 0 || (n > 0 && (!xyz || !bgr))) return RSM_E_INVALID;

@@ -190,3 +190,22 @@ size_t mls_arena_bytes(int64_t n); // scratch one call needs for n points (calle
 int mls_cloud_device(FilterArena *a, const float *d_xyz, int64_t n, const float4 *d_ref, double radius, int order, float *d_oxyz, float *d_onrm,
                      int32_t *d_oidx, int64_t *n_out, hipStream_t st);
 void launch_point16_xyz(const void *rec, int64_t n, float *xyz, hipStream_t st); // rsm_point16 records -> n x 3 float
+
+// multi-view duplicate deletion (k_dedup.hip; CCloudOptimization::run's isdelete branch, CCloudOptimization.cpp:152-346): one pair as the
+// kernels see it -- R / T of both views as float (cv2eigen of P's columns), CamCenter, the left bound, the images on the device, and
+// the first key of the pair's buckets
+struct DedupPair {
+    float R0[9], T0[3], R1[9], T1[3], C[3];
+    int XL, YL, bw, bh, W, H;
+    unsigned long long base;
+    const uint8_t *img0, *img1, *m0, *m1;
+};
+struct rsm_dedup_view;
+int dedup_views_ok(const rsm_dedup_view *v, int n_pairs); // bounds inside their images, 2 px from the edge (empty bounds pass)
+size_t dedup_arena_bytes(const rsm_dedup_view *v, int n_pairs, int64_t n); // scratch one call needs (images included; callers add theirs)
+// n points (float x, y, z at d_pts[stride * j]) with float4 normals -> d_index (capacity n) = indicesptr, *n_out of them; stats = s1, s2,
+// count0, buckets visited.  Uploads the views' host images into the arena; one host round trip after the sort, one at the end.
+int dedup_cloud_device(FilterArena *a, const float *d_pts, int stride, const float4 *d_nrm, int64_t n, const rsm_dedup_view *v, int n_pairs,
+                       int32_t *d_index, int64_t *n_out, int64_t stats[4], hipStream_t st);
+// the kept points as rsm_point16 records and their float4 normals (either output may be NULL), what rsm_mls_cloud_device reads
+void launch_dedup_gather(const void *d_rec, const float *d_nrm, const int32_t *d_idx, int64_t m, void *d_orec, float *d_onrm, hipStream_t st);

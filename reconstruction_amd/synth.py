@@ -255,3 +255,85 @@ def make_raw_pair(origin=(640, 480), lowest=(80, 60), pyr_levels=3, seed=7, base
         msks.append(m)
     return dict(K=[K0, K1], E=[E0, E1], origin=origin, lowest=lowest, pyr_levels=pyr_levels, image=imgs, mask=msks,
                 baseline=baseline, depth=depth)
+
+
+def _render_plane(K, R, Cc, tex, s, origin, depth):
+    """View of the textured plane Z = depth from a pinhole camera (K, world -> camera rotation R, centre Cc), bilinear."""
+    ow, oh = origin
+    uu, vv = np.meshgrid(np.arange(ow, dtype=np.float64), np.arange(oh, dtype=np.float64))
+    rays = np.stack([(uu - K[0, 2]) / K[0, 0], (vv - K[1, 2]) / K[1, 1], np.ones_like(uu)], -1) @ R  # R^T applied
+    lam = (depth - Cc[2]) / rays[..., 2]
+    X = Cc[0] + lam * rays[..., 0]
+    Y = Cc[1] + lam * rays[..., 1]
+    th, tw = tex.shape[:2]
+    tx = np.clip(X * s + tw / 2.0, 0, tw - 1.001)
+    ty = np.clip(Y * s + th / 2.0, 0, th - 1.001)
+    x0 = np.floor(tx).astype(np.int64); y0 = np.floor(ty).astype(np.int64)
+    fx = (tx - x0)[..., None]; fy = (ty - y0)[..., None]
+    v = (tex[y0, x0] * (1 - fx) * (1 - fy) + tex[y0, x0 + 1] * fx * (1 - fy) +
+         tex[y0 + 1, x0] * (1 - fx) * fy + tex[y0 + 1, x0 + 1] * fx * fy)
+    return np.clip(np.rint(v), 0, 255).astype(np.uint8)
+
+
+def make_raw_rig(n_cams=3, origin=(640, 480), lowest=(80, 60), pyr_levels=3, seed=7, baseline=-150.0, depth=1500.0, mask_border=40):
+    """A rig of n_cams calibrated pinhole views of ONE textured plane Z = depth (make_raw_pair's renderer, generalised): camera c
+    sits at x = c * baseline with a small jitter and its own small rotation; the pairs are (c, c + 1).  Neighbouring pairs see
+    the same part of the plane, so after Rectify and MatchAllLayer the merged cloud holds real cross-pair duplicates (the input of
+    CCloudOptimization::run's isdelete branch).  The default negative baseline gives positive view-0 disparities (see
+    make_raw_pair's callers)."""
+    ow, oh = origin
+    f = 1.1 * ow
+    rng = np.random.default_rng(seed + 17)
+    span = abs(baseline) * (n_cams - 1)
+    tex = make_texture(2 * ow + int(span * 2 * ow / (depth / f * ow * 1.8)) + 8, 2 * oh, seed, contrast=3.0).astype(np.float64)
+    s = 2 * ow / (depth / f * ow * 1.8)      # world units -> texture pixels
+    Ks, Es, imgs, msks, centres = [], [], [], [], []
+    for c in range(n_cams):
+        K = np.array([[f * (1 + 0.01 * rng.uniform(-1, 1)), 0, ow / 2.0 + rng.uniform(-4, 4)],
+                      [0, f * (1 + 0.01 * rng.uniform(-1, 1)), oh / 2.0 + rng.uniform(-3, 3)], [0, 0, 1.0]])
+        R = _rot(*rng.uniform(-0.01, 0.01, 3))
+        Cc = np.array([c * baseline, rng.uniform(-2, 2), rng.uniform(-2, 2)])
+        Ks.append(K)
+        Es.append(np.hstack([R, (-R @ Cc)[:, None]]))
+        imgs.append(_render_plane(K, R, Cc, tex, s, origin, depth))
+        m = np.zeros((oh, ow), np.uint8)
+        m[mask_border:oh - mask_border, mask_border:ow - mask_border] = 255
+        msks.append(m)
+        centres.append(Cc)
+    return dict(K=Ks, E=Es, origin=origin, lowest=lowest, pyr_levels=pyr_levels, image=imgs, mask=msks, centre=centres,
+                pairs=[(c, c + 1) for c in range(n_cams - 1)], baseline=baseline, depth=depth)
+
+
+def rig_data(rig):
+    """ManageData of make_raw_rig's pairs, raw images attached (what MatchAllLayer rectifies), CamCenter = -R^T t as load_config
+    sets it (CManageData.cpp:61-62)."""
+    from .api import Camera, ManageData
+    cams = []
+    for a, b in rig["pairs"]:
+        pair = []
+        for c in (a, b):
+            cam = Camera(camID=c, MatIntrinsics=rig["K"][c], MatExtrinsics=rig["E"][c])
+            R, t = rig["E"][c][:, :3], rig["E"][c][:, 3]
+            cam.CamCenter = (-R.T @ t).astype(np.float32)
+            cam.raw_image, cam.raw_mask = rig["image"][c], rig["mask"][c]
+            pair.append(cam)
+        cams.append(pair)
+    return ManageData(cam=cams, m_PyrmNum=rig["pyr_levels"], m_LowestLevelSize=rig["lowest"], m_OriginSize=rig["origin"])
+
+
+def rectified_views(Q, R_final, T_final):
+    """Projections of a pre-rectified pair (its Q, R_final, T_final; top level = origin size): (P0, P1, CamCenter) with
+    P0 = K_rect [R_final^T | -R_final^T T_final], P1 the right view B = -1 / Q[3,2] along the rectified x axis with its principal
+    point cx + B Q[3,3], and CamCenter = T_final -- the inverse of DisparityToCloud's X = R_final (x - cx, y - cy, f) / w + T_final
+    (CStereoMatching.cpp:734-749), so a matched pair's cloud projects back onto its own pixels."""
+    Q = np.asarray(Q, np.float64).reshape(4, 4)
+    Rf = np.asarray(R_final, np.float64).reshape(3, 3)
+    Tf = np.asarray(T_final, np.float64).reshape(3)
+    f, cx, cy = Q[2, 3], -Q[0, 3], -Q[1, 3]
+    B = -1.0 / Q[3, 2]
+    K0 = np.array([[f, 0, cx], [0, f, cy], [0, 0, 1.0]])
+    K1 = np.array([[f, 0, cx + B * Q[3, 3]], [0, f, cy], [0, 0, 1.0]])
+    E = np.hstack([Rf.T, (-Rf.T @ Tf)[:, None]])
+    P0 = K0 @ E
+    P1 = K1 @ (E - np.hstack([np.zeros((3, 3)), np.array([[B], [0.0], [0.0]])]))
+    return P0, P1, Tf.astype(np.float32)
