@@ -274,6 +274,10 @@ int rsm_gather_plan(int rank, int world, int root, int n_local, const int *pair_
  *                          probed again on every 8th call, for another k or image size, when it stops deciding 70 % of the queries and
  *                          after any "filter_*" option), 0 off (the generic grid
  *                          search decides every query), 7 / 12 / 16 / 20 / 24 that radius
+ *   "filter_ladder_h"      rsm_filter_cloud / rsm_filter_last_cloud: the bit pattern of a positive finite float32 pins the search radius
+ *                          of the k-nearest grid ladder's first level (each further level doubles it; its cells are a hair wider, see
+ *                          csrc/cloud_grid.h); 0 (default) = from the cloud's sampled extent.  Route only: a level decides a query
+ *                          only with all of its k + 1 nearest in hand, so the results are the same bits (tests; rsm_filter_last_grid)
  *   "shared_gpu" = 1       the caller's hint that other contexts use this context's GPU (pairs in flight): the lone-pair split
  *                          below is never used, whatever the library's own count says at the moment a level is enqueued;
  *                          rsm_run_pairs / rsm_match_pairs derive the same per call from their pool (the option stays as the caller
@@ -422,6 +426,12 @@ int rsm_filter_last_info(rsm_ctx *ctx, int64_t info[4]);
  * grid of radius-cells over the filtered cloud instead; info[1] = the widest window any point needed (the search radius in pixel
  * spacings at the nearest point: a property of the rig), -1 when the lattice was not available.  Option "filter_normals_window". */
 int rsm_filter_last_normals_info(rsm_ctx *ctx, int64_t info[2]);
+/* ... and the k-nearest grid ladder of the last rsm_filter_cloud or rsm_filter_last_cloud[_host]: grid[0] = its first level's search
+ * radius (0: no level ran -- the pixel-window passes decided every query), grid[1..3] = that level's grid origin (world x, y, z);
+ * info[0..2] = its cells per world axis, info[3] = the levels run, info[4] = the first level's cell table kind t (k_sor_knn<t>; 1: per
+ * cell, 2: per row of cells, 0: none; -1: no level ran), info[5] = bit t set when some level searched with kind t.  Option
+ * "filter_ladder_h". */
+int rsm_filter_last_grid(rsm_ctx *ctx, double grid[4], int64_t info[6]);
 /* The same with HOST output buffers (page-locked ones from rsm_host_alloc arrive at the link's rate): what a pipeline that
  * replaces the first half of CCloudOptimization::filter (CCloudOptimization.cpp:82-121) downloads instead of the raw cloud --
  * the surviving points and their oriented normals (the reference's cloud_normal, :110-121).  h_normals may be NULL. */

@@ -339,6 +339,15 @@ class Context:
             self._chk(self._lib.rsm_filter_last_normals_info(self._h, w))
         return dict(window=bool(v[0]), radius=int(v[0]), undecided=int(v[1]), points=int(v[2]), kept=int(v[3]), normals_window=int(w[0]), normals_need=int(w[1]))
 
+    def filter_last_grid(self) -> dict:
+        """The k-nearest grid ladder of the last filter_cloud / filter_last_cloud[_host]: its first level's search radius h (float32),
+        grid origin and cells per world axis, the levels run and the cell-table kinds they searched with (option "filter_ladder_h")."""
+        g = (C.c_double * 4)()
+        v = (C.c_int64 * 6)()
+        self._chk(self._lib.rsm_filter_last_grid(self._h, g, v))
+        return dict(h=np.float32(g[0]), origin=np.array(g[1:4], np.float32), cells=[int(v[a]) for a in range(3)], levels=int(v[3]),
+                    kind0=int(v[4]), kinds=sorted(t for t in range(3) if (v[5] >> t) & 1))
+
     def filter_last_cloud_host(self, mean_k=100, std_mul=1.0, normal_radius=2.5, cam_center=(0.0, 0.0, 0.0), want_normals=True):
         """rsm_filter_last_cloud_host: the per-pair filter on the GPU, its output -- the surviving points as rsm_point16 records
         and their oriented normals (nx, ny, nz, curvature) -- downloaded.  Returns (records, normals or None, stats dict)."""

@@ -9,7 +9,7 @@
 // a depth map is a sheet in a deep box, so the rows of cells along its depth hold a handful of points each and the
 // per-row table + short search inside the row (table kind 2) stays cheap when the cells are too many for a table.
 struct FGrid {
-    float ox, oy, oz, inv_h;
+    double ox, oy, oz, inv_h; // origin (the box's low corner, floats), 1 / the cell edge H = grid_edge(h)
     int nx, ny, nz;
     int p0, p1, p2; // world axis (0 = x, 1 = y, 2 = z) of key axis x, y, z
 };
@@ -20,9 +20,24 @@ __device__ __forceinline__ float fdist2(float ax, float ay, float az, float bx, 
     return (dx * dx + dy * dy) + dz * dz;
 }
 
-__device__ __forceinline__ int cell_of(float v, float o, float inv_h, int n) {
-    const int c = (int)floorf((v - o) * inv_h);
-    return min(max(c, 0), n - 1);
+// The searches rest on one invariant: every point q that passes a membership test against p -- fdist2(p, q) <= fl(h h) for the
+// k nearest, fdist2(p, q) < fl32(r r) with h = fl32(r) for the radius searches -- lies at most one cell from p on each axis.
+// The bound (u = 2^-24, float32; e = 2^-53, double):
+//   fdist2 is a rounded sum of the non-negative fl(d_a^2), so fl(d_a^2) <= T on each axis, d_a = fl(p_a - q_a): |d_a| <= sqrt(T) (1 + u/2)
+//   and |p_a - q_a| <= |d_a| (1 + u); sqrt(T) <= h (1 + 3u/2) for both tests.  So |p_a - q_a| <= h (1 + 3u) < h (1 + 2^-22)
+//   (for h^2 a normal float; below 2^-63 the accepted differences are below 2^-63: the edge's floor).
+//   cell_of evaluates t = fl64(fl64(v - o) s), s = fl64(1 / H), in double: |t - (v - o) / H| <= 3e |t|, and a pair that clamping
+//   could not merge has |t| <= n + 2 <= 2^20 + 2 on both ends: t_p - t_q <= (h / H)(1 + 2^-22)(1 + e) + 2^-30.
+//   With H = grid_edge(h) = h (1 + 2^-20) that is < 1, so floor(t_p) - floor(t_q) <= 1; clamping to [0, n - 1] keeps it.
+// (The float form, floorf(fl32(v - o) * fl32(1 / h)), has no such bound: its rounding of v - o alone puts pairs at a float distance
+// below r into cells two apart -- tests/cloud_probes.py builds them, tests/test_gpu_cloud_grid_edges.py runs them.)
+__host__ __device__ __forceinline__ double grid_edge(float h) {
+    const double H = (double)h * (1.0 + 0x1p-20);
+    return H > 0x1p-62 ? H : 0x1p-62;
+}
+__device__ __forceinline__ int cell_of(float v, double o, double inv_h, int n) {
+    const double t = floor(((double)v - o) * inv_h);
+    return (int)fmin(fmax(t, 0.0), (double)(n - 1)); // (clamped in double: no out-of-range conversion for far points)
 }
 // cell of a world point, in key order
 __device__ __forceinline__ void grid_cell(const FGrid &g, float x, float y, float z, int &ix, int &iy, int &iz) {
@@ -132,10 +147,10 @@ struct FilterGridDev {
     FGrid g{};
 };
 
-// k_filter.hip: sorts the n points of d_xyz (n x 3 float) by the key of a grid with cell edge h over the box [bb_lo, bb_hi] (points
-// outside fall into the border cells: clamping is non-expansive, so two points within h of each other still sit in adjacent cells;
-// non-finite points sort behind every cell); nv = finite points, 0 = no cell table (ranges by binary search).  The arrays come from
-// the arena and stay allocated until its caller rewinds it.
+// k_filter.hip: sorts the n points of d_xyz (n x 3 float) by the key of a grid for the search radius h -- cell edge grid_edge(h) --
+// over the box [bb_lo, bb_hi] (points outside fall into the border cells: clamping is non-expansive, so two points within h of each
+// other still sit in adjacent cells; non-finite points sort behind every cell); nv = finite points, 0 = no cell table (ranges by
+// binary search).  The arrays come from the arena and stay allocated until its caller rewinds it.
 int build_grid(FilterArena *A, const float *d_xyz, int64_t n, int64_t nv, float h, const float bb_lo[3], const float bb_hi[3],
                hipStream_t st, FilterGridDev &G);
 // k_filter.hip: the exact bounding box of the finite points of d_xyz and their number (one host round trip)

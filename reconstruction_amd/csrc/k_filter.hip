@@ -1417,17 +1417,19 @@ bool sample_extent(FilterArena *A, const float *d_xyz, int64_t n, hipStream_t st
 } // namespace
 
 
-// sorts the n points of d_xyz by the key of a grid with cell edge h over the box [bb_lo, bb_hi] (points outside fall
-// into the border cells: clamping is non-expansive, so two points within h of each other still sit in adjacent cells);
-// nv = finite points (they sort first).  Arena space stays allocated until the caller releases its mark.
+// sorts the n points of d_xyz by the key of a grid for the search radius h (cell edge grid_edge(h), a hair wider than h: see
+// cell_of) over the box [bb_lo, bb_hi] (points outside fall into the border cells: clamping is non-expansive, so two points within
+// h of each other still sit in adjacent cells); nv = finite points (they sort first).  Arena space stays allocated until the
+// caller releases its mark.
 int build_grid(FilterArena *A, const float *d_xyz, int64_t n, int64_t nv, float h, const float bb_lo[3], const float bb_hi[3],
                       hipStream_t st, FilterGridDev &G) {
-    G.g.inv_h = 1.0f / h;
-    auto dim = [&](int a) { return (int)std::min<double>(1 << 20, std::max<double>(1.0, floor((double)(bb_hi[a] - bb_lo[a]) / h) + 1.0)); };
+    const double H = grid_edge(h);
+    G.g.inv_h = 1.0 / H;
+    auto dim = [&](int a) { return (int)std::min<double>(1 << 20, std::max<double>(1.0, floor(((double)bb_hi[a] - (double)bb_lo[a]) / H) + 1.0)); };
     int ax[3] = {0, 1, 2};
     std::sort(ax, ax + 3, [&](int a, int b) { return dim(a) != dim(b) ? dim(a) > dim(b) : a < b; }); // most cells first = fastest key digit
     G.g.p0 = ax[0], G.g.p1 = ax[1], G.g.p2 = ax[2];
-    G.g.ox = bb_lo[ax[0]], G.g.oy = bb_lo[ax[1]], G.g.oz = bb_lo[ax[2]];
+    G.g.ox = (double)bb_lo[ax[0]], G.g.oy = (double)bb_lo[ax[1]], G.g.oz = (double)bb_lo[ax[2]];
     G.g.nx = dim(ax[0]), G.g.ny = dim(ax[1]), G.g.nz = dim(ax[2]);
     unsigned long long *k1 = A->get<unsigned long long>((size_t)n), *k2 = A->get<unsigned long long>((size_t)n);
     unsigned int *v1 = A->get<unsigned int>((size_t)n), *v2 = A->get<unsigned int>((size_t)n);
@@ -1518,8 +1520,13 @@ static void launch_knn(const float *d_xyz, const FilterGridDev &G, int nv, float
 // the grid ladder only sees the rest.
 int filter_cloud_device(FilterArena *A, const float *d_xyz, int64_t n, int mean_k, double std_mul, double normal_radius,
                         const float cam_center[3], int32_t *d_kept_index, float *d_fxyz, float4 *d_normals, int64_t *n_kept,
-                        double stats[4], hipStream_t st, const FilterLattice *pre) {
+                        double stats[4], hipStream_t st, const FilterLattice *pre, FilterRoute *route) {
     *n_kept = 0;
+    if (route) {
+        const float h0 = route->h0;
+        *route = FilterRoute{};
+        route->h0 = h0;
+    }
     if (n <= 0) return RSM_OK;
     if (n >= (1ll << 31) || mean_k < 1 || !A) return RSM_E_INVALID;
     float lo[3], hi[3], flo[3], fhi[3];
@@ -1582,6 +1589,7 @@ int filter_cloud_device(FilterArena *A, const float *d_xyz, int64_t n, int mean_
         }
         h *= 0.5f;
         if (h_floor > h) h = h_floor;
+        if (route && route->h0 > 0.0f) h = route->h0; // (a level decides a query only with all of its k + 1 nearest in hand: any start gives the same bits)
         have_grid_box = true;
         return true;
     };
@@ -1707,6 +1715,19 @@ int filter_cloud_device(FilterArena *A, const float *d_xyz, int64_t n, int mean_
         lat_keep = nullptr;
         s = build_grid(A, d_xyz, n, nv, h, glo, ghi, st, G);
         if (s != RSM_OK) return s;
+        if (route) {
+            if (level == 0) {
+                route->h = h;
+                route->kind0 = G.table_kind;
+                const int nk[3] = {G.g.nx, G.g.ny, G.g.nz}, pk[3] = {G.g.p0, G.g.p1, G.g.p2};
+                for (int a = 0; a < 3; a++) {
+                    route->origin[a] = glo[a];
+                    route->cells[pk[a]] = nk[a];
+                }
+            }
+            route->levels++;
+            route->kinds |= 1 << G.table_kind;
+        }
         if (level == 0 && !prepassed) queries = G.vals; // every point, in grid order (coherent waves)
         unsigned int *out_list = (queries == d_redo) ? d_redo2 : d_redo; // never the list being read
         launch_knn(d_xyz, G, (int)nv, h, mean_k, queries, nq, d_dist, d_flag, st);

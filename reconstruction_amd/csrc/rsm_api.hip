@@ -128,6 +128,7 @@ struct rsm_ctx {
     int opt_filter_window = 1;         // rsm_filter_last_cloud: the pixel-window k-nearest pass in front of the grid ladder (1: radius from a sparse probe; 0: off; else the radius)
     int64_t filt_tile_left = 0;        // ... queries the tile pass alone left over
     int64_t filt_info[4]{};            // last rsm_filter_last_cloud: window pass used, queries it left to the ladder, points in, points kept
+    FilterRoute filt_route;            // the grid ladder: option "filter_ladder_h" in, what the last rsm_filter_cloud / rsm_filter_last_cloud did out
 
     // results
     double *res_disp[2]{};
@@ -550,6 +551,11 @@ extern "C" int rsm_set_option(rsm_ctx *c, const char *name, long long value) {
     } else if (!strcmp(name, "shared_gpu")) c->opt_shared_gpu = value != 0;
     else if (!strcmp(name, "filter_list")) c->opt_filter_list = (int)std::max(0LL, std::min(value, 31LL)); // bit 0: the 24-pixel list pass, bit 1: the 40-pixel one, bit 2: the wave passes (80, 160, ... pixels) for what they leave, bits 3 / 4: the 24- / 40-pixel pass in the wave form too
     else if (!strcmp(name, "filter_window")) c->opt_filter_window = (int)std::max(0LL, std::min(value, 24LL)); // 0 off, 1 default, else the radius
+    else if (!strcmp(name, "filter_ladder_h")) { // the bit pattern of a positive finite float32: the first ladder level's search radius; 0: from the sample
+        if (value < 0 || value >= 0x7f800000LL) return set_err(c, RSM_E_INVALID, "filter_ladder_h %lld: 0 or the bit pattern of a positive finite float", value);
+        uint32_t bits = (uint32_t)value;
+        memcpy(&c->filt_route.h0, &bits, sizeof bits);
+    }
     else if (!strcmp(name, "refine_skew_waves_alone")) c->opt_refine_skew_waves_alone = (int)std::max(0LL, std::min(value, 1000000LL));
     else if (!strcmp(name, "refine_skew_rows")) c->opt_refine_skew_rows = (int)std::max(0LL, std::min(value, 1000000LL));
     else if (!strcmp(name, "cu_share")) {
@@ -1836,7 +1842,7 @@ extern "C" int rsm_filter_cloud(rsm_ctx *c, const float *xyz, int64_t n, const r
     if (sb != RSM_OK) return sb;
     HIPCHK(c, hipMemcpyAsync(dx, xyz, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, c->stream));
     const int s = filter_cloud_device(c->filt_arena, dx, n, prm->sor_mean_k, prm->sor_std_mul, prm->normal_radius, prm->cam_center, dk, df, dn,
-                                      n_kept, stats, c->stream);
+                                      n_kept, stats, c->stream, nullptr, &c->filt_route);
     if (s != RSM_OK) return set_err(c, s, "cloud filter failed");
     if (*n_kept > 0) {
         t.down(kept_index, (const int32_t *)dk, (size_t)*n_kept);
@@ -1926,7 +1932,7 @@ extern "C" int rsm_filter_last_cloud(rsm_ctx *c, const rsm_filter_params *prm, r
     launch_f64_to_f32x3(c->xyz, n, dx, fs); // InsertPoint's cast, CCloudOptimization.cpp:61
     int64_t m = 0;
     const int s = filter_cloud_device(c->filt_arena, dx, n, prm->sor_mean_k, prm->sor_std_mul, prm->normal_radius, prm->cam_center, dk, df, dn, &m, stats,
-                                      fs, use_lat ? &lat : nullptr);
+                                      fs, use_lat ? &lat : nullptr, &c->filt_route);
     if (s != RSM_OK) return set_err(c, s, "cloud filter failed");
     if (use_lat && c->opt_filter_window == 1) {
         if (memo_ok && tile_left >= 0 && (double)tile_left <= 0.3 * (double)n) c->filt_memo_uses++; // still a good choice
@@ -1961,6 +1967,20 @@ extern "C" int rsm_filter_last_normals_info(rsm_ctx *c, int64_t info[2]) {
 extern "C" int rsm_filter_last_info(rsm_ctx *c, int64_t info[4]) {
     if (!c || !info) return RSM_E_INVALID;
     memcpy(info, c->filt_info, sizeof c->filt_info);
+    return RSM_OK;
+}
+
+extern "C" int rsm_filter_last_grid(rsm_ctx *c, double grid[4], int64_t info[6]) {
+    if (!c || !grid || !info) return RSM_E_INVALID;
+    const FilterRoute &r = c->filt_route;
+    grid[0] = r.h;
+    for (int a = 0; a < 3; a++) {
+        grid[1 + a] = r.origin[a];
+        info[a] = r.cells[a];
+    }
+    info[3] = r.levels;
+    info[4] = r.kind0;
+    info[5] = r.kinds;
     return RSM_OK;
 }
 

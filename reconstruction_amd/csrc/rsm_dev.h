@@ -177,10 +177,20 @@ struct FilterLattice {
     int normals_wmax;   // the normals' radius search on the lattice copy while no point needs a window wider than this (0: always on a grid of radius-cells)
     int *normals_out;   // optional, 2 ints: the window the normals used (0: the grid), the widest window a point needed
 };
+// The k-nearest grid ladder's route (option "filter_ladder_h", rsm_filter_last_grid): which levels decide a query, never its result.
+struct FilterRoute {
+    float h0 = 0.0f;        // in: > 0 pins the first level's search radius (0: from the sample's extent, as without a route)
+    float h = 0.0f;         // out: the first level's search radius (0: no level ran)
+    float origin[3] = {};   // out: its grid origin (world x, y, z)
+    int cells[3] = {};      // out: its cells per world axis
+    int levels = 0;         // out: levels run
+    int kind0 = -1;         // out: the first level's cell table kind (-1: no level ran)
+    int kinds = 0;          // out: bit t set when a level searched with table kind t (k_sor_knn<t>)
+};
 size_t cloud_lattice_bytes(int XL, int XR, int YL, int YR);
 int filter_cloud_device(FilterArena *a, const float *d_xyz, int64_t n, int mean_k, double std_mul, double normal_radius,
                         const float cam_center[3], int32_t *d_kept_index, float *d_fxyz, float4 *d_normals, int64_t *n_kept,
-                        double stats[4], hipStream_t st, const FilterLattice *pre = nullptr);
+                        double stats[4], hipStream_t st, const FilterLattice *pre = nullptr, FilterRoute *route = nullptr);
 void launch_f64_to_f32x3(const double *src, int64_t n, float *dst, hipStream_t st);
 void launch_pack_filtered16(const double *xyz, const uint8_t *bgr, const int32_t *kept, int64_t m, void *dst16, hipStream_t st);
 
