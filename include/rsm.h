@@ -220,7 +220,10 @@ int rsm_gather_plan(int rank, int world, int root, int n_local, const int *pair_
                     int n_pairs_total, const int64_t *meta_summed, int64_t *offsets, rsm_gather_op *ops, int max_ops,
                     int *n_ops);
 
-/* Tuning / validation knobs.  None of them changes a result (every alternative path is held bit-identical by the tests):
+/* Tuning / validation knobs.  None of them changes a result.  The tests hold every alternative path bit-identical -- the NCC
+ * routing options ("wide_rows", "ncc_mid", "ncc_slide_max") on both sides of every threshold of the row routing -- except
+ * those of "refine_prefill", "refine_skew_prio", "refine_skew_waves" / "refine_skew_waves_alone", "heavy_*", "shared_gpu"
+ * and "filter_low_priority", which no test sets yet:
  *   "ncc_bytes" = 1        the generic byte-wise NCC kernel instead of the dot4 one
  *   "wide_rows" = 0 | 1 | 2 | 3   rows of wide pixels: 0 (default) = chosen per row on the device (k_rg_rows: the sliding window
  *                          sums when the row's widest interval has at most ncc_slide_max candidates and the row holds enough
@@ -316,6 +319,13 @@ int rsm_stage_initial_match(rsm_ctx *ctx, const uint8_t *img_own, const uint8_t 
                             int offset, const rsm_boundary *own, const rsm_boundary *oth,
                             const double *parent /* NULL = lowest level */, int Wp, int Hp,
                             int16_t *disp);
+/* What the last rsm_stage_initial_match on this context decided, per row y < H (H = that call's): wide[y] = pixels that left
+ * the band kernel, mid[y] = pixels whose interval is longer than the effective ncc_mid, widest[y] = the widest interval
+ * (mid and widest stay 0 with wide_rows = 1, which skips that count), route[y] = 0 no wide pixel / 1 the one-workgroup-per-pixel
+ * kernel / 2 the int8 row GEMM / 3 the sliding sums (-1: listed for both); *worklist = wide pixels appended in all, *ties =
+ * pixels handed to the reference-order re-evaluation.  RSM_E_STATE before the first such call, RSM_E_INVALID for another H. */
+int rsm_stage_last_ncc_routes(rsm_ctx *ctx, int H, int32_t *wide, int32_t *mid, int32_t *widest, int32_t *route,
+                              int64_t *worklist, int64_t *ties);
 int rsm_stage_smooth(rsm_ctx *ctx, int16_t *disp, int W, int H, const rsm_boundary *own);
 int rsm_stage_order(rsm_ctx *ctx, int16_t *disp, int W, int H, const rsm_boundary *own);
 int rsm_stage_uniqueness_pass_s16(rsm_ctx *ctx, int16_t *p, const int16_t *q, int W, int H,

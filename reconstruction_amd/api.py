@@ -574,6 +574,18 @@ class Context:
                                                     pp, Wp, Hp, _p(d)))
         return d
 
+    def last_ncc_routes(self, H):
+        """What the last initial_match decided per row (include/rsm.h rsm_stage_last_ncc_routes): dict of int32 arrays
+        wide / mid / widest / route (0 none, 1 workgroup per pixel, 2 int8 row GEMM, 3 sliding sums) and the ints
+        worklist, ties."""
+        out = {k: np.zeros(H, np.int32) for k in ("wide", "mid", "widest", "route")}
+        wl, ti = C.c_int64(), C.c_int64()
+        self._chk(self._lib.rsm_stage_last_ncc_routes(self._h, int(H), _p(out["wide"]), _p(out["mid"]), _p(out["widest"]),
+                                                      _p(out["route"]), C.byref(wl), C.byref(ti)))
+        out["worklist"] = int(wl.value)
+        out["ties"] = int(ti.value)
+        return out
+
     def smooth_constraint(self, disp, own):
         d = np.array(disp, dtype=np.int16, order="C"); H, W = d.shape
         self._chk(self._lib.rsm_stage_smooth(self._h, _p(d), W, H, C.byref(_bd(own))))

@@ -161,6 +161,12 @@ struct rsm_ctx {
     int opt_refine_skew_prio = 0;        // the time-skewed kernel's waves rotate their issue priority every 2^this shader clocks (0: never)
     int opt_refine_skew_uw = 0;          // columns a strip owns; 0: 66 - 2T, all its last level can compute (an even number <= that: A/B)
 
+    // what the last rsm_stage_initial_match's NCC launch decided (rsm_stage_last_ncc_routes): its per-row counters and row
+    // lists (StageArgs::wrow, rsm_dev.h), the worklist length and the tie count; H = 0 until such a call succeeded
+    std::vector<int32_t> ncc_wit_wrow;
+    int ncc_wit_H = 0;
+    int32_t ncc_wit_cnt = 0, ncc_wit_ties = 0;
+
     // profiling
     bool profile = false;
     bool profile_stages = false;
@@ -1411,7 +1417,47 @@ extern "C" int rsm_stage_initial_match(rsm_ctx *c, const uint8_t *img_own, const
         launch_ncc_argmax(a, 1, c->stream);
     }
     t.down(disp, dd, px);
-    return finish(c, t);
+    // the routing witness, copied before the scratch is freed
+    c->ncc_wit_H = 0;
+    std::vector<int32_t> wr(NCC_WROW_INTS((size_t)H));
+    int32_t cnt = 0, ties = 0;
+    t.down(wr.data(), b.wr, wr.size());
+    t.down(&cnt, b.wc, 1);
+    t.down(&ties, b.tc, 1);
+    const int s = finish(c, t);
+    if (s == RSM_OK) {
+        c->ncc_wit_wrow.swap(wr);
+        c->ncc_wit_H = H;
+        c->ncc_wit_cnt = cnt;
+        c->ncc_wit_ties = ties;
+    }
+    return s;
+}
+
+extern "C" int rsm_stage_last_ncc_routes(rsm_ctx *c, int H, int32_t *wide, int32_t *mid, int32_t *widest, int32_t *route,
+                                         int64_t *worklist, int64_t *ties) {
+    if (!c || !wide || !mid || !widest || !route || !worklist || !ties) return RSM_E_INVALID;
+    if (c->ncc_wit_H == 0) return set_err(c, RSM_E_STATE, "no rsm_stage_initial_match has run on this context");
+    if (H != c->ncc_wit_H) return set_err(c, RSM_E_INVALID, "H %d: the last initial match had %d rows", H, c->ncc_wit_H);
+    const int32_t *w = c->ncc_wit_wrow.data();
+    for (int y = 0; y < H; y++) {
+        wide[y] = w[y];
+        mid[y] = w[NCC_WROW_MID(H) + y];
+        widest[y] = w[NCC_WROW_MAX(H) + y];
+        route[y] = w[y] > 0 ? 1 : 0;
+    }
+    for (int which = 0; which < 2; which++) { // list 0: k_ncc_rowgemm, list 1: k_ncc_slide ([0] = count, then the rows)
+        const int32_t *l = w + NCC_WROW_LIST(H, which);
+        const int n = std::min(std::max(l[0], 0), H);
+        for (int i = 0; i < n; i++) {
+            const int y = l[1 + i];
+            if (y < 0 || y >= H) return set_err(c, RSM_E_STATE, "row list %d holds row %d of %d", which, y, H);
+            route[y] = route[y] >= 2 ? -1 : 2 + which; // -1: a row listed twice
+        }
+    }
+    *worklist = c->ncc_wit_cnt;
+    *ties = c->ncc_wit_ties;
+    return RSM_OK;
 }
 
 extern "C" int rsm_stage_smooth(rsm_ctx *c, int16_t *disp, int W, int H, const rsm_boundary *own) {
