@@ -39,7 +39,8 @@ typedef enum rsm_status {
     RSM_E_HIP = -3,               /* HIP runtime error (rsm_last_error() has the text) */
     RSM_E_NOMEM = -4,
     RSM_E_STATE = -5,             /* call order (e.g. run before upload) */
-    RSM_E_COMM = -6               /* RCCL missing or failed (rsm_comm_last_error() has the text) */
+    RSM_E_COMM = -6,              /* RCCL missing or failed (rsm_comm_last_error() has the text) */
+    RSM_W_NOT_CONVERGED = 1       /* rsm_poisson_mesh / rsm_stage_poisson_solve: max_cycles reached above rel_residual; the results are valid */
 } rsm_status;
 
 /* struct Boundary, reconstruction/CManageData.h:10-14 (same field order) */
@@ -493,6 +494,46 @@ int rsm_dedup_cloud(rsm_ctx *ctx, const float *xyz, const float *normals4, int64
 int rsm_dedup_cloud_device(rsm_ctx *ctx, const rsm_point16 *d_points, const float *d_normals4, int64_t n, const rsm_dedup_view *views,
                            int n_pairs, int32_t *d_index, rsm_point16 *d_out_points, float *d_out_normals, int64_t *n_out,
                            int64_t stats[4]);
+
+/* ---- surface from the oriented cloud (where CCloudOptimization::run calls meshlab.bat's "Surface Reconstruction:
+ * Poisson" on bigcloud.ply, .cpp:389-, and filter() calls mesh.bat's PoissonRecon --pointWeight 0 + SurfaceTrimmer) ------------------
+ * Unscreened Poisson reconstruction (Kazhdan, Bolitho, Hoppe 2006) on a dense grid of 2^depth nodes per axis, marching tetrahedra, trim
+ * by the dilated sample occupancy.  Not a bit-parity port of those tools: the method as DESIGN.md 9 (f7) defines it. */
+typedef struct rsm_poisson_params {
+    int depth;            /* 5..9: N = 2^depth nodes per axis */
+    double scale;         /* finite, >= 1: the grid's side over the samples' largest extent (PoissonRecon's --scale, 1.1) */
+    double rel_residual;  /* in (0, 1): the solve stops at ||b - L chi|| / ||b|| <= rel_residual ... */
+    int max_cycles;       /* ... or after max_cycles >= 1 cycles (-> RSM_W_NOT_CONVERGED) */
+    int trim_cells;       /* >= 0: faces survive within this many cells (Chebyshev) of a cell that holds a sample; 0 = no trim */
+} rsm_poisson_params;
+/* stats: [0] valid samples, [1] samples that took no part (non-finite, zero normal), [2] the relative residual reached, [3] cycles used,
+ * [4] iso, [5..7] grid origin, [8] h, [9] N, [10] / [11] vertices / faces before the trim */
+#define RSM_POISSON_STATS 12
+/* n samples in host buffers (xyz n*3 float, normals4 n*4 float: nx, ny, nz, curvature as rsm_mls_cloud returns them).  The mesh stays
+ * with the context until the next call; *n_vertices / *n_faces size the buffers of rsm_poisson_last_mesh.  Returns RSM_OK,
+ * RSM_W_NOT_CONVERGED (a valid mesh from the chi reached) or an error.  No valid sample, or all points equal: an empty mesh, RSM_OK.
+ * RSM_E_INVALID (rsm_last_error names the parameter): depth outside 5..9, scale not finite or < 1, rel_residual not in (0, 1),
+ * max_cycles < 1, trim_cells < 0, n < 0 or above INT32_MAX, a NULL pointer. */
+int rsm_poisson_mesh(rsm_ctx *ctx, const float *xyz, const float *normals4, int64_t n, const rsm_poisson_params *p, int64_t *n_vertices,
+                     int64_t *n_faces, double *stats);
+/* the same on DEVICE buffers, as rsm_mls_cloud_device leaves them (d_out_xyz, d_out_normals) */
+int rsm_poisson_mesh_device(rsm_ctx *ctx, const float *d_xyz, const float *d_normals4, int64_t n, const rsm_poisson_params *p,
+                            int64_t *n_vertices, int64_t *n_faces, double *stats);
+/* copies the last mesh of this context out: xyz 3 * n_vertices float, faces 3 * n_faces int32 (either may be NULL); host / device buffers */
+int rsm_poisson_last_mesh(rsm_ctx *ctx, float *xyz, int32_t *faces);
+int rsm_poisson_last_mesh_device(rsm_ctx *ctx, float *d_xyz, int32_t *d_faces);
+/* stage entry points (host buffers) for the tests.  rhs: samples -> grid = {origin x, y, z, h}, b (N^3 doubles, exact from the fixed-point
+ * splat; the solver reads it rounded to float), occ (N^3 bytes), counts = {valid, not valid}; h = 0: nothing to mesh, b and occ are zero.
+ * solve: b (N^3 floats) -> chi, the residual reached, cycles used, history (optional, max_cycles doubles: the residual after each cycle).
+ * iso_mesh: a caller's chi (N^3 floats), iso, grid and occ (may be NULL with trim_cells = 0) -> the context's last mesh. */
+int rsm_stage_poisson_rhs(rsm_ctx *ctx, const float *xyz, const float *normals4, int64_t n, const rsm_poisson_params *p, double grid[4],
+                          double *b, uint8_t *occ, int64_t counts[2]);
+int rsm_stage_poisson_solve(rsm_ctx *ctx, const float *b, int depth, double rel_residual, int max_cycles, float *chi, double *residual,
+                            int *cycles, double *history);
+int rsm_stage_iso_mesh(rsm_ctx *ctx, const float *chi, int depth, double iso, const double grid[4], const uint8_t *occ, int trim_cells,
+                       int64_t *n_vertices, int64_t *n_faces);
+/* binary little-endian PLY mesh: vertex float x, y, z; face list uchar int vertex_indices (what MeshLab and TextureStitcher read).  Host only. */
+int rsm_write_ply_mesh(const char *path, const float *xyz, int64_t n_vertices, const int32_t *faces, int64_t n_faces);
 
 /* ---- kernel microbenchmark (MDE/s: pixel x candidate NCC evaluations) -------------------- */
 /* Runs the NCC interval-argmax kernel `iters` times on a resident level-sized problem with

@@ -6,5 +6,5 @@ pair-sharding / RCCL cloud gather for multi-GPU runs.
 """
 from .api import (Context, StereoMatching, ManageData, Camera, PairResult, Boundary, NOMATCH, RsmError,  # noqa: F401
                   write_ply, stereo_rectify, run_pairs, match_pairs, match_pairs_multi_gpu, CloudOptimization, host_empty,
-                  write_ply_pointnormal)
+                  write_ply_pointnormal, write_ply_mesh)
 from . import synth  # noqa: F401

@@ -1,4 +1,5 @@
 """python -m reconstruction_amd <config.yml> [--device N] [--out cloud.ply] [--filter] [--mls [--isdelete] [--mls-out bigcloud.ply]]
+                              [--mesh [--mesh-depth 9] [--mesh-trim 4] [--mesh-out bigmesh.ply]]
 
 The command-line shape of the reference's main() (reconstruction/main.cpp:5-23) for the part this package covers:
 CReconstrction::Init (configuration + calibration, CReconstruction.cpp:5-19) -> CStereoMatching::MatchAllLayer
@@ -7,8 +8,10 @@ and normals (--filter; CCloudOptimization.cpp:82-121, on the GPU) -> the merged 
 (implies --filter) the moving-least-squares block of CCloudOptimization::run (CCloudOptimization.cpp:348-389, on the GPU):
 the smoothed, oriented cloud as bigcloud.ply (pcl::PointNormal, savePLYFileBinary), what the mesher reads; --isdelete runs the
 multi-view duplicate deletion before it (CCloudOptimization.cpp:152-346, on the GPU).
-The rest of CCloudOptimization::run (Poisson meshing, texture: external executables; main.cpp:19) is outside this
-package: feed bigcloud.ply to it.
+With --mesh (implies --mls) the surface of that cloud: unscreened Poisson reconstruction on a dense grid and a trim, on the GPU,
+where CCloudOptimization::run calls meshlab.bat's Poisson filter -> bigmesh.ply (not a bit-parity port of that tool: DESIGN.md 9 f7).
+The rest of CCloudOptimization::run (MeshLab's smoothing, texture: external executables; main.cpp:19) is outside this
+package: feed bigcloud.ply or bigmesh.ply to it.
 Needs an MI355X; there is no CPU path.
 """
 from __future__ import annotations
@@ -53,7 +56,16 @@ def main(argv=None) -> int:
     ap.add_argument("--isdelete", action="store_true",
                     help="with --mls: the multi-view duplicate deletion before the MLS (Init's isdelete = true; CCloudOptimization.cpp:"
                          "152-346): one point per surface layer per pixel of the view each point faces best")
+    ap.add_argument("--mesh", action="store_true",
+                    help="after the MLS (implied): the surface of the smoothed cloud by unscreened Poisson reconstruction on a dense grid, "
+                         "marching tetrahedra and a trim, on the GPU -> bigmesh.ply")
+    ap.add_argument("--mesh-depth", type=int, default=9, help="2^depth grid nodes per axis, 5..9 (mesh.bat: --depth 9)")
+    ap.add_argument("--mesh-trim", type=int, default=4,
+                    help="faces survive within this many cells of a cell that holds a point (4 = mesh.bat's --trim 7 at depth 9; 0 = no trim)")
+    ap.add_argument("--mesh-out", default=None, help="path of the mesh (default: bigmesh.ply next to the --out PLY)")
     args = ap.parse_args(argv)
+    if args.mesh:
+        args.mls = True
     if args.isdelete and not args.mls:
         ap.error("--isdelete needs --mls (it selects the points the MLS reads)")
     if args.mls:
@@ -112,6 +124,19 @@ def main(argv=None) -> int:
         write_ply_pointnormal(big, mxyz, mnrm)                     # savePLYFileBinary("tmp\\bigcloud.ply"), .cpp:389
         print("MLS time: %.3f s" % (time.perf_counter() - t1))
         print("%d points -> %s" % (len(mxyz), big))
+    if args.mesh:
+        from . import RsmError, write_ply_mesh
+        t2 = time.perf_counter()
+        try:
+            mv, mf, mst = sink.mesh(depth=args.mesh_depth, trim_cells=args.mesh_trim)
+        except RsmError as e:                                      # e.g. --mesh-depth outside 5..9
+            print(e)
+            return 1
+        mesh_out = args.mesh_out or os.path.join(os.path.dirname(os.path.abspath(out)), "bigmesh.ply")
+        write_ply_mesh(mesh_out, mv, mf)
+        print("Mesh time: %.3f s (%d cycles, residual %.2e%s)" % (time.perf_counter() - t2, mst["cycles"], mst["residual"],
+                                                                  "" if mst["converged"] else ", NOT converged"))
+        print("%d vertices, %d faces -> %s" % (len(mv), len(mf), mesh_out))
     return 0
 
 

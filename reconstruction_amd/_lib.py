@@ -18,6 +18,7 @@ RSM_E_HIP = -3
 RSM_E_NOMEM = -4
 RSM_E_STATE = -5
 RSM_E_COMM = -6
+RSM_W_NOT_CONVERGED = 1   # rsm_poisson_mesh / rsm_stage_poisson_solve: max_cycles reached; the results are valid
 NOMATCH = -10000
 
 
@@ -62,6 +63,14 @@ class MlsParams(C.Structure):
     _fields_ = [("search_radius", C.c_double), ("polynomial_order", C.c_int)]
 
 
+class PoissonParams(C.Structure):
+    """rsm_poisson_params (include/rsm.h)."""
+    _fields_ = [("depth", C.c_int), ("scale", C.c_double), ("rel_residual", C.c_double), ("max_cycles", C.c_int), ("trim_cells", C.c_int)]
+
+
+POISSON_STATS = 12
+
+
 class DedupView(C.Structure):
     """rsm_dedup_view (include/rsm.h): one pair of the rig for the duplicate deletion (host pointers)."""
     _fields_ = [("P", (C.c_double * 12) * 2), ("cam_center", C.c_float * 3), ("bound0", Boundary), ("width", C.c_int),
@@ -95,6 +104,8 @@ EXPORTS = [
     "rsm_gather_clouds", "rsm_gather_counts", "rsm_gather_meta_fill", "rsm_gather_plan", "rsm_comm_create_transport",
     "rsm_filter_cloud", "rsm_filter_last_cloud", "rsm_host_alloc", "rsm_host_free", "rsm_host_register", "rsm_host_unregister",
     "rsm_mls_cloud", "rsm_mls_cloud_device", "rsm_dedup_cloud", "rsm_dedup_cloud_device",
+    "rsm_poisson_mesh", "rsm_poisson_mesh_device", "rsm_poisson_last_mesh", "rsm_poisson_last_mesh_device",
+    "rsm_stage_poisson_rhs", "rsm_stage_poisson_solve", "rsm_stage_iso_mesh", "rsm_write_ply_mesh",
 ]
 
 _lib = None
@@ -136,5 +147,17 @@ def load():
                                     C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.rsm_dedup_cloud_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(DedupView), C.c_int, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    for name in ("rsm_poisson_mesh", "rsm_poisson_mesh_device"):
+        getattr(lib, name).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(PoissonParams), C.POINTER(C.c_int64),
+                                       C.POINTER(C.c_int64), C.c_void_p]
+    lib.rsm_poisson_last_mesh.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rsm_poisson_last_mesh_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rsm_stage_poisson_rhs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(PoissonParams), C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]
+    lib.rsm_stage_poisson_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_void_p, C.POINTER(C.c_double),
+                                            C.POINTER(C.c_int), C.c_void_p]
+    lib.rsm_stage_iso_mesh.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int64),
+                                       C.POINTER(C.c_int64)]
+    lib.rsm_write_ply_mesh.argtypes = [C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]
     _lib = lib
     return lib

@@ -19,7 +19,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from ._lib import Boundary, DedupView, FilterParams, MlsParams, NOMATCH, PairIn, PairOut, RectifyIn, RectifyOut, RsmError  # noqa: F401
+from ._lib import Boundary, DedupView, FilterParams, MlsParams, PoissonParams, NOMATCH, PairIn, PairOut, RectifyIn, RectifyOut, RsmError  # noqa: F401
 
 
 class _Pinned:
@@ -115,6 +115,21 @@ def write_ply_pointnormal(path, xyz, normals):
                  "property float normal_x\nproperty float normal_y\nproperty float normal_z\nproperty float curvature\nend_header\n"
                  % len(xyz)).encode())
         f.write(rec.tobytes())
+
+
+def write_ply_mesh(path, vertices, faces):
+    """The mesh as a binary little-endian PLY (vertex float x y z, face list uchar int vertex_indices: what MeshLab and TextureStitcher
+    read) through the C ABI (rsm_write_ply_mesh; host-only, no GPU needed)."""
+    v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+    f = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+    st = _lib.load().rsm_write_ply_mesh(str(path).encode(), _p(v), C.c_int64(len(v)), _p(f), C.c_int64(len(f)))
+    if st != 0:
+        raise RsmError(st, "rsm_write_ply_mesh(%s)" % path)
+
+
+# the solve's default stopping residual: one decade above the 4.2e-6 the float32 solver reaches at depth 9 (DESIGN.md 9 f7)
+POISSON_REL_RESIDUAL = 4e-5
+POISSON_MAX_CYCLES = 100
 
 
 @dataclass
@@ -512,6 +527,109 @@ class Context:
                                                    C.c_void_p(out_normals_ptr or None), C.byref(m), st))
         del keep
         return int(m.value), self._dedup_stats(st)
+
+    # ---- surface from the oriented cloud: dense-grid Poisson + trim (csrc/k_poisson.hip) ----
+    @staticmethod
+    def _poisson_params(depth, scale, rel_residual, max_cycles, trim_cells):
+        prm = PoissonParams()
+        prm.depth, prm.scale, prm.rel_residual, prm.max_cycles, prm.trim_cells = int(depth), float(scale), float(rel_residual), int(max_cycles), int(trim_cells)
+        return prm
+
+    @staticmethod
+    def _poisson_stats(st, status):
+        return dict(n_valid=int(st[0]), n_invalid=int(st[1]), residual=float(st[2]), cycles=int(st[3]), iso=float(st[4]),
+                    origin=(float(st[5]), float(st[6]), float(st[7])), h=float(st[8]), N=int(st[9]), n_vertices_untrimmed=int(st[10]),
+                    n_faces_untrimmed=int(st[11]), status=int(status), converged=status == 0)
+
+    @staticmethod
+    def _normals4(normals, n):
+        nrm = np.zeros((n, 4), np.float32)
+        if n > 0:
+            r = np.asarray(normals, np.float32).reshape(n, -1)
+            nrm[:, :min(4, r.shape[1])] = r[:, :4]
+        return nrm
+
+    def poisson_last_mesh(self, n_vertices, n_faces):
+        """The context's last mesh on the host: (vertices float32 [nv,3], faces int32 [nf,3])."""
+        v = np.zeros((max(n_vertices, 1), 3), np.float32)
+        f = np.zeros((max(n_faces, 1), 3), np.int32)
+        self._chk(self._lib.rsm_poisson_last_mesh(self._h, _p(v), _p(f)))
+        return v[:n_vertices].copy(), f[:n_faces].copy()
+
+    def poisson_mesh(self, xyz, normals, depth=9, scale=1.1, trim_cells=4, rel_residual=POISSON_REL_RESIDUAL, max_cycles=POISSON_MAX_CYCLES):
+        """Unscreened Poisson reconstruction on a dense 2^depth grid, marching tetrahedra and the occupancy trim, of a host cloud:
+        xyz [n,3] float32 with normals [n,4] or [n,3] (what mls_cloud returns).  Returns (vertices float32 [nv,3], faces int32 [nf,3],
+        stats dict); stats['converged'] is False (status 1) when max_cycles came before rel_residual -- the mesh is that of the
+        chi reached.  Samples that are not finite or have a zero normal take no part (stats['n_invalid'])."""
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        n = len(xyz)
+        nrm = self._normals4(normals, n)
+        nv, nf = C.c_int64(), C.c_int64()
+        st = (C.c_double * _lib.POISSON_STATS)()
+        prm = self._poisson_params(depth, scale, rel_residual, max_cycles, trim_cells)
+        status = self._lib.rsm_poisson_mesh(self._h, _p(xyz), _p(nrm), C.c_int64(n), C.byref(prm), C.byref(nv), C.byref(nf), st)
+        if status < 0:
+            self._chk(status)
+        v, f = self.poisson_last_mesh(int(nv.value), int(nf.value))
+        return v, f, self._poisson_stats(st, status)
+
+    def poisson_mesh_device(self, xyz_ptr, normals_ptr, n, depth=9, scale=1.1, trim_cells=4, rel_residual=POISSON_REL_RESIDUAL,
+                            max_cycles=POISSON_MAX_CYCLES):
+        """rsm_poisson_mesh_device on device buffers (addresses): n float xyz (stride 3) and n float4 normals, as mls_cloud_device leaves
+        them.  The mesh stays with the context: returns (n_vertices, n_faces, stats); poisson_last_mesh[_device] copies it out."""
+        nv, nf = C.c_int64(), C.c_int64()
+        st = (C.c_double * _lib.POISSON_STATS)()
+        prm = self._poisson_params(depth, scale, rel_residual, max_cycles, trim_cells)
+        status = self._lib.rsm_poisson_mesh_device(self._h, C.c_void_p(xyz_ptr or None), C.c_void_p(normals_ptr or None), C.c_int64(n), C.byref(prm),
+                                                   C.byref(nv), C.byref(nf), st)
+        if status < 0:
+            self._chk(status)
+        return int(nv.value), int(nf.value), self._poisson_stats(st, status)
+
+    def poisson_last_mesh_device(self, vertices_ptr, faces_ptr):
+        """Copies the context's last mesh into caller-owned device buffers (addresses; either may be 0)."""
+        self._chk(self._lib.rsm_poisson_last_mesh_device(self._h, C.c_void_p(vertices_ptr or None), C.c_void_p(faces_ptr or None)))
+
+    def poisson_rhs(self, xyz, normals, depth, scale=1.1):
+        """Stage: samples -> (grid (ox, oy, oz, h), b float64 [N,N,N] indexed [k,j,i], occ uint8 [N,N,N], (valid, invalid))."""
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        n = len(xyz)
+        nrm = self._normals4(normals, n)
+        N = 1 << int(depth)
+        grid = np.zeros(4, np.float64)
+        b = np.zeros((N, N, N), np.float64)
+        occ = np.zeros((N, N, N), np.uint8)
+        counts = np.zeros(2, np.int64)
+        prm = self._poisson_params(depth, scale, 0.5, 1, 0)
+        self._chk(self._lib.rsm_stage_poisson_rhs(self._h, _p(xyz), _p(nrm), C.c_int64(n), C.byref(prm), _p(grid), _p(b), _p(occ), _p(counts)))
+        return grid, b, occ, (int(counts[0]), int(counts[1]))
+
+    def poisson_solve(self, b, rel_residual=POISSON_REL_RESIDUAL, max_cycles=POISSON_MAX_CYCLES):
+        """Stage: b [N,N,N] (rounded to float32) -> (chi float32 [N,N,N], residual reached, cycles, status 0 / 1, residual per cycle)."""
+        b = np.ascontiguousarray(b, np.float32)
+        N = b.shape[0]
+        depth = int(N).bit_length() - 1
+        assert b.shape == (N, N, N) and (1 << depth) == N
+        chi = np.zeros_like(b)
+        res, cyc = C.c_double(), C.c_int()
+        hist = np.zeros(max(1, int(max_cycles)), np.float64)
+        status = self._lib.rsm_stage_poisson_solve(self._h, _p(b), depth, float(rel_residual), int(max_cycles), _p(chi), C.byref(res), C.byref(cyc),
+                                                   _p(hist))
+        if status < 0:
+            self._chk(status)
+        return chi, float(res.value), int(cyc.value), int(status), hist[:int(cyc.value)].copy()
+
+    def iso_mesh(self, chi, iso, grid, occ=None, trim_cells=0):
+        """Stage: a caller's chi (float32 [N,N,N]), iso, grid (ox, oy, oz, h) and occ -> (vertices, faces)."""
+        chi = np.ascontiguousarray(chi, np.float32)
+        N = chi.shape[0]
+        depth = int(N).bit_length() - 1
+        grid = np.ascontiguousarray(grid, np.float64).reshape(4)
+        o8 = None if occ is None else _u8(occ)
+        nv, nf = C.c_int64(), C.c_int64()
+        self._chk(self._lib.rsm_stage_iso_mesh(self._h, _p(chi), depth, float(iso), _p(grid), None if o8 is None else _p(o8), int(trim_cells),
+                                               C.byref(nv), C.byref(nf)))
+        return self.poisson_last_mesh(int(nv.value), int(nf.value))
 
     @property
     def n_points(self):
@@ -921,7 +1039,8 @@ class CloudOptimization:
     Init (:40-57: only the per-pair filter's parameters are used), InsertPoint (:59-62), filter(idx) (:64-147: the
     StatisticalOutlierRemoval + NormalEstimation + normal flip of :82-121 on the GPU; the mesh / texture tooling
     after :123 is Windows executables and out of scope), run() (:348-389: MLS over the merged cloud + the normal flip
-    on the GPU; meshing and texturing after :389 are external executables).  `cloud_normals` accumulates what the
+    on the GPU), mesh() (where run() calls the external Poisson mesher after :389: the dense-grid Poisson surface and trim on the GPU;
+    MeshLab's smoothing and the texturing stay external executables).  `cloud_normals` accumulates what the
     reference's global `*cloud_normals += *cloud_normal` (:123) does: per pair (xyz float32 [m,3], normals float32 [m,4])."""
 
     def __init__(self, ctx: Context | None = None, device: int = 0):
@@ -981,3 +1100,13 @@ class CloudOptimization:
         else:
             self.cloud_ms_normals = self._ctx.mls_cloud(xyz, self.m_mls_radius, 1, ref)
         return self.cloud_ms_normals
+
+    def mesh(self, depth=9, scale=1.1, trim_cells=4, rel_residual=POISSON_REL_RESIDUAL, max_cycles=POISSON_MAX_CYCLES):
+        """Where CCloudOptimization::run hands bigcloud.ply to the Poisson mesher (after :389): the surface of cloud_ms_normals, run()'s
+        result, by the dense-grid Poisson reconstruction and trim on the GPU (Context.poisson_mesh).  run() keeps its result on the
+        host, so the host entry point is used.  Stores and returns (vertices float32 [nv,3], faces int32 [nf,3], stats)."""
+        if getattr(self, "cloud_ms_normals", None) is None:
+            raise ValueError("CloudOptimization.mesh: run() first (it meshes run()'s smoothed, oriented cloud)")
+        xyz, nrm = self.cloud_ms_normals[0], self.cloud_ms_normals[1]
+        self.mesh_result = self._ctx.poisson_mesh(xyz, nrm, depth, scale, trim_cells, rel_residual, max_cycles)
+        return self.mesh_result

@@ -119,6 +119,7 @@ struct rsm_ctx {
     rsm_point16 *pack16 = nullptr; // the cloud as 16-byte records / the filter's output, staged for a host download (on first use)
     float *pack_nrm = nullptr;     // ... and the filter's normals
     FilterArena *filt_arena = nullptr; // the cloud filter's scratch (created on first use, grows with the cloud)
+    PoissonMesh pmesh;                 // the last mesh of rsm_poisson_mesh / rsm_stage_iso_mesh (rsm_poisson_last_mesh copies it out)
     int opt_filter_wg_max = 2048;      // rsm_filter_last_cloud: the wave passes' workgroup form while at most this many queries are left (0: never)
     int opt_filter_normals_window = 8; // rsm_filter_last_cloud: the normals' radius search on the pixel lattice while no point needs a wider window than this (0: grid)
     int filt_normals[2]{};             // last rsm_filter_last_cloud: the window the normals used (0: the grid), the widest a point needed (-1: not asked)
@@ -337,6 +338,7 @@ extern "C" void rsm_destroy(rsm_ctx *c) {
     (void)hipStreamSynchronize(c->stream);
     free_workspace(c);
     filter_arena_destroy(c->filt_arena);
+    poisson_mesh_free(&c->pmesh);
     for (auto &e : c->evpool) {
         (void)hipEventDestroy(e.a);
         (void)hipEventDestroy(e.b);
@@ -2170,6 +2172,208 @@ extern "C" int rsm_dedup_cloud(rsm_ctx *c, const float *xyz, const float *normal
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     return RSM_OK;
+}
+
+// ---- dense-grid Poisson surface and trim (k_poisson.hip) -----------------------------------------------------------
+static int poisson_params_ok(rsm_ctx *c, const rsm_poisson_params *p) {
+    if (!p) return set_err(c, RSM_E_INVALID, "poisson: params is NULL");
+    if (p->depth < 5 || p->depth > 9) return set_err(c, RSM_E_INVALID, "poisson: depth %d outside 5..9", p->depth);
+    if (!std::isfinite(p->scale) || p->scale < 1.0) return set_err(c, RSM_E_INVALID, "poisson: scale %g not finite or < 1", p->scale);
+    if (!(p->rel_residual > 0.0 && p->rel_residual < 1.0)) return set_err(c, RSM_E_INVALID, "poisson: rel_residual %g not in (0, 1)", p->rel_residual);
+    if (p->max_cycles < 1) return set_err(c, RSM_E_INVALID, "poisson: max_cycles %d < 1", p->max_cycles);
+    if (p->trim_cells < 0) return set_err(c, RSM_E_INVALID, "poisson: trim_cells %d < 0", p->trim_cells);
+    return RSM_OK;
+}
+static int poisson_n_ok(rsm_ctx *c, int64_t n) {
+    if (n < 0 || n > (int64_t)INT32_MAX) return set_err(c, RSM_E_INVALID, "poisson: n %lld outside 0..INT32_MAX", (long long)n);
+    return RSM_OK;
+}
+static int poisson_fail(rsm_ctx *c, int s, const char *what) {
+    return set_err(c, s, "poisson: %s failed%s%s", what, s == RSM_E_HIP ? ": " : "", s == RSM_E_HIP ? hipGetErrorString(hipGetLastError()) : "");
+}
+
+// the eight steps on device buffers; the mesh lands in c->pmesh
+static int poisson_run(rsm_ctx *c, const float *d_xyz, const float *d_nrm, int64_t n, const rsm_poisson_params *p, int64_t *n_vertices,
+                       int64_t *n_faces, double *stats) {
+    double st[RSM_POISSON_STATS] = {0};
+    *n_vertices = *n_faces = 0;
+    poisson_mesh_free(&c->pmesh);
+    double grid[4];
+    int64_t counts[2];
+    int s = poisson_grid_device(d_xyz, d_nrm, n, p->depth, p->scale, grid, counts, c->stream);
+    if (s != RSM_OK) return poisson_fail(c, s, "bounding box");
+    st[0] = (double)counts[0];
+    st[1] = (double)counts[1];
+    st[9] = (double)(1 << p->depth);
+    int solved = RSM_OK;
+    if (grid[3] > 0.0) {
+        const size_t N3 = (size_t)1 << (3 * p->depth);
+        Tmp T(c);
+        float *b = T.alloc<float>(N3), *chi = T.alloc<float>(N3);
+        uint8_t *occ = T.alloc<uint8_t>(N3);
+        if (!b || !chi || !occ) return set_err(c, RSM_E_NOMEM, "poisson: no device memory for depth %d", p->depth);
+        if ((s = poisson_rhs_device(d_xyz, d_nrm, n, p->depth, grid, b, nullptr, occ, c->stream)) != RSM_OK) return poisson_fail(c, s, "right-hand side");
+        double res = 0.0, iso = 0.0;
+        int cycles = 0;
+        solved = poisson_solve_device(b, p->depth, p->rel_residual, p->max_cycles, chi, &res, &cycles, nullptr, c->stream);
+        if (solved < 0) return poisson_fail(c, solved, "solve");
+        if ((s = poisson_iso_device(d_xyz, d_nrm, n, counts[0], chi, p->depth, grid, &iso, c->stream)) != RSM_OK) return poisson_fail(c, s, "iso-value");
+        int64_t un[2];
+        if ((s = poisson_extract_device(chi, p->depth, iso, grid, occ, p->trim_cells, &c->pmesh, un, c->stream)) != RSM_OK)
+            return poisson_fail(c, s, "extraction");
+        st[2] = res;
+        st[3] = (double)cycles;
+        st[4] = iso;
+        for (int a = 0; a < 4; a++) st[5 + a] = grid[a];
+        st[10] = (double)un[0];
+        st[11] = (double)un[1];
+        if (solved == RSM_W_NOT_CONVERGED) set_err(c, solved, "poisson: residual %g after %d cycles (rel_residual %g)", res, cycles, p->rel_residual);
+    }
+    *n_vertices = c->pmesh.nv;
+    *n_faces = c->pmesh.nf;
+    if (stats) memcpy(stats, st, sizeof st);
+    return solved;
+}
+
+extern "C" int rsm_poisson_mesh_device(rsm_ctx *c, const float *d_xyz, const float *d_normals4, int64_t n, const rsm_poisson_params *p,
+                                       int64_t *n_vertices, int64_t *n_faces, double *stats) {
+    if (!c) return RSM_E_INVALID;
+    int s = poisson_params_ok(c, p);
+    if (s != RSM_OK || (s = poisson_n_ok(c, n)) != RSM_OK) return s;
+    if (!n_vertices || !n_faces || (n > 0 && (!d_xyz || !d_normals4))) return set_err(c, RSM_E_INVALID, "poisson: a NULL pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    return poisson_run(c, d_xyz, d_normals4, n, p, n_vertices, n_faces, stats);
+}
+
+extern "C" int rsm_poisson_mesh(rsm_ctx *c, const float *xyz, const float *normals4, int64_t n, const rsm_poisson_params *p, int64_t *n_vertices,
+                                int64_t *n_faces, double *stats) {
+    if (!c) return RSM_E_INVALID;
+    int s = poisson_params_ok(c, p);
+    if (s != RSM_OK || (s = poisson_n_ok(c, n)) != RSM_OK) return s;
+    if (!n_vertices || !n_faces || (n > 0 && (!xyz || !normals4))) return set_err(c, RSM_E_INVALID, "poisson: a NULL pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    Tmp T(c);
+    float *dx = T.alloc<float>(3 * (size_t)n), *dn = T.alloc<float>(4 * (size_t)n);
+    if (!dx || !dn) return set_err(c, RSM_E_NOMEM, "poisson: no device memory for %lld samples", (long long)n);
+    if (n > 0) {
+        HIPCHK(c, hipMemcpyAsync(dx, xyz, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(dn, normals4, sizeof(float) * 4 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    return poisson_run(c, dx, dn, n, p, n_vertices, n_faces, stats);
+}
+
+extern "C" int rsm_poisson_last_mesh_device(rsm_ctx *c, float *d_xyz, int32_t *d_faces) {
+    if (!c) return RSM_E_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (d_xyz && c->pmesh.nv > 0) HIPCHK(c, hipMemcpyAsync(d_xyz, c->pmesh.d_v, sizeof(float) * 3 * (size_t)c->pmesh.nv, hipMemcpyDeviceToDevice, c->stream));
+    if (d_faces && c->pmesh.nf > 0) HIPCHK(c, hipMemcpyAsync(d_faces, c->pmesh.d_f, sizeof(int32_t) * 3 * (size_t)c->pmesh.nf, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RSM_OK;
+}
+
+extern "C" int rsm_poisson_last_mesh(rsm_ctx *c, float *xyz, int32_t *faces) {
+    if (!c) return RSM_E_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (xyz && c->pmesh.nv > 0) HIPCHK(c, hipMemcpyAsync(xyz, c->pmesh.d_v, sizeof(float) * 3 * (size_t)c->pmesh.nv, hipMemcpyDeviceToHost, c->stream));
+    if (faces && c->pmesh.nf > 0) HIPCHK(c, hipMemcpyAsync(faces, c->pmesh.d_f, sizeof(int32_t) * 3 * (size_t)c->pmesh.nf, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RSM_OK;
+}
+
+extern "C" int rsm_stage_poisson_rhs(rsm_ctx *c, const float *xyz, const float *normals4, int64_t n, const rsm_poisson_params *p, double grid[4],
+                                     double *b, uint8_t *occ, int64_t counts[2]) {
+    if (!c) return RSM_E_INVALID;
+    int s = poisson_params_ok(c, p);
+    if (s != RSM_OK || (s = poisson_n_ok(c, n)) != RSM_OK) return s;
+    if (!grid || !b || !occ || !counts || (n > 0 && (!xyz || !normals4))) return set_err(c, RSM_E_INVALID, "poisson: a NULL pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t N3 = (size_t)1 << (3 * p->depth);
+    Tmp T(c);
+    float *dx = T.alloc<float>(3 * (size_t)n), *dn = T.alloc<float>(4 * (size_t)n);
+    double *db = T.alloc<double>(N3);
+    uint8_t *docc = T.alloc<uint8_t>(N3);
+    if (!dx || !dn || !db || !docc) return set_err(c, RSM_E_NOMEM, "poisson: no device memory");
+    if (n > 0) {
+        HIPCHK(c, hipMemcpyAsync(dx, xyz, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(dn, normals4, sizeof(float) * 4 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    if ((s = poisson_grid_device(dx, dn, n, p->depth, p->scale, grid, counts, c->stream)) != RSM_OK) return poisson_fail(c, s, "bounding box");
+    if (!(grid[3] > 0.0)) {
+        memset(b, 0, sizeof(double) * N3);
+        memset(occ, 0, N3);
+        return RSM_OK;
+    }
+    if ((s = poisson_rhs_device(dx, dn, n, p->depth, grid, nullptr, db, docc, c->stream)) != RSM_OK) return poisson_fail(c, s, "right-hand side");
+    HIPCHK(c, hipMemcpyAsync(b, db, sizeof(double) * N3, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(occ, docc, N3, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RSM_OK;
+}
+
+extern "C" int rsm_stage_poisson_solve(rsm_ctx *c, const float *b, int depth, double rel_residual, int max_cycles, float *chi, double *residual,
+                                       int *cycles, double *history) {
+    if (!c) return RSM_E_INVALID;
+    const rsm_poisson_params p{depth, 1.0, rel_residual, max_cycles, 0};
+    int s = poisson_params_ok(c, &p);
+    if (s != RSM_OK) return s;
+    if (!b || !chi || !residual || !cycles) return set_err(c, RSM_E_INVALID, "poisson: a NULL pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t N3 = (size_t)1 << (3 * depth);
+    Tmp T(c);
+    float *db = T.alloc<float>(N3), *dchi = T.alloc<float>(N3);
+    if (!db || !dchi) return set_err(c, RSM_E_NOMEM, "poisson: no device memory");
+    HIPCHK(c, hipMemcpyAsync(db, b, sizeof(float) * N3, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    s = poisson_solve_device(db, depth, rel_residual, max_cycles, dchi, residual, cycles, history, c->stream);
+    if (s < 0) return poisson_fail(c, s, "solve");
+    HIPCHK(c, hipMemcpyAsync(chi, dchi, sizeof(float) * N3, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return s;
+}
+
+extern "C" int rsm_stage_iso_mesh(rsm_ctx *c, const float *chi, int depth, double iso, const double grid[4], const uint8_t *occ, int trim_cells,
+                                  int64_t *n_vertices, int64_t *n_faces) {
+    if (!c) return RSM_E_INVALID;
+    const rsm_poisson_params p{depth, 1.0, 0.5, 1, trim_cells};
+    int s = poisson_params_ok(c, &p);
+    if (s != RSM_OK) return s;
+    if (!chi || !grid || !n_vertices || !n_faces || (trim_cells > 0 && !occ)) return set_err(c, RSM_E_INVALID, "poisson: a NULL pointer");
+    if (!std::isfinite(iso) || !std::isfinite(grid[0]) || !std::isfinite(grid[1]) || !std::isfinite(grid[2]) || !(grid[3] > 0.0) || !std::isfinite(grid[3]))
+        return set_err(c, RSM_E_INVALID, "poisson: iso or grid not finite, or h <= 0");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t N3 = (size_t)1 << (3 * depth);
+    Tmp T(c);
+    float *dchi = T.alloc<float>(N3);
+    uint8_t *docc = occ ? T.alloc<uint8_t>(N3) : nullptr;
+    if (!dchi || (occ && !docc)) return set_err(c, RSM_E_NOMEM, "poisson: no device memory");
+    HIPCHK(c, hipMemcpyAsync(dchi, chi, sizeof(float) * N3, hipMemcpyHostToDevice, c->stream));
+    if (occ) HIPCHK(c, hipMemcpyAsync(docc, occ, N3, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    int64_t un[2];
+    if ((s = poisson_extract_device(dchi, depth, iso, grid, docc, trim_cells, &c->pmesh, un, c->stream)) != RSM_OK) return poisson_fail(c, s, "extraction");
+    *n_vertices = c->pmesh.nv;
+    *n_faces = c->pmesh.nf;
+    return RSM_OK;
+}
+
+// binary little-endian PLY mesh: what MeshLab and TextureStitcher read
+extern "C" int rsm_write_ply_mesh(const char *path, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf) {
+    if (!path || nv < 0 || nf < 0 || nv > (int64_t)INT32_MAX || nf > (int64_t)INT32_MAX || (nv > 0 && !xyz) || (nf > 0 && !faces)) return RSM_E_INVALID;
+    FILE *fp = fopen(path, "wb");
+    if (!fp) return RSM_E_INVALID;
+    fprintf(fp, "ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n", (int)nv);
+    fprintf(fp, "element face %d\nproperty list uchar int vertex_indices\nend_header\n", (int)nf);
+    if (nv > 0) fwrite(xyz, sizeof(float), 3 * (size_t)nv, fp);
+    const unsigned char three = 3;
+    for (int64_t f = 0; f < nf; f++) {
+        fwrite(&three, 1, 1, fp);
+        fwrite(faces + 3 * f, sizeof(int32_t), 3, fp);
+    }
+    const int ok = ferror(fp) == 0;
+    fclose(fp);
+    return ok ? RSM_OK : RSM_E_INVALID;
 }
 
 // ---- PLY writer (CStereoMatching.cpp:723-729, 754-756) ----------------------------------------------

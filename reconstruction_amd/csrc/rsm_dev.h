@@ -219,3 +219,24 @@ int dedup_cloud_device(FilterArena *a, const float *d_pts, int stride, const flo
                        int32_t *d_index, int64_t *n_out, int64_t stats[4], hipStream_t st);
 // the kept points as rsm_point16 records and their float4 normals (either output may be NULL), what rsm_mls_cloud_device reads
 void launch_dedup_gather(const void *d_rec, const float *d_nrm, const int32_t *d_idx, int64_t m, void *d_orec, float *d_onrm, hipStream_t st);
+
+// dense-grid Poisson surface and trim (k_poisson.hip).  Device buffers: n float xyz (stride 3), n float4 normals.
+struct PoissonMesh { // a library-owned result: nv float xyz, nf int32 x 3
+    float *d_v = nullptr;
+    int32_t *d_f = nullptr;
+    int64_t nv = 0, nf = 0;
+};
+void poisson_mesh_free(PoissonMesh *m);
+// grid = {origin x, y, z, h} (h = 0: no valid sample or all points equal), counts = {valid, not valid}
+int poisson_grid_device(const float *d_xyz, const float *d_nrm4, int64_t n, int depth, double scale, double grid[4], int64_t counts[2], hipStream_t st);
+// splat + right-hand side: b as float (the solver's) and / or as double (exact from the fixed-point sums), occ = N^3 bytes
+int poisson_rhs_device(const float *d_xyz, const float *d_nrm4, int64_t n, int depth, const double grid[4], float *d_b32, double *d_b64, uint8_t *d_occ,
+                       hipStream_t st);
+// RSM_OK, RSM_W_NOT_CONVERGED or an error; history (optional, max_cycles doubles) = the residual after each cycle
+int poisson_solve_device(const float *d_b, int depth, double rel_residual, int max_cycles, float *d_chi, double *residual, int *cycles, double *history,
+                         hipStream_t st);
+int poisson_iso_device(const float *d_xyz, const float *d_nrm4, int64_t n, int64_t n_valid, const float *d_chi, int depth, const double grid[4], double *iso,
+                       hipStream_t st);
+// d_occ may be NULL with trim_cells = 0; untrimmed = {vertices, faces} before the trim
+int poisson_extract_device(const float *d_chi, int depth, double iso, const double grid[4], const uint8_t *d_occ, int trim_cells, PoissonMesh *out,
+                           int64_t untrimmed[2], hipStream_t st);
