@@ -535,6 +535,43 @@ int rsm_stage_iso_mesh(rsm_ctx *ctx, const float *chi, int depth, double iso, co
 /* binary little-endian PLY mesh: vertex float x, y, z; face list uchar int vertex_indices (what MeshLab and TextureStitcher read).  Host only. */
 int rsm_write_ply_mesh(const char *path, const float *xyz, int64_t n_vertices, const int32_t *faces, int64_t n_faces);
 
+/* ---- smoothing and clean-up of the surface (where meshlab.bat goes on after the Poisson filter: script1.mlx's "Laplacian Smooth", then
+ * script2.mlx's "Remove Isolated pieces (wrt Diameter)", "Remove Duplicate Faces", "Remove Zero Area Faces", "Remove Faces from Non
+ * Manifold Edges" -> bigmesh.ply) ------------------------------------------------------------------------------------------------------
+ * Not a bit-parity port of MeshLab / VCG: the rules as DESIGN.md 9 (f8) defines them.  "Close Holes" is not done. */
+#define RSM_MESH_CLEAN_DUPLICATES 1u  /* flags: of the faces with the same three vertices the lowest index stays */
+#define RSM_MESH_CLEAN_ZERO_AREA 2u   /*        faces with a repeated index or without area go */
+#define RSM_MESH_CLEAN_NONMANIFOLD 4u /*        every face on an edge that more than two surviving faces share goes */
+typedef struct rsm_mesh_clean_params {
+    int smooth_steps;        /* >= 0: simultaneous Laplacian steps (script1: 5); 0 = no smoothing */
+    int cotangent;           /* 0 / 1: weights 1 / cotangents clamped at 0 (script1: 1) */
+    int boundary;            /* 1: border vertices move along the border (script1's 1D boundary smoothing); 0: they stay */
+    double min_piece;        /* finite, >= 0: components with a bounding-box diameter below the threshold go; 0 removes nothing */
+    int min_piece_relative;  /* 1: threshold = min_piece * (diameter of the box of all vertices); 0: threshold = min_piece (script2: 42.1253) */
+    unsigned int flags;      /* RSM_MESH_CLEAN_* */
+} rsm_mesh_clean_params;
+/* stats: [0] / [1] vertices / faces in, [2] / [3] out, [4] border vertices (endpoints of an edge of one face) of the input, [5] components,
+ * [6] components removed, [7..10] faces removed as isolated pieces / duplicates / zero area / on non-manifold edges, [11] vertices dropped,
+ * [12] D = the diameter of the box of all (smoothed) vertices, [13] the threshold */
+#define RSM_MESH_CLEAN_STATS 14
+/* nv vertices (xyz nv*3 float) and nf faces (faces nf*3 int32) in host buffers -> the context's last mesh (rsm_poisson_last_mesh copies it
+ * out; *n_vertices / *n_faces size its buffers).  An empty mesh in, or nothing left: an empty mesh, RSM_OK.  RSM_E_INVALID (rsm_last_error
+ * names the cause): a face index outside [0, nv), a coordinate that is not finite, 3 nf >= 2^31, nv above INT32_MAX, a negative count,
+ * smooth_steps < 0, cotangent / boundary / min_piece_relative not 0 or 1, min_piece negative or not finite, an unknown flag, a NULL pointer. */
+int rsm_mesh_clean(rsm_ctx *ctx, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, const rsm_mesh_clean_params *p, int64_t *n_vertices,
+                   int64_t *n_faces, double *stats);
+/* the same on DEVICE buffers */
+int rsm_mesh_clean_device(rsm_ctx *ctx, const float *d_xyz, int64_t nv, const int32_t *d_faces, int64_t nf, const rsm_mesh_clean_params *p,
+                          int64_t *n_vertices, int64_t *n_faces, double *stats);
+/* the same on the context's last mesh where it lies (what rsm_poisson_mesh left): no host round trip; the result replaces it */
+int rsm_mesh_clean_last(rsm_ctx *ctx, const rsm_mesh_clean_params *p, int64_t *n_vertices, int64_t *n_faces, double *stats);
+/* stage entry points (host buffers) for the tests.  smooth: the positions after `steps` steps (out_xyz nv*3 float; connectivity is untouched),
+ * *n_border (may be NULL) = border vertices.  components: labels[f] = the lowest face index of f's component (faces are connected across a
+ * shared edge, not across a shared vertex), -1 for a face with a repeated index; *n_components = the components found. */
+int rsm_stage_mesh_smooth(rsm_ctx *ctx, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, int steps, int cotangent, int boundary,
+                          float *out_xyz, int64_t *n_border);
+int rsm_stage_mesh_components(rsm_ctx *ctx, const int32_t *faces, int64_t nv, int64_t nf, int32_t *labels, int64_t *n_components);
+
 /* ---- kernel microbenchmark (MDE/s: pixel x candidate NCC evaluations) -------------------- */
 /* Runs the NCC interval-argmax kernel `iters` times on a resident level-sized problem with
  * `cands` candidates per pixel and returns average milliseconds per launch. */

@@ -1,5 +1,6 @@
 """python -m reconstruction_amd <config.yml> [--device N] [--out cloud.ply] [--filter] [--mls [--isdelete] [--mls-out bigcloud.ply]]
-                              [--mesh [--mesh-depth 9] [--mesh-trim 4] [--mesh-out bigmesh.ply]]
+                              [--mesh [--mesh-depth 9] [--mesh-trim 4] [--mesh-out bigmesh.ply]
+                               [--mesh-clean [--mesh-smooth 5] [--mesh-min-piece 10%]]]
 
 The command-line shape of the reference's main() (reconstruction/main.cpp:5-23) for the part this package covers:
 CReconstrction::Init (configuration + calibration, CReconstruction.cpp:5-19) -> CStereoMatching::MatchAllLayer
@@ -10,7 +11,9 @@ the smoothed, oriented cloud as bigcloud.ply (pcl::PointNormal, savePLYFileBinar
 multi-view duplicate deletion before it (CCloudOptimization.cpp:152-346, on the GPU).
 With --mesh (implies --mls) the surface of that cloud: unscreened Poisson reconstruction on a dense grid and a trim, on the GPU,
 where CCloudOptimization::run calls meshlab.bat's Poisson filter -> bigmesh.ply (not a bit-parity port of that tool: DESIGN.md 9 f7).
-The rest of CCloudOptimization::run (MeshLab's smoothing, texture: external executables; main.cpp:19) is outside this
+With --mesh-clean (implies --mesh) bigmesh.ply is that surface after meshlab.bat's other filters, on the GPU: Laplacian smoothing
+(script1.mlx) and the removal of isolated pieces, duplicate, zero-area and non-manifold faces (script2.mlx).
+The rest of CCloudOptimization::run (MeshLab's hole closing, texture: external executables; main.cpp:19) is outside this
 package: feed bigcloud.ply or bigmesh.ply to it.
 Needs an MI355X; there is no CPU path.
 """
@@ -63,7 +66,21 @@ def main(argv=None) -> int:
     ap.add_argument("--mesh-trim", type=int, default=4,
                     help="faces survive within this many cells of a cell that holds a point (4 = mesh.bat's --trim 7 at depth 9; 0 = no trim)")
     ap.add_argument("--mesh-out", default=None, help="path of the mesh (default: bigmesh.ply next to the --out PLY)")
+    ap.add_argument("--mesh-clean", action="store_true",
+                    help="after the surface (implied): meshlab.bat's Laplacian smoothing and clean-up (isolated pieces, duplicate, zero-area "
+                         "and non-manifold faces) on the GPU; bigmesh.ply is then the cleaned mesh")
+    ap.add_argument("--mesh-smooth", type=int, default=5, help="with --mesh-clean: smoothing steps (script1.mlx: 5; 0 = none)")
+    ap.add_argument("--mesh-min-piece", default="10%",
+                    help="with --mesh-clean: pieces with a bounding-box diameter below this go; '10%%' = of the whole mesh's diagonal "
+                         "(script2.mlx's ratio), a plain number = a length in scene units")
     args = ap.parse_args(argv)
+    if args.mesh_clean:
+        args.mesh = True
+        piece = args.mesh_min_piece.strip()
+        try:
+            min_piece, relative = (float(piece[:-1]) / 100.0, True) if piece.endswith("%") else (float(piece), False)
+        except ValueError:
+            ap.error("--mesh-min-piece: '%s' is neither a percentage like 10%% nor a length" % piece)
     if args.mesh:
         args.mls = True
     if args.isdelete and not args.mls:
@@ -132,10 +149,21 @@ def main(argv=None) -> int:
         except RsmError as e:                                      # e.g. --mesh-depth outside 5..9
             print(e)
             return 1
+        cst = None
+        if args.mesh_clean:
+            try:
+                mv, mf, cst = sink.clean_mesh(smooth_steps=args.mesh_smooth, min_piece=min_piece, relative=relative)
+            except RsmError as e:                                  # e.g. a negative --mesh-smooth
+                print(e)
+                return 1
         mesh_out = args.mesh_out or os.path.join(os.path.dirname(os.path.abspath(out)), "bigmesh.ply")
         write_ply_mesh(mesh_out, mv, mf)
         print("Mesh time: %.3f s (%d cycles, residual %.2e%s)" % (time.perf_counter() - t2, mst["cycles"], mst["residual"],
                                                                   "" if mst["converged"] else ", NOT converged"))
+        if cst is not None:
+            print("Mesh clean: %d of %d pieces removed (%d faces); %d duplicate, %d zero-area, %d non-manifold faces removed; %d border vertices"
+                  % (cst["components_removed"], cst["components"], cst["removed_isolated"], cst["removed_duplicate"], cst["removed_zero_area"],
+                     cst["removed_nonmanifold"], cst["border_vertices"]))
         print("%d vertices, %d faces -> %s" % (len(mv), len(mf), mesh_out))
     return 0
 

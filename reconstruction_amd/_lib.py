@@ -71,6 +71,16 @@ class PoissonParams(C.Structure):
 POISSON_STATS = 12
 
 
+class MeshCleanParams(C.Structure):
+    """rsm_mesh_clean_params (include/rsm.h)."""
+    _fields_ = [("smooth_steps", C.c_int), ("cotangent", C.c_int), ("boundary", C.c_int), ("min_piece", C.c_double),
+                ("min_piece_relative", C.c_int), ("flags", C.c_uint)]
+
+
+MESH_CLEAN_STATS = 14
+MESH_CLEAN_DUPLICATES, MESH_CLEAN_ZERO_AREA, MESH_CLEAN_NONMANIFOLD = 1, 2, 4
+
+
 class DedupView(C.Structure):
     """rsm_dedup_view (include/rsm.h): one pair of the rig for the duplicate deletion (host pointers)."""
     _fields_ = [("P", (C.c_double * 12) * 2), ("cam_center", C.c_float * 3), ("bound0", Boundary), ("width", C.c_int),
@@ -106,6 +116,7 @@ EXPORTS = [
     "rsm_mls_cloud", "rsm_mls_cloud_device", "rsm_dedup_cloud", "rsm_dedup_cloud_device",
     "rsm_poisson_mesh", "rsm_poisson_mesh_device", "rsm_poisson_last_mesh", "rsm_poisson_last_mesh_device",
     "rsm_stage_poisson_rhs", "rsm_stage_poisson_solve", "rsm_stage_iso_mesh", "rsm_write_ply_mesh",
+    "rsm_mesh_clean", "rsm_mesh_clean_device", "rsm_mesh_clean_last", "rsm_stage_mesh_smooth", "rsm_stage_mesh_components",
 ]
 
 _lib = None
@@ -159,5 +170,12 @@ def load():
     lib.rsm_stage_iso_mesh.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int64),
                                        C.POINTER(C.c_int64)]
     lib.rsm_write_ply_mesh.argtypes = [C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]
+    for name in ("rsm_mesh_clean", "rsm_mesh_clean_device"):
+        getattr(lib, name).argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(MeshCleanParams), C.POINTER(C.c_int64),
+                                       C.POINTER(C.c_int64), C.c_void_p]
+    lib.rsm_mesh_clean_last.argtypes = [C.c_void_p, C.POINTER(MeshCleanParams), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p]
+    lib.rsm_stage_mesh_smooth.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                          C.POINTER(C.c_int64)]
+    lib.rsm_stage_mesh_components.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]
     _lib = lib
     return lib

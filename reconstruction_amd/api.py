@@ -19,7 +19,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from ._lib import Boundary, DedupView, FilterParams, MlsParams, PoissonParams, NOMATCH, PairIn, PairOut, RectifyIn, RectifyOut, RsmError  # noqa: F401
+from ._lib import Boundary, DedupView, FilterParams, MeshCleanParams, MlsParams, PoissonParams, NOMATCH, PairIn, PairOut, RectifyIn, RectifyOut, RsmError  # noqa: F401
 
 
 class _Pinned:
@@ -631,6 +631,85 @@ class Context:
                                                C.byref(nv), C.byref(nf)))
         return self.poisson_last_mesh(int(nv.value), int(nf.value))
 
+    # ---- smoothing and clean-up of the surface: meshlab.bat's script1 / script2 after the Poisson filter (csrc/k_meshclean.hip) ----
+    @staticmethod
+    def _mesh_clean_params(smooth_steps, cotangent, boundary, min_piece, relative, duplicates, zero_area, nonmanifold):
+        prm = MeshCleanParams()
+        prm.smooth_steps, prm.cotangent, prm.boundary = int(smooth_steps), int(bool(cotangent)), int(bool(boundary))
+        prm.min_piece, prm.min_piece_relative = float(min_piece), int(bool(relative))
+        prm.flags = ((_lib.MESH_CLEAN_DUPLICATES if duplicates else 0) | (_lib.MESH_CLEAN_ZERO_AREA if zero_area else 0)
+                     | (_lib.MESH_CLEAN_NONMANIFOLD if nonmanifold else 0))
+        return prm
+
+    @staticmethod
+    def _mesh_clean_stats(st):
+        keys = ("n_vertices_in", "n_faces_in", "n_vertices", "n_faces", "border_vertices", "components", "components_removed", "removed_isolated",
+                "removed_duplicate", "removed_zero_area", "removed_nonmanifold", "vertices_dropped")
+        d = {k: int(st[i]) for i, k in enumerate(keys)}
+        d["diameter"], d["threshold"] = float(st[12]), float(st[13])
+        return d
+
+    @staticmethod
+    def _mesh_arrays(vertices, faces):
+        return np.ascontiguousarray(vertices, np.float32).reshape(-1, 3), np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+
+    def mesh_clean(self, vertices, faces, smooth_steps=5, cotangent=True, boundary=True, min_piece=0.10, relative=True, duplicates=True,
+                   zero_area=True, nonmanifold=True):
+        """What meshlab.bat does to the Poisson surface, on the GPU: script1's Laplacian smoothing (smooth_steps simultaneous steps, cotangent
+        weights clamped at 0, border vertices smoothed along the border), then script2's removal of isolated pieces (components whose
+        bounding-box diameter is below min_piece -- a fraction of the whole mesh's with relative=True, a length otherwise), duplicate
+        faces, zero-area faces and faces on non-manifold edges, and of the vertices no face uses.  vertices [nv,3] float32, faces [nf,3]
+        int32 -> (vertices, faces, stats dict).  The result is the context's last mesh (poisson_last_mesh[_device])."""
+        v, f = self._mesh_arrays(vertices, faces)
+        nv, nf = C.c_int64(), C.c_int64()
+        st = (C.c_double * _lib.MESH_CLEAN_STATS)()
+        prm = self._mesh_clean_params(smooth_steps, cotangent, boundary, min_piece, relative, duplicates, zero_area, nonmanifold)
+        self._chk(self._lib.rsm_mesh_clean(self._h, _p(v), C.c_int64(len(v)), _p(f), C.c_int64(len(f)), C.byref(prm), C.byref(nv), C.byref(nf), st))
+        ov, of = self.poisson_last_mesh(int(nv.value), int(nf.value))
+        return ov, of, self._mesh_clean_stats(st)
+
+    def mesh_clean_device(self, vertices_ptr, n_vertices, faces_ptr, n_faces, **kw):
+        """rsm_mesh_clean_device on device buffers (addresses); keywords as mesh_clean.  Returns (n_vertices, n_faces, stats); the mesh
+        stays with the context (poisson_last_mesh[_device] copies it out)."""
+        nv, nf = C.c_int64(), C.c_int64()
+        st = (C.c_double * _lib.MESH_CLEAN_STATS)()
+        prm = self._mesh_clean_params(**{**dict(smooth_steps=5, cotangent=True, boundary=True, min_piece=0.10, relative=True, duplicates=True,
+                                                zero_area=True, nonmanifold=True), **kw})
+        self._chk(self._lib.rsm_mesh_clean_device(self._h, C.c_void_p(vertices_ptr or None), C.c_int64(n_vertices), C.c_void_p(faces_ptr or None),
+                                                  C.c_int64(n_faces), C.byref(prm), C.byref(nv), C.byref(nf), st))
+        return int(nv.value), int(nf.value), self._mesh_clean_stats(st)
+
+    def mesh_clean_last(self, smooth_steps=5, cotangent=True, boundary=True, min_piece=0.10, relative=True, duplicates=True, zero_area=True,
+                        nonmanifold=True):
+        """mesh_clean of the context's last mesh (what poisson_mesh left) where it lies on the device; the result replaces it.
+        Returns (vertices, faces, stats)."""
+        nv, nf = C.c_int64(), C.c_int64()
+        st = (C.c_double * _lib.MESH_CLEAN_STATS)()
+        prm = self._mesh_clean_params(smooth_steps, cotangent, boundary, min_piece, relative, duplicates, zero_area, nonmanifold)
+        self._chk(self._lib.rsm_mesh_clean_last(self._h, C.byref(prm), C.byref(nv), C.byref(nf), st))
+        ov, of = self.poisson_last_mesh(int(nv.value), int(nf.value))
+        return ov, of, self._mesh_clean_stats(st)
+
+    def mesh_smooth(self, vertices, faces, steps=5, cotangent=True, boundary=True, return_border=False):
+        """Stage: the positions after `steps` smoothing steps (float32 [nv,3]; the faces are untouched); with return_border also the
+        number of border vertices."""
+        v, f = self._mesh_arrays(vertices, faces)
+        out = np.zeros((max(len(v), 1), 3), np.float32)
+        nb = C.c_int64()
+        self._chk(self._lib.rsm_stage_mesh_smooth(self._h, _p(v), C.c_int64(len(v)), _p(f), C.c_int64(len(f)), int(steps), int(bool(cotangent)),
+                                                  int(bool(boundary)), _p(out), C.byref(nb)))
+        out = out[:len(v)].copy()
+        return (out, int(nb.value)) if return_border else out
+
+    def mesh_components(self, faces, n_vertices):
+        """Stage: (labels int32 [nf] = the lowest face index of each face's component, -1 for a face with a repeated index; the number of
+        components).  Faces are connected across a shared edge, not across a shared vertex."""
+        f = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+        lab = np.zeros(max(len(f), 1), np.int32)
+        nc = C.c_int64()
+        self._chk(self._lib.rsm_stage_mesh_components(self._h, _p(f), C.c_int64(int(n_vertices)), C.c_int64(len(f)), _p(lab), C.byref(nc)))
+        return lab[:len(f)].copy(), int(nc.value)
+
     @property
     def n_points(self):
         return self.result_device()[2]
@@ -1039,8 +1118,9 @@ class CloudOptimization:
     Init (:40-57: only the per-pair filter's parameters are used), InsertPoint (:59-62), filter(idx) (:64-147: the
     StatisticalOutlierRemoval + NormalEstimation + normal flip of :82-121 on the GPU; the mesh / texture tooling
     after :123 is Windows executables and out of scope), run() (:348-389: MLS over the merged cloud + the normal flip
-    on the GPU), mesh() (where run() calls the external Poisson mesher after :389: the dense-grid Poisson surface and trim on the GPU;
-    MeshLab's smoothing and the texturing stay external executables).  `cloud_normals` accumulates what the
+    on the GPU), mesh() (where run() calls the external Poisson mesher after :389: the dense-grid Poisson surface and trim on the GPU),
+    clean_mesh() (what meshlab.bat goes on to do: Laplacian smoothing and the removal of isolated pieces and bad faces, on the GPU;
+    its hole closing and the texturing stay external executables).  `cloud_normals` accumulates what the
     reference's global `*cloud_normals += *cloud_normal` (:123) does: per pair (xyz float32 [m,3], normals float32 [m,4])."""
 
     def __init__(self, ctx: Context | None = None, device: int = 0):
@@ -1109,4 +1189,13 @@ class CloudOptimization:
             raise ValueError("CloudOptimization.mesh: run() first (it meshes run()'s smoothed, oriented cloud)")
         xyz, nrm = self.cloud_ms_normals[0], self.cloud_ms_normals[1]
         self.mesh_result = self._ctx.poisson_mesh(xyz, nrm, depth, scale, trim_cells, rel_residual, max_cycles)
+        return self.mesh_result
+
+    def clean_mesh(self, smooth_steps=5, cotangent=True, boundary=True, min_piece=0.10, relative=True, duplicates=True, zero_area=True,
+                   nonmanifold=True):
+        """Where meshlab.bat goes on after its Poisson filter (script1.mlx's Laplacian Smooth, script2.mlx's clean-up -> bigmesh.ply):
+        Context.mesh_clean_last on the mesh mesh() left with the context, without a host round trip.  Replaces mesh_result."""
+        if getattr(self, "mesh_result", None) is None:
+            raise ValueError("CloudOptimization.clean_mesh: mesh() first (it smooths and cleans mesh()'s surface)")
+        self.mesh_result = self._ctx.mesh_clean_last(smooth_steps, cotangent, boundary, min_piece, relative, duplicates, zero_area, nonmanifold)
         return self.mesh_result

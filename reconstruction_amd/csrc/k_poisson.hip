@@ -17,6 +17,7 @@
 // (dot products, the iso-value) runs over a grid that depends on the problem size only, block trees in LDS, then one block over the partials.
 #include "../../include/rsm.h"
 #include "rsm_dev.h"
+#include "mesh_common.h"
 
 #include <string.h>
 
@@ -43,38 +44,10 @@ struct TetTable {
     uint8_t e[16][2][3]; // edge code u << 2 | v
 };
 
-struct DevMem { // scratch of one call
-    std::vector<void *> p;
-    bool ok = true;
-    template <typename T> T *get(size_t n) {
-        void *q = nullptr;
-        if (!ok || hipMalloc(&q, (n ? n : 1) * sizeof(T)) != hipSuccess) {
-            ok = false;
-            return nullptr;
-        }
-        p.push_back(q);
-        return (T *)q;
-    }
-    ~DevMem() {
-        for (void *q : p) (void)hipFree(q);
-    }
-};
-
 #define PCHK(call)                                 \
     do {                                           \
         if ((call) != hipSuccess) return RSM_E_HIP; \
     } while (0)
-
-__device__ __forceinline__ unsigned int f2ord(float f) { // order-preserving map float -> uint
-    const unsigned int u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-static float ord2f(unsigned int u) {
-    const unsigned int v = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
-    float f;
-    memcpy(&f, &v, 4);
-    return f;
-}
 
 __device__ __forceinline__ bool pv_valid(const float *__restrict__ xyz, const float *__restrict__ nrm, int64_t s, double p[3], double nh[3]) {
     const float x = xyz[3 * s], y = xyz[3 * s + 1], z = xyz[3 * s + 2];
@@ -455,7 +428,6 @@ __global__ __launch_bounds__(256) void k_pv_compact_verts(const float *__restric
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
-static inline dim3 blocks_for(size_t n) { return dim3((unsigned)((n + 255) / 256)); }
 static inline unsigned red_blocks(size_t n) { return (unsigned)std::min<size_t>(PV_RED_BLOCKS, (n + 255) / 256); }
 
 template <typename In>

@@ -2358,6 +2358,117 @@ extern "C" int rsm_stage_iso_mesh(rsm_ctx *c, const float *chi, int depth, doubl
     return RSM_OK;
 }
 
+// ---- smoothing and clean-up of the surface (k_meshclean.hip) ------------------------------------------------------------
+static int meshclean_params_ok(rsm_ctx *c, const rsm_mesh_clean_params *p) {
+    if (!p) return set_err(c, RSM_E_INVALID, "mesh_clean: params is NULL");
+    if (p->smooth_steps < 0) return set_err(c, RSM_E_INVALID, "mesh_clean: smooth_steps %d < 0", p->smooth_steps);
+    if (p->cotangent != 0 && p->cotangent != 1) return set_err(c, RSM_E_INVALID, "mesh_clean: cotangent %d not 0 or 1", p->cotangent);
+    if (p->boundary != 0 && p->boundary != 1) return set_err(c, RSM_E_INVALID, "mesh_clean: boundary %d not 0 or 1", p->boundary);
+    if (!std::isfinite(p->min_piece) || p->min_piece < 0.0) return set_err(c, RSM_E_INVALID, "mesh_clean: min_piece %g negative or not finite", p->min_piece);
+    if (p->min_piece_relative != 0 && p->min_piece_relative != 1)
+        return set_err(c, RSM_E_INVALID, "mesh_clean: min_piece_relative %d not 0 or 1", p->min_piece_relative);
+    if (p->flags & ~(RSM_MESH_CLEAN_DUPLICATES | RSM_MESH_CLEAN_ZERO_AREA | RSM_MESH_CLEAN_NONMANIFOLD))
+        return set_err(c, RSM_E_INVALID, "mesh_clean: flags 0x%x has an unknown bit", p->flags);
+    return RSM_OK;
+}
+static int meshclean_counts_ok(rsm_ctx *c, int64_t nv, int64_t nf) {
+    if (nv < 0 || nv > (int64_t)INT32_MAX) return set_err(c, RSM_E_INVALID, "mesh_clean: nv %lld outside 0..INT32_MAX", (long long)nv);
+    if (nf < 0 || 3 * nf >= ((int64_t)1 << 31)) return set_err(c, RSM_E_INVALID, "mesh_clean: nf %lld negative or 3 nf >= 2^31", (long long)nf);
+    return RSM_OK;
+}
+static int meshclean_fail(rsm_ctx *c, int s, int invalid) {
+    if (s == RSM_E_INVALID) return set_err(c, s, invalid == 1 ? "mesh_clean: a face index outside [0, nv)" : "mesh_clean: a coordinate that is not finite");
+    return set_err(c, s, "mesh_clean: failed%s%s", s == RSM_E_HIP ? ": " : "", s == RSM_E_HIP ? hipGetErrorString(hipGetLastError()) : "");
+}
+// d_xyz / d_faces may be c->pmesh's own buffers
+static int meshclean_run(rsm_ctx *c, const float *d_xyz, int64_t nv, const int32_t *d_faces, int64_t nf, const rsm_mesh_clean_params *p, int64_t *n_vertices,
+                         int64_t *n_faces, double *stats) {
+    int invalid = 0;
+    const int s = mesh_clean_device(d_xyz, nv, d_faces, nf, p, &c->pmesh, stats, &invalid, c->stream);
+    if (s != RSM_OK) return meshclean_fail(c, s, invalid);
+    *n_vertices = c->pmesh.nv;
+    *n_faces = c->pmesh.nf;
+    return RSM_OK;
+}
+
+extern "C" int rsm_mesh_clean_device(rsm_ctx *c, const float *d_xyz, int64_t nv, const int32_t *d_faces, int64_t nf, const rsm_mesh_clean_params *p,
+                                     int64_t *n_vertices, int64_t *n_faces, double *stats) {
+    if (!c) return RSM_E_INVALID;
+    int s = meshclean_params_ok(c, p);
+    if (s != RSM_OK || (s = meshclean_counts_ok(c, nv, nf)) != RSM_OK) return s;
+    if (!n_vertices || !n_faces || (nv > 0 && !d_xyz) || (nf > 0 && !d_faces)) return set_err(c, RSM_E_INVALID, "mesh_clean: a NULL pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    return meshclean_run(c, d_xyz, nv, d_faces, nf, p, n_vertices, n_faces, stats);
+}
+
+extern "C" int rsm_mesh_clean(rsm_ctx *c, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, const rsm_mesh_clean_params *p, int64_t *n_vertices,
+                              int64_t *n_faces, double *stats) {
+    if (!c) return RSM_E_INVALID;
+    int s = meshclean_params_ok(c, p);
+    if (s != RSM_OK || (s = meshclean_counts_ok(c, nv, nf)) != RSM_OK) return s;
+    if (!n_vertices || !n_faces || (nv > 0 && !xyz) || (nf > 0 && !faces)) return set_err(c, RSM_E_INVALID, "mesh_clean: a NULL pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    Tmp T(c);
+    float *dv = T.alloc<float>(3 * (size_t)nv);
+    int32_t *df = T.alloc<int32_t>(3 * (size_t)nf);
+    if (!dv || !df) return set_err(c, RSM_E_NOMEM, "mesh_clean: no device memory for %lld vertices, %lld faces", (long long)nv, (long long)nf);
+    if (nv > 0) HIPCHK(c, hipMemcpyAsync(dv, xyz, sizeof(float) * 3 * (size_t)nv, hipMemcpyHostToDevice, c->stream));
+    if (nf > 0) HIPCHK(c, hipMemcpyAsync(df, faces, sizeof(int32_t) * 3 * (size_t)nf, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return meshclean_run(c, dv, nv, df, nf, p, n_vertices, n_faces, stats);
+}
+
+extern "C" int rsm_mesh_clean_last(rsm_ctx *c, const rsm_mesh_clean_params *p, int64_t *n_vertices, int64_t *n_faces, double *stats) {
+    if (!c) return RSM_E_INVALID;
+    const int s = meshclean_params_ok(c, p);
+    if (s != RSM_OK) return s;
+    if (!n_vertices || !n_faces) return set_err(c, RSM_E_INVALID, "mesh_clean: a NULL pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    return meshclean_run(c, c->pmesh.d_v, c->pmesh.nv, c->pmesh.d_f, c->pmesh.nf, p, n_vertices, n_faces, stats);
+}
+
+extern "C" int rsm_stage_mesh_smooth(rsm_ctx *c, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, int steps, int cotangent, int boundary,
+                                     float *out_xyz, int64_t *n_border) {
+    if (!c) return RSM_E_INVALID;
+    const rsm_mesh_clean_params p{steps, cotangent, boundary, 0.0, 0, 0u};
+    int s = meshclean_params_ok(c, &p);
+    if (s != RSM_OK || (s = meshclean_counts_ok(c, nv, nf)) != RSM_OK) return s;
+    if ((nv > 0 && (!xyz || !out_xyz)) || (nf > 0 && !faces)) return set_err(c, RSM_E_INVALID, "mesh_clean: a NULL pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    Tmp T(c);
+    float *dv = T.alloc<float>(3 * (size_t)nv), *dout = T.alloc<float>(3 * (size_t)nv);
+    int32_t *df = T.alloc<int32_t>(3 * (size_t)nf);
+    if (!dv || !dout || !df) return set_err(c, RSM_E_NOMEM, "mesh_clean: no device memory");
+    if (nv > 0) HIPCHK(c, hipMemcpyAsync(dv, xyz, sizeof(float) * 3 * (size_t)nv, hipMemcpyHostToDevice, c->stream));
+    if (nf > 0) HIPCHK(c, hipMemcpyAsync(df, faces, sizeof(int32_t) * 3 * (size_t)nf, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    int invalid = 0;
+    int64_t nb = 0;
+    if ((s = mesh_smooth_device(dv, nv, df, nf, steps, cotangent, boundary, dout, &nb, &invalid, c->stream)) != RSM_OK) return meshclean_fail(c, s, invalid);
+    if (nv > 0) HIPCHK(c, hipMemcpyAsync(out_xyz, dout, sizeof(float) * 3 * (size_t)nv, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (n_border) *n_border = nb;
+    return RSM_OK;
+}
+
+extern "C" int rsm_stage_mesh_components(rsm_ctx *c, const int32_t *faces, int64_t nv, int64_t nf, int32_t *labels, int64_t *n_components) {
+    if (!c) return RSM_E_INVALID;
+    int s = meshclean_counts_ok(c, nv, nf);
+    if (s != RSM_OK) return s;
+    if (!n_components || (nf > 0 && (!faces || !labels))) return set_err(c, RSM_E_INVALID, "mesh_clean: a NULL pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    Tmp T(c);
+    int32_t *df = T.alloc<int32_t>(3 * (size_t)nf), *dl = T.alloc<int32_t>((size_t)nf);
+    if (!df || !dl) return set_err(c, RSM_E_NOMEM, "mesh_clean: no device memory");
+    if (nf > 0) HIPCHK(c, hipMemcpyAsync(df, faces, sizeof(int32_t) * 3 * (size_t)nf, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    int invalid = 0;
+    if ((s = mesh_components_device(df, nv, nf, dl, n_components, &invalid, c->stream)) != RSM_OK) return meshclean_fail(c, s, invalid);
+    if (nf > 0) HIPCHK(c, hipMemcpyAsync(labels, dl, sizeof(int32_t) * (size_t)nf, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RSM_OK;
+}
+
 // binary little-endian PLY mesh: what MeshLab and TextureStitcher read
 extern "C" int rsm_write_ply_mesh(const char *path, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf) {
     if (!path || nv < 0 || nf < 0 || nv > (int64_t)INT32_MAX || nf > (int64_t)INT32_MAX || (nv > 0 && !xyz) || (nf > 0 && !faces)) return RSM_E_INVALID;

@@ -240,3 +240,15 @@ int poisson_iso_device(const float *d_xyz, const float *d_nrm4, int64_t n, int64
 // d_occ may be NULL with trim_cells = 0; untrimmed = {vertices, faces} before the trim
 int poisson_extract_device(const float *d_chi, int depth, double iso, const double grid[4], const uint8_t *d_occ, int trim_cells, PoissonMesh *out,
                            int64_t untrimmed[2], hipStream_t st);
+
+// smoothing and clean-up of a triangle mesh (k_meshclean.hip).  Device buffers: nv float xyz, nf int32 x 3.  RSM_E_INVALID
+// comes with *invalid = 1 (a face index outside [0, nv)) or 2 (a coordinate that is not finite); parameters are the caller's to check.
+struct rsm_mesh_clean_params;
+// d_out may not alias d_v; *n_border = the endpoints of incidence-1 edges
+int mesh_smooth_device(const float *d_v, int64_t nv, const int32_t *d_f, int64_t nf, int steps, int cotangent, int boundary, float *d_out, int64_t *n_border,
+                       int *invalid, hipStream_t st);
+// d_label[f] = the lowest face index of f's component (-1: a face with a repeated index)
+int mesh_components_device(const int32_t *d_f, int64_t nv, int64_t nf, int32_t *d_label, int64_t *n_components, int *invalid, hipStream_t st);
+// the result replaces *out, which may own d_v / d_f (it is freed after the last read); stats: RSM_MESH_CLEAN_STATS doubles, may be NULL
+int mesh_clean_device(const float *d_v, int64_t nv, const int32_t *d_f, int64_t nf, const rsm_mesh_clean_params *p, PoissonMesh *out, double *stats, int *invalid,
+                      hipStream_t st);
