@@ -6,7 +6,8 @@ Test infrastructure only: the package never imports it.  The eight steps:
                     h = side / N; node (i, j, k) at o + (i + 1/2, j + 1/2, k + 1/2) h; linear index i + N (j + N k)
   3 splat           V(node) = sum w n^ (trilinear, 8 nodes; outside the grid dropped); occ(cell floor((p - o) / h), clamped to the grid) = 1
   4 right-hand side b = 1/2 [(Vx(i+1) - Vx(i-1)) + (Vy(j+1) - Vy(j-1)) + (Vz(k+1) - Vz(k-1))], V = 0 outside
-  5 solve           L chi = b, 7-point Laplacian (-6, +1 x 6), chi = 0 outside; scipy's conjugate gradients on -L
+  5 solve           L chi = b, 7-point Laplacian (-6, +1 x 6), chi = 0 outside; scipy's conjugate gradients on -L (solve), the direct
+                    solution by sine transforms (solve_exact), and the library's own V-cycle-preconditioned iteration (vcycle, pcg_history)
   6 iso             mean over the valid samples of the trilinear interpolation of chi
   7 extraction      chi < iso is inside; six Kuhn tetrahedra per cell (axis permutations in lexicographic order, path 000 -> +a -> +a+b -> 111);
                     one vertex per crossed lattice edge (a, direction), in ascending (a, direction); faces in (cell, tetrahedron, triangle)
@@ -147,6 +148,105 @@ def solve(b, rel_residual=1e-10, maxiter=20000):
     return chi, float(np.linalg.norm(b - apply_L(chi)) / bn)
 
 
+def solve_exact(b):
+    """The direct solution of L chi = b, independent of any iterative solver: the 7-point Laplacian with chi = 0 outside is diagonal in
+    the type-I discrete sine transform, eigenvalues sum over the axes of 2 cos(pi m / (N + 1)) - 2, m = 1..N."""
+    from scipy.fft import dstn, idstn
+    b = np.asarray(b, np.float64)
+    N = b.shape[0]
+    lam = 2.0 * np.cos(np.pi * np.arange(1, N + 1) / (N + 1)) - 2.0
+    return idstn(dstn(b, type=1) / (lam[:, None, None] + lam[None, :, None] + lam[None, None, :]), type=1)
+
+
+def laplacian_min_eigenvalue(N):
+    """the eigenvalue of -L closest to 0: ||L^-1 r|| <= ||r|| / this"""
+    return 3.0 * (2.0 - 2.0 * np.cos(np.pi / (N + 1)))
+
+
+# ---- step 5 as the library runs it (k_pv_rbgs, k_pv_stencil, k_pv_restrict, k_pv_prolong_add, poisson_solve_device), operation for
+# operation in the kernels' order; fields in `dtype`, dot products in fp64 ------------------------------------------------------------
+def _nbr_sum(x):
+    P = np.pad(x, 1)
+    return ((P[1:-1, 1:-1, :-2] + P[1:-1, 1:-1, 2:]) + (P[1:-1, :-2, 1:-1] + P[1:-1, 2:, 1:-1])) + (P[:-2, 1:-1, 1:-1] + P[2:, 1:-1, 1:-1])
+
+
+def _stencil(x):
+    return _nbr_sum(x) - x.dtype.type(6.0) * x
+
+
+_colour_masks = {}
+
+
+def _colour(n, colour):
+    if (n, colour) not in _colour_masks:
+        k, j, i = np.indices((n, n, n))
+        _colour_masks[n, colour] = ((i + j + k) & 1) == colour
+    return _colour_masks[n, colour]
+
+
+def _rbgs(x, b, colour):
+    m = _colour(x.shape[0], colour)
+    x[m] = ((_nbr_sum(x) - b) / x.dtype.type(6.0))[m]
+
+
+def vcycle(b, dtype=np.float64):
+    """x = M^-1 b: one V-cycle from x = 0.  Red-black Gauss-Seidel (red, black) down, the residual, coarse right-hand side = 0.5 x the
+    sum of the 8 residuals of a coarse cell (= 4 x their mean: the same stencil at 2h), the coarse cycle, piecewise-constant
+    prolongation added, Gauss-Seidel (black, red) up; at 2^3 eight sweeps (red, black) and eight (black, red)."""
+    b = np.ascontiguousarray(b, dtype)
+    n = b.shape[0]
+    x = np.zeros_like(b)
+    if n == 2:
+        for s in range(16):
+            for c in range(2):
+                _rbgs(x, b, c if s < 8 else 1 - c)
+        return x
+    for c in range(2):
+        _rbgs(x, b, c)
+    r = b - _stencil(x)
+    s = (((r[0::2, 0::2, 0::2] + r[0::2, 0::2, 1::2]) + (r[0::2, 1::2, 0::2] + r[0::2, 1::2, 1::2]))
+         + ((r[1::2, 0::2, 0::2] + r[1::2, 0::2, 1::2]) + (r[1::2, 1::2, 0::2] + r[1::2, 1::2, 1::2])))
+    xc = vcycle(b.dtype.type(0.5) * s, dtype)
+    x += np.repeat(np.repeat(np.repeat(xc, 2, 0), 2, 1), 2, 2)
+    for c in range(2):
+        _rbgs(x, b, 1 - c)
+    return x
+
+
+def _dot64(x, y):
+    return float(np.dot(x.ravel().astype(np.float64), y.ravel().astype(np.float64)))
+
+
+def pcg_history(b, cycles, dtype=np.float64, stop=0.0):
+    """Conjugate gradients preconditioned by vcycle, as poisson_solve_device runs them without its best-iterate bookkeeping: chi from 0,
+    the residual recomputed from chi every cycle, fp64 dot products, the two step lengths rounded to `dtype`.  Returns (the relative
+    residual after every cycle, the last chi); ends after `cycles` cycles or at the first residual <= stop."""
+    b = np.ascontiguousarray(b, dtype)
+    T = b.dtype.type
+    chi = np.zeros_like(b)
+    hist = []
+    bb = _dot64(b, b)
+    if not bb > 0.0:
+        return np.zeros(0), chi
+    bnorm = np.sqrt(bb)
+    r, p, rho_old = b.copy(), None, 0.0
+    for it in range(1, cycles + 1):
+        z = vcycle(r, dtype)
+        rho = _dot64(r, z)
+        p = z if it == 1 else z + T(rho / rho_old) * p
+        q = _stencil(p)
+        pq = _dot64(p, q)
+        if pq == 0.0 or not np.isfinite(rho / pq):
+            break
+        chi = chi + T(rho / pq) * p
+        r = b - _stencil(chi)
+        rho_old = rho
+        hist.append(np.sqrt(_dot64(r, r)) / bnorm)
+        if hist[-1] <= stop:
+            break
+    return np.array(hist), chi
+
+
 def iso_value(chi, p, o, h):
     N = chi.shape[0]
     idx, w, ok = _trilinear(p, o, h, N)
@@ -281,6 +381,207 @@ def sphere_samples(n, seed=1, noise=0.05, cap=False):
         keep = d[:, 2] < -0.3
         xyz, nrm = xyz[keep], nrm[keep]
     return xyz, nrm
+
+
+def _with_normals(xyz, d):
+    nrm = np.zeros((len(xyz), 4), np.float32)
+    nrm[:, :3] = d
+    return np.asarray(xyz, np.float32), nrm
+
+
+TORUS_C = np.array([-300.0, 7.0, -2.5])
+TORUS_R, TORUS_r = 40.0, 15.0
+
+
+def torus_samples(n, seed=2, noise=0.05):
+    """Of n draws, those an area-uniform rejection keeps (about 3/4): noisy samples of the torus around TORUS_C (axis z, R = 40, r = 15)
+    with outward normals.  Away from the sphere's coordinates: x near -300, y and z on both sides of 0."""
+    rng = np.random.default_rng(seed)
+    u, v = rng.uniform(0.0, 2.0 * np.pi, n), rng.uniform(0.0, 2.0 * np.pi, n)
+    keep = rng.uniform(size=n) * (TORUS_R + TORUS_r) <= TORUS_R + TORUS_r * np.cos(v)
+    rr = TORUS_r + noise * rng.normal(size=n)
+    u, v, rr = u[keep], v[keep], rr[keep]
+    d = np.stack([np.cos(v) * np.cos(u), np.cos(v) * np.sin(u), np.sin(v)], 1)
+    ring = np.stack([TORUS_R * np.cos(u), TORUS_R * np.sin(u), np.zeros_like(u)], 1)
+    return _with_normals(TORUS_C + ring + d * rr[:, None], d)
+
+
+def torus_distance(verts):
+    q = np.asarray(verts, np.float64) - TORUS_C
+    return np.abs(np.hypot(np.hypot(q[:, 0], q[:, 1]) - TORUS_R, q[:, 2]) - TORUS_r)
+
+
+TWO_C = np.array([[-20.0, 3.0, -1.0], [-20.0 + 33.6, 3.0 + 44.8, -1.0]])      # 56 apart
+TWO_R = np.array([30.0, 12.0])
+
+
+def two_spheres_samples(n, seed=3, noise=0.05):
+    """n noisy samples of two spheres (radii 30 and 12, centres 56 apart: a gap of 14), shared by area, outward normals"""
+    rng = np.random.default_rng(seed)
+    d = rng.normal(size=(n, 3))
+    d /= np.linalg.norm(d, axis=1)[:, None]
+    which = (rng.uniform(size=n) * (TWO_R ** 2).sum() >= TWO_R[0] ** 2).astype(np.int64)
+    r = TWO_R[which] + noise * rng.normal(size=n)
+    return _with_normals(TWO_C[which] + d * r[:, None], d)
+
+
+def two_spheres_distance(verts):
+    v = np.asarray(verts, np.float64)
+    return np.abs(np.linalg.norm(v[:, None, :] - TWO_C[None], axis=2) - TWO_R).min(1)
+
+
+PLATE_LO, PLATE_HI, PLATE_Z = np.array([-96.0, -40.0]), np.array([32.0, 40.0]), -7.5
+
+
+def plate_samples(n, seed=4):
+    """n samples of the rectangle [-96, 32] x [-40, 40] at z = -7.5 (zero extent along z), normals +z; the first four are its corners,
+    so at scale = 1.0 (side 128, h = 128 / N, all exact in binary) samples lie on the grid box's faces x = o and x = o + N h."""
+    rng = np.random.default_rng(seed)
+    xy = rng.uniform(PLATE_LO, PLATE_HI, size=(n, 2))
+    xy[:4] = [[PLATE_LO[0], PLATE_LO[1]], [PLATE_HI[0], PLATE_LO[1]], [PLATE_LO[0], PLATE_HI[1]], [PLATE_HI[0], PLATE_HI[1]]]
+    xyz = np.concatenate([xy, np.full((n, 1), PLATE_Z)], 1)
+    return _with_normals(xyz, np.tile([0.0, 0.0, 1.0], (n, 1)))
+
+
+def rhs_of(xyz, normals, depth, scale=1.1):
+    """steps 1 to 4 alone: dict p, nh, o, h, b, occ, cnt"""
+    p, nh, ok = valid_samples(xyz, normals)
+    o, h = make_grid(p, depth, scale)
+    V, occ, cnt = splat(p, nh, o, h, depth)
+    return dict(p=p, nh=nh, o=o, h=h, b=rhs(V), occ=occ, cnt=cnt)
+
+
+def rhs_fixed_point_bound(cnt, b_ref):
+    """The bound on |b - b_ref| of a splat that adds llrint(w n^ 2^32): each contribution is off by at most half a unit, 2^-33.  A node's V is
+    off by cnt(node) 2^-33 (cnt = contributions, counted by the restatement), and b = 1/2 (six neighbour values) by 1/2 sum_6 cnt(neighbour)
+    2^-33; the integer differences and their conversion are exact.  The restatement's own fp64 sums round by at most cnt^2 2^-53 per node
+    (partial sums <= cnt), and its three additions and the product by 2^-50 (1 + |b|)."""
+    cnt = np.asarray(cnt, np.float64)
+
+    def six(a):
+        p = np.pad(a, 1)
+        return p[1:-1, 1:-1, :-2] + p[1:-1, 1:-1, 2:] + p[1:-1, :-2, 1:-1] + p[1:-1, 2:, 1:-1] + p[:-2, 1:-1, 1:-1] + p[2:, 1:-1, 1:-1]
+    return 0.5 * six(cnt) * 2.0 ** -33 + 0.5 * six(cnt * cnt) * 2.0 ** -53 + 2.0 ** -50 * (1.0 + np.abs(b_ref))
+
+
+def node_centre_samples(N=32):
+    """Samples exactly on node centres of the grid they define at scale = 1.0 (all but one trilinear weight 0): the nodes of a 2^5 lattice of
+    spacing 2 nearest a sphere of radius 20, at odd offsets from (-200, 0, 100), and two samples that pin the bounding box to 64 a side."""
+    k, j, i = np.indices((N, N, N))
+    q = np.stack([i, j, k], -1).reshape(-1, 3) * 2.0 + 1.0
+    d = q - np.array([33.0, 31.0, 35.0])
+    r = np.linalg.norm(d, axis=1)
+    sel = np.abs(r - 20.0) <= 1.0
+    lo = np.array([-200.0, 0.0, 100.0])
+    xyz = np.concatenate([[lo, lo + 2.0 * N], lo + q[sel]])
+    nrm = np.concatenate([[[-1.0, 0.0, 0.0], [1.0, 0.0, 0.0]], d[sel] / r[sel, None]])
+    return _with_normals(xyz, nrm)
+
+
+def solver_rhs(kind, depth=5):
+    """The right-hand sides the solver is held to: 'sphere' = the noisy sphere's; 'random' = seeded normal values (every frequency);
+    'corners' = zero but for the nodes (0, 0, 0), (N-1, N-1, N-1) and one on an edge of the box (the boundary terms of every kernel)."""
+    N = 1 << depth
+    if kind == "sphere":
+        return rhs_of(*sphere_samples(20000 * 4 ** (depth - 5)), depth)["b"]
+    if kind == "random":
+        return np.random.default_rng(21).normal(size=(N, N, N))
+    b = np.zeros((N, N, N))
+    b[0, 0, 0], b[N - 1, N - 1, N - 1], b[0, N - 1, N // 3] = 1.0, -0.75, 0.5
+    return b
+
+
+FIELD_O, FIELD_H = np.array([-3.5, 7.25, 100.0]), 0.37
+
+
+def lattice_field(kind, N=32):
+    """Constructed fields for the extraction, (chi float32 [N, N, N], iso): 'random' = seeded normal values, the surface runs into every
+    face of the lattice and every tetrahedron case occurs; 'closed' = the same with the outermost node layer forced outside;
+    'tie0' / 'tie1' = integers -2..2 with iso 0 / 1 one of them (t = 0, coincident vertices, zero-area faces)."""
+    if kind in ("random", "closed"):
+        chi = np.random.default_rng(11).normal(size=(N, N, N)).astype(np.float32)
+        iso = 0.1
+        assert not (chi == np.float32(iso)).any()
+        if kind == "closed":
+            chi[[0, -1]] = chi[:, [0, -1]] = chi[:, :, [0, -1]] = 5.0
+        return chi, iso
+    chi = np.random.default_rng(12).integers(-2, 3, size=(N, N, N)).astype(np.float32)
+    return chi, {"tie0": 0.0, "tie1": 1.0}[kind]
+
+
+def edge_ends(keys, N):
+    """the two lattice nodes (x, y, z) of each emitted vertex, from extract's keys = 8 a + direction: (int64 [nv, 3], int64 [nv, 3])"""
+    keys = np.asarray(keys, np.int64)
+    a, d = keys // 8, keys % 8
+    na = np.stack([a % N, (a // N) % N, a // (N * N)], 1)
+    return na, na + DIRS[d]
+
+
+def _undirected_edges(faces, nv):
+    """(int64 [ne, 2] the distinct undirected edges, the number of faces on each)"""
+    f = np.asarray(faces, np.int64)
+    und = np.sort(np.concatenate([f[:, [0, 1]], f[:, [1, 2]], f[:, [2, 0]]]), 1)
+    uk, cnt = np.unique(und[:, 0] * np.int64(nv + 1) + und[:, 1], return_counts=True)     # int64: nv (nv + 1) passes 2^31
+    return np.stack([uk // (nv + 1), uk % (nv + 1)], 1), cnt
+
+
+def boundary_edge_report(verts, faces, keys, N):
+    """The open-border rule of the extraction.  A mesh edge lies in one of the six boundary planes of the node lattice (a coordinate 0 or
+    N - 1) when both its vertices sit on lattice edges whose two nodes are in that plane; such an edge belongs to one tetrahedron
+    face that no second cell shares, and is in one face; every other edge is in two.  Counts by faces per edge and by in / off plane."""
+    na, nb = edge_ends(keys, N)
+    bits = np.zeros(len(keys), np.int64)
+    for c in range(3):
+        for s, val in enumerate((0, N - 1)):
+            bits |= ((na[:, c] == val) & (nb[:, c] == val)).astype(np.int64) << (2 * c + s)
+    e, cnt = _undirected_edges(faces, len(verts))
+    inp = (bits[e[:, 0]] & bits[e[:, 1]]) != 0
+    return dict(once_in_plane=int(((cnt == 1) & inp).sum()), once_off_plane=int(((cnt == 1) & ~inp).sum()),
+                twice_in_plane=int(((cnt == 2) & inp).sum()), twice_off_plane=int(((cnt == 2) & ~inp).sum()),
+                more_than_twice=int((cnt > 2).sum()))
+
+
+def orientation_products(verts, faces, keys, chi32, iso, o, h):
+    """per face: normal . (mean of its three vertices' outside nodes - mean of their inside nodes); > 0 = wound toward growing chi"""
+    chi32 = np.ascontiguousarray(chi32, np.float32)
+    N = chi32.shape[0]
+    na, nb = edge_ends(keys, N)
+    a_in = chi32[na[:, 2], na[:, 1], na[:, 0]] < np.float32(iso)
+    b_in = chi32[nb[:, 2], nb[:, 1], nb[:, 0]] < np.float32(iso)
+    assert (a_in != b_in).all()
+    pos = lambda ijk: np.asarray(o, np.float64) + (ijk + 0.5) * h
+    inside, outside = pos(np.where(a_in[:, None], na, nb)), pos(np.where(a_in[:, None], nb, na))
+    v = np.asarray(verts, np.float64)
+    f = np.asarray(faces, np.int64)
+    n = np.cross(v[f[:, 1]] - v[f[:, 0]], v[f[:, 2]] - v[f[:, 0]])
+    return np.einsum("ij,ij->i", n, outside[f].mean(1) - inside[f].mean(1))
+
+
+def tet_case_counts(chi32, iso):
+    """int64 [6, 16]: how many cells put tetrahedron t (PERMS order) into case m (bit v: corner v inside)"""
+    ins = np.ascontiguousarray(chi32, np.float32) < np.float32(iso)
+    out = np.zeros((6, 16), np.int64)
+    corner_of = lambda c: ins[(c >> 2) & 1:, (c >> 1) & 1:, c & 1:][:ins.shape[0] - 1, :ins.shape[1] - 1, :ins.shape[2] - 1]
+    for ti, perm in enumerate(PERMS):
+        corner = [0, 1 << perm[0], (1 << perm[0]) | (1 << perm[1]), 7]
+        m = sum(corner_of(corner[v]).astype(np.int64) << v for v in range(4))
+        out[ti] = np.bincount(m.ravel(), minlength=16)
+    return out
+
+
+def components(faces, nv):
+    """the number of edge-connected components of the faces"""
+    import scipy.sparse as sp
+    from scipy.sparse.csgraph import connected_components
+    f = np.asarray(faces, np.int64)
+    he = np.concatenate([f[:, [0, 1]], f[:, [1, 2]], f[:, [2, 0]]])
+    owner = np.tile(np.arange(len(f)), 3)
+    und = np.sort(he, 1)
+    key = und[:, 0] * np.int64(nv + 1) + und[:, 1]
+    order = np.argsort(key, kind="stable")
+    same = key[order][1:] == key[order][:-1]
+    g = sp.coo_matrix((np.ones(same.sum()), (owner[order][1:][same], owner[order][:-1][same])), shape=(len(f), len(f)))
+    return int(connected_components(g, directed=False)[0])
 
 
 def manifold_report(verts, faces):

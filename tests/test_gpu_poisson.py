@@ -115,26 +115,24 @@ def test_extraction_equals_the_restatement(ctx, depth, n, cap):
 
 
 # ---- 5: right-hand side ----------------------------------------------------------------------------------------------------------------
+def check_rhs(ctx, R, xyz, nrm, depth, scale, label):
+    """The GPU's step 1 to 4 (ctx.poisson_rhs) against the restatement's (R: its o, h, occ, cnt, b): grid, counts and occ equal, b within
+    pr.rhs_fixed_point_bound node by node (the derivation is there).  Returns the GPU's (grid, b, occ)."""
+    grid, b, occ, counts = ctx.poisson_rhs(xyz, nrm, depth, scale)
+    assert np.array_equal(grid, np.array([R["o"][0], R["o"][1], R["o"][2], R["h"]])) and counts == (len(xyz), 0)
+    assert np.array_equal(occ, R["occ"])
+    bound = pr.rhs_fixed_point_bound(R["cnt"], R["b"])
+    err = np.abs(b - R["b"])
+    print("%s: max |b - b_ref| %.3e, max bound %.3e, max err / bound %.3f" % (label, err.max(), bound.max(), (err / bound).max()))
+    assert (err <= bound).all()
+    return grid, b, occ
+
+
 @pytest.mark.parametrize("cap", [False, True])
 @pytest.mark.parametrize("depth,n", CASES)
 def test_rhs_within_the_fixed_point_bound(ctx, depth, n, cap):
-    """The splat adds llrint(w n^ 2^32): each contribution is off by at most half a unit, 2^-33.  A node's V is off by cnt(node) 2^-33
-    (cnt = contributions, counted by the restatement), and b = 1/2 (six neighbour values) by 1/2 sum_6 cnt(neighbour) 2^-33; the integer
-    differences and their conversion are exact.  The restatement's own fp64 sums round by at most cnt^2 2^-53 per node (partial sums <=
-    cnt), and its three additions and the product by 2^-50 (1 + |b|)."""
     R = ref(depth, n, cap)
-    grid, b, occ, counts = ctx.poisson_rhs(R["xyz"], R["nrm"], depth)
-    assert np.array_equal(grid, grid_of(R)) and counts == (len(R["xyz"]), 0)
-    assert np.array_equal(occ, R["occ"])
-    cnt = R["cnt"].astype(np.float64)
-
-    def six(a):
-        p = np.pad(a, 1)
-        return p[1:-1, 1:-1, :-2] + p[1:-1, 1:-1, 2:] + p[1:-1, :-2, 1:-1] + p[1:-1, 2:, 1:-1] + p[:-2, 1:-1, 1:-1] + p[2:, 1:-1, 1:-1]
-    bound = 0.5 * six(cnt) * 2.0 ** -33 + 0.5 * six(cnt * cnt) * 2.0 ** -53 + 2.0 ** -50 * (1.0 + np.abs(R["b"]))
-    err = np.abs(b - R["b"])
-    print("depth %d cap %d: max |b - b_ref| %.3e, max bound %.3e, max err / bound %.3f" % (depth, cap, err.max(), bound.max(), (err / bound).max()))
-    assert (err <= bound).all()
+    check_rhs(ctx, R, R["xyz"], R["nrm"], depth, 1.1, "depth %d cap %d" % (depth, cap))
 
 
 # ---- the field -------------------------------------------------------------------------------------------------------------------------

@@ -128,3 +128,104 @@ def test_restatement_ignores_invalid_samples_and_handles_empty_input():
     assert len(E["verts"]) == 0 and len(E["faces"]) == 0
     E = pr.reconstruct(np.tile(xyz[:1], (10, 1)), nrm[:10], 5)
     assert len(E["verts"]) == 0 and len(E["faces"]) == 0
+
+
+# ---- the restatement held to what tests/test_gpu_poisson_stages.py then asks of the GPU ---------------------------------------------------
+OPEN_OK = dict(index_out_of_range=0, repeated_index=0, directed_edge_twice=0)
+RHS_KINDS = ["sphere", "random", "corners"]
+
+
+@pytest.mark.parametrize("kind", RHS_KINDS)
+def test_direct_solution_solves_and_agrees_with_conjugate_gradients(kind):
+    b = pr.solver_rhs(kind)
+    x = pr.solve_exact(b)
+    res = np.linalg.norm(b - pr.apply_L(x)) / np.linalg.norm(b)
+    cg, _ = pr.solve(b, 1e-10)
+    gap = np.abs(cg - x).max() / (x.max() - x.min())
+    print("%s: direct solution residual %.2e, against conjugate gradients at 1e-10: %.2e of range" % (kind, res, gap))
+    assert res < 1e-12 and gap <= 1e-8
+
+
+def test_vcycle_is_a_symmetric_operator():
+    rng = np.random.default_rng(5)
+    r1, r2 = rng.normal(size=(16, 16, 16)), rng.normal(size=(16, 16, 16))
+    a, b = np.vdot(pr.vcycle(r1), r2), np.vdot(r1, pr.vcycle(r2))
+    print("<M r1, r2> = %.15e, <r1, M r2> = %.15e" % (a, b))
+    assert abs(a - b) <= 1e-12 * abs(a)
+    assert np.vdot(pr.vcycle(r1), r1) < 0.0         # and, like L, negative
+
+
+@pytest.mark.parametrize("kind", RHS_KINDS)
+def test_preconditioned_history_falls_monotonically_to_the_default(kind):
+    """The error bound: chi - chi_exact = L^-1 (L chi - b), and ||L^-1|| is 1 / the smallest eigenvalue of -L."""
+    b = pr.solver_rhs(kind)
+    hist, chi = pr.pcg_history(b, 14, np.float64, stop=4e-5)
+    print("%s: fp64 history %s" % (kind, " ".join("%.3e" % v for v in hist)))
+    assert hist[-1] <= 4e-5 and len(hist) <= 12 and (np.diff(hist) < 0).all()
+    err = np.linalg.norm(chi - pr.solve_exact(b))
+    assert err <= hist[-1] * np.linalg.norm(b) / pr.laplacian_min_eigenvalue(b.shape[0])
+
+
+def check_open_mesh(chi, iso, v, f, keys, orientation):
+    """the conditions of an extraction whose surface may run into the lattice's border"""
+    N = chi.shape[0]
+    rep = pr.manifold_report(v, f)
+    assert {k: rep[k] for k in OPEN_OK} == OPEN_OK and rep["unused_vertices"] == 0
+    br = pr.boundary_edge_report(v, f, keys, N)
+    assert br["once_off_plane"] == 0 and br["twice_in_plane"] == 0 and br["more_than_twice"] == 0
+    if orientation:
+        assert len(np.unique(v, axis=0)) == len(v)
+        assert pr.orientation_products(v, f, keys, chi, iso, pr.FIELD_O, pr.FIELD_H).min() > 0.0
+    return rep, br
+
+
+def test_random_field_extraction_open_border_orientation_and_every_case():
+    chi, iso = pr.lattice_field("random")
+    v, f, keys = pr.extract(chi, iso, pr.FIELD_O, pr.FIELD_H)
+    rep, br = check_open_mesh(chi, iso, v, f, keys, True)
+    cc = pr.tet_case_counts(chi, iso)
+    print("random field: %d vertices, %d faces, %s; cases per tetrahedron min %d max %d" % (len(v), len(f), br, cc[:, 1:15].min(), cc[:, 1:15].max()))
+    assert br["once_in_plane"] > 1000 and br["twice_off_plane"] > 100000
+    assert (cc[:, 1:15] > 0).all()
+    assert len(f) == (cc * np.array([len(c) for c in pr.tet_cases()])).sum()
+
+
+def test_closed_random_field_is_closed():
+    chi, iso = pr.lattice_field("closed")
+    v, f, keys = pr.extract(chi, iso, pr.FIELD_O, pr.FIELD_H)
+    rep, br = check_open_mesh(chi, iso, v, f, keys, True)
+    assert rep["edge_without_opposite"] == 0 and rep["edges_not_in_two_faces"] == 0 and br["once_in_plane"] == 0
+
+
+@pytest.mark.parametrize("kind", ["tie0", "tie1"])
+def test_ties_keep_the_connectivity(kind):
+    """chi == iso on a node is outside, t = 0: every crossed edge of that node puts its vertex on the node.  Connectivity is by lattice
+    edge and does not see it; orientation of the slivers is rounding's, not asserted."""
+    chi, iso = pr.lattice_field(kind)
+    assert (chi == np.float32(iso)).sum() > 1000
+    v, f, keys = pr.extract(chi, iso, pr.FIELD_O, pr.FIELD_H)
+    check_open_mesh(chi, iso, v, f, keys, False)
+    a, b, c = (v[f[:, q]].astype(np.float64) for q in range(3))
+    zero = (np.linalg.norm(np.cross(b - a, c - a), axis=1) == 0.0).sum()
+    print("%s: %d vertices (%d distinct), %d faces, %d of zero area" % (kind, len(v), len(np.unique(v, axis=0)), len(f), zero))
+    assert len(np.unique(v, axis=0)) < len(v) and zero > 0
+
+
+def test_restatement_torus_two_spheres_and_plate():
+    closed = dict(index_out_of_range=0, repeated_index=0, directed_edge_twice=0, edge_without_opposite=0, edges_not_in_two_faces=0,
+                  unused_vertices=0)
+    R = pr.reconstruct(*pr.torus_samples(30000), 5)
+    rep = pr.manifold_report(R["verts"], R["faces"])
+    print("torus: %d faces, %s, distance max %.3f h" % (len(R["faces"]), rep, pr.torus_distance(R["verts"]).max() / R["h"]))
+    assert rep == dict(closed, euler=0) and pr.components(R["faces"], len(R["verts"])) == 1
+    R = pr.reconstruct(*pr.two_spheres_samples(20000), 5)
+    rep = pr.manifold_report(R["verts"], R["faces"])
+    print("two spheres: %d faces, %s, distance max %.3f h" % (len(R["faces"]), rep, pr.two_spheres_distance(R["verts"]).max() / R["h"]))
+    assert rep == dict(closed, euler=4) and pr.components(R["faces"], len(R["verts"])) == 2
+    R = pr.reconstruct(*pr.plate_samples(20000), 5, scale=1.0)
+    assert ((R["p"] - R["o"]) / R["h"]).max() == 32.0 and ((R["p"] - R["o"]) / R["h"]).min() == 0.0
+    rep = pr.manifold_report(R["verts"], R["faces"])
+    br = pr.boundary_edge_report(R["verts"], R["faces"], R["keys"], 32)
+    print("plate: %d faces, %s" % (len(R["faces"]), br))
+    assert {k: rep[k] for k in OPEN_OK} == OPEN_OK
+    assert br["once_in_plane"] > 50 and br["once_off_plane"] == 0 and br["more_than_twice"] == 0
