@@ -572,6 +572,50 @@ int rsm_stage_mesh_smooth(rsm_ctx *ctx, const float *xyz, int64_t nv, const int3
                           float *out_xyz, int64_t *n_border);
 int rsm_stage_mesh_components(rsm_ctx *ctx, const int32_t *faces, int64_t nv, int64_t nf, int32_t *labels, int64_t *n_components);
 
+/* ---- colours of the final mesh from the rig's views (where CCloudOptimization::run hands tmp\bigmesh.ply and scans.txt to TextureStitcher,
+ * .cpp:394-397; the scans are the per-view meshes filter() colours through texture_color, .cpp:127-143, :400-421) ------------------------
+ * Not a bit-parity port of TextureStitcher (no source in the reference tree): the rules as DESIGN.md 9 (f9) defines them.  Its seam removal
+ * by gradient stitching is not done.  n_pairs records of rsm_dedup_view give V = 2 n_pairs views, numbered in scans.txt's
+ * order: every pair's view 0, then every pair's view 1 (v = k * n_pairs + i).  bound0 and cam_center are ignored -- the centre is
+ * -M^-1 p4 of P in fp64 -- and a mask may be NULL: all 255.
+ * A vertex is visible in a view when it lies in front of it (q2 > 0), its texture_color pixel is inside the image with mask 255, its
+ * normal (the sum of its faces' normals, fp64) makes cos > min_cos with the direction to the view's centre, and the view's depth buffer of
+ * the mesh holds nothing at that pixel or a depth within depth_eps behind which the vertex does not lie.
+ * Option "meshcolor_big_box" (rsm_set_option, 1 .. 2^20, default 4096): a (face, view) item whose bounding box holds more pixels is
+ * rasterised by a workgroup instead of one thread -- the same result either way. */
+typedef struct rsm_mesh_color_params {
+    int mode;          /* 0: the colour of the visible view of largest cos (ties: the lowest view); 1: the cos-weighted blend of the visible views */
+    double min_cos;    /* in [-1, 1): views at a cos not above it do not see the vertex (0.2) */
+    double depth_eps;  /* finite, >= 0, a length in scene units: the slack of the depth test (CloudOptimization: twice the Poisson grid step) */
+} rsm_mesh_color_params;
+/* stats: [0] vertices, [1] vertices coloured (at least one visible view), [2] vertices without a normal, [3] the sum of visible views over
+ * the vertices, [4] (face, view) items drawn, [5] of them in the big-box tier */
+#define RSM_MESH_COLOR_STATS 6
+/* host buffers: xyz nv*3 float, faces nf*3 int32 -> rgb nv*3 bytes (red, green, blue; (127, 127, 127) where no view sees the vertex),
+ * best_view nv int32 (-1 there; may be NULL).  An empty mesh: nothing written, RSM_OK.  RSM_E_INVALID (rsm_last_error names the cause): a
+ * NULL pointer, n_pairs < 1 with nv > 0, mode outside 0..1, min_cos outside [-1, 1), depth_eps negative or not finite, a face index outside
+ * [0, nv), a coordinate that is not finite, width / height < 1, a singular P, 3 nf >= 2^31, nv above INT32_MAX, a negative count. */
+int rsm_mesh_color(rsm_ctx *ctx, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, const rsm_dedup_view *views, int n_pairs,
+                   const rsm_mesh_color_params *p, uint8_t *rgb, int32_t *best_view, double *stats);
+/* the same on DEVICE buffers (xyz, faces, rgb, best_view); the views' images stay host pointers, as in rsm_dedup_cloud_device */
+int rsm_mesh_color_device(rsm_ctx *ctx, const float *d_xyz, int64_t nv, const int32_t *d_faces, int64_t nf, const rsm_dedup_view *views, int n_pairs,
+                          const rsm_mesh_color_params *p, uint8_t *d_rgb, int32_t *d_best_view, double *stats);
+/* the same on the context's last mesh where it lies (what rsm_poisson_mesh / rsm_mesh_clean left): the mesh is untouched, the colours stay
+ * with the context until the mesh changes; rsm_mesh_last_colors copies them out (rgb 3 * n_vertices bytes, best_view n_vertices int32;
+ * either may be NULL; RSM_E_STATE when the last mesh has no colours) */
+int rsm_mesh_color_last(rsm_ctx *ctx, const rsm_dedup_view *views, int n_pairs, const rsm_mesh_color_params *p, double *stats);
+int rsm_mesh_last_colors(rsm_ctx *ctx, uint8_t *rgb, int32_t *best_view);
+/* stage entry points (host buffers) for the tests.  texture_color (.cpp:400-421) over n points: q = R p + T with R, T the float casts of
+ * P12's columns, pixel = ROUND of the float quotients, rgb = the BGR image's pixel as red, green, blue, (127, 127, 127) outside the image
+ * or where the quotient is not finite; no test of the depth's sign -- also what MyPlyIo::ReadAndWrite does to mesh_trimmer.ply.
+ * mesh_depth: one view's depth buffer, width * height uint32: the largest float32 bit pattern of the inverse depth drawn at each pixel. */
+int rsm_texture_color(rsm_ctx *ctx, const float *xyz, int64_t n, const double P12[12], const uint8_t *image, int width, int height, uint8_t *rgb);
+int rsm_stage_mesh_depth(rsm_ctx *ctx, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, const double P12[12], int width, int height,
+                         uint32_t *wbuf);
+/* binary little-endian PLY: vertex float x, y, z, uchar red, green, blue; face list uchar int vertex_indices (MyPlyIo's property order,
+ * my_ply_interface.cpp:35-50).  Host only. */
+int rsm_write_ply_mesh_color(const char *path, const float *xyz, int64_t n_vertices, const int32_t *faces, int64_t n_faces, const uint8_t *rgb);
+
 /* ---- kernel microbenchmark (MDE/s: pixel x candidate NCC evaluations) -------------------- */
 /* Runs the NCC interval-argmax kernel `iters` times on a resident level-sized problem with
  * `cands` candidates per pixel and returns average milliseconds per launch. */

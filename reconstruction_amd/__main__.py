@@ -1,6 +1,7 @@
 """python -m reconstruction_amd <config.yml> [--device N] [--out cloud.ply] [--filter] [--mls [--isdelete] [--mls-out bigcloud.ply]]
                               [--mesh [--mesh-depth 9] [--mesh-trim 4] [--mesh-out bigmesh.ply]
-                               [--mesh-clean [--mesh-smooth 5] [--mesh-min-piece 10%]]]
+                               [--mesh-clean [--mesh-smooth 5] [--mesh-min-piece 10%]]
+                               [--mesh-color [--mesh-color-mode blend] [--mesh-color-min-cos 0.2] [--mesh-color-eps LENGTH]]]
 
 The command-line shape of the reference's main() (reconstruction/main.cpp:5-23) for the part this package covers:
 CReconstrction::Init (configuration + calibration, CReconstruction.cpp:5-19) -> CStereoMatching::MatchAllLayer
@@ -13,8 +14,11 @@ With --mesh (implies --mls) the surface of that cloud: unscreened Poisson recons
 where CCloudOptimization::run calls meshlab.bat's Poisson filter -> bigmesh.ply (not a bit-parity port of that tool: DESIGN.md 9 f7).
 With --mesh-clean (implies --mesh) bigmesh.ply is that surface after meshlab.bat's other filters, on the GPU: Laplacian smoothing
 (script1.mlx) and the removal of isolated pieces, duplicate, zero-area and non-manifold faces (script2.mlx).
-The rest of CCloudOptimization::run (MeshLab's hole closing, texture: external executables; main.cpp:19) is outside this
-package: feed bigcloud.ply or bigmesh.ply to it.
+With --mesh-color (implies --mesh) the mesh's vertices are coloured from every camera's rectified image, on the GPU, where
+CCloudOptimization::run calls TextureStitcher (visibility by a depth buffer per view, the best view or a cos-weighted blend; DESIGN.md 9
+f9): the coloured mesh goes to the configuration's outfilename, where TextureStitcher's --out goes, and the cloud PLY to <name>_cloud.ply.
+The rest of CCloudOptimization::run (MeshLab's hole closing, TextureStitcher's seam removal: external executables; main.cpp:19) is
+outside this package: feed bigcloud.ply or bigmesh.ply to it.
 Needs an MI355X; there is no CPU path.
 """
 from __future__ import annotations
@@ -73,7 +77,19 @@ def main(argv=None) -> int:
     ap.add_argument("--mesh-min-piece", default="10%",
                     help="with --mesh-clean: pieces with a bounding-box diameter below this go; '10%%' = of the whole mesh's diagonal "
                          "(script2.mlx's ratio), a plain number = a length in scene units")
+    ap.add_argument("--mesh-color", action="store_true",
+                    help="after the surface (implied; after --mesh-clean when given): colour the mesh's vertices from the rectified views on the "
+                         "GPU, where the reference calls TextureStitcher.  The coloured PLY goes to the configuration's outfilename (TextureStitcher's "
+                         "--out), which is also --out's default: without --out the cloud PLY then goes to <name>_cloud.ply")
+    ap.add_argument("--mesh-color-mode", choices=("best", "blend"), default="blend",
+                    help="with --mesh-color: the colour of the best-facing visible view, or the cos-weighted blend of all visible views")
+    ap.add_argument("--mesh-color-min-cos", type=float, default=0.2,
+                    help="with --mesh-color: a view sees a vertex only at a cosine above this between its normal and the direction to the camera")
+    ap.add_argument("--mesh-color-eps", type=float, default=None,
+                    help="with --mesh-color: the depth test's slack in scene units (default: twice the Poisson grid step)")
     args = ap.parse_args(argv)
+    if args.mesh_color:
+        args.mesh = True
     if args.mesh_clean:
         args.mesh = True
         piece = args.mesh_min_piece.strip()
@@ -122,6 +138,11 @@ def main(argv=None) -> int:
     # the configuration's outfilename already carries its extension ("%s%d.ply", BatchProcess/main.cpp:56)
     name = data.outfilename or "cloud"
     out = args.out or (name if name.lower().endswith(".ply") else name + ".ply")
+    color_out = None
+    if args.mesh_color:                       # TextureStitcher's --out is the configuration's outfilename: the cloud steps aside
+        color_out = name if name.lower().endswith(".ply") else name + ".ply"
+        if args.out is None:
+            out = color_out[:-4] + "_cloud.ply"
     write_ply(out, xyz, bgr, normals if args.filter else None)
     print("%d points -> %s" % (len(xyz), out))
     if args.mls:
@@ -165,6 +186,16 @@ def main(argv=None) -> int:
                   % (cst["components_removed"], cst["components"], cst["removed_isolated"], cst["removed_duplicate"], cst["removed_zero_area"],
                      cst["removed_nonmanifold"], cst["border_vertices"]))
         print("%d vertices, %d faces -> %s" % (len(mv), len(mf), mesh_out))
+        if args.mesh_color:
+            try:
+                rgb, _, kst = sink.color_mesh(mode=1 if args.mesh_color_mode == "blend" else 0, min_cos=args.mesh_color_min_cos,
+                                              depth_eps=args.mesh_color_eps)
+            except (RsmError, ValueError) as e:                    # pre-rectified input (no P), --mesh-color-min-cos outside [-1, 1)
+                print(e)
+                return 1
+            write_ply_mesh(color_out, mv, mf, rgb)
+            print("Mesh colour: %d of %d vertices coloured from %d views (%d without a normal) -> %s"
+                  % (kst["coloured"], kst["n_vertices"], 2 * len(data.cam), kst["no_normal"], color_out))
     return 0
 
 

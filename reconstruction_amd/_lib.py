@@ -81,6 +81,14 @@ MESH_CLEAN_STATS = 14
 MESH_CLEAN_DUPLICATES, MESH_CLEAN_ZERO_AREA, MESH_CLEAN_NONMANIFOLD = 1, 2, 4
 
 
+class MeshColorParams(C.Structure):
+    """rsm_mesh_color_params (include/rsm.h)."""
+    _fields_ = [("mode", C.c_int), ("min_cos", C.c_double), ("depth_eps", C.c_double)]
+
+
+MESH_COLOR_STATS = 6
+
+
 class DedupView(C.Structure):
     """rsm_dedup_view (include/rsm.h): one pair of the rig for the duplicate deletion (host pointers)."""
     _fields_ = [("P", (C.c_double * 12) * 2), ("cam_center", C.c_float * 3), ("bound0", Boundary), ("width", C.c_int),
@@ -117,6 +125,8 @@ EXPORTS = [
     "rsm_poisson_mesh", "rsm_poisson_mesh_device", "rsm_poisson_last_mesh", "rsm_poisson_last_mesh_device",
     "rsm_stage_poisson_rhs", "rsm_stage_poisson_solve", "rsm_stage_iso_mesh", "rsm_write_ply_mesh",
     "rsm_mesh_clean", "rsm_mesh_clean_device", "rsm_mesh_clean_last", "rsm_stage_mesh_smooth", "rsm_stage_mesh_components",
+    "rsm_mesh_color", "rsm_mesh_color_device", "rsm_mesh_color_last", "rsm_mesh_last_colors", "rsm_texture_color", "rsm_stage_mesh_depth",
+    "rsm_write_ply_mesh_color",
 ]
 
 _lib = None
@@ -177,5 +187,13 @@ def load():
     lib.rsm_stage_mesh_smooth.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                           C.POINTER(C.c_int64)]
     lib.rsm_stage_mesh_components.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]
+    for name in ("rsm_mesh_color", "rsm_mesh_color_device"):
+        getattr(lib, name).argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(DedupView), C.c_int,
+                                       C.POINTER(MeshColorParams), C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rsm_mesh_color_last.argtypes = [C.c_void_p, C.POINTER(DedupView), C.c_int, C.POINTER(MeshColorParams), C.c_void_p]
+    lib.rsm_mesh_last_colors.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.rsm_texture_color.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    lib.rsm_stage_mesh_depth.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+    lib.rsm_write_ply_mesh_color.argtypes = [C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
     _lib = lib
     return lib

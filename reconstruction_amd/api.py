@@ -19,7 +19,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from . import _lib
-from ._lib import Boundary, DedupView, FilterParams, MeshCleanParams, MlsParams, PoissonParams, NOMATCH, PairIn, PairOut, RectifyIn, RectifyOut, RsmError  # noqa: F401
+from ._lib import Boundary, DedupView, FilterParams, MeshCleanParams, MeshColorParams, MlsParams, PoissonParams, NOMATCH, PairIn, PairOut, RectifyIn, RectifyOut, RsmError  # noqa: F401
 
 
 class _Pinned:
@@ -117,11 +117,20 @@ def write_ply_pointnormal(path, xyz, normals):
         f.write(rec.tobytes())
 
 
-def write_ply_mesh(path, vertices, faces):
+def write_ply_mesh(path, vertices, faces, rgb=None):
     """The mesh as a binary little-endian PLY (vertex float x y z, face list uchar int vertex_indices: what MeshLab and TextureStitcher
-    read) through the C ABI (rsm_write_ply_mesh; host-only, no GPU needed)."""
+    read) through the C ABI (rsm_write_ply_mesh; host-only, no GPU needed).  With rgb (uint8 [nv,3]: red, green, blue) every vertex also
+    carries uchar red green blue, MyPlyIo's property order (my_ply_interface.cpp:35-50; rsm_write_ply_mesh_color)."""
     v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
     f = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+    if rgb is not None:
+        c = np.ascontiguousarray(rgb, np.uint8).reshape(-1, 3)
+        if len(c) != len(v):
+            raise ValueError("write_ply_mesh: %d colours for %d vertices" % (len(c), len(v)))
+        st = _lib.load().rsm_write_ply_mesh_color(str(path).encode(), _p(v), C.c_int64(len(v)), _p(f), C.c_int64(len(f)), _p(c))
+        if st != 0:
+            raise RsmError(st, "rsm_write_ply_mesh_color(%s)" % path)
+        return
     st = _lib.load().rsm_write_ply_mesh(str(path).encode(), _p(v), C.c_int64(len(v)), _p(f), C.c_int64(len(f)))
     if st != 0:
         raise RsmError(st, "rsm_write_ply_mesh(%s)" % path)
@@ -710,6 +719,103 @@ class Context:
         self._chk(self._lib.rsm_stage_mesh_components(self._h, _p(f), C.c_int64(int(n_vertices)), C.c_int64(len(f)), _p(lab), C.byref(nc)))
         return lab[:len(f)].copy(), int(nc.value)
 
+    # ---- colours of the mesh from the rig's views, where run() calls TextureStitcher (csrc/k_meshcolor.hip) ----
+    @staticmethod
+    def mesh_color_views(cams):
+        """rsm_dedup_view per pair from cam[i][0..1] (Camera objects: P, image and, optionally, mask) as the colouring reads them: bound and
+        CamCenter are not used, a mask of None means all 255.  Returns (ctypes array, arrays to keep alive during the call)."""
+        views = (DedupView * max(1, len(cams)))()
+        keep = []
+        for i, pair in enumerate(cams):
+            v = views[i]
+            shape = None
+            for k in range(2):
+                v.P[k][:] = np.asarray(pair[k].P, np.float64).reshape(3, 4).ravel().tolist()
+                img = _u8(pair[k].image)
+                msk = None if pair[k].mask is None else _u8(pair[k].mask)
+                if img.ndim != 3 or img.shape[2] != 3 or (msk is not None and msk.shape != img.shape[:2]) or (shape is not None and img.shape[:2] != shape):
+                    raise ValueError("mesh_color: pair %d view %d: image %s / mask %s do not form one rectified pair"
+                                     % (i, k, img.shape, None if msk is None else msk.shape))
+                shape = img.shape[:2]
+                keep += [img, msk]
+                v.image[k], v.mask[k] = img.ctypes.data, (None if msk is None else msk.ctypes.data)
+            v.height, v.width = shape
+        return views, keep
+
+    @staticmethod
+    def _mesh_color_params(mode, min_cos, depth_eps):
+        prm = MeshColorParams()
+        prm.mode, prm.min_cos, prm.depth_eps = int(mode), float(min_cos), float(depth_eps)
+        return prm
+
+    @staticmethod
+    def _mesh_color_stats(st):
+        keys = ("n_vertices", "coloured", "no_normal", "visible_views", "items_drawn", "items_big_box")
+        return {k: int(st[i]) for i, k in enumerate(keys)}
+
+    def mesh_color(self, vertices, faces, cams, depth_eps, mode=1, min_cos=0.2):
+        """Colours of a host mesh from the views of cams (m_ImageData.cam: per pair two cameras with P, image, mask), where
+        CCloudOptimization::run calls TextureStitcher.  The views are numbered every pair's view 0, then every pair's view 1.  A vertex is
+        visible in a view when it is in front of it, projects (texture_color's pixel) inside the image onto mask 255, its normal makes
+        cos > min_cos with the direction to the camera centre, and the view's depth buffer of the mesh holds no surface more than
+        depth_eps (scene units) in front of it.  mode 0: the colour of the visible view of largest cos; 1: the cos-weighted blend.
+        Returns (rgb uint8 [nv,3]: red, green, blue, (127, 127, 127) where no view sees the vertex; best_view int32 [nv], -1 there;
+        stats dict)."""
+        v, f = self._mesh_arrays(vertices, faces)
+        views, keep = self.mesh_color_views(cams)
+        rgb = np.zeros((max(len(v), 1), 3), np.uint8)
+        best = np.zeros(max(len(v), 1), np.int32)
+        st = (C.c_double * _lib.MESH_COLOR_STATS)()
+        prm = self._mesh_color_params(mode, min_cos, depth_eps)
+        self._chk(self._lib.rsm_mesh_color(self._h, _p(v), C.c_int64(len(v)), _p(f), C.c_int64(len(f)), views, C.c_int(len(cams)), C.byref(prm),
+                                           _p(rgb), _p(best), st))
+        del keep
+        return rgb[:len(v)].copy(), best[:len(v)].copy(), self._mesh_color_stats(st)
+
+    def mesh_color_device(self, vertices_ptr, n_vertices, faces_ptr, n_faces, cams, rgb_ptr, best_view_ptr, depth_eps, mode=1, min_cos=0.2):
+        """rsm_mesh_color_device on device buffers (addresses; best_view_ptr may be 0); the views' images stay on the host.  Returns stats."""
+        views, keep = self.mesh_color_views(cams)
+        st = (C.c_double * _lib.MESH_COLOR_STATS)()
+        prm = self._mesh_color_params(mode, min_cos, depth_eps)
+        self._chk(self._lib.rsm_mesh_color_device(self._h, C.c_void_p(vertices_ptr or None), C.c_int64(n_vertices), C.c_void_p(faces_ptr or None),
+                                                  C.c_int64(n_faces), views, C.c_int(len(cams)), C.byref(prm), C.c_void_p(rgb_ptr or None),
+                                                  C.c_void_p(best_view_ptr or None), st))
+        del keep
+        return self._mesh_color_stats(st)
+
+    def mesh_color_last(self, cams, depth_eps, mode=1, min_cos=0.2):
+        """mesh_color of the context's last mesh (what poisson_mesh / mesh_clean left) where it lies on the device; the mesh is untouched.
+        Returns (rgb, best_view, stats)."""
+        views, keep = self.mesh_color_views(cams)
+        st = (C.c_double * _lib.MESH_COLOR_STATS)()
+        prm = self._mesh_color_params(mode, min_cos, depth_eps)
+        self._chk(self._lib.rsm_mesh_color_last(self._h, views, C.c_int(len(cams)), C.byref(prm), st))
+        del keep
+        nv = int(st[0])
+        rgb = np.zeros((max(nv, 1), 3), np.uint8)
+        best = np.zeros(max(nv, 1), np.int32)
+        self._chk(self._lib.rsm_mesh_last_colors(self._h, _p(rgb), _p(best)))
+        return rgb[:nv].copy(), best[:nv].copy(), self._mesh_color_stats(st)
+
+    def texture_color(self, xyz, P, image):
+        """Stage: texture_color (CCloudOptimization.cpp:400-421) of xyz [n,3] float32 against one view (P 3x4, image BGR uint8 [H,W,3]):
+        rgb uint8 [n,3], (127, 127, 127) outside the image."""
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        P = np.ascontiguousarray(P, np.float64).reshape(12)
+        img = _u8(image)
+        rgb = np.zeros((max(len(xyz), 1), 3), np.uint8)
+        self._chk(self._lib.rsm_texture_color(self._h, _p(xyz), C.c_int64(len(xyz)), _p(P), _p(img), int(img.shape[1]), int(img.shape[0]), _p(rgb)))
+        return rgb[:len(xyz)].copy()
+
+    def mesh_depth(self, vertices, faces, P, width, height):
+        """Stage: one view's depth buffer of the mesh, uint32 [height,width]: the largest float32 bit pattern of the inverse depth drawn at
+        each pixel centre (0: nothing drawn)."""
+        v, f = self._mesh_arrays(vertices, faces)
+        P = np.ascontiguousarray(P, np.float64).reshape(12)
+        w = np.zeros((max(int(height), 1), max(int(width), 1)), np.uint32)
+        self._chk(self._lib.rsm_stage_mesh_depth(self._h, _p(v), C.c_int64(len(v)), _p(f), C.c_int64(len(f)), _p(P), int(width), int(height), _p(w)))
+        return w
+
     @property
     def n_points(self):
         return self.result_device()[2]
@@ -1120,7 +1226,8 @@ class CloudOptimization:
     after :123 is Windows executables and out of scope), run() (:348-389: MLS over the merged cloud + the normal flip
     on the GPU), mesh() (where run() calls the external Poisson mesher after :389: the dense-grid Poisson surface and trim on the GPU),
     clean_mesh() (what meshlab.bat goes on to do: Laplacian smoothing and the removal of isolated pieces and bad faces, on the GPU;
-    its hole closing and the texturing stay external executables).  `cloud_normals` accumulates what the
+    its hole closing stays an external executable), color_mesh() (where run() ends with TextureStitcher: the mesh's vertices coloured
+    from every camera's rectified image, on the GPU; the tool's seam removal is not done).  `cloud_normals` accumulates what the
     reference's global `*cloud_normals += *cloud_normal` (:123) does: per pair (xyz float32 [m,3], normals float32 [m,4])."""
 
     def __init__(self, ctx: Context | None = None, device: int = 0):
@@ -1189,6 +1296,8 @@ class CloudOptimization:
             raise ValueError("CloudOptimization.mesh: run() first (it meshes run()'s smoothed, oriented cloud)")
         xyz, nrm = self.cloud_ms_normals[0], self.cloud_ms_normals[1]
         self.mesh_result = self._ctx.poisson_mesh(xyz, nrm, depth, scale, trim_cells, rel_residual, max_cycles)
+        self.mesh_grid_step = self.mesh_result[2]["h"]
+        self.mesh_colors = None
         return self.mesh_result
 
     def clean_mesh(self, smooth_steps=5, cotangent=True, boundary=True, min_piece=0.10, relative=True, duplicates=True, zero_area=True,
@@ -1198,4 +1307,22 @@ class CloudOptimization:
         if getattr(self, "mesh_result", None) is None:
             raise ValueError("CloudOptimization.clean_mesh: mesh() first (it smooths and cleans mesh()'s surface)")
         self.mesh_result = self._ctx.mesh_clean_last(smooth_steps, cotangent, boundary, min_piece, relative, duplicates, zero_area, nonmanifold)
+        self.mesh_colors = None
         return self.mesh_result
+
+    def color_mesh(self, mode=1, min_cos=0.2, depth_eps=None):
+        """Where CCloudOptimization::run calls TextureStitcher on bigmesh.ply (:394-397): the colours of mesh_result's vertices from every
+        camera's rectified image (Context.mesh_color_last on the mesh mesh() / clean_mesh() left with the context; the mesh itself is
+        untouched).  depth_eps defaults to twice the Poisson grid step.  Stores and returns
+        mesh_colors = (rgb uint8 [nv,3], best_view int32 [nv], stats)."""
+        if getattr(self, "mesh_result", None) is None:
+            raise ValueError("CloudOptimization.color_mesh: mesh() first (it colours mesh()'s surface)")
+        cams = self.m_ImageData.cam
+        if any(c.P is None or c.image is None for pair in cams for c in pair[:2]):
+            raise ValueError("CloudOptimization.color_mesh: the mesh colouring (where CCloudOptimization::run calls TextureStitcher, "
+                             "CCloudOptimization.cpp:394-397) needs every camera's P and image, as Rectify leaves them; pre-rectified input "
+                             "carries no P")
+        if depth_eps is None:
+            depth_eps = 2.0 * self.mesh_grid_step
+        self.mesh_colors = self._ctx.mesh_color_last(cams, depth_eps, mode, min_cos)
+        return self.mesh_colors

@@ -495,14 +495,11 @@ static int smooth(DevMem &M, const Tables &T, const float *d_in, size_t nv, cons
                   const float **d_res, hipStream_t st) {
     *d_res = d_in;
     if (steps <= 0 || nv == 0 || nf == 0) return RSM_OK;
-    const size_t n = 3 * nf;
-    uint32_t *k0 = M.get<uint32_t>(n), *k1 = M.get<uint32_t>(n), *v0 = M.get<uint32_t>(n), *corner = M.get<uint32_t>(n), *row = M.get<uint32_t>(nv + 1);
+    uint32_t *corner = nullptr, *row = nullptr;
+    const int s = mesh_corner_lists_device(M, d_f, nv, nf, &row, &corner, st);
+    if (s != RSM_OK) return s;
     float *buf[2] = {M.get<float>(3 * nv), M.get<float>(3 * nv)};
     if (!M.ok) return RSM_E_NOMEM;
-    hipLaunchKernelGGL(k_mc_corner_keys, blocks_for(nf), dim3(256), 0, st, d_f, nf, (uint32_t)nv, k0, v0);
-    const int s = sort_pairs(M, k0, k1, v0, corner, n, bits_of((u64)nv), st);
-    if (s != RSM_OK) return s;
-    hipLaunchKernelGGL(k_mc_row_starts, blocks_for(nv + 1), dim3(256), 0, st, (const uint32_t *)k1, n, nv, row);
     const float *src = d_in;
     for (int it = 0; it < steps; it++) {
         float *dst = buf[it & 1];
@@ -525,6 +522,27 @@ static int finish(hipStream_t st) {
 }
 
 } // namespace
+
+int mesh_validate_device(const float *d_v, int64_t nv, const int32_t *d_f, int64_t nf, int *invalid, hipStream_t st) {
+    DevMem M;
+    Tables T;
+    return validate(M, T, d_v, (size_t)nv, d_f, (size_t)nf, invalid, st);
+}
+
+int mesh_corner_lists_device(DevMem &M, const int32_t *d_f, size_t nv, size_t nf, uint32_t **row, uint32_t **corner, hipStream_t st) {
+    const size_t n = 3 * nf;
+    uint32_t *k0 = M.get<uint32_t>(n), *k1 = M.get<uint32_t>(n), *v0 = M.get<uint32_t>(n);
+    *corner = M.get<uint32_t>(n);
+    *row = M.get<uint32_t>(nv + 1);
+    if (!M.ok) return RSM_E_NOMEM;
+    if (nf > 0) {
+        hipLaunchKernelGGL(k_mc_corner_keys, blocks_for(nf), dim3(256), 0, st, d_f, nf, (uint32_t)nv, k0, v0);
+        const int s = sort_pairs(M, k0, k1, v0, *corner, n, bits_of((u64)nv), st);
+        if (s != RSM_OK) return s;
+    }
+    hipLaunchKernelGGL(k_mc_row_starts, blocks_for(nv + 1), dim3(256), 0, st, (const uint32_t *)k1, n, nv, *row);
+    return RSM_OK;
+}
 
 int mesh_smooth_device(const float *d_v, int64_t nv_, const int32_t *d_f, int64_t nf_, int steps, int cotangent, int boundary, float *d_out, int64_t *n_border,
                        int *invalid, hipStream_t st) {

@@ -120,6 +120,11 @@ struct rsm_ctx {
     float *pack_nrm = nullptr;     // ... and the filter's normals
     FilterArena *filt_arena = nullptr; // the cloud filter's scratch (created on first use, grows with the cloud)
     PoissonMesh pmesh;                 // the last mesh of rsm_poisson_mesh / rsm_stage_iso_mesh (rsm_poisson_last_mesh copies it out)
+    uint8_t *mcol_rgb = nullptr;       // rsm_mesh_color_last's colours of that mesh (rsm_mesh_last_colors copies them out) ...
+    int32_t *mcol_best = nullptr;      // ... and best views
+    const float *mcol_of = nullptr;    // the vertex buffer they belong to, and its vertex count: a later mesh has no colours
+    int64_t mcol_nv = 0;
+    long long opt_meshcolor_big_box = 4096; // rsm_mesh_color: a (face, view) bounding box of more pixels is strided by a block, not walked by one thread
     int opt_filter_wg_max = 2048;      // rsm_filter_last_cloud: the wave passes' workgroup form while at most this many queries are left (0: never)
     int opt_filter_normals_window = 8; // rsm_filter_last_cloud: the normals' radius search on the pixel lattice while no point needs a wider window than this (0: grid)
     int filt_normals[2]{};             // last rsm_filter_last_cloud: the window the normals used (0: the grid), the widest a point needed (-1: not asked)
@@ -339,6 +344,8 @@ extern "C" void rsm_destroy(rsm_ctx *c) {
     free_workspace(c);
     filter_arena_destroy(c->filt_arena);
     poisson_mesh_free(&c->pmesh);
+    if (c->mcol_rgb) (void)hipFree(c->mcol_rgb);
+    if (c->mcol_best) (void)hipFree(c->mcol_best);
     for (auto &e : c->evpool) {
         (void)hipEventDestroy(e.a);
         (void)hipEventDestroy(e.b);
@@ -564,6 +571,7 @@ extern "C" int rsm_set_option(rsm_ctx *c, const char *name, long long value) {
         uint32_t bits = (uint32_t)value;
         memcpy(&c->filt_route.h0, &bits, sizeof bits);
     }
+    else if (!strcmp(name, "meshcolor_big_box")) c->opt_meshcolor_big_box = std::max(1LL, std::min(value, 1LL << 20));
     else if (!strcmp(name, "refine_skew_waves_alone")) c->opt_refine_skew_waves_alone = (int)std::max(0LL, std::min(value, 1000000LL));
     else if (!strcmp(name, "refine_skew_rows")) c->opt_refine_skew_rows = (int)std::max(0LL, std::min(value, 1000000LL));
     else if (!strcmp(name, "cu_share")) {
@@ -2477,6 +2485,174 @@ extern "C" int rsm_write_ply_mesh(const char *path, const float *xyz, int64_t nv
     fprintf(fp, "ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n", (int)nv);
     fprintf(fp, "element face %d\nproperty list uchar int vertex_indices\nend_header\n", (int)nf);
     if (nv > 0) fwrite(xyz, sizeof(float), 3 * (size_t)nv, fp);
+    const unsigned char three = 3;
+    for (int64_t f = 0; f < nf; f++) {
+        fwrite(&three, 1, 1, fp);
+        fwrite(faces + 3 * f, sizeof(int32_t), 3, fp);
+    }
+    const int ok = ferror(fp) == 0;
+    fclose(fp);
+    return ok ? RSM_OK : RSM_E_INVALID;
+}
+
+// ---- colours of the mesh from the rig's views (k_meshcolor.hip) ----------------------------------------------------------
+static int meshcolor_params_ok(rsm_ctx *c, const rsm_mesh_color_params *p) {
+    if (!p) return set_err(c, RSM_E_INVALID, "mesh_color: params is NULL");
+    if (p->mode != 0 && p->mode != 1) return set_err(c, RSM_E_INVALID, "mesh_color: mode %d not 0 (best view) or 1 (blend)", p->mode);
+    if (!(p->min_cos >= -1.0 && p->min_cos < 1.0)) return set_err(c, RSM_E_INVALID, "mesh_color: min_cos %g outside [-1, 1)", p->min_cos);
+    if (!std::isfinite(p->depth_eps) || p->depth_eps < 0.0) return set_err(c, RSM_E_INVALID, "mesh_color: depth_eps %g negative or not finite", p->depth_eps);
+    return RSM_OK;
+}
+static int meshcolor_counts_ok(rsm_ctx *c, int64_t nv, int64_t nf) {
+    if (nv < 0 || nv > (int64_t)INT32_MAX) return set_err(c, RSM_E_INVALID, "mesh_color: nv %lld outside 0..INT32_MAX", (long long)nv);
+    if (nf < 0 || 3 * nf >= ((int64_t)1 << 31)) return set_err(c, RSM_E_INVALID, "mesh_color: nf %lld negative or 3 nf >= 2^31", (long long)nf);
+    return RSM_OK;
+}
+static int meshcolor_views_ok(rsm_ctx *c, int64_t nv, const rsm_dedup_view *v, int np) {
+    if (nv == 0) return RSM_OK;
+    if (np < 1 || np > 32767) return set_err(c, RSM_E_INVALID, "mesh_color: n_pairs %d outside 1..32767", np);
+    if (!v) return set_err(c, RSM_E_INVALID, "mesh_color: a NULL pointer (views)");
+    for (int i = 0; i < np; i++) {
+        if (v[i].width < 1 || v[i].height < 1) return set_err(c, RSM_E_INVALID, "mesh_color: pair %d: width %d / height %d < 1", i, v[i].width, v[i].height);
+        if (!v[i].image[0] || !v[i].image[1]) return set_err(c, RSM_E_INVALID, "mesh_color: pair %d: a NULL pointer (image)", i);
+    }
+    return RSM_OK;
+}
+static int meshcolor_fail(rsm_ctx *c, int s, int invalid) {
+    if (s == RSM_E_INVALID)
+        return set_err(c, s, invalid == 1 ? "mesh_color: a face index outside [0, nv)" : invalid == 2 ? "mesh_color: a coordinate that is not finite"
+                                                                                                       : "mesh_color: a singular P (det of its left 3x3 is 0)");
+    return set_err(c, s, "mesh_color: failed%s%s", s == RSM_E_HIP ? ": " : "", s == RSM_E_HIP ? hipGetErrorString(hipGetLastError()) : "");
+}
+
+extern "C" int rsm_mesh_color_device(rsm_ctx *c, const float *d_xyz, int64_t nv, const int32_t *d_faces, int64_t nf, const rsm_dedup_view *views, int n_pairs,
+                                     const rsm_mesh_color_params *p, uint8_t *d_rgb, int32_t *d_best_view, double *stats) {
+    if (!c) return RSM_E_INVALID;
+    int s = meshcolor_params_ok(c, p);
+    if (s != RSM_OK || (s = meshcolor_counts_ok(c, nv, nf)) != RSM_OK) return s;
+    if ((nv > 0 && (!d_xyz || !d_rgb)) || (nf > 0 && !d_faces)) return set_err(c, RSM_E_INVALID, "mesh_color: a NULL pointer");
+    if ((s = meshcolor_views_ok(c, nv, views, n_pairs)) != RSM_OK) return s;
+    HIPCHK(c, hipSetDevice(c->device));
+    int invalid = 0;
+    s = mesh_color_device(d_xyz, nv, d_faces, nf, views, n_pairs, p, c->opt_meshcolor_big_box, d_rgb, d_best_view, stats, &invalid, c->stream);
+    return s == RSM_OK ? RSM_OK : meshcolor_fail(c, s, invalid);
+}
+
+extern "C" int rsm_mesh_color(rsm_ctx *c, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, const rsm_dedup_view *views, int n_pairs,
+                              const rsm_mesh_color_params *p, uint8_t *rgb, int32_t *best_view, double *stats) {
+    if (!c) return RSM_E_INVALID;
+    int s = meshcolor_params_ok(c, p);
+    if (s != RSM_OK || (s = meshcolor_counts_ok(c, nv, nf)) != RSM_OK) return s;
+    if ((nv > 0 && (!xyz || !rgb)) || (nf > 0 && !faces)) return set_err(c, RSM_E_INVALID, "mesh_color: a NULL pointer");
+    if ((s = meshcolor_views_ok(c, nv, views, n_pairs)) != RSM_OK) return s;
+    HIPCHK(c, hipSetDevice(c->device));
+    Tmp T(c);
+    float *dv = T.alloc<float>(3 * (size_t)nv);
+    int32_t *df = T.alloc<int32_t>(3 * (size_t)nf), *db = T.alloc<int32_t>((size_t)nv);
+    uint8_t *dc = T.alloc<uint8_t>(3 * (size_t)nv);
+    if (!dv || !df || !db || !dc) return set_err(c, RSM_E_NOMEM, "mesh_color: no device memory for %lld vertices, %lld faces", (long long)nv, (long long)nf);
+    if (nv > 0) HIPCHK(c, hipMemcpyAsync(dv, xyz, sizeof(float) * 3 * (size_t)nv, hipMemcpyHostToDevice, c->stream));
+    if (nf > 0) HIPCHK(c, hipMemcpyAsync(df, faces, sizeof(int32_t) * 3 * (size_t)nf, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    int invalid = 0;
+    s = mesh_color_device(dv, nv, df, nf, views, n_pairs, p, c->opt_meshcolor_big_box, dc, db, stats, &invalid, c->stream);
+    if (s != RSM_OK) return meshcolor_fail(c, s, invalid);
+    if (nv > 0) HIPCHK(c, hipMemcpyAsync(rgb, dc, 3 * (size_t)nv, hipMemcpyDeviceToHost, c->stream));
+    if (nv > 0 && best_view) HIPCHK(c, hipMemcpyAsync(best_view, db, sizeof(int32_t) * (size_t)nv, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RSM_OK;
+}
+
+extern "C" int rsm_mesh_color_last(rsm_ctx *c, const rsm_dedup_view *views, int n_pairs, const rsm_mesh_color_params *p, double *stats) {
+    if (!c) return RSM_E_INVALID;
+    int s = meshcolor_params_ok(c, p);
+    const int64_t nv = c->pmesh.nv, nf = c->pmesh.nf;
+    if (s != RSM_OK || (s = meshcolor_views_ok(c, nv, views, n_pairs)) != RSM_OK) return s;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (c->mcol_rgb) (void)hipFree(c->mcol_rgb);
+    if (c->mcol_best) (void)hipFree(c->mcol_best);
+    c->mcol_rgb = nullptr;
+    c->mcol_best = nullptr;
+    c->mcol_of = nullptr;
+    c->mcol_nv = 0;
+    if (hipMalloc((void **)&c->mcol_rgb, 3 * (size_t)nv + 64) != hipSuccess || hipMalloc((void **)&c->mcol_best, sizeof(int32_t) * (size_t)nv + 64) != hipSuccess)
+        return set_err(c, RSM_E_NOMEM, "mesh_color: no device memory for %lld vertices", (long long)nv);
+    int invalid = 0;
+    s = mesh_color_device(c->pmesh.d_v, nv, c->pmesh.d_f, nf, views, n_pairs, p, c->opt_meshcolor_big_box, c->mcol_rgb, c->mcol_best, stats, &invalid, c->stream);
+    if (s != RSM_OK) return meshcolor_fail(c, s, invalid);
+    c->mcol_of = c->pmesh.d_v;
+    c->mcol_nv = nv;
+    return RSM_OK;
+}
+
+extern "C" int rsm_mesh_last_colors(rsm_ctx *c, uint8_t *rgb, int32_t *best_view) {
+    if (!c) return RSM_E_INVALID;
+    if (!c->mcol_rgb || c->mcol_of != c->pmesh.d_v || c->mcol_nv != c->pmesh.nv)
+        return set_err(c, RSM_E_STATE, "mesh_last_colors: the context's last mesh has no colours (rsm_mesh_color_last first)");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (rgb && c->mcol_nv > 0) HIPCHK(c, hipMemcpyAsync(rgb, c->mcol_rgb, 3 * (size_t)c->mcol_nv, hipMemcpyDeviceToHost, c->stream));
+    if (best_view && c->mcol_nv > 0) HIPCHK(c, hipMemcpyAsync(best_view, c->mcol_best, sizeof(int32_t) * (size_t)c->mcol_nv, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RSM_OK;
+}
+
+extern "C" int rsm_texture_color(rsm_ctx *c, const float *xyz, int64_t n, const double P12[12], const uint8_t *image, int width, int height, uint8_t *rgb) {
+    if (!c) return RSM_E_INVALID;
+    if (n < 0 || n > (int64_t)INT32_MAX) return set_err(c, RSM_E_INVALID, "texture_color: n %lld outside 0..INT32_MAX", (long long)n);
+    if (width < 1 || height < 1) return set_err(c, RSM_E_INVALID, "texture_color: width %d / height %d < 1", width, height);
+    if (!P12 || !image || (n > 0 && (!xyz || !rgb))) return set_err(c, RSM_E_INVALID, "texture_color: a NULL pointer");
+    if (n == 0) return RSM_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    Tmp T(c);
+    const size_t pix = (size_t)width * (size_t)height;
+    float *dp = T.alloc<float>(3 * (size_t)n);
+    uint8_t *di = T.alloc<uint8_t>(3 * pix), *dc = T.alloc<uint8_t>(3 * (size_t)n);
+    if (!dp || !di || !dc) return set_err(c, RSM_E_NOMEM, "texture_color: no device memory");
+    HIPCHK(c, hipMemcpyAsync(dp, xyz, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(di, image, 3 * pix, hipMemcpyHostToDevice, c->stream));
+    const int s = texture_color_device(dp, n, P12, di, width, height, dc, c->stream);
+    if (s != RSM_OK) return set_err(c, s, "texture_color: failed");
+    HIPCHK(c, hipMemcpyAsync(rgb, dc, 3 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RSM_OK;
+}
+
+extern "C" int rsm_stage_mesh_depth(rsm_ctx *c, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, const double P12[12], int width, int height,
+                                    uint32_t *wbuf) {
+    if (!c) return RSM_E_INVALID;
+    int s = meshcolor_counts_ok(c, nv, nf);
+    if (s != RSM_OK) return s;
+    if (width < 1 || height < 1) return set_err(c, RSM_E_INVALID, "mesh_color: width %d / height %d < 1", width, height);
+    if (!P12 || !wbuf || (nv > 0 && !xyz) || (nf > 0 && !faces)) return set_err(c, RSM_E_INVALID, "mesh_color: a NULL pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    Tmp T(c);
+    const size_t pix = (size_t)width * (size_t)height;
+    float *dv = T.alloc<float>(3 * (size_t)nv);
+    int32_t *df = T.alloc<int32_t>(3 * (size_t)nf);
+    uint32_t *dw = T.alloc<uint32_t>(pix);
+    if (!dv || !df || !dw) return set_err(c, RSM_E_NOMEM, "mesh_color: no device memory");
+    if (nv > 0) HIPCHK(c, hipMemcpyAsync(dv, xyz, sizeof(float) * 3 * (size_t)nv, hipMemcpyHostToDevice, c->stream));
+    if (nf > 0) HIPCHK(c, hipMemcpyAsync(df, faces, sizeof(int32_t) * 3 * (size_t)nf, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    int invalid = 0;
+    if ((s = mesh_depth_device(dv, nv, df, nf, P12, width, height, c->opt_meshcolor_big_box, dw, &invalid, c->stream)) != RSM_OK) return meshcolor_fail(c, s, invalid);
+    HIPCHK(c, hipMemcpyAsync(wbuf, dw, sizeof(uint32_t) * pix, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RSM_OK;
+}
+
+// the coloured mesh as MyPlyIo writes it (my_ply_interface.cpp:35-50): vertex x y z red green blue, face vertex_indices.  Host only.
+extern "C" int rsm_write_ply_mesh_color(const char *path, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, const uint8_t *rgb) {
+    if (!path || nv < 0 || nf < 0 || nv > (int64_t)INT32_MAX || nf > (int64_t)INT32_MAX || (nv > 0 && (!xyz || !rgb)) || (nf > 0 && !faces)) return RSM_E_INVALID;
+    FILE *fp = fopen(path, "wb");
+    if (!fp) return RSM_E_INVALID;
+    fprintf(fp, "ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n", (int)nv);
+    fprintf(fp, "property uchar red\nproperty uchar green\nproperty uchar blue\n");
+    fprintf(fp, "element face %d\nproperty list uchar int vertex_indices\nend_header\n", (int)nf);
+    for (int64_t v = 0; v < nv; v++) {
+        fwrite(xyz + 3 * v, sizeof(float), 3, fp);
+        fwrite(rgb + 3 * v, 1, 3, fp);
+    }
     const unsigned char three = 3;
     for (int64_t f = 0; f < nf; f++) {
         fwrite(&three, 1, 1, fp);

@@ -252,3 +252,16 @@ int mesh_components_device(const int32_t *d_f, int64_t nv, int64_t nf, int32_t *
 // the result replaces *out, which may own d_v / d_f (it is freed after the last read); stats: RSM_MESH_CLEAN_STATS doubles, may be NULL
 int mesh_clean_device(const float *d_v, int64_t nv, const int32_t *d_f, int64_t nf, const rsm_mesh_clean_params *p, PoissonMesh *out, double *stats, int *invalid,
                       hipStream_t st);
+
+// colours of a mesh from the rig's views (k_meshcolor.hip).  Device buffers: nv float xyz, nf int32 x 3, d_rgb nv x 3 bytes,
+// d_best nv int32 (may be NULL); the views' images are host pointers and are uploaded here.  RSM_E_INVALID comes with *invalid = 1 (a face
+// index outside [0, nv)), 2 (a coordinate that is not finite) or 3 (a singular P); parameters and views are the caller's to check.
+// big_box: a (face, view) box of more pixels is strided by a block instead of walked by one thread.
+struct rsm_mesh_color_params;
+int mesh_color_device(const float *d_v, int64_t nv, const int32_t *d_f, int64_t nf, const rsm_dedup_view *views, int n_pairs, const rsm_mesh_color_params *p,
+                      long long big_box, uint8_t *d_rgb, int32_t *d_best, double *stats, int *invalid, hipStream_t st);
+// one view's depth buffer: W x H uint32, the largest float32 bit pattern of the inverse depth drawn at each pixel centre, 0 where nothing is
+int mesh_depth_device(const float *d_v, int64_t nv, const int32_t *d_f, int64_t nf, const double P12[12], int W, int H, long long big_box, uint32_t *d_wbuf,
+                      int *invalid, hipStream_t st);
+// texture_color (CCloudOptimization.cpp:400-421) of n points against a BGR image on the device
+int texture_color_device(const float *d_xyz, int64_t n, const double P12[12], const uint8_t *d_img, int W, int H, uint8_t *d_rgb, hipStream_t st);
