@@ -4,185 +4,22 @@
 // rectified top-level images: ConstructPyrm (:1040-1053) -> MatchOneLayer x PyrmNum (:36-113, stage order
 // kept exactly) -> DisparityToCloud<double> (:682-761).  Everything stays resident in HBM between the one
 // upload and the one download; both matching directions run in the same launches (gridDim.z).
-#include "../../include/rsm.h"
 #include "rectify_host.h"
-#include "rsm_dev.h"
+#include "rsm_ctx.h"
 
 #include <algorithm>
+#include <mutex>
+#include <thread>
 
-#include <limits.h>
 #include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
-#include <atomic>
-#include <mutex>
-#include <string>
-#include <thread>
-#include <vector>
-
-// ------------------------------------------------------------------------------------------------
-enum Stage {
-    ST_PYRAMID = 0,
-    ST_MARGIN,
-    ST_BOXSUM,
-    ST_INITIAL_MATCH,
-    ST_SMOOTH,
-    ST_ORDER,
-    ST_UNIQ16,
-    ST_REMATCH,
-    ST_MEDIAN,
-    ST_REFINE_INIT,
-    ST_REFINE_SWEEP,     // all levels below the top
-    ST_REFINE_SWEEP_TOP, // the top level's sweeps (light + worklist kernels)
-    ST_REFINE_LIGHT_TOP, // only the k_refine_sweep<1> launches of the top level
-    ST_REFINE_SKEW_TOP,  // only the k_refine_skew<T,1> launches of the top level (T sweeps each; the dominant kernel)
-    ST_UNIQ64,
-    ST_CLOUD,
-    ST_COUNT
-};
 static const char *kStageNames[ST_COUNT] = {"pyramid", "margin", "boxsum", "initial_match", "smooth", "order",
                                             "uniqueness_s16", "rematch", "median", "refine_init",
                                             "refine_sweep", "refine_sweep_top", "refine_light_top", "refine_skew_top", "uniqueness_f64", "cloud"};
-
-struct EvPair {
-    hipEvent_t a, b;
-    int stage;
-};
-
-struct rsm_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;
-    hipStream_t stream2 = nullptr; // side stream: per-level BGRX copies and window sums (they depend on the images only)
-    hipEvent_t ev_pyr = nullptr, ev_prep[RSM_MAX_LEVELS]{};
-    std::string err;
-
-    // resident pair
-    bool have_pair = false, have_result = false;
-    rsm_pair_in in{};
-    int N = 0;
-    int Wk[RSM_MAX_LEVELS]{}, Hk[RSM_MAX_LEVELS]{};
-    uint8_t *img[RSM_MAX_LEVELS][2]{}, *msk[RSM_MAX_LEVELS][2]{};
-    Mg mg[RSM_MAX_LEVELS][2]{};
-    int h_margin_init[RSM_MAX_LEVELS * 2 * 4]{}; // host source of the margins' initial values (async copy)
-
-    // workspace (sized for the top level)
-    size_t cap_px = 0;
-    std::vector<void *> allocs;
-    int *d_margins = nullptr; // N*2*4 ints
-    int32_t *S1[RSM_MAX_LEVELS][2]{}, *S2[RSM_MAX_LEVELS][2]{}, *tmp1 = nullptr, *tmp2 = nullptr; // per level and view
-    uint32_t *img4[RSM_MAX_LEVELS][2]{};
-    int16_t *d16a[2]{}, *BL[2]{}, *BR[2]{}; // d16a: scratch (Rectify's mask temp)
-    uint8_t *cloud_flags = nullptr;         // k_cloud's per-pixel "emitted a point" flags of the last run: rsm_filter_last_cloud's lattice reads them
-                                            // long after rsm_run_pair has returned, so they have a buffer nothing else borrows
-    int16_t *d16i[RSM_MAX_LEVELS][2]{}, *d16s[RSM_MAX_LEVELS][2]{}, *d16m[RSM_MAX_LEVELS][2]{}; // per level: initial-match / constraint-stage / median maps, pre-filled NOMATCH
-    double *f64[3][2]{};
-    int32_t *nv[2]{};
-    uint32_t *rf_key[2]{};
-    int32_t *rf_cnt = nullptr; // NCC wide-pixel counter
-    int32_t *wrow = nullptr;   // NCC: wide pixels per (direction, row) of the level at hand
-    uint32_t *rf_list = nullptr;
-    uint32_t *tie_list = nullptr; // NCC tie pixels (k_ncc_exact)
-    int32_t *tie_cnt = nullptr;   // [2 * level + (Rematch ? 1 : 0)]
-    double2 *rf_ent[2]{};
-    RfUpd *upd_list = nullptr; // k_refine_skew's cache updates
-    int32_t *upd_cnt = nullptr;
-    int upd_cap = 0;
-    int32_t *prefix = nullptr;
-    int *d_j1 = nullptr, *d_j2 = nullptr;   // structuring-element spans: Rectify's mask erosion
-    int *d_cj1 = nullptr, *d_cj2 = nullptr; // ... and DisparityToCloud's (uploaded with the pair)
-    uint8_t *blk = nullptr;                 // coarse bad-block map of the top-level mask (cloud erosion)
-    hipEvent_t ev_cloudprep = nullptr;
-    int ordinal = 0;               // n-th context created on its device
-    int opt_cu_share = 0;          // > 1: the context's streams are confined to one of that many equal shares of the compute units
-    hipEvent_t ev_heavy = nullptr; // end of this context's last bandwidth-bound section (heavy_begin / heavy_end)
-    hipStream_t stream_filter = nullptr; // rsm_filter_last_cloud's stream: the lowest priority the device offers (filter_stream())
-    hipEvent_t ev_filter = nullptr;      // orders the filter behind whatever `stream` still holds
-    hipEvent_t ev_heavy2 = nullptr; // ... of its last issue-bound (time-skewed) section: lane 1
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr; // the two directions of a time-skewed section on two streams (refine_sweeps)
-    RfUpd *upd_list2 = nullptr;     // the second direction's update list / counters while the two run as separate launch chains
-    int32_t *upd_cnt2 = nullptr;
-    int opt_refine_split = 1;       // a pair that has the GPU to itself runs the two directions of its time-skewed sections on two streams
-    int opt_shared_gpu = 0;         // the caller's hint that other contexts use this GPU (a pool of pairs in flight): never split, whatever g_running says at the moment
-    int pool_shared = 0;            // the same, derived per call by rsm_run_pairs / rsm_match_pairs from their pool (the caller's option stays as set)
-    bool shared_now() const { return opt_shared_gpu || pool_shared; }
-    std::atomic<int> in_run{0};     // inside rsm_run_pair (options that replace the streams refuse to act then)
-    int32_t *row_count = nullptr;
-    int64_t *row_offset = nullptr;
-    int64_t *d_npoints = nullptr;
-    unsigned long long *d_vtop = nullptr;
-    double *d_q = nullptr, *d_R = nullptr, *d_T = nullptr;
-    double *xyz = nullptr;
-    uint8_t *bgr = nullptr;
-    rsm_point16 *pack16 = nullptr; // the cloud as 16-byte records / the filter's output, staged for a host download (on first use)
-    float *pack_nrm = nullptr;     // ... and the filter's normals
-    FilterArena *filt_arena = nullptr; // the cloud filter's scratch (created on first use, grows with the cloud)
-    PoissonMesh pmesh;                 // the last mesh of rsm_poisson_mesh / rsm_stage_iso_mesh (rsm_poisson_last_mesh copies it out)
-    uint8_t *mcol_rgb = nullptr;       // rsm_mesh_color_last's colours of that mesh (rsm_mesh_last_colors copies them out) ...
-    int32_t *mcol_best = nullptr;      // ... and best views
-    const float *mcol_of = nullptr;    // the vertex buffer they belong to, and its vertex count: a later mesh has no colours
-    int64_t mcol_nv = 0;
-    long long opt_meshcolor_big_box = 4096; // rsm_mesh_color: a (face, view) bounding box of more pixels is strided by a block, not walked by one thread
-    int opt_filter_wg_max = 2048;      // rsm_filter_last_cloud: the wave passes' workgroup form while at most this many queries are left (0: never)
-    int opt_filter_normals_window = 8; // rsm_filter_last_cloud: the normals' radius search on the pixel lattice while no point needs a wider window than this (0: grid)
-    int filt_normals[2]{};             // last rsm_filter_last_cloud: the window the normals used (0: the grid), the widest a point needed (-1: not asked)
-    int opt_filter_list = 23;          // ... and the 24-pixel window a thread each for what the tile pass leaves over
-    int filt_memo_radius = 0, filt_memo_k = 0, filt_memo_w = 0, filt_memo_h = 0, filt_memo_uses = 0; // rsm_filter_last_cloud: the last probe's choice
-    int opt_filter_low_priority = 1;   // rsm_filter_last_cloud on a stream of the lowest priority (1) or on the context's own (0)
-    int opt_filter_window = 1;         // rsm_filter_last_cloud: the pixel-window k-nearest pass in front of the grid ladder (1: radius from a sparse probe; 0: off; else the radius)
-    int64_t filt_tile_left = 0;        // ... queries the tile pass alone left over
-    int64_t filt_info[4]{};            // last rsm_filter_last_cloud: window pass used, queries it left to the ladder, points in, points kept
-    FilterRoute filt_route;            // the grid ladder: option "filter_ladder_h" in, what the last rsm_filter_cloud / rsm_filter_last_cloud did out
-
-    // results
-    double *res_disp[2]{};
-    int64_t n_points = 0;
-    int64_t v_top = 0;
-
-    // options (rsm_set_option)
-    int opt_ncc_bytes = 0;
-    int opt_no_exact = 0;
-    int opt_no_rowgemm = 0;
-    int opt_ncc_mid = 0;         // rows that hold many (RG_MIN) pixels with intervals longer than this go to a row kernel; 0 = by window size
-                                 // (measured crossover against the band kernel: 11x11 from ~40 candidates on, 5x5 beyond 160)
-    int opt_ncc_slide_max = 512; // rows whose widest interval has at most this many candidates take the sliding-sums kernel, the others the int8 row GEMM
-    int opt_heavy_from_sweep = 1;  // ... from this sweep of the level on
-    int opt_heavy_min_px = 400000; // ... from this many margin pixels on (smaller levels are launch-bound themselves)
-    int opt_heavy_lanes = 2;     // 2: the single-sweep part and the time-skewed part of a level's refine take turns separately (lanes 0 / 1)
-    int opt_heavy_exclusive = 1; // refine sections of contexts sharing a GPU take turns (heavy_begin): 1 = the top level's, 2 = every large level's, 0 = none
-    int opt_refine_skew_from = 4;  // first sweep of a level that may run in the time-skewed kernel (k_refine_skew; 0: never): 22 without the re-key below -- before
-                                   // that too many pixels still miss the data-term cache for its lane-serial miss service
-    int opt_refine_rekey_until = 22; // a time-skewed launch that starts before this sweep is preceded by k_refine_rekey (both cache ways set for the current
-                                     // state: the key and its nearer neighbour), which keeps the early launches' misses at the settled rate (0: never)
-    int opt_refine_rekey_side = 0;   // 1: k_refine_rekey installs the FARTHER neighbour (a wrong prediction: tests)
-    int opt_refine_prefill = 1;    // k_refine_first also fills the second cache way with the neighbour iMatch its update points to
-    int opt_refine_skew_T = 4;     // sweeps per time-skewed launch (2..4)
-    int opt_refine_skew_min_px = 1000000; // ... at levels with at least this many margin pixels per direction (smaller levels: the 4T-step pipeline fill of a chunk eats the gain)
-    int opt_refine_skew_waves = 2560;    // workgroups a time-skewed launch aims at (sets the rows per chunk): 5 per CU are resident, so two rounds --
-                                         // workgroups at different points of their chunks share a CU better than 1 280 in lockstep (measured: 0.28 against 0.34 ms)
-    int opt_refine_skew_waves_alone = 3840; // ... when no other context of the device is inside rsm_run_pair (0: the same)
-    int opt_refine_skew_rows = 0;        // > 0: rows per chunk, overrides refine_skew_waves (tests)
-    int opt_refine_skew_prio = 0;        // the time-skewed kernel's waves rotate their issue priority every 2^this shader clocks (0: never)
-    int opt_refine_skew_uw = 0;          // columns a strip owns; 0: 66 - 2T, all its last level can compute (an even number <= that: A/B)
-
-    // what the last rsm_stage_initial_match's NCC launch decided (rsm_stage_last_ncc_routes): its per-row counters and row
-    // lists (StageArgs::wrow, rsm_dev.h), the worklist length and the tie count; H = 0 until such a call succeeded
-    std::vector<int32_t> ncc_wit_wrow;
-    int ncc_wit_H = 0;
-    int32_t ncc_wit_cnt = 0, ncc_wit_ties = 0;
-
-    // profiling
-    bool profile = false;
-    bool profile_stages = false;
-    std::vector<EvPair> evpool;
-    size_t ev_used = 0;
-    double prof_ms[ST_COUNT]{};
-    int64_t prof_launches[ST_COUNT]{};
-    double prof_bytes[ST_COUNT]{};
-};
-
 
 // ---- one bandwidth-bound section at a time per GPU ------------------------------------------------------------
 // Contexts that share a GPU (rsm_run_pairs / rsm_match_pairs: several pairs in flight) overlap usefully only where
@@ -241,7 +78,7 @@ static void heavy_forget(rsm_ctx *c) { // the context goes away: nobody may wait
     }
 }
 
-static int set_err(rsm_ctx *c, int code, const char *fmt, ...) {
+int set_err(rsm_ctx *c, int code, const char *fmt, ...) {
     if (c) {
         char buf[512];
         va_list ap;
@@ -253,21 +90,8 @@ static int set_err(rsm_ctx *c, int code, const char *fmt, ...) {
     return code;
 }
 
-#define HIPCHK(c, call)                                                                               \
-    do {                                                                                              \
-        hipError_t e__ = (call);                                                                      \
-        if (e__ != hipSuccess)                                                                        \
-            return set_err((c), RSM_E_HIP, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e__),    \
-                           __FILE__, __LINE__);                                                       \
-    } while (0)
-
-static Mg to_mg(const rsm_boundary &b) { return Mg{b.YL, b.YR, b.XL, b.XR}; }
-static rsm_boundary to_boundary(const Mg &m) {
-    return rsm_boundary{m.YL, m.YR, m.XL, m.XR, m.XR - m.XL + 1, m.YR - m.YL + 1};
-}
-
 // ---- cv::getStructuringElement(MORPH_ELLIPSE) row spans (OpenCV 2.4; see oracle + DESIGN.md) ----
-static void ellipse_spans(int k, std::vector<int> &j1, std::vector<int> &j2) {
+void ellipse_spans(int k, std::vector<int> &j1, std::vector<int> &j2) {
     j1.assign(k, 0);
     j2.assign(k, 0);
     const int r = k / 2, c = k / 2;
@@ -365,15 +189,6 @@ extern "C" void rsm_destroy(rsm_ctx *c) {
     delete c;
 }
 
-template <typename T>
-static int dalloc(rsm_ctx *c, T **p, size_t n) {
-    void *q = nullptr;
-    hipError_t e = hipMalloc(&q, n * sizeof(T) + 64);
-    if (e != hipSuccess) return set_err(c, RSM_E_NOMEM, "hipMalloc(%zu) failed: %s", n * sizeof(T), hipGetErrorString(e));
-    c->allocs.push_back(q);
-    *p = (T *)q;
-    return RSM_OK;
-}
 #define DALLOC(c, p, n)                         \
     do {                                        \
         int s__ = dalloc((c), &(p), (size_t)(n)); \
@@ -683,7 +498,6 @@ static StageArgs level_args(rsm_ctx *c, int k) {
     return a;
 }
 
-static bool degenerate(const Mg &m) { return m.YL >= m.YR || m.XL >= m.XR; } // .cpp:827
 
 // DisparityRefine's Jacobi sweeps (.cpp:590-678): sweep t reads A (t even) or B (t odd) and writes the other.
 // Sweep 0 is k_refine_first (every pixel computes its data term); then one launch per sweep (k_refine_sweep) while the
@@ -1230,406 +1044,7 @@ extern "C" int rsm_match_pairs_multi_gpu(const rsm_pair_in *in, int n_pairs, int
     return s;
 }
 
-// =================================================================================================
-// Per-stage entry points (host buffers, one direction) for the parity tests.
-// =================================================================================================
-namespace {
-struct Tmp { // scoped device allocations of one stage call
-    rsm_ctx *c;
-    std::vector<void *> ptrs;
-    bool ok = true;
-    explicit Tmp(rsm_ctx *c_) : c(c_) {}
-    ~Tmp() {
-        for (void *p : ptrs) (void)hipFree(p);
-    }
-    template <typename T>
-    T *alloc(size_t n) {
-        void *p = nullptr;
-        if (hipMalloc(&p, n * sizeof(T) + 64) != hipSuccess) {
-            ok = false;
-            return nullptr;
-        }
-        ptrs.push_back(p);
-        return (T *)p;
-    }
-    template <typename T>
-    T *up(const T *h, size_t n) {
-        T *d = alloc<T>(n);
-        if (d && (hipMemcpyAsync(d, h, n * sizeof(T), hipMemcpyHostToDevice, c->stream) != hipSuccess ||
-                  hipStreamSynchronize(c->stream) != hipSuccess))
-            ok = false;
-        return d;
-    }
-    template <typename T>
-    void down(T *h, const T *d, size_t n) {
-        if (hipMemcpyAsync(h, d, n * sizeof(T), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-            hipStreamSynchronize(c->stream) != hipSuccess)
-            ok = false;
-    }
-};
-int finish(rsm_ctx *c, Tmp &t) {
-    hipError_t e = hipStreamSynchronize(c->stream);
-    if (e == hipSuccess) e = hipGetLastError();
-    if (e != hipSuccess) return set_err(c, RSM_E_HIP, "stage failed: %s", hipGetErrorString(e));
-    if (!t.ok) return set_err(c, RSM_E_HIP, "stage alloc/copy failed");
-    return RSM_OK;
-}
-bool stage_ok(rsm_ctx *c, int W, int H) { return c && W > 0 && H > 0 && hipSetDevice(c->device) == hipSuccess; }
-} // namespace
-
-extern "C" int rsm_stage_find_margin(rsm_ctx *c, const uint8_t *mask, int W, int H, int r, rsm_boundary *m) {
-    if (!stage_ok(c, W, H) || !mask || !m) return RSM_E_INVALID;
-    Tmp t(c);
-    uint8_t *dm = t.up(mask, (size_t)W * H);
-    int *d4 = t.alloc<int>(4);
-    if (!t.ok) return finish(c, t);
-    launch_find_margin(dm, W, H, r, d4, c->stream);
-    int h[4];
-    t.down(h, d4, 4);
-    *m = to_boundary(Mg{h[2], h[3], h[0], h[1]});
-    return finish(c, t);
-}
-
-extern "C" int rsm_stage_pyr_down(rsm_ctx *c, const uint8_t *src, int W, int H, int ch, uint8_t *dst) {
-    if (!stage_ok(c, W, H) || !src || !dst || (ch != 1 && ch != 3)) return RSM_E_INVALID;
-    Tmp t(c);
-    const size_t nd = (size_t)((W + 1) / 2) * ((H + 1) / 2) * ch;
-    uint8_t *ds = t.up(src, (size_t)W * H * ch);
-    uint8_t *dd = t.alloc<uint8_t>(nd);
-    if (!t.ok) return finish(c, t);
-    launch_pyr_down(ds, W, H, ch, dd, c->stream);
-    t.down(dst, dd, nd);
-    return finish(c, t);
-}
-
-extern "C" int rsm_stage_erode_ellipse(rsm_ctx *c, const uint8_t *mask, int W, int H, int ksize, uint8_t *dst) {
-    if (!stage_ok(c, W, H) || !mask || !dst || ksize < 1 || ksize > 4096) return RSM_E_INVALID;
-    Tmp t(c);
-    std::vector<int> j1, j2;
-    ellipse_spans(ksize, j1, j2);
-    uint8_t *dm = t.up(mask, (size_t)W * H);
-    int *d1 = t.up(j1.data(), (size_t)ksize), *d2 = t.up(j2.data(), (size_t)ksize);
-    int32_t *pre = t.alloc<int32_t>((size_t)(W + 1) * H);
-    uint8_t *dd = t.alloc<uint8_t>((size_t)W * H);
-    if (!t.ok) return finish(c, t);
-    launch_bad_prefix(dm, W, H, pre, c->stream);
-    launch_erode_binary(pre, W, H, ksize, d1, d2, dd, c->stream);
-    t.down(dst, dd, (size_t)W * H);
-    return finish(c, t);
-}
-
-namespace {
-// uploads the images/masks of one direction and builds the window-sum tables
-struct MatchBufs {
-    uint8_t *io, *it, *mo, *mt;
-    uint32_t *i4o, *i4t;
-    uint32_t *wl; // wide-pixel worklist + counter of the NCC kernels
-    int32_t *wc;
-    uint32_t *tl; // tie list + counters (k_ncc_exact)
-    int32_t *tc;
-    int32_t *wr;  // wide pixels per row
-    int32_t *S1o, *S2o, *S1t, *S2t;
-};
-bool setup_match(rsm_ctx *c, Tmp &t, const uint8_t *img_own, const uint8_t *img_oth, const uint8_t *mask_own,
-                 const uint8_t *mask_oth, int W, int H, int r, MatchBufs &b) {
-    const size_t px = (size_t)W * H;
-    b.io = t.up(img_own, px * 3);
-    b.it = t.up(img_oth, px * 3);
-    b.mo = t.up(mask_own, px);
-    b.mt = t.up(mask_oth, px);
-    b.wl = t.alloc<uint32_t>(std::max(px + 64, SETB_SCRATCH(W))); // NCC worklist / SetBoundary scratch
-    b.wc = t.alloc<int32_t>(16 + 2 * (size_t)H);
-    if (b.wc) (void)hipMemsetAsync(b.wc, 0, sizeof(int), c->stream); // wide-pixel counter of the NCC launch
-    b.tl = t.alloc<uint32_t>(px + 64);
-    b.tc = t.alloc<int32_t>(2);
-    if (b.tc) (void)hipMemsetAsync(b.tc, 0, 2 * sizeof(int), c->stream);
-    b.wr = t.alloc<int32_t>(NCC_WROW_INTS((size_t)H));
-    if (b.wr) (void)hipMemsetAsync(b.wr, 0, sizeof(int32_t) * NCC_WROW_INTS((size_t)H), c->stream);
-    b.i4o = t.alloc<uint32_t>(px);
-    b.i4t = t.alloc<uint32_t>(px);
-    b.S1o = t.alloc<int32_t>(px);
-    b.S2o = t.alloc<int32_t>(px);
-    b.S1t = t.alloc<int32_t>(px);
-    b.S2t = t.alloc<int32_t>(px);
-    int32_t *t1 = t.alloc<int32_t>(px), *t2 = t.alloc<int32_t>(px);
-    if (!t.ok) return false;
-    launch_bgr_to_bgrx(b.io, W, H, b.i4o, c->stream);
-    launch_bgr_to_bgrx(b.it, W, H, b.i4t, c->stream);
-    launch_box_sums(b.i4o, W, H, r, t1, t2, b.S1o, b.S2o, c->stream);
-    launch_box_sums(b.i4t, W, H, r, t1, t2, b.S1t, b.S2t, c->stream);
-    return true;
-}
-StageArgs one_dir(rsm_ctx *c, int W, int H, int r, const rsm_boundary *own, const rsm_boundary *oth) {
-    StageArgs a{};
-    a.opt_ncc_bytes = c->opt_ncc_bytes;
-    a.opt_no_exact = c->opt_no_exact;
-    a.opt_no_rowgemm = c->opt_no_rowgemm;
-    a.ncc_mid = c->opt_ncc_mid;
-    a.ncc_slide_max = c->opt_ncc_slide_max;
-    a.ndir = 1;
-    a.W = W;
-    a.H = H;
-    a.r = r;
-    a.d[0].own = to_mg(*own);
-    if (oth) a.d[0].oth = to_mg(*oth);
-    return a;
-}
-void bind_match(StageArgs &a, const MatchBufs &b) {
-    a.rf_list = b.wl;
-    a.ncc_cnt = b.wc;
-    a.tie_list = b.tl;
-    a.tie_cnt = b.tc;
-    a.wrow = b.wr;
-    DirArgs &d = a.d[0];
-    d.img_own = b.io;
-    d.img_oth = b.it;
-    d.img4_own = b.i4o;
-    d.img4_oth = b.i4t;
-    d.mask_own = b.mo;
-    d.mask_oth = b.mt;
-    d.S1_own = b.S1o;
-    d.S2_own = b.S2o;
-    d.S1_oth = b.S1t;
-    d.S2_oth = b.S2t;
-}
-} // namespace
-
-extern "C" int rsm_stage_initial_match(rsm_ctx *c, const uint8_t *img_own, const uint8_t *img_oth,
-                                       const uint8_t *mask_own, const uint8_t *mask_oth, int W, int H, int r,
-                                       int offset, const rsm_boundary *own, const rsm_boundary *oth,
-                                       const double *parent, int Wp, int Hp, int16_t *disp) {
-    if (!stage_ok(c, W, H) || !img_own || !img_oth || !mask_own || !mask_oth || !own || !oth || !disp) return RSM_E_INVALID;
-    Tmp t(c);
-    const size_t px = (size_t)W * H;
-    MatchBufs b{};
-    if (!setup_match(c, t, img_own, img_oth, mask_own, mask_oth, W, H, r, b)) return finish(c, t);
-    StageArgs a = one_dir(c, W, H, r, own, oth);
-    bind_match(a, b);
-    a.offset = offset;
-    a.Wp = Wp;
-    a.Hp = Hp;
-    int16_t *dd = t.alloc<int16_t>(px);
-    a.d[0].BL = t.alloc<int16_t>(px);
-    a.d[0].BR = t.alloc<int16_t>(px);
-    if (!t.ok) return finish(c, t);
-    launch_fill_i16(dd, px, (int16_t)NOMATCH, c->stream);
-    a.d[0].d16_in = a.d[0].d16_out = dd;
-    if (!parent) {
-        launch_ncc_argmax(a, 0, c->stream);
-    } else {
-        double *dp = t.up(parent, (size_t)Wp * Hp);
-        int32_t *nv = t.alloc<int32_t>((size_t)Wp * Hp);
-        if (!t.ok) return finish(c, t);
-        a.d[0].parent = dp;
-        a.d[0].parent_nv = nv;
-        launch_next_valid(dp, Wp, Hp, nv, c->stream);
-        launch_hl_interval(a, c->stream);
-        launch_ncc_argmax(a, 1, c->stream);
-    }
-    t.down(disp, dd, px);
-    // the routing witness, copied before the scratch is freed
-    c->ncc_wit_H = 0;
-    std::vector<int32_t> wr(NCC_WROW_INTS((size_t)H));
-    int32_t cnt = 0, ties = 0;
-    t.down(wr.data(), b.wr, wr.size());
-    t.down(&cnt, b.wc, 1);
-    t.down(&ties, b.tc, 1);
-    const int s = finish(c, t);
-    if (s == RSM_OK) {
-        c->ncc_wit_wrow.swap(wr);
-        c->ncc_wit_H = H;
-        c->ncc_wit_cnt = cnt;
-        c->ncc_wit_ties = ties;
-    }
-    return s;
-}
-
-extern "C" int rsm_stage_last_ncc_routes(rsm_ctx *c, int H, int32_t *wide, int32_t *mid, int32_t *widest, int32_t *route,
-                                         int64_t *worklist, int64_t *ties) {
-    if (!c || !wide || !mid || !widest || !route || !worklist || !ties) return RSM_E_INVALID;
-    if (c->ncc_wit_H == 0) return set_err(c, RSM_E_STATE, "no rsm_stage_initial_match has run on this context");
-    if (H != c->ncc_wit_H) return set_err(c, RSM_E_INVALID, "H %d: the last initial match had %d rows", H, c->ncc_wit_H);
-    const int32_t *w = c->ncc_wit_wrow.data();
-    for (int y = 0; y < H; y++) {
-        wide[y] = w[y];
-        mid[y] = w[NCC_WROW_MID(H) + y];
-        widest[y] = w[NCC_WROW_MAX(H) + y];
-        route[y] = w[y] > 0 ? 1 : 0;
-    }
-    for (int which = 0; which < 2; which++) { // list 0: k_ncc_rowgemm, list 1: k_ncc_slide ([0] = count, then the rows)
-        const int32_t *l = w + NCC_WROW_LIST(H, which);
-        const int n = std::min(std::max(l[0], 0), H);
-        for (int i = 0; i < n; i++) {
-            const int y = l[1 + i];
-            if (y < 0 || y >= H) return set_err(c, RSM_E_STATE, "row list %d holds row %d of %d", which, y, H);
-            route[y] = route[y] >= 2 ? -1 : 2 + which; // -1: a row listed twice
-        }
-    }
-    *worklist = c->ncc_wit_cnt;
-    *ties = c->ncc_wit_ties;
-    return RSM_OK;
-}
-
-extern "C" int rsm_stage_smooth(rsm_ctx *c, int16_t *disp, int W, int H, const rsm_boundary *own) {
-    if (!stage_ok(c, W, H) || !disp || !own) return RSM_E_INVALID;
-    Tmp t(c);
-    const size_t px = (size_t)W * H;
-    StageArgs a = one_dir(c, W, H, 0, own, nullptr);
-    a.d[0].d16_in = t.up(disp, px);
-    a.d[0].d16_out = t.alloc<int16_t>(px);
-    if (!t.ok) return finish(c, t);
-    launch_smooth(a, c->stream);
-    t.down(disp, a.d[0].d16_out, px);
-    return finish(c, t);
-}
-
-extern "C" int rsm_stage_order(rsm_ctx *c, int16_t *disp, int W, int H, const rsm_boundary *own) {
-    if (!stage_ok(c, W, H) || !disp || !own) return RSM_E_INVALID;
-    Tmp t(c);
-    const size_t px = (size_t)W * H;
-    StageArgs a = one_dir(c, W, H, 0, own, nullptr);
-    a.d[0].d16_in = a.d[0].d16_out = t.up(disp, px);
-    if (!t.ok) return finish(c, t);
-    launch_order(a, c->stream);
-    t.down(disp, a.d[0].d16_in, px);
-    return finish(c, t);
-}
-
-extern "C" int rsm_stage_uniqueness_pass_s16(rsm_ctx *c, int16_t *p, const int16_t *q, int W, int H,
-                                             const rsm_boundary *own, const rsm_boundary *oth) {
-    if (!stage_ok(c, W, H) || !p || !q || !own || !oth) return RSM_E_INVALID;
-    Tmp t(c);
-    const size_t px = (size_t)W * H;
-    int16_t *dp = t.up(p, px);
-    int16_t *dq = t.up(q, px);
-    if (!t.ok) return finish(c, t);
-    launch_uniq_s16(dp, dq, W, H, to_mg(*own), to_mg(*oth), c->stream);
-    t.down(p, dp, px);
-    return finish(c, t);
-}
-
-extern "C" int rsm_stage_uniqueness_pass_f64(rsm_ctx *c, double *p, const double *q, int W, int H,
-                                             const rsm_boundary *own, const rsm_boundary *oth) {
-    if (!stage_ok(c, W, H) || !p || !q || !own || !oth) return RSM_E_INVALID;
-    Tmp t(c);
-    const size_t px = (size_t)W * H;
-    double *dp = t.up(p, px);
-    double *dq = t.up(q, px);
-    if (!t.ok) return finish(c, t);
-    launch_uniq_f64(dp, dq, W, H, to_mg(*own), to_mg(*oth), c->stream);
-    t.down(p, dp, px);
-    return finish(c, t);
-}
-
-extern "C" int rsm_stage_set_boundary(rsm_ctx *c, const int16_t *disp, const uint8_t *mask_own, int W, int H,
-                                      const rsm_boundary *own, const rsm_boundary *oth, int16_t *BL, int16_t *BR) {
-    if (!stage_ok(c, W, H) || !disp || !mask_own || !own || !oth || !BL || !BR) return RSM_E_INVALID;
-    if (degenerate(to_mg(*own))) return set_err(c, RSM_E_DEGENERATE_MARGIN, "YL>=YR || XL>=XR");
-    Tmp t(c);
-    const size_t px = (size_t)W * H;
-    StageArgs a = one_dir(c, W, H, 0, own, oth);
-    a.d[0].d16_in = t.up(disp, px);
-    a.d[0].mask_own = t.up(mask_own, px);
-    a.d[0].BL = t.alloc<int16_t>(px);
-    a.d[0].BR = t.alloc<int16_t>(px);
-    a.rf_list = t.alloc<uint32_t>(SETB_SCRATCH(W));
-    if (!t.ok) return finish(c, t);
-    launch_fill_i16(a.d[0].BL, px, (int16_t)-10000, c->stream);
-    launch_fill_i16(a.d[0].BR, px, (int16_t)10000, c->stream);
-    launch_set_boundary(a, c->stream);
-    t.down(BL, a.d[0].BL, px);
-    t.down(BR, a.d[0].BR, px);
-    return finish(c, t);
-}
-
-extern "C" int rsm_stage_rematch(rsm_ctx *c, const uint8_t *img_own, const uint8_t *img_oth, const uint8_t *mask_own,
-                                 const uint8_t *mask_oth, int W, int H, int r, const rsm_boundary *own,
-                                 const rsm_boundary *oth, int16_t *disp) {
-    if (!stage_ok(c, W, H) || !img_own || !img_oth || !mask_own || !mask_oth || !own || !oth || !disp) return RSM_E_INVALID;
-    if (degenerate(to_mg(*own))) return set_err(c, RSM_E_DEGENERATE_MARGIN, "YL>=YR || XL>=XR");
-    Tmp t(c);
-    const size_t px = (size_t)W * H;
-    MatchBufs b{};
-    if (!setup_match(c, t, img_own, img_oth, mask_own, mask_oth, W, H, r, b)) return finish(c, t);
-    StageArgs a = one_dir(c, W, H, r, own, oth);
-    bind_match(a, b);
-    a.d[0].d16_in = a.d[0].d16_out = t.up(disp, px);
-    a.d[0].BL = t.alloc<int16_t>(px);
-    a.d[0].BR = t.alloc<int16_t>(px);
-    if (!t.ok) return finish(c, t);
-    launch_set_boundary(a, c->stream, true);
-    launch_ncc_argmax(a, 2, c->stream);
-    t.down(disp, a.d[0].d16_in, px);
-    return finish(c, t);
-}
-
-extern "C" int rsm_stage_median(rsm_ctx *c, int16_t *disp, const uint8_t *mask_own, int W, int H,
-                                const rsm_boundary *own) {
-    if (!stage_ok(c, W, H) || !disp || !mask_own || !own) return RSM_E_INVALID;
-    Tmp t(c);
-    const size_t px = (size_t)W * H;
-    StageArgs a = one_dir(c, W, H, 0, own, nullptr);
-    a.d[0].d16_in = t.up(disp, px);
-    a.d[0].mask_own = t.up(mask_own, px);
-    a.d[0].d16_out = t.alloc<int16_t>(px);
-    if (!t.ok) return finish(c, t);
-    launch_fill_i16(a.d[0].d16_out, px, (int16_t)NOMATCH, c->stream);
-    launch_median(a, c->stream);
-    t.down(disp, a.d[0].d16_out, px);
-    return finish(c, t);
-}
-
-// The specified exp(-t) of DisparityRefine's smoothness weights (k_refine.hip: exp_neg) on an array: lets the parity
-// tests hold the device evaluation to the oracle's bit for bit over the whole argument range.
-static int stage_exp_neg(rsm_ctx *c, const double *t_in, int64_t n, double *out, int small_form) {
-    if (!c || !t_in || !out || n < 0) return RSM_E_INVALID;
-    if (n == 0) return RSM_OK;
-    if (hipSetDevice(c->device) != hipSuccess) return set_err(c, RSM_E_HIP, "hipSetDevice");
-    Tmp t(c);
-    const double *dt = t.up(t_in, (size_t)n);
-    double *dout = t.alloc<double>((size_t)n);
-    if (!t.ok) return finish(c, t);
-    launch_exp_neg(dt, dout, (long long)n, c->stream, small_form);
-    t.down(out, dout, (size_t)n);
-    return finish(c, t);
-}
-extern "C" int rsm_stage_exp_neg(rsm_ctx *c, const double *t_in, int64_t n, double *out) { return stage_exp_neg(c, t_in, n, out, 0); }
-// the form the time-skewed kernel's common path uses (no special-case code) on every argument below 512, the general one elsewhere
-extern "C" int rsm_stage_exp_neg_small(rsm_ctx *c, const double *t_in, int64_t n, double *out) { return stage_exp_neg(c, t_in, n, out, 1); }
-
-// k_refine_skew's unscaled division beside the compiler's (k_refine.hip: div_unscaled) on arrays of operands
-extern "C" int rsm_stage_div_unscaled(rsm_ctx *c, const double *a_in, const double *b_in, int64_t n, double *q_fast, double *q_ieee) {
-    if (!c || !a_in || !b_in || !q_fast || !q_ieee || n < 0) return RSM_E_INVALID;
-    if (n == 0) return RSM_OK;
-    if (hipSetDevice(c->device) != hipSuccess) return set_err(c, RSM_E_HIP, "hipSetDevice");
-    Tmp t(c);
-    const double *da = t.up(a_in, (size_t)n), *db = t.up(b_in, (size_t)n);
-    double *df = t.alloc<double>((size_t)n), *di = t.alloc<double>((size_t)n);
-    if (!t.ok) return finish(c, t);
-    launch_div_unscaled(da, db, df, di, (long long)n, c->stream);
-    t.down(q_fast, df, (size_t)n);
-    t.down(q_ieee, di, (size_t)n);
-    return finish(c, t);
-}
-
-// the cloud filter's trimmed sqrtf (k_filter.hip: sqrtf_rn) against the compiler's on the floats with bit patterns first .. first + n - 1
-extern "C" int rsm_stage_sqrt_check(rsm_ctx *c, uint32_t first_bits, int64_t n, int64_t *mismatches) {
-    if (!c || !mismatches || n < 0 || (uint64_t)first_bits + (uint64_t)n > (1ull << 32)) return RSM_E_INVALID;
-    *mismatches = 0;
-    if (n == 0) return RSM_OK;
-    if (hipSetDevice(c->device) != hipSuccess) return set_err(c, RSM_E_HIP, "hipSetDevice");
-    Tmp t(c);
-    unsigned long long *d = t.alloc<unsigned long long>(1);
-    if (!t.ok) return finish(c, t);
-    if (hipMemsetAsync(d, 0, sizeof(unsigned long long), c->stream) != hipSuccess) return set_err(c, RSM_E_HIP, "hipMemsetAsync");
-    launch_sqrt_check(first_bits, (long long)n, d, c->stream);
-    unsigned long long h = 0;
-    t.down(&h, d, 1);
-    const int rc = finish(c, t);
-    *mismatches = (int64_t)h;
-    return rc;
-}
-
+// the one parity entry point that stays here: it runs refine_sweeps, the pair path's own scheduler
 extern "C" int rsm_stage_refine(rsm_ctx *c, const int16_t *disp_in, const uint8_t *img_own, const uint8_t *img_oth,
                                 int W, int H, int iterations, double ws, const rsm_boundary *own, double *disp_out) {
     if (!stage_ok(c, W, H) || !disp_in || !img_own || !img_oth || !own || !disp_out || iterations < 0) return RSM_E_INVALID;
@@ -1663,65 +1078,6 @@ extern "C" int rsm_stage_refine(rsm_ctx *c, const int16_t *disp_in, const uint8_
     refine_sweeps(c, a, bufA, bufB, iterations, c->stream, false, &inB);
     d.f64_a = inB ? B : A; // the buffer the last sweep wrote
     t.down(disp_out, (const double *)d.f64_a, px);
-    return finish(c, t);
-}
-
-// DisparityRefine's matching costs xi (CStereoMatching.cpp:624-629) as the device restatements of the data term compute them:
-// lets the parity tests hold them to the compiled reference's own values (tests/golden: xi_table_*), bit for bit.
-extern "C" int rsm_stage_refine_xi(rsm_ctx *c, const uint8_t *img_own, const uint8_t *img_oth, int W, int H, int form, double *out) {
-    if (!stage_ok(c, W, H) || !img_own || !img_oth || !out || W < 3 || H < 3 || form < 0 || form > 2) return RSM_E_INVALID;
-    Tmp t(c);
-    const size_t px = (size_t)W * H, n = (size_t)(H - 2) * (W - 2) * (W - 2);
-    const uint8_t *io = t.up(img_own, px * 3), *it = t.up(img_oth, px * 3);
-    uint32_t *i4o = t.alloc<uint32_t>(px), *i4t = t.alloc<uint32_t>(px);
-    double *dout = t.alloc<double>(3 * n);
-    if (!t.ok) return finish(c, t);
-    launch_bgr_to_bgrx(io, W, H, i4o, c->stream);
-    launch_bgr_to_bgrx(it, W, H, i4t, c->stream);
-    launch_refine_xi(i4o, i4t, W, H, form, dout, c->stream);
-    t.down(out, (const double *)dout, 3 * n);
-    return finish(c, t);
-}
-
-extern "C" int rsm_stage_cloud(rsm_ctx *c, const double *disp, const uint8_t *mask_org, const uint8_t *img_own, int W,
-                               int H, const double *Q, double scale, const double *R_final, const double *T_final,
-                               const rsm_boundary *own, double *xyz, uint8_t *bgr, int64_t max_points,
-                               int64_t *n_points) {
-    if (!stage_ok(c, W, H) || !disp || !mask_org || !img_own || !Q || !R_final || !T_final || !own || !n_points)
-        return RSM_E_INVALID;
-    Tmp t(c);
-    const size_t px = (size_t)W * H;
-    const int ksize = (int)ceil(0.02 * H);
-    if (ksize < 1 || ksize > 4096) return RSM_E_INVALID;
-    std::vector<int> j1, j2;
-    ellipse_spans(ksize, j1, j2);
-    double q[16];
-    memcpy(q, Q, sizeof q);
-    for (int i = 0; i < 4; i++) q[i * 4 + 3] *= scale;
-    double *dd = t.up(disp, px);
-    uint8_t *dm = t.up(mask_org, px);
-    uint8_t *di = t.up(img_own, px * 3);
-    int *d1 = t.up(j1.data(), (size_t)ksize), *d2 = t.up(j2.data(), (size_t)ksize);
-    double *dq = t.up(q, 16), *dR = t.up(R_final, 9), *dT = t.up(T_final, 3);
-    int32_t *pre = t.alloc<int32_t>((size_t)(W + 1) * H);
-    int32_t *rc = t.alloc<int32_t>((size_t)H);
-    int64_t *ro = t.alloc<int64_t>((size_t)H);
-    int64_t *dn = t.alloc<int64_t>(1);
-    const int64_t cap = max_points > 0 ? max_points : 0;
-    double *dx = (xyz && cap) ? t.alloc<double>((size_t)cap * 3) : nullptr;
-    uint8_t *db = (bgr && cap) ? t.alloc<uint8_t>((size_t)cap * 3) : nullptr;
-    if (!t.ok) return finish(c, t);
-    launch_bad_prefix(dm, W, H, pre, c->stream);
-    uint8_t *fl = t.alloc<uint8_t>(px + CLOUD_BLOCKS(W, H));
-    if (!t.ok) return finish(c, t);
-    launch_bad_blocks(pre, W, H, fl + px, c->stream);
-    launch_cloud(dd, pre, di, W, H, ksize, d1, d2, dq, dR, dT, to_mg(*own), fl, fl + px, rc, ro, dn, dx, db, cap, c->stream);
-    int64_t n = 0;
-    t.down(&n, (const int64_t *)dn, 1);
-    *n_points = n;
-    const int64_t m = n < cap ? n : cap;
-    if (m > 0 && dx) t.down(xyz, (const double *)dx, (size_t)m * 3);
-    if (m > 0 && db) t.down(bgr, (const uint8_t *)db, (size_t)m * 3);
     return finish(c, t);
 }
 
@@ -1814,940 +1170,4 @@ extern "C" int rsm_rectify_pair(rsm_ctx *c, const rsm_rectify_in *in, int radius
     c->have_pair = true;
     c->have_result = false;
     return RSM_OK;
-}
-
-extern "C" int rsm_stage_rect_map(rsm_ctx *c, const double *A, const double *R, const double *newA, int W, int H,
-                                  int16_t *map1, uint16_t *map2) {
-    if (!stage_ok(c, W, H) || !A || !R || !newA || !map1 || !map2) return RSM_E_INVALID;
-    // (newA * R)^-1 through the same host routine the pipeline uses
-    double AR[9], ir[9];
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) AR[3 * i + j] = newA[3 * i] * R[j] + newA[3 * i + 1] * R[3 + j] + newA[3 * i + 2] * R[6 + j];
-    rectify_inv3(AR, ir);
-    Tmp t(c);
-    const size_t px = (size_t)W * H;
-    int16_t *d1 = t.alloc<int16_t>(px * 2);
-    uint16_t *d2 = t.alloc<uint16_t>(px);
-    if (!t.ok) return finish(c, t);
-    launch_rect_map(ir, A[0], A[4], A[2], A[5], W, H, d1, d2, c->stream);
-    t.down(map1, (const int16_t *)d1, px * 2);
-    t.down(map2, (const uint16_t *)d2, px);
-    return finish(c, t);
-}
-
-extern "C" int rsm_stage_remap(rsm_ctx *c, const uint8_t *src, int Ws, int Hs, int ch, const int16_t *map1,
-                               const uint16_t *map2, int W, int H, uint8_t *dst) {
-    if (!stage_ok(c, W, H) || !src || !map1 || !map2 || !dst || Ws <= 0 || Hs <= 0 || (ch != 1 && ch != 3)) return RSM_E_INVALID;
-    Tmp t(c);
-    const size_t px = (size_t)W * H;
-    uint8_t *ds = t.up(src, (size_t)Ws * Hs * ch);
-    int16_t *d1 = t.up(map1, px * 2);
-    uint16_t *d2 = t.up(map2, px);
-    uint8_t *dd = t.alloc<uint8_t>(px * ch);
-    if (!t.ok) return finish(c, t);
-    launch_remap(ds, Ws, Hs, ch, d1, d2, W, H, dd, c->stream);
-    t.down(dst, (const uint8_t *)dd, px * ch);
-    return finish(c, t);
-}
-
-extern "C" int rsm_stage_erode_gray(rsm_ctx *c, const uint8_t *src, int W, int H, int ksize, uint8_t *dst) {
-    if (!stage_ok(c, W, H) || !src || !dst || ksize < 1 || ksize > 255) return RSM_E_INVALID;
-    Tmp t(c);
-    const size_t px = (size_t)W * H;
-    std::vector<int> j1, j2;
-    ellipse_spans(ksize, j1, j2);
-    uint8_t *ds = t.up(src, px);
-    int *d1 = t.up(j1.data(), (size_t)ksize), *d2 = t.up(j2.data(), (size_t)ksize);
-    uint8_t *stb = t.alloc<uint8_t>(px * 9), *dd = t.alloc<uint8_t>(px);
-    if (!t.ok) return finish(c, t);
-    launch_erode_gray(ds, W, H, ksize, d1, d2, stb, dd, c->stream);
-    t.down(dst, (const uint8_t *)dd, px);
-    return finish(c, t);
-}
-
-// ---- per-pair cloud filter (CloudOptimization/CCloudOptimization.cpp:82-121) -------------------------------------
-static int filter_params_ok(const rsm_filter_params *p) {
-    return p && p->sor_mean_k >= 1 && p->sor_mean_k <= 100000 && p->normal_radius > 0.0 && p->sor_std_mul == p->sor_std_mul;
-}
-
-// the filter's buffers come from the context's arena: (re)sized for the cloud at hand, then the caller-visible ones first
-static int filter_buffers(rsm_ctx *c, int64_t n, bool want_normals, float **dx, int32_t **dk, float **df, float4 **dn, size_t extra = 0) {
-    if (!c->filt_arena) c->filt_arena = filter_arena_create();
-    const size_t own = (size_t)n * (12 + 4 + 12 + 16) + 4096 + extra;
-    if (filter_arena_reserve(c->filt_arena, own + filter_arena_bytes(n)) != RSM_OK)
-        return set_err(c, RSM_E_NOMEM, "cloud filter: no device memory for %lld points", (long long)n);
-    *dx = (float *)filter_arena_alloc(c->filt_arena, sizeof(float) * 3 * (size_t)n);
-    *dk = (int32_t *)filter_arena_alloc(c->filt_arena, sizeof(int32_t) * (size_t)n);
-    *df = (float *)filter_arena_alloc(c->filt_arena, sizeof(float) * 3 * (size_t)n);
-    *dn = want_normals ? (float4 *)filter_arena_alloc(c->filt_arena, sizeof(float4) * (size_t)n) : nullptr;
-    if (!*dx || !*dk || !*df || (want_normals && !*dn)) return set_err(c, RSM_E_NOMEM, "cloud filter: arena too small");
-    return RSM_OK;
-}
-
-extern "C" int rsm_filter_cloud(rsm_ctx *c, const float *xyz, int64_t n, const rsm_filter_params *prm, int32_t *kept_index,
-                                float *normals, int64_t *n_kept, double *stats) {
-    if (!c || n < 0 || (n > 0 && (!xyz || !kept_index)) || !n_kept || !filter_params_ok(prm)) return RSM_E_INVALID;
-    HIPCHK(c, hipSetDevice(c->device));
-    *n_kept = 0;
-    if (n == 0) return RSM_OK;
-    Tmp t(c);
-    float *dx, *df;
-    int32_t *dk;
-    float4 *dn;
-    const int sb = filter_buffers(c, n, normals != nullptr, &dx, &dk, &df, &dn);
-    if (sb != RSM_OK) return sb;
-    HIPCHK(c, hipMemcpyAsync(dx, xyz, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    const int s = filter_cloud_device(c->filt_arena, dx, n, prm->sor_mean_k, prm->sor_std_mul, prm->normal_radius, prm->cam_center, dk, df, dn,
-                                      n_kept, stats, c->stream, nullptr, &c->filt_route);
-    if (s != RSM_OK) return set_err(c, s, "cloud filter failed");
-    if (*n_kept > 0) {
-        t.down(kept_index, (const int32_t *)dk, (size_t)*n_kept);
-        if (normals) t.down(normals, (const float *)dn, (size_t)4 * *n_kept);
-    }
-    return finish(c, t);
-}
-
-// The stream of the per-pair cloud filter.  With several pairs in flight on a GPU the filter of one pair runs beside the matching of
-// the others, and its large kernels (21 000 workgroups of 75 KB LDS) took the compute units the matchers' dependent launches -- the
-// top level's refine sweeps, the loop's critical path -- were waiting for: 29.5 ms per pair in the adapter's loop for 15.3 ms of
-// matching + 9.5 ms of filter.  On a stream of the lowest priority the dispatcher hands compute units to the matchers first.
-static hipStream_t filter_stream(rsm_ctx *c) {
-    if (!c->opt_filter_low_priority) return c->stream;
-    if (!c->stream_filter) {
-        int least = 0, greatest = 0;
-        if (hipDeviceGetStreamPriorityRange(&least, &greatest) != hipSuccess || hipStreamCreateWithPriority(&c->stream_filter, hipStreamNonBlocking, least) != hipSuccess ||
-            hipEventCreateWithFlags(&c->ev_filter, hipEventDisableTiming) != hipSuccess) {
-            (void)hipGetLastError();
-            if (c->stream_filter) (void)hipStreamDestroy(c->stream_filter);
-            c->stream_filter = nullptr;
-            return c->stream;
-        }
-    }
-    if (hipEventRecord(c->ev_filter, c->stream) != hipSuccess || hipStreamWaitEvent(c->stream_filter, c->ev_filter, 0) != hipSuccess) return c->stream;
-    return c->stream_filter;
-}
-
-extern "C" int rsm_filter_last_cloud(rsm_ctx *c, const rsm_filter_params *prm, rsm_point16 *d_points, float *d_normals,
-                                     int64_t max_points, int64_t *n_kept, double *stats) {
-    if (!c || !n_kept || !filter_params_ok(prm)) return RSM_E_INVALID;
-    if (!c->have_result) return set_err(c, RSM_E_STATE, "no result");
-    HIPCHK(c, hipSetDevice(c->device));
-    *n_kept = 0;
-    const int64_t n = c->n_points;
-    if (n == 0) return RSM_OK;
-    Tmp t(c);
-    float *dx, *df;
-    int32_t *dk;
-    float4 *dn;
-    // The cloud is the depth map this context just made: its pixel lattice (k_cloud's flags and row offsets are still in place)
-    // decides most k-nearest queries (k_filter.hip: k_sor_window).  Needs R_final to be a rotation (distances in the cloud =
-    // distances in the camera frame); anything else takes the generic search.
-    const int k = c->N - 1;
-    const Mg &mg = c->mg[k][0];
-    FilterLattice lat{};
-    bool use_lat = c->opt_filter_window && mg.XR >= mg.XL && mg.YR >= mg.YL;
-    if (use_lat) {
-        const double *R = c->in.R_final;
-        for (int i = 0; i < 3 && use_lat; i++)
-            for (int j = 0; j < 3; j++) {
-                double d = 0.0;
-                for (int l = 0; l < 3; l++) d += R[3 * l + i] * R[3 * l + j];
-                if (!(fabs(d - (i == j ? 1.0 : 0.0)) < 1e-9)) use_lat = false;
-            }
-        const double scale = (double)c->Wk[0] / c->in.origin_width * (1 << k); // .cpp:692
-        lat.flags = c->cloud_flags;
-        lat.row_offset = c->row_offset;
-        lat.W = c->Wk[k];
-        lat.XL = mg.XL, lat.XR = mg.XR, lat.YL = mg.YL, lat.YR = mg.YR;
-        lat.xyz64 = c->xyz;
-        lat.qz = c->in.Q[11] * scale;
-        memcpy(lat.R, c->in.R_final, sizeof lat.R);
-        memcpy(lat.T, c->in.T_final, sizeof lat.T);
-        if (!(fabs(lat.qz) > 0.0) || !std::isfinite(lat.qz)) use_lat = false;
-    }
-    int left = -1, tile_left = -1;
-    lat.undecided_out = &left;
-    lat.tile_left_out = &tile_left;
-    lat.list_pass = c->opt_filter_list;
-    lat.wg_max = c->opt_filter_wg_max;
-    lat.normals_wmax = std::min(c->opt_filter_normals_window, 40);
-    c->filt_normals[0] = 0, c->filt_normals[1] = -1;
-    lat.normals_out = c->filt_normals;
-    int used_radius = 0;
-    lat.radius_out = &used_radius;
-    lat.radius = c->opt_filter_window <= 1 ? 0 : (c->opt_filter_window <= 7 ? 7 : (c->opt_filter_window <= 12 ? 12 : (c->opt_filter_window <= 16 ? 16 : (c->opt_filter_window <= 20 ? 20 : 24))));
-    // The probed radius is a property of the rig (how thick its clouds are in pixel spacings): a context remembers what the probe
-    // chose for its last cloud and skips the three probe launches and their host round trips (0.6 ms of C2's 14.8) while the
-    // choice keeps deciding most queries; every 8th call, a different k, a different image size or a set_option probes again.
-    const bool memo_ok = c->opt_filter_window == 1 && c->filt_memo_radius > 0 && c->filt_memo_k == prm->sor_mean_k && c->filt_memo_w == c->Wk[k] &&
-                         c->filt_memo_h == c->Hk[k] && c->filt_memo_uses < 7;
-    if (use_lat && memo_ok) lat.radius = c->filt_memo_radius;
-    const int sb = filter_buffers(c, n, d_normals != nullptr, &dx, &dk, &df, &dn, use_lat ? cloud_lattice_bytes(mg.XL, mg.XR, mg.YL, mg.YR) + (size_t)n * 4 + 8192 : 0);
-    if (sb != RSM_OK) return sb;
-    const hipStream_t fs = filter_stream(c);
-    launch_f64_to_f32x3(c->xyz, n, dx, fs); // InsertPoint's cast, CCloudOptimization.cpp:61
-    int64_t m = 0;
-    const int s = filter_cloud_device(c->filt_arena, dx, n, prm->sor_mean_k, prm->sor_std_mul, prm->normal_radius, prm->cam_center, dk, df, dn, &m, stats,
-                                      fs, use_lat ? &lat : nullptr, &c->filt_route);
-    if (s != RSM_OK) return set_err(c, s, "cloud filter failed");
-    if (use_lat && c->opt_filter_window == 1) {
-        if (memo_ok && tile_left >= 0 && (double)tile_left <= 0.3 * (double)n) c->filt_memo_uses++; // still a good choice
-        else if (!memo_ok && used_radius > 0) { // a fresh probe's choice
-            c->filt_memo_radius = used_radius;
-            c->filt_memo_k = prm->sor_mean_k;
-            c->filt_memo_w = c->Wk[k];
-            c->filt_memo_h = c->Hk[k];
-            c->filt_memo_uses = 0;
-        } else c->filt_memo_radius = 0; // left too much over (or no window at all): probe next time
-    }
-    c->filt_info[0] = left >= 0 ? used_radius : 0;
-    c->filt_info[1] = left >= 0 ? left : 0;
-    c->filt_tile_left = tile_left >= 0 ? tile_left : 0;
-    c->filt_info[2] = n;
-    c->filt_info[3] = m;
-    if (m > max_points) return set_err(c, RSM_E_INVALID, "rsm_filter_last_cloud: %lld points survive, capacity %lld", (long long)m, (long long)max_points);
-    if (m > 0 && d_points) launch_pack_filtered16(c->xyz, c->bgr, dk, m, d_points, fs);
-    if (m > 0 && d_normals) HIPCHK(c, hipMemcpyAsync(d_normals, dn, sizeof(float4) * (size_t)m, hipMemcpyDeviceToDevice, fs));
-    *n_kept = m;
-    if (fs != c->stream) HIPCHK(c, hipStreamSynchronize(fs));
-    return finish(c, t);
-}
-
-extern "C" int rsm_filter_last_normals_info(rsm_ctx *c, int64_t info[2]) {
-    if (!c || !info) return RSM_E_INVALID;
-    info[0] = c->filt_normals[0];
-    info[1] = c->filt_normals[1];
-    return RSM_OK;
-}
-
-extern "C" int rsm_filter_last_info(rsm_ctx *c, int64_t info[4]) {
-    if (!c || !info) return RSM_E_INVALID;
-    memcpy(info, c->filt_info, sizeof c->filt_info);
-    return RSM_OK;
-}
-
-extern "C" int rsm_filter_last_grid(rsm_ctx *c, double grid[4], int64_t info[6]) {
-    if (!c || !grid || !info) return RSM_E_INVALID;
-    const FilterRoute &r = c->filt_route;
-    grid[0] = r.h;
-    for (int a = 0; a < 3; a++) {
-        grid[1 + a] = r.origin[a];
-        info[a] = r.cells[a];
-    }
-    info[3] = r.levels;
-    info[4] = r.kind0;
-    info[5] = r.kinds;
-    return RSM_OK;
-}
-
-extern "C" int rsm_filter_last_cloud_host(rsm_ctx *c, const rsm_filter_params *prm, rsm_point16 *h_points, float *h_normals,
-                                          int64_t max_points, int64_t *n_kept, double *stats) {
-    if (!c || !n_kept || !h_points || max_points < 0) return RSM_E_INVALID;
-    if (!c->have_result) return set_err(c, RSM_E_STATE, "no result");
-    HIPCHK(c, hipSetDevice(c->device));
-    if (!c->pack16) {
-        const int s = dalloc(c, &c->pack16, c->cap_px);
-        if (s != RSM_OK) return s;
-    }
-    if (h_normals && !c->pack_nrm) {
-        const int s = dalloc(c, &c->pack_nrm, c->cap_px * 4);
-        if (s != RSM_OK) return s;
-    }
-    const int64_t cap = (int64_t)c->cap_px < max_points ? (int64_t)c->cap_px : max_points;
-    const int s = rsm_filter_last_cloud(c, prm, c->pack16, h_normals ? c->pack_nrm : nullptr, cap, n_kept, stats);
-    if (s != RSM_OK) return s;
-    const size_t m = (size_t)*n_kept;
-    if (m > 0) {
-        HIPCHK(c, hipMemcpyAsync(h_points, c->pack16, m * sizeof(rsm_point16), hipMemcpyDeviceToHost, c->stream));
-        if (h_normals) HIPCHK(c, hipMemcpyAsync(h_normals, c->pack_nrm, m * 4 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    return RSM_OK;
-}
-
-// ---- moving-least-squares smoothing (CCloudOptimization::run, CloudOptimization/CCloudOptimization.cpp:348-389) -----------
-static int mls_args_ok(rsm_ctx *c, int64_t n, const rsm_mls_params *p, const void *out_xyz, const void *out_nrm, const void *src_index,
-                       const int64_t *n_out) {
-    return c && p && n_out && out_xyz && out_nrm && src_index && n >= 0 && n <= (int64_t)INT32_MAX && std::isfinite(p->search_radius) &&
-           p->search_radius > 0.0 && p->polynomial_order >= 0 && p->polynomial_order <= 2;
-}
-// (re)sizes the context's filter arena for an MLS call on n points plus `own` bytes of the caller's
-static int mls_reserve(rsm_ctx *c, int64_t n, size_t own) {
-    if (!c->filt_arena) c->filt_arena = filter_arena_create();
-    if (filter_arena_reserve(c->filt_arena, own + 4096 + mls_arena_bytes(n)) != RSM_OK)
-        return set_err(c, RSM_E_NOMEM, "mls: no device memory for %lld points", (long long)n);
-    return RSM_OK;
-}
-
-extern "C" int rsm_mls_cloud_device(rsm_ctx *c, const rsm_point16 *d_points, int64_t n, const float *d_ref_normals, const rsm_mls_params *p,
-                                    float *d_out_xyz, float *d_out_normals, int32_t *d_src_index, int64_t *n_out) {
-    if (!mls_args_ok(c, n, p, d_out_xyz, d_out_normals, d_src_index, n_out) || (n > 0 && !d_points)) return RSM_E_INVALID;
-    *n_out = 0;
-    if (n == 0) return RSM_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    int s = mls_reserve(c, n, sizeof(float) * 3 * (size_t)n);
-    if (s != RSM_OK) return s;
-    float *dx = (float *)filter_arena_alloc(c->filt_arena, sizeof(float) * 3 * (size_t)n);
-    if (!dx) return set_err(c, RSM_E_NOMEM, "mls: arena too small");
-    launch_point16_xyz(d_points, n, dx, c->stream);
-    s = mls_cloud_device(c->filt_arena, dx, n, (const float4 *)d_ref_normals, p->search_radius, p->polynomial_order, d_out_xyz, d_out_normals,
-                         d_src_index, n_out, c->stream);
-    if (s != RSM_OK) return set_err(c, s, "mls failed");
-    return RSM_OK;
-}
-
-extern "C" int rsm_mls_cloud(rsm_ctx *c, const float *xyz, int64_t n, const float *ref_normals, const rsm_mls_params *p, float *out_xyz,
-                             float *out_normals, int32_t *src_index, int64_t *n_out) {
-    if (!mls_args_ok(c, n, p, out_xyz, out_normals, src_index, n_out) || (n > 0 && !xyz)) return RSM_E_INVALID;
-    *n_out = 0;
-    if (n == 0) return RSM_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t bx = sizeof(float) * 3 * (size_t)n, bn = sizeof(float) * 4 * (size_t)n, bi = sizeof(int32_t) * (size_t)n;
-    int s = mls_reserve(c, n, 2 * bx + (ref_normals ? bn : 0) + bn + bi + 5 * 256);
-    if (s != RSM_OK) return s;
-    FilterArena *A = c->filt_arena;
-    float *dx = (float *)filter_arena_alloc(A, bx), *dox = (float *)filter_arena_alloc(A, bx), *don = (float *)filter_arena_alloc(A, bn);
-    int32_t *doi = (int32_t *)filter_arena_alloc(A, bi);
-    float *dr = ref_normals ? (float *)filter_arena_alloc(A, bn) : nullptr;
-    if (!dx || !dox || !don || !doi || (ref_normals && !dr)) return set_err(c, RSM_E_NOMEM, "mls: arena too small");
-    HIPCHK(c, hipMemcpyAsync(dx, xyz, bx, hipMemcpyHostToDevice, c->stream));
-    if (dr) HIPCHK(c, hipMemcpyAsync(dr, ref_normals, bn, hipMemcpyHostToDevice, c->stream));
-    s = mls_cloud_device(A, dx, n, (const float4 *)dr, p->search_radius, p->polynomial_order, dox, don, doi, n_out, c->stream);
-    if (s != RSM_OK) return set_err(c, s, "mls failed");
-    const size_t m = (size_t)*n_out;
-    if (m > 0) {
-        HIPCHK(c, hipMemcpyAsync(out_xyz, dox, sizeof(float) * 3 * m, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(out_normals, don, sizeof(float) * 4 * m, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(src_index, doi, sizeof(int32_t) * m, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    return RSM_OK;
-}
-
-// ---- multi-view duplicate deletion (the isdelete branch of CCloudOptimization::run, CCloudOptimization.cpp:152-346) ----------------
-static int dedup_args_ok(rsm_ctx *c, int64_t n, const rsm_dedup_view *v, int np, const void *index, const int64_t *n_out, const int64_t *stats) {
-    if (!c || !index || !n_out || !stats || n < 0 || n > (int64_t)INT32_MAX) return 0;
-    if (n > 0 && (np < 1 || !v)) return 0;
-    return np < 1 || (v && dedup_views_ok(v, np));
-}
-static int dedup_reserve(rsm_ctx *c, const rsm_dedup_view *v, int np, int64_t n, size_t own) {
-    if (!c->filt_arena) c->filt_arena = filter_arena_create();
-    if (filter_arena_reserve(c->filt_arena, own + 4096 + dedup_arena_bytes(v, np, n)) != RSM_OK)
-        return set_err(c, RSM_E_NOMEM, "dedup: no device memory for %lld points", (long long)n);
-    return RSM_OK;
-}
-
-extern "C" int rsm_dedup_cloud_device(rsm_ctx *c, const rsm_point16 *d_points, const float *d_normals4, int64_t n, const rsm_dedup_view *views,
-                                      int n_pairs, int32_t *d_index, rsm_point16 *d_out_points, float *d_out_normals, int64_t *n_out,
-                                      int64_t stats[4]) {
-    if (!dedup_args_ok(c, n, views, n_pairs, d_index, n_out, stats) || (n > 0 && (!d_points || !d_normals4))) return RSM_E_INVALID;
-    *n_out = 0;
-    for (int t = 0; t < 4; t++) stats[t] = 0;
-    if (n == 0) return RSM_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    int s = dedup_reserve(c, views, n_pairs, n, 0);
-    if (s != RSM_OK) return s;
-    s = dedup_cloud_device(c->filt_arena, (const float *)d_points, 4, (const float4 *)d_normals4, n, views, n_pairs, d_index, n_out, stats, c->stream);
-    if (s != RSM_OK) return set_err(c, s, "dedup failed");
-    if (*n_out > 0 && (d_out_points || d_out_normals)) {
-        launch_dedup_gather(d_points, d_normals4, d_index, *n_out, d_out_points, d_out_normals, c->stream);
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipGetLastError());
-    }
-    return RSM_OK;
-}
-
-extern "C" int rsm_dedup_cloud(rsm_ctx *c, const float *xyz, const float *normals4, int64_t n, const rsm_dedup_view *views, int n_pairs,
-                               int32_t *index, int64_t *n_out, int64_t stats[4]) {
-    if (!dedup_args_ok(c, n, views, n_pairs, index, n_out, stats) || (n > 0 && (!xyz || !normals4))) return RSM_E_INVALID;
-    *n_out = 0;
-    for (int t = 0; t < 4; t++) stats[t] = 0;
-    if (n == 0) return RSM_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t bx = sizeof(float) * 3 * (size_t)n, bn = sizeof(float) * 4 * (size_t)n, bi = sizeof(int32_t) * (size_t)n;
-    int s = dedup_reserve(c, views, n_pairs, n, bx + bn + bi + 3 * 256);
-    if (s != RSM_OK) return s;
-    FilterArena *A = c->filt_arena;
-    float *dx = (float *)filter_arena_alloc(A, bx), *dn = (float *)filter_arena_alloc(A, bn);
-    int32_t *di = (int32_t *)filter_arena_alloc(A, bi);
-    if (!dx || !dn || !di) return set_err(c, RSM_E_NOMEM, "dedup: arena too small");
-    HIPCHK(c, hipMemcpyAsync(dx, xyz, bx, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(dn, normals4, bn, hipMemcpyHostToDevice, c->stream));
-    s = dedup_cloud_device(A, dx, 3, (const float4 *)dn, n, views, n_pairs, di, n_out, stats, c->stream);
-    if (s != RSM_OK) return set_err(c, s, "dedup failed");
-    if (*n_out > 0) {
-        HIPCHK(c, hipMemcpyAsync(index, di, sizeof(int32_t) * (size_t)*n_out, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    return RSM_OK;
-}
-
-// ---- dense-grid Poisson surface and trim (k_poisson.hip) -----------------------------------------------------------
-static int poisson_params_ok(rsm_ctx *c, const rsm_poisson_params *p) {
-    if (!p) return set_err(c, RSM_E_INVALID, "poisson: params is NULL");
-    if (p->depth < 5 || p->depth > 9) return set_err(c, RSM_E_INVALID, "poisson: depth %d outside 5..9", p->depth);
-    if (!std::isfinite(p->scale) || p->scale < 1.0) return set_err(c, RSM_E_INVALID, "poisson: scale %g not finite or < 1", p->scale);
-    if (!(p->rel_residual > 0.0 && p->rel_residual < 1.0)) return set_err(c, RSM_E_INVALID, "poisson: rel_residual %g not in (0, 1)", p->rel_residual);
-    if (p->max_cycles < 1) return set_err(c, RSM_E_INVALID, "poisson: max_cycles %d < 1", p->max_cycles);
-    if (p->trim_cells < 0) return set_err(c, RSM_E_INVALID, "poisson: trim_cells %d < 0", p->trim_cells);
-    return RSM_OK;
-}
-static int poisson_n_ok(rsm_ctx *c, int64_t n) {
-    if (n < 0 || n > (int64_t)INT32_MAX) return set_err(c, RSM_E_INVALID, "poisson: n %lld outside 0..INT32_MAX", (long long)n);
-    return RSM_OK;
-}
-static int poisson_fail(rsm_ctx *c, int s, const char *what) {
-    return set_err(c, s, "poisson: %s failed%s%s", what, s == RSM_E_HIP ? ": " : "", s == RSM_E_HIP ? hipGetErrorString(hipGetLastError()) : "");
-}
-
-// the eight steps on device buffers; the mesh lands in c->pmesh
-static int poisson_run(rsm_ctx *c, const float *d_xyz, const float *d_nrm, int64_t n, const rsm_poisson_params *p, int64_t *n_vertices,
-                       int64_t *n_faces, double *stats) {
-    double st[RSM_POISSON_STATS] = {0};
-    *n_vertices = *n_faces = 0;
-    poisson_mesh_free(&c->pmesh);
-    double grid[4];
-    int64_t counts[2];
-    int s = poisson_grid_device(d_xyz, d_nrm, n, p->depth, p->scale, grid, counts, c->stream);
-    if (s != RSM_OK) return poisson_fail(c, s, "bounding box");
-    st[0] = (double)counts[0];
-    st[1] = (double)counts[1];
-    st[9] = (double)(1 << p->depth);
-    int solved = RSM_OK;
-    if (grid[3] > 0.0) {
-        const size_t N3 = (size_t)1 << (3 * p->depth);
-        Tmp T(c);
-        float *b = T.alloc<float>(N3), *chi = T.alloc<float>(N3);
-        uint8_t *occ = T.alloc<uint8_t>(N3);
-        if (!b || !chi || !occ) return set_err(c, RSM_E_NOMEM, "poisson: no device memory for depth %d", p->depth);
-        if ((s = poisson_rhs_device(d_xyz, d_nrm, n, p->depth, grid, b, nullptr, occ, c->stream)) != RSM_OK) return poisson_fail(c, s, "right-hand side");
-        double res = 0.0, iso = 0.0;
-        int cycles = 0;
-        solved = poisson_solve_device(b, p->depth, p->rel_residual, p->max_cycles, chi, &res, &cycles, nullptr, c->stream);
-        if (solved < 0) return poisson_fail(c, solved, "solve");
-        if ((s = poisson_iso_device(d_xyz, d_nrm, n, counts[0], chi, p->depth, grid, &iso, c->stream)) != RSM_OK) return poisson_fail(c, s, "iso-value");
-        int64_t un[2];
-        if ((s = poisson_extract_device(chi, p->depth, iso, grid, occ, p->trim_cells, &c->pmesh, un, c->stream)) != RSM_OK)
-            return poisson_fail(c, s, "extraction");
-        st[2] = res;
-        st[3] = (double)cycles;
-        st[4] = iso;
-        for (int a = 0; a < 4; a++) st[5 + a] = grid[a];
-        st[10] = (double)un[0];
-        st[11] = (double)un[1];
-        if (solved == RSM_W_NOT_CONVERGED) set_err(c, solved, "poisson: residual %g after %d cycles (rel_residual %g)", res, cycles, p->rel_residual);
-    }
-    *n_vertices = c->pmesh.nv;
-    *n_faces = c->pmesh.nf;
-    if (stats) memcpy(stats, st, sizeof st);
-    return solved;
-}
-
-extern "C" int rsm_poisson_mesh_device(rsm_ctx *c, const float *d_xyz, const float *d_normals4, int64_t n, const rsm_poisson_params *p,
-                                       int64_t *n_vertices, int64_t *n_faces, double *stats) {
-    if (!c) return RSM_E_INVALID;
-    int s = poisson_params_ok(c, p);
-    if (s != RSM_OK || (s = poisson_n_ok(c, n)) != RSM_OK) return s;
-    if (!n_vertices || !n_faces || (n > 0 && (!d_xyz || !d_normals4))) return set_err(c, RSM_E_INVALID, "poisson: a NULL pointer");
-    HIPCHK(c, hipSetDevice(c->device));
-    return poisson_run(c, d_xyz, d_normals4, n, p, n_vertices, n_faces, stats);
-}
-
-extern "C" int rsm_poisson_mesh(rsm_ctx *c, const float *xyz, const float *normals4, int64_t n, const rsm_poisson_params *p, int64_t *n_vertices,
-                                int64_t *n_faces, double *stats) {
-    if (!c) return RSM_E_INVALID;
-    int s = poisson_params_ok(c, p);
-    if (s != RSM_OK || (s = poisson_n_ok(c, n)) != RSM_OK) return s;
-    if (!n_vertices || !n_faces || (n > 0 && (!xyz || !normals4))) return set_err(c, RSM_E_INVALID, "poisson: a NULL pointer");
-    HIPCHK(c, hipSetDevice(c->device));
-    Tmp T(c);
-    float *dx = T.alloc<float>(3 * (size_t)n), *dn = T.alloc<float>(4 * (size_t)n);
-    if (!dx || !dn) return set_err(c, RSM_E_NOMEM, "poisson: no device memory for %lld samples", (long long)n);
-    if (n > 0) {
-        HIPCHK(c, hipMemcpyAsync(dx, xyz, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(dn, normals4, sizeof(float) * 4 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    return poisson_run(c, dx, dn, n, p, n_vertices, n_faces, stats);
-}
-
-extern "C" int rsm_poisson_last_mesh_device(rsm_ctx *c, float *d_xyz, int32_t *d_faces) {
-    if (!c) return RSM_E_INVALID;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (d_xyz && c->pmesh.nv > 0) HIPCHK(c, hipMemcpyAsync(d_xyz, c->pmesh.d_v, sizeof(float) * 3 * (size_t)c->pmesh.nv, hipMemcpyDeviceToDevice, c->stream));
-    if (d_faces && c->pmesh.nf > 0) HIPCHK(c, hipMemcpyAsync(d_faces, c->pmesh.d_f, sizeof(int32_t) * 3 * (size_t)c->pmesh.nf, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RSM_OK;
-}
-
-extern "C" int rsm_poisson_last_mesh(rsm_ctx *c, float *xyz, int32_t *faces) {
-    if (!c) return RSM_E_INVALID;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (xyz && c->pmesh.nv > 0) HIPCHK(c, hipMemcpyAsync(xyz, c->pmesh.d_v, sizeof(float) * 3 * (size_t)c->pmesh.nv, hipMemcpyDeviceToHost, c->stream));
-    if (faces && c->pmesh.nf > 0) HIPCHK(c, hipMemcpyAsync(faces, c->pmesh.d_f, sizeof(int32_t) * 3 * (size_t)c->pmesh.nf, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RSM_OK;
-}
-
-extern "C" int rsm_stage_poisson_rhs(rsm_ctx *c, const float *xyz, const float *normals4, int64_t n, const rsm_poisson_params *p, double grid[4],
-                                     double *b, uint8_t *occ, int64_t counts[2]) {
-    if (!c) return RSM_E_INVALID;
-    int s = poisson_params_ok(c, p);
-    if (s != RSM_OK || (s = poisson_n_ok(c, n)) != RSM_OK) return s;
-    if (!grid || !b || !occ || !counts || (n > 0 && (!xyz || !normals4))) return set_err(c, RSM_E_INVALID, "poisson: a NULL pointer");
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t N3 = (size_t)1 << (3 * p->depth);
-    Tmp T(c);
-    float *dx = T.alloc<float>(3 * (size_t)n), *dn = T.alloc<float>(4 * (size_t)n);
-    double *db = T.alloc<double>(N3);
-    uint8_t *docc = T.alloc<uint8_t>(N3);
-    if (!dx || !dn || !db || !docc) return set_err(c, RSM_E_NOMEM, "poisson: no device memory");
-    if (n > 0) {
-        HIPCHK(c, hipMemcpyAsync(dx, xyz, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(dn, normals4, sizeof(float) * 4 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-    }
-    if ((s = poisson_grid_device(dx, dn, n, p->depth, p->scale, grid, counts, c->stream)) != RSM_OK) return poisson_fail(c, s, "bounding box");
-    if (!(grid[3] > 0.0)) {
-        memset(b, 0, sizeof(double) * N3);
-        memset(occ, 0, N3);
-        return RSM_OK;
-    }
-    if ((s = poisson_rhs_device(dx, dn, n, p->depth, grid, nullptr, db, docc, c->stream)) != RSM_OK) return poisson_fail(c, s, "right-hand side");
-    HIPCHK(c, hipMemcpyAsync(b, db, sizeof(double) * N3, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(occ, docc, N3, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RSM_OK;
-}
-
-extern "C" int rsm_stage_poisson_solve(rsm_ctx *c, const float *b, int depth, double rel_residual, int max_cycles, float *chi, double *residual,
-                                       int *cycles, double *history) {
-    if (!c) return RSM_E_INVALID;
-    const rsm_poisson_params p{depth, 1.0, rel_residual, max_cycles, 0};
-    int s = poisson_params_ok(c, &p);
-    if (s != RSM_OK) return s;
-    if (!b || !chi || !residual || !cycles) return set_err(c, RSM_E_INVALID, "poisson: a NULL pointer");
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t N3 = (size_t)1 << (3 * depth);
-    Tmp T(c);
-    float *db = T.alloc<float>(N3), *dchi = T.alloc<float>(N3);
-    if (!db || !dchi) return set_err(c, RSM_E_NOMEM, "poisson: no device memory");
-    HIPCHK(c, hipMemcpyAsync(db, b, sizeof(float) * N3, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    s = poisson_solve_device(db, depth, rel_residual, max_cycles, dchi, residual, cycles, history, c->stream);
-    if (s < 0) return poisson_fail(c, s, "solve");
-    HIPCHK(c, hipMemcpyAsync(chi, dchi, sizeof(float) * N3, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return s;
-}
-
-extern "C" int rsm_stage_iso_mesh(rsm_ctx *c, const float *chi, int depth, double iso, const double grid[4], const uint8_t *occ, int trim_cells,
-                                  int64_t *n_vertices, int64_t *n_faces) {
-    if (!c) return RSM_E_INVALID;
-    const rsm_poisson_params p{depth, 1.0, 0.5, 1, trim_cells};
-    int s = poisson_params_ok(c, &p);
-    if (s != RSM_OK) return s;
-    if (!chi || !grid || !n_vertices || !n_faces || (trim_cells > 0 && !occ)) return set_err(c, RSM_E_INVALID, "poisson: a NULL pointer");
-    if (!std::isfinite(iso) || !std::isfinite(grid[0]) || !std::isfinite(grid[1]) || !std::isfinite(grid[2]) || !(grid[3] > 0.0) || !std::isfinite(grid[3]))
-        return set_err(c, RSM_E_INVALID, "poisson: iso or grid not finite, or h <= 0");
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t N3 = (size_t)1 << (3 * depth);
-    Tmp T(c);
-    float *dchi = T.alloc<float>(N3);
-    uint8_t *docc = occ ? T.alloc<uint8_t>(N3) : nullptr;
-    if (!dchi || (occ && !docc)) return set_err(c, RSM_E_NOMEM, "poisson: no device memory");
-    HIPCHK(c, hipMemcpyAsync(dchi, chi, sizeof(float) * N3, hipMemcpyHostToDevice, c->stream));
-    if (occ) HIPCHK(c, hipMemcpyAsync(docc, occ, N3, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    int64_t un[2];
-    if ((s = poisson_extract_device(dchi, depth, iso, grid, docc, trim_cells, &c->pmesh, un, c->stream)) != RSM_OK) return poisson_fail(c, s, "extraction");
-    *n_vertices = c->pmesh.nv;
-    *n_faces = c->pmesh.nf;
-    return RSM_OK;
-}
-
-// ---- smoothing and clean-up of the surface (k_meshclean.hip) ------------------------------------------------------------
-static int meshclean_params_ok(rsm_ctx *c, const rsm_mesh_clean_params *p) {
-    if (!p) return set_err(c, RSM_E_INVALID, "mesh_clean: params is NULL");
-    if (p->smooth_steps < 0) return set_err(c, RSM_E_INVALID, "mesh_clean: smooth_steps %d < 0", p->smooth_steps);
-    if (p->cotangent != 0 && p->cotangent != 1) return set_err(c, RSM_E_INVALID, "mesh_clean: cotangent %d not 0 or 1", p->cotangent);
-    if (p->boundary != 0 && p->boundary != 1) return set_err(c, RSM_E_INVALID, "mesh_clean: boundary %d not 0 or 1", p->boundary);
-    if (!std::isfinite(p->min_piece) || p->min_piece < 0.0) return set_err(c, RSM_E_INVALID, "mesh_clean: min_piece %g negative or not finite", p->min_piece);
-    if (p->min_piece_relative != 0 && p->min_piece_relative != 1)
-        return set_err(c, RSM_E_INVALID, "mesh_clean: min_piece_relative %d not 0 or 1", p->min_piece_relative);
-    if (p->flags & ~(RSM_MESH_CLEAN_DUPLICATES | RSM_MESH_CLEAN_ZERO_AREA | RSM_MESH_CLEAN_NONMANIFOLD))
-        return set_err(c, RSM_E_INVALID, "mesh_clean: flags 0x%x has an unknown bit", p->flags);
-    return RSM_OK;
-}
-static int meshclean_counts_ok(rsm_ctx *c, int64_t nv, int64_t nf) {
-    if (nv < 0 || nv > (int64_t)INT32_MAX) return set_err(c, RSM_E_INVALID, "mesh_clean: nv %lld outside 0..INT32_MAX", (long long)nv);
-    if (nf < 0 || 3 * nf >= ((int64_t)1 << 31)) return set_err(c, RSM_E_INVALID, "mesh_clean: nf %lld negative or 3 nf >= 2^31", (long long)nf);
-    return RSM_OK;
-}
-static int meshclean_fail(rsm_ctx *c, int s, int invalid) {
-    if (s == RSM_E_INVALID) return set_err(c, s, invalid == 1 ? "mesh_clean: a face index outside [0, nv)" : "mesh_clean: a coordinate that is not finite");
-    return set_err(c, s, "mesh_clean: failed%s%s", s == RSM_E_HIP ? ": " : "", s == RSM_E_HIP ? hipGetErrorString(hipGetLastError()) : "");
-}
-// d_xyz / d_faces may be c->pmesh's own buffers
-static int meshclean_run(rsm_ctx *c, const float *d_xyz, int64_t nv, const int32_t *d_faces, int64_t nf, const rsm_mesh_clean_params *p, int64_t *n_vertices,
-                         int64_t *n_faces, double *stats) {
-    int invalid = 0;
-    const int s = mesh_clean_device(d_xyz, nv, d_faces, nf, p, &c->pmesh, stats, &invalid, c->stream);
-    if (s != RSM_OK) return meshclean_fail(c, s, invalid);
-    *n_vertices = c->pmesh.nv;
-    *n_faces = c->pmesh.nf;
-    return RSM_OK;
-}
-
-extern "C" int rsm_mesh_clean_device(rsm_ctx *c, const float *d_xyz, int64_t nv, const int32_t *d_faces, int64_t nf, const rsm_mesh_clean_params *p,
-                                     int64_t *n_vertices, int64_t *n_faces, double *stats) {
-    if (!c) return RSM_E_INVALID;
-    int s = meshclean_params_ok(c, p);
-    if (s != RSM_OK || (s = meshclean_counts_ok(c, nv, nf)) != RSM_OK) return s;
-    if (!n_vertices || !n_faces || (nv > 0 && !d_xyz) || (nf > 0 && !d_faces)) return set_err(c, RSM_E_INVALID, "mesh_clean: a NULL pointer");
-    HIPCHK(c, hipSetDevice(c->device));
-    return meshclean_run(c, d_xyz, nv, d_faces, nf, p, n_vertices, n_faces, stats);
-}
-
-extern "C" int rsm_mesh_clean(rsm_ctx *c, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, const rsm_mesh_clean_params *p, int64_t *n_vertices,
-                              int64_t *n_faces, double *stats) {
-    if (!c) return RSM_E_INVALID;
-    int s = meshclean_params_ok(c, p);
-    if (s != RSM_OK || (s = meshclean_counts_ok(c, nv, nf)) != RSM_OK) return s;
-    if (!n_vertices || !n_faces || (nv > 0 && !xyz) || (nf > 0 && !faces)) return set_err(c, RSM_E_INVALID, "mesh_clean: a NULL pointer");
-    HIPCHK(c, hipSetDevice(c->device));
-    Tmp T(c);
-    float *dv = T.alloc<float>(3 * (size_t)nv);
-    int32_t *df = T.alloc<int32_t>(3 * (size_t)nf);
-    if (!dv || !df) return set_err(c, RSM_E_NOMEM, "mesh_clean: no device memory for %lld vertices, %lld faces", (long long)nv, (long long)nf);
-    if (nv > 0) HIPCHK(c, hipMemcpyAsync(dv, xyz, sizeof(float) * 3 * (size_t)nv, hipMemcpyHostToDevice, c->stream));
-    if (nf > 0) HIPCHK(c, hipMemcpyAsync(df, faces, sizeof(int32_t) * 3 * (size_t)nf, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return meshclean_run(c, dv, nv, df, nf, p, n_vertices, n_faces, stats);
-}
-
-extern "C" int rsm_mesh_clean_last(rsm_ctx *c, const rsm_mesh_clean_params *p, int64_t *n_vertices, int64_t *n_faces, double *stats) {
-    if (!c) return RSM_E_INVALID;
-    const int s = meshclean_params_ok(c, p);
-    if (s != RSM_OK) return s;
-    if (!n_vertices || !n_faces) return set_err(c, RSM_E_INVALID, "mesh_clean: a NULL pointer");
-    HIPCHK(c, hipSetDevice(c->device));
-    return meshclean_run(c, c->pmesh.d_v, c->pmesh.nv, c->pmesh.d_f, c->pmesh.nf, p, n_vertices, n_faces, stats);
-}
-
-extern "C" int rsm_stage_mesh_smooth(rsm_ctx *c, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, int steps, int cotangent, int boundary,
-                                     float *out_xyz, int64_t *n_border) {
-    if (!c) return RSM_E_INVALID;
-    const rsm_mesh_clean_params p{steps, cotangent, boundary, 0.0, 0, 0u};
-    int s = meshclean_params_ok(c, &p);
-    if (s != RSM_OK || (s = meshclean_counts_ok(c, nv, nf)) != RSM_OK) return s;
-    if ((nv > 0 && (!xyz || !out_xyz)) || (nf > 0 && !faces)) return set_err(c, RSM_E_INVALID, "mesh_clean: a NULL pointer");
-    HIPCHK(c, hipSetDevice(c->device));
-    Tmp T(c);
-    float *dv = T.alloc<float>(3 * (size_t)nv), *dout = T.alloc<float>(3 * (size_t)nv);
-    int32_t *df = T.alloc<int32_t>(3 * (size_t)nf);
-    if (!dv || !dout || !df) return set_err(c, RSM_E_NOMEM, "mesh_clean: no device memory");
-    if (nv > 0) HIPCHK(c, hipMemcpyAsync(dv, xyz, sizeof(float) * 3 * (size_t)nv, hipMemcpyHostToDevice, c->stream));
-    if (nf > 0) HIPCHK(c, hipMemcpyAsync(df, faces, sizeof(int32_t) * 3 * (size_t)nf, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    int invalid = 0;
-    int64_t nb = 0;
-    if ((s = mesh_smooth_device(dv, nv, df, nf, steps, cotangent, boundary, dout, &nb, &invalid, c->stream)) != RSM_OK) return meshclean_fail(c, s, invalid);
-    if (nv > 0) HIPCHK(c, hipMemcpyAsync(out_xyz, dout, sizeof(float) * 3 * (size_t)nv, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (n_border) *n_border = nb;
-    return RSM_OK;
-}
-
-extern "C" int rsm_stage_mesh_components(rsm_ctx *c, const int32_t *faces, int64_t nv, int64_t nf, int32_t *labels, int64_t *n_components) {
-    if (!c) return RSM_E_INVALID;
-    int s = meshclean_counts_ok(c, nv, nf);
-    if (s != RSM_OK) return s;
-    if (!n_components || (nf > 0 && (!faces || !labels))) return set_err(c, RSM_E_INVALID, "mesh_clean: a NULL pointer");
-    HIPCHK(c, hipSetDevice(c->device));
-    Tmp T(c);
-    int32_t *df = T.alloc<int32_t>(3 * (size_t)nf), *dl = T.alloc<int32_t>((size_t)nf);
-    if (!df || !dl) return set_err(c, RSM_E_NOMEM, "mesh_clean: no device memory");
-    if (nf > 0) HIPCHK(c, hipMemcpyAsync(df, faces, sizeof(int32_t) * 3 * (size_t)nf, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    int invalid = 0;
-    if ((s = mesh_components_device(df, nv, nf, dl, n_components, &invalid, c->stream)) != RSM_OK) return meshclean_fail(c, s, invalid);
-    if (nf > 0) HIPCHK(c, hipMemcpyAsync(labels, dl, sizeof(int32_t) * (size_t)nf, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RSM_OK;
-}
-
-// binary little-endian PLY mesh: what MeshLab and TextureStitcher read
-extern "C" int rsm_write_ply_mesh(const char *path, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf) {
-    if (!path || nv < 0 || nf < 0 || nv > (int64_t)INT32_MAX || nf > (int64_t)INT32_MAX || (nv > 0 && !xyz) || (nf > 0 && !faces)) return RSM_E_INVALID;
-    FILE *fp = fopen(path, "wb");
-    if (!fp) return RSM_E_INVALID;
-    fprintf(fp, "ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n", (int)nv);
-    fprintf(fp, "element face %d\nproperty list uchar int vertex_indices\nend_header\n", (int)nf);
-    if (nv > 0) fwrite(xyz, sizeof(float), 3 * (size_t)nv, fp);
-    const unsigned char three = 3;
-    for (int64_t f = 0; f < nf; f++) {
-        fwrite(&three, 1, 1, fp);
-        fwrite(faces + 3 * f, sizeof(int32_t), 3, fp);
-    }
-    const int ok = ferror(fp) == 0;
-    fclose(fp);
-    return ok ? RSM_OK : RSM_E_INVALID;
-}
-
-// ---- colours of the mesh from the rig's views (k_meshcolor.hip) ----------------------------------------------------------
-static int meshcolor_params_ok(rsm_ctx *c, const rsm_mesh_color_params *p) {
-    if (!p) return set_err(c, RSM_E_INVALID, "mesh_color: params is NULL");
-    if (p->mode != 0 && p->mode != 1) return set_err(c, RSM_E_INVALID, "mesh_color: mode %d not 0 (best view) or 1 (blend)", p->mode);
-    if (!(p->min_cos >= -1.0 && p->min_cos < 1.0)) return set_err(c, RSM_E_INVALID, "mesh_color: min_cos %g outside [-1, 1)", p->min_cos);
-    if (!std::isfinite(p->depth_eps) || p->depth_eps < 0.0) return set_err(c, RSM_E_INVALID, "mesh_color: depth_eps %g negative or not finite", p->depth_eps);
-    return RSM_OK;
-}
-static int meshcolor_counts_ok(rsm_ctx *c, int64_t nv, int64_t nf) {
-    if (nv < 0 || nv > (int64_t)INT32_MAX) return set_err(c, RSM_E_INVALID, "mesh_color: nv %lld outside 0..INT32_MAX", (long long)nv);
-    if (nf < 0 || 3 * nf >= ((int64_t)1 << 31)) return set_err(c, RSM_E_INVALID, "mesh_color: nf %lld negative or 3 nf >= 2^31", (long long)nf);
-    return RSM_OK;
-}
-static int meshcolor_views_ok(rsm_ctx *c, int64_t nv, const rsm_dedup_view *v, int np) {
-    if (nv == 0) return RSM_OK;
-    if (np < 1 || np > 32767) return set_err(c, RSM_E_INVALID, "mesh_color: n_pairs %d outside 1..32767", np);
-    if (!v) return set_err(c, RSM_E_INVALID, "mesh_color: a NULL pointer (views)");
-    for (int i = 0; i < np; i++) {
-        if (v[i].width < 1 || v[i].height < 1) return set_err(c, RSM_E_INVALID, "mesh_color: pair %d: width %d / height %d < 1", i, v[i].width, v[i].height);
-        if (!v[i].image[0] || !v[i].image[1]) return set_err(c, RSM_E_INVALID, "mesh_color: pair %d: a NULL pointer (image)", i);
-    }
-    return RSM_OK;
-}
-static int meshcolor_fail(rsm_ctx *c, int s, int invalid) {
-    if (s == RSM_E_INVALID)
-        return set_err(c, s, invalid == 1 ? "mesh_color: a face index outside [0, nv)" : invalid == 2 ? "mesh_color: a coordinate that is not finite"
-                                                                                                       : "mesh_color: a singular P (det of its left 3x3 is 0)");
-    return set_err(c, s, "mesh_color: failed%s%s", s == RSM_E_HIP ? ": " : "", s == RSM_E_HIP ? hipGetErrorString(hipGetLastError()) : "");
-}
-
-extern "C" int rsm_mesh_color_device(rsm_ctx *c, const float *d_xyz, int64_t nv, const int32_t *d_faces, int64_t nf, const rsm_dedup_view *views, int n_pairs,
-                                     const rsm_mesh_color_params *p, uint8_t *d_rgb, int32_t *d_best_view, double *stats) {
-    if (!c) return RSM_E_INVALID;
-    int s = meshcolor_params_ok(c, p);
-    if (s != RSM_OK || (s = meshcolor_counts_ok(c, nv, nf)) != RSM_OK) return s;
-    if ((nv > 0 && (!d_xyz || !d_rgb)) || (nf > 0 && !d_faces)) return set_err(c, RSM_E_INVALID, "mesh_color: a NULL pointer");
-    if ((s = meshcolor_views_ok(c, nv, views, n_pairs)) != RSM_OK) return s;
-    HIPCHK(c, hipSetDevice(c->device));
-    int invalid = 0;
-    s = mesh_color_device(d_xyz, nv, d_faces, nf, views, n_pairs, p, c->opt_meshcolor_big_box, d_rgb, d_best_view, stats, &invalid, c->stream);
-    return s == RSM_OK ? RSM_OK : meshcolor_fail(c, s, invalid);
-}
-
-extern "C" int rsm_mesh_color(rsm_ctx *c, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, const rsm_dedup_view *views, int n_pairs,
-                              const rsm_mesh_color_params *p, uint8_t *rgb, int32_t *best_view, double *stats) {
-    if (!c) return RSM_E_INVALID;
-    int s = meshcolor_params_ok(c, p);
-    if (s != RSM_OK || (s = meshcolor_counts_ok(c, nv, nf)) != RSM_OK) return s;
-    if ((nv > 0 && (!xyz || !rgb)) || (nf > 0 && !faces)) return set_err(c, RSM_E_INVALID, "mesh_color: a NULL pointer");
-    if ((s = meshcolor_views_ok(c, nv, views, n_pairs)) != RSM_OK) return s;
-    HIPCHK(c, hipSetDevice(c->device));
-    Tmp T(c);
-    float *dv = T.alloc<float>(3 * (size_t)nv);
-    int32_t *df = T.alloc<int32_t>(3 * (size_t)nf), *db = T.alloc<int32_t>((size_t)nv);
-    uint8_t *dc = T.alloc<uint8_t>(3 * (size_t)nv);
-    if (!dv || !df || !db || !dc) return set_err(c, RSM_E_NOMEM, "mesh_color: no device memory for %lld vertices, %lld faces", (long long)nv, (long long)nf);
-    if (nv > 0) HIPCHK(c, hipMemcpyAsync(dv, xyz, sizeof(float) * 3 * (size_t)nv, hipMemcpyHostToDevice, c->stream));
-    if (nf > 0) HIPCHK(c, hipMemcpyAsync(df, faces, sizeof(int32_t) * 3 * (size_t)nf, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    int invalid = 0;
-    s = mesh_color_device(dv, nv, df, nf, views, n_pairs, p, c->opt_meshcolor_big_box, dc, db, stats, &invalid, c->stream);
-    if (s != RSM_OK) return meshcolor_fail(c, s, invalid);
-    if (nv > 0) HIPCHK(c, hipMemcpyAsync(rgb, dc, 3 * (size_t)nv, hipMemcpyDeviceToHost, c->stream));
-    if (nv > 0 && best_view) HIPCHK(c, hipMemcpyAsync(best_view, db, sizeof(int32_t) * (size_t)nv, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RSM_OK;
-}
-
-extern "C" int rsm_mesh_color_last(rsm_ctx *c, const rsm_dedup_view *views, int n_pairs, const rsm_mesh_color_params *p, double *stats) {
-    if (!c) return RSM_E_INVALID;
-    int s = meshcolor_params_ok(c, p);
-    const int64_t nv = c->pmesh.nv, nf = c->pmesh.nf;
-    if (s != RSM_OK || (s = meshcolor_views_ok(c, nv, views, n_pairs)) != RSM_OK) return s;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (c->mcol_rgb) (void)hipFree(c->mcol_rgb);
-    if (c->mcol_best) (void)hipFree(c->mcol_best);
-    c->mcol_rgb = nullptr;
-    c->mcol_best = nullptr;
-    c->mcol_of = nullptr;
-    c->mcol_nv = 0;
-    if (hipMalloc((void **)&c->mcol_rgb, 3 * (size_t)nv + 64) != hipSuccess || hipMalloc((void **)&c->mcol_best, sizeof(int32_t) * (size_t)nv + 64) != hipSuccess)
-        return set_err(c, RSM_E_NOMEM, "mesh_color: no device memory for %lld vertices", (long long)nv);
-    int invalid = 0;
-    s = mesh_color_device(c->pmesh.d_v, nv, c->pmesh.d_f, nf, views, n_pairs, p, c->opt_meshcolor_big_box, c->mcol_rgb, c->mcol_best, stats, &invalid, c->stream);
-    if (s != RSM_OK) return meshcolor_fail(c, s, invalid);
-    c->mcol_of = c->pmesh.d_v;
-    c->mcol_nv = nv;
-    return RSM_OK;
-}
-
-extern "C" int rsm_mesh_last_colors(rsm_ctx *c, uint8_t *rgb, int32_t *best_view) {
-    if (!c) return RSM_E_INVALID;
-    if (!c->mcol_rgb || c->mcol_of != c->pmesh.d_v || c->mcol_nv != c->pmesh.nv)
-        return set_err(c, RSM_E_STATE, "mesh_last_colors: the context's last mesh has no colours (rsm_mesh_color_last first)");
-    HIPCHK(c, hipSetDevice(c->device));
-    if (rgb && c->mcol_nv > 0) HIPCHK(c, hipMemcpyAsync(rgb, c->mcol_rgb, 3 * (size_t)c->mcol_nv, hipMemcpyDeviceToHost, c->stream));
-    if (best_view && c->mcol_nv > 0) HIPCHK(c, hipMemcpyAsync(best_view, c->mcol_best, sizeof(int32_t) * (size_t)c->mcol_nv, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RSM_OK;
-}
-
-extern "C" int rsm_texture_color(rsm_ctx *c, const float *xyz, int64_t n, const double P12[12], const uint8_t *image, int width, int height, uint8_t *rgb) {
-    if (!c) return RSM_E_INVALID;
-    if (n < 0 || n > (int64_t)INT32_MAX) return set_err(c, RSM_E_INVALID, "texture_color: n %lld outside 0..INT32_MAX", (long long)n);
-    if (width < 1 || height < 1) return set_err(c, RSM_E_INVALID, "texture_color: width %d / height %d < 1", width, height);
-    if (!P12 || !image || (n > 0 && (!xyz || !rgb))) return set_err(c, RSM_E_INVALID, "texture_color: a NULL pointer");
-    if (n == 0) return RSM_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    Tmp T(c);
-    const size_t pix = (size_t)width * (size_t)height;
-    float *dp = T.alloc<float>(3 * (size_t)n);
-    uint8_t *di = T.alloc<uint8_t>(3 * pix), *dc = T.alloc<uint8_t>(3 * (size_t)n);
-    if (!dp || !di || !dc) return set_err(c, RSM_E_NOMEM, "texture_color: no device memory");
-    HIPCHK(c, hipMemcpyAsync(dp, xyz, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(di, image, 3 * pix, hipMemcpyHostToDevice, c->stream));
-    const int s = texture_color_device(dp, n, P12, di, width, height, dc, c->stream);
-    if (s != RSM_OK) return set_err(c, s, "texture_color: failed");
-    HIPCHK(c, hipMemcpyAsync(rgb, dc, 3 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RSM_OK;
-}
-
-extern "C" int rsm_stage_mesh_depth(rsm_ctx *c, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, const double P12[12], int width, int height,
-                                    uint32_t *wbuf) {
-    if (!c) return RSM_E_INVALID;
-    int s = meshcolor_counts_ok(c, nv, nf);
-    if (s != RSM_OK) return s;
-    if (width < 1 || height < 1) return set_err(c, RSM_E_INVALID, "mesh_color: width %d / height %d < 1", width, height);
-    if (!P12 || !wbuf || (nv > 0 && !xyz) || (nf > 0 && !faces)) return set_err(c, RSM_E_INVALID, "mesh_color: a NULL pointer");
-    HIPCHK(c, hipSetDevice(c->device));
-    Tmp T(c);
-    const size_t pix = (size_t)width * (size_t)height;
-    float *dv = T.alloc<float>(3 * (size_t)nv);
-    int32_t *df = T.alloc<int32_t>(3 * (size_t)nf);
-    uint32_t *dw = T.alloc<uint32_t>(pix);
-    if (!dv || !df || !dw) return set_err(c, RSM_E_NOMEM, "mesh_color: no device memory");
-    if (nv > 0) HIPCHK(c, hipMemcpyAsync(dv, xyz, sizeof(float) * 3 * (size_t)nv, hipMemcpyHostToDevice, c->stream));
-    if (nf > 0) HIPCHK(c, hipMemcpyAsync(df, faces, sizeof(int32_t) * 3 * (size_t)nf, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    int invalid = 0;
-    if ((s = mesh_depth_device(dv, nv, df, nf, P12, width, height, c->opt_meshcolor_big_box, dw, &invalid, c->stream)) != RSM_OK) return meshcolor_fail(c, s, invalid);
-    HIPCHK(c, hipMemcpyAsync(wbuf, dw, sizeof(uint32_t) * pix, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RSM_OK;
-}
-
-// the coloured mesh as MyPlyIo writes it (my_ply_interface.cpp:35-50): vertex x y z red green blue, face vertex_indices.  Host only.
-extern "C" int rsm_write_ply_mesh_color(const char *path, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, const uint8_t *rgb) {
-    if (!path || nv < 0 || nf < 0 || nv > (int64_t)INT32_MAX || nf > (int64_t)INT32_MAX || (nv > 0 && (!xyz || !rgb)) || (nf > 0 && !faces)) return RSM_E_INVALID;
-    FILE *fp = fopen(path, "wb");
-    if (!fp) return RSM_E_INVALID;
-    fprintf(fp, "ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n", (int)nv);
-    fprintf(fp, "property uchar red\nproperty uchar green\nproperty uchar blue\n");
-    fprintf(fp, "element face %d\nproperty list uchar int vertex_indices\nend_header\n", (int)nf);
-    for (int64_t v = 0; v < nv; v++) {
-        fwrite(xyz + 3 * v, sizeof(float), 3, fp);
-        fwrite(rgb + 3 * v, 1, 3, fp);
-    }
-    const unsigned char three = 3;
-    for (int64_t f = 0; f < nf; f++) {
-        fwrite(&three, 1, 1, fp);
-        fwrite(faces + 3 * f, sizeof(int32_t), 3, fp);
-    }
-    const int ok = ferror(fp) == 0;
-    fclose(fp);
-    return ok ? RSM_OK : RSM_E_INVALID;
-}
-
-// ---- PLY writer (CStereoMatching.cpp:723-729, 754-756) ----------------------------------------------
-extern "C" int rsm_write_ply(const char *path, const double *xyz, const uint8_t *bgr, int64_t n) {
-    if (!path || n < 0 || (n > 0 && (!xyz || !bgr))) return RSM_E_INVALID;
-    FILE *fp = fopen(path, "wb");
-    if (!fp) return RSM_E_INVALID;
-    fprintf(fp, "ply\n");
-    fprintf(fp, "format binary_little_endian 1.0\n");
-    fprintf(fp, "element vertex %d\n", (int)n);
-    fprintf(fp, "property float x\nproperty float y\nproperty float z\nproperty uchar blue\nproperty uchar green\nproperty uchar red\n");
-    fprintf(fp, "end_header\n");
-    for (int64_t i = 0; i < n; i++) {
-        const float p[3] = {(float)xyz[3 * i], (float)xyz[3 * i + 1], (float)xyz[3 * i + 2]}; // convertTo CV_32F, .cpp:754
-        fwrite(p, sizeof(float), 3, fp);
-        fwrite(bgr + 3 * i, 1, 3, fp);
-    }
-    const int ok = ferror(fp) == 0;
-    fclose(fp);
-    return ok ? RSM_OK : RSM_E_INVALID;
-}
-
-// the same file from the 16-byte records (float xyz + BGR are exactly a PLY vertex of this header)
-extern "C" int rsm_write_ply16(const char *path, const rsm_point16 *points, int64_t n) {
-    if (!path || n < 0 || (n > 0 && !points)) return RSM_E_INVALID;
-    FILE *fp = fopen(path, "wb");
-    if (!fp) return RSM_E_INVALID;
-    fprintf(fp, "ply\n");
-    fprintf(fp, "format binary_little_endian 1.0\n");
-    fprintf(fp, "element vertex %d\n", (int)n);
-    fprintf(fp, "property float x\nproperty float y\nproperty float z\nproperty uchar blue\nproperty uchar green\nproperty uchar red\n");
-    fprintf(fp, "end_header\n");
-    for (int64_t i = 0; i < n; i++) fwrite(&points[i], 1, 15, fp); // x, y, z, b, g, r (the pad byte stays behind)
-    const int ok = ferror(fp) == 0;
-    fclose(fp);
-    return ok ? RSM_OK : RSM_E_INVALID;
-}
-
-// ---- NCC kernel microbenchmark --------------------------------------------------------------------
-extern "C" int rsm_bench_ncc(rsm_ctx *c, int W, int H, int r, int cands, int iters, double *ms_per_launch) {
-    if (!stage_ok(c, W, H) || r < 1 || r > 15 || cands < 1 || iters < 1 || !ms_per_launch) return RSM_E_INVALID;
-    if (W <= 2 * r + cands + 2 || H <= 2 * r + 2) return RSM_E_INVALID;
-    Tmp t(c);
-    const size_t px = (size_t)W * H;
-    std::vector<uint8_t> hi(px * 3), hm(px, 255);
-    uint32_t s = 12345u;
-    for (auto &v : hi) {
-        s = s * 1664525u + 1013904223u;
-        v = (uint8_t)(s >> 24);
-    }
-    MatchBufs b{};
-    if (!setup_match(c, t, hi.data(), hi.data(), hm.data(), hm.data(), W, H, r, b)) return finish(c, t);
-    rsm_boundary m{r, H - 1 - r, r, W - 1 - r, W - 2 * r, H - 2 * r};
-    StageArgs a = one_dir(c, W, H, r, &m, &m);
-    bind_match(a, b);
-    std::vector<int16_t> hl(px), hr(px);
-    for (int y = 0; y < H; y++)
-        for (int x = 0; x < W; x++) {
-            int L = x - cands / 2, R = L + cands - 1;
-            if (L < r) { L = r; R = L + cands - 1; }
-            if (R > W - 1 - r) { R = W - 1 - r; L = R - cands + 1; }
-            hl[(size_t)y * W + x] = (int16_t)L;
-            hr[(size_t)y * W + x] = (int16_t)R;
-        }
-    a.d[0].BL = t.up(hl.data(), px);
-    a.d[0].BR = t.up(hr.data(), px);
-    int16_t *dd = t.alloc<int16_t>(px);
-    if (!t.ok) return finish(c, t);
-    a.d[0].d16_in = a.d[0].d16_out = dd;
-    launch_fill_i16(dd, px, (int16_t)NOMATCH, c->stream);
-    launch_ncc_argmax(a, 1, c->stream); // warm-up (setup_match zeroed the counter)
-    hipEvent_t e0, e1;
-    HIPCHK(c, hipEventCreate(&e0));
-    HIPCHK(c, hipEventCreate(&e1));
-    HIPCHK(c, hipEventRecord(e0, c->stream));
-    for (int i = 0; i < iters; i++) {
-        (void)hipMemsetAsync(a.ncc_cnt, 0, sizeof(int), c->stream); // fresh wide-pixel counter per launch
-        (void)hipMemsetAsync(a.tie_cnt, 0, 2 * sizeof(int), c->stream);
-        (void)hipMemsetAsync(a.wrow, 0, sizeof(int32_t) * (size_t)H, c->stream);
-        launch_ncc_argmax(a, 1, c->stream);
-    }
-    HIPCHK(c, hipEventRecord(e1, c->stream));
-    HIPCHK(c, hipEventSynchronize(e1));
-    float ms = 0;
-    HIPCHK(c, hipEventElapsedTime(&ms, e0, e1));
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    *ms_per_launch = (double)ms / iters;
-    return finish(c, t);
 }

@@ -1,0 +1,412 @@
+// rsm_mesh.hip -- the mesh back end's host side: the dense-grid Poisson surface, its smoothing and clean-up, and its colours
+// from the rig's views (k_poisson.hip, k_meshclean.hip, k_meshcolor.hip).
+#include "rsm_ctx.h"
+
+#include <cmath>
+#include <string.h>
+
+// ---- dense-grid Poisson surface and trim (k_poisson.hip) -----------------------------------------------------------
+static int poisson_params_ok(rsm_ctx *c, const rsm_poisson_params *p) {
+    if (!p) return set_err(c, RSM_E_INVALID, "poisson: params is NULL");
+    if (p->depth < 5 || p->depth > 9) return set_err(c, RSM_E_INVALID, "poisson: depth %d outside 5..9", p->depth);
+    if (!std::isfinite(p->scale) || p->scale < 1.0) return set_err(c, RSM_E_INVALID, "poisson: scale %g not finite or < 1", p->scale);
+    if (!(p->rel_residual > 0.0 && p->rel_residual < 1.0)) return set_err(c, RSM_E_INVALID, "poisson: rel_residual %g not in (0, 1)", p->rel_residual);
+    if (p->max_cycles < 1) return set_err(c, RSM_E_INVALID, "poisson: max_cycles %d < 1", p->max_cycles);
+    if (p->trim_cells < 0) return set_err(c, RSM_E_INVALID, "poisson: trim_cells %d < 0", p->trim_cells);
+    return RSM_OK;
+}
+static int poisson_n_ok(rsm_ctx *c, int64_t n) {
+    if (n < 0 || n > (int64_t)INT32_MAX) return set_err(c, RSM_E_INVALID, "poisson: n %lld outside 0..INT32_MAX", (long long)n);
+    return RSM_OK;
+}
+// the end of the three *_fail texts: after a HIP failure ": " and the runtime's last error, else nothing
+static std::string hip_tail(int s) { return s == RSM_E_HIP ? std::string(": ") + hipGetErrorString(hipGetLastError()) : std::string(); }
+static int poisson_fail(rsm_ctx *c, int s, const char *what) { return set_err(c, s, "poisson: %s failed%s", what, hip_tail(s).c_str()); }
+
+// the eight steps on device buffers; the mesh lands in c->pmesh
+static int poisson_run(rsm_ctx *c, const float *d_xyz, const float *d_nrm, int64_t n, const rsm_poisson_params *p, int64_t *n_vertices,
+                       int64_t *n_faces, double *stats) {
+    double st[RSM_POISSON_STATS] = {0};
+    *n_vertices = *n_faces = 0;
+    poisson_mesh_free(&c->pmesh);
+    double grid[4];
+    int64_t counts[2];
+    int s = poisson_grid_device(d_xyz, d_nrm, n, p->depth, p->scale, grid, counts, c->stream);
+    if (s != RSM_OK) return poisson_fail(c, s, "bounding box");
+    st[0] = (double)counts[0];
+    st[1] = (double)counts[1];
+    st[9] = (double)(1 << p->depth);
+    int solved = RSM_OK;
+    if (grid[3] > 0.0) {
+        const size_t N3 = (size_t)1 << (3 * p->depth);
+        Tmp T(c);
+        float *b = T.alloc<float>(N3), *chi = T.alloc<float>(N3);
+        uint8_t *occ = T.alloc<uint8_t>(N3);
+        if (!b || !chi || !occ) return set_err(c, RSM_E_NOMEM, "poisson: no device memory for depth %d", p->depth);
+        if ((s = poisson_rhs_device(d_xyz, d_nrm, n, p->depth, grid, b, nullptr, occ, c->stream)) != RSM_OK) return poisson_fail(c, s, "right-hand side");
+        double res = 0.0, iso = 0.0;
+        int cycles = 0;
+        solved = poisson_solve_device(b, p->depth, p->rel_residual, p->max_cycles, chi, &res, &cycles, nullptr, c->stream);
+        if (solved < 0) return poisson_fail(c, solved, "solve");
+        if ((s = poisson_iso_device(d_xyz, d_nrm, n, counts[0], chi, p->depth, grid, &iso, c->stream)) != RSM_OK) return poisson_fail(c, s, "iso-value");
+        int64_t un[2];
+        if ((s = poisson_extract_device(chi, p->depth, iso, grid, occ, p->trim_cells, &c->pmesh, un, c->stream)) != RSM_OK)
+            return poisson_fail(c, s, "extraction");
+        st[2] = res;
+        st[3] = (double)cycles;
+        st[4] = iso;
+        for (int a = 0; a < 4; a++) st[5 + a] = grid[a];
+        st[10] = (double)un[0];
+        st[11] = (double)un[1];
+        if (solved == RSM_W_NOT_CONVERGED) set_err(c, solved, "poisson: residual %g after %d cycles (rel_residual %g)", res, cycles, p->rel_residual);
+    }
+    *n_vertices = c->pmesh.nv;
+    *n_faces = c->pmesh.nf;
+    if (stats) memcpy(stats, st, sizeof st);
+    return solved;
+}
+
+extern "C" int rsm_poisson_mesh_device(rsm_ctx *c, const float *d_xyz, const float *d_normals4, int64_t n, const rsm_poisson_params *p,
+                                       int64_t *n_vertices, int64_t *n_faces, double *stats) {
+    if (!c) return RSM_E_INVALID;
+    int s = poisson_params_ok(c, p);
+    if (s != RSM_OK || (s = poisson_n_ok(c, n)) != RSM_OK) return s;
+    if (!n_vertices || !n_faces || (n > 0 && (!d_xyz || !d_normals4))) return set_err(c, RSM_E_INVALID, "poisson: a NULL pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    return poisson_run(c, d_xyz, d_normals4, n, p, n_vertices, n_faces, stats);
+}
+
+extern "C" int rsm_poisson_mesh(rsm_ctx *c, const float *xyz, const float *normals4, int64_t n, const rsm_poisson_params *p, int64_t *n_vertices,
+                                int64_t *n_faces, double *stats) {
+    if (!c) return RSM_E_INVALID;
+    int s = poisson_params_ok(c, p);
+    if (s != RSM_OK || (s = poisson_n_ok(c, n)) != RSM_OK) return s;
+    if (!n_vertices || !n_faces || (n > 0 && (!xyz || !normals4))) return set_err(c, RSM_E_INVALID, "poisson: a NULL pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    Tmp T(c);
+    float *dx = T.up(xyz, 3 * (size_t)n), *dn = T.up(normals4, 4 * (size_t)n);
+    if (!dx || !dn) return set_err(c, RSM_E_NOMEM, "poisson: no device memory for %lld samples", (long long)n);
+    if (n > 0 && (s = finish(c, T)) != RSM_OK) return s;
+    return poisson_run(c, dx, dn, n, p, n_vertices, n_faces, stats);
+}
+
+static int pmesh_copy_out(rsm_ctx *c, float *xyz, int32_t *faces, hipMemcpyKind kind) {
+    if (!c) return RSM_E_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (xyz && c->pmesh.nv > 0) HIPCHK(c, hipMemcpyAsync(xyz, c->pmesh.d_v, sizeof(float) * 3 * (size_t)c->pmesh.nv, kind, c->stream));
+    if (faces && c->pmesh.nf > 0) HIPCHK(c, hipMemcpyAsync(faces, c->pmesh.d_f, sizeof(int32_t) * 3 * (size_t)c->pmesh.nf, kind, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RSM_OK;
+}
+extern "C" int rsm_poisson_last_mesh_device(rsm_ctx *c, float *d_xyz, int32_t *d_faces) { return pmesh_copy_out(c, d_xyz, d_faces, hipMemcpyDeviceToDevice); }
+extern "C" int rsm_poisson_last_mesh(rsm_ctx *c, float *xyz, int32_t *faces) { return pmesh_copy_out(c, xyz, faces, hipMemcpyDeviceToHost); }
+
+extern "C" int rsm_stage_poisson_rhs(rsm_ctx *c, const float *xyz, const float *normals4, int64_t n, const rsm_poisson_params *p, double grid[4],
+                                     double *b, uint8_t *occ, int64_t counts[2]) {
+    if (!c) return RSM_E_INVALID;
+    int s = poisson_params_ok(c, p);
+    if (s != RSM_OK || (s = poisson_n_ok(c, n)) != RSM_OK) return s;
+    if (!grid || !b || !occ || !counts || (n > 0 && (!xyz || !normals4))) return set_err(c, RSM_E_INVALID, "poisson: a NULL pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t N3 = (size_t)1 << (3 * p->depth);
+    Tmp T(c);
+    float *dx = T.up(xyz, 3 * (size_t)n), *dn = T.up(normals4, 4 * (size_t)n);
+    double *db = T.alloc<double>(N3);
+    uint8_t *docc = T.alloc<uint8_t>(N3);
+    if (!dx || !dn || !db || !docc) return set_err(c, RSM_E_NOMEM, "poisson: no device memory");
+    if (n > 0 && (s = finish(c, T)) != RSM_OK) return s;
+    if ((s = poisson_grid_device(dx, dn, n, p->depth, p->scale, grid, counts, c->stream)) != RSM_OK) return poisson_fail(c, s, "bounding box");
+    if (!(grid[3] > 0.0)) {
+        memset(b, 0, sizeof(double) * N3);
+        memset(occ, 0, N3);
+        return RSM_OK;
+    }
+    if ((s = poisson_rhs_device(dx, dn, n, p->depth, grid, nullptr, db, docc, c->stream)) != RSM_OK) return poisson_fail(c, s, "right-hand side");
+    HIPCHK(c, hipMemcpyAsync(b, db, sizeof(double) * N3, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(occ, docc, N3, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RSM_OK;
+}
+
+extern "C" int rsm_stage_poisson_solve(rsm_ctx *c, const float *b, int depth, double rel_residual, int max_cycles, float *chi, double *residual,
+                                       int *cycles, double *history) {
+    if (!c) return RSM_E_INVALID;
+    const rsm_poisson_params p{depth, 1.0, rel_residual, max_cycles, 0};
+    int s = poisson_params_ok(c, &p);
+    if (s != RSM_OK) return s;
+    if (!b || !chi || !residual || !cycles) return set_err(c, RSM_E_INVALID, "poisson: a NULL pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t N3 = (size_t)1 << (3 * depth);
+    Tmp T(c);
+    float *db = T.up(b, N3), *dchi = T.alloc<float>(N3);
+    if (!db || !dchi) return set_err(c, RSM_E_NOMEM, "poisson: no device memory");
+    if ((s = finish(c, T)) != RSM_OK) return s;
+    s = poisson_solve_device(db, depth, rel_residual, max_cycles, dchi, residual, cycles, history, c->stream);
+    if (s < 0) return poisson_fail(c, s, "solve");
+    HIPCHK(c, hipMemcpyAsync(chi, dchi, sizeof(float) * N3, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return s;
+}
+
+extern "C" int rsm_stage_iso_mesh(rsm_ctx *c, const float *chi, int depth, double iso, const double grid[4], const uint8_t *occ, int trim_cells,
+                                  int64_t *n_vertices, int64_t *n_faces) {
+    if (!c) return RSM_E_INVALID;
+    const rsm_poisson_params p{depth, 1.0, 0.5, 1, trim_cells};
+    int s = poisson_params_ok(c, &p);
+    if (s != RSM_OK) return s;
+    if (!chi || !grid || !n_vertices || !n_faces || (trim_cells > 0 && !occ)) return set_err(c, RSM_E_INVALID, "poisson: a NULL pointer");
+    if (!std::isfinite(iso) || !std::isfinite(grid[0]) || !std::isfinite(grid[1]) || !std::isfinite(grid[2]) || !(grid[3] > 0.0) || !std::isfinite(grid[3]))
+        return set_err(c, RSM_E_INVALID, "poisson: iso or grid not finite, or h <= 0");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t N3 = (size_t)1 << (3 * depth);
+    Tmp T(c);
+    float *dchi = T.up(chi, N3);
+    uint8_t *docc = occ ? T.up(occ, N3) : nullptr;
+    if (!dchi || (occ && !docc)) return set_err(c, RSM_E_NOMEM, "poisson: no device memory");
+    if ((s = finish(c, T)) != RSM_OK) return s;
+    int64_t un[2];
+    if ((s = poisson_extract_device(dchi, depth, iso, grid, docc, trim_cells, &c->pmesh, un, c->stream)) != RSM_OK) return poisson_fail(c, s, "extraction");
+    *n_vertices = c->pmesh.nv;
+    *n_faces = c->pmesh.nf;
+    return RSM_OK;
+}
+
+// ---- smoothing and clean-up of the surface (k_meshclean.hip) ------------------------------------------------------------
+static int meshclean_params_ok(rsm_ctx *c, const rsm_mesh_clean_params *p) {
+    if (!p) return set_err(c, RSM_E_INVALID, "mesh_clean: params is NULL");
+    if (p->smooth_steps < 0) return set_err(c, RSM_E_INVALID, "mesh_clean: smooth_steps %d < 0", p->smooth_steps);
+    if (p->cotangent != 0 && p->cotangent != 1) return set_err(c, RSM_E_INVALID, "mesh_clean: cotangent %d not 0 or 1", p->cotangent);
+    if (p->boundary != 0 && p->boundary != 1) return set_err(c, RSM_E_INVALID, "mesh_clean: boundary %d not 0 or 1", p->boundary);
+    if (!std::isfinite(p->min_piece) || p->min_piece < 0.0) return set_err(c, RSM_E_INVALID, "mesh_clean: min_piece %g negative or not finite", p->min_piece);
+    if (p->min_piece_relative != 0 && p->min_piece_relative != 1)
+        return set_err(c, RSM_E_INVALID, "mesh_clean: min_piece_relative %d not 0 or 1", p->min_piece_relative);
+    if (p->flags & ~(RSM_MESH_CLEAN_DUPLICATES | RSM_MESH_CLEAN_ZERO_AREA | RSM_MESH_CLEAN_NONMANIFOLD))
+        return set_err(c, RSM_E_INVALID, "mesh_clean: flags 0x%x has an unknown bit", p->flags);
+    return RSM_OK;
+}
+static int mesh_counts_ok(rsm_ctx *c, const char *who, int64_t nv, int64_t nf) { // who: "mesh_clean" / "mesh_color"
+    if (nv < 0 || nv > (int64_t)INT32_MAX) return set_err(c, RSM_E_INVALID, "%s: nv %lld outside 0..INT32_MAX", who, (long long)nv);
+    if (nf < 0 || 3 * nf >= ((int64_t)1 << 31)) return set_err(c, RSM_E_INVALID, "%s: nf %lld negative or 3 nf >= 2^31", who, (long long)nf);
+    return RSM_OK;
+}
+static int meshclean_fail(rsm_ctx *c, int s, int invalid) {
+    if (s == RSM_E_INVALID) return set_err(c, s, invalid == 1 ? "mesh_clean: a face index outside [0, nv)" : "mesh_clean: a coordinate that is not finite");
+    return set_err(c, s, "mesh_clean: failed%s", hip_tail(s).c_str());
+}
+// d_xyz / d_faces may be c->pmesh's own buffers
+static int meshclean_run(rsm_ctx *c, const float *d_xyz, int64_t nv, const int32_t *d_faces, int64_t nf, const rsm_mesh_clean_params *p, int64_t *n_vertices,
+                         int64_t *n_faces, double *stats) {
+    int invalid = 0;
+    const int s = mesh_clean_device(d_xyz, nv, d_faces, nf, p, &c->pmesh, stats, &invalid, c->stream);
+    if (s != RSM_OK) return meshclean_fail(c, s, invalid);
+    *n_vertices = c->pmesh.nv;
+    *n_faces = c->pmesh.nf;
+    return RSM_OK;
+}
+
+extern "C" int rsm_mesh_clean_device(rsm_ctx *c, const float *d_xyz, int64_t nv, const int32_t *d_faces, int64_t nf, const rsm_mesh_clean_params *p,
+                                     int64_t *n_vertices, int64_t *n_faces, double *stats) {
+    if (!c) return RSM_E_INVALID;
+    int s = meshclean_params_ok(c, p);
+    if (s != RSM_OK || (s = mesh_counts_ok(c, "mesh_clean", nv, nf)) != RSM_OK) return s;
+    if (!n_vertices || !n_faces || (nv > 0 && !d_xyz) || (nf > 0 && !d_faces)) return set_err(c, RSM_E_INVALID, "mesh_clean: a NULL pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    return meshclean_run(c, d_xyz, nv, d_faces, nf, p, n_vertices, n_faces, stats);
+}
+
+extern "C" int rsm_mesh_clean(rsm_ctx *c, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, const rsm_mesh_clean_params *p, int64_t *n_vertices,
+                              int64_t *n_faces, double *stats) {
+    if (!c) return RSM_E_INVALID;
+    int s = meshclean_params_ok(c, p);
+    if (s != RSM_OK || (s = mesh_counts_ok(c, "mesh_clean", nv, nf)) != RSM_OK) return s;
+    if (!n_vertices || !n_faces || (nv > 0 && !xyz) || (nf > 0 && !faces)) return set_err(c, RSM_E_INVALID, "mesh_clean: a NULL pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    Tmp T(c);
+    float *dv = T.up(xyz, 3 * (size_t)nv);
+    int32_t *df = T.up(faces, 3 * (size_t)nf);
+    if (!dv || !df) return set_err(c, RSM_E_NOMEM, "mesh_clean: no device memory for %lld vertices, %lld faces", (long long)nv, (long long)nf);
+    if ((s = finish(c, T)) != RSM_OK) return s;
+    return meshclean_run(c, dv, nv, df, nf, p, n_vertices, n_faces, stats);
+}
+
+extern "C" int rsm_mesh_clean_last(rsm_ctx *c, const rsm_mesh_clean_params *p, int64_t *n_vertices, int64_t *n_faces, double *stats) {
+    if (!c) return RSM_E_INVALID;
+    const int s = meshclean_params_ok(c, p);
+    if (s != RSM_OK) return s;
+    if (!n_vertices || !n_faces) return set_err(c, RSM_E_INVALID, "mesh_clean: a NULL pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    return meshclean_run(c, c->pmesh.d_v, c->pmesh.nv, c->pmesh.d_f, c->pmesh.nf, p, n_vertices, n_faces, stats);
+}
+
+extern "C" int rsm_stage_mesh_smooth(rsm_ctx *c, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, int steps, int cotangent, int boundary,
+                                     float *out_xyz, int64_t *n_border) {
+    if (!c) return RSM_E_INVALID;
+    const rsm_mesh_clean_params p{steps, cotangent, boundary, 0.0, 0, 0u};
+    int s = meshclean_params_ok(c, &p);
+    if (s != RSM_OK || (s = mesh_counts_ok(c, "mesh_clean", nv, nf)) != RSM_OK) return s;
+    if ((nv > 0 && (!xyz || !out_xyz)) || (nf > 0 && !faces)) return set_err(c, RSM_E_INVALID, "mesh_clean: a NULL pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    Tmp T(c);
+    float *dv = T.up(xyz, 3 * (size_t)nv), *dout = T.alloc<float>(3 * (size_t)nv);
+    int32_t *df = T.up(faces, 3 * (size_t)nf);
+    if (!dv || !dout || !df) return set_err(c, RSM_E_NOMEM, "mesh_clean: no device memory");
+    if ((s = finish(c, T)) != RSM_OK) return s;
+    int invalid = 0;
+    int64_t nb = 0;
+    if ((s = mesh_smooth_device(dv, nv, df, nf, steps, cotangent, boundary, dout, &nb, &invalid, c->stream)) != RSM_OK) return meshclean_fail(c, s, invalid);
+    if (nv > 0) HIPCHK(c, hipMemcpyAsync(out_xyz, dout, sizeof(float) * 3 * (size_t)nv, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (n_border) *n_border = nb;
+    return RSM_OK;
+}
+
+extern "C" int rsm_stage_mesh_components(rsm_ctx *c, const int32_t *faces, int64_t nv, int64_t nf, int32_t *labels, int64_t *n_components) {
+    if (!c) return RSM_E_INVALID;
+    int s = mesh_counts_ok(c, "mesh_clean", nv, nf);
+    if (s != RSM_OK) return s;
+    if (!n_components || (nf > 0 && (!faces || !labels))) return set_err(c, RSM_E_INVALID, "mesh_clean: a NULL pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    Tmp T(c);
+    int32_t *df = T.up(faces, 3 * (size_t)nf), *dl = T.alloc<int32_t>((size_t)nf);
+    if (!df || !dl) return set_err(c, RSM_E_NOMEM, "mesh_clean: no device memory");
+    if ((s = finish(c, T)) != RSM_OK) return s;
+    int invalid = 0;
+    if ((s = mesh_components_device(df, nv, nf, dl, n_components, &invalid, c->stream)) != RSM_OK) return meshclean_fail(c, s, invalid);
+    if (nf > 0) HIPCHK(c, hipMemcpyAsync(labels, dl, sizeof(int32_t) * (size_t)nf, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RSM_OK;
+}
+
+// ---- colours of the mesh from the rig's views (k_meshcolor.hip) ----------------------------------------------------------
+static int meshcolor_params_ok(rsm_ctx *c, const rsm_mesh_color_params *p) {
+    if (!p) return set_err(c, RSM_E_INVALID, "mesh_color: params is NULL");
+    if (p->mode != 0 && p->mode != 1) return set_err(c, RSM_E_INVALID, "mesh_color: mode %d not 0 (best view) or 1 (blend)", p->mode);
+    if (!(p->min_cos >= -1.0 && p->min_cos < 1.0)) return set_err(c, RSM_E_INVALID, "mesh_color: min_cos %g outside [-1, 1)", p->min_cos);
+    if (!std::isfinite(p->depth_eps) || p->depth_eps < 0.0) return set_err(c, RSM_E_INVALID, "mesh_color: depth_eps %g negative or not finite", p->depth_eps);
+    return RSM_OK;
+}
+static int meshcolor_views_ok(rsm_ctx *c, int64_t nv, const rsm_dedup_view *v, int np) {
+    if (nv == 0) return RSM_OK;
+    if (np < 1 || np > 32767) return set_err(c, RSM_E_INVALID, "mesh_color: n_pairs %d outside 1..32767", np);
+    if (!v) return set_err(c, RSM_E_INVALID, "mesh_color: a NULL pointer (views)");
+    for (int i = 0; i < np; i++) {
+        if (v[i].width < 1 || v[i].height < 1) return set_err(c, RSM_E_INVALID, "mesh_color: pair %d: width %d / height %d < 1", i, v[i].width, v[i].height);
+        if (!v[i].image[0] || !v[i].image[1]) return set_err(c, RSM_E_INVALID, "mesh_color: pair %d: a NULL pointer (image)", i);
+    }
+    return RSM_OK;
+}
+static int meshcolor_fail(rsm_ctx *c, int s, int invalid) {
+    if (s == RSM_E_INVALID)
+        return set_err(c, s, invalid == 1 ? "mesh_color: a face index outside [0, nv)" : invalid == 2 ? "mesh_color: a coordinate that is not finite"
+                                                                                                       : "mesh_color: a singular P (det of its left 3x3 is 0)");
+    return set_err(c, s, "mesh_color: failed%s", hip_tail(s).c_str());
+}
+
+extern "C" int rsm_mesh_color_device(rsm_ctx *c, const float *d_xyz, int64_t nv, const int32_t *d_faces, int64_t nf, const rsm_dedup_view *views, int n_pairs,
+                                     const rsm_mesh_color_params *p, uint8_t *d_rgb, int32_t *d_best_view, double *stats) {
+    if (!c) return RSM_E_INVALID;
+    int s = meshcolor_params_ok(c, p);
+    if (s != RSM_OK || (s = mesh_counts_ok(c, "mesh_color", nv, nf)) != RSM_OK) return s;
+    if ((nv > 0 && (!d_xyz || !d_rgb)) || (nf > 0 && !d_faces)) return set_err(c, RSM_E_INVALID, "mesh_color: a NULL pointer");
+    if ((s = meshcolor_views_ok(c, nv, views, n_pairs)) != RSM_OK) return s;
+    HIPCHK(c, hipSetDevice(c->device));
+    int invalid = 0;
+    s = mesh_color_device(d_xyz, nv, d_faces, nf, views, n_pairs, p, c->opt_meshcolor_big_box, d_rgb, d_best_view, stats, &invalid, c->stream);
+    return s == RSM_OK ? RSM_OK : meshcolor_fail(c, s, invalid);
+}
+
+extern "C" int rsm_mesh_color(rsm_ctx *c, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, const rsm_dedup_view *views, int n_pairs,
+                              const rsm_mesh_color_params *p, uint8_t *rgb, int32_t *best_view, double *stats) {
+    if (!c) return RSM_E_INVALID;
+    int s = meshcolor_params_ok(c, p);
+    if (s != RSM_OK || (s = mesh_counts_ok(c, "mesh_color", nv, nf)) != RSM_OK) return s;
+    if ((nv > 0 && (!xyz || !rgb)) || (nf > 0 && !faces)) return set_err(c, RSM_E_INVALID, "mesh_color: a NULL pointer");
+    if ((s = meshcolor_views_ok(c, nv, views, n_pairs)) != RSM_OK) return s;
+    HIPCHK(c, hipSetDevice(c->device));
+    Tmp T(c);
+    float *dv = T.up(xyz, 3 * (size_t)nv);
+    int32_t *df = T.up(faces, 3 * (size_t)nf), *db = T.alloc<int32_t>((size_t)nv);
+    uint8_t *dc = T.alloc<uint8_t>(3 * (size_t)nv);
+    if (!dv || !df || !db || !dc) return set_err(c, RSM_E_NOMEM, "mesh_color: no device memory for %lld vertices, %lld faces", (long long)nv, (long long)nf);
+    if ((s = finish(c, T)) != RSM_OK) return s;
+    int invalid = 0;
+    s = mesh_color_device(dv, nv, df, nf, views, n_pairs, p, c->opt_meshcolor_big_box, dc, db, stats, &invalid, c->stream);
+    if (s != RSM_OK) return meshcolor_fail(c, s, invalid);
+    if (nv > 0) HIPCHK(c, hipMemcpyAsync(rgb, dc, 3 * (size_t)nv, hipMemcpyDeviceToHost, c->stream));
+    if (nv > 0 && best_view) HIPCHK(c, hipMemcpyAsync(best_view, db, sizeof(int32_t) * (size_t)nv, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RSM_OK;
+}
+
+extern "C" int rsm_mesh_color_last(rsm_ctx *c, const rsm_dedup_view *views, int n_pairs, const rsm_mesh_color_params *p, double *stats) {
+    if (!c) return RSM_E_INVALID;
+    int s = meshcolor_params_ok(c, p);
+    const int64_t nv = c->pmesh.nv, nf = c->pmesh.nf;
+    if (s != RSM_OK || (s = meshcolor_views_ok(c, nv, views, n_pairs)) != RSM_OK) return s;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (c->mcol_rgb) (void)hipFree(c->mcol_rgb);
+    if (c->mcol_best) (void)hipFree(c->mcol_best);
+    c->mcol_rgb = nullptr;
+    c->mcol_best = nullptr;
+    c->mcol_of = nullptr;
+    c->mcol_nv = 0;
+    if (hipMalloc((void **)&c->mcol_rgb, 3 * (size_t)nv + 64) != hipSuccess || hipMalloc((void **)&c->mcol_best, sizeof(int32_t) * (size_t)nv + 64) != hipSuccess)
+        return set_err(c, RSM_E_NOMEM, "mesh_color: no device memory for %lld vertices", (long long)nv);
+    int invalid = 0;
+    s = mesh_color_device(c->pmesh.d_v, nv, c->pmesh.d_f, nf, views, n_pairs, p, c->opt_meshcolor_big_box, c->mcol_rgb, c->mcol_best, stats, &invalid, c->stream);
+    if (s != RSM_OK) return meshcolor_fail(c, s, invalid);
+    c->mcol_of = c->pmesh.d_v;
+    c->mcol_nv = nv;
+    return RSM_OK;
+}
+
+extern "C" int rsm_mesh_last_colors(rsm_ctx *c, uint8_t *rgb, int32_t *best_view) {
+    if (!c) return RSM_E_INVALID;
+    if (!c->mcol_rgb || c->mcol_of != c->pmesh.d_v || c->mcol_nv != c->pmesh.nv)
+        return set_err(c, RSM_E_STATE, "mesh_last_colors: the context's last mesh has no colours (rsm_mesh_color_last first)");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (rgb && c->mcol_nv > 0) HIPCHK(c, hipMemcpyAsync(rgb, c->mcol_rgb, 3 * (size_t)c->mcol_nv, hipMemcpyDeviceToHost, c->stream));
+    if (best_view && c->mcol_nv > 0) HIPCHK(c, hipMemcpyAsync(best_view, c->mcol_best, sizeof(int32_t) * (size_t)c->mcol_nv, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RSM_OK;
+}
+
+extern "C" int rsm_texture_color(rsm_ctx *c, const float *xyz, int64_t n, const double P12[12], const uint8_t *image, int width, int height, uint8_t *rgb) {
+    if (!c) return RSM_E_INVALID;
+    if (n < 0 || n > (int64_t)INT32_MAX) return set_err(c, RSM_E_INVALID, "texture_color: n %lld outside 0..INT32_MAX", (long long)n);
+    if (width < 1 || height < 1) return set_err(c, RSM_E_INVALID, "texture_color: width %d / height %d < 1", width, height);
+    if (!P12 || !image || (n > 0 && (!xyz || !rgb))) return set_err(c, RSM_E_INVALID, "texture_color: a NULL pointer");
+    if (n == 0) return RSM_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    Tmp T(c);
+    const size_t pix = (size_t)width * (size_t)height;
+    float *dp = T.up(xyz, 3 * (size_t)n);
+    uint8_t *di = T.up(image, 3 * pix), *dc = T.alloc<uint8_t>(3 * (size_t)n);
+    if (!dp || !di || !dc) return set_err(c, RSM_E_NOMEM, "texture_color: no device memory");
+    const int s = texture_color_device(dp, n, P12, di, width, height, dc, c->stream);
+    if (s != RSM_OK) return set_err(c, s, "texture_color: failed");
+    HIPCHK(c, hipMemcpyAsync(rgb, dc, 3 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    return finish(c, T);
+}
+
+extern "C" int rsm_stage_mesh_depth(rsm_ctx *c, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, const double P12[12], int width, int height,
+                                    uint32_t *wbuf) {
+    if (!c) return RSM_E_INVALID;
+    int s = mesh_counts_ok(c, "mesh_color", nv, nf);
+    if (s != RSM_OK) return s;
+    if (width < 1 || height < 1) return set_err(c, RSM_E_INVALID, "mesh_color: width %d / height %d < 1", width, height);
+    if (!P12 || !wbuf || (nv > 0 && !xyz) || (nf > 0 && !faces)) return set_err(c, RSM_E_INVALID, "mesh_color: a NULL pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    Tmp T(c);
+    const size_t pix = (size_t)width * (size_t)height;
+    float *dv = T.up(xyz, 3 * (size_t)nv);
+    int32_t *df = T.up(faces, 3 * (size_t)nf);
+    uint32_t *dw = T.alloc<uint32_t>(pix);
+    if (!dv || !df || !dw) return set_err(c, RSM_E_NOMEM, "mesh_color: no device memory");
+    if ((s = finish(c, T)) != RSM_OK) return s;
+    int invalid = 0;
+    if ((s = mesh_depth_device(dv, nv, df, nf, P12, width, height, c->opt_meshcolor_big_box, dw, &invalid, c->stream)) != RSM_OK) return meshcolor_fail(c, s, invalid);
+    HIPCHK(c, hipMemcpyAsync(wbuf, dw, sizeof(uint32_t) * pix, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RSM_OK;
+}

@@ -186,6 +186,8 @@ def test_nothing_to_mesh_is_an_empty_mesh(ctx):
         v, f, st = ctx.poisson_mesh(xyz, nrm, 5)
         assert v.shape == (0, 3) and f.shape == (0, 3) and st["status"] == 0
         assert st["n_valid"] == valid and st["n_invalid"] == len(xyz) - valid
+    grid, b, occ, counts = ctx.poisson_rhs(np.zeros((0, 3), np.float32), np.zeros((0, 4), np.float32), 5)   # the stage entry without samples
+    assert not grid.any() and b.shape == (32, 32, 32) and not b.any() and not occ.any() and counts == (0, 0)
 
 
 def test_invalid_samples_take_no_part(ctx):

@@ -21,7 +21,7 @@ def test_constants_are_the_kernel_source_s():
 
 
 def test_options_clamp_as_rsm_set_option():
-    src = open(nr.K_MATCH.replace("k_match.hip", "rsm_api.hip")).read()
+    src = "".join(open(nr.K_MATCH.replace("k_match.hip", f)).read() for f in ("rsm_api.hip", "rsm_ctx.h"))   # rsm_set_option; struct rsm_ctx
     assert 'c->opt_ncc_mid = value <= 0 ? 0 : (int)std::max(8LL, std::min(value, 160LL));' in src
     assert 'c->opt_ncc_slide_max = (int)std::max(0LL, std::min(value, 1000000LL));' in src
     assert 'int opt_ncc_slide_max = 512;' in src
