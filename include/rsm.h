@@ -315,6 +315,9 @@ int rsm_profile_get(rsm_ctx *ctx, double *ms, int64_t *launches, double *bytes);
 int rsm_stage_find_margin(rsm_ctx *ctx, const uint8_t *mask, int W, int H, int r, rsm_boundary *m);
 int rsm_stage_pyr_down(rsm_ctx *ctx, const uint8_t *src, int W, int H, int channels, uint8_t *dst);
 int rsm_stage_erode_ellipse(rsm_ctx *ctx, const uint8_t *mask, int W, int H, int ksize, uint8_t *dst255);
+/* the NCC window-sum tables of one BGR image as the matchers build them: S1 / S2[y W + x] = sum / sum of squares of the (2r+1)^2 x 3 bytes
+ * centred on (x, y), 0 where the window leaves the image; r in 1..15 */
+int rsm_stage_box_sums(rsm_ctx *ctx, const uint8_t *img_bgr, int W, int H, int r, int32_t *S1, int32_t *S2);
 int rsm_stage_initial_match(rsm_ctx *ctx, const uint8_t *img_own, const uint8_t *img_oth,
                             const uint8_t *mask_own, const uint8_t *mask_oth, int W, int H, int r,
                             int offset, const rsm_boundary *own, const rsm_boundary *oth,

@@ -113,7 +113,7 @@ EXPORTS = [
     "rsm_create", "rsm_destroy", "rsm_last_error", "rsm_version", "rsm_abi_version", "rsm_device_count", "rsm_filter_last_cloud_host", "rsm_filter_last_info", "rsm_filter_last_normals_info", "rsm_filter_last_grid", "rsm_match_pair", "rsm_upload_pair",
     "rsm_upload_pair_device", "rsm_run_pair", "rsm_download_pair", "rsm_result_device", "rsm_export_cloud_device",
     "rsm_set_option", "rsm_profile_enable", "rsm_profile_stage_count", "rsm_profile_stage_name", "rsm_profile_get",
-    "rsm_stage_find_margin", "rsm_stage_pyr_down", "rsm_stage_erode_ellipse", "rsm_stage_initial_match",
+    "rsm_stage_find_margin", "rsm_stage_pyr_down", "rsm_stage_erode_ellipse", "rsm_stage_box_sums", "rsm_stage_initial_match",
     "rsm_stage_last_ncc_routes", "rsm_stage_smooth", "rsm_stage_order", "rsm_stage_uniqueness_pass_s16", "rsm_stage_uniqueness_pass_f64",
     "rsm_stage_set_boundary", "rsm_stage_rematch", "rsm_stage_median", "rsm_stage_refine", "rsm_stage_exp_neg", "rsm_stage_exp_neg_small", "rsm_stage_div_unscaled", "rsm_stage_sqrt_check", "rsm_stage_refine_xi", "rsm_stage_cloud",
     "rsm_bench_ncc", "rsm_write_ply", "rsm_write_ply16", "rsm_rectify_pair", "rsm_stereo_rectify", "rsm_stage_rect_map",
@@ -160,6 +160,7 @@ def load():
     lib.rsm_comm_last_error.argtypes = [C.c_void_p]
     lib.rsm_comm_destroy.restype = None
     lib.rsm_comm_destroy.argtypes = [C.c_void_p]
+    lib.rsm_stage_box_sums.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     lib.rsm_mls_cloud.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(MlsParams), C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.POINTER(C.c_int64)]
     lib.rsm_mls_cloud_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(MlsParams), C.c_void_p,

@@ -862,6 +862,14 @@ class Context:
         self._chk(self._lib.rsm_stage_erode_ellipse(self._h, _p(mask), W, H, ksize, _p(dst)))
         return dst
 
+    def box_sums(self, img, r):
+        """The NCC window-sum tables (S1, S2) of a BGR image, int32 [H, W] (include/rsm.h rsm_stage_box_sums)."""
+        img = _u8(img); H, W = img.shape[:2]
+        assert img.shape == (H, W, 3)
+        S1 = np.zeros((H, W), np.int32); S2 = np.zeros((H, W), np.int32)
+        self._chk(self._lib.rsm_stage_box_sums(self._h, _p(img), W, H, int(r), _p(S1), _p(S2)))
+        return S1, S2
+
     def initial_match(self, img_own, img_oth, mask_own, mask_oth, r, offset, own, oth, parent=None):
         img_own, img_oth, mask_own, mask_oth = map(_u8, (img_own, img_oth, mask_own, mask_oth))
         H, W = mask_own.shape
@@ -982,17 +990,22 @@ class Context:
         self._chk(self._lib.rsm_stage_sqrt_check(self._h, C.c_uint32(int(first_bits)), C.c_int64(int(n)), C.byref(m)))
         return int(m.value)
 
-    def disparity_to_cloud(self, disp, mask_org, img_own, Q, scale, R, T, own):
+    def disparity_to_cloud(self, disp, mask_org, img_own, Q, scale, R, T, own, max_points=None):
+        """(xyz, bgr) of DisparityToCloud.  max_points: the capacity handed to the stage (default W * H, which always
+        holds the cloud); when given, returns (xyz, bgr, total): the whole capacity-sized host arrays, of which the stage
+        fills the first min(total, max_points) records, and the number of points the cloud has."""
         d = np.ascontiguousarray(disp, np.float64); mask_org = _u8(mask_org); img_own = _u8(img_own)
         H, W = d.shape
         Q = np.ascontiguousarray(Q, np.float64); R = np.ascontiguousarray(R, np.float64)
         T = np.ascontiguousarray(T, np.float64)
-        cap = W * H
+        cap = W * H if max_points is None else int(max_points)
         xyz = np.zeros((cap, 3), np.float64); bgr = np.zeros((cap, 3), np.uint8)
         n = C.c_int64()
         self._chk(self._lib.rsm_stage_cloud(self._h, _p(d), _p(mask_org), _p(img_own), W, H, _p(Q), C.c_double(scale),
                                             _p(R), _p(T), C.byref(_bd(own)), _p(xyz), _p(bgr), C.c_int64(cap),
                                             C.byref(n)))
+        if max_points is not None:
+            return xyz, bgr, int(n.value)
         return xyz[:n.value].copy(), bgr[:n.value].copy()
 
 

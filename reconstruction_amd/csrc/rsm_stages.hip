@@ -48,6 +48,22 @@ extern "C" int rsm_stage_erode_ellipse(rsm_ctx *c, const uint8_t *mask, int W, i
     return finish(c, t);
 }
 
+extern "C" int rsm_stage_box_sums(rsm_ctx *c, const uint8_t *img_bgr, int W, int H, int r, int32_t *S1, int32_t *S2) {
+    if (!stage_ok(c, W, H) || !img_bgr || !S1 || !S2 || r < 1 || r > 15) return RSM_E_INVALID;
+    Tmp t(c);
+    const size_t px = (size_t)W * H;
+    uint8_t *di = t.up(img_bgr, px * 3);
+    uint32_t *i4 = t.alloc<uint32_t>(px);
+    int32_t *d1 = t.alloc<int32_t>(px), *d2 = t.alloc<int32_t>(px);
+    int32_t *t1 = t.alloc<int32_t>(px), *t2 = t.alloc<int32_t>(px);
+    if (!t.ok) return finish(c, t);
+    launch_bgr_to_bgrx(di, W, H, i4, c->stream); // the sequence of setup_match below
+    launch_box_sums(i4, W, H, r, t1, t2, d1, d2, c->stream);
+    t.down(S1, (const int32_t *)d1, px);
+    t.down(S2, (const int32_t *)d2, px);
+    return finish(c, t);
+}
+
 namespace {
 // uploads the images/masks of one direction and builds the window-sum tables
 struct MatchBufs {

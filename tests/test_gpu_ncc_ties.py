@@ -83,6 +83,11 @@ CASES = [
     ("saturated", 192, 96, 2, 2, 15, 8),
     ("periodic", 192, 72, 2, 2, 16, -4),
     ("periodic2d", 192, 96, 3, 2, 17, 8),
+    # radii 9..15: ties decided by k_ncc_exact on windows of 1083 / 1875 / 2883 bytes, found by the byte-wise kernel in all three modes
+    ("2level", 150, 64, 1, 12, 31, 3),
+    ("3level", 150, 64, 1, 15, 32, -4),
+    ("periodic", 256, 128, 2, 9, 33, 4),
+    ("2level", 256, 128, 2, 15, 34, 6),
 ]
 
 

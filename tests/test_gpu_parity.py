@@ -36,6 +36,13 @@ CASES = {
     "s144x96_r1_r6": dict(width=144, height=96, levels=2, radius=1, offset=5, pair=9, occlude=True, mask_l0_width=50,
                           border_l0=4),
     "s288x160_r6": dict(width=288, height=160, levels=3, radius=6, offset=2, pair=10, mask_l0_width=40, border_l0=9),
+    # radii 8..15: k_box_h_any, k_ncc_bytes by dispatch in all three modes, k_ncc_exact on windows of up to 2883 bytes
+    "s192x128_r8": dict(width=192, height=128, levels=2, radius=8, offset=2, pair=3, holes=True, mask_l0_width=60, border_l0=2),
+    "s224x144_r11_neg": dict(width=224, height=144, levels=2, radius=11, offset=3, pair=4, occlude=True, mask_l0_width=80,
+                             border_l0=1),
+    "s192x128_r15": dict(width=192, height=128, levels=2, radius=15, offset=2, pair=5, mask_l0_width=70, border_l0=1),
+    "s384x256_r9_3levels": dict(width=384, height=256, levels=3, radius=9, offset=2, pair=6, holes=True, mask_l0_width=60,
+                                border_l0=1),
 }
 
 _cache = {}
@@ -269,10 +276,8 @@ def test_order_constraint_heavy_crossings(ctx):
     assert np.array_equal(a, b), diff_report("order heavy", a, b)
 
 
-@pytest.mark.parametrize("opt", [("ncc_bytes", 1)])
-def test_kernel_variants_give_identical_results(ctx, opt):
-    """The dot4 and the generic byte-wise NCC kernels are interchangeable bit for bit."""
-    cfg = synth.config_small(**CASES["s320x160_occluded_neg_r4"])
+def _pair_under_option(ctx, name, opt):
+    cfg = synth.config_small(**CASES[name])
     base = ctx.match_pair(cfg)
     ctx.set_option(*opt)
     try:
@@ -282,6 +287,19 @@ def test_kernel_variants_give_identical_results(ctx, opt):
     for v in range(2):
         assert np.array_equal(base.disparity[v], alt.disparity[v]), opt
     assert np.array_equal(base.xyz, alt.xyz, equal_nan=True)
+    return base
+
+
+@pytest.mark.parametrize("opt", [("ncc_bytes", 1)])
+def test_kernel_variants_give_identical_results(ctx, opt):
+    """The dot4 and the generic byte-wise NCC kernels are interchangeable bit for bit."""
+    _pair_under_option(ctx, "s320x160_occluded_neg_r4", opt)
+
+
+def test_ncc_bytes_option_changes_nothing_above_radius_7(ctx):
+    """Radius 8 reaches the byte-wise kernel by dispatch; the option asks for what already happens."""
+    base = _pair_under_option(ctx, "s192x128_r8", ("ncc_bytes", 1))
+    assert base.n_points > 0
 
 
 def test_reference_shaped_mirror_drives_the_pipeline(ctx):
