@@ -1,6 +1,8 @@
 """Shared test helpers: the oracle's MatchOneLayer sequence with every stage boundary captured."""
 from __future__ import annotations
 
+import contextlib
+
 import numpy as np
 
 from oracle import oracle as orc
@@ -98,6 +100,58 @@ def diff_report(name, a, b):
         idx = tuple(int(i) for i in idx)
         msg += "\n   at %s: got %s expected %s" % (idx, a[idx], b[idx])
     return msg
+
+
+class BitsResult:
+    """Truthy when the bit patterns were equal; its text is the report.  `r = bits_equal(a, b); assert r, r`."""
+
+    def __init__(self, ok, text):
+        self.ok, self.text = ok, text
+
+    def __bool__(self):
+        return self.ok
+
+    def __str__(self):
+        return self.text
+
+    __repr__ = __str__
+
+
+def bits_equal(a, b, name=""):
+    """Bit patterns of two float arrays (uint64 / uint32 views): -0.0 differs from +0.0, +inf from -inf, one NaN pattern from
+    another -- what `==` and np.array_equal cannot see.  Reports the first differing element with both values in hex."""
+    a = np.ascontiguousarray(a); b = np.ascontiguousarray(b)
+    if a.shape != b.shape or a.dtype != b.dtype:
+        return BitsResult(False, "%s: shape / dtype %s %s against %s %s" % (name, a.shape, a.dtype, b.shape, b.dtype))
+    view = {8: np.uint64, 4: np.uint32, 2: np.uint16, 1: np.uint8}[a.dtype.itemsize]
+    ua, ub = a.view(view), b.view(view)
+    bad = np.argwhere(ua != ub)
+    if len(bad) == 0:
+        return BitsResult(True, "%s: bit-equal" % name)
+    idx = tuple(int(i) for i in bad[0])
+    width = 2 * a.dtype.itemsize
+    return BitsResult(False, "%s: %d / %d elements differ in their bits; first at %s: got %r = 0x%0*x, expected %r = 0x%0*x"
+                      % (name, len(bad), a.size, idx, a[idx].item(), width, int(ua[idx]), b[idx].item(), width, int(ub[idx])))
+
+
+# The refine schedule's defaults (rsm_ctx.h), in ONE place: every test that changes one of them goes through refine_options,
+# which puts these back -- the session's context is shared, and files run in name order.
+REFINE_DEFAULTS = dict(refine_skew_from=4, refine_rekey_until=22, refine_rekey_side=0, refine_skew_uw=0, refine_skew_rows=0,
+                       refine_skew_T=4, refine_skew_min_px=1000000)
+
+
+@contextlib.contextmanager
+def refine_options(ctx, **opts):
+    """Sets the refine schedule's options (the defaults where not given) on a context and restores the defaults on exit."""
+    unknown = set(opts) - set(REFINE_DEFAULTS)
+    assert not unknown, unknown
+    try:
+        for k, v in dict(REFINE_DEFAULTS, **opts).items():
+            ctx.set_option(k, v)
+        yield ctx
+    finally:
+        for k, v in REFINE_DEFAULTS.items():
+            ctx.set_option(k, v)
 
 
 def libm_exp_stats(res_disp, ref_disp):

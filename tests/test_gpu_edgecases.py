@@ -6,6 +6,8 @@ import pytest
 from oracle import oracle as orc
 from reconstruction_amd import synth
 
+from helpers import refine_options
+
 pytestmark = pytest.mark.gpu
 NOMATCH = -10000
 
@@ -149,18 +151,9 @@ def test_refine_with_weights_across_the_exps_whole_range(ctx, skew):
     d[:, 100:140] += 40                                                                          # a whole band far away: both weights 0 along its edges
     d[rng.random((H, W)) < 0.05] = NOMATCH
     own = (3, H - 4, 4, W - 5, W - 8, H - 6)
-    if skew:
-        ctx.set_option("refine_skew_T", skew)
-        ctx.set_option("refine_skew_from", 1)
-        ctx.set_option("refine_skew_min_px", 0)
-        ctx.set_option("refine_skew_rows", 16)
-    try:
+    opts = dict(refine_skew_T=skew, refine_skew_from=1, refine_skew_min_px=0, refine_skew_rows=16) if skew else {}
+    with refine_options(ctx, **opts):
         a = ctx.disparity_refine(d, img0, img1, iters, 0.03, own)
-    finally:
-        ctx.set_option("refine_skew_T", 4)
-        ctx.set_option("refine_skew_from", 22)
-        ctx.set_option("refine_skew_min_px", 1000000)
-        ctx.set_option("refine_skew_rows", 0)
     b = orc.disparity_refine(d, img0, img1, iters, 0.03, own)
     assert np.array_equal(a == NOMATCH, b == NOMATCH)
     assert np.array_equal(a, b), float(np.abs(a - b).max())

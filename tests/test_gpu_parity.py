@@ -12,7 +12,7 @@ import pytest
 from oracle import oracle as orc
 from reconstruction_amd import synth
 
-from helpers import NOMATCH, cloud_scale, diff_report, host_libm_is_glibc_with_fma, libm_exp_stats, oracle_stages
+from helpers import NOMATCH, cloud_scale, diff_report, host_libm_is_glibc_with_fma, libm_exp_stats, oracle_stages, refine_options
 
 pytestmark = pytest.mark.gpu
 
@@ -406,12 +406,7 @@ def test_refine_time_skewed_sweeps_are_bit_identical(ctx, T, first, rows, uw):
     from sweep `first` on -- from the first cached sweep, where nearly every pixel misses and every row takes the rare path, to
     the settled regime -- gives the single-sweep result, i.e. the oracle's, bit for bit; chunk heights from 4T rows to the whole
     level, sweep counts that leave 0..T-1 single sweeps at the end, strips of 66 - 2T columns (the default) and narrower."""
-    ctx.set_option("refine_skew_from", first)
-    ctx.set_option("refine_skew_T", T)
-    ctx.set_option("refine_skew_min_px", 0)
-    ctx.set_option("refine_skew_rows", rows)
-    ctx.set_option("refine_skew_uw", uw)
-    try:
+    with refine_options(ctx, refine_skew_from=first, refine_skew_T=T, refine_skew_min_px=0, refine_skew_rows=rows, refine_skew_uw=uw):
         for name in ("s512x384_5levels", "s192x128_ellipse", "s320x160_occluded_neg_r4"):
             cfg, rec, fin = stages(name)
             for q in rec:
@@ -425,9 +420,3 @@ def test_refine_time_skewed_sweeps_are_bit_identical(ctx, T, first, rows, uw):
             res = ctx.match_pair(cfg)
             for v in range(2):
                 assert np.array_equal(res.disparity[v], fin["disparity"][v])
-    finally:
-        ctx.set_option("refine_skew_from", 22)  # the defaults
-        ctx.set_option("refine_skew_T", 4)
-        ctx.set_option("refine_skew_min_px", 1000000)
-        ctx.set_option("refine_skew_rows", 0)
-        ctx.set_option("refine_skew_uw", 0)

@@ -7,7 +7,7 @@ import pytest
 from oracle import oracle as orc
 from reconstruction_amd import synth
 
-from helpers import diff_report, oracle_stages
+from helpers import diff_report, oracle_stages, refine_options
 
 pytestmark = pytest.mark.gpu
 
@@ -27,10 +27,6 @@ def stages(name):
         cfg = synth.config_small(**CASES[name])
         _cache[name] = (cfg,) + tuple(oracle_stages(cfg))
     return _cache[name]
-
-
-DEFAULTS = dict(refine_skew_from=4, refine_skew_T=4, refine_skew_min_px=1000000, refine_skew_rows=0, refine_rekey_until=22,
-                refine_rekey_side=0)
 
 
 def check_refine(ctx, label):
@@ -56,12 +52,6 @@ def test_refine_rekey_sweeps_are_bit_identical(ctx, T, first, until, rows, side)
     """Time-skewed launches from sweep `first` (T = 2, 3, 4), each one that starts before sweep `until` preceded by the re-key pass
     -- the nearest-side neighbour (side 0) or the other one (side 1, a deliberately wrong prediction); until = 0: no re-key, the
     early launches miss heavily -- with chunk heights from 4T rows to the whole level: the oracle's result, bit for bit."""
-    opts = dict(DEFAULTS, refine_skew_from=first, refine_skew_T=T, refine_skew_min_px=0, refine_skew_rows=rows,
-                refine_rekey_until=until, refine_rekey_side=side)
-    for k, v in opts.items():
-        ctx.set_option(k, v)
-    try:
+    with refine_options(ctx, refine_skew_from=first, refine_skew_T=T, refine_skew_min_px=0, refine_skew_rows=rows,
+                        refine_rekey_until=until, refine_rekey_side=side):
         check_refine(ctx, "T %d from %d rekey until %d side %d rows %d" % (T, first, until, side, rows))
-    finally:
-        for k, v in DEFAULTS.items():
-            ctx.set_option(k, v)
