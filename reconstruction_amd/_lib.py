@@ -48,6 +48,9 @@ class PairIn(C.Structure):
                 ("T_final", C.c_double * 3), ("verbose", C.c_int)]
 
 
+RSM_ABI_VERSION = 2   # include/rsm.h: the struct layouts mirrored here (PairOut carries points16); load() holds the library to it
+
+
 class PairOut(C.Structure):
     _fields_ = [("disparity", C.c_void_p * 2), ("margin", Boundary * 2),
                 ("n_points", C.c_int64), ("max_points", C.c_int64),
@@ -108,32 +111,115 @@ class RectifyOut(C.Structure):
                 ("image", C.c_void_p * 2), ("mask", C.c_void_p * 2)]
 
 
-# every symbol include/rsm.h declares (tests/test_abi.py checks the header against this list)
-EXPORTS = [
-    "rsm_create", "rsm_destroy", "rsm_last_error", "rsm_version", "rsm_abi_version", "rsm_device_count", "rsm_filter_last_cloud_host", "rsm_filter_last_info", "rsm_filter_last_normals_info", "rsm_filter_last_grid", "rsm_match_pair", "rsm_upload_pair",
-    "rsm_upload_pair_device", "rsm_run_pair", "rsm_download_pair", "rsm_result_device", "rsm_export_cloud_device",
-    "rsm_set_option", "rsm_profile_enable", "rsm_profile_stage_count", "rsm_profile_stage_name", "rsm_profile_get",
-    "rsm_stage_find_margin", "rsm_stage_pyr_down", "rsm_stage_erode_ellipse", "rsm_stage_box_sums", "rsm_stage_initial_match",
-    "rsm_stage_last_ncc_routes", "rsm_stage_smooth", "rsm_stage_order", "rsm_stage_uniqueness_pass_s16", "rsm_stage_uniqueness_pass_f64",
-    "rsm_stage_set_boundary", "rsm_stage_rematch", "rsm_stage_median", "rsm_stage_refine", "rsm_stage_exp_neg", "rsm_stage_exp_neg_small", "rsm_stage_div_unscaled", "rsm_stage_sqrt_check", "rsm_stage_refine_xi", "rsm_stage_cloud",
-    "rsm_bench_ncc", "rsm_write_ply", "rsm_write_ply16", "rsm_rectify_pair", "rsm_stereo_rectify", "rsm_stage_rect_map",
-    "rsm_stage_remap", "rsm_stage_erode_gray", "rsm_run_pairs", "rsm_run_pairs_repeat", "rsm_match_pairs", "rsm_match_pairs_multi_gpu",
-    "rsm_pack_cloud16", "rsm_comm_unique_id", "rsm_comm_create", "rsm_comm_destroy", "rsm_comm_last_error",
-    "rsm_gather_clouds", "rsm_gather_counts", "rsm_gather_meta_fill", "rsm_gather_plan", "rsm_comm_create_transport",
-    "rsm_filter_cloud", "rsm_filter_last_cloud", "rsm_host_alloc", "rsm_host_free", "rsm_host_register", "rsm_host_unregister",
-    "rsm_mls_cloud", "rsm_mls_cloud_device", "rsm_dedup_cloud", "rsm_dedup_cloud_device",
-    "rsm_poisson_mesh", "rsm_poisson_mesh_device", "rsm_poisson_last_mesh", "rsm_poisson_last_mesh_device",
-    "rsm_stage_poisson_rhs", "rsm_stage_poisson_solve", "rsm_stage_iso_mesh", "rsm_write_ply_mesh",
-    "rsm_mesh_clean", "rsm_mesh_clean_device", "rsm_mesh_clean_last", "rsm_stage_mesh_smooth", "rsm_stage_mesh_components",
-    "rsm_mesh_color", "rsm_mesh_color_device", "rsm_mesh_color_last", "rsm_mesh_last_colors", "rsm_texture_color", "rsm_stage_mesh_depth",
-    "rsm_write_ply_mesh_color",
-]
+# ---- the prototypes of include/rsm.h, one row per function: name -> (restype, argtypes); tests/test_abi.py holds every row against the header.
+# Pointers to the structs above are typed; every other data, handle or array pointer is void *.
+_I, _L, _U, _LL, _Z, _D, _V, _S = C.c_int, C.c_int64, C.c_uint32, C.c_longlong, C.c_size_t, C.c_double, C.c_void_p, C.c_char_p
+_pI, _pL, _pD = C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_double)
+_PIN, _POUT, _BND, _RIN, _ROUT, _FLT = (C.POINTER(t) for t in (PairIn, PairOut, Boundary, RectifyIn, RectifyOut, FilterParams))
+_MLS, _VIEW, _PSN, _CLN, _COL = (C.POINTER(t) for t in (MlsParams, DedupView, PoissonParams, MeshCleanParams, MeshColorParams))
+PROTOTYPES = {
+    "rsm_create": (_I, [_V, _I]),
+    "rsm_destroy": (None, [_V]),
+    "rsm_last_error": (_S, [_V]),
+    "rsm_version": (_S, []),
+    "rsm_abi_version": (_I, []),
+    "rsm_device_count": (_I, []),
+    "rsm_match_pair": (_I, [_V, _PIN, _POUT]),
+    "rsm_upload_pair": (_I, [_V, _PIN]),
+    "rsm_upload_pair_device": (_I, [_V, _PIN]),
+    "rsm_run_pair": (_I, [_V]),
+    "rsm_download_pair": (_I, [_V, _POUT]),
+    "rsm_host_alloc": (_V, [_Z]),
+    "rsm_host_free": (None, [_V]),
+    "rsm_host_register": (_I, [_V, _Z]),
+    "rsm_host_unregister": (_I, [_V]),
+    "rsm_result_device": (_I, [_V, _V, _V, _V, _V, _V]),
+    "rsm_export_cloud_device": (_I, [_V, _V, _V, _L]),
+    "rsm_run_pairs": (_I, [_V, _I]),
+    "rsm_run_pairs_repeat": (_I, [_V, _I, _I]),
+    "rsm_match_pairs": (_I, [_V, _I, _PIN, _POUT, _I, _V]),
+    "rsm_match_pairs_multi_gpu": (_I, [_PIN, _I, _I, _I, _POUT, _V]),
+    "rsm_pack_cloud16": (_I, [_V, _V, _L, _V]),
+    "rsm_comm_unique_id": (_I, [_S]),
+    "rsm_comm_create": (_I, [_V, _S, _I, _I, _I]),
+    "rsm_comm_create_transport": (_I, [_V, _V, _I, _I]),
+    "rsm_comm_destroy": (None, [_V]),
+    "rsm_comm_last_error": (_S, [_V]),
+    "rsm_gather_clouds": (_I, [_V, _I, _I, _V, _V, _V, _I, _V, _L, _V]),
+    "rsm_gather_counts": (_I, [_V, _I, _V, _V, _I, _V]),
+    "rsm_gather_meta_fill": (_I, [_I, _I, _I, _I, _V, _V, _I, _L, _V]),
+    "rsm_gather_plan": (_I, [_I, _I, _I, _I, _V, _V, _I, _V, _V, _V, _I, _V]),
+    "rsm_set_option": (_I, [_V, _S, _LL]),
+    "rsm_profile_enable": (_I, [_V, _I]),
+    "rsm_profile_stage_count": (_I, []),
+    "rsm_profile_stage_name": (_S, [_I]),
+    "rsm_profile_get": (_I, [_V, _V, _V, _V]),
+    "rsm_stage_find_margin": (_I, [_V, _V, _I, _I, _I, _BND]),
+    "rsm_stage_pyr_down": (_I, [_V, _V, _I, _I, _I, _V]),
+    "rsm_stage_erode_ellipse": (_I, [_V, _V, _I, _I, _I, _V]),
+    "rsm_stage_box_sums": (_I, [_V, _V, _I, _I, _I, _V, _V]),
+    "rsm_stage_initial_match": (_I, [_V, _V, _V, _V, _V, _I, _I, _I, _I, _BND, _BND, _V, _I, _I, _V]),
+    "rsm_stage_last_ncc_routes": (_I, [_V, _I, _V, _V, _V, _V, _V, _V]),
+    "rsm_stage_smooth": (_I, [_V, _V, _I, _I, _BND]),
+    "rsm_stage_order": (_I, [_V, _V, _I, _I, _BND]),
+    "rsm_stage_uniqueness_pass_s16": (_I, [_V, _V, _V, _I, _I, _BND, _BND]),
+    "rsm_stage_uniqueness_pass_f64": (_I, [_V, _V, _V, _I, _I, _BND, _BND]),
+    "rsm_stage_set_boundary": (_I, [_V, _V, _V, _I, _I, _BND, _BND, _V, _V]),
+    "rsm_stage_rematch": (_I, [_V, _V, _V, _V, _V, _I, _I, _I, _BND, _BND, _V]),
+    "rsm_stage_median": (_I, [_V, _V, _V, _I, _I, _BND]),
+    "rsm_stage_refine": (_I, [_V, _V, _V, _V, _I, _I, _I, _D, _BND, _V]),
+    "rsm_stage_exp_neg": (_I, [_V, _V, _L, _V]),
+    "rsm_stage_exp_neg_small": (_I, [_V, _V, _L, _V]),
+    "rsm_stage_div_unscaled": (_I, [_V, _V, _V, _L, _V, _V]),
+    "rsm_stage_sqrt_check": (_I, [_V, _U, _L, _V]),
+    "rsm_stage_refine_xi": (_I, [_V, _V, _V, _I, _I, _I, _V]),
+    "rsm_stage_cloud": (_I, [_V, _V, _V, _V, _I, _I, _V, _D, _V, _V, _BND, _V, _V, _L, _V]),
+    "rsm_rectify_pair": (_I, [_V, _RIN, _I, _D, _I, _I, _ROUT]),
+    "rsm_stereo_rectify": (_I, [_V, _V, _I, _I, _V, _V, _V, _V, _V, _V, _V]),
+    "rsm_stage_rect_map": (_I, [_V, _V, _V, _V, _I, _I, _V, _V]),
+    "rsm_stage_remap": (_I, [_V, _V, _I, _I, _I, _V, _V, _I, _I, _V]),
+    "rsm_stage_erode_gray": (_I, [_V, _V, _I, _I, _I, _V]),
+    "rsm_write_ply": (_I, [_S, _V, _V, _L]),
+    "rsm_write_ply16": (_I, [_S, _V, _L]),
+    "rsm_filter_cloud": (_I, [_V, _V, _L, _FLT, _V, _V, _V, _V]),
+    "rsm_filter_last_cloud": (_I, [_V, _FLT, _V, _V, _L, _V, _V]),
+    "rsm_filter_last_info": (_I, [_V, _V]),
+    "rsm_filter_last_normals_info": (_I, [_V, _V]),
+    "rsm_filter_last_grid": (_I, [_V, _V, _V]),
+    "rsm_filter_last_cloud_host": (_I, [_V, _FLT, _V, _V, _L, _V, _V]),
+    "rsm_mls_cloud": (_I, [_V, _V, _L, _V, _MLS, _V, _V, _V, _pL]),
+    "rsm_mls_cloud_device": (_I, [_V, _V, _L, _V, _MLS, _V, _V, _V, _pL]),
+    "rsm_dedup_cloud": (_I, [_V, _V, _V, _L, _VIEW, _I, _V, _pL, _pL]),
+    "rsm_dedup_cloud_device": (_I, [_V, _V, _V, _L, _VIEW, _I, _V, _V, _V, _pL, _pL]),
+    "rsm_poisson_mesh": (_I, [_V, _V, _V, _L, _PSN, _pL, _pL, _V]),
+    "rsm_poisson_mesh_device": (_I, [_V, _V, _V, _L, _PSN, _pL, _pL, _V]),
+    "rsm_poisson_last_mesh": (_I, [_V, _V, _V]),
+    "rsm_poisson_last_mesh_device": (_I, [_V, _V, _V]),
+    "rsm_stage_poisson_rhs": (_I, [_V, _V, _V, _L, _PSN, _V, _V, _V, _V]),
+    "rsm_stage_poisson_solve": (_I, [_V, _V, _I, _D, _I, _V, _pD, _pI, _V]),
+    "rsm_stage_iso_mesh": (_I, [_V, _V, _I, _D, _V, _V, _I, _pL, _pL]),
+    "rsm_write_ply_mesh": (_I, [_S, _V, _L, _V, _L]),
+    "rsm_mesh_clean": (_I, [_V, _V, _L, _V, _L, _CLN, _pL, _pL, _V]),
+    "rsm_mesh_clean_device": (_I, [_V, _V, _L, _V, _L, _CLN, _pL, _pL, _V]),
+    "rsm_mesh_clean_last": (_I, [_V, _CLN, _pL, _pL, _V]),
+    "rsm_stage_mesh_smooth": (_I, [_V, _V, _L, _V, _L, _I, _I, _I, _V, _pL]),
+    "rsm_stage_mesh_components": (_I, [_V, _V, _L, _L, _V, _pL]),
+    "rsm_mesh_color": (_I, [_V, _V, _L, _V, _L, _VIEW, _I, _COL, _V, _V, _V]),
+    "rsm_mesh_color_device": (_I, [_V, _V, _L, _V, _L, _VIEW, _I, _COL, _V, _V, _V]),
+    "rsm_mesh_color_last": (_I, [_V, _VIEW, _I, _COL, _V]),
+    "rsm_mesh_last_colors": (_I, [_V, _V, _V]),
+    "rsm_texture_color": (_I, [_V, _V, _L, _V, _V, _I, _I, _V]),
+    "rsm_stage_mesh_depth": (_I, [_V, _V, _L, _V, _L, _V, _I, _I, _V]),
+    "rsm_write_ply_mesh_color": (_I, [_S, _V, _L, _V, _L, _V]),
+    "rsm_bench_ncc": (_I, [_V, _I, _I, _I, _I, _I, _V]),
+}
+EXPORTS = list(PROTOTYPES)   # every symbol include/rsm.h declares
 
 _lib = None
 
 
 def load():
-    """Load the HIP library; raises if it has not been built (no fallback)."""
+    """Load the HIP library and give every function its prototype; raises if it has not been built (no fallback)."""
     global _lib
     if _lib is not None:
         return _lib
@@ -141,60 +227,11 @@ def load():
         raise RsmError(RSM_E_STATE, "librsm_mi355.so not built: run `python -c 'import __graft_entry__ as g; "
                                     "g.build()'` (hipcc, gfx950); there is no CPU fallback")
     lib = C.CDLL(LIB_PATH)
-    lib.rsm_last_error.restype = C.c_char_p
-    lib.rsm_last_error.argtypes = [C.c_void_p]
-    lib.rsm_version.restype = C.c_char_p
-    abi = lib.rsm_abi_version() if hasattr(lib, "rsm_abi_version") else 1   # include/rsm.h: RSM_ABI_VERSION (PairOut below carries points16)
-    if abi != 2 and os.environ.get("RSM_AB_OLD_LIBRARY") != "1":          # (the A/B scripts load round 5's library: same layouts, no version symbol)
-        raise RsmError(RSM_E_STATE, "librsm_mi355.so has ABI %d, this binding ABI 2: rebuild the library" % abi)
-    lib.rsm_profile_stage_name.restype = C.c_char_p
-    lib.rsm_destroy.restype = None
-    lib.rsm_host_alloc.restype = C.c_void_p
-    lib.rsm_host_alloc.argtypes = [C.c_size_t]
-    lib.rsm_host_free.restype = None
-    lib.rsm_host_free.argtypes = [C.c_void_p]
-    lib.rsm_host_register.argtypes = [C.c_void_p, C.c_size_t]
-    lib.rsm_host_unregister.argtypes = [C.c_void_p]
-    lib.rsm_destroy.argtypes = [C.c_void_p]
-    lib.rsm_comm_last_error.restype = C.c_char_p
-    lib.rsm_comm_last_error.argtypes = [C.c_void_p]
-    lib.rsm_comm_destroy.restype = None
-    lib.rsm_comm_destroy.argtypes = [C.c_void_p]
-    lib.rsm_stage_box_sums.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    lib.rsm_mls_cloud.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(MlsParams), C.c_void_p, C.c_void_p,
-                                  C.c_void_p, C.POINTER(C.c_int64)]
-    lib.rsm_mls_cloud_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(MlsParams), C.c_void_p,
-                                         C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
-    lib.rsm_dedup_cloud.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(DedupView), C.c_int, C.c_void_p,
-                                    C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-    lib.rsm_dedup_cloud_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(DedupView), C.c_int, C.c_void_p,
-                                           C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-    for name in ("rsm_poisson_mesh", "rsm_poisson_mesh_device"):
-        getattr(lib, name).argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(PoissonParams), C.POINTER(C.c_int64),
-                                       C.POINTER(C.c_int64), C.c_void_p]
-    lib.rsm_poisson_last_mesh.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.rsm_poisson_last_mesh_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.rsm_stage_poisson_rhs.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(PoissonParams), C.c_void_p, C.c_void_p,
-                                          C.c_void_p, C.c_void_p]
-    lib.rsm_stage_poisson_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_void_p, C.POINTER(C.c_double),
-                                            C.POINTER(C.c_int), C.c_void_p]
-    lib.rsm_stage_iso_mesh.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int64),
-                                       C.POINTER(C.c_int64)]
-    lib.rsm_write_ply_mesh.argtypes = [C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]
-    for name in ("rsm_mesh_clean", "rsm_mesh_clean_device"):
-        getattr(lib, name).argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(MeshCleanParams), C.POINTER(C.c_int64),
-                                       C.POINTER(C.c_int64), C.c_void_p]
-    lib.rsm_mesh_clean_last.argtypes = [C.c_void_p, C.POINTER(MeshCleanParams), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p]
-    lib.rsm_stage_mesh_smooth.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                          C.POINTER(C.c_int64)]
-    lib.rsm_stage_mesh_components.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.POINTER(C.c_int64)]
-    for name in ("rsm_mesh_color", "rsm_mesh_color_device"):
-        getattr(lib, name).argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(DedupView), C.c_int,
-                                       C.POINTER(MeshColorParams), C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.rsm_mesh_color_last.argtypes = [C.c_void_p, C.POINTER(DedupView), C.c_int, C.POINTER(MeshColorParams), C.c_void_p]
-    lib.rsm_mesh_last_colors.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.rsm_texture_color.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-    lib.rsm_stage_mesh_depth.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-    lib.rsm_write_ply_mesh_color.argtypes = [C.c_char_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    abi = lib.rsm_abi_version()
+    if abi != RSM_ABI_VERSION:
+        raise RsmError(RSM_E_STATE, "librsm_mi355.so has ABI %d, this binding ABI %d: rebuild the library" % (abi, RSM_ABI_VERSION))
     _lib = lib
     return lib

@@ -1,0 +1,231 @@
+"""The surface stages (csrc/rsm_mesh.hip): dense-grid Poisson surface and trim, smoothing and clean-up, colours from the rig's views."""
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from ._context import ContextBase, _normals4, _p, _u8, _views
+from ._lib import MeshCleanParams, MeshColorParams, PoissonParams
+
+# the solve's default stopping residual: one decade above the 4.2e-6 the float32 solver reaches at depth 9
+POISSON_REL_RESIDUAL = 4e-5
+POISSON_MAX_CYCLES = 100
+# meshlab.bat's script1 / script2 settings: the defaults of mesh_clean, mesh_clean_device and mesh_clean_last
+_MC = dict(smooth_steps=5, cotangent=True, boundary=True, min_piece=0.10, relative=True, duplicates=True, zero_area=True, nonmanifold=True)
+
+
+def _mesh_arrays(vertices, faces):
+    return np.ascontiguousarray(vertices, np.float32).reshape(-1, 3), np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+
+
+class MeshPart(ContextBase):
+    # ---- surface from the oriented cloud: dense-grid Poisson + trim (csrc/k_poisson.hip) ----
+    def poisson_last_mesh(self, n_vertices, n_faces):
+        """The context's last mesh on the host: (vertices float32 [nv,3], faces int32 [nf,3])."""
+        v = np.zeros((max(n_vertices, 1), 3), np.float32)
+        f = np.zeros((max(n_faces, 1), 3), np.int32)
+        self._chk(self._lib.rsm_poisson_last_mesh(self._h, _p(v), _p(f)))
+        return v[:n_vertices].copy(), f[:n_faces].copy()
+
+    def _poisson(self, fn, xyz, nrm, n, depth, scale, trim_cells, rel_residual, max_cycles):
+        nv, nf = C.c_int64(), C.c_int64()
+        st = (C.c_double * _lib.POISSON_STATS)()
+        prm = PoissonParams(int(depth), float(scale), float(rel_residual), int(max_cycles), int(trim_cells))
+        status = fn(self._h, xyz, nrm, n, C.byref(prm), C.byref(nv), C.byref(nf), st)
+        if status < 0:
+            self._chk(status)
+        stats = dict(n_valid=int(st[0]), n_invalid=int(st[1]), residual=float(st[2]), cycles=int(st[3]), iso=float(st[4]),
+                     origin=(float(st[5]), float(st[6]), float(st[7])), h=float(st[8]), N=int(st[9]), n_vertices_untrimmed=int(st[10]),
+                     n_faces_untrimmed=int(st[11]), status=int(status), converged=status == 0)
+        return int(nv.value), int(nf.value), stats
+
+    def poisson_mesh(self, xyz, normals, depth=9, scale=1.1, trim_cells=4, rel_residual=POISSON_REL_RESIDUAL, max_cycles=POISSON_MAX_CYCLES):
+        """Unscreened Poisson reconstruction on a dense 2^depth grid, marching tetrahedra and the occupancy trim, of a host cloud:
+        xyz [n,3] float32 with normals [n,4] or [n,3] (what mls_cloud returns).  Returns (vertices float32 [nv,3], faces int32 [nf,3],
+        stats dict); stats['converged'] is False (status 1) when max_cycles came before rel_residual -- the mesh is that of the
+        chi reached.  Samples that are not finite or have a zero normal take no part (stats['n_invalid'])."""
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        nrm = _normals4(normals, len(xyz))
+        nv, nf, stats = self._poisson(self._lib.rsm_poisson_mesh, _p(xyz), _p(nrm), len(xyz), depth, scale, trim_cells, rel_residual, max_cycles)
+        return self.poisson_last_mesh(nv, nf) + (stats,)
+
+    def poisson_mesh_device(self, xyz_ptr, normals_ptr, n, depth=9, scale=1.1, trim_cells=4, rel_residual=POISSON_REL_RESIDUAL,
+                            max_cycles=POISSON_MAX_CYCLES):
+        """rsm_poisson_mesh_device on device buffers (addresses): n float xyz (stride 3) and n float4 normals, as mls_cloud_device leaves
+        them.  The mesh stays with the context: returns (n_vertices, n_faces, stats); poisson_last_mesh[_device] copies it out."""
+        return self._poisson(self._lib.rsm_poisson_mesh_device, xyz_ptr, normals_ptr, n, depth, scale, trim_cells, rel_residual, max_cycles)
+
+    def poisson_last_mesh_device(self, vertices_ptr, faces_ptr):
+        """Copies the context's last mesh into caller-owned device buffers (addresses; either may be 0)."""
+        self._chk(self._lib.rsm_poisson_last_mesh_device(self._h, vertices_ptr, faces_ptr))
+
+    def poisson_rhs(self, xyz, normals, depth, scale=1.1):
+        """Stage: samples -> (grid (ox, oy, oz, h), b float64 [N,N,N] indexed [k,j,i], occ uint8 [N,N,N], (valid, invalid))."""
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        n = len(xyz)
+        nrm = _normals4(normals, n)
+        N = 1 << int(depth)
+        grid = np.zeros(4, np.float64)
+        b = np.zeros((N, N, N), np.float64)
+        occ = np.zeros((N, N, N), np.uint8)
+        counts = np.zeros(2, np.int64)
+        prm = PoissonParams(int(depth), float(scale), 0.5, 1, 0)
+        self._chk(self._lib.rsm_stage_poisson_rhs(self._h, _p(xyz), _p(nrm), n, C.byref(prm), _p(grid), _p(b), _p(occ), _p(counts)))
+        return grid, b, occ, (int(counts[0]), int(counts[1]))
+
+    def poisson_solve(self, b, rel_residual=POISSON_REL_RESIDUAL, max_cycles=POISSON_MAX_CYCLES):
+        """Stage: b [N,N,N] (rounded to float32) -> (chi float32 [N,N,N], residual reached, cycles, status 0 / 1, residual per cycle)."""
+        b = np.ascontiguousarray(b, np.float32)
+        N = b.shape[0]
+        depth = int(N).bit_length() - 1
+        assert b.shape == (N, N, N) and (1 << depth) == N
+        chi = np.zeros_like(b)
+        res, cyc = C.c_double(), C.c_int()
+        hist = np.zeros(max(1, int(max_cycles)), np.float64)
+        status = self._lib.rsm_stage_poisson_solve(self._h, _p(b), depth, float(rel_residual), int(max_cycles), _p(chi), C.byref(res), C.byref(cyc), _p(hist))
+        if status < 0:
+            self._chk(status)
+        return chi, float(res.value), int(cyc.value), int(status), hist[:int(cyc.value)].copy()
+
+    def iso_mesh(self, chi, iso, grid, occ=None, trim_cells=0):
+        """Stage: a caller's chi (float32 [N,N,N]), iso, grid (ox, oy, oz, h) and occ -> (vertices, faces)."""
+        chi = np.ascontiguousarray(chi, np.float32)
+        N = chi.shape[0]
+        depth = int(N).bit_length() - 1
+        grid = np.ascontiguousarray(grid, np.float64).reshape(4)
+        o8 = None if occ is None else _u8(occ)
+        nv, nf = C.c_int64(), C.c_int64()
+        self._chk(self._lib.rsm_stage_iso_mesh(self._h, _p(chi), depth, float(iso), _p(grid), None if o8 is None else _p(o8), int(trim_cells),
+                                               C.byref(nv), C.byref(nf)))
+        return self.poisson_last_mesh(int(nv.value), int(nf.value))
+
+    # ---- smoothing and clean-up of the surface: meshlab.bat's script1 / script2 after the Poisson filter (csrc/k_meshclean.hip) ----
+    @staticmethod
+    def _mesh_clean_params(smooth_steps, cotangent, boundary, min_piece, relative, duplicates, zero_area, nonmanifold):
+        prm = MeshCleanParams()
+        prm.smooth_steps, prm.cotangent, prm.boundary = int(smooth_steps), int(bool(cotangent)), int(bool(boundary))
+        prm.min_piece, prm.min_piece_relative = float(min_piece), int(bool(relative))
+        prm.flags = ((_lib.MESH_CLEAN_DUPLICATES if duplicates else 0) | (_lib.MESH_CLEAN_ZERO_AREA if zero_area else 0)
+                     | (_lib.MESH_CLEAN_NONMANIFOLD if nonmanifold else 0))
+        return prm
+
+    def _mesh_clean(self, fn, mesh_args, prm):
+        """One of the three rsm_mesh_clean* entries: (n_vertices, n_faces, stats) of the mesh it leaves with the context."""
+        nv, nf = C.c_int64(), C.c_int64()
+        st = (C.c_double * _lib.MESH_CLEAN_STATS)()
+        self._chk(fn(self._h, *mesh_args, C.byref(prm), C.byref(nv), C.byref(nf), st))
+        keys = ("n_vertices_in", "n_faces_in", "n_vertices", "n_faces", "border_vertices", "components", "components_removed", "removed_isolated",
+                "removed_duplicate", "removed_zero_area", "removed_nonmanifold", "vertices_dropped")
+        stats = {k: int(st[i]) for i, k in enumerate(keys)}
+        stats["diameter"], stats["threshold"] = float(st[12]), float(st[13])
+        return int(nv.value), int(nf.value), stats
+
+    def mesh_clean(self, vertices, faces, smooth_steps=_MC["smooth_steps"], cotangent=_MC["cotangent"], boundary=_MC["boundary"],
+                   min_piece=_MC["min_piece"], relative=_MC["relative"], duplicates=_MC["duplicates"], zero_area=_MC["zero_area"],
+                   nonmanifold=_MC["nonmanifold"]):
+        """What meshlab.bat does to the Poisson surface, on the GPU: script1's Laplacian smoothing (smooth_steps simultaneous steps, cotangent
+        weights clamped at 0, border vertices smoothed along the border), then script2's removal of isolated pieces (components whose
+        bounding-box diameter is below min_piece -- a fraction of the whole mesh's with relative=True, a length otherwise), duplicate
+        faces, zero-area faces and faces on non-manifold edges, and of the vertices no face uses.  vertices [nv,3] float32, faces [nf,3]
+        int32 -> (vertices, faces, stats dict).  The result is the context's last mesh (poisson_last_mesh[_device])."""
+        v, f = _mesh_arrays(vertices, faces)
+        prm = self._mesh_clean_params(smooth_steps, cotangent, boundary, min_piece, relative, duplicates, zero_area, nonmanifold)
+        nv, nf, stats = self._mesh_clean(self._lib.rsm_mesh_clean, (_p(v), len(v), _p(f), len(f)), prm)
+        return self.poisson_last_mesh(nv, nf) + (stats,)
+
+    def mesh_clean_device(self, vertices_ptr, n_vertices, faces_ptr, n_faces, **kw):
+        """rsm_mesh_clean_device on device buffers (addresses); keywords as mesh_clean.  Returns (n_vertices, n_faces, stats); the mesh
+        stays with the context (poisson_last_mesh[_device] copies it out)."""
+        prm = self._mesh_clean_params(**{**_MC, **kw})
+        return self._mesh_clean(self._lib.rsm_mesh_clean_device, (vertices_ptr, n_vertices, faces_ptr, n_faces), prm)
+
+    def mesh_clean_last(self, smooth_steps=_MC["smooth_steps"], cotangent=_MC["cotangent"], boundary=_MC["boundary"], min_piece=_MC["min_piece"],
+                        relative=_MC["relative"], duplicates=_MC["duplicates"], zero_area=_MC["zero_area"], nonmanifold=_MC["nonmanifold"]):
+        """mesh_clean of the context's last mesh (what poisson_mesh left) where it lies on the device; the result replaces it.
+        Returns (vertices, faces, stats)."""
+        prm = self._mesh_clean_params(smooth_steps, cotangent, boundary, min_piece, relative, duplicates, zero_area, nonmanifold)
+        nv, nf, stats = self._mesh_clean(self._lib.rsm_mesh_clean_last, (), prm)
+        return self.poisson_last_mesh(nv, nf) + (stats,)
+
+    def mesh_smooth(self, vertices, faces, steps=5, cotangent=True, boundary=True, return_border=False):
+        """Stage: the positions after `steps` smoothing steps (float32 [nv,3]; the faces are untouched); with return_border also the
+        number of border vertices."""
+        v, f = _mesh_arrays(vertices, faces)
+        out = np.zeros((max(len(v), 1), 3), np.float32)
+        nb = C.c_int64()
+        self._chk(self._lib.rsm_stage_mesh_smooth(self._h, _p(v), len(v), _p(f), len(f), int(steps), int(bool(cotangent)), int(bool(boundary)),
+                                                  _p(out), C.byref(nb)))
+        out = out[:len(v)].copy()
+        return (out, int(nb.value)) if return_border else out
+
+    def mesh_components(self, faces, n_vertices):
+        """Stage: (labels int32 [nf] = the lowest face index of each face's component, -1 for a face with a repeated index; the number of
+        components).  Faces are connected across a shared edge, not across a shared vertex."""
+        f = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+        lab = np.zeros(max(len(f), 1), np.int32)
+        nc = C.c_int64()
+        self._chk(self._lib.rsm_stage_mesh_components(self._h, _p(f), int(n_vertices), len(f), _p(lab), C.byref(nc)))
+        return lab[:len(f)].copy(), int(nc.value)
+
+    # ---- colours of the mesh from the rig's views, where run() calls TextureStitcher (csrc/k_meshcolor.hip) ----
+    @staticmethod
+    def mesh_color_views(cams):
+        """rsm_dedup_view per pair from cam[i][0..1] (Camera objects: P, image and, optionally, mask) as the colouring reads them: bound and
+        CamCenter are not used, a mask of None means all 255.  Returns (ctypes array, arrays to keep alive during the call)."""
+        return _views(cams, "mesh_color", False)
+
+    def _mesh_color(self, fn, mesh_args, cams, out_args, depth_eps, mode, min_cos):
+        """One of the three rsm_mesh_color* entries over the views of cams: the stats."""
+        views, keep = self.mesh_color_views(cams)
+        st = (C.c_double * _lib.MESH_COLOR_STATS)()
+        prm = MeshColorParams(int(mode), float(min_cos), float(depth_eps))
+        self._chk(fn(self._h, *mesh_args, views, len(cams), C.byref(prm), *out_args, st))
+        del keep
+        return {k: int(st[i]) for i, k in enumerate(("n_vertices", "coloured", "no_normal", "visible_views", "items_drawn", "items_big_box"))}
+
+    def mesh_color(self, vertices, faces, cams, depth_eps, mode=1, min_cos=0.2):
+        """Colours of a host mesh from the views of cams (m_ImageData.cam: per pair two cameras with P, image, mask), where
+        CCloudOptimization::run calls TextureStitcher.  The views are numbered every pair's view 0, then every pair's view 1.  A vertex is
+        visible in a view when it is in front of it, projects (texture_color's pixel) inside the image onto mask 255, its normal makes
+        cos > min_cos with the direction to the camera centre, and the view's depth buffer of the mesh holds no surface more than
+        depth_eps (scene units) in front of it.  mode 0: the colour of the visible view of largest cos; 1: the cos-weighted blend.
+        Returns (rgb uint8 [nv,3]: red, green, blue, (127, 127, 127) where no view sees the vertex; best_view int32 [nv], -1 there;
+        stats dict)."""
+        v, f = _mesh_arrays(vertices, faces)
+        rgb = np.zeros((max(len(v), 1), 3), np.uint8)
+        best = np.zeros(max(len(v), 1), np.int32)
+        stats = self._mesh_color(self._lib.rsm_mesh_color, (_p(v), len(v), _p(f), len(f)), cams, (_p(rgb), _p(best)), depth_eps, mode, min_cos)
+        return rgb[:len(v)].copy(), best[:len(v)].copy(), stats
+
+    def mesh_color_device(self, vertices_ptr, n_vertices, faces_ptr, n_faces, cams, rgb_ptr, best_view_ptr, depth_eps, mode=1, min_cos=0.2):
+        """rsm_mesh_color_device on device buffers (addresses; best_view_ptr may be 0); the views' images stay on the host.  Returns stats."""
+        return self._mesh_color(self._lib.rsm_mesh_color_device, (vertices_ptr, n_vertices, faces_ptr, n_faces), cams, (rgb_ptr, best_view_ptr), depth_eps, mode, min_cos)
+
+    def mesh_color_last(self, cams, depth_eps, mode=1, min_cos=0.2):
+        """mesh_color of the context's last mesh (what poisson_mesh / mesh_clean left) where it lies on the device; the mesh is untouched.
+        Returns (rgb, best_view, stats)."""
+        stats = self._mesh_color(self._lib.rsm_mesh_color_last, (), cams, (), depth_eps, mode, min_cos)
+        nv = stats["n_vertices"]
+        rgb = np.zeros((max(nv, 1), 3), np.uint8)
+        best = np.zeros(max(nv, 1), np.int32)
+        self._chk(self._lib.rsm_mesh_last_colors(self._h, _p(rgb), _p(best)))
+        return rgb[:nv].copy(), best[:nv].copy(), stats
+
+    def texture_color(self, xyz, P, image):
+        """Stage: texture_color (CCloudOptimization.cpp:400-421) of xyz [n,3] float32 against one view (P 3x4, image BGR uint8 [H,W,3]):
+        rgb uint8 [n,3], (127, 127, 127) outside the image."""
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        P = np.ascontiguousarray(P, np.float64).reshape(12)
+        img = _u8(image)
+        rgb = np.zeros((max(len(xyz), 1), 3), np.uint8)
+        self._chk(self._lib.rsm_texture_color(self._h, _p(xyz), len(xyz), _p(P), _p(img), int(img.shape[1]), int(img.shape[0]), _p(rgb)))
+        return rgb[:len(xyz)].copy()
+
+    def mesh_depth(self, vertices, faces, P, width, height):
+        """Stage: one view's depth buffer of the mesh, uint32 [height,width]: the largest float32 bit pattern of the inverse depth drawn at
+        each pixel centre (0: nothing drawn)."""
+        v, f = _mesh_arrays(vertices, faces)
+        P = np.ascontiguousarray(P, np.float64).reshape(12)
+        w = np.zeros((max(int(height), 1), max(int(width), 1)), np.uint32)
+        self._chk(self._lib.rsm_stage_mesh_depth(self._h, _p(v), len(v), _p(f), len(f), _p(P), int(width), int(height), _p(w)))
+        return w

@@ -21,6 +21,8 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from . import _lib
+
 META_PAIRS = 64  # pairs per rank and call that fit the fixed-size metadata message
 REC = 16         # bytes per point record (rsm_point16)
 
@@ -123,33 +125,36 @@ class Comm:
     The 128-byte id made by rank 0 (`Comm.unique_id()`) reaches the other ranks by any side channel."""
 
     def __init__(self, unique_id: bytes, rank: int, world: int, device: int):
-        from . import _lib
         self._lib = _lib.load()
         h = C.c_void_p()
-        st = self._lib.rsm_comm_create(C.byref(h), C.c_char_p(bytes(unique_id)), rank, world, device)
+        st = self._lib.rsm_comm_create(C.byref(h), bytes(unique_id), rank, world, device)
         if st != 0:
             raise _lib.RsmError(st, "rsm_comm_create (is librccl loadable?)")
         self._h, self.rank, self.world = h, rank, world
 
     @staticmethod
     def unique_id() -> bytes:
-        from . import _lib
         buf = C.create_string_buffer(128)
         st = _lib.load().rsm_comm_unique_id(buf)
         if st != 0:
             raise _lib.RsmError(st, "rsm_comm_unique_id (is librccl loadable?)")
         return buf.raw
 
-    def counts(self, local, n_pairs_total):
-        """Point count of every pair, on every rank (rsm_gather_counts: one all-reduce)."""
-        from . import _lib
-        n = len(local)
-        ids = (C.c_int * max(n, 1))(*[int(p) for p, _ in local])
-        cnts = (C.c_int64 * max(n, 1))(*[int(r.shape[0]) for _, r in local])
-        out = (C.c_int64 * max(n_pairs_total, 1))()
-        st = self._lib.rsm_gather_counts(self._h, n, ids, cnts, n_pairs_total, out)
+    def _chk(self, st):
         if st != 0:
             raise _lib.RsmError(st, (self._lib.rsm_comm_last_error(self._h) or b"").decode())
+
+    @staticmethod
+    def _ids_counts(local):
+        """(n, pair ids as int array, point counts as int64 array) of local = [(pair_id, records)]."""
+        n = len(local)
+        return n, (C.c_int * max(n, 1))(*[int(p) for p, _ in local]), (C.c_int64 * max(n, 1))(*[int(r.shape[0]) for _, r in local])
+
+    def counts(self, local, n_pairs_total):
+        """Point count of every pair, on every rank (rsm_gather_counts: one all-reduce)."""
+        n, ids, cnts = self._ids_counts(local)
+        out = (C.c_int64 * max(n_pairs_total, 1))()
+        self._chk(self._lib.rsm_gather_counts(self._h, n, ids, cnts, n_pairs_total, out))
         return list(out[:n_pairs_total])
 
     def gather(self, local, n_pairs_total, root=0, capacity=None):
@@ -158,24 +163,19 @@ class Comm:
         peers inside rsm_gather_clouds' own all-reduce); None sizes it exactly from the counts.  The counts-only
         exchange is posted by EVERY rank on EVERY call, whatever its `capacity` argument: ranks that disagreed about
         it would otherwise post different collective sequences and hang."""
-        from . import _lib
-        n = len(local)
         total = sum(self.counts(local, n_pairs_total))
         if capacity is None:
             capacity = total
-        ids = (C.c_int * max(n, 1))(*[int(p) for p, _ in local])
+        n, ids, cnts = self._ids_counts(local)
         ptrs = (C.c_void_p * max(n, 1))(*[int(r.data_ptr()) if r.shape[0] else None for _, r in local])
-        cnts = (C.c_int64 * max(n, 1))(*[int(r.shape[0]) for _, r in local])
         offs = (C.c_int64 * (n_pairs_total + 1))()
         out = None
         cap = 0
         if self.rank == root:
             cap = int(capacity)
             out = torch.empty((max(cap, 1), REC), dtype=torch.uint8, device=local[0][1].device if local else "cuda")
-        st = self._lib.rsm_gather_clouds(self._h, root, n, ids, ptrs, cnts, n_pairs_total,
-                                         C.c_void_p(out.data_ptr()) if out is not None else None, C.c_int64(cap), offs)
-        if st != 0:
-            raise _lib.RsmError(st, (self._lib.rsm_comm_last_error(self._h) or b"").decode())
+        st = self._lib.rsm_gather_clouds(self._h, root, n, ids, ptrs, cnts, n_pairs_total, out.data_ptr() if out is not None else None, cap, offs)
+        self._chk(st)
         if self.rank != root:
             return None
         return [(p, out[offs[p]:offs[p + 1]]) for p in range(n_pairs_total)]

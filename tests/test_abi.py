@@ -42,27 +42,95 @@ def test_struct_layouts_match_the_header():
     assert C.sizeof(_lib.PairOut) == 2 * 8 + 2 * 24 + 8 + 8 + 8 + 8 + 8 + 8
 
 
+MIRRORS = {"rsm_boundary": "Boundary", "rsm_pair_in": "PairIn", "rsm_pair_out": "PairOut", "rsm_filter_params": "FilterParams", "rsm_mls_params": "MlsParams",
+           "rsm_poisson_params": "PoissonParams", "rsm_mesh_clean_params": "MeshCleanParams", "rsm_mesh_color_params": "MeshColorParams",
+           "rsm_dedup_view": "DedupView", "rsm_rectify_in": "RectifyIn", "rsm_rectify_out": "RectifyOut"}
+
+
 def test_struct_layouts_as_the_c_compiler_sees_them(tmp_path):
-    """sizeof / offsetof of the header's structs from gcc itself against the ctypes mirror (rsm_pair_out grew a trailing
-    `points16` in round 5: both sides must agree on every member's offset)."""
+    """sizeof / offsetof of every struct the binding mirrors, from gcc itself, against the ctypes classes; the member names come from each
+    class's _fields_, so a member the header does not have fails to compile."""
     from reconstruction_amd import _lib
     src = tmp_path / "layout.c"
-    fields = {"rsm_pair_in": ["image", "mask", "width", "height", "pyr_levels", "radius", "ws", "offset", "origin_width", "Q", "R_final", "T_final", "verbose"],
-              "rsm_pair_out": ["disparity", "margin", "n_points", "max_points", "xyz", "bgr", "v_top", "points16"],
-              "rsm_filter_params": ["sor_mean_k", "sor_std_mul", "normal_radius", "cam_center"]}
-    body = "".join('printf("%s %%zu\\n", sizeof(%s));\n' % (t, t) + "".join('printf("%s.%s %%zu\\n", offsetof(%s, %s));\n' % (t, f, t, f) for f in fs)
-                   for t, fs in fields.items())
+    mirror = {t: getattr(_lib, c) for t, c in MIRRORS.items()}
+    body = "".join('printf("%s %%zu\\n", sizeof(%s));\n' % (t, t) + "".join('printf("%s.%s %%zu\\n", offsetof(%s, %s));\n' % (t, f, t, f) for f, _ in c._fields_)
+                   for t, c in mirror.items())
     src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "rsm.h"\nint main(void) {\n%sprintf("rsm_point16 %%zu\\n", sizeof(rsm_point16));\nreturn 0; }\n' % body)
     exe = tmp_path / "layout"
     r = subprocess.run(["gcc", "-std=c99", "-I" + os.path.dirname(HEADER), str(src), "-o", str(exe)], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     got = dict(l.split() for l in subprocess.run([str(exe)], capture_output=True, text=True).stdout.splitlines())
-    mirror = {"rsm_pair_in": _lib.PairIn, "rsm_pair_out": _lib.PairOut, "rsm_filter_params": _lib.FilterParams}
-    for t, fs in fields.items():
-        assert int(got[t]) == C.sizeof(mirror[t]), t
-        for f in fs:
-            assert int(got["%s.%s" % (t, f)]) == getattr(mirror[t], f).offset, (t, f)
+    for t, c in mirror.items():
+        assert int(got[t]) == C.sizeof(c), t
+        for f, _ in c._fields_:
+            assert int(got["%s.%s" % (t, f)]) == getattr(c, f).offset, (t, f)
     assert int(got["rsm_point16"]) == 16
+
+
+# the header's scalar vocabulary -> (bytes, signed, floating); a type that is not listed fails the prototype test
+SCALARS = {"int": (4, True, False), "int64_t": (8, True, False), "long long": (8, True, False), "uint32_t": (4, False, False),
+           "size_t": (8, False, False), "double": (8, True, True)}
+
+
+def header_prototypes():
+    """{name: (return kind, [parameter kind])} of every function include/rsm.h declares; a kind is "void", "ptr" or a key of SCALARS."""
+    txt = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    txt = re.sub(r"^\s*#.*$", "", txt, flags=re.M)
+    txt = re.sub(r"typedef\s+(struct|enum)\s+\w+\s*\{.*?\}\s*\w+\s*;", "", txt, flags=re.S)
+
+    def kind(decl, named):
+        decl = decl.strip()
+        if "*" in decl or "[" in decl:
+            return "ptr"
+        words = [w for w in decl.split() if w != "const"]
+        return " ".join(words[:-1] if named else words)
+
+    protos = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][\w\s]*?[\s*]+)(rsm_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", txt):
+        params = [] if params.strip() == "void" else [kind(q, True) for q in params.split(",")]
+        protos[name] = (kind(ret, False), params)
+    return protos
+
+
+def shape(t):
+    """A ctypes type of the binding's table as "void", "ptr" or a value of SCALARS."""
+    if t is None:
+        return "void"
+    if t in (C.c_void_p, C.c_char_p) or issubclass(t, C._Pointer):
+        return "ptr"
+    return (C.sizeof(t), t(-1).value < 0, t is C.c_double)
+
+
+def test_every_prototype_of_the_binding_matches_the_header():
+    """Return kind, parameter count and, per parameter, pointer or scalar -- and a scalar's width, signedness and integer / double --
+    of every row of _lib.PROTOTYPES against include/rsm.h."""
+    from reconstruction_amd import _lib
+    protos = header_prototypes()
+    assert sorted(protos) == declared() == sorted(_lib.PROTOTYPES) and len(protos) >= 94
+    want = dict(SCALARS, ptr="ptr", void="void")
+    for name, (ret, params) in protos.items():
+        assert ret in want and set(params) <= set(want) - {"void"}, (name, ret, params)   # a type the header grew and this test does not know
+        restype, argtypes = _lib.PROTOTYPES[name]
+        assert shape(restype) == want[ret], (name, "returns", ret)
+        assert len(argtypes) == len(params), (name, len(params))
+        for i, (t, k) in enumerate(zip(argtypes, params)):
+            assert shape(t) == want[k], (name, i, k, t)
+
+
+def test_no_function_is_left_without_a_prototype():
+    from reconstruction_amd import _lib
+    lib = _lib.load()
+    assert _lib.EXPORTS == list(_lib.PROTOTYPES)
+    for name in _lib.EXPORTS:
+        fn = getattr(lib, name)
+        assert fn.argtypes is not None and list(fn.argtypes) == list(_lib.PROTOTYPES[name][1]), name
+        assert fn.restype == _lib.PROTOTYPES[name][0], name
+
+
+def test_abi_constant_is_the_headers():
+    from reconstruction_amd import _lib
+    m = re.search(r"^#define\s+RSM_ABI_VERSION\s+(\d+)\s*$", open(HEADER).read(), flags=re.M)
+    assert m and _lib.RSM_ABI_VERSION == int(m.group(1)) == _lib.load().rsm_abi_version()
 
 
 def test_no_gpu_means_error_not_fallback():
