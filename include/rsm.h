@@ -577,8 +577,8 @@ int rsm_stage_mesh_components(rsm_ctx *ctx, const int32_t *faces, int64_t nv, in
 
 /* ---- colours of the final mesh from the rig's views (where CCloudOptimization::run hands tmp\bigmesh.ply and scans.txt to TextureStitcher,
  * .cpp:394-397; the scans are the per-view meshes filter() colours through texture_color, .cpp:127-143, :400-421) ------------------------
- * Not a bit-parity port of TextureStitcher (no source in the reference tree): the rules as DESIGN.md 9 (f9) defines them.  Its seam removal
- * by gradient stitching is not done.  n_pairs records of rsm_dedup_view give V = 2 n_pairs views, numbered in scans.txt's
+ * Not a bit-parity port of TextureStitcher (no source in the reference tree): the rules as DESIGN.md 9 (f9) defines them.  Its seam
+ * levelling is rsm_mesh_stitch below.  n_pairs records of rsm_dedup_view give V = 2 n_pairs views, numbered in scans.txt's
  * order: every pair's view 0, then every pair's view 1 (v = k * n_pairs + i).  bound0 and cam_center are ignored -- the centre is
  * -M^-1 p4 of P in fp64 -- and a mask may be NULL: all 255.
  * A vertex is visible in a view when it lies in front of it (q2 > 0), its texture_color pixel is inside the image with mask 255, its
@@ -618,6 +618,50 @@ int rsm_stage_mesh_depth(rsm_ctx *ctx, const float *xyz, int64_t nv, const int32
 /* binary little-endian PLY: vertex float x, y, z, uchar red, green, blue; face list uchar int vertex_indices (MyPlyIo's property order,
  * my_ply_interface.cpp:35-50).  Host only. */
 int rsm_write_ply_mesh_color(const char *path, const float *xyz, int64_t n_vertices, const int32_t *faces, int64_t n_faces, const uint8_t *rgb);
+
+/* ---- the views' exposure seams levelled in the mesh's colours (the other half of TextureStitcher's job) ----------------
+ * Starts from the best-view colouring c of rsm_mesh_color (mode 0; the colour params' mode must be 0) and solves, per channel and over the
+ * coloured vertices, the screened gradient-domain system  sum_j (x_i - x_j) + lambda x_i = sum_j g_ij + lambda c_i  over each vertex's
+ * incidences (its corner list: an interior edge counts twice, a border edge once; only coloured neighbours).  g_ij = c_i - c_j where both
+ * ends take the same view; across a seam (views a = best_i, b = best_j) it is 0 with seam_gradient = 0, else the mean of the views' own
+ * differences that exist: c_i - col_a(j) if view a sees j, col_b(i) - c_j if view b sees i (col_v = texture_color's pixel in view v, "sees"
+ * = the colouring's visibility test).  Solver: Jacobi-preconditioned Chebyshev iteration with a fixed number of steps -- `iterations`, or with
+ * iterations = 0 the least k with T_k(sigma) >= 1 / reduction (T_k the Chebyshev polynomial by its recurrence, sigma = (2 + lmin) / (2 - lmin),
+ * lmin = lambda / (dmax + lambda), dmax the largest incidence count), after which the error in the M-norm is at most `reduction` times the
+ * start's.  Bytes = clamp(floor(x + 0.5), 0, 255); uncoloured vertices stay (127, 127, 127).  A mesh without a seam comes back bit for bit.
+ * The visibility masks are 64 bits: V = 2 n_pairs <= 64. */
+typedef struct rsm_mesh_stitch_params {
+    double lambda;      /* finite, > 0: the pull towards the colouring; a view's offset decays over about 1 / sqrt(lambda) edges (0.01) */
+    int iterations;     /* 0 .. 1000000; 0 = from reduction */
+    double reduction;   /* in (0, 1), used when iterations = 0 (1e-4) */
+    int seam_gradient;  /* 0 / 1 (1) */
+} rsm_mesh_stitch_params;
+#define RSM_MESH_STITCH_MAX_ITERATIONS 1000000
+/* stats: [0] vertices, [1] vertices coloured, [2] incidences between coloured vertices, [3] of them across a seam, [4] seam incidences with
+ * two terms, [5] with one, [6] with none, [7] dmax, [8] steps run, [9] the relative residual ||b - A x|| / ||b - A c|| after them (reported,
+ * not a stopping test; 0 when the start solves the system), [10] the largest |x - c|, [11] values clamped */
+#define RSM_MESH_STITCH_STATS 12
+/* The arguments of rsm_mesh_color[_device / _last] with the stitch params and stats after the colour params.  An empty mesh or no coloured
+ * vertex: the colouring's bytes, RSM_OK.  RSM_E_INVALID (rsm_last_error names the cause): everything rsm_mesh_color refuses, mode != 0,
+ * V = 2 n_pairs > 64, lambda not finite or not > 0, iterations outside 0 .. 1000000, reduction outside (0, 1) when it is used (or one
+ * that needs more than 1000000 steps), seam_gradient not 0 or 1.  The _last form leaves the colours with the context as
+ * rsm_mesh_color_last does: rsm_mesh_last_colors copies them out. */
+int rsm_mesh_stitch(rsm_ctx *ctx, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, const rsm_dedup_view *views, int n_pairs,
+                    const rsm_mesh_color_params *p, const rsm_mesh_stitch_params *sp, uint8_t *rgb, int32_t *best_view, double *stats);
+int rsm_mesh_stitch_device(rsm_ctx *ctx, const float *d_xyz, int64_t nv, const int32_t *d_faces, int64_t nf, const rsm_dedup_view *views, int n_pairs,
+                           const rsm_mesh_color_params *p, const rsm_mesh_stitch_params *sp, uint8_t *d_rgb, int32_t *d_best_view, double *stats);
+int rsm_mesh_stitch_last(rsm_ctx *ctx, const rsm_dedup_view *views, int n_pairs, const rsm_mesh_color_params *p, const rsm_mesh_stitch_params *sp,
+                         double *stats);
+/* stage entry points (host buffers) for the tests.  visibility: vis[nv], bit v = view v sees the vertex.  rhs: a caller's colouring (rgb
+ * nv*3 bytes, best_view in -1 .. V - 1, vis) -> G nv*3 doubles (0 for an uncoloured vertex), deg nv int32, counts = stats [2] .. [6].
+ * solve: `iterations` (0 .. 1000000, taken as given) steps from a caller's best_view (its sign alone counts), rgb and G -> x nv*3 doubles
+ * (c for an uncoloured vertex) and the relative residual. */
+int rsm_stage_mesh_visibility(rsm_ctx *ctx, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, const rsm_dedup_view *views, int n_pairs,
+                              const rsm_mesh_color_params *p, uint64_t *vis);
+int rsm_stage_mesh_stitch_rhs(rsm_ctx *ctx, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, const rsm_dedup_view *views, int n_pairs,
+                              const uint8_t *rgb, const int32_t *best_view, const uint64_t *vis, int seam_gradient, double *G, int32_t *deg, int64_t counts[5]);
+int rsm_stage_mesh_stitch_solve(rsm_ctx *ctx, const int32_t *faces, int64_t nv, int64_t nf, const int32_t *best_view, const uint8_t *rgb, const double *G,
+                                double lambda, int iterations, double *x, double *rel_residual);
 
 /* ---- kernel microbenchmark (MDE/s: pixel x candidate NCC evaluations) -------------------- */
 /* Runs the NCC interval-argmax kernel `iters` times on a resident level-sized problem with

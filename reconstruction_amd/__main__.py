@@ -1,7 +1,8 @@
 """python -m reconstruction_amd <config.yml> [--device N] [--out cloud.ply] [--filter] [--mls [--isdelete] [--mls-out bigcloud.ply]]
                               [--mesh [--mesh-depth 9] [--mesh-trim 4] [--mesh-out bigmesh.ply]
                                [--mesh-clean [--mesh-smooth 5] [--mesh-min-piece 10%]]
-                               [--mesh-color [--mesh-color-mode blend] [--mesh-color-min-cos 0.2] [--mesh-color-eps LENGTH]]]
+                               [--mesh-color [--mesh-color-mode blend] [--mesh-color-min-cos 0.2] [--mesh-color-eps LENGTH]]
+                               [--mesh-stitch [--mesh-stitch-lambda 0.01] [--mesh-stitch-iterations 0]]]
 
 The command-line shape of the reference's main() (reconstruction/main.cpp:5-23) for the part this package covers:
 CReconstrction::Init (configuration + calibration, CReconstruction.cpp:5-19) -> CStereoMatching::MatchAllLayer
@@ -17,7 +18,9 @@ With --mesh-clean (implies --mesh) bigmesh.ply is that surface after meshlab.bat
 With --mesh-color (implies --mesh) the mesh's vertices are coloured from every camera's rectified image, on the GPU, where
 CCloudOptimization::run calls TextureStitcher (visibility by a depth buffer per view, the best view or a cos-weighted blend; DESIGN.md 9
 f9): the coloured mesh goes to the configuration's outfilename, where TextureStitcher's --out goes, and the cloud PLY to <name>_cloud.ply.
-The rest of CCloudOptimization::run (MeshLab's hole closing, TextureStitcher's seam removal: external executables; main.cpp:19) is
+With --mesh-stitch (implies --mesh-color) the vertices take their best view's colour and the views' exposure seams are levelled on the
+GPU by a screened gradient-domain solve on the mesh graph, TextureStitcher's seam removal; the same PLY at outfilename.
+The rest of CCloudOptimization::run (MeshLab's hole closing: an external executable; main.cpp:19) is
 outside this package: feed bigcloud.ply or bigmesh.ply to it.
 Needs an MI355X; there is no CPU path.
 """
@@ -87,7 +90,16 @@ def main(argv=None) -> int:
                     help="with --mesh-color: a view sees a vertex only at a cosine above this between its normal and the direction to the camera")
     ap.add_argument("--mesh-color-eps", type=float, default=None,
                     help="with --mesh-color: the depth test's slack in scene units (default: twice the Poisson grid step)")
+    ap.add_argument("--mesh-stitch", action="store_true",
+                    help="implies --mesh-color: level the views' exposure seams in the colours on the GPU (a screened gradient-domain solve on the "
+                         "mesh graph).  It always colours by best view: --mesh-color-mode is not consulted.  The same PLY at outfilename")
+    ap.add_argument("--mesh-stitch-lambda", type=float, default=0.01,
+                    help="with --mesh-stitch: the pull towards the views' colours; a view's offset decays over about 1/sqrt(lambda) edges")
+    ap.add_argument("--mesh-stitch-iterations", type=int, default=0,
+                    help="with --mesh-stitch: Chebyshev steps (0: as many as reduce the error to 1e-4 of the start's)")
     args = ap.parse_args(argv)
+    if args.mesh_stitch:
+        args.mesh_color = True
     if args.mesh_color:
         args.mesh = True
     if args.mesh_clean:
@@ -188,12 +200,21 @@ def main(argv=None) -> int:
         print("%d vertices, %d faces -> %s" % (len(mv), len(mf), mesh_out))
         if args.mesh_color:
             try:
-                rgb, _, kst = sink.color_mesh(mode=1 if args.mesh_color_mode == "blend" else 0, min_cos=args.mesh_color_min_cos,
-                                              depth_eps=args.mesh_color_eps)
-            except (RsmError, ValueError) as e:                    # pre-rectified input (no P), --mesh-color-min-cos outside [-1, 1)
+                if args.mesh_stitch:
+                    rgb, _, sst = sink.stitch_mesh(min_cos=args.mesh_color_min_cos, depth_eps=args.mesh_color_eps, lam=args.mesh_stitch_lambda,
+                                                   iterations=args.mesh_stitch_iterations)
+                else:
+                    rgb, _, kst = sink.color_mesh(mode=1 if args.mesh_color_mode == "blend" else 0, min_cos=args.mesh_color_min_cos,
+                                                  depth_eps=args.mesh_color_eps)
+            except (RsmError, ValueError) as e:                    # pre-rectified input (no P), --mesh-color-min-cos outside [-1, 1), a lambda <= 0
                 print(e)
                 return 1
             write_ply_mesh(color_out, mv, mf, rgb)
+            if args.mesh_stitch:
+                print("Mesh stitch: %d of %d vertices coloured from %d views, %d of %d incidences across a seam, %d steps (residual %.2e), largest "
+                      "change %.2f levels -> %s" % (sst["coloured"], sst["n_vertices"], 2 * len(data.cam), sst["seam_incidences"], sst["incidences"],
+                                                    sst["steps"], sst["rel_residual"], sst["max_change"], color_out))
+                return 0
             print("Mesh colour: %d of %d vertices coloured from %d views (%d without a normal) -> %s"
                   % (kst["coloured"], kst["n_vertices"], 2 * len(data.cam), kst["no_normal"], color_out))
     return 0

@@ -92,6 +92,14 @@ class MeshColorParams(C.Structure):
 MESH_COLOR_STATS = 6
 
 
+class MeshStitchParams(C.Structure):
+    """rsm_mesh_stitch_params (include/rsm.h); `lambda` is set by position or setattr."""
+    _fields_ = [("lambda", C.c_double), ("iterations", C.c_int), ("reduction", C.c_double), ("seam_gradient", C.c_int)]
+
+
+MESH_STITCH_STATS = 12
+
+
 class DedupView(C.Structure):
     """rsm_dedup_view (include/rsm.h): one pair of the rig for the duplicate deletion (host pointers)."""
     _fields_ = [("P", (C.c_double * 12) * 2), ("cam_center", C.c_float * 3), ("bound0", Boundary), ("width", C.c_int),
@@ -116,7 +124,7 @@ class RectifyOut(C.Structure):
 _I, _L, _U, _LL, _Z, _D, _V, _S = C.c_int, C.c_int64, C.c_uint32, C.c_longlong, C.c_size_t, C.c_double, C.c_void_p, C.c_char_p
 _pI, _pL, _pD = C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_double)
 _PIN, _POUT, _BND, _RIN, _ROUT, _FLT = (C.POINTER(t) for t in (PairIn, PairOut, Boundary, RectifyIn, RectifyOut, FilterParams))
-_MLS, _VIEW, _PSN, _CLN, _COL = (C.POINTER(t) for t in (MlsParams, DedupView, PoissonParams, MeshCleanParams, MeshColorParams))
+_MLS, _VIEW, _PSN, _CLN, _COL, _STI = (C.POINTER(t) for t in (MlsParams, DedupView, PoissonParams, MeshCleanParams, MeshColorParams, MeshStitchParams))
 PROTOTYPES = {
     "rsm_create": (_I, [_V, _I]),
     "rsm_destroy": (None, [_V]),
@@ -211,6 +219,12 @@ PROTOTYPES = {
     "rsm_texture_color": (_I, [_V, _V, _L, _V, _V, _I, _I, _V]),
     "rsm_stage_mesh_depth": (_I, [_V, _V, _L, _V, _L, _V, _I, _I, _V]),
     "rsm_write_ply_mesh_color": (_I, [_S, _V, _L, _V, _L, _V]),
+    "rsm_mesh_stitch": (_I, [_V, _V, _L, _V, _L, _VIEW, _I, _COL, _STI, _V, _V, _V]),
+    "rsm_mesh_stitch_device": (_I, [_V, _V, _L, _V, _L, _VIEW, _I, _COL, _STI, _V, _V, _V]),
+    "rsm_mesh_stitch_last": (_I, [_V, _VIEW, _I, _COL, _STI, _V]),
+    "rsm_stage_mesh_visibility": (_I, [_V, _V, _L, _V, _L, _VIEW, _I, _COL, _V]),
+    "rsm_stage_mesh_stitch_rhs": (_I, [_V, _V, _L, _V, _L, _VIEW, _I, _V, _V, _V, _I, _V, _V, _V]),
+    "rsm_stage_mesh_stitch_solve": (_I, [_V, _V, _L, _L, _V, _V, _V, _D, _I, _V, _pD]),
     "rsm_bench_ncc": (_I, [_V, _I, _I, _I, _I, _I, _V]),
 }
 EXPORTS = list(PROTOTYPES)   # every symbol include/rsm.h declares

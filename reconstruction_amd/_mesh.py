@@ -1,11 +1,12 @@
-"""The surface stages (csrc/rsm_mesh.hip): dense-grid Poisson surface and trim, smoothing and clean-up, colours from the rig's views."""
+"""The surface stages (csrc/rsm_mesh.hip): dense-grid Poisson surface and trim, smoothing and clean-up, colours from the rig's views and the
+levelling of their seams."""
 import ctypes as C
 
 import numpy as np
 
 from . import _lib
 from ._context import ContextBase, _normals4, _p, _u8, _views
-from ._lib import MeshCleanParams, MeshColorParams, PoissonParams
+from ._lib import MeshCleanParams, MeshColorParams, MeshStitchParams, PoissonParams
 
 # the solve's default stopping residual: one decade above the 4.2e-6 the float32 solver reaches at depth 9
 POISSON_REL_RESIDUAL = 4e-5
@@ -210,6 +211,93 @@ class MeshPart(ContextBase):
         best = np.zeros(max(nv, 1), np.int32)
         self._chk(self._lib.rsm_mesh_last_colors(self._h, _p(rgb), _p(best)))
         return rgb[:nv].copy(), best[:nv].copy(), stats
+
+    # ---- the views' exposure seams levelled in those colours (csrc/k_meshstitch.hip) ----
+    _STITCH_KEYS = ("n_vertices", "coloured", "incidences", "seam_incidences", "seam_two_terms", "seam_one_term", "seam_no_term", "dmax", "steps")
+
+    def _mesh_stitch(self, fn, mesh_args, cams, out_args, depth_eps, min_cos, lam, iterations, reduction, seam_gradient):
+        """One of the three rsm_mesh_stitch* entries over the views of cams: the stats."""
+        views, keep = self.mesh_color_views(cams)
+        st = (C.c_double * _lib.MESH_STITCH_STATS)()
+        prm = MeshColorParams(0, float(min_cos), float(depth_eps))
+        sp = MeshStitchParams(float(lam), int(iterations), float(reduction), int(seam_gradient))
+        self._chk(fn(self._h, *mesh_args, views, len(cams), C.byref(prm), C.byref(sp), *out_args, st))
+        del keep
+        stats = {k: int(st[i]) for i, k in enumerate(self._STITCH_KEYS)}
+        stats.update(rel_residual=float(st[9]), max_change=float(st[10]), clamped=int(st[11]))
+        return stats
+
+    def mesh_stitch(self, vertices, faces, cams, depth_eps, min_cos=0.2, lam=0.01, iterations=0, reduction=1e-4, seam_gradient=True):
+        """mesh_color's best-view colours (mode 0) of a host mesh with the views' exposure seams levelled, the other half of
+        TextureStitcher's job: per channel the screened gradient-domain system over the coloured vertices -- inside a
+        view the colours' own differences are kept, across a seam the views' own differences where they see both ends
+        (seam_gradient=False: 0), and lam pulls towards the colouring, so that a view's offset decays over about 1 / sqrt(lam) edges.
+        iterations Chebyshev steps, or with 0 as many as bring the error down to `reduction` of the start's.  Returns (rgb uint8 [nv,3],
+        best_view int32 [nv], stats dict); uncoloured vertices stay (127, 127, 127)."""
+        v, f = _mesh_arrays(vertices, faces)
+        rgb = np.zeros((max(len(v), 1), 3), np.uint8)
+        best = np.zeros(max(len(v), 1), np.int32)
+        stats = self._mesh_stitch(self._lib.rsm_mesh_stitch, (_p(v), len(v), _p(f), len(f)), cams, (_p(rgb), _p(best)), depth_eps, min_cos, lam, iterations,
+                                  reduction, seam_gradient)
+        return rgb[:len(v)].copy(), best[:len(v)].copy(), stats
+
+    def mesh_stitch_device(self, vertices_ptr, n_vertices, faces_ptr, n_faces, cams, rgb_ptr, best_view_ptr, depth_eps, min_cos=0.2, lam=0.01, iterations=0,
+                           reduction=1e-4, seam_gradient=True):
+        """rsm_mesh_stitch_device on device buffers (addresses; best_view_ptr may be 0); the views' images stay on the host.  Returns stats."""
+        return self._mesh_stitch(self._lib.rsm_mesh_stitch_device, (vertices_ptr, n_vertices, faces_ptr, n_faces), cams, (rgb_ptr, best_view_ptr), depth_eps,
+                                 min_cos, lam, iterations, reduction, seam_gradient)
+
+    def mesh_stitch_last(self, cams, depth_eps, min_cos=0.2, lam=0.01, iterations=0, reduction=1e-4, seam_gradient=True):
+        """mesh_stitch of the context's last mesh where it lies on the device; the mesh is untouched and the colours stay with the context
+        as mesh_color_last's do.  Returns (rgb, best_view, stats)."""
+        stats = self._mesh_stitch(self._lib.rsm_mesh_stitch_last, (), cams, (), depth_eps, min_cos, lam, iterations, reduction, seam_gradient)
+        nv = stats["n_vertices"]
+        rgb = np.zeros((max(nv, 1), 3), np.uint8)
+        best = np.zeros(max(nv, 1), np.int32)
+        self._chk(self._lib.rsm_mesh_last_colors(self._h, _p(rgb), _p(best)))
+        return rgb[:nv].copy(), best[:nv].copy(), stats
+
+    def mesh_visibility(self, vertices, faces, cams, depth_eps, min_cos=0.2):
+        """Stage: per vertex the mask of the views that see it (uint64 [nv], bit v = view v), by the colouring's visibility test."""
+        v, f = _mesh_arrays(vertices, faces)
+        views, keep = self.mesh_color_views(cams)
+        vis = np.zeros(max(len(v), 1), np.uint64)
+        prm = MeshColorParams(0, float(min_cos), float(depth_eps))
+        self._chk(self._lib.rsm_stage_mesh_visibility(self._h, _p(v), len(v), _p(f), len(f), views, len(cams), C.byref(prm), _p(vis)))
+        del keep
+        return vis[:len(v)].copy()
+
+    def mesh_stitch_rhs(self, vertices, faces, cams, rgb, best_view, vis, seam_gradient=True):
+        """Stage: a caller's colouring (rgb uint8 [nv,3], best_view int32 [nv], vis uint64 [nv]) -> (G float64 [nv,3], deg int32 [nv],
+        counts dict: incidences, seam_incidences, seam_two_terms, seam_one_term, seam_no_term)."""
+        v, f = _mesh_arrays(vertices, faces)
+        n = len(v)
+        views, keep = self.mesh_color_views(cams)
+        c = np.ascontiguousarray(rgb, np.uint8).reshape(-1, 3)
+        b = np.ascontiguousarray(best_view, np.int32).reshape(-1)
+        m = np.ascontiguousarray(vis, np.uint64).reshape(-1)
+        assert len(c) == n and len(b) == n and len(m) == n
+        G = np.zeros((max(n, 1), 3), np.float64)
+        deg = np.zeros(max(n, 1), np.int32)
+        counts = np.zeros(5, np.int64)
+        self._chk(self._lib.rsm_stage_mesh_stitch_rhs(self._h, _p(v), n, _p(f), len(f), views, len(cams), _p(c), _p(b), _p(m), int(bool(seam_gradient)),
+                                                      _p(G), _p(deg), _p(counts)))
+        del keep
+        return G[:n].copy(), deg[:n].copy(), {k: int(counts[i]) for i, k in enumerate(self._STITCH_KEYS[2:7])}
+
+    def mesh_stitch_solve(self, faces, best_view, rgb, G, lam, iterations):
+        """Stage: `iterations` Chebyshev steps from a caller's best_view (its sign alone counts), rgb and G -> (x float64 [nv,3], the
+        relative residual after them)."""
+        f = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+        b = np.ascontiguousarray(best_view, np.int32).reshape(-1)
+        n = len(b)
+        c = np.ascontiguousarray(rgb, np.uint8).reshape(-1, 3)
+        g = np.ascontiguousarray(G, np.float64).reshape(-1, 3)
+        assert len(c) == n and len(g) == n
+        x = np.zeros((max(n, 1), 3), np.float64)
+        rel = C.c_double()
+        self._chk(self._lib.rsm_stage_mesh_stitch_solve(self._h, _p(f), n, len(f), _p(b), _p(c), _p(g), float(lam), int(iterations), _p(x), C.byref(rel)))
+        return x[:n].copy(), float(rel.value)
 
     def texture_color(self, xyz, P, image):
         """Stage: texture_color (CCloudOptimization.cpp:400-421) of xyz [n,3] float32 against one view (P 3x4, image BGR uint8 [H,W,3]):

@@ -350,3 +350,20 @@ class CloudOptimization:
             depth_eps = 2.0 * self.mesh_grid_step
         self.mesh_colors = self._ctx.mesh_color_last(cams, depth_eps, mode, min_cos)
         return self.mesh_colors
+
+    def stitch_mesh(self, min_cos=0.2, depth_eps=None, lam=0.01, iterations=0, reduction=1e-4, seam_gradient=True):
+        """The other half of TextureStitcher's job (:394-397): mesh_result's vertices coloured by their best view, then the views'
+        exposure seams levelled by the screened gradient-domain solve of DESIGN.md 9 f10 (Context.mesh_stitch_last; the mesh itself is
+        untouched).  depth_eps defaults to twice the Poisson grid step.  Stores and returns
+        mesh_colors = (rgb uint8 [nv,3], best_view int32 [nv], stats)."""
+        if getattr(self, "mesh_result", None) is None:
+            raise ValueError("CloudOptimization.stitch_mesh: mesh() first (it colours mesh()'s surface)")
+        cams = self.m_ImageData.cam
+        if any(c.P is None or c.image is None for pair in cams for c in pair[:2]):
+            raise ValueError("CloudOptimization.stitch_mesh: the mesh colouring (where CCloudOptimization::run calls TextureStitcher, "
+                             "CCloudOptimization.cpp:394-397) needs every camera's P and image, as Rectify leaves them; pre-rectified input "
+                             "carries no P")
+        if depth_eps is None:
+            depth_eps = 2.0 * self.mesh_grid_step
+        self.mesh_colors = self._ctx.mesh_stitch_last(cams, depth_eps, min_cos, lam, iterations, reduction, seam_gradient)
+        return self.mesh_colors

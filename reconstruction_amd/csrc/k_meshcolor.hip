@@ -14,8 +14,7 @@
 // evaluated as written.
 #include "../../include/rsm.h"
 #include "rsm_dev.h"
-#include "mesh_common.h"
-#include "project_common.h"
+#include "meshcolor_common.h"
 
 #include <math.h>
 #include <string.h>
@@ -33,32 +32,8 @@ typedef unsigned long long u64;
 
 enum { K_COLOURED = 0, K_NONORMAL, K_VISIBLE, K_DRAWN, K_BIG, K_CURSOR, K_N };
 
-// one view as the kernels see it: R / T as float (cv2eigen of P's columns, as k_dedup), the centre in fp64, the images on the device
-struct McView {
-    float R[9], T[3];
-    double C[3];
-    int W, H;
-    const uint8_t *img, *mask; // BGR, stride 3 W; mask may be NULL: all 255
-    uint32_t *wbuf;            // W x H
-};
-
 __device__ __forceinline__ void count_if(bool flag, u64 *ctr) {
     if (flag) atomicAdd(ctr, (u64)1);
-}
-
-__device__ __forceinline__ void mcol_q(const McView &c, float px, float py, float pz, float *q0, float *q1, float *q2) {
-    *q0 = dd_dot3(c.R[0], c.R[1], c.R[2], px, py, pz) + c.T[0];
-    *q1 = dd_dot3(c.R[3], c.R[4], c.R[5], px, py, pz) + c.T[1];
-    *q2 = dd_dot3(c.R[6], c.R[7], c.R[8], px, py, pz) + c.T[2];
-}
-
-// the texture_color pixel of a projected point; false where texture_color answers (127, 127, 127)
-__device__ __forceinline__ bool mcol_pixel(float q0, float q1, float q2, int W, int H, size_t *pix) {
-    long long x, y;
-    if (!dd_round(q0 / q2, &x) || !dd_round(q1 / q2, &y)) return false;
-    if (x < 0 || x >= W || y < 0 || y >= H) return false;
-    *pix = (size_t)y * (size_t)W + (size_t)x;
-    return true;
 }
 
 // ---- texture_color over an array ----------------------------------------------------------------------------------------------------
@@ -185,10 +160,10 @@ __global__ __launch_bounds__(256) void k_mcol_raster_big(const float *__restrict
 // ---- colours ------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_mcol_color(const float *__restrict__ p, size_t nv, const int32_t *__restrict__ f, const uint32_t *__restrict__ row,
                                                     const uint32_t *__restrict__ corner, const McView *__restrict__ views, int V, int mode, double min_cos,
-                                                    double depth_eps, uint8_t *__restrict__ rgb, int32_t *__restrict__ best_view, u64 *__restrict__ ctr) {
+                                                    double depth_eps, uint8_t *__restrict__ rgb, int32_t *__restrict__ best_view, u64 *__restrict__ vis, u64 *__restrict__ ctr) {
     const size_t j = (size_t)blockIdx.x * 256 + threadIdx.x;
     bool coloured = false, no_normal = false;
-    u64 n_vis = 0;
+    u64 n_vis = 0, seen = 0; // seen: bit k = view k sees the vertex (written only where vis is given: V <= 64 there)
     if (j < nv) {
         // the normal: the faces' (P1 - P0) x (P2 - P0), fp64 from the float positions, summed over the corner list in ascending 3 f + j
         double nx = 0.0, ny = 0.0, nz = 0.0;
@@ -226,6 +201,7 @@ __global__ __launch_bounds__(256) void k_mcol_color(const float *__restrict__ p,
                 const uint32_t wb = c.wbuf[pix];
                 if (wb != 0 && !((double)q2 <= 1.0 / (double)__uint_as_float(wb) + depth_eps)) continue;
                 n_vis++;
+                seen |= (u64)1 << (k & 63);
                 const uint8_t cb = c.img[3 * pix], cg = c.img[3 * pix + 1], cr = c.img[3 * pix + 2];
                 if (best < 0 || cs > best_cos) { // (strict: a tie stays with the lower view)
                     best = k;
@@ -251,6 +227,7 @@ __global__ __launch_bounds__(256) void k_mcol_color(const float *__restrict__ p,
         rgb[3 * j + 1] = bg;
         rgb[3 * j + 2] = bb;
         if (best_view) best_view[j] = best;
+        if (vis) vis[j] = seen;
     }
     count_if(coloured, ctr + K_COLOURED);
     count_if(no_normal, ctr + K_NONORMAL);
@@ -341,20 +318,11 @@ int mesh_depth_device(const float *d_v, int64_t nv, const int32_t *d_f, int64_t 
     return RSM_OK;
 }
 
-int mesh_color_device(const float *d_v, int64_t nv_, const int32_t *d_f, int64_t nf_, const rsm_dedup_view *views, int n_pairs, const rsm_mesh_color_params *p,
-                      long long big_box, uint8_t *d_rgb, int32_t *d_best, double *stats, int *invalid, hipStream_t st) {
-    const size_t nv = (size_t)nv_, nf = (size_t)nf_;
-    double S[RSM_MESH_COLOR_STATS] = {0};
-    S[0] = (double)nv;
-    int s = mesh_validate_device(d_v, nv_, d_f, nf_, invalid, st);
-    if (s != RSM_OK) return s;
-    if (nv == 0) {
-        if (stats) memcpy(stats, S, sizeof S);
-        return RSM_OK;
-    }
+int mesh_views_device(DevMem &M, const rsm_dedup_view *views, int n_pairs, bool with_wbuf, std::vector<McView> *hv_, McView **d_views, int *invalid, hipStream_t st) {
     // the views in scans.txt's order: every pair's view 0, then every pair's view 1
     const int V = 2 * n_pairs;
-    std::vector<McView> hv((size_t)V);
+    std::vector<McView> &hv = *hv_;
+    hv.resize((size_t)V);
     for (int k = 0; k < 2; k++)
         for (int i = 0; i < n_pairs; i++) {
             McView &c = hv[(size_t)k * n_pairs + i];
@@ -366,29 +334,48 @@ int mesh_color_device(const float *d_v, int64_t nv_, const int32_t *d_f, int64_t
             c.W = views[i].width;
             c.H = views[i].height;
         }
-    DevMem M;
     for (int k = 0; k < 2; k++)
         for (int i = 0; i < n_pairs; i++) {
             McView &c = hv[(size_t)k * n_pairs + i];
             const size_t pix = (size_t)c.W * (size_t)c.H;
             uint8_t *img = M.get<uint8_t>(3 * pix), *msk = views[i].mask[k] ? M.get<uint8_t>(pix) : nullptr;
-            c.wbuf = M.get<uint32_t>(pix);
+            c.wbuf = with_wbuf ? M.get<uint32_t>(pix) : nullptr;
             if (!M.ok) return RSM_E_NOMEM;
             KCHK(hipMemcpyAsync(img, views[i].image[k], 3 * pix, hipMemcpyHostToDevice, st));
             if (msk) KCHK(hipMemcpyAsync(msk, views[i].mask[k], pix, hipMemcpyHostToDevice, st));
             c.img = img;
             c.mask = msk;
         }
-    McView *d_views = M.get<McView>((size_t)V);
+    *d_views = M.get<McView>((size_t)V);
+    if (!M.ok) return RSM_E_NOMEM;
+    KCHK(hipMemcpyAsync(*d_views, hv.data(), sizeof(McView) * (size_t)V, hipMemcpyHostToDevice, st));
+    return RSM_OK;
+}
+
+int mesh_color_scene_device(DevMem &M, const float *d_v, int64_t nv_, const int32_t *d_f, int64_t nf_, const rsm_dedup_view *views, int n_pairs,
+                            const rsm_mesh_color_params *p, long long big_box, uint8_t *d_rgb, int32_t *d_best, u64 *d_vis, double *stats, int *invalid,
+                            McScene *scene, hipStream_t st) {
+    const size_t nv = (size_t)nv_, nf = (size_t)nf_;
+    double S[RSM_MESH_COLOR_STATS] = {0};
+    S[0] = (double)nv;
+    int s = mesh_validate_device(d_v, nv_, d_f, nf_, invalid, st);
+    if (s != RSM_OK) return s;
+    if (nv == 0) {
+        if (stats) memcpy(stats, S, sizeof S);
+        return RSM_OK;
+    }
+    const int V = 2 * n_pairs;
+    std::vector<McView> hv;
+    McView *d_views = nullptr;
+    if ((s = mesh_views_device(M, views, n_pairs, true, &hv, &d_views, invalid, st)) != RSM_OK) return s;
     u64 *ctr = M.get<u64>(K_N);
     if (!M.ok) return RSM_E_NOMEM;
-    KCHK(hipMemcpyAsync(d_views, hv.data(), sizeof(McView) * (size_t)V, hipMemcpyHostToDevice, st));
     KCHK(hipMemsetAsync(ctr, 0, K_N * sizeof(u64), st));
     uint32_t *row = nullptr, *corner = nullptr;
     if ((s = mesh_corner_lists_device(M, d_f, nv, nf, &row, &corner, st)) != RSM_OK) return s;
     if ((s = raster(M, d_v, d_f, nf, hv, d_views, big_box, ctr, st)) != RSM_OK) return s;
     hipLaunchKernelGGL(k_mcol_color, blocks_for(nv), dim3(256), 0, st, d_v, nv, d_f, (const uint32_t *)row, (const uint32_t *)corner, (const McView *)d_views, V,
-                       p->mode, p->min_cos, p->depth_eps, d_rgb, d_best, ctr);
+                       p->mode, p->min_cos, p->depth_eps, d_rgb, d_best, d_vis, ctr);
     u64 h[K_N];
     KCHK(hipMemcpyAsync(h, ctr, sizeof h, hipMemcpyDeviceToHost, st));
     KCHK(hipStreamSynchronize(st)); // (the views' host images and hv were read by the copies above before this returns)
@@ -399,5 +386,16 @@ int mesh_color_device(const float *d_v, int64_t nv_, const int32_t *d_f, int64_t
     S[4] = (double)h[K_DRAWN];
     S[5] = (double)h[K_BIG];
     if (stats) memcpy(stats, S, sizeof S);
+    scene->d_views = d_views;
+    scene->V = V;
+    scene->row = row;
+    scene->corner = corner;
     return RSM_OK;
+}
+
+int mesh_color_device(const float *d_v, int64_t nv, const int32_t *d_f, int64_t nf, const rsm_dedup_view *views, int n_pairs, const rsm_mesh_color_params *p,
+                      long long big_box, uint8_t *d_rgb, int32_t *d_best, double *stats, int *invalid, hipStream_t st) {
+    DevMem M;
+    McScene scene;
+    return mesh_color_scene_device(M, d_v, nv, d_f, nf, views, n_pairs, p, big_box, d_rgb, d_best, nullptr, stats, invalid, &scene, st);
 }

@@ -265,3 +265,21 @@ int mesh_depth_device(const float *d_v, int64_t nv, const int32_t *d_f, int64_t 
                       int *invalid, hipStream_t st);
 // texture_color (CCloudOptimization.cpp:400-421) of n points against a BGR image on the device
 int texture_color_device(const float *d_xyz, int64_t n, const double P12[12], const uint8_t *d_img, int W, int H, uint8_t *d_rgb, hipStream_t st);
+
+// the views' exposure seams levelled in those colours (k_meshstitch.hip).  mesh_stitch_device: mesh_color_device's
+// arguments (mode 0; d_best may be NULL) and the stitch parameters, d_rgb = the levelled bytes, stats = RSM_MESH_STITCH_STATS doubles (may
+// be NULL); *invalid as there, or 4 (the reduction needs more than RSM_MESH_STITCH_MAX_ITERATIONS steps).  Parameters, views and V <= 64
+// are the caller's to check.
+struct rsm_mesh_stitch_params;
+int mesh_stitch_device(const float *d_v, int64_t nv, const int32_t *d_f, int64_t nf, const rsm_dedup_view *views, int n_pairs, const rsm_mesh_color_params *cp,
+                       const rsm_mesh_stitch_params *sp, long long big_box, uint8_t *d_rgb, int32_t *d_best, double *stats, int *invalid, hipStream_t st);
+// the least k with T_k(sigma) >= 1 / reduction by the recurrence; -1: more than RSM_MESH_STITCH_MAX_ITERATIONS
+int mesh_stitch_steps(double lambda, unsigned long long dmax, double reduction);
+// the stages: d_vis nv uint64 (bit v = view v sees the vertex); d_best's values lie in -1 .. V - 1 (the caller's to check)
+int mesh_visibility_device(const float *d_v, int64_t nv, const int32_t *d_f, int64_t nf, const rsm_dedup_view *views, int n_pairs, const rsm_mesh_color_params *p,
+                           long long big_box, unsigned long long *d_vis, int *invalid, hipStream_t st);
+int mesh_stitch_rhs_device(const float *d_v, int64_t nv, const int32_t *d_f, int64_t nf, const rsm_dedup_view *views, int n_pairs, const uint8_t *d_rgb,
+                           const int32_t *d_best, const unsigned long long *d_vis, int seam_gradient, double *d_G, int32_t *d_deg, int64_t counts[5], int *invalid,
+                           hipStream_t st);
+int mesh_stitch_solve_device(const int32_t *d_f, int64_t nv, int64_t nf, const int32_t *d_best, const uint8_t *d_rgb, const double *d_G, double lambda,
+                             int iterations, double *d_x, double *rel_residual, int *invalid, hipStream_t st);

@@ -1,5 +1,5 @@
 // rsm_mesh.hip -- the mesh back end's host side: the dense-grid Poisson surface, its smoothing and clean-up, and its colours
-// from the rig's views (k_poisson.hip, k_meshclean.hip, k_meshcolor.hip).
+// from the rig's views with their seams levelled (k_poisson.hip, k_meshclean.hip, k_meshcolor.hip, k_meshstitch.hip).
 #include "rsm_ctx.h"
 
 #include <cmath>
@@ -338,12 +338,8 @@ extern "C" int rsm_mesh_color(rsm_ctx *c, const float *xyz, int64_t nv, const in
     return RSM_OK;
 }
 
-extern "C" int rsm_mesh_color_last(rsm_ctx *c, const rsm_dedup_view *views, int n_pairs, const rsm_mesh_color_params *p, double *stats) {
-    if (!c) return RSM_E_INVALID;
-    int s = meshcolor_params_ok(c, p);
-    const int64_t nv = c->pmesh.nv, nf = c->pmesh.nf;
-    if (s != RSM_OK || (s = meshcolor_views_ok(c, nv, views, n_pairs)) != RSM_OK) return s;
-    HIPCHK(c, hipSetDevice(c->device));
+// the context's colour buffers for a mesh of nv vertices (what rsm_mesh_last_colors copies out), without an owner yet
+static int mcol_reserve(rsm_ctx *c, const char *who, int64_t nv) {
     if (c->mcol_rgb) (void)hipFree(c->mcol_rgb);
     if (c->mcol_best) (void)hipFree(c->mcol_best);
     c->mcol_rgb = nullptr;
@@ -351,7 +347,17 @@ extern "C" int rsm_mesh_color_last(rsm_ctx *c, const rsm_dedup_view *views, int 
     c->mcol_of = nullptr;
     c->mcol_nv = 0;
     if (hipMalloc((void **)&c->mcol_rgb, 3 * (size_t)nv + 64) != hipSuccess || hipMalloc((void **)&c->mcol_best, sizeof(int32_t) * (size_t)nv + 64) != hipSuccess)
-        return set_err(c, RSM_E_NOMEM, "mesh_color: no device memory for %lld vertices", (long long)nv);
+        return set_err(c, RSM_E_NOMEM, "%s: no device memory for %lld vertices", who, (long long)nv);
+    return RSM_OK;
+}
+
+extern "C" int rsm_mesh_color_last(rsm_ctx *c, const rsm_dedup_view *views, int n_pairs, const rsm_mesh_color_params *p, double *stats) {
+    if (!c) return RSM_E_INVALID;
+    int s = meshcolor_params_ok(c, p);
+    const int64_t nv = c->pmesh.nv, nf = c->pmesh.nf;
+    if (s != RSM_OK || (s = meshcolor_views_ok(c, nv, views, n_pairs)) != RSM_OK) return s;
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((s = mcol_reserve(c, "mesh_color", nv)) != RSM_OK) return s;
     int invalid = 0;
     s = mesh_color_device(c->pmesh.d_v, nv, c->pmesh.d_f, nf, views, n_pairs, p, c->opt_meshcolor_big_box, c->mcol_rgb, c->mcol_best, stats, &invalid, c->stream);
     if (s != RSM_OK) return meshcolor_fail(c, s, invalid);
@@ -407,6 +413,153 @@ extern "C" int rsm_stage_mesh_depth(rsm_ctx *c, const float *xyz, int64_t nv, co
     int invalid = 0;
     if ((s = mesh_depth_device(dv, nv, df, nf, P12, width, height, c->opt_meshcolor_big_box, dw, &invalid, c->stream)) != RSM_OK) return meshcolor_fail(c, s, invalid);
     HIPCHK(c, hipMemcpyAsync(wbuf, dw, sizeof(uint32_t) * pix, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RSM_OK;
+}
+
+// ---- the views' exposure seams levelled in those colours (k_meshstitch.hip) ---------------------------------------------
+static int meshstitch_params_ok(rsm_ctx *c, const rsm_mesh_color_params *p, const rsm_mesh_stitch_params *sp, int64_t nv, int n_pairs) {
+    int s = meshcolor_params_ok(c, p);
+    if (s != RSM_OK) return s;
+    if (p->mode != 0) return set_err(c, RSM_E_INVALID, "mesh_stitch: mode %d not 0 (the best view's colours are what it levels)", p->mode);
+    if (!sp) return set_err(c, RSM_E_INVALID, "mesh_stitch: stitch params is NULL");
+    if (!std::isfinite(sp->lambda) || !(sp->lambda > 0.0)) return set_err(c, RSM_E_INVALID, "mesh_stitch: lambda %g not finite or not > 0", sp->lambda);
+    if (sp->iterations < 0 || sp->iterations > RSM_MESH_STITCH_MAX_ITERATIONS)
+        return set_err(c, RSM_E_INVALID, "mesh_stitch: iterations %d outside 0..%d", sp->iterations, RSM_MESH_STITCH_MAX_ITERATIONS);
+    if (sp->iterations == 0 && !(sp->reduction > 0.0 && sp->reduction < 1.0)) return set_err(c, RSM_E_INVALID, "mesh_stitch: reduction %g not in (0, 1)", sp->reduction);
+    if (sp->seam_gradient != 0 && sp->seam_gradient != 1) return set_err(c, RSM_E_INVALID, "mesh_stitch: seam_gradient %d not 0 or 1", sp->seam_gradient);
+    if (nv > 0 && n_pairs > 32) return set_err(c, RSM_E_INVALID, "mesh_stitch: V = 2 n_pairs = %d views, more than the 64 a visibility mask holds", 2 * n_pairs);
+    return RSM_OK;
+}
+static int meshstitch_fail(rsm_ctx *c, int s, int invalid) {
+    if (s == RSM_E_INVALID && invalid == 4)
+        return set_err(c, s, "mesh_stitch: reduction needs more than %d steps at this lambda (give iterations)", RSM_MESH_STITCH_MAX_ITERATIONS);
+    return meshcolor_fail(c, s, invalid);
+}
+
+extern "C" int rsm_mesh_stitch_device(rsm_ctx *c, const float *d_xyz, int64_t nv, const int32_t *d_faces, int64_t nf, const rsm_dedup_view *views, int n_pairs,
+                                      const rsm_mesh_color_params *p, const rsm_mesh_stitch_params *sp, uint8_t *d_rgb, int32_t *d_best_view, double *stats) {
+    if (!c) return RSM_E_INVALID;
+    int s = meshstitch_params_ok(c, p, sp, nv, n_pairs);
+    if (s != RSM_OK || (s = mesh_counts_ok(c, "mesh_color", nv, nf)) != RSM_OK) return s;
+    if ((nv > 0 && (!d_xyz || !d_rgb)) || (nf > 0 && !d_faces)) return set_err(c, RSM_E_INVALID, "mesh_color: a NULL pointer");
+    if ((s = meshcolor_views_ok(c, nv, views, n_pairs)) != RSM_OK) return s;
+    HIPCHK(c, hipSetDevice(c->device));
+    int invalid = 0;
+    s = mesh_stitch_device(d_xyz, nv, d_faces, nf, views, n_pairs, p, sp, c->opt_meshcolor_big_box, d_rgb, d_best_view, stats, &invalid, c->stream);
+    return s == RSM_OK ? RSM_OK : meshstitch_fail(c, s, invalid);
+}
+
+extern "C" int rsm_mesh_stitch(rsm_ctx *c, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, const rsm_dedup_view *views, int n_pairs,
+                               const rsm_mesh_color_params *p, const rsm_mesh_stitch_params *sp, uint8_t *rgb, int32_t *best_view, double *stats) {
+    if (!c) return RSM_E_INVALID;
+    int s = meshstitch_params_ok(c, p, sp, nv, n_pairs);
+    if (s != RSM_OK || (s = mesh_counts_ok(c, "mesh_color", nv, nf)) != RSM_OK) return s;
+    if ((nv > 0 && (!xyz || !rgb)) || (nf > 0 && !faces)) return set_err(c, RSM_E_INVALID, "mesh_color: a NULL pointer");
+    if ((s = meshcolor_views_ok(c, nv, views, n_pairs)) != RSM_OK) return s;
+    HIPCHK(c, hipSetDevice(c->device));
+    Tmp T(c);
+    float *dv = T.up(xyz, 3 * (size_t)nv);
+    int32_t *df = T.up(faces, 3 * (size_t)nf), *db = T.alloc<int32_t>((size_t)nv);
+    uint8_t *dc = T.alloc<uint8_t>(3 * (size_t)nv);
+    if (!dv || !df || !db || !dc) return set_err(c, RSM_E_NOMEM, "mesh_stitch: no device memory for %lld vertices, %lld faces", (long long)nv, (long long)nf);
+    if ((s = finish(c, T)) != RSM_OK) return s;
+    int invalid = 0;
+    s = mesh_stitch_device(dv, nv, df, nf, views, n_pairs, p, sp, c->opt_meshcolor_big_box, dc, db, stats, &invalid, c->stream);
+    if (s != RSM_OK) return meshstitch_fail(c, s, invalid);
+    if (nv > 0) HIPCHK(c, hipMemcpyAsync(rgb, dc, 3 * (size_t)nv, hipMemcpyDeviceToHost, c->stream));
+    if (nv > 0 && best_view) HIPCHK(c, hipMemcpyAsync(best_view, db, sizeof(int32_t) * (size_t)nv, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RSM_OK;
+}
+
+extern "C" int rsm_mesh_stitch_last(rsm_ctx *c, const rsm_dedup_view *views, int n_pairs, const rsm_mesh_color_params *p, const rsm_mesh_stitch_params *sp,
+                                    double *stats) {
+    if (!c) return RSM_E_INVALID;
+    const int64_t nv = c->pmesh.nv, nf = c->pmesh.nf;
+    int s = meshstitch_params_ok(c, p, sp, nv, n_pairs);
+    if (s != RSM_OK || (s = meshcolor_views_ok(c, nv, views, n_pairs)) != RSM_OK) return s;
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((s = mcol_reserve(c, "mesh_stitch", nv)) != RSM_OK) return s;
+    int invalid = 0;
+    s = mesh_stitch_device(c->pmesh.d_v, nv, c->pmesh.d_f, nf, views, n_pairs, p, sp, c->opt_meshcolor_big_box, c->mcol_rgb, c->mcol_best, stats, &invalid, c->stream);
+    if (s != RSM_OK) return meshstitch_fail(c, s, invalid);
+    c->mcol_of = c->pmesh.d_v;
+    c->mcol_nv = nv;
+    return RSM_OK;
+}
+
+extern "C" int rsm_stage_mesh_visibility(rsm_ctx *c, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, const rsm_dedup_view *views, int n_pairs,
+                                         const rsm_mesh_color_params *p, uint64_t *vis) {
+    if (!c) return RSM_E_INVALID;
+    int s = meshcolor_params_ok(c, p);
+    if (s != RSM_OK || (s = mesh_counts_ok(c, "mesh_color", nv, nf)) != RSM_OK) return s;
+    if ((nv > 0 && (!xyz || !vis)) || (nf > 0 && !faces)) return set_err(c, RSM_E_INVALID, "mesh_color: a NULL pointer");
+    if ((s = meshcolor_views_ok(c, nv, views, n_pairs)) != RSM_OK) return s;
+    if (nv > 0 && n_pairs > 32) return set_err(c, RSM_E_INVALID, "mesh_stitch: V = 2 n_pairs = %d views, more than the 64 a visibility mask holds", 2 * n_pairs);
+    HIPCHK(c, hipSetDevice(c->device));
+    Tmp T(c);
+    float *dv = T.up(xyz, 3 * (size_t)nv);
+    int32_t *df = T.up(faces, 3 * (size_t)nf);
+    unsigned long long *dm = T.alloc<unsigned long long>((size_t)nv);
+    if (!dv || !df || !dm) return set_err(c, RSM_E_NOMEM, "mesh_stitch: no device memory");
+    if ((s = finish(c, T)) != RSM_OK) return s;
+    int invalid = 0;
+    if ((s = mesh_visibility_device(dv, nv, df, nf, views, n_pairs, p, c->opt_meshcolor_big_box, dm, &invalid, c->stream)) != RSM_OK) return meshcolor_fail(c, s, invalid);
+    if (nv > 0) HIPCHK(c, hipMemcpyAsync(vis, dm, sizeof(uint64_t) * (size_t)nv, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RSM_OK;
+}
+
+extern "C" int rsm_stage_mesh_stitch_rhs(rsm_ctx *c, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, const rsm_dedup_view *views, int n_pairs,
+                                         const uint8_t *rgb, const int32_t *best_view, const uint64_t *vis, int seam_gradient, double *G, int32_t *deg,
+                                         int64_t counts[5]) {
+    if (!c) return RSM_E_INVALID;
+    int s = mesh_counts_ok(c, "mesh_color", nv, nf);
+    if (s != RSM_OK) return s;
+    if (!counts || (nv > 0 && (!xyz || !rgb || !best_view || !vis || !G || !deg)) || (nf > 0 && !faces)) return set_err(c, RSM_E_INVALID, "mesh_stitch: a NULL pointer");
+    if (seam_gradient != 0 && seam_gradient != 1) return set_err(c, RSM_E_INVALID, "mesh_stitch: seam_gradient %d not 0 or 1", seam_gradient);
+    if ((s = meshcolor_views_ok(c, nv, views, n_pairs)) != RSM_OK) return s;
+    if (nv > 0 && n_pairs > 32) return set_err(c, RSM_E_INVALID, "mesh_stitch: V = 2 n_pairs = %d views, more than the 64 a visibility mask holds", 2 * n_pairs);
+    for (int64_t i = 0; i < nv; i++)
+        if (best_view[i] < -1 || best_view[i] >= 2 * n_pairs) return set_err(c, RSM_E_INVALID, "mesh_stitch: best_view[%lld] = %d outside -1..V-1", (long long)i, best_view[i]);
+    HIPCHK(c, hipSetDevice(c->device));
+    Tmp T(c);
+    float *dv = T.up(xyz, 3 * (size_t)nv);
+    int32_t *df = T.up(faces, 3 * (size_t)nf), *db = T.up(best_view, (size_t)nv), *dd = T.alloc<int32_t>((size_t)nv);
+    uint8_t *dc = T.up(rgb, 3 * (size_t)nv);
+    unsigned long long *dm = T.up((const unsigned long long *)vis, (size_t)nv);
+    double *dG = T.alloc<double>(3 * (size_t)nv);
+    if (!dv || !df || !db || !dd || !dc || !dm || !dG) return set_err(c, RSM_E_NOMEM, "mesh_stitch: no device memory");
+    if ((s = finish(c, T)) != RSM_OK) return s;
+    int invalid = 0;
+    if ((s = mesh_stitch_rhs_device(dv, nv, df, nf, views, n_pairs, dc, db, dm, seam_gradient, dG, dd, counts, &invalid, c->stream)) != RSM_OK)
+        return meshcolor_fail(c, s, invalid);
+    if (nv > 0) HIPCHK(c, hipMemcpyAsync(G, dG, sizeof(double) * 3 * (size_t)nv, hipMemcpyDeviceToHost, c->stream));
+    if (nv > 0) HIPCHK(c, hipMemcpyAsync(deg, dd, sizeof(int32_t) * (size_t)nv, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RSM_OK;
+}
+
+extern "C" int rsm_stage_mesh_stitch_solve(rsm_ctx *c, const int32_t *faces, int64_t nv, int64_t nf, const int32_t *best_view, const uint8_t *rgb, const double *G,
+                                           double lambda, int iterations, double *x, double *rel_residual) {
+    if (!c) return RSM_E_INVALID;
+    int s = mesh_counts_ok(c, "mesh_color", nv, nf);
+    if (s != RSM_OK) return s;
+    if (!rel_residual || (nv > 0 && (!best_view || !rgb || !G || !x)) || (nf > 0 && !faces)) return set_err(c, RSM_E_INVALID, "mesh_stitch: a NULL pointer");
+    if (!std::isfinite(lambda) || !(lambda > 0.0)) return set_err(c, RSM_E_INVALID, "mesh_stitch: lambda %g not finite or not > 0", lambda);
+    if (iterations < 0 || iterations > RSM_MESH_STITCH_MAX_ITERATIONS)
+        return set_err(c, RSM_E_INVALID, "mesh_stitch: iterations %d outside 0..%d", iterations, RSM_MESH_STITCH_MAX_ITERATIONS);
+    HIPCHK(c, hipSetDevice(c->device));
+    Tmp T(c);
+    int32_t *df = T.up(faces, 3 * (size_t)nf), *db = T.up(best_view, (size_t)nv);
+    uint8_t *dc = T.up(rgb, 3 * (size_t)nv);
+    double *dG = T.up(G, 3 * (size_t)nv), *dx = T.alloc<double>(3 * (size_t)nv);
+    if (!df || !db || !dc || !dG || !dx) return set_err(c, RSM_E_NOMEM, "mesh_stitch: no device memory");
+    if ((s = finish(c, T)) != RSM_OK) return s;
+    int invalid = 0;
+    if ((s = mesh_stitch_solve_device(df, nv, nf, db, dc, dG, lambda, iterations, dx, rel_residual, &invalid, c->stream)) != RSM_OK) return meshcolor_fail(c, s, invalid);
+    if (nv > 0) HIPCHK(c, hipMemcpyAsync(x, dx, sizeof(double) * 3 * (size_t)nv, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return RSM_OK;
 }
