@@ -2,10 +2,13 @@
 // vendored Armadillo primitives on inputs from a blob file, writes their outputs to another blob.
 //
 // Linked with the reference's own objects (ref_tu_stereo.o / ref_tu_data.o, compiled from the sources
-// where they lie) using --unresolved-symbols=ignore-all: nothing is stood in for OpenCV; the functions
-// called here (CManageData::WindowToVec, CStereoMatching::FindMargin / OrderConstraint /
-// UniquenessContraint<T>) only use header-inline cv::Mat accessors over caller-owned buffers.
-// Everything that allocates a cv::Mat (the other stages) cannot run and stays "parity unpinned".
+// where they lie) using --unresolved-symbols=ignore-all.  The first group of functions called here
+// (CManageData::WindowToVec, CStereoMatching::FindMargin / OrderConstraint / UniquenessContraint<T>)
+// only uses header-inline cv::Mat accessors over caller-owned buffers.  The second group (SmoothConstraint,
+// SetBoundary_smooth<short>, MedianFilter, Rematch, LowestLevelInitialMatch) allocates cv::Mat objects and
+// runs on mat_storage.cpp: allocate, fill with a constant, free -- storage only, nothing that computes a
+// pixel value.  Every other OpenCV symbol stays unresolved, so the stages that need one (HighLevelInitialMatch:
+// copyTo; DisparityRefine: convertTo; DisparityToCloud: erode, MatExpr) cannot run and stay "parity unpinned".
 #define __declspec(x)
 #define _Longlong long long
 #include "SharedInclude.h"
@@ -15,6 +18,7 @@
 
 #include <cstdint>
 #include <cstdio>
+#include <cstring>
 #include <map>
 #include <string>
 #include <vector>
@@ -239,6 +243,99 @@ int main(int argc, char **argv) {
         snprintf(key, sizeof key, "xi_table_%d", i); out[key] = tb;
     }
     fprintf(stderr, "probe: refine data term done\n");
+    // ==== the stages that allocate a cv::Mat, on mat_storage.cpp's storage (allocate / fill / free only).  IsZeroOne = true
+    //      throughout: own = margin[0], other = margin[1].
+    // ---- CStereoMatching::SmoothConstraint (.cpp:370-448) and ::MedianFilter (.cpp:763-815, iteration = 1) on the same maps
+    for (int i = 0;; i++) {
+        snprintf(key, sizeof key, "sm_disp_%d", i);
+        if (!in.count(key)) break;
+        Arr d = in[key], e = in[key];
+        snprintf(key, sizeof key, "sm_mask_%d", i);
+        Arr &mk = in[key];
+        snprintf(key, sizeof key, "sm_margin_%d", i);
+        sm.margin[0] = bd(in[key].p<int>());
+        const int H = (int)d.dims[0], W = (int)d.dims[1];
+        cv::Mat disp(H, W, CV_16SC1, d.p<short>());
+        sm.SmoothConstraint(disp, true);
+        snprintf(key, sizeof key, "sm_smooth_%d", i); out[key] = d;
+        cv::Mat disp2(H, W, CV_16SC1, e.p<short>());
+        cv::Mat mask(H, W, CV_8UC1, mk.p<uchar>());
+        sm.MedianFilter(disp2, mask, 1, true);      // disp2 leaves as the header of the map the stage allocated
+        Arr r = make(1, {H, W});
+        for (int y = 0; y < H; y++) memcpy(r.p<short>() + (size_t)y * W, disp2.ptr<short>(y), sizeof(short) * W);
+        snprintf(key, sizeof key, "sm_median_%d", i); out[key] = r;
+    }
+    fprintf(stderr, "probe: smooth / median done\n");
+    // ---- CStereoMatching::SetBoundary_smooth<short> (.cpp:817-942)
+    for (int i = 0;; i++) {
+        snprintf(key, sizeof key, "sb_disp_%d", i);
+        if (!in.count(key)) break;
+        Arr d = in[key];
+        snprintf(key, sizeof key, "sb_mask_%d", i);
+        Arr &mk = in[key];
+        snprintf(key, sizeof key, "sb_margins_%d", i);
+        const int *m = in[key].p<int>(); // own(6), oth(6)
+        sm.margin[0] = bd(m);
+        sm.margin[1] = bd(m + 6);
+        const int H = (int)d.dims[0], W = (int)d.dims[1];
+        cv::Mat disp(H, W, CV_16SC1, d.p<short>());
+        cv::Mat mask(H, W, CV_8UC1, mk.p<uchar>());
+        cv::Mat BL, BR;
+        sm.SetBoundary_smooth<short>(disp, mask, BL, BR, true);
+        Arr bl = make(1, {H, W}), br = make(1, {H, W});
+        for (int y = 0; y < H; y++) {
+            memcpy(bl.p<short>() + (size_t)y * W, BL.ptr<short>(y), sizeof(short) * W);
+            memcpy(br.p<short>() + (size_t)y * W, BR.ptr<short>(y), sizeof(short) * W);
+        }
+        snprintf(key, sizeof key, "sb_bl_%d", i); out[key] = bl;
+        snprintf(key, sizeof key, "sb_br_%d", i); out[key] = br;
+    }
+    fprintf(stderr, "probe: set-boundary done\n");
+    // ---- CStereoMatching::LowestLevelInitialMatch (.cpp:170-227) and ::Rematch (.cpp:499-570) on the same images:
+    //      mt_disp_<i> stacks the maps Rematch is run on
+    for (int i = 0;; i++) {
+        snprintf(key, sizeof key, "mt_imgA_%d", i);
+        if (!in.count(key)) break;
+        Arr &A = in[key];
+        snprintf(key, sizeof key, "mt_imgB_%d", i);
+        Arr &B = in[key];
+        snprintf(key, sizeof key, "mt_maskA_%d", i);
+        Arr &mA = in[key];
+        snprintf(key, sizeof key, "mt_maskB_%d", i);
+        Arr &mB = in[key];
+        snprintf(key, sizeof key, "mt_r_%d", i);
+        sm.MatchBlockRadius = in[key].p<int>()[0];
+        snprintf(key, sizeof key, "mt_margins_%d", i);
+        const int *m = in[key].p<int>();
+        sm.margin[0] = bd(m);
+        sm.margin[1] = bd(m + 6);
+        const int H = (int)A.dims[0], W = (int)A.dims[1];
+        cv::Mat image[2] = {cv::Mat(H, W, CV_8UC3, A.p<uchar>()), cv::Mat(H, W, CV_8UC3, B.p<uchar>())};
+        cv::Mat mask[2] = {cv::Mat(H, W, CV_8UC1, mA.p<uchar>()), cv::Mat(H, W, CV_8UC1, mB.p<uchar>())};
+        data.m_LowestLevelSize = cv::Size(W, H);
+        cv::Mat low;
+        sm.LowestLevelInitialMatch(image, mask, low, true);
+        Arr r = make(1, {H, W});
+        for (int y = 0; y < H; y++) memcpy(r.p<short>() + (size_t)y * W, low.ptr<short>(y), sizeof(short) * W);
+        snprintf(key, sizeof key, "mt_lowest_%d", i); out[key] = r;
+        snprintf(key, sizeof key, "mt_disp_%d", i);
+        Arr d = in[key]; // n x H x W
+        Arr bl = make(1, d.dims), br = make(1, d.dims); // the intervals Rematch scans (its own SetBoundary_smooth call, :514)
+        for (int k = 0; k < (int)d.dims[0]; k++) {
+            cv::Mat disp(H, W, CV_16SC1, d.p<short>() + (size_t)k * H * W);
+            cv::Mat BL, BR;
+            sm.SetBoundary_smooth<short>(disp, mask[0], BL, BR, true);
+            for (int y = 0; y < H; y++) {
+                memcpy(bl.p<short>() + ((size_t)k * H + y) * W, BL.ptr<short>(y), sizeof(short) * W);
+                memcpy(br.p<short>() + ((size_t)k * H + y) * W, BR.ptr<short>(y), sizeof(short) * W);
+            }
+            sm.Rematch(image, mask, disp, true);
+        }
+        snprintf(key, sizeof key, "mt_rematch_%d", i); out[key] = d;
+        snprintf(key, sizeof key, "mt_bl_%d", i); out[key] = bl;
+        snprintf(key, sizeof key, "mt_br_%d", i); out[key] = br;
+    }
+    fprintf(stderr, "probe: lowest-level match / rematch done\n");
     write_blob(argv[2], out);
     printf("ref_probe: %zu outputs\n", out.size());
     return 0;

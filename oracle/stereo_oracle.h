@@ -8,16 +8,19 @@
  * (reconstruction_amd/, include/rsm.h) never links or calls it.
  *
  * PARITY PINNING STATUS (see DESIGN.md "Oracle"):
- *   - The reference cannot be linked here (OpenCV 2.4.5 binaries are absent and
- *     may not be stood in for), and it ships no tests/golden vectors.
+ *   - The reference cannot be linked here (OpenCV 2.4.5 binaries are absent; only
+ *     cv::Mat's storage -- allocate, constant fill, free -- is stood in for,
+ *     oracle/ref_probe/mat_storage.cpp), and it ships no tests/golden vectors.
  *   - Pinned against the real reference: the Armadillo 4.200 primitives this
  *     path uses (mean/norm/dot/median; vendored header-only library, compiled
- *     where it lies by oracle/ref_probe) and the reference functions that
+ *     where it lies by oracle/ref_probe), the reference functions that
  *     need no OpenCV library symbol (WindowToVec, FindMargin, OrderConstraint,
- *     UniquenessContraint_) -- golden vectors under tests/golden/.
- *   - Everything else (stages that allocate cv::Mat, pyrDown, erode): PARITY
- *     UNPINNED -- restated line by line from the source, checked only by
- *     known-answer tests derivable from the code.
+ *     UniquenessContraint_) and those that need cv::Mat storage only
+ *     (SmoothConstraint, SetBoundary_smooth, MedianFilter, Rematch,
+ *     LowestLevelInitialMatch) -- golden vectors under tests/golden/.
+ *   - Everything else (HighLevelInitialMatch's control flow, DisparityToCloud,
+ *     pyrDown, erode): PARITY UNPINNED -- restated line by line from the
+ *     source, checked only by known-answer tests derivable from the code.
  *   - DisparityRefine's exp() (the C runtime's: MSVC's for the reference, absent here) is evaluated by a fully specified
  *     routine shared with the GPU kernels: orc_exp_neg = the published table-driven algorithm of glibc 2.35's exp
  *     (e_exp.c, third-party, pinned version = this image's libm) in the operation order of its FMA build; pinned against
