@@ -1,9 +1,11 @@
-// cloud_grid.h -- the radius-cell grid of the cloud kernels (k_filter.hip's searches, k_mls.hip) and PCL's eigen33 in double.
+// cloud_grid.h -- the radius-cell grid of the cloud kernels (k_filter.hip's searches, k_mls.hip; built by cloud_grid.hip) and PCL's eigen33
+// in double.
 // Points sorted by the key of a uniform grid (cell edge h): the 27 cells around a point are 9 contiguous ranges of the
 // sorted array (ranges9), found by binary search on the keys.
 #pragma once
 
-#include "rsm_dev.h"
+#include "cloud_arena.h"
+#include "dev_prims.h"
 
 // Grid in KEY order: axis "x" is the fastest digit of the cell key, and it is the WORLD axis with the most cells (p0) --
 // a depth map is a sheet in a deep box, so the rows of cells along its depth hold a handful of points each and the
@@ -147,11 +149,13 @@ struct FilterGridDev {
     FGrid g{};
 };
 
-// k_filter.hip: sorts the n points of d_xyz (n x 3 float) by the key of a grid for the search radius h -- cell edge grid_edge(h) --
+// cloud_grid.hip: sorts the n points of d_xyz (n x 3 float) by the key of a grid for the search radius h -- cell edge grid_edge(h) --
 // over the box [bb_lo, bb_hi] (points outside fall into the border cells: clamping is non-expansive, so two points within h of each
 // other still sit in adjacent cells; non-finite points sort behind every cell); nv = finite points, 0 = no cell table (ranges by
 // binary search).  The arrays come from the arena and stay allocated until its caller rewinds it.
 int build_grid(FilterArena *A, const float *d_xyz, int64_t n, int64_t nv, float h, const float bb_lo[3], const float bb_hi[3],
                hipStream_t st, FilterGridDev &G);
-// k_filter.hip: the exact bounding box of the finite points of d_xyz and their number (one host round trip)
+// the exact bounding box of the finite points of d_xyz and their number (one host round trip; its 8 device words stay allocated)
 int cloud_bbox(FilterArena *A, const float *d_xyz, int64_t n, hipStream_t st, float lo[3], float hi[3], int64_t *nv);
+// the 1 % .. 99 % quantiles per axis of a sample of d_xyz (one host round trip; false: a HIP error or a full arena)
+bool sample_extent(FilterArena *A, const float *d_xyz, int64_t n, hipStream_t st, float lo[3], float hi[3]);

@@ -19,13 +19,11 @@
 // one thread per bucket start and writes the bucket's emitted indices into its own slice of a scratch array plus a count; the
 // counts' exclusive scan and k_dedup_write give indicesptr in (pair, y, x) order -- the reference's visiting order.
 #include "../../include/rsm.h"
-#include "rsm_dev.h"
+#include "cloud_arena.h"
+#include "dev_prims.h"
 #include "project_common.h"
 
 #include <float.h>
-#include <string.h>
-
-#include <rocprim/rocprim.hpp>
 
 #include <algorithm>
 #include <cmath>
@@ -276,48 +274,37 @@ size_t sort_scan_bytes(int64_t n) {
 
 template <typename K>
 int dedup_run(FilterArena *A, const float *d_pts, int stride, const float4 *d_nrm, int n, const DedupPair *d_pairs, int np, unsigned long long total, int32_t *d_index, int64_t *n_out, int64_t stats[4], hipStream_t st) {
-    unsigned long long *ctr = (unsigned long long *)filter_arena_alloc(A, 4 * sizeof(unsigned long long));
-    K *k0 = (K *)filter_arena_alloc(A, sizeof(K) * (size_t)n), *k1 = (K *)filter_arena_alloc(A, sizeof(K) * (size_t)n);
-    uint32_t *v0 = (uint32_t *)filter_arena_alloc(A, 4 * (size_t)n), *v1 = (uint32_t *)filter_arena_alloc(A, 4 * (size_t)n);
-    unsigned long long *h = (unsigned long long *)filter_arena_host(A); // [0..3] counters, [4] the last count + offset
+    unsigned long long *ctr = A->get<unsigned long long>(4);
+    K *k0 = A->get<K>((size_t)n), *k1 = A->get<K>((size_t)n);
+    uint32_t *v0 = A->get<uint32_t>((size_t)n), *v1 = A->get<uint32_t>((size_t)n);
+    unsigned long long *h = (unsigned long long *)filter_arena_host(A); // [0..3] counters, [4] the last offset and count
     if (!ctr || !k0 || !k1 || !v0 || !v1 || !h) return RSM_E_NOMEM;
-    if (hipMemsetAsync(ctr, 0, 4 * sizeof(unsigned long long), st) != hipSuccess) return RSM_E_HIP;
-    const dim3 grid((unsigned)((n + 255) / 256));
-    hipLaunchKernelGGL(k_dedup_assign<K>, grid, dim3(256), 0, st, d_pts, stride, d_nrm, n, d_pairs, np, (K)total, k0, v0, ctr);
-    int bits = 1; // keys 0 .. total (the sentinel): only the bits in use
-    while (bits < (int)(8 * sizeof(K)) && (total >> bits) != 0) bits++;
-    size_t sb = 0;
-    if (rocprim::radix_sort_pairs(nullptr, sb, k0, k1, v0, v1, (size_t)n, 0, bits, st) != hipSuccess) return RSM_E_HIP;
-    void *stmp = filter_arena_alloc(A, sb);
-    if (!stmp) return RSM_E_NOMEM;
-    if (rocprim::radix_sort_pairs(stmp, sb, k0, k1, v0, v1, (size_t)n, 0, bits, st) != hipSuccess) return RSM_E_HIP;
-    if (hipMemcpyAsync(h, ctr, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-        return RSM_E_HIP;
+    DEVCHK(hipMemsetAsync(ctr, 0, 4 * sizeof(unsigned long long), st));
+    hipLaunchKernelGGL(k_dedup_assign<K>, blocks_for(n), dim3(256), 0, st, d_pts, stride, d_nrm, n, d_pairs, np, (K)total, k0, v0, ctr);
+    // keys 0 .. total (the sentinel): only the bits in use
+    int s = sort_pairs(*A, k0, k1, v0, v1, (size_t)n, key_bits(total), st);
+    if (s != RSM_OK) return s;
+    DEVCHK(hipMemcpyAsync(h, ctr, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    DEVCHK(hipStreamSynchronize(st));
     const int nv = n - (int)(h[0] + h[1]);
     stats[0] = (int64_t)h[0];
     stats[1] = (int64_t)h[1];
     if (nv > 0) {
-        uint32_t *cnt = (uint32_t *)filter_arena_alloc(A, 4 * (size_t)nv), *off = (uint32_t *)filter_arena_alloc(A, 4 * (size_t)nv);
-        int32_t *tmp = (int32_t *)filter_arena_alloc(A, 4 * (size_t)nv);
-        float *dsc = (float *)filter_arena_alloc(A, 4 * (size_t)nv);
-        uint32_t *osc = (uint32_t *)filter_arena_alloc(A, 4 * (size_t)nv);
+        uint32_t *cnt = A->get<uint32_t>((size_t)nv), *off = A->get<uint32_t>((size_t)nv);
+        int32_t *tmp = A->get<int32_t>((size_t)nv);
+        float *dsc = A->get<float>((size_t)nv);
+        uint32_t *osc = A->get<uint32_t>((size_t)nv);
         if (!cnt || !off || !tmp || !dsc || !osc) return RSM_E_NOMEM;
-        const dim3 gv((unsigned)((nv + 255) / 256));
+        const dim3 gv = blocks_for(nv);
         hipLaunchKernelGGL(k_dedup_select<K>, gv, dim3(256), 0, st, k1, v1, nv, d_pts, stride, d_nrm, d_pairs, np, cnt, tmp, dsc, osc, ctr);
-        size_t cb = 0;
-        if (rocprim::exclusive_scan(nullptr, cb, cnt, off, 0u, (size_t)nv, rocprim::plus<uint32_t>(), st) != hipSuccess) return RSM_E_HIP;
-        void *ctmp = filter_arena_alloc(A, cb);
-        if (!ctmp) return RSM_E_NOMEM;
-        if (rocprim::exclusive_scan(ctmp, cb, cnt, off, 0u, (size_t)nv, rocprim::plus<uint32_t>(), st) != hipSuccess) return RSM_E_HIP;
+        if ((s = scan_u32(*A, cnt, off, (size_t)nv, st)) != RSM_OK) return s;
         hipLaunchKernelGGL(k_dedup_write, gv, dim3(256), 0, st, cnt, off, tmp, nv, d_index);
-        uint32_t *h32 = (uint32_t *)(h + 4);
-        if (hipMemcpyAsync(&h[2], &ctr[2], 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipMemcpyAsync(&h32[0], off + (nv - 1), 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-            hipMemcpyAsync(&h32[1], cnt + (nv - 1), 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-            return RSM_E_HIP;
+        uint64_t emitted = 0;
+        DEVCHK(hipMemcpyAsync(&h[2], &ctr[2], 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st)); // (read back with the total)
+        if ((s = scan_total(cnt, off, (size_t)nv, st, &emitted, (unsigned int *)(h + 4))) != RSM_OK) return s;
         stats[2] = (int64_t)h[2];
         stats[3] = (int64_t)h[3];
-        *n_out = (int64_t)h32[0] + h32[1];
+        *n_out = (int64_t)emitted;
     } else {
         stats[2] = stats[3] = 0;
         *n_out = 0;
@@ -391,7 +378,7 @@ int dedup_cloud_device(FilterArena *A, const float *d_pts, int stride, const flo
         const size_t pix = (size_t)w.width * w.height;
         uint8_t *d[4];
         for (int k = 0; k < 4; k++) {
-            d[k] = (uint8_t *)filter_arena_alloc(A, k < 2 ? 3 * pix : pix);
+            d[k] = A->get<uint8_t>(k < 2 ? 3 * pix : pix);
             if (!d[k]) return RSM_E_NOMEM;
             const uint8_t *src = k < 2 ? w.image[k] : w.mask[k - 2];
             if (hipMemcpyAsync(d[k], src, k < 2 ? 3 * pix : pix, hipMemcpyHostToDevice, st) != hipSuccess) return RSM_E_HIP;
@@ -405,7 +392,7 @@ int dedup_cloud_device(FilterArena *A, const float *d_pts, int stride, const flo
         stats[0] = n;
         return RSM_OK;
     }
-    DedupPair *dp = (DedupPair *)filter_arena_alloc(A, sizeof(DedupPair) * (size_t)np);
+    DedupPair *dp = A->get<DedupPair>((size_t)np);
     if (!dp) return RSM_E_NOMEM;
     if (hipMemcpyAsync(dp, hp.data(), sizeof(DedupPair) * (size_t)np, hipMemcpyHostToDevice, st) != hipSuccess) return RSM_E_HIP;
     // (the staged host vector is read by the copy before the first synchronisation inside dedup_run)
@@ -416,6 +403,6 @@ int dedup_cloud_device(FilterArena *A, const float *d_pts, int stride, const flo
 
 void launch_dedup_gather(const void *d_rec, const float *d_nrm, const int32_t *d_idx, int64_t m, void *d_orec, float *d_onrm, hipStream_t st) {
     if (m > 0)
-        hipLaunchKernelGGL(k_dedup_gather, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, (const float4 *)d_rec, (const float4 *)d_nrm, d_idx,
+        hipLaunchKernelGGL(k_dedup_gather, blocks_for(m), dim3(256), 0, st, (const float4 *)d_rec, (const float4 *)d_nrm, d_idx,
                            (int)m, (float4 *)d_orec, (float4 *)d_onrm);
 }

@@ -20,27 +20,13 @@
 //     corners) go to a list and are redone against ALL points by a workgroup each (three-pass radix select).
 //   radius search: cell edge = radius, the 27 cells cover the ball.
 #include "../../include/rsm.h"
-#include "rsm_dev.h"
 #include "cloud_grid.h"
 
-#include <cstring>
 #include <string.h>
-
-#include <rocprim/rocprim.hpp>
 
 #include <algorithm>
 #include <cmath>
-#include <limits>
 #include <vector>
-
-#include <string.h>
-
-#define FILTER_MAX_CELLS (1 << 25) // most cells a per-cell table is made for (256 MB); beyond that: per-row table / binary search on the keys
-// ... for an n-point cloud: a table of far more cells than points is mostly empty, and its bytes are pinned in the context's
-// grow-only arena (a 1-point cloud must not cost 256 MB)
-static inline size_t filter_max_cells(int64_t n) {
-    return (size_t)std::min<int64_t>(FILTER_MAX_CELLS, std::max<int64_t>(1 << 16, 8 * n));
-}
 
 // sqrtf, correctly rounded, for the k-nearest sums (PCL adds sqrt of the float32 squared distances): the compiler's own sequence --
 // v_sqrt_f32 (1 ulp), the two neighbouring floats, an fma residual each, two selects -- WITHOUT its input scaling for
@@ -73,40 +59,6 @@ void launch_sqrt_check(unsigned int first, long long n, unsigned long long *mism
     if (n > 0) hipLaunchKernelGGL(k_sqrt_check, dim3(8192), dim3(256), 0, st, first, n, mismatches);
 }
 
-
-__global__ void k_cell_keys(const float *__restrict__ xyz, int64_t n, FGrid g, unsigned long long *__restrict__ keys,
-                            unsigned int *__restrict__ vals) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    vals[i] = (unsigned int)i;
-    const float x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2];
-    if (!(isfinite(x) && isfinite(y) && isfinite(z))) { // PCL's searches skip such points: they sort behind every cell
-        keys[i] = ~0ull;
-        return;
-    }
-    int ix, iy, iz;
-    grid_cell(g, x, y, z, ix, iy, iz);
-    keys[i] = ((unsigned long long)iz * g.ny + iy) * g.nx + ix;
-}
-
-__global__ void k_gather_sorted(const float *__restrict__ xyz, const unsigned int *__restrict__ vals, int64_t n,
-                                float4 *__restrict__ sxyz) {
-    const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (j >= n) return;
-    const unsigned int i = vals[j];
-    sxyz[j] = make_float4(xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2], __uint_as_float(i));
-}
-
-
-// cell table: (first, one-past-last) sorted index of every cell's points; (0, 0) for an empty cell
-// div = 1: per cell; div = nx: per (y, z) row of cells (a deep or thick cloud has too many cells for a table of them)
-__global__ void k_cell_table(const unsigned long long *__restrict__ keys, int nv, unsigned long long div, int2 *__restrict__ table) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nv) return;
-    const unsigned long long k = keys[i] / div;
-    if (i == 0 || keys[i - 1] / div != k) table[k].x = i;
-    if (i == nv - 1 || keys[i + 1] / div != k) table[k].y = i + 1;
-}
 __device__ __forceinline__ int lower_bound_key_in(const unsigned long long *__restrict__ keys, int lo, int hi, unsigned long long k) {
     while (lo < hi) {
         const int mid = (lo + hi) >> 1;
@@ -585,11 +537,7 @@ __device__ __forceinline__ bool win_query(const Loader &ld, const float4 P, cons
     // what lies beyond the bound goes to the sink row
     for_disc([](int) {}, [&](float d2) {
         const int b = bin_of(d2);
-#if defined(WIN_EXP) && (WIN_EXP & 1) // timing experiment (results invalid): no histogram updates
-        asm volatile("" ::"v"(b));
-#else
         atomicAdd(col + 256 * b, 1u); // (no return value: a fire-and-forget ds_add)
-#endif
     });
     // the bin holding rank `want` (all counters read first: one LDS round trip, not one per bin)
     int below = 0, bstar = -1, in_bin = 0;
@@ -654,7 +602,6 @@ __device__ __forceinline__ bool win_query(const Loader &ld, const float4 P, cons
         wait = wait0;
         asm volatile("" : "+v"(wait));
     };
-#if !(defined(WIN_EXP) && (WIN_EXP & 2)) // (timing experiment, results invalid: no second pass)
     for_disc(
         [&](int n) {
             if (__builtin_expect(__any(wait + 256 * n > wait_end), 0)) drain();
@@ -667,7 +614,6 @@ __device__ __forceinline__ bool win_query(const Loader &ld, const float4 P, cons
                 wait += 256;
             }
         });
-#endif
     drain();
     // tau = the (want - below)-th smallest of the listed values (by value: ties are equal distances): the list into registers
     // (unused slots +inf), sorted by Batcher's merge exchange on the bit patterns (non-negative floats order as unsigned integers)
@@ -780,21 +726,25 @@ __global__ __launch_bounds__(256) void k_sor_window_list(const float4 *__restric
     undecided[q] = ok ? 0u : 1u; // (indexed like the list: the caller compacts it into the ladder's first list)
 }
 
-// Wave form: a wave = one listed query -- what the list passes leave: the points within a few dozen pixels of the mask's corners,
-// around holes, the outliers this filter exists to remove; hundreds, not millions -- its window of ANY radius read from the lattice
-// copy, candidates lane-strided (wave_knn_core: the grid search's selection).  The same bound as the other forms decides whether
-// the window holds the k + 1 nearest; the window is clipped to the lattice copy (no point lies outside the margin's box).
-__global__ __launch_bounds__(256) void k_sor_window_wave(const float4 *__restrict__ lat, const unsigned int *__restrict__ cell_of, WinGeom g, int mean_k, int WR,
-                                                          const unsigned int *__restrict__ list, int nq, float *__restrict__ dist, unsigned int *__restrict__ undecided) {
-    __shared__ float s_d2[4][KNN_CAP];
-    const int lane = threadIdx.x & 63;
-    const int qi = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (qi >= nq) return; // wave-uniform; no workgroup barrier below
-    const unsigned int pt = list[qi];
-    const unsigned int cell = cell_of[pt];
+// What the wave and the workgroup form share per query: the bound and its rounding margin as win_query forms them, the largest squared
+// distance h2 that stays below it, the window clipped to the lattice copy (no point lies outside the margin's box) and the squared
+// distance to its candidate c < M, row-major.  false: no positive bound -- the query stays undecided.
+// (Row of candidate c by a multiplication: the integer division was half of the wave kernel's instructions.  It is c / ncx exactly only
+// for c ncx < 2^32 -- a window of more than 2^16 pixels a side is past that; both forms take it from here, the one place to mend it.)
+struct WinCand {
+    const float4 *base; // the window's first pixel
+    float4 P;
+    int gw, ncx;        // the lattice copy's row length, the window's
+    unsigned int ncx_inv;
+    __device__ __forceinline__ float operator()(int c) const { // NaN for a pixel without a point: every comparison fails
+        const int r = ncx > 1 ? (int)__umulhi((unsigned int)c, ncx_inv) : c, col = c - r * ncx; // (ncx = 1: the reciprocal does not fit)
+        const float4 o = base[(size_t)r * gw + col];
+        return fdist2(P.x, P.y, P.z, o.x, o.y, o.z);
+    }
+};
+__device__ __forceinline__ bool win_clip(const float4 *__restrict__ lat, unsigned int cell, const WinGeom &g, int WR, WinCand &cand, float &h2, int &M) {
     const int cy = (int)(cell / (unsigned int)g.gw), cx = (int)(cell - (unsigned int)cy * (unsigned int)g.gw);
     const float4 P = lat[cell];
-    // the bound and its rounding margin, as win_query forms them
     const double dx = (double)P.x - g.T[0], dy = (double)P.y - g.T[1], dz = (double)P.z - g.T[2];
     const double F2 = fabs(g.rz[0] * dx + g.rz[1] * dy + g.rz[2] * dz), nP = sqrt(dx * dx + dy * dy + dz * dz);
     const double iw = F2 / fabs(g.qz);
@@ -802,22 +752,36 @@ __global__ __launch_bounds__(256) void k_sor_window_wave(const float4 *__restric
     const double coord = fmax(fmax(fabs((double)P.x), fabs((double)P.y)), fabs((double)P.z)) + nP;
     const double lim = LB * (1.0 - 1e-5) - 4e-7 * coord;
     const float range = (lim > 0.0) ? (float)(lim * lim * (1.0 - 1e-6)) : 0.0f; // tau must stay below this
-    if (!(range > 0.0f && isfinite(range))) {
+    if (!(range > 0.0f && isfinite(range))) return false;
+    h2 = __uint_as_float(__float_as_uint(range) - 1u); // d2 <= h2 is d2 < range
+    const int x0 = max(cx - WR, 0), x1 = min(cx + WR, g.gw - 1), y0 = max(cy - WR, 0), y1 = min(cy + WR, g.gh - 1);
+    cand.ncx = x1 - x0 + 1;
+    M = cand.ncx * (y1 - y0 + 1);
+    cand.base = lat + (size_t)y0 * g.gw + x0;
+    cand.P = P;
+    cand.gw = g.gw;
+    cand.ncx_inv = 0xffffffffu / (unsigned int)cand.ncx + 1u;
+    return true;
+}
+
+// Wave form: a wave = one listed query -- what the list passes leave: the points within a few dozen pixels of the mask's corners,
+// around holes, the outliers this filter exists to remove; hundreds, not millions -- its window of ANY radius read from the lattice
+// copy, candidates lane-strided (wave_knn_core: the grid search's selection).  The same bound as the other forms decides whether
+// the window holds the k + 1 nearest (win_clip).
+__global__ __launch_bounds__(256) void k_sor_window_wave(const float4 *__restrict__ lat, const unsigned int *__restrict__ cell_of, WinGeom g, int mean_k, int WR,
+                                                          const unsigned int *__restrict__ list, int nq, float *__restrict__ dist, unsigned int *__restrict__ undecided) {
+    __shared__ float s_d2[4][KNN_CAP];
+    const int lane = threadIdx.x & 63;
+    const int qi = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (qi >= nq) return; // wave-uniform; no workgroup barrier below
+    const unsigned int pt = list[qi];
+    WinCand cand;
+    float h2;
+    int M;
+    if (!win_clip(lat, cell_of[pt], g, WR, cand, h2, M)) {
         if (lane == 0) undecided[qi] = 1u;
         return;
     }
-    const float h2 = __uint_as_float(__float_as_uint(range) - 1u); // d2 <= h2 is d2 < range
-    const int x0 = max(cx - WR, 0), x1 = min(cx + WR, g.gw - 1), y0 = max(cy - WR, 0), y1 = min(cy + WR, g.gh - 1);
-    const int ncx = x1 - x0 + 1, M = ncx * (y1 - y0 + 1);
-    const float4 *base = lat + (size_t)y0 * g.gw + x0;
-    const int gw = g.gw;
-    // (row of candidate c by a multiplication: c / ncx exactly for c ncx < 2^32 -- the integer division was half of this kernel's instructions)
-    const unsigned int ncx_inv = 0xffffffffu / (unsigned int)ncx + 1u;
-    auto cand = [&](int c) -> float { // NaN for a pixel without a point: every comparison fails
-        const int r = ncx > 1 ? (int)__umulhi((unsigned int)c, ncx_inv) : c, col = c - r * ncx; // (ncx = 1: the reciprocal does not fit)
-        const float4 o = base[(size_t)r * gw + col];
-        return fdist2(P.x, P.y, P.z, o.x, o.y, o.z);
-    };
     float tau;
     double sum;
     int less;
@@ -841,31 +805,13 @@ __global__ __launch_bounds__(256) void k_sor_window_wg(const float4 *__restrict_
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     const int qi = blockIdx.x;
     const unsigned int pt = list[qi];
-    const unsigned int cell = cell_of[pt];
-    const int cy = (int)(cell / (unsigned int)g.gw), cx = (int)(cell - (unsigned int)cy * (unsigned int)g.gw);
-    const float4 P = lat[cell];
-    const double dx = (double)P.x - g.T[0], dy = (double)P.y - g.T[1], dz = (double)P.z - g.T[2];
-    const double F2 = fabs(g.rz[0] * dx + g.rz[1] * dy + g.rz[2] * dz), nP = sqrt(dx * dx + dy * dy + dz * dz);
-    const double iw = F2 / fabs(g.qz);
-    const double LB = F2 * (WR + 1) / (nP / fmax(iw, 1e-300) + (WR + 1));
-    const double coord = fmax(fmax(fabs((double)P.x), fabs((double)P.y)), fabs((double)P.z)) + nP;
-    const double lim = LB * (1.0 - 1e-5) - 4e-7 * coord;
-    const float range = (lim > 0.0) ? (float)(lim * lim * (1.0 - 1e-6)) : 0.0f; // (k_sor_window_wave's bound, the same expressions)
-    if (!(range > 0.0f && isfinite(range))) { // uniform
+    WinCand cand;
+    float h2;
+    int M;
+    if (!win_clip(lat, cell_of[pt], g, WR, cand, h2, M)) { // uniform
         if (threadIdx.x == 0) undecided[qi] = 1u;
         return;
     }
-    const float h2 = __uint_as_float(__float_as_uint(range) - 1u);
-    const int x0 = max(cx - WR, 0), x1 = min(cx + WR, g.gw - 1), y0 = max(cy - WR, 0), y1 = min(cy + WR, g.gh - 1);
-    const int ncx = x1 - x0 + 1, M = ncx * (y1 - y0 + 1);
-    const float4 *base = lat + (size_t)y0 * g.gw + x0;
-    const int gw = g.gw;
-    const unsigned int ncx_inv = 0xffffffffu / (unsigned int)ncx + 1u;
-    auto cand = [&](int c) -> float {
-        const int r = ncx > 1 ? (int)__umulhi((unsigned int)c, ncx_inv) : c, col = c - r * ncx;
-        const float4 o = base[(size_t)r * gw + col];
-        return fdist2(P.x, P.y, P.z, o.x, o.y, o.z);
-    };
     const float inf = __uint_as_float(0x7f800000u);
     const unsigned long long lt = (1ull << lane) - 1ull;
     int Kw = 0;
@@ -903,51 +849,46 @@ __global__ __launch_bounds__(256) void k_sor_window_wg(const float4 *__restrict_
     if (lane == 0) dist[pt] = (float)((sum + (double)(want - less) * (double)sqrtf(tau)) / mean_k);
 }
 
-void launch_cloud_lattice(const uint8_t *flags, const int64_t *row_offset, int W, int XL, int XR, int YL, int YR, const double *xyz, int64_t n, float4 *lat,
-                          unsigned int *cell_of, hipStream_t st) {
-    const int gw = XR - XL + 1 + 2 * WIN_PAD, gh = YR - YL + 1 + 2 * WIN_PAD;
-    (void)hipMemsetD32Async((hipDeviceptr_t)lat, 0x7fc00000, (size_t)4 * gw * gh, st);
-    hipLaunchKernelGGL(k_cloud_lattice, dim3((unsigned)(YR - YL + 1)), dim3(256), 0, st, flags, row_offset, W, XL, XR, YL, xyz, n, gw, lat, cell_of);
+size_t cloud_lattice_bytes(int XL, int XR, int YL, int YR) {
+    return sizeof(float4) * (size_t)(XR - XL + 1 + 2 * WIN_PAD) * (size_t)(YR - YL + 1 + 2 * WIN_PAD);
 }
-static WinGeom win_geom(int XL, int XR, int YL, int YR, double qz, const double *R, const double *T) {
+static WinGeom win_geom(const FilterLattice &L) {
     WinGeom g;
-    g.gw = XR - XL + 1 + 2 * WIN_PAD;
-    g.gh = YR - YL + 1 + 2 * WIN_PAD;
-    g.qz = qz;
+    g.gw = L.XR - L.XL + 1 + 2 * WIN_PAD;
+    g.gh = L.YR - L.YL + 1 + 2 * WIN_PAD;
+    g.qz = L.qz;
     for (int i = 0; i < 3; i++) {
-        g.rz[i] = R[3 * i + 2];
-        g.T[i] = T[i];
+        g.rz[i] = L.R[3 * i + 2];
+        g.T[i] = L.T[i];
     }
     return g;
 }
+static void launch_cloud_lattice(const FilterLattice &L, const WinGeom &g, int64_t n, float4 *lat, unsigned int *cell_of, hipStream_t st) {
+    (void)hipMemsetD32Async((hipDeviceptr_t)lat, 0x7fc00000, (size_t)4 * g.gw * g.gh, st);
+    hipLaunchKernelGGL(k_cloud_lattice, dim3((unsigned)(L.YR - L.YL + 1)), dim3(256), 0, st, L.flags, L.row_offset, L.W, L.XL, L.XR, L.YL, L.xyz64, n, g.gw, lat,
+                       cell_of);
+}
 // the list form over nq listed queries at radius 24 or 40: dist (per point) / undecided (per list entry)
-void launch_sor_window_list(const float4 *lat, const unsigned int *cell_of, int XL, int XR, int YL, int YR, double qz, const double *R, const double *T, int mean_k,
-                            int radius, const unsigned int *list, int nq, float *dist, unsigned int *undecided, hipStream_t st) {
+static void launch_sor_window_list(const float4 *lat, const unsigned int *cell_of, const WinGeom &g, int mean_k, int radius, const unsigned int *list, int nq,
+                                   float *dist, unsigned int *undecided, hipStream_t st) {
     if (nq <= 0) return;
-    const WinGeom g = win_geom(XL, XR, YL, YR, qz, R, T);
-    const dim3 grid((unsigned)((nq + 255) / 256));
-    if (radius <= 24) hipLaunchKernelGGL((k_sor_window_list<24, 7>), grid, dim3(256), 0, st, lat, cell_of, g, mean_k, list, nq, dist, undecided);
-    else hipLaunchKernelGGL((k_sor_window_list<40, 9>), grid, dim3(256), 0, st, lat, cell_of, g, mean_k, list, nq, dist, undecided);
+    if (radius <= 24) hipLaunchKernelGGL((k_sor_window_list<24, 7>), blocks_for(nq), dim3(256), 0, st, lat, cell_of, g, mean_k, list, nq, dist, undecided);
+    else hipLaunchKernelGGL((k_sor_window_list<40, 9>), blocks_for(nq), dim3(256), 0, st, lat, cell_of, g, mean_k, list, nq, dist, undecided);
 }
 // the wave form over nq listed queries at any radius: dist (per point) / undecided (per list entry)
-void launch_sor_window_wave(const float4 *lat, const unsigned int *cell_of, int XL, int XR, int YL, int YR, double qz, const double *R, const double *T, int mean_k,
-                            int radius, const unsigned int *list, int nq, float *dist, unsigned int *undecided, hipStream_t st, int wg_max = 2048) {
+static void launch_sor_window_wave(const float4 *lat, const unsigned int *cell_of, const WinGeom &g, int mean_k, int radius, const unsigned int *list, int nq,
+                                   float *dist, unsigned int *undecided, hipStream_t st, int wg_max) {
     if (nq <= 0) return;
-    const WinGeom g = win_geom(XL, XR, YL, YR, qz, R, T);
     if (nq <= wg_max) // (few enough to leave most of the chip idle at a wave each: four waves per query)
         hipLaunchKernelGGL(k_sor_window_wg, dim3((unsigned)nq), dim3(256), 0, st, lat, cell_of, g, mean_k, radius, list, nq, dist, undecided);
     else
         hipLaunchKernelGGL(k_sor_window_wave, dim3((unsigned)((nq + 3) / 4)), dim3(256), 0, st, lat, cell_of, g, mean_k, radius, list, nq, dist, undecided);
 }
-size_t cloud_lattice_bytes(int XL, int XR, int YL, int YR) {
-    return sizeof(float4) * (size_t)(XR - XL + 1 + 2 * WIN_PAD) * (size_t)(YR - YL + 1 + 2 * WIN_PAD);
-}
 // the window pass over the whole lattice: dist / undecided (one entry per cloud point; undecided pre-set to 1 by the caller);
 // tile_step > 1 + probe_cnt: the sparse probe (see k_sor_window)
-void launch_sor_window(const float4 *lat, int XL, int XR, int YL, int YR, double qz, const double *R, const double *T, int mean_k, int radius, float *dist,
-                       unsigned int *undecided, hipStream_t st, int tile_step = 1, unsigned int *probe_cnt = nullptr) {
-    const WinGeom g = win_geom(XL, XR, YL, YR, qz, R, T);
-    const int tx = (XR - XL + 1 + WIN_TX - 1) / WIN_TX, ty = (YR - YL + 1 + WIN_TY - 1) / WIN_TY;
+static void launch_sor_window(const float4 *lat, const WinGeom &g, int mean_k, int radius, float *dist, unsigned int *undecided, hipStream_t st,
+                              int tile_step = 1, unsigned int *probe_cnt = nullptr) {
+    const int tx = (g.gw - 2 * WIN_PAD + WIN_TX - 1) / WIN_TX, ty = (g.gh - 2 * WIN_PAD + WIN_TY - 1) / WIN_TY; // tiles over the margin's box
     const dim3 grid((unsigned)((tx + tile_step - 1) / tile_step), (unsigned)((ty + tile_step - 1) / tile_step));
 #define WIN_LAUNCH(R_)                                                                                                                     \
     do {                                                                                                                                   \
@@ -1094,11 +1035,6 @@ __device__ __forceinline__ int low_bit_exp(float v) { // exponent of the lowest 
     if (e == 0) return -149 + (__ffs((int)m) - 1);           // subnormal
     return (e - 150) + (m ? __ffs((int)m) - 1 : 23);
 }
-struct DistStats {
-    double sum, sq_sum;
-    int q_sum, q_sq;
-    int bad; // a negative or non-finite distance (cannot happen; makes the host take the sequential path)
-};
 __global__ __launch_bounds__(256) void k_dist_stats(const float *__restrict__ dist, int64_t n, DistStats *__restrict__ out) {
     double s = 0.0, s2 = 0.0;
     int q1 = 0x7fffffff, q2 = 0x7fffffff, bad = 0;
@@ -1133,16 +1069,6 @@ __global__ __launch_bounds__(256) void k_dist_stats(const float *__restrict__ di
         atomicMin(&out->q_sq, min(min(s_i[0][1], s_i[1][1]), min(s_i[2][1], s_i[3][1])));
         if (s_i[0][2] | s_i[1][2] | s_i[2][2] | s_i[3][2]) atomicOr(&out->bad, 1);
     }
-}
-
-// every `step`-th point into a small buffer (the robust extent's sample)
-__global__ void k_sample_points(const float *__restrict__ xyz, int64_t step, int S, float *__restrict__ out) {
-    const int s = blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= S) return;
-    const size_t i = (size_t)s * (size_t)step;
-    out[3 * s] = xyz[3 * i];
-    out[3 * s + 1] = xyz[3 * i + 1];
-    out[3 * s + 2] = xyz[3 * i + 2];
 }
 
 __global__ void k_keep_flags(const float *__restrict__ dist, int64_t n, double thr, unsigned int *__restrict__ flag) {
@@ -1292,201 +1218,6 @@ __global__ void k_f64_to_f32x3(const double *__restrict__ src, int64_t n3, float
     if (i < n3) dst[i] = (float)src[i]; // InsertPoint: pcl::PointXYZ(double, double, double) -> float (:61)
 }
 
-// order-preserving float <-> uint map for atomicMin / atomicMax
-__host__ __device__ inline unsigned int float_to_ord(float f) {
-    unsigned int u;
-    memcpy(&u, &f, 4);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__host__ __device__ inline float ord_to_float(unsigned int o) {
-    const unsigned int u = (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o;
-    float f;
-    memcpy(&f, &u, 4);
-    return f;
-}
-__global__ void k_bbox(const float *__restrict__ xyz, int64_t n, unsigned int *__restrict__ bb) {
-    unsigned int lo[3] = {0xffffffffu, 0xffffffffu, 0xffffffffu}, hi[3] = {0u, 0u, 0u};
-    unsigned int nfin = 0;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        if (!(isfinite(xyz[3 * i]) && isfinite(xyz[3 * i + 1]) && isfinite(xyz[3 * i + 2]))) continue;
-        nfin++;
-        for (int a = 0; a < 3; a++) {
-            const unsigned int o = float_to_ord(xyz[3 * i + a]);
-            lo[a] = min(lo[a], o);
-            hi[a] = max(hi[a], o);
-        }
-    }
-    // one set of atomics per WORKGROUP (same-address atomics retire at ~88 per microsecond: per wave they were the kernel)
-    __shared__ unsigned int s_r[4][7];
-    for (int o = 32; o > 0; o >>= 1) nfin += (unsigned int)__shfl_xor((int)nfin, o);
-    for (int a = 0; a < 3; a++)
-        for (int o = 32; o > 0; o >>= 1) {
-            lo[a] = min(lo[a], (unsigned int)__shfl_xor((int)lo[a], o));
-            hi[a] = max(hi[a], (unsigned int)__shfl_xor((int)hi[a], o));
-        }
-    if ((threadIdx.x & 63) == 0) {
-        unsigned int *r = s_r[threadIdx.x >> 6];
-        r[0] = lo[0], r[1] = lo[1], r[2] = lo[2], r[3] = hi[0], r[4] = hi[1], r[5] = hi[2], r[6] = nfin;
-    }
-    __syncthreads();
-    if (threadIdx.x < 7) {
-        const int a = threadIdx.x;
-        unsigned int v = s_r[0][a];
-        for (int w = 1; w < (int)(blockDim.x >> 6); w++) v = a < 3 ? min(v, s_r[w][a]) : (a < 6 ? max(v, s_r[w][a]) : v + s_r[w][a]);
-        if (a < 3) atomicMin(&bb[a], v);
-        else if (a < 6) atomicMax(&bb[a], v);
-        else if (v) atomicAdd(&bb[6], v);
-    }
-}
-
-// ------------------------------------------------------------------------------------------------ host side
-// Grow-only device arena owned by the context: one hipMalloc sized for the cloud at hand instead of ~25 hipMalloc /
-// hipFree pairs per call (hipFree synchronises the device).  Stack discipline: mark() / release().
-struct FilterArena {
-    char *base = nullptr;
-    size_t cap = 0, off = 0;
-    void *h_pinned = nullptr; // small pinned staging block (samples, counters, statistics)
-    bool failed = false;
-    template <typename T>
-    T *get(size_t n) {
-        const size_t bytes = (n * sizeof(T) + 255) & ~(size_t)255;
-        if (off + bytes > cap) {
-            failed = true;
-            return nullptr;
-        }
-        T *p = (T *)(base + off);
-        off += bytes;
-        return p;
-    }
-};
-FilterArena *filter_arena_create() { return new FilterArena(); }
-void filter_arena_destroy(FilterArena *a) {
-    if (!a) return;
-    if (a->base) (void)hipFree(a->base);
-    if (a->h_pinned) (void)hipHostFree(a->h_pinned);
-    delete a;
-}
-#define FA_PINNED_BYTES (3 * 8192 * sizeof(float) + 1024)
-// room for `bytes` from offset 0 (contents are scratch: nothing survives a call)
-int filter_arena_reserve(FilterArena *a, size_t bytes) {
-    if (!a->h_pinned && hipHostMalloc(&a->h_pinned, FA_PINNED_BYTES, hipHostMallocDefault) != hipSuccess) return RSM_E_NOMEM;
-    a->off = 0;
-    a->failed = false;
-    if (bytes <= a->cap) return RSM_OK;
-    // grows geometrically: hipFree synchronises the whole device, other contexts' pairs in flight included
-    const size_t want = std::max(bytes, a->cap + a->cap / 2);
-    if (a->base) (void)hipFree(a->base);
-    a->base = nullptr;
-    a->cap = 0;
-    if (hipMalloc((void **)&a->base, want) == hipSuccess) a->cap = want;
-    else if (hipMalloc((void **)&a->base, bytes) == hipSuccess) a->cap = bytes;
-    else return RSM_E_NOMEM;
-    return RSM_OK;
-}
-size_t filter_arena_bytes(int64_t n) { // upper bound of one filter call's scratch for an n-point cloud (callers add their own buffers)
-    return (size_t)n * 112 + (filter_max_cells(n) + 64) * sizeof(int2) + std::min<size_t>((size_t)64 << 20, ((size_t)32 << 20) + (size_t)n * 16) /* sort / scan temporaries, the exhaustive search's 16 MB of histograms */;
-}
-void *filter_arena_alloc(FilterArena *a, size_t bytes) { return a->get<char>(bytes); }
-void *filter_arena_host(FilterArena *a) { return a->h_pinned; } // (the first 3 * 8192 floats stage the filter's samples: free outside its call)
-
-namespace {
-// robust grid: extents from the 1 % .. 99 % quantiles of a sample (far outliers must not set the cell size)
-bool sample_extent(FilterArena *A, const float *d_xyz, int64_t n, hipStream_t st, float lo[3], float hi[3]) {
-    const int S = (int)std::min<int64_t>(n, 8192);
-    const size_t mark = A->off;
-    float *d_s = A->get<float>((size_t)3 * S);
-    float *h = (float *)A->h_pinned;
-    if (!d_s) return false;
-    hipLaunchKernelGGL(k_sample_points, dim3((S + 255) / 256), dim3(256), 0, st, d_xyz, n / S, S, d_s);
-    if (hipMemcpyAsync(h, d_s, sizeof(float) * 3 * (size_t)S, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-        return false;
-    A->off = mark;
-    for (int a = 0; a < 3; a++) {
-        std::vector<float> v;
-        for (int s = 0; s < S; s++)
-            if (std::isfinite(h[3 * (size_t)s]) && std::isfinite(h[3 * (size_t)s + 1]) && std::isfinite(h[3 * (size_t)s + 2])) v.push_back(h[3 * (size_t)s + a]);
-        if (v.empty()) v.push_back(0.0f);
-        const size_t q_lo = (size_t)(0.01 * (v.size() - 1)), q_hi = (size_t)(0.99 * (v.size() - 1)); // (two selections: a full sort of the
-        std::nth_element(v.begin(), v.begin() + q_lo, v.end());                                        // three samples took 0.8 ms of every call)
-        lo[a] = v[q_lo];
-        std::nth_element(v.begin() + q_lo, v.begin() + q_hi, v.end());
-        hi[a] = v[q_hi];
-    }
-    return true;
-}
-} // namespace
-
-
-// sorts the n points of d_xyz by the key of a grid for the search radius h (cell edge grid_edge(h), a hair wider than h: see
-// cell_of) over the box [bb_lo, bb_hi] (points outside fall into the border cells: clamping is non-expansive, so two points within
-// h of each other still sit in adjacent cells); nv = finite points (they sort first).  Arena space stays allocated until the
-// caller releases its mark.
-int build_grid(FilterArena *A, const float *d_xyz, int64_t n, int64_t nv, float h, const float bb_lo[3], const float bb_hi[3],
-                      hipStream_t st, FilterGridDev &G) {
-    const double H = grid_edge(h);
-    G.g.inv_h = 1.0 / H;
-    auto dim = [&](int a) { return (int)std::min<double>(1 << 20, std::max<double>(1.0, floor(((double)bb_hi[a] - (double)bb_lo[a]) / H) + 1.0)); };
-    int ax[3] = {0, 1, 2};
-    std::sort(ax, ax + 3, [&](int a, int b) { return dim(a) != dim(b) ? dim(a) > dim(b) : a < b; }); // most cells first = fastest key digit
-    G.g.p0 = ax[0], G.g.p1 = ax[1], G.g.p2 = ax[2];
-    G.g.ox = (double)bb_lo[ax[0]], G.g.oy = (double)bb_lo[ax[1]], G.g.oz = (double)bb_lo[ax[2]];
-    G.g.nx = dim(ax[0]), G.g.ny = dim(ax[1]), G.g.nz = dim(ax[2]);
-    unsigned long long *k1 = A->get<unsigned long long>((size_t)n), *k2 = A->get<unsigned long long>((size_t)n);
-    unsigned int *v1 = A->get<unsigned int>((size_t)n), *v2 = A->get<unsigned int>((size_t)n);
-    G.sxyz = A->get<float4>((size_t)n);
-    if (!k1 || !k2 || !v1 || !v2 || !G.sxyz) return RSM_E_NOMEM;
-    const unsigned blocks = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL(k_cell_keys, dim3(blocks), dim3(256), 0, st, d_xyz, n, G.g, k1, v1);
-    const double ncell = (double)G.g.nx * G.g.ny * G.g.nz;
-    int key_bits = 1;
-    while (key_bits < 64 && ncell > (double)(1ull << key_bits)) key_bits++;
-    key_bits = 64; // non-finite points carry the key ~0: all bits take part
-    size_t tmp_bytes = 0;
-    if (rocprim::radix_sort_pairs(nullptr, tmp_bytes, k1, k2, v1, v2, (size_t)n, 0, key_bits, st) != hipSuccess) return RSM_E_HIP;
-    void *tmp = A->get<uint8_t>(tmp_bytes);
-    if (!tmp) return RSM_E_NOMEM;
-    if (rocprim::radix_sort_pairs(tmp, tmp_bytes, k1, k2, v1, v2, (size_t)n, 0, key_bits, st) != hipSuccess) return RSM_E_HIP;
-    hipLaunchKernelGGL(k_gather_sorted, dim3(blocks), dim3(256), 0, st, d_xyz, v2, n, G.sxyz);
-    G.keys = k2;
-    G.vals = v2;
-    G.table = nullptr;
-    G.table_kind = 0;
-    const double nrow = (double)G.g.ny * G.g.nz;
-    const double max_cells = (double)filter_max_cells(n);
-    if (nv > 0 && (ncell <= max_cells || nrow <= max_cells)) {
-        G.table_kind = ncell <= max_cells ? 1 : 2;
-        const size_t nc = (size_t)(G.table_kind == 1 ? ncell : nrow);
-        G.table = A->get<int2>(nc);
-        if (!G.table) return RSM_E_NOMEM;
-        if (hipMemsetAsync(G.table, 0, sizeof(int2) * nc, st) != hipSuccess) return RSM_E_HIP;
-        hipLaunchKernelGGL(k_cell_table, dim3((unsigned)((nv + 255) / 256)), dim3(256), 0, st, k2, (int)nv,
-                           (unsigned long long)(G.table_kind == 1 ? 1 : G.g.nx), G.table);
-    }
-    return RSM_OK;
-}
-
-// the bounding box and the finite-point count the filter computes first (k_bbox), for the other cloud steps (k_mls.hip)
-int cloud_bbox(FilterArena *A, const float *d_xyz, int64_t n, hipStream_t st, float lo[3], float hi[3], int64_t *nv) {
-    *nv = 0;
-    for (int a = 0; a < 3; a++) lo[a] = hi[a] = 0.0f;
-    if (n <= 0) return RSM_OK;
-    if (!A->h_pinned) return RSM_E_STATE;
-    unsigned int *d_bb = A->get<unsigned int>(8);
-    if (!d_bb) return RSM_E_NOMEM;
-    unsigned int *h_bb = (unsigned int *)((char *)A->h_pinned + 3 * 8192 * sizeof(float));
-    const unsigned int init[7] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u, 0u};
-    memcpy(h_bb, init, sizeof init);
-    if (hipMemcpyAsync(d_bb, h_bb, sizeof init, hipMemcpyHostToDevice, st) != hipSuccess) return RSM_E_HIP;
-    hipLaunchKernelGGL(k_bbox, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 1024)), dim3(256), 0, st, d_xyz, n, d_bb);
-    if (hipMemcpyAsync(h_bb, d_bb, sizeof init, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return RSM_E_HIP;
-    *nv = h_bb[6];
-    for (int a = 0; a < 3 && *nv; a++) {
-        lo[a] = ord_to_float(h_bb[a]);
-        hi[a] = ord_to_float(h_bb[3 + a]);
-    }
-    return RSM_OK;
-}
-
 // (pixel-window pass) every finite point starts undecided; the others take no part in the searches (distance 0, as PCL)
 __global__ void k_finite_flags(const float *__restrict__ xyz, int64_t n, unsigned int *__restrict__ flag, unsigned int *__restrict__ iota) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1514,6 +1245,322 @@ static void launch_knn(const float *d_xyz, const FilterGridDev &G, int nv, float
         hipLaunchKernelGGL(k_sor_knn<0>, grid, dim3(256), 0, st, d_xyz, G.sxyz, G.keys, G.table, nv, G.g, h * h, mean_k, queries, nq, d_dist, d_cnt);
 }
 
+// ------------------------------------------------------------------------------------------------ host side
+namespace {
+// what the steps of one filter_cloud_device call share
+struct FilterRun {
+    FilterArena *A;
+    hipStream_t st;
+    const float *d_xyz;
+    int64_t n, nv = 0; // points, finite points: only they take part in the searches (PCL: the k-d tree skips the others)
+    int mean_k;
+    const FilterLattice *pre;
+    FilterRoute *route;
+    float flo[3], fhi[3]; // the exact bounding box of the finite points (a sample's extremes are not the cloud's)
+    int *d_cnt = nullptr;          // 4 ints
+    DistStats *d_stats = nullptr;
+    float *d_dist = nullptr;       // n each, from here on
+    unsigned int *d_redo = nullptr, *d_redo2 = nullptr, *d_flag = nullptr, *d_pos = nullptr;
+    const unsigned int *queries = nullptr; // the queries still undecided: d_redo, d_redo2, or the first grid level's point order
+    int nq = 0;
+    size_t mark = 0, mark_lat = 0; // the arena before the searches' buffers / behind the lattice copy
+    WinGeom wg;                    // (with pre)
+    float4 *lat = nullptr;         // the lattice copy and every point's place in it
+    unsigned int *cell_of = nullptr;
+    bool lat_kept = false;                    // no grid level has taken the lattice copy's arena space: the normals may use it
+    bool prepassed = false, wave_done = false; // the tile pass ran / the wave passes ran
+    float h_floor = 0.0f;                     // the ladder need not start below this search radius
+    ScanTmp win_scan;                         // the tile pass's scan temporary, which the list and wave passes use again
+    FilterGridDev G;                          // the last grid level
+    int64_t lat_cells() const { return prepassed ? (int64_t)wg.gw * (int64_t)wg.gh : 0; }
+    void rewind() { A->off = lat_kept ? mark_lat : mark; }
+};
+
+// Of the `count` queries in R.queries, those whose flag is still up become the list (in order, in the buffer that is not being read)
+// and R.nq their number: one host round trip.
+int compact_undecided(FilterRun &R, int count, ScanTmp *keep = nullptr) {
+    unsigned int *dst = (R.queries == R.d_redo) ? R.d_redo2 : R.d_redo;
+    const int s = scan_u32(*R.A, R.d_flag, R.d_pos, (size_t)count, R.st, keep);
+    if (s != RSM_OK) return s;
+    hipLaunchKernelGGL(k_compact_list, blocks_for(count), dim3(256), 0, R.st, R.queries, R.d_flag, R.d_pos, count, dst, R.d_cnt);
+    int *h_cnt = R.A->pin->cnt;
+    DEVCHK(hipMemcpyAsync(h_cnt, R.d_cnt, sizeof(int), hipMemcpyDeviceToHost, R.st));
+    DEVCHK(hipStreamSynchronize(R.st));
+    R.queries = dst;
+    R.nq = h_cnt[0];
+    return RSM_OK;
+}
+
+// Step 2: the lattice copy (every finite point flagged undecided, d_redo2 = 0 .. n - 1) and the tile pass's window radius.
+// Which window?  pre->radius > 0: the caller's; 0: the smallest of 7 / 12 / 16 pixels that decides >= 85 % of a sparse sample of the
+// tiles (every 6th in x and y: ~3 % of the queries) -- a thin sheet (depth noise below the lateral spacing, the reference's rig
+// geometry) is decided inside 15 x 15 pixels, a thick one (the synthetic bench rig: a disparity step of 0.05 pixel is 6 lateral
+// spacings deep) needs 33 x 33; nothing decides enough: no window pass (*radius = 0).
+int lattice_and_probe(FilterRun &R, int *radius_out) {
+    const FilterLattice &L = *R.pre;
+    R.lat = R.A->get<float4>(cloud_lattice_bytes(L.XL, L.XR, L.YL, L.YR) / sizeof(float4));
+    R.cell_of = R.A->get<unsigned int>((size_t)R.n);
+    if (!R.lat || !R.cell_of) return RSM_E_NOMEM;
+    R.lat_kept = true;
+    R.mark_lat = R.A->off;
+    hipLaunchKernelGGL(k_finite_flags, blocks_for(R.n), dim3(256), 0, R.st, R.d_xyz, R.n, R.d_flag, R.d_redo2);
+    launch_cloud_lattice(L, R.wg, R.n, R.lat, R.cell_of, R.st);
+    int radius = L.radius;
+    if (radius <= 0) {
+        unsigned int *d_pc = (unsigned int *)R.d_cnt, *h_pc = (unsigned int *)R.A->pin->cnt; // (4 ints each)
+        const int cand[3] = {7, 12, 16};
+        for (int ci = 0; ci < 3 && radius <= 0; ci++) {
+            DEVCHK(hipMemsetAsync(d_pc, 0, 3 * sizeof(unsigned int), R.st));
+            launch_sor_window(R.lat, R.wg, R.mean_k, cand[ci], R.d_dist, R.d_flag, R.st, 6, d_pc);
+            DEVCHK(hipMemcpyAsync(h_pc, d_pc, 3 * sizeof(unsigned int), hipMemcpyDeviceToHost, R.st));
+            DEVCHK(hipStreamSynchronize(R.st));
+            const double best = h_pc[0] ? (double)h_pc[1] / (double)h_pc[0] : 0.0;
+            if (best >= 0.85 || (ci == 2 && best >= 0.5)) {
+                radius = cand[ci];
+                // every query this window leaves over has its (k+1)-th neighbour beyond the window's bound (closer points
+                // cannot hide outside it): the ladder need not start below that scale
+                float sum_lim;
+                memcpy(&sum_lim, &h_pc[2], sizeof sum_lim);
+                // (1.25 x the mean bound: a level at the bound itself would decide almost none of them)
+                const float hf = 1.25f * sum_lim / (float)h_pc[0];
+                if (std::isfinite(hf)) R.h_floor = hf;
+            }
+        }
+    }
+    if (L.radius_out) *L.radius_out = radius > 0 ? radius : 0;
+    *radius_out = radius;
+    return RSM_OK;
+}
+
+// Step 3: the tile pass over the whole lattice; what it cannot decide becomes the first query list.
+int tile_pass(FilterRun &R, int radius) {
+    launch_sor_window(R.lat, R.wg, R.mean_k, radius, R.d_dist, R.d_flag, R.st);
+    R.queries = R.d_redo2;
+    const int s = compact_undecided(R, (int)R.n, &R.win_scan);
+    if (s != RSM_OK) return s;
+    R.prepassed = true;
+    if (R.pre->tile_left_out) *R.pre->tile_left_out = R.nq;
+    return RSM_OK;
+}
+
+// Step 4: what a window below 24 pixels leaves over (a thick sheet's points whose neighbours spread wider: scattered, a seventh
+// of C2's cloud) gets the 49 x 49 window a thread each, straight from the lattice copy (k_sor_window_list); what THAT
+// leaves -- the points within a dozen pixels of the mask's border and of depth edges, whose neighbours lie on one
+// side: 1.6 % of C2's cloud, the queries that cost the grid ladder most (coarse levels: tens of thousands of
+// candidates in the 27 cells of each) -- an 81 x 81 window; only the rest (holes, outliers, islands) goes on.
+// *last: in, the tile pass's radius; out, the widest window run.
+int list_passes(FilterRun &R, int *last) {
+    const FilterLattice &L = *R.pre;
+    const int radii[2] = {24, 40};
+    for (int pass = 0; pass < 2 && R.nq > 0; pass++) {
+        if (radii[pass] <= *last || !((L.list_pass >> pass) & 1)) continue;
+        if ((L.list_pass >> (3 + pass)) & 1) // (A/B: the wave form at this radius instead of the thread form)
+            launch_sor_window_wave(R.lat, R.cell_of, R.wg, R.mean_k, radii[pass], R.queries, R.nq, R.d_dist, R.d_flag, R.st, L.wg_max);
+        else
+            launch_sor_window_list(R.lat, R.cell_of, R.wg, R.mean_k, radii[pass], R.queries, R.nq, R.d_dist, R.d_flag, R.st);
+        const int s = compact_undecided(R, R.nq, &R.win_scan);
+        if (s != RSM_OK) return s;
+        *last = radii[pass]; // (the ladder keeps its start: what is left now is few, and a level whose 27 cells hold tens of
+                             // thousands of candidates costs a wave-per-query search milliseconds however few the queries)
+    }
+    return RSM_OK;
+}
+
+// Step 5: what the list passes leave (C2: 564 of 5.5 M -- mask corners, hole rims, outliers): a wave each over windows of 80, 160,
+// 320 ... pixels of the lattice copy, while there are few enough for that to be cheaper than a grid level (a level is a
+// sort of the whole cloud plus, for these queries, 27 cells of tens of thousands of candidates each: 4 ms a level on C2).
+int wave_passes(FilterRun &R, int last) {
+    const FilterLattice &L = *R.pre;
+    const int span = std::max(L.XR - L.XL, L.YR - L.YL) + 1;
+    for (int wr = std::max(80, 2 * last); R.nq > 0 && R.nq <= 65536; wr *= 2) {
+        launch_sor_window_wave(R.lat, R.cell_of, R.wg, R.mean_k, wr, R.queries, R.nq, R.d_dist, R.d_flag, R.st, L.wg_max);
+        const int s = compact_undecided(R, R.nq, &R.win_scan);
+        if (s != RSM_OK) return s;
+        if (wr >= span) break; // the window already covers the whole box: what is left has fewer than k + 1 points within its bound
+    }
+    R.wave_done = true;
+    return RSM_OK;
+}
+
+// Step 6, the grid ladder.
+// first cell edge: ~sqrt(k + 1) point spacings of a surface patch whose area is the product of the two largest
+// robust extents; queries that cannot be decided inside their 27 cells (fewer than k + 1 points within h: thick or
+// sparse parts of the cloud, patch corners, isolated points) are retried on a grid with twice the edge; what is left
+// after KNN_LEVELS grids (or once only a handful remain) is searched against all points by the whole chip.
+// One cell edge does not fit a whole cloud: a perspective depth map is 25 times denser (per unit of space) in its near
+// part than in its far part (C2: 1.25 vs 6 units between neighbours), and the surface estimate above is off for a deep
+// or thick one.  The search therefore runs over a ladder of grids from fine to coarse, h doubling: a query is decided
+// at the first level whose 27 cells hold its k + 1 nearest (there its candidates number a few hundred whatever the
+// local density); an undecided attempt costs one table lookup and one count over the few candidates a too-fine grid
+// offers.  Every level re-sorts the points (0.65 ms for 5.5 M): cheap next to one query pass with a wrong h
+// (a single level at the surface estimate ran the near part's queries over ~50 000 candidates each: 390 ms).
+// The ladder starts one octave below the surface estimate (on C2 two octaves below decides 10 % of the queries for
+// a quarter of the search time, three octaves below nothing).
+// All of it only when a grid is built at all: the cloud of a matched pair is searched on its pixel lattice and the sample, its
+// round trip and its quantiles stay out of the call.
+int grid_ladder(FilterRun &R) {
+    const int KNN_LEVELS = 12;
+    float lo[3], hi[3], glo[3], ghi[3];
+    if (!sample_extent(R.A, R.d_xyz, R.n, R.st, lo, hi)) return RSM_E_HIP;
+    double e[3] = {(double)hi[0] - lo[0], (double)hi[1] - lo[1], (double)hi[2] - lo[2]};
+    std::sort(e, e + 3);
+    const double area = std::max(e[2] * e[1], 1e-12), spacing = sqrt(area / (0.98 * 0.98 * 0.98 * (double)std::max<int64_t>(R.nv, 1)));
+    float h = (float)(spacing * sqrt((double)(R.mean_k + 1)));
+    if (!(h > 0.0f) || !std::isfinite(h)) h = 1.0f;
+    // the grid box: the robust extent grown by a few cells, inside the exact bounding box (far outliers are clamped
+    // into the border cells instead of blowing up the cell count)
+    for (int a = 0; a < 3; a++) {
+        glo[a] = std::max(R.flo[a], lo[a] - 4.0f * h);
+        ghi[a] = std::min(R.fhi[a], hi[a] + 4.0f * h);
+        if (!(ghi[a] >= glo[a])) ghi[a] = glo[a];
+    }
+    h *= 0.5f;
+    if (R.h_floor > h) h = R.h_floor;
+    if (R.route && R.route->h0 > 0.0f) h = R.route->h0; // (a level decides a query only with all of its k + 1 nearest in hand: any start gives the same bits)
+    for (int level = 0; level < KNN_LEVELS && R.nq > 0; level++, h *= 2.0f) {
+        R.A->off = R.mark; // the previous level's grid is done (its kernels are ordered before this level's on the stream)
+        R.lat_kept = false; // (the grid takes the lattice copy's arena space: R.lat and R.cell_of dangle from here on, only lat_kept says so)
+        FilterGridDev &G = R.G;
+        int s = build_grid(R.A, R.d_xyz, R.n, R.nv, h, glo, ghi, R.st, G);
+        if (s != RSM_OK) return s;
+        if (R.route) {
+            FilterRoute *route = R.route;
+            if (level == 0) {
+                route->h = h;
+                route->kind0 = G.table_kind;
+                const int nk[3] = {G.g.nx, G.g.ny, G.g.nz}, pk[3] = {G.g.p0, G.g.p1, G.g.p2};
+                for (int a = 0; a < 3; a++) {
+                    route->origin[a] = glo[a];
+                    route->cells[pk[a]] = nk[a];
+                }
+            }
+            route->levels++;
+            route->kinds |= 1 << G.table_kind;
+        }
+        if (level == 0 && !R.prepassed) R.queries = G.vals; // every point, in grid order (coherent waves)
+        launch_knn(R.d_xyz, G, (int)R.nv, h, R.mean_k, R.queries, R.nq, R.d_dist, R.d_flag, R.st);
+        if ((s = compact_undecided(R, R.nq)) != RSM_OK) return s; // undecided queries -> the next level's list, in order
+        if (R.nq <= 48) break; // cheaper to finish against all points than to sort again (a coarser level costs ~0.8 ms, the
+                               // whole-chip search ~25 us per query)
+    }
+    return RSM_OK;
+}
+
+// Step 7: the queries still left against ALL points (k_xq_*), read from any array that holds every finite point once: the last grid
+// level's sorted copy, still in the arena, or -- no level ran -- the lattice copy (its empty pixels are NaN: never below any threshold)
+int whole_chip_search(FilterRun &R, bool over_lattice) {
+    const int XQ_BATCH = 2048; // queries per round (their histograms: 16 MB)
+    XqState *d_xq = R.A->get<XqState>((size_t)XQ_BATCH);
+    int *d_hist = R.A->get<int>((size_t)XQ_BATCH * 2048);
+    if (!d_xq || !d_hist) return RSM_E_NOMEM;
+    DEVCHK(hipMemsetAsync(d_hist, 0, sizeof(int) * (size_t)XQ_BATCH * 2048, R.st));
+    const int shifts[3] = {20, 9, 0}, widths[3] = {11, 11, 9};
+    const float4 *arr = over_lattice ? R.lat : R.G.sxyz;
+    const int arr_n = over_lattice ? (int)R.lat_cells() : (int)R.nv;
+    if (!arr || R.lat_cells() >= (1ll << 31)) return RSM_E_INVALID;
+    for (int q0 = 0; q0 < R.nq; q0 += XQ_BATCH) {
+        const int cnt = std::min(XQ_BATCH, R.nq - q0), qy = std::min(cnt, 1024);
+        const unsigned int *list = R.queries + q0;
+        hipLaunchKernelGGL(k_xq_init, blocks_for(cnt), dim3(256), 0, R.st, d_xq, cnt, R.mean_k, (int)R.nv);
+        for (int pass = 0; pass < 3; pass++) {
+            hipLaunchKernelGGL(k_xq_hist, dim3(XQ_SLICES, (unsigned)qy), dim3(256), 0, R.st, R.d_xyz, arr, arr_n, list, cnt, d_xq, shifts[pass], widths[pass],
+                               d_hist);
+            hipLaunchKernelGGL(k_xq_pick, dim3((unsigned)cnt), dim3(64), 0, R.st, d_xq, cnt, shifts[pass], widths[pass], d_hist);
+        }
+        hipLaunchKernelGGL(k_xq_sum, dim3(XQ_SLICES, (unsigned)qy), dim3(256), 0, R.st, R.d_xyz, arr, arr_n, list, cnt, d_xq);
+        hipLaunchKernelGGL(k_xq_finish, blocks_for(cnt), dim3(256), 0, R.st, d_xq, list, cnt, R.mean_k, (int)R.nv, R.d_dist);
+    }
+    return RSM_OK;
+}
+
+// Step 8: mean / stddev exactly as PCL forms them (a sequential loop over the per-point distances in point order): on the
+// device when no addition can round (k_dist_stats), else on the host; *thr = the removal threshold.  need_r > 0: the widest window a
+// normal's radius search of that radius needs on the lattice comes back with the statistics (pin->cnt[3]; 1 << 20 when not asked).
+int distance_threshold(FilterRun &R, double std_mul, double need_r, double stats[4], double *thr) {
+    DistStats *h_stats = &R.A->pin->stats;
+    int *h_cnt = R.A->pin->cnt;
+    double sum = 0.0, sq_sum = 0.0;
+    const DistStats init{0.0, 0.0, 0x7fffffff, 0x7fffffff, 0};
+    *h_stats = init;
+    DEVCHK(hipMemcpyAsync(R.d_stats, h_stats, sizeof init, hipMemcpyHostToDevice, R.st));
+    hipLaunchKernelGGL(k_dist_stats, dim3((unsigned)std::min<int64_t>((R.n + 255) / 256, 1024)), dim3(256), 0, R.st, R.d_dist, R.n, R.d_stats);
+    h_cnt[3] = 1 << 20;
+    if (need_r > 0.0) {
+        DEVCHK(hipMemsetAsync(R.d_cnt + 3, 0, sizeof(int), R.st));
+        hipLaunchKernelGGL(k_normal_need, blocks_for(R.n), dim3(256), 0, R.st, R.lat, R.cell_of, R.n, R.wg, need_r, R.d_cnt + 3);
+        DEVCHK(hipMemcpyAsync(h_cnt + 3, R.d_cnt + 3, sizeof(int), hipMemcpyDeviceToHost, R.st));
+    }
+    DEVCHK(hipMemcpyAsync(h_stats, R.d_stats, sizeof init, hipMemcpyDeviceToHost, R.st));
+    DEVCHK(hipStreamSynchronize(R.st));
+    auto exact = [](double total, int q) { // every partial sum is a multiple of 2^q below 2^(q + 53)
+        if (q == 0x7fffffff) return true;   // all zero
+        return total * (1.0 + 1e-9) < ldexp(1.0, q + 53);
+    };
+    if (!h_stats->bad && exact(h_stats->sum, h_stats->q_sum) && exact(h_stats->sq_sum, h_stats->q_sq)) {
+        sum = h_stats->sum;
+        sq_sum = h_stats->sq_sum;
+    } else {
+        std::vector<float> hd((size_t)R.n);
+        DEVCHK(hipMemcpyAsync(hd.data(), R.d_dist, sizeof(float) * (size_t)R.n, hipMemcpyDeviceToHost, R.st));
+        DEVCHK(hipStreamSynchronize(R.st));
+        for (int64_t i = 0; i < R.n; i++) {
+            sum += hd[(size_t)i];
+            sq_sum += hd[(size_t)i] * hd[(size_t)i]; // float * float, as in PCL
+        }
+    }
+    const double mean = sum / (double)R.nv; // valid_distances
+    const double variance = (sq_sum - sum * sum / (double)R.nv) / ((double)R.nv - 1);
+    const double stddev = sqrt(variance);
+    *thr = mean + std_mul * stddev;
+    if (stats) {
+        stats[0] = mean;
+        stats[1] = stddev;
+        stats[2] = *thr;
+        stats[3] = (double)R.nq; // what the whole-chip search took
+    }
+    return RSM_OK;
+}
+
+// Step 9: d_flag = kept, the kept points and their indices in order, *m = their number (one host round trip)
+int keep_compact(FilterRun &R, double thr, float *d_fxyz, int32_t *d_kept_index, int64_t *m) {
+    hipLaunchKernelGGL(k_keep_flags, blocks_for(R.n), dim3(256), 0, R.st, R.d_dist, R.n, thr, R.d_flag);
+    int s = scan_u32(*R.A, R.d_flag, R.d_pos, (size_t)R.n, R.st);
+    if (s != RSM_OK) return s;
+    hipLaunchKernelGGL(k_compact_kept, blocks_for(R.n), dim3(256), 0, R.st, R.d_xyz, R.d_flag, R.d_pos, R.n, d_fxyz, d_kept_index);
+    uint64_t total = 0;
+    if ((s = scan_total(R.d_flag, R.d_pos, (size_t)R.n, R.st, &total, (unsigned int *)R.A->pin->cnt)) != RSM_OK) return s;
+    *m = (int64_t)total;
+    return RSM_OK;
+}
+
+// Step 10, on the lattice copy with the removed points blanked: a window of w pixels holds every normal's neighbourhood
+int normals_on_lattice(FilterRun &R, int64_t m, const int32_t *d_kept_index, double normal_radius, const float cam_center[3], float4 *d_normals) {
+    hipLaunchKernelGGL(k_lattice_drop, blocks_for(R.n), dim3(256), 0, R.st, R.d_flag, R.cell_of, R.n, R.lat);
+    DEVCHK(hipMemsetD32Async((hipDeviceptr_t)d_normals, 0x7fc00000, (size_t)4 * m, R.st));
+    hipLaunchKernelGGL(k_normals_lattice, blocks_for(m), dim3(256), 0, R.st, R.lat, R.cell_of, d_kept_index, m, R.wg, normal_radius,
+                       (float)(normal_radius * normal_radius), cam_center[0], cam_center[1], cam_center[2], d_normals);
+    DEVCHK(hipStreamSynchronize(R.st));
+    DEVCHK(hipGetLastError());
+    return RSM_OK;
+}
+// ... or on a grid with cell edge = search radius; the non-finite points (all kept: distance 0) sort behind the finite ones and keep
+// the NaN normal the buffer is filled with
+int normals_on_grid(FilterRun &R, int64_t m, const float *d_fxyz, double normal_radius, const float cam_center[3], float4 *d_normals) {
+    FilterGridDev G2;
+    const int64_t mv = m - (R.n - R.nv);
+    const int s = build_grid(R.A, d_fxyz, m, 0 /* no table: the normals walk their ranges by binary search */, (float)normal_radius, R.flo, R.fhi, R.st, G2);
+    if (s != RSM_OK) return s;
+    const float r2 = (float)(normal_radius * normal_radius);
+    DEVCHK(hipMemsetD32Async((hipDeviceptr_t)d_normals, 0x7fc00000, (size_t)4 * m, R.st));
+    if (mv > 0)
+        hipLaunchKernelGGL(k_cloud_normals, blocks_for(mv), dim3(256), 0, R.st, G2.sxyz, G2.keys, (int)mv, G2.g, r2, cam_center[0], cam_center[1], cam_center[2],
+                           d_normals);
+    DEVCHK(hipStreamSynchronize(R.st));
+    DEVCHK(hipGetLastError());
+    return RSM_OK;
+}
+} // namespace
+
 // d_xyz: n x 3 float (device).  Outputs (device): kept_index [n] (first *n_kept valid), fxyz [3n], normals [n] float4.
 // A: reserved by the caller (filter_arena_reserve) with at least filter_arena_bytes(n) free.
 // pre (optional): the cloud is the depth map of a matched pair -- its pixel lattice decides most queries (k_sor_window),
@@ -1529,341 +1576,60 @@ int filter_cloud_device(FilterArena *A, const float *d_xyz, int64_t n, int mean_
     }
     if (n <= 0) return RSM_OK;
     if (n >= (1ll << 31) || mean_k < 1 || !A) return RSM_E_INVALID;
-    float lo[3], hi[3], flo[3], fhi[3];
-    // exact bounding box (the sample's extremes are not the cloud's) and the number of finite points: only they take
-    // part in the searches (PCL: the k-d tree skips the others)
-    unsigned int *d_bb = A->get<unsigned int>(8);
-    int *d_cnt = A->get<int>(4);
-    DistStats *d_stats = A->get<DistStats>(1);
-    float *d_dist = A->get<float>((size_t)n);
-    unsigned int *d_redo = A->get<unsigned int>((size_t)n), *d_redo2 = A->get<unsigned int>((size_t)n);
-    unsigned int *d_flag = A->get<unsigned int>((size_t)n), *d_pos = A->get<unsigned int>((size_t)n);
-    if (A->failed) return RSM_E_NOMEM;
-    unsigned int *h_bb = (unsigned int *)((char *)A->h_pinned + 3 * 8192 * sizeof(float));
-    int *h_cnt = (int *)(h_bb + 8);
-    DistStats *h_stats = (DistStats *)(h_cnt + 4);
-    int64_t nv = 0;
-    {
-        const unsigned int init[7] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u, 0u};
-        memcpy(h_bb, init, sizeof init);
-        if (hipMemcpyAsync(d_bb, h_bb, sizeof init, hipMemcpyHostToDevice, st) != hipSuccess) return RSM_E_HIP;
-        hipLaunchKernelGGL(k_bbox, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 1024)), dim3(256), 0, st, d_xyz, n, d_bb);
-        if (hipMemcpyAsync(h_bb, d_bb, sizeof init, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return RSM_E_HIP;
-        nv = h_bb[6];
-        for (int a = 0; a < 3; a++) {
-            flo[a] = nv ? ord_to_float(h_bb[a]) : 0.0f;
-            fhi[a] = nv ? ord_to_float(h_bb[3 + a]) : 0.0f;
-        }
-    }
-    // first cell edge: ~sqrt(k + 1) point spacings of a surface patch whose area is the product of the two largest
-    // robust extents; queries that cannot be decided inside their 27 cells (fewer than k + 1 points within h: thick or
-    // sparse parts of the cloud, patch corners, isolated points) are retried on a grid with twice the edge; what is left
-    // after KNN_LEVELS grids (or once only a handful remain) is searched against all points by the whole chip.
-    // One cell edge does not fit a whole cloud: a perspective depth map is 25 times denser (per unit of space) in its near
-    // part than in its far part (C2: 1.25 vs 6 units between neighbours), and the surface estimate above is off for a deep
-    // or thick one.  The search therefore runs over a ladder of grids from fine to coarse, h doubling: a query is decided
-    // at the first level whose 27 cells hold its k + 1 nearest (there its candidates number a few hundred whatever the
-    // local density); an undecided attempt costs one table lookup and one count over the few candidates a too-fine grid
-    // offers.  Every level re-sorts the points (0.65 ms for 5.5 M): cheap next to one query pass with a wrong h
-    // (a single level at the surface estimate ran the near part's queries over ~50 000 candidates each: 390 ms).
-    // The ladder starts one octave below the surface estimate (on C2 two octaves below decides 10 % of the queries for
-    // a quarter of the search time, three octaves below nothing).
-    // All of it only when a grid is built at all: the cloud of a matched pair is searched on its pixel lattice and the sample, its
-    // round trip and its quantiles stay out of the call.
-    float h = 0.0f, h_floor = 0.0f, glo[3] = {0.0f, 0.0f, 0.0f}, ghi[3] = {0.0f, 0.0f, 0.0f};
-    bool have_grid_box = false;
-    auto grid_box = [&]() -> bool {
-        if (have_grid_box) return true;
-        if (!sample_extent(A, d_xyz, n, st, lo, hi)) return false;
-        double e[3] = {(double)hi[0] - lo[0], (double)hi[1] - lo[1], (double)hi[2] - lo[2]};
-        std::sort(e, e + 3);
-        const double area = std::max(e[2] * e[1], 1e-12), spacing = sqrt(area / (0.98 * 0.98 * 0.98 * (double)std::max<int64_t>(nv, 1)));
-        h = (float)(spacing * sqrt((double)(mean_k + 1)));
-        if (!(h > 0.0f) || !std::isfinite(h)) h = 1.0f;
-        // the grid box: the robust extent grown by a few cells, inside the exact bounding box (far outliers are clamped
-        // into the border cells instead of blowing up the cell count)
-        for (int a = 0; a < 3; a++) {
-            glo[a] = std::max(flo[a], lo[a] - 4.0f * h);
-            ghi[a] = std::min(fhi[a], hi[a] + 4.0f * h);
-            if (!(ghi[a] >= glo[a])) ghi[a] = glo[a];
-        }
-        h *= 0.5f;
-        if (h_floor > h) h = h_floor;
-        if (route && route->h0 > 0.0f) h = route->h0; // (a level decides a query only with all of its k + 1 nearest in hand: any start gives the same bits)
-        have_grid_box = true;
-        return true;
-    };
-    const unsigned blocks = (unsigned)((n + 255) / 256);
-    const int KNN_LEVELS = 12;
-    if (hipMemsetAsync(d_dist, 0, sizeof(float) * (size_t)n, st) != hipSuccess) return RSM_E_HIP; // non-finite points: distance 0, as PCL
-    int nq = (int)nv, redo_n = 0;
-    const unsigned int *queries = nullptr;
-    int s = RSM_OK;
-    const size_t mark = A->off;
-    bool prepassed = false, wave_done = false;
-    float4 *lat_keep = nullptr;          // the lattice copy, kept for the normals while no grid level has taken its arena space
-    const unsigned int *cell_keep = nullptr;
-    size_t mark_lat = mark;
-    const float4 *lat_all = nullptr;
-    int64_t lat_cells = 0;
-    if (pre && mean_k <= 128 && nv > 0) { // the pixel-window pass: what it cannot decide becomes the ladder's first query list
-        float4 *lat = A->get<float4>(cloud_lattice_bytes(pre->XL, pre->XR, pre->YL, pre->YR) / sizeof(float4));
-        unsigned int *cell_of = A->get<unsigned int>((size_t)n);
-        if (!lat || !cell_of) return RSM_E_NOMEM;
-        lat_keep = lat;
-        cell_keep = cell_of;
-        mark_lat = A->off;
-        hipLaunchKernelGGL(k_finite_flags, dim3(blocks), dim3(256), 0, st, d_xyz, n, d_flag, d_redo2);
-        launch_cloud_lattice(pre->flags, pre->row_offset, pre->W, pre->XL, pre->XR, pre->YL, pre->YR, pre->xyz64, n, lat, cell_of, st);
-        // which window?  pre->radius > 0: the caller's; 0: the smallest of 7 / 12 / 16 pixels that decides >= 85 % of a sparse
-        // sample of the tiles (every 6th in x and y: ~3 % of the queries) -- a thin sheet (depth noise below the lateral
-        // spacing, the reference's rig geometry) is decided inside 15 x 15 pixels, a thick one (the synthetic bench rig: a
-        // disparity step of 0.05 pixel is 6 lateral spacings deep) needs 33 x 33; nothing decides enough: no window pass
-        int radius = pre->radius;
-        if (radius <= 0) {
-            unsigned int *d_pc = (unsigned int *)d_cnt; // (d_cnt has 4 ints)
-            unsigned int *h_pc = (unsigned int *)h_cnt;
-            const int cand[3] = {7, 12, 16};
-            double best = 0.0;
-            for (int ci = 0; ci < 3 && radius <= 0; ci++) {
-                if (hipMemsetAsync(d_pc, 0, 3 * sizeof(unsigned int), st) != hipSuccess) return RSM_E_HIP;
-                launch_sor_window(lat, pre->XL, pre->XR, pre->YL, pre->YR, pre->qz, pre->R, pre->T, mean_k, cand[ci], d_dist, d_flag, st, 6, d_pc);
-                if (hipMemcpyAsync(h_pc, d_pc, 3 * sizeof(unsigned int), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-                    return RSM_E_HIP;
-                best = h_pc[0] ? (double)h_pc[1] / (double)h_pc[0] : 0.0;
-                if (best >= 0.85 || (ci == 2 && best >= 0.5)) {
-                    radius = cand[ci];
-                    // every query this window leaves over has its (k+1)-th neighbour beyond the window's bound (closer points
-                    // cannot hide outside it): the ladder need not start below that scale
-                    float sum_lim;
-                    memcpy(&sum_lim, &h_pc[2], sizeof sum_lim);
-                    // (1.25 x the mean bound: a level at the bound itself would decide almost none of them)
-                    const float hf = 1.25f * sum_lim / (float)h_pc[0];
-                    if (std::isfinite(hf)) h_floor = hf;
-                }
-            }
-        }
-        if (pre->radius_out) *pre->radius_out = radius > 0 ? radius : 0;
-        if (radius > 0) {
-            launch_sor_window(lat, pre->XL, pre->XR, pre->YL, pre->YR, pre->qz, pre->R, pre->T, mean_k, radius, d_dist, d_flag, st);
-            size_t tb = 0;
-            if (rocprim::exclusive_scan(nullptr, tb, d_flag, d_pos, 0u, (size_t)n, rocprim::plus<unsigned int>(), st) != hipSuccess) return RSM_E_HIP;
-            void *tp = A->get<uint8_t>(tb);
-            if (!tp) return RSM_E_NOMEM;
-            if (rocprim::exclusive_scan(tp, tb, d_flag, d_pos, 0u, (size_t)n, rocprim::plus<unsigned int>(), st) != hipSuccess) return RSM_E_HIP;
-            hipLaunchKernelGGL(k_compact_list, dim3(blocks), dim3(256), 0, st, d_redo2, d_flag, d_pos, (int)n, d_redo, d_cnt);
-            if (hipMemcpyAsync(h_cnt, d_cnt, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return RSM_E_HIP;
-            nq = h_cnt[0];
-            queries = d_redo;
-            prepassed = true;
-            if (pre->tile_left_out) *pre->tile_left_out = nq;
-            // What a window below 24 pixels leaves over (a thick sheet's points whose neighbours spread wider: scattered, a seventh
-            // of C2's cloud) gets the 49 x 49 window a thread each, straight from the lattice copy (k_sor_window_list); only what
-            // that leaves as well -- depth edges, holes, outliers -- goes to the grid ladder.
-            // What a window below 24 pixels leaves over (a thick sheet's points whose neighbours spread wider: scattered, a seventh
-            // of C2's cloud) gets the 49 x 49 window a thread each, straight from the lattice copy (k_sor_window_list); what THAT
-            // leaves -- the points within a dozen pixels of the mask's border and of depth edges, whose neighbours lie on one
-            // side: 1.6 % of C2's cloud, the queries that cost the grid ladder most (coarse levels: tens of thousands of
-            // candidates in the 27 cells of each) -- an 81 x 81 window; only the rest (holes, outliers, islands) goes to the ladder.
-            unsigned int *cur = d_redo, *oth = d_redo2;
-            const int radii[2] = {24, 40};
-            int last = radius;
-            for (int pass = 0; pass < 2 && nq > 0; pass++) {
-                if (radii[pass] <= last || !((pre->list_pass >> pass) & 1)) continue;
-                if ((pre->list_pass >> (3 + pass)) & 1) // (A/B: the wave form at this radius instead of the thread form)
-                    launch_sor_window_wave(lat, cell_of, pre->XL, pre->XR, pre->YL, pre->YR, pre->qz, pre->R, pre->T, mean_k, radii[pass], cur, nq, d_dist, d_flag, st, pre->wg_max);
-                else
-                    launch_sor_window_list(lat, cell_of, pre->XL, pre->XR, pre->YL, pre->YR, pre->qz, pre->R, pre->T, mean_k, radii[pass], cur, nq, d_dist, d_flag, st);
-                if (rocprim::exclusive_scan(tp, tb, d_flag, d_pos, 0u, (size_t)nq, rocprim::plus<unsigned int>(), st) != hipSuccess) return RSM_E_HIP;
-                hipLaunchKernelGGL(k_compact_list, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, cur, d_flag, d_pos, nq, oth, d_cnt);
-                if (hipMemcpyAsync(h_cnt, d_cnt, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return RSM_E_HIP;
-                nq = h_cnt[0];
-                std::swap(cur, oth);
-                last = radii[pass]; // (the ladder keeps its start: what is left now is few, and a level whose 27 cells hold tens of
-                                    // thousands of candidates costs a wave-per-query search milliseconds however few the queries)
-            }
-            // What the list passes leave (C2: 564 of 5.5 M -- mask corners, hole rims, outliers): a wave each over windows of 80, 160,
-            // 320 ... pixels of the lattice copy, while there are few enough for that to be cheaper than a grid level (a level is a
-            // sort of the whole cloud plus, for these queries, 27 cells of tens of thousands of candidates each: 4 ms a level on C2).
-            if ((pre->list_pass & 4) && last >= 24) {
-                const int span = std::max(pre->XR - pre->XL, pre->YR - pre->YL) + 1;
-                for (int wr = std::max(80, 2 * last); nq > 0 && nq <= 65536; wr *= 2) {
-                    launch_sor_window_wave(lat, cell_of, pre->XL, pre->XR, pre->YL, pre->YR, pre->qz, pre->R, pre->T, mean_k, wr, cur, nq, d_dist, d_flag, st, pre->wg_max);
-                    if (rocprim::exclusive_scan(tp, tb, d_flag, d_pos, 0u, (size_t)nq, rocprim::plus<unsigned int>(), st) != hipSuccess) return RSM_E_HIP;
-                    hipLaunchKernelGGL(k_compact_list, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, cur, d_flag, d_pos, nq, oth, d_cnt);
-                    if (hipMemcpyAsync(h_cnt, d_cnt, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return RSM_E_HIP;
-                    nq = h_cnt[0];
-                    std::swap(cur, oth);
-                    if (wr >= span) break; // the window already covers the whole box: what is left has fewer than k + 1 points within its bound
-                }
-                wave_done = true;
-            }
-            queries = cur;
-            if (pre->undecided_out) *pre->undecided_out = nq;
-            lat_all = lat;
-            lat_cells = (int64_t)(pre->XR - pre->XL + 1 + 2 * WIN_PAD) * (int64_t)(pre->YR - pre->YL + 1 + 2 * WIN_PAD);
-        }
-    }
-    FilterGridDev G;
-    G.sxyz = nullptr;
-    // after the wave passes a handful is left at most (isolated points): straight to the whole-chip search, over the lattice copy
-    // as the point array (its empty pixels are NaN: never below any threshold) -- no grid level, no sort
-    const bool skip_ladder = wave_done && nq <= 48 && lat_all != nullptr;
-    if (nq > 0 && !skip_ladder && !grid_box()) return RSM_E_HIP;
-    for (int level = 0; level < KNN_LEVELS && nq > 0 && !skip_ladder; level++, h *= 2.0f) {
-        A->off = mark; // the previous level's grid is done (its kernels are ordered before this level's on the stream)
-        lat_keep = nullptr;
-        s = build_grid(A, d_xyz, n, nv, h, glo, ghi, st, G);
-        if (s != RSM_OK) return s;
-        if (route) {
-            if (level == 0) {
-                route->h = h;
-                route->kind0 = G.table_kind;
-                const int nk[3] = {G.g.nx, G.g.ny, G.g.nz}, pk[3] = {G.g.p0, G.g.p1, G.g.p2};
-                for (int a = 0; a < 3; a++) {
-                    route->origin[a] = glo[a];
-                    route->cells[pk[a]] = nk[a];
-                }
-            }
-            route->levels++;
-            route->kinds |= 1 << G.table_kind;
-        }
-        if (level == 0 && !prepassed) queries = G.vals; // every point, in grid order (coherent waves)
-        unsigned int *out_list = (queries == d_redo) ? d_redo2 : d_redo; // never the list being read
-        launch_knn(d_xyz, G, (int)nv, h, mean_k, queries, nq, d_dist, d_flag, st);
-        { // undecided queries -> the next level's list, in order
-            size_t tb = 0;
-            if (rocprim::exclusive_scan(nullptr, tb, d_flag, d_pos, 0u, (size_t)nq, rocprim::plus<unsigned int>(), st) != hipSuccess) return RSM_E_HIP;
-            void *tp = A->get<uint8_t>(tb);
-            if (!tp) return RSM_E_NOMEM;
-            if (rocprim::exclusive_scan(tp, tb, d_flag, d_pos, 0u, (size_t)nq, rocprim::plus<unsigned int>(), st) != hipSuccess) return RSM_E_HIP;
-            hipLaunchKernelGGL(k_compact_list, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, queries, d_flag, d_pos, nq, out_list, d_cnt);
-        }
-        if (hipMemcpyAsync(h_cnt, d_cnt, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-            return RSM_E_HIP;
-        redo_n = h_cnt[0];
-        queries = out_list;
-        nq = redo_n;
-        if (nq <= 48) break; // cheaper to finish against all points than to sort again (a coarser level costs ~0.8 ms, the
-                             // whole-chip search ~25 us per query)
-    }
-    redo_n = nq;
-    if (nq > 0) { // against all points; the last grid's sorted copy is still in the arena (any ordering of the points serves)
-        const int XQ_BATCH = 2048; // queries per round (their histograms: 16 MB)
-        XqState *d_xq = A->get<XqState>((size_t)XQ_BATCH);
-        int *d_hist = A->get<int>((size_t)XQ_BATCH * 2048);
-        if (!d_xq || !d_hist) return RSM_E_NOMEM;
-        if (hipMemsetAsync(d_hist, 0, sizeof(int) * (size_t)XQ_BATCH * 2048, st) != hipSuccess) return RSM_E_HIP;
-        const int shifts[3] = {20, 9, 0}, widths[3] = {11, 11, 9};
-        const float4 *arr = skip_ladder ? lat_all : G.sxyz; // any array holding every finite point once
-        const int arr_n = skip_ladder ? (int)lat_cells : (int)nv;
-        if (!arr || lat_cells >= (1ll << 31)) return RSM_E_INVALID;
-        for (int q0 = 0; q0 < nq; q0 += XQ_BATCH) {
-            const int cnt = std::min(XQ_BATCH, nq - q0), qy = std::min(cnt, 1024);
-            const unsigned int *list = queries + q0;
-            hipLaunchKernelGGL(k_xq_init, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, d_xq, cnt, mean_k, (int)nv);
-            for (int pass = 0; pass < 3; pass++) {
-                hipLaunchKernelGGL(k_xq_hist, dim3(XQ_SLICES, (unsigned)qy), dim3(256), 0, st, d_xyz, arr, arr_n, list, cnt, d_xq, shifts[pass],
-                                   widths[pass], d_hist);
-                hipLaunchKernelGGL(k_xq_pick, dim3((unsigned)cnt), dim3(64), 0, st, d_xq, cnt, shifts[pass], widths[pass], d_hist);
-            }
-            hipLaunchKernelGGL(k_xq_sum, dim3(XQ_SLICES, (unsigned)qy), dim3(256), 0, st, d_xyz, arr, arr_n, list, cnt, d_xq);
-            hipLaunchKernelGGL(k_xq_finish, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, st, d_xq, list, cnt, mean_k, (int)nv, d_dist);
-        }
-    }
-    A->off = lat_keep ? mark_lat : mark;
-    // mean / stddev exactly as PCL forms them (a sequential loop over the per-point distances in point order): on the
-    // device when no addition can round (k_dist_stats), else on the host
-    double sum = 0.0, sq_sum = 0.0;
-    {
-        DistStats init{0.0, 0.0, 0x7fffffff, 0x7fffffff, 0};
-        *h_stats = init;
-        if (hipMemcpyAsync(d_stats, h_stats, sizeof init, hipMemcpyHostToDevice, st) != hipSuccess) return RSM_E_HIP;
-        hipLaunchKernelGGL(k_dist_stats, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 1024)), dim3(256), 0, st, d_dist, n, d_stats);
-        h_cnt[3] = 1 << 20;
-        if (lat_keep && d_normals && pre->normals_wmax > 0) { // the widest window a normal's radius search needs on the lattice (read back with the statistics)
-            if (hipMemsetAsync(d_cnt + 3, 0, sizeof(int), st) != hipSuccess) return RSM_E_HIP;
-            hipLaunchKernelGGL(k_normal_need, dim3(blocks), dim3(256), 0, st, lat_keep, cell_keep, n, win_geom(pre->XL, pre->XR, pre->YL, pre->YR, pre->qz, pre->R, pre->T),
-                               normal_radius, d_cnt + 3);
-            if (hipMemcpyAsync(h_cnt + 3, d_cnt + 3, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess) return RSM_E_HIP;
-        }
-        if (hipMemcpyAsync(h_stats, d_stats, sizeof init, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-            return RSM_E_HIP;
-        auto exact = [](double total, int q) { // every partial sum is a multiple of 2^q below 2^(q + 53)
-            if (q == 0x7fffffff) return true;   // all zero
-            return total * (1.0 + 1e-9) < ldexp(1.0, q + 53);
-        };
-        if (!h_stats->bad && exact(h_stats->sum, h_stats->q_sum) && exact(h_stats->sq_sum, h_stats->q_sq)) {
-            sum = h_stats->sum;
-            sq_sum = h_stats->sq_sum;
-        } else {
-            std::vector<float> hd((size_t)n);
-            if (hipMemcpyAsync(hd.data(), d_dist, sizeof(float) * (size_t)n, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-                return RSM_E_HIP;
-            for (int64_t i = 0; i < n; i++) {
-                sum += hd[(size_t)i];
-                sq_sum += hd[(size_t)i] * hd[(size_t)i]; // float * float, as in PCL
-            }
-        }
-    }
-    const double mean = sum / (double)nv; // valid_distances
-    const double variance = (sq_sum - sum * sum / (double)nv) / ((double)nv - 1);
-    const double stddev = sqrt(variance), thr = mean + std_mul * stddev;
-    if (stats) {
-        stats[0] = mean;
-        stats[1] = stddev;
-        stats[2] = thr;
-        stats[3] = (double)redo_n;
-    }
-    hipLaunchKernelGGL(k_keep_flags, dim3(blocks), dim3(256), 0, st, d_dist, n, thr, d_flag);
-    size_t tb = 0;
-    if (rocprim::exclusive_scan(nullptr, tb, d_flag, d_pos, 0u, (size_t)n, rocprim::plus<unsigned int>(), st) != hipSuccess) return RSM_E_HIP;
-    void *tp = A->get<uint8_t>(tb);
-    if (!tp) return RSM_E_NOMEM;
-    if (rocprim::exclusive_scan(tp, tb, d_flag, d_pos, 0u, (size_t)n, rocprim::plus<unsigned int>(), st) != hipSuccess) return RSM_E_HIP;
-    hipLaunchKernelGGL(k_compact_kept, dim3(blocks), dim3(256), 0, st, d_xyz, d_flag, d_pos, n, d_fxyz, d_kept_index);
-    unsigned int *h_last = (unsigned int *)h_cnt;
-    if (hipMemcpyAsync(&h_last[0], d_pos + (n - 1), 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipMemcpyAsync(&h_last[1], d_flag + (n - 1), 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-        return RSM_E_HIP;
-    const int64_t m = (int64_t)h_last[0] + h_last[1];
-    *n_kept = m;
-    A->off = lat_keep ? mark_lat : mark;
-    if (m == 0 || !d_normals) {
-        A->off = mark;
-        return RSM_OK;
-    }
-    // normals of the filtered cloud.  On the lattice copy when it is still there and a window of at most pre->normals_wmax pixels holds every
-    // normal's neighbourhood (k_normal_need: a property of the rig -- the search radius in pixel spacings at the nearest point)
-    if (pre && pre->normals_out) {
-        pre->normals_out[0] = 0;
-        pre->normals_out[1] = lat_keep ? h_cnt[3] : -1;
-    }
-    if (lat_keep && h_cnt[3] <= pre->normals_wmax) {
-        if (pre->normals_out) pre->normals_out[0] = std::max(h_cnt[3], 1);
-        const WinGeom g = win_geom(pre->XL, pre->XR, pre->YL, pre->YR, pre->qz, pre->R, pre->T);
-        hipLaunchKernelGGL(k_lattice_drop, dim3(blocks), dim3(256), 0, st, d_flag, cell_keep, n, lat_keep);
-        if (hipMemsetD32Async((hipDeviceptr_t)d_normals, 0x7fc00000, (size_t)4 * m, st) != hipSuccess) return RSM_E_HIP;
-        hipLaunchKernelGGL(k_normals_lattice, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, lat_keep, cell_keep, d_kept_index, m, g, normal_radius,
-                           (float)(normal_radius * normal_radius), cam_center[0], cam_center[1], cam_center[2], d_normals);
-        if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) return RSM_E_HIP;
-        A->off = mark;
-        return RSM_OK;
-    }
-    A->off = mark;
-    // normals of the filtered cloud: grid with cell edge = search radius; the non-finite points (all kept: distance 0)
-    // sort behind the finite ones and keep the NaN normal the buffer is filled with
-    FilterGridDev G2;
-    const int64_t mv = m - (n - nv);
-    s = build_grid(A, d_fxyz, m, 0 /* no table: the normals walk their ranges by binary search */, (float)normal_radius, flo, fhi, st, G2);
+    FilterRun R;
+    R.A = A, R.st = st, R.d_xyz = d_xyz, R.n = n, R.mean_k = mean_k, R.pre = pre, R.route = route;
+    int s = cloud_bbox(A, d_xyz, n, st, R.flo, R.fhi, &R.nv); // step 1
     if (s != RSM_OK) return s;
-    const float r2 = (float)(normal_radius * normal_radius);
-    if (hipMemsetD32Async((hipDeviceptr_t)d_normals, 0x7fc00000, (size_t)4 * m, st) != hipSuccess) return RSM_E_HIP;
-    if (mv > 0)
-        hipLaunchKernelGGL(k_cloud_normals, dim3((unsigned)((mv + 255) / 256)), dim3(256), 0, st, G2.sxyz, G2.keys, (int)mv, G2.g, r2,
-                           cam_center[0], cam_center[1], cam_center[2], d_normals);
-    if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) return RSM_E_HIP;
-    A->off = mark;
+    R.d_cnt = A->get<int>(4);
+    R.d_stats = A->get<DistStats>(1);
+    R.d_dist = A->get<float>((size_t)n);
+    R.d_redo = A->get<unsigned int>((size_t)n), R.d_redo2 = A->get<unsigned int>((size_t)n);
+    R.d_flag = A->get<unsigned int>((size_t)n), R.d_pos = A->get<unsigned int>((size_t)n);
+    if (A->failed) return RSM_E_NOMEM;
+    DEVCHK(hipMemsetAsync(R.d_dist, 0, sizeof(float) * (size_t)n, st)); // non-finite points: distance 0, as PCL
+    R.nq = (int)R.nv;
+    R.mark = R.mark_lat = A->off;
+    if (pre && mean_k <= 128 && R.nv > 0) { // the pixel-window passes: what they cannot decide becomes the ladder's first query list
+        R.wg = win_geom(*pre);
+        int radius = 0;
+        if ((s = lattice_and_probe(R, &radius)) != RSM_OK) return s;
+        if (radius > 0) {
+            if ((s = tile_pass(R, radius)) != RSM_OK || (s = list_passes(R, &radius)) != RSM_OK) return s;
+            if ((pre->list_pass & 4) && radius >= 24 && (s = wave_passes(R, radius)) != RSM_OK) return s;
+            if (pre->undecided_out) *pre->undecided_out = R.nq;
+        }
+    }
+    // after the wave passes a handful is left at most (isolated points): straight to the whole-chip search, over the lattice copy
+    // as the point array -- no grid level, no sort
+    const bool skip_ladder = R.wave_done && R.nq <= 48;
+    if (R.nq > 0 && !skip_ladder && (s = grid_ladder(R)) != RSM_OK) return s;
+    if (R.nq > 0 && (s = whole_chip_search(R, skip_ladder)) != RSM_OK) return s;
+    R.rewind();
+    double thr = 0.0;
+    // (the normals' window is asked for while the lattice copy is still there and the caller lets them use it)
+    const bool ask = R.lat_kept && d_normals && pre->normals_wmax > 0;
+    if ((s = distance_threshold(R, std_mul, ask ? normal_radius : 0.0, stats, &thr)) != RSM_OK) return s;
+    int64_t m = 0;
+    if ((s = keep_compact(R, thr, d_fxyz, d_kept_index, &m)) != RSM_OK) return s;
+    *n_kept = m;
+    if (m > 0 && d_normals) {
+        // normals of the filtered cloud.  On the lattice copy when it is still there and a window of at most pre->normals_wmax pixels holds every
+        // normal's neighbourhood (k_normal_need: a property of the rig -- the search radius in pixel spacings at the nearest point)
+        const int need = A->pin->cnt[3];
+        if (pre && pre->normals_out) {
+            pre->normals_out[0] = 0;
+            pre->normals_out[1] = R.lat_kept ? need : -1;
+        }
+        if (R.lat_kept && need <= pre->normals_wmax) {
+            if (pre->normals_out) pre->normals_out[0] = std::max(need, 1);
+            s = normals_on_lattice(R, m, d_kept_index, normal_radius, cam_center, d_normals);
+        } else {
+            A->off = R.mark;
+            s = normals_on_grid(R, m, d_fxyz, normal_radius, cam_center, d_normals);
+        }
+        if (s != RSM_OK) return s;
+    }
+    A->off = R.mark;
     return RSM_OK;
 }
 

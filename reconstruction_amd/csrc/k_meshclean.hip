@@ -20,19 +20,12 @@
 
 #include <string.h>
 
-#include <rocprim/rocprim.hpp>
-
 #include <math.h>
 
 #include <algorithm>
 #include <vector>
 
 namespace {
-
-#define MCHK(call)                                  \
-    do {                                            \
-        if ((call) != hipSuccess) return RSM_E_HIP; \
-    } while (0)
 
 typedef unsigned long long u64;
 
@@ -388,59 +381,8 @@ __global__ __launch_bounds__(256) void k_mc_keep(const int32_t *__restrict__ f, 
     }
     count_if(r4, ctr + C_RM4);
 }
-__global__ __launch_bounds__(256) void k_mc_compact_faces(const int32_t *__restrict__ faces, size_t nf, const unsigned int *__restrict__ fkeep,
-                                                          const unsigned int *__restrict__ fpos, const unsigned int *__restrict__ vpos, int32_t *__restrict__ out) {
-    const size_t f = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (f >= nf || !fkeep[f]) return;
-    const size_t o = fpos[f];
-    for (int c = 0; c < 3; c++) out[3 * o + c] = (int32_t)vpos[faces[3 * f + c]];
-}
-__global__ __launch_bounds__(256) void k_mc_compact_verts(const float *__restrict__ verts, size_t nv, const unsigned int *__restrict__ vused,
-                                                          const unsigned int *__restrict__ vpos, float *__restrict__ out) {
-    const size_t v = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (v >= nv || !vused[v]) return;
-    const size_t o = vpos[v];
-    for (int c = 0; c < 3; c++) out[3 * o + c] = verts[3 * v + c];
-}
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
-static inline int bits_of(u64 x) { // the bits keys 0 .. x use
-    int b = 1;
-    while (b < 64 && (x >> b) != 0) b++;
-    return b;
-}
-
-template <typename K>
-static int sort_pairs(DevMem &M, K *k0, K *k1, uint32_t *v0, uint32_t *v1, size_t n, int bits, hipStream_t st) {
-    size_t tb = 0;
-    if (rocprim::radix_sort_pairs(nullptr, tb, k0, k1, v0, v1, n, 0, bits, st) != hipSuccess) return RSM_E_HIP;
-    void *tp = M.get<uint8_t>(tb);
-    if (!tp) return RSM_E_NOMEM;
-    if (rocprim::radix_sort_pairs(tp, tb, k0, k1, v0, v1, n, 0, bits, st) != hipSuccess) return RSM_E_HIP;
-    return RSM_OK;
-}
-static int scan_u32(DevMem &M, const unsigned int *in, unsigned int *out, size_t n, hipStream_t st) {
-    size_t tb = 0;
-    if (rocprim::exclusive_scan(nullptr, tb, in, out, 0u, n, rocprim::plus<unsigned int>(), st) != hipSuccess) return RSM_E_HIP;
-    void *tp = M.get<uint8_t>(tb);
-    if (!tp) return RSM_E_NOMEM;
-    if (rocprim::exclusive_scan(tp, tb, in, out, 0u, n, rocprim::plus<unsigned int>(), st) != hipSuccess) return RSM_E_HIP;
-    return RSM_OK;
-}
-// totals of two flag arrays and their exclusive scans, pos[n - 1] + flag[n - 1], in one host round trip
-static int scan_totals(const unsigned int *flag_a, const unsigned int *pos_a, size_t na, const unsigned int *flag_b, const unsigned int *pos_b, size_t nb,
-                       hipStream_t st, uint64_t *total_a, uint64_t *total_b) {
-    unsigned int h[4] = {0, 0, 0, 0};
-    MCHK(hipMemcpyAsync(h, pos_a + (na - 1), sizeof(unsigned int), hipMemcpyDeviceToHost, st));
-    MCHK(hipMemcpyAsync(h + 1, flag_a + (na - 1), sizeof(unsigned int), hipMemcpyDeviceToHost, st));
-    MCHK(hipMemcpyAsync(h + 2, pos_b + (nb - 1), sizeof(unsigned int), hipMemcpyDeviceToHost, st));
-    MCHK(hipMemcpyAsync(h + 3, flag_b + (nb - 1), sizeof(unsigned int), hipMemcpyDeviceToHost, st));
-    MCHK(hipStreamSynchronize(st));
-    *total_a = (uint64_t)h[0] + h[1];
-    *total_b = (uint64_t)h[2] + h[3];
-    return RSM_OK;
-}
-
 // what the stages share: counters, the sorted edge table, and (on request) incidences, border flags, the union-find forest
 struct Tables {
     u64 *ctr = nullptr;     // C_N counters
@@ -454,13 +396,13 @@ struct Tables {
 static int validate(DevMem &M, Tables &T, const float *d_v, size_t nv, const int32_t *d_f, size_t nf, int *what, hipStream_t st) {
     T.ctr = M.get<u64>(C_N);
     if (!M.ok) return RSM_E_NOMEM;
-    MCHK(hipMemsetAsync(T.ctr, 0, C_N * sizeof(u64), st));
+    DEVCHK(hipMemsetAsync(T.ctr, 0, C_N * sizeof(u64), st));
     const size_t n_coords = d_v ? 3 * nv : 0, n = std::max(n_coords, 3 * nf);
     if (n > 0) hipLaunchKernelGGL(k_mc_validate, blocks_for(n), dim3(256), 0, st, d_v, n_coords, d_f, nv, nf, T.ctr);
     u64 h[2] = {0, 0};
-    MCHK(hipMemcpyAsync(h, T.ctr, sizeof h, hipMemcpyDeviceToHost, st));
-    MCHK(hipStreamSynchronize(st));
-    MCHK(hipGetLastError());
+    DEVCHK(hipMemcpyAsync(h, T.ctr, sizeof h, hipMemcpyDeviceToHost, st));
+    DEVCHK(hipStreamSynchronize(st));
+    DEVCHK(hipGetLastError());
     *what = h[C_BAD_INDEX] ? 1 : h[C_BAD_COORD] ? 2 : 0;
     return *what ? RSM_E_INVALID : RSM_OK;
 }
@@ -479,11 +421,11 @@ static int edge_table(DevMem &M, Tables &T, const int32_t *d_f, size_t nv, size_
     if (want_uf) T.parent = M.get<int>(nf);
     if (!M.ok) return RSM_E_NOMEM;
     hipLaunchKernelGGL(k_mc_edge_keys, blocks_for(nf), dim3(256), 0, st, d_f, nf, (u64)nv, k0, v0);
-    const int s = sort_pairs(M, k0, T.ekey, v0, T.eval, n, 32 + bits_of((u64)nv), st);
+    const int s = sort_pairs(M, k0, T.ekey, v0, T.eval, n, 32 + key_bits((u64)nv), st);
     if (s != RSM_OK) return s;
     if (want_inc) {
-        MCHK(hipMemsetAsync(T.einc, 0, n, st));
-        MCHK(hipMemsetAsync(T.vborder, 0, nv ? nv : 1, st));
+        DEVCHK(hipMemsetAsync(T.einc, 0, n, st));
+        DEVCHK(hipMemsetAsync(T.vborder, 0, nv ? nv : 1, st));
     }
     if (want_uf) hipLaunchKernelGGL(k_mc_iota, blocks_for(nf), dim3(256), 0, st, T.parent, nf);
     hipLaunchKernelGGL(k_mc_edge_runs, blocks_for(n), dim3(256), 0, st, (const u64 *)T.ekey, (const uint32_t *)T.eval, n, (u64)nv, T.einc, T.vborder, T.parent);
@@ -516,8 +458,8 @@ static int smooth(DevMem &M, const Tables &T, const float *d_in, size_t nv, cons
 }
 
 static int finish(hipStream_t st) {
-    MCHK(hipStreamSynchronize(st));
-    MCHK(hipGetLastError());
+    DEVCHK(hipStreamSynchronize(st));
+    DEVCHK(hipGetLastError());
     return RSM_OK;
 }
 
@@ -537,7 +479,7 @@ int mesh_corner_lists_device(DevMem &M, const int32_t *d_f, size_t nv, size_t nf
     if (!M.ok) return RSM_E_NOMEM;
     if (nf > 0) {
         hipLaunchKernelGGL(k_mc_corner_keys, blocks_for(nf), dim3(256), 0, st, d_f, nf, (uint32_t)nv, k0, v0);
-        const int s = sort_pairs(M, k0, k1, v0, *corner, n, bits_of((u64)nv), st);
+        const int s = sort_pairs(M, k0, k1, v0, *corner, n, key_bits((u64)nv), st);
         if (s != RSM_OK) return s;
     }
     hipLaunchKernelGGL(k_mc_row_starts, blocks_for(nv + 1), dim3(256), 0, st, (const uint32_t *)k1, n, nv, *row);
@@ -558,9 +500,9 @@ int mesh_smooth_device(const float *d_v, int64_t nv_, const int32_t *d_f, int64_
         hipLaunchKernelGGL(k_mc_count_u8, blocks_for(nv), dim3(256), 0, st, (const uint8_t *)T.vborder, nv, T.ctr + C_BORDER);
         if ((s = smooth(M, T, d_v, nv, d_f, nf, steps, cotangent, boundary, &res, st)) != RSM_OK) return s;
     }
-    if (nv > 0) MCHK(hipMemcpyAsync(d_out, res, 3 * nv * sizeof(float), hipMemcpyDeviceToDevice, st));
+    if (nv > 0) DEVCHK(hipMemcpyAsync(d_out, res, 3 * nv * sizeof(float), hipMemcpyDeviceToDevice, st));
     u64 h[C_N];
-    MCHK(hipMemcpyAsync(h, T.ctr, sizeof h, hipMemcpyDeviceToHost, st));
+    DEVCHK(hipMemcpyAsync(h, T.ctr, sizeof h, hipMemcpyDeviceToHost, st));
     if ((s = finish(st)) != RSM_OK) return s;
     *n_border = (int64_t)h[C_BORDER];
     return RSM_OK;
@@ -576,7 +518,7 @@ int mesh_components_device(const int32_t *d_f, int64_t nv_, int64_t nf_, int32_t
     if ((s = edge_table(M, T, d_f, nv, nf, false, true, st)) != RSM_OK) return s;
     hipLaunchKernelGGL(k_mc_labels, blocks_for(nf), dim3(256), 0, st, d_f, nf, T.parent, d_label, T.ctr);
     u64 h[C_N];
-    MCHK(hipMemcpyAsync(h, T.ctr, sizeof h, hipMemcpyDeviceToHost, st));
+    DEVCHK(hipMemcpyAsync(h, T.ctr, sizeof h, hipMemcpyDeviceToHost, st));
     if ((s = finish(st)) != RSM_OK) return s;
     *n_components = (int64_t)h[C_COMPS];
     return RSM_OK;
@@ -608,7 +550,7 @@ int mesh_clean_device(const float *d_v, int64_t nv_, const int32_t *d_f, int64_t
     if (nv > 0) {
         unsigned int h[6];
         hipLaunchKernelGGL(k_mc_vertex_box, dim3((unsigned)std::min<size_t>(1024, (nv + 255) / 256)), dim3(256), 0, st, pos, nv, box + 6 * nf);
-        MCHK(hipMemcpyAsync(h, box + 6 * nf, sizeof h, hipMemcpyDeviceToHost, st));
+        DEVCHK(hipMemcpyAsync(h, box + 6 * nf, sizeof h, hipMemcpyDeviceToHost, st));
         if ((s = finish(st)) != RSM_OK) return s;
         const double dx = (double)ord2f(h[3]) - (double)ord2f(h[0]), dy = (double)ord2f(h[4]) - (double)ord2f(h[1]), dz = (double)ord2f(h[5]) - (double)ord2f(h[2]);
         D = sqrt((dx * dx + dy * dy) + dz * dz);
@@ -622,9 +564,9 @@ int mesh_clean_device(const float *d_v, int64_t nv_, const int32_t *d_f, int64_t
         uint8_t *dead = M.get<uint8_t>(nf), *dup = M.get<uint8_t>(nf), *alive = M.get<uint8_t>(nf), *nm = M.get<uint8_t>(nf);
         unsigned int *fkeep = M.get<unsigned int>(nf), *fpos = M.get<unsigned int>(nf), *vused = M.get<unsigned int>(nv), *vpos = M.get<unsigned int>(nv);
         if (!M.ok) return RSM_E_NOMEM;
-        MCHK(hipMemsetAsync(dup, 0, nf, st));
-        MCHK(hipMemsetAsync(nm, 0, nf, st));
-        MCHK(hipMemsetAsync(vused, 0, nv * sizeof(unsigned int), st));
+        DEVCHK(hipMemsetAsync(dup, 0, nf, st));
+        DEVCHK(hipMemsetAsync(nm, 0, nf, st));
+        DEVCHK(hipMemsetAsync(vused, 0, nv * sizeof(unsigned int), st));
         hipLaunchKernelGGL(k_mc_labels, blocks_for(nf), dim3(256), 0, st, d_f, nf, T.parent, label, T.ctr);
         hipLaunchKernelGGL(k_mc_comp_boxes, blocks_for(nf), dim3(256), 0, st, pos, d_f, nf, (const int32_t *)label, box);
         hipLaunchKernelGGL(k_mc_comp_dead, blocks_for(nf), dim3(256), 0, st, (const int32_t *)label, nf, (const unsigned int *)box, threshold, dead, T.ctr);
@@ -635,7 +577,7 @@ int mesh_clean_device(const float *d_v, int64_t nv_, const int32_t *d_f, int64_t
         if (p->flags & RSM_MESH_CLEAN_NONMANIFOLD)
             hipLaunchKernelGGL(k_mc_nonmanifold, blocks_for(n), dim3(256), 0, st, (const u64 *)T.ekey, (const uint32_t *)T.eval, n, (u64)nv, (const uint8_t *)alive, nm);
         hipLaunchKernelGGL(k_mc_keep, blocks_for(nf), dim3(256), 0, st, d_f, nf, (const uint8_t *)alive, (const uint8_t *)nm, p->flags, fkeep, vused, T.ctr);
-        if ((s = scan_u32(M, fkeep, fpos, nf, st)) != RSM_OK || (s = scan_u32(M, vused, vpos, nv, st)) != RSM_OK) return s;
+        if ((s = scan_u32(M, (const unsigned int *)fkeep, fpos, nf, st)) != RSM_OK || (s = scan_u32(M, (const unsigned int *)vused, vpos, nv, st)) != RSM_OK) return s;
         uint64_t kf = 0, kv = 0;
         if ((s = scan_totals(fkeep, fpos, nf, vused, vpos, nv, st, &kf, &kv)) != RSM_OK) return s;
         if (kf > 0) {
@@ -645,9 +587,9 @@ int mesh_clean_device(const float *d_v, int64_t nv_, const int32_t *d_f, int64_t
             }
             res.nv = (int64_t)kv;
             res.nf = (int64_t)kf;
-            hipLaunchKernelGGL(k_mc_compact_faces, blocks_for(nf), dim3(256), 0, st, d_f, nf, (const unsigned int *)fkeep, (const unsigned int *)fpos,
+            hipLaunchKernelGGL(k_mesh_compact_faces<>, blocks_for(nf), dim3(256), 0, st, d_f, nf, (const unsigned int *)fkeep, (const unsigned int *)fpos,
                                (const unsigned int *)vpos, res.d_f);
-            hipLaunchKernelGGL(k_mc_compact_verts, blocks_for(nv), dim3(256), 0, st, pos, nv, (const unsigned int *)vused, (const unsigned int *)vpos, res.d_v);
+            hipLaunchKernelGGL(k_mesh_compact_verts<>, blocks_for(nv), dim3(256), 0, st, pos, nv, (const unsigned int *)vused, (const unsigned int *)vpos, res.d_v);
         }
     }
     u64 h[C_N];

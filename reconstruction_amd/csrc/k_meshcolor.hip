@@ -23,11 +23,6 @@
 
 namespace {
 
-#define KCHK(call)                                  \
-    do {                                            \
-        if ((call) != hipSuccess) return RSM_E_HIP; \
-    } while (0)
-
 typedef unsigned long long u64;
 
 enum { K_COLOURED = 0, K_NONORMAL, K_VISIBLE, K_DRAWN, K_BIG, K_CURSOR, K_N };
@@ -262,19 +257,19 @@ static bool view_from_P(const double P[12], bool with_center, McView *c) {
 static int raster(DevMem &M, const float *d_v, const int32_t *d_f, size_t nf, const std::vector<McView> &hv, const McView *d_views, long long big_box, u64 *ctr,
                   hipStream_t st) {
     const int V = (int)hv.size();
-    for (const McView &c : hv) KCHK(hipMemsetAsync(c.wbuf, 0, sizeof(uint32_t) * (size_t)c.W * (size_t)c.H, st));
+    for (const McView &c : hv) DEVCHK(hipMemsetAsync(c.wbuf, 0, sizeof(uint32_t) * (size_t)c.W * (size_t)c.H, st));
     if (nf == 0) return RSM_OK;
     const dim3 grid(blocks_for(nf).x, (unsigned)V);
     hipLaunchKernelGGL(k_mcol_raster<0>, grid, dim3(256), 0, st, d_v, d_f, nf, d_views, big_box, (uint2 *)nullptr, (u64)0, ctr);
     u64 n_big = 0;
-    KCHK(hipMemcpyAsync(&n_big, ctr + K_BIG, sizeof n_big, hipMemcpyDeviceToHost, st));
-    KCHK(hipStreamSynchronize(st));
-    KCHK(hipGetLastError());
+    DEVCHK(hipMemcpyAsync(&n_big, ctr + K_BIG, sizeof n_big, hipMemcpyDeviceToHost, st));
+    DEVCHK(hipStreamSynchronize(st));
+    DEVCHK(hipGetLastError());
     if (n_big == 0) return RSM_OK;
     if (n_big > 0x7fffffffull) return RSM_E_NOMEM;
     uint2 *list = M.get<uint2>((size_t)n_big);
     if (!M.ok) return RSM_E_NOMEM;
-    KCHK(hipMemsetAsync(list, 0, sizeof(uint2) * (size_t)n_big, st));
+    DEVCHK(hipMemsetAsync(list, 0, sizeof(uint2) * (size_t)n_big, st));
     hipLaunchKernelGGL(k_mcol_raster<1>, grid, dim3(256), 0, st, d_v, d_f, nf, d_views, big_box, list, n_big, ctr);
     hipLaunchKernelGGL(k_mcol_raster_big, dim3((unsigned)n_big), dim3(256), 0, st, d_v, d_f, d_views, (const uint2 *)list);
     return RSM_OK;
@@ -291,8 +286,8 @@ int texture_color_device(const float *d_xyz, int64_t n, const double P12[12], co
     c.H = H;
     c.img = d_img;
     hipLaunchKernelGGL(k_mcol_texture, blocks_for((size_t)n), dim3(256), 0, st, d_xyz, (size_t)n, c, d_rgb);
-    KCHK(hipStreamSynchronize(st));
-    KCHK(hipGetLastError());
+    DEVCHK(hipStreamSynchronize(st));
+    DEVCHK(hipGetLastError());
     return RSM_OK;
 }
 
@@ -310,11 +305,11 @@ int mesh_depth_device(const float *d_v, int64_t nv, const int32_t *d_f, int64_t 
     McView *d_views = M.get<McView>(1);
     u64 *ctr = M.get<u64>(K_N);
     if (!M.ok) return RSM_E_NOMEM;
-    KCHK(hipMemcpyAsync(d_views, hv.data(), sizeof(McView), hipMemcpyHostToDevice, st));
-    KCHK(hipMemsetAsync(ctr, 0, K_N * sizeof(u64), st));
+    DEVCHK(hipMemcpyAsync(d_views, hv.data(), sizeof(McView), hipMemcpyHostToDevice, st));
+    DEVCHK(hipMemsetAsync(ctr, 0, K_N * sizeof(u64), st));
     if ((s = raster(M, d_v, d_f, (size_t)nf, hv, d_views, big_box, ctr, st)) != RSM_OK) return s;
-    KCHK(hipStreamSynchronize(st));
-    KCHK(hipGetLastError());
+    DEVCHK(hipStreamSynchronize(st));
+    DEVCHK(hipGetLastError());
     return RSM_OK;
 }
 
@@ -341,14 +336,14 @@ int mesh_views_device(DevMem &M, const rsm_dedup_view *views, int n_pairs, bool 
             uint8_t *img = M.get<uint8_t>(3 * pix), *msk = views[i].mask[k] ? M.get<uint8_t>(pix) : nullptr;
             c.wbuf = with_wbuf ? M.get<uint32_t>(pix) : nullptr;
             if (!M.ok) return RSM_E_NOMEM;
-            KCHK(hipMemcpyAsync(img, views[i].image[k], 3 * pix, hipMemcpyHostToDevice, st));
-            if (msk) KCHK(hipMemcpyAsync(msk, views[i].mask[k], pix, hipMemcpyHostToDevice, st));
+            DEVCHK(hipMemcpyAsync(img, views[i].image[k], 3 * pix, hipMemcpyHostToDevice, st));
+            if (msk) DEVCHK(hipMemcpyAsync(msk, views[i].mask[k], pix, hipMemcpyHostToDevice, st));
             c.img = img;
             c.mask = msk;
         }
     *d_views = M.get<McView>((size_t)V);
     if (!M.ok) return RSM_E_NOMEM;
-    KCHK(hipMemcpyAsync(*d_views, hv.data(), sizeof(McView) * (size_t)V, hipMemcpyHostToDevice, st));
+    DEVCHK(hipMemcpyAsync(*d_views, hv.data(), sizeof(McView) * (size_t)V, hipMemcpyHostToDevice, st));
     return RSM_OK;
 }
 
@@ -370,16 +365,16 @@ int mesh_color_scene_device(DevMem &M, const float *d_v, int64_t nv_, const int3
     if ((s = mesh_views_device(M, views, n_pairs, true, &hv, &d_views, invalid, st)) != RSM_OK) return s;
     u64 *ctr = M.get<u64>(K_N);
     if (!M.ok) return RSM_E_NOMEM;
-    KCHK(hipMemsetAsync(ctr, 0, K_N * sizeof(u64), st));
+    DEVCHK(hipMemsetAsync(ctr, 0, K_N * sizeof(u64), st));
     uint32_t *row = nullptr, *corner = nullptr;
     if ((s = mesh_corner_lists_device(M, d_f, nv, nf, &row, &corner, st)) != RSM_OK) return s;
     if ((s = raster(M, d_v, d_f, nf, hv, d_views, big_box, ctr, st)) != RSM_OK) return s;
     hipLaunchKernelGGL(k_mcol_color, blocks_for(nv), dim3(256), 0, st, d_v, nv, d_f, (const uint32_t *)row, (const uint32_t *)corner, (const McView *)d_views, V,
                        p->mode, p->min_cos, p->depth_eps, d_rgb, d_best, d_vis, ctr);
     u64 h[K_N];
-    KCHK(hipMemcpyAsync(h, ctr, sizeof h, hipMemcpyDeviceToHost, st));
-    KCHK(hipStreamSynchronize(st)); // (the views' host images and hv were read by the copies above before this returns)
-    KCHK(hipGetLastError());
+    DEVCHK(hipMemcpyAsync(h, ctr, sizeof h, hipMemcpyDeviceToHost, st));
+    DEVCHK(hipStreamSynchronize(st)); // (the views' host images and hv were read by the copies above before this returns)
+    DEVCHK(hipGetLastError());
     S[1] = (double)h[K_COLOURED];
     S[2] = (double)h[K_NONORMAL];
     S[3] = (double)h[K_VISIBLE];

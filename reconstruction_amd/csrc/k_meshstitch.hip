@@ -24,11 +24,6 @@
 
 namespace {
 
-#define KCHK(call)                                  \
-    do {                                            \
-        if ((call) != hipSuccess) return RSM_E_HIP; \
-    } while (0)
-
 typedef unsigned long long u64;
 
 // the counters: S_INC .. S_NONE are the stage's counts[5]
@@ -273,7 +268,7 @@ int build_csr(DevMem &M, const int32_t *d_best, size_t nv, const int32_t *d_f, s
     c->deg = M.get<uint32_t>(nv);
     c->ctr = M.get<u64>(S_N);
     if (!M.ok) return RSM_E_NOMEM;
-    KCHK(hipMemsetAsync(c->ctr, 0, S_N * sizeof(u64), st));
+    DEVCHK(hipMemsetAsync(c->ctr, 0, S_N * sizeof(u64), st));
     hipLaunchKernelGGL(k_mst_csr, blocks_for(nv), dim3(256), 0, st, d_best, nv, d_f, row, corner, c->nbr, c->deg, c->ctr);
     return RSM_OK;
 }
@@ -311,9 +306,9 @@ int solve(DevMem &M, size_t nv, const int32_t *d_best, const uint8_t *d_rgb, con
                            (const double *)d, (const double *)b, lambda, part);
         hipLaunchKernelGGL(k_mst_sum2, dim3(1), dim3(256), 0, st, (const double *)part, MST_RED_BLOCKS, part + 2 * MST_RED_BLOCKS);
         double h[2];
-        KCHK(hipMemcpyAsync(h, part + 2 * MST_RED_BLOCKS, sizeof h, hipMemcpyDeviceToHost, st));
-        KCHK(hipStreamSynchronize(st));
-        KCHK(hipGetLastError());
+        DEVCHK(hipMemcpyAsync(h, part + 2 * MST_RED_BLOCKS, sizeof h, hipMemcpyDeviceToHost, st));
+        DEVCHK(hipStreamSynchronize(st));
+        DEVCHK(hipGetLastError());
         *rel = h[1] > 0.0 ? sqrt(h[0]) / sqrt(h[1]) : 0.0;
     }
     return RSM_OK;
@@ -364,10 +359,10 @@ int mesh_stitch_rhs_device(const float *d_v, int64_t nv_, const int32_t *d_f, in
     hipLaunchKernelGGL(k_mst_rhs, blocks_for(nv), dim3(256), 0, st, d_v, nv, d_best, d_rgb, (const u64 *)d_vis, (const McView *)d_views, seam_gradient,
                        (const uint32_t *)row, (const uint32_t *)c.deg, (const uint32_t *)c.nbr, d_G, c.ctr);
     u64 h[S_N];
-    KCHK(hipMemcpyAsync(h, c.ctr, sizeof h, hipMemcpyDeviceToHost, st));
-    KCHK(hipMemcpyAsync(d_deg, c.deg, sizeof(uint32_t) * nv, hipMemcpyDeviceToDevice, st));
-    KCHK(hipStreamSynchronize(st)); // (the views' host images were read by the copies above before this returns)
-    KCHK(hipGetLastError());
+    DEVCHK(hipMemcpyAsync(h, c.ctr, sizeof h, hipMemcpyDeviceToHost, st));
+    DEVCHK(hipMemcpyAsync(d_deg, c.deg, sizeof(uint32_t) * nv, hipMemcpyDeviceToDevice, st));
+    DEVCHK(hipStreamSynchronize(st)); // (the views' host images were read by the copies above before this returns)
+    DEVCHK(hipGetLastError());
     for (int k = 0; k < 5; k++) counts[k] = (int64_t)h[S_INC + k];
     return RSM_OK;
 }
@@ -384,13 +379,13 @@ int mesh_stitch_solve_device(const int32_t *d_f, int64_t nv_, int64_t nf_, const
     Csr c;
     if ((s = build_csr(M, d_best, nv, d_f, nf, row, corner, &c, st)) != RSM_OK) return s;
     u64 h[S_N];
-    KCHK(hipMemcpyAsync(h, c.ctr, sizeof h, hipMemcpyDeviceToHost, st));
-    KCHK(hipStreamSynchronize(st));
-    KCHK(hipGetLastError());
+    DEVCHK(hipMemcpyAsync(h, c.ctr, sizeof h, hipMemcpyDeviceToHost, st));
+    DEVCHK(hipStreamSynchronize(st));
+    DEVCHK(hipGetLastError());
     double *x = nullptr;
     if ((s = solve(M, nv, d_best, d_rgb, d_G, row, c, h[S_DMAX], lambda, iterations, &x, rel_residual, st)) != RSM_OK) return s;
-    KCHK(hipMemcpyAsync(d_x, x, sizeof(double) * 3 * nv, hipMemcpyDeviceToDevice, st));
-    KCHK(hipStreamSynchronize(st));
+    DEVCHK(hipMemcpyAsync(d_x, x, sizeof(double) * 3 * nv, hipMemcpyDeviceToDevice, st));
+    DEVCHK(hipStreamSynchronize(st));
     return RSM_OK;
 }
 
@@ -416,9 +411,9 @@ int mesh_stitch_device(const float *d_v, int64_t nv_, const int32_t *d_f, int64_
         hipLaunchKernelGGL(k_mst_rhs, blocks_for(nv), dim3(256), 0, st, d_v, nv, (const int32_t *)d_best, (const uint8_t *)d_rgb, (const u64 *)vis, scene.d_views,
                            sp->seam_gradient, scene.row, (const uint32_t *)c.deg, (const uint32_t *)c.nbr, G, c.ctr);
         u64 h[S_N];
-        KCHK(hipMemcpyAsync(h, c.ctr, sizeof h, hipMemcpyDeviceToHost, st));
-        KCHK(hipStreamSynchronize(st));
-        KCHK(hipGetLastError());
+        DEVCHK(hipMemcpyAsync(h, c.ctr, sizeof h, hipMemcpyDeviceToHost, st));
+        DEVCHK(hipStreamSynchronize(st));
+        DEVCHK(hipGetLastError());
         int steps = sp->iterations;
         if (steps == 0 && (steps = mesh_stitch_steps(sp->lambda, h[S_DMAX], sp->reduction)) < 0) {
             *invalid = 4;
@@ -427,9 +422,9 @@ int mesh_stitch_device(const float *d_v, int64_t nv_, const int32_t *d_f, int64_
         double *x = nullptr, rel = 0.0;
         if ((s = solve(M, nv, d_best, d_rgb, G, scene.row, c, h[S_DMAX], sp->lambda, steps, &x, &rel, st)) != RSM_OK) return s;
         hipLaunchKernelGGL(k_mst_finish, blocks_for(nv), dim3(256), 0, st, nv, (const int32_t *)d_best, (const double *)x, d_rgb, c.ctr);
-        KCHK(hipMemcpyAsync(h, c.ctr, sizeof h, hipMemcpyDeviceToHost, st));
-        KCHK(hipStreamSynchronize(st));
-        KCHK(hipGetLastError());
+        DEVCHK(hipMemcpyAsync(h, c.ctr, sizeof h, hipMemcpyDeviceToHost, st));
+        DEVCHK(hipStreamSynchronize(st));
+        DEVCHK(hipGetLastError());
         for (int k = 0; k < 5; k++) S[2 + k] = (double)h[S_INC + k];
         S[7] = (double)h[S_DMAX];
         S[8] = (double)steps;

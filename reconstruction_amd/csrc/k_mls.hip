@@ -19,11 +19,6 @@
 // compaction give the input order (as the filter's k_keep_flags / k_compact_kept).
 #include "../../include/rsm.h"
 #include "cloud_grid.h"
-#include "rsm_dev.h"
-
-#include <string.h>
-
-#include <rocprim/rocprim.hpp>
 
 #include <algorithm>
 #include <cmath>
@@ -209,7 +204,7 @@ __global__ void k_mls_compact(const unsigned int *__restrict__ flag, const unsig
 }
 
 void launch_point16_xyz(const void *rec, int64_t n, float *xyz, hipStream_t st) {
-    if (n > 0) hipLaunchKernelGGL(k_point16_xyz, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const float4 *)rec, n, xyz);
+    if (n > 0) hipLaunchKernelGGL(k_point16_xyz, blocks_for(n), dim3(256), 0, st, (const float4 *)rec, n, xyz);
 }
 
 size_t mls_arena_bytes(int64_t n) { // grid (keys x2, values x2, sorted points), staged results, flags + positions, sort / scan temporaries
@@ -230,35 +225,28 @@ int mls_cloud_device(FilterArena *A, const float *d_xyz, int64_t n, const float4
     int s = cloud_bbox(A, d_xyz, n, st, lo, hi, &nv);
     if (s != RSM_OK) return s;
     if (nv == 0) return RSM_OK;
-    float *txyz = (float *)filter_arena_alloc(A, sizeof(float) * 3 * (size_t)n);
-    float4 *tnrm = (float4 *)filter_arena_alloc(A, sizeof(float4) * (size_t)n);
-    unsigned int *flag = (unsigned int *)filter_arena_alloc(A, sizeof(unsigned int) * (size_t)n);
-    unsigned int *pos = (unsigned int *)filter_arena_alloc(A, sizeof(unsigned int) * (size_t)n);
-    unsigned int *h_last = (unsigned int *)filter_arena_host(A);
-    if (!txyz || !tnrm || !flag || !pos || !h_last) return RSM_E_NOMEM;
+    float *txyz = A->get<float>(3 * (size_t)n);
+    float4 *tnrm = A->get<float4>((size_t)n);
+    unsigned int *flag = A->get<unsigned int>((size_t)n), *pos = A->get<unsigned int>((size_t)n);
+    if (!txyz || !tnrm || !flag || !pos) return RSM_E_NOMEM;
     FilterGridDev G;
     s = build_grid(A, d_xyz, n, 0 /* no table: ranges by binary search, as the filter's normals */, (float)radius, lo, hi, st, G);
     if (s != RSM_OK) return s;
-    if (hipMemsetAsync(flag, 0, sizeof(unsigned int) * (size_t)n, st) != hipSuccess) return RSM_E_HIP;
+    DEVCHK(hipMemsetAsync(flag, 0, sizeof(unsigned int) * (size_t)n, st));
     const float r2 = (float)(radius * radius);
     const double gauss = radius * radius; // sqr_gauss_param_ (setSearchRadius sets it to radius^2)
-    const dim3 grid((unsigned)((nv + 255) / 256));
+    const dim3 grid = blocks_for(nv);
     if (order == 0)
         hipLaunchKernelGGL(k_mls<0>, grid, dim3(256), 0, st, G.sxyz, G.keys, (int)nv, G.g, r2, gauss, d_ref, txyz, tnrm, flag);
     else if (order == 1)
         hipLaunchKernelGGL(k_mls<1>, grid, dim3(256), 0, st, G.sxyz, G.keys, (int)nv, G.g, r2, gauss, d_ref, txyz, tnrm, flag);
     else
         hipLaunchKernelGGL(k_mls<2>, grid, dim3(256), 0, st, G.sxyz, G.keys, (int)nv, G.g, r2, gauss, d_ref, txyz, tnrm, flag);
-    size_t tb = 0;
-    if (rocprim::exclusive_scan(nullptr, tb, flag, pos, 0u, (size_t)n, rocprim::plus<unsigned int>(), st) != hipSuccess) return RSM_E_HIP;
-    void *tp = filter_arena_alloc(A, tb);
-    if (!tp) return RSM_E_NOMEM;
-    if (rocprim::exclusive_scan(tp, tb, flag, pos, 0u, (size_t)n, rocprim::plus<unsigned int>(), st) != hipSuccess) return RSM_E_HIP;
-    hipLaunchKernelGGL(k_mls_compact, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, flag, pos, n, txyz, tnrm, d_oxyz, d_onrm, d_oidx);
-    if (hipMemcpyAsync(&h_last[0], pos + (n - 1), 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-        hipMemcpyAsync(&h_last[1], flag + (n - 1), 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess ||
-        hipGetLastError() != hipSuccess)
-        return RSM_E_HIP;
-    *n_out = (int64_t)h_last[0] + h_last[1];
+    if ((s = scan_u32(*A, flag, pos, (size_t)n, st)) != RSM_OK) return s;
+    hipLaunchKernelGGL(k_mls_compact, blocks_for(n), dim3(256), 0, st, flag, pos, n, txyz, tnrm, d_oxyz, d_onrm, d_oidx);
+    uint64_t total = 0;
+    if ((s = scan_total(flag, pos, (size_t)n, st, &total, (unsigned int *)filter_arena_host(A))) != RSM_OK) return s;
+    DEVCHK(hipGetLastError());
+    *n_out = (int64_t)total;
     return RSM_OK;
 }

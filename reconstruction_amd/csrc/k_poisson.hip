@@ -21,8 +21,6 @@
 
 #include <string.h>
 
-#include <rocprim/rocprim.hpp>
-
 #include <math.h>
 
 #include <vector>
@@ -43,11 +41,6 @@ struct TetTable {
     uint8_t ntri[16];
     uint8_t e[16][2][3]; // edge code u << 2 | v
 };
-
-#define PCHK(call)                                 \
-    do {                                           \
-        if ((call) != hipSuccess) return RSM_E_HIP; \
-    } while (0)
 
 __device__ __forceinline__ bool pv_valid(const float *__restrict__ xyz, const float *__restrict__ nrm, int64_t s, double p[3], double nh[3]) {
     const float x = xyz[3 * s], y = xyz[3 * s + 1], z = xyz[3 * s + 2];
@@ -411,45 +404,9 @@ __global__ __launch_bounds__(256) void k_pv_face_keep(const int32_t *__restrict_
     fkeep[f] = keep;
     if (keep) vused[a] = vused[b] = vused[c] = 1u; // (every writer stores the same value)
 }
-__global__ __launch_bounds__(256) void k_pv_compact_faces(const int32_t *__restrict__ faces, size_t nf, const unsigned int *__restrict__ fkeep,
-                                                          const unsigned int *__restrict__ fpos, const unsigned int *__restrict__ vpos,
-                                                          int32_t *__restrict__ out) {
-    const size_t f = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (f >= nf || !fkeep[f]) return;
-    const size_t o = fpos[f];
-    for (int c = 0; c < 3; c++) out[3 * o + c] = (int32_t)vpos[faces[3 * f + c]];
-}
-__global__ __launch_bounds__(256) void k_pv_compact_verts(const float *__restrict__ verts, size_t nv, const unsigned int *__restrict__ vused,
-                                                          const unsigned int *__restrict__ vpos, float *__restrict__ out) {
-    const size_t v = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (v >= nv || !vused[v]) return;
-    const size_t o = vpos[v];
-    for (int c = 0; c < 3; c++) out[3 * o + c] = verts[3 * v + c];
-}
 
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
 static inline unsigned red_blocks(size_t n) { return (unsigned)std::min<size_t>(PV_RED_BLOCKS, (n + 255) / 256); }
-
-template <typename In>
-static int scan_u32(DevMem &M, In in, unsigned int *out, size_t n, hipStream_t st) {
-    size_t tb = 0;
-    if (rocprim::exclusive_scan(nullptr, tb, in, out, 0u, n, rocprim::plus<unsigned int>(), st) != hipSuccess) return RSM_E_HIP;
-    void *tp = M.get<uint8_t>(tb);
-    if (!tp) return RSM_E_NOMEM;
-    if (rocprim::exclusive_scan(tp, tb, in, out, 0u, n, rocprim::plus<unsigned int>(), st) != hipSuccess) return RSM_E_HIP;
-    return RSM_OK;
-}
-// total of a flag array and its exclusive scan: pos[n - 1] + flag[n - 1]
-template <typename F>
-static int scan_total(const F *flag, const unsigned int *pos, size_t n, hipStream_t st, uint64_t *total) {
-    unsigned int p = 0;
-    F f = 0;
-    PCHK(hipMemcpyAsync(&p, pos + (n - 1), sizeof p, hipMemcpyDeviceToHost, st));
-    PCHK(hipMemcpyAsync(&f, flag + (n - 1), sizeof f, hipMemcpyDeviceToHost, st));
-    PCHK(hipStreamSynchronize(st));
-    *total = (uint64_t)p + (uint64_t)f;
-    return RSM_OK;
-}
 
 static TetTable make_tet_table() {
     TetTable T;
@@ -509,15 +466,15 @@ int poisson_grid_device(const float *d_xyz, const float *d_nrm4, int64_t n, int 
     unsigned long long *cnt = M.get<unsigned long long>(1);
     if (!M.ok) return RSM_E_NOMEM;
     const unsigned int init[6] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u};
-    PCHK(hipMemcpyAsync(mm, init, sizeof init, hipMemcpyHostToDevice, st));
-    PCHK(hipMemsetAsync(cnt, 0, sizeof *cnt, st));
+    DEVCHK(hipMemcpyAsync(mm, init, sizeof init, hipMemcpyHostToDevice, st));
+    DEVCHK(hipMemsetAsync(cnt, 0, sizeof *cnt, st));
     hipLaunchKernelGGL(k_pv_bbox, dim3(red_blocks((size_t)n)), dim3(256), 0, st, d_xyz, d_nrm4, n, mm, cnt);
     unsigned int h_mm[6];
     unsigned long long h_cnt = 0;
-    PCHK(hipMemcpyAsync(h_mm, mm, sizeof h_mm, hipMemcpyDeviceToHost, st));
-    PCHK(hipMemcpyAsync(&h_cnt, cnt, sizeof h_cnt, hipMemcpyDeviceToHost, st));
-    PCHK(hipStreamSynchronize(st));
-    PCHK(hipGetLastError());
+    DEVCHK(hipMemcpyAsync(h_mm, mm, sizeof h_mm, hipMemcpyDeviceToHost, st));
+    DEVCHK(hipMemcpyAsync(&h_cnt, cnt, sizeof h_cnt, hipMemcpyDeviceToHost, st));
+    DEVCHK(hipStreamSynchronize(st));
+    DEVCHK(hipGetLastError());
     counts[0] = (int64_t)h_cnt;
     counts[1] = n - (int64_t)h_cnt;
     if (h_cnt == 0) return RSM_OK;
@@ -542,13 +499,13 @@ int poisson_rhs_device(const float *d_xyz, const float *d_nrm4, int64_t n, int d
     DevMem M;
     unsigned long long *V = M.get<unsigned long long>(3 * N3);
     if (!M.ok) return RSM_E_NOMEM;
-    PCHK(hipMemsetAsync(V, 0, 3 * N3 * sizeof(unsigned long long), st));
-    PCHK(hipMemsetAsync(d_occ, 0, N3, st));
+    DEVCHK(hipMemsetAsync(V, 0, 3 * N3 * sizeof(unsigned long long), st));
+    DEVCHK(hipMemsetAsync(d_occ, 0, N3, st));
     const PvGrid g = make_grid(grid, depth);
     hipLaunchKernelGGL(k_pv_splat, blocks_for((size_t)n), dim3(256), 0, st, d_xyz, d_nrm4, n, g, V, d_occ);
     hipLaunchKernelGGL(k_pv_rhs, blocks_for(N3), dim3(256), 0, st, (const long long *)V, depth, d_b32, d_b64);
-    PCHK(hipStreamSynchronize(st));
-    PCHK(hipGetLastError());
+    DEVCHK(hipStreamSynchronize(st));
+    DEVCHK(hipGetLastError());
     return RSM_OK;
 }
 
@@ -562,7 +519,7 @@ struct Solver {
         const int sh = depth - l;
         const size_t n3 = (size_t)1 << (3 * sh);
         const dim3 gh = blocks_for(n3 / 2);
-        PCHK(hipMemsetAsync(x[l], 0, n3 * sizeof(float), st));
+        DEVCHK(hipMemsetAsync(x[l], 0, n3 * sizeof(float), st));
         if (sh == 1) { // 2^3: 8 red-black sweeps, then 8 black-red (symmetric)
             for (int s = 0; s < 16; s++)
                 for (int c = 0; c < 2; c++) hipLaunchKernelGGL(k_pv_rbgs, gh, dim3(256), 0, st, x[l], b[l], sh, s < 8 ? c : 1 - c);
@@ -579,8 +536,8 @@ struct Solver {
     }
     int fetch(int m, double *out) { // the sum of `m` partials
         hipLaunchKernelGGL(k_pv_sum, dim3(1), dim3(256), 0, st, part, m, scal);
-        PCHK(hipMemcpyAsync(out, scal, sizeof(double), hipMemcpyDeviceToHost, st));
-        PCHK(hipStreamSynchronize(st));
+        DEVCHK(hipMemcpyAsync(out, scal, sizeof(double), hipMemcpyDeviceToHost, st));
+        DEVCHK(hipStreamSynchronize(st));
         return RSM_OK;
     }
 };
@@ -607,8 +564,8 @@ int poisson_solve_device(const float *d_b, int depth, double rel_residual, int m
     if (!M.ok) return RSM_E_NOMEM;
     float *z = S.x[0], *r = S.b[0];
     const unsigned rb = red_blocks(N3);
-    PCHK(hipMemsetAsync(d_chi, 0, N3 * sizeof(float), st));
-    PCHK(hipMemcpyAsync(r, d_b, N3 * sizeof(float), hipMemcpyDeviceToDevice, st));
+    DEVCHK(hipMemsetAsync(d_chi, 0, N3 * sizeof(float), st));
+    DEVCHK(hipMemcpyAsync(r, d_b, N3 * sizeof(float), hipMemcpyDeviceToDevice, st));
     double bb = 0.0;
     hipLaunchKernelGGL(k_pv_dot, dim3(rb), dim3(256), 0, st, d_b, d_b, N3, S.part);
     int s = S.fetch((int)rb, &bb);
@@ -618,7 +575,7 @@ int poisson_solve_device(const float *d_b, int depth, double rel_residual, int m
     double rho_old = 0.0;
     int worse = 0;
     bool have_best = true; // (chi = 0, residual 1)
-    PCHK(hipMemsetAsync(best, 0, N3 * sizeof(float), st));
+    DEVCHK(hipMemsetAsync(best, 0, N3 * sizeof(float), st));
     *residual = 1.0;
     for (int it = 1; it <= max_cycles; it++) {
         s = S.vcycle(0); // z = M^-1 r
@@ -626,7 +583,7 @@ int poisson_solve_device(const float *d_b, int depth, double rel_residual, int m
         double rho = 0.0, pq = 0.0, rr = 0.0;
         hipLaunchKernelGGL(k_pv_dot, dim3(rb), dim3(256), 0, st, r, z, N3, S.part);
         if ((s = S.fetch((int)rb, &rho)) != RSM_OK) return s;
-        if (it == 1) PCHK(hipMemcpyAsync(p, z, N3 * sizeof(float), hipMemcpyDeviceToDevice, st));
+        if (it == 1) DEVCHK(hipMemcpyAsync(p, z, N3 * sizeof(float), hipMemcpyDeviceToDevice, st));
         else hipLaunchKernelGGL(k_pv_xpay, blocks_for(N3), dim3(256), 0, st, p, z, (float)(rho / rho_old), N3);
         hipLaunchKernelGGL(k_pv_stencil<0>, dim3(rb), dim3(256), 0, st, p, (const float *)nullptr, q, depth, S.part);
         if ((s = S.fetch((int)rb, &pq)) != RSM_OK) return s;
@@ -645,14 +602,14 @@ int poisson_solve_device(const float *d_b, int depth, double rel_residual, int m
             *residual = res;
             worse = 0;
             if (res <= rel_residual) break; // (chi is the best iterate)
-            PCHK(hipMemcpyAsync(best, d_chi, N3 * sizeof(float), hipMemcpyDeviceToDevice, st));
+            DEVCHK(hipMemcpyAsync(best, d_chi, N3 * sizeof(float), hipMemcpyDeviceToDevice, st));
             have_best = true;
         } else if (++worse >= 2)
             break;
     }
-    if (*residual > rel_residual && have_best) PCHK(hipMemcpyAsync(d_chi, best, N3 * sizeof(float), hipMemcpyDeviceToDevice, st));
-    PCHK(hipStreamSynchronize(st));
-    PCHK(hipGetLastError());
+    if (*residual > rel_residual && have_best) DEVCHK(hipMemcpyAsync(d_chi, best, N3 * sizeof(float), hipMemcpyDeviceToDevice, st));
+    DEVCHK(hipStreamSynchronize(st));
+    DEVCHK(hipGetLastError());
     return *residual <= rel_residual ? RSM_OK : RSM_W_NOT_CONVERGED;
 }
 
@@ -668,9 +625,9 @@ int poisson_iso_device(const float *d_xyz, const float *d_nrm4, int64_t n, int64
     hipLaunchKernelGGL(k_pv_sum_f64, dim3(rb), dim3(256), 0, st, (const double *)val, n, part);
     hipLaunchKernelGGL(k_pv_sum, dim3(1), dim3(256), 0, st, (const double *)part, (int)rb, scal);
     double sum = 0.0;
-    PCHK(hipMemcpyAsync(&sum, scal, sizeof sum, hipMemcpyDeviceToHost, st));
-    PCHK(hipStreamSynchronize(st));
-    PCHK(hipGetLastError());
+    DEVCHK(hipMemcpyAsync(&sum, scal, sizeof sum, hipMemcpyDeviceToHost, st));
+    DEVCHK(hipStreamSynchronize(st));
+    DEVCHK(hipGetLastError());
     *iso = sum / (double)n_valid;
     return RSM_OK;
 }
@@ -698,7 +655,7 @@ int poisson_extract_device(const float *d_chi, int depth, double iso, const doub
     // (the last node has no edge toward higher indices and is no cell: both last flags are 0, the totals are the last positions)
     if ((s = scan_total(flag + 8 * N3 - 1, pos + 8 * N3 - 1, 1, st, &nv)) != RSM_OK) return s;
     if ((s = scan_total(cnt + N3 - 1, foff + N3 - 1, 1, st, &nf)) != RSM_OK) return s;
-    PCHK(hipGetLastError());
+    DEVCHK(hipGetLastError());
     untrimmed[0] = (int64_t)nv;
     untrimmed[1] = (int64_t)nf;
     if (nv == 0 || nf == 0) return RSM_OK;
@@ -761,9 +718,9 @@ int poisson_extract_device(const float *d_chi, int depth, double iso, const doub
         } else {
             kept.nv = (int64_t)kv;
             kept.nf = (int64_t)kf;
-            hipLaunchKernelGGL(k_pv_compact_faces, blocks_for(nf), dim3(256), 0, st, (const int32_t *)faces, (size_t)nf, (const unsigned int *)fkeep,
+            hipLaunchKernelGGL(k_mesh_compact_faces<>, blocks_for(nf), dim3(256), 0, st, (const int32_t *)faces, (size_t)nf, (const unsigned int *)fkeep,
                                (const unsigned int *)fpos, (const unsigned int *)vpos, kept.d_f);
-            hipLaunchKernelGGL(k_pv_compact_verts, blocks_for(nv), dim3(256), 0, st, (const float *)verts, (size_t)nv, (const unsigned int *)vused,
+            hipLaunchKernelGGL(k_mesh_compact_verts<>, blocks_for(nv), dim3(256), 0, st, (const float *)verts, (size_t)nv, (const unsigned int *)vused,
                                (const unsigned int *)vpos, kept.d_v);
             if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) {
                 poisson_mesh_free(&kept);

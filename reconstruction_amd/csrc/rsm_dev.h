@@ -150,14 +150,15 @@ void launch_erode_gray(const uint8_t *src, int W, int H, int ksize, const int *d
                        uint8_t *dst, hipStream_t st_);
 
 // cloud filter (k_filter.hip): SOR + radius normals on a device cloud of n float xyz points
-// FilterArena: grow-only device scratch owned by the context (one hipMalloc per cloud size instead of dozens per call)
+// FilterArena (cloud_arena.h; its functions: cloud_grid.hip): grow-only device scratch owned by the context (one hipMalloc per cloud size
+// instead of dozens per call)
 struct FilterArena;
 FilterArena *filter_arena_create();
 void filter_arena_destroy(FilterArena *a);
 size_t filter_arena_bytes(int64_t n);                      // scratch one filter call needs for n points
 int filter_arena_reserve(FilterArena *a, size_t bytes);    // makes room, rewinds the arena
 void *filter_arena_alloc(FilterArena *a, size_t bytes);    // caller buffers that live across the call (nullptr: full)
-void *filter_arena_host(FilterArena *a);                   // its small pinned host block (after a reserve; 64 bytes are free for a caller)
+void *filter_arena_host(FilterArena *a);                   // 64 bytes of its pinned host block that no cloud step uses itself: free for the caller (after a reserve)
 // The cloud as the depth map it is (rsm_filter_last_cloud): which pixels of the top level's margin box emitted a point (k_cloud's
 // flags + per-row offsets: point index = compaction order), the fp64 points, and the geometry that bounds how far a point outside
 // a pixel window can be (k_filter.hip: k_sor_window).  R_final must be a rotation (the caller checks).
