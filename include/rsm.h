@@ -575,6 +575,52 @@ int rsm_stage_mesh_smooth(rsm_ctx *ctx, const float *xyz, int64_t nv, const int3
                           float *out_xyz, int64_t *n_border);
 int rsm_stage_mesh_components(rsm_ctx *ctx, const int32_t *faces, int64_t nv, int64_t nf, int32_t *labels, int64_t *n_components);
 
+/* ---- the density trim of the surface (where mesh.bat runs PoissonRecon --density --samplesPerNode 2 and then SurfaceTrimmer --smooth 100
+ * --trim 7 --aRatio 0.01) -------------------------------------------------------------------------------------------------------------
+ * Not a bit-parity port of those tools: the rules as DESIGN.md 9 (f11) defines them.  Every vertex gets the depth at which a grid node
+ * would hold samples_per_node of the samples around it (from a trilinear count splat on 2^kernel_depth nodes per axis of the Poisson call's
+ * box), the values are smoothed over the mesh, the surface is cut along the iso-line value = trim (crossing triangles are split), and
+ * pieces on either side of the cut smaller than island_ratio of the whole area change side.  Opt-in: rsm_poisson_mesh's trim_cells is the
+ * occupancy trim and stays what it is; run the Poisson call with trim_cells = 0 before this one. */
+typedef struct rsm_mesh_trim_params {
+    int depth;               /* 5..9, the Poisson call's depth */
+    double scale;            /* finite, >= 1, the Poisson call's scale: the same box */
+    int kernel_depth;        /* 3..depth: the density is estimated on 2^kernel_depth nodes per axis; 0 = depth - 2 (PoissonRecon's default) */
+    double samples_per_node; /* finite, > 0 (mesh.bat: 2) */
+    int smooth_steps;        /* >= 0 (mesh.bat: 100) */
+    double trim;             /* finite (mesh.bat: 7): vertices with value >= trim are kept */
+    double island_ratio;     /* finite, in [0, 1) (mesh.bat: 0.01); 0 = no island rule */
+} rsm_mesh_trim_params;
+/* stats: [0] / [1] vertices / faces in, [2] / [3] out, [4] / [5] valid / invalid samples, [6] cut edges, [7] faces split, [8] faces with a
+ * repeated index dropped, [9] zero-area triangles the splits emitted, [10] / [11] components on the kept / dropped side, [12] / [13]
+ * components moved kept -> dropped / dropped -> kept, [14] Q_total (the area of both sides in units of D^2 2^-32), [15] / [16] the least /
+ * largest value after smoothing (0 for an empty mesh), [17] D^2 (the squared diagonal of the box of the input vertices), [18] the density
+ * grid's step (0: no valid sample or all of them equal -- every value is 0), [19] the kernel depth used */
+#define RSM_MESH_TRIM_STATS 20
+/* host buffers: xyz nv*3 float, faces nf*3 int32, n samples (samples_xyz n*3 float, samples_normals4 n*4 float or NULL: without normals a
+ * finite point is a valid sample, with them the Poisson call's rule holds) -> the context's last mesh, as rsm_mesh_clean (rsm_poisson_last_mesh
+ * copies it out; colours of the last mesh are dropped).  An empty mesh in, or nothing kept: an empty mesh, RSM_OK.  RSM_E_INVALID
+ * (rsm_last_error names the cause): every range stated in the struct, a face index outside [0, nv), a coordinate that is not finite,
+ * 3 nf >= 2^31, nv above INT32_MAX, n above INT32_MAX, a negative count, a NULL pointer. */
+int rsm_mesh_trim(rsm_ctx *ctx, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, const float *samples_xyz, const float *samples_normals4,
+                  int64_t n, const rsm_mesh_trim_params *p, int64_t *n_vertices, int64_t *n_faces, double *stats);
+/* the same with every buffer on the DEVICE */
+int rsm_mesh_trim_device(rsm_ctx *ctx, const float *d_xyz, int64_t nv, const int32_t *d_faces, int64_t nf, const float *d_samples_xyz,
+                         const float *d_samples_normals4, int64_t n, const rsm_mesh_trim_params *p, int64_t *n_vertices, int64_t *n_faces, double *stats);
+/* the same on the context's last mesh where it lies (what rsm_poisson_mesh left); the samples are host buffers; the result replaces it */
+int rsm_mesh_trim_last(rsm_ctx *ctx, const float *samples_xyz, const float *samples_normals4, int64_t n, const rsm_mesh_trim_params *p, int64_t *n_vertices,
+                       int64_t *n_faces, double *stats);
+/* stage entry points (host buffers) for the tests.  density: the samples and p's depth, scale, kernel_depth and samples_per_node -> rho and
+ * value at nv points (nv doubles each), counts = {valid, not valid}.  value_smooth: a caller's nv finite values -> the values after `steps`
+ * steps.  split: a caller's nv finite values, trim and island_ratio -> the context's last mesh and stats (may be NULL; [4], [5], [18], [19]
+ * stay 0); src_face / side / label (each 3 nf int32, may be NULL): per output face its source face, its side before the island rule
+ * (1 = kept) and its component (the lowest triangle of the split mesh it is connected to on its side). */
+int rsm_stage_mesh_density(rsm_ctx *ctx, const float *samples_xyz, const float *samples_normals4, int64_t n, const rsm_mesh_trim_params *p, const float *xyz,
+                           int64_t nv, double *rho, double *value, int64_t counts[2]);
+int rsm_stage_mesh_value_smooth(rsm_ctx *ctx, const int32_t *faces, int64_t nv, int64_t nf, const double *values, int steps, double *out_values);
+int rsm_stage_mesh_split(rsm_ctx *ctx, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, const double *values, double trim, double island_ratio,
+                         int64_t *n_vertices, int64_t *n_faces, double *stats, int32_t *src_face, int32_t *side, int32_t *label);
+
 /* ---- colours of the final mesh from the rig's views (where CCloudOptimization::run hands tmp\bigmesh.ply and scans.txt to TextureStitcher,
  * .cpp:394-397; the scans are the per-view meshes filter() colours through texture_color, .cpp:127-143, :400-421) ------------------------
  * Not a bit-parity port of TextureStitcher (no source in the reference tree): the rules as DESIGN.md 9 (f9) defines them.  Its seam

@@ -1,5 +1,6 @@
 """python -m reconstruction_amd <config.yml> [--device N] [--out cloud.ply] [--filter] [--mls [--isdelete] [--mls-out bigcloud.ply]]
                               [--mesh [--mesh-depth 9] [--mesh-trim 4] [--mesh-out bigmesh.ply]
+                               [--mesh-density-trim [7] [--mesh-density-smooth 100] [--mesh-island-ratio 0.01]]
                                [--mesh-clean [--mesh-smooth 5] [--mesh-min-piece 10%]]
                                [--mesh-color [--mesh-color-mode blend] [--mesh-color-min-cos 0.2] [--mesh-color-eps LENGTH]]
                                [--mesh-stitch [--mesh-stitch-lambda 0.01] [--mesh-stitch-iterations 0]]]
@@ -13,6 +14,8 @@ the smoothed, oriented cloud as bigcloud.ply (pcl::PointNormal, savePLYFileBinar
 multi-view duplicate deletion before it (CCloudOptimization.cpp:152-346, on the GPU).
 With --mesh (implies --mls) the surface of that cloud: unscreened Poisson reconstruction on a dense grid and a trim, on the GPU,
 where CCloudOptimization::run calls meshlab.bat's Poisson filter -> bigmesh.ply (not a bit-parity port of that tool: DESIGN.md 9 f7).
+With --mesh-density-trim (implies --mesh) the Poisson call runs without its occupancy trim and the surface is trimmed as mesh.bat's
+SurfaceTrimmer does, on the GPU: cut along the iso-line of the smoothed sample density, small islands moved across.
 With --mesh-clean (implies --mesh) bigmesh.ply is that surface after meshlab.bat's other filters, on the GPU: Laplacian smoothing
 (script1.mlx) and the removal of isolated pieces, duplicate, zero-area and non-manifold faces (script2.mlx).
 With --mesh-color (implies --mesh) the mesh's vertices are coloured from every camera's rectified image, on the GPU, where
@@ -73,6 +76,12 @@ def main(argv=None) -> int:
     ap.add_argument("--mesh-trim", type=int, default=4,
                     help="faces survive within this many cells of a cell that holds a point (4 = mesh.bat's --trim 7 at depth 9; 0 = no trim)")
     ap.add_argument("--mesh-out", default=None, help="path of the mesh (default: bigmesh.ply next to the --out PLY)")
+    ap.add_argument("--mesh-density-trim", type=float, nargs="?", const=7.0, default=None, metavar="T",
+                    help="after the surface (implied; --mesh-trim is then not applied): cut it where the smoothed sample-density value falls below T "
+                         "(mesh.bat's SurfaceTrimmer --trim 7; 7 when given bare) on the GPU, before --mesh-clean")
+    ap.add_argument("--mesh-density-smooth", type=int, default=100, help="with --mesh-density-trim: smoothing steps of the values (SurfaceTrimmer --smooth 100)")
+    ap.add_argument("--mesh-island-ratio", type=float, default=0.01,
+                    help="with --mesh-density-trim: pieces on either side of the cut below this share of the area change side (SurfaceTrimmer --aRatio 0.01; 0 = never)")
     ap.add_argument("--mesh-clean", action="store_true",
                     help="after the surface (implied): meshlab.bat's Laplacian smoothing and clean-up (isolated pieces, duplicate, zero-area "
                          "and non-manifold faces) on the GPU; bigmesh.ply is then the cleaned mesh")
@@ -101,6 +110,8 @@ def main(argv=None) -> int:
     if args.mesh_stitch:
         args.mesh_color = True
     if args.mesh_color:
+        args.mesh = True
+    if args.mesh_density_trim is not None:
         args.mesh = True
     if args.mesh_clean:
         args.mesh = True
@@ -178,11 +189,17 @@ def main(argv=None) -> int:
         from . import RsmError, write_ply_mesh
         t2 = time.perf_counter()
         try:
-            mv, mf, mst = sink.mesh(depth=args.mesh_depth, trim_cells=args.mesh_trim)
+            mv, mf, mst = sink.mesh(depth=args.mesh_depth, trim_cells=args.mesh_trim if args.mesh_density_trim is None else 0)
         except RsmError as e:                                      # e.g. --mesh-depth outside 5..9
             print(e)
             return 1
-        cst = None
+        cst = tst = None
+        if args.mesh_density_trim is not None:
+            try:
+                mv, mf, tst = sink.trim_mesh(smooth_steps=args.mesh_density_smooth, trim=args.mesh_density_trim, island_ratio=args.mesh_island_ratio)
+            except RsmError as e:                                  # e.g. --mesh-island-ratio outside [0, 1)
+                print(e)
+                return 1
         if args.mesh_clean:
             try:
                 mv, mf, cst = sink.clean_mesh(smooth_steps=args.mesh_smooth, min_piece=min_piece, relative=relative)
@@ -193,6 +210,10 @@ def main(argv=None) -> int:
         write_ply_mesh(mesh_out, mv, mf)
         print("Mesh time: %.3f s (%d cycles, residual %.2e%s)" % (time.perf_counter() - t2, mst["cycles"], mst["residual"],
                                                                   "" if mst["converged"] else ", NOT converged"))
+        if tst is not None:
+            print("Mesh density trim: %d faces from %d (%d split along %d cut edges); values %.2f .. %.2f; %d pieces moved to the kept side, %d to the dropped"
+                  % (tst["n_faces"], tst["n_faces_in"], tst["faces_split"], tst["cut_edges"], tst["value_min"], tst["value_max"], tst["moved_to_kept"],
+                     tst["moved_to_dropped"]))
         if cst is not None:
             print("Mesh clean: %d of %d pieces removed (%d faces); %d duplicate, %d zero-area, %d non-manifold faces removed; %d border vertices"
                   % (cst["components_removed"], cst["components"], cst["removed_isolated"], cst["removed_duplicate"], cst["removed_zero_area"],

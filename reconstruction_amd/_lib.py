@@ -84,6 +84,15 @@ MESH_CLEAN_STATS = 14
 MESH_CLEAN_DUPLICATES, MESH_CLEAN_ZERO_AREA, MESH_CLEAN_NONMANIFOLD = 1, 2, 4
 
 
+class MeshTrimParams(C.Structure):
+    """rsm_mesh_trim_params (include/rsm.h)."""
+    _fields_ = [("depth", C.c_int), ("scale", C.c_double), ("kernel_depth", C.c_int), ("samples_per_node", C.c_double), ("smooth_steps", C.c_int),
+                ("trim", C.c_double), ("island_ratio", C.c_double)]
+
+
+MESH_TRIM_STATS = 20
+
+
 class MeshColorParams(C.Structure):
     """rsm_mesh_color_params (include/rsm.h)."""
     _fields_ = [("mode", C.c_int), ("min_cos", C.c_double), ("depth_eps", C.c_double)]
@@ -125,6 +134,7 @@ _I, _L, _U, _LL, _Z, _D, _V, _S = C.c_int, C.c_int64, C.c_uint32, C.c_longlong, 
 _pI, _pL, _pD = C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_double)
 _PIN, _POUT, _BND, _RIN, _ROUT, _FLT = (C.POINTER(t) for t in (PairIn, PairOut, Boundary, RectifyIn, RectifyOut, FilterParams))
 _MLS, _VIEW, _PSN, _CLN, _COL, _STI = (C.POINTER(t) for t in (MlsParams, DedupView, PoissonParams, MeshCleanParams, MeshColorParams, MeshStitchParams))
+_TRM = C.POINTER(MeshTrimParams)
 PROTOTYPES = {
     "rsm_create": (_I, [_V, _I]),
     "rsm_destroy": (None, [_V]),
@@ -212,6 +222,12 @@ PROTOTYPES = {
     "rsm_mesh_clean_last": (_I, [_V, _CLN, _pL, _pL, _V]),
     "rsm_stage_mesh_smooth": (_I, [_V, _V, _L, _V, _L, _I, _I, _I, _V, _pL]),
     "rsm_stage_mesh_components": (_I, [_V, _V, _L, _L, _V, _pL]),
+    "rsm_mesh_trim": (_I, [_V, _V, _L, _V, _L, _V, _V, _L, _TRM, _pL, _pL, _V]),
+    "rsm_mesh_trim_device": (_I, [_V, _V, _L, _V, _L, _V, _V, _L, _TRM, _pL, _pL, _V]),
+    "rsm_mesh_trim_last": (_I, [_V, _V, _V, _L, _TRM, _pL, _pL, _V]),
+    "rsm_stage_mesh_density": (_I, [_V, _V, _V, _L, _TRM, _V, _L, _V, _V, _V]),
+    "rsm_stage_mesh_value_smooth": (_I, [_V, _V, _L, _L, _V, _I, _V]),
+    "rsm_stage_mesh_split": (_I, [_V, _V, _L, _V, _L, _V, _D, _D, _pL, _pL, _V, _V, _V, _V]),
     "rsm_mesh_color": (_I, [_V, _V, _L, _V, _L, _VIEW, _I, _COL, _V, _V, _V]),
     "rsm_mesh_color_device": (_I, [_V, _V, _L, _V, _L, _VIEW, _I, _COL, _V, _V, _V]),
     "rsm_mesh_color_last": (_I, [_V, _VIEW, _I, _COL, _V]),

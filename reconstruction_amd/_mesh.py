@@ -6,13 +6,15 @@ import numpy as np
 
 from . import _lib
 from ._context import ContextBase, _normals4, _p, _u8, _views
-from ._lib import MeshCleanParams, MeshColorParams, MeshStitchParams, PoissonParams
+from ._lib import MeshCleanParams, MeshColorParams, MeshStitchParams, MeshTrimParams, PoissonParams
 
 # the solve's default stopping residual: one decade above the 4.2e-6 the float32 solver reaches at depth 9
 POISSON_REL_RESIDUAL = 4e-5
 POISSON_MAX_CYCLES = 100
 # meshlab.bat's script1 / script2 settings: the defaults of mesh_clean, mesh_clean_device and mesh_clean_last
 _MC = dict(smooth_steps=5, cotangent=True, boundary=True, min_piece=0.10, relative=True, duplicates=True, zero_area=True, nonmanifold=True)
+# mesh.bat's PoissonRecon --samplesPerNode 2 and SurfaceTrimmer --smooth 100 --trim 7 --aRatio 0.01: the defaults of mesh_trim, mesh_trim_device and mesh_trim_last
+_MT = dict(kernel_depth=0, samples_per_node=2.0, smooth_steps=100, trim=7.0, island_ratio=0.01)
 
 
 def _mesh_arrays(vertices, faces):
@@ -167,6 +169,91 @@ class MeshPart(ContextBase):
         nc = C.c_int64()
         self._chk(self._lib.rsm_stage_mesh_components(self._h, _p(f), int(n_vertices), len(f), _p(lab), C.byref(nc)))
         return lab[:len(f)].copy(), int(nc.value)
+
+    # ---- the density trim of the surface: mesh.bat's PoissonRecon --density + SurfaceTrimmer (csrc/k_meshtrim.hip) ----
+    _TRIM_KEYS = ("n_vertices_in", "n_faces_in", "n_vertices", "n_faces", "n_valid", "n_invalid", "cut_edges", "faces_split", "repeated_index_faces",
+                  "zero_area_triangles", "components_kept", "components_dropped", "moved_to_dropped", "moved_to_kept", "q_total")
+
+    @classmethod
+    def _trim_stats(cls, st):
+        stats = {k: int(st[i]) for i, k in enumerate(cls._TRIM_KEYS)}
+        stats.update(value_min=float(st[15]), value_max=float(st[16]), diagonal2=float(st[17]), density_step=float(st[18]), kernel_depth=int(st[19]))
+        return stats
+
+    @staticmethod
+    def _samples(samples_xyz, samples_normals):
+        xyz = np.ascontiguousarray(samples_xyz, np.float32).reshape(-1, 3)
+        return xyz, None if samples_normals is None else _normals4(samples_normals, len(xyz))
+
+    def _mesh_trim(self, fn, mesh_args, sample_args, depth, scale, kernel_depth, samples_per_node, smooth_steps, trim, island_ratio):
+        """One of the three rsm_mesh_trim* entries: (n_vertices, n_faces, stats) of the mesh it leaves with the context."""
+        nv, nf = C.c_int64(), C.c_int64()
+        st = (C.c_double * _lib.MESH_TRIM_STATS)()
+        prm = MeshTrimParams(int(depth), float(scale), int(kernel_depth), float(samples_per_node), int(smooth_steps), float(trim), float(island_ratio))
+        self._chk(fn(self._h, *mesh_args, *sample_args, C.byref(prm), C.byref(nv), C.byref(nf), st))
+        return int(nv.value), int(nf.value), self._trim_stats(st)
+
+    def mesh_trim(self, vertices, faces, samples_xyz, samples_normals=None, depth=9, scale=1.1, kernel_depth=_MT["kernel_depth"],
+                  samples_per_node=_MT["samples_per_node"], smooth_steps=_MT["smooth_steps"], trim=_MT["trim"], island_ratio=_MT["island_ratio"]):
+        """What mesh.bat's PoissonRecon --density and SurfaceTrimmer do to the surface, on the GPU: every vertex gets the depth at which a
+        grid node would hold samples_per_node of the samples around it (a count splat on 2^kernel_depth nodes per axis of the box the
+        Poisson call with this depth and scale used; 0 = depth - 2), the values are smoothed over the mesh smooth_steps times, the surface
+        is cut along value = trim (crossing triangles are split) and pieces on either side of the cut below island_ratio of the whole area
+        change side.  Call poisson_mesh with trim_cells=0 first.  vertices [nv,3] float32, faces [nf,3] int32, samples [n,3] float32 with
+        normals [n,4] / [n,3] or None -> (vertices, faces, stats dict).  The result is the context's last mesh."""
+        v, f = _mesh_arrays(vertices, faces)
+        xyz, nrm = self._samples(samples_xyz, samples_normals)
+        nv, nf, stats = self._mesh_trim(self._lib.rsm_mesh_trim, (_p(v), len(v), _p(f), len(f)), (_p(xyz), None if nrm is None else _p(nrm), len(xyz)), depth, scale,
+                                        kernel_depth, samples_per_node, smooth_steps, trim, island_ratio)
+        return self.poisson_last_mesh(nv, nf) + (stats,)
+
+    def mesh_trim_device(self, vertices_ptr, n_vertices, faces_ptr, n_faces, samples_ptr, normals_ptr, n, depth=9, scale=1.1, **kw):
+        """rsm_mesh_trim_device on device buffers (addresses; normals_ptr may be 0); keywords as mesh_trim.  Returns (n_vertices, n_faces,
+        stats); the mesh stays with the context (poisson_last_mesh[_device] copies it out)."""
+        return self._mesh_trim(self._lib.rsm_mesh_trim_device, (vertices_ptr, n_vertices, faces_ptr, n_faces), (samples_ptr, normals_ptr or None, n), depth, scale,
+                               **{**_MT, **kw})
+
+    def mesh_trim_last(self, samples_xyz, samples_normals=None, depth=9, scale=1.1, kernel_depth=_MT["kernel_depth"],
+                       samples_per_node=_MT["samples_per_node"], smooth_steps=_MT["smooth_steps"], trim=_MT["trim"], island_ratio=_MT["island_ratio"]):
+        """mesh_trim of the context's last mesh (what poisson_mesh left) where it lies on the device; the result replaces it.
+        Returns (vertices, faces, stats)."""
+        xyz, nrm = self._samples(samples_xyz, samples_normals)
+        nv, nf, stats = self._mesh_trim(self._lib.rsm_mesh_trim_last, (), (_p(xyz), None if nrm is None else _p(nrm), len(xyz)), depth, scale, kernel_depth,
+                                        samples_per_node, smooth_steps, trim, island_ratio)
+        return self.poisson_last_mesh(nv, nf) + (stats,)
+
+    def mesh_density(self, samples_xyz, samples_normals, points, depth, scale=1.1, kernel_depth=_MT["kernel_depth"], samples_per_node=_MT["samples_per_node"]):
+        """Stage: the samples -> (rho float64 [m], value float64 [m], (valid, invalid)) at points [m,3] float32."""
+        xyz, nrm = self._samples(samples_xyz, samples_normals)
+        v = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        rho, val = np.zeros(max(len(v), 1), np.float64), np.zeros(max(len(v), 1), np.float64)
+        counts = np.zeros(2, np.int64)
+        prm = MeshTrimParams(int(depth), float(scale), int(kernel_depth), float(samples_per_node), 0, 0.0, 0.0)
+        self._chk(self._lib.rsm_stage_mesh_density(self._h, _p(xyz), None if nrm is None else _p(nrm), len(xyz), C.byref(prm), _p(v), len(v), _p(rho), _p(val),
+                                                   _p(counts)))
+        return rho[:len(v)].copy(), val[:len(v)].copy(), (int(counts[0]), int(counts[1]))
+
+    def mesh_value_smooth(self, values, faces, steps=_MT["smooth_steps"]):
+        """Stage: a caller's values (float64 [nv]) after `steps` smoothing steps over the faces' incidences."""
+        x = np.ascontiguousarray(values, np.float64).reshape(-1)
+        f = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+        out = np.zeros(max(len(x), 1), np.float64)
+        self._chk(self._lib.rsm_stage_mesh_value_smooth(self._h, _p(f), len(x), len(f), _p(x), int(steps), _p(out)))
+        return out[:len(x)].copy()
+
+    def mesh_split(self, vertices, faces, values, trim=_MT["trim"], island_ratio=0.0):
+        """Stage: a caller's values (float64 [nv]) -> (vertices, faces, src_face int32 [nf'], side int32 [nf'] before the island rule,
+        label int32 [nf'], stats) of the mesh cut along value = trim."""
+        v, f = _mesh_arrays(vertices, faces)
+        x = np.ascontiguousarray(values, np.float64).reshape(-1)
+        assert len(x) == len(v)
+        nv, nf = C.c_int64(), C.c_int64()
+        st = (C.c_double * _lib.MESH_TRIM_STATS)()
+        info = [np.zeros(max(3 * len(f), 1), np.int32) for _ in range(3)]
+        self._chk(self._lib.rsm_stage_mesh_split(self._h, _p(v), len(v), _p(f), len(f), _p(x), float(trim), float(island_ratio), C.byref(nv), C.byref(nf), st,
+                                                 *(_p(a) for a in info)))
+        ov, of = self.poisson_last_mesh(int(nv.value), int(nf.value))
+        return (ov, of) + tuple(a[:len(of)].copy() for a in info) + (self._trim_stats(st),)
 
     # ---- colours of the mesh from the rig's views, where run() calls TextureStitcher (DESIGN.md 9 f9; csrc/k_meshcolor.hip) ----
     @staticmethod

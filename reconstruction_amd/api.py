@@ -249,6 +249,7 @@ class CloudOptimization:
     StatisticalOutlierRemoval + NormalEstimation + normal flip of :82-121 on the GPU; the mesh / texture tooling
     after :123 is Windows executables and out of scope), run() (:348-389: MLS over the merged cloud + the normal flip
     on the GPU), mesh() (where run() calls the external Poisson mesher after :389: the dense-grid Poisson surface and trim on the GPU),
+    trim_mesh() (mesh.bat's SurfaceTrimmer: the surface cut where the samples' density falls below a depth, on the GPU),
     clean_mesh() (what meshlab.bat goes on to do: Laplacian smoothing and the removal of isolated pieces and bad faces, on the GPU;
     its hole closing stays an external executable), color_mesh() (where run() ends with TextureStitcher: the mesh's vertices coloured
     from every camera's rectified image, on the GPU; the tool's seam removal is not done).  `cloud_normals` accumulates what the
@@ -321,6 +322,19 @@ class CloudOptimization:
         xyz, nrm = self.cloud_ms_normals[0], self.cloud_ms_normals[1]
         self.mesh_result = self._ctx.poisson_mesh(xyz, nrm, depth, scale, trim_cells, rel_residual, max_cycles)
         self.mesh_grid_step = self.mesh_result[2]["h"]
+        self._mesh_box = (depth, scale)
+        self.mesh_colors = None
+        return self.mesh_result
+
+    def trim_mesh(self, kernel_depth=0, samples_per_node=2.0, smooth_steps=100, trim=7.0, island_ratio=0.01):
+        """Where mesh.bat follows PoissonRecon --density with SurfaceTrimmer --smooth 100 --trim 7 --aRatio 0.01: the density trim of
+        mesh_result (Context.mesh_trim_last on the mesh mesh() left with the context) with the samples and the depth / scale mesh() used;
+        call mesh(trim_cells=0) so that the occupancy trim has not cut the surface already.  Replaces mesh_result."""
+        if getattr(self, "mesh_result", None) is None:
+            raise ValueError("CloudOptimization.trim_mesh: mesh() first (it trims mesh()'s surface by the density of mesh()'s samples)")
+        depth, scale = self._mesh_box
+        self.mesh_result = self._ctx.mesh_trim_last(self.cloud_ms_normals[0], self.cloud_ms_normals[1], depth, scale, kernel_depth, samples_per_node,
+                                                    smooth_steps, trim, island_ratio)
         self.mesh_colors = None
         return self.mesh_result
 

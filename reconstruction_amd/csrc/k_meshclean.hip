@@ -4,7 +4,7 @@
 // MeshLab / VCG (no source in the reference tree): every rule is defined in DESIGN.md 9 (f8) and restated in numpy in
 // tests/meshclean_restatement.py, and the kernels are held to that restatement exactly.
 //   edge table    per face with three distinct indices, edge j = (v_j, v_j+1): key (min << 32) | max, value 3 f + j; rocprim's stable
-//                 radix sort over the key bits in use; a run of equal keys = the faces on one edge (its incidence)   k_mc_edge_keys, k_mc_edge_runs
+//                 radix sort over the key bits in use; a run of equal keys = the faces on one edge (its incidence)   k_mesh_edge_keys, k_mc_edge_runs
 //   corner lists  stable sort of (vertex, 3 f + j): a CSR whose lists ascend                                          k_mc_corner_keys, k_mc_row_starts
 //   smoothing     one thread per vertex gathers through its corner list in ascending (f, j): a fixed order of fp64 basic operations,
 //                 no float atomics -- the same bits from run to run and as the restatement                            k_mc_smooth
@@ -36,8 +36,6 @@ __device__ __forceinline__ void count_if(bool flag, u64 *ctr) {
     if (flag) atomicAdd(ctr, (u64)1);
 }
 
-__device__ __forceinline__ bool face_distinct(int a, int b, int c) { return a != b && b != c && a != c; }
-
 // ---- validation: every index in [0, nv), every coordinate finite --------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_mc_validate(const float *__restrict__ v, size_t n_coords, const int32_t *__restrict__ f, size_t nv, size_t nf,
                                                      u64 *__restrict__ ctr) {
@@ -49,47 +47,7 @@ __global__ __launch_bounds__(256) void k_mc_validate(const float *__restrict__ v
     count_if(bad_i, ctr + C_BAD_INDEX);
 }
 
-// ---- the edge table -----------------------------------------------------------------------------------------------------------------
-// entry 3 f + j: key (min << 32) | max of edge j = (v_j, v_j+1); a face with a repeated index gets the key after every edge, nv << 32
-__global__ __launch_bounds__(256) void k_mc_edge_keys(const int32_t *__restrict__ f, size_t nf, u64 nv, u64 *__restrict__ key, uint32_t *__restrict__ val) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= nf) return;
-    const int v[3] = {f[3 * i], f[3 * i + 1], f[3 * i + 2]};
-    const bool ok = face_distinct(v[0], v[1], v[2]);
-    for (int j = 0; j < 3; j++) {
-        const u64 a = (u64)v[j], b = (u64)v[(j + 1) % 3];
-        key[3 * i + j] = ok ? ((a < b ? a : b) << 32 | (a < b ? b : a)) : nv << 32;
-        val[3 * i + j] = (uint32_t)(3 * i + j);
-    }
-}
-
-__device__ __forceinline__ int uf_load(int *parent, int x) { return __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-// the root of x; halves the path on the way (a parent only ever moves to an ancestor, and ancestors have lower indices)
-__device__ __forceinline__ int uf_find(int *parent, int x) {
-    int p = uf_load(parent, x);
-    while (p != x) {
-        const int g = uf_load(parent, p);
-        if (g != p) atomicMin(parent + x, g);
-        x = p;
-        p = g;
-    }
-    return x;
-}
-// the larger root hooks under the smaller, so every root is the lowest index of its tree whatever the order of the hooks
-__device__ __forceinline__ void uf_union(int *parent, int a, int b) {
-    for (;;) {
-        a = uf_find(parent, a);
-        b = uf_find(parent, b);
-        if (a == b) return;
-        if (a > b) {
-            const int t = a;
-            a = b;
-            b = t;
-        }
-        if (atomicCAS(parent + b, b, a) == b) return; // (b was still a root; otherwise somebody hooked it first: again)
-    }
-}
-
+// ---- the edge table (keys and union-find: mesh_common.h) -------------------------------------------------------------------------------
 // one thread per sorted entry.  The first of a run counts the run (the edge's incidence), writes min(incidence, 3) to each of its
 // entries' corners and marks both endpoints of an incidence-1 edge as border; every other entry unites its face with the one before.
 __global__ __launch_bounds__(256) void k_mc_edge_runs(const u64 *__restrict__ key, const uint32_t *__restrict__ val, size_t n, u64 nv,
@@ -221,10 +179,6 @@ __global__ __launch_bounds__(256) void k_mc_count_u8(const uint8_t *__restrict__
 }
 
 // ---- components ---------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_mc_iota(int *__restrict__ a, size_t n) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) a[i] = (int)i;
-}
 // label = the root (the lowest face of the component); -1 for a face with a repeated index.  (Runs after every union, in a launch of its own.)
 __global__ __launch_bounds__(256) void k_mc_labels(const int32_t *__restrict__ f, size_t nf, int *__restrict__ parent, int32_t *__restrict__ label, u64 *__restrict__ ctr) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -420,14 +374,14 @@ static int edge_table(DevMem &M, Tables &T, const int32_t *d_f, size_t nv, size_
     }
     if (want_uf) T.parent = M.get<int>(nf);
     if (!M.ok) return RSM_E_NOMEM;
-    hipLaunchKernelGGL(k_mc_edge_keys, blocks_for(nf), dim3(256), 0, st, d_f, nf, (u64)nv, k0, v0);
+    hipLaunchKernelGGL(k_mesh_edge_keys<>, blocks_for(nf), dim3(256), 0, st, d_f, nf, (u64)nv, k0, v0);
     const int s = sort_pairs(M, k0, T.ekey, v0, T.eval, n, 32 + key_bits((u64)nv), st);
     if (s != RSM_OK) return s;
     if (want_inc) {
         DEVCHK(hipMemsetAsync(T.einc, 0, n, st));
         DEVCHK(hipMemsetAsync(T.vborder, 0, nv ? nv : 1, st));
     }
-    if (want_uf) hipLaunchKernelGGL(k_mc_iota, blocks_for(nf), dim3(256), 0, st, T.parent, nf);
+    if (want_uf) hipLaunchKernelGGL(k_mesh_iota<>, blocks_for(nf), dim3(256), 0, st, T.parent, nf);
     hipLaunchKernelGGL(k_mc_edge_runs, blocks_for(n), dim3(256), 0, st, (const u64 *)T.ekey, (const uint32_t *)T.eval, n, (u64)nv, T.einc, T.vborder, T.parent);
     return RSM_OK;
 }

@@ -42,22 +42,10 @@ struct TetTable {
     uint8_t e[16][2][3]; // edge code u << 2 | v
 };
 
-__device__ __forceinline__ bool pv_valid(const float *__restrict__ xyz, const float *__restrict__ nrm, int64_t s, double p[3], double nh[3]) {
-    const float x = xyz[3 * s], y = xyz[3 * s + 1], z = xyz[3 * s + 2];
-    const float a = nrm[4 * s], b = nrm[4 * s + 1], c = nrm[4 * s + 2];
-    if (!(isfinite(x) && isfinite(y) && isfinite(z) && isfinite(a) && isfinite(b) && isfinite(c))) return false;
-    const double da = (double)a, db = (double)b, dc = (double)c;
-    const double nn = (da * da + db * db) + dc * dc;
-    if (!(nn > 0.0)) return false;
-    const double len = sqrt(nn);
-    nh[0] = da / len; nh[1] = db / len; nh[2] = dc / len;
-    p[0] = (double)x; p[1] = (double)y; p[2] = (double)z;
-    return true;
-}
-
 // ---- 1: valid samples and their bounding box: mm[0..2] = min, mm[3..5] = max (ordered uints), cnt[0] = valid ------------------
-__global__ __launch_bounds__(256) void k_pv_bbox(const float *__restrict__ xyz, const float *__restrict__ nrm, int64_t n, unsigned int *__restrict__ mm,
-                                                 unsigned long long *__restrict__ cnt) {
+template <bool HAS_N>
+__device__ __forceinline__ void pv_bbox_body(const float *__restrict__ xyz, const float *__restrict__ nrm, int64_t n, unsigned int *__restrict__ mm,
+                                             unsigned long long *__restrict__ cnt) {
     __shared__ unsigned int s_mm[6];
     __shared__ unsigned int s_cnt;
     if (threadIdx.x < 6) s_mm[threadIdx.x] = threadIdx.x < 3 ? 0xffffffffu : 0u;
@@ -65,7 +53,7 @@ __global__ __launch_bounds__(256) void k_pv_bbox(const float *__restrict__ xyz, 
     __syncthreads();
     for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < n; s += (int64_t)gridDim.x * blockDim.x) {
         double p[3], nh[3];
-        if (!pv_valid(xyz, nrm, s, p, nh)) continue;
+        if (!(HAS_N ? pv_valid(xyz, nrm, s, p, nh) : pv_valid_point(xyz, s, p))) continue;
         for (int a = 0; a < 3; a++) {
             const unsigned int o = f2ord(xyz[3 * s + a]);
             atomicMin(&s_mm[a], o);
@@ -77,6 +65,14 @@ __global__ __launch_bounds__(256) void k_pv_bbox(const float *__restrict__ xyz, 
     if (threadIdx.x < 3) atomicMin(&mm[threadIdx.x], s_mm[threadIdx.x]);
     else if (threadIdx.x < 6) atomicMax(&mm[threadIdx.x], s_mm[threadIdx.x]);
     if (threadIdx.x == 0 && s_cnt) atomicAdd(cnt, (unsigned long long)s_cnt);
+}
+__global__ __launch_bounds__(256) void k_pv_bbox(const float *__restrict__ xyz, const float *__restrict__ nrm, int64_t n, unsigned int *__restrict__ mm,
+                                                 unsigned long long *__restrict__ cnt) {
+    pv_bbox_body<true>(xyz, nrm, n, mm, cnt);
+}
+// the density trim's samples without normals: a finite point is a valid sample
+__global__ __launch_bounds__(256) void k_pv_bbox_points(const float *__restrict__ xyz, int64_t n, unsigned int *__restrict__ mm, unsigned long long *__restrict__ cnt) {
+    pv_bbox_body<false>(xyz, nullptr, n, mm, cnt);
 }
 
 // ---- 3: splat -----------------------------------------------------------------------------------------------------------------
@@ -468,7 +464,8 @@ int poisson_grid_device(const float *d_xyz, const float *d_nrm4, int64_t n, int 
     const unsigned int init[6] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0u, 0u, 0u};
     DEVCHK(hipMemcpyAsync(mm, init, sizeof init, hipMemcpyHostToDevice, st));
     DEVCHK(hipMemsetAsync(cnt, 0, sizeof *cnt, st));
-    hipLaunchKernelGGL(k_pv_bbox, dim3(red_blocks((size_t)n)), dim3(256), 0, st, d_xyz, d_nrm4, n, mm, cnt);
+    if (d_nrm4) hipLaunchKernelGGL(k_pv_bbox, dim3(red_blocks((size_t)n)), dim3(256), 0, st, d_xyz, d_nrm4, n, mm, cnt);
+    else hipLaunchKernelGGL(k_pv_bbox_points, dim3(red_blocks((size_t)n)), dim3(256), 0, st, d_xyz, n, mm, cnt);
     unsigned int h_mm[6];
     unsigned long long h_cnt = 0;
     DEVCHK(hipMemcpyAsync(h_mm, mm, sizeof h_mm, hipMemcpyDeviceToHost, st));

@@ -228,7 +228,7 @@ struct PoissonMesh { // a library-owned result: nv float xyz, nf int32 x 3
     int64_t nv = 0, nf = 0;
 };
 void poisson_mesh_free(PoissonMesh *m);
-// grid = {origin x, y, z, h} (h = 0: no valid sample or all points equal), counts = {valid, not valid}
+// grid = {origin x, y, z, h} (h = 0: no valid sample or all points equal), counts = {valid, not valid}; d_nrm4 = NULL: a finite point is valid
 int poisson_grid_device(const float *d_xyz, const float *d_nrm4, int64_t n, int depth, double scale, double grid[4], int64_t counts[2], hipStream_t st);
 // splat + right-hand side: b as float (the solver's) and / or as double (exact from the fixed-point sums), occ = N^3 bytes
 int poisson_rhs_device(const float *d_xyz, const float *d_nrm4, int64_t n, int depth, const double grid[4], float *d_b32, double *d_b64, uint8_t *d_occ,
@@ -253,6 +253,23 @@ int mesh_components_device(const int32_t *d_f, int64_t nv, int64_t nf, int32_t *
 // the result replaces *out, which may own d_v / d_f (it is freed after the last read); stats: RSM_MESH_CLEAN_STATS doubles, may be NULL
 int mesh_clean_device(const float *d_v, int64_t nv, const int32_t *d_f, int64_t nf, const rsm_mesh_clean_params *p, PoissonMesh *out, double *stats, int *invalid,
                       hipStream_t st);
+
+// the density trim of the surface (k_meshtrim.hip).  Device buffers: n float xyz samples with float4 normals (d_sn4 may be
+// NULL: a finite point is a valid sample), nv float xyz, nf int32 x 3.  Parameters are the caller's to check; each call validates the
+// mesh it is given, and RSM_E_INVALID comes with *invalid as mesh_clean_device's.
+struct rsm_mesh_trim_params;
+// rho (may be NULL) and value at the vertices; counts = {valid, not valid} samples, *hk = the density grid's step (0: every value is 0)
+int mesh_density_device(const float *d_sx, const float *d_sn4, int64_t n, int depth, double scale, int kernel_depth, double samples_per_node, const float *d_v,
+                        int64_t nv, double *d_rho, double *d_val, int64_t counts[2], double *hk, int *invalid, hipStream_t st);
+// nv values after `steps` steps over the mesh's incidences; d_out may not alias d_in
+int mesh_value_smooth_device(const int32_t *d_f, int64_t nv, int64_t nf, const double *d_in, int steps, double *d_out, int *invalid, hipStream_t st);
+// split, island rule and compaction of a mesh by nv values; the result replaces *out, which may own d_v / d_f.  d_src / d_side /
+// d_label (each 3 nf int32, may be NULL): per output face its source face, its side before the island rule, its component's lowest triangle
+int mesh_split_device(const float *d_v, int64_t nv, const int32_t *d_f, int64_t nf, const double *d_val, double trim, double island_ratio, PoissonMesh *out,
+                      int32_t *d_src, int32_t *d_side, int32_t *d_label, double *stats, int *invalid, hipStream_t st);
+// the whole call
+int mesh_trim_device(const float *d_v, int64_t nv, const int32_t *d_f, int64_t nf, const float *d_sx, const float *d_sn4, int64_t n, const rsm_mesh_trim_params *p,
+                     PoissonMesh *out, double *stats, int *invalid, hipStream_t st);
 
 // colours of a mesh from the rig's views (k_meshcolor.hip).  Device buffers: nv float xyz, nf int32 x 3, d_rgb nv x 3 bytes,
 // d_best nv int32 (may be NULL); the views' images are host pointers and are uploaded here.  RSM_E_INVALID comes with *invalid = 1 (a face

@@ -1,5 +1,5 @@
-// rsm_mesh.hip -- the mesh back end's host side: the dense-grid Poisson surface, its smoothing and clean-up, and its colours
-// from the rig's views with their seams levelled (k_poisson.hip, k_meshclean.hip, k_meshcolor.hip, k_meshstitch.hip).
+// rsm_mesh.hip -- the mesh back end's host side: the dense-grid Poisson surface, its smoothing and clean-up, its density trim, and its colours
+// from the rig's views with their seams levelled (k_poisson.hip, k_meshclean.hip, k_meshtrim.hip, k_meshcolor.hip, k_meshstitch.hip).
 #include "rsm_ctx.h"
 
 #include <cmath>
@@ -184,7 +184,7 @@ static int meshclean_params_ok(rsm_ctx *c, const rsm_mesh_clean_params *p) {
         return set_err(c, RSM_E_INVALID, "mesh_clean: flags 0x%x has an unknown bit", p->flags);
     return RSM_OK;
 }
-static int mesh_counts_ok(rsm_ctx *c, const char *who, int64_t nv, int64_t nf) { // who: "mesh_clean" / "mesh_color"
+static int mesh_counts_ok(rsm_ctx *c, const char *who, int64_t nv, int64_t nf) { // who: "mesh_clean" / "mesh_trim" / "mesh_color"
     if (nv < 0 || nv > (int64_t)INT32_MAX) return set_err(c, RSM_E_INVALID, "%s: nv %lld outside 0..INT32_MAX", who, (long long)nv);
     if (nf < 0 || 3 * nf >= ((int64_t)1 << 31)) return set_err(c, RSM_E_INVALID, "%s: nf %lld negative or 3 nf >= 2^31", who, (long long)nf);
     return RSM_OK;
@@ -273,6 +273,158 @@ extern "C" int rsm_stage_mesh_components(rsm_ctx *c, const int32_t *faces, int64
     int invalid = 0;
     if ((s = mesh_components_device(df, nv, nf, dl, n_components, &invalid, c->stream)) != RSM_OK) return meshclean_fail(c, s, invalid);
     if (nf > 0) HIPCHK(c, hipMemcpyAsync(labels, dl, sizeof(int32_t) * (size_t)nf, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RSM_OK;
+}
+
+// ---- the density trim of the surface (k_meshtrim.hip) -------------------------------------------------------------------
+static int meshtrim_params_ok(rsm_ctx *c, const rsm_mesh_trim_params *p) {
+    if (!p) return set_err(c, RSM_E_INVALID, "mesh_trim: params is NULL");
+    if (p->depth < 5 || p->depth > 9) return set_err(c, RSM_E_INVALID, "mesh_trim: depth %d outside 5..9", p->depth);
+    if (!std::isfinite(p->scale) || p->scale < 1.0) return set_err(c, RSM_E_INVALID, "mesh_trim: scale %g not finite or < 1", p->scale);
+    if (p->kernel_depth != 0 && (p->kernel_depth < 3 || p->kernel_depth > p->depth))
+        return set_err(c, RSM_E_INVALID, "mesh_trim: kernel_depth %d neither 0 nor in 3..depth (%d)", p->kernel_depth, p->depth);
+    if (!std::isfinite(p->samples_per_node) || !(p->samples_per_node > 0.0))
+        return set_err(c, RSM_E_INVALID, "mesh_trim: samples_per_node %g not finite or not > 0", p->samples_per_node);
+    if (p->smooth_steps < 0) return set_err(c, RSM_E_INVALID, "mesh_trim: smooth_steps %d < 0", p->smooth_steps);
+    if (!std::isfinite(p->trim)) return set_err(c, RSM_E_INVALID, "mesh_trim: trim %g not finite", p->trim);
+    if (!(p->island_ratio >= 0.0 && p->island_ratio < 1.0)) return set_err(c, RSM_E_INVALID, "mesh_trim: island_ratio %g not in [0, 1)", p->island_ratio);
+    return RSM_OK;
+}
+static int meshtrim_n_ok(rsm_ctx *c, int64_t n) {
+    if (n < 0 || n > (int64_t)INT32_MAX) return set_err(c, RSM_E_INVALID, "mesh_trim: n %lld outside 0..INT32_MAX", (long long)n);
+    return RSM_OK;
+}
+static int meshtrim_fail(rsm_ctx *c, int s, int invalid) {
+    if (s == RSM_E_INVALID) return set_err(c, s, invalid == 1 ? "mesh_trim: a face index outside [0, nv)" : "mesh_trim: a coordinate that is not finite");
+    if (s == RSM_E_NOMEM) return set_err(c, s, "mesh_trim: no device memory");
+    return set_err(c, s, "mesh_trim: failed%s", hip_tail(s).c_str());
+}
+static int meshtrim_values_ok(rsm_ctx *c, const double *values, int64_t nv) {
+    for (int64_t i = 0; i < nv; i++)
+        if (!std::isfinite(values[i])) return set_err(c, RSM_E_INVALID, "mesh_trim: values[%lld] is not finite", (long long)i);
+    return RSM_OK;
+}
+// d_xyz / d_faces may be c->pmesh's own buffers
+static int meshtrim_run(rsm_ctx *c, const float *d_xyz, int64_t nv, const int32_t *d_faces, int64_t nf, const float *d_sx, const float *d_sn, int64_t n,
+                        const rsm_mesh_trim_params *p, int64_t *n_vertices, int64_t *n_faces, double *stats) {
+    int invalid = 0;
+    const int s = mesh_trim_device(d_xyz, nv, d_faces, nf, d_sx, d_sn, n, p, &c->pmesh, stats, &invalid, c->stream);
+    if (s != RSM_OK) return meshtrim_fail(c, s, invalid);
+    c->mcol_of = nullptr; // (the colours belonged to the mesh this one replaces)
+    *n_vertices = c->pmesh.nv;
+    *n_faces = c->pmesh.nf;
+    return RSM_OK;
+}
+
+extern "C" int rsm_mesh_trim_device(rsm_ctx *c, const float *d_xyz, int64_t nv, const int32_t *d_faces, int64_t nf, const float *d_samples_xyz,
+                                    const float *d_samples_normals4, int64_t n, const rsm_mesh_trim_params *p, int64_t *n_vertices, int64_t *n_faces, double *stats) {
+    if (!c) return RSM_E_INVALID;
+    int s = meshtrim_params_ok(c, p);
+    if (s != RSM_OK || (s = mesh_counts_ok(c, "mesh_trim", nv, nf)) != RSM_OK || (s = meshtrim_n_ok(c, n)) != RSM_OK) return s;
+    if (!n_vertices || !n_faces || (nv > 0 && !d_xyz) || (nf > 0 && !d_faces) || (n > 0 && !d_samples_xyz)) return set_err(c, RSM_E_INVALID, "mesh_trim: a NULL pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    return meshtrim_run(c, d_xyz, nv, d_faces, nf, d_samples_xyz, d_samples_normals4, n, p, n_vertices, n_faces, stats);
+}
+
+extern "C" int rsm_mesh_trim(rsm_ctx *c, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, const float *samples_xyz, const float *samples_normals4,
+                             int64_t n, const rsm_mesh_trim_params *p, int64_t *n_vertices, int64_t *n_faces, double *stats) {
+    if (!c) return RSM_E_INVALID;
+    int s = meshtrim_params_ok(c, p);
+    if (s != RSM_OK || (s = mesh_counts_ok(c, "mesh_trim", nv, nf)) != RSM_OK || (s = meshtrim_n_ok(c, n)) != RSM_OK) return s;
+    if (!n_vertices || !n_faces || (nv > 0 && !xyz) || (nf > 0 && !faces) || (n > 0 && !samples_xyz)) return set_err(c, RSM_E_INVALID, "mesh_trim: a NULL pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    Tmp T(c);
+    float *dv = T.up(xyz, 3 * (size_t)nv), *dx = T.up(samples_xyz, 3 * (size_t)n), *dn = samples_normals4 ? T.up(samples_normals4, 4 * (size_t)n) : nullptr;
+    int32_t *df = T.up(faces, 3 * (size_t)nf);
+    if (!dv || !dx || !df || (samples_normals4 && !dn))
+        return set_err(c, RSM_E_NOMEM, "mesh_trim: no device memory for %lld vertices, %lld faces, %lld samples", (long long)nv, (long long)nf, (long long)n);
+    if ((s = finish(c, T)) != RSM_OK) return s;
+    return meshtrim_run(c, dv, nv, df, nf, dx, dn, n, p, n_vertices, n_faces, stats);
+}
+
+extern "C" int rsm_mesh_trim_last(rsm_ctx *c, const float *samples_xyz, const float *samples_normals4, int64_t n, const rsm_mesh_trim_params *p, int64_t *n_vertices,
+                                  int64_t *n_faces, double *stats) {
+    if (!c) return RSM_E_INVALID;
+    int s = meshtrim_params_ok(c, p);
+    if (s != RSM_OK || (s = meshtrim_n_ok(c, n)) != RSM_OK) return s;
+    if (!n_vertices || !n_faces || (n > 0 && !samples_xyz)) return set_err(c, RSM_E_INVALID, "mesh_trim: a NULL pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    Tmp T(c);
+    float *dx = T.up(samples_xyz, 3 * (size_t)n), *dn = samples_normals4 ? T.up(samples_normals4, 4 * (size_t)n) : nullptr;
+    if (!dx || (samples_normals4 && !dn)) return set_err(c, RSM_E_NOMEM, "mesh_trim: no device memory for %lld samples", (long long)n);
+    if ((s = finish(c, T)) != RSM_OK) return s;
+    return meshtrim_run(c, c->pmesh.d_v, c->pmesh.nv, c->pmesh.d_f, c->pmesh.nf, dx, dn, n, p, n_vertices, n_faces, stats);
+}
+
+extern "C" int rsm_stage_mesh_density(rsm_ctx *c, const float *samples_xyz, const float *samples_normals4, int64_t n, const rsm_mesh_trim_params *p, const float *xyz,
+                                      int64_t nv, double *rho, double *value, int64_t counts[2]) {
+    if (!c) return RSM_E_INVALID;
+    int s = meshtrim_params_ok(c, p);
+    if (s != RSM_OK || (s = mesh_counts_ok(c, "mesh_trim", nv, 0)) != RSM_OK || (s = meshtrim_n_ok(c, n)) != RSM_OK) return s;
+    if (!counts || (nv > 0 && (!xyz || !rho || !value)) || (n > 0 && !samples_xyz)) return set_err(c, RSM_E_INVALID, "mesh_trim: a NULL pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    Tmp T(c);
+    float *dv = T.up(xyz, 3 * (size_t)nv), *dx = T.up(samples_xyz, 3 * (size_t)n), *dn = samples_normals4 ? T.up(samples_normals4, 4 * (size_t)n) : nullptr;
+    double *dr = T.alloc<double>((size_t)nv), *da = T.alloc<double>((size_t)nv);
+    if (!dv || !dx || !dr || !da || (samples_normals4 && !dn)) return set_err(c, RSM_E_NOMEM, "mesh_trim: no device memory");
+    if ((s = finish(c, T)) != RSM_OK) return s;
+    int invalid = 0;
+    double hk = 0.0;
+    const int kd = p->kernel_depth ? p->kernel_depth : p->depth - 2;
+    if ((s = mesh_density_device(dx, dn, n, p->depth, p->scale, kd, p->samples_per_node, dv, nv, dr, da, counts, &hk, &invalid, c->stream)) != RSM_OK)
+        return meshtrim_fail(c, s, invalid);
+    if (nv > 0) HIPCHK(c, hipMemcpyAsync(rho, dr, sizeof(double) * (size_t)nv, hipMemcpyDeviceToHost, c->stream));
+    if (nv > 0) HIPCHK(c, hipMemcpyAsync(value, da, sizeof(double) * (size_t)nv, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RSM_OK;
+}
+
+extern "C" int rsm_stage_mesh_value_smooth(rsm_ctx *c, const int32_t *faces, int64_t nv, int64_t nf, const double *values, int steps, double *out_values) {
+    if (!c) return RSM_E_INVALID;
+    int s = mesh_counts_ok(c, "mesh_trim", nv, nf);
+    if (s != RSM_OK) return s;
+    if (steps < 0) return set_err(c, RSM_E_INVALID, "mesh_trim: smooth_steps %d < 0", steps);
+    if ((nv > 0 && (!values || !out_values)) || (nf > 0 && !faces)) return set_err(c, RSM_E_INVALID, "mesh_trim: a NULL pointer");
+    if ((s = meshtrim_values_ok(c, values, nv)) != RSM_OK) return s;
+    HIPCHK(c, hipSetDevice(c->device));
+    Tmp T(c);
+    int32_t *df = T.up(faces, 3 * (size_t)nf);
+    double *din = T.up(values, (size_t)nv), *dout = T.alloc<double>((size_t)nv);
+    if (!df || !din || !dout) return set_err(c, RSM_E_NOMEM, "mesh_trim: no device memory");
+    if ((s = finish(c, T)) != RSM_OK) return s;
+    int invalid = 0;
+    if ((s = mesh_value_smooth_device(df, nv, nf, din, steps, dout, &invalid, c->stream)) != RSM_OK) return meshtrim_fail(c, s, invalid);
+    if (nv > 0) HIPCHK(c, hipMemcpyAsync(out_values, dout, sizeof(double) * (size_t)nv, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RSM_OK;
+}
+
+extern "C" int rsm_stage_mesh_split(rsm_ctx *c, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, const double *values, double trim, double island_ratio,
+                                    int64_t *n_vertices, int64_t *n_faces, double *stats, int32_t *src_face, int32_t *side, int32_t *label) {
+    if (!c) return RSM_E_INVALID;
+    const rsm_mesh_trim_params p{5, 1.0, 0, 1.0, 0, trim, island_ratio};
+    int s = meshtrim_params_ok(c, &p);
+    if (s != RSM_OK || (s = mesh_counts_ok(c, "mesh_trim", nv, nf)) != RSM_OK) return s;
+    if (!n_vertices || !n_faces || (nv > 0 && (!xyz || !values)) || (nf > 0 && !faces)) return set_err(c, RSM_E_INVALID, "mesh_trim: a NULL pointer");
+    if ((s = meshtrim_values_ok(c, values, nv)) != RSM_OK) return s;
+    HIPCHK(c, hipSetDevice(c->device));
+    Tmp T(c);
+    float *dv = T.up(xyz, 3 * (size_t)nv);
+    int32_t *df = T.up(faces, 3 * (size_t)nf), *dsrc = T.alloc<int32_t>(3 * (size_t)nf), *dside = T.alloc<int32_t>(3 * (size_t)nf), *dlab = T.alloc<int32_t>(3 * (size_t)nf);
+    double *dx = T.up(values, (size_t)nv);
+    if (!dv || !df || !dsrc || !dside || !dlab || !dx) return set_err(c, RSM_E_NOMEM, "mesh_trim: no device memory");
+    if ((s = finish(c, T)) != RSM_OK) return s;
+    int invalid = 0;
+    if ((s = mesh_split_device(dv, nv, df, nf, dx, trim, island_ratio, &c->pmesh, dsrc, dside, dlab, stats, &invalid, c->stream)) != RSM_OK)
+        return meshtrim_fail(c, s, invalid);
+    c->mcol_of = nullptr;
+    *n_vertices = c->pmesh.nv;
+    *n_faces = c->pmesh.nf;
+    const size_t m = (size_t)c->pmesh.nf;
+    if (m > 0 && src_face) HIPCHK(c, hipMemcpyAsync(src_face, dsrc, sizeof(int32_t) * m, hipMemcpyDeviceToHost, c->stream));
+    if (m > 0 && side) HIPCHK(c, hipMemcpyAsync(side, dside, sizeof(int32_t) * m, hipMemcpyDeviceToHost, c->stream));
+    if (m > 0 && label) HIPCHK(c, hipMemcpyAsync(label, dlab, sizeof(int32_t) * m, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return RSM_OK;
 }
