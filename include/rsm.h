@@ -541,7 +541,8 @@ int rsm_write_ply_mesh(const char *path, const float *xyz, int64_t n_vertices, c
 /* ---- smoothing and clean-up of the surface (where meshlab.bat goes on after the Poisson filter: script1.mlx's "Laplacian Smooth", then
  * script2.mlx's "Remove Isolated pieces (wrt Diameter)", "Remove Duplicate Faces", "Remove Zero Area Faces", "Remove Faces from Non
  * Manifold Edges" -> bigmesh.ply) ------------------------------------------------------------------------------------------------------
- * Not a bit-parity port of MeshLab / VCG: the rules as DESIGN.md 9 (f8) defines them.  "Close Holes" is not done. */
+ * Not a bit-parity port of MeshLab / VCG: the rules as DESIGN.md 9 (f8) defines them.  script2.mlx's last filter, "Close Holes", is
+ * rsm_mesh_close_holes below. */
 #define RSM_MESH_CLEAN_DUPLICATES 1u  /* flags: of the faces with the same three vertices the lowest index stays */
 #define RSM_MESH_CLEAN_ZERO_AREA 2u   /*        faces with a repeated index or without area go */
 #define RSM_MESH_CLEAN_NONMANIFOLD 4u /*        every face on an edge that more than two surviving faces share goes */
@@ -574,6 +575,43 @@ int rsm_mesh_clean_last(rsm_ctx *ctx, const rsm_mesh_clean_params *p, int64_t *n
 int rsm_stage_mesh_smooth(rsm_ctx *ctx, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, int steps, int cotangent, int boundary,
                           float *out_xyz, int64_t *n_border);
 int rsm_stage_mesh_components(rsm_ctx *ctx, const int32_t *faces, int64_t nv, int64_t nf, int32_t *labels, int64_t *n_components);
+
+/* ---- the closing of the surface's small holes (script2.mlx's last filter, "Close Holes" with MaxHoleSize 30) ---------------------------
+ * Not a bit-parity port of MeshLab / VCG: the rules as DESIGN.md 9 (f12) defines them.  The script runs the filter on a selection that its
+ * earlier filters leave empty; here EVERY border loop is a candidate.  With the edge table of the clean-up, an entry 3 f + j whose edge no
+ * other face has is a border entry, directed as its face; a vertex is simple when one border entry reaches it and one leaves it; border
+ * entries are linked through simple vertices, and a component all of whose vertices are simple is a loop (everything else -- bow-ties,
+ * faces oriented against each other, chains that end -- is open and is never closed).  A loop of at most max_hole_size edges that is not
+ * the border of a lone triangle gets the least-area triangulation of its ring (Barequet-Sharir; no refinement, no fairing) that uses no
+ * diagonal the mesh already has as an edge and no triangle without area; a loop without such a triangulation stays whole.  The vertices and
+ * the input's faces are untouched and in place; the new faces follow them, hole by hole in the order of the holes' lowest entry, oriented
+ * like their neighbours.  Opt-in: no other call changes. */
+#define RSM_MESH_CLOSE_MAX_HOLE 64
+typedef struct rsm_mesh_close_params {
+    int max_hole_size;       /* 3..RSM_MESH_CLOSE_MAX_HOLE: loops of more edges stay open (script2: 30) */
+} rsm_mesh_close_params;
+/* stats: [0] / [1] vertices / faces in, [2] faces out, [3] border entries, [4] border components, [5] loops, [6] open components, [7] loops
+ * closed, [8] loops skipped as too long, [9] lone triangles, [10] loops without an admissible triangulation, [11] faces added, [12] / [13]
+ * the longest loop closed / seen */
+#define RSM_MESH_CLOSE_STATS 14
+/* nv vertices (xyz nv*3 float) and nf faces (faces nf*3 int32) in host buffers -> the context's last mesh, as rsm_mesh_clean
+ * (rsm_poisson_last_mesh copies it out; *n_vertices = nv, *n_faces size its buffers; colours of the last mesh are dropped).  An empty mesh
+ * in: an empty mesh, RSM_OK.  RSM_E_INVALID (rsm_last_error names the cause): max_hole_size outside 3..64, a face index outside [0, nv), a
+ * coordinate that is not finite, 3 nf >= 2^31, nv above INT32_MAX, a negative count, a NULL pointer. */
+int rsm_mesh_close_holes(rsm_ctx *ctx, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, const rsm_mesh_close_params *p, int64_t *n_vertices,
+                         int64_t *n_faces, double *stats);
+/* the same on DEVICE buffers */
+int rsm_mesh_close_holes_device(rsm_ctx *ctx, const float *d_xyz, int64_t nv, const int32_t *d_faces, int64_t nf, const rsm_mesh_close_params *p,
+                                int64_t *n_vertices, int64_t *n_faces, double *stats);
+/* the same on the context's last mesh where it lies (what rsm_poisson_mesh / rsm_mesh_trim / rsm_mesh_clean left); the result replaces it */
+int rsm_mesh_close_holes_last(rsm_ctx *ctx, const rsm_mesh_close_params *p, int64_t *n_vertices, int64_t *n_faces, double *stats);
+/* stage entry points (host buffers) for the tests.  border_loops: per entry 3 f + j (3 nf int32 each) labels = the lowest entry of its border
+ * component (-1: no border entry) and sizes = L for a loop's entries, 0 for an open component's, -1 otherwise; *n_components = the border
+ * components.  hole_triangulate: a ring of L (3..64) finite points (ring_xyz L*3 float) and forbidden (L*L bytes or NULL: pair (i, j),
+ * i + 2 <= j, (i, j) != (0, L-1), is forbidden when byte i*L + j is not 0) -> *weight = W(0, L-1), triangles ((L-2)*3 int32 of ring
+ * positions, in the order of the output) and *n_triangles = L - 2; +inf and 0 when the ring has no admissible triangulation. */
+int rsm_stage_mesh_border_loops(rsm_ctx *ctx, const int32_t *faces, int64_t nv, int64_t nf, int32_t *labels, int32_t *sizes, int64_t *n_components);
+int rsm_stage_hole_triangulate(rsm_ctx *ctx, const float *ring_xyz, int L, const uint8_t *forbidden, double *weight, int32_t *triangles, int *n_triangles);
 
 /* ---- the density trim of the surface (where mesh.bat runs PoissonRecon --density --samplesPerNode 2 and then SurfaceTrimmer --smooth 100
  * --trim 7 --aRatio 0.01) -------------------------------------------------------------------------------------------------------------

@@ -1,7 +1,7 @@
 """python -m reconstruction_amd <config.yml> [--device N] [--out cloud.ply] [--filter] [--mls [--isdelete] [--mls-out bigcloud.ply]]
                               [--mesh [--mesh-depth 9] [--mesh-trim 4] [--mesh-out bigmesh.ply]
                                [--mesh-density-trim [7] [--mesh-density-smooth 100] [--mesh-island-ratio 0.01]]
-                               [--mesh-clean [--mesh-smooth 5] [--mesh-min-piece 10%]]
+                               [--mesh-clean [--mesh-smooth 5] [--mesh-min-piece 10%]] [--mesh-close-holes [30]]
                                [--mesh-color [--mesh-color-mode blend] [--mesh-color-min-cos 0.2] [--mesh-color-eps LENGTH]]
                                [--mesh-stitch [--mesh-stitch-lambda 0.01] [--mesh-stitch-iterations 0]]]
 
@@ -18,13 +18,14 @@ With --mesh-density-trim (implies --mesh) the Poisson call runs without its occu
 SurfaceTrimmer does, on the GPU: cut along the iso-line of the smoothed sample density, small islands moved across.
 With --mesh-clean (implies --mesh) bigmesh.ply is that surface after meshlab.bat's other filters, on the GPU: Laplacian smoothing
 (script1.mlx) and the removal of isolated pieces, duplicate, zero-area and non-manifold faces (script2.mlx).
+With --mesh-close-holes (implies --mesh) the small border loops of that mesh are filled on the GPU as script2.mlx's last filter, "Close
+Holes", does: loops of at most N edges (30 when given bare) get their least-area triangulation, after --mesh-clean.
 With --mesh-color (implies --mesh) the mesh's vertices are coloured from every camera's rectified image, on the GPU, where
 CCloudOptimization::run calls TextureStitcher (visibility by a depth buffer per view, the best view or a cos-weighted blend; DESIGN.md 9
 f9): the coloured mesh goes to the configuration's outfilename, where TextureStitcher's --out goes, and the cloud PLY to <name>_cloud.ply.
 With --mesh-stitch (implies --mesh-color) the vertices take their best view's colour and the views' exposure seams are levelled on the
 GPU by a screened gradient-domain solve on the mesh graph, TextureStitcher's seam removal; the same PLY at outfilename.
-The rest of CCloudOptimization::run (MeshLab's hole closing: an external executable; main.cpp:19) is
-outside this package: feed bigcloud.ply or bigmesh.ply to it.
+The rest of CCloudOptimization::run (main.cpp:19) is outside this package: feed bigcloud.ply or bigmesh.ply to it.
 Needs an MI355X; there is no CPU path.
 """
 from __future__ import annotations
@@ -89,6 +90,9 @@ def main(argv=None) -> int:
     ap.add_argument("--mesh-min-piece", default="10%",
                     help="with --mesh-clean: pieces with a bounding-box diameter below this go; '10%%' = of the whole mesh's diagonal "
                          "(script2.mlx's ratio), a plain number = a length in scene units")
+    ap.add_argument("--mesh-close-holes", type=int, nargs="?", const=30, default=None, metavar="N",
+                    help="after the surface (implied; after --mesh-clean when given): fill every simple border loop of at most N edges (3..64; "
+                         "script2.mlx's MaxHoleSize 30 when given bare) with its least-area triangulation on the GPU, before the mesh is written and coloured")
     ap.add_argument("--mesh-color", action="store_true",
                     help="after the surface (implied; after --mesh-clean when given): colour the mesh's vertices from the rectified views on the "
                          "GPU, where the reference calls TextureStitcher.  The coloured PLY goes to the configuration's outfilename (TextureStitcher's "
@@ -111,7 +115,7 @@ def main(argv=None) -> int:
         args.mesh_color = True
     if args.mesh_color:
         args.mesh = True
-    if args.mesh_density_trim is not None:
+    if args.mesh_density_trim is not None or args.mesh_close_holes is not None:
         args.mesh = True
     if args.mesh_clean:
         args.mesh = True
@@ -193,7 +197,7 @@ def main(argv=None) -> int:
         except RsmError as e:                                      # e.g. --mesh-depth outside 5..9
             print(e)
             return 1
-        cst = tst = None
+        cst = tst = hst = None
         if args.mesh_density_trim is not None:
             try:
                 mv, mf, tst = sink.trim_mesh(smooth_steps=args.mesh_density_smooth, trim=args.mesh_density_trim, island_ratio=args.mesh_island_ratio)
@@ -204,6 +208,12 @@ def main(argv=None) -> int:
             try:
                 mv, mf, cst = sink.clean_mesh(smooth_steps=args.mesh_smooth, min_piece=min_piece, relative=relative)
             except RsmError as e:                                  # e.g. a negative --mesh-smooth
+                print(e)
+                return 1
+        if args.mesh_close_holes is not None:
+            try:
+                mv, mf, hst = sink.close_mesh_holes(max_hole_size=args.mesh_close_holes)
+            except RsmError as e:                                  # --mesh-close-holes outside 3..64
                 print(e)
                 return 1
         mesh_out = args.mesh_out or os.path.join(os.path.dirname(os.path.abspath(out)), "bigmesh.ply")
@@ -218,6 +228,10 @@ def main(argv=None) -> int:
             print("Mesh clean: %d of %d pieces removed (%d faces); %d duplicate, %d zero-area, %d non-manifold faces removed; %d border vertices"
                   % (cst["components_removed"], cst["components"], cst["removed_isolated"], cst["removed_duplicate"], cst["removed_zero_area"],
                      cst["removed_nonmanifold"], cst["border_vertices"]))
+        if hst is not None:
+            print("Mesh close holes: %d of %d loops closed with %d faces (longest %d of %d); %d too long, %d lone triangles, %d without a triangulation; "
+                  "%d open border components" % (hst["loops_closed"], hst["loops"], hst["faces_added"], hst["longest_closed"], hst["longest_loop"],
+                                                 hst["loops_too_long"], hst["lone_triangles"], hst["loops_untriangulated"], hst["open_components"]))
         print("%d vertices, %d faces -> %s" % (len(mv), len(mf), mesh_out))
         if args.mesh_color:
             try:

@@ -93,6 +93,15 @@ class MeshTrimParams(C.Structure):
 MESH_TRIM_STATS = 20
 
 
+class MeshCloseParams(C.Structure):
+    """rsm_mesh_close_params (include/rsm.h)."""
+    _fields_ = [("max_hole_size", C.c_int)]
+
+
+MESH_CLOSE_STATS = 14
+MESH_CLOSE_MAX_HOLE = 64
+
+
 class MeshColorParams(C.Structure):
     """rsm_mesh_color_params (include/rsm.h)."""
     _fields_ = [("mode", C.c_int), ("min_cos", C.c_double), ("depth_eps", C.c_double)]
@@ -134,7 +143,7 @@ _I, _L, _U, _LL, _Z, _D, _V, _S = C.c_int, C.c_int64, C.c_uint32, C.c_longlong, 
 _pI, _pL, _pD = C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_double)
 _PIN, _POUT, _BND, _RIN, _ROUT, _FLT = (C.POINTER(t) for t in (PairIn, PairOut, Boundary, RectifyIn, RectifyOut, FilterParams))
 _MLS, _VIEW, _PSN, _CLN, _COL, _STI = (C.POINTER(t) for t in (MlsParams, DedupView, PoissonParams, MeshCleanParams, MeshColorParams, MeshStitchParams))
-_TRM = C.POINTER(MeshTrimParams)
+_TRM, _CLO = C.POINTER(MeshTrimParams), C.POINTER(MeshCloseParams)
 PROTOTYPES = {
     "rsm_create": (_I, [_V, _I]),
     "rsm_destroy": (None, [_V]),
@@ -228,6 +237,11 @@ PROTOTYPES = {
     "rsm_stage_mesh_density": (_I, [_V, _V, _V, _L, _TRM, _V, _L, _V, _V, _V]),
     "rsm_stage_mesh_value_smooth": (_I, [_V, _V, _L, _L, _V, _I, _V]),
     "rsm_stage_mesh_split": (_I, [_V, _V, _L, _V, _L, _V, _D, _D, _pL, _pL, _V, _V, _V, _V]),
+    "rsm_mesh_close_holes": (_I, [_V, _V, _L, _V, _L, _CLO, _pL, _pL, _V]),
+    "rsm_mesh_close_holes_device": (_I, [_V, _V, _L, _V, _L, _CLO, _pL, _pL, _V]),
+    "rsm_mesh_close_holes_last": (_I, [_V, _CLO, _pL, _pL, _V]),
+    "rsm_stage_mesh_border_loops": (_I, [_V, _V, _L, _L, _V, _V, _pL]),
+    "rsm_stage_hole_triangulate": (_I, [_V, _V, _I, _V, _pD, _V, _pI]),
     "rsm_mesh_color": (_I, [_V, _V, _L, _V, _L, _VIEW, _I, _COL, _V, _V, _V]),
     "rsm_mesh_color_device": (_I, [_V, _V, _L, _V, _L, _VIEW, _I, _COL, _V, _V, _V]),
     "rsm_mesh_color_last": (_I, [_V, _VIEW, _I, _COL, _V]),

@@ -1,12 +1,12 @@
-"""The surface stages (csrc/rsm_mesh.hip): dense-grid Poisson surface and trim, smoothing and clean-up, colours from the rig's views and the
-levelling of their seams."""
+"""The surface stages (csrc/rsm_mesh.hip): dense-grid Poisson surface and trim, smoothing and clean-up, the closing of small holes, colours
+from the rig's views and the levelling of their seams."""
 import ctypes as C
 
 import numpy as np
 
 from . import _lib
 from ._context import ContextBase, _normals4, _p, _u8, _views
-from ._lib import MeshCleanParams, MeshColorParams, MeshStitchParams, MeshTrimParams, PoissonParams
+from ._lib import MeshCleanParams, MeshCloseParams, MeshColorParams, MeshStitchParams, MeshTrimParams, PoissonParams
 
 # the solve's default stopping residual: one decade above the 4.2e-6 the float32 solver reaches at depth 9
 POISSON_REL_RESIDUAL = 4e-5
@@ -254,6 +254,62 @@ class MeshPart(ContextBase):
                                                  *(_p(a) for a in info)))
         ov, of = self.poisson_last_mesh(int(nv.value), int(nf.value))
         return (ov, of) + tuple(a[:len(of)].copy() for a in info) + (self._trim_stats(st),)
+
+    # ---- the closing of the surface's small holes: script2.mlx's "Close Holes" (csrc/k_meshclose.hip) ----
+    _CLOSE_KEYS = ("n_vertices_in", "n_faces_in", "n_faces", "border_entries", "components", "loops", "open_components", "loops_closed", "loops_too_long",
+                   "lone_triangles", "loops_untriangulated", "faces_added", "longest_closed", "longest_loop")
+
+    def _mesh_close(self, fn, mesh_args, max_hole_size):
+        """One of the three rsm_mesh_close_holes* entries: (n_vertices, n_faces, stats) of the mesh it leaves with the context."""
+        nv, nf = C.c_int64(), C.c_int64()
+        st = (C.c_double * _lib.MESH_CLOSE_STATS)()
+        prm = MeshCloseParams(int(max_hole_size))
+        self._chk(fn(self._h, *mesh_args, C.byref(prm), C.byref(nv), C.byref(nf), st))
+        return int(nv.value), int(nf.value), {k: int(st[i]) for i, k in enumerate(self._CLOSE_KEYS)}
+
+    def mesh_close_holes(self, vertices, faces, max_hole_size=30):
+        """script2.mlx's last filter, "Close Holes", on the GPU: every border loop of at most max_hole_size (3..64) edges whose vertices all
+        have one border edge in and one out, other than the border of a lone triangle, is filled with the least-area triangulation of its
+        ring that uses no edge the mesh already has and no triangle without area; bow-ties, borders between faces
+        oriented against each other and longer loops stay.  vertices [nv,3] float32, faces [nf,3] int32 -> (vertices: the input's, faces:
+        the input's followed by the new ones, stats dict).  The result is the context's last mesh (poisson_last_mesh[_device])."""
+        v, f = _mesh_arrays(vertices, faces)
+        nv, nf, stats = self._mesh_close(self._lib.rsm_mesh_close_holes, (_p(v), len(v), _p(f), len(f)), max_hole_size)
+        return self.poisson_last_mesh(nv, nf) + (stats,)
+
+    def mesh_close_holes_device(self, vertices_ptr, n_vertices, faces_ptr, n_faces, max_hole_size=30):
+        """rsm_mesh_close_holes_device on device buffers (addresses).  Returns (n_vertices, n_faces, stats); the mesh stays with the context
+        (poisson_last_mesh[_device] copies it out)."""
+        return self._mesh_close(self._lib.rsm_mesh_close_holes_device, (vertices_ptr, n_vertices, faces_ptr, n_faces), max_hole_size)
+
+    def mesh_close_holes_last(self, max_hole_size=30):
+        """mesh_close_holes of the context's last mesh (what poisson_mesh / mesh_trim / mesh_clean left) where it lies on the device; the
+        result replaces it and its colours are dropped.  Returns (vertices, faces, stats)."""
+        nv, nf, stats = self._mesh_close(self._lib.rsm_mesh_close_holes_last, (), max_hole_size)
+        return self.poisson_last_mesh(nv, nf) + (stats,)
+
+    def mesh_border_loops(self, faces, n_vertices):
+        """Stage: per entry 3 f + j (labels int32 [3 nf] = the lowest entry of its border component, -1 where the edge is no border; sizes
+        int32 [3 nf] = L for a loop's entries, 0 for an open component's, -1 otherwise; the number of border components)."""
+        f = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+        lab = np.zeros(max(3 * len(f), 1), np.int32)
+        size = np.zeros(max(3 * len(f), 1), np.int32)
+        nc = C.c_int64()
+        self._chk(self._lib.rsm_stage_mesh_border_loops(self._h, _p(f), int(n_vertices), len(f), _p(lab), _p(size), C.byref(nc)))
+        return lab[:3 * len(f)].copy(), size[:3 * len(f)].copy(), int(nc.value)
+
+    def mesh_hole_triangulate(self, ring_xyz, forbidden=None):
+        """Stage: a ring of L (3..64) float32 points and, optionally, an L x L array of forbidden pairs (read at [i, j], i + 2 <= j) ->
+        (W(0, L-1) float, triangles int32 [L-2, 3] of ring positions in the order of the output); (inf, [0, 3]) when the ring has no
+        admissible triangulation."""
+        r = np.ascontiguousarray(ring_xyz, np.float32).reshape(-1, 3)
+        L = len(r)
+        m = None if forbidden is None else np.ascontiguousarray(np.asarray(forbidden) != 0, np.uint8)
+        assert m is None or m.shape == (L, L)
+        tri = np.zeros((max(L - 2, 1), 3), np.int32)
+        w, nt = C.c_double(), C.c_int()
+        self._chk(self._lib.rsm_stage_hole_triangulate(self._h, _p(r), L, None if m is None else _p(m), C.byref(w), _p(tri), C.byref(nt)))
+        return float(w.value), tri[:int(nt.value)].copy()
 
     # ---- colours of the mesh from the rig's views, where run() calls TextureStitcher (DESIGN.md 9 f9; csrc/k_meshcolor.hip) ----
     @staticmethod

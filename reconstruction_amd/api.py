@@ -250,9 +250,10 @@ class CloudOptimization:
     after :123 is Windows executables and out of scope), run() (:348-389: MLS over the merged cloud + the normal flip
     on the GPU), mesh() (where run() calls the external Poisson mesher after :389: the dense-grid Poisson surface and trim on the GPU),
     trim_mesh() (mesh.bat's SurfaceTrimmer: the surface cut where the samples' density falls below a depth, on the GPU),
-    clean_mesh() (what meshlab.bat goes on to do: Laplacian smoothing and the removal of isolated pieces and bad faces, on the GPU;
-    its hole closing stays an external executable), color_mesh() (where run() ends with TextureStitcher: the mesh's vertices coloured
-    from every camera's rectified image, on the GPU; the tool's seam removal is not done).  `cloud_normals` accumulates what the
+    clean_mesh() (what meshlab.bat goes on to do: Laplacian smoothing and the removal of isolated pieces and bad faces, on the GPU),
+    close_mesh_holes() (its last filter: small border loops filled with their least-area triangulation, on the GPU),
+    color_mesh() (where run() ends with TextureStitcher: the mesh's vertices coloured from every camera's rectified image, on the
+    GPU), stitch_mesh() (the tool's seam removal: the views' exposure seams levelled in those colours, on the GPU).  `cloud_normals` accumulates what the
     reference's global `*cloud_normals += *cloud_normal` (:123) does: per pair (xyz float32 [m,3], normals float32 [m,4])."""
 
     def __init__(self, ctx: Context | None = None, device: int = 0):
@@ -345,6 +346,16 @@ class CloudOptimization:
         if getattr(self, "mesh_result", None) is None:
             raise ValueError("CloudOptimization.clean_mesh: mesh() first (it smooths and cleans mesh()'s surface)")
         self.mesh_result = self._ctx.mesh_clean_last(smooth_steps, cotangent, boundary, min_piece, relative, duplicates, zero_area, nonmanifold)
+        self.mesh_colors = None
+        return self.mesh_result
+
+    def close_mesh_holes(self, max_hole_size=30):
+        """Where meshlab.bat's script2.mlx ends with "Close Holes" (MaxHoleSize 30): every simple border loop of mesh_result of at most
+        max_hole_size edges filled with its least-area triangulation (Context.mesh_close_holes_last on the mesh mesh() / trim_mesh() /
+        clean_mesh() left with the context, without a host round trip).  Replaces mesh_result."""
+        if getattr(self, "mesh_result", None) is None:
+            raise ValueError("CloudOptimization.close_mesh_holes: mesh() first (it closes the small holes of mesh()'s surface)")
+        self.mesh_result = self._ctx.mesh_close_holes_last(max_hole_size)
         self.mesh_colors = None
         return self.mesh_result
 

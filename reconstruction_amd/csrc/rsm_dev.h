@@ -254,6 +254,19 @@ int mesh_components_device(const int32_t *d_f, int64_t nv, int64_t nf, int32_t *
 int mesh_clean_device(const float *d_v, int64_t nv, const int32_t *d_f, int64_t nf, const rsm_mesh_clean_params *p, PoissonMesh *out, double *stats, int *invalid,
                       hipStream_t st);
 
+// the closing of the surface's small holes (k_meshclose.hip).  Device buffers: nv float xyz, nf int32 x 3; *invalid as
+// mesh_clean_device's; parameters are the caller's to check.
+struct rsm_mesh_close_params;
+// per entry 3 f + j (3 nf int32 each): d_label = the lowest entry of its border component (-1: no border entry), d_size = L for a loop's
+// entries, 0 for an open component's, -1 otherwise
+int mesh_border_loops_device(const int32_t *d_f, int64_t nv, int64_t nf, int32_t *d_label, int32_t *d_size, int64_t *n_components, int *invalid, hipStream_t st);
+// one ring of L (3 .. RSM_MESH_CLOSE_MAX_HOLE) finite points, d_mask = L x L bytes of forbidden pairs or NULL -> *weight = W(0, L-1),
+// d_tri (L - 2 triangles of ring positions), *n_tri = L - 2, or +inf and 0
+int hole_triangulate_device(const float *d_ring, int L, const uint8_t *d_mask, double *weight, int32_t *d_tri, int *n_tri, hipStream_t st);
+// the whole call; the result replaces *out, which may own d_v / d_f; stats: RSM_MESH_CLOSE_STATS doubles, may be NULL
+int mesh_close_holes_device(const float *d_v, int64_t nv, const int32_t *d_f, int64_t nf, const rsm_mesh_close_params *p, PoissonMesh *out, double *stats,
+                            int *invalid, hipStream_t st);
+
 // the density trim of the surface (k_meshtrim.hip).  Device buffers: n float xyz samples with float4 normals (d_sn4 may be
 // NULL: a finite point is a valid sample), nv float xyz, nf int32 x 3.  Parameters are the caller's to check; each call validates the
 // mesh it is given, and RSM_E_INVALID comes with *invalid as mesh_clean_device's.

@@ -429,6 +429,102 @@ extern "C" int rsm_stage_mesh_split(rsm_ctx *c, const float *xyz, int64_t nv, co
     return RSM_OK;
 }
 
+// ---- the closing of the surface's small holes (k_meshclose.hip) ---------------------------------------------------------
+static int meshclose_params_ok(rsm_ctx *c, const rsm_mesh_close_params *p) {
+    if (!p) return set_err(c, RSM_E_INVALID, "mesh_close_holes: params is NULL");
+    if (p->max_hole_size < 3 || p->max_hole_size > RSM_MESH_CLOSE_MAX_HOLE)
+        return set_err(c, RSM_E_INVALID, "mesh_close_holes: max_hole_size %d outside 3..%d", p->max_hole_size, RSM_MESH_CLOSE_MAX_HOLE);
+    return RSM_OK;
+}
+static int meshclose_fail(rsm_ctx *c, int s, int invalid) {
+    if (s == RSM_E_INVALID) return set_err(c, s, invalid == 1 ? "mesh_close_holes: a face index outside [0, nv)" : "mesh_close_holes: a coordinate that is not finite");
+    if (s == RSM_E_NOMEM) return set_err(c, s, "mesh_close_holes: no device memory");
+    return set_err(c, s, "mesh_close_holes: failed%s", hip_tail(s).c_str());
+}
+// d_xyz / d_faces may be c->pmesh's own buffers
+static int meshclose_run(rsm_ctx *c, const float *d_xyz, int64_t nv, const int32_t *d_faces, int64_t nf, const rsm_mesh_close_params *p, int64_t *n_vertices,
+                         int64_t *n_faces, double *stats) {
+    int invalid = 0;
+    const int s = mesh_close_holes_device(d_xyz, nv, d_faces, nf, p, &c->pmesh, stats, &invalid, c->stream);
+    if (s != RSM_OK) return meshclose_fail(c, s, invalid);
+    c->mcol_of = nullptr; // (the colours belonged to the mesh this one replaces)
+    *n_vertices = c->pmesh.nv;
+    *n_faces = c->pmesh.nf;
+    return RSM_OK;
+}
+
+extern "C" int rsm_mesh_close_holes_device(rsm_ctx *c, const float *d_xyz, int64_t nv, const int32_t *d_faces, int64_t nf, const rsm_mesh_close_params *p,
+                                           int64_t *n_vertices, int64_t *n_faces, double *stats) {
+    if (!c) return RSM_E_INVALID;
+    int s = meshclose_params_ok(c, p);
+    if (s != RSM_OK || (s = mesh_counts_ok(c, "mesh_close_holes", nv, nf)) != RSM_OK) return s;
+    if (!n_vertices || !n_faces || (nv > 0 && !d_xyz) || (nf > 0 && !d_faces)) return set_err(c, RSM_E_INVALID, "mesh_close_holes: a NULL pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    return meshclose_run(c, d_xyz, nv, d_faces, nf, p, n_vertices, n_faces, stats);
+}
+
+extern "C" int rsm_mesh_close_holes(rsm_ctx *c, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, const rsm_mesh_close_params *p, int64_t *n_vertices,
+                                    int64_t *n_faces, double *stats) {
+    if (!c) return RSM_E_INVALID;
+    int s = meshclose_params_ok(c, p);
+    if (s != RSM_OK || (s = mesh_counts_ok(c, "mesh_close_holes", nv, nf)) != RSM_OK) return s;
+    if (!n_vertices || !n_faces || (nv > 0 && !xyz) || (nf > 0 && !faces)) return set_err(c, RSM_E_INVALID, "mesh_close_holes: a NULL pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    Tmp T(c);
+    float *dv = T.up(xyz, 3 * (size_t)nv);
+    int32_t *df = T.up(faces, 3 * (size_t)nf);
+    if (!dv || !df) return set_err(c, RSM_E_NOMEM, "mesh_close_holes: no device memory for %lld vertices, %lld faces", (long long)nv, (long long)nf);
+    if ((s = finish(c, T)) != RSM_OK) return s;
+    return meshclose_run(c, dv, nv, df, nf, p, n_vertices, n_faces, stats);
+}
+
+extern "C" int rsm_mesh_close_holes_last(rsm_ctx *c, const rsm_mesh_close_params *p, int64_t *n_vertices, int64_t *n_faces, double *stats) {
+    if (!c) return RSM_E_INVALID;
+    const int s = meshclose_params_ok(c, p);
+    if (s != RSM_OK) return s;
+    if (!n_vertices || !n_faces) return set_err(c, RSM_E_INVALID, "mesh_close_holes: a NULL pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    return meshclose_run(c, c->pmesh.d_v, c->pmesh.nv, c->pmesh.d_f, c->pmesh.nf, p, n_vertices, n_faces, stats);
+}
+
+extern "C" int rsm_stage_mesh_border_loops(rsm_ctx *c, const int32_t *faces, int64_t nv, int64_t nf, int32_t *labels, int32_t *sizes, int64_t *n_components) {
+    if (!c) return RSM_E_INVALID;
+    int s = mesh_counts_ok(c, "mesh_close_holes", nv, nf);
+    if (s != RSM_OK) return s;
+    if (!n_components || (nf > 0 && (!faces || !labels || !sizes))) return set_err(c, RSM_E_INVALID, "mesh_close_holes: a NULL pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    Tmp T(c);
+    int32_t *df = T.up(faces, 3 * (size_t)nf), *dl = T.alloc<int32_t>(3 * (size_t)nf), *ds = T.alloc<int32_t>(3 * (size_t)nf);
+    if (!df || !dl || !ds) return set_err(c, RSM_E_NOMEM, "mesh_close_holes: no device memory");
+    if ((s = finish(c, T)) != RSM_OK) return s;
+    int invalid = 0;
+    if ((s = mesh_border_loops_device(df, nv, nf, dl, ds, n_components, &invalid, c->stream)) != RSM_OK) return meshclose_fail(c, s, invalid);
+    if (nf > 0) HIPCHK(c, hipMemcpyAsync(labels, dl, sizeof(int32_t) * 3 * (size_t)nf, hipMemcpyDeviceToHost, c->stream));
+    if (nf > 0) HIPCHK(c, hipMemcpyAsync(sizes, ds, sizeof(int32_t) * 3 * (size_t)nf, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RSM_OK;
+}
+
+extern "C" int rsm_stage_hole_triangulate(rsm_ctx *c, const float *ring_xyz, int L, const uint8_t *forbidden, double *weight, int32_t *triangles, int *n_triangles) {
+    if (!c) return RSM_E_INVALID;
+    if (L < 3 || L > RSM_MESH_CLOSE_MAX_HOLE) return set_err(c, RSM_E_INVALID, "mesh_close_holes: L %d outside 3..%d", L, RSM_MESH_CLOSE_MAX_HOLE);
+    if (!ring_xyz || !weight || !triangles || !n_triangles) return set_err(c, RSM_E_INVALID, "mesh_close_holes: a NULL pointer");
+    for (int i = 0; i < 3 * L; i++)
+        if (!std::isfinite(ring_xyz[i])) return set_err(c, RSM_E_INVALID, "mesh_close_holes: a coordinate that is not finite");
+    HIPCHK(c, hipSetDevice(c->device));
+    Tmp T(c);
+    float *dr = T.up(ring_xyz, 3 * (size_t)L);
+    uint8_t *dm = forbidden ? T.up(forbidden, (size_t)L * (size_t)L) : nullptr;
+    int32_t *dt = T.alloc<int32_t>(3 * (size_t)(L - 2));
+    if (!dr || !dt || (forbidden && !dm)) return set_err(c, RSM_E_NOMEM, "mesh_close_holes: no device memory");
+    int s = finish(c, T);
+    if (s != RSM_OK) return s;
+    if ((s = hole_triangulate_device(dr, L, dm, weight, dt, n_triangles, c->stream)) != RSM_OK) return meshclose_fail(c, s, 0);
+    if (*n_triangles > 0) HIPCHK(c, hipMemcpyAsync(triangles, dt, sizeof(int32_t) * 3 * (size_t)*n_triangles, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RSM_OK;
+}
+
 // ---- colours of the mesh from the rig's views (k_meshcolor.hip) ----------------------------------------------------------
 static int meshcolor_params_ok(rsm_ctx *c, const rsm_mesh_color_params *p) {
     if (!p) return set_err(c, RSM_E_INVALID, "mesh_color: params is NULL");
