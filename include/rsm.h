@@ -613,6 +613,64 @@ int rsm_mesh_close_holes_last(rsm_ctx *ctx, const rsm_mesh_close_params *p, int6
 int rsm_stage_mesh_border_loops(rsm_ctx *ctx, const int32_t *faces, int64_t nv, int64_t nf, int32_t *labels, int32_t *sizes, int64_t *n_components);
 int rsm_stage_hole_triangulate(rsm_ctx *ctx, const float *ring_xyz, int L, const uint8_t *forbidden, double *weight, int32_t *triangles, int *n_triangles);
 
+/* ---- the decimation of the final mesh (Demo/meshlab/decimation.mlx: "Quadric Edge Collapse Decimation", TargetFaceNum 100000, QualityThr
+ * 0.3, PreserveTopology and OptimalPlacement on, AutoClean on) ---------------------------------------------------------------------------
+ * Not a bit-parity port of MeshLab / VCG: the rules as DESIGN.md 9 (f13) defines them.  Faces with a repeated index go first.  Every vertex
+ * gets the sum of its faces' plane quadrics (not normalised: a face weighs by 4 area^2) and of the border planes of its border edges, once;
+ * a collapse adds the two quadrics.  Rounds: every unique edge of one or two faces without a locked endpoint (an endpoint of an edge of more
+ * than two faces; with preserve_boundary every border vertex) that passes the link condition (preserve_topology) and leaves no two faces with
+ * the same vertices is a candidate; its position is the quadric's optimum (3 x 3 solve by cofactors, refused when singular, not finite or
+ * further than two edge lengths from the midpoint) or the best of Pa, Pb and the midpoint, rounded to float32 and judged as that; its cost is
+ * max(error, min_error) over the clamped least shape quality of the faces around it.  The candidates of the lowest ceil(need / 2) ranks in
+ * (cost, key) take part; an edge is selected when its rank is the least among the participating edges at its endpoints and their
+ * neighbours (no two selected edges have adjacent endpoints); in rank order the selected edges are kept while the faces removed before them
+ * are fewer than need = faces - target; b -> a (the lower index), V[a] = the position, Q[a] += Q[b]; faces with a repeated index leave in
+ * order.  Rounds run until faces <= target, no candidate is left or max_rounds; the result has target or target - 1 faces while candidates
+ * last.  At the end the vertices no face refers to go (the input's as well).  Opt-in: no other call changes. */
+typedef struct rsm_mesh_decimate_params {
+    int64_t target_faces;    /* >= 0 (decimation.mlx: 100000) */
+    double target_fraction;  /* 0 = unused, else in (0, 1]: target = floor(fraction * faces in), and target_faces is not read (TargetPerc) */
+    double quality_thr;      /* [0, 1]; 0 = no shape penalty (0.3) */
+    int preserve_boundary;   /* 0 / 1: border vertices are locked (0) */
+    double boundary_weight;  /* finite, > 0: the weight of a border edge's plane (1) */
+    int preserve_normal;     /* 0 / 1: a collapse that turns a face's normal by 90 degrees or more is refused (0) */
+    int preserve_topology;   /* 0 / 1: the link condition (1) */
+    int optimal_placement;   /* 0 / 1: the quadric's optimum, else the best of the endpoints and the midpoint (1) */
+    double min_error;        /* finite, >= 0: the floor of an edge's error (the binding's default: 1e-15) */
+    int max_rounds;          /* 1..1000000 (the binding's default: 1000) */
+} rsm_mesh_decimate_params;
+/* stats: [0] / [1] vertices / faces in, [2] / [3] vertices / faces out, [4] faces with a repeated index dropped, [5] rounds, [6] collapses, [7]
+ * collapses of border edges, [8..14] the edges of the last round that were no candidates: [8] of more than two faces, [9] a locked endpoint,
+ * [10] the link condition's common neighbours, [11] both endpoints on the border but the edge not, [12] two faces with the same vertices, [13]
+ * a normal turned over, [14] an error or cost that is not finite; [15] the locked vertices of the last round, [16] the largest number of
+ * faces at a vertex met, [17] the largest cost collapsed, [18] target_reached (faces out <= target), [19] the target */
+#define RSM_MESH_DECIMATE_STATS 20
+/* nv vertices (xyz nv*3 float) and nf faces (faces nf*3 int32) in host buffers -> the context's last mesh, as rsm_mesh_clean
+ * (rsm_poisson_last_mesh copies it out; *n_vertices, *n_faces size its buffers; colours of the last mesh are dropped).  An empty mesh in: an
+ * empty mesh, RSM_OK.  A mesh at or below the target: only the repeated-index faces and the unreferenced vertices go.  RSM_E_INVALID
+ * (rsm_last_error names the cause): a parameter outside its range above, a face index outside [0, nv), a coordinate that is not finite,
+ * 3 nf >= 2^31, nv above INT32_MAX, a negative count, a NULL pointer. */
+int rsm_mesh_decimate(rsm_ctx *ctx, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, const rsm_mesh_decimate_params *p, int64_t *n_vertices,
+                      int64_t *n_faces, double *stats);
+/* the same on DEVICE buffers */
+int rsm_mesh_decimate_device(rsm_ctx *ctx, const float *d_xyz, int64_t nv, const int32_t *d_faces, int64_t nf, const rsm_mesh_decimate_params *p,
+                             int64_t *n_vertices, int64_t *n_faces, double *stats);
+/* the same on the context's last mesh where it lies; the result replaces it */
+int rsm_mesh_decimate_last(rsm_ctx *ctx, const rsm_mesh_decimate_params *p, int64_t *n_vertices, int64_t *n_faces, double *stats);
+/* stage entry points (host buffers) for the tests.  A quadric is 10 doubles: xx xy xz xd yy yz yd zz zd dd.  quadrics: out_q nv*10.
+ * collapse_costs: per unique edge of the faces without a repeated index, in key order (room for 3 nf each): key = (a << 32) | b with a < b,
+ * multiplicity, cost (+inf: not a candidate), reject (bits 0-3: 0 a candidate, else 1..7 in the order of stats [8..14]; bits 4-5 where a
+ * position was computed -- codes 0, 6, 7 --: 0 the optimum, 1 Pa, 2 Pb, 3 the midpoint) and position (3 float); *n_edges of them.
+ * collapse_round: one round with need = faces to remove on (xyz, faces, quadrics nv*10) -> out_xyz (nv*3), out_quadrics (nv*10), out_faces
+ * (room for nf*3; *n_faces_out of them), selected_keys (room for 3 nf; *n_selected of them in priority order, the first *n_kept collapsed). */
+int rsm_stage_mesh_quadrics(rsm_ctx *ctx, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, double boundary_weight, double *out_q);
+int rsm_stage_mesh_collapse_costs(rsm_ctx *ctx, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, const double *quadrics,
+                                  const rsm_mesh_decimate_params *p, uint64_t *keys, int32_t *multiplicity, double *cost, int32_t *reject, float *position,
+                                  int64_t *n_edges);
+int rsm_stage_mesh_collapse_round(rsm_ctx *ctx, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, const double *quadrics,
+                                  const rsm_mesh_decimate_params *p, int64_t need, float *out_xyz, int32_t *out_faces, double *out_quadrics, int64_t *n_faces_out,
+                                  uint64_t *selected_keys, int64_t *n_selected, int64_t *n_kept);
+
 /* ---- the density trim of the surface (where mesh.bat runs PoissonRecon --density --samplesPerNode 2 and then SurfaceTrimmer --smooth 100
  * --trim 7 --aRatio 0.01) -------------------------------------------------------------------------------------------------------------
  * Not a bit-parity port of those tools: the rules as DESIGN.md 9 (f11) defines them.  Every vertex gets the depth at which a grid node

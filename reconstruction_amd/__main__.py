@@ -1,7 +1,7 @@
 """python -m reconstruction_amd <config.yml> [--device N] [--out cloud.ply] [--filter] [--mls [--isdelete] [--mls-out bigcloud.ply]]
                               [--mesh [--mesh-depth 9] [--mesh-trim 4] [--mesh-out bigmesh.ply]
                                [--mesh-density-trim [7] [--mesh-density-smooth 100] [--mesh-island-ratio 0.01]]
-                               [--mesh-clean [--mesh-smooth 5] [--mesh-min-piece 10%]] [--mesh-close-holes [30]]
+                               [--mesh-clean [--mesh-smooth 5] [--mesh-min-piece 10%]] [--mesh-close-holes [30]] [--mesh-decimate [100000]]
                                [--mesh-color [--mesh-color-mode blend] [--mesh-color-min-cos 0.2] [--mesh-color-eps LENGTH]]
                                [--mesh-stitch [--mesh-stitch-lambda 0.01] [--mesh-stitch-iterations 0]]]
 
@@ -20,6 +20,8 @@ With --mesh-clean (implies --mesh) bigmesh.ply is that surface after meshlab.bat
 (script1.mlx) and the removal of isolated pieces, duplicate, zero-area and non-manifold faces (script2.mlx).
 With --mesh-close-holes (implies --mesh) the small border loops of that mesh are filled on the GPU as script2.mlx's last filter, "Close
 Holes", does: loops of at most N edges (30 when given bare) get their least-area triangulation, after --mesh-clean.
+With --mesh-decimate (implies --mesh) that mesh is thinned to N faces (100000 when given bare) on the GPU as Demo/meshlab/decimation.mlx's
+"Quadric Edge Collapse Decimation" does, after --mesh-close-holes and before the colouring.
 With --mesh-color (implies --mesh) the mesh's vertices are coloured from every camera's rectified image, on the GPU, where
 CCloudOptimization::run calls TextureStitcher (visibility by a depth buffer per view, the best view or a cos-weighted blend; DESIGN.md 9
 f9): the coloured mesh goes to the configuration's outfilename, where TextureStitcher's --out goes, and the cloud PLY to <name>_cloud.ply.
@@ -93,6 +95,9 @@ def main(argv=None) -> int:
     ap.add_argument("--mesh-close-holes", type=int, nargs="?", const=30, default=None, metavar="N",
                     help="after the surface (implied; after --mesh-clean when given): fill every simple border loop of at most N edges (3..64; "
                          "script2.mlx's MaxHoleSize 30 when given bare) with its least-area triangulation on the GPU, before the mesh is written and coloured")
+    ap.add_argument("--mesh-decimate", type=int, nargs="?", const=100000, default=None, metavar="N",
+                    help="after the surface (implied; after --mesh-clean and --mesh-close-holes when given): thin the mesh to N faces (decimation.mlx's "
+                         "TargetFaceNum 100000 when given bare) by quadric edge collapses on the GPU, before the mesh is written and coloured")
     ap.add_argument("--mesh-color", action="store_true",
                     help="after the surface (implied; after --mesh-clean when given): colour the mesh's vertices from the rectified views on the "
                          "GPU, where the reference calls TextureStitcher.  The coloured PLY goes to the configuration's outfilename (TextureStitcher's "
@@ -115,7 +120,7 @@ def main(argv=None) -> int:
         args.mesh_color = True
     if args.mesh_color:
         args.mesh = True
-    if args.mesh_density_trim is not None or args.mesh_close_holes is not None:
+    if args.mesh_density_trim is not None or args.mesh_close_holes is not None or args.mesh_decimate is not None:
         args.mesh = True
     if args.mesh_clean:
         args.mesh = True
@@ -197,7 +202,7 @@ def main(argv=None) -> int:
         except RsmError as e:                                      # e.g. --mesh-depth outside 5..9
             print(e)
             return 1
-        cst = tst = hst = None
+        cst = tst = hst = dst = None
         if args.mesh_density_trim is not None:
             try:
                 mv, mf, tst = sink.trim_mesh(smooth_steps=args.mesh_density_smooth, trim=args.mesh_density_trim, island_ratio=args.mesh_island_ratio)
@@ -216,6 +221,12 @@ def main(argv=None) -> int:
             except RsmError as e:                                  # --mesh-close-holes outside 3..64
                 print(e)
                 return 1
+        if args.mesh_decimate is not None:
+            try:
+                mv, mf, dst = sink.decimate_mesh(target_faces=args.mesh_decimate)
+            except RsmError as e:                                  # a negative --mesh-decimate
+                print(e)
+                return 1
         mesh_out = args.mesh_out or os.path.join(os.path.dirname(os.path.abspath(out)), "bigmesh.ply")
         write_ply_mesh(mesh_out, mv, mf)
         print("Mesh time: %.3f s (%d cycles, residual %.2e%s)" % (time.perf_counter() - t2, mst["cycles"], mst["residual"],
@@ -232,6 +243,10 @@ def main(argv=None) -> int:
             print("Mesh close holes: %d of %d loops closed with %d faces (longest %d of %d); %d too long, %d lone triangles, %d without a triangulation; "
                   "%d open border components" % (hst["loops_closed"], hst["loops"], hst["faces_added"], hst["longest_closed"], hst["longest_loop"],
                                                  hst["loops_too_long"], hst["lone_triangles"], hst["loops_untriangulated"], hst["open_components"]))
+        if dst is not None:
+            print("Mesh decimate: %d -> %d faces (target %d%s) in %d rounds, %d collapses (%d of border edges); %d locked vertices, largest cost %.3g"
+                  % (dst["n_faces_in"], dst["n_faces"], dst["target"], "" if dst["target_reached"] else ", not reached", dst["rounds"], dst["collapses"],
+                     dst["border_collapses"], dst["locked_vertices"], dst["max_cost"]))
         print("%d vertices, %d faces -> %s" % (len(mv), len(mf), mesh_out))
         if args.mesh_color:
             try:

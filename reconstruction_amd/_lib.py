@@ -102,6 +102,16 @@ MESH_CLOSE_STATS = 14
 MESH_CLOSE_MAX_HOLE = 64
 
 
+class MeshDecimateParams(C.Structure):
+    """rsm_mesh_decimate_params (include/rsm.h)."""
+    _fields_ = [("target_faces", C.c_int64), ("target_fraction", C.c_double), ("quality_thr", C.c_double), ("preserve_boundary", C.c_int),
+                ("boundary_weight", C.c_double), ("preserve_normal", C.c_int), ("preserve_topology", C.c_int), ("optimal_placement", C.c_int),
+                ("min_error", C.c_double), ("max_rounds", C.c_int)]
+
+
+MESH_DECIMATE_STATS = 20
+
+
 class MeshColorParams(C.Structure):
     """rsm_mesh_color_params (include/rsm.h)."""
     _fields_ = [("mode", C.c_int), ("min_cos", C.c_double), ("depth_eps", C.c_double)]
@@ -143,7 +153,7 @@ _I, _L, _U, _LL, _Z, _D, _V, _S = C.c_int, C.c_int64, C.c_uint32, C.c_longlong, 
 _pI, _pL, _pD = C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_double)
 _PIN, _POUT, _BND, _RIN, _ROUT, _FLT = (C.POINTER(t) for t in (PairIn, PairOut, Boundary, RectifyIn, RectifyOut, FilterParams))
 _MLS, _VIEW, _PSN, _CLN, _COL, _STI = (C.POINTER(t) for t in (MlsParams, DedupView, PoissonParams, MeshCleanParams, MeshColorParams, MeshStitchParams))
-_TRM, _CLO = C.POINTER(MeshTrimParams), C.POINTER(MeshCloseParams)
+_TRM, _CLO, _DEC = C.POINTER(MeshTrimParams), C.POINTER(MeshCloseParams), C.POINTER(MeshDecimateParams)
 PROTOTYPES = {
     "rsm_create": (_I, [_V, _I]),
     "rsm_destroy": (None, [_V]),
@@ -242,6 +252,12 @@ PROTOTYPES = {
     "rsm_mesh_close_holes_last": (_I, [_V, _CLO, _pL, _pL, _V]),
     "rsm_stage_mesh_border_loops": (_I, [_V, _V, _L, _L, _V, _V, _pL]),
     "rsm_stage_hole_triangulate": (_I, [_V, _V, _I, _V, _pD, _V, _pI]),
+    "rsm_mesh_decimate": (_I, [_V, _V, _L, _V, _L, _DEC, _pL, _pL, _V]),
+    "rsm_mesh_decimate_device": (_I, [_V, _V, _L, _V, _L, _DEC, _pL, _pL, _V]),
+    "rsm_mesh_decimate_last": (_I, [_V, _DEC, _pL, _pL, _V]),
+    "rsm_stage_mesh_quadrics": (_I, [_V, _V, _L, _V, _L, _D, _V]),
+    "rsm_stage_mesh_collapse_costs": (_I, [_V, _V, _L, _V, _L, _V, _DEC, _V, _V, _V, _V, _V, _pL]),
+    "rsm_stage_mesh_collapse_round": (_I, [_V, _V, _L, _V, _L, _V, _DEC, _L, _V, _V, _V, _pL, _V, _pL, _pL]),
     "rsm_mesh_color": (_I, [_V, _V, _L, _V, _L, _VIEW, _I, _COL, _V, _V, _V]),
     "rsm_mesh_color_device": (_I, [_V, _V, _L, _V, _L, _VIEW, _I, _COL, _V, _V, _V]),
     "rsm_mesh_color_last": (_I, [_V, _VIEW, _I, _COL, _V]),

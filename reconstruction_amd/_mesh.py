@@ -1,12 +1,12 @@
-"""The surface stages (csrc/rsm_mesh.hip): dense-grid Poisson surface and trim, smoothing and clean-up, the closing of small holes, colours
-from the rig's views and the levelling of their seams."""
+"""The surface stages (csrc/rsm_mesh.hip): dense-grid Poisson surface and trim, smoothing and clean-up, the closing of small holes, the
+decimation, colours from the rig's views and the levelling of their seams."""
 import ctypes as C
 
 import numpy as np
 
 from . import _lib
 from ._context import ContextBase, _normals4, _p, _u8, _views
-from ._lib import MeshCleanParams, MeshCloseParams, MeshColorParams, MeshStitchParams, MeshTrimParams, PoissonParams
+from ._lib import MeshCleanParams, MeshCloseParams, MeshColorParams, MeshDecimateParams, MeshStitchParams, MeshTrimParams, PoissonParams
 
 # the solve's default stopping residual: one decade above the 4.2e-6 the float32 solver reaches at depth 9
 POISSON_REL_RESIDUAL = 4e-5
@@ -310,6 +310,81 @@ class MeshPart(ContextBase):
         w, nt = C.c_double(), C.c_int()
         self._chk(self._lib.rsm_stage_hole_triangulate(self._h, _p(r), L, None if m is None else _p(m), C.byref(w), _p(tri), C.byref(nt)))
         return float(w.value), tri[:int(nt.value)].copy()
+
+    # ---- the decimation of the final mesh: decimation.mlx's "Quadric Edge Collapse Decimation" (csrc/k_meshdecimate.hip) ----
+    _DECIMATE_KEYS = ("n_vertices_in", "n_faces_in", "n_vertices", "n_faces", "repeated_index_faces", "rounds", "collapses", "border_collapses",
+                      "rejected_nonmanifold", "rejected_locked", "rejected_link", "rejected_border", "rejected_duplicate", "rejected_normal",
+                      "rejected_not_finite", "locked_vertices", "max_valence", "max_cost", "target_reached", "target")
+
+    @staticmethod
+    def mesh_decimate_params(target_faces=100000, target_fraction=0.0, quality_thr=0.3, preserve_boundary=False, boundary_weight=1.0, preserve_normal=False,
+                             preserve_topology=True, optimal_placement=True, min_error=1e-15, max_rounds=1000):
+        """rsm_mesh_decimate_params with decimation.mlx's values as defaults (min_error: VCG's floor; max_rounds: DESIGN.md 9 f13)."""
+        return MeshDecimateParams(int(target_faces), float(target_fraction), float(quality_thr), int(preserve_boundary), float(boundary_weight),
+                                  int(preserve_normal), int(preserve_topology), int(optimal_placement), float(min_error), int(max_rounds))
+
+    def _mesh_decimate(self, fn, mesh_args, prm):
+        """One of the three rsm_mesh_decimate* entries: (n_vertices, n_faces, stats) of the mesh it leaves with the context."""
+        nv, nf = C.c_int64(), C.c_int64()
+        st = (C.c_double * _lib.MESH_DECIMATE_STATS)()
+        self._chk(fn(self._h, *mesh_args, C.byref(prm), C.byref(nv), C.byref(nf), st))
+        return int(nv.value), int(nf.value), {k: (float(st[i]) if k == "max_cost" else int(st[i])) for i, k in enumerate(self._DECIMATE_KEYS)}
+
+    def mesh_decimate(self, vertices, faces, **params):
+        """decimation.mlx's "Quadric Edge Collapse Decimation" on the GPU: rounds of independent edge collapses in the order
+        of their quadric error over the clamped shape quality, until the mesh has target_faces (or target_fraction of its) faces or no edge
+        may collapse; then the vertices no face refers to go.  params: mesh_decimate_params'.  vertices [nv,3] float32, faces [nf,3] int32 ->
+        (vertices, faces, stats dict).  The result is the context's last mesh (poisson_last_mesh[_device])."""
+        v, f = _mesh_arrays(vertices, faces)
+        nv, nf, stats = self._mesh_decimate(self._lib.rsm_mesh_decimate, (_p(v), len(v), _p(f), len(f)), self.mesh_decimate_params(**params))
+        return self.poisson_last_mesh(nv, nf) + (stats,)
+
+    def mesh_decimate_device(self, vertices_ptr, n_vertices, faces_ptr, n_faces, **params):
+        """rsm_mesh_decimate_device on device buffers (addresses).  Returns (n_vertices, n_faces, stats); the mesh stays with the context
+        (poisson_last_mesh[_device] copies it out)."""
+        return self._mesh_decimate(self._lib.rsm_mesh_decimate_device, (vertices_ptr, n_vertices, faces_ptr, n_faces), self.mesh_decimate_params(**params))
+
+    def mesh_decimate_last(self, **params):
+        """mesh_decimate of the context's last mesh where it lies on the device; the result replaces it and its colours are dropped.
+        Returns (vertices, faces, stats)."""
+        nv, nf, stats = self._mesh_decimate(self._lib.rsm_mesh_decimate_last, (), self.mesh_decimate_params(**params))
+        return self.poisson_last_mesh(nv, nf) + (stats,)
+
+    def mesh_quadrics(self, vertices, faces, boundary_weight=1.0):
+        """Stage: the quadric of every vertex, float64 [nv,10] (xx xy xz xd yy yz yd zz zd dd)."""
+        v, f = _mesh_arrays(vertices, faces)
+        q = np.zeros((max(len(v), 1), 10), np.float64)
+        self._chk(self._lib.rsm_stage_mesh_quadrics(self._h, _p(v), len(v), _p(f), len(f), float(boundary_weight), _p(q)))
+        return q[:len(v)].copy()
+
+    def mesh_collapse_costs(self, vertices, faces, quadrics, **params):
+        """Stage: per unique edge in key order (keys uint64 = (a << 32) | b, multiplicity int32, cost float64 with +inf for no candidate,
+        reject int32 -- bits 0-3 why, bits 4-5 the placement branch --, position float32 [ne,3])."""
+        v, f = _mesh_arrays(vertices, faces)
+        q = np.ascontiguousarray(quadrics, np.float64).reshape(-1, 10)
+        assert len(q) == len(v)
+        n = max(3 * len(f), 1)
+        key, mult, cost, rej, pos = np.zeros(n, np.uint64), np.zeros(n, np.int32), np.zeros(n, np.float64), np.zeros(n, np.int32), np.zeros((n, 3), np.float32)
+        ne = C.c_int64()
+        prm = self.mesh_decimate_params(**params)
+        self._chk(self._lib.rsm_stage_mesh_collapse_costs(self._h, _p(v), len(v), _p(f), len(f), _p(q), C.byref(prm), _p(key), _p(mult), _p(cost), _p(rej), _p(pos),
+                                                          C.byref(ne)))
+        ne = int(ne.value)
+        return tuple(a[:ne].copy() for a in (key, mult, cost, rej, pos))
+
+    def mesh_collapse_round(self, vertices, faces, quadrics, need, **params):
+        """Stage: one round that is to remove `need` faces -> (vertices float32 [nv,3], faces int32 [nf',3], quadrics float64 [nv,10], the
+        selected keys uint64 in priority order, the number of them that were collapsed)."""
+        v, f = _mesh_arrays(vertices, faces)
+        q = np.ascontiguousarray(quadrics, np.float64).reshape(-1, 10)
+        assert len(q) == len(v)
+        ov, oq = np.zeros((max(len(v), 1), 3), np.float32), np.zeros((max(len(v), 1), 10), np.float64)
+        of, sel = np.zeros((max(len(f), 1), 3), np.int32), np.zeros(max(3 * len(f), 1), np.uint64)
+        nfo, nsel, nkept = C.c_int64(), C.c_int64(), C.c_int64()
+        prm = self.mesh_decimate_params(**params)
+        self._chk(self._lib.rsm_stage_mesh_collapse_round(self._h, _p(v), len(v), _p(f), len(f), _p(q), C.byref(prm), int(need), _p(ov), _p(of), _p(oq),
+                                                          C.byref(nfo), _p(sel), C.byref(nsel), C.byref(nkept)))
+        return ov[:len(v)].copy(), of[:int(nfo.value)].copy(), oq[:len(v)].copy(), sel[:int(nsel.value)].copy(), int(nkept.value)
 
     # ---- colours of the mesh from the rig's views, where run() calls TextureStitcher (DESIGN.md 9 f9; csrc/k_meshcolor.hip) ----
     @staticmethod

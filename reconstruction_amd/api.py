@@ -252,6 +252,7 @@ class CloudOptimization:
     trim_mesh() (mesh.bat's SurfaceTrimmer: the surface cut where the samples' density falls below a depth, on the GPU),
     clean_mesh() (what meshlab.bat goes on to do: Laplacian smoothing and the removal of isolated pieces and bad faces, on the GPU),
     close_mesh_holes() (its last filter: small border loops filled with their least-area triangulation, on the GPU),
+    decimate_mesh() (decimation.mlx: the mesh thinned to a face count by quadric edge collapses, on the GPU),
     color_mesh() (where run() ends with TextureStitcher: the mesh's vertices coloured from every camera's rectified image, on the
     GPU), stitch_mesh() (the tool's seam removal: the views' exposure seams levelled in those colours, on the GPU).  `cloud_normals` accumulates what the
     reference's global `*cloud_normals += *cloud_normal` (:123) does: per pair (xyz float32 [m,3], normals float32 [m,4])."""
@@ -356,6 +357,17 @@ class CloudOptimization:
         if getattr(self, "mesh_result", None) is None:
             raise ValueError("CloudOptimization.close_mesh_holes: mesh() first (it closes the small holes of mesh()'s surface)")
         self.mesh_result = self._ctx.mesh_close_holes_last(max_hole_size)
+        self.mesh_colors = None
+        return self.mesh_result
+
+    def decimate_mesh(self, target_faces=100000, **params):
+        """Where a user of the reference reaches for Demo/meshlab/decimation.mlx ("Quadric Edge Collapse Decimation", TargetFaceNum 100000):
+        mesh_result thinned to target_faces faces by rounds of independent edge collapses (Context.mesh_decimate_last on the mesh mesh() /
+        clean_mesh() / close_mesh_holes() left with the context, without a host round trip).  params: the script's other
+        parameters, Context.mesh_decimate_params'.  Replaces mesh_result."""
+        if getattr(self, "mesh_result", None) is None:
+            raise ValueError("CloudOptimization.decimate_mesh: mesh() first (it decimates mesh()'s surface)")
+        self.mesh_result = self._ctx.mesh_decimate_last(target_faces=target_faces, **params)
         self.mesh_colors = None
         return self.mesh_result
 

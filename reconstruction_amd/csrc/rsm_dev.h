@@ -267,6 +267,20 @@ int hole_triangulate_device(const float *d_ring, int L, const uint8_t *d_mask, d
 int mesh_close_holes_device(const float *d_v, int64_t nv, const int32_t *d_f, int64_t nf, const rsm_mesh_close_params *p, PoissonMesh *out, double *stats,
                             int *invalid, hipStream_t st);
 
+// the decimation of the final mesh (k_meshdecimate.hip).  Device buffers: nv float xyz, nf int32 x 3, quadrics nv x 10
+// double; *invalid as mesh_clean_device's; parameters are the caller's to check.
+struct rsm_mesh_decimate_params;
+int mesh_quadrics_device(const float *d_v, int64_t nv, const int32_t *d_f, int64_t nf, double boundary_weight, double *d_q, int *invalid, hipStream_t st);
+// per unique edge in key order (room for 3 nf each): key, multiplicity, cost (+inf: no candidate), reject code, position
+int mesh_collapse_costs_device(const float *d_v, int64_t nv, const int32_t *d_f, int64_t nf, const double *d_q, const rsm_mesh_decimate_params *p, uint64_t *d_key,
+                               int32_t *d_mult, double *d_cost, int32_t *d_reject, float *d_pos, int64_t *n_edges, int *invalid, hipStream_t st);
+// one round: d_v and d_q are updated in place, the faces go to d_fout (room for nf), the selected keys in priority order to d_sel (room for 3 nf)
+int mesh_collapse_round_device(float *d_v, int64_t nv, const int32_t *d_f, int64_t nf, double *d_q, const rsm_mesh_decimate_params *p, int64_t need, int32_t *d_fout,
+                               int64_t *nf_out, uint64_t *d_sel, int64_t *n_selected, int64_t *n_kept, int *invalid, hipStream_t st);
+// the whole call; the result replaces *out, which may own d_v / d_f; stats: RSM_MESH_DECIMATE_STATS doubles, may be NULL
+int mesh_decimate_device(const float *d_v, int64_t nv, const int32_t *d_f, int64_t nf, const rsm_mesh_decimate_params *p, PoissonMesh *out, double *stats,
+                         int *invalid, hipStream_t st);
+
 // the density trim of the surface (k_meshtrim.hip).  Device buffers: n float xyz samples with float4 normals (d_sn4 may be
 // NULL: a finite point is a valid sample), nv float xyz, nf int32 x 3.  Parameters are the caller's to check; each call validates the
 // mesh it is given, and RSM_E_INVALID comes with *invalid as mesh_clean_device's.

@@ -1,5 +1,6 @@
-// rsm_mesh.hip -- the mesh back end's host side: the dense-grid Poisson surface, its smoothing and clean-up, its density trim, and its colours
-// from the rig's views with their seams levelled (k_poisson.hip, k_meshclean.hip, k_meshtrim.hip, k_meshcolor.hip, k_meshstitch.hip).
+// rsm_mesh.hip -- the mesh back end's host side: the dense-grid Poisson surface, its smoothing and clean-up, its density trim, the closing of
+// its holes, its decimation, and its colours from the rig's views with their seams levelled (k_poisson.hip, k_meshclean.hip, k_meshtrim.hip,
+// k_meshclose.hip, k_meshdecimate.hip, k_meshcolor.hip, k_meshstitch.hip).
 #include "rsm_ctx.h"
 
 #include <cmath>
@@ -521,6 +522,157 @@ extern "C" int rsm_stage_hole_triangulate(rsm_ctx *c, const float *ring_xyz, int
     if (s != RSM_OK) return s;
     if ((s = hole_triangulate_device(dr, L, dm, weight, dt, n_triangles, c->stream)) != RSM_OK) return meshclose_fail(c, s, 0);
     if (*n_triangles > 0) HIPCHK(c, hipMemcpyAsync(triangles, dt, sizeof(int32_t) * 3 * (size_t)*n_triangles, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RSM_OK;
+}
+
+// ---- the decimation of the final mesh (k_meshdecimate.hip) ----------------------------------------------------------------
+static int meshdecimate_params_ok(rsm_ctx *c, const rsm_mesh_decimate_params *p) {
+    if (!p) return set_err(c, RSM_E_INVALID, "mesh_decimate: params is NULL");
+    if (p->target_faces < 0) return set_err(c, RSM_E_INVALID, "mesh_decimate: target_faces %lld < 0", (long long)p->target_faces);
+    if (!(p->target_fraction >= 0.0 && p->target_fraction <= 1.0)) return set_err(c, RSM_E_INVALID, "mesh_decimate: target_fraction %g outside [0, 1]", p->target_fraction);
+    if (!(p->quality_thr >= 0.0 && p->quality_thr <= 1.0)) return set_err(c, RSM_E_INVALID, "mesh_decimate: quality_thr %g outside [0, 1]", p->quality_thr);
+    if (!std::isfinite(p->boundary_weight) || !(p->boundary_weight > 0.0))
+        return set_err(c, RSM_E_INVALID, "mesh_decimate: boundary_weight %g not finite or not positive", p->boundary_weight);
+    if (!std::isfinite(p->min_error) || p->min_error < 0.0) return set_err(c, RSM_E_INVALID, "mesh_decimate: min_error %g negative or not finite", p->min_error);
+    if (p->max_rounds < 1 || p->max_rounds > 1000000) return set_err(c, RSM_E_INVALID, "mesh_decimate: max_rounds %d outside 1..1000000", p->max_rounds);
+    const int flag[4] = {p->preserve_boundary, p->preserve_normal, p->preserve_topology, p->optimal_placement};
+    const char *name[4] = {"preserve_boundary", "preserve_normal", "preserve_topology", "optimal_placement"};
+    for (int i = 0; i < 4; i++)
+        if (flag[i] != 0 && flag[i] != 1) return set_err(c, RSM_E_INVALID, "mesh_decimate: %s %d not 0 or 1", name[i], flag[i]);
+    return RSM_OK;
+}
+static int meshdecimate_fail(rsm_ctx *c, int s, int invalid) {
+    if (s == RSM_E_INVALID) return set_err(c, s, invalid == 1 ? "mesh_decimate: a face index outside [0, nv)" : "mesh_decimate: a coordinate that is not finite");
+    if (s == RSM_E_NOMEM) return set_err(c, s, "mesh_decimate: no device memory");
+    return set_err(c, s, "mesh_decimate: failed%s", hip_tail(s).c_str());
+}
+// d_xyz / d_faces may be c->pmesh's own buffers
+static int meshdecimate_run(rsm_ctx *c, const float *d_xyz, int64_t nv, const int32_t *d_faces, int64_t nf, const rsm_mesh_decimate_params *p, int64_t *n_vertices,
+                            int64_t *n_faces, double *stats) {
+    int invalid = 0;
+    const int s = mesh_decimate_device(d_xyz, nv, d_faces, nf, p, &c->pmesh, stats, &invalid, c->stream);
+    if (s != RSM_OK) return meshdecimate_fail(c, s, invalid);
+    c->mcol_of = nullptr; // (the colours belonged to the mesh this one replaces)
+    *n_vertices = c->pmesh.nv;
+    *n_faces = c->pmesh.nf;
+    return RSM_OK;
+}
+
+extern "C" int rsm_mesh_decimate_device(rsm_ctx *c, const float *d_xyz, int64_t nv, const int32_t *d_faces, int64_t nf, const rsm_mesh_decimate_params *p,
+                                        int64_t *n_vertices, int64_t *n_faces, double *stats) {
+    if (!c) return RSM_E_INVALID;
+    int s = meshdecimate_params_ok(c, p);
+    if (s != RSM_OK || (s = mesh_counts_ok(c, "mesh_decimate", nv, nf)) != RSM_OK) return s;
+    if (!n_vertices || !n_faces || (nv > 0 && !d_xyz) || (nf > 0 && !d_faces)) return set_err(c, RSM_E_INVALID, "mesh_decimate: a NULL pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    return meshdecimate_run(c, d_xyz, nv, d_faces, nf, p, n_vertices, n_faces, stats);
+}
+
+extern "C" int rsm_mesh_decimate(rsm_ctx *c, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, const rsm_mesh_decimate_params *p, int64_t *n_vertices,
+                                 int64_t *n_faces, double *stats) {
+    if (!c) return RSM_E_INVALID;
+    int s = meshdecimate_params_ok(c, p);
+    if (s != RSM_OK || (s = mesh_counts_ok(c, "mesh_decimate", nv, nf)) != RSM_OK) return s;
+    if (!n_vertices || !n_faces || (nv > 0 && !xyz) || (nf > 0 && !faces)) return set_err(c, RSM_E_INVALID, "mesh_decimate: a NULL pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    Tmp T(c);
+    float *dv = T.up(xyz, 3 * (size_t)nv);
+    int32_t *df = T.up(faces, 3 * (size_t)nf);
+    if (!dv || !df) return set_err(c, RSM_E_NOMEM, "mesh_decimate: no device memory for %lld vertices, %lld faces", (long long)nv, (long long)nf);
+    if ((s = finish(c, T)) != RSM_OK) return s;
+    return meshdecimate_run(c, dv, nv, df, nf, p, n_vertices, n_faces, stats);
+}
+
+extern "C" int rsm_mesh_decimate_last(rsm_ctx *c, const rsm_mesh_decimate_params *p, int64_t *n_vertices, int64_t *n_faces, double *stats) {
+    if (!c) return RSM_E_INVALID;
+    const int s = meshdecimate_params_ok(c, p);
+    if (s != RSM_OK) return s;
+    if (!n_vertices || !n_faces) return set_err(c, RSM_E_INVALID, "mesh_decimate: a NULL pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    return meshdecimate_run(c, c->pmesh.d_v, c->pmesh.nv, c->pmesh.d_f, c->pmesh.nf, p, n_vertices, n_faces, stats);
+}
+
+extern "C" int rsm_stage_mesh_quadrics(rsm_ctx *c, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, double boundary_weight, double *out_q) {
+    if (!c) return RSM_E_INVALID;
+    int s = mesh_counts_ok(c, "mesh_decimate", nv, nf);
+    if (s != RSM_OK) return s;
+    if (!std::isfinite(boundary_weight) || !(boundary_weight > 0.0))
+        return set_err(c, RSM_E_INVALID, "mesh_decimate: boundary_weight %g not finite or not positive", boundary_weight);
+    if ((nv > 0 && (!xyz || !out_q)) || (nf > 0 && !faces)) return set_err(c, RSM_E_INVALID, "mesh_decimate: a NULL pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    Tmp T(c);
+    float *dv = T.up(xyz, 3 * (size_t)nv);
+    int32_t *df = T.up(faces, 3 * (size_t)nf);
+    double *dq = T.alloc<double>(10 * (size_t)nv);
+    if (!dv || !df || !dq) return set_err(c, RSM_E_NOMEM, "mesh_decimate: no device memory");
+    if ((s = finish(c, T)) != RSM_OK) return s;
+    int invalid = 0;
+    if ((s = mesh_quadrics_device(dv, nv, df, nf, boundary_weight, dq, &invalid, c->stream)) != RSM_OK) return meshdecimate_fail(c, s, invalid);
+    if (nv > 0) HIPCHK(c, hipMemcpyAsync(out_q, dq, sizeof(double) * 10 * (size_t)nv, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RSM_OK;
+}
+
+extern "C" int rsm_stage_mesh_collapse_costs(rsm_ctx *c, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, const double *quadrics,
+                                             const rsm_mesh_decimate_params *p, uint64_t *keys, int32_t *multiplicity, double *cost, int32_t *reject, float *position,
+                                             int64_t *n_edges) {
+    if (!c) return RSM_E_INVALID;
+    int s = meshdecimate_params_ok(c, p);
+    if (s != RSM_OK || (s = mesh_counts_ok(c, "mesh_decimate", nv, nf)) != RSM_OK) return s;
+    if (!n_edges || (nv > 0 && (!xyz || !quadrics)) || (nf > 0 && (!faces || !keys || !multiplicity || !cost || !reject || !position)))
+        return set_err(c, RSM_E_INVALID, "mesh_decimate: a NULL pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t n = 3 * (size_t)nf;
+    Tmp T(c);
+    float *dv = T.up(xyz, 3 * (size_t)nv);
+    int32_t *df = T.up(faces, n);
+    double *dq = T.up(quadrics, 10 * (size_t)nv);
+    uint64_t *dk = T.alloc<uint64_t>(n);
+    int32_t *dm = T.alloc<int32_t>(n), *dr = T.alloc<int32_t>(n);
+    double *dc = T.alloc<double>(n);
+    float *dp = T.alloc<float>(3 * n);
+    if (!dv || !df || !dq || !dk || !dm || !dr || !dc || !dp) return set_err(c, RSM_E_NOMEM, "mesh_decimate: no device memory");
+    if ((s = finish(c, T)) != RSM_OK) return s;
+    int invalid = 0;
+    if ((s = mesh_collapse_costs_device(dv, nv, df, nf, dq, p, dk, dm, dc, dr, dp, n_edges, &invalid, c->stream)) != RSM_OK) return meshdecimate_fail(c, s, invalid);
+    const size_t ne = (size_t)*n_edges;
+    if (ne > 0) {
+        HIPCHK(c, hipMemcpyAsync(keys, dk, sizeof(uint64_t) * ne, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(multiplicity, dm, sizeof(int32_t) * ne, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(cost, dc, sizeof(double) * ne, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(reject, dr, sizeof(int32_t) * ne, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(position, dp, sizeof(float) * 3 * ne, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return RSM_OK;
+}
+
+extern "C" int rsm_stage_mesh_collapse_round(rsm_ctx *c, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, const double *quadrics,
+                                             const rsm_mesh_decimate_params *p, int64_t need, float *out_xyz, int32_t *out_faces, double *out_quadrics,
+                                             int64_t *n_faces_out, uint64_t *selected_keys, int64_t *n_selected, int64_t *n_kept) {
+    if (!c) return RSM_E_INVALID;
+    int s = meshdecimate_params_ok(c, p);
+    if (s != RSM_OK || (s = mesh_counts_ok(c, "mesh_decimate", nv, nf)) != RSM_OK) return s;
+    if (need < 0) return set_err(c, RSM_E_INVALID, "mesh_decimate: need %lld < 0", (long long)need);
+    if (!n_faces_out || !n_selected || !n_kept || (nv > 0 && (!xyz || !quadrics || !out_xyz || !out_quadrics)) || (nf > 0 && (!faces || !out_faces || !selected_keys)))
+        return set_err(c, RSM_E_INVALID, "mesh_decimate: a NULL pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t n = 3 * (size_t)nf;
+    Tmp T(c);
+    float *dv = T.up(xyz, 3 * (size_t)nv);
+    int32_t *df = T.up(faces, n), *dfo = T.alloc<int32_t>(n);
+    double *dq = T.up(quadrics, 10 * (size_t)nv);
+    uint64_t *ds = T.alloc<uint64_t>(n);
+    if (!dv || !df || !dfo || !dq || !ds) return set_err(c, RSM_E_NOMEM, "mesh_decimate: no device memory");
+    if ((s = finish(c, T)) != RSM_OK) return s;
+    int invalid = 0;
+    if ((s = mesh_collapse_round_device(dv, nv, df, nf, dq, p, need, dfo, n_faces_out, ds, n_selected, n_kept, &invalid, c->stream)) != RSM_OK)
+        return meshdecimate_fail(c, s, invalid);
+    if (nv > 0) HIPCHK(c, hipMemcpyAsync(out_xyz, dv, sizeof(float) * 3 * (size_t)nv, hipMemcpyDeviceToHost, c->stream));
+    if (nv > 0) HIPCHK(c, hipMemcpyAsync(out_quadrics, dq, sizeof(double) * 10 * (size_t)nv, hipMemcpyDeviceToHost, c->stream));
+    if (*n_faces_out > 0) HIPCHK(c, hipMemcpyAsync(out_faces, dfo, sizeof(int32_t) * 3 * (size_t)*n_faces_out, hipMemcpyDeviceToHost, c->stream));
+    if (*n_selected > 0) HIPCHK(c, hipMemcpyAsync(selected_keys, ds, sizeof(uint64_t) * (size_t)*n_selected, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return RSM_OK;
 }
