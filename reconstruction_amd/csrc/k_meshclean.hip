@@ -3,13 +3,13 @@
 // "Remove Duplicate Faces", "Remove Zero Area Faces" and "Remove Faces from Non Manifold Edges", in that order.  Not a bit-parity port of
 // MeshLab / VCG (no source in the reference tree): every rule is defined in DESIGN.md 9 (f8) and restated in numpy in
 // tests/meshclean_restatement.py, and the kernels are held to that restatement exactly.
-//   edge table    per face with three distinct indices, edge j = (v_j, v_j+1): key (min << 32) | max, value 3 f + j; rocprim's stable
-//                 radix sort over the key bits in use; a run of equal keys = the faces on one edge (its incidence)   k_mesh_edge_keys, k_mc_edge_runs
-//   corner lists  stable sort of (vertex, 3 f + j): a CSR whose lists ascend                                          k_mc_corner_keys, k_mc_row_starts
+//   edge table    mesh_common.h's sorted table (mesh_edge_table); a run of equal keys = the faces on one edge (its incidence)      k_mc_edge_runs
+//   corner lists  mesh_common.h's CSR whose lists ascend (mesh_corner_lists)
 //   smoothing     one thread per vertex gathers through its corner list in ascending (f, j): a fixed order of fp64 basic operations,
 //                 no float atomics -- the same bits from run to run and as the restatement                            k_mc_smooth
 //   components    union-find over the runs (the larger root hooks under the smaller: a root is its component's lowest face), boxes by
 //                 ordered-integer atomics behind a per-block reduction                                                k_mc_edge_runs, k_mc_labels, k_mc_comp_boxes
+//                 (the box of all vertices: mesh_common.h's k_mesh_vertex_box)
 //   rules 2-4     duplicates inside the run of a face's lowest edge, zero area at corner 0, incidences recounted over the survivors
 //                                                                                                                     k_mc_duplicates, k_mc_classify, k_mc_nonmanifold
 //   compaction    faces and the vertices they use, both renumbered in order (as the trim of k_poisson.hip)
@@ -68,35 +68,7 @@ __global__ __launch_bounds__(256) void k_mc_edge_runs(const u64 *__restrict__ ke
     if (inc == 1) vborder[k >> 32] = vborder[k & 0xffffffffu] = 1; // (every writer stores the same value)
 }
 
-// ---- the corner lists ---------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_mc_corner_keys(const int32_t *__restrict__ f, size_t nf, uint32_t nv, uint32_t *__restrict__ key, uint32_t *__restrict__ val) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= nf) return;
-    const int v[3] = {f[3 * i], f[3 * i + 1], f[3 * i + 2]};
-    const bool ok = face_distinct(v[0], v[1], v[2]);
-    for (int j = 0; j < 3; j++) {
-        key[3 * i + j] = ok ? (uint32_t)v[j] : nv;
-        val[3 * i + j] = (uint32_t)(3 * i + j);
-    }
-}
-// row[v] = the first sorted position whose key is >= v, v = 0 .. nv
-__global__ __launch_bounds__(256) void k_mc_row_starts(const uint32_t *__restrict__ key, size_t n, size_t nv, uint32_t *__restrict__ row) {
-    const size_t v = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (v > nv) return;
-    size_t lo = 0, hi = n;
-    while (lo < hi) {
-        const size_t mid = (lo + hi) / 2;
-        if (key[mid] < (uint32_t)v) lo = mid + 1;
-        else hi = mid;
-    }
-    row[v] = (uint32_t)lo;
-}
-
 // ---- smoothing ----------------------------------------------------------------------------------------------------------------------
-struct D3 {
-    double x, y, z;
-};
-__device__ __forceinline__ D3 ldp(const float *__restrict__ p, int v) { return D3{(double)p[3 * (size_t)v], (double)p[3 * (size_t)v + 1], (double)p[3 * (size_t)v + 2]}; }
 // |(Pa - Pc) x (Pb - Pc)|^2 and (Pa - Pc) . (Pb - Pc), in the project's order (a0 b0 + a1 b1) + a2 b2
 __device__ __forceinline__ double corner_n2(const D3 &pc, const D3 &pa, const D3 &pb, double *dot) {
     const double u0 = pa.x - pc.x, u1 = pa.y - pc.y, u2 = pa.z - pc.z;
@@ -120,7 +92,7 @@ __global__ __launch_bounds__(256) void k_mc_smooth(const float *__restrict__ pin
                                                    const uint8_t *__restrict__ vborder, int boundary) {
     const size_t v = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (v >= nv) return;
-    const D3 P = ldp(pin, (int)v);
+    const D3 P = ld3(pin, (int)v);
     const bool border = vborder[v] != 0;
     if (border && !boundary) {
         for (int a = 0; a < 3; a++) pout[3 * v + a] = pin[3 * v + a];
@@ -140,7 +112,7 @@ __global__ __launch_bounds__(256) void k_mc_smooth(const float *__restrict__ pin
         const int j = (int)(c % 3);
         const int vi[3] = {f[3 * fi], f[3 * fi + 1], f[3 * fi + 2]};
         const int n1 = vi[(j + 1) % 3], n2 = vi[(j + 2) % 3];
-        const D3 p1 = ldp(pin, n1), p2 = ldp(pin, n2);
+        const D3 p1 = ld3(pin, n1), p2 = ld3(pin, n2);
         if (border) { // 1D: the other endpoint of every incidence-1 edge, weight 1
             if (einc[3 * fi + j] == 1) {
                 sx += p1.x;
@@ -230,20 +202,6 @@ __global__ __launch_bounds__(256) void k_mc_box_init(unsigned int *__restrict__ 
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i < n6) box[i] = (i % 6) < 3 ? 0xffffffffu : 0u;
 }
-__global__ __launch_bounds__(256) void k_mc_vertex_box(const float *__restrict__ p, size_t nv, unsigned int *__restrict__ mm) {
-    __shared__ unsigned int s_mm[6];
-    if (threadIdx.x < 6) s_mm[threadIdx.x] = threadIdx.x < 3 ? 0xffffffffu : 0u;
-    __syncthreads();
-    for (size_t v = (size_t)blockIdx.x * 256 + threadIdx.x; v < nv; v += (size_t)gridDim.x * 256)
-        for (int a = 0; a < 3; a++) {
-            const unsigned int o = f2ord(p[3 * v + a]);
-            atomicMin(&s_mm[a], o);
-            atomicMax(&s_mm[3 + a], o);
-        }
-    __syncthreads();
-    if (threadIdx.x < 3) atomicMin(&mm[threadIdx.x], s_mm[threadIdx.x]);
-    else if (threadIdx.x < 6) atomicMax(&mm[threadIdx.x], s_mm[threadIdx.x]);
-}
 // a component goes when the fp64 diameter of its float32 box is below the threshold (strictly)
 __global__ __launch_bounds__(256) void k_mc_comp_dead(const int32_t *__restrict__ label, size_t nf, const unsigned int *__restrict__ box, double threshold,
                                                       uint8_t *__restrict__ dead, u64 *__restrict__ ctr) {
@@ -251,10 +209,7 @@ __global__ __launch_bounds__(256) void k_mc_comp_dead(const int32_t *__restrict_
     bool d = false;
     if (i < nf) {
         if (label[i] == (int)i) {
-            const unsigned int *b = box + 6 * i;
-            const double dx = (double)ord2f(b[3]) - (double)ord2f(b[0]), dy = (double)ord2f(b[4]) - (double)ord2f(b[1]),
-                         dz = (double)ord2f(b[5]) - (double)ord2f(b[2]);
-            d = sqrt((dx * dx + dy * dy) + dz * dz) < threshold;
+            d = sqrt(box_diagonal2(box + 6 * i)) < threshold;
         }
         dead[i] = d ? 1 : 0;
     }
@@ -299,7 +254,7 @@ __global__ __launch_bounds__(256) void k_mc_classify(const float *__restrict__ p
             if (!face_distinct(a, b, c)) r3 = true;
             else {
                 double dot;
-                r3 = corner_n2(ldp(p, a), ldp(p, b), ldp(p, c), &dot) == 0.0;
+                r3 = corner_n2(ld3(p, a), ld3(p, b), ld3(p, c), &dot) == 0.0;
             }
         }
         alive[i] = live && !r3;
@@ -374,8 +329,7 @@ static int edge_table(DevMem &M, Tables &T, const int32_t *d_f, size_t nv, size_
     }
     if (want_uf) T.parent = M.get<int>(nf);
     if (!M.ok) return RSM_E_NOMEM;
-    hipLaunchKernelGGL(k_mesh_edge_keys<>, blocks_for(nf), dim3(256), 0, st, d_f, nf, (u64)nv, k0, v0);
-    const int s = sort_pairs(M, k0, T.ekey, v0, T.eval, n, 32 + key_bits((u64)nv), st);
+    const int s = mesh_edge_table(M, d_f, nv, nf, k0, v0, T.ekey, T.eval, st);
     if (s != RSM_OK) return s;
     if (want_inc) {
         DEVCHK(hipMemsetAsync(T.einc, 0, n, st));
@@ -392,7 +346,7 @@ static int smooth(DevMem &M, const Tables &T, const float *d_in, size_t nv, cons
     *d_res = d_in;
     if (steps <= 0 || nv == 0 || nf == 0) return RSM_OK;
     uint32_t *corner = nullptr, *row = nullptr;
-    const int s = mesh_corner_lists_device(M, d_f, nv, nf, &row, &corner, st);
+    const int s = mesh_corner_lists(M, d_f, nv, nf, &row, &corner, st);
     if (s != RSM_OK) return s;
     float *buf[2] = {M.get<float>(3 * nv), M.get<float>(3 * nv)};
     if (!M.ok) return RSM_E_NOMEM;
@@ -411,33 +365,12 @@ static int smooth(DevMem &M, const Tables &T, const float *d_in, size_t nv, cons
     return RSM_OK;
 }
 
-static int finish(hipStream_t st) {
-    DEVCHK(hipStreamSynchronize(st));
-    DEVCHK(hipGetLastError());
-    return RSM_OK;
-}
-
 } // namespace
 
 int mesh_validate_device(const float *d_v, int64_t nv, const int32_t *d_f, int64_t nf, int *invalid, hipStream_t st) {
     DevMem M;
     Tables T;
     return validate(M, T, d_v, (size_t)nv, d_f, (size_t)nf, invalid, st);
-}
-
-int mesh_corner_lists_device(DevMem &M, const int32_t *d_f, size_t nv, size_t nf, uint32_t **row, uint32_t **corner, hipStream_t st) {
-    const size_t n = 3 * nf;
-    uint32_t *k0 = M.get<uint32_t>(n), *k1 = M.get<uint32_t>(n), *v0 = M.get<uint32_t>(n);
-    *corner = M.get<uint32_t>(n);
-    *row = M.get<uint32_t>(nv + 1);
-    if (!M.ok) return RSM_E_NOMEM;
-    if (nf > 0) {
-        hipLaunchKernelGGL(k_mc_corner_keys, blocks_for(nf), dim3(256), 0, st, d_f, nf, (uint32_t)nv, k0, v0);
-        const int s = sort_pairs(M, k0, k1, v0, *corner, n, key_bits((u64)nv), st);
-        if (s != RSM_OK) return s;
-    }
-    hipLaunchKernelGGL(k_mc_row_starts, blocks_for(nv + 1), dim3(256), 0, st, (const uint32_t *)k1, n, nv, *row);
-    return RSM_OK;
 }
 
 int mesh_smooth_device(const float *d_v, int64_t nv_, const int32_t *d_f, int64_t nf_, int steps, int cotangent, int boundary, float *d_out, int64_t *n_border,
@@ -457,7 +390,7 @@ int mesh_smooth_device(const float *d_v, int64_t nv_, const int32_t *d_f, int64_
     if (nv > 0) DEVCHK(hipMemcpyAsync(d_out, res, 3 * nv * sizeof(float), hipMemcpyDeviceToDevice, st));
     u64 h[C_N];
     DEVCHK(hipMemcpyAsync(h, T.ctr, sizeof h, hipMemcpyDeviceToHost, st));
-    if ((s = finish(st)) != RSM_OK) return s;
+    if ((s = mesh_finish(st)) != RSM_OK) return s;
     *n_border = (int64_t)h[C_BORDER];
     return RSM_OK;
 }
@@ -473,7 +406,7 @@ int mesh_components_device(const int32_t *d_f, int64_t nv_, int64_t nf_, int32_t
     hipLaunchKernelGGL(k_mc_labels, blocks_for(nf), dim3(256), 0, st, d_f, nf, T.parent, d_label, T.ctr);
     u64 h[C_N];
     DEVCHK(hipMemcpyAsync(h, T.ctr, sizeof h, hipMemcpyDeviceToHost, st));
-    if ((s = finish(st)) != RSM_OK) return s;
+    if ((s = mesh_finish(st)) != RSM_OK) return s;
     *n_components = (int64_t)h[C_COMPS];
     return RSM_OK;
 }
@@ -503,11 +436,10 @@ int mesh_clean_device(const float *d_v, int64_t nv_, const int32_t *d_f, int64_t
     double D = 0.0;
     if (nv > 0) {
         unsigned int h[6];
-        hipLaunchKernelGGL(k_mc_vertex_box, dim3((unsigned)std::min<size_t>(1024, (nv + 255) / 256)), dim3(256), 0, st, pos, nv, box + 6 * nf);
+        hipLaunchKernelGGL(k_mesh_vertex_box<>, dim3((unsigned)std::min<size_t>(1024, (nv + 255) / 256)), dim3(256), 0, st, pos, nv, box + 6 * nf);
         DEVCHK(hipMemcpyAsync(h, box + 6 * nf, sizeof h, hipMemcpyDeviceToHost, st));
-        if ((s = finish(st)) != RSM_OK) return s;
-        const double dx = (double)ord2f(h[3]) - (double)ord2f(h[0]), dy = (double)ord2f(h[4]) - (double)ord2f(h[1]), dz = (double)ord2f(h[5]) - (double)ord2f(h[2]);
-        D = sqrt((dx * dx + dy * dy) + dz * dz);
+        if ((s = mesh_finish(st)) != RSM_OK) return s;
+        D = sqrt(box_diagonal2(h));
     }
     const double threshold = p->min_piece_relative ? p->min_piece * D : p->min_piece;
     S[12] = D;
@@ -535,19 +467,14 @@ int mesh_clean_device(const float *d_v, int64_t nv_, const int32_t *d_f, int64_t
         uint64_t kf = 0, kv = 0;
         if ((s = scan_totals(fkeep, fpos, nf, vused, vpos, nv, st, &kf, &kv)) != RSM_OK) return s;
         if (kf > 0) {
-            if (hipMalloc((void **)&res.d_v, kv * 3 * sizeof(float)) != hipSuccess || hipMalloc((void **)&res.d_f, kf * 3 * sizeof(int32_t)) != hipSuccess) {
-                poisson_mesh_free(&res);
-                return RSM_E_NOMEM;
-            }
-            res.nv = (int64_t)kv;
-            res.nf = (int64_t)kf;
+            if ((s = mesh_result_alloc(res, kv, kf)) != RSM_OK) return s;
             hipLaunchKernelGGL(k_mesh_compact_faces<>, blocks_for(nf), dim3(256), 0, st, d_f, nf, (const unsigned int *)fkeep, (const unsigned int *)fpos,
                                (const unsigned int *)vpos, res.d_f);
             hipLaunchKernelGGL(k_mesh_compact_verts<>, blocks_for(nv), dim3(256), 0, st, pos, nv, (const unsigned int *)vused, (const unsigned int *)vpos, res.d_v);
         }
     }
     u64 h[C_N];
-    if (hipMemcpyAsync(h, T.ctr, sizeof h, hipMemcpyDeviceToHost, st) != hipSuccess || finish(st) != RSM_OK) {
+    if (hipMemcpyAsync(h, T.ctr, sizeof h, hipMemcpyDeviceToHost, st) != hipSuccess || mesh_finish(st) != RSM_OK) {
         poisson_mesh_free(&res);
         return RSM_E_HIP;
     }
@@ -562,7 +489,6 @@ int mesh_clean_device(const float *d_v, int64_t nv_, const int32_t *d_f, int64_t
     S[10] = (double)h[C_RM4];
     S[11] = (double)(nv - (size_t)res.nv);
     if (stats) memcpy(stats, S, sizeof S);
-    poisson_mesh_free(out); // (the input may be *out's own buffers: they were read to the end above)
-    *out = res;
+    mesh_result_commit(out, res);
     return RSM_OK;
 }

@@ -1,7 +1,7 @@
 // k_meshclose.hip -- script2.mlx's last filter, "Close Holes" (MaxHoleSize 30), on the cleaned surface.  Not a bit-parity
 // port of MeshLab / VCG (no source in the reference tree): every rule is defined in DESIGN.md 9 (f12) and restated in numpy in
 // tests/meshclose_restatement.py, and the kernels are held to that restatement exactly -- the same faces in the same order.
-//   border        the sorted edge table of k_meshclean.hip; an entry whose run has length 1 is a border entry, directed as its face
+//   border        the sorted edge table of mesh_common.h; an entry whose run has length 1 is a border entry, directed as its face
 //                 (tail v_j, head v_j+1); per vertex the border entries that leave / reach it are counted by integer atomics, and the one
 //                 entry of a simple vertex (one in, one out) is recorded by a plain store                          k_ch_border
 //   components    union-find over the entries (mesh_common.h): e joins the entry that leaves its head when the head is simple; size and
@@ -269,12 +269,6 @@ __global__ __launch_bounds__(256) void k_ch_gather(size_t total, int stride, con
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------------------
-static int finish(hipStream_t st) {
-    DEVCHK(hipStreamSynchronize(st));
-    DEVCHK(hipGetLastError());
-    return RSM_OK;
-}
-
 struct Loops {
     u64 *ctr = nullptr, *ekey = nullptr;
     uint32_t *eval = nullptr;
@@ -309,8 +303,7 @@ static int border_loops(DevMem &M, Loops &T, const int32_t *d_f, size_t nv, size
     DEVCHK(hipMemsetAsync(T.out_entry, 0, nv * sizeof(int), st));
     DEVCHK(hipMemsetAsync(T.csize, 0, n * sizeof(int), st));
     DEVCHK(hipMemsetAsync(T.copen, 0, n * sizeof(int), st));
-    hipLaunchKernelGGL(k_mesh_edge_keys<>, blocks_for(nf), dim3(256), 0, st, d_f, nf, (u64)nv, k0, v0);
-    const int s = sort_pairs(M, k0, T.ekey, v0, T.eval, n, 32 + key_bits((u64)nv), st);
+    const int s = mesh_edge_table(M, d_f, nv, nf, k0, v0, T.ekey, T.eval, st);
     if (s != RSM_OK) return s;
     hipLaunchKernelGGL(k_ch_border, blocks_for(n), dim3(256), 0, st, (const u64 *)T.ekey, (const uint32_t *)T.eval, n, (u64)nv, d_f, T.isb, T.n_in, T.n_out, T.in_entry,
                        T.out_entry, T.ctr);
@@ -355,7 +348,7 @@ int mesh_border_loops_device(const int32_t *d_f, int64_t nv_, int64_t nf_, int32
     DEVCHK(hipMemcpyAsync(d_label, T.label, n * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
     u64 h[H_N];
     DEVCHK(hipMemcpyAsync(h, T.ctr, sizeof h, hipMemcpyDeviceToHost, st));
-    if ((s = finish(st)) != RSM_OK) return s;
+    if ((s = mesh_finish(st)) != RSM_OK) return s;
     *n_components = (int64_t)h[H_COMPS];
     return RSM_OK;
 }
@@ -370,7 +363,7 @@ int hole_triangulate_device(const float *d_ring, int L, const uint8_t *d_mask, d
     unsigned int hn = 0;
     DEVCHK(hipMemcpyAsync(&hn, nadd, sizeof hn, hipMemcpyDeviceToHost, st));
     DEVCHK(hipMemcpyAsync(weight, w, sizeof(double), hipMemcpyDeviceToHost, st));
-    const int s = finish(st);
+    const int s = mesh_finish(st);
     if (s != RSM_OK) return s;
     *n_tri = (int)hn;
     return RSM_OK;
@@ -418,12 +411,7 @@ int mesh_close_holes_device(const float *d_v, int64_t nv_, const int32_t *d_f, i
     }
     // the result: the input's vertices and faces, the new faces behind them
     const size_t nfo = nf + (size_t)added;
-    if ((nv > 0 && hipMalloc((void **)&res.d_v, nv * 3 * sizeof(float)) != hipSuccess) || (nfo > 0 && hipMalloc((void **)&res.d_f, nfo * 3 * sizeof(int32_t)) != hipSuccess)) {
-        poisson_mesh_free(&res);
-        return RSM_E_NOMEM;
-    }
-    res.nv = (int64_t)nv;
-    res.nf = (int64_t)nfo;
+    if ((s = mesh_result_alloc(res, nv, nfo)) != RSM_OK) return s;
     bool ok = true;
     if (nv > 0) ok = ok && hipMemcpyAsync(res.d_v, d_v, nv * 3 * sizeof(float), hipMemcpyDeviceToDevice, st) == hipSuccess;
     if (nf > 0) ok = ok && hipMemcpyAsync(res.d_f, d_f, n * sizeof(int32_t), hipMemcpyDeviceToDevice, st) == hipSuccess;
@@ -431,7 +419,7 @@ int mesh_close_holes_device(const float *d_v, int64_t nv_, const int32_t *d_f, i
         hipLaunchKernelGGL(k_ch_gather, blocks_for((size_t)stride * holes), dim3(256), 0, st, (size_t)stride * holes, stride, (const unsigned int *)nadd,
                            (const unsigned int *)off, (const int32_t *)tri, res.d_f + n);
     if (work) ok = ok && hipMemcpyAsync(h, T.ctr, sizeof h, hipMemcpyDeviceToHost, st) == hipSuccess;
-    if (!ok || finish(st) != RSM_OK) {
+    if (!ok || mesh_finish(st) != RSM_OK) {
         poisson_mesh_free(&res);
         return RSM_E_HIP;
     }
@@ -448,7 +436,6 @@ int mesh_close_holes_device(const float *d_v, int64_t nv_, const int32_t *d_f, i
     S[12] = (double)h[H_LMAX_CLOSED];
     S[13] = (double)h[H_LMAX_SEEN];
     if (stats) memcpy(stats, S, sizeof S);
-    poisson_mesh_free(out); // (the input may be *out's own buffers: they were read to the end above)
-    *out = res;
+    mesh_result_commit(out, res);
     return RSM_OK;
 }

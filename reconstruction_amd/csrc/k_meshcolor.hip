@@ -367,7 +367,7 @@ int mesh_color_scene_device(DevMem &M, const float *d_v, int64_t nv_, const int3
     if (!M.ok) return RSM_E_NOMEM;
     DEVCHK(hipMemsetAsync(ctr, 0, K_N * sizeof(u64), st));
     uint32_t *row = nullptr, *corner = nullptr;
-    if ((s = mesh_corner_lists_device(M, d_f, nv, nf, &row, &corner, st)) != RSM_OK) return s;
+    if ((s = mesh_corner_lists(M, d_f, nv, nf, &row, &corner, st)) != RSM_OK) return s;
     if ((s = raster(M, d_v, d_f, nf, hv, d_views, big_box, ctr, st)) != RSM_OK) return s;
     hipLaunchKernelGGL(k_mcol_color, blocks_for(nv), dim3(256), 0, st, d_v, nv, d_f, (const uint32_t *)row, (const uint32_t *)corner, (const McView *)d_views, V,
                        p->mode, p->min_cos, p->depth_eps, d_rgb, d_best, d_vis, ctr);

@@ -4,7 +4,7 @@
 // the same order, the same float32 positions, the same fp64 quadrics and costs.
 //   quadrics     once: per vertex the sum over its corner list, ascending, of the face's plane quadric and of the border planes of the two
 //                edges of that corner                                                                   k_md_entry_border, k_md_quadrics
-//   a round      the sorted edge table -> the unique edges with their multiplicity, border and locked vertices     k_md_heads, k_md_unique, k_md_vertex
+//   a round      mesh_common.h's sorted edge table -> the unique edges with their multiplicity, border and locked vertices     k_md_heads, k_md_unique, k_md_vertex
 //                a thread per unique edge: link condition, duplicate faces, placement, error, quality, normals     k_md_costs
 //                rank = the position in a stable sort by (cost bits, key order); the budget's participants;
 //                m1 / m2 by integer atomicMin; the independent set                                                   k_md_rank, k_md_m2, k_md_select
@@ -39,10 +39,6 @@ enum { C_LOCKED = R_N, C_KEPT, C_BKEPT, C_SELECTED, C_VALENCE, C_MAXCOST, C_N };
 __device__ __forceinline__ bool finite64(double x) { return ((u64)__double_as_longlong(x) & MD_INF_BITS) != MD_INF_BITS; }
 __device__ __forceinline__ bool finite32(float x) { return (__float_as_uint(x) & 0x7f800000u) != 0x7f800000u; }
 
-struct D3 {
-    double x, y, z;
-};
-__device__ __forceinline__ D3 ld3(const float *__restrict__ v, size_t i) { return D3{(double)v[3 * i], (double)v[3 * i + 1], (double)v[3 * i + 2]}; }
 __device__ __forceinline__ D3 sub3(const D3 &a, const D3 &b) { return D3{a.x - b.x, a.y - b.y, a.z - b.z}; }
 __device__ __forceinline__ double dot3(const D3 &a, const D3 &b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
 __device__ __forceinline__ D3 cross3(const D3 &u, const D3 &w) { return D3{u.y * w.z - u.z * w.y, u.z * w.x - u.x * w.z, u.x * w.y - u.y * w.x}; }
@@ -106,30 +102,6 @@ __global__ __launch_bounds__(256) void k_md_compact(const int32_t *__restrict__ 
     if (i >= nf || !fkeep[i]) return;
     const size_t o = fpos[i];
     for (int c = 0; c < 3; c++) out[3 * o + c] = f[3 * i + c];
-}
-
-// corner lists: key = the vertex of corner 3 f + j, nv for the corners of a face with a repeated index (they sort behind every list)
-__global__ __launch_bounds__(256) void k_md_corner_keys(const int32_t *__restrict__ f, size_t nf, uint32_t nv, uint32_t *__restrict__ key, uint32_t *__restrict__ val) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= nf) return;
-    const int a = f[3 * i], b = f[3 * i + 1], c = f[3 * i + 2];
-    const bool ok = face_distinct(a, b, c);
-    key[3 * i] = ok ? (uint32_t)a : nv;
-    key[3 * i + 1] = ok ? (uint32_t)b : nv;
-    key[3 * i + 2] = ok ? (uint32_t)c : nv;
-    for (int j = 0; j < 3; j++) val[3 * i + j] = (uint32_t)(3 * i + j);
-}
-// row[v] = the first sorted position whose key is >= v, v = 0 .. nv (a binary search per vertex)
-__global__ __launch_bounds__(256) void k_md_row_starts(const uint32_t *__restrict__ key, size_t n, size_t nv, uint32_t *__restrict__ row) {
-    const size_t v = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (v > nv) return;
-    size_t lo = 0, hi = n;
-    while (lo < hi) {
-        const size_t mid = (lo + hi) / 2;
-        if ((size_t)key[mid] < v) lo = mid + 1;
-        else hi = mid;
-    }
-    row[v] = (uint32_t)lo;
 }
 
 // per sorted position of the edge table: the entry of a run of length 1 is a border entry
@@ -458,12 +430,6 @@ __global__ __launch_bounds__(256) void k_md_renumber(const int32_t *__restrict__
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------------------
-static int finish(hipStream_t st) {
-    DEVCHK(hipStreamSynchronize(st));
-    DEVCHK(hipGetLastError());
-    return RSM_OK;
-}
-
 // the scratch of the rounds: an allocator (dev_prims.h) that hands out pieces of a few large blocks and starts over with rewind(), so that
 // only the first round allocates (a later round asks for the same pieces in the same order, none of them larger)
 struct Pool {
@@ -506,37 +472,25 @@ struct Round {
     float *pos = nullptr;
 };
 
+// both of mesh_common.h's tables
 template <class Alloc>
-static int edge_table(Alloc &M, Round &T, const int32_t *d_f, size_t nv, size_t nf, hipStream_t st) {
+static int tables(Alloc &M, Round &T, const int32_t *d_f, size_t nv, size_t nf, hipStream_t st) {
     const size_t n = 3 * nf;
     u64 *k0 = M.template get<u64>(n);
     uint32_t *v0 = M.template get<uint32_t>(n);
     T.ekey = M.template get<u64>(n);
     T.eval = M.template get<uint32_t>(n);
     if (!k0 || !v0 || !T.ekey || !T.eval) return RSM_E_NOMEM;
-    hipLaunchKernelGGL(k_mesh_edge_keys<>, blocks_for(nf), dim3(256), 0, st, d_f, nf, (u64)nv, k0, v0);
-    return sort_pairs(M, k0, T.ekey, v0, T.eval, n, 32 + key_bits((u64)nv), st);
-}
-template <class Alloc>
-static int corner_lists(Alloc &M, Round &T, const int32_t *d_f, size_t nv, size_t nf, hipStream_t st) {
-    const size_t n = 3 * nf;
-    uint32_t *k0 = M.template get<uint32_t>(n), *k1 = M.template get<uint32_t>(n), *v0 = M.template get<uint32_t>(n);
-    T.corner = M.template get<uint32_t>(n);
-    T.row = M.template get<uint32_t>(nv + 1);
-    if (!k0 || !k1 || !v0 || !T.corner || !T.row) return RSM_E_NOMEM;
-    hipLaunchKernelGGL(k_md_corner_keys, blocks_for(nf), dim3(256), 0, st, d_f, nf, (uint32_t)nv, k0, v0);
-    const int s = sort_pairs(M, k0, k1, v0, T.corner, n, key_bits((u64)nv), st);
-    if (s != RSM_OK) return s;
-    hipLaunchKernelGGL(k_md_row_starts, blocks_for(nv + 1), dim3(256), 0, st, (const uint32_t *)k1, n, nv, T.row);
-    return RSM_OK;
+    const int s = mesh_edge_table(M, d_f, nv, nf, k0, v0, T.ekey, T.eval, st);
+    return s != RSM_OK ? s : mesh_corner_lists(M, d_f, nv, nf, &T.row, &T.corner, st);
 }
 
 // nv > 0, nf > 0, a validated mesh
 template <class Alloc>
 static int quadrics(Alloc &M, const float *d_v, size_t nv, const int32_t *d_f, size_t nf, double bw, double *d_q, hipStream_t st) {
     Round T;
-    int s = edge_table(M, T, d_f, nv, nf, st);
-    if (s != RSM_OK || (s = corner_lists(M, T, d_f, nv, nf, st)) != RSM_OK) return s;
+    int s = tables(M, T, d_f, nv, nf, st);
+    if (s != RSM_OK) return s;
     uint8_t *isb = M.template get<uint8_t>(3 * nf);
     if (!isb) return RSM_E_NOMEM;
     DEVCHK(hipMemsetAsync(isb, 0, 3 * nf, st));
@@ -550,8 +504,8 @@ template <class Alloc>
 static int costs(Alloc &M, Round &T, const float *d_v, size_t nv, const int32_t *d_f, size_t nf, const double *d_q, const rsm_mesh_decimate_params *p, u64 *ctr,
                  hipStream_t st) {
     const size_t n = 3 * nf;
-    int s = edge_table(M, T, d_f, nv, nf, st);
-    if (s != RSM_OK || (s = corner_lists(M, T, d_f, nv, nf, st)) != RSM_OK) return s;
+    int s = tables(M, T, d_f, nv, nf, st);
+    if (s != RSM_OK) return s;
     unsigned int *head = M.template get<unsigned int>(n), *upos = M.template get<unsigned int>(n);
     T.vborder = M.template get<uint8_t>(nv);
     T.locked = M.template get<uint8_t>(nv);
@@ -636,7 +590,7 @@ int mesh_quadrics_device(const float *d_v, int64_t nv_, const int32_t *d_f, int6
     DEVCHK(hipMemsetAsync(d_q, 0, 10 * nv * sizeof(double), st));
     DevMem M;
     if (nf > 0 && (s = quadrics(M, d_v, nv, d_f, nf, boundary_weight, d_q, st)) != RSM_OK) return s;
-    return finish(st);
+    return mesh_finish(st);
 }
 
 int mesh_collapse_costs_device(const float *d_v, int64_t nv_, const int32_t *d_f, int64_t nf_, const double *d_q, const rsm_mesh_decimate_params *p, uint64_t *d_key,
@@ -659,7 +613,7 @@ int mesh_collapse_costs_device(const float *d_v, int64_t nv_, const int32_t *d_f
         DEVCHK(hipMemcpyAsync(d_pos, T.pos, 3 * T.ne * sizeof(float), hipMemcpyDeviceToDevice, st));
     }
     *n_edges = (int64_t)T.ne;
-    return finish(st);
+    return mesh_finish(st);
 }
 
 int mesh_collapse_round_device(float *d_v, int64_t nv_, const int32_t *d_f, int64_t nf_, double *d_q, const rsm_mesh_decimate_params *p, int64_t need, int32_t *d_fout,
@@ -690,7 +644,7 @@ int mesh_collapse_round_device(float *d_v, int64_t nv_, const int32_t *d_f, int6
     *nf_out = (int64_t)kept_faces;
     *n_selected = (int64_t)h[C_SELECTED];
     *n_kept = (int64_t)h[C_KEPT];
-    return finish(st);
+    return mesh_finish(st);
 }
 
 int mesh_decimate_device(const float *d_v, int64_t nv_, const int32_t *d_f, int64_t nf_, const rsm_mesh_decimate_params *p, PoissonMesh *out, double *stats, int *invalid,
@@ -752,16 +706,11 @@ int mesh_decimate_device(const float *d_v, int64_t nv_, const int32_t *d_f, int6
             DEVCHK(hipMemsetAsync(vused, 0, nv * sizeof(unsigned int), st));
             hipLaunchKernelGGL(k_md_used, blocks_for(3 * cur_nf), dim3(256), 0, st, (const int32_t *)F[cur], 3 * cur_nf, vused);
             if ((s = scan_u32(M, (const unsigned int *)vused, vpos, nv, st)) != RSM_OK || (s = scan_total(vused, vpos, nv, st, &kv)) != RSM_OK) return s;
-            if (hipMalloc((void **)&res.d_v, (size_t)kv * 3 * sizeof(float)) != hipSuccess || hipMalloc((void **)&res.d_f, cur_nf * 3 * sizeof(int32_t)) != hipSuccess) {
-                poisson_mesh_free(&res);
-                return RSM_E_NOMEM;
-            }
-            res.nv = (int64_t)kv;
-            res.nf = (int64_t)cur_nf;
+            if ((s = mesh_result_alloc(res, (size_t)kv, cur_nf)) != RSM_OK) return s;
             hipLaunchKernelGGL(k_md_renumber, blocks_for(3 * cur_nf), dim3(256), 0, st, (const int32_t *)F[cur], 3 * cur_nf, (const unsigned int *)vpos, res.d_f);
             hipLaunchKernelGGL(k_mesh_compact_verts<>, blocks_for(nv), dim3(256), 0, st, (const float *)V, nv, (const unsigned int *)vused, (const unsigned int *)vpos, res.d_v);
         }
-        if (finish(st) != RSM_OK) {
+        if (mesh_finish(st) != RSM_OK) {
             poisson_mesh_free(&res);
             return RSM_E_HIP;
         }
@@ -776,7 +725,6 @@ int mesh_decimate_device(const float *d_v, int64_t nv_, const int32_t *d_f, int6
     S[17] = maxcost;
     S[18] = res.nf <= target ? 1.0 : 0.0;
     if (stats) memcpy(stats, S, sizeof S);
-    poisson_mesh_free(out); // (the input may be *out's own buffers: they were read to the end above)
-    *out = res;
+    mesh_result_commit(out, res);
     return RSM_OK;
 }

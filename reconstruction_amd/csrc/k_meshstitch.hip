@@ -353,7 +353,7 @@ int mesh_stitch_rhs_device(const float *d_v, int64_t nv_, const int32_t *d_f, in
     McView *d_views = nullptr;
     if ((s = mesh_views_device(M, views, n_pairs, false, &hv, &d_views, invalid, st)) != RSM_OK) return s;
     uint32_t *row = nullptr, *corner = nullptr;
-    if ((s = mesh_corner_lists_device(M, d_f, nv, nf, &row, &corner, st)) != RSM_OK) return s;
+    if ((s = mesh_corner_lists(M, d_f, nv, nf, &row, &corner, st)) != RSM_OK) return s;
     Csr c;
     if ((s = build_csr(M, d_best, nv, d_f, nf, row, corner, &c, st)) != RSM_OK) return s;
     hipLaunchKernelGGL(k_mst_rhs, blocks_for(nv), dim3(256), 0, st, d_v, nv, d_best, d_rgb, (const u64 *)d_vis, (const McView *)d_views, seam_gradient,
@@ -375,7 +375,7 @@ int mesh_stitch_solve_device(const int32_t *d_f, int64_t nv_, int64_t nf_, const
     if (s != RSM_OK || nv == 0) return s;
     DevMem M;
     uint32_t *row = nullptr, *corner = nullptr;
-    if ((s = mesh_corner_lists_device(M, d_f, nv, nf, &row, &corner, st)) != RSM_OK) return s;
+    if ((s = mesh_corner_lists(M, d_f, nv, nf, &row, &corner, st)) != RSM_OK) return s;
     Csr c;
     if ((s = build_csr(M, d_best, nv, d_f, nf, row, corner, &c, st)) != RSM_OK) return s;
     u64 h[S_N];

@@ -6,9 +6,9 @@
 //                 (2^31 - 1) 2^32 < 2^63                                                                             k_mt_splat
 //   value         rho = the same weights times C 2^-32, eight fp64 terms in the corner order dz, dy, dx; value = max(0, kernel_depth +
 //                 1/2 log2(rho / samples_per_node))                                                                  k_mt_value
-//   smoothing     neighbour CSR in the order of the corner lists (as k_mst_csr), one gather launch per step, values ping-pong, no host
+//   smoothing     neighbour CSR in the order of mesh_common.h's corner lists (as k_mst_csr), one gather launch per step, values ping-pong, no host
 //                 synchronisation inside the loop                                                                   k_mt_csr, k_mt_step
-//   split         the first entry of a run of the sorted edge table whose ends lie on different sides of `trim` is a cut edge; its rank
+//   split         the first entry of a run of mesh_common.h's sorted edge table whose ends lie on different sides of `trim` is a cut edge; its rank
 //                 among them (a scan) numbers its vertex; faces count 0 / 1 / 3 triangles, scan, emit               k_mt_cut_flags .. k_mt_face_emit
 //   islands       the edge table of the split mesh, union-find per side, areas as 64-bit fixed point (llrint(area 2^32 / D^2) <= 2^31 per
 //                 triangle and fewer than 2^31 triangles: every sum stays below 2^62), integer atomics behind a per-block reduction for the
@@ -222,10 +222,6 @@ __global__ __launch_bounds__(256) void k_mt_face_count(const int32_t *__restrict
     count_if(spl, ctr + T_SPLIT);
 }
 
-struct D3 {
-    double x, y, z;
-};
-__device__ __forceinline__ D3 ldp(const float *__restrict__ p, int v) { return D3{(double)p[3 * (size_t)v], (double)p[3 * (size_t)v + 1], (double)p[3 * (size_t)v + 2]}; }
 __device__ __forceinline__ double dist2(const D3 &a, const D3 &b) {
     const double dx = a.x - b.x, dy = a.y - b.y, dz = a.z - b.z;
     return (dx * dx + dy * dy) + dz * dz;
@@ -263,14 +259,14 @@ __global__ __launch_bounds__(256) void k_mt_face_emit(const int32_t *__restrict_
                     tside[o + m] = 0;
                 }
             } else {
-                const D3 q0 = ldp(sv, ab), q1 = ldp(sv, b), q2 = ldp(sv, c), q3 = ldp(sv, ca);
+                const D3 q0 = ld3(sv, ab), q1 = ld3(sv, b), q2 = ld3(sv, c), q3 = ld3(sv, ca);
                 const bool d13 = dist2(q1, q3) < dist2(q0, q2);
                 const int t[3][3] = {{a, ab, ca}, {ab, b, d13 ? ca : c}, {d13 ? b : ab, c, ca}};
                 for (int m = 0; m < 3; m++) {
                     for (int e = 0; e < 3; e++) tri[3 * (o + m) + e] = t[m][e];
                     tsrc[o + m] = (int32_t)i;
                     tside[o + m] = m == 0 ? k[j] : k[(j + 1) % 3];
-                    zero += tri_n2(ldp(sv, t[m][0]), ldp(sv, t[m][1]), ldp(sv, t[m][2])) == 0.0;
+                    zero += tri_n2(ld3(sv, t[m][0]), ld3(sv, t[m][1]), ld3(sv, t[m][2])) == 0.0;
                 }
             }
         }
@@ -300,10 +296,6 @@ __global__ __launch_bounds__(256) void k_mt_labels(int *__restrict__ parent, siz
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i < nt) label[i] = uf_find(parent, (int)i);
 }
-__device__ __forceinline__ double box_d2(const unsigned int *__restrict__ b) {
-    const double dx = (double)ord2f(b[3]) - (double)ord2f(b[0]), dy = (double)ord2f(b[4]) - (double)ord2f(b[1]), dz = (double)ord2f(b[5]) - (double)ord2f(b[2]);
-    return (dx * dx + dy * dy) + dz * dz;
-}
 // Q[label] += q, the total, and touch[label] = the component holds a triangle of a split face.  One giant component is the contention case:
 // the threads of a block that share thread 0's label add up in LDS first, one atomic per block
 __global__ __launch_bounds__(256) void k_mt_areas(const float *__restrict__ sv, const int32_t *__restrict__ tri, size_t nt, const int32_t *__restrict__ label,
@@ -319,10 +311,10 @@ __global__ __launch_bounds__(256) void k_mt_areas(const float *__restrict__ sv, 
     }
     __syncthreads();
     if (lab >= 0) {
-        const double D2 = box_d2(box);
+        const double D2 = box_diagonal2(box);
         long long q = 0;
         if (D2 > 0.0) {
-            const double area = 0.5 * sqrt(tri_n2(ldp(sv, tri[3 * i]), ldp(sv, tri[3 * i + 1]), ldp(sv, tri[3 * i + 2])));
+            const double area = 0.5 * sqrt(tri_n2(ld3(sv, tri[3 * i]), ld3(sv, tri[3 * i + 1]), ld3(sv, tri[3 * i + 2])));
             q = __double2ll_rn((area * MT_FIX) / D2);
         }
         if (fcnt[tsrc[i]] == 3u) touch[lab] = 1; // (every writer stores the same value)
@@ -375,27 +367,7 @@ __global__ __launch_bounds__(256) void k_mt_compact_info(size_t nt, const unsign
     if (olabel) olabel[o] = label[i];
 }
 
-__global__ __launch_bounds__(256) void k_mt_vertex_box(const float *__restrict__ p, size_t nv, unsigned int *__restrict__ mm) {
-    __shared__ unsigned int s_mm[6];
-    if (threadIdx.x < 6) s_mm[threadIdx.x] = threadIdx.x < 3 ? 0xffffffffu : 0u;
-    __syncthreads();
-    for (size_t v = (size_t)blockIdx.x * 256 + threadIdx.x; v < nv; v += (size_t)gridDim.x * 256)
-        for (int a = 0; a < 3; a++) {
-            const unsigned int o = f2ord(p[3 * v + a]);
-            atomicMin(&s_mm[a], o);
-            atomicMax(&s_mm[3 + a], o);
-        }
-    __syncthreads();
-    if (threadIdx.x < 3) atomicMin(&mm[threadIdx.x], s_mm[threadIdx.x]);
-    else if (threadIdx.x < 6) atomicMax(&mm[threadIdx.x], s_mm[threadIdx.x]);
-}
-
 // ---- host -------------------------------------------------------------------------------------------------------------------------------
-static int finish(hipStream_t st) {
-    DEVCHK(hipStreamSynchronize(st));
-    DEVCHK(hipGetLastError());
-    return RSM_OK;
-}
 static dim3 red_grid(size_t n) { return dim3((unsigned)std::max<size_t>(1, std::min<size_t>(1024, (n + 255) / 256))); }
 
 // rho (optional) and value at nv > 0 vertices; *hk = 0: no valid sample or all of them equal, every value 0
@@ -427,7 +399,7 @@ static int smooth_values(DevMem &M, const int32_t *d_f, size_t nv, size_t nf, co
     *d_res = d_in;
     if (steps <= 0 || nf == 0) return RSM_OK;
     uint32_t *corner = nullptr, *row = nullptr;
-    const int s = mesh_corner_lists_device(M, d_f, nv, nf, &row, &corner, st);
+    const int s = mesh_corner_lists(M, d_f, nv, nf, &row, &corner, st);
     if (s != RSM_OK) return s;
     uint32_t *nbr = M.get<uint32_t>(6 * nf);
     double *buf[2] = {M.get<double>(nv), M.get<double>(nv)};
@@ -465,11 +437,10 @@ static int split(DevMem &M, const float *d_v, size_t nv, const int32_t *d_f, siz
         DEVCHK(hipMemcpyAsync(ctr, init, sizeof init, hipMemcpyHostToDevice, st));
         DEVCHK(hipMemcpyAsync(box, binit, sizeof binit, hipMemcpyHostToDevice, st));
         DEVCHK(hipMemsetAsync(ecut, 0xff, n * sizeof(int32_t), st));
-        hipLaunchKernelGGL(k_mt_vertex_box, red_grid(nv), dim3(256), 0, st, d_v, nv, box);
+        hipLaunchKernelGGL(k_mesh_vertex_box<>, red_grid(nv), dim3(256), 0, st, d_v, nv, box);
         hipLaunchKernelGGL(k_mt_minmax, red_grid(nv), dim3(256), 0, st, d_x, nv, ctr);
         // the input's edge table, the cut edges ranked
-        hipLaunchKernelGGL(k_mesh_edge_keys<>, blocks_for(nf), dim3(256), 0, st, d_f, nf, (u64)nv, k0, v0);
-        int s = sort_pairs(M, k0, ekey, v0, eval, n, 32 + key_bits((u64)nv), st);
+        int s = mesh_edge_table(M, d_f, nv, nf, k0, v0, ekey, eval, st);
         if (s != RSM_OK) return s;
         hipLaunchKernelGGL(k_mt_cut_flags, blocks_for(n), dim3(256), 0, st, (const u64 *)ekey, n, (u64)nv, d_x, trim, cflag, ctr);
         hipLaunchKernelGGL(k_mt_face_count, blocks_for(nf), dim3(256), 0, st, d_f, nf, d_x, trim, fcnt, ctr);
@@ -498,8 +469,7 @@ static int split(DevMem &M, const float *d_v, size_t nv, const int32_t *d_f, siz
             hipLaunchKernelGGL(k_mt_face_emit, blocks_for(nf), dim3(256), 0, st, d_f, nf, d_x, trim, (const unsigned int *)fcnt, (const unsigned int *)foff,
                                (const int32_t *)ecut, (const float *)sv, tri, tsrc, tside, ctr);
             // the split mesh's edge table, components per side, areas, the island rule
-            hipLaunchKernelGGL(k_mesh_edge_keys<>, blocks_for(nt), dim3(256), 0, st, (const int32_t *)tri, (size_t)nt, (u64)nvs, sk0, sv0);
-            if ((s = sort_pairs(M, sk0, skey, sv0, sval, m, 32 + key_bits((u64)nvs), st)) != RSM_OK) return s;
+            if ((s = mesh_edge_table(M, (const int32_t *)tri, nvs, (size_t)nt, sk0, sv0, skey, sval, st)) != RSM_OK) return s;
             hipLaunchKernelGGL(k_mesh_iota<>, blocks_for(nt), dim3(256), 0, st, parent, (size_t)nt);
             hipLaunchKernelGGL(k_mt_unite, blocks_for(m), dim3(256), 0, st, (const u64 *)skey, (const uint32_t *)sval, m, (u64)nvs, (const uint8_t *)tside, parent);
             hipLaunchKernelGGL(k_mt_labels, blocks_for(nt), dim3(256), 0, st, parent, (size_t)nt, label);
@@ -511,12 +481,7 @@ static int split(DevMem &M, const float *d_v, size_t nv, const int32_t *d_f, siz
             uint64_t kf = 0, kv = 0;
             if ((s = scan_totals(fkeep, fpos, nt, vused, vpos, nvs, st, &kf, &kv)) != RSM_OK) return s;
             if (kf > 0) {
-                if (hipMalloc((void **)&res.d_v, kv * 3 * sizeof(float)) != hipSuccess || hipMalloc((void **)&res.d_f, kf * 3 * sizeof(int32_t)) != hipSuccess) {
-                    poisson_mesh_free(&res);
-                    return RSM_E_NOMEM;
-                }
-                res.nv = (int64_t)kv;
-                res.nf = (int64_t)kf;
+                if ((s = mesh_result_alloc(res, kv, kf)) != RSM_OK) return s;
                 hipLaunchKernelGGL(k_mesh_compact_faces<>, blocks_for(nt), dim3(256), 0, st, (const int32_t *)tri, (size_t)nt, (const unsigned int *)fkeep,
                                    (const unsigned int *)fpos, (const unsigned int *)vpos, res.d_f);
                 hipLaunchKernelGGL(k_mesh_compact_verts<>, blocks_for(nvs), dim3(256), 0, st, (const float *)sv, nvs, (const unsigned int *)vused,
@@ -527,15 +492,13 @@ static int split(DevMem &M, const float *d_v, size_t nv, const int32_t *d_f, siz
             }
         }
         if (hipMemcpyAsync(h, ctr, sizeof h, hipMemcpyDeviceToHost, st) != hipSuccess || hipMemcpyAsync(hbox, box, sizeof hbox, hipMemcpyDeviceToHost, st) != hipSuccess ||
-            finish(st) != RSM_OK) {
+            mesh_finish(st) != RSM_OK) {
             poisson_mesh_free(&res);
             return RSM_E_HIP;
         }
-        const double dx = (double)ord2f(hbox[3]) - (double)ord2f(hbox[0]), dy = (double)ord2f(hbox[4]) - (double)ord2f(hbox[1]),
-                     dz = (double)ord2f(hbox[5]) - (double)ord2f(hbox[2]);
         S[15] = ord2d(h[T_VMIN]);
         S[16] = ord2d(h[T_VMAX]);
-        S[17] = (dx * dx + dy * dy) + dz * dz;
+        S[17] = box_diagonal2(hbox);
     }
     S[2] = (double)res.nv;
     S[3] = (double)res.nf;
@@ -548,8 +511,7 @@ static int split(DevMem &M, const float *d_v, size_t nv, const int32_t *d_f, siz
     S[12] = (double)h[T_MOVED_KD];
     S[13] = (double)h[T_MOVED_DK];
     S[14] = (double)h[T_QTOTAL];
-    poisson_mesh_free(out); // (the input may be *out's own buffers: they were read to the end above)
-    *out = res;
+    mesh_result_commit(out, res);
     return RSM_OK;
 }
 
@@ -561,7 +523,7 @@ int mesh_density_device(const float *d_sx, const float *d_sn4, int64_t n, int de
     int s = mesh_validate_device(d_v, nv, nullptr, 0, invalid, st);
     if (s != RSM_OK) return s;
     s = density(M, d_sx, d_sn4, n, depth, scale, kernel_depth, samples_per_node, d_v, (size_t)nv, d_rho, d_val, counts, hk, st);
-    return s != RSM_OK ? s : finish(st);
+    return s != RSM_OK ? s : mesh_finish(st);
 }
 
 int mesh_value_smooth_device(const int32_t *d_f, int64_t nv, int64_t nf, const double *d_in, int steps, double *d_out, int *invalid, hipStream_t st) {
@@ -572,7 +534,7 @@ int mesh_value_smooth_device(const int32_t *d_f, int64_t nv, int64_t nf, const d
     s = smooth_values(M, d_f, (size_t)nv, (size_t)nf, d_in, steps, &res, st);
     if (s != RSM_OK) return s;
     DEVCHK(hipMemcpyAsync(d_out, res, (size_t)nv * sizeof(double), hipMemcpyDeviceToDevice, st));
-    return finish(st);
+    return mesh_finish(st);
 }
 
 int mesh_split_device(const float *d_v, int64_t nv, const int32_t *d_f, int64_t nf, const double *d_val, double trim, double island_ratio, PoissonMesh *out,

@@ -709,12 +709,7 @@ int poisson_extract_device(const float *d_chi, int depth, double iso, const doub
     if (s == RSM_OK) s = scan_total(vused, vpos, nv, st, &kv);
     if (s == RSM_OK && kf > 0) {
         PoissonMesh kept;
-        if (hipMalloc((void **)&kept.d_v, kv * 3 * sizeof(float)) != hipSuccess || hipMalloc((void **)&kept.d_f, kf * 3 * sizeof(int32_t)) != hipSuccess) {
-            poisson_mesh_free(&kept);
-            s = RSM_E_NOMEM;
-        } else {
-            kept.nv = (int64_t)kv;
-            kept.nf = (int64_t)kf;
+        if ((s = mesh_result_alloc(kept, kv, kf)) == RSM_OK) {
             hipLaunchKernelGGL(k_mesh_compact_faces<>, blocks_for(nf), dim3(256), 0, st, (const int32_t *)faces, (size_t)nf, (const unsigned int *)fkeep,
                                (const unsigned int *)fpos, (const unsigned int *)vpos, kept.d_f);
             hipLaunchKernelGGL(k_mesh_compact_verts<>, blocks_for(nv), dim3(256), 0, st, (const float *)verts, (size_t)nv, (const unsigned int *)vused,
@@ -723,7 +718,7 @@ int poisson_extract_device(const float *d_chi, int depth, double iso, const doub
                 poisson_mesh_free(&kept);
                 s = RSM_E_HIP;
             } else
-                *out = kept;
+                mesh_result_commit(out, kept);
         }
     }
     if (hipStreamSynchronize(st) != hipSuccess && s == RSM_OK) s = RSM_E_HIP;

@@ -1,8 +1,13 @@
-// mesh_common.h -- what the surface (k_poisson.hip), its smoothing / clean-up (k_meshclean.hip) and its density trim (k_meshtrim.hip) share
-// beyond dev_prims.h: the scratch of one call, the mesh tables the colouring reads as well, the edge keys and the union-find.
+// mesh_common.h -- the mesh units' topology layer, beyond dev_prims.h: what the surface (k_poisson.hip), its smoothing / clean-up
+// (k_meshclean.hip), its density trim (k_meshtrim.hip), the closing of its holes (k_meshclose.hip), its decimation (k_meshdecimate.hip) and
+// its colours (k_meshcolor.hip, k_meshstitch.hip) share.  The scratch of one call; the sorted edge table and the corner lists of a mesh,
+// built from any allocator (dev_prims.h: DevMem here, the decimation's Pool); the union-find over the table; the vertex box and its
+// diagonal; a point in fp64; the end of a call that replaces a mesh.  What a stage does with the table's runs stays in its own unit.
+// The kernels are templates for the reason dev_prims.h gives: only a unit that launches one (k_mesh_edge_keys<>) holds a copy.
 #pragma once
 
 #include "dev_prims.h"
+#include "rsm_dev.h"
 
 #include <vector>
 
@@ -23,18 +28,26 @@ struct DevMem { // scratch of one call
     }
 };
 
-// what k_meshclean.hip builds and the colouring (k_meshcolor.hip) reads as well.  validate: RSM_OK, or RSM_E_INVALID with *invalid = 1 (a
-// face index outside [0, nv)) / 2 (a coordinate that is not finite); d_v may be NULL (indices only).  corner lists: a CSR over the vertices
-// of the corners 3 f + j that hold them, each list ascending (row: nv + 1 starts, corner: 3 nf entries, both M's); faces with a repeated
-// index are in no list.
+// (k_meshclean.hip) RSM_OK, or RSM_E_INVALID with *invalid = 1 (a face index outside [0, nv)) / 2 (a coordinate that is not finite); d_v may
+// be NULL (indices only)
 int mesh_validate_device(const float *d_v, int64_t nv, const int32_t *d_f, int64_t nf, int *invalid, hipStream_t st);
-int mesh_corner_lists_device(DevMem &M, const int32_t *d_f, size_t nv, size_t nf, uint32_t **row, uint32_t **corner, hipStream_t st);
 
-// ---- the sorted edge table's keys and the union-find over it (k_meshclean.hip, k_meshtrim.hip) ---------------------------------------------
+static inline int mesh_finish(hipStream_t st) {
+    DEVCHK(hipStreamSynchronize(st));
+    DEVCHK(hipGetLastError());
+    return RSM_OK;
+}
+
+// a vertex in fp64
+struct D3 {
+    double x, y, z;
+};
+__device__ __forceinline__ D3 ld3(const float *__restrict__ v, size_t i) { return D3{(double)v[3 * i], (double)v[3 * i + 1], (double)v[3 * i + 2]}; }
+
+// ---- the sorted edge table and the union-find over it ---------------------------------------------------------------------------------------
 __device__ __forceinline__ bool face_distinct(int a, int b, int c) { return a != b && b != c && a != c; }
 
-// entry 3 f + j: key (min << 32) | max of edge j = (v_j, v_j+1); a face with a repeated index gets the key after every edge, nv << 32.
-// (Templates for the reason dev_prims.h gives: only a unit that launches them holds a copy.)
+// entry 3 f + j: key (min << 32) | max of edge j = (v_j, v_j+1); a face with a repeated index gets the key after every edge, nv << 32
 template <int = 0>
 __global__ __launch_bounds__(256) void k_mesh_edge_keys(const int32_t *__restrict__ f, size_t nf, unsigned long long nv, unsigned long long *__restrict__ key,
                                                         uint32_t *__restrict__ val) {
@@ -53,6 +66,18 @@ template <int = 0>
 __global__ __launch_bounds__(256) void k_mesh_iota(int *__restrict__ a, size_t n) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (i < n) a[i] = (int)i;
+}
+
+// the table of nf > 0 faces: (ekey, eval) = the 3 nf keys and their entries 3 f + j, sorted by rocprim's stable radix sort over the key bits
+// in use; (k0, v0) = the unsorted ones.  A run of equal keys = the faces on one edge; the faces of a run ascend.  The four buffers (3 nf
+// each) are the caller's, allocated where it allocates its own: a stage allocates everything before it enqueues anything, and a
+// hipMalloc issued once work is on the stream costs the call time (profiles/LAB_NOTES.md, f23); only the sort's temporary comes from M here.
+template <class Alloc>
+static int mesh_edge_table(Alloc &M, const int32_t *d_f, size_t nv, size_t nf, unsigned long long *k0, uint32_t *v0, unsigned long long *ekey, uint32_t *eval,
+                           hipStream_t st) {
+    typedef unsigned long long u64;
+    hipLaunchKernelGGL(k_mesh_edge_keys<>, blocks_for(nf), dim3(256), 0, st, d_f, nf, (u64)nv, k0, v0);
+    return sort_pairs(M, k0, ekey, v0, eval, 3 * nf, 32 + key_bits((u64)nv), st);
 }
 
 __device__ __forceinline__ int uf_load(int *parent, int x) { return __hip_atomic_load(parent + x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -80,6 +105,88 @@ __device__ __forceinline__ void uf_union(int *parent, int a, int b) {
         }
         if (atomicCAS(parent + b, b, a) == b) return; // (b was still a root; otherwise somebody hooked it first: again)
     }
+}
+
+// ---- the corner lists: a CSR over the vertices of the corners 3 f + j that hold them, each list ascending -------------------------------------
+// key = the vertex of corner 3 f + j, nv for the corners of a face with a repeated index (they sort behind every list)
+template <int = 0>
+__global__ __launch_bounds__(256) void k_mesh_corner_keys(const int32_t *__restrict__ f, size_t nf, uint32_t nv, uint32_t *__restrict__ key, uint32_t *__restrict__ val) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nf) return;
+    const int v[3] = {f[3 * i], f[3 * i + 1], f[3 * i + 2]};
+    const bool ok = face_distinct(v[0], v[1], v[2]);
+    for (int j = 0; j < 3; j++) {
+        key[3 * i + j] = ok ? (uint32_t)v[j] : nv;
+        val[3 * i + j] = (uint32_t)(3 * i + j);
+    }
+}
+// row[v] = the first sorted position whose key is >= v, v = 0 .. nv
+template <int = 0>
+__global__ __launch_bounds__(256) void k_mesh_row_starts(const uint32_t *__restrict__ key, size_t n, size_t nv, uint32_t *__restrict__ row) {
+    const size_t v = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (v > nv) return;
+    size_t lo = 0, hi = n;
+    while (lo < hi) {
+        const size_t mid = (lo + hi) / 2;
+        if (key[mid] < (uint32_t)v) lo = mid + 1;
+        else hi = mid;
+    }
+    row[v] = (uint32_t)lo;
+}
+// row: nv + 1 starts, corner: 3 nf entries, both M's; faces with a repeated index are in no list.  nf = 0: every start is 0.
+template <class Alloc>
+static int mesh_corner_lists(Alloc &M, const int32_t *d_f, size_t nv, size_t nf, uint32_t **row, uint32_t **corner, hipStream_t st) {
+    const size_t n = 3 * nf;
+    uint32_t *k0 = M.template get<uint32_t>(n), *k1 = M.template get<uint32_t>(n), *v0 = M.template get<uint32_t>(n);
+    *corner = M.template get<uint32_t>(n);
+    *row = M.template get<uint32_t>(nv + 1);
+    if (!k0 || !k1 || !v0 || !*corner || !*row) return RSM_E_NOMEM;
+    if (nf > 0) {
+        hipLaunchKernelGGL(k_mesh_corner_keys<>, blocks_for(nf), dim3(256), 0, st, d_f, nf, (uint32_t)nv, k0, v0);
+        const int s = sort_pairs(M, k0, k1, v0, *corner, n, key_bits((unsigned long long)nv), st);
+        if (s != RSM_OK) return s;
+    }
+    hipLaunchKernelGGL(k_mesh_row_starts<>, blocks_for(nv + 1), dim3(256), 0, st, (const uint32_t *)k1, n, nv, *row);
+    return RSM_OK;
+}
+
+// ---- the box of the vertices: mm[0 .. 5] = min x, y, z, max x, y, z as ordered uints (dev_prims.h), preset to ~0 / 0 ---------------------------
+template <int = 0>
+__global__ __launch_bounds__(256) void k_mesh_vertex_box(const float *__restrict__ p, size_t nv, unsigned int *__restrict__ mm) {
+    __shared__ unsigned int s_mm[6];
+    if (threadIdx.x < 6) s_mm[threadIdx.x] = threadIdx.x < 3 ? 0xffffffffu : 0u;
+    __syncthreads();
+    for (size_t v = (size_t)blockIdx.x * 256 + threadIdx.x; v < nv; v += (size_t)gridDim.x * 256)
+        for (int a = 0; a < 3; a++) {
+            const unsigned int o = f2ord(p[3 * v + a]);
+            atomicMin(&s_mm[a], o);
+            atomicMax(&s_mm[3 + a], o);
+        }
+    __syncthreads();
+    if (threadIdx.x < 3) atomicMin(&mm[threadIdx.x], s_mm[threadIdx.x]);
+    else if (threadIdx.x < 6) atomicMax(&mm[threadIdx.x], s_mm[threadIdx.x]);
+}
+// the square of such a box's fp64 diagonal
+__host__ __device__ __forceinline__ double box_diagonal2(const unsigned int *b) {
+    const double dx = (double)ord2f(b[3]) - (double)ord2f(b[0]), dy = (double)ord2f(b[4]) - (double)ord2f(b[1]), dz = (double)ord2f(b[5]) - (double)ord2f(b[2]);
+    return (dx * dx + dy * dy) + dz * dz;
+}
+
+// ---- the end of a call that replaces a mesh ---------------------------------------------------------------------------------------------------
+// res = room for kv vertices and kf faces (a count of 0 gets no buffer); when either allocation fails res is freed whole
+static inline int mesh_result_alloc(PoissonMesh &res, size_t kv, size_t kf) {
+    if ((kv > 0 && hipMalloc((void **)&res.d_v, kv * 3 * sizeof(float)) != hipSuccess) || (kf > 0 && hipMalloc((void **)&res.d_f, kf * 3 * sizeof(int32_t)) != hipSuccess)) {
+        poisson_mesh_free(&res);
+        return RSM_E_NOMEM;
+    }
+    res.nv = (int64_t)kv;
+    res.nf = (int64_t)kf;
+    return RSM_OK;
+}
+// *out may own the buffers the call read: it goes only now, after the last read
+static inline void mesh_result_commit(PoissonMesh *out, const PoissonMesh &res) {
+    poisson_mesh_free(out);
+    *out = res;
 }
 
 // ---- f7's valid sample (k_poisson.hip, k_meshtrim.hip): finite point and normal, normal != 0; p = the point, nh = the unit normal, fp64 ------

@@ -105,8 +105,7 @@ struct rsm_ctx {
     PoissonMesh pmesh;                 // the last mesh of rsm_poisson_mesh / rsm_stage_iso_mesh (rsm_poisson_last_mesh copies it out)
     uint8_t *mcol_rgb = nullptr;       // rsm_mesh_color_last's colours of that mesh (rsm_mesh_last_colors copies them out) ...
     int32_t *mcol_best = nullptr;      // ... and best views
-    const float *mcol_of = nullptr;    // the vertex buffer they belong to, and its vertex count: a later mesh has no colours
-    int64_t mcol_nv = 0;
+    bool mcol_valid = false;           // they are the colours of pmesh as it is now: a later mesh has none (mesh_replaced(), rsm_mesh.hip)
     long long opt_meshcolor_big_box = 4096; // rsm_mesh_color: a (face, view) bounding box of more pixels is strided by a block, not walked by one thread
     int opt_filter_wg_max = 2048;      // rsm_filter_last_cloud: the wave passes' workgroup form while at most this many queries are left (0: never)
     int opt_filter_normals_window = 8; // rsm_filter_last_cloud: the normals' radius search on the pixel lattice while no point needs a wider window than this (0: grid)
@@ -197,6 +196,7 @@ struct Tmp { // scoped device allocations of one stage call
     rsm_ctx *c;
     std::vector<void *> ptrs;
     bool ok = true;
+    hipError_t down_err = hipSuccess; // the first later() copy that failed: finish() names it
     bool pending = false; // an up() copy may still be reading its host buffer: no wait for c->stream since
     explicit Tmp(rsm_ctx *c_) : c(c_) {}
     ~Tmp() {
@@ -225,6 +225,12 @@ struct Tmp { // scoped device allocations of one stage call
         }
         return d;
     }
+    // n elements down where there are any and the caller gave room for them; only enqueued: finish() waits and reports a failure
+    template <typename T>
+    Tmp &later(T *h, const T *d, size_t n) {
+        if (n > 0 && h && down_err == hipSuccess) down_err = hipMemcpyAsync(h, d, n * sizeof(T), hipMemcpyDeviceToHost, c->stream);
+        return *this;
+    }
     template <typename T>
     void down(T *h, const T *d, size_t n) {
         if (hipMemcpyAsync(h, d, n * sizeof(T), hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
@@ -238,6 +244,7 @@ static inline int finish(rsm_ctx *c, Tmp &t) {
     t.pending = false;
     if (e == hipSuccess) e = hipGetLastError();
     if (e != hipSuccess) return set_err(c, RSM_E_HIP, "stage failed: %s", hipGetErrorString(e));
+    if (t.down_err != hipSuccess) return set_err(c, RSM_E_HIP, "hipMemcpyAsync (device to host) failed: %s", hipGetErrorString(t.down_err));
     if (!t.ok) return set_err(c, RSM_E_HIP, "stage alloc/copy failed");
     return RSM_OK;
 }

@@ -6,6 +6,14 @@
 #include <cmath>
 #include <string.h>
 
+// ---- what the entries below share -------------------------------------------------------------------------------------------------------
+// the end of the *_fail texts: after a HIP failure ": " and the runtime's last error, else nothing
+static std::string hip_tail(int s) { return s == RSM_E_HIP ? std::string(": ") + hipGetErrorString(hipGetLastError()) : std::string(); }
+
+// The colours of rsm_mesh_color_last / rsm_mesh_stitch_last are those of the mesh they were computed on.  Whoever hands &c->pmesh to a producer
+// calls this once the producer has replaced (or freed) that mesh; nothing else decides whether the colours still hold.
+static void mesh_replaced(rsm_ctx *c) { c->mcol_valid = false; }
+
 // ---- dense-grid Poisson surface and trim (k_poisson.hip) -----------------------------------------------------------
 static int poisson_params_ok(rsm_ctx *c, const rsm_poisson_params *p) {
     if (!p) return set_err(c, RSM_E_INVALID, "poisson: params is NULL");
@@ -20,8 +28,6 @@ static int poisson_n_ok(rsm_ctx *c, int64_t n) {
     if (n < 0 || n > (int64_t)INT32_MAX) return set_err(c, RSM_E_INVALID, "poisson: n %lld outside 0..INT32_MAX", (long long)n);
     return RSM_OK;
 }
-// the end of the three *_fail texts: after a HIP failure ": " and the runtime's last error, else nothing
-static std::string hip_tail(int s) { return s == RSM_E_HIP ? std::string(": ") + hipGetErrorString(hipGetLastError()) : std::string(); }
 static int poisson_fail(rsm_ctx *c, int s, const char *what) { return set_err(c, s, "poisson: %s failed%s", what, hip_tail(s).c_str()); }
 
 // the eight steps on device buffers; the mesh lands in c->pmesh
@@ -30,6 +36,7 @@ static int poisson_run(rsm_ctx *c, const float *d_xyz, const float *d_nrm, int64
     double st[RSM_POISSON_STATS] = {0};
     *n_vertices = *n_faces = 0;
     poisson_mesh_free(&c->pmesh);
+    mesh_replaced(c);
     double grid[4];
     int64_t counts[2];
     int s = poisson_grid_device(d_xyz, d_nrm, n, p->depth, p->scale, grid, counts, c->stream);
@@ -53,6 +60,7 @@ static int poisson_run(rsm_ctx *c, const float *d_xyz, const float *d_nrm, int64
         int64_t un[2];
         if ((s = poisson_extract_device(chi, p->depth, iso, grid, occ, p->trim_cells, &c->pmesh, un, c->stream)) != RSM_OK)
             return poisson_fail(c, s, "extraction");
+        mesh_replaced(c);
         st[2] = res;
         st[3] = (double)cycles;
         st[4] = iso;
@@ -123,10 +131,8 @@ extern "C" int rsm_stage_poisson_rhs(rsm_ctx *c, const float *xyz, const float *
         return RSM_OK;
     }
     if ((s = poisson_rhs_device(dx, dn, n, p->depth, grid, nullptr, db, docc, c->stream)) != RSM_OK) return poisson_fail(c, s, "right-hand side");
-    HIPCHK(c, hipMemcpyAsync(b, db, sizeof(double) * N3, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(occ, docc, N3, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RSM_OK;
+    T.later(b, db, N3).later(occ, docc, N3);
+    return finish(c, T);
 }
 
 extern "C" int rsm_stage_poisson_solve(rsm_ctx *c, const float *b, int depth, double rel_residual, int max_cycles, float *chi, double *residual,
@@ -144,9 +150,9 @@ extern "C" int rsm_stage_poisson_solve(rsm_ctx *c, const float *b, int depth, do
     if ((s = finish(c, T)) != RSM_OK) return s;
     s = poisson_solve_device(db, depth, rel_residual, max_cycles, dchi, residual, cycles, history, c->stream);
     if (s < 0) return poisson_fail(c, s, "solve");
-    HIPCHK(c, hipMemcpyAsync(chi, dchi, sizeof(float) * N3, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return s;
+    T.later(chi, dchi, N3);
+    const int d = finish(c, T);
+    return d != RSM_OK ? d : s;
 }
 
 extern "C" int rsm_stage_iso_mesh(rsm_ctx *c, const float *chi, int depth, double iso, const double grid[4], const uint8_t *occ, int trim_cells,
@@ -166,10 +172,93 @@ extern "C" int rsm_stage_iso_mesh(rsm_ctx *c, const float *chi, int depth, doubl
     if (!dchi || (occ && !docc)) return set_err(c, RSM_E_NOMEM, "poisson: no device memory");
     if ((s = finish(c, T)) != RSM_OK) return s;
     int64_t un[2];
-    if ((s = poisson_extract_device(dchi, depth, iso, grid, docc, trim_cells, &c->pmesh, un, c->stream)) != RSM_OK) return poisson_fail(c, s, "extraction");
+    s = poisson_extract_device(dchi, depth, iso, grid, docc, trim_cells, &c->pmesh, un, c->stream);
+    mesh_replaced(c); // (also when it failed: the extraction frees the mesh before anything else)
+    if (s != RSM_OK) return poisson_fail(c, s, "extraction");
     *n_vertices = c->pmesh.nv;
     *n_faces = c->pmesh.nf;
     return RSM_OK;
+}
+
+// ---- the mesh-to-mesh stages: clean, trim, close_holes, decimate (how the back end's units are laid out) -------------------------
+static int mesh_counts_ok(rsm_ctx *c, const char *who, int64_t nv, int64_t nf) { // who: "mesh_clean" / "mesh_trim" / "mesh_color" ...
+    if (nv < 0 || nv > (int64_t)INT32_MAX) return set_err(c, RSM_E_INVALID, "%s: nv %lld outside 0..INT32_MAX", who, (long long)nv);
+    if (nf < 0 || 3 * nf >= ((int64_t)1 << 31)) return set_err(c, RSM_E_INVALID, "%s: nf %lld negative or 3 nf >= 2^31", who, (long long)nf);
+    return RSM_OK;
+}
+static int no_check() { return RSM_OK; }
+// the counts, what the stage checks next (trim's n), then the pointers
+template <class Extra>
+static int mesh_in_ok(rsm_ctx *c, const char *who, int64_t nv, int64_t nf, const float *xyz, const int32_t *faces, const int64_t *n_vertices, const int64_t *n_faces,
+                      Extra extra_ok) {
+    int s = mesh_counts_ok(c, who, nv, nf);
+    if (s != RSM_OK || (s = extra_ok()) != RSM_OK) return s;
+    if (!n_vertices || !n_faces || (nv > 0 && !xyz) || (nf > 0 && !faces)) return set_err(c, RSM_E_INVALID, "%s: a NULL pointer", who);
+    return RSM_OK;
+}
+// invalid: mesh_validate_device's 1 / 2
+static int mesh_fail(rsm_ctx *c, const char *who, int s, int invalid) {
+    if (s == RSM_E_INVALID) return set_err(c, s, invalid == 1 ? "%s: a face index outside [0, nv)" : "%s: a coordinate that is not finite", who);
+    if (s == RSM_E_NOMEM) return set_err(c, s, "%s: no device memory", who);
+    return set_err(c, s, "%s: failed%s", who, hip_tail(s).c_str());
+}
+
+// where a stage's mesh comes from: host arrays, device buffers, or the context's last mesh (no arrays then: its counts need no check)
+enum MeshFrom { MESH_HOST, MESH_DEVICE, MESH_LAST };
+struct MeshIn {
+    MeshFrom from;
+    const float *xyz = nullptr;
+    int64_t nv = 0;
+    const int32_t *faces = nullptr;
+    int64_t nf = 0;
+};
+// One stage `who`, the same from every source.  params_ok() / extra_ok(): the stage's checks in front of and behind the counts;
+// run(d_v, nv, d_f, nf, &c->pmesh, stats, &invalid): its *_device function, whose result replaces the context's last mesh (d_v / d_f may be
+// that mesh's own buffers).  A refused or failed call leaves mesh and colours as they were.  The two halves are there for the trim, which
+// uploads its samples between them.
+template <class ParamsOk, class ExtraOk>
+static int mesh_stage_check(rsm_ctx *c, const char *who, const MeshIn &in, ParamsOk params_ok, ExtraOk extra_ok, const int64_t *n_vertices, const int64_t *n_faces) {
+    if (!c) return RSM_E_INVALID;
+    const int s = params_ok();
+    if (s != RSM_OK) return s;
+    return mesh_in_ok(c, who, in.nv, in.nf, in.xyz, in.faces, n_vertices, n_faces, extra_ok);
+}
+template <class Run>
+static int mesh_stage_run(rsm_ctx *c, const char *who, const float *d_xyz, int64_t nv, const int32_t *d_faces, int64_t nf, Run run, int64_t *n_vertices, int64_t *n_faces,
+                          double *stats) {
+    int invalid = 0;
+    const int s = run(d_xyz, nv, d_faces, nf, &c->pmesh, stats, &invalid);
+    if (s != RSM_OK) return mesh_fail(c, who, s, invalid);
+    mesh_replaced(c);
+    *n_vertices = c->pmesh.nv;
+    *n_faces = c->pmesh.nf;
+    return RSM_OK;
+}
+template <class ParamsOk, class ExtraOk, class Run>
+static int mesh_stage(rsm_ctx *c, const char *who, const MeshIn &in, ParamsOk params_ok, ExtraOk extra_ok, Run run, int64_t *n_vertices, int64_t *n_faces, double *stats) {
+    int s = mesh_stage_check(c, who, in, params_ok, extra_ok, n_vertices, n_faces);
+    if (s != RSM_OK) return s;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (in.from == MESH_LAST) return mesh_stage_run(c, who, c->pmesh.d_v, c->pmesh.nv, c->pmesh.d_f, c->pmesh.nf, run, n_vertices, n_faces, stats);
+    if (in.from == MESH_DEVICE) return mesh_stage_run(c, who, in.xyz, in.nv, in.faces, in.nf, run, n_vertices, n_faces, stats);
+    Tmp T(c);
+    float *dv = T.up(in.xyz, 3 * (size_t)in.nv);
+    int32_t *df = T.up(in.faces, 3 * (size_t)in.nf);
+    if (!dv || !df) return set_err(c, RSM_E_NOMEM, "%s: no device memory for %lld vertices, %lld faces", who, (long long)in.nv, (long long)in.nf);
+    if ((s = finish(c, T)) != RSM_OK) return s;
+    return mesh_stage_run(c, who, dv, in.nv, df, in.nf, run, n_vertices, n_faces, stats);
+}
+// ... of a stage whose *_device function takes the caller's params as they are (every one but the trim)
+template <class P>
+static int mesh_stage_p(rsm_ctx *c, const char *who, const MeshIn &in, const P *p, int (*params_ok)(rsm_ctx *, const P *),
+                        int (*device)(const float *, int64_t, const int32_t *, int64_t, const P *, PoissonMesh *, double *, int *, hipStream_t), int64_t *n_vertices,
+                        int64_t *n_faces, double *stats) {
+    return mesh_stage(
+        c, who, in, [&] { return params_ok(c, p); }, no_check,
+        [&](const float *d_v, int64_t nv, const int32_t *d_f, int64_t nf, PoissonMesh *out, double *st, int *invalid) {
+            return device(d_v, nv, d_f, nf, p, out, st, invalid, c->stream);
+        },
+        n_vertices, n_faces, stats);
 }
 
 // ---- smoothing and clean-up of the surface (k_meshclean.hip) ------------------------------------------------------------
@@ -185,58 +274,16 @@ static int meshclean_params_ok(rsm_ctx *c, const rsm_mesh_clean_params *p) {
         return set_err(c, RSM_E_INVALID, "mesh_clean: flags 0x%x has an unknown bit", p->flags);
     return RSM_OK;
 }
-static int mesh_counts_ok(rsm_ctx *c, const char *who, int64_t nv, int64_t nf) { // who: "mesh_clean" / "mesh_trim" / "mesh_color"
-    if (nv < 0 || nv > (int64_t)INT32_MAX) return set_err(c, RSM_E_INVALID, "%s: nv %lld outside 0..INT32_MAX", who, (long long)nv);
-    if (nf < 0 || 3 * nf >= ((int64_t)1 << 31)) return set_err(c, RSM_E_INVALID, "%s: nf %lld negative or 3 nf >= 2^31", who, (long long)nf);
-    return RSM_OK;
-}
-static int meshclean_fail(rsm_ctx *c, int s, int invalid) {
-    if (s == RSM_E_INVALID) return set_err(c, s, invalid == 1 ? "mesh_clean: a face index outside [0, nv)" : "mesh_clean: a coordinate that is not finite");
-    return set_err(c, s, "mesh_clean: failed%s", hip_tail(s).c_str());
-}
-// d_xyz / d_faces may be c->pmesh's own buffers
-static int meshclean_run(rsm_ctx *c, const float *d_xyz, int64_t nv, const int32_t *d_faces, int64_t nf, const rsm_mesh_clean_params *p, int64_t *n_vertices,
-                         int64_t *n_faces, double *stats) {
-    int invalid = 0;
-    const int s = mesh_clean_device(d_xyz, nv, d_faces, nf, p, &c->pmesh, stats, &invalid, c->stream);
-    if (s != RSM_OK) return meshclean_fail(c, s, invalid);
-    *n_vertices = c->pmesh.nv;
-    *n_faces = c->pmesh.nf;
-    return RSM_OK;
-}
-
 extern "C" int rsm_mesh_clean_device(rsm_ctx *c, const float *d_xyz, int64_t nv, const int32_t *d_faces, int64_t nf, const rsm_mesh_clean_params *p,
                                      int64_t *n_vertices, int64_t *n_faces, double *stats) {
-    if (!c) return RSM_E_INVALID;
-    int s = meshclean_params_ok(c, p);
-    if (s != RSM_OK || (s = mesh_counts_ok(c, "mesh_clean", nv, nf)) != RSM_OK) return s;
-    if (!n_vertices || !n_faces || (nv > 0 && !d_xyz) || (nf > 0 && !d_faces)) return set_err(c, RSM_E_INVALID, "mesh_clean: a NULL pointer");
-    HIPCHK(c, hipSetDevice(c->device));
-    return meshclean_run(c, d_xyz, nv, d_faces, nf, p, n_vertices, n_faces, stats);
+    return mesh_stage_p(c, "mesh_clean", MeshIn{MESH_DEVICE, d_xyz, nv, d_faces, nf}, p, meshclean_params_ok, mesh_clean_device, n_vertices, n_faces, stats);
 }
-
 extern "C" int rsm_mesh_clean(rsm_ctx *c, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, const rsm_mesh_clean_params *p, int64_t *n_vertices,
                               int64_t *n_faces, double *stats) {
-    if (!c) return RSM_E_INVALID;
-    int s = meshclean_params_ok(c, p);
-    if (s != RSM_OK || (s = mesh_counts_ok(c, "mesh_clean", nv, nf)) != RSM_OK) return s;
-    if (!n_vertices || !n_faces || (nv > 0 && !xyz) || (nf > 0 && !faces)) return set_err(c, RSM_E_INVALID, "mesh_clean: a NULL pointer");
-    HIPCHK(c, hipSetDevice(c->device));
-    Tmp T(c);
-    float *dv = T.up(xyz, 3 * (size_t)nv);
-    int32_t *df = T.up(faces, 3 * (size_t)nf);
-    if (!dv || !df) return set_err(c, RSM_E_NOMEM, "mesh_clean: no device memory for %lld vertices, %lld faces", (long long)nv, (long long)nf);
-    if ((s = finish(c, T)) != RSM_OK) return s;
-    return meshclean_run(c, dv, nv, df, nf, p, n_vertices, n_faces, stats);
+    return mesh_stage_p(c, "mesh_clean", MeshIn{MESH_HOST, xyz, nv, faces, nf}, p, meshclean_params_ok, mesh_clean_device, n_vertices, n_faces, stats);
 }
-
 extern "C" int rsm_mesh_clean_last(rsm_ctx *c, const rsm_mesh_clean_params *p, int64_t *n_vertices, int64_t *n_faces, double *stats) {
-    if (!c) return RSM_E_INVALID;
-    const int s = meshclean_params_ok(c, p);
-    if (s != RSM_OK) return s;
-    if (!n_vertices || !n_faces) return set_err(c, RSM_E_INVALID, "mesh_clean: a NULL pointer");
-    HIPCHK(c, hipSetDevice(c->device));
-    return meshclean_run(c, c->pmesh.d_v, c->pmesh.nv, c->pmesh.d_f, c->pmesh.nf, p, n_vertices, n_faces, stats);
+    return mesh_stage_p(c, "mesh_clean", MeshIn{MESH_LAST}, p, meshclean_params_ok, mesh_clean_device, n_vertices, n_faces, stats);
 }
 
 extern "C" int rsm_stage_mesh_smooth(rsm_ctx *c, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, int steps, int cotangent, int boundary,
@@ -254,9 +301,9 @@ extern "C" int rsm_stage_mesh_smooth(rsm_ctx *c, const float *xyz, int64_t nv, c
     if ((s = finish(c, T)) != RSM_OK) return s;
     int invalid = 0;
     int64_t nb = 0;
-    if ((s = mesh_smooth_device(dv, nv, df, nf, steps, cotangent, boundary, dout, &nb, &invalid, c->stream)) != RSM_OK) return meshclean_fail(c, s, invalid);
-    if (nv > 0) HIPCHK(c, hipMemcpyAsync(out_xyz, dout, sizeof(float) * 3 * (size_t)nv, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if ((s = mesh_smooth_device(dv, nv, df, nf, steps, cotangent, boundary, dout, &nb, &invalid, c->stream)) != RSM_OK) return mesh_fail(c, "mesh_clean", s, invalid);
+    T.later(out_xyz, dout, 3 * (size_t)nv);
+    if ((s = finish(c, T)) != RSM_OK) return s;
     if (n_border) *n_border = nb;
     return RSM_OK;
 }
@@ -272,10 +319,9 @@ extern "C" int rsm_stage_mesh_components(rsm_ctx *c, const int32_t *faces, int64
     if (!df || !dl) return set_err(c, RSM_E_NOMEM, "mesh_clean: no device memory");
     if ((s = finish(c, T)) != RSM_OK) return s;
     int invalid = 0;
-    if ((s = mesh_components_device(df, nv, nf, dl, n_components, &invalid, c->stream)) != RSM_OK) return meshclean_fail(c, s, invalid);
-    if (nf > 0) HIPCHK(c, hipMemcpyAsync(labels, dl, sizeof(int32_t) * (size_t)nf, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RSM_OK;
+    if ((s = mesh_components_device(df, nv, nf, dl, n_components, &invalid, c->stream)) != RSM_OK) return mesh_fail(c, "mesh_clean", s, invalid);
+    T.later(labels, dl, (size_t)nf);
+    return finish(c, T);
 }
 
 // ---- the density trim of the surface (k_meshtrim.hip) -------------------------------------------------------------------
@@ -296,44 +342,42 @@ static int meshtrim_n_ok(rsm_ctx *c, int64_t n) {
     if (n < 0 || n > (int64_t)INT32_MAX) return set_err(c, RSM_E_INVALID, "mesh_trim: n %lld outside 0..INT32_MAX", (long long)n);
     return RSM_OK;
 }
-static int meshtrim_fail(rsm_ctx *c, int s, int invalid) {
-    if (s == RSM_E_INVALID) return set_err(c, s, invalid == 1 ? "mesh_trim: a face index outside [0, nv)" : "mesh_trim: a coordinate that is not finite");
-    if (s == RSM_E_NOMEM) return set_err(c, s, "mesh_trim: no device memory");
-    return set_err(c, s, "mesh_trim: failed%s", hip_tail(s).c_str());
-}
 static int meshtrim_values_ok(rsm_ctx *c, const double *values, int64_t nv) {
     for (int64_t i = 0; i < nv; i++)
         if (!std::isfinite(values[i])) return set_err(c, RSM_E_INVALID, "mesh_trim: values[%lld] is not finite", (long long)i);
     return RSM_OK;
 }
-// d_xyz / d_faces may be c->pmesh's own buffers
-static int meshtrim_run(rsm_ctx *c, const float *d_xyz, int64_t nv, const int32_t *d_faces, int64_t nf, const float *d_sx, const float *d_sn, int64_t n,
-                        const rsm_mesh_trim_params *p, int64_t *n_vertices, int64_t *n_faces, double *stats) {
-    int invalid = 0;
-    const int s = mesh_trim_device(d_xyz, nv, d_faces, nf, d_sx, d_sn, n, p, &c->pmesh, stats, &invalid, c->stream);
-    if (s != RSM_OK) return meshtrim_fail(c, s, invalid);
-    c->mcol_of = nullptr; // (the colours belonged to the mesh this one replaces)
-    *n_vertices = c->pmesh.nv;
-    *n_faces = c->pmesh.nf;
+// the samples a trim is given: checked between the counts and the pointers; the entries with host samples upload them themselves
+struct TrimSamples {
+    const float *xyz, *normals4;
+    int64_t n;
+};
+static int meshtrim_samples_ok(rsm_ctx *c, const TrimSamples &S) {
+    const int s = meshtrim_n_ok(c, S.n);
+    if (s != RSM_OK) return s;
+    if (S.n > 0 && !S.xyz) return set_err(c, RSM_E_INVALID, "mesh_trim: a NULL pointer");
     return RSM_OK;
+}
+static auto meshtrim_run(rsm_ctx *c, const TrimSamples &D, const rsm_mesh_trim_params *p) { // D: on the device
+    return [=](const float *d_v, int64_t nv, const int32_t *d_f, int64_t nf, PoissonMesh *out, double *st, int *invalid) {
+        return mesh_trim_device(d_v, nv, d_f, nf, D.xyz, D.normals4, D.n, p, out, st, invalid, c->stream);
+    };
 }
 
 extern "C" int rsm_mesh_trim_device(rsm_ctx *c, const float *d_xyz, int64_t nv, const int32_t *d_faces, int64_t nf, const float *d_samples_xyz,
                                     const float *d_samples_normals4, int64_t n, const rsm_mesh_trim_params *p, int64_t *n_vertices, int64_t *n_faces, double *stats) {
-    if (!c) return RSM_E_INVALID;
-    int s = meshtrim_params_ok(c, p);
-    if (s != RSM_OK || (s = mesh_counts_ok(c, "mesh_trim", nv, nf)) != RSM_OK || (s = meshtrim_n_ok(c, n)) != RSM_OK) return s;
-    if (!n_vertices || !n_faces || (nv > 0 && !d_xyz) || (nf > 0 && !d_faces) || (n > 0 && !d_samples_xyz)) return set_err(c, RSM_E_INVALID, "mesh_trim: a NULL pointer");
-    HIPCHK(c, hipSetDevice(c->device));
-    return meshtrim_run(c, d_xyz, nv, d_faces, nf, d_samples_xyz, d_samples_normals4, n, p, n_vertices, n_faces, stats);
+    const TrimSamples D{d_samples_xyz, d_samples_normals4, n};
+    return mesh_stage(
+        c, "mesh_trim", MeshIn{MESH_DEVICE, d_xyz, nv, d_faces, nf}, [&] { return meshtrim_params_ok(c, p); }, [&] { return meshtrim_samples_ok(c, D); },
+        meshtrim_run(c, D, p), n_vertices, n_faces, stats);
 }
 
 extern "C" int rsm_mesh_trim(rsm_ctx *c, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, const float *samples_xyz, const float *samples_normals4,
                              int64_t n, const rsm_mesh_trim_params *p, int64_t *n_vertices, int64_t *n_faces, double *stats) {
-    if (!c) return RSM_E_INVALID;
-    int s = meshtrim_params_ok(c, p);
-    if (s != RSM_OK || (s = mesh_counts_ok(c, "mesh_trim", nv, nf)) != RSM_OK || (s = meshtrim_n_ok(c, n)) != RSM_OK) return s;
-    if (!n_vertices || !n_faces || (nv > 0 && !xyz) || (nf > 0 && !faces) || (n > 0 && !samples_xyz)) return set_err(c, RSM_E_INVALID, "mesh_trim: a NULL pointer");
+    const TrimSamples S{samples_xyz, samples_normals4, n};
+    int s = mesh_stage_check(
+        c, "mesh_trim", MeshIn{MESH_HOST, xyz, nv, faces, nf}, [&] { return meshtrim_params_ok(c, p); }, [&] { return meshtrim_samples_ok(c, S); }, n_vertices, n_faces);
+    if (s != RSM_OK) return s;
     HIPCHK(c, hipSetDevice(c->device));
     Tmp T(c);
     float *dv = T.up(xyz, 3 * (size_t)nv), *dx = T.up(samples_xyz, 3 * (size_t)n), *dn = samples_normals4 ? T.up(samples_normals4, 4 * (size_t)n) : nullptr;
@@ -341,21 +385,20 @@ extern "C" int rsm_mesh_trim(rsm_ctx *c, const float *xyz, int64_t nv, const int
     if (!dv || !dx || !df || (samples_normals4 && !dn))
         return set_err(c, RSM_E_NOMEM, "mesh_trim: no device memory for %lld vertices, %lld faces, %lld samples", (long long)nv, (long long)nf, (long long)n);
     if ((s = finish(c, T)) != RSM_OK) return s;
-    return meshtrim_run(c, dv, nv, df, nf, dx, dn, n, p, n_vertices, n_faces, stats);
+    return mesh_stage_run(c, "mesh_trim", dv, nv, df, nf, meshtrim_run(c, TrimSamples{dx, dn, n}, p), n_vertices, n_faces, stats);
 }
 
 extern "C" int rsm_mesh_trim_last(rsm_ctx *c, const float *samples_xyz, const float *samples_normals4, int64_t n, const rsm_mesh_trim_params *p, int64_t *n_vertices,
                                   int64_t *n_faces, double *stats) {
-    if (!c) return RSM_E_INVALID;
-    int s = meshtrim_params_ok(c, p);
-    if (s != RSM_OK || (s = meshtrim_n_ok(c, n)) != RSM_OK) return s;
-    if (!n_vertices || !n_faces || (n > 0 && !samples_xyz)) return set_err(c, RSM_E_INVALID, "mesh_trim: a NULL pointer");
+    const TrimSamples S{samples_xyz, samples_normals4, n};
+    int s = mesh_stage_check(c, "mesh_trim", MeshIn{MESH_LAST}, [&] { return meshtrim_params_ok(c, p); }, [&] { return meshtrim_samples_ok(c, S); }, n_vertices, n_faces);
+    if (s != RSM_OK) return s;
     HIPCHK(c, hipSetDevice(c->device));
     Tmp T(c);
     float *dx = T.up(samples_xyz, 3 * (size_t)n), *dn = samples_normals4 ? T.up(samples_normals4, 4 * (size_t)n) : nullptr;
     if (!dx || (samples_normals4 && !dn)) return set_err(c, RSM_E_NOMEM, "mesh_trim: no device memory for %lld samples", (long long)n);
     if ((s = finish(c, T)) != RSM_OK) return s;
-    return meshtrim_run(c, c->pmesh.d_v, c->pmesh.nv, c->pmesh.d_f, c->pmesh.nf, dx, dn, n, p, n_vertices, n_faces, stats);
+    return mesh_stage_run(c, "mesh_trim", c->pmesh.d_v, c->pmesh.nv, c->pmesh.d_f, c->pmesh.nf, meshtrim_run(c, TrimSamples{dx, dn, n}, p), n_vertices, n_faces, stats);
 }
 
 extern "C" int rsm_stage_mesh_density(rsm_ctx *c, const float *samples_xyz, const float *samples_normals4, int64_t n, const rsm_mesh_trim_params *p, const float *xyz,
@@ -374,11 +417,9 @@ extern "C" int rsm_stage_mesh_density(rsm_ctx *c, const float *samples_xyz, cons
     double hk = 0.0;
     const int kd = p->kernel_depth ? p->kernel_depth : p->depth - 2;
     if ((s = mesh_density_device(dx, dn, n, p->depth, p->scale, kd, p->samples_per_node, dv, nv, dr, da, counts, &hk, &invalid, c->stream)) != RSM_OK)
-        return meshtrim_fail(c, s, invalid);
-    if (nv > 0) HIPCHK(c, hipMemcpyAsync(rho, dr, sizeof(double) * (size_t)nv, hipMemcpyDeviceToHost, c->stream));
-    if (nv > 0) HIPCHK(c, hipMemcpyAsync(value, da, sizeof(double) * (size_t)nv, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RSM_OK;
+        return mesh_fail(c, "mesh_trim", s, invalid);
+    T.later(rho, dr, (size_t)nv).later(value, da, (size_t)nv);
+    return finish(c, T);
 }
 
 extern "C" int rsm_stage_mesh_value_smooth(rsm_ctx *c, const int32_t *faces, int64_t nv, int64_t nf, const double *values, int steps, double *out_values) {
@@ -395,10 +436,9 @@ extern "C" int rsm_stage_mesh_value_smooth(rsm_ctx *c, const int32_t *faces, int
     if (!df || !din || !dout) return set_err(c, RSM_E_NOMEM, "mesh_trim: no device memory");
     if ((s = finish(c, T)) != RSM_OK) return s;
     int invalid = 0;
-    if ((s = mesh_value_smooth_device(df, nv, nf, din, steps, dout, &invalid, c->stream)) != RSM_OK) return meshtrim_fail(c, s, invalid);
-    if (nv > 0) HIPCHK(c, hipMemcpyAsync(out_values, dout, sizeof(double) * (size_t)nv, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RSM_OK;
+    if ((s = mesh_value_smooth_device(df, nv, nf, din, steps, dout, &invalid, c->stream)) != RSM_OK) return mesh_fail(c, "mesh_trim", s, invalid);
+    T.later(out_values, dout, (size_t)nv);
+    return finish(c, T);
 }
 
 extern "C" int rsm_stage_mesh_split(rsm_ctx *c, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, const double *values, double trim, double island_ratio,
@@ -418,16 +458,13 @@ extern "C" int rsm_stage_mesh_split(rsm_ctx *c, const float *xyz, int64_t nv, co
     if ((s = finish(c, T)) != RSM_OK) return s;
     int invalid = 0;
     if ((s = mesh_split_device(dv, nv, df, nf, dx, trim, island_ratio, &c->pmesh, dsrc, dside, dlab, stats, &invalid, c->stream)) != RSM_OK)
-        return meshtrim_fail(c, s, invalid);
-    c->mcol_of = nullptr;
+        return mesh_fail(c, "mesh_trim", s, invalid);
+    mesh_replaced(c);
     *n_vertices = c->pmesh.nv;
     *n_faces = c->pmesh.nf;
     const size_t m = (size_t)c->pmesh.nf;
-    if (m > 0 && src_face) HIPCHK(c, hipMemcpyAsync(src_face, dsrc, sizeof(int32_t) * m, hipMemcpyDeviceToHost, c->stream));
-    if (m > 0 && side) HIPCHK(c, hipMemcpyAsync(side, dside, sizeof(int32_t) * m, hipMemcpyDeviceToHost, c->stream));
-    if (m > 0 && label) HIPCHK(c, hipMemcpyAsync(label, dlab, sizeof(int32_t) * m, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RSM_OK;
+    T.later(src_face, dsrc, m).later(side, dside, m).later(label, dlab, m);
+    return finish(c, T);
 }
 
 // ---- the closing of the surface's small holes (k_meshclose.hip) ---------------------------------------------------------
@@ -437,55 +474,16 @@ static int meshclose_params_ok(rsm_ctx *c, const rsm_mesh_close_params *p) {
         return set_err(c, RSM_E_INVALID, "mesh_close_holes: max_hole_size %d outside 3..%d", p->max_hole_size, RSM_MESH_CLOSE_MAX_HOLE);
     return RSM_OK;
 }
-static int meshclose_fail(rsm_ctx *c, int s, int invalid) {
-    if (s == RSM_E_INVALID) return set_err(c, s, invalid == 1 ? "mesh_close_holes: a face index outside [0, nv)" : "mesh_close_holes: a coordinate that is not finite");
-    if (s == RSM_E_NOMEM) return set_err(c, s, "mesh_close_holes: no device memory");
-    return set_err(c, s, "mesh_close_holes: failed%s", hip_tail(s).c_str());
-}
-// d_xyz / d_faces may be c->pmesh's own buffers
-static int meshclose_run(rsm_ctx *c, const float *d_xyz, int64_t nv, const int32_t *d_faces, int64_t nf, const rsm_mesh_close_params *p, int64_t *n_vertices,
-                         int64_t *n_faces, double *stats) {
-    int invalid = 0;
-    const int s = mesh_close_holes_device(d_xyz, nv, d_faces, nf, p, &c->pmesh, stats, &invalid, c->stream);
-    if (s != RSM_OK) return meshclose_fail(c, s, invalid);
-    c->mcol_of = nullptr; // (the colours belonged to the mesh this one replaces)
-    *n_vertices = c->pmesh.nv;
-    *n_faces = c->pmesh.nf;
-    return RSM_OK;
-}
-
 extern "C" int rsm_mesh_close_holes_device(rsm_ctx *c, const float *d_xyz, int64_t nv, const int32_t *d_faces, int64_t nf, const rsm_mesh_close_params *p,
                                            int64_t *n_vertices, int64_t *n_faces, double *stats) {
-    if (!c) return RSM_E_INVALID;
-    int s = meshclose_params_ok(c, p);
-    if (s != RSM_OK || (s = mesh_counts_ok(c, "mesh_close_holes", nv, nf)) != RSM_OK) return s;
-    if (!n_vertices || !n_faces || (nv > 0 && !d_xyz) || (nf > 0 && !d_faces)) return set_err(c, RSM_E_INVALID, "mesh_close_holes: a NULL pointer");
-    HIPCHK(c, hipSetDevice(c->device));
-    return meshclose_run(c, d_xyz, nv, d_faces, nf, p, n_vertices, n_faces, stats);
+    return mesh_stage_p(c, "mesh_close_holes", MeshIn{MESH_DEVICE, d_xyz, nv, d_faces, nf}, p, meshclose_params_ok, mesh_close_holes_device, n_vertices, n_faces, stats);
 }
-
 extern "C" int rsm_mesh_close_holes(rsm_ctx *c, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, const rsm_mesh_close_params *p, int64_t *n_vertices,
                                     int64_t *n_faces, double *stats) {
-    if (!c) return RSM_E_INVALID;
-    int s = meshclose_params_ok(c, p);
-    if (s != RSM_OK || (s = mesh_counts_ok(c, "mesh_close_holes", nv, nf)) != RSM_OK) return s;
-    if (!n_vertices || !n_faces || (nv > 0 && !xyz) || (nf > 0 && !faces)) return set_err(c, RSM_E_INVALID, "mesh_close_holes: a NULL pointer");
-    HIPCHK(c, hipSetDevice(c->device));
-    Tmp T(c);
-    float *dv = T.up(xyz, 3 * (size_t)nv);
-    int32_t *df = T.up(faces, 3 * (size_t)nf);
-    if (!dv || !df) return set_err(c, RSM_E_NOMEM, "mesh_close_holes: no device memory for %lld vertices, %lld faces", (long long)nv, (long long)nf);
-    if ((s = finish(c, T)) != RSM_OK) return s;
-    return meshclose_run(c, dv, nv, df, nf, p, n_vertices, n_faces, stats);
+    return mesh_stage_p(c, "mesh_close_holes", MeshIn{MESH_HOST, xyz, nv, faces, nf}, p, meshclose_params_ok, mesh_close_holes_device, n_vertices, n_faces, stats);
 }
-
 extern "C" int rsm_mesh_close_holes_last(rsm_ctx *c, const rsm_mesh_close_params *p, int64_t *n_vertices, int64_t *n_faces, double *stats) {
-    if (!c) return RSM_E_INVALID;
-    const int s = meshclose_params_ok(c, p);
-    if (s != RSM_OK) return s;
-    if (!n_vertices || !n_faces) return set_err(c, RSM_E_INVALID, "mesh_close_holes: a NULL pointer");
-    HIPCHK(c, hipSetDevice(c->device));
-    return meshclose_run(c, c->pmesh.d_v, c->pmesh.nv, c->pmesh.d_f, c->pmesh.nf, p, n_vertices, n_faces, stats);
+    return mesh_stage_p(c, "mesh_close_holes", MeshIn{MESH_LAST}, p, meshclose_params_ok, mesh_close_holes_device, n_vertices, n_faces, stats);
 }
 
 extern "C" int rsm_stage_mesh_border_loops(rsm_ctx *c, const int32_t *faces, int64_t nv, int64_t nf, int32_t *labels, int32_t *sizes, int64_t *n_components) {
@@ -499,11 +497,9 @@ extern "C" int rsm_stage_mesh_border_loops(rsm_ctx *c, const int32_t *faces, int
     if (!df || !dl || !ds) return set_err(c, RSM_E_NOMEM, "mesh_close_holes: no device memory");
     if ((s = finish(c, T)) != RSM_OK) return s;
     int invalid = 0;
-    if ((s = mesh_border_loops_device(df, nv, nf, dl, ds, n_components, &invalid, c->stream)) != RSM_OK) return meshclose_fail(c, s, invalid);
-    if (nf > 0) HIPCHK(c, hipMemcpyAsync(labels, dl, sizeof(int32_t) * 3 * (size_t)nf, hipMemcpyDeviceToHost, c->stream));
-    if (nf > 0) HIPCHK(c, hipMemcpyAsync(sizes, ds, sizeof(int32_t) * 3 * (size_t)nf, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RSM_OK;
+    if ((s = mesh_border_loops_device(df, nv, nf, dl, ds, n_components, &invalid, c->stream)) != RSM_OK) return mesh_fail(c, "mesh_close_holes", s, invalid);
+    T.later(labels, dl, 3 * (size_t)nf).later(sizes, ds, 3 * (size_t)nf);
+    return finish(c, T);
 }
 
 extern "C" int rsm_stage_hole_triangulate(rsm_ctx *c, const float *ring_xyz, int L, const uint8_t *forbidden, double *weight, int32_t *triangles, int *n_triangles) {
@@ -520,10 +516,9 @@ extern "C" int rsm_stage_hole_triangulate(rsm_ctx *c, const float *ring_xyz, int
     if (!dr || !dt || (forbidden && !dm)) return set_err(c, RSM_E_NOMEM, "mesh_close_holes: no device memory");
     int s = finish(c, T);
     if (s != RSM_OK) return s;
-    if ((s = hole_triangulate_device(dr, L, dm, weight, dt, n_triangles, c->stream)) != RSM_OK) return meshclose_fail(c, s, 0);
-    if (*n_triangles > 0) HIPCHK(c, hipMemcpyAsync(triangles, dt, sizeof(int32_t) * 3 * (size_t)*n_triangles, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RSM_OK;
+    if ((s = hole_triangulate_device(dr, L, dm, weight, dt, n_triangles, c->stream)) != RSM_OK) return mesh_fail(c, "mesh_close_holes", s, 0);
+    T.later(triangles, dt, 3 * (size_t)*n_triangles);
+    return finish(c, T);
 }
 
 // ---- the decimation of the final mesh (k_meshdecimate.hip) ----------------------------------------------------------------
@@ -542,55 +537,16 @@ static int meshdecimate_params_ok(rsm_ctx *c, const rsm_mesh_decimate_params *p)
         if (flag[i] != 0 && flag[i] != 1) return set_err(c, RSM_E_INVALID, "mesh_decimate: %s %d not 0 or 1", name[i], flag[i]);
     return RSM_OK;
 }
-static int meshdecimate_fail(rsm_ctx *c, int s, int invalid) {
-    if (s == RSM_E_INVALID) return set_err(c, s, invalid == 1 ? "mesh_decimate: a face index outside [0, nv)" : "mesh_decimate: a coordinate that is not finite");
-    if (s == RSM_E_NOMEM) return set_err(c, s, "mesh_decimate: no device memory");
-    return set_err(c, s, "mesh_decimate: failed%s", hip_tail(s).c_str());
-}
-// d_xyz / d_faces may be c->pmesh's own buffers
-static int meshdecimate_run(rsm_ctx *c, const float *d_xyz, int64_t nv, const int32_t *d_faces, int64_t nf, const rsm_mesh_decimate_params *p, int64_t *n_vertices,
-                            int64_t *n_faces, double *stats) {
-    int invalid = 0;
-    const int s = mesh_decimate_device(d_xyz, nv, d_faces, nf, p, &c->pmesh, stats, &invalid, c->stream);
-    if (s != RSM_OK) return meshdecimate_fail(c, s, invalid);
-    c->mcol_of = nullptr; // (the colours belonged to the mesh this one replaces)
-    *n_vertices = c->pmesh.nv;
-    *n_faces = c->pmesh.nf;
-    return RSM_OK;
-}
-
 extern "C" int rsm_mesh_decimate_device(rsm_ctx *c, const float *d_xyz, int64_t nv, const int32_t *d_faces, int64_t nf, const rsm_mesh_decimate_params *p,
                                         int64_t *n_vertices, int64_t *n_faces, double *stats) {
-    if (!c) return RSM_E_INVALID;
-    int s = meshdecimate_params_ok(c, p);
-    if (s != RSM_OK || (s = mesh_counts_ok(c, "mesh_decimate", nv, nf)) != RSM_OK) return s;
-    if (!n_vertices || !n_faces || (nv > 0 && !d_xyz) || (nf > 0 && !d_faces)) return set_err(c, RSM_E_INVALID, "mesh_decimate: a NULL pointer");
-    HIPCHK(c, hipSetDevice(c->device));
-    return meshdecimate_run(c, d_xyz, nv, d_faces, nf, p, n_vertices, n_faces, stats);
+    return mesh_stage_p(c, "mesh_decimate", MeshIn{MESH_DEVICE, d_xyz, nv, d_faces, nf}, p, meshdecimate_params_ok, mesh_decimate_device, n_vertices, n_faces, stats);
 }
-
 extern "C" int rsm_mesh_decimate(rsm_ctx *c, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, const rsm_mesh_decimate_params *p, int64_t *n_vertices,
                                  int64_t *n_faces, double *stats) {
-    if (!c) return RSM_E_INVALID;
-    int s = meshdecimate_params_ok(c, p);
-    if (s != RSM_OK || (s = mesh_counts_ok(c, "mesh_decimate", nv, nf)) != RSM_OK) return s;
-    if (!n_vertices || !n_faces || (nv > 0 && !xyz) || (nf > 0 && !faces)) return set_err(c, RSM_E_INVALID, "mesh_decimate: a NULL pointer");
-    HIPCHK(c, hipSetDevice(c->device));
-    Tmp T(c);
-    float *dv = T.up(xyz, 3 * (size_t)nv);
-    int32_t *df = T.up(faces, 3 * (size_t)nf);
-    if (!dv || !df) return set_err(c, RSM_E_NOMEM, "mesh_decimate: no device memory for %lld vertices, %lld faces", (long long)nv, (long long)nf);
-    if ((s = finish(c, T)) != RSM_OK) return s;
-    return meshdecimate_run(c, dv, nv, df, nf, p, n_vertices, n_faces, stats);
+    return mesh_stage_p(c, "mesh_decimate", MeshIn{MESH_HOST, xyz, nv, faces, nf}, p, meshdecimate_params_ok, mesh_decimate_device, n_vertices, n_faces, stats);
 }
-
 extern "C" int rsm_mesh_decimate_last(rsm_ctx *c, const rsm_mesh_decimate_params *p, int64_t *n_vertices, int64_t *n_faces, double *stats) {
-    if (!c) return RSM_E_INVALID;
-    const int s = meshdecimate_params_ok(c, p);
-    if (s != RSM_OK) return s;
-    if (!n_vertices || !n_faces) return set_err(c, RSM_E_INVALID, "mesh_decimate: a NULL pointer");
-    HIPCHK(c, hipSetDevice(c->device));
-    return meshdecimate_run(c, c->pmesh.d_v, c->pmesh.nv, c->pmesh.d_f, c->pmesh.nf, p, n_vertices, n_faces, stats);
+    return mesh_stage_p(c, "mesh_decimate", MeshIn{MESH_LAST}, p, meshdecimate_params_ok, mesh_decimate_device, n_vertices, n_faces, stats);
 }
 
 extern "C" int rsm_stage_mesh_quadrics(rsm_ctx *c, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, double boundary_weight, double *out_q) {
@@ -608,10 +564,9 @@ extern "C" int rsm_stage_mesh_quadrics(rsm_ctx *c, const float *xyz, int64_t nv,
     if (!dv || !df || !dq) return set_err(c, RSM_E_NOMEM, "mesh_decimate: no device memory");
     if ((s = finish(c, T)) != RSM_OK) return s;
     int invalid = 0;
-    if ((s = mesh_quadrics_device(dv, nv, df, nf, boundary_weight, dq, &invalid, c->stream)) != RSM_OK) return meshdecimate_fail(c, s, invalid);
-    if (nv > 0) HIPCHK(c, hipMemcpyAsync(out_q, dq, sizeof(double) * 10 * (size_t)nv, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RSM_OK;
+    if ((s = mesh_quadrics_device(dv, nv, df, nf, boundary_weight, dq, &invalid, c->stream)) != RSM_OK) return mesh_fail(c, "mesh_decimate", s, invalid);
+    T.later(out_q, dq, 10 * (size_t)nv);
+    return finish(c, T);
 }
 
 extern "C" int rsm_stage_mesh_collapse_costs(rsm_ctx *c, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, const double *quadrics,
@@ -635,17 +590,10 @@ extern "C" int rsm_stage_mesh_collapse_costs(rsm_ctx *c, const float *xyz, int64
     if (!dv || !df || !dq || !dk || !dm || !dr || !dc || !dp) return set_err(c, RSM_E_NOMEM, "mesh_decimate: no device memory");
     if ((s = finish(c, T)) != RSM_OK) return s;
     int invalid = 0;
-    if ((s = mesh_collapse_costs_device(dv, nv, df, nf, dq, p, dk, dm, dc, dr, dp, n_edges, &invalid, c->stream)) != RSM_OK) return meshdecimate_fail(c, s, invalid);
+    if ((s = mesh_collapse_costs_device(dv, nv, df, nf, dq, p, dk, dm, dc, dr, dp, n_edges, &invalid, c->stream)) != RSM_OK) return mesh_fail(c, "mesh_decimate", s, invalid);
     const size_t ne = (size_t)*n_edges;
-    if (ne > 0) {
-        HIPCHK(c, hipMemcpyAsync(keys, dk, sizeof(uint64_t) * ne, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(multiplicity, dm, sizeof(int32_t) * ne, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(cost, dc, sizeof(double) * ne, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(reject, dr, sizeof(int32_t) * ne, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(position, dp, sizeof(float) * 3 * ne, hipMemcpyDeviceToHost, c->stream));
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RSM_OK;
+    T.later(keys, dk, ne).later(multiplicity, dm, ne).later(cost, dc, ne).later(reject, dr, ne).later(position, dp, 3 * ne);
+    return finish(c, T);
 }
 
 extern "C" int rsm_stage_mesh_collapse_round(rsm_ctx *c, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, const double *quadrics,
@@ -668,13 +616,10 @@ extern "C" int rsm_stage_mesh_collapse_round(rsm_ctx *c, const float *xyz, int64
     if ((s = finish(c, T)) != RSM_OK) return s;
     int invalid = 0;
     if ((s = mesh_collapse_round_device(dv, nv, df, nf, dq, p, need, dfo, n_faces_out, ds, n_selected, n_kept, &invalid, c->stream)) != RSM_OK)
-        return meshdecimate_fail(c, s, invalid);
-    if (nv > 0) HIPCHK(c, hipMemcpyAsync(out_xyz, dv, sizeof(float) * 3 * (size_t)nv, hipMemcpyDeviceToHost, c->stream));
-    if (nv > 0) HIPCHK(c, hipMemcpyAsync(out_quadrics, dq, sizeof(double) * 10 * (size_t)nv, hipMemcpyDeviceToHost, c->stream));
-    if (*n_faces_out > 0) HIPCHK(c, hipMemcpyAsync(out_faces, dfo, sizeof(int32_t) * 3 * (size_t)*n_faces_out, hipMemcpyDeviceToHost, c->stream));
-    if (*n_selected > 0) HIPCHK(c, hipMemcpyAsync(selected_keys, ds, sizeof(uint64_t) * (size_t)*n_selected, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RSM_OK;
+        return mesh_fail(c, "mesh_decimate", s, invalid);
+    T.later(out_xyz, dv, 3 * (size_t)nv).later(out_quadrics, dq, 10 * (size_t)nv);
+    T.later(out_faces, dfo, 3 * (size_t)*n_faces_out).later(selected_keys, ds, (size_t)*n_selected);
+    return finish(c, T);
 }
 
 // ---- colours of the mesh from the rig's views (k_meshcolor.hip) ----------------------------------------------------------
@@ -732,10 +677,8 @@ extern "C" int rsm_mesh_color(rsm_ctx *c, const float *xyz, int64_t nv, const in
     int invalid = 0;
     s = mesh_color_device(dv, nv, df, nf, views, n_pairs, p, c->opt_meshcolor_big_box, dc, db, stats, &invalid, c->stream);
     if (s != RSM_OK) return meshcolor_fail(c, s, invalid);
-    if (nv > 0) HIPCHK(c, hipMemcpyAsync(rgb, dc, 3 * (size_t)nv, hipMemcpyDeviceToHost, c->stream));
-    if (nv > 0 && best_view) HIPCHK(c, hipMemcpyAsync(best_view, db, sizeof(int32_t) * (size_t)nv, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RSM_OK;
+    T.later(rgb, dc, 3 * (size_t)nv).later(best_view, db, (size_t)nv);
+    return finish(c, T);
 }
 
 // the context's colour buffers for a mesh of nv vertices (what rsm_mesh_last_colors copies out), without an owner yet
@@ -744,8 +687,7 @@ static int mcol_reserve(rsm_ctx *c, const char *who, int64_t nv) {
     if (c->mcol_best) (void)hipFree(c->mcol_best);
     c->mcol_rgb = nullptr;
     c->mcol_best = nullptr;
-    c->mcol_of = nullptr;
-    c->mcol_nv = 0;
+    c->mcol_valid = false;
     if (hipMalloc((void **)&c->mcol_rgb, 3 * (size_t)nv + 64) != hipSuccess || hipMalloc((void **)&c->mcol_best, sizeof(int32_t) * (size_t)nv + 64) != hipSuccess)
         return set_err(c, RSM_E_NOMEM, "%s: no device memory for %lld vertices", who, (long long)nv);
     return RSM_OK;
@@ -761,18 +703,18 @@ extern "C" int rsm_mesh_color_last(rsm_ctx *c, const rsm_dedup_view *views, int 
     int invalid = 0;
     s = mesh_color_device(c->pmesh.d_v, nv, c->pmesh.d_f, nf, views, n_pairs, p, c->opt_meshcolor_big_box, c->mcol_rgb, c->mcol_best, stats, &invalid, c->stream);
     if (s != RSM_OK) return meshcolor_fail(c, s, invalid);
-    c->mcol_of = c->pmesh.d_v;
-    c->mcol_nv = nv;
+    c->mcol_valid = true;
     return RSM_OK;
 }
 
 extern "C" int rsm_mesh_last_colors(rsm_ctx *c, uint8_t *rgb, int32_t *best_view) {
     if (!c) return RSM_E_INVALID;
-    if (!c->mcol_rgb || c->mcol_of != c->pmesh.d_v || c->mcol_nv != c->pmesh.nv)
+    if (!c->mcol_rgb || !c->mcol_valid)
         return set_err(c, RSM_E_STATE, "mesh_last_colors: the context's last mesh has no colours (rsm_mesh_color_last first)");
     HIPCHK(c, hipSetDevice(c->device));
-    if (rgb && c->mcol_nv > 0) HIPCHK(c, hipMemcpyAsync(rgb, c->mcol_rgb, 3 * (size_t)c->mcol_nv, hipMemcpyDeviceToHost, c->stream));
-    if (best_view && c->mcol_nv > 0) HIPCHK(c, hipMemcpyAsync(best_view, c->mcol_best, sizeof(int32_t) * (size_t)c->mcol_nv, hipMemcpyDeviceToHost, c->stream));
+    const size_t nv = (size_t)c->pmesh.nv; // (valid: the mesh is the one they were computed on)
+    if (rgb && nv > 0) HIPCHK(c, hipMemcpyAsync(rgb, c->mcol_rgb, 3 * nv, hipMemcpyDeviceToHost, c->stream));
+    if (best_view && nv > 0) HIPCHK(c, hipMemcpyAsync(best_view, c->mcol_best, sizeof(int32_t) * nv, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return RSM_OK;
 }
@@ -812,9 +754,8 @@ extern "C" int rsm_stage_mesh_depth(rsm_ctx *c, const float *xyz, int64_t nv, co
     if ((s = finish(c, T)) != RSM_OK) return s;
     int invalid = 0;
     if ((s = mesh_depth_device(dv, nv, df, nf, P12, width, height, c->opt_meshcolor_big_box, dw, &invalid, c->stream)) != RSM_OK) return meshcolor_fail(c, s, invalid);
-    HIPCHK(c, hipMemcpyAsync(wbuf, dw, sizeof(uint32_t) * pix, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RSM_OK;
+    T.later(wbuf, dw, pix);
+    return finish(c, T);
 }
 
 // ---- the views' exposure seams levelled in those colours (k_meshstitch.hip) ---------------------------------------------
@@ -867,10 +808,8 @@ extern "C" int rsm_mesh_stitch(rsm_ctx *c, const float *xyz, int64_t nv, const i
     int invalid = 0;
     s = mesh_stitch_device(dv, nv, df, nf, views, n_pairs, p, sp, c->opt_meshcolor_big_box, dc, db, stats, &invalid, c->stream);
     if (s != RSM_OK) return meshstitch_fail(c, s, invalid);
-    if (nv > 0) HIPCHK(c, hipMemcpyAsync(rgb, dc, 3 * (size_t)nv, hipMemcpyDeviceToHost, c->stream));
-    if (nv > 0 && best_view) HIPCHK(c, hipMemcpyAsync(best_view, db, sizeof(int32_t) * (size_t)nv, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RSM_OK;
+    T.later(rgb, dc, 3 * (size_t)nv).later(best_view, db, (size_t)nv);
+    return finish(c, T);
 }
 
 extern "C" int rsm_mesh_stitch_last(rsm_ctx *c, const rsm_dedup_view *views, int n_pairs, const rsm_mesh_color_params *p, const rsm_mesh_stitch_params *sp,
@@ -884,8 +823,7 @@ extern "C" int rsm_mesh_stitch_last(rsm_ctx *c, const rsm_dedup_view *views, int
     int invalid = 0;
     s = mesh_stitch_device(c->pmesh.d_v, nv, c->pmesh.d_f, nf, views, n_pairs, p, sp, c->opt_meshcolor_big_box, c->mcol_rgb, c->mcol_best, stats, &invalid, c->stream);
     if (s != RSM_OK) return meshstitch_fail(c, s, invalid);
-    c->mcol_of = c->pmesh.d_v;
-    c->mcol_nv = nv;
+    c->mcol_valid = true;
     return RSM_OK;
 }
 
@@ -906,9 +844,8 @@ extern "C" int rsm_stage_mesh_visibility(rsm_ctx *c, const float *xyz, int64_t n
     if ((s = finish(c, T)) != RSM_OK) return s;
     int invalid = 0;
     if ((s = mesh_visibility_device(dv, nv, df, nf, views, n_pairs, p, c->opt_meshcolor_big_box, dm, &invalid, c->stream)) != RSM_OK) return meshcolor_fail(c, s, invalid);
-    if (nv > 0) HIPCHK(c, hipMemcpyAsync(vis, dm, sizeof(uint64_t) * (size_t)nv, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RSM_OK;
+    T.later(vis, (const uint64_t *)dm, (size_t)nv);
+    return finish(c, T);
 }
 
 extern "C" int rsm_stage_mesh_stitch_rhs(rsm_ctx *c, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, const rsm_dedup_view *views, int n_pairs,
@@ -935,10 +872,8 @@ extern "C" int rsm_stage_mesh_stitch_rhs(rsm_ctx *c, const float *xyz, int64_t n
     int invalid = 0;
     if ((s = mesh_stitch_rhs_device(dv, nv, df, nf, views, n_pairs, dc, db, dm, seam_gradient, dG, dd, counts, &invalid, c->stream)) != RSM_OK)
         return meshcolor_fail(c, s, invalid);
-    if (nv > 0) HIPCHK(c, hipMemcpyAsync(G, dG, sizeof(double) * 3 * (size_t)nv, hipMemcpyDeviceToHost, c->stream));
-    if (nv > 0) HIPCHK(c, hipMemcpyAsync(deg, dd, sizeof(int32_t) * (size_t)nv, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RSM_OK;
+    T.later(G, dG, 3 * (size_t)nv).later(deg, dd, (size_t)nv);
+    return finish(c, T);
 }
 
 extern "C" int rsm_stage_mesh_stitch_solve(rsm_ctx *c, const int32_t *faces, int64_t nv, int64_t nf, const int32_t *best_view, const uint8_t *rgb, const double *G,
@@ -959,7 +894,6 @@ extern "C" int rsm_stage_mesh_stitch_solve(rsm_ctx *c, const int32_t *faces, int
     if ((s = finish(c, T)) != RSM_OK) return s;
     int invalid = 0;
     if ((s = mesh_stitch_solve_device(df, nv, nf, db, dc, dG, lambda, iterations, dx, rel_residual, &invalid, c->stream)) != RSM_OK) return meshcolor_fail(c, s, invalid);
-    if (nv > 0) HIPCHK(c, hipMemcpyAsync(x, dx, sizeof(double) * 3 * (size_t)nv, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return RSM_OK;
+    T.later(x, dx, 3 * (size_t)nv);
+    return finish(c, T);
 }

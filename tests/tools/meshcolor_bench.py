@@ -31,7 +31,7 @@ def analyze(path):
     for f in files:
         with open(f, newline="") as fp:
             for r in csv.DictReader(fp):
-                m = re.search(r"k_mcol_\w+(<[^>]*>)?|k_mc_(validate|corner_keys|row_starts)", r["Kernel_Name"])
+                m = re.search(r"k_mcol_\w+(<[^>]*>)?|k_mc_validate|k_mesh_(corner_keys|row_starts)", r["Kernel_Name"])
                 if m:
                     per.setdefault(m.group(0), []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) * 1e-6)
     total = sum(sum(v) for v in per.values())

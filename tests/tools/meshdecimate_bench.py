@@ -24,7 +24,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 GROUPS = (("the cost kernel", ("k_md_costs",)), ("the selection", ("k_md_rank", "k_md_m2", "k_md_select", "k_md_apply")),
           ("the sorts", ("radix", "onesweep", "histogram", "sort")), ("the scans", ("scan", "lookback")),
-          ("tables", ("k_mesh_edge_keys", "k_md_corner_keys", "k_md_row_starts", "k_md_heads", "k_md_unique", "k_md_vertex", "k_md_entry_border", "k_md_quadrics")),
+          ("tables", ("k_mesh_edge_keys", "k_mesh_corner_keys", "k_mesh_row_starts", "k_md_heads", "k_md_unique", "k_md_vertex", "k_md_entry_border", "k_md_quadrics")),
           ("memsets and copies", ("fillbuffer", "copybuffer")),
           ("faces and vertices", ("k_md_remap", "k_md_compact", "k_md_distinct", "k_md_used", "k_md_renumber", "k_mesh_iota", "k_mesh_compact")))
 
