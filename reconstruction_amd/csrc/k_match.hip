@@ -16,6 +16,10 @@
 // reference-order fp64 restatement of WindowToVec + arma::dot (CManageData.cpp:81-90, op_dot_meat.hpp:20-55),
 // which overwrites their result: the chosen column is the reference's on few-level, saturated and periodic
 // textures too (tests/test_gpu_ncc_ties.py).
+// Layout of the NCC part: the constants; one section of __device__ helpers that states each shared rule once (a pixel's
+// candidate interval, which kernel takes a pixel, list entries, the dot4 group, 1/sqrt, offer / tie / merge of best
+// scores); then the nine kernels, each dynamic-LDS kernel behind the constexpr layout struct that its launcher sizes
+// the launch with; the launchers last.
 #include "rsm_dev.h"
 
 #include <stdlib.h>
@@ -116,6 +120,79 @@ void launch_hl_interval(const StageArgs &a, hipStream_t st) {
 // |integer-form score - reference fp64 score| < 1e-12 for every radius <= 15 (n <= 2883 terms of relative 1.1e-16);
 // two candidates closer than this in integer form are decided by k_ncc_exact
 #define NCC_TIE_TOL 1e-11
+#define NCC_G 5      // candidates of one register-blocked dot4 group
+#define NCC_WIDE 160 // the largest interval the band kernel takes (its LDS staging is sized for it); StageArgs::ncc_wide may lower the threshold
+#define RG_SLOTS 512 // row-kernel workgroups per direction in grid.y: every workgroup loops over the listed rows slot by slot (slot, slot + gridDim.y, ...),
+                     // so no listed row is ever left out; k_ncc_wide skips every row that k_rg_rows listed (>= RG_MIN wide pixels)
+#define RG_MIN 48 // wide pixels of a (direction, row) from which the row is matched by k_ncc_rowgemm instead of k_ncc_wide
+#define RG_SLIDE_MIN 1024 // wide pixels of a row from which k_ncc_slide takes it (when its widest interval allows): C2's rows below an empty parent row at
+                          // the lower levels (128...1024 pixels x as many candidates) run faster in the GEMM (initial match 1.43 against 1.83 ms)
+#define RG_MID_MIN 512 // pixels of a row with an interval beyond the band kernel's crossover (ncc_mid) from which ALL of them join the row
+                       // kernel: a short row (C2's lowest level: 128 pixels x 128 candidates) is latency-bound there (initial match 1.40 -> 1.88 ms)
+
+// ---------------------------------------------------------------- the rules every NCC kernel shares, each stated once
+// Every pixel must reach exactly one kernel (tests/ncc_routes.py), and every kernel must scan the same candidates and
+// break ties the same way: the interval, the routing tests, the score pieces and the best-score rules live here only.
+// The helpers take values, never the kernel's StageArgs / DirArgs by reference: handed out by reference, the argument
+// struct's loads are no longer known to be unclobbered and stop being scalar loads (k_ncc_rowgemm<3>: an occupancy step).
+
+// List entries (wide-pixel worklist, tie list): the pixel's index in the low 31 bits, the direction on top.
+__device__ __forceinline__ uint32_t ncc_entry(size_t pix, unsigned dir) { return (uint32_t)pix | (dir << 31); }
+__device__ __forceinline__ uint32_t ncc_entry_pix(uint32_t e) { return e & 0x7fffffffu; }
+__device__ __forceinline__ unsigned ncc_entry_dir(uint32_t e) { return e >> 31; }
+
+// The candidate columns L..R of a pixel: the other margin at the lowest level (mode 0, .cpp:207), else the interval
+// k_hl_interval / the boundary pass left in BL / BR; windows that would leave the image are skipped (UB in the
+// reference).  Empty when L > R.  oXL..oXR: the other margin (d.oth).
+struct NccIv {
+    int L, R;
+};
+__device__ __forceinline__ NccIv ncc_interval(int mode, int oXL, int oXR, const int16_t *BL, const int16_t *BR, size_t pix, int W, int r) {
+    int L, R;
+    if (mode == 0) {
+        L = oXL;
+        R = oXR;
+    } else {
+        L = BL[pix];
+        R = BR[pix];
+    }
+    return NccIv{max(L, r), min(R, W - 1 - r)};
+}
+// Routing.  A pixel is wide -- leaves k_ncc_dot4 for the worklist -- when its interval is longer than its row's wide_from.
+// A row that holds RG_MID_MIN or more pixels with an interval longer than ncc_mid goes to a row kernel (k_ncc_rowstat counted
+// them): there every such pixel leaves the band kernel, elsewhere only those beyond its own limit.  row_kernels: the band
+// kernel passes opt_no_rowgemm != 1; the row kernels, launched only then, pass true (k_ncc_slide sits at the SGPR limit:
+// reading the option there spilled 8 more SGPRs around its sliding loop).  wide_from > 0, so a wide interval is never empty.
+__device__ __forceinline__ int ncc_wide_from(bool row_kernels, const int32_t *wrow, int H, unsigned dir, int y, int ncc_mid) {
+    return (row_kernels && wrow[NCC_WROW_MID(H) + dir * H + y] >= RG_MID_MIN) ? ncc_mid : NCC_WIDE;
+}
+__device__ __forceinline__ bool ncc_is_wide(NccIv iv, int wide_from) { return iv.R - iv.L + 1 > wide_from; }
+// A row kernel's view of one masked pixel: its interval when it is a wide pixel, else the empty {INT_MAX, -1} (R >= 0
+// tells the two apart).  The callers ask under `masked ? ... : ncc_no_interval()`, so that what the interval reads is read
+// inside the pixel's branch and holds no scalar registers across the kernel's main loop.
+__device__ __forceinline__ NccIv ncc_no_interval() { return NccIv{0x7fffffff, -1}; }
+__device__ __forceinline__ NccIv ncc_wide_only(NccIv iv, int wide_from) { return ncc_is_wide(iv, wide_from) ? iv : ncc_no_interval(); }
+
+// min of lo / max of hi over the wave, and over the workgroup into s[0] / s[1] (a barrier on either side is the caller's)
+__device__ __forceinline__ void ncc_wave_minmax(int &lo, int &hi) {
+    for (int o = 32; o > 0; o >>= 1) {
+        lo = min(lo, __shfl_xor(lo, o));
+        hi = max(hi, __shfl_xor(hi, o));
+    }
+}
+__device__ __forceinline__ void ncc_block_minmax_init(int *s) {
+    if (threadIdx.x == 0) {
+        s[0] = 0x7fffffff;
+        s[1] = -1;
+    }
+}
+__device__ __forceinline__ void ncc_block_minmax(int *s, int lo, int hi) {
+    ncc_wave_minmax(lo, hi);
+    if ((threadIdx.x & 63) == 0) {
+        atomicMin(&s[0], lo);
+        atomicMax(&s[1], hi);
+    }
+}
 
 // Running best of the strict '>' scan (.cpp:213) over integer-form scores.  `exact`: the score is the reference's to
 // the last bit (a zero-variance window scores exactly 0 there too: u = 0 everywhere, CManageData.cpp:86-89, and the
@@ -126,18 +203,40 @@ struct NccBest {
     bool exact;
     bool tie;
 };
+// The rules are predicates over values (tol: NCC_TIE_TOL, or ncc_scaled_tol() where the scores are scaled): the flags of a
+// running best live in lane masks or in bits of a register, whichever the kernel can afford, and a helper that took them
+// by reference or in a struct moved them into vector registers (k_ncc_wide<5>, <7>: an occupancy step).
+// a score this close to the best so far is a tie, unless both are exact
+__device__ __forceinline__ bool ncc_near_tie(double sc, bool exact, double bv, bool bexact, double tol) {
+    return fabs(sc - bv) <= tol && !(exact && bexact);
+}
 __device__ __forceinline__ void ncc_offer(NccBest &b, double sc, int c, bool exact) {
-    if (fabs(sc - b.v) <= NCC_TIE_TOL && !(exact && b.exact)) b.tie = true;
+    if (ncc_near_tie(sc, exact, b.v, b.exact, NCC_TIE_TOL)) b.tie = true;
     if (sc > b.v) { // .cpp:213
         b.v = sc;
         b.c = c;
         b.exact = exact;
     }
 }
+// Two partial bests (v, c, exact) of one pixel over disjoint candidate sets: the other one is taken when its score is
+// larger or, at equal scores, its column smaller (the reference scans ascending with '>', so it keeps the first maximum);
+// two bests are a tie like two candidates of one scan, unless a side holds no candidate (column INT_MAX).  A side without
+// a candidate is never taken: it still holds the initial score, which no best lies below, and INT_MAX is below no column.
+__device__ __forceinline__ bool ncc_merge_ties(double bv, int bc, bool bx, double ov, int oc, bool ox, double tol) {
+    return bc != 0x7fffffff && oc != 0x7fffffff && ncc_near_tie(ov, ox, bv, bx, tol);
+}
+__device__ __forceinline__ bool ncc_merge_takes(double bv, int bc, double ov, int oc) { return ov > bv || (ov == bv && oc < bc); }
+
+// 1 / sqrt(x) for x > 0 (`pos`; otherwise some finite value the caller replaces): the hardware estimate plus one Newton
+// step (relative error ~2e-16) -- four times cheaper than a correctly rounded sqrt and divide, and the filter only has to
+// be within NCC_TIE_TOL / 2 of the reference's score.
+__device__ __forceinline__ double ncc_rsqrt(double x, bool pos) {
+    const double r = __builtin_amdgcn_rsq(pos ? x : 1.0);
+    const double e = __builtin_fma(-(x * r), r, 1.0);
+    return __builtin_fma(0.5 * r, e, r);
+}
 // Filter score (n Sab - Sa Sb) / sqrt(va vb) of one candidate, va = n Saa - Sa^2 > 0 of the own window given as a
-// double.  Every integer here is below 2^53, so the fp64 products and differences are exact; 1/sqrt is the
-// hardware estimate plus one Newton step (relative error ~2e-16) -- four times cheaper than a correctly rounded
-// sqrt and divide, and the filter only has to be within NCC_TIE_TOL / 2 of the reference's score.
+// double.  Every integer here is below 2^53, so the fp64 products and differences are exact.
 // Zero variance on either side -> exactly 0, as in the reference; *exact tells the caller so.
 __device__ __forceinline__ double ncc_filter_score(double nd, uint32_t Sab, double Sa, double va, int Sb, int Sbb, bool *exact) {
     const double sb = (double)Sb;
@@ -145,11 +244,75 @@ __device__ __forceinline__ double ncc_filter_score(double nd, uint32_t Sab, doub
     const double num = nd * (double)Sab - Sa * sb;
     const double p = va * vb;
     const bool nz = va > 0.0 && vb > 0.0;
-    double r = __builtin_amdgcn_rsq(nz ? p : 1.0);
-    const double e = __builtin_fma(-(p * r), r, 1.0);
-    r = __builtin_fma(0.5 * r, e, r);
+    const double r = ncc_rsqrt(p, nz);
     *exact = !nz;
     return nz ? num * r : 0.0;
+}
+// The row kernels score a pixel's candidates scaled by its own sv = sqrt(va) (constant per pixel, so the argmax and -- with
+// the tolerance scaled alike -- the tie test are unchanged; sv = -1 stands for zero variance: every score is exactly 0,
+// the scale is 1) from rvb = 1 / sqrt(vb), or 0 for zero variance.  The scan starts from the scaled -1 (.cpp:205).  Bit e
+// of `exact` / `tie` are the flags of a lane's e-th running best (two registers for all of them).  tol = ncc_scaled_tol(sv), which the
+// caller forms once per pixel in front of its candidate loop: formed behind the candidate's `continue`, the scoring blocks
+// of k_ncc_slide's sliding loop were laid out behind the loop (2 % of the kernel).
+__device__ __forceinline__ double ncc_scaled_tol(double sv) { return NCC_TIE_TOL * (sv > 0.0 ? sv : 1.0); }
+__device__ __forceinline__ double ncc_scaled_start(double sv) { return sv > 0.0 ? -sv : -1.0; }
+__device__ __forceinline__ void ncc_offer_scaled(double &bv, int &bc, unsigned &exact, unsigned &tie, int e, double nd, int Sab, double Sa,
+                                                 double sv, double tol, int Sb, double rvb, int c) {
+    const double sc = (nd * (double)Sab - Sa * (double)Sb) * rvb; // score * sqrt(va)
+    const bool exc = rvb == 0.0 || !(sv > 0.0);                   // a zero-variance window on either side: exactly 0
+    if (ncc_near_tie(sc, exc, bv, (exact >> e) & 1u, tol)) tie |= 1u << e;
+    if (sc > bv) { // .cpp:213
+        bv = sc;
+        bc = c;
+        exact = (exact & ~(1u << e)) | ((unsigned)exc << e);
+    }
+}
+
+// One register-blocked group: Sab of NCC_G consecutive candidates, (2R+1) window rows x (2R+1) own dwords x NCC_G
+// v_dot4_u32_u8.  own(j, m): own-view dword m of window row j; oth(j, t): other-view dword t of window row j, t = 0
+// being the first candidate's leftmost column.
+template <int R, class Own, class Oth>
+__device__ __forceinline__ void ncc_dot4_group(uint32_t (&acc)[NCC_G], Own own, Oth oth) {
+    constexpr int WS = 2 * R + 1, G = NCC_G, NB = G + WS - 1;
+#pragma unroll
+    for (int g = 0; g < G; g++) acc[g] = 0u;
+#pragma unroll 1 // one window row per iteration keeps the live set at ~2R+1+NB+G dwords (occupancy)
+    for (int j = 0; j < WS; j++) {
+        uint32_t av[WS], bw[NB];
+#pragma unroll
+        for (int m = 0; m < WS; m++) av[m] = own(j, m);
+#pragma unroll
+        for (int t = 0; t < NB; t++) bw[t] = oth(j, t);
+#pragma unroll
+        for (int m = 0; m < WS; m++)
+#pragma unroll
+            for (int g = 0; g < G; g++) acc[g] = __builtin_amdgcn_udot4(av[m], bw[g + m], acc[g], false);
+    }
+}
+// mask and window sums of the group's candidates c0 .. c0 + NCC_G - 1 from global memory (columns past cend: never scored)
+__device__ __forceinline__ void ncc_group_consts(const uint8_t *mask, const int32_t *S1, const int32_t *S2, int y, int W, int c0, int cend,
+                                                 uint8_t (&mk)[NCC_G], int32_t (&s1)[NCC_G], int32_t (&s2)[NCC_G]) {
+#pragma unroll
+    for (int g = 0; g < NCC_G; g++) {
+        const size_t o = (size_t)y * W + min(c0 + g, cend);
+        mk[g] = mask[o];
+        s1[g] = S1[o];
+        s2[g] = S2[o];
+    }
+}
+// offers the candidate group c0..c0+G-1 (their G accumulated Sab) to the running best, ascending columns
+template <int R>
+__device__ __forceinline__ void ncc_score_group(const uint32_t (&acc)[NCC_G], int c0, int cend, const uint8_t *mk,
+                                                const int32_t *s1, const int32_t *s2, double Sa, double va, NccBest &b) {
+    constexpr int n = (2 * R + 1) * (2 * R + 1) * 3;
+#pragma unroll
+    for (int g = 0; g < NCC_G; g++) {
+        const int c = c0 + g;
+        if (c > cend || mk[g] != 255) continue; // .cpp:209
+        bool ex;
+        const double sc = ncc_filter_score((double)n, acc[g], Sa, va, s1[g], s2[g], &ex);
+        ncc_offer(b, sc, c, ex);
+    }
 }
 // appends the pixels of this wave whose scan saw a (near) tie to the tie list of k_ncc_exact
 __device__ __forceinline__ void ncc_tie_append(const StageArgs &a, int cnt_slot, bool tie, uint32_t entry) {
@@ -182,33 +345,14 @@ __global__ __launch_bounds__(NCC_TX) void k_ncc_bytes(StageArgs a, int mode, int
     if (mode == 2 && active) active = (d.d16_in[pix] == NOMATCH); // Rematch: .cpp:538
     int L = 0x7fffffff, R = -1;
     if (active) {
-        if (mode == 0) {
-            L = d.oth.XL; // .cpp:207
-            R = d.oth.XR;
-        } else {
-            L = d.BL[pix];
-            R = d.BR[pix];
-        }
-        L = max(L, r); // windows that would leave the image are skipped (UB in the reference)
-        R = min(R, W - 1 - r);
+        const NccIv iv = ncc_interval(mode, d.oth.XL, d.oth.XR, d.BL, d.BR, pix, W, r);
+        L = iv.L;
+        R = iv.R;
         if (L > R) active = false;
     }
-    if (threadIdx.x == 0) {
-        s_lohi[0] = 0x7fffffff;
-        s_lohi[1] = -1;
-    }
+    ncc_block_minmax_init(s_lohi);
     __syncthreads();
-    {
-        int lo = active ? L : 0x7fffffff, hi = active ? R : -1;
-        for (int o = 32; o > 0; o >>= 1) {
-            lo = min(lo, __shfl_xor(lo, o));
-            hi = max(hi, __shfl_xor(hi, o));
-        }
-        if ((threadIdx.x & 63) == 0) {
-            atomicMin(&s_lohi[0], lo);
-            atomicMax(&s_lohi[1], hi);
-        }
-    }
+    ncc_block_minmax(s_lohi, active ? L : 0x7fffffff, active ? R : -1);
     __syncthreads();
     const int cmin = s_lohi[0], cmax = s_lohi[1];
     if (cmax < cmin) return; // nothing to do in this block
@@ -269,7 +413,7 @@ __global__ __launch_bounds__(NCC_TX) void k_ncc_bytes(StageArgs a, int mode, int
         }
     }
     if (active && bb.c != -1) d.d16_out[pix] = (int16_t)(bb.c - x); // .cpp:219-222 / 301-302 / 563-564
-    ncc_tie_append(a, mode == 2, active && bb.tie, (uint32_t)pix | ((uint32_t)blockIdx.z << 31));
+    ncc_tie_append(a, mode == 2, active && bb.tie, ncc_entry(pix, blockIdx.z));
 }
 
 // ---------------------------------------------------------------- NCC interval argmax, v_dot4_u32_u8
@@ -282,43 +426,32 @@ __global__ __launch_bounds__(NCC_TX) void k_ncc_bytes(StageArgs a, int mode, int
 //  k_ncc_wide : one workgroup per worklist pixel, its candidates spread over the 256 lanes.  (Whole rows
 //               whose parent row is NOMATCH search the entire other margin, .cpp:260-283: a handful of
 //               rows carrying as many evaluations as the rest of the level.)
-#define NCC_G 5
-#define NCC_WIDE 160 // the largest interval the band kernel takes (its LDS staging is sized for it); StageArgs::ncc_wide may lower the threshold
-#define RG_SLOTS 512 // row-kernel workgroups per direction in grid.y: every workgroup loops over the listed rows slot by slot (slot, slot + gridDim.y, ...),
-                     // so no listed row is ever left out; k_ncc_wide skips every row that k_rg_rows listed (>= RG_MIN wide pixels)
-#define RG_MIN 48 // wide pixels of a (direction, row) from which the row is matched by k_ncc_rowgemm instead of k_ncc_wide
-#define RG_SLIDE_MIN 1024 // wide pixels of a row from which k_ncc_slide takes it (when its widest interval allows): C2's rows below an empty parent row at
-                          // the lower levels (128...1024 pixels x as many candidates) run faster in the GEMM (initial match 1.43 against 1.83 ms)
-#define RG_MID_MIN 512 // pixels of a row with an interval beyond the band kernel's crossover (ncc_mid) from which ALL of them join the row
-                       // kernel: a short row (C2's lowest level: 128 pixels x 128 candidates) is latency-bound there (initial match 1.40 -> 1.88 ms)
-
-// offers the candidate group c0..c0+G-1 (their G accumulated Sab) to the running best, ascending columns
+// dynamic LDS of k_ncc_dot4<R>, byte offsets: the kernel indexes with it, the launcher sizes with it
 template <int R>
-__device__ __forceinline__ void ncc_score_group(const uint32_t (&acc)[NCC_G], int c0, int cend, const uint8_t *mk,
-                                                const int32_t *s1, const int32_t *s2, double Sa, double va, NccBest &b) {
-    constexpr int n = (2 * R + 1) * (2 * R + 1) * 3;
-#pragma unroll
-    for (int g = 0; g < NCC_G; g++) {
-        const int c = c0 + g;
-        if (c > cend || mk[g] != 255) continue; // .cpp:209
-        bool ex;
-        const double sc = ncc_filter_score((double)n, acc[g], Sa, va, s1[g], s2[g], &ex);
-        ncc_offer(b, sc, c, ex);
-    }
-}
-
+struct NccDot4Lds {
+    static constexpr int WS = 2 * R + 1;
+    static constexpr int SA = NCC_TX + 2 * R;             // dwords per staged own-view row
+    static constexpr int SB = NCC_CH + 2 * R + NCC_G + 3; // dwords per staged other-view row
+    static constexpr int NC = NCC_CH + NCC_G;             // candidate columns of a pass (+ group padding)
+    static constexpr size_t CTL = 0;                      // int[2]: min L, max R over the narrow pixels of the block
+    static constexpr size_t A = 16;                       // u32 [WS][SA]
+    static constexpr size_t B = A + (size_t)WS * SA * 4;  // u32 [WS][SB]
+    static constexpr size_t S1 = B + (size_t)WS * SB * 4; // i32 [NC]
+    static constexpr size_t S2 = S1 + (size_t)NC * 4;     // i32 [NC]
+    static constexpr size_t M = S2 + (size_t)NC * 4;      // u8 [NC]
+    static constexpr size_t BYTES = M + NC + 16;
+};
 template <int R>
 __global__ __launch_bounds__(NCC_TX) void k_ncc_dot4(StageArgs a, int mode) {
-    constexpr int WS = 2 * R + 1, G = NCC_G, NB = G + WS - 1;
-    constexpr int SA = NCC_TX + 2 * R;         // dwords per staged own-view row
-    constexpr int SB = NCC_CH + 2 * R + G + 3; // dwords per staged other-view row
+    using Lds = NccDot4Lds<R>;
+    constexpr int WS = Lds::WS, G = NCC_G, SA = Lds::SA, SB = Lds::SB;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    int *s_ctl = (int *)smem; // [0]=min L, [1]=max R over the narrow pixels of the block
-    uint32_t *sA = (uint32_t *)(smem + 16);
-    uint32_t *sB = sA + WS * SA;
-    int32_t *sS1 = (int32_t *)(sB + WS * SB);
-    int32_t *sS2 = sS1 + NCC_CH + G;
-    uint8_t *sM = (uint8_t *)(sS2 + NCC_CH + G);
+    int *s_ctl = (int *)(smem + Lds::CTL);
+    uint32_t *sA = (uint32_t *)(smem + Lds::A);
+    uint32_t *sB = (uint32_t *)(smem + Lds::B);
+    int32_t *sS1 = (int32_t *)(smem + Lds::S1);
+    int32_t *sS2 = (int32_t *)(smem + Lds::S2);
+    uint8_t *sM = smem + Lds::M;
     const DirArgs &d = a.d[blockIdx.z];
     const int W = a.W;
     constexpr int n = WS * WS * 3;
@@ -333,21 +466,13 @@ __global__ __launch_bounds__(NCC_TX) void k_ncc_dot4(StageArgs a, int mode) {
     if (mode == 2 && active) active = (d.d16_in[pix] == NOMATCH); // Rematch: .cpp:538
     int L = 0x7fffffff, Rr = -1;
     if (active) {
-        if (mode == 0) {
-            L = d.oth.XL; // .cpp:207
-            Rr = d.oth.XR;
-        } else {
-            L = d.BL[pix];
-            Rr = d.BR[pix];
-        }
-        L = max(L, R); // windows that would leave the image are skipped (UB in the reference)
-        Rr = min(Rr, W - 1 - R);
+        const NccIv iv = ncc_interval(mode, d.oth.XL, d.oth.XR, d.BL, d.BR, pix, W, R);
+        L = iv.L;
+        Rr = iv.R;
         if (L > Rr) active = false;
     }
-    // a row that holds RG_MIN or more pixels with an interval longer than ncc_mid goes to a row kernel (k_ncc_rowstat counted them):
-    // there every such pixel leaves this kernel, elsewhere only those beyond its own limit
-    const int wide_from = (a.opt_no_rowgemm != 1 && a.wrow[NCC_WROW_MID(a.H) + blockIdx.z * a.H + y] >= RG_MID_MIN) ? a.ncc_mid : NCC_WIDE;
-    const bool wide = active && (Rr - L + 1 > wide_from);
+    const int wide_from = ncc_wide_from(a.opt_no_rowgemm != 1, a.wrow, a.H, blockIdx.z, y, a.ncc_mid);
+    const bool wide = active && ncc_is_wide(NccIv{L, Rr}, wide_from);
     // append of the wide pixels to the worklist of k_ncc_wide / the row kernels, ONE pair of atomics per workgroup
     // (per wave, the single list counter -- ~88 same-address atomics per microsecond -- was 2.2 ms of a 12.5 MP frame
     // of wide pixels)
@@ -355,35 +480,22 @@ __global__ __launch_bounds__(NCC_TX) void k_ncc_dot4(StageArgs a, int mode) {
     const unsigned long long wmask = __ballot(wide);
     const bool narrow = active && !wide;
     if (lane == 0) s_wn[tid >> 6] = __popcll(wmask);
-    if (tid == 0) {
-        s_ctl[0] = 0x7fffffff;
-        s_ctl[1] = -1;
-    }
+    ncc_block_minmax_init(s_ctl);
     __syncthreads();
-    {
-        int lo = narrow ? L : 0x7fffffff, hi = narrow ? Rr : -1;
-        for (int o = 32; o > 0; o >>= 1) {
-            lo = min(lo, __shfl_xor(lo, o));
-            hi = max(hi, __shfl_xor(hi, o));
-        }
-        if (lane == 0) {
-            atomicMin(&s_ctl[0], lo);
-            atomicMax(&s_ctl[1], hi);
-        }
-        if (tid == 0) {
-            int tot = 0;
-            for (int w = 0; w < NCC_TX / 64; w++) tot += s_wn[w];
-            if (tot) {
-                s_wbase = atomicAdd(a.ncc_cnt, tot);
-                atomicAdd(a.wrow + blockIdx.z * a.H + y, tot);
-            }
+    ncc_block_minmax(s_ctl, narrow ? L : 0x7fffffff, narrow ? Rr : -1);
+    if (tid == 0) {
+        int tot = 0;
+        for (int w = 0; w < NCC_TX / 64; w++) tot += s_wn[w];
+        if (tot) {
+            s_wbase = atomicAdd(a.ncc_cnt, tot);
+            atomicAdd(a.wrow + blockIdx.z * a.H + y, tot);
         }
     }
     __syncthreads();
     if (wide) {
         int base = s_wbase;
         for (int w = 0; w < (tid >> 6); w++) base += s_wn[w];
-        a.rf_list[base + __popcll(wmask & ((1ull << lane) - 1ull))] = (uint32_t)pix | ((uint32_t)blockIdx.z << 31);
+        a.rf_list[base + __popcll(wmask & ((1ull << lane) - 1ull))] = ncc_entry(pix, blockIdx.z);
     }
     const int cmin = s_ctl[0], cmax = s_ctl[1];
     if (cmax < cmin) return;
@@ -431,40 +543,34 @@ __global__ __launch_bounds__(NCC_TX) void k_ncc_dot4(StageArgs a, int mode) {
             const int c1 = min(Rr, hi);
             for (int c0 = max(L, lo); c0 <= c1; c0 += G) {
                 uint32_t acc[G];
-#pragma unroll
-                for (int g = 0; g < G; g++) acc[g] = 0u;
                 const int bo = c0 - lo;
-#pragma unroll 1 // one window row per iteration keeps the live set at ~2R+1+NB+G dwords (occupancy)
-                for (int j = 0; j < WS; j++) {
-                    uint32_t av[WS], bw[NB];
-#pragma unroll
-                    for (int m = 0; m < WS; m++) av[m] = sA[j * SA + tid + m];
-#pragma unroll
-                    for (int t = 0; t < NB; t++) bw[t] = sB[j * SB + bo + t];
-#pragma unroll
-                    for (int m = 0; m < WS; m++)
-#pragma unroll
-                        for (int g = 0; g < G; g++) acc[g] = __builtin_amdgcn_udot4(av[m], bw[g + m], acc[g], false);
-                }
+                ncc_dot4_group<R>(
+                    acc, [=](int j, int m) { return sA[j * SA + tid + m]; }, [=](int j, int t) { return sB[j * SB + bo + t]; });
                 ncc_score_group<R>(acc, c0, c1, sM + bo, sS1 + bo, sS2 + bo, Sa, va, bb);
             }
         }
     }
     if (narrow && bb.c != -1) d.d16_out[pix] = (int16_t)(bb.c - x); // .cpp:219-222 / 301-302 / 563-564
-    ncc_tie_append(a, 0, narrow && bb.tie, (uint32_t)pix | ((uint32_t)blockIdx.z << 31));
+    ncc_tie_append(a, 0, narrow && bb.tie, ncc_entry(pix, blockIdx.z));
 }
 
 // One workgroup per wide pixel (worklist of k_ncc_dot4), candidates spread over the 256 lanes, NCC_G consecutive
 // ones per lane and pass.  The other view's rows of a pass (256 * NCC_G candidates + window) are staged in LDS with
 // coalesced loads first: read straight from global memory every lane would fetch 15 dwords per window row.
 template <int R>
+struct NccWideLds {                                      // dynamic LDS of k_ncc_wide<R>: the other view's rows of a pass, u32 [WS][ROW]
+    static constexpr int WS = 2 * R + 1;
+    static constexpr int CHW = NCC_TX * NCC_G;           // candidates per pass
+    static constexpr int ROW = CHW + 2 * R + NCC_G;      // dwords per staged row (window and group padding)
+    static constexpr size_t BYTES = (size_t)WS * ROW * 4;
+};
+template <int R>
 __global__ __launch_bounds__(NCC_TX) void k_ncc_wide(StageArgs a, int mode) {
-    constexpr int WS = 2 * R + 1, G = NCC_G, NB = G + WS - 1;
+    using Lds = NccWideLds<R>;
+    constexpr int WS = Lds::WS, G = NCC_G, CHW = Lds::CHW;
     constexpr int n = WS * WS * 3;
-    constexpr int CHW = NCC_TX * G;  // candidates per pass
-    constexpr int SBW = CHW + 2 * R; // dwords per staged row
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    uint32_t *sB = (uint32_t *)smem; // [WS][SBW]
+    uint32_t *sB = (uint32_t *)smem;
     __shared__ uint32_t sAw[WS * WS];
     __shared__ double s_v[NCC_TX / 64];
     __shared__ int s_c[NCC_TX / 64];
@@ -486,26 +592,18 @@ __global__ __launch_bounds__(NCC_TX) void k_ncc_wide(StageArgs a, int mode) {
     __syncthreads();
     if (tid < chunk && base + tid < count) {
         const uint32_t e0 = a.rf_list[base + tid];
-        const int y0 = (int)((e0 & 0x7fffffffu) / W);
-        if (a.opt_no_rowgemm == 1 || a.wrow[(e0 >> 31) * a.H + y0] < RG_MIN) s_items[atomicAdd(&s_nitems, 1)] = e0;
+        const int y0 = (int)(ncc_entry_pix(e0) / W);
+        if (a.opt_no_rowgemm == 1 || a.wrow[ncc_entry_dir(e0) * a.H + y0] < RG_MIN) s_items[atomicAdd(&s_nitems, 1)] = e0;
     }
     __syncthreads();
     const int nitems = s_nitems;
     for (int it = 0; it < nitems; it++) { // uniform
         const uint32_t ent = s_items[it];
-        const DirArgs &d = a.d[ent >> 31];
-        const size_t pix = ent & 0x7fffffffu;
+        const DirArgs &d = a.d[ncc_entry_dir(ent)];
+        const size_t pix = ncc_entry_pix(ent);
         const int y = (int)(pix / W), x = (int)(pix % W);
-        int L, Rr;
-        if (mode == 0) {
-            L = d.oth.XL;
-            Rr = d.oth.XR;
-        } else {
-            L = d.BL[pix];
-            Rr = d.BR[pix];
-        }
-        L = max(L, R);
-        Rr = min(Rr, W - 1 - R);
+        const NccIv iv = ncc_interval(mode, d.oth.XL, d.oth.XR, d.BL, d.BR, pix, W, R);
+        const int L = iv.L, Rr = iv.R;
         __syncthreads(); // previous item done with sAw / s_v / s_c / sB
         if (tid < WS * WS) sAw[tid] = d.img4_own[(size_t)(y - R + tid / WS) * W + x - R + tid % WS];
         const double Sa = (double)d.S1_own[pix];
@@ -521,41 +619,22 @@ __global__ __launch_bounds__(NCC_TX) void k_ncc_wide(StageArgs a, int mode) {
 #pragma unroll
                 for (int j = 0; j < WS; j++) v[j] = d.img4_oth[(size_t)(y - R + j) * W + col];
 #pragma unroll
-                for (int j = 0; j < WS; j++) sB[j * (SBW + G) + i] = v[j];
+                for (int j = 0; j < WS; j++) sB[j * Lds::ROW + i] = v[j];
             }
             __syncthreads();
             const int c0 = lo + tid * G;
             if (c0 <= hi) {
                 uint32_t acc[G];
-#pragma unroll
-                for (int g = 0; g < G; g++) acc[g] = 0u;
                 const int bo = c0 - lo;
-#pragma unroll 1
-                for (int j = 0; j < WS; j++) {
-                    uint32_t av[WS], bw[NB];
-#pragma unroll
-                    for (int m = 0; m < WS; m++) av[m] = sAw[j * WS + m];
-#pragma unroll
-                    for (int t = 0; t < NB; t++) bw[t] = sB[j * (SBW + G) + bo + t];
-#pragma unroll
-                    for (int m = 0; m < WS; m++)
-#pragma unroll
-                        for (int g = 0; g < G; g++) acc[g] = __builtin_amdgcn_udot4(av[m], bw[g + m], acc[g], false);
-                }
+                ncc_dot4_group<R>(
+                    acc, [=](int j, int m) { return sAw[j * WS + m]; }, [=](int j, int t) { return sB[j * Lds::ROW + bo + t]; });
                 uint8_t mk[G];
                 int32_t s1[G], s2[G];
-#pragma unroll
-                for (int g = 0; g < G; g++) {
-                    const size_t o = (size_t)y * W + min(c0 + g, Rr);
-                    mk[g] = d.mask_oth[o];
-                    s1[g] = d.S1_oth[o];
-                    s2[g] = d.S2_oth[o];
-                }
+                ncc_group_consts(d.mask_oth, d.S1_oth, d.S2_oth, y, W, c0, Rr, mk, s1, s2);
                 ncc_score_group<R>(acc, c0, Rr, mk, s1, s2, Sa, va, bb);
             }
         }
-        // block argmax; equal scores -> the smaller column (the reference scans ascending with '>'); two lanes'
-        // bests within NCC_TIE_TOL of each other are a tie like two candidates of one lane
+        // block argmax (ncc_merge_takes / _ties): the lanes of a wave, then the waves through LDS
         double bv = bb.v;
         int bc = bb.c;
         bool bx = bb.exact, tie = bb.tie;
@@ -563,8 +642,8 @@ __global__ __launch_bounds__(NCC_TX) void k_ncc_wide(StageArgs a, int mode) {
             const double ov = __shfl_xor(bv, o);
             const int oc = __shfl_xor(bc, o);
             const bool ox = __shfl_xor((int)bx, o) != 0;
-            if (bc != 0x7fffffff && oc != 0x7fffffff && fabs(ov - bv) <= NCC_TIE_TOL && !(ox && bx)) tie = true;
-            if (ov > bv || (ov == bv && oc < bc)) {
+            if (ncc_merge_ties(bv, bc, bx, ov, oc, ox, NCC_TIE_TOL)) tie = true;
+            if (ncc_merge_takes(bv, bc, ov, oc)) {
                 bv = ov;
                 bc = oc;
                 bx = ox;
@@ -579,12 +658,14 @@ __global__ __launch_bounds__(NCC_TX) void k_ncc_wide(StageArgs a, int mode) {
         __syncthreads();
         if (tid == 0) {
             for (int w = 1; w < NCC_TX / 64; w++) {
-                const bool ox = s_x[w] & 1;
-                if (s_x[w] & 2) tie = true;
-                if (bc != 0x7fffffff && s_c[w] != 0x7fffffff && fabs(s_v[w] - bv) <= NCC_TIE_TOL && !(ox && bx)) tie = true;
-                if (s_v[w] > bv || (s_v[w] == bv && s_c[w] < bc)) {
-                    bv = s_v[w];
-                    bc = s_c[w];
+                const double ov = s_v[w];
+                const int oc = s_c[w], of = s_x[w];
+                const bool ox = of & 1;
+                if (of & 2) tie = true;
+                if (ncc_merge_ties(bv, bc, bx, ov, oc, ox, NCC_TIE_TOL)) tie = true;
+                if (ncc_merge_takes(bv, bc, ov, oc)) {
+                    bv = ov;
+                    bc = oc;
                     bx = ox;
                 }
             }
@@ -601,7 +682,7 @@ __global__ __launch_bounds__(NCC_TX) void k_ncc_wide(StageArgs a, int mode) {
 // active lanes.
 template <int R>
 __global__ __launch_bounds__(256) void k_ncc_sparse(StageArgs a) {
-    constexpr int WS = 2 * R + 1, G = NCC_G, NB = G + WS - 1;
+    constexpr int WS = 2 * R + 1, G = NCC_G;
     constexpr int n = WS * WS * 3;
     const int W = a.W, H = a.H;
     const int lane = threadIdx.x & 63;
@@ -614,41 +695,24 @@ __global__ __launch_bounds__(256) void k_ncc_sparse(StageArgs a) {
         const DirArgs &d = a.d[dir];
         const size_t pix = a.rf_list[(size_t)row * W + item];
         const int y = (int)(pix / W), x = (int)(pix % W);
-        const int L = max((int)d.BL[pix], R), Rr = min((int)d.BR[pix], W - 1 - R);
+        const NccIv iv = ncc_interval(2, d.oth.XL, d.oth.XR, d.BL, d.BR, pix, W, R);
+        const int L = iv.L, Rr = iv.R;
         const double Sa = (double)d.S1_own[pix];
         const double va = (double)n * (double)d.S2_own[pix] - Sa * Sa;
         NccBest bb{-1.0, -1, true, false};
         for (int c0 = L; c0 <= Rr; c0 += G) {
             uint32_t acc[G];
-#pragma unroll
-            for (int g = 0; g < G; g++) acc[g] = 0u;
-#pragma unroll 1
-            for (int j = 0; j < WS; j++) {
-                const uint32_t *arow = d.img4_own + (size_t)(y - R + j) * W + x - R;
-                const uint32_t *brow = d.img4_oth + (size_t)(y - R + j) * W;
-                uint32_t av[WS], bw[NB];
-#pragma unroll
-                for (int m = 0; m < WS; m++) av[m] = arow[m];
-#pragma unroll
-                for (int t = 0; t < NB; t++) bw[t] = brow[min(c0 - R + t, W - 1)]; // clamped columns belong to c > Rr only
-#pragma unroll
-                for (int m = 0; m < WS; m++)
-#pragma unroll
-                    for (int g = 0; g < G; g++) acc[g] = __builtin_amdgcn_udot4(av[m], bw[g + m], acc[g], false);
-            }
+            const uint32_t *own = d.img4_own, *oth = d.img4_oth;
+            ncc_dot4_group<R>(
+                acc, [=](int j, int m) { return own[(size_t)(y - R + j) * W + x - R + m]; },
+                [=](int j, int t) { return oth[(size_t)(y - R + j) * W + min(c0 - R + t, W - 1)]; }); // clamped columns belong to c > Rr only
             uint8_t mk[G];
             int32_t s1[G], s2[G];
-#pragma unroll
-            for (int g = 0; g < G; g++) {
-                const size_t o = (size_t)y * W + min(c0 + g, Rr);
-                mk[g] = d.mask_oth[o];
-                s1[g] = d.S1_oth[o];
-                s2[g] = d.S2_oth[o];
-            }
+            ncc_group_consts(d.mask_oth, d.S1_oth, d.S2_oth, y, W, c0, Rr, mk, s1, s2);
             ncc_score_group<R>(acc, c0, Rr, mk, s1, s2, Sa, va, bb);
         }
         if (bb.c != -1) d.d16_out[pix] = (int16_t)(bb.c - x); // .cpp:563-564
-        if (bb.tie) a.tie_list[atomicAdd(a.tie_cnt + 1, 1)] = (uint32_t)pix | ((uint32_t)dir << 31); // rare: no aggregation
+        if (bb.tie) a.tie_list[atomicAdd(a.tie_cnt + 1, 1)] = ncc_entry(pix, dir); // rare: no aggregation
     }
     }
 }
@@ -674,19 +738,11 @@ __global__ __launch_bounds__(256) void k_ncc_exact(StageArgs a, int mode) {
         const int item = base + wid;
         const bool on = item < count; // wave-uniform
         const uint32_t ent = a.tie_list[on ? item : base];
-        const DirArgs &d = a.d[ent >> 31];
-        const size_t pix = ent & 0x7fffffffu;
+        const DirArgs &d = a.d[ncc_entry_dir(ent)];
+        const size_t pix = ncc_entry_pix(ent);
         const int y = (int)(pix / W), x = (int)(pix % W);
-        int L, Rr;
-        if (mode == 0) {
-            L = d.oth.XL;
-            Rr = d.oth.XR;
-        } else {
-            L = d.BL[pix];
-            Rr = d.BR[pix];
-        }
-        L = max(L, r); // windows that would leave the image are skipped (UB in the reference), as in the scan kernels
-        Rr = min(Rr, W - 1 - r);
+        const NccIv iv = ncc_interval(mode, d.oth.XL, d.oth.XR, d.BL, d.BR, pix, W, r); // the scan kernels' candidates
+        const int L = iv.L, Rr = iv.R;
         __syncthreads(); // previous round done with sT / sWin
         // own window in the reference's vector order: k = j * w + i <-> byte column j of window row i
         for (int k = lane; k < n; k += 64) {
@@ -736,10 +792,10 @@ __global__ __launch_bounds__(256) void k_ncc_exact(StageArgs a, int mode) {
                 }
             }
         }
-        for (int o = 32; o > 0; o >>= 1) {
+        for (int o = 32; o > 0; o >>= 1) { // these scores ARE the reference's: no ties
             const double ov = __shfl_xor(bv, o);
             const int oc = __shfl_xor(bc, o);
-            if (ov > bv || (ov == bv && oc < bc)) {
+            if (ncc_merge_takes(bv, bc, ov, oc)) {
                 bv = ov;
                 bc = oc;
             }
@@ -790,10 +846,8 @@ __global__ __launch_bounds__(256) void k_ncc_rowstat(StageArgs a, int mode) {
         if (x <= d.own.XR) {
             const size_t pix = (size_t)y * W + x;
             if (d.mask_own[pix] == 255) {
-                int L = mode == 0 ? d.oth.XL : (int)d.BL[pix], Rr = mode == 0 ? d.oth.XR : (int)d.BR[pix];
-                L = max(L, R);
-                Rr = min(Rr, W - 1 - R);
-                width = max(Rr - L + 1, 0);
+                const NccIv iv = ncc_interval(mode, d.oth.XL, d.oth.XR, d.BL, d.BR, pix, W, R);
+                width = max(iv.R - iv.L + 1, 0);
             }
         }
         cnt += __popcll(__ballot(width > a.ncc_mid));
@@ -851,45 +905,22 @@ __global__ __launch_bounds__(256) void k_ncc_rowgemm(StageArgs a, int mode) {
     for (int slot = blockIdx.y; slot < nrows; slot += gridDim.y) { // uniform
         __syncthreads(); // the previous row is done with the shared arrays
         const int y = rowlist[1 + slot];
-        const int wide_from = a.wrow[NCC_WROW_MID(a.H) + blockIdx.z * a.H + y] >= RG_MID_MIN ? a.ncc_mid : NCC_WIDE; // as k_ncc_dot4 chose for this row
-        if (tid == 0) {
-            s_lohi[0] = 0x7fffffff;
-            s_lohi[1] = -1;
-        }
+        const int wide_from = ncc_wide_from(true, a.wrow, a.H, blockIdx.z, y, a.ncc_mid);
+        ncc_block_minmax_init(s_lohi);
         __syncthreads();
         if (tid < RG_PX) { // this workgroup's pixels
             const int x = x0 + tid;
             const size_t pix = (size_t)y * W + min(x, W - 1);
-            bool active = (x <= d.own.XR) && (d.mask_own[pix] == 255);
-            int L = 0x7fffffff, Rr = -1;
-            if (active) {
-                if (mode == 0) {
-                    L = d.oth.XL; // .cpp:207
-                    Rr = d.oth.XR;
-                } else {
-                    L = d.BL[pix];
-                    Rr = d.BR[pix];
-                }
-                L = max(L, R);
-                Rr = min(Rr, W - 1 - R);
-                if (L > Rr) active = false;
-            }
-            const bool wide = active && (Rr - L + 1 > wide_from); // exactly k_ncc_dot4's test
+            const bool masked = x <= d.own.XR && d.mask_own[pix] == 255;
+            const NccIv iv = masked ? ncc_wide_only(ncc_interval(mode, d.oth.XL, d.oth.XR, d.BL, d.BR, pix, W, R), wide_from) : ncc_no_interval();
+            const bool wide = iv.R >= 0;
             const double Sa = wide ? (double)d.S1_own[pix] : 0.0;
             const double va = wide ? (double)n * (double)d.S2_own[pix] - Sa * Sa : 0.0;
             sPSa[tid] = Sa;
-            sPsv[tid] = va > 0.0 ? sqrt(va) : -1.0; // -1: zero variance -- every score is exactly 0, the scale is 1
-            sPL[tid] = wide ? L : 0x7fffffff;
-            sPR[tid] = wide ? Rr : -1;
-            int lo_ = wide ? L : 0x7fffffff, hi_ = wide ? Rr : -1;
-            for (int o = 32; o > 0; o >>= 1) {
-                lo_ = min(lo_, __shfl_xor(lo_, o));
-                hi_ = max(hi_, __shfl_xor(hi_, o));
-            }
-            if (lane == 0) {
-                atomicMin(&s_lohi[0], lo_);
-                atomicMax(&s_lohi[1], hi_);
-            }
+            sPsv[tid] = va > 0.0 ? sqrt(va) : -1.0; // -1: zero variance (ncc_offer_scaled)
+            sPL[tid] = iv.L;
+            sPR[tid] = iv.R;
+            ncc_block_minmax(s_lohi, iv.L, iv.R);
         }
         // own-view rows as signed bytes: sA[j][i] <-> column x0 - R + i of row y - R + j
         for (int i = tid; i < SA; i += 256) {
@@ -905,8 +936,7 @@ __global__ __launch_bounds__(256) void k_ncc_rowgemm(StageArgs a, int mode) {
         unsigned exact = 0xffu, tie = 0u; // the initial -1 is exact
 #pragma unroll
         for (int e = 0; e < 4 * RG_T; e++) {
-            const double sv = sPsv[wv * (16 * RG_T) + (e >> 2) * 16 + lg * 4 + (e & 3)];
-            bestv[e] = sv > 0.0 ? -sv : -1.0; // .cpp:205, scaled
+            bestv[e] = ncc_scaled_start(sPsv[wv * (16 * RG_T) + (e >> 2) * 16 + lg * 4 + (e & 3)]);
             bestc[e] = 0x7fffffff;
         }
         for (int lo = cmin; lo <= cmax; lo += RG_CC) { // uniform (no trip when the chunk holds no wide pixel)
@@ -924,8 +954,7 @@ __global__ __launch_bounds__(256) void k_ncc_rowgemm(StageArgs a, int mode) {
                 const size_t o = (size_t)y * W + (ok ? c : min(max(lo, 0), W - 1));
                 const int Sb = d.S1_oth[o];
                 const double vb = (double)n * (double)d.S2_oth[o] - (double)Sb * (double)Sb;
-                double r = __builtin_amdgcn_rsq(vb > 0.0 ? vb : 1.0);
-                r = __builtin_fma(0.5 * r, __builtin_fma(-(vb * r), r, 1.0), r); // one Newton step: ~2e-16 relative
+                const double r = ncc_rsqrt(vb, vb > 0.0);
                 sOk[ci] = ok;
                 sSb[ci] = Sb;
                 sRvb[ci] = vb > 0.0 ? r : 0.0; // zero variance: score exactly 0
@@ -972,23 +1001,15 @@ __global__ __launch_bounds__(256) void k_ncc_rowgemm(StageArgs a, int mode) {
                     const int xl = wv * (16 * RG_T) + (e >> 2) * 16 + lg * 4 + (e & 3);
                     const int Lp = sPL[xl], Rp = sPR[xl];
                     const double Sa = sPSa[xl], sv = sPsv[xl];
-                    const double tol = NCC_TIE_TOL * (sv > 0.0 ? sv : 1.0);
+                    const double tol = ncc_scaled_tol(sv);
                     const int Sai = (int)Sa;
 #pragma unroll
                     for (int u = 0; u < 4; u++) {
                         const int cl = cb * 64 + u * 16 + lr, c = lo + cl;
                         if (!sOk[cl] || c < Lp || c > Rp) continue;
                         const int Sb = sSb[cl];
-                        const double rvb = sRvb[cl];
                         const int Sab = acc[e >> 2][u][e & 3] + 128 * (Sai + Sb) - 16384 * n;
-                        const double sc = ((double)n * (double)Sab - Sa * (double)Sb) * rvb; // score * sqrt(va)
-                        const bool exc = rvb == 0.0 || !(sv > 0.0); // a zero-variance window on either side: exactly 0
-                        if (fabs(sc - bestv[e]) <= tol && !(exc && ((exact >> e) & 1u))) tie |= 1u << e;
-                        if (sc > bestv[e]) { // .cpp:213
-                            bestv[e] = sc;
-                            bestc[e] = c;
-                            exact = (exact & ~(1u << e)) | ((unsigned)exc << e);
-                        }
+                        ncc_offer_scaled(bestv[e], bestc[e], exact, tie, e, (double)n, Sab, Sa, sv, tol, Sb, sRvb[cl], c);
                     }
                     __builtin_amdgcn_sched_barrier(0); // one pixel's constants live at a time
                 }
@@ -998,8 +1019,7 @@ __global__ __launch_bounds__(256) void k_ncc_rowgemm(StageArgs a, int mode) {
 #pragma unroll
         for (int e = 0; e < 4 * RG_T; e++) {
             const int xl = wv * (16 * RG_T) + (e >> 2) * 16 + lg * 4 + (e & 3), x = x0 + xl;
-            const double sv = sPsv[xl];
-            const double tol = NCC_TIE_TOL * (sv > 0.0 ? sv : 1.0);
+            const double tol = ncc_scaled_tol(sPsv[xl]);
             double bv = bestv[e];
             int bc = bestc[e];
             bool bx = (exact >> e) & 1u, tt = (tie >> e) & 1u;
@@ -1007,8 +1027,8 @@ __global__ __launch_bounds__(256) void k_ncc_rowgemm(StageArgs a, int mode) {
                 const double ov = __shfl_xor(bv, o);
                 const int oc = __shfl_xor(bc, o);
                 const bool ox = __shfl_xor((int)bx, o) != 0;
-                if (bc != 0x7fffffff && oc != 0x7fffffff && fabs(ov - bv) <= tol && !(ox && bx)) tt = true;
-                if (ov > bv || (ov == bv && oc < bc)) {
+                if (ncc_merge_ties(bv, bc, bx, ov, oc, ox, tol)) tt = true;
+                if (ncc_merge_takes(bv, bc, ov, oc)) {
                     bv = ov;
                     bc = oc;
                     bx = ox;
@@ -1018,7 +1038,7 @@ __global__ __launch_bounds__(256) void k_ncc_rowgemm(StageArgs a, int mode) {
             if (lr == 0 && sPR[xl] >= 0) { // a wide pixel
                 const size_t pix = (size_t)y * W + x;
                 if (bc != 0x7fffffff) d.d16_out[pix] = (int16_t)(bc - x); // .cpp:219-222 / 301-302
-                if (tt) a.tie_list[atomicAdd(a.tie_cnt, 1)] = (uint32_t)pix | ((uint32_t)blockIdx.z << 31);
+                if (tt) a.tie_list[atomicAdd(a.tie_cnt, 1)] = ncc_entry(pix, blockIdx.z);
             }
         }
     }
@@ -1040,25 +1060,37 @@ __global__ __launch_bounds__(256) void k_ncc_rowgemm(StageArgs a, int mode) {
 // of a tile are its pixels.  Scores, running best, tie flags: exactly k_ncc_rowgemm's epilogue (scaled filter score).
 #define SL_COLS 128
 #define SL_DC 64 // disparity planes per staged chunk (even)
+// dynamic LDS of k_ncc_slide<R>, byte offsets: a region per wave, the merge area behind the four of them
+template <int R>
+struct NccSlideLds {
+    static constexpr int WS = 2 * R + 1;
+    static constexpr int NBC = SL_COLS + SL_DC + 4;       // other-view columns / candidates staged per chunk
+    static constexpr int NV = SL_COLS + 2 * R + 2;        // V line
+    static constexpr size_t RVB = 0;                      // f64 [NBC]: -1: not a candidate, 0: zero variance (score exactly 0)
+    static constexpr size_t B = RVB + (size_t)NBC * 8;    // u32 [WS][NBC]
+    static constexpr size_t SB = B + (size_t)WS * NBC * 4; // i32 [NBC]
+    static constexpr size_t V = SB + (size_t)NBC * 4;     // i32 [2][NV]
+    static constexpr size_t WAVE_BYTES = (V + (size_t)2 * NV * 4 + 15) & ~(size_t)15;
+    static constexpr size_t MV = 4 * WAVE_BYTES;                       // f64 [4][SL_COLS]
+    static constexpr size_t MC = MV + (size_t)4 * SL_COLS * 8;   // i32 [4][SL_COLS]
+    static constexpr size_t MF = MC + (size_t)4 * SL_COLS * 4;   // i32 [4][SL_COLS]: bit 0 exact, bit 1 tie
+    static constexpr size_t BYTES = MF + (size_t)4 * SL_COLS * 4;
+};
 template <int R>
 __global__ __launch_bounds__(256) void k_ncc_slide(StageArgs a, int mode) {
-    constexpr int WS = 2 * R + 1, n = 3 * WS * WS;
-    constexpr int NBC = SL_COLS + SL_DC + 4;         // other-view columns / candidates staged per chunk
-    constexpr int NV = SL_COLS + 2 * R + 2;          // V line
-    constexpr int PXT = SL_COLS - 2 * R;             // pixels of a tile
+    using Lds = NccSlideLds<R>;
+    constexpr int WS = Lds::WS, n = 3 * WS * WS, NBC = Lds::NBC, NV = Lds::NV;
+    constexpr int PXT = SL_COLS - 2 * R; // pixels of a tile
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    // per wave: sB[WS][NBC] u32 | sRvb[NBC] f64 | sSb[NBC] i32 | sV[2][NV] i32
-    constexpr size_t WAVE_BYTES = ((size_t)WS * NBC * 4 + (size_t)NBC * 8 + (size_t)NBC * 4 + (size_t)2 * NV * 4 + 15) & ~(size_t)15;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    uint8_t *wbase = smem + wv * WAVE_BYTES;
-    double *sRvb = (double *)wbase;                              // -1: not a candidate, 0: zero variance (score exactly 0)
-    uint32_t *sB = (uint32_t *)(wbase + (size_t)NBC * 8);
-    int *sSb = (int *)(sB + WS * NBC);
-    int *sV = sSb + NBC;
-    // merge area behind the four wave regions
-    double *mV = (double *)(smem + 4 * WAVE_BYTES); // [4][SL_COLS]
-    int *mC = (int *)(mV + 4 * SL_COLS);            // [4][SL_COLS]
-    int *mF = mC + 4 * SL_COLS;                     // [4][SL_COLS]: bit 0 exact, bit 1 tie
+    uint8_t *wbase = smem + wv * Lds::WAVE_BYTES;
+    double *sRvb = (double *)(wbase + Lds::RVB);
+    uint32_t *sB = (uint32_t *)(wbase + Lds::B);
+    int *sSb = (int *)(wbase + Lds::SB);
+    int *sV = (int *)(wbase + Lds::V);
+    double *mV = (double *)(smem + Lds::MV);
+    int *mC = (int *)(smem + Lds::MC);
+    int *mF = (int *)(smem + Lds::MF);
     const DirArgs &d = a.d[blockIdx.z];
     const int W = a.W;
     const int32_t *rowlist = a.wrow + NCC_WROW_LIST(a.H, 1) + blockIdx.z * (a.H + 1); // [0] = number of rows, then the rows (k_rg_rows)
@@ -1067,7 +1099,7 @@ __global__ __launch_bounds__(256) void k_ncc_slide(StageArgs a, int mode) {
     for (int q = lane; q < 2 * NV; q += 64) sV[q] = 0;
     for (int slot = blockIdx.y; slot < nrows; slot += gridDim.y) { // uniform
         const int y = rowlist[1 + slot];
-        const int wide_from = a.wrow[NCC_WROW_MID(a.H) + blockIdx.z * a.H + y] >= RG_MID_MIN ? a.ncc_mid : NCC_WIDE; // as k_ncc_dot4 chose for this row
+        const int wide_from = ncc_wide_from(true, a.wrow, a.H, blockIdx.z, y, a.ncc_mid);
         // A workgroup owns FOUR consecutive tiles.  How its 4 waves share them depends on the disparity range the tiles
         // span (device data: a pre-pass measures it): up to ~2 chunks of planes per tile every wave takes a tile of its own
         // and walks all its planes (setup and merge amortised over 4 times the work: 257 candidates are 65 planes per
@@ -1078,21 +1110,15 @@ __global__ __launch_bounds__(256) void k_ncc_slide(StageArgs a, int mode) {
 #pragma unroll
             for (int e = 0; e < 2; e++) {
                 const int t = 2 * lane + e, x = ut + t;
-                const bool inside = t >= R && t < SL_COLS - R && x <= d.own.XR;
                 const size_t pix = (size_t)y * W + min(max(x, 0), W - 1);
-                if (!(inside && d.mask_own[pix] == 255)) continue;
-                int L = mode == 0 ? d.oth.XL : (int)d.BL[pix], Rr = mode == 0 ? d.oth.XR : (int)d.BR[pix];
-                L = max(L, R);
-                Rr = min(Rr, W - 1 - R);
-                if (Rr - L + 1 > wide_from) {
-                    dlo = min(dlo, L - x);
-                    dhi = max(dhi, Rr - x);
+                const bool masked = t >= R && t < SL_COLS - R && x <= d.own.XR && d.mask_own[pix] == 255;
+                const NccIv iv = masked ? ncc_wide_only(ncc_interval(mode, d.oth.XL, d.oth.XR, d.BL, d.BR, pix, W, R), wide_from) : ncc_no_interval();
+                if (iv.R >= 0) {
+                    dlo = min(dlo, iv.L - x);
+                    dhi = max(dhi, iv.R - x);
                 }
             }
-            for (int o = 32; o > 0; o >>= 1) {
-                dlo = min(dlo, __shfl_xor(dlo, o));
-                dhi = max(dhi, __shfl_xor(dhi, o));
-            }
+            ncc_wave_minmax(dlo, dhi);
             __syncthreads(); // the previous row is done with s_planes and the merge area
             if (lane == 0) s_planes[wv] = dhi >= dlo ? dhi - dlo + 1 : 0;
             __syncthreads();
@@ -1112,40 +1138,24 @@ __global__ __launch_bounds__(256) void k_ncc_slide(StageArgs a, int mode) {
 #pragma unroll
         for (int e = 0; e < 2; e++) {
             const int t = 2 * lane + e, x = u0 + t;
-            const bool inside = t >= R && t < SL_COLS - R && x <= d.own.XR;
             const size_t pix = (size_t)y * W + min(max(x, 0), W - 1);
-            bool active = inside && d.mask_own[pix] == 255;
-            int L = 0x7fffffff, Rr = -1;
-            if (active) {
-                if (mode == 0) {
-                    L = d.oth.XL; // .cpp:207
-                    Rr = d.oth.XR;
-                } else {
-                    L = d.BL[pix];
-                    Rr = d.BR[pix];
-                }
-                L = max(L, R);
-                Rr = min(Rr, W - 1 - R);
-                if (L > Rr) active = false;
-            }
-            const bool wide = active && (Rr - L + 1 > wide_from); // exactly k_ncc_dot4's test
+            const bool masked = t >= R && t < SL_COLS - R && x <= d.own.XR && d.mask_own[pix] == 255;
+            const NccIv iv = masked ? ncc_wide_only(ncc_interval(mode, d.oth.XL, d.oth.XR, d.BL, d.BR, pix, W, R), wide_from) : ncc_no_interval();
+            const bool wide = iv.R >= 0;
             const double s1 = wide ? (double)d.S1_own[pix] : 0.0;
             const double va = wide ? (double)n * (double)d.S2_own[pix] - s1 * s1 : 0.0;
             Sa[e] = s1;
-            sv[e] = va > 0.0 ? sqrt(va) : -1.0; // -1: zero variance -- every score is exactly 0, the scale is 1
-            Lp[e] = wide ? L : 0x7fffffff;
-            Rp[e] = wide ? Rr : -1;
-            bestv[e] = sv[e] > 0.0 ? -sv[e] : -1.0; // .cpp:205, scaled
+            sv[e] = va > 0.0 ? sqrt(va) : -1.0; // -1: zero variance (ncc_offer_scaled)
+            Lp[e] = iv.L;
+            Rp[e] = iv.R;
+            bestv[e] = ncc_scaled_start(sv[e]);
             bestc[e] = 0x7fffffff;
             if (wide) {
-                dlo = min(dlo, L - x);
-                dhi = max(dhi, Rr - x);
+                dlo = min(dlo, iv.L - x);
+                dhi = max(dhi, iv.R - x);
             }
         }
-        for (int o = 32; o > 0; o >>= 1) {
-            dlo = min(dlo, __shfl_xor(dlo, o));
-            dhi = max(dhi, __shfl_xor(dhi, o));
-        }
+        ncc_wave_minmax(dlo, dhi);
         if (dhi >= dlo) { // uniform over the waves that share the tile
             dlo &= ~1; // even: the sliding reads stay 8-byte aligned
             int span = (dhi - dlo + 1 + nsplit - 1) / nsplit;
@@ -1195,8 +1205,7 @@ __global__ __launch_bounds__(256) void k_ncc_slide(StageArgs a, int mode) {
                         const bool ok = in && col >= R && col <= W - 1 - R && mk_[ii] == 255; // .cpp:209
                         const int Sb = sb_[ii];
                         const double vb = (double)n * (double)s2_[ii] - (double)Sb * (double)Sb;
-                        double r = __builtin_amdgcn_rsq(vb > 0.0 ? vb : 1.0);
-                        r = __builtin_fma(0.5 * r, __builtin_fma(-(vb * r), r, 1.0), r); // one Newton step: ~2e-16 relative
+                        const double r = ncc_rsqrt(vb, vb > 0.0);
                         sSb[i] = Sb;
                         sRvb[i] = !ok ? -1.0 : (vb > 0.0 ? r : 0.0);
                     }
@@ -1259,23 +1268,13 @@ __global__ __launch_bounds__(256) void k_ncc_slide(StageArgs a, int mode) {
                     const double rvv[3] = {rv01.x, rv01.y, rv23.x};
 #pragma unroll
                     for (int e = 0; e < 2; e++) {
-                        const double tol = NCC_TIE_TOL * (sv[e] > 0.0 ? sv[e] : 1.0);
-                        const int Sai = (int)Sa[e];
+                        const double tol = ncc_scaled_tol(sv[e]);
 #pragma unroll
                         for (int pl = 0; pl < 2; pl++) { // ascending candidates
                             const int c = u0 + 2 * lane + e + D + pl;
                             const double rvb = rvv[e + pl];
                             if (rvb < 0.0 || c < Lp[e] || c > Rp[e]) continue;
-                            const int Sb = sbv[e + pl];
-                            (void)Sai;
-                            const double sc = ((double)n * (double)S[pl][e] - Sa[e] * (double)Sb) * rvb; // score * sqrt(va)
-                            const bool exc = rvb == 0.0 || !(sv[e] > 0.0); // a zero-variance window on either side: exactly 0
-                            if (fabs(sc - bestv[e]) <= tol && !(exc && ((exact >> e) & 1u))) tie |= 1u << e;
-                            if (sc > bestv[e]) { // .cpp:213
-                                bestv[e] = sc;
-                                bestc[e] = c;
-                                exact = (exact & ~(1u << e)) | ((unsigned)exc << e);
-                            }
+                            ncc_offer_scaled(bestv[e], bestc[e], exact, tie, e, (double)n, S[pl][e], Sa[e], sv[e], tol, sbv[e + pl], rvb, c);
                         }
                     }
                     sb01 = sb23;
@@ -1298,7 +1297,7 @@ __global__ __launch_bounds__(256) void k_ncc_slide(StageArgs a, int mode) {
             for (int e = 0; e < 2; e++) {
                 if (Rp[e] < 0) continue; // not a wide pixel of this tile
                 const int t = 2 * lane + e, x = u0 + t;
-                const double tol = NCC_TIE_TOL * (sv[e] > 0.0 ? sv[e] : 1.0);
+                const double tol = ncc_scaled_tol(sv[e]);
                 double bv = bestv[e];
                 int bc = bestc[e];
                 bool bx = (exact >> e) & 1u, tt = (tie >> e) & 1u;
@@ -1307,8 +1306,8 @@ __global__ __launch_bounds__(256) void k_ncc_slide(StageArgs a, int mode) {
                     const int oc = mC[w2 * SL_COLS + t], of = mF[w2 * SL_COLS + t];
                     const bool ox = of & 1;
                     tt |= (of >> 1) & 1;
-                    if (bc != 0x7fffffff && oc != 0x7fffffff && fabs(ov - bv) <= tol && !(ox && bx)) tt = true;
-                    if (oc != 0x7fffffff && (ov > bv || (ov == bv && oc < bc))) {
+                    if (ncc_merge_ties(bv, bc, bx, ov, oc, ox, tol)) tt = true;
+                    if (ncc_merge_takes(bv, bc, ov, oc)) {
                         bv = ov;
                         bc = oc;
                         bx = ox;
@@ -1316,25 +1315,17 @@ __global__ __launch_bounds__(256) void k_ncc_slide(StageArgs a, int mode) {
                 }
                 const size_t pix = (size_t)y * W + x;
                 if (bc != 0x7fffffff) d.d16_out[pix] = (int16_t)(bc - x); // .cpp:219-222 / 301-302
-                if (tt) a.tie_list[atomicAdd(a.tie_cnt, 1)] = (uint32_t)pix | ((uint32_t)blockIdx.z << 31);
+                if (tt) a.tie_list[atomicAdd(a.tie_cnt, 1)] = ncc_entry(pix, blockIdx.z);
             }
         }
         } // tile groups
     }
-}
-template <int R>
-static size_t slide_lds_bytes() {
-    constexpr int WS = 2 * R + 1, NBC = SL_COLS + SL_DC + 4, NV = SL_COLS + 2 * R + 2;
-    const size_t wave = ((size_t)WS * NBC * 4 + (size_t)NBC * 8 + (size_t)NBC * 4 + (size_t)2 * NV * 4 + 15) & ~(size_t)15;
-    return 4 * wave + (size_t)4 * SL_COLS * (8 + 4 + 4);
 }
 
 template <int R>
 static void launch_dot4(const StageArgs &a_in, int mode, dim3 grid, hipStream_t st) {
     StageArgs a = a_in;
     if (a.ncc_mid <= 0) a.ncc_mid = R >= 5 ? 64 : (R >= 3 ? 96 : NCC_WIDE); // 11x11 / 65 candidates: 261 against 177 G pairs/s; 5x5 / 65: 372 against 444
-    constexpr int WS = 2 * R + 1, SA = NCC_TX + 2 * R, SB = NCC_CH + 2 * R + NCC_G + 3;
-    const size_t lds = 16 + (size_t)WS * (SA + SB) * 4 + (size_t)(NCC_CH + NCC_G) * 9 + 16;
     if (mode == 2) { // the worklist was filled by launch_set_boundary
         hipLaunchKernelGGL(k_ncc_sparse<R>, dim3(2048), dim3(256), 0, st, a);
         if (!a.opt_no_exact) hipLaunchKernelGGL(k_ncc_exact, dim3(128), dim3(256), 0, st, a, mode);
@@ -1343,8 +1334,8 @@ static void launch_dot4(const StageArgs &a_in, int mode, dim3 grid, hipStream_t 
     // per row: pixels with long intervals and the widest interval (decides, before the matchers run, which rows the row kernels take)
     if (a.opt_no_rowgemm != 1) hipLaunchKernelGGL(k_ncc_rowstat, dim3((grid.y + 3) / 4, 1, grid.z), dim3(256), 0, st, a, mode);
     // *a.ncc_cnt (wide-pixel count) is zero on entry: the caller hands every launch a fresh counter
-    hipLaunchKernelGGL(k_ncc_dot4<R>, grid, dim3(NCC_TX), lds, st, a, mode);
-    const size_t ldsw = (size_t)WS * (NCC_TX * NCC_G + 2 * R + NCC_G) * 4;
+    hipLaunchKernelGGL(k_ncc_dot4<R>, grid, dim3(NCC_TX), NccDot4Lds<R>::BYTES, st, a, mode);
+    constexpr size_t ldsw = NccWideLds<R>::BYTES;
     if (ldsw > 65536) // radii 6 and 7 stage more than the default 64 KB of dynamic LDS per workgroup
         (void)hipFuncSetAttribute((const void *)k_ncc_wide<R>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsw);
     hipLaunchKernelGGL(k_ncc_wide<R>, dim3(8192), dim3(NCC_TX), ldsw, st, a, mode);
@@ -1360,7 +1351,7 @@ static void launch_dot4(const StageArgs &a_in, int mode, dim3 grid, hipStream_t 
         if (kind != 3)
             hipLaunchKernelGGL(k_ncc_rowgemm<R>, dim3((grid.x * NCC_TX + RG_PX - 1) / RG_PX, min((int)grid.y, RG_SLOTS), grid.z), dim3(256), 0, st, a, mode);
         if (kind != 2) {
-            const size_t lds_s = slide_lds_bytes<R>();
+            constexpr size_t lds_s = NccSlideLds<R>::BYTES;
             if (lds_s > 65536) // the attribute is per DEVICE: set on every launch, as for k_ncc_wide (contexts may live on several GPUs)
                 (void)hipFuncSetAttribute((const void *)k_ncc_slide<R>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s);
             const int tiles = (grid.x * NCC_TX + (SL_COLS - 2 * R) - 1) / (SL_COLS - 2 * R);
