@@ -16,8 +16,11 @@ from __future__ import annotations
 import numpy as np
 
 
-def plane_from_cov(cov):
-    """PCL's eigen33 (smallest eigenvalue, its unit vector) + curvature |lambda / trace| on a batch [B,3,3] of covariances."""
+def plane_from_cov(cov, census=None):
+    """PCL's eigen33 (smallest eigenvalue, its unit vector) + curvature |lambda / trace| on a batch [B,3,3] of covariances.
+    census (a dict, optional) receives the branch each covariance took: c0_small (computeRoots2 because |c0| < eps), fallback (the
+    trigonometric roots with r0 <= 0, then computeRoots2), r0 (the smallest trigonometric root), pick (1, 2, 3: which cross product
+    won) and tie (won on an equal length)."""
     cov = np.asarray(cov, np.float64)
     B = len(cov)
     c = cov.reshape(B, 9)
@@ -68,6 +71,10 @@ def plane_from_cov(cov):
         v = np.where(pick1[:, None], v1, np.where(pick2[:, None], v2, v3))
         l = np.where(pick1, l1, np.where(pick2, l2, l3))
         n = v / np.sqrt(l)[:, None]
+        if census is not None:
+            c0_small = np.abs(c0) < 2.220446049250313e-16
+            census.update(c0_small=c0_small, fallback=~c0_small & (r0 <= 0.0), r0=r0, pick=np.where(pick1, 1, np.where(pick2, 2, 3)),
+                          tie=(pick1 & ((l1 == l2) | (l1 == l3))) | (pick2 & (l2 == l3)))
         tr = cov[:, 0, 0] + cov[:, 1, 1] + cov[:, 2, 2]
         curv = np.where(tr != 0.0, np.abs(ev / tr), 0.0)
     return n, curv
@@ -136,11 +143,13 @@ def _terms(uc, vc, order):
     return np.stack(out, -1)
 
 
-def mls(xyz, radius, orders=(1,), ref_normals=None, queries=None, block=256):
+def mls(xyz, radius, orders=(1,), ref_normals=None, queries=None, block=256, census=None):
     """The MLS output of the queried input points (default: all) for each polynomial order in `orders`.
 
     Returns {order: (emit bool [q], xyz float32 [q,3], normals float32 [q,4] = nx, ny, nz, curvature)} for the queries in the
-    order given (their input indices); rows where emit is False carry nothing.  ref_normals ([n,>=3]): the flip of :378-385."""
+    order given (their input indices); rows where emit is False carry nothing.  ref_normals ([n,>=3]): the flip of :378-385.
+    census (a dict, optional) receives per query: cnt, plane_from_cov's branches, uo_form (1, 2: unitOrthogonal's form) and, per order
+    o > 0, ("pivots_ok", o) (every Cholesky pivot positive) and ("c0_finite", o)."""
     xyz = np.asarray(xyz, np.float32).reshape(-1, 3)
     n_all = len(xyz)
     q_idx = np.arange(n_all) if queries is None else np.asarray(queries, np.int64).ravel()
@@ -190,7 +199,11 @@ def mls(xyz, radius, orders=(1,), ref_normals=None, queries=None, block=256):
             cen = (Mf @ C64) / cnt[:, None]
             D = C64[None] - cen[:, None]
             cov = np.matmul((D * Mf[..., None]).transpose(0, 2, 1), D)
-            nrm, curv = plane_from_cov(cov)
+            cen_b = None if census is None else {}
+            nrm, curv = plane_from_cov(cov, cen_b)
+            if census is not None:
+                cen_b["cnt"] = cnt
+                cen_b["uo_form"] = np.where((np.abs(nrm[:, 0]) > np.abs(nrm[:, 2]) * 1e-12) | (np.abs(nrm[:, 1]) > np.abs(nrm[:, 2]) * 1e-12), 1, 2)
             dd = -_dot3(nrm, cen)
             p64 = Q.astype(np.float64)
             dist = ((p64[:, 0] * nrm[:, 0] + p64[:, 1] * nrm[:, 1]) + p64[:, 2] * nrm[:, 2]) + dd
@@ -212,6 +225,8 @@ def mls(xyz, radius, orders=(1,), ref_normals=None, queries=None, block=256):
                     bb = np.matmul(PW, f[..., None])[..., 0]
                     c, ok = _llt_solve(A, bb)
                     fit = (cnt >= nc) & ok & np.isfinite(c[:, 0])
+                    if census is not None:
+                        cen_b[("pivots_ok", o)], cen_b[("c0_finite", o)] = ok, np.isfinite(c[:, 0])
                     pto = np.where(fit[:, None], pt + c[:, :1] * nrm, pt)
                     no = np.where(fit[:, None], nrm - (c[:, o + 1:o + 2] * u + c[:, 1:2] * v), nrm)
             fn = no.astype(np.float32)
@@ -224,6 +239,9 @@ def mls(xyz, radius, orders=(1,), ref_normals=None, queries=None, block=256):
             x_[rows] = np.where(emit[:, None], pto.astype(np.float32), np.nan)
             n_[rows, :3] = np.where(emit[:, None], fn, np.nan)
             n_[rows, 3] = np.where(emit, curv.astype(np.float32), np.nan)
+        if census is not None:
+            for k, val in cen_b.items():
+                census.setdefault(k, np.zeros(len(q_idx), np.asarray(val).dtype))[rows] = val
     return res
 
 
