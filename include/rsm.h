@@ -245,6 +245,17 @@ int rsm_gather_plan(int rank, int world, int root, int n_local, const int *pair_
  *                          holds its current key and the neighbour key on the side the state is nearest to, so the early launches
  *                          miss at the settled rate.  "refine_rekey_side" = 1 installs the other neighbour instead (tests: a wrong
  *                          prediction costs misses, never bits)
+ *   "refine_tile_T" / "refine_tile_from" / "refine_tile_min_px"   the levels BELOW refine_skew_min_px (bound by launch latency:
+ *                          a sweep there is a few microseconds of work): T (2..8, default 4; 0 = off, one launch per sweep)
+ *                          sweeps per launch on overlapped tiles (k_refine_tile: a workgroup stages a 32 x 16 tile grown by T
+ *                          pixels and sweeps it T times in LDS) from that sweep of a level on (default 4), at levels with at least
+ *                          min_px margin pixels per direction (default 0); the launches that start before "refine_rekey_until" are
+ *                          preceded by the re-key pass, leftover sweeps run one per launch
+ *   "refine_skew_waves_low"   the workgroups a time-skewed launch aims at on the levels below the top while other contexts of
+ *                          the device are inside rsm_run_pair (default 640: C2's level 3 then runs 83-row chunks instead of 20-row
+ *                          ones, fewer recomputed halo rows; a pair alone keeps "refine_skew_waves_alone"); 0 = the top level's aim
+ *   "refine_upd_cap"       n > 0: a shard of the sweep kernels' cache-update list holds at most n records (tests: a full list
+ *                          drops records, which costs later cache misses and never bits); 0 (default) = what was allocated
  *   "refine_skew_uw"       columns a strip of that kernel owns: 0 (default) = 66 - 2T, all that its last sweep can compute from 64
  *                          lanes; an even number below that (e.g. 56: every strip starts on a 128-byte line of the cache ways) for A/B
  *   "refine_skew_waves_alone"  the workgroups a time-skewed launch aims at while no other context of the device is inside

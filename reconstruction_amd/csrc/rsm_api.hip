@@ -389,6 +389,13 @@ extern "C" int rsm_set_option(rsm_ctx *c, const char *name, long long value) {
     else if (!strcmp(name, "meshcolor_big_box")) c->opt_meshcolor_big_box = std::max(1LL, std::min(value, 1LL << 20));
     else if (!strcmp(name, "refine_skew_waves_alone")) c->opt_refine_skew_waves_alone = (int)std::max(0LL, std::min(value, 1000000LL));
     else if (!strcmp(name, "refine_skew_rows")) c->opt_refine_skew_rows = (int)std::max(0LL, std::min(value, 1000000LL));
+    else if (!strcmp(name, "refine_tile_T")) {
+        if (value != 0 && (value < 2 || value > RF_TILE_MAXT)) return set_err(c, RSM_E_INVALID, "refine_tile_T %lld: 0 (off) or 2 .. %d", value, RF_TILE_MAXT);
+        c->opt_refine_tile_T = (int)value;
+    } else if (!strcmp(name, "refine_tile_from")) c->opt_refine_tile_from = (int)std::max(1LL, std::min(value, 100000LL));
+    else if (!strcmp(name, "refine_tile_min_px")) c->opt_refine_tile_min_px = (int)std::max(0LL, std::min(value, 2000000000LL));
+    else if (!strcmp(name, "refine_skew_waves_low")) c->opt_refine_skew_waves_low = (int)std::max(0LL, std::min(value, 1000000LL));
+    else if (!strcmp(name, "refine_upd_cap")) c->opt_refine_upd_cap = (int)std::max(0LL, std::min(value, 1LL << 30));
     else if (!strcmp(name, "cu_share")) {
         // Contexts that share a GPU each on their own share of the compute units (the `ordinal % n`-th of n equal ranges of the
         // CU mask, hipExtStreamCreateWithCUMask) instead of all of them on the whole chip; 0 / 1 = the whole chip.
@@ -525,9 +532,9 @@ static int refine_sweeps(rsm_ctx *c, StageArgs &a, double *const bufA[2], double
     };
     int nlaunch = 0;
     bool split_now = false; // inside a time-skewed section whose two directions run on two streams (below)
-    auto launch = [&](int t, int skewT) { // sweeps t .. t + max(skewT, 1) - 1; skewT > 0: one k_refine_skew launch
+    auto launch = [&](int t, int skewT, int tileT = 0) { // sweeps t .. t + max(skewT, tileT, 1) - 1; skewT > 0: one k_refine_skew launch, tileT > 0: one k_refine_tile launch
         bind(t);
-        const bool timed = c && c->profile && top && (nlaunch++ & 7) == 4;
+        const bool timed = c && c->profile && top && !tileT && (nlaunch++ & 7) == 4;
         hipEvent_t e0 = nullptr, e1 = nullptr;
         if (timed) { // every 8th sweep launch of the top level
             const int stg = skewT ? ST_REFINE_SKEW_TOP : ST_REFINE_LIGHT_TOP;
@@ -539,7 +546,7 @@ static int refine_sweeps(rsm_ctx *c, StageArgs &a, double *const bufA[2], double
         }
         // an early time-skewed launch: k_refine_rekey first sets both cache ways for the state it starts from (the previous
         // launch's cache updates are in: k_refine_apply runs behind every skewed launch on the same stream)
-        const bool rekey = skewT && t < c->opt_refine_rekey_until;
+        const bool rekey = (skewT || tileT) && t < c->opt_refine_rekey_until;
         if (skewT && split_now) { // the two directions as two launch chains: one's tail runs beside the other's head
             StageArgs a0 = a, a1 = a;
             a0.ndir = a1.ndir = 1;
@@ -561,9 +568,16 @@ static int refine_sweeps(rsm_ctx *c, StageArgs &a, double *const bufA[2], double
                 launch_refine_rekey(r, st);
             }
             launch_refine_skew(a, skewT, st, e0, e1);
+        } else if (tileT) {
+            if (rekey) {
+                StageArgs r = a;
+                r.flag3 = c->opt_refine_rekey_side;
+                launch_refine_rekey(r, st);
+            }
+            launch_refine_tile(a, tileT, st);
         }
         else launch_refine_sweep(a, st, e0, e1);
-        launches += skewT ? skewT : 1;
+        launches += skewT ? skewT : (tileT ? tileT : 1);
         curB = !curB;
     };
     *final_in_B = false;
@@ -579,8 +593,12 @@ static int refine_sweeps(rsm_ctx *c, StageArgs &a, double *const bufA[2], double
     // settled sweeps of the large levels T per launch, time-skewed (k_refine_skew)
     const bool skew = c && c->opt_refine_skew_from > 0 && a.upd_list && px / a.ndir >= c->opt_refine_skew_min_px && refine_skew_fits(a);
     const int skewT = skew ? c->opt_refine_skew_T : 0;
+    // the levels below that: T sweeps per launch on overlapped tiles (k_refine_tile) -- they are bound by launch latency
+    const bool tile = c && c->opt_refine_tile_T >= 2 && a.upd_list && px / a.ndir < c->opt_refine_skew_min_px && px / a.ndir >= c->opt_refine_tile_min_px;
+    const int tileT = tile ? c->opt_refine_tile_T : 0;
+    if (c && c->opt_refine_upd_cap > 0) a.upd_cap = std::min(a.upd_cap, c->opt_refine_upd_cap);
+    if (skew || tile) (void)hipMemsetAsync(a.upd_cnt, 0, sizeof(int32_t) * 2 * RF_UPD_SHARDS, st);
     if (skew) {
-        (void)hipMemsetAsync(a.upd_cnt, 0, sizeof(int32_t) * 2 * RF_UPD_SHARDS, st);
         a.skew_prio = c->opt_refine_skew_prio;
         a.skew_uw = (c->opt_refine_skew_uw > 0 && c->opt_refine_skew_uw <= 66 - 2 * skewT) ? c->opt_refine_skew_uw : 66 - 2 * skewT;
         int rows = 1, strips = 0;
@@ -592,7 +610,9 @@ static int refine_sweeps(rsm_ctx *c, StageArgs &a, double *const bufA[2], double
         // waves per SIMD that nothing else fills, and a second round of workgroups shortens it; with pairs in flight the other
         // pairs' kernels fill the tail and the extra pipeline fill only costs.
         const bool lone = c->device < RSM_MAX_DEVICES && !c->shared_now() && g_running[c->device].load() == 1 && c->opt_refine_skew_waves_alone > 0;
-        const int waves = lone ? c->opt_refine_skew_waves_alone : c->opt_refine_skew_waves;
+        // Below the top level, with pairs in flight, the aim has a value of its own (refine_skew_waves_low): there the launch's
+        // own time matters less than the work it costs the other pairs' kernels, and taller chunks recompute fewer halo rows.
+        const int waves = lone ? c->opt_refine_skew_waves_alone : ((!top && c->opt_refine_skew_waves_low > 0) ? c->opt_refine_skew_waves_low : c->opt_refine_skew_waves);
         const int chunks = std::max(1, waves / std::max(1, strips));
         a.skew_rows = c->opt_refine_skew_rows > 0 ? c->opt_refine_skew_rows : std::max(4 * skewT, (rows + chunks - 1) / chunks);
     }
@@ -634,6 +654,10 @@ static int refine_sweeps(rsm_ctx *c, StageArgs &a, double *const bufA[2], double
             a.flag3 = nskew++;
             launch(t, skewT);
             t += skewT;
+        } else if (tile && t >= c->opt_refine_tile_from && t + tileT <= iters) {
+            a.flag3 = nskew++; // (a level runs one of the two kernels: the launch index picks the update list's counter set)
+            launch(t, 0, tileT);
+            t += tileT;
         } else {
             launch(t, 0);
             t += 1;

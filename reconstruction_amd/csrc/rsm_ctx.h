@@ -145,9 +145,15 @@ struct rsm_ctx {
     int opt_refine_skew_waves = 2560;    // workgroups a time-skewed launch aims at (sets the rows per chunk): 5 per CU are resident, so two rounds --
                                          // workgroups at different points of their chunks share a CU better than 1 280 in lockstep (measured: 0.28 against 0.34 ms)
     int opt_refine_skew_waves_alone = 3840; // ... when no other context of the device is inside rsm_run_pair (0: the same)
+    int opt_refine_skew_waves_low = 640; // ... at the levels below the top while other contexts are inside rsm_run_pair (0: the same as the top's): taller chunks
+                                         // recompute fewer halo rows, which is what the other pairs' kernels pay for (C2 in flight: 386 -> 394 Mdisp/s)
     int opt_refine_skew_rows = 0;        // > 0: rows per chunk, overrides refine_skew_waves (tests)
     int opt_refine_skew_prio = 0;        // the time-skewed kernel's waves rotate their issue priority every 2^this shader clocks (0: never)
     int opt_refine_skew_uw = 0;          // columns a strip owns; 0: 66 - 2T, all its last level can compute (an even number <= that: A/B)
+    int opt_refine_tile_T = 4;           // sweeps per launch of the tile kernel (k_refine_tile; 2..RF_TILE_MAXT, 0: off) at the levels below refine_skew_min_px
+    int opt_refine_tile_from = 4;        // ... from this sweep of a level on (k_refine_rekey in front of the launches before refine_rekey_until)
+    int opt_refine_tile_min_px = 0;      // ... at levels with at least this many margin pixels per direction
+    int opt_refine_upd_cap = 0;          // > 0: the update list's shards hold at most this many records (tests: overflow costs misses, never bits)
 
     // what the last rsm_stage_initial_match's NCC launch decided (rsm_stage_last_ncc_routes): its per-row counters and row
     // lists (StageArgs::wrow, rsm_dev.h), the worklist length and the tie count; H = 0 until such a call succeeded

@@ -11,6 +11,7 @@
 #define RF_NOKEY ((int16_t)-32768)
 #define RF_NOKEY2 0x80008000u // both ways of DirArgs::rf_key empty
 #define RF_PPT 4      // pixels per thread of the refine sweep kernel
+#define RF_TILE_MAXT 8 // sweeps per launch of the tile kernel (k_refine_tile), at most
 #define SBV_S 32 // SetBoundary: row segments per column of the vertical sweeps
 // int32 scratch of launch_set_boundary (in rf_list), per direction
 #define SETB_SCRATCH(W) ((size_t)(SBV_S * 6 + 2) * (size_t)(W))
@@ -123,6 +124,8 @@ void launch_refine_sweep(const StageArgs &a, hipStream_t st, hipEvent_t ev0 = nu
 void launch_refine_apply(const StageArgs &a, hipStream_t st); // k_refine.hip
 void launch_refine_rekey(const StageArgs &a, hipStream_t st); // k_refine.hip: both cache ways for the state a.d[].f64_a (k_refine_rekey)
 void launch_refine_skew(const StageArgs &a, int T, hipStream_t st, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr); // k_refine_skew.hip
+// T (2..RF_TILE_MAXT) sweeps f64_a -> f64_b in one launch on overlapped tiles (a.flag3 = launch index) + the cache-update launch
+void launch_refine_tile(const StageArgs &a, int T, hipStream_t st); // k_refine_tile.hip
 int refine_skew_strips(const Mg &m, int T, int uw); // strips of 64 lanes a direction's interior takes (k_refine_skew.hip)
 bool refine_skew_fits(const StageArgs &a);          // the kernel's flat over-reads stay inside the level
 
