@@ -120,8 +120,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     const double dC = in[pix];
     if (dC == (double)NOMATCH) return;
     const double dE = in[pix + 1], dW = in[pix - 1], dN = in[pix - W], dS = in[pix + W];
-    const int mode = (int)(dE != (double)NOMATCH && dW != (double)NOMATCH) +
-                     (int)(dS != (double)NOMATCH && dN != (double)NOMATCH) * 2;
+    const int mode = refine_mode(dE, dW, dN, dS);
     if (mode == 0) {
         d.f64_b[pix] = dC;
         return;
@@ -145,7 +144,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     // (tests/tools/analyze_keys.py), the next iMatch a pixel needs is the neighbour in that direction for > 99.9 % of the
     // pixels -- in the sweep kernels each of them would be a cache miss (C2's top level: 4.8 M in the third sweep alone).
     // The neighbour's data term shares two of its three matching costs with this one: one more right window.
-    if (a.flag3 & 2) return; // option refine_prefill = 0 (A/B)
+    if (a.rf_no_prefill) return; // option refine_prefill = 0 (A/B)
     const int rel0 = key - x, rel1 = (int)(val - 1.5);
     const int rel2 = rel1 != rel0 ? rel1 : (val > dC ? rel0 + 1 : (val < dC ? rel0 - 1 : rel0));
     if (rel2 == rel0 + 1 || rel2 == rel0 - 1) {
@@ -213,7 +212,7 @@ __global__ __launch_bounds__(256) void k_refine_sweep(StageArgs a) {
         const int yy = min(y0 + i, ylast);
         rel[i] = (int)(col[i + 1] - 1.5); // .cpp:625 (iMatch - x)
         const double2 e = d.rf_ent[(size_t)yy * W + xs + (size_t)(rel[i] & 1) * a.rf_stride]; // the way the state selects
-        crel[i] = (int)(int16_t)(kk[i] >> ((rel[i] & 1) << 4));
+        crel[i] = rf_key_get(kk[i], rel[i]);
         pwp[i] = e.x;
         delta[i] = e.y;
     }
@@ -226,48 +225,20 @@ __global__ __launch_bounds__(256) void k_refine_sweep(StageArgs a) {
     for (int i = 0; i < RF_PPT; i++) {
         const double dC = col[i + 1], dN = col[i], dS = col[i + 2];
         const bool lv = colok && (y0 + i <= ylast) && dC != (double)NOMATCH; // .cpp:613
-        mode[i] = (int)(dE[i] != (double)NOMATCH && dW[i] != (double)NOMATCH) +
-                  (int)(dS != (double)NOMATCH && dN != (double)NOMATCH) * 2; // .cpp:620
+        mode[i] = refine_mode(dE[i], dW[i], dN, dS);
         const bool ms = lv && mode[i] != 0 && crel[i] != rel[i];
         const unsigned long long mm = __ballot(ms);
         pos[i] = n + __popcll(mm & ((1ull << lane) - 1ull));
-        if (ms) s_list[wid][pos[i]] = (uint32_t)(lane * RF_PPT + i) | ((uint32_t)(rel[i] & 0xffff) << 16);
+        if (ms) s_list[wid][pos[i]] = rf_miss_entry(lane * RF_PPT + i, rel[i]);
         n += __popcll(mm);
         live |= (unsigned)lv << i;
         miss |= (unsigned)ms << i;
     }
-    if (n) { // wave-uniform
-        __builtin_amdgcn_wave_barrier();
-        for (int done = 0; done < n;) { // uniform
-            if (n - done > 16) { // a lane per entry: one round serves up to 64 with 1/3 of the quads' instructions
-                const int e = done + lane;
-                if (e < n) {
-                    const uint32_t en = s_list[wid][e];
-                    const int slot = en & 0xffff, r = (int)(int16_t)(en >> 16);
-                    const int ex = xw0 + slot / RF_PPT, ey = y0 + slot % RF_PPT;
-                    double p, q;
-                    refine_data_term_packed(d.img4_own, d.img4_oth, W, H, ex, ey, r + ex, p, q);
-                    s_res[wid][e][0] = p;
-                    s_res[wid][e][1] = q;
-                }
-                done += 64;
-            } else { // four lanes per entry: a third of the latency, which is what a handful of misses costs
-                const int e = done + (lane >> 2);
-                const bool ok = e < n;
-                const uint32_t en = s_list[wid][ok ? e : done];
-                const int slot = en & 0xffff, r = (int)(int16_t)(en >> 16);
-                const int ex = xw0 + slot / RF_PPT, ey = y0 + slot % RF_PPT;
-                double p, q;
-                refine_data_term_quad(d.img4_own, d.img4_oth, W, H, ex, ey, r + ex, lane & 3, p, q);
-                if (ok && (lane & 3) == 0) {
-                    s_res[wid][e][0] = p;
-                    s_res[wid][e][1] = q;
-                }
-                done += 16;
-            }
-        }
-        __builtin_amdgcn_wave_barrier();
-    }
+    if (n) // wave-uniform
+        rf_serve_misses(
+            s_list[wid], n, lane, &d, W, H,
+            [&](uint32_t en, int &ex, int &ey, int &r) { ex = xw0 + rf_miss_slot(en) / RF_PPT, ey = y0 + rf_miss_slot(en) % RF_PPT, r = rf_miss_rel(en); },
+            [&](int e, int, int, int, double p, double q) { s_res[wid][e][0] = p, s_res[wid][e][1] = q; });
 #pragma unroll
     for (int i = 0; i < RF_PPT; i++) {
         if (!((live >> i) & 1u)) continue;
@@ -284,12 +255,11 @@ __global__ __launch_bounds__(256) void k_refine_sweep(StageArgs a) {
 
 // Re-key (before an early time-skewed launch, after k_refine_apply): for every live interior pixel of the current state f64_a
 // the way of its key k = iMatch - x = int(d - 1.5) holds k, and the other way holds the neighbour key on the side of k's interval
-// the state is nearest to (a.flag3 = 1: the other side -- a deliberately wrong prediction, tests only).  k + 1 and k - 1 share a
+// the state is nearest to (a.rf_rekey_far: the other side -- a deliberately wrong prediction, tests only).  k + 1 and k - 1 share a
 // way, so only one of them can be resident; what the early sweeps need next is the near one (tests/tools/simulate_rekey.py:
 // the rare-row fraction of a T = 4 launch from sweep 4 drops from 0.80 to 0.01).  Nothing but exact data terms is written, so
 // the sweeps' results do not depend on it.  The entries to compute are compacted per wave through an LDS list over RK_PPT rows
-// and served a lane each while the list is long, four lanes each for the last 16 or fewer (as k_refine_sweep serves misses):
-// a few scattered entries do not run the data-term routine in every wave.
+// and served by rf_serve_misses: a few scattered entries do not run the data-term routine in every wave.
 #define RK_PPT 8                // vertically adjacent pixels per thread
 #define RKW_CAP (2 * 64 * RK_PPT) // both ways of every pixel of a wave
 __global__ __launch_bounds__(256) void k_refine_rekey(StageArgs a) {
@@ -302,7 +272,7 @@ __global__ __launch_bounds__(256) void k_refine_rekey(StageArgs a) {
     if (y0 > ylast) return; // uniform
     const bool colok = x <= d.own.XR - 1;
     const int xs = colok ? x : d.own.XL + 1;
-    const bool wrong = a.flag3 == 1;
+    const bool wrong = a.rf_rekey_far != 0;
     double dc[RK_PPT];
     uint32_t kk[RK_PPT];
 #pragma unroll
@@ -322,59 +292,34 @@ __global__ __launch_bounds__(256) void k_refine_rekey(StageArgs a) {
         const int rel = (int)v; // .cpp:625 (iMatch - x)
         const double centre = rel > 0 ? rel + 0.5 : (rel < 0 ? rel - 0.5 : 0.0); // (int() truncates: key 0's interval is (-1, 1))
         const int nb = ((v > centre) != wrong) ? rel + 1 : rel - 1;
-        const bool n0 = lv && (int)(int16_t)(kk[i] >> ((rel & 1) << 4)) != rel;
-        const bool n1 = lv && (int)(int16_t)(kk[i] >> ((nb & 1) << 4)) != nb;
-        const uint32_t slot = (uint32_t)(lane * RK_PPT + i);
+        const bool n0 = lv && rf_key_get(kk[i], rel) != rel;
+        const bool n1 = lv && rf_key_get(kk[i], nb) != nb;
+        const int slot = lane * RK_PPT + i;
         const unsigned long long m0 = __ballot(n0);
-        if (n0) s_list[wid][n + __popcll(m0 & below)] = slot | ((uint32_t)(rel & 0xffff) << 16);
+        if (n0) s_list[wid][n + __popcll(m0 & below)] = rf_miss_entry(slot, rel);
         n += __popcll(m0);
         const unsigned long long m1 = __ballot(n1);
-        if (n1) s_list[wid][n + __popcll(m1 & below)] = slot | ((uint32_t)(nb & 0xffff) << 16);
+        if (n1) s_list[wid][n + __popcll(m1 & below)] = rf_miss_entry(slot, nb);
         n += __popcll(m1);
     }
     if (!n) return; // wave-uniform; no workgroup barrier follows
-    __builtin_amdgcn_wave_barrier();
-    for (int done = 0; done < n;) { // uniform
-        if (n - done > 16) { // a lane per entry
-            const int e = done + lane;
-            if (e < n) {
-                const uint32_t en = s_list[wid][e];
-                const int slot = en & 0xffff, r = (int)(int16_t)(en >> 16);
-                const int ex = xw0 + slot / RK_PPT, ey = y0 + slot % RK_PPT;
-                double p, q;
-                refine_data_term_packed(d.img4_own, d.img4_oth, W, H, ex, ey, r + ex, p, q);
-                rf_store(d, a.rf_stride, (size_t)ey * W + ex, r, p, q);
-            }
-            done += 64;
-        } else { // four lanes per entry
-            const int e = done + (lane >> 2);
-            const bool ok = e < n;
-            const uint32_t en = s_list[wid][ok ? e : done];
-            const int slot = en & 0xffff, r = (int)(int16_t)(en >> 16);
-            const int ex = xw0 + slot / RK_PPT, ey = y0 + slot % RK_PPT;
-            double p, q;
-            refine_data_term_quad(d.img4_own, d.img4_oth, W, H, ex, ey, r + ex, lane & 3, p, q);
-            if (ok && (lane & 3) == 0) rf_store(d, a.rf_stride, (size_t)ey * W + ex, r, p, q);
-            done += 16;
-        }
-    }
+    rf_serve_misses(
+        s_list[wid], n, lane, &d, W, H,
+        [&](uint32_t en, int &ex, int &ey, int &r) { ex = xw0 + rf_miss_slot(en) / RK_PPT, ey = y0 + rf_miss_slot(en) % RK_PPT, r = rf_miss_rel(en); },
+        [&](int, int r, int ex, int ey, double p, double q) { rf_store(d, a.rf_stride, (size_t)ey * W + ex, r, p, q); });
 }
 
-// the re-key pass over the interior of the current state a.d[].f64_a (a.flag3 = 1: the mispredicting side, tests)
+// the re-key pass over the interior of the current state a.d[].f64_a (a.rf_rekey_far: the mispredicting side, tests)
 void launch_refine_rekey(const StageArgs &a, hipStream_t st) {
-    int rows = 0, cols = 0;
-    for (int v = 0; v < a.ndir; v++) {
-        rows = max(rows, a.d[v].own.YR - a.d[v].own.YL - 1);
-        cols = max(cols, a.d[v].own.XR - a.d[v].own.XL - 1);
-    }
-    if (rows <= 0 || cols <= 0) return;
+    int rows, cols;
+    if (!refine_interior(a, rows, cols)) return;
     hipLaunchKernelGGL(k_refine_rekey, dim3((cols + 255) / 256, (rows + RK_PPT - 1) / RK_PPT, a.ndir), dim3(256), 0, st, a);
 }
 
-// scatters the update list of the k_refine_skew launch a.flag3 into the cache and clears the other counter set
+// scatters the update list of the k_refine_skew / k_refine_tile launch a.rf_launch into the cache and clears the other counter set
 __global__ __launch_bounds__(256) void k_refine_apply(StageArgs a) {
-    const int32_t *cnt = a.upd_cnt + (a.flag3 & 1) * RF_UPD_SHARDS;
-    if (blockIdx.x == 0 && threadIdx.x < RF_UPD_SHARDS) a.upd_cnt[((a.flag3 + 1) & 1) * RF_UPD_SHARDS + threadIdx.x] = 0;
+    const int32_t *cnt = rf_upd_counters(a, a.rf_launch);
+    if (blockIdx.x == 0 && threadIdx.x < RF_UPD_SHARDS) rf_upd_counters(a, a.rf_launch + 1)[threadIdx.x] = 0;
     for (int sh = blockIdx.y; sh < RF_UPD_SHARDS; sh += gridDim.y) {
         const int n = min(cnt[sh], a.upd_cap);
         for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
@@ -388,23 +333,20 @@ __global__ __launch_bounds__(256) void k_refine_apply(StageArgs a) {
 // scatters a time-skewed launch's update list into the cache
 void launch_refine_apply(const StageArgs &a, hipStream_t st) { hipLaunchKernelGGL(k_refine_apply, dim3(8, RF_UPD_SHARDS), dim3(256), 0, st, a); }
 
-// One sweep f64_a -> f64_b over the interior (a.flag2 = sweep index: 0 = k_refine_first; a.flag = top level); ev0 / ev1 (optional)
-// bracket the launch.
+// The first sweep of a level f64_a -> f64_b: every pixel of the interior needs its data term (a.rf_no_prefill: own way only).
+void launch_refine_first(const StageArgs &a, hipStream_t st) {
+    int rows, cols;
+    if (!refine_interior(a, rows, cols)) return;
+    hipLaunchKernelGGL(k_refine_first, dim3((cols + 255) / 256, rows, a.ndir), dim3(256), 0, st, a);
+}
+
+// One later sweep f64_a -> f64_b over the interior (a.flag = top level); ev0 / ev1 (optional) bracket the launch.
 void launch_refine_sweep(const StageArgs &a, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
-    int rows = 0, cols = 0;
-    for (int v = 0; v < a.ndir; v++) {
-        rows = max(rows, a.d[v].own.YR - a.d[v].own.YL - 1);
-        cols = max(cols, a.d[v].own.XR - a.d[v].own.XL - 1);
-    }
-    if (rows <= 0 || cols <= 0) return;
-    const dim3 grid((cols + 255) / 256, rows, a.ndir);
+    int rows, cols;
+    if (!refine_interior(a, rows, cols)) return;
+    const dim3 grid((cols + 255) / 256, (rows + RF_PPT - 1) / RF_PPT, a.ndir);
     if (ev0) (void)hipEventRecord(ev0, st);
-    if (a.flag2 == 0) { // first sweep: every pixel needs its data term
-        hipLaunchKernelGGL(k_refine_first, grid, dim3(256), 0, st, a);
-    } else {
-        const dim3 sgrid(grid.x, (grid.y + RF_PPT - 1) / RF_PPT, grid.z);
-        if (a.flag) hipLaunchKernelGGL(k_refine_sweep<1>, sgrid, dim3(256), 0, st, a);
-        else hipLaunchKernelGGL(k_refine_sweep<0>, sgrid, dim3(256), 0, st, a);
-    }
+    if (a.flag) hipLaunchKernelGGL(k_refine_sweep<1>, grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(k_refine_sweep<0>, grid, dim3(256), 0, st, a);
     if (ev1) (void)hipEventRecord(ev1, st);
 }

@@ -63,7 +63,7 @@ struct SkewRare {
     uint32_t rdC, rdN, rdS; // LDS offsets of lane 0's dC / dN / dS
     uint32_t wr;           // LDS offset of lane 0's result slot (levels below T)
     uint32_t ent, key, emit, ml, tab; // LDS offsets: the row's entries [2][64], keys [64], emit masks [2], this wave's list, the exp table
-    uint32_t dir;          // direction << 31
+    uint32_t dir;          // the direction
     int owned_row;         // the row is one this workgroup owns (its new entries go to the update list)
 };
 
@@ -74,15 +74,14 @@ struct SkewRare {
 __device__ __forceinline__ void skew_rare_row(SkewRare q, u64 m_redo, u64 m_own) {
     const int lane = (int)__lane_id();
     char *L = q.lds;
-    const double NM = (double)NOMATCH;
     const double dC = *(const double *)(L + q.rdC + lane * 8), dW = *(const double *)(L + q.rdC + lane * 8 - 8), dE = *(const double *)(L + q.rdC + lane * 8 + 8);
     const double dN = *(const double *)(L + q.rdN + lane * 8), dS = *(const double *)(L + q.rdS + lane * 8);
     uint32_t kk = *(const uint32_t *)(L + q.key + lane * 4);
     const bool lv = (m_redo >> lane) & 1ull;
-    const int mode = (int)(dE != NM && dW != NM) + (int)(dS != NM && dN != NM) * 2; // .cpp:620
-    const int rel = (int)(dC - 1.5);                                                 // .cpp:625 (iMatch - x)
+    const int mode = refine_mode(dE, dW, dN, dS);
+    const int rel = (int)(dC - 1.5); // .cpp:625 (iMatch - x)
     const int way = rel & 1;
-    const bool miss = lv && mode != 0 && (int)(int16_t)(kk >> (way << 4)) != rel;
+    const bool miss = lv && mode != 0 && rf_key_get(kk, rel) != rel;
     double2 *ent = (double2 *)(L + q.ent);
     const u64 mm = __ballot(miss);
     if (mm) { // wave-uniform
@@ -106,8 +105,7 @@ __device__ __forceinline__ void skew_rare_row(SkewRare q, u64 m_redo, u64 m_own)
         }
         if (miss) {
             ent[way * 64 + lane] = pd;
-            kk = way ? ((kk & 0xffffu) | ((uint32_t)(rel & 0xffff) << 16)) : ((kk & 0xffff0000u) | (uint32_t)(rel & 0xffff));
-            *(uint32_t *)(L + q.key + lane * 4) = kk;
+            *(uint32_t *)(L + q.key + lane * 4) = rf_key_put(kk, rel);
         }
         u64 *emit_row = (u64 *)(L + q.emit);
         const u64 fl0 = emit_row[0], fl1 = emit_row[1]; // (one wave at a time works on a row slot)
@@ -119,14 +117,7 @@ __device__ __forceinline__ void skew_rare_row(SkewRare q, u64 m_redo, u64 m_own)
             if (lane == leader) base = atomicAdd(q.cnt, __popcll(em));
             base = __shfl(base, leader) + __popcll(em & ((1ull << lane) - 1ull));
             const bool listed = emit && base < q.upd_cap;
-            if (listed) {
-                RfUpd u;
-                u.pix = (uint32_t)((size_t)q.r * q.W + q.x0 + lane) | q.dir;
-                u.rel = rel;
-                u.pwp = pd.x;
-                u.delta = pd.y;
-                q.upd[base] = u;
-            }
+            if (listed) q.upd[base] = rf_upd_record((uint32_t)((size_t)q.r * q.W + q.x0 + lane), q.dir, rel, pd);
             const u64 n0 = __ballot(listed && !way), n1 = __ballot(listed && way);
             if (lane == 0) {
                 emit_row[0] = fl0 | n0;
@@ -219,7 +210,7 @@ __global__ __launch_bounds__(64 * T) __attribute__((amdgpu_waves_per_eu(SKEW_WPE
     const int cy_lo = max(YL + 1, ya - (T - t)), cy_hi = min(YR - 1, yb - 1 + (T - t));
     const bool colok = lane >= t - 1 && lane <= 64 - t && x >= XL + 1 && x <= XR - 1;
     const u64 m_col = __builtin_amdgcn_ballot_w64(colok), m_own = __builtin_amdgcn_ballot_w64(x >= xa && x < xb);
-    const unsigned shard = (blockIdx.x + blockIdx.y * gridDim.x + blockIdx.z * 7u) & (RF_UPD_SHARDS - 1);
+    const unsigned shard = rf_upd_wg_shard(); // (here, not in the rare branch: its scalar registers spill otherwise)
     const double ws = a.ws;
     const bool wsok = ws >= 0x1p-200 && ws <= 0x1p200; // the unscaled divisions' guard on pwp + ws (pwp is in [0, 1])
 
@@ -371,7 +362,7 @@ __global__ __launch_bounds__(64 * T) __attribute__((amdgpu_waves_per_eu(SKEW_WPE
                         const int way = rel & 1;
                         // the way the state selects, as ONE 16-byte read (two 8-byte reads at a 16-byte lane stride conflict two ways)
                         const double2 pd = *(const double2 *)__builtin_assume_aligned(s_mem + LY::OFF_ENT + ek * 8u + (unsigned)way * 1024u + lane16, 16);
-                        const int crel = (int)(int16_t)(kk >> (way << 4));
+                        const int crel = rf_key_get(kk, rel);
                         // the common row's update; the masks known EARLY in its chain select what is written, the two that need the
                         // numerators only decide whether the row is redone, so the row's result never waits for them
                         double u;
@@ -386,8 +377,7 @@ __global__ __launch_bounds__(64 * T) __attribute__((amdgpu_waves_per_eu(SKEW_WPE
                 if (__builtin_expect(m_redo != 0ull, 0)) { // wave-uniform, rare
                     SkewRare q;
                     q.A = d.img4_own, q.B = d.img4_oth;
-                    q.upd = a.upd_list + (size_t)shard * a.upd_cap;
-                    q.cnt = a.upd_cnt + (a.flag3 & 1) * RF_UPD_SHARDS + shard;
+                    rf_upd_shard(a, shard, q.upd, q.cnt);
                     q.gout = last ? (double *)optr : nullptr;
                     q.lds = s_mem;
                     q.ws = ws;
@@ -398,7 +388,7 @@ __global__ __launch_bounds__(64 * T) __attribute__((amdgpu_waves_per_eu(SKEW_WPE
                     q.rdS = LY::OFF_D + (unsigned)(t - 1) * LY::RING + ((K + 3) & 3) * RPB + 16;
                     q.wr = LY::OFF_D + (unsigned)t * LY::RING + K * RPB + 16;
                     q.ent = LY::OFF_ENT + ek * 8u, q.key = LY::OFF_KEY + ek, q.emit = LY::OFF_EMIT + (ek >> 4), q.ml = LY::OFF_ML + wid * 64, q.tab = LY::OFF_EXP;
-                    q.dir = (uint32_t)blockIdx.z << 31;
+                    q.dir = blockIdx.z;
                     q.owned_row = r >= ya && r < yb;
                     skew_rare_row(q, m_redo, m_own);
                     // every memory operation of the rare path (its image loads, list appends, register spills) is complete before
@@ -448,8 +438,8 @@ __global__ __launch_bounds__(64 * T) __attribute__((amdgpu_waves_per_eu(SKEW_WPE
     }
 #undef SKEW_LD16
 #ifdef SKEW_TIMING
-    if (TOP && lane == 0 && a.flag3 == 28 && blockIdx.x == 13 && (blockIdx.y % 4) == 1)
-        printf("skewtime launch %d z %d wg %d %d wave %d steps %d: update %llu loadwait %llu write %llu barrier %llu\n", a.flag3, (int)blockIdx.z, (int)blockIdx.x, (int)blockIdx.y, wid, nsteps,
+    if (TOP && lane == 0 && a.rf_launch == 28 && blockIdx.x == 13 && (blockIdx.y % 4) == 1)
+        printf("skewtime launch %d z %d wg %d %d wave %d steps %d: update %llu loadwait %llu write %llu barrier %llu\n", a.rf_launch, (int)blockIdx.z, (int)blockIdx.x, (int)blockIdx.y, wid, nsteps,
                tm[0] / nsteps, tm[1] / nsteps, tm[2] / nsteps, tm[3] / nsteps);
 #endif
 }
@@ -471,14 +461,12 @@ bool refine_skew_fits(const StageArgs &a) {
     return true;
 }
 
-// T sweeps f64_a -> f64_b in one launch (a.flag3 = launch index, a.skew_rows = rows per chunk, a.skew_uw = columns per strip)
+// T sweeps f64_a -> f64_b in one launch (a.rf_launch = launch index, a.skew_rows = rows per chunk, a.skew_uw = columns per strip)
 // + the launch that applies its cache updates.  T in {2, 3, 4}.
 void launch_refine_skew(const StageArgs &a, int T, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {
-    int rows = 0, strips = 0;
-    for (int v = 0; v < a.ndir; v++) {
-        rows = std::max(rows, a.d[v].own.YR - a.d[v].own.YL - 1);
-        strips = std::max(strips, refine_skew_strips(a.d[v].own, T, a.skew_uw));
-    }
+    int rows, cols, strips = 0;
+    refine_interior(a, rows, cols);
+    for (int v = 0; v < a.ndir; v++) strips = std::max(strips, refine_skew_strips(a.d[v].own, T, a.skew_uw));
     if (rows <= 0 || a.skew_rows <= 0 || a.skew_uw <= 0 || a.skew_uw > 66 - 2 * T) return;
     const dim3 grid(strips, (rows + a.skew_rows - 1) / a.skew_rows, a.ndir);
     if (ev0) (void)hipEventRecord(ev0, st);

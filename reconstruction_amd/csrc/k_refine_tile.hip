@@ -10,8 +10,8 @@
 // state ping-pongs between two LDS planes; a thread keeps its pixels' key dwords and both ways' cache entries in registers.
 // All global loads go out in one batch up front; the owned pixels go to f64_b at the end.
 //
-// The update is refine_update and the miss service k_refine_sweep's (per wave through an LDS list: a lane per entry while the
-// list is long, four lanes per entry for the last 16 or fewer): no new formulation of the arithmetic.  A new entry lives in the
+// The update is refine_update and the miss service rf_serve_misses (per wave through an LDS list), the single sweep kernel's
+// too: no new formulation of the arithmetic.  A new entry lives in the
 // thread's registers for the rest of the launch; those of OWNED pixels go to the update list that k_refine_apply scatters
 // after the launch, at most one record per (pixel, way) and launch, exactly as k_refine_skew does it (a neighbouring tile may
 // be staging that pixel at the same moment: an in-place write could be read torn).  A full list drops the record, which costs
@@ -74,9 +74,9 @@ __global__ __launch_bounds__(256) void k_refine_tile(StageArgs a) {
     }
     if (!__syncthreads_or(any)) return; // workgroup-uniform: no live pixel in the tile (outside an elliptic mask, a hole)
 
-    const unsigned shard = (blockIdx.x + blockIdx.y * gridDim.x + blockIdx.z * 7u) & (RF_UPD_SHARDS - 1);
-    RfUpd *upd = a.upd_list + (size_t)shard * a.upd_cap;
-    int32_t *cnt = a.upd_cnt + (a.flag3 & 1) * RF_UPD_SHARDS + shard;
+    RfUpd *upd;
+    int32_t *cnt;
+    rf_upd_shard(a, rf_upd_wg_shard(), upd, cnt);
     const u64 below = (1ull << lane) - 1ull;
     unsigned listed = 0; // bit 2 i + way: this launch has listed a new entry for that cache slot
 
@@ -92,8 +92,8 @@ __global__ __launch_bounds__(256) void k_refine_tile(StageArgs a) {
             dC = cur[p < NPIX ? p : 0];
             const int pa = act ? p : RW + 1;
             dE = cur[pa + 1], dW = cur[pa - 1], dN = cur[pa - RW], dS = cur[pa + RW];
-            mode = (int)(dE != NM && dW != NM) + (int)(dS != NM && dN != NM) * 2; // .cpp:620
-            return act && dC != NM && mode != 0;                                   // .cpp:613 (mode 0 copies through, .cpp:655)
+            mode = refine_mode(dE, dW, dN, dS);
+            return act && dC != NM && mode != 0; // .cpp:613 (mode 0 copies through, .cpp:655)
         };
         // (1) the misses of this wave's pixels, compacted
         unsigned need = 0, miss = 0;
@@ -105,43 +105,20 @@ __global__ __launch_bounds__(256) void k_refine_tile(StageArgs a) {
             int mode;
             const bool nd = fetch(i, dC, dE, dW, dN, dS, mode);
             rel[i] = (int)(dC - 1.5); // .cpp:625 (iMatch - x)
-            const bool ms = nd && (int)(int16_t)(kk[i] >> ((rel[i] & 1) << 4)) != rel[i];
+            const bool ms = nd && rf_key_get(kk[i], rel[i]) != rel[i];
             const u64 mm = __ballot(ms);
             pos[i] = n + __popcll(mm & below);
-            if (ms) s_list[wid][pos[i]] = (uint32_t)(i * 256 + tid) | ((uint32_t)(rel[i] & 0xffff) << 16);
+            if (ms) s_list[wid][pos[i]] = rf_miss_entry(i * 256 + tid, rel[i]);
             n += __popcll(mm);
             need |= (unsigned)nd << i;
             miss |= (unsigned)ms << i;
         }
         if (n) { // wave-uniform
-            // (2) served per wave, as k_refine_sweep serves them
-            __builtin_amdgcn_wave_barrier();
-#pragma unroll 1
-            for (int done = 0; done < n;) { // uniform
-                if (n - done > 16) {         // a lane per entry
-                    const int e = done + lane;
-                    if (e < n) {
-                        const uint32_t en = s_list[wid][e];
-                        const int p = en & 0xffff, r = (int)(int16_t)(en >> 16);
-                        const int ex = gx0 + p % RW, ey = gy0 + p / RW;
-                        double pw, dl;
-                        refine_data_term_packed(d.img4_own, d.img4_oth, W, H, ex, ey, r + ex, pw, dl);
-                        s_res[wid][e] = make_double2(pw, dl);
-                    }
-                    done += 64;
-                } else { // four lanes per entry
-                    const int e = done + (lane >> 2);
-                    const bool ok = e < n;
-                    const uint32_t en = s_list[wid][ok ? e : done];
-                    const int p = en & 0xffff, r = (int)(int16_t)(en >> 16);
-                    const int ex = gx0 + p % RW, ey = gy0 + p / RW;
-                    double pw, dl;
-                    refine_data_term_quad(d.img4_own, d.img4_oth, W, H, ex, ey, r + ex, lane & 3, pw, dl);
-                    if (ok && (lane & 3) == 0) s_res[wid][e] = make_double2(pw, dl);
-                    done += 16;
-                }
-            }
-            __builtin_amdgcn_wave_barrier();
+            // (2) served per wave
+            rf_serve_misses(
+                s_list[wid], n, lane, &d, W, H,
+                [&](uint32_t en, int &ex, int &ey, int &r) { ex = gx0 + rf_miss_slot(en) % RW, ey = gy0 + rf_miss_slot(en) / RW, r = rf_miss_rel(en); },
+                [&](int e, int, int, int, double pw, double dl) { s_res[wid][e] = make_double2(pw, dl); });
             // (3) the new entries into the registers; those of owned pixels to the update list, once per (pixel, way)
             u64 bm[PPT];
             unsigned emit = 0;
@@ -152,13 +129,9 @@ __global__ __launch_bounds__(256) void k_refine_tile(StageArgs a) {
                 const bool ms = (miss >> i) & 1u;
                 if (ms) {
                     const double2 pd = s_res[wid][pos[i]];
-                    if (way) {
-                        e1[i] = pd;
-                        kk[i] = (kk[i] & 0xffffu) | ((uint32_t)(rel[i] & 0xffff) << 16);
-                    } else {
-                        e0[i] = pd;
-                        kk[i] = (kk[i] & 0xffff0000u) | (uint32_t)(rel[i] & 0xffff);
-                    }
+                    if (way) e1[i] = pd;
+                    else e0[i] = pd;
+                    kk[i] = rf_key_put(kk[i], rel[i]);
                 }
                 const bool em = ms && lim[i] == T && !((listed >> (2 * i + way)) & 1u);
                 bm[i] = __ballot(em);
@@ -174,13 +147,7 @@ __global__ __launch_bounds__(256) void k_refine_tile(StageArgs a) {
                     const int way = rel[i] & 1;
                     const int at = base + __popcll(bm[i] & below);
                     if (((emit >> i) & 1u) && at < a.upd_cap) {
-                        const double2 pd = way ? e1[i] : e0[i];
-                        RfUpd u;
-                        u.pix = (uint32_t)pix[i] | ((uint32_t)blockIdx.z << 31);
-                        u.rel = rel[i];
-                        u.pwp = pd.x;
-                        u.delta = pd.y;
-                        upd[at] = u;
+                        upd[at] = rf_upd_record((uint32_t)pix[i], blockIdx.z, rel[i], way ? e1[i] : e0[i]);
                         listed |= 1u << (2 * i + way);
                     }
                     base += __popcll(bm[i]);
@@ -212,15 +179,11 @@ __global__ __launch_bounds__(256) void k_refine_tile(StageArgs a) {
     }
 }
 
-// T sweeps f64_a -> f64_b in one launch on overlapped tiles (a.flag3 = launch index: the update list's counter set) + the launch
-// that applies its cache updates.  T in 2 .. RF_TILE_MAXT.
+// T sweeps f64_a -> f64_b in one launch on overlapped tiles (a.rf_launch = launch index: the update list's counter set) + the
+// launch that applies its cache updates.  T in 2 .. RF_TILE_MAXT.
 void launch_refine_tile(const StageArgs &a, int T, hipStream_t st) {
-    int rows = 0, cols = 0;
-    for (int v = 0; v < a.ndir; v++) {
-        rows = std::max(rows, a.d[v].own.YR - a.d[v].own.YL - 1);
-        cols = std::max(cols, a.d[v].own.XR - a.d[v].own.XL - 1);
-    }
-    if (rows <= 0 || cols <= 0 || T < 2 || T > RF_TILE_MAXT) return;
+    int rows, cols;
+    if (!refine_interior(a, rows, cols) || T < 2 || T > RF_TILE_MAXT) return;
     const dim3 grid((cols + TL_TX - 1) / TL_TX, (rows + TL_TY - 1) / TL_TY, a.ndir);
     switch (T) {
 #define RF_LAUNCH(TT) \

@@ -1,6 +1,7 @@
-// refine_common.h -- device functions shared by the DisparityRefine kernels (k_refine.hip, k_refine_skew.hip):
-// the specified exp(-t), the update of CStereoMatching.cpp:652-672, the division without operand scaling, and the three
-// bit-faithful restatements of the data term (CManageData.cpp:81-90 + arma::dot, .cpp:624-650).
+// refine_common.h -- device functions shared by the DisparityRefine kernels (k_refine.hip, k_refine_skew.hip, k_refine_tile.hip):
+// the specified exp(-t), the update of CStereoMatching.cpp:652-672, the division without operand scaling, the cache's key dword
+// and update list, the three bit-faithful forms of the data term (CManageData.cpp:81-90 + arma::dot, .cpp:624-650) over one
+// statement of its window rule, mean, norm guard and cost formula, and the per-wave miss service.
 #pragma once
 #include "rsm_dev.h"
 
@@ -151,6 +152,33 @@ __device__ __forceinline__ void rf_store(const DirArgs &d, size_t rf_stride, siz
     d.rf_ent[pix + (size_t)way * rf_stride] = make_double2(pwp, delta);
     ((int16_t *)d.rf_key)[2 * pix + way] = (int16_t)rel;
 }
+// the key dword of a pixel (both ways' keys, way 0 in the low half): the key in rel's way; the dword with rel in its way
+__device__ __forceinline__ int rf_key_get(uint32_t kk, int rel) { return (int)(int16_t)(kk >> ((rel & 1) << 4)); }
+__device__ __forceinline__ uint32_t rf_key_put(uint32_t kk, int rel) {
+    return (rel & 1) ? ((kk & 0xffffu) | ((uint32_t)(rel & 0xffff) << 16)) : ((kk & 0xffff0000u) | (uint32_t)(rel & 0xffff));
+}
+// which neighbour pairs of a pixel are valid (.cpp:620): 1 = east and west, 2 = north and south, 3 = both, 0 = neither
+__device__ __forceinline__ int refine_mode(double dE, double dW, double dN, double dS) {
+    return (int)(dE != (double)NOMATCH && dW != (double)NOMATCH) + (int)(dS != (double)NOMATCH && dN != (double)NOMATCH) * 2;
+}
+
+// The update list of a launch that runs several sweeps (k_refine_skew, k_refine_tile; k_refine_apply scatters it afterwards): the
+// counter set of launch `launch` (the two sets alternate), the shard a workgroup appends to, that shard's list and counter, and a
+// record.
+__device__ __forceinline__ int32_t *rf_upd_counters(const StageArgs &a, int launch) { return a.upd_cnt + (launch & 1) * RF_UPD_SHARDS; }
+__device__ __forceinline__ unsigned rf_upd_wg_shard() { return (blockIdx.x + blockIdx.y * gridDim.x + blockIdx.z * 7u) & (RF_UPD_SHARDS - 1); }
+__device__ __forceinline__ void rf_upd_shard(const StageArgs &a, unsigned shard, RfUpd *&list, int32_t *&cnt) {
+    list = a.upd_list + (size_t)shard * a.upd_cap;
+    cnt = rf_upd_counters(a, a.rf_launch) + shard;
+}
+__device__ __forceinline__ RfUpd rf_upd_record(uint32_t pix, uint32_t dir, int rel, double2 pd) {
+    RfUpd u;
+    u.pix = pix | (dir << 31);
+    u.rel = rel;
+    u.pwp = pd.x;
+    u.delta = pd.y;
+    return u;
+}
 
 // Lane masks straight from a compare (one v_cmp into a scalar pair), combined with scalar logic; rf_sel turns a mask back into
 // a select / branch condition at no cost.  A ballot of a COMBINED bool costs two vector instructions (v_cndmask 0 / 1 + v_cmp).
@@ -168,9 +196,43 @@ __device__ __forceinline__ int sum4(uint32_t v, int acc) { return (int)__builtin
 // 27-element windows, same gather order (byte column outer, row inner) and the same two-accumulator sums as
 // Armadillo (op_dot_meat.hpp:20-55, fn_norm.hpp:99-130): the sweep is ill-conditioned at int(d - 1.5)
 // boundaries, so xi must match the reference to the last bit.
-// Reads the BGRX copies (one aligned dword per pixel, X = 0): 24 loads, the window bytes stay packed in
-// registers.  The reference's unchecked right-window reads (.cpp:628) are emulated on the flat buffer: the flat
-// byte index test fi in [0, 3WH) of the BGR image is the flat pixel index test in [0, WH) here.
+// Reads the BGRX copies (one aligned dword per pixel, X = 0): the window bytes stay packed in registers.  The pieces below
+// state the window rule, the mean, the zero-norm guard and the cost formula ONCE; the three forms of the data term
+// (refine_data_term_packed, refine_left + refine_cost_left, refine_data_term_quad) differ only in which lane computes which
+// window and in what they keep in registers.
+
+// A right-window pixel.  The reference's unchecked right-window reads (.cpp:628) are emulated on the flat buffer: the flat
+// byte index test fi in [0, 3WH) of the BGR image is the flat pixel index test in [0, WH) here, everything outside reads 0.
+__device__ __forceinline__ uint32_t rf_right_px(const uint32_t *__restrict__ B, long long npx, long long fi) {
+    return (fi >= 0 && fi < npx) ? B[fi] : 0u;
+}
+// the left 3x3 window around (x, y): inside the image by the margin's construction
+__device__ __forceinline__ void rf_left_win(const uint32_t *__restrict__ A, int W, int x, int y, uint32_t (&aP)[3][3]) {
+#pragma unroll
+    for (int j = 0; j < 3; j++) {
+        const uint32_t *pa = A + (size_t)(y - 1 + j) * W + (x - 1);
+#pragma unroll
+        for (int p = 0; p < 3; p++) aP[j][p] = pa[p];
+    }
+}
+// element k of a window's 27-vector (the window's first three columns), and the vector's mean: an exact byte sum, one division
+template <int N>
+__device__ __forceinline__ double rf_win_elem(const uint32_t (&w)[3][N], int k) { return byte_f64(w[k % 3][(k / 3) / 3], (k / 3) % 3); }
+template <int N>
+__device__ __forceinline__ double rf_win_mean(const uint32_t (&w)[3][N]) {
+    int S = 0;
+#pragma unroll
+    for (int j = 0; j < 3; j++)
+#pragma unroll
+        for (int p = 0; p < 3; p++) S = sum4(w[j][p], S);
+    return (double)S / 27.0;
+}
+__device__ __forceinline__ double norm_or_one(double n) { return n == 0 ? 1 : n; } // WindowToVec's zero-norm guard
+__device__ __forceinline__ double rf_xi(double dot, double normL, double normR) { return (1 - dot / (normL * normR)) / 2; } // .cpp:629
+// The 27-element sums stay written out where they are used, each with Armadillo's two accumulators (even k, odd k): how the
+// loops are fused and which differences stay in registers is what the three forms differ in, and the register allocation of
+// every kernel around them follows the order of these statements.
+
 // (pwp, delta) from the three matching costs xi at iMatch + {0, 1, 2}: .cpp:631-650
 __device__ __forceinline__ void refine_entry(double x0, double x1, double x2, double &pwp, double &delta) {
     int index = x0 >= x1; // .cpp:631-632
@@ -187,39 +249,28 @@ __device__ __forceinline__ void refine_entry(double x0, double x1, double x2, do
     }
 }
 
-// xs (optional): the three matching costs themselves.
+// One lane computes the whole data term (24 loads).  xs (optional): the three matching costs themselves.
 __device__ __forceinline__ void refine_data_term_packed(const uint32_t *__restrict__ A, const uint32_t *__restrict__ B,
                                                         int W, int H, int x, int y, int key, double &pwp, double &delta,
                                                         double *xs = nullptr) {
     const long long npx = (long long)W * H;
     uint32_t aP[3][3], bP[3][5];
+    rf_left_win(A, W, x, y, aP);
 #pragma unroll
     for (int j = 0; j < 3; j++) {
-        const uint32_t *pa = A + (size_t)(y - 1 + j) * W + (x - 1);
         const long long fb = (long long)(y - 1 + j) * W + key;
 #pragma unroll
-        for (int p = 0; p < 3; p++) aP[j][p] = pa[p];
-#pragma unroll
-        for (int q = 0; q < 5; q++) {
-            const long long fi = fb + q;
-            bP[j][q] = (fi >= 0 && fi < npx) ? B[fi] : 0u;
-        }
+        for (int q = 0; q < 5; q++) bP[j][q] = rf_right_px(B, npx, fb + q);
     }
-    int SL = 0;
-#pragma unroll
-    for (int j = 0; j < 3; j++)
-#pragma unroll
-        for (int p = 0; p < 3; p++) SL = sum4(aP[j][p], SL);
-    const double meanL = (double)SL / 27.0;
+    const double meanL = rf_win_mean(aP);
     double n1 = 0.0, n2 = 0.0;
 #pragma unroll
     for (int k = 0; k < 27; k++) {
-        const double u = byte_f64(aP[k % 3][(k / 3) / 3], (k / 3) % 3) - meanL;
+        const double u = rf_win_elem(aP, k) - meanL;
         if (k & 1) n2 += u * u;
         else n1 += u * u;
     }
-    double normL = sqrt(n1 + n2);
-    if (normL == 0) normL = 1;
+    const double normL = norm_or_one(sqrt(n1 + n2));
     // the three shifts c = 0, 1, 2 as a rolled loop over a sliding register window (the body reads bP[.][0..2],
     // then the window moves one pixel): keeps the routine at ~50 registers.  The empty asm stops the compiler
     // from hoisting the 27 left-window differences (54 registers) out of the loop; they are recomputed instead.
@@ -230,17 +281,12 @@ __device__ __forceinline__ void refine_data_term_packed(const uint32_t *__restri
         for (int j = 0; j < 3; j++)
 #pragma unroll
             for (int p = 0; p < 3; p++) asm volatile("" : "+v"(aP[j][p]));
-        int SR = 0;
-#pragma unroll
-        for (int j = 0; j < 3; j++)
-#pragma unroll
-            for (int p = 0; p < 3; p++) SR = sum4(bP[j][p], SR);
-        const double meanR = (double)SR / 27.0;
+        const double meanR = rf_win_mean(bP);
         double m1 = 0.0, m2 = 0.0, d1 = 0.0, d2 = 0.0;
 #pragma unroll
         for (int k = 0; k < 27; k++) {
-            const double ur = byte_f64(bP[k % 3][(k / 3) / 3], (k / 3) % 3) - meanR;
-            const double ul = byte_f64(aP[k % 3][(k / 3) / 3], (k / 3) % 3) - meanL;
+            const double ur = rf_win_elem(bP, k) - meanR;
+            const double ul = rf_win_elem(aP, k) - meanL;
             if (k & 1) {
                 m2 += ur * ur;
                 d2 += ul * ur;
@@ -249,11 +295,10 @@ __device__ __forceinline__ void refine_data_term_packed(const uint32_t *__restri
                 d1 += ul * ur;
             }
         }
-        double normR = sqrt(m1 + m2);
-        if (normR == 0) normR = 1;
+        const double normR = norm_or_one(sqrt(m1 + m2));
         x0 = x1;
         x1 = x2;
-        x2 = (1 - (d1 + d2) / (normL * normR)) / 2; // .cpp:629
+        x2 = rf_xi(d1 + d2, normL, normR);
 #pragma unroll
         for (int j = 0; j < 3; j++)
 #pragma unroll
@@ -278,29 +323,17 @@ struct RfLeft {
 };
 __device__ __forceinline__ void refine_left(const uint32_t *__restrict__ A, int W, int x, int y, RfLeft &L) {
     uint32_t aP[3][3];
-#pragma unroll
-    for (int j = 0; j < 3; j++) {
-        const uint32_t *pa = A + (size_t)(y - 1 + j) * W + (x - 1);
-#pragma unroll
-        for (int p = 0; p < 3; p++) aP[j][p] = pa[p];
-    }
-    int SL = 0;
-#pragma unroll
-    for (int j = 0; j < 3; j++)
-#pragma unroll
-        for (int p = 0; p < 3; p++) SL = sum4(aP[j][p], SL);
-    const double meanL = (double)SL / 27.0;
+    rf_left_win(A, W, x, y, aP);
+    const double meanL = rf_win_mean(aP);
     double n1 = 0.0, n2 = 0.0;
 #pragma unroll
     for (int k = 0; k < 27; k++) {
-        const double u = byte_f64(aP[k % 3][(k / 3) / 3], (k / 3) % 3) - meanL;
+        const double u = rf_win_elem(aP, k) - meanL;
         L.ul[k] = u;
         if (k & 1) n2 += u * u;
         else n1 += u * u;
     }
-    double normL = sqrt(n1 + n2);
-    if (normL == 0) normL = 1;
-    L.normL = normL;
+    L.normL = norm_or_one(sqrt(n1 + n2));
 }
 // the matching cost xi = (1 - ncc) / 2 against the right window whose left edge is column `col` (.cpp:626-629)
 __device__ __forceinline__ double refine_cost_left(const RfLeft &L, const uint32_t *__restrict__ B, int W, int H, int y, int col) {
@@ -310,21 +343,13 @@ __device__ __forceinline__ double refine_cost_left(const RfLeft &L, const uint32
     for (int j = 0; j < 3; j++) {
         const long long fb = (long long)(y - 1 + j) * W + col;
 #pragma unroll
-        for (int p = 0; p < 3; p++) {
-            const long long fi = fb + p;
-            bP[j][p] = (fi >= 0 && fi < npx) ? B[fi] : 0u;
-        }
+        for (int p = 0; p < 3; p++) bP[j][p] = rf_right_px(B, npx, fb + p);
     }
-    int SR = 0;
-#pragma unroll
-    for (int j = 0; j < 3; j++)
-#pragma unroll
-        for (int p = 0; p < 3; p++) SR = sum4(bP[j][p], SR);
-    const double meanR = (double)SR / 27.0;
+    const double meanR = rf_win_mean(bP);
     double m1 = 0.0, m2 = 0.0, d1 = 0.0, d2 = 0.0;
 #pragma unroll
     for (int k = 0; k < 27; k++) {
-        const double ur = byte_f64(bP[k % 3][(k / 3) / 3], (k / 3) % 3) - meanR;
+        const double ur = rf_win_elem(bP, k) - meanR;
         if (k & 1) {
             m2 += ur * ur;
             d2 += L.ul[k] * ur;
@@ -333,9 +358,8 @@ __device__ __forceinline__ double refine_cost_left(const RfLeft &L, const uint32
             d1 += L.ul[k] * ur;
         }
     }
-    double normR = sqrt(m1 + m2);
-    if (normR == 0) normR = 1;
-    return (1 - (d1 + d2) / (L.normL * normR)) / 2; // .cpp:629
+    const double normR = norm_or_one(sqrt(m1 + m2));
+    return rf_xi(d1 + d2, L.normL, normR);
 }
 
 // One quad (4 adjacent lanes) computes refine_data_term_packed for one (x, y, key): every lane restates the left
@@ -348,30 +372,21 @@ __device__ __forceinline__ void refine_data_term_quad(const uint32_t *__restrict
     const int c = q > 0 ? q - 1 : 0;
     uint32_t aP[3][3], bP[3][3];
 #pragma unroll
-    for (int j = 0; j < 3; j++) {
+    for (int j = 0; j < 3; j++) { // (the two windows' loads pixel by pixel: k_refine_skew's rare path spills by this order)
         const uint32_t *pa = A + (size_t)(y - 1 + j) * W + (x - 1);
         const long long fb = (long long)(y - 1 + j) * W + key + c;
 #pragma unroll
         for (int p = 0; p < 3; p++) {
             aP[j][p] = pa[p];
-            const long long fi = fb + p;
-            bP[j][p] = (fi >= 0 && fi < npx) ? B[fi] : 0u;
+            bP[j][p] = rf_right_px(B, npx, fb + p);
         }
     }
-    int SL = 0, SR = 0;
-#pragma unroll
-    for (int j = 0; j < 3; j++)
-#pragma unroll
-        for (int p = 0; p < 3; p++) {
-            SL = sum4(aP[j][p], SL);
-            SR = sum4(bP[j][p], SR);
-        }
-    const double meanL = (double)SL / 27.0, meanR = (double)SR / 27.0;
+    const double meanL = rf_win_mean(aP), meanR = rf_win_mean(bP);
     double n1 = 0.0, n2 = 0.0, m1 = 0.0, m2 = 0.0, d1 = 0.0, d2 = 0.0;
 #pragma unroll
     for (int k = 0; k < 27; k++) {
-        const double ul = byte_f64(aP[k % 3][(k / 3) / 3], (k / 3) % 3) - meanL;
-        const double ur = byte_f64(bP[k % 3][(k / 3) / 3], (k / 3) % 3) - meanR;
+        const double ul = rf_win_elem(aP, k) - meanL;
+        const double ur = rf_win_elem(bP, k) - meanR;
         if (k & 1) {
             n2 += ul * ul;
             m2 += ur * ur;
@@ -382,12 +397,50 @@ __device__ __forceinline__ void refine_data_term_quad(const uint32_t *__restrict
             d1 += ul * ur;
         }
     }
-    double normL = sqrt(n1 + n2), normR = sqrt(m1 + m2);
-    if (normL == 0) normL = 1;
-    if (normR == 0) normR = 1;
-    const double xi = (1 - (d1 + d2) / (normL * normR)) / 2; // .cpp:629
+    const double normL = norm_or_one(sqrt(n1 + n2)), normR = norm_or_one(sqrt(m1 + m2));
+    const double xi = rf_xi(d1 + d2, normL, normR);
     if (xi_own) *xi_own = xi; // (test entry: this lane's own matching cost)
     const int qb = (int)(threadIdx.x & 63) & ~3; // the quad's first lane
     const double x0 = __shfl(xi, qb + 1), x1 = __shfl(xi, qb + 2), x2 = __shfl(xi, qb + 3);
     refine_entry(x0, x1, x2, pwp, delta);
 }
+
+// The per-wave miss service of k_refine_sweep, k_refine_rekey and k_refine_tile.  The wave's `n` (uniform) entries are compacted
+// in its LDS list; decode(entry, ex, ey, rel) names an entry's pixel and iMatch - x, sink(e, rel, ex, ey, pwp, delta) takes
+// entry e's data term (one lane calls it per entry).  Served a lane per entry while more than 16 are left (one round serves up
+// to 64 with 1/3 of the quads' instructions), then four lanes per entry: a third of the latency, which is what a handful of
+// misses costs.  (skew_rare_row keeps a form of its own -- quads only, results returned by shuffle -- inside the dominant kernel.)
+// The images come through `d` (a pointer, so that their addresses are loaded in the round that needs them: loaded up front
+// they cost k_refine_tile scalar registers it does not have).
+template <class Decode, class Sink>
+__device__ __forceinline__ void rf_serve_misses(const uint32_t *s_list, int n, int lane, const DirArgs *d, int W, int H, Decode decode, Sink sink) {
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll 1
+    for (int done = 0; done < n;) { // uniform
+        int ex, ey, rel;
+        double p, q;
+        if (n - done > 16) { // a lane per entry
+            const int e = done + lane;
+            if (e < n) {
+                decode(s_list[e], ex, ey, rel);
+                refine_data_term_packed(d->img4_own, d->img4_oth, W, H, ex, ey, rel + ex, p, q);
+                sink(e, rel, ex, ey, p, q);
+            }
+            asm volatile(""); // (keeps the compiler from merging the two rounds' sinks into one tail: two more registers in k_refine_tile)
+            done += 64;
+        } else { // four lanes per entry
+            const int e = done + (lane >> 2);
+            const bool ok = e < n;
+            decode(s_list[ok ? e : done], ex, ey, rel); // (whole quads stay active: the quad routine shuffles)
+            refine_data_term_quad(d->img4_own, d->img4_oth, W, H, ex, ey, rel + ex, lane & 3, p, q);
+            if (ok && (lane & 3) == 0) sink(e, rel, ex, ey, p, q);
+            done += 16;
+        }
+    }
+    __builtin_amdgcn_wave_barrier();
+}
+// an entry of such a list: the owner's slot in the low half, iMatch - x in the high half
+__device__ __forceinline__ uint32_t rf_miss_entry(int slot, int rel) { return (uint32_t)slot | ((uint32_t)(rel & 0xffff) << 16); }
+__device__ __forceinline__ int rf_miss_slot(uint32_t en) { return (int)(en & 0xffff); }
+__device__ __forceinline__ int rf_miss_rel(uint32_t en) { return (int)(int16_t)(en >> 16); }
+

@@ -515,12 +515,11 @@ static int refine_sweeps(rsm_ctx *c, StageArgs &a, double *const bufA[2], double
                          hipStream_t st, bool top, bool *final_in_B, double heavy_px = 0.0) {
     int launches = 0;
     bool curB = false; // the current values are in bufA
-    auto bind = [&](int t) {
+    auto bind = [&]() {
         for (int v = 0; v < a.ndir; v++) {
             a.d[v].f64_a = curB ? bufB[v] : bufA[v];
             a.d[v].f64_b = curB ? bufA[v] : bufB[v];
         }
-        a.flag2 = t;
     };
     auto level_bytes = [&]() { // 16 B per interior pixel (fp64 in + out)
         double bytes = 0;
@@ -532,62 +531,52 @@ static int refine_sweeps(rsm_ctx *c, StageArgs &a, double *const bufA[2], double
     };
     int nlaunch = 0;
     bool split_now = false; // inside a time-skewed section whose two directions run on two streams (below)
-    auto launch = [&](int t, int skewT, int tileT = 0) { // sweeps t .. t + max(skewT, tileT, 1) - 1; skewT > 0: one k_refine_skew launch, tileT > 0: one k_refine_tile launch
-        bind(t);
-        const bool timed = c && c->profile && top && !tileT && (nlaunch++ & 7) == 4;
+    int nmulti = 0; // multi-sweep launches so far: the index picks the update list's counter set (a level runs one of the two kernels)
+    enum Kind { SINGLE, SKEW, TILE };
+    auto launch = [&](int t, Kind kind, int T) { // sweeps t .. t + T - 1 as one launch of k_refine_sweep (T = 1), k_refine_skew or k_refine_tile
+        bind();
+        const bool timed = c && c->profile && top && kind != TILE && (nlaunch++ & 7) == 4;
         hipEvent_t e0 = nullptr, e1 = nullptr;
         if (timed) { // every 8th sweep launch of the top level
-            const int stg = skewT ? ST_REFINE_SKEW_TOP : ST_REFINE_LIGHT_TOP;
+            const int stg = kind == SKEW ? ST_REFINE_SKEW_TOP : ST_REFINE_LIGHT_TOP;
             const int es = prof_slot(c, stg);
             e0 = c->evpool[es].a;
             e1 = c->evpool[es].b;
             c->prof_launches[stg] += 1;
-            c->prof_bytes[stg] += (skewT ? (double)skewT : 1.0) * level_bytes();
+            c->prof_bytes[stg] += (double)T * level_bytes();
         }
-        // an early time-skewed launch: k_refine_rekey first sets both cache ways for the state it starts from (the previous
-        // launch's cache updates are in: k_refine_apply runs behind every skewed launch on the same stream)
-        const bool rekey = (skewT || tileT) && t < c->opt_refine_rekey_until;
-        if (skewT && split_now) { // the two directions as two launch chains: one's tail runs beside the other's head
-            StageArgs a0 = a, a1 = a;
-            a0.ndir = a1.ndir = 1;
-            a1.d[0] = a.d[1];
-            a1.upd_list = c->upd_list2;
-            a1.upd_cnt = c->upd_cnt2;
-            if (rekey) {
-                StageArgs r0 = a0, r1 = a1;
-                r0.flag3 = r1.flag3 = c->opt_refine_rekey_side;
-                launch_refine_rekey(r0, st);
-                launch_refine_rekey(r1, c->stream2);
+        if (kind == SINGLE) launch_refine_sweep(a, st, e0, e1);
+        else {
+            a.rf_launch = nmulti++;
+            // one launch chain, or -- a split section -- the two directions as two: one's tail runs beside the other's head
+            const int nch = (kind == SKEW && split_now) ? 2 : 1;
+            StageArgs ch[2] = {a, a};
+            hipStream_t cs[2] = {st, c->stream2};
+            if (nch == 2) {
+                ch[0].ndir = ch[1].ndir = 1;
+                ch[1].d[0] = a.d[1];
+                ch[1].upd_list = c->upd_list2;
+                ch[1].upd_cnt = c->upd_cnt2;
             }
-            launch_refine_skew(a0, skewT, st, e0, e1); // (e0 / e1: only under refine_split = 2, an A/B mode)
-            launch_refine_skew(a1, skewT, c->stream2, nullptr, nullptr);
-        } else if (skewT) {
-            if (rekey) {
-                StageArgs r = a;
-                r.flag3 = c->opt_refine_rekey_side;
-                launch_refine_rekey(r, st);
-            }
-            launch_refine_skew(a, skewT, st, e0, e1);
-        } else if (tileT) {
-            if (rekey) {
-                StageArgs r = a;
-                r.flag3 = c->opt_refine_rekey_side;
-                launch_refine_rekey(r, st);
-            }
-            launch_refine_tile(a, tileT, st);
+            // an early launch: k_refine_rekey first sets both cache ways for the state it starts from (the previous launch's
+            // cache updates are in: k_refine_apply runs behind every multi-sweep launch on the same stream)
+            if (t < c->opt_refine_rekey_until)
+                for (int i = 0; i < nch; i++) launch_refine_rekey(ch[i], cs[i]);
+            if (kind == TILE) launch_refine_tile(a, T, st);
+            else
+                for (int i = 0; i < nch; i++) launch_refine_skew(ch[i], T, cs[i], i ? nullptr : e0, i ? nullptr : e1); // (e0 / e1 in a split: only under refine_split = 2, an A/B mode)
         }
-        else launch_refine_sweep(a, st, e0, e1);
-        launches += skewT ? skewT : (tileT ? tileT : 1);
+        launches += T;
         curB = !curB;
     };
     *final_in_B = false;
     if (iters <= 0) return 0;
     double px = 0;
     for (int v = 0; v < a.ndir; v++) px += (double)(a.d[v].own.XR - a.d[v].own.XL + 1) * (a.d[v].own.YR - a.d[v].own.YL + 1);
-    bind(0);
-    a.flag3 = (c && !c->opt_refine_prefill) ? 2 : 0;
-    launch_refine_sweep(a, st); // k_refine_first: whole interior
-    a.flag3 = 0;
+    bind();
+    a.rf_no_prefill = c && !c->opt_refine_prefill;
+    a.rf_rekey_far = c ? c->opt_refine_rekey_side : 0;
+    launch_refine_first(a, st);
     launches++;
     curB = true;
     // settled sweeps of the large levels T per launch, time-skewed (k_refine_skew)
@@ -601,11 +590,10 @@ static int refine_sweeps(rsm_ctx *c, StageArgs &a, double *const bufA[2], double
     if (skew) {
         a.skew_prio = c->opt_refine_skew_prio;
         a.skew_uw = (c->opt_refine_skew_uw > 0 && c->opt_refine_skew_uw <= 66 - 2 * skewT) ? c->opt_refine_skew_uw : 66 - 2 * skewT;
-        int rows = 1, strips = 0;
-        for (int v = 0; v < a.ndir; v++) {
-            rows = std::max(rows, a.d[v].own.YR - a.d[v].own.YL - 1);
-            strips += refine_skew_strips(a.d[v].own, skewT, a.skew_uw);
-        }
+        int rows, cols, strips = 0;
+        refine_interior(a, rows, cols);
+        rows = std::max(rows, 1);
+        for (int v = 0; v < a.ndir; v++) strips += refine_skew_strips(a.d[v].own, skewT, a.skew_uw);
         // A pair that has the GPU to itself takes twice as many, half as tall chunks: its launches end in a tail of one or two
         // waves per SIMD that nothing else fills, and a second round of workgroups shortens it; with pairs in flight the other
         // pairs' kernels fill the tail and the extra pipeline fill only costs.
@@ -616,7 +604,6 @@ static int refine_sweeps(rsm_ctx *c, StageArgs &a, double *const bufA[2], double
         const int chunks = std::max(1, waves / std::max(1, strips));
         a.skew_rows = c->opt_refine_skew_rows > 0 ? c->opt_refine_skew_rows : std::max(4 * skewT, (rows + chunks - 1) / chunks);
     }
-    int nskew = 0;
     // the section that takes turns with the other contexts of this GPU starts once the sweeps have settled into pure
     // streaming: the first ones are busy computing data terms (VALU) and run well beside another pair's streaming sweeps
     bool held = false;
@@ -650,18 +637,10 @@ static int refine_sweeps(rsm_ctx *c, StageArgs &a, double *const bufA[2], double
             (void)hipStreamWaitEvent(c->stream2, c->ev_fork, 0);
             split_now = true;
         }
-        if (skew_now) {
-            a.flag3 = nskew++;
-            launch(t, skewT);
-            t += skewT;
-        } else if (tile && t >= c->opt_refine_tile_from && t + tileT <= iters) {
-            a.flag3 = nskew++; // (a level runs one of the two kernels: the launch index picks the update list's counter set)
-            launch(t, 0, tileT);
-            t += tileT;
-        } else {
-            launch(t, 0);
-            t += 1;
-        }
+        const bool tile_now = tile && t >= c->opt_refine_tile_from && t + tileT <= iters;
+        const int T = skew_now ? skewT : (tile_now ? tileT : 1);
+        launch(t, skew_now ? SKEW : (tile_now ? TILE : SINGLE), T);
+        t += T;
     }
     join();
     heavy_end(c, held, lane);

@@ -63,13 +63,14 @@ struct StageArgs {
     int r;       // MatchBlockRadius
     int offset;  // m_offset
     double ws;   // m_ws
-    int flag;    // stage-specific
-    int flag2;   // refine: sweep index
+    int flag;    // stage-specific (refine: the top level)
     size_t rf_stride;  // refine: elements between the two cache ways (>= W*H)
-    RfUpd *upd_list;   // refine (k_refine_skew): RF_UPD_SHARDS regions of upd_cap records
-    int32_t *upd_cnt;  // [2][RF_UPD_SHARDS]: append counters, the set in use alternates per launch (flag3 & 1)
+    RfUpd *upd_list;   // refine (k_refine_skew, k_refine_tile): RF_UPD_SHARDS regions of upd_cap records
+    int32_t *upd_cnt;  // [2][RF_UPD_SHARDS]: append counters, the set in use alternates per launch (rf_launch & 1)
     int upd_cap;
-    int flag3;         // refine: k_refine_first: bit 1 = no prefill of the second way; k_refine_skew: launch index (counter set)
+    int rf_launch;     // refine (k_refine_skew, k_refine_tile, k_refine_apply): index of the multi-sweep launch within the level
+    int rf_no_prefill; // refine (k_refine_first): leave the second cache way empty (option refine_prefill = 0)
+    int rf_rekey_far;  // refine (k_refine_rekey): predict the neighbour key on the far side of the interval (tests)
     int skew_rows;     // refine (k_refine_skew): rows per chunk
     int skew_uw;       // refine (k_refine_skew): columns a strip owns (<= 66 - 2T)
     int skew_prio;     // refine (k_refine_skew): issue priority rotates every 2^skew_prio shader clocks (0: never)
@@ -118,13 +119,24 @@ void launch_refine_xi(const uint32_t *A, const uint32_t *B, int W, int H, int fo
 void launch_sqrt_check(unsigned int first, long long n, unsigned long long *mismatches, hipStream_t st); // k_filter.hip
 void launch_div_unscaled(const double *a, const double *b, double *q_fast, double *q_ieee, long long n, hipStream_t st);
 void launch_refine_init(const StageArgs &a, hipStream_t st);   // d16_in -> f64_a, f64_b, cache reset
-// f64_a -> f64_b; ev0/ev1 (optional) are recorded right around the light sweep kernel
+// interior rows / columns of the margins, the largest over the directions: what a refine launch's grid covers; false: nothing to do
+inline bool refine_interior(const StageArgs &a, int &rows, int &cols) {
+    rows = cols = 0;
+    for (int v = 0; v < a.ndir; v++) {
+        const Mg &m = a.d[v].own;
+        if (m.YR - m.YL - 1 > rows) rows = m.YR - m.YL - 1;
+        if (m.XR - m.XL - 1 > cols) cols = m.XR - m.XL - 1;
+    }
+    return rows > 0 && cols > 0;
+}
+void launch_refine_first(const StageArgs &a, hipStream_t st); // the first sweep f64_a -> f64_b (k_refine_first; a.rf_no_prefill)
+// a later single sweep f64_a -> f64_b; ev0/ev1 (optional) are recorded right around the light sweep kernel
 void launch_refine_sweep(const StageArgs &a, hipStream_t st, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
-// T (2..4) sweeps f64_a -> f64_b in one time-skewed launch (a.flag3 = launch index, a.skew_rows, a.skew_uw) + the cache-update launch
-void launch_refine_apply(const StageArgs &a, hipStream_t st); // k_refine.hip
-void launch_refine_rekey(const StageArgs &a, hipStream_t st); // k_refine.hip: both cache ways for the state a.d[].f64_a (k_refine_rekey)
+void launch_refine_apply(const StageArgs &a, hipStream_t st); // k_refine.hip: the update list of launch a.rf_launch into the cache
+void launch_refine_rekey(const StageArgs &a, hipStream_t st); // k_refine.hip: both cache ways for the state a.d[].f64_a (k_refine_rekey; a.rf_rekey_far)
+// T (2..4) sweeps f64_a -> f64_b in one time-skewed launch (a.rf_launch = launch index, a.skew_rows, a.skew_uw) + the cache-update launch
 void launch_refine_skew(const StageArgs &a, int T, hipStream_t st, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr); // k_refine_skew.hip
-// T (2..RF_TILE_MAXT) sweeps f64_a -> f64_b in one launch on overlapped tiles (a.flag3 = launch index) + the cache-update launch
+// T (2..RF_TILE_MAXT) sweeps f64_a -> f64_b in one launch on overlapped tiles (a.rf_launch = launch index) + the cache-update launch
 void launch_refine_tile(const StageArgs &a, int T, hipStream_t st); // k_refine_tile.hip
 int refine_skew_strips(const Mg &m, int T, int uw); // strips of 64 lanes a direction's interior takes (k_refine_skew.hip)
 bool refine_skew_fits(const StageArgs &a);          // the kernel's flat over-reads stay inside the level
