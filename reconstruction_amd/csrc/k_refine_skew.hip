@@ -444,23 +444,6 @@ __global__ __launch_bounds__(64 * T) __attribute__((amdgpu_waves_per_eu(SKEW_WPE
 #endif
 }
 
-// strips of 64 lanes the interior of margin m takes (strip b owns the columns [xorg + T - 1 + b uw, + uw) of [XL + 1, XR - 1])
-int refine_skew_strips(const Mg &m, int T, int uw) {
-    const int xorg = (m.XL + 1 - (T - 1)) & ~7;
-    return std::max(1, (m.XR - xorg - T + 1 + uw - 1) / uw);
-}
-
-// The kernel addresses rows of 64 + 4 columns on the flat row-major buffers without clamping: a strip may hang over a row's
-// ends into the neighbouring rows, never out of the level (rows 1 .. H - 2 are the only ones a margin can hold, r >= 1).
-bool refine_skew_fits(const StageArgs &a) {
-    if (a.W < 80 || a.H < 3) return false;
-    for (int v = 0; v < a.ndir; v++) {
-        const Mg &m = a.d[v].own;
-        if (m.XL < 1 || m.YL < 1 || m.XR > a.W - 2 || m.YR > a.H - 2) return false;
-    }
-    return true;
-}
-
 // T sweeps f64_a -> f64_b in one launch (a.rf_launch = launch index, a.skew_rows = rows per chunk, a.skew_uw = columns per strip)
 // + the launch that applies its cache updates.  T in {2, 3, 4}.
 void launch_refine_skew(const StageArgs &a, int T, hipStream_t st, hipEvent_t ev0, hipEvent_t ev1) {

@@ -8,7 +8,6 @@
 #include "rsm_ctx.h"
 
 #include <algorithm>
-#include <mutex>
 #include <thread>
 
 #include <math.h>
@@ -20,63 +19,6 @@
 static const char *kStageNames[ST_COUNT] = {"pyramid", "margin", "boxsum", "initial_match", "smooth", "order",
                                             "uniqueness_s16", "rematch", "median", "refine_init",
                                             "refine_sweep", "refine_sweep_top", "refine_light_top", "refine_skew_top", "uniqueness_f64", "cloud"};
-
-// ---- one bandwidth-bound section at a time per GPU ------------------------------------------------------------
-// Contexts that share a GPU (rsm_run_pairs / rsm_match_pairs: several pairs in flight) overlap usefully only where
-// one of them leaves the chip idle: the launch-latency-bound small levels, the row-serial stages, host syncs.  Two
-// pairs' large-level Jacobi sweeps gain nothing from running side by side -- each streams at the fabric's rate
-// alone -- and would only halve each other's speed.  So those sections take turns, ordered on the GPU by events (the host
-// never blocks for it): a section waits for the event that ends the previous context's section; the short mutex
-// only makes "enqueue the section, publish its end event" atomic.
-// MEASURED (C2, two pairs in flight): no turns 214-220 Mdisp/s with every top-level sweep launch twice as long (236 us);
-// turns for every large level 210 with isolated-like launches (125 us); turns for the TOP level only (the default) 227-231:
-// the other pair's second-largest level and full-size non-refine stages then run beside the top-level sweeps and fill
-// their launch tails, at the price of 158 us per top-level launch.
-#define RSM_MAX_DEVICES 64
-static std::atomic<int> g_running[RSM_MAX_DEVICES]; // contexts inside rsm_run_pair, per device
-struct RunningGuard {
-    int dev;
-    std::atomic<int> *own;
-    RunningGuard(int d, std::atomic<int> *in_run) : dev(d), own(in_run) {
-        if (dev < RSM_MAX_DEVICES) g_running[dev].fetch_add(1);
-        own->store(1);
-    }
-    ~RunningGuard() {
-        own->store(0);
-        if (dev < RSM_MAX_DEVICES) g_running[dev].fetch_sub(1);
-    }
-};
-static std::mutex g_heavy_mu[RSM_MAX_DEVICES][2];
-static hipEvent_t g_heavy_last[RSM_MAX_DEVICES][2];
-static rsm_ctx *g_heavy_owner[RSM_MAX_DEVICES][2];
-
-// lane 0: sections bound by the fabric (one sweep per launch); lane 1 (option heavy_lanes = 2): the time-skewed sections, bound
-// by fp64 issue -- a section of one kind runs well beside a section of the other kind of another pair
-static bool heavy_begin(rsm_ctx *c, double pixels, bool top, int lane = 0) {
-    if (!c->opt_heavy_exclusive || pixels < (double)c->opt_heavy_min_px || c->device >= RSM_MAX_DEVICES) return false;
-    if (c->opt_heavy_exclusive == 1 && !top) return false; // 1: only the top level's sweeps take turns
-    g_heavy_mu[c->device][lane].lock();
-    if (g_heavy_last[c->device][lane] && g_heavy_owner[c->device][lane] != c) (void)hipStreamWaitEvent(c->stream, g_heavy_last[c->device][lane], 0);
-    return true;
-}
-static void heavy_end(rsm_ctx *c, bool held, int lane = 0) {
-    if (!held) return;
-    hipEvent_t ev = lane ? c->ev_heavy2 : c->ev_heavy;
-    (void)hipEventRecord(ev, c->stream);
-    g_heavy_last[c->device][lane] = ev;
-    g_heavy_owner[c->device][lane] = c;
-    g_heavy_mu[c->device][lane].unlock();
-}
-static void heavy_forget(rsm_ctx *c) { // the context goes away: nobody may wait on its event any more
-    if (c->device >= RSM_MAX_DEVICES) return;
-    for (int lane = 0; lane < 2; lane++) {
-        std::lock_guard<std::mutex> g(g_heavy_mu[c->device][lane]);
-        if (g_heavy_owner[c->device][lane] == c) {
-            g_heavy_owner[c->device][lane] = nullptr;
-            g_heavy_last[c->device][lane] = nullptr;
-        }
-    }
-}
 
 int set_err(rsm_ctx *c, int code, const char *fmt, ...) {
     if (c) {
@@ -327,7 +269,7 @@ extern "C" int rsm_upload_pair_device(rsm_ctx *c, const rsm_pair_in *in) {
 }
 
 // ---- profiling helpers --------------------------------------------------------------------------
-static int prof_slot(rsm_ctx *c, int stage) { // next event pair of the pool
+int prof_slot(rsm_ctx *c, int stage) { // next event pair of the pool
     if (c->ev_used == c->evpool.size()) {
         EvPair e{};
         (void)hipEventCreate(&e.a);
@@ -337,100 +279,161 @@ static int prof_slot(rsm_ctx *c, int stage) { // next event pair of the pool
     c->evpool[c->ev_used].stage = stage;
     return (int)c->ev_used++;
 }
-static int prof_begin(rsm_ctx *c, int stage) {
-    if (!c->profile || !c->profile_stages) return -1;
-    const int s = prof_slot(c, stage);
-    (void)hipEventRecord(c->evpool[s].a, c->stream);
-    return s;
+// A stage of rsm_run_pair on the main stream, for rsm_profile_*: event a where the bracket is made, event b where its scope
+// ends, and the stage's launches and bytes booked there.
+struct StageScope {
+    rsm_ctx *c;
+    int stage, slot = -1, launches;
+    double bytes;
+    StageScope(rsm_ctx *c_, int stage_, int launches_, double bytes_) : c(c_), stage(stage_), launches(launches_), bytes(bytes_) {
+        if (!c->profile || !c->profile_stages) return;
+        slot = prof_slot(c, stage);
+        (void)hipEventRecord(c->evpool[slot].a, c->stream);
+    }
+    ~StageScope() {
+        if (slot < 0) return;
+        (void)hipEventRecord(c->evpool[slot].b, c->stream);
+        c->prof_launches[stage] += launches;
+        c->prof_bytes[stage] += bytes;
+    }
+    StageScope(const StageScope &) = delete;
+    StageScope &operator=(const StageScope &) = delete;
+};
+
+// ---- options ------------------------------------------------------------------------------------
+// The plain ones: a flag (value != 0) or a value clamped to [lo, hi].  Their defaults are the member initialisers (rsm_ctx.h),
+// what they do is told in include/rsm.h.
+enum OptKind { OPT_BOOL, OPT_CLAMP };
+struct OptRow {
+    const char *name;
+    int rsm_ctx::*member;
+    OptKind kind;
+    long long lo, hi;
+};
+static const OptRow kOptions[] = {
+    {"ncc_bytes", &rsm_ctx::opt_ncc_bytes, OPT_BOOL, 0, 0},
+    {"ncc_slide_max", &rsm_ctx::opt_ncc_slide_max, OPT_CLAMP, 0, 1000000},
+    {"no_exact", &rsm_ctx::opt_no_exact, OPT_BOOL, 0, 0},
+    {"heavy_exclusive", &rsm_ctx::opt_heavy_exclusive, OPT_CLAMP, 0, 2},
+    {"heavy_from_sweep", &rsm_ctx::opt_heavy_from_sweep, OPT_CLAMP, 1, 100000},
+    {"heavy_min_px", &rsm_ctx::opt_heavy_min_px, OPT_CLAMP, 0, 2000000000},
+    {"heavy_lanes", &rsm_ctx::opt_heavy_lanes, OPT_CLAMP, 1, 2},
+    {"shared_gpu", &rsm_ctx::opt_shared_gpu, OPT_BOOL, 0, 0},
+    {"refine_prefill", &rsm_ctx::opt_refine_prefill, OPT_BOOL, 0, 0},
+    {"refine_rekey_until", &rsm_ctx::opt_refine_rekey_until, OPT_CLAMP, 0, 100000},
+    {"refine_rekey_side", &rsm_ctx::opt_refine_rekey_side, OPT_BOOL, 0, 0},
+    {"refine_split", &rsm_ctx::opt_refine_split, OPT_CLAMP, 0, 2}, // 2: also with pairs in flight (A/B)
+    {"refine_skew_from", &rsm_ctx::opt_refine_skew_from, OPT_CLAMP, 0, 100000},
+    {"refine_skew_T", &rsm_ctx::opt_refine_skew_T, OPT_CLAMP, 2, 4},
+    {"refine_skew_min_px", &rsm_ctx::opt_refine_skew_min_px, OPT_CLAMP, 0, 2000000000},
+    {"refine_skew_waves", &rsm_ctx::opt_refine_skew_waves, OPT_CLAMP, 1, 1000000},
+    {"refine_skew_waves_alone", &rsm_ctx::opt_refine_skew_waves_alone, OPT_CLAMP, 0, 1000000},
+    {"refine_skew_waves_low", &rsm_ctx::opt_refine_skew_waves_low, OPT_CLAMP, 0, 1000000},
+    {"refine_skew_rows", &rsm_ctx::opt_refine_skew_rows, OPT_CLAMP, 0, 1000000},
+    {"refine_skew_prio", &rsm_ctx::opt_refine_skew_prio, OPT_CLAMP, 0, 40},
+    {"refine_tile_from", &rsm_ctx::opt_refine_tile_from, OPT_CLAMP, 1, 100000},
+    {"refine_tile_min_px", &rsm_ctx::opt_refine_tile_min_px, OPT_CLAMP, 0, 2000000000},
+    {"refine_upd_cap", &rsm_ctx::opt_refine_upd_cap, OPT_CLAMP, 0, 1LL << 30},
+    {"filter_wg_max", &rsm_ctx::opt_filter_wg_max, OPT_CLAMP, 0, 1LL << 30},
+    {"filter_normals_window", &rsm_ctx::opt_filter_normals_window, OPT_CLAMP, 0, 40},
+    {"filter_low_priority", &rsm_ctx::opt_filter_low_priority, OPT_BOOL, 0, 0},
+    {"filter_list", &rsm_ctx::opt_filter_list, OPT_CLAMP, 0, 31}, // bit 0: the 24-pixel list pass, bit 1: the 40-pixel one, bit 2: the wave passes (80, 160, ... pixels) for what they leave, bits 3 / 4: the 24- / 40-pixel pass in the wave form too
+    {"filter_window", &rsm_ctx::opt_filter_window, OPT_CLAMP, 0, 24}, // 0 off, 1 default, else the radius
+};
+
+// The options that do more than that.
+static int set_no_rowgemm(rsm_ctx *c, long long value) {
+    c->opt_no_rowgemm = value != 0 ? 1 : 0;
+    return RSM_OK;
 }
-static void prof_end(rsm_ctx *c, int slot, int stage, int launches, double bytes) {
-    if (slot < 0) return;
-    (void)hipEventRecord(c->evpool[slot].b, c->stream);
-    c->prof_launches[stage] += launches;
-    c->prof_bytes[stage] += bytes;
+static int set_wide_rows(rsm_ctx *c, long long value) {
+    c->opt_no_rowgemm = (value >= 0 && value <= 3) ? (int)value : 0;
+    return RSM_OK;
 }
+static int set_ncc_mid(rsm_ctx *c, long long value) {
+    c->opt_ncc_mid = value <= 0 ? 0 : (int)std::max(8LL, std::min(value, 160LL));
+    return RSM_OK;
+}
+static int set_meshcolor_big_box(rsm_ctx *c, long long value) { // (a 64-bit member)
+    c->opt_meshcolor_big_box = std::max(1LL, std::min(value, 1LL << 20));
+    return RSM_OK;
+}
+static int set_refine_skew_uw(rsm_ctx *c, long long value) { // an even number of columns (the state row's 16-byte pieces start on even columns)
+    if (value < 0 || value > 62 || (value & 1)) return set_err(c, RSM_E_INVALID, "refine_skew_uw %lld: 0 (= 66 - 2T) or an even number <= 66 - 2T", value);
+    c->opt_refine_skew_uw = (int)value;
+    return RSM_OK;
+}
+static int set_refine_tile_T(rsm_ctx *c, long long value) {
+    if (value != 0 && (value < 2 || value > RF_TILE_MAXT)) return set_err(c, RSM_E_INVALID, "refine_tile_T %lld: 0 (off) or 2 .. %d", value, RF_TILE_MAXT);
+    c->opt_refine_tile_T = (int)value;
+    return RSM_OK;
+}
+static int set_filter_ladder_h(rsm_ctx *c, long long value) { // the bit pattern of a positive finite float32: the first ladder level's search radius; 0: from the sample
+    if (value < 0 || value >= 0x7f800000LL) return set_err(c, RSM_E_INVALID, "filter_ladder_h %lld: 0 or the bit pattern of a positive finite float", value);
+    uint32_t bits = (uint32_t)value;
+    memcpy(&c->filt_route.h0, &bits, sizeof bits);
+    return RSM_OK;
+}
+// Contexts that share a GPU each on their own share of the compute units (the `ordinal % n`-th of n equal ranges of the
+// CU mask, hipExtStreamCreateWithCUMask) instead of all of them on the whole chip; 0 / 1 = the whole chip.
+static int set_cu_share(rsm_ctx *c, long long value) {
+    const int n = (int)std::max(0LL, std::min(value, 64LL));
+    if (c->in_run.load()) return set_err(c, RSM_E_STATE, "cu_share: the context is inside rsm_run_pair (its streams are in use)");
+    if (hipSetDevice(c->device) != hipSuccess) return set_err(c, RSM_E_HIP, "hipSetDevice");
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, c->device) != hipSuccess) return set_err(c, RSM_E_HIP, "hipGetDeviceProperties");
+    const int ncu = prop.multiProcessorCount;
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipStreamSynchronize(c->stream2);
+    hipStream_t s1 = nullptr, s2 = nullptr;
+    hipError_t e1, e2;
+    if (n > 1) {
+        std::vector<uint32_t> mask((size_t)(ncu + 31) / 32, 0u);
+        const int idx = c->ordinal % n, lo = (int)((long long)idx * ncu / n), hi = (int)((long long)(idx + 1) * ncu / n);
+        for (int i = lo; i < hi; i++) mask[(size_t)i / 32] |= 1u << (i & 31);
+        e1 = hipExtStreamCreateWithCUMask(&s1, (uint32_t)mask.size(), mask.data());
+        e2 = hipExtStreamCreateWithCUMask(&s2, (uint32_t)mask.size(), mask.data());
+    } else {
+        e1 = hipStreamCreateWithFlags(&s1, hipStreamNonBlocking);
+        e2 = hipStreamCreateWithFlags(&s2, hipStreamNonBlocking);
+    }
+    if (e1 != hipSuccess || e2 != hipSuccess) {
+        if (s1) (void)hipStreamDestroy(s1);
+        if (s2) (void)hipStreamDestroy(s2);
+        return set_err(c, RSM_E_HIP, "cu_share: stream creation failed");
+    }
+    (void)hipStreamDestroy(c->stream);
+    (void)hipStreamDestroy(c->stream2);
+    c->stream = s1;
+    c->stream2 = s2;
+    c->opt_cu_share = n;
+    return RSM_OK;
+}
+static const struct {
+    const char *name;
+    int (*set)(rsm_ctx *c, long long value);
+} kSpecialOptions[] = {
+    {"no_rowgemm", set_no_rowgemm},
+    {"wide_rows", set_wide_rows},
+    {"ncc_mid", set_ncc_mid},
+    {"meshcolor_big_box", set_meshcolor_big_box},
+    {"refine_skew_uw", set_refine_skew_uw},
+    {"refine_tile_T", set_refine_tile_T},
+    {"filter_ladder_h", set_filter_ladder_h},
+    {"cu_share", set_cu_share},
+};
 
 extern "C" int rsm_set_option(rsm_ctx *c, const char *name, long long value) {
     if (!c || !name) return RSM_E_INVALID;
     if (!strncmp(name, "filter_", 7)) c->filt_memo_radius = 0; // (the cloud filter's own options: it probes its window radius afresh)
-    if (!strcmp(name, "ncc_bytes")) c->opt_ncc_bytes = value != 0;
-    else if (!strcmp(name, "heavy_from_sweep")) c->opt_heavy_from_sweep = (int)std::max(1LL, std::min(value, 100000LL));
-    else if (!strcmp(name, "heavy_min_px")) c->opt_heavy_min_px = (int)std::max(0LL, std::min(value, 2000000000LL));
-    else if (!strcmp(name, "heavy_lanes")) c->opt_heavy_lanes = (int)std::max(1LL, std::min(value, 2LL));
-    else if (!strcmp(name, "filter_wg_max")) c->opt_filter_wg_max = (int)std::max(0LL, std::min(value, 1LL << 30));
-    else if (!strcmp(name, "filter_normals_window")) c->opt_filter_normals_window = (int)std::max(0LL, std::min(value, 40LL));
-    else if (!strcmp(name, "filter_low_priority")) c->opt_filter_low_priority = value != 0;
-    else if (!strcmp(name, "heavy_exclusive")) c->opt_heavy_exclusive = (int)std::max(0LL, std::min(value, 2LL));
-    else if (!strcmp(name, "no_rowgemm")) c->opt_no_rowgemm = value != 0 ? 1 : 0;
-    else if (!strcmp(name, "wide_rows")) c->opt_no_rowgemm = (value >= 0 && value <= 3) ? (int)value : 0;
-    else if (!strcmp(name, "ncc_mid")) c->opt_ncc_mid = value <= 0 ? 0 : (int)std::max(8LL, std::min(value, 160LL));
-    else if (!strcmp(name, "ncc_slide_max")) c->opt_ncc_slide_max = (int)std::max(0LL, std::min(value, 1000000LL));
-    else if (!strcmp(name, "no_exact")) c->opt_no_exact = value != 0;
-    else if (!strcmp(name, "refine_skew_from")) c->opt_refine_skew_from = (int)std::max(0LL, std::min(value, 100000LL));
-    else if (!strcmp(name, "refine_prefill")) c->opt_refine_prefill = value != 0;
-    else if (!strcmp(name, "refine_rekey_until")) c->opt_refine_rekey_until = (int)std::max(0LL, std::min(value, 100000LL));
-    else if (!strcmp(name, "refine_rekey_side")) c->opt_refine_rekey_side = value != 0;
-    else if (!strcmp(name, "refine_split")) c->opt_refine_split = (int)std::max(0LL, std::min(value, 2LL)); // 2: also with pairs in flight (A/B)
-    else if (!strcmp(name, "refine_skew_T")) c->opt_refine_skew_T = (int)std::max(2LL, std::min(value, 4LL));
-    else if (!strcmp(name, "refine_skew_min_px")) c->opt_refine_skew_min_px = (int)std::max(0LL, std::min(value, 2000000000LL));
-    else if (!strcmp(name, "refine_skew_waves")) c->opt_refine_skew_waves = (int)std::max(1LL, std::min(value, 1000000LL));
-    else if (!strcmp(name, "refine_skew_prio")) c->opt_refine_skew_prio = (int)std::max(0LL, std::min(value, 40LL));
-    else if (!strcmp(name, "refine_skew_uw")) { // an even number of columns (the state row's 16-byte pieces start on even columns)
-        if (value < 0 || value > 62 || (value & 1)) return set_err(c, RSM_E_INVALID, "refine_skew_uw %lld: 0 (= 66 - 2T) or an even number <= 66 - 2T", value);
-        c->opt_refine_skew_uw = (int)value;
-    } else if (!strcmp(name, "shared_gpu")) c->opt_shared_gpu = value != 0;
-    else if (!strcmp(name, "filter_list")) c->opt_filter_list = (int)std::max(0LL, std::min(value, 31LL)); // bit 0: the 24-pixel list pass, bit 1: the 40-pixel one, bit 2: the wave passes (80, 160, ... pixels) for what they leave, bits 3 / 4: the 24- / 40-pixel pass in the wave form too
-    else if (!strcmp(name, "filter_window")) c->opt_filter_window = (int)std::max(0LL, std::min(value, 24LL)); // 0 off, 1 default, else the radius
-    else if (!strcmp(name, "filter_ladder_h")) { // the bit pattern of a positive finite float32: the first ladder level's search radius; 0: from the sample
-        if (value < 0 || value >= 0x7f800000LL) return set_err(c, RSM_E_INVALID, "filter_ladder_h %lld: 0 or the bit pattern of a positive finite float", value);
-        uint32_t bits = (uint32_t)value;
-        memcpy(&c->filt_route.h0, &bits, sizeof bits);
-    }
-    else if (!strcmp(name, "meshcolor_big_box")) c->opt_meshcolor_big_box = std::max(1LL, std::min(value, 1LL << 20));
-    else if (!strcmp(name, "refine_skew_waves_alone")) c->opt_refine_skew_waves_alone = (int)std::max(0LL, std::min(value, 1000000LL));
-    else if (!strcmp(name, "refine_skew_rows")) c->opt_refine_skew_rows = (int)std::max(0LL, std::min(value, 1000000LL));
-    else if (!strcmp(name, "refine_tile_T")) {
-        if (value != 0 && (value < 2 || value > RF_TILE_MAXT)) return set_err(c, RSM_E_INVALID, "refine_tile_T %lld: 0 (off) or 2 .. %d", value, RF_TILE_MAXT);
-        c->opt_refine_tile_T = (int)value;
-    } else if (!strcmp(name, "refine_tile_from")) c->opt_refine_tile_from = (int)std::max(1LL, std::min(value, 100000LL));
-    else if (!strcmp(name, "refine_tile_min_px")) c->opt_refine_tile_min_px = (int)std::max(0LL, std::min(value, 2000000000LL));
-    else if (!strcmp(name, "refine_skew_waves_low")) c->opt_refine_skew_waves_low = (int)std::max(0LL, std::min(value, 1000000LL));
-    else if (!strcmp(name, "refine_upd_cap")) c->opt_refine_upd_cap = (int)std::max(0LL, std::min(value, 1LL << 30));
-    else if (!strcmp(name, "cu_share")) {
-        // Contexts that share a GPU each on their own share of the compute units (the `ordinal % n`-th of n equal ranges of the
-        // CU mask, hipExtStreamCreateWithCUMask) instead of all of them on the whole chip; 0 / 1 = the whole chip.
-        const int n = (int)std::max(0LL, std::min(value, 64LL));
-        if (c->in_run.load()) return set_err(c, RSM_E_STATE, "cu_share: the context is inside rsm_run_pair (its streams are in use)");
-        if (hipSetDevice(c->device) != hipSuccess) return set_err(c, RSM_E_HIP, "hipSetDevice");
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, c->device) != hipSuccess) return set_err(c, RSM_E_HIP, "hipGetDeviceProperties");
-        const int ncu = prop.multiProcessorCount;
-        (void)hipStreamSynchronize(c->stream);
-        (void)hipStreamSynchronize(c->stream2);
-        hipStream_t s1 = nullptr, s2 = nullptr;
-        hipError_t e1, e2;
-        if (n > 1) {
-            std::vector<uint32_t> mask((size_t)(ncu + 31) / 32, 0u);
-            const int idx = c->ordinal % n, lo = (int)((long long)idx * ncu / n), hi = (int)((long long)(idx + 1) * ncu / n);
-            for (int i = lo; i < hi; i++) mask[(size_t)i / 32] |= 1u << (i & 31);
-            e1 = hipExtStreamCreateWithCUMask(&s1, (uint32_t)mask.size(), mask.data());
-            e2 = hipExtStreamCreateWithCUMask(&s2, (uint32_t)mask.size(), mask.data());
-        } else {
-            e1 = hipStreamCreateWithFlags(&s1, hipStreamNonBlocking);
-            e2 = hipStreamCreateWithFlags(&s2, hipStreamNonBlocking);
+    for (const OptRow &o : kOptions)
+        if (!strcmp(name, o.name)) {
+            c->*o.member = o.kind == OPT_BOOL ? (int)(value != 0) : (int)std::max(o.lo, std::min(value, o.hi));
+            return RSM_OK;
         }
-        if (e1 != hipSuccess || e2 != hipSuccess) {
-            if (s1) (void)hipStreamDestroy(s1);
-            if (s2) (void)hipStreamDestroy(s2);
-            return set_err(c, RSM_E_HIP, "cu_share: stream creation failed");
-        }
-        (void)hipStreamDestroy(c->stream);
-        (void)hipStreamDestroy(c->stream2);
-        c->stream = s1;
-        c->stream2 = s2;
-        c->opt_cu_share = n;
-    } else return set_err(c, RSM_E_INVALID, "unknown option %s", name);
-    return RSM_OK;
+    for (const auto &o : kSpecialOptions)
+        if (!strcmp(name, o.name)) return o.set(c, value);
+    return set_err(c, RSM_E_INVALID, "unknown option %s", name);
 }
 
 extern "C" int rsm_profile_enable(rsm_ctx *c, int on) {
@@ -506,189 +509,50 @@ static StageArgs level_args(rsm_ctx *c, int k) {
 }
 
 
-// DisparityRefine's Jacobi sweeps (.cpp:590-678): sweep t reads A (t even) or B (t odd) and writes the other.
-// Sweep 0 is k_refine_first (every pixel computes its data term); then one launch per sweep (k_refine_sweep) while the
-// data-term cache fills, and from sweep `refine_skew_from` on the large levels run T sweeps per launch, time-skewed
-// (k_refine_skew.hip), with the leftover sweeps single again.  Returns the number of sweeps launched; *final_in_B tells
-// which buffer holds the result.
-static int refine_sweeps(rsm_ctx *c, StageArgs &a, double *const bufA[2], double *const bufB[2], int iters,
-                         hipStream_t st, bool top, bool *final_in_B, double heavy_px = 0.0) {
-    int launches = 0;
-    bool curB = false; // the current values are in bufA
-    auto bind = [&]() {
-        for (int v = 0; v < a.ndir; v++) {
-            a.d[v].f64_a = curB ? bufB[v] : bufA[v];
-            a.d[v].f64_b = curB ? bufA[v] : bufB[v];
+// ---- rsm_run_pair's steps, in the order they run --------------------------------------------------
+
+// ConstructPyrm, .cpp:1040-1053 (top level = uploaded images).  The main stream needs the masks (margins) first;
+// everything that depends on the images or the top mask only goes to the side stream and is made while the small
+// levels (launch-latency bound, the GPU mostly idle) are matched: the image pyramid, every level's BGRX copy and
+// NCC window sums (level k waits for ev_prep[k]), and the cloud's bad-pixel prefix + block map (ev_cloudprep).
+static int prepare_side_stream(rsm_ctx *c) {
+    const int N = c->N, r = c->in.radius;
+    hipStream_t s2 = c->stream2;
+    HIPCHK(c, hipEventRecord(c->ev_pyr, c->stream)); // everything enqueued before this run
+    HIPCHK(c, hipStreamWaitEvent(s2, c->ev_pyr, 0));
+    for (int k = N - 2; k >= 0; k--)
+        for (int v = 0; v < 2; v++) launch_pyr_down(c->img[k + 1][v], c->Wk[k + 1], c->Hk[k + 1], 3, c->img[k][v], s2);
+    for (int k = 0; k < N; k++) {
+        const int W = c->Wk[k], H = c->Hk[k];
+        for (int v = 0; v < 2; v++) {
+            launch_bgr_to_bgrx(c->img[k][v], W, H, c->img4[k][v], s2);
+            launch_box_sums(c->img4[k][v], W, H, r, c->tmp1, c->tmp2, c->S1[k][v], c->S2[k][v], s2);
+            // the maps the initial match and the median filter write into start as NOMATCH everywhere (.cpp:772)
+            launch_fill_i16(c->d16i[k][v], (size_t)W * H, (int16_t)NOMATCH, s2);
+            launch_fill_i16(c->d16m[k][v], (size_t)W * H, (int16_t)NOMATCH, s2);
+            launch_fill_i16(c->d16s[k][v], (size_t)W * H, (int16_t)NOMATCH, s2);
         }
-    };
-    auto level_bytes = [&]() { // 16 B per interior pixel (fp64 in + out)
-        double bytes = 0;
-        for (int v = 0; v < a.ndir; v++) {
-            const int r0 = a.d[v].own.YL + 1, r1 = a.d[v].own.YR;
-            if (r1 > r0) bytes += 16.0 * (r1 - r0) * (a.d[v].own.XR - a.d[v].own.XL + 1);
-        }
-        return bytes;
-    };
-    int nlaunch = 0;
-    bool split_now = false; // inside a time-skewed section whose two directions run on two streams (below)
-    int nmulti = 0; // multi-sweep launches so far: the index picks the update list's counter set (a level runs one of the two kernels)
-    enum Kind { SINGLE, SKEW, TILE };
-    auto launch = [&](int t, Kind kind, int T) { // sweeps t .. t + T - 1 as one launch of k_refine_sweep (T = 1), k_refine_skew or k_refine_tile
-        bind();
-        const bool timed = c && c->profile && top && kind != TILE && (nlaunch++ & 7) == 4;
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        if (timed) { // every 8th sweep launch of the top level
-            const int stg = kind == SKEW ? ST_REFINE_SKEW_TOP : ST_REFINE_LIGHT_TOP;
-            const int es = prof_slot(c, stg);
-            e0 = c->evpool[es].a;
-            e1 = c->evpool[es].b;
-            c->prof_launches[stg] += 1;
-            c->prof_bytes[stg] += (double)T * level_bytes();
-        }
-        if (kind == SINGLE) launch_refine_sweep(a, st, e0, e1);
-        else {
-            a.rf_launch = nmulti++;
-            // one launch chain, or -- a split section -- the two directions as two: one's tail runs beside the other's head
-            const int nch = (kind == SKEW && split_now) ? 2 : 1;
-            StageArgs ch[2] = {a, a};
-            hipStream_t cs[2] = {st, c->stream2};
-            if (nch == 2) {
-                ch[0].ndir = ch[1].ndir = 1;
-                ch[1].d[0] = a.d[1];
-                ch[1].upd_list = c->upd_list2;
-                ch[1].upd_cnt = c->upd_cnt2;
-            }
-            // an early launch: k_refine_rekey first sets both cache ways for the state it starts from (the previous launch's
-            // cache updates are in: k_refine_apply runs behind every multi-sweep launch on the same stream)
-            if (t < c->opt_refine_rekey_until)
-                for (int i = 0; i < nch; i++) launch_refine_rekey(ch[i], cs[i]);
-            if (kind == TILE) launch_refine_tile(a, T, st);
-            else
-                for (int i = 0; i < nch; i++) launch_refine_skew(ch[i], T, cs[i], i ? nullptr : e0, i ? nullptr : e1); // (e0 / e1 in a split: only under refine_split = 2, an A/B mode)
-        }
-        launches += T;
-        curB = !curB;
-    };
-    *final_in_B = false;
-    if (iters <= 0) return 0;
-    double px = 0;
-    for (int v = 0; v < a.ndir; v++) px += (double)(a.d[v].own.XR - a.d[v].own.XL + 1) * (a.d[v].own.YR - a.d[v].own.YL + 1);
-    bind();
-    a.rf_no_prefill = c && !c->opt_refine_prefill;
-    a.rf_rekey_far = c ? c->opt_refine_rekey_side : 0;
-    launch_refine_first(a, st);
-    launches++;
-    curB = true;
-    // settled sweeps of the large levels T per launch, time-skewed (k_refine_skew)
-    const bool skew = c && c->opt_refine_skew_from > 0 && a.upd_list && px / a.ndir >= c->opt_refine_skew_min_px && refine_skew_fits(a);
-    const int skewT = skew ? c->opt_refine_skew_T : 0;
-    // the levels below that: T sweeps per launch on overlapped tiles (k_refine_tile) -- they are bound by launch latency
-    const bool tile = c && c->opt_refine_tile_T >= 2 && a.upd_list && px / a.ndir < c->opt_refine_skew_min_px && px / a.ndir >= c->opt_refine_tile_min_px;
-    const int tileT = tile ? c->opt_refine_tile_T : 0;
-    if (c && c->opt_refine_upd_cap > 0) a.upd_cap = std::min(a.upd_cap, c->opt_refine_upd_cap);
-    if (skew || tile) (void)hipMemsetAsync(a.upd_cnt, 0, sizeof(int32_t) * 2 * RF_UPD_SHARDS, st);
-    if (skew) {
-        a.skew_prio = c->opt_refine_skew_prio;
-        a.skew_uw = (c->opt_refine_skew_uw > 0 && c->opt_refine_skew_uw <= 66 - 2 * skewT) ? c->opt_refine_skew_uw : 66 - 2 * skewT;
-        int rows, cols, strips = 0;
-        refine_interior(a, rows, cols);
-        rows = std::max(rows, 1);
-        for (int v = 0; v < a.ndir; v++) strips += refine_skew_strips(a.d[v].own, skewT, a.skew_uw);
-        // A pair that has the GPU to itself takes twice as many, half as tall chunks: its launches end in a tail of one or two
-        // waves per SIMD that nothing else fills, and a second round of workgroups shortens it; with pairs in flight the other
-        // pairs' kernels fill the tail and the extra pipeline fill only costs.
-        const bool lone = c->device < RSM_MAX_DEVICES && !c->shared_now() && g_running[c->device].load() == 1 && c->opt_refine_skew_waves_alone > 0;
-        // Below the top level, with pairs in flight, the aim has a value of its own (refine_skew_waves_low): there the launch's
-        // own time matters less than the work it costs the other pairs' kernels, and taller chunks recompute fewer halo rows.
-        const int waves = lone ? c->opt_refine_skew_waves_alone : ((!top && c->opt_refine_skew_waves_low > 0) ? c->opt_refine_skew_waves_low : c->opt_refine_skew_waves);
-        const int chunks = std::max(1, waves / std::max(1, strips));
-        a.skew_rows = c->opt_refine_skew_rows > 0 ? c->opt_refine_skew_rows : std::max(4 * skewT, (rows + chunks - 1) / chunks);
+        HIPCHK(c, hipEventRecord(c->ev_prep[k], s2));
     }
-    // the section that takes turns with the other contexts of this GPU starts once the sweeps have settled into pure
-    // streaming: the first ones are busy computing data terms (VALU) and run well beside another pair's streaming sweeps
-    bool held = false;
-    int lane = 0;
-    const int turn_from = (c && heavy_px > 0.0) ? std::min(std::max(c->opt_heavy_from_sweep, 1), iters) : iters + 1;
-    // A pair that has the GPU to itself (no other context inside rsm_run_pair on this device, no per-launch timing) runs the
-    // two directions of a time-skewed section as separate launch chains on its two streams: every skewed launch ends in a
-    // tail of one or two waves per SIMD, and the other direction's launch fills it.  With pairs in flight the other pairs'
-    // kernels do that already, and the split costs throughput (measured): not used there.
-    const bool may_split = skew && a.ndir == 2 && c->opt_refine_split && (!c->profile || c->opt_refine_split == 2) && c->stream2 != st && c->upd_list2 &&
-                           c->device < RSM_MAX_DEVICES && (c->opt_refine_split == 2 || (!c->shared_now() && g_running[c->device].load() == 1));
-    auto join = [&]() {
-        if (!split_now) return;
-        (void)hipEventRecord(c->ev_join, c->stream2);
-        (void)hipStreamWaitEvent(st, c->ev_join, 0);
-        split_now = false;
-    };
-    for (int t = 1; t < iters;) {
-        const bool skew_now = skew && t >= c->opt_refine_skew_from && t + skewT <= iters;
-        if (!skew_now) join(); // (before the lane is handed on: the section's end event must cover the second stream's launches)
-        if (c && c->opt_heavy_lanes == 2 && (int)skew_now != lane && t >= turn_from) { // the section changes kind: hand its lane on
-            heavy_end(c, held, lane);
-            held = false;
-            lane = (int)skew_now;
-        }
-        if (t >= turn_from && !held) held = heavy_begin(c, heavy_px, top, lane);
-        if (skew_now && may_split && !split_now) { // fork: the second stream continues from here -- AFTER heavy_begin's wait has
-                                                   // been enqueued on `st`, so the second direction takes turns like the first
-            (void)hipMemsetAsync(c->upd_cnt2, 0, sizeof(int32_t) * 2 * RF_UPD_SHARDS, st);
-            (void)hipEventRecord(c->ev_fork, st);
-            (void)hipStreamWaitEvent(c->stream2, c->ev_fork, 0);
-            split_now = true;
-        }
-        const bool tile_now = tile && t >= c->opt_refine_tile_from && t + tileT <= iters;
-        const int T = skew_now ? skewT : (tile_now ? tileT : 1);
-        launch(t, skew_now ? SKEW : (tile_now ? TILE : SINGLE), T);
-        t += T;
-    }
-    join();
-    heavy_end(c, held, lane);
-    *final_in_B = curB;
-    return launches;
+    launch_bad_prefix(c->msk[N - 1][0], c->Wk[N - 1], c->Hk[N - 1], c->prefix, s2);
+    launch_bad_blocks(c->prefix, c->Wk[N - 1], c->Hk[N - 1], c->blk, s2);
+    HIPCHK(c, hipEventRecord(c->ev_cloudprep, s2));
+    return RSM_OK;
 }
 
-extern "C" int rsm_run_pair(rsm_ctx *c) {
-    if (!c) return RSM_E_INVALID;
-    if (!c->have_pair) return set_err(c, RSM_E_STATE, "rsm_run_pair before rsm_upload_pair");
-    HIPCHK(c, hipSetDevice(c->device));
-    RunningGuard running(c->device, &c->in_run);
+// The mask pyramid and FindMargin for every level and view (.cpp:51-52: they depend on the masks only), down to the host.
+// Rematch -> SetBoundary_smooth exits on a degenerate margin (.cpp:827-830): every level's margin is known here, so that
+// is decided before any level is enqueued, and no side-stream work is left behind that the next call could collide with.
+static int find_margins(rsm_ctx *c) {
+    const int N = c->N;
     hipStream_t st = c->stream;
-    const int N = c->N, r = c->in.radius;
-    c->have_result = false;
-    c->ev_used = 0;
-    const double P_top_full = (double)c->Wk[N - 1] * c->Hk[N - 1];
-
-    // ConstructPyrm, .cpp:1040-1053 (top level = uploaded images).  The main stream needs the masks (margins) first;
-    // everything that depends on the images or the top mask only goes to the side stream and is made while the small
-    // levels (launch-latency bound, the GPU mostly idle) are matched: the image pyramid, every level's BGRX copy and
-    // NCC window sums (level k waits for ev_prep[k]), and the cloud's bad-pixel prefix + block map (ev_cloudprep).
-    HIPCHK(c, hipEventRecord(c->ev_pyr, st)); // everything enqueued before this run
-    HIPCHK(c, hipStreamWaitEvent(c->stream2, c->ev_pyr, 0));
-    for (int k = N - 2; k >= 0; k--)
-        for (int v = 0; v < 2; v++) launch_pyr_down(c->img[k + 1][v], c->Wk[k + 1], c->Hk[k + 1], 3, c->img[k][v], c->stream2);
-    for (int k = 0; k < N; k++) {
-        for (int v = 0; v < 2; v++) {
-            launch_bgr_to_bgrx(c->img[k][v], c->Wk[k], c->Hk[k], c->img4[k][v], c->stream2);
-            launch_box_sums(c->img4[k][v], c->Wk[k], c->Hk[k], r, c->tmp1, c->tmp2, c->S1[k][v], c->S2[k][v], c->stream2);
-            // the maps the initial match and the median filter write into start as NOMATCH everywhere (.cpp:772)
-            launch_fill_i16(c->d16i[k][v], (size_t)c->Wk[k] * c->Hk[k], (int16_t)NOMATCH, c->stream2);
-            launch_fill_i16(c->d16m[k][v], (size_t)c->Wk[k] * c->Hk[k], (int16_t)NOMATCH, c->stream2);
-            launch_fill_i16(c->d16s[k][v], (size_t)c->Wk[k] * c->Hk[k], (int16_t)NOMATCH, c->stream2);
-        }
-        HIPCHK(c, hipEventRecord(c->ev_prep[k], c->stream2));
-    }
-    launch_bad_prefix(c->msk[N - 1][0], c->Wk[N - 1], c->Hk[N - 1], c->prefix, c->stream2);
-    launch_bad_blocks(c->prefix, c->Wk[N - 1], c->Hk[N - 1], c->blk, c->stream2);
-    HIPCHK(c, hipEventRecord(c->ev_cloudprep, c->stream2));
-    const int ps1 = prof_begin(c, ST_PYRAMID);
-    for (int k = N - 2; k >= 0; k--)
-        for (int v = 0; v < 2; v++) launch_pyr_down(c->msk[k + 1][v], c->Wk[k + 1], c->Hk[k + 1], 1, c->msk[k][v], st);
-    prof_end(c, ps1, ST_PYRAMID, 2 * (N - 1), 14.0 * P_top_full);
-
-    // FindMargin for every level and view (.cpp:51-52): depends on the masks only
-    const int ps2 = prof_begin(c, ST_MARGIN);
     {
+        StageScope ps(c, ST_PYRAMID, 2 * (N - 1), 14.0 * (double)c->Wk[N - 1] * c->Hk[N - 1]);
+        for (int k = N - 2; k >= 0; k--)
+            for (int v = 0; v < 2; v++) launch_pyr_down(c->msk[k + 1][v], c->Wk[k + 1], c->Hk[k + 1], 1, c->msk[k][v], st);
+    }
+    {
+        StageScope ps(c, ST_MARGIN, 1, 0);
         const uint8_t *masks[RSM_MAX_LEVELS * 2];
         int Ws[RSM_MAX_LEVELS * 2], Hs[RSM_MAX_LEVELS * 2];
         for (int k = 0; k < N; k++)
@@ -697,11 +561,10 @@ extern "C" int rsm_run_pair(rsm_ctx *c) {
                 Ws[k * 2 + v] = c->Wk[k];
                 Hs[k * 2 + v] = c->Hk[k];
             }
-        launch_find_margin_batch(2 * N, masks, Ws, Hs, r, c->d_margins, c->h_margin_init, st);
+        launch_find_margin_batch(2 * N, masks, Ws, Hs, c->in.radius, c->d_margins, c->h_margin_init, st);
         HIPCHK(c, hipMemsetAsync(c->rf_cnt, 0, sizeof(int) * 16, st)); // the levels' wide-pixel counters
         HIPCHK(c, hipMemsetAsync(c->tie_cnt, 0, sizeof(int) * 2 * RSM_MAX_LEVELS, st));
     }
-    prof_end(c, ps2, ST_MARGIN, 1, 0);
     int hm[RSM_MAX_LEVELS * 2 * 4];
     HIPCHK(c, hipMemcpyAsync(hm, c->d_margins, sizeof(int) * N * 2 * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
@@ -710,32 +573,74 @@ extern "C" int rsm_run_pair(rsm_ctx *c) {
             const int *m = hm + (k * 2 + v) * 4;
             c->mg[k][v] = Mg{m[2], m[3], m[0], m[1]};
         }
-    // Rematch -> SetBoundary_smooth exits on a degenerate margin (.cpp:827-830).  Every level's margin is known now:
-    // decide before any level is enqueued, and leave no side-stream work behind that the next call could collide with
     for (int k = 0; k < N; k++)
         if (degenerate(c->mg[k][0]) || degenerate(c->mg[k][1])) {
             (void)hipStreamSynchronize(c->stream2);
             return set_err(c, RSM_E_DEGENERATE_MARGIN, "level %d: YL>=YR || XL>=XR", k);
         }
     launch_count_masked(c->msk[N - 1][0], c->Wk[N - 1], c->Hk[N - 1], c->mg[N - 1][0], c->d_vtop, st);
+    return RSM_OK;
+}
 
-    int par = 0; // index of the fp64 buffer holding the previous level's disparity (this is `disparity[]`)
-    for (int k = 0; k < N; k++) {
-        const int W = c->Wk[k], H = c->Hk[k];
-        StageArgs a = level_args(c, k);
-        const double Pk = 0.5 * ((double)(a.d[0].own.XR - a.d[0].own.XL + 1) * (a.d[0].own.YR - a.d[0].own.YL + 1) +
-                                 (double)(a.d[1].own.XR - a.d[1].own.XL + 1) * (a.d[1].own.YR - a.d[1].own.YL + 1));
+// UniquenessContraint (.cpp:75, :86, :109): own against other, other against own, own again
+template <typename F, typename P>
+static void uniq3(F launcher, P *p0, P *p1, int W, int H, const Mg &m0, const Mg &m1, hipStream_t st) {
+    launcher(p0, p1, W, H, m0, m1, st);
+    launcher(p1, p0, W, H, m1, m0, st);
+    launcher(p0, p1, W, H, m0, m1, st);
+}
 
-        const int ps3 = prof_begin(c, ST_BOXSUM); // what the main stream still has to wait for
-        HIPCHK(c, hipStreamWaitEvent(st, c->ev_prep[k], 0));
-        prof_end(c, ps3, ST_BOXSUM, 6, 0);
-
-        // ---- initial match (.cpp:53-62) -> d16i[k] (NOMATCH-filled by the side stream)
-        const int ps4 = prof_begin(c, ST_INITIAL_MATCH);
+// DisparityRefine (.cpp:95-98): int16 d16m[k] -> fp64, 30 + 30k Jacobi sweeps, and UniquenessContraint<double> (.cpp:109) on
+// the refined maps.  f64[par] holds the previous level's disparity; returns the buffer that holds this level's.
+static int refine_level(rsm_ctx *c, StageArgs &a, int k, int par, double Pk) {
+    hipStream_t st = c->stream;
+    const bool top = k == c->N - 1;
+    const int iters = 30 + k * 30;
+    const int ia = (par + 1) % 3, ib = (par + 2) % 3;
+    {
+        StageScope ps(c, ST_REFINE_INIT, 1, 12.0 * Pk);
         for (int v = 0; v < 2; v++) {
-            a.d[v].d16_in = c->d16i[k][v];
-            a.d[v].d16_out = c->d16i[k][v];
+            a.d[v].d16_in = c->d16m[k][v];
+            a.d[v].f64_a = c->f64[ia][v];
+            a.d[v].f64_b = c->f64[ib][v];
         }
+        launch_refine_init(a, st);
+    }
+    bool inB = false;
+    {
+        StageScope ps(c, top ? ST_REFINE_SWEEP_TOP : ST_REFINE_SWEEP, 0, 32.0 * Pk * iters);
+        a.flag = top;
+        double *bufA[2] = {c->f64[ia][0], c->f64[ia][1]}, *bufB[2] = {c->f64[ib][0], c->f64[ib][1]};
+        ps.launches = refine_sweeps(c, a, bufA, bufB, iters, st, top, &inB, Pk);
+    }
+    const int cur = inB ? ib : ia;
+    StageScope ps(c, ST_UNIQ64, 3, 72.0 * Pk);
+    uniq3(launch_uniq_f64, c->f64[cur][0], c->f64[cur][1], a.W, a.H, c->mg[k][0], c->mg[k][1], st);
+    return cur;
+}
+
+// MatchOneLayer (.cpp:36-113) for level k, stage order kept exactly.  `par` is the fp64 buffer holding the previous level's
+// disparity (this is `disparity[]`); returns the buffer holding this level's, or a negative status.
+static int match_level(rsm_ctx *c, int k, int par) {
+    hipStream_t st = c->stream;
+    const int W = c->Wk[k], H = c->Hk[k];
+    StageArgs a = level_args(c, k);
+    const double Pk = 0.5 * ((double)(a.d[0].own.XR - a.d[0].own.XL + 1) * (a.d[0].own.YR - a.d[0].own.YL + 1) +
+                             (double)(a.d[1].own.XR - a.d[1].own.XL + 1) * (a.d[1].own.YR - a.d[1].own.YL + 1));
+    auto maps = [&](int16_t *const in[2], int16_t *const out[2]) {
+        for (int v = 0; v < 2; v++) {
+            a.d[v].d16_in = in[v];
+            a.d[v].d16_out = out[v];
+        }
+    };
+    int16_t **d16i = c->d16i[k], **d16s = c->d16s[k], **d16m = c->d16m[k];
+    { // what the main stream still has to wait for
+        StageScope ps(c, ST_BOXSUM, 6, 0);
+        HIPCHK(c, hipStreamWaitEvent(st, c->ev_prep[k], 0));
+    }
+    { // initial match (.cpp:53-62) -> d16i[k] (NOMATCH-filled by the side stream)
+        StageScope ps(c, ST_INITIAL_MATCH, k == 0 ? 3 : 6, 24.0 * Pk);
+        maps(d16i, d16i);
         HIPCHK(c, hipMemsetAsync(c->wrow, 0, sizeof(int32_t) * 2 * (size_t)H, st)); // wide pixels per row of this level
         if (k == 0) {
             launch_ncc_argmax(a, 0, st);
@@ -745,99 +650,57 @@ extern "C" int rsm_run_pair(rsm_ctx *c) {
             launch_hl_interval(a, st);
             launch_ncc_argmax(a, 1, st);
         }
-        prof_end(c, ps4, ST_INITIAL_MATCH, k == 0 ? 3 : 6, 24.0 * Pk);
-
-        // ---- SmoothConstraint (.cpp:66-67): d16i[k] -> d16s[k] (both NOMATCH outside the margins: no copy)
-        const int ps5 = prof_begin(c, ST_SMOOTH);
-        for (int v = 0; v < 2; v++) {
-            a.d[v].d16_in = c->d16i[k][v];
-            a.d[v].d16_out = c->d16s[k][v];
-        }
+    }
+    { // SmoothConstraint (.cpp:66-67): d16i[k] -> d16s[k] (both NOMATCH outside the margins: no copy)
+        StageScope ps(c, ST_SMOOTH, 1, 8.0 * Pk);
+        maps(d16i, d16s);
         launch_smooth(a, st, false);
-        prof_end(c, ps5, ST_SMOOTH, 1, 8.0 * Pk);
-
-        // ---- OrderConstraint (.cpp:71-72): d16s[k] in place
-        const int ps6 = prof_begin(c, ST_ORDER);
-        for (int v = 0; v < 2; v++) a.d[v].d16_in = a.d[v].d16_out = c->d16s[k][v];
+    }
+    { // OrderConstraint (.cpp:71-72): d16s[k] in place
+        StageScope ps(c, ST_ORDER, 1, 8.0 * Pk);
+        maps(d16s, d16s);
         launch_order(a, st);
-        prof_end(c, ps6, ST_ORDER, 1, 8.0 * Pk);
-
-        // ---- UniquenessContraint<short> (.cpp:75)
-        const int ps7 = prof_begin(c, ST_UNIQ16);
-        launch_uniq_s16(c->d16s[k][0], c->d16s[k][1], W, H, c->mg[k][0], c->mg[k][1], st);
-        launch_uniq_s16(c->d16s[k][1], c->d16s[k][0], W, H, c->mg[k][1], c->mg[k][0], st);
-        launch_uniq_s16(c->d16s[k][0], c->d16s[k][1], W, H, c->mg[k][0], c->mg[k][1], st);
-        prof_end(c, ps7, ST_UNIQ16, 3, 18.0 * Pk);
-
-        // ---- Rematch (.cpp:80-81): SetBoundary_smooth + NCC on still-unmatched pixels, in place
-        const int ps8 = prof_begin(c, ST_REMATCH);
+    }
+    { // UniquenessContraint<short> (.cpp:75)
+        StageScope ps(c, ST_UNIQ16, 3, 18.0 * Pk);
+        uniq3(launch_uniq_s16, d16s[0], d16s[1], W, H, c->mg[k][0], c->mg[k][1], st);
+    }
+    { // Rematch (.cpp:80-81): SetBoundary_smooth + NCC on still-unmatched pixels, in place
+        StageScope ps(c, ST_REMATCH, 3, 46.0 * Pk);
         launch_set_boundary(a, st, true);
         launch_ncc_argmax(a, 2, st);
-        prof_end(c, ps8, ST_REMATCH, 3, 46.0 * Pk);
-
-        // ---- UniquenessContraint<short> (.cpp:86)
-        const int ps9 = prof_begin(c, ST_UNIQ16);
-        launch_uniq_s16(c->d16s[k][0], c->d16s[k][1], W, H, c->mg[k][0], c->mg[k][1], st);
-        launch_uniq_s16(c->d16s[k][1], c->d16s[k][0], W, H, c->mg[k][1], c->mg[k][0], st);
-        launch_uniq_s16(c->d16s[k][0], c->d16s[k][1], W, H, c->mg[k][0], c->mg[k][1], st);
-        prof_end(c, ps9, ST_UNIQ16, 3, 18.0 * Pk);
-
-        // ---- MedianFilter (.cpp:89-90): d16s[k] -> d16m[k] (pre-filled NOMATCH, .cpp:772)
-        const int ps10 = prof_begin(c, ST_MEDIAN);
-        for (int v = 0; v < 2; v++) {
-            a.d[v].d16_in = c->d16s[k][v];
-            a.d[v].d16_out = c->d16m[k][v];
-        }
-        launch_median(a, st);
-        prof_end(c, ps10, ST_MEDIAN, 3, 10.0 * Pk);
-
-        // ---- DisparityRefine (.cpp:95-98): int16 d16m[k] -> fp64, 30 + 30k Jacobi sweeps
-        const int iters = 30 + k * 30;
-        const int ia = (par + 1) % 3, ib = (par + 2) % 3;
-        const int ps11 = prof_begin(c, ST_REFINE_INIT);
-        for (int v = 0; v < 2; v++) {
-            a.d[v].d16_in = c->d16m[k][v];
-            a.d[v].f64_a = c->f64[ia][v];
-            a.d[v].f64_b = c->f64[ib][v];
-        }
-        launch_refine_init(a, st);
-        prof_end(c, ps11, ST_REFINE_INIT, 1, 12.0 * Pk);
-        const int st_sweep = (k == N - 1) ? ST_REFINE_SWEEP_TOP : ST_REFINE_SWEEP;
-        const int ps12 = prof_begin(c, st_sweep);
-        a.flag = (k == N - 1);
-        double *bufA[2] = {c->f64[ia][0], c->f64[ia][1]}, *bufB[2] = {c->f64[ib][0], c->f64[ib][1]};
-        bool inB = false;
-        const int nlaunch = refine_sweeps(c, a, bufA, bufB, iters, st, k == N - 1, &inB, Pk);
-        const int cur = inB ? ib : ia;
-        prof_end(c, ps12, st_sweep, nlaunch, 32.0 * Pk * iters);
-
-        // ---- UniquenessContraint<double> (.cpp:109) on the refined maps (now in f64[cur])
-        const int ps13 = prof_begin(c, ST_UNIQ64);
-        launch_uniq_f64(c->f64[cur][0], c->f64[cur][1], W, H, c->mg[k][0], c->mg[k][1], st);
-        launch_uniq_f64(c->f64[cur][1], c->f64[cur][0], W, H, c->mg[k][1], c->mg[k][0], st);
-        launch_uniq_f64(c->f64[cur][0], c->f64[cur][1], W, H, c->mg[k][0], c->mg[k][1], st);
-        prof_end(c, ps13, ST_UNIQ64, 3, 72.0 * Pk);
-        par = cur;
-        { // a launch that could not start (e.g. an LDS request the input drove too high) must not go unnoticed
-            const hipError_t le = hipGetLastError();
-            if (le != hipSuccess) {
-                (void)hipStreamSynchronize(c->stream2);
-                (void)hipStreamSynchronize(st);
-                return set_err(c, RSM_E_HIP, "level %d: kernel launch failed: %s", k, hipGetErrorString(le));
-            }
-        }
     }
+    { // UniquenessContraint<short> (.cpp:86)
+        StageScope ps(c, ST_UNIQ16, 3, 18.0 * Pk);
+        uniq3(launch_uniq_s16, d16s[0], d16s[1], W, H, c->mg[k][0], c->mg[k][1], st);
+    }
+    { // MedianFilter (.cpp:89-90): d16s[k] -> d16m[k] (pre-filled NOMATCH, .cpp:772)
+        StageScope ps(c, ST_MEDIAN, 3, 10.0 * Pk);
+        maps(d16s, d16m);
+        launch_median(a, st);
+    }
+    const int cur = refine_level(c, a, k, par, Pk);
+    // a launch that could not start (e.g. an LDS request the input drove too high) must not go unnoticed
+    const hipError_t le = hipGetLastError();
+    if (le != hipSuccess) {
+        (void)hipStreamSynchronize(c->stream2);
+        (void)hipStreamSynchronize(st);
+        return set_err(c, RSM_E_HIP, "level %d: kernel launch failed: %s", k, hipGetErrorString(le));
+    }
+    return cur;
+}
 
-    // ---- DisparityToCloud<double>(disparity[0], maskPyrm[top][0], Q, top, true) (.cpp:29)
+// DisparityToCloud<double>(disparity[0], maskPyrm[top][0], Q, top, true) (.cpp:29) from f64[par], and the run's results
+static int make_cloud(rsm_ctx *c, int par) {
+    hipStream_t st = c->stream;
+    const int k = c->N - 1, W = c->Wk[k], H = c->Hk[k];
     {
-        const int k = N - 1, W = c->Wk[k], H = c->Hk[k];
-        const int ps14 = prof_begin(c, ST_CLOUD);
+        const Mg &m = c->mg[k][0];
+        StageScope ps(c, ST_CLOUD, 4, 28.0 * (double)(m.XR - m.XL + 1) * (m.YR - m.YL + 1));
         const int ksize = (int)ceil(0.02 * H); // .cpp:703; spans, Q, R, T: upload_cloud_params
         HIPCHK(c, hipStreamWaitEvent(st, c->ev_cloudprep, 0));
-        launch_cloud(c->f64[par][0], c->prefix, c->img[k][0], W, H, ksize, c->d_cj1, c->d_cj2, c->d_q, c->d_R, c->d_T,
-                     c->mg[k][0], c->cloud_flags, c->blk, c->row_count, c->row_offset, c->d_npoints, c->xyz, c->bgr, (int64_t)c->cap_px, st);
-        const Mg &m = c->mg[k][0];
-        prof_end(c, ps14, ST_CLOUD, 4, 28.0 * (double)(m.XR - m.XL + 1) * (m.YR - m.YL + 1));
+        launch_cloud(c->f64[par][0], c->prefix, c->img[k][0], W, H, ksize, c->d_cj1, c->d_cj2, c->d_q, c->d_R, c->d_T, m,
+                     c->cloud_flags, c->blk, c->row_count, c->row_offset, c->d_npoints, c->xyz, c->bgr, (int64_t)c->cap_px, st);
     }
     int64_t np = 0;
     unsigned long long vt = 0;
@@ -850,12 +713,35 @@ extern "C" int rsm_run_pair(rsm_ctx *c) {
     c->res_disp[0] = c->f64[par][0];
     c->res_disp[1] = c->f64[par][1];
     c->have_result = true;
-    if (c->profile) {
-        for (size_t i = 0; i < c->ev_used; i++) {
-            float ms = 0;
-            if (hipEventElapsedTime(&ms, c->evpool[i].a, c->evpool[i].b) == hipSuccess) c->prof_ms[c->evpool[i].stage] += ms;
-        }
+    return RSM_OK;
+}
+
+static void collect_profile(rsm_ctx *c) { // (the run has been waited for)
+    if (!c->profile) return;
+    for (size_t i = 0; i < c->ev_used; i++) {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, c->evpool[i].a, c->evpool[i].b) == hipSuccess) c->prof_ms[c->evpool[i].stage] += ms;
     }
+}
+
+extern "C" int rsm_run_pair(rsm_ctx *c) {
+    if (!c) return RSM_E_INVALID;
+    if (!c->have_pair) return set_err(c, RSM_E_STATE, "rsm_run_pair before rsm_upload_pair");
+    HIPCHK(c, hipSetDevice(c->device));
+    RunningGuard running(c->device, &c->in_run);
+    c->have_result = false;
+    c->ev_used = 0;
+    int s = prepare_side_stream(c);
+    if (s == RSM_OK) s = find_margins(c);
+    if (s != RSM_OK) return s;
+    int par = 0;
+    for (int k = 0; k < c->N; k++) {
+        par = match_level(c, k, par);
+        if (par < 0) return par;
+    }
+    s = make_cloud(c, par);
+    if (s != RSM_OK) return s;
+    collect_profile(c);
     return RSM_OK;
 }
 
@@ -1046,44 +932,6 @@ extern "C" int rsm_match_pairs_multi_gpu(const rsm_pair_in *in, int n_pairs, int
     for (rsm_ctx *c : ctxs) rsm_destroy(c);
     return s;
 }
-
-// the one parity entry point that stays here: it runs refine_sweeps, the pair path's own scheduler
-extern "C" int rsm_stage_refine(rsm_ctx *c, const int16_t *disp_in, const uint8_t *img_own, const uint8_t *img_oth,
-                                int W, int H, int iterations, double ws, const rsm_boundary *own, double *disp_out) {
-    if (!stage_ok(c, W, H) || !disp_in || !img_own || !img_oth || !own || !disp_out || iterations < 0) return RSM_E_INVALID;
-    Tmp t(c);
-    const size_t px = (size_t)W * H;
-    StageArgs a = one_dir(c, W, H, 0, own, nullptr);
-    a.ws = ws;
-    DirArgs &d = a.d[0];
-    d.d16_in = t.up(disp_in, px);
-    d.img_own = t.up(img_own, px * 3);
-    d.img_oth = t.up(img_oth, px * 3);
-    uint32_t *i4o = t.alloc<uint32_t>(px), *i4t = t.alloc<uint32_t>(px);
-    double *A = t.alloc<double>(px), *B = t.alloc<double>(px);
-    d.rf_key = t.alloc<uint32_t>(px);
-    d.rf_ent = t.alloc<double2>(2 * px);
-    a.rf_stride = px;
-    a.upd_cap = 4096;
-    a.upd_list = t.alloc<RfUpd>((size_t)RF_UPD_SHARDS * a.upd_cap);
-    a.upd_cnt = t.alloc<int32_t>(2 * RF_UPD_SHARDS);
-    if (!t.ok) return finish(c, t);
-    if (iterations > RF_MAX_SWEEPS) return set_err(c, RSM_E_INVALID, "iterations");
-    d.f64_a = A;
-    d.f64_b = B;
-    launch_bgr_to_bgrx(d.img_own, W, H, i4o, c->stream);
-    launch_bgr_to_bgrx(d.img_oth, W, H, i4t, c->stream);
-    d.img4_own = i4o;
-    d.img4_oth = i4t;
-    launch_refine_init(a, c->stream);
-    double *bufA[2] = {A, nullptr}, *bufB[2] = {B, nullptr};
-    bool inB = false;
-    refine_sweeps(c, a, bufA, bufB, iterations, c->stream, false, &inB);
-    d.f64_a = inB ? B : A; // the buffer the last sweep wrote
-    t.down(disp_out, (const double *)d.f64_a, px);
-    return finish(c, t);
-}
-
 
 // =================================================================================================
 // Rectify (CStereoMatching.cpp:117-168): host fp64 plan + device maps / remap / grey erosion.

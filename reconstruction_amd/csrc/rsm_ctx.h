@@ -172,6 +172,29 @@ struct rsm_ctx {
 };
 
 int set_err(rsm_ctx *c, int code, const char *fmt, ...); // rsm_api.hip
+int prof_slot(rsm_ctx *c, int stage);                    // rsm_api.hip: the next event pair of the pool, booked to `stage`
+
+// contexts inside rsm_run_pair, per device: a pair that finds itself alone there schedules its refine differently (refine_plan.h)
+#define RSM_MAX_DEVICES 64
+inline std::atomic<int> g_running[RSM_MAX_DEVICES];
+struct RunningGuard {
+    int dev;
+    std::atomic<int> *own;
+    RunningGuard(int d, std::atomic<int> *in_run) : dev(d), own(in_run) {
+        if (dev < RSM_MAX_DEVICES) g_running[dev].fetch_add(1);
+        own->store(1);
+    }
+    ~RunningGuard() {
+        own->store(0);
+        if (dev < RSM_MAX_DEVICES) g_running[dev].fetch_sub(1);
+    }
+};
+
+// rsm_refine.hip: the executor of a level's refine schedule.  Returns the number of sweeps launched; *final_in_B tells which
+// buffer holds the result.  turn_px: margin pixels per direction for the turn-taking with the device's other contexts (0: none).
+int refine_sweeps(rsm_ctx *c, StageArgs &a, double *const bufA[2], double *const bufB[2], int iters, hipStream_t st, bool top,
+                  bool *final_in_B, double turn_px = 0.0);
+void heavy_forget(rsm_ctx *c); // the context goes away: nobody may wait on its turn events any more
 
 #define HIPCHK(c, call)                                                                               \
     do {                                                                                              \

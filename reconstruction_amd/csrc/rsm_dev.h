@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "refine_plan.h" // Mg, refine_interior / refine_skew_strips / refine_skew_fits: the launchers and the schedule share them
+
 #define NOMATCH (-10000) // reconstruction/CStereoMatching.h:9
 #define WAVE 64
 #define RF_MAX_SWEEPS 1024
@@ -15,11 +17,6 @@
 #define SBV_S 32 // SetBoundary: row segments per column of the vertical sweeps
 // int32 scratch of launch_set_boundary (in rf_list), per direction
 #define SETB_SCRATCH(W) ((size_t)(SBV_S * 6 + 2) * (size_t)(W))
-
-// Margin of one view at one level (struct Boundary, CManageData.h:10-14, without width/height).
-struct Mg {
-    int YL, YR, XL, XR;
-};
 
 // Everything one direction of one stage may need. Direction v: own view = v, other = 1-v
 // (IsZeroOne = (v == 0) in the reference's signatures).
@@ -119,27 +116,23 @@ void launch_refine_xi(const uint32_t *A, const uint32_t *B, int W, int H, int fo
 void launch_sqrt_check(unsigned int first, long long n, unsigned long long *mismatches, hipStream_t st); // k_filter.hip
 void launch_div_unscaled(const double *a, const double *b, double *q_fast, double *q_ieee, long long n, hipStream_t st);
 void launch_refine_init(const StageArgs &a, hipStream_t st);   // d16_in -> f64_a, f64_b, cache reset
-// interior rows / columns of the margins, the largest over the directions: what a refine launch's grid covers; false: nothing to do
+// (refine_plan.h) the grid a refine launch covers, from the stage's margins
 inline bool refine_interior(const StageArgs &a, int &rows, int &cols) {
-    rows = cols = 0;
-    for (int v = 0; v < a.ndir; v++) {
-        const Mg &m = a.d[v].own;
-        if (m.YR - m.YL - 1 > rows) rows = m.YR - m.YL - 1;
-        if (m.XR - m.XL - 1 > cols) cols = m.XR - m.XL - 1;
-    }
-    return rows > 0 && cols > 0;
+    const Mg m[2] = {a.d[0].own, a.d[1].own};
+    return refine_interior(m, a.ndir, rows, cols);
 }
 void launch_refine_first(const StageArgs &a, hipStream_t st); // the first sweep f64_a -> f64_b (k_refine_first; a.rf_no_prefill)
 // a later single sweep f64_a -> f64_b; ev0/ev1 (optional) are recorded right around the light sweep kernel
 void launch_refine_sweep(const StageArgs &a, hipStream_t st, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 void launch_refine_apply(const StageArgs &a, hipStream_t st); // k_refine.hip: the update list of launch a.rf_launch into the cache
 void launch_refine_rekey(const StageArgs &a, hipStream_t st); // k_refine.hip: both cache ways for the state a.d[].f64_a (k_refine_rekey; a.rf_rekey_far)
-// T (2..4) sweeps f64_a -> f64_b in one time-skewed launch (a.rf_launch = launch index, a.skew_rows, a.skew_uw) + the cache-update launch
+// T (2..4) sweeps f64_a -> f64_b in one time-skewed launch (a.rf_launch = launch index, a.skew_rows, a.skew_uw) + the cache-update launch.
+// PRECONDITION, the caller's to keep (refine_skew_fits, refine_plan.h; the launcher does not check it): the level is at least 80
+// columns wide and every margin lies inside rows 1 .. H - 2 and columns 1 .. W - 2.  The kernel reads rows of 68 columns from the
+// flat f64_a, rf_key and rf_ent buffers without clamping (lane 0's column may be as low as -8), and those buffers have no slack.
 void launch_refine_skew(const StageArgs &a, int T, hipStream_t st, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr); // k_refine_skew.hip
 // T (2..RF_TILE_MAXT) sweeps f64_a -> f64_b in one launch on overlapped tiles (a.rf_launch = launch index) + the cache-update launch
 void launch_refine_tile(const StageArgs &a, int T, hipStream_t st); // k_refine_tile.hip
-int refine_skew_strips(const Mg &m, int T, int uw); // strips of 64 lanes a direction's interior takes (k_refine_skew.hip)
-bool refine_skew_fits(const StageArgs &a);          // the kernel's flat over-reads stay inside the level
 
 // cloud: returns nothing; *d_npoints (device int64) receives the point count; `flags` = W*H bytes of scratch,
 // `blk` = launch_bad_blocks' map (CLOUD_BLOCKS(W,H) bytes)

@@ -1,5 +1,5 @@
 // rsm_stages.hip -- the parity and benchmark entry points of the matcher and of Rectify: one stage, host buffers in and out,
-// one direction (include/rsm.h: rsm_stage_*, rsm_bench_ncc).  rsm_stage_refine lives beside refine_sweeps in rsm_api.hip.
+// one direction (include/rsm.h: rsm_stage_*, rsm_bench_ncc).  rsm_stage_refine lives beside refine_sweeps in rsm_refine.hip.
 #include "rectify_host.h"
 #include "rsm_ctx.h"
 

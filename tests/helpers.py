@@ -138,6 +138,7 @@ def bits_equal(a, b, name=""):
 # which puts these back -- the session's context is shared, and files run in name order.
 REFINE_DEFAULTS = dict(refine_skew_from=4, refine_rekey_until=22, refine_rekey_side=0, refine_skew_uw=0, refine_skew_rows=0,
                        refine_skew_T=4, refine_skew_min_px=1000000)
+TILE_DEFAULTS = dict(refine_tile_T=4, refine_tile_from=4, refine_tile_min_px=0, refine_upd_cap=0)  # the tile kernel's (k_refine_tile)
 
 
 @contextlib.contextmanager

@@ -9,12 +9,11 @@ import pytest
 from oracle import oracle as orc
 from reconstruction_amd import synth
 
-from helpers import diff_report, oracle_stages, refine_options
+from helpers import TILE_DEFAULTS, diff_report, oracle_stages, refine_options
 from refine_cache_replay import simulate, stage_states, wave_misses
 
 RF_PPT = 4  # rows per thread of k_refine_sweep (csrc/rsm_dev.h): a wave takes 64 columns x RF_PPT rows
 # the tile schedule's defaults (csrc/rsm_ctx.h); helpers.refine_options does not know these names
-TILE_DEFAULTS = dict(refine_tile_T=4, refine_tile_from=4, refine_tile_min_px=0, refine_upd_cap=0)
 
 CASES = {  # (two of the cases of test_gpu_refine_rekey.py)
     "s192x128_ellipse": dict(width=192, height=128, levels=3, radius=2, offset=2, pair=3, mask_kind="ellipse",

@@ -10,12 +10,11 @@ import pytest
 from oracle import oracle as orc
 from reconstruction_amd import synth
 
-from helpers import diff_report, oracle_stages, refine_options
+from helpers import TILE_DEFAULTS, diff_report, oracle_stages, refine_options
 
 pytestmark = pytest.mark.gpu
 
 # the tile schedule's defaults (csrc/rsm_ctx.h); helpers.refine_options does not know these names
-TILE_DEFAULTS = dict(refine_tile_T=4, refine_tile_from=4, refine_tile_min_px=0, refine_upd_cap=0)
 TILE_MAXT = 8   # RF_TILE_MAXT (csrc/rsm_dev.h)
 TX, TY = 32, 16  # the tile a workgroup owns (csrc/k_refine_tile.hip)
 

@@ -23,7 +23,8 @@ def test_constants_are_the_kernel_source_s():
 def test_options_clamp_as_rsm_set_option():
     src = "".join(open(nr.K_MATCH.replace("k_match.hip", f)).read() for f in ("rsm_api.hip", "rsm_ctx.h"))   # rsm_set_option; struct rsm_ctx
     assert 'c->opt_ncc_mid = value <= 0 ? 0 : (int)std::max(8LL, std::min(value, 160LL));' in src
-    assert 'c->opt_ncc_slide_max = (int)std::max(0LL, std::min(value, 1000000LL));' in src
+    assert '{"ncc_slide_max", &rsm_ctx::opt_ncc_slide_max, OPT_CLAMP, 0, 1000000},' in src   # a row of the option table, stored as ...
+    assert 'o.kind == OPT_BOOL ? (int)(value != 0) : (int)std::max(o.lo, std::min(value, o.hi));' in src
     assert 'int opt_ncc_slide_max = 512;' in src
     assert nr.options(ncc_mid=1, ncc_slide_max=1 << 20) == dict(wide_rows=0, ncc_mid=8, ncc_slide_max=1000000)
     assert nr.options(ncc_mid=400) == dict(wide_rows=0, ncc_mid=160, ncc_slide_max=512)
