@@ -10,7 +10,8 @@
 struct DistStats {
     double sum, sq_sum;
     int q_sum, q_sq;
-    int bad; // a negative or non-finite distance (cannot happen; makes the host take the sequential path)
+    int bad; // a NaN distance, or one whose float32 square is not finite (a point beyond 1.8e19: its neighbours' squared distances overflow);
+             // makes the host take the sequential path
 };
 
 #define FA_SAMPLES 8192

@@ -14,8 +14,10 @@
 //   k nearest: every point within distance h of p lies in those 27 cells.  The (k+1)-th smallest squared distance tau
 //     (the point itself included, as in PCL's nearestKSearch(k + 1)) is found by bisection on its float bit pattern over
 //     [0, h^2], re-scanning the candidates per step (~900 candidates from L1/L2: cheaper than keeping 100 running minima
-//     per thread); then sum sqrt(d2) over d2 < tau + (k + 1 - #less) sqrt(tau).  The sum of <= 100 float32 values in a
-//     double is exact (no rounding as long as they span < 2^29), so its order does not matter.
+//     per thread); then sum sqrt(d2) over d2 < tau + (k + 1 - #less) sqrt(tau).  PCL adds these float32 values into a double one
+//     after the other, ascending.  The lanes add them in another order, which gives the same bits only while no addition rounds:
+//     knn_sum_exact tests that per query (every value a multiple of 2^q, the total below 2^(q + 53)) and a query that fails it --
+//     a near-duplicate beside neighbours 2^22 times as far -- gets the sequential ascending sum (knn_sum_ascending).
 //     Points with fewer than k + 1 candidates within h (isolated points -- what this filter removes -- and patch
 //     corners) go to a list and are redone against ALL points by a workgroup each (three-pass radix select).
 //   radius search: cell edge = radius, the 27 cells cover the ball.
@@ -69,16 +71,49 @@ __device__ __forceinline__ int lower_bound_key_in(const unsigned long long *__re
 }
 
 
+// ---- the k-nearest sum's order.  PCL (and oracle/cloud_oracle.c) add sqrtf of the k nearest squared distances into a double one after the
+// other, ascending.  Any other order gives the same bits as long as no addition rounds: the values are non-negative float32, each a
+// multiple of 2^q with q = (exponent of the smallest positive one) - 23, so every partial sum is a multiple of 2^q, and one below
+// 2^(q + 53) is representable.  min_m1 = the smallest positive SQUARED distance's bit pattern minus one (0xffffffff: none -- zeros add
+// exactly), total = the whole sum as the parallel order gave it (+inf / NaN fail the test).
+__device__ __forceinline__ unsigned int knn_min_m1(unsigned int min_m1, float d2) { return min(min_m1, __float_as_uint(d2) - 1u); } // (0 wraps to the top)
+__device__ __forceinline__ bool knn_sum_exact(double total, unsigned int min_m1) {
+    if (min_m1 == 0xffffffffu) return true;
+    const int e = (int)(__float_as_uint(sqrtf(__uint_as_float(min_m1 + 1u))) >> 23); // biased; the root of a positive float32 is a normal one
+    return total < __hiloint2double((e - 150 + 53 + 1023) << 20, 0);                // 2^(q + 53), q = e - 127 - 23
+}
+// The sum in PCL's order, for the queries that fail the test.  next(from, m, cnt): m = the smallest squared distance's bit pattern in
+// [from, tau) among the query's candidates, cnt = how many carry it; m >= tau's pattern: none is left (wave- or workgroup-uniform).  Equal
+// values are interchangeable, so the order among them is no choice; `ties` values equal tau itself close the sum.
+template <class Next>
+__device__ __forceinline__ double knn_sum_ascending(const Next &next, float tau, int ties) {
+    const unsigned int tau_b = __float_as_uint(tau);
+    double s = 0.0;
+    for (unsigned int from = 1u; from < tau_b;) { // (zeros add nothing)
+        unsigned int m = tau_b;
+        int cnt = 0;
+        next(from, m, cnt);
+        if (m >= tau_b) break;
+        const double v = (double)sqrtf(__uint_as_float(m));
+        for (int c = 0; c < cnt; c++) s += v;
+        from = m + 1u;
+    }
+    const double vt = (double)sqrtf(tau);
+    for (int c = 0; c < ties; c++) s += vt;
+    return s;
+}
+
 #define KNN_C 32    // registers per lane for the candidates within h
 #define KNN_CAP (64 * KNN_C)
 #define KNN_B 16    // candidate loads in flight per lane
 // The selection a wave runs for one query over M candidates `cand(c)` (squared float32 distances, NaN = no candidate): the (k+1)-th
-// smallest among those <= h2 and the exact double sum of the square roots below it.  Returns false -- nothing written but
-// `undecided` -- when fewer than `want` candidates lie within h2.  Shared by the grid search (k_sor_knn: the 27 cells of a query)
+// smallest among those <= h2 and the sum of the `want` smallest square roots (the query's own 0 among them) as PCL's sequential
+// ascending loop forms it.  Returns false -- nothing written but `undecided` -- when fewer than `want` candidates lie within h2 (or
+// the sum's order matters and the list that would order it has overflowed).  Shared by the grid search (k_sor_knn: the 27 cells of a query)
 // and the wave form of the pixel-window search (k_sor_window_wave: a window of the lattice copy).
 template <int C_ = KNN_C, class Cand>
 __device__ __forceinline__ bool wave_knn_core(const Cand &cand, int M, float h2, int want, float *mine, int lane, unsigned int *undecided_slot,
-                                              float &tau_out, double &sum_out, int &less_out, int K_pre = -1) {
+                                              double &sum_out, int K_pre = -1) {
     // K_pre >= 0: `mine` already holds the candidates within h2 (the first CAP_ of the K_pre there are, in a fixed order): the
     // workgroup form's four waves have made the first pass together
     constexpr int CAP_ = 64 * C_; // the list's capacity: C_ registers per lane in the selection
@@ -191,6 +226,7 @@ __device__ __forceinline__ bool wave_knn_core(const Cand &cand, int M, float h2,
     float tau;
     double sum = 0.0;
     int less = 0;
+    unsigned int min_m1 = 0xffffffffu; // (knn_sum_exact)
     if (K <= CAP_) {
         __builtin_amdgcn_wave_barrier();
         float d2[C_];
@@ -243,6 +279,7 @@ __device__ __forceinline__ bool wave_knn_core(const Cand &cand, int M, float h2,
             if (i < nreg && d2[i] < tau) {
                 sum += (double)sqrtf(d2[i]);
                 less++;
+                min_m1 = knn_min_m1(min_m1, d2[i]);
             }
     } else { // more than CAP_ points within h (a far too coarse first level): bisection straight on the candidates
         auto count_le = [&](float t) {
@@ -265,16 +302,31 @@ __device__ __forceinline__ bool wave_knn_core(const Cand &cand, int M, float h2,
             if (v < tau) {
                 sum += (double)sqrtf(v);
                 less++;
+                min_m1 = knn_min_m1(min_m1, v);
             }
         }
     }
     for (int o = 32; o > 0; o >>= 1) {
         sum += __shfl_xor(sum, o);
         less += __shfl_xor(less, o);
+        min_m1 = min(min_m1, (unsigned int)__shfl_xor((int)min_m1, o));
     }
-    tau_out = tau;
+    sum += (double)(want - less) * (double)sqrtf(tau); // the values equal to tau that the rank takes in
+    if (__builtin_expect(!knn_sum_exact(sum, knn_min_m1(min_m1, tau)), 0)) { // the order matters: PCL's
+        if (K > CAP_) { // (no list to add from: the query is left to the passes behind this one; the whole-cloud search at the end lists)
+            if (lane == 0) *undecided_slot = 1u;
+            return false;
+        }
+        sum = knn_sum_ascending(
+            [&](unsigned int from, unsigned int &m, int &cnt) { // (the list is still what the registers were read from)
+                for (int j = lane; j < K; j += 64) m = (__float_as_uint(mine[j]) >= from) ? min(m, __float_as_uint(mine[j])) : m;
+                for (int o = 32; o > 0; o >>= 1) m = min(m, (unsigned int)__shfl_xor((int)m, o));
+                for (int j = lane; j < K; j += 64) cnt += __float_as_uint(mine[j]) == m;
+                for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+            },
+            tau, want - less);
+    }
     sum_out = sum;
-    less_out = less;
     return true;
 }
 
@@ -351,11 +403,9 @@ __global__ __launch_bounds__(256) void k_sor_knn(const float *__restrict__ xyz, 
         const float4 o = sxyz[base + c];
         return fdist2(px, py, pz, o.x, o.y, o.z);
     };
-    float tau;
     double sum;
-    int less;
-    if (!wave_knn_core(cand, M, h2, want, s_d2[threadIdx.x >> 6], lane, &undecided[qi], tau, sum, less)) return;
-    if (lane == 0) dist_orig[orig] = (float)((sum + (double)(want - less) * (double)sqrtf(tau)) / mean_k);
+    if (!wave_knn_core(cand, M, h2, want, s_d2[threadIdx.x >> 6], lane, &undecided[qi], sum)) return;
+    if (lane == 0) dist_orig[orig] = (float)(sum / mean_k);
 }
 
 // =================================================================================================================
@@ -374,7 +424,8 @@ __global__ __launch_bounds__(256) void k_sor_knn(const float *__restrict__ xyz, 
 // sheet -- is flagged and goes to the grid ladder below.  The selection is per LANE (a query per thread, a 32 x 8 tile of
 // pixels per workgroup, the tile and its halo in LDS as float4): pass 1 bins the window's squared distances into 32
 // per-thread LDS counters over [0, 4 tau_est] (tau_est = the (k+1)/pi lateral spacings^2 of a fronto-parallel sheet), the
-// scan finds the bin holding rank k + 1, pass 2 sums sqrt(d2) of the bins below it in double (exact, order-free) and lists
+// scan finds the bin holding rank k + 1, pass 2 sums sqrt(d2) of the bins below it in double (in window order: a query is decided
+// here only if knn_sum_exact says that no addition rounded, so that the order is no choice) and lists
 // the few values of that bin, whose rank-th smallest is tau.  ~120 wave-instructions per query against ~2000 of the
 // wave-per-query grid search.
 #define WIN_PAD 40  // invalid-pixel border of the lattice copy (>= the largest window radius): no bounds checks in the loops
@@ -560,8 +611,8 @@ __device__ __forceinline__ bool win_query(const Loader &ld, const float4 P, cons
     // sequence for a few lanes nearly every time (36 instructions per candidate, round 5).  Instead every value below t_hi WAITS in
     // the lane's own column -- rows in_bin .. WIN_NB, the rows the bin's list leaves free -- and before a chunk that some lane has
     // no room for, the wave takes the square roots of everything waiting, eight rows at a time (the reads in flight together, the
-    // sequences interleaved): most lanes busy, a tenth as often.  The sum is exact in double (order-free), so its bits are those
-    // of the sum in window order.
+    // sequences interleaved): most lanes busy, a tenth as often.  That changes the order of the additions; the sum's bits are
+    // PCL's whenever none of them rounds, which knn_sum_exact tests at the end (odd_min: the smallest positive value added).
     float *lst = (float *)col;
     double sum = 0.0;
     int nl = 0;
@@ -656,7 +707,11 @@ __device__ __forceinline__ bool win_query(const Loader &ld, const float4 P, cons
     }
     if (!(nl == in_bin && tau < range) || odd_min < 0x0f7fffffu) return false;
     // every point outside the window is farther than sqrt(tau): the k + 1 smallest are all here
-    *out = (float)((sum + (double)(want - (below + less)) * (double)sqrtf(tau)) / mean_k);
+    sum += (double)(want - (below + less)) * (double)sqrtf(tau);
+    // odd_min is knn_sum_exact's min_m1 over everything added above.  A sum whose order matters (no lattice cloud produces one: DESIGN.md
+    // 9 f3) is left to the later passes, which add it in PCL's order
+    if (!knn_sum_exact(sum, knn_min_m1(odd_min, tau))) return false;
+    *out = (float)(sum / mean_k);
     return true;
 }
 
@@ -782,12 +837,9 @@ __global__ __launch_bounds__(256) void k_sor_window_wave(const float4 *__restric
         if (lane == 0) undecided[qi] = 1u;
         return;
     }
-    float tau;
     double sum;
-    int less;
-    const int want = mean_k + 1;
-    if (!wave_knn_core(cand, M, h2, want, s_d2[threadIdx.x >> 6], lane, &undecided[qi], tau, sum, less)) return;
-    if (lane == 0) dist[pt] = (float)((sum + (double)(want - less) * (double)sqrtf(tau)) / mean_k);
+    if (!wave_knn_core(cand, M, h2, mean_k + 1, s_d2[threadIdx.x >> 6], lane, &undecided[qi], sum)) return;
+    if (lane == 0) dist[pt] = (float)(sum / mean_k);
 }
 
 // Workgroup form: the wave form's query with its first pass -- every candidate of the window, those within the bound kept -- made by
@@ -841,12 +893,9 @@ __global__ __launch_bounds__(256) void k_sor_window_wg(const float4 *__restrict_
     }
     __syncthreads();
     if (w != 0) return;
-    float tau;
     double sum;
-    int less;
-    const int want = mean_k + 1;
-    if (!wave_knn_core<WG_C>(cand, M, h2, want, s_d2, lane, &undecided[qi], tau, sum, less, fits ? k0 + k1 + k2 + k3 : -1)) return;
-    if (lane == 0) dist[pt] = (float)((sum + (double)(want - less) * (double)sqrtf(tau)) / mean_k);
+    if (!wave_knn_core<WG_C>(cand, M, h2, mean_k + 1, s_d2, lane, &undecided[qi], sum, fits ? k0 + k1 + k2 + k3 : -1)) return;
+    if (lane == 0) dist[pt] = (float)(sum / mean_k);
 }
 
 size_t cloud_lattice_bytes(int XL, int XR, int YL, int YR) {
@@ -909,13 +958,16 @@ static void launch_sor_window(const float4 *lat, const WinGeom &g, int mean_k, i
 // than k): against ALL points, the whole chip on every query.  Three-pass radix select of the (k+1)-th smallest squared
 // distance (bits 30..20, 19..9, 8..0 of its pattern): per pass every workgroup histograms its slice of the points for
 // one query and adds the non-empty bins to the query's global histogram, a one-workgroup kernel picks the bin; then the
-// partial sums of sqrt(d2) over d2 < tau (exact in double for <= 100 float32 values, hence order-free) are added up.
+// slices' partial sums of sqrt(d2) over d2 < tau are added up as the workgroups retire -- PCL's bits only if no addition rounded:
+// k_xq_finish tests that (knn_sum_exact) and adds a query that fails it again, sequentially and ascending.
 #define XQ_SLICES 128
+#define XQ_LIST 4096 // values below tau a workgroup of k_xq_finish lists in LDS (more: it re-reads the points per distinct value)
 struct XqState { // per listed query
     unsigned int prefix, mask;
     int rank;
     int less;
     double sum;
+    unsigned int min_m1; // knn_sum_exact's: the smallest positive squared distance below tau, minus one
 };
 __global__ void k_xq_init(XqState *__restrict__ st, int count, int mean_k, int n) {
     const int q = blockIdx.x * blockDim.x + threadIdx.x;
@@ -925,6 +977,7 @@ __global__ void k_xq_init(XqState *__restrict__ st, int count, int mean_k, int n
     st[q].rank = min(mean_k + 1, n);
     st[q].less = 0;
     st[q].sum = 0.0;
+    st[q].min_m1 = 0xffffffffu;
 }
 __global__ __launch_bounds__(256) void k_xq_hist(const float *__restrict__ xyz, const float4 *__restrict__ sxyz, int n,
                                                   const unsigned int *__restrict__ list, int count,
@@ -979,6 +1032,7 @@ __global__ __launch_bounds__(256) void k_xq_sum(const float *__restrict__ xyz, c
                                                  XqState *__restrict__ st) {
     __shared__ double s_sum[4];
     __shared__ int s_less[4];
+    __shared__ unsigned int s_min[4];
     const int per = (n + XQ_SLICES - 1) / XQ_SLICES, q0 = blockIdx.x * per, q1 = min(n, q0 + per);
     for (int item = blockIdx.y; item < count; item += gridDim.y) {
         const unsigned int orig = list[item];
@@ -986,47 +1040,101 @@ __global__ __launch_bounds__(256) void k_xq_sum(const float *__restrict__ xyz, c
         const float tau = __uint_as_float(st[item].prefix);
         double sum = 0.0;
         int less = 0;
+        unsigned int min_m1 = 0xffffffffu;
         for (int q = q0 + threadIdx.x; q < q1; q += 256) {
             const float4 o = sxyz[q];
             const float d2 = fdist2(px, py, pz, o.x, o.y, o.z);
             if (d2 < tau) {
                 sum += (double)sqrtf(d2);
                 less++;
+                min_m1 = knn_min_m1(min_m1, d2);
             }
         }
         for (int o = 32; o > 0; o >>= 1) {
             sum += __shfl_xor(sum, o);
             less += __shfl_xor(less, o);
+            min_m1 = min(min_m1, (unsigned int)__shfl_xor((int)min_m1, o));
         }
         if ((threadIdx.x & 63) == 0) {
             s_sum[threadIdx.x >> 6] = sum;
             s_less[threadIdx.x >> 6] = less;
+            s_min[threadIdx.x >> 6] = min_m1;
         }
         __syncthreads();
         if (threadIdx.x == 0) {
             const int l = s_less[0] + s_less[1] + s_less[2] + s_less[3];
-            if (l) { // at most k values are below tau over ALL slices: the double sum is exact, any order
+            if (l) { // (the order of these additions is the workgroups': k_xq_finish accepts the sum only if none of them can have rounded)
                 atomicAdd(&st[item].sum, (s_sum[0] + s_sum[1]) + (s_sum[2] + s_sum[3]));
                 atomicAdd(&st[item].less, l);
+                atomicMin(&st[item].min_m1, min(min(s_min[0], s_min[1]), min(s_min[2], s_min[3])));
             }
         }
         __syncthreads();
     }
 }
-__global__ void k_xq_finish(const XqState *__restrict__ st, const unsigned int *__restrict__ list, int count, int mean_k,
-                            int n, float *__restrict__ dist_orig) {
-    const int q = blockIdx.x * blockDim.x + threadIdx.x;
-    if (q >= count) return;
-    const int want = min(mean_k + 1, n);
-    const float tau = __uint_as_float(st[q].prefix);
-    dist_orig[list[q]] = (float)((st[q].sum + (double)(want - st[q].less) * (double)sqrtf(tau)) / mean_k);
+// A workgroup per listed query: the mean distance from the slices' sum, or -- its order mattered -- from the sequential ascending sum
+// over the values below tau: listed in LDS by one more pass over the points (at most k of them), else read again per distinct value.
+__global__ __launch_bounds__(256) void k_xq_finish(const float *__restrict__ xyz, const float4 *__restrict__ sxyz, int n_arr, const XqState *__restrict__ st,
+                                                    const unsigned int *__restrict__ list, int count, int mean_k, int n, float *__restrict__ dist_orig) {
+    __shared__ unsigned int s_v[XQ_LIST];
+    __shared__ int s_m[4], s_c[4], s_n;
+    const int item = blockIdx.x; // (< count: the grid)
+    const int want = min(mean_k + 1, n), less = st[item].less;
+    const float tau = __uint_as_float(st[item].prefix);
+    const unsigned int orig = list[item];
+    double sum = st[item].sum + (double)(want - less) * (double)sqrtf(tau);
+    if (__builtin_expect(!knn_sum_exact(sum, knn_min_m1(st[item].min_m1, tau)), 0)) { // uniform
+        const float px = xyz[3 * (size_t)orig], py = xyz[3 * (size_t)orig + 1], pz = xyz[3 * (size_t)orig + 2];
+        const bool listed = less <= XQ_LIST;
+        if (threadIdx.x == 0) s_n = 0;
+        __syncthreads();
+        if (listed) {
+            for (int q = threadIdx.x; q < n_arr; q += 256) {
+                const float4 o = sxyz[q];
+                const float d2 = fdist2(px, py, pz, o.x, o.y, o.z);
+                if (d2 < tau && d2 > 0.0f) s_v[min(atomicAdd(&s_n, 1), XQ_LIST - 1)] = __float_as_uint(d2); // (at most less <= XQ_LIST of them)
+            }
+            __syncthreads();
+        }
+        const int nl = min(s_n, XQ_LIST);
+        sum = knn_sum_ascending(
+            [&](unsigned int from, unsigned int &m, int &cnt) { // every thread gets the workgroup's m and cnt
+                auto each = [&](auto &&f) {
+                    if (listed) {
+                        for (int j = threadIdx.x; j < nl; j += 256) f(s_v[j]);
+                    } else {
+                        for (int q = threadIdx.x; q < n_arr; q += 256) {
+                            const float4 o = sxyz[q];
+                            f(__float_as_uint(fdist2(px, py, pz, o.x, o.y, o.z)));
+                        }
+                    }
+                };
+                auto reduce = [&](auto &v, auto *s, auto &&op) { // over the workgroup, into every thread
+                    for (int o = 32; o > 0; o >>= 1) v = op(v, __shfl_xor(v, o));
+                    __syncthreads();
+                    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = v;
+                    __syncthreads();
+                    v = op(op(s[0], s[1]), op(s[2], s[3]));
+                };
+                int mi = (int)(m ^ 0x80000000u); // (shuffled and compared as int: the sign bit flipped keeps the unsigned order)
+                each([&](unsigned int u) { mi = (u >= from) ? min(mi, (int)(u ^ 0x80000000u)) : mi; });
+                reduce(mi, s_m, [](int a, int b) { return min(a, b); });
+                m = (unsigned int)mi ^ 0x80000000u;
+                cnt = 0;
+                each([&](unsigned int u) { cnt += u == m; });
+                reduce(cnt, s_c, [](int a, int b) { return a + b; });
+            },
+            tau, want - less);
+    }
+    if (threadIdx.x == 0) dist_orig[orig] = (float)(sum / mean_k);
 }
 
 // ---- sum and sum of squares of the per-point distances as PCL forms them (a sequential loop adding floats to doubles,
 // `sq_sum += d * d` with the product in float).  A parallel reduction gives the same bits whenever NO addition rounds:
 // every value is a multiple of 2^q (q = the lowest set bit over all values) and the total is below 2^(q + 53), so every
 // partial sum, in any order, is representable.  The kernel returns the sums and the two q's; the host checks the
-// condition and falls back to the sequential loop otherwise (never on the test or bench clouds).
+// condition and falls back to the sequential loop otherwise: one far point (a near-zero disparity) or one cluster of near-duplicates
+// is enough for that -- tests/cloud_range_fixtures.py's wide clouds, tests/test_gpu_cloud_filter_range.py.
 __device__ __forceinline__ int low_bit_exp(float v) { // exponent of the lowest set bit of a finite float, INT_MAX for 0
     const unsigned int u = __float_as_uint(v) & 0x7fffffffu;
     if (u == 0u) return 0x7fffffff;
@@ -1468,7 +1576,7 @@ int whole_chip_search(FilterRun &R, bool over_lattice) {
             hipLaunchKernelGGL(k_xq_pick, dim3((unsigned)cnt), dim3(64), 0, R.st, d_xq, cnt, shifts[pass], widths[pass], d_hist);
         }
         hipLaunchKernelGGL(k_xq_sum, dim3(XQ_SLICES, (unsigned)qy), dim3(256), 0, R.st, R.d_xyz, arr, arr_n, list, cnt, d_xq);
-        hipLaunchKernelGGL(k_xq_finish, blocks_for(cnt), dim3(256), 0, R.st, d_xq, list, cnt, R.mean_k, (int)R.nv, R.d_dist);
+        hipLaunchKernelGGL(k_xq_finish, dim3((unsigned)cnt), dim3(256), 0, R.st, R.d_xyz, arr, arr_n, d_xq, list, cnt, R.mean_k, (int)R.nv, R.d_dist);
     }
     return RSM_OK;
 }

@@ -7,27 +7,11 @@ import numpy as np
 import pytest
 import torch
 
+from cloud_range_fixtures import surface_cloud
 from oracle import oracle as orc
 from reconstruction_amd import synth
 
 pytestmark = pytest.mark.gpu
-
-
-def surface_cloud(n, seed, extent=60.0, outliers=200, duplicates=50):
-    """A bumpy depth-map-like patch (anisotropic sampling as a perspective camera gives it), far and near outliers,
-    exact duplicates, an isolated cluster smaller than k."""
-    rng = np.random.default_rng(seed)
-    u = rng.random((n, 2)) * [extent, 0.7 * extent] - [extent / 2, 0.35 * extent]
-    z = 600.0 + 6.0 * np.sin(u[:, 0] / 9.0) * np.cos(u[:, 1] / 7.0) + rng.normal(0, 0.03, n)
-    xyz = np.c_[u * (z[:, None] / 600.0), z]
-    idx = rng.choice(n, outliers, replace=False)
-    xyz[idx] += rng.normal(0, 1.0, (outliers, 3)) * rng.choice([0.5, 3.0, 40.0], (outliers, 1))
-    idx = rng.choice(n, duplicates, replace=False)
-    xyz[idx] = xyz[rng.choice(n, duplicates)]
-    xyz[:30] = [200.0, 150.0, 900.0] + rng.normal(0, 0.2, (30, 3))     # an island of 30 < k points
-    xyz = xyz.astype(np.float32)
-    xyz[40:44] = [[np.inf, 1.0, 2.0], [np.nan, np.nan, np.nan], [0.0, -np.inf, 5.0], [1.0, 2.0, np.nan]]   # d == 0 gives 1/0 (.cpp:745)
-    return xyz
 
 
 @pytest.mark.parametrize("n,seed,k", [(50000, 1, 100), (6000, 2, 100), (3000, 3, 20)])
