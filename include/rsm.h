@@ -369,6 +369,10 @@ int rsm_stage_div_unscaled(rsm_ctx *ctx, const double *a, const double *b, int64
  * CCloudOptimization.cpp:25-61 via pcl::StatisticalOutlierRemoval) -- the compiler's correctly rounded sequence without its
  * denormal scaling -- against sqrtf on the n floats with bit patterns first_bits .. first_bits + n - 1: *mismatches = how many differ */
 int rsm_stage_sqrt_check(rsm_ctx *ctx, uint32_t first_bits, int64_t n, int64_t *mismatches);
+/* the cloud filter's split of a window candidate c into (row, column) (csrc/win_index.h: a multiplication and, for windows past
+ * ~1625 pixels a side, one correction step) against the device's own c / ncx and c % ncx for every c < ncx * ncy (< 2^31):
+ * *mismatches = how many differ */
+int rsm_stage_win_index_check(rsm_ctx *ctx, int ncx, int ncy, int64_t *mismatches);
 /* DisparityRefine's matching costs xi = (1 - arma::dot(vecL, vecR) / (normL * normR)) / 2 (CStereoMatching.cpp:624-629) of 3x3x3
  * windows, as the device restatements of the data term compute them (form 0: the first sweep's, 1: a lane per cache miss, 2: four
  * lanes per cache miss): out[c][((y-1) (W-2) + (x-1)) (W-2) + col] = xi(own column x, row y, other view's window left edge col + c),
@@ -457,6 +461,24 @@ int rsm_filter_last_normals_info(rsm_ctx *ctx, int64_t info[2]);
  * cell, 2: per row of cells, 0: none; -1: no level ran), info[5] = bit t set when some level searched with kind t.  Option
  * "filter_ladder_h". */
 int rsm_filter_last_grid(rsm_ctx *ctx, double grid[4], int64_t info[6]);
+/* ... and the passes between the tile pass and the grid ladder of the last rsm_filter_last_cloud[_host] / rsm_stage_filter_depth_map:
+ * every pass that took a wave (k_sor_window_wave) or a workgroup (k_sor_window_wg, option "filter_wg_max") per listed query -- the 24-
+ * and 40-pixel passes where "filter_list" puts them there, then windows of 80, 160, ... pixels while at most 65536 queries are left.
+ * *n_passes = how many ran (at most head[3]); passes (capacity 4 * max_passes) receives, per pass, its window radius in pixels, the
+ * queries it was given, the queries it decided, and 1 for the workgroup form / 0 for the wave form.  head[0] = queries handed to the
+ * grid ladder (0: it did not run), head[1] = queries handed to the whole-cloud search, head[2] = 1 when that search read the lattice
+ * copy as its point array (no ladder level ran), head[3] = the most passes a report holds.  All zero when no window pass ran. */
+int rsm_filter_last_passes(rsm_ctx *ctx, int64_t head[4], int64_t *passes, int64_t max_passes, int64_t *n_passes);
+/* Stage entry for the tests: DisparityToCloud of a given top-level fp64 disparity map (rsm_stage_cloud's arguments) and the per-pair
+ * filter of that cloud exactly as rsm_filter_last_cloud runs it on the cloud of a matched pair -- the same function behind both, so
+ * every "filter_*" option and rsm_filter_last_info / _normals_info / _grid / _passes behave the same; no matching runs.  xyz (capacity
+ * 3 * max_points floats) receives the UNFILTERED points in cloud order as InsertPoint keeps them (float32), kept_index (capacity
+ * max_points) the indices of the survivors, normals (4 * max_points floats, may be NULL) theirs; *n_points / *n_kept their numbers
+ * (RSM_E_INVALID when the cloud has more than max_points points); stats as rsm_filter_cloud. */
+int rsm_stage_filter_depth_map(rsm_ctx *ctx, const double *disp, const uint8_t *mask_org, const uint8_t *img_own, int W, int H,
+                               const double *Q, double scale, const double *R_final, const double *T_final,
+                               const rsm_boundary *own, const rsm_filter_params *params, float *xyz, int32_t *kept_index,
+                               float *normals, int64_t max_points, int64_t *n_points, int64_t *n_kept, double *stats);
 /* The same with HOST output buffers (page-locked ones from rsm_host_alloc arrive at the link's rate): what a pipeline that
  * replaces the first half of CCloudOptimization::filter (CCloudOptimization.cpp:82-121) downloads instead of the raw cloud --
  * the surviving points and their oriented normals (the reference's cloud_normal, :110-121).  h_normals may be NULL. */

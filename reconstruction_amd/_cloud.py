@@ -3,7 +3,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._context import ContextBase, _normals4, _p, _views
+from ._context import ContextBase, _bd, _normals4, _p, _u8, _views
 from ._lib import FilterParams, MlsParams
 
 
@@ -51,6 +51,36 @@ class CloudPart(ContextBase):
         w = (C.c_int64 * 2)()
         self._chk(self._lib.rsm_filter_last_normals_info(self._h, w))
         return dict(window=bool(v[0]), radius=int(v[0]), undecided=int(v[1]), points=int(v[2]), kept=int(v[3]), normals_window=int(w[0]), normals_need=int(w[1]))
+
+    def filter_depth_map(self, disp, mask_org, img_own, Q, scale, R, T, own, mean_k=100, std_mul=1.0, normal_radius=2.5, cam_center=(0.0, 0.0, 0.0),
+                         max_points=None):
+        """rsm_stage_filter_depth_map: DisparityToCloud of a top-level fp64 disparity map, then the per-pair filter of that cloud as
+        filter_last_cloud runs it (same options, same filter_last_* reports) -- no matching.  Returns (xyz float32 [n,3]: the unfiltered
+        cloud, kept_index int32 [m], normals float32 [m,4], stats dict)."""
+        d = np.ascontiguousarray(disp, np.float64); mask_org = _u8(mask_org); img_own = _u8(img_own)
+        H, W = d.shape
+        Q, R, T = (np.ascontiguousarray(a, np.float64) for a in (Q, R, T))
+        cap = W * H if max_points is None else int(max_points)
+        xyz = np.zeros((max(cap, 1), 3), np.float32)
+        kept = np.zeros(max(cap, 1), np.int32)
+        nrm = np.zeros((max(cap, 1), 4), np.float32)
+        n = C.c_int64()
+        m, stats = self._filter(self._lib.rsm_stage_filter_depth_map, (_p(d), _p(mask_org), _p(img_own), W, H, _p(Q), float(scale), _p(R), _p(T), C.byref(_bd(own))),
+                                (_p(xyz), _p(kept), _p(nrm), cap, C.byref(n)), mean_k, std_mul, normal_radius, cam_center)
+        return xyz[:n.value].copy(), kept[:m].copy(), nrm[:m].copy(), stats
+
+    def filter_last_passes(self) -> dict:
+        """The passes between the tile pass and the grid ladder of the last filter_last_cloud[_host] / filter_depth_map
+        (rsm_filter_last_passes): `passes` = one dict per pass that ran a wave or a workgroup per query (radius, entered, decided,
+        workgroup), `ladder` / `whole` = the queries handed to the grid ladder / the whole-cloud search, `whole_over_lattice` = whether
+        that search read the lattice copy."""
+        head, cnt = (C.c_int64 * 4)(), C.c_int64()
+        self._chk(self._lib.rsm_filter_last_passes(self._h, head, None, 0, C.byref(cnt)))
+        rows = (C.c_int64 * (4 * max(int(head[3]), 1)))()
+        self._chk(self._lib.rsm_filter_last_passes(self._h, head, rows, int(head[3]), C.byref(cnt)))
+        passes = [dict(radius=int(rows[4 * i]), entered=int(rows[4 * i + 1]), decided=int(rows[4 * i + 2]), workgroup=bool(rows[4 * i + 3]))
+                  for i in range(int(cnt.value))]
+        return dict(passes=passes, ladder=int(head[0]), whole=int(head[1]), whole_over_lattice=bool(head[2]))
 
     def filter_last_grid(self) -> dict:
         """The k-nearest grid ladder of the last filter_cloud / filter_last_cloud[_host]: its first level's search radius h (float32),

@@ -209,6 +209,7 @@ PROTOTYPES = {
     "rsm_stage_exp_neg_small": (_I, [_V, _V, _L, _V]),
     "rsm_stage_div_unscaled": (_I, [_V, _V, _V, _L, _V, _V]),
     "rsm_stage_sqrt_check": (_I, [_V, _U, _L, _V]),
+    "rsm_stage_win_index_check": (_I, [_V, _I, _I, _V]),
     "rsm_stage_refine_xi": (_I, [_V, _V, _V, _I, _I, _I, _V]),
     "rsm_stage_cloud": (_I, [_V, _V, _V, _V, _I, _I, _V, _D, _V, _V, _BND, _V, _V, _L, _V]),
     "rsm_rectify_pair": (_I, [_V, _RIN, _I, _D, _I, _I, _ROUT]),
@@ -223,6 +224,8 @@ PROTOTYPES = {
     "rsm_filter_last_info": (_I, [_V, _V]),
     "rsm_filter_last_normals_info": (_I, [_V, _V]),
     "rsm_filter_last_grid": (_I, [_V, _V, _V]),
+    "rsm_filter_last_passes": (_I, [_V, _V, _V, _L, _V]),
+    "rsm_stage_filter_depth_map": (_I, [_V, _V, _V, _V, _I, _I, _V, _D, _V, _V, _BND, _FLT, _V, _V, _V, _L, _V, _V, _V]),
     "rsm_filter_last_cloud_host": (_I, [_V, _FLT, _V, _V, _L, _V, _V]),
     "rsm_mls_cloud": (_I, [_V, _V, _L, _V, _MLS, _V, _V, _V, _pL]),
     "rsm_mls_cloud_device": (_I, [_V, _V, _L, _V, _MLS, _V, _V, _V, _pL]),

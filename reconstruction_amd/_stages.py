@@ -177,6 +177,13 @@ class StagesPart(ContextBase):
         self._chk(self._lib.rsm_stage_sqrt_check(self._h, int(first_bits), int(n), C.byref(m)))
         return int(m.value)
 
+    def win_index_check(self, ncx, ncy):
+        """How many candidates c < ncx * ncy of an ncx x ncy window the cloud filter's (row, column) split (csrc/win_index.h) gets
+        wrong on the device, against the device's own c / ncx and c % ncx."""
+        m = C.c_int64()
+        self._chk(self._lib.rsm_stage_win_index_check(self._h, int(ncx), int(ncy), C.byref(m)))
+        return int(m.value)
+
     def disparity_to_cloud(self, disp, mask_org, img_own, Q, scale, R, T, own, max_points=None):
         """(xyz, bgr) of DisparityToCloud.  max_points: the capacity handed to the stage (default W * H, which always
         holds the cloud); when given, returns (xyz, bgr, total): the whole capacity-sized host arrays, of which the stage

@@ -23,6 +23,7 @@
 //   radius search: cell edge = radius, the 27 cells cover the ball.
 #include "../../include/rsm.h"
 #include "cloud_grid.h"
+#include "win_index.h"
 
 #include <string.h>
 
@@ -59,6 +60,23 @@ __global__ void k_sqrt_check(unsigned int first, long long n, unsigned long long
 }
 void launch_sqrt_check(unsigned int first, long long n, unsigned long long *mismatches, hipStream_t st) {
     if (n > 0) hipLaunchKernelGGL(k_sqrt_check, dim3(8192), dim3(256), 0, st, first, n, mismatches);
+}
+// test entry (rsm_stage_win_index_check): win_index.h's split against the device's own c / ncx and c % ncx on every candidate of an
+// ncx x ncy window
+__global__ void k_win_index_check(WinIndex w, long long M, unsigned long long *mismatches) {
+    const long long i0 = (long long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long long)gridDim.x * blockDim.x;
+    unsigned int bad = 0;
+    for (long long i = i0; i < M; i += stride) {
+        const int c = (int)i;
+        int r, col;
+        win_index_split(w, c, r, col);
+        bad += r != c / w.ncx || col != c % w.ncx;
+    }
+    if (bad) atomicAdd(mismatches, (unsigned long long)bad);
+}
+void launch_win_index_check(int ncx, int ncy, unsigned long long *mismatches, hipStream_t st) {
+    const long long M = (long long)ncx * ncy;
+    if (M > 0) hipLaunchKernelGGL(k_win_index_check, dim3((unsigned)std::min<long long>((M + 255) / 256, 8192)), dim3(256), 0, st, win_index_make(ncx, ncy), M, mismatches);
 }
 
 __device__ __forceinline__ int lower_bound_key_in(const unsigned long long *__restrict__ keys, int lo, int hi, unsigned long long k) {
@@ -784,15 +802,17 @@ __global__ __launch_bounds__(256) void k_sor_window_list(const float4 *__restric
 // What the wave and the workgroup form share per query: the bound and its rounding margin as win_query forms them, the largest squared
 // distance h2 that stays below it, the window clipped to the lattice copy (no point lies outside the margin's box) and the squared
 // distance to its candidate c < M, row-major.  false: no positive bound -- the query stays undecided.
-// (Row of candidate c by a multiplication: the integer division was half of the wave kernel's instructions.  It is c / ncx exactly only
-// for c ncx < 2^32 -- a window of more than 2^16 pixels a side is past that; both forms take it from here, the one place to mend it.)
+// (Row and column of candidate c: win_index.h -- a multiplication, exact on its own for windows up to ~1625 pixels a side (M ncx <= 2^32), with one
+// correction step beyond; both forms take the split from there, and tests/cpp/win_index_check.cpp and rsm_stage_win_index_check hold it against
+// / and % for every candidate of the windows the passes form.)
 struct WinCand {
     const float4 *base; // the window's first pixel
     float4 P;
-    int gw, ncx;        // the lattice copy's row length, the window's
-    unsigned int ncx_inv;
+    int gw;             // the lattice copy's row length
+    WinIndex ix;        // the window's row length and the constant of the split
     __device__ __forceinline__ float operator()(int c) const { // NaN for a pixel without a point: every comparison fails
-        const int r = ncx > 1 ? (int)__umulhi((unsigned int)c, ncx_inv) : c, col = c - r * ncx; // (ncx = 1: the reciprocal does not fit)
+        int r, col;
+        win_index_split(ix, c, r, col);
         const float4 o = base[(size_t)r * gw + col];
         return fdist2(P.x, P.y, P.z, o.x, o.y, o.z);
     }
@@ -810,12 +830,11 @@ __device__ __forceinline__ bool win_clip(const float4 *__restrict__ lat, unsigne
     if (!(range > 0.0f && isfinite(range))) return false;
     h2 = __uint_as_float(__float_as_uint(range) - 1u); // d2 <= h2 is d2 < range
     const int x0 = max(cx - WR, 0), x1 = min(cx + WR, g.gw - 1), y0 = max(cy - WR, 0), y1 = min(cy + WR, g.gh - 1);
-    cand.ncx = x1 - x0 + 1;
-    M = cand.ncx * (y1 - y0 + 1);
+    cand.ix = win_index_make(x1 - x0 + 1, y1 - y0 + 1); // (M < 2^31: the lattice copy has fewer cells)
+    M = cand.ix.ncx * (y1 - y0 + 1);
     cand.base = lat + (size_t)y0 * g.gw + x0;
     cand.P = P;
     cand.gw = g.gw;
-    cand.ncx_inv = 0xffffffffu / (unsigned int)cand.ncx + 1u;
     return true;
 }
 
@@ -1399,6 +1418,17 @@ int compact_undecided(FilterRun &R, int count, ScanTmp *keep = nullptr) {
     return RSM_OK;
 }
 
+// A pass through launch_sor_window_wave, for the caller's report (FilterLattice::passes_out): R.nq is already what it left over.
+void report_wave_pass(FilterRun &R, int radius, int entered) {
+    FilterPasses *P = R.pre->passes_out;
+    if (!P || P->n >= FILTER_MAX_PASSES) return;
+    P->radius[P->n] = radius;
+    P->entered[P->n] = entered;
+    P->decided[P->n] = entered - R.nq;
+    P->workgroup[P->n] = entered <= R.pre->wg_max; // (launch_sor_window_wave's rule)
+    P->n++;
+}
+
 // Step 2: the lattice copy (every finite point flagged undecided, d_redo2 = 0 .. n - 1) and the tile pass's window radius.
 // Which window?  pre->radius > 0: the caller's; 0: the smallest of 7 / 12 / 16 pixels that decides >= 85 % of a sparse sample of the
 // tiles (every 6th in x and y: ~3 % of the queries) -- a thin sheet (depth noise below the lateral spacing, the reference's rig
@@ -1462,12 +1492,13 @@ int list_passes(FilterRun &R, int *last) {
     const int radii[2] = {24, 40};
     for (int pass = 0; pass < 2 && R.nq > 0; pass++) {
         if (radii[pass] <= *last || !((L.list_pass >> pass) & 1)) continue;
-        if ((L.list_pass >> (3 + pass)) & 1) // (A/B: the wave form at this radius instead of the thread form)
-            launch_sor_window_wave(R.lat, R.cell_of, R.wg, R.mean_k, radii[pass], R.queries, R.nq, R.d_dist, R.d_flag, R.st, L.wg_max);
-        else
-            launch_sor_window_list(R.lat, R.cell_of, R.wg, R.mean_k, radii[pass], R.queries, R.nq, R.d_dist, R.d_flag, R.st);
+        const bool wave = (L.list_pass >> (3 + pass)) & 1; // (A/B: the wave form at this radius instead of the thread form)
+        const int entered = R.nq;
+        if (wave) launch_sor_window_wave(R.lat, R.cell_of, R.wg, R.mean_k, radii[pass], R.queries, R.nq, R.d_dist, R.d_flag, R.st, L.wg_max);
+        else launch_sor_window_list(R.lat, R.cell_of, R.wg, R.mean_k, radii[pass], R.queries, R.nq, R.d_dist, R.d_flag, R.st);
         const int s = compact_undecided(R, R.nq, &R.win_scan);
         if (s != RSM_OK) return s;
+        if (wave) report_wave_pass(R, radii[pass], entered);
         *last = radii[pass]; // (the ladder keeps its start: what is left now is few, and a level whose 27 cells hold tens of
                              // thousands of candidates costs a wave-per-query search milliseconds however few the queries)
     }
@@ -1481,9 +1512,11 @@ int wave_passes(FilterRun &R, int last) {
     const FilterLattice &L = *R.pre;
     const int span = std::max(L.XR - L.XL, L.YR - L.YL) + 1;
     for (int wr = std::max(80, 2 * last); R.nq > 0 && R.nq <= 65536; wr *= 2) {
+        const int entered = R.nq;
         launch_sor_window_wave(R.lat, R.cell_of, R.wg, R.mean_k, wr, R.queries, R.nq, R.d_dist, R.d_flag, R.st, L.wg_max);
         const int s = compact_undecided(R, R.nq, &R.win_scan);
         if (s != RSM_OK) return s;
+        report_wave_pass(R, wr, entered);
         if (wr >= span) break; // the window already covers the whole box: what is left has fewer than k + 1 points within its bound
     }
     R.wave_done = true;
@@ -1682,6 +1715,7 @@ int filter_cloud_device(FilterArena *A, const float *d_xyz, int64_t n, int mean_
         *route = FilterRoute{};
         route->h0 = h0;
     }
+    if (pre && pre->passes_out) *pre->passes_out = FilterPasses{};
     if (n <= 0) return RSM_OK;
     if (n >= (1ll << 31) || mean_k < 1 || !A) return RSM_E_INVALID;
     FilterRun R;
@@ -1710,7 +1744,10 @@ int filter_cloud_device(FilterArena *A, const float *d_xyz, int64_t n, int mean_
     // after the wave passes a handful is left at most (isolated points): straight to the whole-chip search, over the lattice copy
     // as the point array -- no grid level, no sort
     const bool skip_ladder = R.wave_done && R.nq <= 48;
+    FilterPasses *const report = pre ? pre->passes_out : nullptr;
+    if (report && !skip_ladder) report->ladder_in = R.nq;
     if (R.nq > 0 && !skip_ladder && (s = grid_ladder(R)) != RSM_OK) return s;
+    if (report) report->whole_in = R.nq, report->whole_over_lattice = R.nq > 0 && skip_ladder;
     if (R.nq > 0 && (s = whole_chip_search(R, skip_ladder)) != RSM_OK) return s;
     R.rewind();
     double thr = 0.0;

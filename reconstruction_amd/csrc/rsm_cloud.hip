@@ -6,6 +6,8 @@
 #include <cmath>
 #include <string.h>
 
+#include <vector>
+
 // ---- per-pair cloud filter (CloudOptimization/CCloudOptimization.cpp:82-121) -------------------------------------
 static int filter_params_ok(const rsm_filter_params *p) {
     return p && p->sor_mean_k >= 1 && p->sor_mean_k <= 100000 && p->normal_radius > 0.0 && p->sor_std_mul == p->sor_std_mul;
@@ -68,42 +70,56 @@ static hipStream_t filter_stream(rsm_ctx *c) {
     return c->stream_filter;
 }
 
-extern "C" int rsm_filter_last_cloud(rsm_ctx *c, const rsm_filter_params *prm, rsm_point16 *d_points, float *d_normals,
-                                     int64_t max_points, int64_t *n_kept, double *stats) {
-    if (!c || !n_kept || !filter_params_ok(prm)) return RSM_E_INVALID;
-    if (!c->have_result) return set_err(c, RSM_E_STATE, "no result");
-    HIPCHK(c, hipSetDevice(c->device));
-    *n_kept = 0;
-    const int64_t n = c->n_points;
-    if (n == 0) return RSM_OK;
-    Tmp t(c);
+// A cloud as the depth map launch_cloud made it, on the device: what the per-pair filter needs beside the points themselves.
+struct DepthCloud {
+    const uint8_t *flags;      // k_cloud's per-pixel "emitted a point" flags, W bytes a row
+    const int64_t *row_offset; // ... and its per-row offsets (first row: box.YL)
+    int W, H;                  // the level's size
+    Mg box;                    // the margin's box
+    const double *xyz;         // the n fp64 points in compaction order
+    int64_t n;
+    double qz;                 // Q[2][3] * scale (.cpp:698)
+    const double *R, *T;       // R_final, T_final (host)
+};
+// The filter's device buffers of one call (the context's arena: valid until its next reserve) and the stream the call ran on
+struct FilteredCloud {
+    float *xyz;         // the n unfiltered float32 points
+    int32_t *kept;      // first m valid
+    float4 *normals;    // first m valid (nullptr: not asked for)
+    int64_t m;
+    hipStream_t stream;
+};
+
+// From "fill the FilterLattice" to the info fields: the filter of a depth-map cloud, behind rsm_filter_last_cloud (the cloud of the last
+// rsm_run_pair) and rsm_stage_filter_depth_map (the cloud of a given disparity map).  Every "filter_*" option and every rsm_filter_last_*
+// report behaves the same behind either.
+static int filter_depth_cloud(rsm_ctx *c, const rsm_filter_params *prm, const DepthCloud &dc, bool want_normals, FilteredCloud *out, double *stats) {
+    const int64_t n = dc.n;
     float *dx, *df;
     int32_t *dk;
     float4 *dn;
-    // The cloud is the depth map this context just made: its pixel lattice (k_cloud's flags and row offsets are still in place)
+    // The cloud is a depth map: its pixel lattice (k_cloud's flags and row offsets are still in place)
     // decides most k-nearest queries (k_filter.hip: k_sor_window).  Needs R_final to be a rotation (distances in the cloud =
     // distances in the camera frame); anything else takes the generic search.
-    const int k = c->N - 1;
-    const Mg &mg = c->mg[k][0];
+    const Mg &mg = dc.box;
     FilterLattice lat{};
     bool use_lat = c->opt_filter_window && mg.XR >= mg.XL && mg.YR >= mg.YL;
     if (use_lat) {
-        const double *R = c->in.R_final;
+        const double *R = dc.R;
         for (int i = 0; i < 3 && use_lat; i++)
             for (int j = 0; j < 3; j++) {
                 double d = 0.0;
                 for (int l = 0; l < 3; l++) d += R[3 * l + i] * R[3 * l + j];
                 if (!(fabs(d - (i == j ? 1.0 : 0.0)) < 1e-9)) use_lat = false;
             }
-        const double scale = (double)c->Wk[0] / c->in.origin_width * (1 << k); // .cpp:692
-        lat.flags = c->cloud_flags;
-        lat.row_offset = c->row_offset;
-        lat.W = c->Wk[k];
+        lat.flags = dc.flags;
+        lat.row_offset = dc.row_offset;
+        lat.W = dc.W;
         lat.XL = mg.XL, lat.XR = mg.XR, lat.YL = mg.YL, lat.YR = mg.YR;
-        lat.xyz64 = c->xyz;
-        lat.qz = c->in.Q[11] * scale;
-        memcpy(lat.R, c->in.R_final, sizeof lat.R);
-        memcpy(lat.T, c->in.T_final, sizeof lat.T);
+        lat.xyz64 = dc.xyz;
+        lat.qz = dc.qz;
+        memcpy(lat.R, dc.R, sizeof lat.R);
+        memcpy(lat.T, dc.T, sizeof lat.T);
         if (!(fabs(lat.qz) > 0.0) || !std::isfinite(lat.qz)) use_lat = false;
     }
     int left = -1, tile_left = -1;
@@ -114,19 +130,21 @@ extern "C" int rsm_filter_last_cloud(rsm_ctx *c, const rsm_filter_params *prm, r
     lat.normals_wmax = std::min(c->opt_filter_normals_window, 40);
     c->filt_normals[0] = 0, c->filt_normals[1] = -1;
     lat.normals_out = c->filt_normals;
+    c->filt_passes = FilterPasses{};
+    lat.passes_out = &c->filt_passes;
     int used_radius = 0;
     lat.radius_out = &used_radius;
     lat.radius = c->opt_filter_window <= 1 ? 0 : (c->opt_filter_window <= 7 ? 7 : (c->opt_filter_window <= 12 ? 12 : (c->opt_filter_window <= 16 ? 16 : (c->opt_filter_window <= 20 ? 20 : 24))));
     // The probed radius is a property of the rig (how thick its clouds are in pixel spacings): a context remembers what the probe
     // chose for its last cloud and skips the three probe launches and their host round trips (0.6 ms of C2's 14.8) while the
     // choice keeps deciding most queries; every 8th call, a different k, a different image size or a set_option probes again.
-    const bool memo_ok = c->opt_filter_window == 1 && c->filt_memo_radius > 0 && c->filt_memo_k == prm->sor_mean_k && c->filt_memo_w == c->Wk[k] &&
-                         c->filt_memo_h == c->Hk[k] && c->filt_memo_uses < 7;
+    const bool memo_ok = c->opt_filter_window == 1 && c->filt_memo_radius > 0 && c->filt_memo_k == prm->sor_mean_k && c->filt_memo_w == dc.W &&
+                         c->filt_memo_h == dc.H && c->filt_memo_uses < 7;
     if (use_lat && memo_ok) lat.radius = c->filt_memo_radius;
-    const int sb = filter_buffers(c, n, d_normals != nullptr, &dx, &dk, &df, &dn, use_lat ? cloud_lattice_bytes(mg.XL, mg.XR, mg.YL, mg.YR) + (size_t)n * 4 + 8192 : 0);
+    const int sb = filter_buffers(c, n, want_normals, &dx, &dk, &df, &dn, use_lat ? cloud_lattice_bytes(mg.XL, mg.XR, mg.YL, mg.YR) + (size_t)n * 4 + 8192 : 0);
     if (sb != RSM_OK) return sb;
     const hipStream_t fs = filter_stream(c);
-    launch_f64_to_f32x3(c->xyz, n, dx, fs); // InsertPoint's cast, CCloudOptimization.cpp:61
+    launch_f64_to_f32x3(dc.xyz, n, dx, fs); // InsertPoint's cast, CCloudOptimization.cpp:61
     int64_t m = 0;
     const int s = filter_cloud_device(c->filt_arena, dx, n, prm->sor_mean_k, prm->sor_std_mul, prm->normal_radius, prm->cam_center, dk, df, dn, &m, stats,
                                       fs, use_lat ? &lat : nullptr, &c->filt_route);
@@ -136,8 +154,8 @@ extern "C" int rsm_filter_last_cloud(rsm_ctx *c, const rsm_filter_params *prm, r
         else if (!memo_ok && used_radius > 0) { // a fresh probe's choice
             c->filt_memo_radius = used_radius;
             c->filt_memo_k = prm->sor_mean_k;
-            c->filt_memo_w = c->Wk[k];
-            c->filt_memo_h = c->Hk[k];
+            c->filt_memo_w = dc.W;
+            c->filt_memo_h = dc.H;
             c->filt_memo_uses = 0;
         } else c->filt_memo_radius = 0; // left too much over (or no window at all): probe next time
     }
@@ -146,12 +164,103 @@ extern "C" int rsm_filter_last_cloud(rsm_ctx *c, const rsm_filter_params *prm, r
     c->filt_tile_left = tile_left >= 0 ? tile_left : 0;
     c->filt_info[2] = n;
     c->filt_info[3] = m;
+    *out = FilteredCloud{dx, dk, dn, m, fs};
+    return RSM_OK;
+}
+
+extern "C" int rsm_filter_last_cloud(rsm_ctx *c, const rsm_filter_params *prm, rsm_point16 *d_points, float *d_normals,
+                                     int64_t max_points, int64_t *n_kept, double *stats) {
+    if (!c || !n_kept || !filter_params_ok(prm)) return RSM_E_INVALID;
+    if (!c->have_result) return set_err(c, RSM_E_STATE, "no result");
+    HIPCHK(c, hipSetDevice(c->device));
+    *n_kept = 0;
+    const int64_t n = c->n_points;
+    if (n == 0) return RSM_OK;
+    Tmp t(c);
+    // the cloud is the depth map this context just made
+    const int k = c->N - 1;
+    const double scale = (double)c->Wk[0] / c->in.origin_width * (1 << k); // .cpp:692
+    const DepthCloud dc{c->cloud_flags, c->row_offset, c->Wk[k], c->Hk[k], c->mg[k][0], c->xyz, n, c->in.Q[11] * scale, c->in.R_final, c->in.T_final};
+    FilteredCloud f{};
+    const int s = filter_depth_cloud(c, prm, dc, d_normals != nullptr, &f, stats);
+    if (s != RSM_OK) return s;
+    const int64_t m = f.m;
     if (m > max_points) return set_err(c, RSM_E_INVALID, "rsm_filter_last_cloud: %lld points survive, capacity %lld", (long long)m, (long long)max_points);
-    if (m > 0 && d_points) launch_pack_filtered16(c->xyz, c->bgr, dk, m, d_points, fs);
-    if (m > 0 && d_normals) HIPCHK(c, hipMemcpyAsync(d_normals, dn, sizeof(float4) * (size_t)m, hipMemcpyDeviceToDevice, fs));
+    if (m > 0 && d_points) launch_pack_filtered16(c->xyz, c->bgr, f.kept, m, d_points, f.stream);
+    if (m > 0 && d_normals) HIPCHK(c, hipMemcpyAsync(d_normals, f.normals, sizeof(float4) * (size_t)m, hipMemcpyDeviceToDevice, f.stream));
     *n_kept = m;
-    if (fs != c->stream) HIPCHK(c, hipStreamSynchronize(fs));
+    if (f.stream != c->stream) HIPCHK(c, hipStreamSynchronize(f.stream));
     return finish(c, t);
+}
+
+// DisparityToCloud of a given top-level disparity map (rsm_stage_cloud's part) and the per-pair filter of that cloud, exactly as
+// rsm_filter_last_cloud filters the cloud of a matched pair: no matching runs, so a test can put a lattice of any width in front of the filter.
+extern "C" int rsm_stage_filter_depth_map(rsm_ctx *c, const double *disp, const uint8_t *mask_org, const uint8_t *img_own, int W, int H, const double *Q,
+                                          double scale, const double *R_final, const double *T_final, const rsm_boundary *own,
+                                          const rsm_filter_params *prm, float *xyz, int32_t *kept_index, float *normals, int64_t max_points,
+                                          int64_t *n_points, int64_t *n_kept, double *stats) {
+    if (!stage_ok(c, W, H) || !disp || !mask_org || !img_own || !Q || !R_final || !T_final || !own || !n_points || !n_kept || !filter_params_ok(prm) ||
+        max_points < 0 || (max_points > 0 && (!xyz || !kept_index)))
+        return RSM_E_INVALID;
+    const Mg box = to_mg(*own);
+    if (box.XL < 0 || box.YL < 0 || box.XR >= W || box.YR >= H) return RSM_E_INVALID;
+    *n_points = *n_kept = 0;
+    Tmp t(c);
+    const size_t px = (size_t)W * H;
+    const int ksize = (int)ceil(0.02 * H);
+    if (ksize < 1 || ksize > 4096) return RSM_E_INVALID;
+    std::vector<int> j1, j2;
+    ellipse_spans(ksize, j1, j2);
+    double q[16];
+    memcpy(q, Q, sizeof q);
+    for (int i = 0; i < 4; i++) q[i * 4 + 3] *= scale;
+    double *dd = t.up(disp, px);
+    uint8_t *dm = t.up(mask_org, px);
+    uint8_t *di = t.up(img_own, px * 3);
+    int *d1 = t.up(j1.data(), (size_t)ksize), *d2 = t.up(j2.data(), (size_t)ksize);
+    double *dq = t.up(q, 16), *dR = t.up(R_final, 9), *dT = t.up(T_final, 3);
+    int32_t *pre = t.alloc<int32_t>((size_t)(W + 1) * H);
+    int32_t *rc = t.alloc<int32_t>((size_t)H);
+    int64_t *ro = t.alloc<int64_t>((size_t)H);
+    int64_t *dn = t.alloc<int64_t>(1);
+    uint8_t *fl = t.alloc<uint8_t>(px + CLOUD_BLOCKS(W, H));
+    double *dx = max_points ? t.alloc<double>((size_t)max_points * 3) : nullptr;
+    if (!t.ok) return finish(c, t);
+    launch_bad_prefix(dm, W, H, pre, c->stream);
+    launch_bad_blocks(pre, W, H, fl + px, c->stream);
+    launch_cloud(dd, pre, di, W, H, ksize, d1, d2, dq, dR, dT, box, fl, fl + px, rc, ro, dn, dx, nullptr, max_points, c->stream);
+    int64_t n = 0;
+    t.down(&n, (const int64_t *)dn, 1);
+    if (!t.ok) return finish(c, t);
+    *n_points = n;
+    if (n > max_points) return set_err(c, RSM_E_INVALID, "rsm_stage_filter_depth_map: %lld points, capacity %lld", (long long)n, (long long)max_points);
+    if (n == 0) return finish(c, t);
+    const DepthCloud dc{fl, ro, W, H, box, dx, n, Q[11] * scale, R_final, T_final};
+    FilteredCloud f{};
+    const int s = filter_depth_cloud(c, prm, dc, normals != nullptr, &f, stats);
+    if (s != RSM_OK) return s;
+    if (f.stream != c->stream) HIPCHK(c, hipStreamSynchronize(f.stream));
+    t.later(xyz, (const float *)f.xyz, (size_t)n * 3).later(kept_index, (const int32_t *)f.kept, (size_t)f.m).later(normals, (const float *)f.normals, (size_t)f.m * 4);
+    *n_kept = f.m;
+    return finish(c, t);
+}
+
+// What the passes behind the tile pass of the last rsm_filter_last_cloud[_host] / rsm_stage_filter_depth_map did
+extern "C" int rsm_filter_last_passes(rsm_ctx *c, int64_t head[4], int64_t *passes, int64_t max_passes, int64_t *n_passes) {
+    if (!c || !head || !n_passes || max_passes < 0 || (max_passes > 0 && !passes)) return RSM_E_INVALID;
+    const FilterPasses &P = c->filt_passes;
+    head[0] = P.ladder_in;
+    head[1] = P.whole_in;
+    head[2] = P.whole_over_lattice;
+    head[3] = FILTER_MAX_PASSES;
+    *n_passes = P.n;
+    for (int i = 0; i < P.n && i < max_passes; i++) {
+        passes[4 * i] = P.radius[i];
+        passes[4 * i + 1] = P.entered[i];
+        passes[4 * i + 2] = P.decided[i];
+        passes[4 * i + 3] = P.workgroup[i];
+    }
+    return RSM_OK;
 }
 
 extern "C" int rsm_filter_last_normals_info(rsm_ctx *c, int64_t info[2]) {

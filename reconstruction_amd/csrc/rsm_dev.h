@@ -114,6 +114,7 @@ void launch_exp_neg(const double *t, double *out, long long n, hipStream_t st, i
 // k_refine_skew's division without operand scaling beside the compiler's a / b (tests)
 void launch_refine_xi(const uint32_t *A, const uint32_t *B, int W, int H, int form, double *out, hipStream_t st); // the data term's matching costs (tests)
 void launch_sqrt_check(unsigned int first, long long n, unsigned long long *mismatches, hipStream_t st); // k_filter.hip
+void launch_win_index_check(int ncx, int ncy, unsigned long long *mismatches, hipStream_t st);            // k_filter.hip: win_index.h on the device
 void launch_div_unscaled(const double *a, const double *b, double *q_fast, double *q_ieee, long long n, hipStream_t st);
 void launch_refine_init(const StageArgs &a, hipStream_t st);   // d16_in -> f64_a, f64_b, cache reset
 // (refine_plan.h) the grid a refine launch covers, from the stage's margins
@@ -170,6 +171,18 @@ void *filter_arena_host(FilterArena *a);                   // 64 bytes of its pi
 // The cloud as the depth map it is (rsm_filter_last_cloud): which pixels of the top level's margin box emitted a point (k_cloud's
 // flags + per-row offsets: point index = compaction order), the fp64 points, and the geometry that bounds how far a point outside
 // a pixel window can be (k_filter.hip: k_sor_window).  R_final must be a rotation (the caller checks).
+// What the passes behind the tile pass did (rsm_filter_last_passes): every pass that ran in the wave or the workgroup form -- the 24- / 40-pixel
+// passes when "filter_list" puts them there, then 80, 160, ... -- and what reached the searches behind them.
+#define FILTER_MAX_PASSES 16
+struct FilterPasses {
+    int n = 0;                                    // passes recorded
+    int radius[FILTER_MAX_PASSES] = {};           // window radius in pixels
+    int entered[FILTER_MAX_PASSES] = {};          // queries the pass was given
+    int decided[FILTER_MAX_PASSES] = {};          // queries it decided
+    int workgroup[FILTER_MAX_PASSES] = {};        // 1: four waves per query (k_sor_window_wg), 0: a wave per query (k_sor_window_wave)
+    int ladder_in = 0;                            // queries handed to the grid ladder (0: it did not run)
+    int whole_in = 0, whole_over_lattice = 0;     // queries handed to the whole-cloud search; whether it read the lattice copy as its point array
+};
 struct FilterLattice {
     const uint8_t *flags;
     const int64_t *row_offset;
@@ -185,6 +198,7 @@ struct FilterLattice {
     int wg_max;         // the wave passes take four waves per query (k_sor_window_wg) while at most this many queries are left (default 2048)
     int normals_wmax;   // the normals' radius search on the lattice copy while no point needs a window wider than this (0: always on a grid of radius-cells)
     int *normals_out;   // optional, 2 ints: the window the normals used (0: the grid), the widest window a point needed
+    FilterPasses *passes_out; // optional: what the wave passes, the ladder and the whole-cloud search were given
 };
 // The k-nearest grid ladder's route (option "filter_ladder_h", rsm_filter_last_grid): which levels decide a query, never its result.
 struct FilterRoute {

@@ -361,6 +361,23 @@ extern "C" int rsm_stage_sqrt_check(rsm_ctx *c, uint32_t first_bits, int64_t n, 
     return rc;
 }
 
+// the wide-window passes' candidate split (win_index.h) against the device's / and % on every candidate of an ncx x ncy window
+extern "C" int rsm_stage_win_index_check(rsm_ctx *c, int ncx, int ncy, int64_t *mismatches) {
+    if (!c || !mismatches || ncx < 1 || ncy < 1 || (int64_t)ncx * ncy >= (1ll << 31)) return RSM_E_INVALID;
+    *mismatches = 0;
+    if (hipSetDevice(c->device) != hipSuccess) return set_err(c, RSM_E_HIP, "hipSetDevice");
+    Tmp t(c);
+    unsigned long long *d = t.alloc<unsigned long long>(1);
+    if (!t.ok) return finish(c, t);
+    if (hipMemsetAsync(d, 0, sizeof(unsigned long long), c->stream) != hipSuccess) return set_err(c, RSM_E_HIP, "hipMemsetAsync");
+    launch_win_index_check(ncx, ncy, d, c->stream);
+    unsigned long long h = 0;
+    t.down(&h, d, 1);
+    const int rc = finish(c, t);
+    *mismatches = (int64_t)h;
+    return rc;
+}
+
 // DisparityRefine's matching costs xi (CStereoMatching.cpp:624-629) as the device restatements of the data term compute them:
 // lets the parity tests hold them to the compiled reference's own values (tests/golden: xi_table_*), bit for bit.
 extern "C" int rsm_stage_refine_xi(rsm_ctx *c, const uint8_t *img_own, const uint8_t *img_oth, int W, int H, int form, double *out) {
