@@ -361,25 +361,30 @@ __global__ __launch_bounds__(64 * ORD_NW) void k_order(StageArgs a, int maxL) {
     }
 }
 
-void launch_order(const StageArgs &a, hipStream_t st) {
+hipError_t launch_order(const StageArgs &a, hipStream_t st) {
     int rows = 0, maxL = 0;
     for (int v = 0; v < a.ndir; v++) {
         rows = max(rows, a.d[v].own.YR - a.d[v].own.YL + 1);
         maxL = max(maxL, a.d[v].own.XR - a.d[v].own.XL + 1);
     }
-    if (rows <= 0 || maxL <= 0) return;
+    if (rows <= 0 || maxL <= 0) return hipSuccess;
     maxL = (maxL + 63) & ~63;
     const size_t lds = (size_t)maxL * 6 + ((size_t)maxL / 64 + 1) * 12 + ((size_t)maxL / ORD_BIG + 1) * 4;
-    if (lds > 65536) // margins wider than ~10 k columns: beyond the default 64 KB of dynamic LDS per workgroup
-        (void)hipFuncSetAttribute((const void *)k_order, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (lds > 65536) { // margins wider than ~10 k columns: beyond the default 64 KB of dynamic LDS per workgroup
+        // without the attribute the row does not fit: nothing is launched, and the caller reports the status
+        const hipError_t e = hipFuncSetAttribute((const void *)k_order, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
     hipLaunchKernelGGL(k_order, dim3(rows, 1, a.ndir), dim3(64 * ORD_NW), lds, st, a, maxL);
+    return hipSuccess;
 }
 
 // ---------------------------------------------------------------- UniquenessContraint_<T>
 // Sequential dependency of the reference: the rescue test at .cpp:492 reads p[x-1] AFTER it may have
 // been killed.  With  g(x) = valid && (direct || rescue by the untouched p[x+1])  and
 // h(x) = valid && !direct && |q[bL+1] + p_orig[x-1]| < 2,  alive(x) = g(x) || (h(x) && alive(x-1)):
-// a carry chain, resolved per 64-pixel chunk with ballots and a Kogge-Stone prefix on the masks.
+// a carry chain, resolved per 64-pixel chunk with ballots and a Kogge-Stone prefix on the masks.  (A p[x-1] that is not alive
+// reads NOMATCH, so where q[bL+1] is within 2 of -NOMATCH the test holds against it: n(x), the chunk's serial path below.)
 template <typename T>
 __device__ __forceinline__ bool close2(T q, T p);
 template <>
@@ -405,7 +410,7 @@ __global__ void k_uniq(T *__restrict__ P, const T *__restrict__ Q, int W, int H,
         if (lane == 0) pm1 = prev_last;
         CT pp1 = (CT)__shfl_down(raw, 1);
         if (lane == 63) pp1 = (x + 1 <= XR + 1 && x + 1 < W) ? (CT)p[x + 1] : (CT)NOMATCH;
-        bool g = false, h = false;
+        bool g = false, h = false, n = false;
         if (valid) {
             const int bL = max((int)(raw + 0.5) + x - 1, XL1); // .cpp:482 (C truncation)
             const int bR = min(bL + 2, XR1);
@@ -426,13 +431,27 @@ __global__ void k_uniq(T *__restrict__ P, const T *__restrict__ Q, int W, int H,
             else {
                 g = close2<CT>(qv, pp1);
                 h = close2<CT>(qv, pm1);
+                n = close2<CT>(qv, (CT)NOMATCH);
             }
         }
         unsigned long long G = __ballot(g), Pm = __ballot(h);
-        G |= Pm & cin; // carry into lane 0
-        for (int s = 1; s < 64; s <<= 1) {
-            G |= Pm & (G << s);
-            Pm &= (Pm << s);
+        const unsigned long long Nm = __ballot(n);
+        if (Nm == 0) {
+            G |= Pm & cin; // carry into lane 0
+            for (int s = 1; s < 64; s <<= 1) {
+                G |= Pm & (G << s);
+                Pm &= (Pm << s);
+            }
+        } else {
+            // q[bL+1] within 2 of +10000 (a column offset only rows wider than 10000 have): a p[x-1] that is not alive READS
+            // NOMATCH at .cpp:492 and the test holds against it -- alive(x) = g(x) || (alive(x-1) ? h(x) : n(x)), no longer
+            // monotone in alive(x-1).  Wave-uniform and rare: the chunk's 64 bits are resolved one after the other.
+            unsigned long long A = 0, c = cin;
+            for (int i = 0; i < 64; i++) {
+                c = ((G | (c ? Pm : Nm)) >> i) & 1ull;
+                A |= c << i;
+            }
+            G = A;
         }
         const bool alive = (G >> lane) & 1ull;
         if (valid && !alive) p[x] = (T)NOMATCH;

@@ -659,7 +659,12 @@ static int match_level(rsm_ctx *c, int k, int par) {
     { // OrderConstraint (.cpp:71-72): d16s[k] in place
         StageScope ps(c, ST_ORDER, 1, 8.0 * Pk);
         maps(d16s, d16s);
-        launch_order(a, st);
+        const hipError_t oe = launch_order(a, st);
+        if (oe != hipSuccess) {
+            (void)hipStreamSynchronize(c->stream2);
+            (void)hipStreamSynchronize(st);
+            return set_err(c, RSM_E_HIP, "level %d: OrderConstraint's margin rows do not fit the LDS: %s", k, hipGetErrorString(oe));
+        }
     }
     { // UniquenessContraint<short> (.cpp:75)
         StageScope ps(c, ST_UNIQ16, 3, 18.0 * Pk);

@@ -104,7 +104,7 @@ void launch_hl_interval(const StageArgs &a, hipStream_t st);
 void launch_ncc_argmax(const StageArgs &a, int mode, hipStream_t st);
 
 void launch_smooth(const StageArgs &a, hipStream_t st, bool copy_outside = true); // d16_in -> d16_out
-void launch_order(const StageArgs &a, hipStream_t st);         // d16_in in place
+hipError_t launch_order(const StageArgs &a, hipStream_t st);   // d16_in in place; an error: nothing was launched
 void launch_uniq_s16(int16_t *p, const int16_t *q, int W, int H, Mg own, Mg oth, hipStream_t st);
 void launch_uniq_f64(double *p, const double *q, int W, int H, Mg own, Mg oth, hipStream_t st);
 // d16_in, mask_own -> BL, BR; emit_list: also fill rf_list / ncc_cnt with the pixels Rematch has to evaluate

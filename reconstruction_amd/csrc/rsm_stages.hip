@@ -221,7 +221,12 @@ extern "C" int rsm_stage_order(rsm_ctx *c, int16_t *disp, int W, int H, const rs
     StageArgs a = one_dir(c, W, H, 0, own, nullptr);
     a.d[0].d16_in = a.d[0].d16_out = t.up(disp, px);
     if (!t.ok) return finish(c, t);
-    launch_order(a, c->stream);
+    const hipError_t oe = launch_order(a, c->stream);
+    if (oe != hipSuccess) {
+        (void)finish(c, t);
+        return set_err(c, RSM_E_HIP, "OrderConstraint: a margin row of %d columns does not fit the LDS: %s", own->XR - own->XL + 1,
+                       hipGetErrorString(oe));
+    }
     t.down(disp, a.d[0].d16_in, px);
     return finish(c, t);
 }

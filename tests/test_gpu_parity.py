@@ -420,3 +420,38 @@ def test_refine_time_skewed_sweeps_are_bit_identical(ctx, T, first, rows, uw):
             res = ctx.match_pair(cfg)
             for v in range(2):
                 assert np.array_equal(res.disparity[v], fin["disparity"][v])
+
+
+def wide_pair_config(height=64):
+    """A one-level pair 12288 wide whose margins are 11048 columns: beyond the 10432 up to which OrderConstraint's row fits
+    64 KB of LDS.  LowestLevelInitialMatch scores every masked pixel against every masked candidate of the other margin, so
+    on the full mask the oracle needs minutes for a single row of this width; the masks keep 40 columns of every 256 (the
+    margin is the masks' extent and stays as wide), with which the oracle takes about 10 s for the 48 margin rows."""
+    cfg = synth.config_small(width=12288, height=height, levels=1, radius=2, offset=2, pair=0, mask_l0_width=11264, border_l0=8)
+    m0, m1 = cfg.mask
+    sh = int(np.nonzero(m1.any(axis=0))[0][0] - np.nonzero(m0.any(axis=0))[0][0])
+    assert sh >= 0
+    m0 = np.where((np.arange(cfg.width) % 256 < 40)[None, :], m0, 0).astype(np.uint8)
+    m1 = np.zeros_like(m0)
+    m1[:, sh:] = m0[:, :cfg.width - sh]
+    cfg.mask = [m0, m1]
+    return cfg
+
+
+def test_wide_pair_beyond_64k_of_order_lds_matches_oracle(ctx):
+    """The pair path (two directions per launch) on margin rows that need more than 64 KB of dynamic LDS in k_order: margins,
+    both maps, point count, colours and XYZ bit for bit."""
+    cfg = wide_pair_config()
+    ref = orc.match_pair(cfg)
+    for v in range(2):
+        YL, YR, XL, XR = ref["margin"][v][:4]
+        assert XR - XL + 1 > 10432 and YR - YL + 1 >= 40
+        assert (ref["disparity"][v] != NOMATCH).sum() > 20000
+    res = ctx.match_pair(cfg)
+    assert res.margin == ref["margin"]
+    assert res.v_top == ref["v_top"]
+    for v in range(2):
+        assert np.array_equal(res.disparity[v], ref["disparity"][v]), diff_report("wide pair map %d" % v, res.disparity[v], ref["disparity"][v])
+    assert res.n_points == ref["n_points"] > 10000
+    assert np.array_equal(res.bgr, ref["bgr"])
+    assert np.array_equal(res.xyz, ref["xyz"], equal_nan=True)
