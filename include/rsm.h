@@ -446,7 +446,7 @@ int rsm_filter_last_cloud(rsm_ctx *ctx, const rsm_filter_params *params, rsm_poi
                           int64_t max_points, int64_t *n_kept, double *stats);
 /* What the last rsm_filter_last_cloud[_host] of this context did: info[0] = the radius (pixels) of the pixel-window k-nearest pass,
  * 0 when it did not run (the cloud of a matched pair is a depth map: the k nearest of most points lie within a small pixel window
- * around their own pixel, proven per point by a bound on the distance to every ray outside it -- csrc/k_filter.hip; the radius --
+ * around their own pixel, proven per point by a bound on the distance to every ray outside it -- csrc/k_filter_win.hip; the radius --
  * 7, 12 or 16 -- comes from a sparse probe), info[1] = queries it left to the generic grid search, info[2] = points in, info[3] =
  * points kept.  Option "filter_window" (rsm_set_option): 1 = probe (default), 0 = no window pass, 7 / 12 / 16 / 20 / 24 = that
  * radius (A/B; the results are the same bits either way). */

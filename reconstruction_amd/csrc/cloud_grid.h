@@ -1,4 +1,4 @@
-// cloud_grid.h -- the radius-cell grid of the cloud kernels (k_filter.hip's searches, k_mls.hip; built by cloud_grid.hip) and PCL's eigen33
+// cloud_grid.h -- the radius-cell grid of the cloud kernels (k_filter_knn.hip's searches, k_filter.hip's normals, k_mls.hip; built by cloud_grid.hip) and PCL's eigen33
 // in double.
 // Points sorted by the key of a uniform grid (cell edge h): the 27 cells around a point are 9 contiguous ranges of the
 // sorted array (ranges9), found by binary search on the keys.

@@ -1,4 +1,4 @@
-// dev_prims.h -- the host plumbing the cloud units (cloud_grid.hip, k_filter.hip, k_mls.hip, k_dedup.hip) and the mesh units (k_poisson.hip,
+// dev_prims.h -- the host plumbing the cloud units (cloud_grid.hip, k_filter*.hip, k_mls.hip, k_dedup.hip) and the mesh units (k_poisson.hip,
 // k_meshclean.hip, k_meshcolor.hip, k_meshstitch.hip) share: the error check, the grid of a thread-per-element launch, rocprim's scan and
 // sort with their temporary taken from the caller's allocator, the read-back of a compaction's total, the order-preserving map between
 // float and unsigned int behind the exact bounding boxes, and the kernels that renumber a mesh's kept faces and vertices.

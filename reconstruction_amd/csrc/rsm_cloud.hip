@@ -99,7 +99,7 @@ static int filter_depth_cloud(rsm_ctx *c, const rsm_filter_params *prm, const De
     int32_t *dk;
     float4 *dn;
     // The cloud is a depth map: its pixel lattice (k_cloud's flags and row offsets are still in place)
-    // decides most k-nearest queries (k_filter.hip: k_sor_window).  Needs R_final to be a rotation (distances in the cloud =
+    // decides most k-nearest queries (k_filter_win.hip: k_sor_window).  Needs R_final to be a rotation (distances in the cloud =
     // distances in the camera frame); anything else takes the generic search.
     const Mg &mg = dc.box;
     FilterLattice lat{};

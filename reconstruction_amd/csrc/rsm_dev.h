@@ -113,7 +113,7 @@ void launch_median(const StageArgs &a, hipStream_t st);        // d16_in -> d16_
 void launch_exp_neg(const double *t, double *out, long long n, hipStream_t st, int small_form); // the specified exp(-t) (tests)
 // k_refine_skew's division without operand scaling beside the compiler's a / b (tests)
 void launch_refine_xi(const uint32_t *A, const uint32_t *B, int W, int H, int form, double *out, hipStream_t st); // the data term's matching costs (tests)
-void launch_sqrt_check(unsigned int first, long long n, unsigned long long *mismatches, hipStream_t st); // k_filter.hip
+void launch_sqrt_check(unsigned int first, long long n, unsigned long long *mismatches, hipStream_t st); // k_filter.hip: knn_select.h's sqrtf_rn on the device
 void launch_win_index_check(int ncx, int ncy, unsigned long long *mismatches, hipStream_t st);            // k_filter.hip: win_index.h on the device
 void launch_div_unscaled(const double *a, const double *b, double *q_fast, double *q_ieee, long long n, hipStream_t st);
 void launch_refine_init(const StageArgs &a, hipStream_t st);   // d16_in -> f64_a, f64_b, cache reset
@@ -170,7 +170,7 @@ void *filter_arena_alloc(FilterArena *a, size_t bytes);    // caller buffers tha
 void *filter_arena_host(FilterArena *a);                   // 64 bytes of its pinned host block that no cloud step uses itself: free for the caller (after a reserve)
 // The cloud as the depth map it is (rsm_filter_last_cloud): which pixels of the top level's margin box emitted a point (k_cloud's
 // flags + per-row offsets: point index = compaction order), the fp64 points, and the geometry that bounds how far a point outside
-// a pixel window can be (k_filter.hip: k_sor_window).  R_final must be a rotation (the caller checks).
+// a pixel window can be (k_filter_win.hip: k_sor_window; win_bound.h).  R_final must be a rotation (the caller checks).
 // What the passes behind the tile pass did (rsm_filter_last_passes): every pass that ran in the wave or the workgroup form -- the 24- / 40-pixel
 // passes when "filter_list" puts them there, then 80, 160, ... -- and what reached the searches behind them.
 #define FILTER_MAX_PASSES 16
@@ -210,7 +210,7 @@ struct FilterRoute {
     int kind0 = -1;         // out: the first level's cell table kind (-1: no level ran)
     int kinds = 0;          // out: bit t set when a level searched with table kind t (k_sor_knn<t>)
 };
-size_t cloud_lattice_bytes(int XL, int XR, int YL, int YR);
+size_t cloud_lattice_bytes(int XL, int XR, int YL, int YR); // k_filter_win.hip
 int filter_cloud_device(FilterArena *a, const float *d_xyz, int64_t n, int mean_k, double std_mul, double normal_radius,
                         const float cam_center[3], int32_t *d_kept_index, float *d_fxyz, float4 *d_normals, int64_t *n_kept,
                         double stats[4], hipStream_t st, const FilterLattice *pre = nullptr, FilterRoute *route = nullptr);

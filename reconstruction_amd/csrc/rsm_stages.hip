@@ -348,7 +348,7 @@ extern "C" int rsm_stage_div_unscaled(rsm_ctx *c, const double *a_in, const doub
     return finish(c, t);
 }
 
-// the cloud filter's trimmed sqrtf (k_filter.hip: sqrtf_rn) against the compiler's on the floats with bit patterns first .. first + n - 1
+// the cloud filter's trimmed sqrtf (knn_select.h: sqrtf_rn) against the compiler's on the floats with bit patterns first .. first + n - 1
 extern "C" int rsm_stage_sqrt_check(rsm_ctx *c, uint32_t first_bits, int64_t n, int64_t *mismatches) {
     if (!c || !mismatches || n < 0 || (uint64_t)first_bits + (uint64_t)n > (1ull << 32)) return RSM_E_INVALID;
     *mismatches = 0;

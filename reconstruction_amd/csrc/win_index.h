@@ -1,5 +1,5 @@
 // win_index.h -- candidate c of a pixel window, row-major, as (row, column): the one copy of that split, for the wave and the workgroup
-// form of the cloud filter's wide-window passes (k_filter.hip: WinCand) and for the programs that hold it against / and %
+// form of the cloud filter's wide-window passes (k_filter_win.hip: WinCand) and for the programs that hold it against / and %
 // (tests/cpp/win_index_check.cpp with plain g++; rsm_stage_win_index_check on the device).
 //
 // DOMAIN: a window of ncx >= 1 columns and ncy >= 1 rows with M = ncx * ncy < 2^31, c in [0, M) -- every window win_clip can form: it is

@@ -1,4 +1,4 @@
-"""Sparse, WIDE depth maps for the cloud filter's wide-window passes (csrc/k_filter.hip: wave_passes, k_sor_window_wave / _wg over
+"""Sparse, WIDE depth maps for the cloud filter's wide-window passes (csrc/k_filter.hip: wave_passes, csrc/k_filter_win.hip: k_sor_window_wave / _wg over
 windows of 80 ... 2560 pixels; tests/test_gpu_cloud_filter_wide.py).  No GPU here: the maps, the numpy restatement of DisparityToCloud
 and of win_clip's bound and window clipping, and what each map claims about itself (tests/test_cloud_lattice_cpu.py checks the
 claims, so the GPU tests cannot pass for the wrong reason).
@@ -22,8 +22,9 @@ import math
 import numpy as np
 
 NOMATCH = -10000.0
-WIN_PAD = 40                                     # k_filter.hip
+WIN_PAD = 40                                     # win_bound.h
 WAVE_RADII = (80, 160, 320, 640, 1280, 2560, 5120)
+KNN_CHUNK, WAVE_LIST, WG_LIST = 1024, 2048, 4096  # knn_select.h: 64 KNN_B candidates a chunk, the wave form's list; k_sor_window_wg's (quarters of 1024)
 BASELINE = 100.0
 
 
@@ -148,6 +149,20 @@ class WideMap:
             first[:] = 0
         return tau2, first, clear
 
+    def listed(self, P32, xs, ys, i, WR):
+        """The gather of the wave and workgroup forms for cloud point i at radius WR, restated: (K = the candidates of its clipped window
+        within the bound -- float32 squared distances below win_clip's `range` --, how many of them each of the workgroup form's four
+        waves lists: wave w takes the chunks w, w + 4, ... of KNN_CHUNK row-major candidates)."""
+        cx, cy = int(xs[i]) - self.XL + WIN_PAD, int(ys[i]) - self.YL + WIN_PAD
+        x0, x1, y0, y1 = max(cx - WR, 0), min(cx + WR, self.gw - 1), max(cy - WR, 0), min(cy + WR, self.gh - 1)
+        gx, gy = xs - self.XL + WIN_PAD, ys - self.YL + WIN_PAD
+        d = P32[i][None, :] - P32
+        d2 = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+        assert d2.dtype == np.float32
+        inside = (gx >= x0) & (gx <= x1) & (gy >= y0) & (gy <= y1) & (d2 < np.float32(self.bound2(P32[i:i + 1], WR)[0]))
+        c = (gy[inside] - y0) * (x1 - x0 + 1) + (gx[inside] - x0)
+        return int(inside.sum()), np.bincount((c // KNN_CHUNK) % 4, minlength=4)
+
 
 def bare_split_wrong(ncx, ncy):
     """(how many, the first) of the candidates c < ncx * ncy which the multiplication alone (row = umulhi(c, ceil(2^32 / ncx))) splits
@@ -228,5 +243,19 @@ def thick_sheet(k):
     return m
 
 
+def dense_f3000(k):
+    """660 x 180, f = 3000, R_final = I -- small, but with more candidates within a window's bound than the lists of the wave and workgroup
+    forms hold.  `over_a`: 182 pixels beside a 72 x 72 patch, decided at 320 pixels with all 5184 of the patch inside the bound: more than
+    the wave form's 2048 and the workgroup form's 4096 -- the histogram narrowing -- and more than 1024 in a quarter -- the workgroup
+    form's fallback to one wave's gather.  `fits_b`: 100 pixels beside a 56 x 56 patch, decided at 160 pixels with ~2900 inside the bound:
+    the workgroup form's list where the wave form's has overflowed, every quarter within its 1024."""
+    m = WideMap("dense_f3000", 660, 180, 3000, False, k, 16)
+    m.patch("patch_a", 185, 40, 72).satellite("over_a", 1, 75, 320)
+    m.patch("patch_b", 330, 48, 56).satellite("fits_b", 486, 75, 160)
+    m.covers = {160, 320}
+    return m
+
+
 MAPS = dict(wide_f10000=wide_f10000, tall_f10000=tall_f10000, wide_f3000=wide_f3000, lone_f3000=lone_f3000)
+DENSE_MAPS = dict(dense_f3000=dense_f3000)       # (not wide: apart from test_cloud_lattice_cpu.py's claims about wide boxes)
 KS = (8, 30)

@@ -4,7 +4,7 @@ flip of :378-385.  Test infrastructure only (oracle/ stays as it is); no scipy.
 
 Per finite input point p:
   neighbours: the finite q with float32 (dx*dx + dy*dy) + dz*dz < r*r (p included); fewer than 3: no output;
-  plane: double centroid c, de-meaned covariance sum (q - c)(q - c)^T, eigen33 (PCL's, as k_filter.hip's pcl_plane_from_cov):
+  plane: double centroid c, de-meaned covariance sum (q - c)(q - c)^T, eigen33 (PCL's, as cloud_grid.h's pcl_plane_from_cov):
     normal n of the smallest eigenvalue, curvature |lambda / trace|; pt = p - (n.p - n.c) n;
   polynomial fit (order > 0, at least (order + 1)(order + 2) / 2 neighbours): v = n.unitOrthogonal() (Eigen), u = n x v,
     e = q - pt, w = exp(-(e.e) / r^2), terms uc^i vc^j in PCL's order, (P W P^T) c = P W f by Cholesky (a pivot that is not

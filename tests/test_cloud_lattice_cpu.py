@@ -125,6 +125,37 @@ def test_clipped_windows_where_the_bare_multiplication_went_wrong():
         assert m.window(*m.islands["far_row1100"][0], 2560)[:2] == (m.gw, m.gh)
 
 
+@pytest.mark.parametrize("k", F.KS)
+def test_the_dense_map_overflows_the_lists_of_the_wave_and_workgroup_forms(k):
+    """dense_f3000's two satellites, from the gather restated in numpy (WideMap.listed): every point of `over_a` is first bounded at 320
+    pixels, where more candidates lie within its bound than the wave form's list (2048) and the workgroup form's (4096) hold, more than
+    1024 of them in one wave's quarter -- the histogram narrowing of wave_knn_select in both forms, and k_sor_window_wg's fallback to one
+    wave's gather; every point of `fits_b` at 160 pixels with more than 2048 and at most 4096, no quarter above 1024 -- the workgroup form's
+    list put together from its quarters.  The third branch behind the selection, the ascending re-sum, no depth map reaches through a
+    window: every distance a window accepts is one from the query, at least its distance to the next pixel's ray (~ a lateral spacing) and
+    below the bound (< (WR + 1) spacings), so k + 1 of them stay below 2^30 times the smallest -- asserted here with 2^8 to spare; the tie
+    cloud of tests/cloud_range_fixtures.py reaches it through the grid search, which shares the code."""
+    m = F.dense_f3000(k)
+    P, xs, ys = m.cloud()
+    ix = m.index_of(xs, ys)
+    assert m.gw < 800 and m.gh < 300 and len(P) < 9000
+    for isl, radius, over in (("over_a", 320, True), ("fits_b", 160, False)):
+        idx = np.array([ix[p] for p in m.islands[isl]])
+        tau2, first, clear = m.first_radius(P, idx)
+        assert clear.all() and (first == radius).all() and m.expect[isl] == radius and (tau2 > 1.02 * m.bound2(P[idx], 40)).all()
+        for i in idx:
+            K, quarters = m.listed(P, xs, ys, i, radius)
+            print("%s k %d %s point %d: %d candidates within the bound at %d pixels, per wave %s" % (m.name, k, isl, i, K, radius, quarters))
+            assert quarters.sum() == K and K > F.WAVE_LIST
+            if over:
+                assert K > F.WG_LIST and quarters.max() > F.WG_LIST // 4
+            else:
+                assert K <= F.WG_LIST and quarters.max() <= F.WG_LIST // 4
+            d = np.sqrt(((P[i].astype(np.float64) - P.astype(np.float64)) ** 2).sum(1))
+            d = np.sort(d[d > 0])[:k]
+            assert d.sum() < 2.0 ** 22 * d[0]
+
+
 def test_the_thick_sheet_sends_more_than_65536_queries_past_the_list_passes():
     """A sample of 64 of its points: for each the (k + 1)-th nearest lies beyond the bound of the 40-pixel window (with 2 % to spare) and within
     that of a wave pass.  Were that true of fewer than 3/4 of all points, a sample like this had a chance of 1e-8; 3/4 of them are more

@@ -86,7 +86,7 @@ def test_tie_cloud_gives_the_ascending_sum_every_time(ctx):
 
 def test_tie_motif_in_the_grid_search(ctx):
     """The tie cloud beside a sheet 600 away, k = 8, the ladder pinned to start at h = 2: the origin's query is decided by the grid
-    search's selection (k_sor_knn / wave_knn_core) on the first level, the motif's other points there or on the second (h = 4),
+    search's selection (k_sor_knn / wave_knn) on the first level, the motif's other points there or on the second (h = 4),
     which runs because the sheet's outliers leave more than the 48 queries at which the ladder hands over to the whole-cloud
     search.  From the second level on the ladder sees what it sees for the sheet alone, so the same queries reach the whole-cloud
     search as for the sheet alone: none of the motif's."""

@@ -1,4 +1,4 @@
-"""The cloud filter's wide-window passes on WIDE lattices (csrc/k_filter.hip: wave_passes -- k_sor_window_wave / k_sor_window_wg over windows
+"""The cloud filter's wide-window passes on WIDE lattices (csrc/k_filter.hip: wave_passes -- k_filter_win.hip's k_sor_window_wave / k_sor_window_wg over windows
 of 80 ... 2560 pixels and the pass that covers the box -- the whole-cloud search over a lattice copy of millions of cells, the hand-over at
 65536 queries): the sparse depth maps of tests/cloud_lattice_fixtures.py (margin boxes of ~2700 x 1400 and 1400 x 2700 pixels, a few thousand
 points) through rsm_stage_filter_depth_map, which filters a given depth map exactly as rsm_filter_last_cloud filters a matched pair's.
@@ -6,6 +6,7 @@ Every map three ways, all points taking part: against the same call with the pix
 oracle/cloud_oracle.c (PCL's statistical outlier removal by brute force) and against rsm_filter_cloud on the downloaded cloud -- kept set,
 normals and the statistics' bits -- with `filter_wg_max` 0 / 2048 / 1 << 30 and `filter_list` 4 / 23 / 31; and rsm_filter_last_passes must
 say that the routes the maps are built for were taken (tests/test_cloud_lattice_cpu.py holds the maps to their claims without a GPU).
+One small map more, dense_f3000, the same three ways: more candidates within a window's bound than the lists of the two forms hold.
 Also here: csrc/win_index.h -- the candidate split of those windows -- against the device's own division."""
 import numpy as np
 import pytest
@@ -54,7 +55,7 @@ def _prepare(maker, k):
 def _runs(ctx, name, k):
     """Every call of one map (memoised: the coverage test at the end reads the reports of all of them)"""
     if (name, k) not in _memo:
-        m, ix = _prepare(F.MAPS[name], k)
+        m, ix = _prepare({**F.MAPS, **F.DENSE_MAPS}[name], k)
         predicted = {}   # wave radius -> satellite points whose k + 1 nearest it is the first to bound
         for isl, px in m.islands.items():
             if "_hub" in isl or isl.startswith("patch"):
@@ -87,7 +88,7 @@ def _check_report(run, fl, wg, predicted):
 
 
 @pytest.mark.parametrize("k", F.KS)
-@pytest.mark.parametrize("name", list(F.MAPS))
+@pytest.mark.parametrize("name", list(F.MAPS) + list(F.DENSE_MAPS))
 def test_wide_lattice_three_ways(ctx, name, k):
     R = _runs(ctx, name, k)
     m, generic = R["m"], R["generic"]
@@ -119,6 +120,11 @@ def test_wide_lattice_three_ways(ctx, name, k):
             widths = [m.window(*m.islands[isl][0], 1280)[0] for isl in ("edge_2540", "edge_2494")]
             assert widths == [2540, 2494] and all(1626 < w < m.gw for w in widths)
             assert by_radius[1280]["decided"] >= len(m.islands["edge_2540"]) + len(m.islands["edge_2494"])
+        if name == "dense_f3000":
+            # more candidates within the bound than the lists hold (test_cloud_lattice_cpu.py counts them): at 160 pixels the workgroup form's
+            # list where the wave form's overflows and narrows, at 320 both narrow, the workgroup form after a quarter has overflowed
+            assert by_radius[160]["decided"] >= len(m.islands["fits_b"]) and by_radius[320]["decided"] >= len(m.islands["over_a"])
+            assert by_radius[320]["workgroup"] == (wg > 0)
         if name == "lone_f3000":
             # the lone points and the lone island: no window bounds their k + 1 nearest; few enough to skip the ladder -- the whole-cloud
             # search reads the lattice copy (4 million cells) as its point array

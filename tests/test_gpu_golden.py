@@ -162,7 +162,7 @@ def test_hip_unscaled_division_is_the_ieee_division_inside_its_guard(ctx):
 
 
 def test_the_cloud_filters_trimmed_sqrt_is_sqrtf_on_every_float(ctx):
-    """k_filter.hip: sqrtf_rn -- the correctly rounded float32 square root the k-nearest sums take (PCL: sqrt of the float32 squared
+    """knn_select.h: sqrtf_rn -- the correctly rounded float32 square root the k-nearest sums take (PCL: sqrt of the float32 squared
     distances, pcl::StatisticalOutlierRemoval behind CCloudOptimization.cpp:25-61) as the compiler's sequence without its denormal
     scaling and zero / infinity test -- against the device's sqrtf on EVERY non-negative float: the 1.88 G patterns from 2^-96 to
     FLT_MAX that take the trimmed sequence, zero, and the patterns below 2^-96, infinity and the NaNs that take sqrtf itself."""
