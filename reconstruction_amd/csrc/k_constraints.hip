@@ -4,7 +4,11 @@
 //   uniq<T>       CStereoMatching::UniquenessContraint_  .cpp:463-497  (one wave per row, carry chain)
 //   set_boundary  CStereoMatching::SetBoundary_smooth    .cpp:817-942  (column sweeps, then row sweeps)
 //   median        CStereoMatching::MedianFilter          .cpp:763-815
+// Rules stated once: the wave scans, lane masks and reductions are wave_prims.h's (each stage keeps its own chunk carry); every launcher's
+// grid comes from margin_extent (rsm_dev.h); k_order's LDS is laid out by OrdLds, its row is compacted by ord_walk_valid, a removal is
+// ord_remove under ord_crosses; a SetBoundary segment's map is an SbvRec (rsm_dev.h), applied by sbv_apply.
 #include "rsm_dev.h"
+#include "wave_prims.h"
 
 __device__ __forceinline__ bool in_margin(const Mg &m, int x, int y) {
     return x >= m.XL && x <= m.XR && y >= m.YL && y <= m.YR;
@@ -61,15 +65,11 @@ __global__ void k_smooth(StageArgs a) {
 }
 
 void launch_smooth(const StageArgs &a, hipStream_t st, bool copy_outside) {
-    int rows = 0, cols = 0;
-    for (int v = 0; v < a.ndir; v++) {
-        if (copy_outside) // the caller may know that both maps already agree outside the margin (NOMATCH there)
-            (void)hipMemcpyAsync(a.d[v].d16_out, a.d[v].d16_in, (size_t)a.W * a.H * sizeof(int16_t), hipMemcpyDeviceToDevice, st);
-        rows = max(rows, a.d[v].own.YR - a.d[v].own.YL + 1);
-        cols = max(cols, a.d[v].own.XR - a.d[v].own.XL + 1);
-    }
-    if (rows <= 0 || cols <= 0) return;
-    hipLaunchKernelGGL(k_smooth, dim3((cols + 255) / 256, rows, a.ndir), dim3(256), 0, st, a);
+    for (int v = 0; v < a.ndir && copy_outside; v++) // the caller may know that both maps already agree outside the margin (NOMATCH there)
+        (void)hipMemcpyAsync(a.d[v].d16_out, a.d[v].d16_in, (size_t)a.W * a.H * sizeof(int16_t), hipMemcpyDeviceToDevice, st);
+    const Extent e = margin_extent(a);
+    if (e.rows <= 0 || e.cols <= 0) return;
+    hipLaunchKernelGGL(k_smooth, dim3((e.cols + 255) / 256, e.rows, a.ndir), dim3(256), 0, st, a);
 }
 
 // ---------------------------------------------------------------- OrderConstraint
@@ -86,6 +86,60 @@ void launch_smooth(const StageArgs &a, hipStream_t st, bool copy_outside) {
 #define ORD_BIG 48
 #define ORD_U 8
 #define ORD_NW 4 // waves per row: wave 0 does the serial passes, all of them the counting and the greedy loops
+// The dynamic LDS of a row of at most maxL valid pixels (maxL a multiple of 64), as byte offsets: the kernel indexes with it, the
+// launcher sizes with it.
+struct OrdLds {
+    static constexpr size_t blocks(size_t maxL) { return maxL / 64 + 1; }                // 64-element blocks of the list
+    static constexpr size_t line(size_t maxL) { return 0; }                              // int16 [maxL] m of the valid pixels, ascending x
+    static constexpr size_t cnt(size_t maxL) { return line(maxL) + 2 * maxL; }           // int16 [maxL] prefix max, later crossing counts (-1 = removed)
+    static constexpr size_t comps(size_t maxL) { return cnt(maxL) + 2 * maxL; }          // uint32 [maxL / 2] components with crossings: first | last << 16
+    static constexpr size_t ends(size_t maxL) { return comps(maxL) + 4 * (maxL / 2); }   // uint64 [blocks] bit i: a component ends at i
+    static constexpr size_t bmx(size_t maxL) { return ends(maxL) + 8 * blocks(maxL); }   // int16 [blocks] max of every 64-element block
+    static constexpr size_t bmn(size_t maxL) { return bmx(maxL) + 2 * blocks(maxL); }    // int16 [blocks] min of every 64-element block
+    static constexpr size_t bigq(size_t maxL) { return bmn(maxL) + 2 * blocks(maxL); }   // uint32 [maxL / ORD_BIG + 1] the long components
+    static constexpr size_t bytes(size_t maxL) { return bigq(maxL) + 4 * (maxL / ORD_BIG + 1); }
+};
+static_assert(OrdLds::bytes(10432) == 65432 && OrdLds::bytes(10496) == 65832, "the widest row under 64 KB and the first over it (ORDER_WIDE_WIDTHS)");
+
+// j and i cross: their order along the row and the order of their matches m = p + x disagree (a set entry of the reference's matrix A)
+__device__ __forceinline__ bool ord_crosses(int j, int mj, int i, int mi) { return (j < i && mj > mi) || (j > i && mj < mi); }
+
+// Wave-uniform walk of a row's valid pixels in compaction order (ascending x): f(column, value, position in the list) for each of
+// them, the lane's own; returns how many there are.  ORD_U row segments in flight: the pass is load latency.
+template <class F>
+__device__ __forceinline__ int ord_walk_valid(const int16_t *p, int XL, int XR, int lane, const F &f) {
+    int n = 0;
+    for (int x0 = XL; x0 <= XR; x0 += 64 * ORD_U) {
+        int v[ORD_U];
+#pragma unroll
+        for (int u = 0; u < ORD_U; u++) {
+            const int x = x0 + u * 64 + lane;
+            v[u] = (x <= XR) ? (int)p[x] : NOMATCH;
+        }
+#pragma unroll
+        for (int u = 0; u < ORD_U; u++) {
+            const bool valid = v[u] != NOMATCH;
+            const unsigned long long m = __ballot(valid);
+            if (valid) f(x0 + u * 64 + lane, v[u], n + ballot_rank(m, lane));
+            n += __popcll(m);
+        }
+    }
+    return n;
+}
+
+// One greedy removal (.cpp:359-361), the part that touches the others: pixel bi of the component [cs, ce] goes, and every pixel
+// still there that it crossed -- inside the component and the window -- has one crossing less.  The caller's share of the
+// candidates is every stride-th one from the first-th on; marking bi itself (cnt = -1) is the caller's.
+__device__ __forceinline__ void ord_remove(const int16_t *line, int16_t *cnt, int bi, int cs, int ce, int win, int first, int stride) {
+    const int mb = line[bi];
+    const int j0 = max(cs, bi - win), j1 = min(ce, bi + win);
+    for (int j = j0 + first; j <= j1; j += stride) {
+        const int c = cnt[j];
+        if (c < 0 || j == bi) continue; // removed pixels have no edges left
+        if (ord_crosses(j, line[j], bi, mb)) cnt[j] = (int16_t)(c - 1);
+    }
+}
+
 __global__ __launch_bounds__(64 * ORD_NW) void k_order(StageArgs a, int maxL) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     __shared__ int s_n, s_win, s_go, s_ncomp, s_nbig, s_removed, s_bv[ORD_NW], s_bi[ORD_NW];
@@ -93,15 +147,12 @@ __global__ __launch_bounds__(64 * ORD_NW) void k_order(StageArgs a, int maxL) {
     const int y = d.own.YL + blockIdx.x;
     if (y > d.own.YR) return;
     const int W = a.W, XL = d.own.XL, XR = d.own.XR;
-    int16_t *line = (int16_t *)smem;                    // [maxL] m of the valid pixels, ascending x
-    int16_t *cnt = line + maxL;                         // [maxL] prefix max, later crossing counts (-1 = removed)
-    uint32_t *comps = (uint32_t *)(cnt + maxL);         // [maxL / 2] components with crossings: first | last << 16
-    unsigned long long *ends = (unsigned long long *)(comps + maxL / 2); // [maxL / 64 + 1] bit i: a component ends at i
-    int16_t *bmx = (int16_t *)(ends + maxL / 64 + 1), *bmn = bmx + maxL / 64 + 1; // max / min of every 64-element block
-    uint32_t *bigq = (uint32_t *)(bmn + maxL / 64 + 1); // [maxL / ORD_BIG + 1] the long components
+    int16_t *line = (int16_t *)(smem + OrdLds::line(maxL)), *cnt = (int16_t *)(smem + OrdLds::cnt(maxL));
+    uint32_t *comps = (uint32_t *)(smem + OrdLds::comps(maxL)), *bigq = (uint32_t *)(smem + OrdLds::bigq(maxL));
+    unsigned long long *ends = (unsigned long long *)(smem + OrdLds::ends(maxL));
+    int16_t *bmx = (int16_t *)(smem + OrdLds::bmx(maxL)), *bmn = (int16_t *)(smem + OrdLds::bmn(maxL));
     int16_t *p = d.d16_in + (size_t)y * W;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const unsigned long long lt = (1ull << lane) - 1ull; // lanes below this one
     if (tid == 0) {
         s_go = 0;
         s_ncomp = 0;
@@ -110,64 +161,37 @@ __global__ __launch_bounds__(64 * ORD_NW) void k_order(StageArgs a, int maxL) {
     }
     __syncthreads();
     if (wv == 0) {
-        int n = 0, pmin = 0x7fffffff, pmax = -0x7fffffff;
-        for (int x0 = XL; x0 <= XR; x0 += 64 * ORD_U) { // ORD_U row segments in flight: the pass is load latency
-            int v[ORD_U];
-#pragma unroll
-            for (int u = 0; u < ORD_U; u++) {
-                const int x = x0 + u * 64 + lane;
-                v[u] = (x <= XR) ? (int)p[x] : NOMATCH;
-            }
-#pragma unroll
-            for (int u = 0; u < ORD_U; u++) {
-                const bool valid = v[u] != NOMATCH;
-                const unsigned long long m = __ballot(valid);
-                if (valid) {
-                    line[n + __popcll(m & lt)] = (int16_t)(v[u] + x0 + u * 64 + lane);
-                    pmin = min(pmin, v[u]);
-                    pmax = max(pmax, v[u]);
-                }
-                n += __popcll(m);
-            }
-        }
+        int pmin = 0x7fffffff, pmax = -0x7fffffff;
+        const int n = ord_walk_valid(p, XL, XR, lane, [&](int x, int v, int k) {
+            line[k] = (int16_t)(v + x);
+            pmin = min(pmin, v);
+            pmax = max(pmax, v);
+        });
         // prefix max (kept in cnt for now); a row that is already non-decreasing has no crossings at all
         bool inv = false;
         int carry = -32768;
         for (int c0 = 0; c0 < n; c0 += 64) {
             const int i = c0 + lane;
             const int own = (i < n) ? (int)line[i] : -32768;
-            int v = own;
-#pragma unroll
-            for (int s = 1; s < 64; s <<= 1) {
-                const int o = __shfl_up(v, s);
-                if (lane >= s) v = max(v, o);
-            }
+            int v = wave_scan<true>(own, lane, [](int l, int r) { return max(l, r); });
             if (lane == 63) bmx[c0 >> 6] = (int16_t)v; // the block's own max (before the carry) ...
             v = max(v, carry);
             inv = inv || (i < n && own < v);
             if (i < n) cnt[i] = (int16_t)v;
             carry = __shfl(v, 63);
-            int mn = (i < n) ? own : 32767; // ... and min
-            for (int o = 32; o > 0; o >>= 1) mn = min(mn, __shfl_xor(mn, o));
+            const int mn = wave_min((i < n) ? own : 32767); // ... and min
             if (lane == 0) bmn[c0 >> 6] = (int16_t)mn;
         }
         if (n >= 2 && __any(inv)) {
-            for (int o = 32; o > 0; o >>= 1) {
-                pmin = min(pmin, __shfl_xor(pmin, o));
-                pmax = max(pmax, __shfl_xor(pmax, o));
-            }
+            pmin = wave_min(pmin);
+            pmax = wave_max(pmax);
             // suffix min -> where components end
             carry = 32767;
             for (int c = ((n + 63) >> 6) - 1; c >= 0; c--) {
                 const int i = c * 64 + lane;
-                int v = (i < n) ? (int)line[i] : 32767;
-#pragma unroll
-                for (int s = 1; s < 64; s <<= 1) {
-                    const int o = __shfl_down(v, s);
-                    if (lane + s < 64) v = min(v, o);
-                }
-                v = min(v, carry);           // min(m_i ..)
-                int nxt = __shfl_down(v, 1); // min(m_i+1 ..)
+                int v = wave_scan<false>((i < n) ? (int)line[i] : 32767, lane, [](int l, int r) { return min(l, r); });
+                v = min(v, carry);                // min(m_i ..)
+                int nxt = wave_prev<false>(v);    // min(m_i+1 ..)
                 if (lane == 63) nxt = carry;
                 const bool end = i < n && (i == n - 1 || (int)cnt[i] <= nxt);
                 const unsigned long long e = __ballot(end);
@@ -208,9 +232,9 @@ __global__ __launch_bounds__(64 * ORD_NW) void k_order(StageArgs a, int maxL) {
             }
         }
         if (i < n) {
-            unsigned long long m = E & ~lt; // ends at or after i
+            unsigned long long m = E & lanes_from(lane); // ends at or after i
             ce = m ? c0 + __builtin_ctzll(m) : next_end;
-            m = E & lt;                     // ends before i
+            m = E & lanes_below(lane);                   // ends before i
             cs = m ? c0 + 64 - __builtin_clzll(m) : prev_end + 1;
             head = (i == cs) && (ce > cs);
         }
@@ -223,11 +247,7 @@ __global__ __launch_bounds__(64 * ORD_NW) void k_order(StageArgs a, int maxL) {
             j0 = max(cs, i - win);
             j1 = min(ce, i + win);
         }
-        int lo = j0, hi = j1;
-        for (int o = 32; o > 0; o >>= 1) {
-            lo = min(lo, __shfl_xor(lo, o));
-            hi = max(hi, __shfl_xor(hi, o));
-        }
+        const int lo = wave_min(j0), hi = wave_max(j1);
         for (int b = lo >> 6; hi >= 0 && b <= (hi >> 6); b++) { // uniform
             const int t0 = b << 6, t1 = min(t0 + 63, n - 1);
             const int mx = bmx[b], mn = bmn[b];
@@ -246,7 +266,7 @@ __global__ __launch_bounds__(64 * ORD_NW) void k_order(StageArgs a, int maxL) {
             if (__any(scan)) {
                 for (int t = t0; t <= t1; t++) {
                     const int v = line[t];
-                    if (scan) k += (t >= j0 && t < i && v > mi) || (t > i && t <= j1 && v < mi);
+                    if (scan) k += t >= j0 && t <= j1 && ord_crosses(t, v, i, mi);
                 }
             }
         }
@@ -254,7 +274,7 @@ __global__ __launch_bounds__(64 * ORD_NW) void k_order(StageArgs a, int maxL) {
         int base = 0;
         if (hm && lane == 0) base = atomicAdd(&s_ncomp, __popcll(hm));
         base = __shfl(base, 0);
-        if (head) comps[base + __popcll(hm & lt)] = (uint32_t)cs | ((uint32_t)ce << 16);
+        if (head) comps[base + ballot_rank(hm, lane)] = (uint32_t)cs | ((uint32_t)ce << 16);
         // (the prefix max in cnt is no longer needed: the ends are final)
         if (i < n) cnt[i] = (int16_t)k;
     }
@@ -278,13 +298,7 @@ __global__ __launch_bounds__(64 * ORD_NW) void k_order(StageArgs a, int maxL) {
                 }
             }
             if (bv <= 0) break; // no crossing left here (.cpp:354)
-            const int mb = line[bi];
-            for (int j = max(cs, bi - win); j <= min(ce, bi + win); j++) {
-                const int c = cnt[j];
-                if (c < 0 || j == bi) continue; // removed pixels have no edges left
-                const int mj = line[j];
-                if ((j < bi && mj > mb) || (j > bi && mj < mb)) cnt[j] = (int16_t)(c - 1);
-            }
+            ord_remove(line, cnt, bi, cs, ce, win, 0, 1);
             cnt[bi] = -1; // row/col of A zeroed (.cpp:359-361)
             s_removed = 1;
         }
@@ -324,14 +338,7 @@ __global__ __launch_bounds__(64 * ORD_NW) void k_order(StageArgs a, int maxL) {
                     bi = s_bi[w];
                 }
             if (bv <= 0) break; // uniform
-            const int mb = line[bi];
-            const int j0 = max(cs, bi - win), j1 = min(ce, bi + win);
-            for (int j = j0 + tid; j <= j1; j += 64 * ORD_NW) {
-                const int c = cnt[j];
-                if (c < 0 || j == bi) continue;
-                const int mj = line[j];
-                if ((j < bi && mj > mb) || (j > bi && mj < mb)) cnt[j] = (int16_t)(c - 1);
-            }
+            ord_remove(line, cnt, bi, cs, ce, win, tid, 64 * ORD_NW);
             if (tid == 0) {
                 cnt[bi] = -1;
                 s_removed = 1;
@@ -342,40 +349,23 @@ __global__ __launch_bounds__(64 * ORD_NW) void k_order(StageArgs a, int maxL) {
     }
     __syncthreads();
     if (!s_removed || wv != 0) return;
-    // the removed pixels become NOMATCH (.cpp:363): same compaction order as above
-    int k = 0;
-    for (int x0 = XL; x0 <= XR; x0 += 64 * ORD_U) {
-        int v[ORD_U];
-#pragma unroll
-        for (int u = 0; u < ORD_U; u++) {
-            const int x = x0 + u * 64 + lane;
-            v[u] = (x <= XR) ? (int)p[x] : NOMATCH;
-        }
-#pragma unroll
-        for (int u = 0; u < ORD_U; u++) {
-            const bool valid = v[u] != NOMATCH;
-            const unsigned long long m = __ballot(valid);
-            if (valid && cnt[k + __popcll(m & lt)] < 0) p[x0 + u * 64 + lane] = (int16_t)NOMATCH;
-            k += __popcll(m);
-        }
-    }
+    // the removed pixels become NOMATCH (.cpp:363)
+    ord_walk_valid(p, XL, XR, lane, [&](int x, int, int k) {
+        if (cnt[k] < 0) p[x] = (int16_t)NOMATCH;
+    });
 }
 
 hipError_t launch_order(const StageArgs &a, hipStream_t st) {
-    int rows = 0, maxL = 0;
-    for (int v = 0; v < a.ndir; v++) {
-        rows = max(rows, a.d[v].own.YR - a.d[v].own.YL + 1);
-        maxL = max(maxL, a.d[v].own.XR - a.d[v].own.XL + 1);
-    }
-    if (rows <= 0 || maxL <= 0) return hipSuccess;
-    maxL = (maxL + 63) & ~63;
-    const size_t lds = (size_t)maxL * 6 + ((size_t)maxL / 64 + 1) * 12 + ((size_t)maxL / ORD_BIG + 1) * 4;
+    const Extent e = margin_extent(a);
+    if (e.rows <= 0 || e.cols <= 0) return hipSuccess;
+    const int maxL = (e.cols + 63) & ~63;
+    const size_t lds = OrdLds::bytes(maxL);
     if (lds > 65536) { // margins wider than ~10 k columns: beyond the default 64 KB of dynamic LDS per workgroup
         // without the attribute the row does not fit: nothing is launched, and the caller reports the status
         const hipError_t e = hipFuncSetAttribute((const void *)k_order, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(k_order, dim3(rows, 1, a.ndir), dim3(64 * ORD_NW), lds, st, a, maxL);
+    hipLaunchKernelGGL(k_order, dim3(e.rows, 1, a.ndir), dim3(64 * ORD_NW), lds, st, a, maxL);
     return hipSuccess;
 }
 
@@ -400,15 +390,17 @@ __global__ void k_uniq(T *__restrict__ P, const T *__restrict__ Q, int W, int H,
     const int XL = own.XL, XR = own.XR, XL1 = oth.XL, XR1 = oth.XR;
     const long long total = (long long)W * H;
     T *p = P + (size_t)y * W;
+    // flat-buffer emulation of q[]: an index outside the map, or one the caller does not want, reads as NOMATCH (one condition, one load)
+    auto q_at = [&](long long fi, bool want = true) -> CT { return (want && fi >= 0 && fi < total) ? (CT)Q[fi] : (CT)NOMATCH; };
     unsigned long long cin = 1ull; // p[XL-1] is never modified: "alive" as far as the chain goes
     CT prev_last = (XL - 1 >= 0) ? (CT)p[XL - 1] : (CT)NOMATCH;
     for (int x0 = XL; x0 <= XR; x0 += 64) {
         const int x = x0 + lane;
         const CT raw = (x <= XR + 1 && x < W) ? (CT)p[x] : (CT)NOMATCH;
         const bool valid = (x <= XR) && (raw != (CT)NOMATCH);
-        CT pm1 = (CT)__shfl_up(raw, 1);
+        CT pm1 = wave_prev<true>(raw);
         if (lane == 0) pm1 = prev_last;
-        CT pp1 = (CT)__shfl_down(raw, 1);
+        CT pp1 = wave_prev<false>(raw);
         if (lane == 63) pp1 = (x + 1 <= XR + 1 && x + 1 < W) ? (CT)p[x + 1] : (CT)NOMATCH;
         bool g = false, h = false, n = false;
         if (valid) {
@@ -420,10 +412,9 @@ __global__ void k_uniq(T *__restrict__ P, const T *__restrict__ Q, int W, int H,
 #pragma unroll
             for (int u = 0; u < 3; u++) {
                 const long long fi = rowo + bL + u; // bL + u <= bR is inside the row; beyond it the value is unused
-                qq[u] = (bL + u <= bR && fi >= 0 && fi < total) ? (CT)Q[fi] : (CT)NOMATCH;
+                qq[u] = q_at(fi, bL + u <= bR);
             }
-            const long long fi = rowo + bL + 1; // flat-buffer emulation of q[bL+1]
-            const CT qv = (fi >= 0 && fi < total) ? (CT)Q[fi] : (CT)NOMATCH;
+            const CT qv = q_at(rowo + bL + 1);
             bool direct = false;
 #pragma unroll
             for (int u = 0; u < 3; u++) direct = direct || (bL + u <= bR && close2<CT>(qq[u], raw));
@@ -460,16 +451,14 @@ __global__ void k_uniq(T *__restrict__ P, const T *__restrict__ Q, int W, int H,
     }
 }
 
-void launch_uniq_s16(int16_t *p, const int16_t *q, int W, int H, Mg own, Mg oth, hipStream_t st) {
-    const int rows = own.YR - own.YL + 1;
-    if (rows <= 0 || own.XR < own.XL) return;
-    hipLaunchKernelGGL((k_uniq<int16_t, int>), dim3((rows + 3) / 4), dim3(256), 0, st, p, q, W, H, own, oth);
+template <typename T, typename CT>
+static void launch_uniq(T *p, const T *q, int W, int H, Mg own, Mg oth, hipStream_t st) {
+    const Extent e = margin_extent(own);
+    if (e.rows <= 0 || e.cols <= 0) return;
+    hipLaunchKernelGGL((k_uniq<T, CT>), dim3((e.rows + 3) / 4), dim3(256), 0, st, p, q, W, H, own, oth);
 }
-void launch_uniq_f64(double *p, const double *q, int W, int H, Mg own, Mg oth, hipStream_t st) {
-    const int rows = own.YR - own.YL + 1;
-    if (rows <= 0 || own.XR < own.XL) return;
-    hipLaunchKernelGGL((k_uniq<double, double>), dim3((rows + 3) / 4), dim3(256), 0, st, p, q, W, H, own, oth);
-}
+void launch_uniq_s16(int16_t *p, const int16_t *q, int W, int H, Mg own, Mg oth, hipStream_t st) { launch_uniq<int16_t, int>(p, q, W, H, own, oth, st); }
+void launch_uniq_f64(double *p, const double *q, int W, int H, Mg own, Mg oth, hipStream_t st) { launch_uniq<double, double>(p, q, W, H, own, oth, st); }
 
 // ---------------------------------------------------------------- SetBoundary_smooth<short>
 #define MAX_DISPARITY 2 // .cpp:4
@@ -488,7 +477,7 @@ void launch_uniq_f64(double *p, const double *q, int W, int H, Mg own, Mg oth, h
 #define SBV_LO (-(1 << 24))   // probes: far outside any value the recurrence can produce or clamp to
 #define SBV_HI (1 << 24)
 #define SBV_INF (1 << 26)
-// scratch (int32, in rf_list): per direction [SBV_S][W][6] = map (a_bl, c_bl, a_br, c_br) + saved pair, then [W][2]
+// scratch (int32, in rf_list; SETB_SCRATCH): per direction [SBV_S][W] SbvRec = map (a_bl, c_bl, a_br, c_br) + saved pair, then [W][2]
 __device__ __forceinline__ int *sbv_scratch(const StageArgs &a, int dir) {
     return (int *)a.rf_list + (size_t)dir * SETB_SCRATCH(a.W);
 }
@@ -496,6 +485,11 @@ __device__ __forceinline__ int *sbv_scratch(const StageArgs &a, int dir) {
 struct SbvPair {
     int bl, br;
 };
+// a segment's map applied to the pair that enters it: what leaves it
+__device__ __forceinline__ void sbv_apply(SbvPair &s, const SbvRec &q) {
+    s.bl = max(s.bl + q.a_bl, q.c_bl);
+    s.br = min(s.br + q.a_br, q.c_br);
+}
 // one row of .cpp:844-868 (downward; UP = 0) or .cpp:876-899 (upward; UP = 1, (ul, ur) = the pair stored at the
 // row above by the downward sweep): `out` is what the row stores, `s` becomes the pair handed to the next row
 template <int UP>
@@ -525,38 +519,26 @@ __global__ __launch_bounds__(64) void k_setb_vert(StageArgs a) {
     const uint8_t *__restrict__ mk = d.mask_own;
     const int16_t *__restrict__ src = d.d16_in;
     int16_t *BL = d.BL, *BR = d.BR;
-    int *sc = sbv_scratch(a, blockIdx.z);
-    int *initp = sc + (size_t)SBV_S * W * 6 + (size_t)x * 2;
-    auto rec = [&](int k) { return sc + ((size_t)k * W + x) * 6; };
+    SbvRec *sc = (SbvRec *)sbv_scratch(a, blockIdx.z);
+    int *initp = (int *)(sc + (size_t)SBV_S * W) + (size_t)x * 2;
+    auto rec = [&](int k) { return sc + (size_t)k * W + x; };
 
     SbvPair s0, s1; // APPLY: s0 = the true pair.  Summary: s0 = (LO, HI) gives the maps' constants, s1 = (HI, LO) their slopes
     int sav_l = 0, sav_r = 0;
     if (APPLY) {
         if (UP) { // from the pair the downward sweep ended with (:870-874), through the segments below this one
-            s0.bl = initp[0];
-            s0.br = initp[1];
-            for (int k = SBV_S - 1; k > seg; k--) {
-                const int *q = rec(k);
-                s0.bl = max(s0.bl + q[0], q[1]);
-                s0.br = min(s0.br + q[2], q[3]);
-            }
-            sav_l = rec(seg)[4];
-            sav_r = rec(seg)[5];
+            s0 = SbvPair{initp[0], initp[1]};
+            for (int k = SBV_S - 1; k > seg; k--) sbv_apply(s0, *rec(k));
+            sav_l = rec(seg)->sav_l;
+            sav_r = rec(seg)->sav_r;
         } else {
-            s0.bl = -10000;
-            s0.br = 10000;
-            for (int k = 0; k < seg; k++) {
-                const int *q = rec(k);
-                s0.bl = max(s0.bl + q[0], q[1]);
-                s0.br = min(s0.br + q[2], q[3]);
-            }
+            s0 = SbvPair{-10000, 10000}; // .cpp:832-833
+            for (int k = 0; k < seg; k++) sbv_apply(s0, *rec(k));
         }
         s1 = s0;
     } else {
-        s0.bl = SBV_LO;
-        s0.br = SBV_HI;
-        s1.bl = SBV_HI;
-        s1.br = SBV_LO;
+        s0 = SbvPair{SBV_LO, SBV_HI};
+        s1 = SbvPair{SBV_HI, SBV_LO};
         if (UP && seg == 0) { // rows are intact during the summary pass
             initp[0] = BL[(size_t)YR * W + x];
             initp[1] = BR[(size_t)YR * W + x];
@@ -610,13 +592,13 @@ __global__ __launch_bounds__(64) void k_setb_vert(StageArgs a) {
             BR[o] = (int16_t)s0.br;
         }
     } else {
-        int *q = rec(seg);
-        q[0] = s1.bl > (1 << 23) ? s1.bl - SBV_HI : -SBV_INF; // slope part survived: x + a, else a constant map
-        q[1] = s0.bl;
-        q[2] = s1.br < -(1 << 23) ? s1.br - SBV_LO : SBV_INF;
-        q[3] = s0.br;
-        q[4] = sav_l;
-        q[5] = sav_r;
+        SbvRec *q = rec(seg);
+        q->a_bl = s1.bl > SBV_HI / 2 ? s1.bl - SBV_HI : -SBV_INF; // the probe is still out at its end: the slope part survived, x + a; else a constant map
+        q->c_bl = s0.bl;
+        q->a_br = s1.br < SBV_LO / 2 ? s1.br - SBV_LO : SBV_INF;
+        q->c_br = s0.br;
+        q->sav_l = sav_l;
+        q->sav_r = sav_r;
     }
 }
 
@@ -640,6 +622,8 @@ __global__ __launch_bounds__(256) void k_setb_horiz(StageArgs a, int emit_list) 
     int16_t *__restrict__ br = d.BR + (size_t)y * W;
     const uint8_t *__restrict__ mk = d.mask_own + (size_t)y * W;
     const int nchunk = (XR - XL) / 64 + 1;
+    const auto imax = [](int l, int r) { return max(l, r); };
+    const auto imin = [](int l, int r) { return min(l, r); };
     // ---- left -> right
     int carryL = 0, carryR = 0;
     for (int k = 0; k < nchunk; k++) {
@@ -648,17 +632,10 @@ __global__ __launch_bounds__(256) void k_setb_horiz(StageArgs a, int emit_list) 
         const bool link = in && x > XL && mk[x - 1] == 255;
         int VL = in ? (int)bl[x] + x : 0, VR = in ? (int)br[x] - 2 * x : 0;
         const unsigned long long heads = __ballot(!link);
-        const unsigned long long below = heads & ((2ull << lane) - 1ull); // lanes <= this one
-        const int head = below ? 63 - __builtin_clzll(below) : -1;       // -1: the run started in an earlier chunk
-        const int lo = head < 0 ? 0 : head;
-#pragma unroll
-        for (int s = 1; s < 64; s <<= 1) {
-            const int oL = __shfl_up(VL, s), oR = __shfl_up(VR, s);
-            if (lane - s >= lo) {
-                VL = max(VL, oL);
-                VR = min(VR, oR);
-            }
-        }
+        const unsigned long long below = heads & lanes_upto(lane);
+        const int head = below ? 63 - __builtin_clzll(below) : -1; // -1: the run started in an earlier chunk
+        VL = wave_scan<true>(VL, lane, imax, max(head, 0));
+        VR = wave_scan<true>(VR, lane, imin, max(head, 0));
         if (head < 0) {
             VL = max(VL, carryL);
             VR = min(VR, carryR);
@@ -686,17 +663,10 @@ __global__ __launch_bounds__(256) void k_setb_horiz(StageArgs a, int emit_list) 
         }
         int VL = tl - 2 * x, VR = tr + x;
         const unsigned long long heads = __ballot(!link);
-        const unsigned long long above = heads & ~((1ull << lane) - 1ull); // lanes >= this one
-        const int head = above ? __builtin_ctzll(above) : 64;             // 64: the run continues in the chunk to the right
-        const int hi = head > 63 ? 63 : head;
-#pragma unroll
-        for (int s = 1; s < 64; s <<= 1) {
-            const int oL = __shfl_down(VL, s), oR = __shfl_down(VR, s);
-            if (lane + s <= hi) {
-                VL = max(VL, oL);
-                VR = min(VR, oR);
-            }
-        }
+        const unsigned long long above = heads & lanes_from(lane);
+        const int head = above ? __builtin_ctzll(above) : 64; // 64: the run continues in the chunk to the right
+        VL = wave_scan<false>(VL, lane, imax, min(head, 63));
+        VR = wave_scan<false>(VR, lane, imin, min(head, 63));
         if (head == 64) {
             VL = max(VL, carryL);
             VR = min(VR, carryR);
@@ -726,7 +696,7 @@ __global__ __launch_bounds__(256) void k_setb_horiz(StageArgs a, int emit_list) 
         }
         if (emit_list) { // uniform: the row's own list, no atomics (a shared counter would see ~30 appends per row)
             const unsigned long long mm = __ballot(emit);
-            if (emit) rowlist[nemit + __popcll(mm & ((1ull << lane) - 1ull))] = (uint32_t)((size_t)y * W + x);
+            if (emit) rowlist[nemit + ballot_rank(mm, lane)] = (uint32_t)((size_t)y * W + x);
             nemit += __popcll(mm);
         }
     }
@@ -734,19 +704,15 @@ __global__ __launch_bounds__(256) void k_setb_horiz(StageArgs a, int emit_list) 
 }
 
 void launch_set_boundary(const StageArgs &a, hipStream_t st, bool emit_list) {
-    int rows = 0, cols = 0;
-    for (int v = 0; v < a.ndir; v++) {
-        rows = max(rows, a.d[v].own.YR - a.d[v].own.YL + 1);
-        cols = max(cols, a.d[v].own.XR - a.d[v].own.XL + 1);
-    }
-    if (rows <= 0 || cols <= 0) return;
-    const dim3 vgrid((cols + 63) / 64, SBV_S, a.ndir);
+    const Extent e = margin_extent(a);
+    if (e.rows <= 0 || e.cols <= 0) return;
+    const dim3 vgrid((e.cols + 63) / 64, SBV_S, a.ndir);
     hipLaunchKernelGGL((k_setb_vert<0, 0>), vgrid, dim3(64), 0, st, a);
     hipLaunchKernelGGL((k_setb_vert<0, 1>), vgrid, dim3(64), 0, st, a);
     hipLaunchKernelGGL((k_setb_vert<1, 0>), vgrid, dim3(64), 0, st, a);
     hipLaunchKernelGGL((k_setb_vert<1, 1>), vgrid, dim3(64), 0, st, a);
     // (the vertical sweeps are done with their scratch in rf_list: the horizontal kernel may refill it)
-    hipLaunchKernelGGL(k_setb_horiz, dim3((rows + 3) / 4, 1, a.ndir), dim3(256), 0, st, a, emit_list ? 1 : 0);
+    hipLaunchKernelGGL(k_setb_horiz, dim3((e.rows + 3) / 4, 1, a.ndir), dim3(256), 0, st, a, emit_list ? 1 : 0);
 }
 
 // ---------------------------------------------------------------- MedianFilter (1 iteration)
@@ -794,11 +760,7 @@ __global__ void k_median(StageArgs a) {
 }
 
 void launch_median(const StageArgs &a, hipStream_t st) {
-    int rows = 0, cols = 0;
-    for (int v = 0; v < a.ndir; v++) {
-        rows = max(rows, a.d[v].own.YR - a.d[v].own.YL + 1);
-        cols = max(cols, a.d[v].own.XR - a.d[v].own.XL + 1);
-    }
-    if (rows <= 0 || cols <= 0) return;
-    hipLaunchKernelGGL(k_median, dim3((cols + 255) / 256, rows, a.ndir), dim3(256), 0, st, a);
+    const Extent e = margin_extent(a);
+    if (e.rows <= 0 || e.cols <= 0) return;
+    hipLaunchKernelGGL(k_median, dim3((e.cols + 255) / 256, e.rows, a.ndir), dim3(256), 0, st, a);
 }

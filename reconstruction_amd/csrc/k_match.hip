@@ -21,6 +21,7 @@
 // scores); then the nine kernels, each dynamic-LDS kernel behind the constexpr layout struct that its launcher sizes
 // the launch with; the launchers last.
 #include "rsm_dev.h"
+#include "wave_prims.h"
 
 #include <stdlib.h>
 
@@ -108,8 +109,7 @@ __global__ void k_hl_interval(StageArgs a) {
 }
 
 void launch_hl_interval(const StageArgs &a, hipStream_t st) {
-    int rows = 0;
-    for (int v = 0; v < a.ndir; v++) rows = max(rows, a.d[v].own.YR - a.d[v].own.YL + 1);
+    const int rows = margin_extent(a).rows;
     if (rows <= 0) return;
     hipLaunchKernelGGL(k_hl_interval, dim3((rows + 3) / 4, 1, a.ndir), dim3(256), 0, st, a);
 }
@@ -853,7 +853,7 @@ __global__ __launch_bounds__(256) void k_ncc_rowstat(StageArgs a, int mode) {
         cnt += __popcll(__ballot(width > a.ncc_mid));
         wmax = max(wmax, width);
     }
-    for (int o = 32; o > 0; o >>= 1) wmax = max(wmax, __shfl_xor(wmax, o));
+    wmax = wave_max(wmax);
     if (lane == 0) {
         a.wrow[NCC_WROW_MID(a.H) + blockIdx.z * a.H + y] = cnt;
         a.wrow[NCC_WROW_MAX(a.H) + blockIdx.z * a.H + y] = wmax;
@@ -1362,13 +1362,9 @@ static void launch_dot4(const StageArgs &a_in, int mode, dim3 grid, hipStream_t 
 }
 
 void launch_ncc_argmax(const StageArgs &a, int mode, hipStream_t st) {
-    int rows = 0, cols = 0;
-    for (int v = 0; v < a.ndir; v++) {
-        rows = max(rows, a.d[v].own.YR - a.d[v].own.YL + 1);
-        cols = max(cols, a.d[v].own.XR - a.d[v].own.XL + 1);
-    }
-    if (rows <= 0 || cols <= 0) return;
-    dim3 grid((cols + NCC_TX - 1) / NCC_TX, rows, a.ndir);
+    const Extent e = margin_extent(a);
+    if (e.rows <= 0 || e.cols <= 0) return;
+    dim3 grid((e.cols + NCC_TX - 1) / NCC_TX, e.rows, a.ndir);
     if (!a.opt_ncc_bytes) {
         switch (a.r) {
         case 1: return launch_dot4<1>(a, mode, grid, st);

@@ -16,6 +16,7 @@
 #include "../../include/rsm.h"
 #include "rsm_dev.h"
 #include "mesh_common.h"
+#include "wave_prims.h"
 
 #include <string.h>
 
@@ -158,17 +159,6 @@ __global__ __launch_bounds__(256) void k_md_unique(const u64 *__restrict__ key, 
     if (m > 2) locked[a] = locked[b] = 1;
 }
 
-__device__ __forceinline__ u64 wave_sum(u64 x) {
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
-__device__ __forceinline__ u64 wave_max(u64 x) {
-    for (int o = 32; o > 0; o >>= 1) {
-        const u64 y = __shfl_xor(x, o, 64);
-        x = y > x ? y : x;
-    }
-    return x;
-}
 // a running maximum that many threads feed: the value only grows, so a thread that reads one at least as large as its own has nothing to add
 __device__ __forceinline__ void ctr_max(u64 *p, u64 x) {
     if (x > __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(p, x);
@@ -184,7 +174,7 @@ __global__ __launch_bounds__(256) void k_md_vertex(size_t nv, const uint32_t *__
         val = (u64)(row[i + 1] - row[i]);
     }
     l = wave_sum(l);
-    val = wave_max(val);
+    val = wave_reduce(val, [](u64 x, u64 y) { return y > x ? y : x; });
     if ((threadIdx.x & 63) == 0) {
         if (l) atomicAdd(ctr + C_LOCKED, l);
         ctr_max(ctr + C_VALENCE, val);

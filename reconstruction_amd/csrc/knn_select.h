@@ -1,26 +1,9 @@
 // knn_select.h -- what the cloud filter's k-nearest searches (k_filter_win.hip: the pixel windows, k_filter_knn.hip: the grid cells and the whole
-// cloud) share on the device: the square root and the exact-sum rules of the k-nearest sums, the wave reductions, and the selection a wave runs
+// cloud) share on the device: the square root and the exact-sum rules of the k-nearest sums, and the selection a wave runs
 // for one query -- gather the candidates within the bound into a list, select among the listed.
 #pragma once
 
-// a value of every lane reduced over the wave, into every lane
-template <class T, class Op>
-__device__ __forceinline__ T wave_reduce(T v, const Op &op) {
-    for (int o = 32; o > 0; o >>= 1) v = op(v, __shfl_xor(v, o));
-    return v;
-}
-template <class T>
-__device__ __forceinline__ T wave_sum(T v) {
-    return wave_reduce(v, [](T a, T b) { return a + b; });
-}
-template <class T>
-__device__ __forceinline__ T wave_min(T v) {
-    return wave_reduce(v, [](T a, T b) { return min(a, b); });
-}
-template <class T>
-__device__ __forceinline__ T wave_max(T v) {
-    return wave_reduce(v, [](T a, T b) { return max(a, b); });
-}
+#include "wave_prims.h" // wave_reduce / wave_sum / wave_min / wave_max
 
 // sqrtf, correctly rounded, for the k-nearest sums (PCL adds sqrt of the float32 squared distances): the compiler's own sequence --
 // v_sqrt_f32 (1 ulp), the two neighbouring floats, an fma residual each, two selects -- WITHOUT its input scaling for

@@ -625,8 +625,8 @@ static int match_level(rsm_ctx *c, int k, int par) {
     hipStream_t st = c->stream;
     const int W = c->Wk[k], H = c->Hk[k];
     StageArgs a = level_args(c, k);
-    const double Pk = 0.5 * ((double)(a.d[0].own.XR - a.d[0].own.XL + 1) * (a.d[0].own.YR - a.d[0].own.YL + 1) +
-                             (double)(a.d[1].own.XR - a.d[1].own.XL + 1) * (a.d[1].own.YR - a.d[1].own.YL + 1));
+    const Extent e0 = margin_extent(a.d[0].own), e1 = margin_extent(a.d[1].own);
+    const double Pk = 0.5 * ((double)e0.cols * e0.rows + (double)e1.cols * e1.rows); // pixels of a margin, the two views averaged
     auto maps = [&](int16_t *const in[2], int16_t *const out[2]) {
         for (int v = 0; v < 2; v++) {
             a.d[v].d16_in = in[v];

@@ -15,8 +15,14 @@
 #define RF_PPT 4      // pixels per thread of the refine sweep kernel
 #define RF_TILE_MAXT 8 // sweeps per launch of the tile kernel (k_refine_tile), at most
 #define SBV_S 32 // SetBoundary: row segments per column of the vertical sweeps
-// int32 scratch of launch_set_boundary (in rf_list), per direction
-#define SETB_SCRATCH(W) ((size_t)(SBV_S * 6 + 2) * (size_t)(W))
+// What a row segment of a column does to the (bl, br) pair the vertical sweep carries through it (k_setb_vert): bl -> max(bl + a_bl, c_bl),
+// br -> min(br + a_br, c_br); sav_l / sav_r: the downward sweep's pair at the row above the segment, saved for the upward sweep
+struct SbvRec {
+    int a_bl, c_bl, a_br, c_br, sav_l, sav_r;
+};
+static_assert(sizeof(SbvRec) == 24, "SbvRec: six ints");
+// int32 scratch of launch_set_boundary (in rf_list), per direction: [SBV_S][W] records, then the pair the downward sweep ended with, [W][2]
+#define SETB_SCRATCH(W) ((size_t)(SBV_S * (sizeof(SbvRec) / sizeof(int)) + 2) * (size_t)(W))
 
 // Everything one direction of one stage may need. Direction v: own view = v, other = 1-v
 // (IsZeroOne = (v == 0) in the reference's signatures).
@@ -82,6 +88,20 @@ struct StageArgs {
     int ncc_slide_max;  // NCC: rows whose widest interval is at most this take k_ncc_slide, the others k_ncc_rowgemm
     int32_t *ncc_cnt;  // NCC: [0] number of wide pixels in rf_list (zero before an initial-match launch), [16 + dir * H + y] Rematch pixels of a row
 };
+
+// rows and columns of one margin, and of the larger margin over a stage's directions: what a launch over the margins covers
+struct Extent {
+    int rows, cols;
+};
+inline Extent margin_extent(const Mg &m) { return Extent{m.YR - m.YL + 1, m.XR - m.XL + 1}; }
+inline Extent margin_extent(const StageArgs &a) {
+    Extent e{0, 0};
+    for (int v = 0; v < a.ndir; v++) {
+        const Extent d = margin_extent(a.d[v].own);
+        e = Extent{std::max(e.rows, d.rows), std::max(e.cols, d.cols)};
+    }
+    return e;
+}
 
 // ---- launchers (each enqueues on `st`, no sync) ----------------------------------------------
 void launch_fill_i16(int16_t *p, size_t n, int16_t v, hipStream_t st);

@@ -231,30 +231,25 @@ extern "C" int rsm_stage_order(rsm_ctx *c, int16_t *disp, int W, int H, const rs
     return finish(c, t);
 }
 
-extern "C" int rsm_stage_uniqueness_pass_s16(rsm_ctx *c, int16_t *p, const int16_t *q, int W, int H,
-                                             const rsm_boundary *own, const rsm_boundary *oth) {
+template <typename T, typename Launch>
+static int uniqueness_pass(rsm_ctx *c, T *p, const T *q, int W, int H, const rsm_boundary *own, const rsm_boundary *oth, Launch launch) {
     if (!stage_ok(c, W, H) || !p || !q || !own || !oth) return RSM_E_INVALID;
     Tmp t(c);
     const size_t px = (size_t)W * H;
-    int16_t *dp = t.up(p, px);
-    int16_t *dq = t.up(q, px);
+    T *dp = t.up(p, px);
+    T *dq = t.up(q, px);
     if (!t.ok) return finish(c, t);
-    launch_uniq_s16(dp, dq, W, H, to_mg(*own), to_mg(*oth), c->stream);
+    launch(dp, dq, W, H, to_mg(*own), to_mg(*oth), c->stream);
     t.down(p, dp, px);
     return finish(c, t);
 }
-
+extern "C" int rsm_stage_uniqueness_pass_s16(rsm_ctx *c, int16_t *p, const int16_t *q, int W, int H,
+                                             const rsm_boundary *own, const rsm_boundary *oth) {
+    return uniqueness_pass(c, p, q, W, H, own, oth, launch_uniq_s16);
+}
 extern "C" int rsm_stage_uniqueness_pass_f64(rsm_ctx *c, double *p, const double *q, int W, int H,
                                              const rsm_boundary *own, const rsm_boundary *oth) {
-    if (!stage_ok(c, W, H) || !p || !q || !own || !oth) return RSM_E_INVALID;
-    Tmp t(c);
-    const size_t px = (size_t)W * H;
-    double *dp = t.up(p, px);
-    double *dq = t.up(q, px);
-    if (!t.ok) return finish(c, t);
-    launch_uniq_f64(dp, dq, W, H, to_mg(*own), to_mg(*oth), c->stream);
-    t.down(p, dp, px);
-    return finish(c, t);
+    return uniqueness_pass(c, p, q, W, H, own, oth, launch_uniq_f64);
 }
 
 extern "C" int rsm_stage_set_boundary(rsm_ctx *c, const int16_t *disp, const uint8_t *mask_own, int W, int H,

@@ -199,6 +199,29 @@ def test_full_pair_matches_oracle(ctx, name):
     assert np.array_equal(res.xyz[fin_], ref["xyz"][fin_])
 
 
+def test_pair_with_margins_unequal_in_height_and_width_matches_oracle(ctx):
+    """The pair launches cover the larger margin of the two directions (margin_extent), rows and columns each: view 0's
+    margin is 3 rows x 2 columns, view 1's 2 rows x 3 columns, so neither view's extent covers the other's.  The smallest
+    pair the validator accepts (5 x 5, one level, radius 1); every output bit for bit."""
+    cfg = synth.config_small(width=5, height=5, levels=1, radius=1, offset=2, pair=0, mask_kind="full", d0_l0=1.0, amp_l0=0.0)
+    m0, m1 = np.zeros((5, 5), np.uint8), np.zeros((5, 5), np.uint8)
+    m0[1:4, 1:3] = 255
+    m1[1:3, 1:4] = 255
+    cfg.mask = [m0, m1]
+    ref = orc.match_pair(cfg)
+    (yl0, yr0, xl0, xr0), (yl1, yr1, xl1, xr1) = ref["margin"][0][:4], ref["margin"][1][:4]
+    assert yr0 - yl0 > yr1 - yl1 and xr0 - xl0 < xr1 - xl1
+    assert all((ref["disparity"][v] != NOMATCH).any() for v in range(2)) and ref["n_points"] > 0
+    res = ctx.match_pair(cfg)
+    assert res.margin == ref["margin"]
+    assert res.v_top == ref["v_top"]
+    for v in range(2):
+        assert np.array_equal(res.disparity[v], ref["disparity"][v]), diff_report("map %d" % v, res.disparity[v], ref["disparity"][v])
+    assert res.n_points == ref["n_points"]
+    assert np.array_equal(res.bgr, ref["bgr"])
+    assert np.array_equal(res.xyz, ref["xyz"], equal_nan=True)
+
+
 def test_run_is_deterministic_and_reusable(ctx):
     cfg = synth.config_small(**CASES["s128x96_r2_neg_holes"])
     a = ctx.match_pair(cfg)
