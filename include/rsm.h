@@ -568,6 +568,33 @@ int rsm_stage_poisson_solve(rsm_ctx *ctx, const float *b, int depth, double rel_
                             int *cycles, double *history);
 int rsm_stage_iso_mesh(rsm_ctx *ctx, const float *chi, int depth, double iso, const double grid[4], const uint8_t *occ, int trim_cells,
                        int64_t *n_vertices, int64_t *n_faces);
+/* ---- the density-adaptive form of the same call (mesh.bat: PoissonRecon --samplesPerNode 2; script1.mlx: SamplesPerNode 3) --------------
+ * Opt-in; the plain call above keeps its behaviour and its bits.  Every sample gets the density rho of the cloud around it (the density
+ * trim's count splat on 2^kernel_depth nodes per axis, read back at the sample), the depth d = min(depth, max(3, kernel_depth +
+ * 1/2 log2(rho / samples_per_node))) at which a grid node would hold samples_per_node samples, and the weight w = min(1, 1 / (64 rho)).  It is
+ * splatted with its weight at the two grid levels around d (levels 3..depth) instead of at the finest level with weight 1; the levels are
+ * added up coarse to fine by trilinear prolongation with the volume factor 8 per level, and the iso-value is the w-weighted mean of chi at
+ * the samples.  Where the cloud is thin the surface no longer caves in.  Solver, extraction and occupancy trim are the plain call's.  Not a
+ * bit-parity port of PoissonRecon: the rules as DESIGN.md 9 (f14) defines them. */
+typedef struct rsm_poisson_density_params {
+    int kernel_depth;         /* 3..depth: the density is estimated on 2^kernel_depth nodes per axis; 0 = depth - 2 (PoissonRecon's default) */
+    double samples_per_node;  /* finite, > 0 (mesh.bat: 2, script1.mlx: 3) */
+} rsm_poisson_density_params;
+/* stats: [0..11] as RSM_POISSON_STATS, [12] the kernel depth used, [13] the least d over the valid samples, [14] the number of samples with
+ * d < depth, [15] the sum of w */
+#define RSM_POISSON_WEIGHTED_STATS 16
+/* as rsm_poisson_mesh[_device]: the mesh becomes the context's last mesh.  RSM_E_INVALID also for kernel_depth neither 0 nor in 3..depth
+ * and samples_per_node not finite or <= 0. */
+int rsm_poisson_mesh_weighted(rsm_ctx *ctx, const float *xyz, const float *normals4, int64_t n, const rsm_poisson_params *p,
+                              const rsm_poisson_density_params *dp, int64_t *n_vertices, int64_t *n_faces, double *stats);
+int rsm_poisson_mesh_weighted_device(rsm_ctx *ctx, const float *d_xyz, const float *d_normals4, int64_t n, const rsm_poisson_params *p,
+                                     const rsm_poisson_density_params *dp, int64_t *n_vertices, int64_t *n_faces, double *stats);
+/* stage entry point (host buffers) for the tests, as rsm_stage_poisson_rhs: b from the levels' sums in fp64.  depth_in (n doubles, may be
+ * NULL; RSM_E_INVALID when one is not finite): each sample's d from the caller, clamped to 3..depth, instead of from its density; the
+ * values at samples that take no part are not used.  rho, w, d (n doubles each, may be NULL): per sample, 0 where it takes no part. */
+int rsm_stage_poisson_rhs_weighted(rsm_ctx *ctx, const float *xyz, const float *normals4, int64_t n, const rsm_poisson_params *p,
+                                   const rsm_poisson_density_params *dp, const double *depth_in, double grid[4], double *b, uint8_t *occ,
+                                   int64_t counts[2], double *rho, double *w, double *d);
 /* binary little-endian PLY mesh: vertex float x, y, z; face list uchar int vertex_indices (what MeshLab and TextureStitcher read).  Host only. */
 int rsm_write_ply_mesh(const char *path, const float *xyz, int64_t n_vertices, const int32_t *faces, int64_t n_faces);
 

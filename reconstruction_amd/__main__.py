@@ -1,5 +1,6 @@
 """python -m reconstruction_amd <config.yml> [--device N] [--out cloud.ply] [--filter] [--mls [--isdelete] [--mls-out bigcloud.ply]]
                               [--mesh [--mesh-depth 9] [--mesh-trim 4] [--mesh-out bigmesh.ply]
+                               [--mesh-samples-per-node [2] [--mesh-kernel-depth 0]]
                                [--mesh-density-trim [7] [--mesh-density-smooth 100] [--mesh-island-ratio 0.01]]
                                [--mesh-clean [--mesh-smooth 5] [--mesh-min-piece 10%]] [--mesh-close-holes [30]] [--mesh-decimate [100000]]
                                [--mesh-color [--mesh-color-mode blend] [--mesh-color-min-cos 0.2] [--mesh-color-eps LENGTH]]
@@ -14,6 +15,8 @@ the smoothed, oriented cloud as bigcloud.ply (pcl::PointNormal, savePLYFileBinar
 multi-view duplicate deletion before it (CCloudOptimization.cpp:152-346, on the GPU).
 With --mesh (implies --mls) the surface of that cloud: unscreened Poisson reconstruction on a dense grid and a trim, on the GPU,
 where CCloudOptimization::run calls meshlab.bat's Poisson filter -> bigmesh.ply (not a bit-parity port of that tool: DESIGN.md 9 f7).
+With --mesh-samples-per-node (implies --mesh) the Poisson call spreads every sample by the density of the cloud around it, as PoissonRecon's
+--samplesPerNode does (2 when given bare, mesh.bat's value; script1.mlx uses 3), so that thinly sampled parts hold their place.
 With --mesh-density-trim (implies --mesh) the Poisson call runs without its occupancy trim and the surface is trimmed as mesh.bat's
 SurfaceTrimmer does, on the GPU: cut along the iso-line of the smoothed sample density, small islands moved across.
 With --mesh-clean (implies --mesh) bigmesh.ply is that surface after meshlab.bat's other filters, on the GPU: Laplacian smoothing
@@ -79,6 +82,12 @@ def main(argv=None) -> int:
     ap.add_argument("--mesh-trim", type=int, default=4,
                     help="faces survive within this many cells of a cell that holds a point (4 = mesh.bat's --trim 7 at depth 9; 0 = no trim)")
     ap.add_argument("--mesh-out", default=None, help="path of the mesh (default: bigmesh.ply next to the --out PLY)")
+    ap.add_argument("--mesh-samples-per-node", type=float, nargs="?", const=2.0, default=None, metavar="S",
+                    help="the surface (implied) with the density-adaptive splat: a sample is spread at the grid levels where a node would hold S of the "
+                         "samples around it and weighs the inverse of their density (PoissonRecon --samplesPerNode; 2 when given bare as in mesh.bat, "
+                         "script1.mlx: 3)")
+    ap.add_argument("--mesh-kernel-depth", type=int, default=0, metavar="K",
+                    help="with --mesh-samples-per-node: the density is estimated on 2^K grid nodes per axis, 3..depth (0 = depth - 2)")
     ap.add_argument("--mesh-density-trim", type=float, nargs="?", const=7.0, default=None, metavar="T",
                     help="after the surface (implied; --mesh-trim is then not applied): cut it where the smoothed sample-density value falls below T "
                          "(mesh.bat's SurfaceTrimmer --trim 7; 7 when given bare) on the GPU, before --mesh-clean")
@@ -120,7 +129,7 @@ def main(argv=None) -> int:
         args.mesh_color = True
     if args.mesh_color:
         args.mesh = True
-    if args.mesh_density_trim is not None or args.mesh_close_holes is not None or args.mesh_decimate is not None:
+    if args.mesh_density_trim is not None or args.mesh_close_holes is not None or args.mesh_decimate is not None or args.mesh_samples_per_node is not None:
         args.mesh = True
     if args.mesh_clean:
         args.mesh = True
@@ -198,8 +207,9 @@ def main(argv=None) -> int:
         from . import RsmError, write_ply_mesh
         t2 = time.perf_counter()
         try:
-            mv, mf, mst = sink.mesh(depth=args.mesh_depth, trim_cells=args.mesh_trim if args.mesh_density_trim is None else 0)
-        except RsmError as e:                                      # e.g. --mesh-depth outside 5..9
+            mv, mf, mst = sink.mesh(depth=args.mesh_depth, trim_cells=args.mesh_trim if args.mesh_density_trim is None else 0,
+                                    samples_per_node=args.mesh_samples_per_node, kernel_depth=args.mesh_kernel_depth)
+        except RsmError as e:                                      # e.g. --mesh-depth outside 5..9, --mesh-samples-per-node 0
             print(e)
             return 1
         cst = tst = hst = dst = None
@@ -231,6 +241,9 @@ def main(argv=None) -> int:
         write_ply_mesh(mesh_out, mv, mf)
         print("Mesh time: %.3f s (%d cycles, residual %.2e%s)" % (time.perf_counter() - t2, mst["cycles"], mst["residual"],
                                                                   "" if mst["converged"] else ", NOT converged"))
+        if args.mesh_samples_per_node is not None:
+            print("Mesh samples per node %g: density on 2^%d nodes, %d of %d samples spread below depth %d (least depth %.2f)"
+                  % (args.mesh_samples_per_node, mst["kernel_depth"], mst["n_below_depth"], mst["n_valid"], args.mesh_depth, mst["min_sample_depth"]))
         if tst is not None:
             print("Mesh density trim: %d faces from %d (%d split along %d cut edges); values %.2f .. %.2f; %d pieces moved to the kept side, %d to the dropped"
                   % (tst["n_faces"], tst["n_faces_in"], tst["faces_split"], tst["cut_edges"], tst["value_min"], tst["value_max"], tst["moved_to_kept"],

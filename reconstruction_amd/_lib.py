@@ -74,6 +74,14 @@ class PoissonParams(C.Structure):
 POISSON_STATS = 12
 
 
+class PoissonDensityParams(C.Structure):
+    """rsm_poisson_density_params (include/rsm.h)."""
+    _fields_ = [("kernel_depth", C.c_int), ("samples_per_node", C.c_double)]
+
+
+POISSON_WEIGHTED_STATS = 16
+
+
 class MeshCleanParams(C.Structure):
     """rsm_mesh_clean_params (include/rsm.h)."""
     _fields_ = [("smooth_steps", C.c_int), ("cotangent", C.c_int), ("boundary", C.c_int), ("min_piece", C.c_double),
@@ -153,7 +161,7 @@ _I, _L, _U, _LL, _Z, _D, _V, _S = C.c_int, C.c_int64, C.c_uint32, C.c_longlong, 
 _pI, _pL, _pD = C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_double)
 _PIN, _POUT, _BND, _RIN, _ROUT, _FLT = (C.POINTER(t) for t in (PairIn, PairOut, Boundary, RectifyIn, RectifyOut, FilterParams))
 _MLS, _VIEW, _PSN, _CLN, _COL, _STI = (C.POINTER(t) for t in (MlsParams, DedupView, PoissonParams, MeshCleanParams, MeshColorParams, MeshStitchParams))
-_TRM, _CLO, _DEC = C.POINTER(MeshTrimParams), C.POINTER(MeshCloseParams), C.POINTER(MeshDecimateParams)
+_TRM, _CLO, _DEC, _PDN = C.POINTER(MeshTrimParams), C.POINTER(MeshCloseParams), C.POINTER(MeshDecimateParams), C.POINTER(PoissonDensityParams)
 PROTOTYPES = {
     "rsm_create": (_I, [_V, _I]),
     "rsm_destroy": (None, [_V]),
@@ -238,6 +246,9 @@ PROTOTYPES = {
     "rsm_stage_poisson_rhs": (_I, [_V, _V, _V, _L, _PSN, _V, _V, _V, _V]),
     "rsm_stage_poisson_solve": (_I, [_V, _V, _I, _D, _I, _V, _pD, _pI, _V]),
     "rsm_stage_iso_mesh": (_I, [_V, _V, _I, _D, _V, _V, _I, _pL, _pL]),
+    "rsm_poisson_mesh_weighted": (_I, [_V, _V, _V, _L, _PSN, _PDN, _pL, _pL, _V]),
+    "rsm_poisson_mesh_weighted_device": (_I, [_V, _V, _V, _L, _PSN, _PDN, _pL, _pL, _V]),
+    "rsm_stage_poisson_rhs_weighted": (_I, [_V, _V, _V, _L, _PSN, _PDN, _V, _V, _V, _V, _V, _V, _V, _V]),
     "rsm_write_ply_mesh": (_I, [_S, _V, _L, _V, _L]),
     "rsm_mesh_clean": (_I, [_V, _V, _L, _V, _L, _CLN, _pL, _pL, _V]),
     "rsm_mesh_clean_device": (_I, [_V, _V, _L, _V, _L, _CLN, _pL, _pL, _V]),

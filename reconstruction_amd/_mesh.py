@@ -6,7 +6,7 @@ import numpy as np
 
 from . import _lib
 from ._context import ContextBase, _normals4, _p, _u8, _views
-from ._lib import MeshCleanParams, MeshCloseParams, MeshColorParams, MeshDecimateParams, MeshStitchParams, MeshTrimParams, PoissonParams
+from ._lib import MeshCleanParams, MeshCloseParams, MeshColorParams, MeshDecimateParams, MeshStitchParams, MeshTrimParams, PoissonDensityParams, PoissonParams
 
 # the solve's default stopping residual: one decade above the 4.2e-6 the float32 solver reaches at depth 9
 POISSON_REL_RESIDUAL = 4e-5
@@ -75,6 +75,60 @@ class MeshPart(ContextBase):
         prm = PoissonParams(int(depth), float(scale), 0.5, 1, 0)
         self._chk(self._lib.rsm_stage_poisson_rhs(self._h, _p(xyz), _p(nrm), n, C.byref(prm), _p(grid), _p(b), _p(occ), _p(counts)))
         return grid, b, occ, (int(counts[0]), int(counts[1]))
+
+    # ---- the density-adaptive form: PoissonRecon's --samplesPerNode (csrc/k_poisson_density.hip) ----
+    def _poisson_weighted(self, fn, xyz, nrm, n, depth, scale, trim_cells, rel_residual, max_cycles, samples_per_node, kernel_depth):
+        nv, nf = C.c_int64(), C.c_int64()
+        st = (C.c_double * _lib.POISSON_WEIGHTED_STATS)()
+        prm = PoissonParams(int(depth), float(scale), float(rel_residual), int(max_cycles), int(trim_cells))
+        dpr = PoissonDensityParams(int(kernel_depth), float(samples_per_node))
+        status = fn(self._h, xyz, nrm, n, C.byref(prm), C.byref(dpr), C.byref(nv), C.byref(nf), st)
+        if status < 0:
+            self._chk(status)
+        stats = dict(n_valid=int(st[0]), n_invalid=int(st[1]), residual=float(st[2]), cycles=int(st[3]), iso=float(st[4]),
+                     origin=(float(st[5]), float(st[6]), float(st[7])), h=float(st[8]), N=int(st[9]), n_vertices_untrimmed=int(st[10]),
+                     n_faces_untrimmed=int(st[11]), kernel_depth=int(st[12]), min_sample_depth=float(st[13]), n_below_depth=int(st[14]),
+                     weight_sum=float(st[15]), status=int(status), converged=status == 0)
+        return int(nv.value), int(nf.value), stats
+
+    def poisson_mesh_weighted(self, xyz, normals, depth=9, scale=1.1, trim_cells=4, rel_residual=POISSON_REL_RESIDUAL, max_cycles=POISSON_MAX_CYCLES,
+                              samples_per_node=2.0, kernel_depth=0):
+        """poisson_mesh with the density-adaptive splat, what PoissonRecon's --samplesPerNode does (mesh.bat: 2, script1.mlx: 3): every
+        sample is spread at the grid levels around the depth at which a node would hold samples_per_node of the samples near it (their
+        density from a count splat on 2^kernel_depth nodes per axis; 0 = depth - 2) and weighs the inverse of that density, so that
+        thinly sampled parts of the surface hold their place.  Returns (vertices, faces, stats dict); beyond poisson_mesh's keys the
+        stats hold kernel_depth, min_sample_depth, n_below_depth (samples spread below the finest level) and weight_sum."""
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        nrm = _normals4(normals, len(xyz))
+        nv, nf, stats = self._poisson_weighted(self._lib.rsm_poisson_mesh_weighted, _p(xyz), _p(nrm), len(xyz), depth, scale, trim_cells, rel_residual,
+                                               max_cycles, samples_per_node, kernel_depth)
+        return self.poisson_last_mesh(nv, nf) + (stats,)
+
+    def poisson_mesh_weighted_device(self, xyz_ptr, normals_ptr, n, depth=9, scale=1.1, trim_cells=4, rel_residual=POISSON_REL_RESIDUAL,
+                                     max_cycles=POISSON_MAX_CYCLES, samples_per_node=2.0, kernel_depth=0):
+        """rsm_poisson_mesh_weighted_device on device buffers (addresses), as poisson_mesh_device: (n_vertices, n_faces, stats)."""
+        return self._poisson_weighted(self._lib.rsm_poisson_mesh_weighted_device, xyz_ptr, normals_ptr, n, depth, scale, trim_cells, rel_residual, max_cycles,
+                                      samples_per_node, kernel_depth)
+
+    def poisson_rhs_weighted(self, xyz, normals, depth, scale=1.1, samples_per_node=2.0, kernel_depth=0, depth_in=None):
+        """Stage: samples -> (grid (ox, oy, oz, h), b float64 [N,N,N] indexed [k,j,i], occ uint8 [N,N,N], (valid, invalid), rho float64 [n],
+        w float64 [n], d float64 [n]) of the density-adaptive splat; depth_in (float64 [n]): every sample's depth from the caller."""
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        n = len(xyz)
+        nrm = _normals4(normals, n)
+        N = 1 << int(depth)
+        grid = np.zeros(4, np.float64)
+        b = np.zeros((N, N, N), np.float64)
+        occ = np.zeros((N, N, N), np.uint8)
+        counts = np.zeros(2, np.int64)
+        rho, w, d = (np.zeros(max(n, 1), np.float64) for _ in range(3))
+        din = None if depth_in is None else np.ascontiguousarray(depth_in, np.float64).reshape(-1)
+        assert din is None or len(din) == n
+        prm = PoissonParams(int(depth), float(scale), 0.5, 1, 0)
+        dpr = PoissonDensityParams(int(kernel_depth), float(samples_per_node))
+        self._chk(self._lib.rsm_stage_poisson_rhs_weighted(self._h, _p(xyz), _p(nrm), n, C.byref(prm), C.byref(dpr), None if din is None else _p(din), _p(grid),
+                                                           _p(b), _p(occ), _p(counts), _p(rho), _p(w), _p(d)))
+        return grid, b, occ, (int(counts[0]), int(counts[1])), rho[:n].copy(), w[:n].copy(), d[:n].copy()
 
     def poisson_solve(self, b, rel_residual=POISSON_REL_RESIDUAL, max_cycles=POISSON_MAX_CYCLES):
         """Stage: b [N,N,N] (rounded to float32) -> (chi float32 [N,N,N], residual reached, cycles, status 0 / 1, residual per cycle)."""

@@ -315,14 +315,20 @@ class CloudOptimization:
             self.cloud_ms_normals = self._ctx.mls_cloud(xyz, self.m_mls_radius, 1, ref)
         return self.cloud_ms_normals
 
-    def mesh(self, depth=9, scale=1.1, trim_cells=4, rel_residual=POISSON_REL_RESIDUAL, max_cycles=POISSON_MAX_CYCLES):
+    def mesh(self, depth=9, scale=1.1, trim_cells=4, rel_residual=POISSON_REL_RESIDUAL, max_cycles=POISSON_MAX_CYCLES, samples_per_node=None,
+             kernel_depth=0):
         """Where CCloudOptimization::run hands bigcloud.ply to the Poisson mesher (after :389): the surface of cloud_ms_normals, run()'s
         result, by the dense-grid Poisson reconstruction and trim on the GPU (Context.poisson_mesh).  run() keeps its result on the
-        host, so the host entry point is used.  Stores and returns (vertices float32 [nv,3], faces int32 [nf,3], stats)."""
+        host, so the host entry point is used.  samples_per_node (mesh.bat: 2, script1.mlx: 3) selects the density-adaptive splat
+        (Context.poisson_mesh_weighted; kernel_depth as there); None is the plain call.  Stores and returns (vertices float32 [nv,3],
+        faces int32 [nf,3], stats)."""
         if getattr(self, "cloud_ms_normals", None) is None:
             raise ValueError("CloudOptimization.mesh: run() first (it meshes run()'s smoothed, oriented cloud)")
         xyz, nrm = self.cloud_ms_normals[0], self.cloud_ms_normals[1]
-        self.mesh_result = self._ctx.poisson_mesh(xyz, nrm, depth, scale, trim_cells, rel_residual, max_cycles)
+        if samples_per_node is None:
+            self.mesh_result = self._ctx.poisson_mesh(xyz, nrm, depth, scale, trim_cells, rel_residual, max_cycles)
+        else:
+            self.mesh_result = self._ctx.poisson_mesh_weighted(xyz, nrm, depth, scale, trim_cells, rel_residual, max_cycles, samples_per_node, kernel_depth)
         self.mesh_grid_step = self.mesh_result[2]["h"]
         self._mesh_box = (depth, scale)
         self.mesh_colors = None

@@ -14,6 +14,8 @@
 //                 triangle and fewer than 2^31 triangles: every sum stays below 2^62), integer atomics behind a per-block reduction for the
 //                 one giant component                                                                               k_mt_unite, k_mt_areas, k_mt_decide
 //   compaction    the kept triangles and the vertices they use, renumbered in order (dev_prims.h)
+// The count splat and the value are also what the density-adaptive Poisson splat weighs its samples by (k_poisson_density.hip; DESIGN.md 9
+// f14): it calls density_at_points_device below with the samples themselves as the points.
 // No float atomics.  Built with -ffp-contract=off (csrc/Makefile): every fp64 expression below is evaluated as written.
 #include "../../include/rsm.h"
 #include "rsm_dev.h"
@@ -33,29 +35,12 @@ typedef unsigned long long u64;
 
 enum { T_CUT = 0, T_SPLIT, T_REPEAT, T_ZERO, T_COMP_KEPT, T_COMP_DROPPED, T_MOVED_KD, T_MOVED_DK, T_QTOTAL, T_VMIN, T_VMAX, T_N };
 
-struct MtGrid {
-    double ox, oy, oz, h;
-    int N;
-};
-
 __device__ __forceinline__ void count_if(bool flag, u64 *ctr) {
     if (flag) atomicAdd(ctr, (u64)1);
 }
 
 // ---- 2: the count splat ---------------------------------------------------------------------------------------------------------------
-// f7's trilinear cell of a point on the grid g: the first node per axis and the fraction toward the next
-__device__ __forceinline__ void mt_cell(const double p[3], const MtGrid &g, double fl[3], double f[3]) {
-    const double o[3] = {g.ox, g.oy, g.oz};
-    for (int a = 0; a < 3; a++) {
-        const double gq = (p[a] - o[a]) / g.h - 0.5;
-        fl[a] = floor(gq);
-        f[a] = gq - fl[a];
-    }
-}
-__device__ __forceinline__ double mt_weight(const double f[3], int dx, int dy, int dz) {
-    return ((dx ? f[0] : 1.0 - f[0]) * (dy ? f[1] : 1.0 - f[1])) * (dz ? f[2] : 1.0 - f[2]);
-}
-
+// (mesh_common.h: MtGrid, mt_cell, mt_weight -- f7's trilinear cell and weights, shared with k_poisson_density.hip)
 template <bool HAS_N>
 __global__ __launch_bounds__(256) void k_mt_splat(const float *__restrict__ xyz, const float *__restrict__ nrm, int64_t n, MtGrid g, u64 *__restrict__ C) {
     const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -370,6 +355,21 @@ __global__ __launch_bounds__(256) void k_mt_compact_info(size_t nt, const unsign
 // ---- host -------------------------------------------------------------------------------------------------------------------------------
 static dim3 red_grid(size_t n) { return dim3((unsigned)std::max<size_t>(1, std::min<size_t>(1024, (n + 255) / 256))); }
 
+// rules 2 and 3 on a box that is known (grid = f7's {o, h}, hk = side / 2^kd > 0): the count splat of the samples, read back at nv > 0 points.
+// Enqueues only; the counts are M's and live as long as M
+static int density_on_grid(DevMem &M, const float *d_sx, const float *d_sn4, int64_t n, const double grid[4], double hk, int kd, double spn, const float *d_v,
+                           size_t nv, double *d_rho, double *d_val, hipStream_t st) {
+    const size_t N3 = (size_t)1 << (3 * kd);
+    u64 *C = M.get<u64>(N3);
+    if (!M.ok) return RSM_E_NOMEM;
+    DEVCHK(hipMemsetAsync(C, 0, N3 * sizeof(u64), st));
+    const MtGrid g{grid[0], grid[1], grid[2], hk, 1 << kd};
+    if (d_sn4) hipLaunchKernelGGL(k_mt_splat<true>, blocks_for((size_t)n), dim3(256), 0, st, d_sx, d_sn4, n, g, C);
+    else hipLaunchKernelGGL(k_mt_splat<false>, blocks_for((size_t)n), dim3(256), 0, st, d_sx, d_sn4, n, g, C);
+    hipLaunchKernelGGL(k_mt_value, blocks_for(nv), dim3(256), 0, st, d_v, nv, g, (const long long *)C, (double)kd, spn, d_rho, d_val);
+    return RSM_OK;
+}
+
 // rho (optional) and value at nv > 0 vertices; *hk = 0: no valid sample or all of them equal, every value 0
 static int density(DevMem &M, const float *d_sx, const float *d_sn4, int64_t n, int depth, double scale, int kd, double spn, const float *d_v, size_t nv,
                    double *d_rho, double *d_val, int64_t counts[2], double *hk, hipStream_t st) {
@@ -383,15 +383,7 @@ static int density(DevMem &M, const float *d_sx, const float *d_sn4, int64_t n, 
         DEVCHK(hipMemsetAsync(d_val, 0, nv * sizeof(double), st));
         return RSM_OK;
     }
-    const size_t N3 = (size_t)1 << (3 * kd);
-    u64 *C = M.get<u64>(N3);
-    if (!M.ok) return RSM_E_NOMEM;
-    DEVCHK(hipMemsetAsync(C, 0, N3 * sizeof(u64), st));
-    const MtGrid g{grid[0], grid[1], grid[2], *hk, 1 << kd};
-    if (d_sn4) hipLaunchKernelGGL(k_mt_splat<true>, blocks_for((size_t)n), dim3(256), 0, st, d_sx, d_sn4, n, g, C);
-    else hipLaunchKernelGGL(k_mt_splat<false>, blocks_for((size_t)n), dim3(256), 0, st, d_sx, d_sn4, n, g, C);
-    hipLaunchKernelGGL(k_mt_value, blocks_for(nv), dim3(256), 0, st, d_v, nv, g, (const long long *)C, (double)kd, spn, d_rho, d_val);
-    return RSM_OK;
+    return density_on_grid(M, d_sx, d_sn4, n, grid, *hk, kd, spn, d_v, nv, d_rho, d_val, st);
 }
 
 // `steps` steps from d_in (nv > 0 values); the result is in *d_res (d_in itself with steps = 0 or no face, else one of two scratch buffers)
@@ -524,6 +516,13 @@ int mesh_density_device(const float *d_sx, const float *d_sn4, int64_t n, int de
     if (s != RSM_OK) return s;
     s = density(M, d_sx, d_sn4, n, depth, scale, kernel_depth, samples_per_node, d_v, (size_t)nv, d_rho, d_val, counts, hk, st);
     return s != RSM_OK ? s : mesh_finish(st);
+}
+
+int density_at_points_device(DevMem &M, const float *d_sx, const float *d_sn4, int64_t n, int depth, const double grid[4], int kernel_depth,
+                             double samples_per_node, const float *d_v, int64_t nv, double *d_rho, double *d_val, hipStream_t st) {
+    if (nv <= 0) return RSM_OK;
+    return density_on_grid(M, d_sx, d_sn4, n, grid, grid[3] * (double)(1 << (depth - kernel_depth)), kernel_depth, samples_per_node, d_v, (size_t)nv, d_rho, d_val,
+                           st);
 }
 
 int mesh_value_smooth_device(const int32_t *d_f, int64_t nv, int64_t nf, const double *d_in, int steps, double *d_out, int *invalid, hipStream_t st) {

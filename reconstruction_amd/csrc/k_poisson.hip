@@ -15,6 +15,8 @@
 // Reproducibility: the splat adds llrint(w n^ 2^32) with 64-bit integer atomics -- integer sums do not depend on arrival order.  |w n^| <= 1
 // and a sample meets a node at most once, so INT32_MAX samples sum to at most (2^31 - 1) 2^32 < 2^63.  Every floating-point reduction
 // (dot products, the iso-value) runs over a grid that depends on the problem size only, block trees in LDS, then one block over the partials.
+// The density-adaptive form of steps 3, 4 and 6 (PoissonRecon's --samplesPerNode) is k_poisson_density.hip; it calls this
+// file's solver, extraction, chi at the samples (poisson_chi_at_samples) and summation tree (poisson_tree_sum).
 #include "../../include/rsm.h"
 #include "rsm_dev.h"
 #include "mesh_common.h"
@@ -26,7 +28,7 @@
 #include <vector>
 
 #define PV_FIX 4294967296.0 // 2^32: the splat's fixed-point scale
-#define PV_RED_BLOCKS 1024  // partial sums of a reduction (fixed: the summation tree depends on the size only)
+#define PV_RED_BLOCKS POISSON_SUM_PARTIALS // partial sums of a reduction (fixed: the summation tree depends on the size only)
 
 namespace {
 
@@ -610,6 +612,17 @@ int poisson_solve_device(const float *d_b, int depth, double rel_residual, int m
     return *residual <= rel_residual ? RSM_OK : RSM_W_NOT_CONVERGED;
 }
 
+void poisson_chi_at_samples(const float *d_xyz, const float *d_nrm4, int64_t n, const float *d_chi, int depth, const double grid[4], double *d_val,
+                            hipStream_t st) {
+    hipLaunchKernelGGL(k_pv_iso, blocks_for((size_t)n), dim3(256), 0, st, d_xyz, d_nrm4, n, make_grid(grid, depth), d_chi, d_val);
+}
+
+void poisson_tree_sum(const double *d_v, int64_t n, double *d_part, double *d_sum, hipStream_t st) {
+    const unsigned rb = red_blocks((size_t)n);
+    hipLaunchKernelGGL(k_pv_sum_f64, dim3(rb), dim3(256), 0, st, d_v, n, d_part);
+    hipLaunchKernelGGL(k_pv_sum, dim3(1), dim3(256), 0, st, (const double *)d_part, (int)rb, d_sum);
+}
+
 int poisson_iso_device(const float *d_xyz, const float *d_nrm4, int64_t n, int64_t n_valid, const float *d_chi, int depth, const double grid[4],
                        double *iso, hipStream_t st) {
     *iso = 0.0;
@@ -617,10 +630,8 @@ int poisson_iso_device(const float *d_xyz, const float *d_nrm4, int64_t n, int64
     DevMem M;
     double *val = M.get<double>((size_t)n), *part = M.get<double>(PV_RED_BLOCKS), *scal = M.get<double>(1);
     if (!M.ok) return RSM_E_NOMEM;
-    const unsigned rb = red_blocks((size_t)n);
-    hipLaunchKernelGGL(k_pv_iso, blocks_for((size_t)n), dim3(256), 0, st, d_xyz, d_nrm4, n, make_grid(grid, depth), d_chi, val);
-    hipLaunchKernelGGL(k_pv_sum_f64, dim3(rb), dim3(256), 0, st, (const double *)val, n, part);
-    hipLaunchKernelGGL(k_pv_sum, dim3(1), dim3(256), 0, st, (const double *)part, (int)rb, scal);
+    poisson_chi_at_samples(d_xyz, d_nrm4, n, d_chi, depth, grid, val, st);
+    poisson_tree_sum(val, n, part, scal, st);
     double sum = 0.0;
     DEVCHK(hipMemcpyAsync(&sum, scal, sizeof sum, hipMemcpyDeviceToHost, st));
     DEVCHK(hipStreamSynchronize(st));

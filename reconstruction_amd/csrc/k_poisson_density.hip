@@ -1,0 +1,237 @@
+// k_poisson_density.hip -- the density-adaptive form of the Poisson surface's splat, where mesh.bat runs PoissonRecon --samplesPerNode 2 and
+// script1.mlx sets SamplesPerNode 3: a sample in a thinly sampled region is spread over a coarser level of the grid and weighs more, so that the
+// surface does not cave in where the cloud is thin.  Not a bit-parity port of that tool (no source in the reference tree): every rule is
+// defined in DESIGN.md 9 (f14) and restated in numpy in tests/poisson_density_restatement.py.
+//   density      rho_s = f11's count splat on 2^kernel_depth nodes per axis, read back at the sample's own position; value_s = f11's value.
+//                k_meshtrim.hip's own kernels through density_at_points_device (mesh_common.h): stated there, called here
+//   sample pass  w_s = min(1, 1 / (64 rho_s)), d_s = min(depth, max(3, value_s or the caller's depth)); the least d_s, how many lie
+//                below depth                                                                                            k_pd_sample
+//   level splat  at level lo = floor(d_s) with alpha = (1 - fr) w_s and, below depth, at lo + 1 with alpha = fr w_s (fr = d_s - lo):
+//                V_L[a](node) += llrint((wt (alpha n^_a)) 2^32), f7's trilinear weights on the level's 2^L nodes per axis; 64-bit integer
+//                atomics, so no order in the sum.  |wt alpha n^_a| <= 1 and a sample meets a node once per level: f7's 2^63 bound holds per
+//                level.  occ is f7's, on the finest level                                                                k_pd_splat
+//   cascade      U_3 = V_3 2^-32 8^(3 - depth); U_L = V_L 2^-32 8^(L - depth) + P(U_{L-1}) in fp64, in place of V_L; P = cell-centred trilinear
+//                prolongation, x then y then z, 0.75 near + 0.25 far, 0 outside                                         k_pd_cascade
+//   rhs          f7's central differences of U_depth in fp64, rounded once to float for the solver                     k_pd_rhs
+//   iso          sum w_s chi(p_s) / sum w_s: f7's chi at the samples (poisson_chi_at_samples) times w_s, both sums in f7's tree   k_pd_mul
+// The levels share one buffer of 64-bit words: level L's three components start at word 3 (8^L - 8^3) / 7.
+// No float atomics.  Built with -ffp-contract=off (csrc/Makefile): every fp64 expression below is evaluated as written.
+#include "../../include/rsm.h"
+#include "rsm_dev.h"
+#include "mesh_common.h"
+
+#include <math.h>
+#include <string.h>
+
+#define PD_FIX 4294967296.0 // 2^32: the splat's fixed-point scale, f7's
+#define PD_LMIN 3           // the coarsest level a sample is spread on
+
+namespace {
+
+typedef unsigned long long u64;
+
+struct PdBox { // f7's box: the origin, the finest step, the finest level
+    double ox, oy, oz, h;
+    int depth;
+};
+__host__ __device__ __forceinline__ size_t pd_level_nodes(int L) { return (size_t)1 << (3 * L); }
+__host__ __device__ __forceinline__ size_t pd_level_word(int L) { return 3 * ((pd_level_nodes(L) - pd_level_nodes(PD_LMIN)) / 7); }
+// level L's grid: h_L = side / 2^L = h 2^(depth - L), exact
+__device__ __forceinline__ MtGrid pd_level_grid(const PdBox &b, int L) { return MtGrid{b.ox, b.oy, b.oz, b.h * (double)(1 << (b.depth - L)), 1 << L}; }
+
+// ---- 3: weight and depth of a sample; ctr[0] = the least d_s as its bit pattern (d_s > 0: the order of the doubles), ctr[1] = samples below depth
+__global__ __launch_bounds__(256) void k_pd_sample(const float *__restrict__ xyz, const float *__restrict__ nrm, int64_t n, int depth,
+                                                   const double *__restrict__ depth_in, const double *__restrict__ val, double *__restrict__ rho,
+                                                   double *__restrict__ w, double *__restrict__ d, u64 *__restrict__ ctr) {
+    __shared__ u64 s_min;
+    __shared__ unsigned int s_below;
+    if (threadIdx.x == 0) {
+        s_min = ~0ull;
+        s_below = 0;
+    }
+    __syncthreads();
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s < n) {
+        double p[3], nh[3], ws = 0.0, ds = 0.0;
+        const bool ok = pv_valid(xyz, nrm, s, p, nh);
+        const double r = ok ? rho[s] : 0.0;
+        if (ok) {
+            const double inv = 1.0 / (64.0 * r); // (r > 0: the sample counts itself; r = 0 would give inf and the clamp)
+            ws = inv < 1.0 ? inv : 1.0;
+            const double v = depth_in ? depth_in[s] : val[s];
+            ds = v > (double)PD_LMIN ? v : (double)PD_LMIN; // (NaN lands on PD_LMIN)
+            ds = ds < (double)depth ? ds : (double)depth;
+            u64 bits;
+            __builtin_memcpy(&bits, &ds, 8);
+            atomicMin(&s_min, bits);
+            if (ds < (double)depth) atomicAdd(&s_below, 1u);
+        }
+        rho[s] = r;
+        w[s] = ws;
+        d[s] = ds;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (s_min != ~0ull) atomicMin(ctr, s_min);
+        if (s_below) atomicAdd(ctr + 1, (u64)s_below);
+    }
+}
+
+// ---- 4: the level splat ---------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_pd_splat(const float *__restrict__ xyz, const float *__restrict__ nrm, int64_t n, PdBox box,
+                                                  const double *__restrict__ w, const double *__restrict__ d, u64 *__restrict__ V,
+                                                  uint8_t *__restrict__ occ) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n) return;
+    double p[3], nh[3];
+    if (!pv_valid(xyz, nrm, s, p, nh)) return;
+    const int depth = box.depth;
+    { // occ: f7's cell on the finest level, clamped to the grid
+        const double o[3] = {box.ox, box.oy, box.oz};
+        const int N = 1 << depth;
+        size_t c[3];
+        for (int a = 0; a < 3; a++) {
+            const double u = floor((p[a] - o[a]) / box.h);
+            c[a] = u >= 0.0 ? (u < (double)N ? (size_t)u : (size_t)(N - 1)) : 0; // (NaN lands on 0)
+        }
+        occ[c[0] + (size_t)N * (c[1] + (size_t)N * c[2])] = 1;
+    }
+    const double ws = w[s], ds = d[s];
+    const double fld = floor(ds);
+    int lo = ds >= (double)PD_LMIN ? (int)fld : PD_LMIN; // (k_pd_sample clamped d_s; the tests here keep the level inside the buffer whatever d holds)
+    lo = lo > depth ? depth : lo;
+    const double fr = ds - fld;
+    for (int t = 0; t < 2; t++) {
+        const int L = lo + t;
+        if (L > depth) break;
+        const double alpha = t ? fr * ws : (1.0 - fr) * ws;
+        const MtGrid g = pd_level_grid(box, L);
+        double fl[3], f[3];
+        int i0[3];
+        mt_cell(p, g, fl, f);
+        if (!mt_cell_index(fl, g.N, i0)) continue;
+        const int N = g.N;
+        const size_t N3 = pd_level_nodes(L);
+        u64 *VL = V + pd_level_word(L);
+        const double an[3] = {alpha * nh[0], alpha * nh[1], alpha * nh[2]};
+        for (int dz = 0; dz < 2; dz++)
+            for (int dy = 0; dy < 2; dy++)
+                for (int dx = 0; dx < 2; dx++) {
+                    const int i = i0[0] + dx, j = i0[1] + dy, k = i0[2] + dz;
+                    if (i < 0 || j < 0 || k < 0 || i >= N || j >= N || k >= N) continue;
+                    const double wt = mt_weight(f, dx, dy, dz);
+                    const size_t node = (size_t)i + (size_t)N * ((size_t)j + (size_t)N * k);
+                    for (int a = 0; a < 3; a++) {
+                        const long long q = __double2ll_rn((wt * an[a]) * PD_FIX);
+                        if (q) atomicAdd(&VL[a * N3 + node], (u64)q);
+                    }
+                }
+    }
+}
+
+// ---- 5: one level of the cascade, in place: the word that held V_L holds U_L afterwards (a thread reads and writes its own word only; the
+// coarser level is another part of the buffer).  grid.y = the component --------------------------------------------------------------------
+__device__ __forceinline__ double pd_coarse(const double *__restrict__ A, int nc, int i, int j, int k) {
+    return (i < 0 || j < 0 || k < 0 || i >= nc || j >= nc || k >= nc) ? 0.0 : A[(size_t)i + (size_t)nc * ((size_t)j + (size_t)nc * k)];
+}
+__global__ __launch_bounds__(256) void k_pd_cascade(u64 *fine, const double *__restrict__ coarse, int shf, double scale) {
+    const int nf = 1 << shf, nc = nf >> 1;
+    const size_t n3 = (size_t)1 << (3 * shf);
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= n3) return;
+    u64 *word = fine + (size_t)blockIdx.y * n3 + t;
+    double u = ((double)(long long)*word / PD_FIX) * scale;
+    if (coarse) {
+        const double *A = coarse + (size_t)blockIdx.y * (n3 >> 3);
+        const int i = (int)(t & (nf - 1)), j = (int)((t >> shf) & (nf - 1)), k = (int)(t >> (2 * shf));
+        const int ci[2] = {i >> 1, (i >> 1) + ((i & 1) ? 1 : -1)}, cj[2] = {j >> 1, (j >> 1) + ((j & 1) ? 1 : -1)}, ck[2] = {k >> 1, (k >> 1) + ((k & 1) ? 1 : -1)};
+        double y[2];
+        for (int c = 0; c < 2; c++) { // x, then y, for the near and the far plane
+            const double x0 = 0.75 * pd_coarse(A, nc, ci[0], cj[0], ck[c]) + 0.25 * pd_coarse(A, nc, ci[1], cj[0], ck[c]);
+            const double x1 = 0.75 * pd_coarse(A, nc, ci[0], cj[1], ck[c]) + 0.25 * pd_coarse(A, nc, ci[1], cj[1], ck[c]);
+            y[c] = 0.75 * x0 + 0.25 * x1;
+        }
+        u = u + (0.75 * y[0] + 0.25 * y[1]);
+    }
+    __builtin_memcpy(word, &u, 8);
+}
+
+// ---- 6: the right-hand side from U_depth ---------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_pd_rhs(const double *__restrict__ U, int sh, float *__restrict__ b32, double *__restrict__ b64) {
+    const int N = 1 << sh;
+    const size_t N3 = (size_t)1 << (3 * sh);
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= N3) return;
+    const int i = (int)(idx & (N - 1)), j = (int)((idx >> sh) & (N - 1)), k = (int)(idx >> (2 * sh));
+    const size_t sy = (size_t)N, sz = (size_t)N * N;
+    const double *Ux = U, *Uy = U + N3, *Uz = U + 2 * N3;
+    const double dx = (i + 1 < N ? Ux[idx + 1] : 0.0) - (i > 0 ? Ux[idx - 1] : 0.0);
+    const double dy = (j + 1 < N ? Uy[idx + sy] : 0.0) - (j > 0 ? Uy[idx - sy] : 0.0);
+    const double dz = (k + 1 < N ? Uz[idx + sz] : 0.0) - (k > 0 ? Uz[idx - sz] : 0.0);
+    const double b = 0.5 * ((dx + dy) + dz);
+    if (b32) b32[idx] = (float)b;
+    if (b64) b64[idx] = b;
+}
+
+// ---- 7: w_s chi(p_s) ---------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_pd_mul(double *__restrict__ x, const double *__restrict__ w, int64_t n) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s < n) x[s] = w[s] * x[s];
+}
+
+} // namespace
+
+int poisson_density_rhs_device(const float *d_xyz, const float *d_nrm4, int64_t n, int depth, const double grid[4], int kernel_depth, double samples_per_node,
+                               const double *d_depth_in, float *d_b32, double *d_b64, uint8_t *d_occ, double *d_rho, double *d_w, double *d_d,
+                               double sample_stats[3], hipStream_t st) {
+    sample_stats[0] = sample_stats[1] = sample_stats[2] = 0.0;
+    const size_t N3 = pd_level_nodes(depth), words = pd_level_word(depth + 1);
+    DevMem M;
+    u64 *V = M.get<u64>(words), *ctr = M.get<u64>(2);
+    double *val = M.get<double>((size_t)n), *part = M.get<double>(POISSON_SUM_PARTIALS), *scal = M.get<double>(1);
+    if (!M.ok) return RSM_E_NOMEM;
+    const u64 init[2] = {~0ull, 0ull};
+    DEVCHK(hipMemcpyAsync(ctr, init, sizeof init, hipMemcpyHostToDevice, st));
+    DEVCHK(hipMemsetAsync(V, 0, words * sizeof(u64), st));
+    DEVCHK(hipMemsetAsync(d_occ, 0, N3, st));
+    // the density at the samples' own positions: they are float xyz of stride 3, as a mesh's vertices are
+    int s = density_at_points_device(M, d_xyz, d_nrm4, n, depth, grid, kernel_depth, samples_per_node, d_xyz, n, d_rho, val, st);
+    if (s != RSM_OK) return s;
+    hipLaunchKernelGGL(k_pd_sample, blocks_for((size_t)n), dim3(256), 0, st, d_xyz, d_nrm4, n, depth, d_depth_in, (const double *)val, d_rho, d_w, d_d, ctr);
+    const PdBox box{grid[0], grid[1], grid[2], grid[3], depth};
+    hipLaunchKernelGGL(k_pd_splat, blocks_for((size_t)n), dim3(256), 0, st, d_xyz, d_nrm4, n, box, (const double *)d_w, (const double *)d_d, V, d_occ);
+    for (int L = PD_LMIN; L <= depth; L++) {
+        const double *coarse = L > PD_LMIN ? (const double *)(V + pd_level_word(L - 1)) : nullptr;
+        hipLaunchKernelGGL(k_pd_cascade, dim3(blocks_for(pd_level_nodes(L)).x, 3), dim3(256), 0, st, V + pd_level_word(L), coarse, L, ldexp(1.0, 3 * (L - depth)));
+    }
+    hipLaunchKernelGGL(k_pd_rhs, blocks_for(N3), dim3(256), 0, st, (const double *)(V + pd_level_word(depth)), depth, d_b32, d_b64);
+    poisson_tree_sum(d_w, n, part, scal, st);
+    u64 h[2] = {0, 0};
+    double sum_w = 0.0;
+    DEVCHK(hipMemcpyAsync(h, ctr, sizeof h, hipMemcpyDeviceToHost, st));
+    DEVCHK(hipMemcpyAsync(&sum_w, scal, sizeof sum_w, hipMemcpyDeviceToHost, st));
+    DEVCHK(hipStreamSynchronize(st));
+    DEVCHK(hipGetLastError());
+    if (h[0] != ~0ull) memcpy(&sample_stats[0], &h[0], 8);
+    sample_stats[1] = (double)h[1];
+    sample_stats[2] = sum_w;
+    return RSM_OK;
+}
+
+int poisson_iso_weighted_device(const float *d_xyz, const float *d_nrm4, int64_t n, const double *d_w, double sum_w, const float *d_chi, int depth,
+                                const double grid[4], double *iso, hipStream_t st) {
+    *iso = 0.0;
+    if (n <= 0 || !(sum_w > 0.0)) return RSM_OK;
+    DevMem M;
+    double *val = M.get<double>((size_t)n), *part = M.get<double>(POISSON_SUM_PARTIALS), *scal = M.get<double>(1);
+    if (!M.ok) return RSM_E_NOMEM;
+    poisson_chi_at_samples(d_xyz, d_nrm4, n, d_chi, depth, grid, val, st);
+    hipLaunchKernelGGL(k_pd_mul, blocks_for((size_t)n), dim3(256), 0, st, val, d_w, n);
+    poisson_tree_sum(val, n, part, scal, st);
+    double sum = 0.0;
+    DEVCHK(hipMemcpyAsync(&sum, scal, sizeof sum, hipMemcpyDeviceToHost, st));
+    DEVCHK(hipStreamSynchronize(st));
+    DEVCHK(hipGetLastError());
+    *iso = sum / sum_w;
+    return RSM_OK;
+}

@@ -32,6 +32,11 @@ struct DevMem { // scratch of one call
 // be NULL (indices only)
 int mesh_validate_device(const float *d_v, int64_t nv, const int32_t *d_f, int64_t nf, int *invalid, hipStream_t st);
 
+// (k_meshtrim.hip) f11's items 2 and 3 on f7's box grid = {o, h of 2^depth nodes}, h > 0: the count splat of the n samples on 2^kernel_depth
+// nodes per axis, read back at nv points (float xyz) -> d_rho (may be NULL), d_val.  Enqueues only; its scratch is M's
+int density_at_points_device(DevMem &M, const float *d_sx, const float *d_sn4, int64_t n, int depth, const double grid[4], int kernel_depth,
+                             double samples_per_node, const float *d_v, int64_t nv, double *d_rho, double *d_val, hipStream_t st);
+
 static inline int mesh_finish(hipStream_t st) {
     DEVCHK(hipStreamSynchronize(st));
     DEVCHK(hipGetLastError());
@@ -207,5 +212,29 @@ __device__ __forceinline__ bool pv_valid_point(const float *__restrict__ xyz, in
     const float x = xyz[3 * s], y = xyz[3 * s + 1], z = xyz[3 * s + 2];
     if (!(isfinite(x) && isfinite(y) && isfinite(z))) return false;
     p[0] = (double)x; p[1] = (double)y; p[2] = (double)z;
+    return true;
+}
+
+// ---- f7's trilinear cell on a cubic grid of N nodes per axis at o + (i + 1/2) h (k_meshtrim.hip, k_poisson_density.hip) ------------------------
+struct MtGrid {
+    double ox, oy, oz, h;
+    int N;
+};
+// the first node per axis and the fraction toward the next
+__device__ __forceinline__ void mt_cell(const double p[3], const MtGrid &g, double fl[3], double f[3]) {
+    const double o[3] = {g.ox, g.oy, g.oz};
+    for (int a = 0; a < 3; a++) {
+        const double gq = (p[a] - o[a]) / g.h - 0.5;
+        fl[a] = floor(gq);
+        f[a] = gq - fl[a];
+    }
+}
+__device__ __forceinline__ double mt_weight(const double f[3], int dx, int dy, int dz) {
+    return ((dx ? f[0] : 1.0 - f[0]) * (dy ? f[1] : 1.0 - f[1])) * (dz ? f[2] : 1.0 - f[2]);
+}
+// fl as node indices when the cell touches the grid (fl in [-1, N - 1]; the test keeps a cast of anything else, NaN included, out)
+__device__ __forceinline__ bool mt_cell_index(const double fl[3], int N, int i0[3]) {
+    if (!(fl[0] >= -1.0 && fl[1] >= -1.0 && fl[2] >= -1.0 && fl[0] < (double)N && fl[1] < (double)N && fl[2] < (double)N)) return false;
+    i0[0] = (int)fl[0]; i0[1] = (int)fl[1]; i0[2] = (int)fl[2];
     return true;
 }

@@ -280,9 +280,25 @@ int poisson_solve_device(const float *d_b, int depth, double rel_residual, int m
                          hipStream_t st);
 int poisson_iso_device(const float *d_xyz, const float *d_nrm4, int64_t n, int64_t n_valid, const float *d_chi, int depth, const double grid[4], double *iso,
                        hipStream_t st);
+// the two halves of the iso-value, which the density-adaptive form (k_poisson_density.hip) weighs between them.  Both enqueue only.
+// chi's trilinear interpolation at the n samples (0 at the samples that take no part) -> d_val, n doubles
+void poisson_chi_at_samples(const float *d_xyz, const float *d_nrm4, int64_t n, const float *d_chi, int depth, const double grid[4], double *d_val, hipStream_t st);
+// the sum of n doubles in f7's fixed tree (it depends on n only) -> *d_sum; d_part = POISSON_SUM_PARTIALS doubles of scratch
+#define POISSON_SUM_PARTIALS 1024
+void poisson_tree_sum(const double *d_v, int64_t n, double *d_part, double *d_sum, hipStream_t st);
 // d_occ may be NULL with trim_cells = 0; untrimmed = {vertices, faces} before the trim
 int poisson_extract_device(const float *d_chi, int depth, double iso, const double grid[4], const uint8_t *d_occ, int trim_cells, PoissonMesh *out,
                            int64_t untrimmed[2], hipStream_t st);
+
+// the density-adaptive form of the splat and the right-hand side (k_poisson_density.hip), on a box with grid[3] > 0.
+// d_depth_in (n doubles, may be NULL): each sample's depth from the caller instead of from its density.  d_rho / d_w / d_d: n doubles each,
+// 0 at the samples that take no part.  sample_stats = {the least d_s, samples with d_s < depth, sum of w_s (f7's fixed tree)}
+int poisson_density_rhs_device(const float *d_xyz, const float *d_nrm4, int64_t n, int depth, const double grid[4], int kernel_depth, double samples_per_node,
+                               const double *d_depth_in, float *d_b32, double *d_b64, uint8_t *d_occ, double *d_rho, double *d_w, double *d_d,
+                               double sample_stats[3], hipStream_t st);
+// iso = sum w_s chi(p_s) / sum_w over the samples (sum_w = sample_stats[2])
+int poisson_iso_weighted_device(const float *d_xyz, const float *d_nrm4, int64_t n, const double *d_w, double sum_w, const float *d_chi, int depth,
+                                const double grid[4], double *iso, hipStream_t st);
 
 // smoothing and clean-up of a triangle mesh (k_meshclean.hip).  Device buffers: nv float xyz, nf int32 x 3.  RSM_E_INVALID
 // comes with *invalid = 1 (a face index outside [0, nv)) or 2 (a coordinate that is not finite); parameters are the caller's to check.

@@ -1,5 +1,5 @@
 // rsm_mesh.hip -- the mesh back end's host side: the dense-grid Poisson surface, its smoothing and clean-up, its density trim, the closing of
-// its holes, its decimation, and its colours from the rig's views with their seams levelled (k_poisson.hip, k_meshclean.hip, k_meshtrim.hip,
+// its holes, its decimation, and its colours from the rig's views with their seams levelled (k_poisson.hip, k_poisson_density.hip, k_meshclean.hip, k_meshtrim.hip,
 // k_meshclose.hip, k_meshdecimate.hip, k_meshcolor.hip, k_meshstitch.hip).
 #include "rsm_ctx.h"
 
@@ -178,6 +178,125 @@ extern "C" int rsm_stage_iso_mesh(rsm_ctx *c, const float *chi, int depth, doubl
     *n_vertices = c->pmesh.nv;
     *n_faces = c->pmesh.nf;
     return RSM_OK;
+}
+
+// ---- the density-adaptive form of the Poisson call (k_poisson_density.hip) --------------------------------------------------
+static int poisson_density_params_ok(rsm_ctx *c, const rsm_poisson_params *p, const rsm_poisson_density_params *dp) {
+    if (!dp) return set_err(c, RSM_E_INVALID, "poisson: density params is NULL");
+    if (dp->kernel_depth != 0 && (dp->kernel_depth < 3 || dp->kernel_depth > p->depth))
+        return set_err(c, RSM_E_INVALID, "poisson: kernel_depth %d neither 0 nor in 3..%d", dp->kernel_depth, p->depth);
+    if (!std::isfinite(dp->samples_per_node) || !(dp->samples_per_node > 0.0))
+        return set_err(c, RSM_E_INVALID, "poisson: samples_per_node %g not finite or <= 0", dp->samples_per_node);
+    return RSM_OK;
+}
+static int density_kernel_depth(const rsm_poisson_params *p, const rsm_poisson_density_params *dp) { return dp->kernel_depth ? dp->kernel_depth : p->depth - 2; }
+
+// poisson_run with the density-adaptive splat and the weighted iso-value; the solver and the extraction are poisson_run's
+static int poisson_run_weighted(rsm_ctx *c, const float *d_xyz, const float *d_nrm, int64_t n, const rsm_poisson_params *p, const rsm_poisson_density_params *dp,
+                                int64_t *n_vertices, int64_t *n_faces, double *stats) {
+    double st[RSM_POISSON_WEIGHTED_STATS] = {0};
+    *n_vertices = *n_faces = 0;
+    poisson_mesh_free(&c->pmesh);
+    mesh_replaced(c);
+    double grid[4];
+    int64_t counts[2];
+    int s = poisson_grid_device(d_xyz, d_nrm, n, p->depth, p->scale, grid, counts, c->stream);
+    if (s != RSM_OK) return poisson_fail(c, s, "bounding box");
+    st[0] = (double)counts[0];
+    st[1] = (double)counts[1];
+    st[9] = (double)(1 << p->depth);
+    st[12] = (double)density_kernel_depth(p, dp);
+    int solved = RSM_OK;
+    if (grid[3] > 0.0) {
+        const size_t N3 = (size_t)1 << (3 * p->depth);
+        Tmp T(c);
+        float *b = T.alloc<float>(N3), *chi = T.alloc<float>(N3);
+        uint8_t *occ = T.alloc<uint8_t>(N3);
+        double *rho = T.alloc<double>((size_t)n), *w = T.alloc<double>((size_t)n), *d = T.alloc<double>((size_t)n);
+        if (!b || !chi || !occ || !rho || !w || !d) return set_err(c, RSM_E_NOMEM, "poisson: no device memory for depth %d", p->depth);
+        if ((s = poisson_density_rhs_device(d_xyz, d_nrm, n, p->depth, grid, density_kernel_depth(p, dp), dp->samples_per_node, nullptr, b, nullptr, occ, rho, w, d,
+                                            &st[13], c->stream)) != RSM_OK)
+            return poisson_fail(c, s, "density-adaptive right-hand side");
+        double res = 0.0, iso = 0.0;
+        int cycles = 0;
+        solved = poisson_solve_device(b, p->depth, p->rel_residual, p->max_cycles, chi, &res, &cycles, nullptr, c->stream);
+        if (solved < 0) return poisson_fail(c, solved, "solve");
+        if ((s = poisson_iso_weighted_device(d_xyz, d_nrm, n, w, st[15], chi, p->depth, grid, &iso, c->stream)) != RSM_OK) return poisson_fail(c, s, "iso-value");
+        int64_t un[2];
+        if ((s = poisson_extract_device(chi, p->depth, iso, grid, occ, p->trim_cells, &c->pmesh, un, c->stream)) != RSM_OK)
+            return poisson_fail(c, s, "extraction");
+        mesh_replaced(c);
+        st[2] = res;
+        st[3] = (double)cycles;
+        st[4] = iso;
+        for (int a = 0; a < 4; a++) st[5 + a] = grid[a];
+        st[10] = (double)un[0];
+        st[11] = (double)un[1];
+        if (solved == RSM_W_NOT_CONVERGED) set_err(c, solved, "poisson: residual %g after %d cycles (rel_residual %g)", res, cycles, p->rel_residual);
+    }
+    *n_vertices = c->pmesh.nv;
+    *n_faces = c->pmesh.nf;
+    if (stats) memcpy(stats, st, sizeof st);
+    return solved;
+}
+
+extern "C" int rsm_poisson_mesh_weighted_device(rsm_ctx *c, const float *d_xyz, const float *d_normals4, int64_t n, const rsm_poisson_params *p,
+                                                const rsm_poisson_density_params *dp, int64_t *n_vertices, int64_t *n_faces, double *stats) {
+    if (!c) return RSM_E_INVALID;
+    int s = poisson_params_ok(c, p);
+    if (s != RSM_OK || (s = poisson_density_params_ok(c, p, dp)) != RSM_OK || (s = poisson_n_ok(c, n)) != RSM_OK) return s;
+    if (!n_vertices || !n_faces || (n > 0 && (!d_xyz || !d_normals4))) return set_err(c, RSM_E_INVALID, "poisson: a NULL pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    return poisson_run_weighted(c, d_xyz, d_normals4, n, p, dp, n_vertices, n_faces, stats);
+}
+
+extern "C" int rsm_poisson_mesh_weighted(rsm_ctx *c, const float *xyz, const float *normals4, int64_t n, const rsm_poisson_params *p,
+                                         const rsm_poisson_density_params *dp, int64_t *n_vertices, int64_t *n_faces, double *stats) {
+    if (!c) return RSM_E_INVALID;
+    int s = poisson_params_ok(c, p);
+    if (s != RSM_OK || (s = poisson_density_params_ok(c, p, dp)) != RSM_OK || (s = poisson_n_ok(c, n)) != RSM_OK) return s;
+    if (!n_vertices || !n_faces || (n > 0 && (!xyz || !normals4))) return set_err(c, RSM_E_INVALID, "poisson: a NULL pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    Tmp T(c);
+    float *dx = T.up(xyz, 3 * (size_t)n), *dn = T.up(normals4, 4 * (size_t)n);
+    if (!dx || !dn) return set_err(c, RSM_E_NOMEM, "poisson: no device memory for %lld samples", (long long)n);
+    if (n > 0 && (s = finish(c, T)) != RSM_OK) return s;
+    return poisson_run_weighted(c, dx, dn, n, p, dp, n_vertices, n_faces, stats);
+}
+
+extern "C" int rsm_stage_poisson_rhs_weighted(rsm_ctx *c, const float *xyz, const float *normals4, int64_t n, const rsm_poisson_params *p,
+                                              const rsm_poisson_density_params *dp, const double *depth_in, double grid[4], double *b, uint8_t *occ,
+                                              int64_t counts[2], double *rho, double *w, double *d) {
+    if (!c) return RSM_E_INVALID;
+    int s = poisson_params_ok(c, p);
+    if (s != RSM_OK || (s = poisson_density_params_ok(c, p, dp)) != RSM_OK || (s = poisson_n_ok(c, n)) != RSM_OK) return s;
+    if (!grid || !b || !occ || !counts || (n > 0 && (!xyz || !normals4))) return set_err(c, RSM_E_INVALID, "poisson: a NULL pointer");
+    if (depth_in)
+        for (int64_t i = 0; i < n; i++)
+            if (!std::isfinite(depth_in[i])) return set_err(c, RSM_E_INVALID, "poisson: depth_in[%lld] is not finite", (long long)i);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t N3 = (size_t)1 << (3 * p->depth);
+    Tmp T(c);
+    float *dx = T.up(xyz, 3 * (size_t)n), *dn = T.up(normals4, 4 * (size_t)n);
+    double *dd_in = depth_in ? T.up(depth_in, (size_t)n) : nullptr;
+    double *db = T.alloc<double>(N3), *drho = T.alloc<double>((size_t)n), *dw = T.alloc<double>((size_t)n), *dd = T.alloc<double>((size_t)n);
+    uint8_t *docc = T.alloc<uint8_t>(N3);
+    if (!dx || !dn || (depth_in && !dd_in) || !db || !docc || !drho || !dw || !dd) return set_err(c, RSM_E_NOMEM, "poisson: no device memory");
+    if (n > 0 && (s = finish(c, T)) != RSM_OK) return s;
+    if ((s = poisson_grid_device(dx, dn, n, p->depth, p->scale, grid, counts, c->stream)) != RSM_OK) return poisson_fail(c, s, "bounding box");
+    if (!(grid[3] > 0.0)) {
+        memset(b, 0, sizeof(double) * N3);
+        memset(occ, 0, N3);
+        for (double *out : {rho, w, d})
+            if (out && n > 0) memset(out, 0, sizeof(double) * (size_t)n);
+        return RSM_OK;
+    }
+    double sample_stats[3];
+    if ((s = poisson_density_rhs_device(dx, dn, n, p->depth, grid, density_kernel_depth(p, dp), dp->samples_per_node, dd_in, nullptr, db, docc, drho, dw, dd,
+                                        sample_stats, c->stream)) != RSM_OK)
+        return poisson_fail(c, s, "density-adaptive right-hand side");
+    T.later(b, db, N3).later(occ, docc, N3).later(rho, (const double *)drho, (size_t)n).later(w, (const double *)dw, (size_t)n).later(d, (const double *)dd, (size_t)n);
+    return finish(c, T);
 }
 
 // ---- the mesh-to-mesh stages: clean, trim, close_holes, decimate (how the back end's units are laid out) -------------------------
