@@ -731,6 +731,47 @@ int rsm_stage_mesh_collapse_round(rsm_ctx *ctx, const float *xyz, int64_t nv, co
                                   const rsm_mesh_decimate_params *p, int64_t need, float *out_xyz, int32_t *out_faces, double *out_quadrics, int64_t *n_faces_out,
                                   uint64_t *selected_keys, int64_t *n_selected, int64_t *n_kept);
 
+/* ---- the subdivision of the final mesh (Demo/meshlab/subdiv.mlx: "Subdivision Surfaces: Loop", Iterations 3, Threshold 1 % of the box
+ * diagonal, whole mesh) ----------------------------------------------------------------------------------------------------------------------
+ * Not a bit-parity port of MeshLab / VCG: the rules as DESIGN.md 9 (f15) defines them.  Per iteration every unique edge strictly longer than
+ * thr is split by a new vertex (index nv + its rank in key order); the old vertices at a split edge move by Loop's rules (interior: the
+ * beta_k ring average; border: 1/8, 3/4, 1/8 along the border; locked -- at an edge of three or more faces, with border edges but not
+ * exactly two, or in no face -- stay); every face is replaced in place by 1 to 4 faces, orientation kept.  An iteration that splits
+ * nothing ends the call.  LIMITS: only Loop's own weights (MeshLab's LoopWeight 0) are built -- LoopWeight 1 / 2 ("Enhance regularity" /
+ * "Enhance continuity"; subdiv.mlx selects 2) rest on VCG's weight tables, which the reference tree does not hold, and any weight_scheme
+ * but 0 is refused; vertex positions only: colours of the last mesh are dropped, not carried across.  Opt-in: no other call changes. */
+typedef struct rsm_mesh_subdivide_params {
+    int iterations;            /* 1..8 (subdiv.mlx: 3) */
+    double threshold;          /* finite, >= 0: an edge splits when it is strictly longer; 0 splits every edge */
+    double threshold_fraction; /* 0 = unused, else in (0, 1]: thr = fraction * the input's box diagonal, and threshold is not read (subdiv.mlx: 0.01) */
+    int weight_scheme;         /* 0 (Loop's weights); 1 and 2 are not built and are refused */
+} rsm_mesh_subdivide_params;
+/* stats: [0] / [1] vertices / faces in, [2] / [3] vertices / faces out, [4] iterations run (those that split an edge), [5] thr, [6] edges
+ * split, [7] of them border edges (one face), [8] of them edges of three or more faces, [9..12] faces with 0 / 1 / 2 / 3 split edges (those
+ * with a repeated index under 0), [13] / [14] interior / border vertices moved -- [6..14] summed over the iterations run --, [15] the locked
+ * vertices of the last mesh looked at, [16] the largest number of faces at a vertex met */
+#define RSM_MESH_SUBDIVIDE_STATS 17
+/* nv vertices (xyz nv*3 float) and nf faces (faces nf*3 int32) in host buffers -> the context's last mesh, as rsm_mesh_decimate
+ * (rsm_poisson_last_mesh copies it out; *n_vertices, *n_faces size its buffers; colours of the last mesh are dropped).  An empty mesh, or
+ * one without an edge longer than thr: the mesh as it came, [4] = 0, RSM_OK.  RSM_E_INVALID (rsm_last_error names the cause): a parameter
+ * outside its range above, weight_scheme not 0, a face index outside [0, nv), a coordinate that is not finite, 3 nf >= 2^31, nv above
+ * INT32_MAX, a negative count, a NULL pointer, an iteration whose result would pass those limits (named).  Every failed call leaves the last
+ * mesh and its colours as they were. */
+int rsm_mesh_subdivide(rsm_ctx *ctx, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, const rsm_mesh_subdivide_params *p, int64_t *n_vertices,
+                       int64_t *n_faces, double *stats);
+/* the same on DEVICE buffers */
+int rsm_mesh_subdivide_device(rsm_ctx *ctx, const float *d_xyz, int64_t nv, const int32_t *d_faces, int64_t nf, const rsm_mesh_subdivide_params *p,
+                              int64_t *n_vertices, int64_t *n_faces, double *stats);
+/* the same on the context's last mesh where it lies; the result replaces it */
+int rsm_mesh_subdivide_last(rsm_ctx *ctx, const rsm_mesh_subdivide_params *p, int64_t *n_vertices, int64_t *n_faces, double *stats);
+/* stage entry point (host buffers) for the tests: the decisions of one iteration.  Per unique edge of the faces without a repeated index,
+ * in key order (room for 3 nf each; *n_edges of them): key = (a << 32) | b with a < b, multiplicity, split (0 / 1), odd_position (3 floats;
+ * zeros where the edge does not split); per vertex: vertex_class (0 interior, 1 border, 2 locked) and even_position (nv*3).  *thr (may be
+ * NULL): the threshold used. */
+int rsm_stage_mesh_subdivide_edges(rsm_ctx *ctx, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, const rsm_mesh_subdivide_params *p, uint64_t *keys,
+                                   int32_t *multiplicity, int32_t *split, float *odd_position, int64_t *n_edges, int32_t *vertex_class, float *even_position,
+                                   double *thr);
+
 /* ---- the density trim of the surface (where mesh.bat runs PoissonRecon --density --samplesPerNode 2 and then SurfaceTrimmer --smooth 100
  * --trim 7 --aRatio 0.01) -------------------------------------------------------------------------------------------------------------
  * Not a bit-parity port of those tools: the rules as DESIGN.md 9 (f11) defines them.  Every vertex gets the depth at which a grid node

@@ -3,6 +3,7 @@
                                [--mesh-samples-per-node [2] [--mesh-kernel-depth 0]]
                                [--mesh-density-trim [7] [--mesh-density-smooth 100] [--mesh-island-ratio 0.01]]
                                [--mesh-clean [--mesh-smooth 5] [--mesh-min-piece 10%]] [--mesh-close-holes [30]] [--mesh-decimate [100000]]
+                               [--mesh-subdivide [3] [--mesh-subdivide-threshold 1]]
                                [--mesh-color [--mesh-color-mode blend] [--mesh-color-min-cos 0.2] [--mesh-color-eps LENGTH]]
                                [--mesh-stitch [--mesh-stitch-lambda 0.01] [--mesh-stitch-iterations 0]]]
 
@@ -25,6 +26,10 @@ With --mesh-close-holes (implies --mesh) the small border loops of that mesh are
 Holes", does: loops of at most N edges (30 when given bare) get their least-area triangulation, after --mesh-clean.
 With --mesh-decimate (implies --mesh) that mesh is thinned to N faces (100000 when given bare) on the GPU as Demo/meshlab/decimation.mlx's
 "Quadric Edge Collapse Decimation" does, after --mesh-close-holes and before the colouring.
+With --mesh-subdivide (implies --mesh) that mesh is refined on the GPU as Demo/meshlab/subdiv.mlx's "Subdivision Surfaces: Loop" does: N
+iterations (3 when given bare), each splitting every edge longer than --mesh-subdivide-threshold per cent of the mesh's box diagonal (1, the
+script's value) -- after --mesh-decimate and before the colouring, whose resolution is the vertex density.  Limits: Loop's own
+weights only (MeshLab's LoopWeight 0; the script's LoopWeight 2 is not built), vertex positions only, no colours carried across.
 With --mesh-color (implies --mesh) the mesh's vertices are coloured from every camera's rectified image, on the GPU, where
 CCloudOptimization::run calls TextureStitcher (visibility by a depth buffer per view, the best view or a cos-weighted blend; DESIGN.md 9
 f9): the coloured mesh goes to the configuration's outfilename, where TextureStitcher's --out goes, and the cloud PLY to <name>_cloud.ply.
@@ -107,6 +112,12 @@ def main(argv=None) -> int:
     ap.add_argument("--mesh-decimate", type=int, nargs="?", const=100000, default=None, metavar="N",
                     help="after the surface (implied; after --mesh-clean and --mesh-close-holes when given): thin the mesh to N faces (decimation.mlx's "
                          "TargetFaceNum 100000 when given bare) by quadric edge collapses on the GPU, before the mesh is written and coloured")
+    ap.add_argument("--mesh-subdivide", type=int, nargs="?", const=3, default=None, metavar="N",
+                    help="after the surface (implied; after --mesh-decimate when given): N iterations (1..8; subdiv.mlx's 3 when given bare) of Loop "
+                         "subdivision on the GPU, before the mesh is written and coloured.  Loop's own weights only (MeshLab's LoopWeight 0; LoopWeight 1 "
+                         "and 2, of which subdiv.mlx selects 2, are not built); positions only")
+    ap.add_argument("--mesh-subdivide-threshold", type=float, default=1.0, metavar="PCT",
+                    help="with --mesh-subdivide: only edges longer than PCT per cent of the mesh's box diagonal split (subdiv.mlx: 1; 0 = every edge)")
     ap.add_argument("--mesh-color", action="store_true",
                     help="after the surface (implied; after --mesh-clean when given): colour the mesh's vertices from the rectified views on the "
                          "GPU, where the reference calls TextureStitcher.  The coloured PLY goes to the configuration's outfilename (TextureStitcher's "
@@ -129,7 +140,8 @@ def main(argv=None) -> int:
         args.mesh_color = True
     if args.mesh_color:
         args.mesh = True
-    if args.mesh_density_trim is not None or args.mesh_close_holes is not None or args.mesh_decimate is not None or args.mesh_samples_per_node is not None:
+    if args.mesh_density_trim is not None or args.mesh_close_holes is not None or args.mesh_decimate is not None or args.mesh_samples_per_node is not None or \
+            args.mesh_subdivide is not None:
         args.mesh = True
     if args.mesh_clean:
         args.mesh = True
@@ -212,7 +224,7 @@ def main(argv=None) -> int:
         except RsmError as e:                                      # e.g. --mesh-depth outside 5..9, --mesh-samples-per-node 0
             print(e)
             return 1
-        cst = tst = hst = dst = None
+        cst = tst = hst = dst = ust = None
         if args.mesh_density_trim is not None:
             try:
                 mv, mf, tst = sink.trim_mesh(smooth_steps=args.mesh_density_smooth, trim=args.mesh_density_trim, island_ratio=args.mesh_island_ratio)
@@ -235,6 +247,12 @@ def main(argv=None) -> int:
             try:
                 mv, mf, dst = sink.decimate_mesh(target_faces=args.mesh_decimate)
             except RsmError as e:                                  # a negative --mesh-decimate
+                print(e)
+                return 1
+        if args.mesh_subdivide is not None:
+            try:
+                mv, mf, ust = sink.subdivide_mesh(iterations=args.mesh_subdivide, threshold_fraction=args.mesh_subdivide_threshold / 100.0)
+            except RsmError as e:                                  # --mesh-subdivide outside 1..8, a threshold outside 0..100
                 print(e)
                 return 1
         mesh_out = args.mesh_out or os.path.join(os.path.dirname(os.path.abspath(out)), "bigmesh.ply")
@@ -260,6 +278,12 @@ def main(argv=None) -> int:
             print("Mesh decimate: %d -> %d faces (target %d%s) in %d rounds, %d collapses (%d of border edges); %d locked vertices, largest cost %.3g"
                   % (dst["n_faces_in"], dst["n_faces"], dst["target"], "" if dst["target_reached"] else ", not reached", dst["rounds"], dst["collapses"],
                      dst["border_collapses"], dst["locked_vertices"], dst["max_cost"]))
+        if ust is not None:
+            print("Mesh subdivide: %d -> %d faces, %d -> %d vertices in %d iterations (threshold %.6g); %d edges split (%d border, %d many-face); "
+                  "faces with 0/1/2/3 splits %d/%d/%d/%d; %d interior and %d border vertices moved, %d locked"
+                  % (ust["n_faces_in"], ust["n_faces"], ust["n_vertices_in"], ust["n_vertices"], ust["iterations"], ust["threshold"], ust["split_edges"],
+                     ust["split_border_edges"], ust["split_many_face_edges"], ust["faces_0_splits"], ust["faces_1_split"], ust["faces_2_splits"],
+                     ust["faces_3_splits"], ust["moved_interior"], ust["moved_border"], ust["locked_vertices"]))
         print("%d vertices, %d faces -> %s" % (len(mv), len(mf), mesh_out))
         if args.mesh_color:
             try:

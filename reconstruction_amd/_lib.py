@@ -120,6 +120,14 @@ class MeshDecimateParams(C.Structure):
 MESH_DECIMATE_STATS = 20
 
 
+class MeshSubdivideParams(C.Structure):
+    """rsm_mesh_subdivide_params (include/rsm.h)."""
+    _fields_ = [("iterations", C.c_int), ("threshold", C.c_double), ("threshold_fraction", C.c_double), ("weight_scheme", C.c_int)]
+
+
+MESH_SUBDIVIDE_STATS = 17
+
+
 class MeshColorParams(C.Structure):
     """rsm_mesh_color_params (include/rsm.h)."""
     _fields_ = [("mode", C.c_int), ("min_cos", C.c_double), ("depth_eps", C.c_double)]
@@ -162,6 +170,7 @@ _pI, _pL, _pD = C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_double)
 _PIN, _POUT, _BND, _RIN, _ROUT, _FLT = (C.POINTER(t) for t in (PairIn, PairOut, Boundary, RectifyIn, RectifyOut, FilterParams))
 _MLS, _VIEW, _PSN, _CLN, _COL, _STI = (C.POINTER(t) for t in (MlsParams, DedupView, PoissonParams, MeshCleanParams, MeshColorParams, MeshStitchParams))
 _TRM, _CLO, _DEC, _PDN = C.POINTER(MeshTrimParams), C.POINTER(MeshCloseParams), C.POINTER(MeshDecimateParams), C.POINTER(PoissonDensityParams)
+_SUB = C.POINTER(MeshSubdivideParams)
 PROTOTYPES = {
     "rsm_create": (_I, [_V, _I]),
     "rsm_destroy": (None, [_V]),
@@ -272,6 +281,10 @@ PROTOTYPES = {
     "rsm_stage_mesh_quadrics": (_I, [_V, _V, _L, _V, _L, _D, _V]),
     "rsm_stage_mesh_collapse_costs": (_I, [_V, _V, _L, _V, _L, _V, _DEC, _V, _V, _V, _V, _V, _pL]),
     "rsm_stage_mesh_collapse_round": (_I, [_V, _V, _L, _V, _L, _V, _DEC, _L, _V, _V, _V, _pL, _V, _pL, _pL]),
+    "rsm_mesh_subdivide": (_I, [_V, _V, _L, _V, _L, _SUB, _pL, _pL, _V]),
+    "rsm_mesh_subdivide_device": (_I, [_V, _V, _L, _V, _L, _SUB, _pL, _pL, _V]),
+    "rsm_mesh_subdivide_last": (_I, [_V, _SUB, _pL, _pL, _V]),
+    "rsm_stage_mesh_subdivide_edges": (_I, [_V, _V, _L, _V, _L, _SUB, _V, _V, _V, _V, _pL, _V, _V, _pD]),
     "rsm_mesh_color": (_I, [_V, _V, _L, _V, _L, _VIEW, _I, _COL, _V, _V, _V]),
     "rsm_mesh_color_device": (_I, [_V, _V, _L, _V, _L, _VIEW, _I, _COL, _V, _V, _V]),
     "rsm_mesh_color_last": (_I, [_V, _VIEW, _I, _COL, _V]),

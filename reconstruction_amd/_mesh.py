@@ -6,7 +6,7 @@ import numpy as np
 
 from . import _lib
 from ._context import ContextBase, _normals4, _p, _u8, _views
-from ._lib import MeshCleanParams, MeshCloseParams, MeshColorParams, MeshDecimateParams, MeshStitchParams, MeshTrimParams, PoissonDensityParams, PoissonParams
+from ._lib import MeshCleanParams, MeshCloseParams, MeshColorParams, MeshDecimateParams, MeshStitchParams, MeshSubdivideParams, MeshTrimParams, PoissonDensityParams, PoissonParams
 
 # the solve's default stopping residual: one decade above the 4.2e-6 the float32 solver reaches at depth 9
 POISSON_REL_RESIDUAL = 4e-5
@@ -439,6 +439,60 @@ class MeshPart(ContextBase):
         self._chk(self._lib.rsm_stage_mesh_collapse_round(self._h, _p(v), len(v), _p(f), len(f), _p(q), C.byref(prm), int(need), _p(ov), _p(of), _p(oq),
                                                           C.byref(nfo), _p(sel), C.byref(nsel), C.byref(nkept)))
         return ov[:len(v)].copy(), of[:int(nfo.value)].copy(), oq[:len(v)].copy(), sel[:int(nsel.value)].copy(), int(nkept.value)
+
+    # ---- the subdivision of the final mesh: subdiv.mlx's "Subdivision Surfaces: Loop" (csrc/k_meshsubdivide.hip) ----
+    _SUBDIVIDE_KEYS = ("n_vertices_in", "n_faces_in", "n_vertices", "n_faces", "iterations", "threshold", "split_edges", "split_border_edges",
+                       "split_many_face_edges", "faces_0_splits", "faces_1_split", "faces_2_splits", "faces_3_splits", "moved_interior", "moved_border",
+                       "locked_vertices", "max_valence")
+
+    @staticmethod
+    def mesh_subdivide_params(iterations=3, threshold=0.0, threshold_fraction=0.0, weight_scheme=0):
+        """rsm_mesh_subdivide_params.  threshold_fraction > 0: the threshold is that fraction of the input's box diagonal (subdiv.mlx: 0.01)
+        and `threshold` is not read; both 0: every edge splits.  weight_scheme: only 0 (Loop's own weights) is built."""
+        return MeshSubdivideParams(int(iterations), float(threshold), float(threshold_fraction), int(weight_scheme))
+
+    def _mesh_subdivide(self, fn, mesh_args, prm):
+        """One of the three rsm_mesh_subdivide* entries: (n_vertices, n_faces, stats) of the mesh it leaves with the context."""
+        nv, nf = C.c_int64(), C.c_int64()
+        st = (C.c_double * _lib.MESH_SUBDIVIDE_STATS)()
+        self._chk(fn(self._h, *mesh_args, C.byref(prm), C.byref(nv), C.byref(nf), st))
+        return int(nv.value), int(nf.value), {k: (float(st[i]) if k == "threshold" else int(st[i])) for i, k in enumerate(self._SUBDIVIDE_KEYS)}
+
+    def mesh_subdivide(self, vertices, faces, **params):
+        """subdiv.mlx's "Subdivision Surfaces: Loop" on the GPU: per iteration every edge strictly longer than the threshold
+        gets a new vertex, the old vertices at such an edge move by Loop's rules, every face becomes 1 to 4.  Loop's own weights only
+        (MeshLab's LoopWeight 0); positions only -- no colours are carried across.  params: mesh_subdivide_params'.  vertices [nv,3]
+        float32, faces [nf,3] int32 -> (vertices, faces, stats dict).  The result is the context's last mesh (poisson_last_mesh[_device])."""
+        v, f = _mesh_arrays(vertices, faces)
+        nv, nf, stats = self._mesh_subdivide(self._lib.rsm_mesh_subdivide, (_p(v), len(v), _p(f), len(f)), self.mesh_subdivide_params(**params))
+        return self.poisson_last_mesh(nv, nf) + (stats,)
+
+    def mesh_subdivide_device(self, vertices_ptr, n_vertices, faces_ptr, n_faces, **params):
+        """rsm_mesh_subdivide_device on device buffers (addresses).  Returns (n_vertices, n_faces, stats); the mesh stays with the context
+        (poisson_last_mesh[_device] copies it out)."""
+        return self._mesh_subdivide(self._lib.rsm_mesh_subdivide_device, (vertices_ptr, n_vertices, faces_ptr, n_faces), self.mesh_subdivide_params(**params))
+
+    def mesh_subdivide_last(self, **params):
+        """mesh_subdivide of the context's last mesh where it lies on the device; the result replaces it and its colours are dropped.
+        Returns (vertices, faces, stats)."""
+        nv, nf, stats = self._mesh_subdivide(self._lib.rsm_mesh_subdivide_last, (), self.mesh_subdivide_params(**params))
+        return self.poisson_last_mesh(nv, nf) + (stats,)
+
+    def mesh_subdivide_edges(self, vertices, faces, **params):
+        """Stage: the decisions of one iteration -> dict(keys uint64 = (a << 32) | b per unique edge in key order, multiplicity int32, split
+        int32 0 / 1, odd float32 [ne,3] (zeros where the edge stays), vertex_class int32 [nv] (0 interior, 1 border, 2 locked), even float32
+        [nv,3], threshold float)."""
+        v, f = _mesh_arrays(vertices, faces)
+        n = max(3 * len(f), 1)
+        key, mult, split, odd = np.zeros(n, np.uint64), np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros((n, 3), np.float32)
+        cls, even = np.zeros(max(len(v), 1), np.int32), np.zeros((max(len(v), 1), 3), np.float32)
+        ne, thr = C.c_int64(), C.c_double()
+        prm = self.mesh_subdivide_params(**params)
+        self._chk(self._lib.rsm_stage_mesh_subdivide_edges(self._h, _p(v), len(v), _p(f), len(f), C.byref(prm), _p(key), _p(mult), _p(split), _p(odd), C.byref(ne),
+                                                           _p(cls), _p(even), C.byref(thr)))
+        ne = int(ne.value)
+        return dict(keys=key[:ne].copy(), multiplicity=mult[:ne].copy(), split=split[:ne].copy(), odd=odd[:ne].copy(), vertex_class=cls[:len(v)].copy(),
+                    even=even[:len(v)].copy(), threshold=float(thr.value))
 
     # ---- colours of the mesh from the rig's views, where run() calls TextureStitcher (DESIGN.md 9 f9; csrc/k_meshcolor.hip) ----
     @staticmethod

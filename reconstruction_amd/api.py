@@ -253,6 +253,7 @@ class CloudOptimization:
     clean_mesh() (what meshlab.bat goes on to do: Laplacian smoothing and the removal of isolated pieces and bad faces, on the GPU),
     close_mesh_holes() (its last filter: small border loops filled with their least-area triangulation, on the GPU),
     decimate_mesh() (decimation.mlx: the mesh thinned to a face count by quadric edge collapses, on the GPU),
+    subdivide_mesh() (subdiv.mlx: the mesh refined by Loop subdivision, Loop's own weights, on the GPU),
     color_mesh() (where run() ends with TextureStitcher: the mesh's vertices coloured from every camera's rectified image, on the
     GPU), stitch_mesh() (the tool's seam removal: the views' exposure seams levelled in those colours, on the GPU).  `cloud_normals` accumulates what the
     reference's global `*cloud_normals += *cloud_normal` (:123) does: per pair (xyz float32 [m,3], normals float32 [m,4])."""
@@ -374,6 +375,19 @@ class CloudOptimization:
         if getattr(self, "mesh_result", None) is None:
             raise ValueError("CloudOptimization.decimate_mesh: mesh() first (it decimates mesh()'s surface)")
         self.mesh_result = self._ctx.mesh_decimate_last(target_faces=target_faces, **params)
+        self.mesh_colors = None
+        return self.mesh_result
+
+    def subdivide_mesh(self, iterations=3, threshold_fraction=0.01, **params):
+        """Where a user of the reference reaches for Demo/meshlab/subdiv.mlx ("Subdivision Surfaces: Loop", Iterations 3, Threshold 1 % of
+        the box diagonal): mesh_result refined by Loop subdivision of every edge longer than the threshold (Context.mesh_subdivide_last on
+        the mesh mesh() / clean_mesh() / decimate_mesh() left with the context, without a host round trip) -- call it
+        before color_mesh(), whose colour resolution is the vertex density.  Loop's own weights only (the script's LoopWeight 2 is not
+        built); positions only: colours computed before are dropped.  params: Context.mesh_subdivide_params' (threshold: an absolute
+        length, read when threshold_fraction is 0).  Replaces mesh_result."""
+        if getattr(self, "mesh_result", None) is None:
+            raise ValueError("CloudOptimization.subdivide_mesh: mesh() first (it subdivides mesh()'s surface)")
+        self.mesh_result = self._ctx.mesh_subdivide_last(iterations=iterations, threshold_fraction=threshold_fraction, **params)
         self.mesh_colors = None
         return self.mesh_result
 

@@ -420,38 +420,6 @@ __global__ __launch_bounds__(256) void k_md_renumber(const int32_t *__restrict__
 }
 
 // ---- host -----------------------------------------------------------------------------------------------------------------------------------
-// the scratch of the rounds: an allocator (dev_prims.h) that hands out pieces of a few large blocks and starts over with rewind(), so that
-// only the first round allocates (a later round asks for the same pieces in the same order, none of them larger)
-struct Pool {
-    struct Block {
-        uint8_t *p;
-        size_t size;
-    };
-    std::vector<Block> blocks;
-    size_t cur = 0, off = 0, first;
-    explicit Pool(size_t first_block) : first(first_block) {}
-    ~Pool() {
-        for (Block &b : blocks) (void)hipFree(b.p);
-    }
-    void rewind() { cur = off = 0; }
-    template <typename T> T *get(size_t n) {
-        const size_t bytes = (((n ? n : 1) * sizeof(T)) + 255) & ~(size_t)255;
-        for (;; cur++, off = 0) {
-            if (cur == blocks.size()) {
-                void *q = nullptr;
-                const size_t size = std::max(bytes, first);
-                if (hipMalloc(&q, size) != hipSuccess) return nullptr;
-                blocks.push_back(Block{(uint8_t *)q, size});
-            }
-            if (off + bytes <= blocks[cur].size) {
-                T *r = (T *)(blocks[cur].p + off);
-                off += bytes;
-                return r;
-            }
-        }
-    }
-};
-
 // the tables of a mesh and the cost of its unique edges
 struct Round {
     size_t ne = 0;

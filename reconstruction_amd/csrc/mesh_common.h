@@ -1,7 +1,7 @@
 // mesh_common.h -- the mesh units' topology layer, beyond dev_prims.h: what the surface (k_poisson.hip), its smoothing / clean-up
-// (k_meshclean.hip), its density trim (k_meshtrim.hip), the closing of its holes (k_meshclose.hip), its decimation (k_meshdecimate.hip) and
-// its colours (k_meshcolor.hip, k_meshstitch.hip) share.  The scratch of one call; the sorted edge table and the corner lists of a mesh,
-// built from any allocator (dev_prims.h: DevMem here, the decimation's Pool); the union-find over the table; the vertex box and its
+// (k_meshclean.hip), its density trim (k_meshtrim.hip), the closing of its holes (k_meshclose.hip), its decimation (k_meshdecimate.hip), its subdivision
+// (k_meshsubdivide.hip) and its colours (k_meshcolor.hip, k_meshstitch.hip) share.  The scratch of one call; the sorted edge table and the corner lists of a mesh,
+// built from any allocator (dev_prims.h: DevMem and Pool here); the union-find over the table; the vertex box and its
 // diagonal; a point in fp64; the end of a call that replaces a mesh.  What a stage does with the table's runs stays in its own unit.
 // The kernels are templates for the reason dev_prims.h gives: only a unit that launches one (k_mesh_edge_keys<>) holds a copy.
 #pragma once
@@ -9,6 +9,7 @@
 #include "dev_prims.h"
 #include "rsm_dev.h"
 
+#include <algorithm>
 #include <vector>
 
 struct DevMem { // scratch of one call
@@ -25,6 +26,39 @@ struct DevMem { // scratch of one call
     }
     ~DevMem() {
         for (void *q : p) (void)hipFree(q);
+    }
+};
+
+// the scratch of a stage that runs rounds: an allocator (dev_prims.h) that hands out pieces of a few large blocks and starts over with
+// rewind(), so that only the first round allocates (the decimation: a later round asks for the same pieces in the same order, none of them
+// larger); without rewind() it is one hipMalloc for everything that fits its first block (the subdivision: a pool an iteration)
+struct Pool {
+    struct Block {
+        uint8_t *p;
+        size_t size;
+    };
+    std::vector<Block> blocks;
+    size_t cur = 0, off = 0, first;
+    explicit Pool(size_t first_block) : first(first_block) {}
+    ~Pool() {
+        for (Block &b : blocks) (void)hipFree(b.p);
+    }
+    void rewind() { cur = off = 0; }
+    template <typename T> T *get(size_t n) {
+        const size_t bytes = (((n ? n : 1) * sizeof(T)) + 255) & ~(size_t)255;
+        for (;; cur++, off = 0) {
+            if (cur == blocks.size()) {
+                void *q = nullptr;
+                const size_t size = std::max(bytes, first);
+                if (hipMalloc(&q, size) != hipSuccess) return nullptr;
+                blocks.push_back(Block{(uint8_t *)q, size});
+            }
+            if (off + bytes <= blocks[cur].size) {
+                T *r = (T *)(blocks[cur].p + off);
+                off += bytes;
+                return r;
+            }
+        }
     }
 };
 

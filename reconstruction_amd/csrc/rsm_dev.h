@@ -339,6 +339,20 @@ int mesh_collapse_round_device(float *d_v, int64_t nv, const int32_t *d_f, int64
 int mesh_decimate_device(const float *d_v, int64_t nv, const int32_t *d_f, int64_t nf, const rsm_mesh_decimate_params *p, PoissonMesh *out, double *stats,
                          int *invalid, hipStream_t st);
 
+// the Loop subdivision of the final mesh (k_meshsubdivide.hip).  Device buffers: nv float xyz, nf int32 x 3; *invalid as
+// mesh_clean_device's, or MESH_INVALID_TOO_LARGE + it: iteration it (from 0) would leave more than INT32_MAX vertices or 3 nf >= 2^31
+// (csrc/subdivide_limits.h); parameters are the caller's to check.
+#define MESH_INVALID_TOO_LARGE 16
+struct rsm_mesh_subdivide_params;
+// one iteration's decisions.  Per unique edge in key order (room for 3 nf each): key, multiplicity, whether it splits, the odd point (zeros
+// where it does not); per vertex: the class (0 interior, 1 border, 2 locked) and the even point; *thr_used: the threshold of the call
+int mesh_subdivide_edges_device(const float *d_v, int64_t nv, const int32_t *d_f, int64_t nf, const rsm_mesh_subdivide_params *p, uint64_t *d_key, int32_t *d_mult,
+                                int32_t *d_split, float *d_odd, int64_t *n_edges, int32_t *d_class, float *d_even, double *thr_used, int *invalid, hipStream_t st);
+// the whole call; the result replaces *out, which may own d_v / d_f, and only at the very end: a failed call leaves *out as it was.
+// stats: RSM_MESH_SUBDIVIDE_STATS doubles, may be NULL
+int mesh_subdivide_device(const float *d_v, int64_t nv, const int32_t *d_f, int64_t nf, const rsm_mesh_subdivide_params *p, PoissonMesh *out, double *stats,
+                          int *invalid, hipStream_t st);
+
 // the density trim of the surface (k_meshtrim.hip).  Device buffers: n float xyz samples with float4 normals (d_sn4 may be
 // NULL: a finite point is a valid sample), nv float xyz, nf int32 x 3.  Parameters are the caller's to check; each call validates the
 // mesh it is given, and RSM_E_INVALID comes with *invalid as mesh_clean_device's.

@@ -1,6 +1,6 @@
 // rsm_mesh.hip -- the mesh back end's host side: the dense-grid Poisson surface, its smoothing and clean-up, its density trim, the closing of
-// its holes, its decimation, and its colours from the rig's views with their seams levelled (k_poisson.hip, k_poisson_density.hip, k_meshclean.hip, k_meshtrim.hip,
-// k_meshclose.hip, k_meshdecimate.hip, k_meshcolor.hip, k_meshstitch.hip).
+// its holes, its decimation, its subdivision, and its colours from the rig's views with their seams levelled (k_poisson.hip, k_poisson_density.hip, k_meshclean.hip, k_meshtrim.hip,
+// k_meshclose.hip, k_meshdecimate.hip, k_meshsubdivide.hip, k_meshcolor.hip, k_meshstitch.hip).
 #include "rsm_ctx.h"
 
 #include <cmath>
@@ -299,7 +299,7 @@ extern "C" int rsm_stage_poisson_rhs_weighted(rsm_ctx *c, const float *xyz, cons
     return finish(c, T);
 }
 
-// ---- the mesh-to-mesh stages: clean, trim, close_holes, decimate (how the back end's units are laid out) -------------------------
+// ---- the mesh-to-mesh stages: clean, trim, close_holes, decimate, subdivide (how the back end's units are laid out) -------------------------
 static int mesh_counts_ok(rsm_ctx *c, const char *who, int64_t nv, int64_t nf) { // who: "mesh_clean" / "mesh_trim" / "mesh_color" ...
     if (nv < 0 || nv > (int64_t)INT32_MAX) return set_err(c, RSM_E_INVALID, "%s: nv %lld outside 0..INT32_MAX", who, (long long)nv);
     if (nf < 0 || 3 * nf >= ((int64_t)1 << 31)) return set_err(c, RSM_E_INVALID, "%s: nf %lld negative or 3 nf >= 2^31", who, (long long)nf);
@@ -317,6 +317,8 @@ static int mesh_in_ok(rsm_ctx *c, const char *who, int64_t nv, int64_t nf, const
 }
 // invalid: mesh_validate_device's 1 / 2
 static int mesh_fail(rsm_ctx *c, const char *who, int s, int invalid) {
+    if (s == RSM_E_INVALID && invalid >= MESH_INVALID_TOO_LARGE)
+        return set_err(c, s, "%s: the result of iteration %d would be too large (vertices above INT32_MAX or 3 nf >= 2^31)", who, invalid - MESH_INVALID_TOO_LARGE + 1);
     if (s == RSM_E_INVALID) return set_err(c, s, invalid == 1 ? "%s: a face index outside [0, nv)" : "%s: a coordinate that is not finite", who);
     if (s == RSM_E_NOMEM) return set_err(c, s, "%s: no device memory", who);
     return set_err(c, s, "%s: failed%s", who, hip_tail(s).c_str());
@@ -738,6 +740,55 @@ extern "C" int rsm_stage_mesh_collapse_round(rsm_ctx *c, const float *xyz, int64
         return mesh_fail(c, "mesh_decimate", s, invalid);
     T.later(out_xyz, dv, 3 * (size_t)nv).later(out_quadrics, dq, 10 * (size_t)nv);
     T.later(out_faces, dfo, 3 * (size_t)*n_faces_out).later(selected_keys, ds, (size_t)*n_selected);
+    return finish(c, T);
+}
+
+// ---- the Loop subdivision of the final mesh (k_meshsubdivide.hip) ----------------------------------------------------------
+static int meshsubdivide_params_ok(rsm_ctx *c, const rsm_mesh_subdivide_params *p) {
+    if (!p) return set_err(c, RSM_E_INVALID, "mesh_subdivide: params is NULL");
+    if (p->iterations < 1 || p->iterations > 8) return set_err(c, RSM_E_INVALID, "mesh_subdivide: iterations %d outside 1..8", p->iterations);
+    if (!std::isfinite(p->threshold) || p->threshold < 0.0) return set_err(c, RSM_E_INVALID, "mesh_subdivide: threshold %g negative or not finite", p->threshold);
+    if (!(p->threshold_fraction >= 0.0 && p->threshold_fraction <= 1.0))
+        return set_err(c, RSM_E_INVALID, "mesh_subdivide: threshold_fraction %g outside [0, 1]", p->threshold_fraction);
+    if (p->weight_scheme != 0)
+        return set_err(c, RSM_E_INVALID, "mesh_subdivide: weight_scheme %d not 0 (only Loop's own weights are built: LoopWeight 1 and 2 rest on tables this library does not have)",
+                       p->weight_scheme);
+    return RSM_OK;
+}
+extern "C" int rsm_mesh_subdivide_device(rsm_ctx *c, const float *d_xyz, int64_t nv, const int32_t *d_faces, int64_t nf, const rsm_mesh_subdivide_params *p,
+                                         int64_t *n_vertices, int64_t *n_faces, double *stats) {
+    return mesh_stage_p(c, "mesh_subdivide", MeshIn{MESH_DEVICE, d_xyz, nv, d_faces, nf}, p, meshsubdivide_params_ok, mesh_subdivide_device, n_vertices, n_faces, stats);
+}
+extern "C" int rsm_mesh_subdivide(rsm_ctx *c, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, const rsm_mesh_subdivide_params *p, int64_t *n_vertices,
+                                  int64_t *n_faces, double *stats) {
+    return mesh_stage_p(c, "mesh_subdivide", MeshIn{MESH_HOST, xyz, nv, faces, nf}, p, meshsubdivide_params_ok, mesh_subdivide_device, n_vertices, n_faces, stats);
+}
+extern "C" int rsm_mesh_subdivide_last(rsm_ctx *c, const rsm_mesh_subdivide_params *p, int64_t *n_vertices, int64_t *n_faces, double *stats) {
+    return mesh_stage_p(c, "mesh_subdivide", MeshIn{MESH_LAST}, p, meshsubdivide_params_ok, mesh_subdivide_device, n_vertices, n_faces, stats);
+}
+
+extern "C" int rsm_stage_mesh_subdivide_edges(rsm_ctx *c, const float *xyz, int64_t nv, const int32_t *faces, int64_t nf, const rsm_mesh_subdivide_params *p,
+                                              uint64_t *keys, int32_t *multiplicity, int32_t *split, float *odd_position, int64_t *n_edges, int32_t *vertex_class,
+                                              float *even_position, double *thr) {
+    if (!c) return RSM_E_INVALID;
+    int s = meshsubdivide_params_ok(c, p);
+    if (s != RSM_OK || (s = mesh_counts_ok(c, "mesh_subdivide", nv, nf)) != RSM_OK) return s;
+    if (!n_edges || (nv > 0 && (!xyz || !vertex_class || !even_position)) || (nf > 0 && (!faces || !keys || !multiplicity || !split || !odd_position)))
+        return set_err(c, RSM_E_INVALID, "mesh_subdivide: a NULL pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t n = 3 * (size_t)nf;
+    Tmp T(c);
+    float *dv = T.up(xyz, 3 * (size_t)nv), *dodd = T.alloc<float>(3 * n), *deven = T.alloc<float>(3 * (size_t)nv);
+    int32_t *df = T.up(faces, n), *dm = T.alloc<int32_t>(n), *ds = T.alloc<int32_t>(n), *dc = T.alloc<int32_t>((size_t)nv);
+    uint64_t *dk = T.alloc<uint64_t>(n);
+    if (!dv || !df || !dodd || !deven || !dm || !ds || !dc || !dk) return set_err(c, RSM_E_NOMEM, "mesh_subdivide: no device memory");
+    if ((s = finish(c, T)) != RSM_OK) return s;
+    int invalid = 0;
+    if ((s = mesh_subdivide_edges_device(dv, nv, df, nf, p, dk, dm, ds, dodd, n_edges, dc, deven, thr, &invalid, c->stream)) != RSM_OK)
+        return mesh_fail(c, "mesh_subdivide", s, invalid);
+    const size_t ne = (size_t)*n_edges;
+    T.later(keys, dk, ne).later(multiplicity, dm, ne).later(split, ds, ne).later(odd_position, dodd, 3 * ne);
+    T.later(vertex_class, dc, (size_t)nv).later(even_position, deven, 3 * (size_t)nv);
     return finish(c, T);
 }
 
