@@ -595,6 +595,47 @@ int rsm_poisson_mesh_weighted_device(rsm_ctx *ctx, const float *d_xyz, const flo
 int rsm_stage_poisson_rhs_weighted(rsm_ctx *ctx, const float *xyz, const float *normals4, int64_t n, const rsm_poisson_params *p,
                                    const rsm_poisson_density_params *dp, const double *depth_in, double grid[4], double *b, uint8_t *occ,
                                    int64_t counts[2], double *rho, double *w, double *d);
+/* ---- one level finer than the dense grid reaches: a finest level on a band of bricks (script1.mlx: OctDepth 10) ---------------------------
+ * Opt-in; the calls above keep their behaviour, their bits and their range 5..9.  Here p->depth is the FINEST depth D, 6..10.  The dense
+ * solve above runs at D - 1 on the same box; the level of 2^D nodes per axis exists only on the bricks (8^3 nodes each) within band_bricks
+ * (Chebyshev) of a brick that holds a sample.  There the splat and right-hand side are the dense call's, the field starts from a quarter of
+ * the trilinear prolongation of the coarse field and is corrected by float32 conjugate gradients (one symmetric red-black Gauss-Seidel sweep
+ * as preconditioner) down to p->rel_residual; iso-value, marching tetrahedra and the occupancy trim are the dense call's, on the cells whose
+ * eight corners lie in the band.  With trim_cells = 0 the mesh has borders where the band ends.  A face the trim keeps needs its cell in the
+ * band: trim_cells <= 8 band_bricks - 1 (script1.mlx at depth 10 corresponds to trim_cells 8, which needs band_bricks 2; with 1 the most is
+ * 7).  Not a bit-parity port of PoissonRecon's octree: the rules as DESIGN.md 9 (f16) defines them. */
+typedef struct rsm_poisson_band_params {
+    int band_bricks;     /* 1..4: the box dilation of the occupied bricks */
+    int max_iterations;  /* >= 1: of the band solve (-> RSM_W_NOT_CONVERGED) */
+} rsm_poisson_band_params;
+#define RSM_POISSON_BAND_MAX_BRICKS (1 << 20) /* more active bricks than this: RSM_E_INVALID (such a cloud fills the volume, it is no surface) */
+/* stats: [0..11] as RSM_POISSON_STATS with h, N and the origin of the fine grid, [2] / [3] the band solve's residual and iterations;
+ * [12] active bricks, [13] occupied bricks, [14] the coarse solve's cycles, [15] its residual, [16] the band residual before the solve */
+#define RSM_POISSON_BAND_STATS 17
+/* as rsm_poisson_mesh[_device]: the mesh becomes the context's last mesh.  RSM_W_NOT_CONVERGED when either solve ended above rel_residual.
+ * RSM_E_INVALID (rsm_last_error names the parameter) also for depth outside 6..10, band_bricks outside 1..4, max_iterations < 1,
+ * trim_cells > 8 band_bricks - 1 and more than RSM_POISSON_BAND_MAX_BRICKS active bricks. */
+int rsm_poisson_mesh_banded(rsm_ctx *ctx, const float *xyz, const float *normals4, int64_t n, const rsm_poisson_params *p,
+                            const rsm_poisson_band_params *bp, int64_t *n_vertices, int64_t *n_faces, double *stats);
+int rsm_poisson_mesh_banded_device(rsm_ctx *ctx, const float *d_xyz, const float *d_normals4, int64_t n, const rsm_poisson_params *p,
+                                   const rsm_poisson_band_params *bp, int64_t *n_vertices, int64_t *n_faces, double *stats);
+/* stage entry points (host buffers) for the tests.  Fields are brick-major: element slot * 512 + lx + 8 (ly + 8 lz), slot = the brick's place in
+ * the ascending list `bricks` of linear brick indices bx + B (by + B bz), B = 2^depth / 8.
+ * band_rhs: samples -> grid (fine), bricks, b (doubles, exact from the fixed point), occ (per fine cell), g (the guess; from chi_c, (N/2)^3
+ * floats, when the caller gives one, else from the dense solve at depth - 1 with p's rel_residual and max_cycles), counts = {valid, not valid,
+ * active bricks, occupied bricks}.  brick_room: the bricks the caller's buffers hold (RSM_E_INVALID when the band has more); max_bricks: the
+ * cap, 0 = RSM_POISSON_BAND_MAX_BRICKS.  h = 0: nothing to mesh, counts[2] = 0.
+ * band_solve: b (floats) and g on n_bricks bricks -> chi, the residual reached, the iterations, the residual before them, history (optional,
+ * max_iterations doubles).  chi_c (optional, (N/2)^3 floats): the coarse field, which gives the guess at the band's inactive neighbours; NULL: 0.
+ * band_iso_mesh: a caller's chi, iso, grid and occ (may be NULL with trim_cells = 0) on n_bricks bricks -> the context's last mesh. */
+int rsm_stage_poisson_band_rhs(rsm_ctx *ctx, const float *xyz, const float *normals4, int64_t n, const rsm_poisson_params *p,
+                               const rsm_poisson_band_params *bp, const float *chi_c, int64_t max_bricks, int64_t brick_room, double grid[4],
+                               int32_t *bricks, double *b, uint8_t *occ, float *g, int64_t counts[4]);
+int rsm_stage_poisson_band_solve(rsm_ctx *ctx, const int32_t *bricks, int64_t n_bricks, int depth, const float *b, const float *g,
+                                 const float *chi_c, double rel_residual, int max_iterations, float *chi, double *residual, int *iterations,
+                                 double *residual0, double *history);
+int rsm_stage_band_iso_mesh(rsm_ctx *ctx, const int32_t *bricks, int64_t n_bricks, int depth, const float *chi, double iso,
+                            const double grid[4], const uint8_t *occ, int trim_cells, int64_t *n_vertices, int64_t *n_faces);
 /* binary little-endian PLY mesh: vertex float x, y, z; face list uchar int vertex_indices (what MeshLab and TextureStitcher read).  Host only. */
 int rsm_write_ply_mesh(const char *path, const float *xyz, int64_t n_vertices, const int32_t *faces, int64_t n_faces);
 

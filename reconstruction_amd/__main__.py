@@ -1,5 +1,5 @@
 """python -m reconstruction_amd <config.yml> [--device N] [--out cloud.ply] [--filter] [--mls [--isdelete] [--mls-out bigcloud.ply]]
-                              [--mesh [--mesh-depth 9] [--mesh-trim 4] [--mesh-out bigmesh.ply]
+                              [--mesh [--mesh-depth 9] [--mesh-trim 4] [--mesh-band [B]] [--mesh-out bigmesh.ply]
                                [--mesh-samples-per-node [2] [--mesh-kernel-depth 0]]
                                [--mesh-density-trim [7] [--mesh-density-smooth 100] [--mesh-island-ratio 0.01]]
                                [--mesh-clean [--mesh-smooth 5] [--mesh-min-piece 10%]] [--mesh-close-holes [30]] [--mesh-decimate [100000]]
@@ -18,6 +18,8 @@ With --mesh (implies --mls) the surface of that cloud: unscreened Poisson recons
 where CCloudOptimization::run calls meshlab.bat's Poisson filter -> bigmesh.ply (not a bit-parity port of that tool: DESIGN.md 9 f7).
 With --mesh-samples-per-node (implies --mesh) the Poisson call spreads every sample by the density of the cloud around it, as PoissonRecon's
 --samplesPerNode does (2 when given bare, mesh.bat's value; script1.mlx uses 3), so that thinly sampled parts hold their place.
+With --mesh-band (implies --mesh) the surface is one level finer than the dense grid reaches: --mesh-depth 6..10 is then the finest depth, a level
+that exists only on a band of bricks around the points, on top of the dense solve one depth coarser (script1.mlx's OctDepth 10).
 With --mesh-density-trim (implies --mesh) the Poisson call runs without its occupancy trim and the surface is trimmed as mesh.bat's
 SurfaceTrimmer does, on the GPU: cut along the iso-line of the smoothed sample density, small islands moved across.
 With --mesh-clean (implies --mesh) bigmesh.ply is that surface after meshlab.bat's other filters, on the GPU: Laplacian smoothing
@@ -83,7 +85,7 @@ def main(argv=None) -> int:
     ap.add_argument("--mesh", action="store_true",
                     help="after the MLS (implied): the surface of the smoothed cloud by unscreened Poisson reconstruction on a dense grid, "
                          "marching tetrahedra and a trim, on the GPU -> bigmesh.ply")
-    ap.add_argument("--mesh-depth", type=int, default=9, help="2^depth grid nodes per axis, 5..9 (mesh.bat: --depth 9)")
+    ap.add_argument("--mesh-depth", type=int, default=9, help="2^depth grid nodes per axis: 5..9 on the dense grid (mesh.bat: --depth 9), 6..10 with --mesh-band (script1.mlx: OctDepth 10)")
     ap.add_argument("--mesh-trim", type=int, default=4,
                     help="faces survive within this many cells of a cell that holds a point (4 = mesh.bat's --trim 7 at depth 9; 0 = no trim)")
     ap.add_argument("--mesh-out", default=None, help="path of the mesh (default: bigmesh.ply next to the --out PLY)")
@@ -91,6 +93,11 @@ def main(argv=None) -> int:
                     help="the surface (implied) with the density-adaptive splat: a sample is spread at the grid levels where a node would hold S of the "
                          "samples around it and weighs the inverse of their density (PoissonRecon --samplesPerNode; 2 when given bare as in mesh.bat, "
                          "script1.mlx: 3)")
+    ap.add_argument("--mesh-band", type=int, nargs="?", const=1, default=None, metavar="B",
+                    help="the surface (implied) one level finer than the dense grid reaches: --mesh-depth (6..10) is the finest depth, which exists only on "
+                         "the bricks of 8^3 nodes within B (1..4; 1 when given bare) of a brick that holds a point, on top of the dense solve one depth "
+                         "coarser; --mesh-trim is then at most 8 B - 1 (script1.mlx at depth 10 corresponds to --mesh-trim 8 --mesh-band 2); not with "
+                         "--mesh-samples-per-node or --mesh-density-trim at depth 10")
     ap.add_argument("--mesh-kernel-depth", type=int, default=0, metavar="K",
                     help="with --mesh-samples-per-node: the density is estimated on 2^K grid nodes per axis, 3..depth (0 = depth - 2)")
     ap.add_argument("--mesh-density-trim", type=float, nargs="?", const=7.0, default=None, metavar="T",
@@ -141,7 +148,7 @@ def main(argv=None) -> int:
     if args.mesh_color:
         args.mesh = True
     if args.mesh_density_trim is not None or args.mesh_close_holes is not None or args.mesh_decimate is not None or args.mesh_samples_per_node is not None or \
-            args.mesh_subdivide is not None:
+            args.mesh_subdivide is not None or args.mesh_band is not None:
         args.mesh = True
     if args.mesh_clean:
         args.mesh = True
@@ -220,8 +227,8 @@ def main(argv=None) -> int:
         t2 = time.perf_counter()
         try:
             mv, mf, mst = sink.mesh(depth=args.mesh_depth, trim_cells=args.mesh_trim if args.mesh_density_trim is None else 0,
-                                    samples_per_node=args.mesh_samples_per_node, kernel_depth=args.mesh_kernel_depth)
-        except RsmError as e:                                      # e.g. --mesh-depth outside 5..9, --mesh-samples-per-node 0
+                                    samples_per_node=args.mesh_samples_per_node, kernel_depth=args.mesh_kernel_depth, band_bricks=args.mesh_band)
+        except (RsmError, ValueError) as e:                        # e.g. --mesh-depth outside 5..9, --mesh-samples-per-node 0, --mesh-band with it
             print(e)
             return 1
         cst = tst = hst = dst = ust = None
@@ -257,8 +264,13 @@ def main(argv=None) -> int:
                 return 1
         mesh_out = args.mesh_out or os.path.join(os.path.dirname(os.path.abspath(out)), "bigmesh.ply")
         write_ply_mesh(mesh_out, mv, mf)
-        print("Mesh time: %.3f s (%d cycles, residual %.2e%s)" % (time.perf_counter() - t2, mst["cycles"], mst["residual"],
-                                                                  "" if mst["converged"] else ", NOT converged"))
+        if args.mesh_band is not None:
+            print("Mesh time: %.3f s (band of %d bricks around %d occupied; %d iterations from residual %.2e to %.2e on %d coarse cycles at %.2e%s)"
+                  % (time.perf_counter() - t2, mst["active_bricks"], mst["occupied_bricks"], mst["iterations"], mst["residual_before"], mst["residual"],
+                     mst["coarse_cycles"], mst["coarse_residual"], "" if mst["converged"] else ", NOT converged"))
+        else:
+            print("Mesh time: %.3f s (%d cycles, residual %.2e%s)" % (time.perf_counter() - t2, mst["cycles"], mst["residual"],
+                                                                      "" if mst["converged"] else ", NOT converged"))
         if args.mesh_samples_per_node is not None:
             print("Mesh samples per node %g: density on 2^%d nodes, %d of %d samples spread below depth %d (least depth %.2f)"
                   % (args.mesh_samples_per_node, mst["kernel_depth"], mst["n_below_depth"], mst["n_valid"], args.mesh_depth, mst["min_sample_depth"]))

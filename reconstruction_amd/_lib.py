@@ -82,6 +82,15 @@ class PoissonDensityParams(C.Structure):
 POISSON_WEIGHTED_STATS = 16
 
 
+class PoissonBandParams(C.Structure):
+    """rsm_poisson_band_params (include/rsm.h)."""
+    _fields_ = [("band_bricks", C.c_int), ("max_iterations", C.c_int)]
+
+
+POISSON_BAND_STATS = 17
+POISSON_BAND_MAX_BRICKS = 1 << 20
+
+
 class MeshCleanParams(C.Structure):
     """rsm_mesh_clean_params (include/rsm.h)."""
     _fields_ = [("smooth_steps", C.c_int), ("cotangent", C.c_int), ("boundary", C.c_int), ("min_piece", C.c_double),
@@ -170,7 +179,7 @@ _pI, _pL, _pD = C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_double)
 _PIN, _POUT, _BND, _RIN, _ROUT, _FLT = (C.POINTER(t) for t in (PairIn, PairOut, Boundary, RectifyIn, RectifyOut, FilterParams))
 _MLS, _VIEW, _PSN, _CLN, _COL, _STI = (C.POINTER(t) for t in (MlsParams, DedupView, PoissonParams, MeshCleanParams, MeshColorParams, MeshStitchParams))
 _TRM, _CLO, _DEC, _PDN = C.POINTER(MeshTrimParams), C.POINTER(MeshCloseParams), C.POINTER(MeshDecimateParams), C.POINTER(PoissonDensityParams)
-_SUB = C.POINTER(MeshSubdivideParams)
+_SUB, _PBD = C.POINTER(MeshSubdivideParams), C.POINTER(PoissonBandParams)
 PROTOTYPES = {
     "rsm_create": (_I, [_V, _I]),
     "rsm_destroy": (None, [_V]),
@@ -258,6 +267,11 @@ PROTOTYPES = {
     "rsm_poisson_mesh_weighted": (_I, [_V, _V, _V, _L, _PSN, _PDN, _pL, _pL, _V]),
     "rsm_poisson_mesh_weighted_device": (_I, [_V, _V, _V, _L, _PSN, _PDN, _pL, _pL, _V]),
     "rsm_stage_poisson_rhs_weighted": (_I, [_V, _V, _V, _L, _PSN, _PDN, _V, _V, _V, _V, _V, _V, _V, _V]),
+    "rsm_poisson_mesh_banded": (_I, [_V, _V, _V, _L, _PSN, _PBD, _pL, _pL, _V]),
+    "rsm_poisson_mesh_banded_device": (_I, [_V, _V, _V, _L, _PSN, _PBD, _pL, _pL, _V]),
+    "rsm_stage_poisson_band_rhs": (_I, [_V, _V, _V, _L, _PSN, _PBD, _V, _L, _L, _V, _V, _V, _V, _V, _V]),
+    "rsm_stage_poisson_band_solve": (_I, [_V, _V, _L, _I, _V, _V, _V, _D, _I, _V, _pD, _pI, _pD, _V]),
+    "rsm_stage_band_iso_mesh": (_I, [_V, _V, _L, _I, _V, _D, _V, _V, _I, _pL, _pL]),
     "rsm_write_ply_mesh": (_I, [_S, _V, _L, _V, _L]),
     "rsm_mesh_clean": (_I, [_V, _V, _L, _V, _L, _CLN, _pL, _pL, _V]),
     "rsm_mesh_clean_device": (_I, [_V, _V, _L, _V, _L, _CLN, _pL, _pL, _V]),

@@ -6,11 +6,13 @@ import numpy as np
 
 from . import _lib
 from ._context import ContextBase, _normals4, _p, _u8, _views
-from ._lib import MeshCleanParams, MeshCloseParams, MeshColorParams, MeshDecimateParams, MeshStitchParams, MeshSubdivideParams, MeshTrimParams, PoissonDensityParams, PoissonParams
+from ._lib import MeshCleanParams, MeshCloseParams, MeshColorParams, MeshDecimateParams, MeshStitchParams, MeshSubdivideParams, MeshTrimParams, PoissonBandParams, PoissonDensityParams, PoissonParams
 
 # the solve's default stopping residual: one decade above the 4.2e-6 the float32 solver reaches at depth 9
 POISSON_REL_RESIDUAL = 4e-5
 POISSON_MAX_CYCLES = 100
+# the band solve's iteration cap: four times the 41 to 50 iterations the sphere fixtures take to POISSON_REL_RESIDUAL
+POISSON_BAND_MAX_ITERATIONS = 200
 # meshlab.bat's script1 / script2 settings: the defaults of mesh_clean, mesh_clean_device and mesh_clean_last
 _MC = dict(smooth_steps=5, cotangent=True, boundary=True, min_piece=0.10, relative=True, duplicates=True, zero_area=True, nonmanifold=True)
 # mesh.bat's PoissonRecon --samplesPerNode 2 and SurfaceTrimmer --smooth 100 --trim 7 --aRatio 0.01: the defaults of mesh_trim, mesh_trim_device and mesh_trim_last
@@ -129,6 +131,98 @@ class MeshPart(ContextBase):
         self._chk(self._lib.rsm_stage_poisson_rhs_weighted(self._h, _p(xyz), _p(nrm), n, C.byref(prm), C.byref(dpr), None if din is None else _p(din), _p(grid),
                                                            _p(b), _p(occ), _p(counts), _p(rho), _p(w), _p(d)))
         return grid, b, occ, (int(counts[0]), int(counts[1])), rho[:n].copy(), w[:n].copy(), d[:n].copy()
+
+    # ---- one level finer on a band of bricks: script1.mlx's OctDepth 10 (csrc/k_poisson_band.hip) ----
+    def _poisson_banded(self, fn, xyz, nrm, n, depth, scale, trim_cells, rel_residual, max_cycles, band_bricks, max_iterations):
+        nv, nf = C.c_int64(), C.c_int64()
+        st = (C.c_double * _lib.POISSON_BAND_STATS)()
+        prm = PoissonParams(int(depth), float(scale), float(rel_residual), int(max_cycles), int(trim_cells))
+        bpr = PoissonBandParams(int(band_bricks), int(max_iterations))
+        status = fn(self._h, xyz, nrm, n, C.byref(prm), C.byref(bpr), C.byref(nv), C.byref(nf), st)
+        if status < 0:
+            self._chk(status)
+        stats = dict(n_valid=int(st[0]), n_invalid=int(st[1]), residual=float(st[2]), iterations=int(st[3]), iso=float(st[4]),
+                     origin=(float(st[5]), float(st[6]), float(st[7])), h=float(st[8]), N=int(st[9]), n_vertices_untrimmed=int(st[10]),
+                     n_faces_untrimmed=int(st[11]), active_bricks=int(st[12]), occupied_bricks=int(st[13]), coarse_cycles=int(st[14]),
+                     coarse_residual=float(st[15]), residual_before=float(st[16]), status=int(status), converged=status == 0)
+        return int(nv.value), int(nf.value), stats
+
+    def poisson_mesh_banded(self, xyz, normals, depth=10, scale=1.1, trim_cells=7, rel_residual=POISSON_REL_RESIDUAL, max_cycles=POISSON_MAX_CYCLES,
+                            band_bricks=1, max_iterations=POISSON_BAND_MAX_ITERATIONS):
+        """poisson_mesh one level finer than the dense grid reaches: depth (6..10) is the FINEST depth; the dense solve runs at depth - 1 and
+        the level of 2^depth nodes per axis exists only on the bricks (8^3 nodes) within band_bricks (1..4) of a brick that holds a sample,
+        where the field is corrected by at most max_iterations conjugate-gradient iterations.  trim_cells <= 8 band_bricks - 1 (script1.mlx
+        at depth 10 corresponds to trim_cells 8, which needs band_bricks 2); with trim_cells = 0 the mesh has borders where the band ends.
+        Returns (vertices, faces, stats dict); beyond poisson_mesh's keys (iterations for cycles) the stats hold active_bricks,
+        occupied_bricks, coarse_cycles, coarse_residual and residual_before (the band residual of the prolonged coarse field)."""
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        nrm = _normals4(normals, len(xyz))
+        nv, nf, stats = self._poisson_banded(self._lib.rsm_poisson_mesh_banded, _p(xyz), _p(nrm), len(xyz), depth, scale, trim_cells, rel_residual, max_cycles,
+                                             band_bricks, max_iterations)
+        return self.poisson_last_mesh(nv, nf) + (stats,)
+
+    def poisson_mesh_banded_device(self, xyz_ptr, normals_ptr, n, depth=10, scale=1.1, trim_cells=7, rel_residual=POISSON_REL_RESIDUAL,
+                                   max_cycles=POISSON_MAX_CYCLES, band_bricks=1, max_iterations=POISSON_BAND_MAX_ITERATIONS):
+        """rsm_poisson_mesh_banded_device on device buffers (addresses), as poisson_mesh_device: (n_vertices, n_faces, stats)."""
+        return self._poisson_banded(self._lib.rsm_poisson_mesh_banded_device, xyz_ptr, normals_ptr, n, depth, scale, trim_cells, rel_residual, max_cycles,
+                                    band_bricks, max_iterations)
+
+    def poisson_band_rhs(self, xyz, normals, depth, scale=1.1, band_bricks=1, chi_c=None, max_bricks=0, rel_residual=POISSON_REL_RESIDUAL,
+                         max_cycles=POISSON_MAX_CYCLES):
+        """Stage: samples -> dict grid (ox, oy, oz, h of the fine grid), bricks int32 [S] (ascending linear brick indices), b float64 [S,512],
+        occ uint8 [S,512], g float32 [S,512] (brick-major: element lx + 8 (ly + 8 lz)), counts (valid, invalid, active, occupied), status.
+        chi_c (float32 [N/2]^3 indexed [k,j,i]): the coarse field the guess is prolonged from; None: the dense solve at depth - 1."""
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        n = len(xyz)
+        nrm = _normals4(normals, n)
+        room = ((1 << int(depth)) >> 3) ** 3 if 6 <= int(depth) <= 10 else 1
+        room = min(room, _lib.POISSON_BAND_MAX_BRICKS if not max_bricks else int(max_bricks))
+        grid = np.zeros(4, np.float64)
+        bricks = np.zeros(max(room, 1), np.int32)
+        b = np.zeros((max(room, 1), 512), np.float64)
+        occ = np.zeros((max(room, 1), 512), np.uint8)
+        g = np.zeros((max(room, 1), 512), np.float32)
+        counts = np.zeros(4, np.int64)
+        cc = None if chi_c is None else np.ascontiguousarray(chi_c, np.float32)
+        assert cc is None or cc.shape == ((1 << int(depth)) >> 1,) * 3
+        prm = PoissonParams(int(depth), float(scale), float(rel_residual), int(max_cycles), 0)
+        bpr = PoissonBandParams(int(band_bricks), 1)
+        status = self._lib.rsm_stage_poisson_band_rhs(self._h, _p(xyz), _p(nrm), n, C.byref(prm), C.byref(bpr), None if cc is None else _p(cc), int(max_bricks),
+                                                      room, _p(grid), _p(bricks), _p(b), _p(occ), _p(g), _p(counts))
+        if status < 0:
+            self._chk(status)
+        S = int(counts[2])
+        return dict(grid=grid, bricks=bricks[:S].copy(), b=b[:S].copy(), occ=occ[:S].copy(), g=g[:S].copy(), counts=tuple(int(v) for v in counts), status=int(status))
+
+    def poisson_band_solve(self, bricks, depth, b, g, chi_c=None, rel_residual=POISSON_REL_RESIDUAL, max_iterations=POISSON_BAND_MAX_ITERATIONS):
+        """Stage: b and g (brick-major [S,512], rounded to float32) on the bricks -> (chi float32 [S,512], residual reached, iterations, status
+        0 / 1, residual per iteration, residual before the first).  chi_c (float32 [N/2]^3): gives the guess next to the band; None: 0 there."""
+        bricks = np.ascontiguousarray(bricks, np.int32).reshape(-1)
+        S = len(bricks)
+        b = np.ascontiguousarray(b, np.float32).reshape(S, 512)
+        g = np.ascontiguousarray(g, np.float32).reshape(S, 512)
+        cc = None if chi_c is None else np.ascontiguousarray(chi_c, np.float32)
+        assert cc is None or cc.shape == ((1 << int(depth)) >> 1,) * 3
+        chi = np.zeros((max(S, 1), 512), np.float32)
+        res, res0, its = C.c_double(), C.c_double(), C.c_int()
+        hist = np.zeros(max(1, int(max_iterations)), np.float64)
+        status = self._lib.rsm_stage_poisson_band_solve(self._h, _p(bricks), S, int(depth), _p(b), _p(g), None if cc is None else _p(cc), float(rel_residual),
+                                                        int(max_iterations), _p(chi), C.byref(res), C.byref(its), C.byref(res0), _p(hist))
+        if status < 0:
+            self._chk(status)
+        return chi[:S].copy(), float(res.value), int(its.value), int(status), hist[:int(its.value)].copy(), float(res0.value)
+
+    def band_iso_mesh(self, bricks, depth, chi, iso, grid, occ=None, trim_cells=0):
+        """Stage: a caller's chi (float32 [S,512], brick-major), iso, grid (ox, oy, oz, h) and occ (uint8 [S,512]) -> (vertices, faces)."""
+        bricks = np.ascontiguousarray(bricks, np.int32).reshape(-1)
+        S = len(bricks)
+        chi = np.ascontiguousarray(chi, np.float32).reshape(S, 512)
+        grid = np.ascontiguousarray(grid, np.float64).reshape(4)
+        o8 = None if occ is None else _u8(occ).reshape(S, 512)
+        nv, nf = C.c_int64(), C.c_int64()
+        self._chk(self._lib.rsm_stage_band_iso_mesh(self._h, _p(bricks), S, int(depth), _p(chi), float(iso), _p(grid), None if o8 is None else _p(o8),
+                                                    int(trim_cells), C.byref(nv), C.byref(nf)))
+        return self.poisson_last_mesh(int(nv.value), int(nf.value))
 
     def poisson_solve(self, b, rel_residual=POISSON_REL_RESIDUAL, max_cycles=POISSON_MAX_CYCLES):
         """Stage: b [N,N,N] (rounded to float32) -> (chi float32 [N,N,N], residual reached, cycles, status 0 / 1, residual per cycle)."""

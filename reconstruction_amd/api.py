@@ -21,7 +21,7 @@ from . import _lib
 from ._cloud import CloudPart
 from ._context import _Pinned, _bd, _p, _u8, host_empty  # noqa: F401
 from ._lib import Boundary, DedupView, FilterParams, MeshCleanParams, MeshColorParams, MlsParams, PoissonParams, NOMATCH, PairIn, PairOut, RectifyIn, RectifyOut, RsmError  # noqa: F401
-from ._mesh import POISSON_MAX_CYCLES, POISSON_REL_RESIDUAL, MeshPart
+from ._mesh import POISSON_BAND_MAX_ITERATIONS, POISSON_MAX_CYCLES, POISSON_REL_RESIDUAL, MeshPart
 from ._pair import PairPart, PairResult, match_pairs, match_pairs_multi_gpu, run_pairs  # noqa: F401
 from ._stages import StagesPart
 
@@ -317,16 +317,22 @@ class CloudOptimization:
         return self.cloud_ms_normals
 
     def mesh(self, depth=9, scale=1.1, trim_cells=4, rel_residual=POISSON_REL_RESIDUAL, max_cycles=POISSON_MAX_CYCLES, samples_per_node=None,
-             kernel_depth=0):
+             kernel_depth=0, band_bricks=None, band_max_iterations=POISSON_BAND_MAX_ITERATIONS):
         """Where CCloudOptimization::run hands bigcloud.ply to the Poisson mesher (after :389): the surface of cloud_ms_normals, run()'s
         result, by the dense-grid Poisson reconstruction and trim on the GPU (Context.poisson_mesh).  run() keeps its result on the
         host, so the host entry point is used.  samples_per_node (mesh.bat: 2, script1.mlx: 3) selects the density-adaptive splat
-        (Context.poisson_mesh_weighted; kernel_depth as there); None is the plain call.  Stores and returns (vertices float32 [nv,3],
+        (Context.poisson_mesh_weighted; kernel_depth as there); None is the plain call.  band_bricks (1..4) selects the banded call
+        (Context.poisson_mesh_banded; script1.mlx's OctDepth 10): depth is then the finest depth, 6..10, and trim_cells at most
+        8 band_bricks - 1; it does not combine with samples_per_node (ValueError).  Stores and returns (vertices float32 [nv,3],
         faces int32 [nf,3], stats)."""
         if getattr(self, "cloud_ms_normals", None) is None:
             raise ValueError("CloudOptimization.mesh: run() first (it meshes run()'s smoothed, oriented cloud)")
+        if band_bricks is not None and samples_per_node is not None:
+            raise ValueError("CloudOptimization.mesh: band_bricks and samples_per_node do not combine (the density-adaptive splat is not built on the band)")
         xyz, nrm = self.cloud_ms_normals[0], self.cloud_ms_normals[1]
-        if samples_per_node is None:
+        if band_bricks is not None:
+            self.mesh_result = self._ctx.poisson_mesh_banded(xyz, nrm, depth, scale, trim_cells, rel_residual, max_cycles, band_bricks, band_max_iterations)
+        elif samples_per_node is None:
             self.mesh_result = self._ctx.poisson_mesh(xyz, nrm, depth, scale, trim_cells, rel_residual, max_cycles)
         else:
             self.mesh_result = self._ctx.poisson_mesh_weighted(xyz, nrm, depth, scale, trim_cells, rel_residual, max_cycles, samples_per_node, kernel_depth)

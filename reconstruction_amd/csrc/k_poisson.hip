@@ -20,6 +20,7 @@
 #include "../../include/rsm.h"
 #include "rsm_dev.h"
 #include "mesh_common.h"
+#include "poisson_common.h"
 
 #include <string.h>
 
@@ -27,22 +28,9 @@
 
 #include <vector>
 
-#define PV_FIX 4294967296.0 // 2^32: the splat's fixed-point scale
 #define PV_RED_BLOCKS POISSON_SUM_PARTIALS // partial sums of a reduction (fixed: the summation tree depends on the size only)
 
 namespace {
-
-struct PvGrid {
-    double ox, oy, oz, h;
-    int sh, N; // N = 1 << sh
-};
-
-// the 16 cases of a tetrahedron (v0..v3, bit i of the case = v_i inside), for a positively oriented tetrahedron: faces as edges (u, v), u < v,
-// wound so that the normal points to the outside vertices; a negatively oriented tetrahedron swaps the last two corners of each face
-struct TetTable {
-    uint8_t ntri[16];
-    uint8_t e[16][2][3]; // edge code u << 2 | v
-};
 
 // ---- 1: valid samples and their bounding box: mm[0..2] = min, mm[3..5] = max (ordered uints), cnt[0] = valid ------------------
 template <bool HAS_N>
@@ -258,17 +246,6 @@ __global__ __launch_bounds__(256) void k_pv_iso(const float *__restrict__ xyz, c
 }
 
 // ---- 7: marching tetrahedra ---------------------------------------------------------------------------------------------------------
-// direction codes of a lattice edge (a, b = a + d): 100, 010, 001, 110, 101, 011, 111 (x, y, z)
-__device__ __constant__ int8_t c_dir[7][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}, {1, 1, 0}, {1, 0, 1}, {0, 1, 1}, {1, 1, 1}};
-__device__ __forceinline__ int pv_dir_code(int dx, int dy, int dz) { // offsets in {0, 1}, not all 0
-    const int m = dx | (dy << 1) | (dz << 2); // 1..7
-    // m: 1 -> 0 (100), 2 -> 1 (010), 4 -> 2 (001), 3 -> 3 (110), 5 -> 4 (101), 6 -> 5 (011), 7 -> 6
-    return (0x6542310 >> (4 * (m - 1))) & 7;
-}
-// the axis permutations (a, b, c) in lexicographic order; tetrahedron = 000, +a, +a+b, 111; its orientation is the permutation's sign
-__device__ __constant__ int8_t c_perm[6][3] = {{0, 1, 2}, {0, 2, 1}, {1, 0, 2}, {1, 2, 0}, {2, 0, 1}, {2, 1, 0}};
-__device__ __constant__ int8_t c_perm_sign[6] = {1, -1, -1, 1, 1, -1};
-
 // flag[8 a + d] = the edge (a, d) crosses the surface; the 8th byte of a node stays 0 (one 8-byte store per node)
 __global__ __launch_bounds__(256) void k_pv_edge_flags(const float *__restrict__ chi, float iso, int sh, unsigned long long *__restrict__ flag8) {
     const int N = 1 << sh;
@@ -393,54 +370,8 @@ __global__ __launch_bounds__(256) void k_pv_dilate(const uint8_t *__restrict__ i
     for (int q = lo; q <= hi && !m; q++) m = in[a + (size_t)(q - c) * st] ? 1 : 0; // (q - c may be negative: size_t wraps back, a + ... stays in range)
     out[a] = m;
 }
-__global__ __launch_bounds__(256) void k_pv_face_keep(const int32_t *__restrict__ faces, size_t nf, const uint8_t *__restrict__ vkeep,
-                                                      unsigned int *__restrict__ fkeep, unsigned int *__restrict__ vused) {
-    const size_t f = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (f >= nf) return;
-    const int32_t a = faces[3 * f], b = faces[3 * f + 1], c = faces[3 * f + 2];
-    const unsigned int keep = (vkeep[a] && vkeep[b] && vkeep[c] && a != b && b != c && a != c) ? 1u : 0u;
-    fkeep[f] = keep;
-    if (keep) vused[a] = vused[b] = vused[c] = 1u; // (every writer stores the same value)
-}
-
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
 static inline unsigned red_blocks(size_t n) { return (unsigned)std::min<size_t>(PV_RED_BLOCKS, (n + 255) / 256); }
-
-static TetTable make_tet_table() {
-    TetTable T;
-    memset(&T, 0, sizeof T);
-    auto edge = [](int u, int v) { return (uint8_t)(u < v ? (u << 2 | v) : (v << 2 | u)); };
-    for (int m = 1; m < 15; m++) {
-        int in[4], ni = 0, out[4], no = 0;
-        for (int v = 0; v < 4; v++) {
-            if ((m >> v) & 1) in[ni++] = v;
-            else out[no++] = v;
-        }
-        if (ni == 1 || ni == 3) {
-            const int L = ni == 1 ? in[0] : out[0];
-            const int *o = ni == 1 ? out : in; // the three others, ascending
-            // (L, A, B, C) is an even permutation of (0, 1, 2, 3) iff L is even: the face (LA, LB, LC) then looks away from L
-            const bool away = (L & 1) == 0;
-            const bool want_away = ni == 1; // L inside: the outside is away from it
-            T.ntri[m] = 1;
-            T.e[m][0][0] = edge(L, o[0]);
-            T.e[m][0][1] = edge(L, away == want_away ? o[1] : o[2]);
-            T.e[m][0][2] = edge(L, away == want_away ? o[2] : o[1]);
-        } else {
-            const int P = in[0], Q = in[1], R = out[0], S = out[1];
-            const int perm[4] = {P, Q, R, S};
-            int inv = 0;
-            for (int a = 0; a < 4; a++)
-                for (int b = a + 1; b < 4; b++) inv += perm[a] > perm[b];
-            const bool even = (inv & 1) == 0; // (P, Q, R, S) positively oriented: the quad PR, PS, QS, QR looks toward R, S
-            const uint8_t pr = edge(P, R), ps = edge(P, S), qs = edge(Q, S), qr = edge(Q, R);
-            T.ntri[m] = 2;
-            T.e[m][0][0] = pr; T.e[m][0][1] = even ? ps : qs; T.e[m][0][2] = even ? qs : ps;
-            T.e[m][1][0] = pr; T.e[m][1][1] = even ? qs : qr; T.e[m][1][2] = even ? qr : qs;
-        }
-    }
-    return T;
-}
 
 } // namespace
 
@@ -640,6 +571,44 @@ int poisson_iso_device(const float *d_xyz, const float *d_nrm4, int64_t n, int64
     return RSM_OK;
 }
 
+// step 8's second half, for the dense extraction and the banded one (k_poisson_band.hip): of `full` (its vertices flagged by vkeep) the faces whose
+// three vertices are kept, the vertices they use, both renumbered in order -> *out; `full` is freed
+int poisson_trim_commit(DevMem &M, PoissonMesh &full, const uint8_t *vkeep, PoissonMesh *out, hipStream_t st) {
+    const uint64_t nv = (uint64_t)full.nv, nf = (uint64_t)full.nf;
+    float *verts = full.d_v;
+    int32_t *faces = full.d_f;
+    int s;
+    // trim: faces whose three vertices lie in the dilated occupancy, the vertices they use, both renumbered in order
+    unsigned int *fkeep = M.get<unsigned int>(nf), *fpos = M.get<unsigned int>(nf), *vused = M.get<unsigned int>(nv), *vpos = M.get<unsigned int>(nv);
+    s = M.ok ? RSM_OK : RSM_E_NOMEM;
+    uint64_t kf = 0, kv = 0;
+    if (s == RSM_OK && hipMemsetAsync(vused, 0, nv * sizeof(unsigned int), st) != hipSuccess) s = RSM_E_HIP;
+    if (s == RSM_OK) {
+        hipLaunchKernelGGL(k_pv_face_keep<>, blocks_for(nf), dim3(256), 0, st, (const int32_t *)faces, (size_t)nf, (const uint8_t *)vkeep, fkeep, vused);
+        s = scan_u32(M, (const unsigned int *)fkeep, fpos, nf, st);
+    }
+    if (s == RSM_OK) s = scan_u32(M, (const unsigned int *)vused, vpos, nv, st);
+    if (s == RSM_OK) s = scan_total(fkeep, fpos, nf, st, &kf);
+    if (s == RSM_OK) s = scan_total(vused, vpos, nv, st, &kv);
+    if (s == RSM_OK && kf > 0) {
+        PoissonMesh kept;
+        if ((s = mesh_result_alloc(kept, kv, kf)) == RSM_OK) {
+            hipLaunchKernelGGL(k_mesh_compact_faces<>, blocks_for(nf), dim3(256), 0, st, (const int32_t *)faces, (size_t)nf, (const unsigned int *)fkeep,
+                               (const unsigned int *)fpos, (const unsigned int *)vpos, kept.d_f);
+            hipLaunchKernelGGL(k_mesh_compact_verts<>, blocks_for(nv), dim3(256), 0, st, (const float *)verts, (size_t)nv, (const unsigned int *)vused,
+                               (const unsigned int *)vpos, kept.d_v);
+            if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) {
+                poisson_mesh_free(&kept);
+                s = RSM_E_HIP;
+            } else
+                mesh_result_commit(out, kept);
+        }
+    }
+    if (hipStreamSynchronize(st) != hipSuccess && s == RSM_OK) s = RSM_E_HIP;
+    poisson_mesh_free(&full);
+    return s;
+}
+
 int poisson_extract_device(const float *d_chi, int depth, double iso, const double grid[4], const uint8_t *d_occ, int trim_cells,
                            PoissonMesh *out, int64_t untrimmed[2], hipStream_t st) {
     poisson_mesh_free(out);
@@ -706,33 +675,5 @@ int poisson_extract_device(const float *d_chi, int depth, double iso, const doub
         *out = full;
         return RSM_OK;
     }
-    // trim: faces whose three vertices lie in the dilated occupancy, the vertices they use, both renumbered in order
-    unsigned int *fkeep = M.get<unsigned int>(nf), *fpos = M.get<unsigned int>(nf), *vused = M.get<unsigned int>(nv), *vpos = M.get<unsigned int>(nv);
-    s = M.ok ? RSM_OK : RSM_E_NOMEM;
-    uint64_t kf = 0, kv = 0;
-    if (s == RSM_OK && hipMemsetAsync(vused, 0, nv * sizeof(unsigned int), st) != hipSuccess) s = RSM_E_HIP;
-    if (s == RSM_OK) {
-        hipLaunchKernelGGL(k_pv_face_keep, blocks_for(nf), dim3(256), 0, st, (const int32_t *)faces, (size_t)nf, (const uint8_t *)vkeep, fkeep, vused);
-        s = scan_u32(M, (const unsigned int *)fkeep, fpos, nf, st);
-    }
-    if (s == RSM_OK) s = scan_u32(M, (const unsigned int *)vused, vpos, nv, st);
-    if (s == RSM_OK) s = scan_total(fkeep, fpos, nf, st, &kf);
-    if (s == RSM_OK) s = scan_total(vused, vpos, nv, st, &kv);
-    if (s == RSM_OK && kf > 0) {
-        PoissonMesh kept;
-        if ((s = mesh_result_alloc(kept, kv, kf)) == RSM_OK) {
-            hipLaunchKernelGGL(k_mesh_compact_faces<>, blocks_for(nf), dim3(256), 0, st, (const int32_t *)faces, (size_t)nf, (const unsigned int *)fkeep,
-                               (const unsigned int *)fpos, (const unsigned int *)vpos, kept.d_f);
-            hipLaunchKernelGGL(k_mesh_compact_verts<>, blocks_for(nv), dim3(256), 0, st, (const float *)verts, (size_t)nv, (const unsigned int *)vused,
-                               (const unsigned int *)vpos, kept.d_v);
-            if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) {
-                poisson_mesh_free(&kept);
-                s = RSM_E_HIP;
-            } else
-                mesh_result_commit(out, kept);
-        }
-    }
-    if (hipStreamSynchronize(st) != hipSuccess && s == RSM_OK) s = RSM_E_HIP;
-    poisson_mesh_free(&full);
-    return s;
+    return poisson_trim_commit(M, full, vkeep, out, st);
 }

@@ -1,0 +1,685 @@
+// k_poisson_band.hip -- the Poisson surface one level finer than the dense grid reaches (script1.mlx's OctDepth 10): a finest
+// level of N = 2^depth nodes per axis that exists only near the samples, on top of k_poisson.hip's dense solve at depth - 1.  The fine grid
+// is cut into bricks of 8^3 nodes; a brick is occupied when a sample's cell lies in it and active within band_bricks (Chebyshev) of an
+// occupied one.  The active bricks are listed in ascending linear index, a brick's slot is its place in the list, a dense B^3 table maps
+// brick -> slot (-1: inactive), and every field lives brick-major: element slot * 512 + lx + 8 (ly + 8 lz).  The steps (restated in numpy in
+// tests/poisson_band_restatement.py):
+//   bricks   occupied -> dilated -> scan -> slot table, list, the 27 neighbour slots of every slot     k_pb_mark .. k_pb_nbr
+//   splat    f7's fixed-point splat and occ on the active nodes, b = 1/2 central differences           k_pb_splat, k_pb_rhs
+//   guess    g = (float)(1/4 trilinear prolongation of the coarse chi), fp64, corner order dz, dy, dx  k_pb_guess
+//   solve    L chi = b on the active nodes, chi = g on the inactive ones, 0 outside the grid: float32 conjugate gradients from chi = g,
+//            preconditioned by one symmetric red-black Gauss-Seidel sweep from zero on the band        k_pb_rbgs, k_pb_stencil
+//   iso      f7's mean of chi at the samples in f7's summation tree                                    k_pb_chi_at_samples
+//   mesh     f7's marching tetrahedra on the cells whose eight corners are active: flags -> scan -> emit, then f7's trim with the occupancy
+//            dilated inside the band                                                                   k_pb_edge_flags .. k_pb_dilate_cells
+// One workgroup per brick in the solver: a 10^3 tile of the field in LDS, filled through the slot's neighbour table.  Every reduction has a fixed
+// shape: an LDS tree over a brick's 512 products, the per-slot partials through f7's tree (poisson_tree_sum).  No float atomics.
+#include "../../include/rsm.h"
+#include "rsm_dev.h"
+#include "mesh_common.h"
+#include "poisson_common.h"
+
+#include <math.h>
+
+#define PB_NODES 512 // nodes of a brick
+// the band solve ends after this many iterations in a row without a new best residual (twice the longest such run of the
+// restatement's float32 histories before their floor)
+#define PB_STALL 20
+
+namespace {
+
+struct PbBand { // what a kernel needs of a PoissonBand
+    const int32_t *slot, *active, *nbr;
+    int sh, bsh, N; // N = 1 << sh nodes, 1 << bsh bricks per axis
+};
+
+// the slot of the brick that holds node (i, j, k): -1 inactive, -2 outside the grid
+__device__ __forceinline__ int pb_slot_of(const PbBand &B, int i, int j, int k) {
+    if ((unsigned)i >= (unsigned)B.N || (unsigned)j >= (unsigned)B.N || (unsigned)k >= (unsigned)B.N) return -2;
+    return B.slot[(size_t)(i >> 3) + (((size_t)(j >> 3) + ((size_t)(k >> 3) << B.bsh)) << B.bsh)];
+}
+__device__ __forceinline__ int pb_local(int i, int j, int k) { return (i & 7) + 8 * ((j & 7) + 8 * (k & 7)); }
+// ... and the node's element, or the negative slot
+__device__ __forceinline__ long long pb_elem_of(const PbBand &B, int i, int j, int k) {
+    const int s = pb_slot_of(B, i, j, k);
+    return s < 0 ? (long long)s : (long long)s * PB_NODES + pb_local(i, j, k);
+}
+// from a slot's 27 neighbour slots nb[(cx + 1) + 3 ((cy + 1) + 3 (cz + 1))]: the element of its node at local (x, y, z), each in -1 .. 8
+__device__ __forceinline__ long long pb_node(const int32_t *nb, int x, int y, int z) {
+    const int s = nb[((x >> 3) + 1) + 3 * (((y >> 3) + 1) + 3 * ((z >> 3) + 1))];
+    return s < 0 ? (long long)s : (long long)s * PB_NODES + pb_local(x, y, z);
+}
+// the grid coordinates of a slot's node 0
+__device__ __forceinline__ void pb_origin(const PbBand &B, int slot, int o[3]) {
+    const int b = B.active[slot], m = (1 << B.bsh) - 1;
+    o[0] = (b & m) << 3;
+    o[1] = ((b >> B.bsh) & m) << 3;
+    o[2] = (b >> (2 * B.bsh)) << 3;
+}
+
+// ---- bricks ---------------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_pb_mark(const float *__restrict__ xyz, const float *__restrict__ nrm, int64_t n, PvGrid g, int bsh,
+                                                 uint8_t *__restrict__ occb) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n) return;
+    double p[3], nh[3];
+    if (!pv_valid(xyz, nrm, s, p, nh)) return;
+    const double o[3] = {g.ox, g.oy, g.oz};
+    int c[3];
+    for (int a = 0; a < 3; a++) {
+        const int cc = (int)floor((p[a] - o[a]) / g.h);
+        c[a] = (cc < 0 ? 0 : (cc > g.N - 1 ? g.N - 1 : cc)) >> 3;
+    }
+    occb[(size_t)c[0] + (((size_t)c[1] + ((size_t)c[2] << bsh)) << bsh)] = 1;
+}
+// one axis of the Chebyshev dilation over the B^3 bricks
+__global__ __launch_bounds__(256) void k_pb_dilate_bricks(const uint8_t *__restrict__ in, uint8_t *__restrict__ out, int bsh, int axis, int r) {
+    const int B = 1 << bsh;
+    const size_t B3 = (size_t)1 << (3 * bsh);
+    const size_t a = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (a >= B3) return;
+    const int c = (int)((a >> (axis * bsh)) & (B - 1));
+    const long long st = (long long)1 << (axis * bsh);
+    const int lo = c - r < 0 ? 0 : c - r, hi = c + r > B - 1 ? B - 1 : c + r;
+    uint8_t m = 0;
+    for (int q = lo; q <= hi && !m; q++) m = in[(long long)a + (q - c) * st] ? 1 : 0;
+    out[a] = m;
+}
+struct PbU8ToU32 {
+    __host__ __device__ unsigned int operator()(uint8_t v) const { return v ? 1u : 0u; }
+};
+__global__ __launch_bounds__(256) void k_pb_slots(const uint8_t *__restrict__ act, const unsigned int *__restrict__ pos, size_t B3, int32_t *__restrict__ slot,
+                                                  int32_t *__restrict__ active) {
+    const size_t b = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (b >= B3) return;
+    slot[b] = act[b] ? (int32_t)pos[b] : -1;
+    if (act[b] && active) active[pos[b]] = (int32_t)b;
+}
+// the slot table from a caller's list
+__global__ __launch_bounds__(256) void k_pb_slots_of_list(const int32_t *__restrict__ active, int S, int32_t *__restrict__ slot) {
+    const int s = blockIdx.x * 256 + threadIdx.x;
+    if (s < S) slot[active[s]] = s;
+}
+__global__ __launch_bounds__(256) void k_pb_nbr(const int32_t *__restrict__ active, int S, const int32_t *__restrict__ slot, int bsh, int32_t *__restrict__ nbr) {
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (size_t)S * 27) return;
+    const int s = (int)(t / 27), code = (int)(t % 27);
+    const int B = 1 << bsh, b = active[s];
+    const int x = (b & (B - 1)) + code % 3 - 1, y = ((b >> bsh) & (B - 1)) + (code / 3) % 3 - 1, z = (b >> (2 * bsh)) + code / 9 - 1;
+    nbr[t] = (x < 0 || y < 0 || z < 0 || x >= B || y >= B || z >= B) ? -2 : slot[(size_t)x + (((size_t)y + ((size_t)z << bsh)) << bsh)];
+}
+
+// ---- splat and right-hand side (f7's steps 3 and 4 on the active nodes) ----------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_pb_splat(const float *__restrict__ xyz, const float *__restrict__ nrm, int64_t n, PvGrid g, PbBand B,
+                                                  unsigned long long *__restrict__ V /* [3][S 512] */, size_t nodes, uint8_t *__restrict__ occ) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n) return;
+    double p[3], nh[3];
+    if (!pv_valid(xyz, nrm, s, p, nh)) return;
+    const double o[3] = {g.ox, g.oy, g.oz};
+    const int N = g.N;
+    int i0[3], c[3];
+    double f[3];
+    for (int a = 0; a < 3; a++) {
+        const double u = (p[a] - o[a]) / g.h;
+        const double gq = u - 0.5;
+        const double fl = floor(gq);
+        i0[a] = (int)fl;
+        f[a] = gq - fl;
+        int cc = (int)floor(u);
+        c[a] = cc < 0 ? 0 : (cc > N - 1 ? N - 1 : cc);
+    }
+    const long long ce = pb_elem_of(B, c[0], c[1], c[2]);
+    if (ce >= 0) occ[ce] = 1; // (the cell's brick is occupied, so active)
+    for (int dz = 0; dz < 2; dz++)
+        for (int dy = 0; dy < 2; dy++)
+            for (int dx = 0; dx < 2; dx++) {
+                const long long node = pb_elem_of(B, i0[0] + dx, i0[1] + dy, i0[2] + dz);
+                if (node < 0) continue; // outside the grid; (inactive cannot happen with band_bricks >= 1)
+                const double w = ((dx ? f[0] : 1.0 - f[0]) * (dy ? f[1] : 1.0 - f[1])) * (dz ? f[2] : 1.0 - f[2]);
+                for (int a = 0; a < 3; a++) {
+                    const long long q = __double2ll_rn((w * nh[a]) * PV_FIX);
+                    if (q) atomicAdd(&V[a * nodes + (size_t)node], (unsigned long long)q);
+                }
+            }
+}
+__device__ __forceinline__ long long pb_v(const long long *__restrict__ V, long long e) { return e < 0 ? 0 : V[e]; }
+__global__ __launch_bounds__(256) void k_pb_rhs(const long long *__restrict__ V, size_t nodes, const int32_t *__restrict__ nbr, float *__restrict__ b32,
+                                                double *__restrict__ b64) {
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= nodes) return;
+    const int32_t *nb = nbr + (t >> 9) * 27;
+    const int l = (int)(t & 511), x = l & 7, y = (l >> 3) & 7, z = l >> 6;
+    const long long *Vx = V, *Vy = V + nodes, *Vz = V + 2 * nodes;
+    const long long dx = pb_v(Vx, pb_node(nb, x + 1, y, z)) - pb_v(Vx, pb_node(nb, x - 1, y, z));
+    const long long dy = pb_v(Vy, pb_node(nb, x, y + 1, z)) - pb_v(Vy, pb_node(nb, x, y - 1, z));
+    const long long dz = pb_v(Vz, pb_node(nb, x, y, z + 1)) - pb_v(Vz, pb_node(nb, x, y, z - 1));
+    const double b = (0.5 * (((double)dx + (double)dy) + (double)dz)) / PV_FIX;
+    if (b32) b32[t] = (float)b;
+    if (b64) b64[t] = b;
+}
+
+// ---- guess: a quarter of the cell-centred trilinear prolongation of the coarse field (chi_c = 0 outside its grid) -------------------------------
+__device__ __forceinline__ float pb_guess(const float *__restrict__ chic, int shc, int i, int j, int k) {
+    const int Nc = 1 << shc, c[3] = {i, j, k};
+    int i0[3];
+    double f[3];
+    for (int a = 0; a < 3; a++) {
+        i0[a] = (c[a] - 1) >> 1; // the lower of the two coarse nodes: the parent of an odd fine node, the parent's lower neighbour of an even one
+        f[a] = (c[a] & 1) ? 0.25 : 0.75;
+    }
+    double acc = 0.0;
+    for (int dz = 0; dz < 2; dz++)
+        for (int dy = 0; dy < 2; dy++)
+            for (int dx = 0; dx < 2; dx++) {
+                const int x = i0[0] + dx, y = i0[1] + dy, z = i0[2] + dz;
+                if (x < 0 || y < 0 || z < 0 || x >= Nc || y >= Nc || z >= Nc) continue;
+                const double w = ((dx ? f[0] : 1.0 - f[0]) * (dy ? f[1] : 1.0 - f[1])) * (dz ? f[2] : 1.0 - f[2]);
+                acc += w * (double)chic[(size_t)x + (((size_t)y + ((size_t)z << shc)) << shc)];
+            }
+    return (float)(0.25 * acc);
+}
+__global__ __launch_bounds__(256) void k_pb_guess(const float *__restrict__ chic, PbBand B, size_t nodes, float *__restrict__ g) {
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (t >= nodes) return;
+    int o[3];
+    pb_origin(B, (int)(t >> 9), o);
+    const int l = (int)(t & 511);
+    g[t] = pb_guess(chic, B.sh - 1, o[0] + (l & 7), o[1] + ((l >> 3) & 7), o[2] + (l >> 6));
+}
+
+// ---- the band solve: one workgroup of 256 threads per brick ----------------------------------------------------------------------------------
+// the sum of a brick's 512 products (thread t gives those of nodes t and t + 256) by a fixed LDS tree -> *dst
+__device__ __forceinline__ void pb_brick_sum_to(double a, double b, double *dst) {
+    __shared__ double s[PB_NODES];
+    s[threadIdx.x] = a;
+    s[threadIdx.x + 256] = b;
+    __syncthreads();
+    for (int w = 256; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) s[threadIdx.x] += s[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *dst = s[0];
+}
+// the 10^3 tile of x around the brick of `slot`: tile[(x + 1) + 10 ((y + 1) + 10 (z + 1))].  GUESS: an inactive node inside the grid holds the guess
+// there (chi = g + e with e = 0; no coarse field: 0); otherwise, and outside the grid, 0
+template <bool GUESS>
+__device__ __forceinline__ void pb_fill_tile(float *tile, int32_t *nb, const float *__restrict__ x, const PbBand &B, int slot, const float *__restrict__ chic) {
+    if (threadIdx.x < 27) nb[threadIdx.x] = B.nbr[(size_t)slot * 27 + threadIdx.x];
+    __syncthreads();
+    int o[3] = {0, 0, 0};
+    if (GUESS) pb_origin(B, slot, o);
+    for (int t = threadIdx.x; t < 1000; t += 256) {
+        const int lx = t % 10 - 1, ly = (t / 10) % 10 - 1, lz = t / 100 - 1;
+        const long long e = pb_node(nb, lx, ly, lz);
+        float v = 0.0f;
+        if (e >= 0) v = x[e];
+        else if (GUESS && e == -1 && chic) v = pb_guess(chic, B.sh - 1, o[0] + lx, o[1] + ly, o[2] + lz);
+        tile[t] = v;
+    }
+    __syncthreads();
+}
+__device__ __forceinline__ float pb_tile_nbr_sum(const float *tile, int c) { // c = the node's place in the tile; f7's order of additions
+    return ((tile[c - 1] + tile[c + 1]) + (tile[c - 10] + tile[c + 10])) + (tile[c - 100] + tile[c + 100]);
+}
+// MODE 0: out = L x (x = 0 off the band), partials of x . out;  1: out = b - L x (x = the guess off the band), partials of out^2
+template <int MODE>
+__global__ __launch_bounds__(256) void k_pb_stencil(const float *__restrict__ x, const float *__restrict__ b, float *__restrict__ out, PbBand B,
+                                                    const float *__restrict__ chic, double *__restrict__ part) {
+    __shared__ float tile[1000];
+    __shared__ int32_t nb[27];
+    const int slot = blockIdx.x;
+    pb_fill_tile<MODE == 1>(tile, nb, x, B, slot, chic);
+    double acc[2];
+    for (int h = 0; h < 2; h++) {
+        const int l = threadIdx.x + 256 * h;
+        const int c = ((l & 7) + 1) + 10 * ((((l >> 3) & 7) + 1) + 10 * ((l >> 6) + 1));
+        const size_t e = (size_t)slot * PB_NODES + l;
+        const float v = tile[c];
+        const float lx = pb_tile_nbr_sum(tile, c) - 6.0f * v;
+        if (MODE == 0) {
+            out[e] = lx;
+            acc[h] = (double)v * (double)lx;
+        } else {
+            const float r = b[e] - lx;
+            out[e] = r;
+            acc[h] = (double)r * (double)r;
+        }
+    }
+    pb_brick_sum_to(acc[0], acc[1], &part[slot]);
+}
+// one colour of a red-black Gauss-Seidel sweep on the band (x = 0 off it): x = (sum of neighbours - b) / 6 where (i + j + k) & 1 == colour (a
+// brick's origin is even, so the local parity is the global one).  FIRST: the sweep's first pass from x = 0, which also writes the zeros of
+// the other colour.  part (optional): partials of b . x after the pass
+template <bool FIRST>
+__global__ __launch_bounds__(256) void k_pb_rbgs(float *__restrict__ x, const float *__restrict__ b, PbBand B, int colour, double *__restrict__ part) {
+    __shared__ float tile[1000];
+    __shared__ int32_t nb[27];
+    const int slot = blockIdx.x;
+    if (!FIRST) pb_fill_tile<false>(tile, nb, x, B, slot, nullptr);
+    const int ly = (threadIdx.x >> 2) & 7, lz = threadIdx.x >> 5;
+    const int lx = 2 * (threadIdx.x & 3) + ((ly + lz + colour) & 1);
+    const int l = lx + 8 * (ly + 8 * lz), lo = l ^ 1; // lo: the node of the other colour beside it
+    const size_t e = (size_t)slot * PB_NODES + l, eo = (size_t)slot * PB_NODES + lo;
+    const int c = (lx + 1) + 10 * ((ly + 1) + 10 * (lz + 1));
+    const float sum = FIRST ? ((0.0f + 0.0f) + (0.0f + 0.0f)) + (0.0f + 0.0f) : pb_tile_nbr_sum(tile, c);
+    const float be = b[e];
+    const float v = (sum - be) / 6.0f;
+    x[e] = v;
+    if (FIRST) x[eo] = 0.0f;
+    if (part) {
+        const float vo = FIRST ? 0.0f : tile[c + (lo - l)];
+        pb_brick_sum_to((double)be * (double)v, (double)b[eo] * (double)vo, &part[slot]);
+    }
+}
+__global__ __launch_bounds__(256) void k_pb_dot(const float *__restrict__ x, const float *__restrict__ y, double *__restrict__ part) {
+    const size_t e = (size_t)blockIdx.x * PB_NODES + threadIdx.x;
+    pb_brick_sum_to((double)x[e] * (double)y[e], (double)x[e + 256] * (double)y[e + 256], &part[blockIdx.x]);
+}
+__global__ __launch_bounds__(256) void k_pb_axpy(float *__restrict__ y, const float *__restrict__ x, float a, size_t n) { // y += a x
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (t < n) y[t] = y[t] + a * x[t];
+}
+__global__ __launch_bounds__(256) void k_pb_xpay(float *__restrict__ y, const float *__restrict__ x, float a, size_t n) { // y = x + a y
+    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (t < n) y[t] = x[t] + a * y[t];
+}
+
+// ---- iso: chi at the samples (0 for those that take no part) ----------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_pb_chi_at_samples(const float *__restrict__ xyz, const float *__restrict__ nrm, int64_t n, PvGrid g, PbBand B,
+                                                           const float *__restrict__ chi, double *__restrict__ val) {
+    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= n) return;
+    double p[3], nh[3], acc = 0.0;
+    if (pv_valid(xyz, nrm, s, p, nh)) {
+        const double o[3] = {g.ox, g.oy, g.oz};
+        int i0[3];
+        double f[3];
+        for (int a = 0; a < 3; a++) {
+            const double gq = (p[a] - o[a]) / g.h - 0.5;
+            const double fl = floor(gq);
+            i0[a] = (int)fl;
+            f[a] = gq - fl;
+        }
+        for (int dz = 0; dz < 2; dz++)
+            for (int dy = 0; dy < 2; dy++)
+                for (int dx = 0; dx < 2; dx++) {
+                    const long long e = pb_elem_of(B, i0[0] + dx, i0[1] + dy, i0[2] + dz);
+                    if (e < 0) continue;
+                    const double w = ((dx ? f[0] : 1.0 - f[0]) * (dy ? f[1] : 1.0 - f[1])) * (dz ? f[2] : 1.0 - f[2]);
+                    acc += w * (double)chi[e];
+                }
+    }
+    val[s] = acc;
+}
+
+// ---- extraction: f7's marching tetrahedra over the band ----------------------------------------------------------------------------------------
+// flag8[a]: byte d = the edge (a, d) has both ends active and crosses the surface; cnt[a] = how many of them
+__global__ __launch_bounds__(256) void k_pb_edge_flags(const float *__restrict__ chi, float iso, const int32_t *__restrict__ nbr, size_t nodes,
+                                                       unsigned long long *__restrict__ flag8, unsigned int *__restrict__ cnt) {
+    const size_t a = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (a >= nodes) return;
+    const int32_t *nb = nbr + (a >> 9) * 27;
+    const int l = (int)(a & 511), x = l & 7, y = (l >> 3) & 7, z = l >> 6;
+    const bool ia = chi[a] < iso;
+    unsigned long long w = 0;
+    unsigned int m = 0;
+    for (int d = 0; d < 7; d++) {
+        const long long e = pb_node(nb, x + c_dir[d][0], y + c_dir[d][1], z + c_dir[d][2]);
+        if (e < 0) continue;
+        if (ia != (chi[e] < iso)) {
+            w |= 1ull << (8 * d);
+            m++;
+        }
+    }
+    flag8[a] = w;
+    cnt[a] = m;
+}
+// the vertex of edge (a, d): a's first vertex plus the flagged directions below d
+__device__ __forceinline__ unsigned int pb_vertex(const unsigned long long *__restrict__ flag8, const unsigned int *__restrict__ vpos, size_t a, int d) {
+    return vpos[a] + (unsigned int)__popcll(flag8[a] & ((1ull << (8 * d)) - 1ull));
+}
+__global__ __launch_bounds__(256) void k_pb_emit_vertices(const float *__restrict__ chi, float iso, PvGrid g, PbBand B, size_t nodes,
+                                                          const unsigned long long *__restrict__ flag8, const unsigned int *__restrict__ vpos,
+                                                          float *__restrict__ verts, const uint8_t *__restrict__ mask, uint8_t *__restrict__ vkeep) {
+    const size_t a = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (a >= nodes) return;
+    const unsigned long long w = flag8[a];
+    if (w == 0) return;
+    const int32_t *nb = B.nbr + (a >> 9) * 27;
+    int org[3];
+    pb_origin(B, (int)(a >> 9), org);
+    const int l = (int)(a & 511), lc[3] = {l & 7, (l >> 3) & 7, l >> 6};
+    const int ijk[3] = {org[0] + lc[0], org[1] + lc[1], org[2] + lc[2]};
+    const double o[3] = {g.ox, g.oy, g.oz};
+    const float ca = chi[a];
+    size_t v = vpos[a];
+    for (int d = 0; d < 7; d++) {
+        if (!((w >> (8 * d)) & 1)) continue;
+        const float cb = chi[pb_node(nb, lc[0] + c_dir[d][0], lc[1] + c_dir[d][1], lc[2] + c_dir[d][2])];
+        const float t = (iso - ca) / (cb - ca);
+        int cell[3];
+        for (int c = 0; c < 3; c++) {
+            const float pa = (float)(o[c] + ((double)ijk[c] + 0.5) * g.h);
+            const float pb = (float)(o[c] + ((double)(ijk[c] + c_dir[d][c]) + 0.5) * g.h);
+            const float p = pa + t * (pb - pa);
+            verts[3 * v + c] = p;
+            const int q = (int)floor(((double)p - o[c]) / g.h);
+            cell[c] = q < 0 ? 0 : (q > g.N - 1 ? g.N - 1 : q);
+        }
+        if (vkeep) {
+            const long long e = pb_elem_of(B, cell[0], cell[1], cell[2]);
+            vkeep[v] = e < 0 ? 0 : mask[e];
+        }
+        v++;
+    }
+}
+// faces of a cell whose eight corners are active (its 000 node is `a`): EMIT = false counts them, true writes them at foff[a]
+template <bool EMIT>
+__global__ __launch_bounds__(256) void k_pb_cell_faces(const float *__restrict__ chi, float iso, const int32_t *__restrict__ nbr, size_t nodes, TetTable tab,
+                                                       unsigned int *__restrict__ cnt, const unsigned int *__restrict__ foff,
+                                                       const unsigned long long *__restrict__ flag8, const unsigned int *__restrict__ vpos,
+                                                       int32_t *__restrict__ faces) {
+    const size_t a = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (a >= nodes) return;
+    const int32_t *nb = nbr + (a >> 9) * 27;
+    const int l = (int)(a & 511), x = l & 7, y = (l >> 3) & 7, z = l >> 6;
+    long long ce[8];
+    bool whole = true;
+    for (int c = 0; c < 8; c++) {
+        ce[c] = pb_node(nb, x + (c & 1), y + ((c >> 1) & 1), z + ((c >> 2) & 1));
+        whole = whole && ce[c] >= 0;
+    }
+    unsigned int cube = 0; // bit (dx | dy << 1 | dz << 2) = that corner is inside
+    if (whole)
+        for (int c = 0; c < 8; c++)
+            if (chi[ce[c]] < iso) cube |= 1u << c;
+    if (!whole || cube == 0 || cube == 255) {
+        if (!EMIT) cnt[a] = 0;
+        return;
+    }
+    unsigned int nf = 0;
+    size_t o = EMIT ? (size_t)foff[a] : 0;
+    for (int t = 0; t < 6; t++) {
+        const int pa = c_perm[t][0], pb = c_perm[t][1];
+        const int corner[4] = {0, 1 << pa, (1 << pa) | (1 << pb), 7};
+        int m = 0;
+        for (int v = 0; v < 4; v++) m |= ((cube >> corner[v]) & 1) << v;
+        const int nt = tab.ntri[m];
+        if (!EMIT) {
+            nf += nt;
+            continue;
+        }
+        for (int q = 0; q < nt; q++) {
+            int32_t vi[3];
+            for (int c = 0; c < 3; c++) {
+                const int e = tab.e[m][q][c];
+                const int cu = corner[e >> 2], cv = corner[e & 3]; // cu is a subset of cv: the lower node is cu's
+                const int d = cv & ~cu;
+                long long na = ce[0];
+                for (int k = 1; k < 8; k++) na = k == cu ? ce[k] : na; // (no dynamic index into ce: it stays in registers)
+                vi[c] = (int32_t)pb_vertex(flag8, vpos, (size_t)na, pv_dir_code(d & 1, (d >> 1) & 1, (d >> 2) & 1));
+            }
+            if (c_perm_sign[t] < 0) {
+                const int32_t w = vi[1];
+                vi[1] = vi[2];
+                vi[2] = w;
+            }
+            faces[3 * o] = vi[0];
+            faces[3 * o + 1] = vi[1];
+            faces[3 * o + 2] = vi[2];
+            o++;
+        }
+    }
+    if (!EMIT) cnt[a] = nf;
+}
+// one axis of the Chebyshev dilation of the cells' occupancy inside the band (0 off it)
+__global__ __launch_bounds__(256) void k_pb_dilate_cells(const uint8_t *__restrict__ in, uint8_t *__restrict__ out, PbBand B, size_t nodes, int axis, int r) {
+    const size_t a = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (a >= nodes) return;
+    int p[3];
+    pb_origin(B, (int)(a >> 9), p);
+    const int l = (int)(a & 511);
+    p[0] += l & 7;
+    p[1] += (l >> 3) & 7;
+    p[2] += l >> 6;
+    const int c = p[axis];
+    const int lo = c - r < 0 ? 0 : c - r, hi = c + r > B.N - 1 ? B.N - 1 : c + r;
+    uint8_t m = 0;
+    for (int q = lo; q <= hi && !m; q++) {
+        p[axis] = q;
+        const long long e = pb_elem_of(B, p[0], p[1], p[2]);
+        m = (e >= 0 && in[e]) ? 1 : 0;
+    }
+    out[a] = m;
+}
+
+static PvGrid pb_grid(const double grid[4], int depth) { return PvGrid{grid[0], grid[1], grid[2], grid[3], depth, 1 << depth}; }
+static PbBand pb_band(const PoissonBand &b) { return PbBand{b.d_slot, b.d_active, b.d_nbr, b.depth, b.depth - 3, 1 << b.depth}; }
+static inline size_t pb_nodes(const PoissonBand &b) { return (size_t)b.n_active * PB_NODES; }
+
+} // namespace
+
+void poisson_band_free(PoissonBand *b) {
+    if (!b) return;
+    for (int32_t *p : {b->d_slot, b->d_active, b->d_nbr})
+        if (p) (void)hipFree(p);
+    b->d_slot = b->d_active = b->d_nbr = nullptr;
+    b->n_active = b->n_occupied = 0;
+}
+
+// the list and the neighbour table of a band whose slot table and count are there
+static int pb_finish_tables(PoissonBand *out, hipStream_t st) {
+    const int bsh = out->depth - 3;
+    hipLaunchKernelGGL(k_pb_nbr, blocks_for((size_t)out->n_active * 27), dim3(256), 0, st, (const int32_t *)out->d_active, (int)out->n_active,
+                       (const int32_t *)out->d_slot, bsh, out->d_nbr);
+    DEVCHK(hipStreamSynchronize(st));
+    DEVCHK(hipGetLastError());
+    return RSM_OK;
+}
+
+int poisson_band_bricks_device(const float *d_xyz, const float *d_nrm4, int64_t n, int depth, const double grid[4], int band_bricks, int64_t max_bricks,
+                               PoissonBand *out, hipStream_t st) {
+    poisson_band_free(out);
+    out->depth = depth;
+    const int bsh = depth - 3;
+    const size_t B3 = (size_t)1 << (3 * bsh);
+    DevMem M;
+    uint8_t *t0 = M.get<uint8_t>(B3), *t1 = M.get<uint8_t>(B3);
+    unsigned int *pos = M.get<unsigned int>(B3), *opos = M.get<unsigned int>(B3);
+    if (!M.ok || hipMalloc((void **)&out->d_slot, B3 * sizeof(int32_t)) != hipSuccess) return RSM_E_NOMEM;
+    DEVCHK(hipMemsetAsync(t0, 0, B3, st));
+    hipLaunchKernelGGL(k_pb_mark, blocks_for((size_t)n), dim3(256), 0, st, d_xyz, d_nrm4, n, pb_grid(grid, depth), bsh, t0);
+    int s = scan_u32(M, rocprim::make_transform_iterator((const uint8_t *)t0, PbU8ToU32()), opos, B3, st);
+    if (s != RSM_OK) return s;
+    uint64_t nocc = 0, nact = 0;
+    if ((s = scan_total(t0, opos, B3, st, &nocc)) != RSM_OK) return s;
+    hipLaunchKernelGGL(k_pb_dilate_bricks, blocks_for(B3), dim3(256), 0, st, (const uint8_t *)t0, t1, bsh, 0, band_bricks);
+    hipLaunchKernelGGL(k_pb_dilate_bricks, blocks_for(B3), dim3(256), 0, st, (const uint8_t *)t1, t0, bsh, 1, band_bricks);
+    hipLaunchKernelGGL(k_pb_dilate_bricks, blocks_for(B3), dim3(256), 0, st, (const uint8_t *)t0, t1, bsh, 2, band_bricks);
+    if ((s = scan_u32(M, rocprim::make_transform_iterator((const uint8_t *)t1, PbU8ToU32()), pos, B3, st)) != RSM_OK) return s;
+    if ((s = scan_total(t1, pos, B3, st, &nact)) != RSM_OK) return s;
+    DEVCHK(hipGetLastError());
+    out->n_occupied = (int64_t)nocc;
+    out->n_active = (int64_t)nact;
+    if (nact == 0 || (int64_t)nact > max_bricks) return RSM_OK; // (the caller refuses a band above its cap by name)
+    if (hipMalloc((void **)&out->d_active, nact * sizeof(int32_t)) != hipSuccess || hipMalloc((void **)&out->d_nbr, nact * 27 * sizeof(int32_t)) != hipSuccess)
+        return RSM_E_NOMEM;
+    hipLaunchKernelGGL(k_pb_slots, blocks_for(B3), dim3(256), 0, st, (const uint8_t *)t1, (const unsigned int *)pos, B3, out->d_slot, out->d_active);
+    return pb_finish_tables(out, st);
+}
+
+int poisson_band_of_list_device(const int32_t *h_bricks, int64_t n_bricks, int depth, PoissonBand *out, hipStream_t st) {
+    poisson_band_free(out);
+    out->depth = depth;
+    const size_t B3 = (size_t)1 << (3 * (depth - 3));
+    if (hipMalloc((void **)&out->d_slot, B3 * sizeof(int32_t)) != hipSuccess) return RSM_E_NOMEM;
+    DEVCHK(hipMemsetAsync(out->d_slot, 0xff, B3 * sizeof(int32_t), st)); // -1
+    out->n_active = n_bricks;
+    if (n_bricks == 0) return mesh_finish(st);
+    if (hipMalloc((void **)&out->d_active, (size_t)n_bricks * sizeof(int32_t)) != hipSuccess ||
+        hipMalloc((void **)&out->d_nbr, (size_t)n_bricks * 27 * sizeof(int32_t)) != hipSuccess)
+        return RSM_E_NOMEM;
+    DEVCHK(hipMemcpyAsync(out->d_active, h_bricks, (size_t)n_bricks * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_pb_slots_of_list, blocks_for((size_t)n_bricks), dim3(256), 0, st, (const int32_t *)out->d_active, (int)n_bricks, out->d_slot);
+    return pb_finish_tables(out, st);
+}
+
+int poisson_band_rhs_device(const PoissonBand &band, const float *d_xyz, const float *d_nrm4, int64_t n, const double grid[4], float *d_b32, double *d_b64,
+                            uint8_t *d_occ, hipStream_t st) {
+    const size_t nodes = pb_nodes(band);
+    DevMem M;
+    unsigned long long *V = M.get<unsigned long long>(3 * nodes);
+    if (!M.ok) return RSM_E_NOMEM;
+    DEVCHK(hipMemsetAsync(V, 0, 3 * nodes * sizeof(unsigned long long), st));
+    DEVCHK(hipMemsetAsync(d_occ, 0, nodes, st));
+    hipLaunchKernelGGL(k_pb_splat, blocks_for((size_t)n), dim3(256), 0, st, d_xyz, d_nrm4, n, pb_grid(grid, band.depth), pb_band(band), V, nodes, d_occ);
+    hipLaunchKernelGGL(k_pb_rhs, blocks_for(nodes), dim3(256), 0, st, (const long long *)V, nodes, (const int32_t *)band.d_nbr, d_b32, d_b64);
+    return mesh_finish(st);
+}
+
+int poisson_band_guess_device(const PoissonBand &band, const float *d_chi_c, float *d_g, hipStream_t st) {
+    const size_t nodes = pb_nodes(band);
+    hipLaunchKernelGGL(k_pb_guess, blocks_for(nodes), dim3(256), 0, st, d_chi_c, pb_band(band), nodes, d_g);
+    return mesh_finish(st);
+}
+
+int poisson_band_solve_device(const PoissonBand &band, const float *d_b, const float *d_chi_c, double rel_residual, int max_iterations, float *d_chi,
+                              double *residual0, double *residual, int *iterations, double *history, hipStream_t st) {
+    const size_t nodes = pb_nodes(band);
+    const unsigned S = (unsigned)band.n_active;
+    const PbBand B = pb_band(band);
+    *residual0 = *residual = 0.0;
+    *iterations = 0;
+    DevMem M; // (all of the solve's scratch before its first launch)
+    float *r = M.get<float>(nodes), *z = M.get<float>(nodes), *p = M.get<float>(nodes), *q = M.get<float>(nodes), *best = M.get<float>(nodes);
+    double *part = M.get<double>(S), *part2 = M.get<double>(POISSON_SUM_PARTIALS), *scal = M.get<double>(1);
+    if (!M.ok) return RSM_E_NOMEM;
+    auto fetch = [&](double *out) -> int { // the sum of the per-slot partials, in slot order through f7's tree
+        poisson_tree_sum(part, (int64_t)S, part2, scal, st);
+        DEVCHK(hipMemcpyAsync(out, scal, sizeof(double), hipMemcpyDeviceToHost, st));
+        DEVCHK(hipStreamSynchronize(st));
+        return RSM_OK;
+    };
+    auto residual_of_chi = [&](double *rr) -> int { // r = b - L chi
+        hipLaunchKernelGGL(k_pb_stencil<1>, dim3(S), dim3(256), 0, st, (const float *)d_chi, d_b, r, B, d_chi_c, part);
+        return fetch(rr);
+    };
+    double bb = 0.0, rr = 0.0;
+    hipLaunchKernelGGL(k_pb_dot, dim3(S), dim3(256), 0, st, d_b, d_b, part);
+    int s = fetch(&bb);
+    if (s != RSM_OK) return s;
+    if (!(bb > 0.0)) return mesh_finish(st); // b = 0 on the band: chi stays the guess
+    const double bnorm = sqrt(bb);
+    if ((s = residual_of_chi(&rr)) != RSM_OK) return s;
+    *residual0 = *residual = sqrt(rr) / bnorm;
+    if (*residual > rel_residual) {
+        DEVCHK(hipMemcpyAsync(best, d_chi, nodes * sizeof(float), hipMemcpyDeviceToDevice, st));
+        double rho_old = 0.0;
+        int worse = 0;
+        for (int it = 1; it <= max_iterations; it++) {
+            // z = M^-1 r: red, black, (black again would recompute the same values from the same red ones), red
+            hipLaunchKernelGGL(k_pb_rbgs<true>, dim3(S), dim3(256), 0, st, z, (const float *)r, B, 0, (double *)nullptr);
+            hipLaunchKernelGGL(k_pb_rbgs<false>, dim3(S), dim3(256), 0, st, z, (const float *)r, B, 1, (double *)nullptr);
+            hipLaunchKernelGGL(k_pb_rbgs<false>, dim3(S), dim3(256), 0, st, z, (const float *)r, B, 0, part);
+            double rho = 0.0, pq = 0.0;
+            if ((s = fetch(&rho)) != RSM_OK) return s;
+            if (it == 1) DEVCHK(hipMemcpyAsync(p, z, nodes * sizeof(float), hipMemcpyDeviceToDevice, st));
+            else hipLaunchKernelGGL(k_pb_xpay, blocks_for(nodes), dim3(256), 0, st, p, (const float *)z, (float)(rho / rho_old), nodes);
+            hipLaunchKernelGGL(k_pb_stencil<0>, dim3(S), dim3(256), 0, st, (const float *)p, (const float *)nullptr, q, B, (const float *)nullptr, part);
+            if ((s = fetch(&pq)) != RSM_OK) return s;
+            if (pq == 0.0 || !std::isfinite(rho / pq)) break; // nothing left to correct in float32
+            hipLaunchKernelGGL(k_pb_axpy, blocks_for(nodes), dim3(256), 0, st, d_chi, (const float *)p, (float)(rho / pq), nodes);
+            if ((s = residual_of_chi(&rr)) != RSM_OK) return s; // recomputed from chi: what is reported is what chi reaches
+            rho_old = rho;
+            *iterations = it;
+            const double res = sqrt(rr) / bnorm;
+            if (history) history[it - 1] = res;
+            if (res < *residual) {
+                *residual = res;
+                worse = 0;
+                if (res <= rel_residual) break; // (chi is the best iterate)
+                DEVCHK(hipMemcpyAsync(best, d_chi, nodes * sizeof(float), hipMemcpyDeviceToDevice, st));
+            } else if (++worse >= PB_STALL)
+                break;
+        }
+        if (*residual > rel_residual) DEVCHK(hipMemcpyAsync(d_chi, best, nodes * sizeof(float), hipMemcpyDeviceToDevice, st));
+    }
+    DEVCHK(hipStreamSynchronize(st));
+    DEVCHK(hipGetLastError());
+    return *residual <= rel_residual ? RSM_OK : RSM_W_NOT_CONVERGED;
+}
+
+int poisson_band_iso_device(const PoissonBand &band, const float *d_xyz, const float *d_nrm4, int64_t n, int64_t n_valid, const float *d_chi,
+                            const double grid[4], double *iso, hipStream_t st) {
+    *iso = 0.0;
+    if (n <= 0 || n_valid <= 0) return RSM_OK;
+    DevMem M;
+    double *val = M.get<double>((size_t)n), *part = M.get<double>(POISSON_SUM_PARTIALS), *scal = M.get<double>(1);
+    if (!M.ok) return RSM_E_NOMEM;
+    hipLaunchKernelGGL(k_pb_chi_at_samples, blocks_for((size_t)n), dim3(256), 0, st, d_xyz, d_nrm4, n, pb_grid(grid, band.depth), pb_band(band), d_chi, val);
+    poisson_tree_sum(val, n, part, scal, st);
+    double sum = 0.0;
+    DEVCHK(hipMemcpyAsync(&sum, scal, sizeof sum, hipMemcpyDeviceToHost, st));
+    DEVCHK(hipStreamSynchronize(st));
+    DEVCHK(hipGetLastError());
+    *iso = sum / (double)n_valid;
+    return RSM_OK;
+}
+
+int poisson_band_extract_device(const PoissonBand &band, const float *d_chi, double iso, const double grid[4], const uint8_t *d_occ, int trim_cells,
+                                PoissonMesh *out, int64_t untrimmed[2], hipStream_t st) {
+    poisson_mesh_free(out);
+    untrimmed[0] = untrimmed[1] = 0;
+    const size_t nodes = pb_nodes(band);
+    if (nodes == 0) return RSM_OK;
+    const PvGrid g = pb_grid(grid, band.depth);
+    const PbBand B = pb_band(band);
+    const float iso32 = (float)iso;
+    const TetTable tab = make_tet_table();
+    const bool trim = trim_cells > 0 && d_occ;
+    DevMem M;
+    unsigned long long *flag8 = M.get<unsigned long long>(nodes);
+    unsigned int *vcnt = M.get<unsigned int>(nodes), *vpos = M.get<unsigned int>(nodes), *cnt = M.get<unsigned int>(nodes), *foff = M.get<unsigned int>(nodes);
+    uint8_t *t0 = trim ? M.get<uint8_t>(nodes) : nullptr, *t1 = trim ? M.get<uint8_t>(nodes) : nullptr;
+    if (!M.ok) return RSM_E_NOMEM;
+    hipLaunchKernelGGL(k_pb_edge_flags, blocks_for(nodes), dim3(256), 0, st, d_chi, iso32, (const int32_t *)band.d_nbr, nodes, flag8, vcnt);
+    int s = scan_u32(M, (const unsigned int *)vcnt, vpos, nodes, st);
+    if (s != RSM_OK) return s;
+    hipLaunchKernelGGL(k_pb_cell_faces<false>, blocks_for(nodes), dim3(256), 0, st, d_chi, iso32, (const int32_t *)band.d_nbr, nodes, tab, cnt,
+                       (const unsigned int *)nullptr, (const unsigned long long *)nullptr, (const unsigned int *)nullptr, (int32_t *)nullptr);
+    if ((s = scan_u32(M, (const unsigned int *)cnt, foff, nodes, st)) != RSM_OK) return s;
+    if (trim) {
+        hipLaunchKernelGGL(k_pb_dilate_cells, blocks_for(nodes), dim3(256), 0, st, d_occ, t0, B, nodes, 0, trim_cells);
+        hipLaunchKernelGGL(k_pb_dilate_cells, blocks_for(nodes), dim3(256), 0, st, (const uint8_t *)t0, t1, B, nodes, 1, trim_cells);
+        hipLaunchKernelGGL(k_pb_dilate_cells, blocks_for(nodes), dim3(256), 0, st, (const uint8_t *)t1, t0, B, nodes, 2, trim_cells);
+    }
+    uint64_t nv = 0, nf = 0;
+    if ((s = scan_total(vcnt, vpos, nodes, st, &nv)) != RSM_OK) return s;
+    if ((s = scan_total(cnt, foff, nodes, st, &nf)) != RSM_OK) return s;
+    DEVCHK(hipGetLastError());
+    untrimmed[0] = (int64_t)nv;
+    untrimmed[1] = (int64_t)nf;
+    if (nv == 0 || nf == 0) return RSM_OK;
+    if (nv > (uint64_t)INT32_MAX || nf > (uint64_t)INT32_MAX / 3) return RSM_E_NOMEM;
+    PoissonMesh full;
+    if ((s = mesh_result_alloc(full, nv, nf)) != RSM_OK) return s;
+    uint8_t *vkeep = trim ? M.get<uint8_t>(nv) : nullptr;
+    if (!M.ok) {
+        poisson_mesh_free(&full);
+        return RSM_E_NOMEM;
+    }
+    hipLaunchKernelGGL(k_pb_emit_vertices, blocks_for(nodes), dim3(256), 0, st, d_chi, iso32, g, B, nodes, (const unsigned long long *)flag8,
+                       (const unsigned int *)vpos, full.d_v, (const uint8_t *)t0, vkeep);
+    hipLaunchKernelGGL(k_pb_cell_faces<true>, blocks_for(nodes), dim3(256), 0, st, d_chi, iso32, (const int32_t *)band.d_nbr, nodes, tab, (unsigned int *)nullptr,
+                       (const unsigned int *)foff, (const unsigned long long *)flag8, (const unsigned int *)vpos, full.d_f);
+    if (!trim) {
+        if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) {
+            poisson_mesh_free(&full);
+            return RSM_E_HIP;
+        }
+        *out = full;
+        return RSM_OK;
+    }
+    return poisson_trim_commit(M, full, vkeep, out, st);
+}

@@ -300,6 +300,36 @@ int poisson_density_rhs_device(const float *d_xyz, const float *d_nrm4, int64_t 
 int poisson_iso_weighted_device(const float *d_xyz, const float *d_nrm4, int64_t n, const double *d_w, double sum_w, const float *d_chi, int depth,
                                 const double grid[4], double *iso, hipStream_t st);
 
+// the banded finest level on top of the dense solve (k_poisson_band.hip).  A band: the active bricks (8^3 nodes each) of the
+// grid of 2^depth nodes per axis in ascending linear index; fields are brick-major, n_active * 512 elements.
+struct PoissonBand {
+    int depth = 0;
+    int64_t n_active = 0, n_occupied = 0;
+    int32_t *d_slot = nullptr;   // (2^(depth-3))^3: brick -> slot, -1 inactive
+    int32_t *d_active = nullptr; // n_active: slot -> brick
+    int32_t *d_nbr = nullptr;    // n_active x 27: the slots around a slot (-1 inactive, -2 outside the grid)
+};
+void poisson_band_free(PoissonBand *b);
+// the bricks within band_bricks of a brick that holds a valid sample's cell.  More than max_bricks of them: RSM_OK with n_active set and no
+// tables (the caller refuses by name)
+int poisson_band_bricks_device(const float *d_xyz, const float *d_nrm4, int64_t n, int depth, const double grid[4], int band_bricks, int64_t max_bricks,
+                               PoissonBand *out, hipStream_t st);
+// ... from a caller's list on the host (ascending, each in range: the caller checks)
+int poisson_band_of_list_device(const int32_t *h_bricks, int64_t n_bricks, int depth, PoissonBand *out, hipStream_t st);
+// f7's splat and right-hand side on the band: d_b32 / d_b64 (either may be NULL) and d_occ (per fine cell), brick-major
+int poisson_band_rhs_device(const PoissonBand &band, const float *d_xyz, const float *d_nrm4, int64_t n, const double grid[4], float *d_b32, double *d_b64,
+                            uint8_t *d_occ, hipStream_t st);
+// g = (float)(1/4 of the trilinear prolongation of d_chi_c, the dense field of depth - 1)
+int poisson_band_guess_device(const PoissonBand &band, const float *d_chi_c, float *d_g, hipStream_t st);
+// d_chi: the guess on entry, the best field on return.  d_chi_c (may be NULL: 0) gives the guess at the inactive neighbours of the band.
+// residual0: before the first iteration; history (optional): max_iterations doubles.  RSM_OK / RSM_W_NOT_CONVERGED / an error
+int poisson_band_solve_device(const PoissonBand &band, const float *d_b, const float *d_chi_c, double rel_residual, int max_iterations, float *d_chi,
+                              double *residual0, double *residual, int *iterations, double *history, hipStream_t st);
+int poisson_band_iso_device(const PoissonBand &band, const float *d_xyz, const float *d_nrm4, int64_t n, int64_t n_valid, const float *d_chi,
+                            const double grid[4], double *iso, hipStream_t st);
+int poisson_band_extract_device(const PoissonBand &band, const float *d_chi, double iso, const double grid[4], const uint8_t *d_occ, int trim_cells,
+                                PoissonMesh *out, int64_t untrimmed[2], hipStream_t st);
+
 // smoothing and clean-up of a triangle mesh (k_meshclean.hip).  Device buffers: nv float xyz, nf int32 x 3.  RSM_E_INVALID
 // comes with *invalid = 1 (a face index outside [0, nv)) or 2 (a coordinate that is not finite); parameters are the caller's to check.
 struct rsm_mesh_clean_params;

@@ -299,6 +299,246 @@ extern "C" int rsm_stage_poisson_rhs_weighted(rsm_ctx *c, const float *xyz, cons
     return finish(c, T);
 }
 
+// ---- the finest level on a band of bricks (k_poisson_band.hip) -----------------------------------------------------------------
+// p with its depth as the finest one; `coarse`: p as the dense solve at depth - 1 reads it
+static int poisson_band_params_ok(rsm_ctx *c, const rsm_poisson_params *p, const rsm_poisson_band_params *bp, rsm_poisson_params *coarse) {
+    if (!p) return set_err(c, RSM_E_INVALID, "poisson: params is NULL");
+    if (!bp) return set_err(c, RSM_E_INVALID, "poisson: band params is NULL");
+    if (p->depth < 6 || p->depth > 10) return set_err(c, RSM_E_INVALID, "poisson: banded depth %d outside 6..10", p->depth);
+    *coarse = *p;
+    coarse->depth = p->depth - 1;
+    const int s = poisson_params_ok(c, coarse);
+    if (s != RSM_OK) return s;
+    if (bp->band_bricks < 1 || bp->band_bricks > 4) return set_err(c, RSM_E_INVALID, "poisson: band_bricks %d outside 1..4", bp->band_bricks);
+    if (bp->max_iterations < 1) return set_err(c, RSM_E_INVALID, "poisson: max_iterations %d < 1", bp->max_iterations);
+    if (p->trim_cells > 8 * bp->band_bricks - 1)
+        return set_err(c, RSM_E_INVALID, "poisson: trim_cells %d > 8 band_bricks - 1 = %d (a kept face needs its cell in the band)", p->trim_cells, 8 * bp->band_bricks - 1);
+    return RSM_OK;
+}
+static int poisson_band_cap(rsm_ctx *c, const PoissonBand &band, int64_t max_bricks) {
+    if (band.n_active > max_bricks)
+        return set_err(c, RSM_E_INVALID, "poisson: %lld active bricks, more than the %lld allowed (such a cloud fills the volume)", (long long)band.n_active,
+                       (long long)max_bricks);
+    return RSM_OK;
+}
+struct BandOwner { // frees a call's band on every way out
+    PoissonBand b;
+    ~BandOwner() { poisson_band_free(&b); }
+};
+// the coarse field of a banded call: f7's steps 3 to 5 at depth - 1 on the box of `grid` (the fine grid) -> chi_c; RSM_OK / RSM_W_NOT_CONVERGED / an error set
+static int poisson_band_coarse(rsm_ctx *c, const float *d_xyz, const float *d_nrm, int64_t n, const rsm_poisson_params *coarse, const double grid[4], float *chi_c,
+                               double *res, int *cycles) {
+    const size_t C3 = (size_t)1 << (3 * coarse->depth);
+    const double cgrid[4] = {grid[0], grid[1], grid[2], 2.0 * grid[3]};
+    Tmp T(c);
+    float *b = T.alloc<float>(C3);
+    uint8_t *occ = T.alloc<uint8_t>(C3);
+    if (!b || !occ) return set_err(c, RSM_E_NOMEM, "poisson: no device memory for depth %d", coarse->depth);
+    int s = poisson_rhs_device(d_xyz, d_nrm, n, coarse->depth, cgrid, b, nullptr, occ, c->stream);
+    if (s != RSM_OK) return poisson_fail(c, s, "coarse right-hand side");
+    s = poisson_solve_device(b, coarse->depth, coarse->rel_residual, coarse->max_cycles, chi_c, res, cycles, nullptr, c->stream);
+    return s < 0 ? poisson_fail(c, s, "coarse solve") : s;
+}
+
+static int poisson_run_banded(rsm_ctx *c, const float *d_xyz, const float *d_nrm, int64_t n, const rsm_poisson_params *p, const rsm_poisson_band_params *bp,
+                              const rsm_poisson_params *coarse, int64_t *n_vertices, int64_t *n_faces, double *stats) {
+    double st[RSM_POISSON_BAND_STATS] = {0};
+    *n_vertices = *n_faces = 0;
+    poisson_mesh_free(&c->pmesh);
+    mesh_replaced(c);
+    double grid[4];
+    int64_t counts[2];
+    int s = poisson_grid_device(d_xyz, d_nrm, n, p->depth, p->scale, grid, counts, c->stream);
+    if (s != RSM_OK) return poisson_fail(c, s, "bounding box");
+    st[0] = (double)counts[0];
+    st[1] = (double)counts[1];
+    st[9] = (double)(1 << p->depth);
+    int status = RSM_OK;
+    if (grid[3] > 0.0) {
+        BandOwner band;
+        if ((s = poisson_band_bricks_device(d_xyz, d_nrm, n, p->depth, grid, bp->band_bricks, RSM_POISSON_BAND_MAX_BRICKS, &band.b, c->stream)) != RSM_OK)
+            return poisson_fail(c, s, "bricks");
+        if ((s = poisson_band_cap(c, band.b, RSM_POISSON_BAND_MAX_BRICKS)) != RSM_OK) return s;
+        const size_t nodes = (size_t)band.b.n_active * 512;
+        Tmp T(c);
+        float *chi_c = T.alloc<float>((size_t)1 << (3 * coarse->depth)), *b = T.alloc<float>(nodes), *chi = T.alloc<float>(nodes);
+        uint8_t *occ = T.alloc<uint8_t>(nodes);
+        if (!chi_c || !b || !chi || !occ) return set_err(c, RSM_E_NOMEM, "poisson: no device memory for %lld bricks at depth %d", (long long)band.b.n_active, p->depth);
+        double cres = 0.0, res0 = 0.0, res = 0.0, iso = 0.0;
+        int ccycles = 0, its = 0;
+        const int csolved = poisson_band_coarse(c, d_xyz, d_nrm, n, coarse, grid, chi_c, &cres, &ccycles);
+        if (csolved < 0) return csolved;
+        if ((s = poisson_band_rhs_device(band.b, d_xyz, d_nrm, n, grid, b, nullptr, occ, c->stream)) != RSM_OK) return poisson_fail(c, s, "band right-hand side");
+        if ((s = poisson_band_guess_device(band.b, chi_c, chi, c->stream)) != RSM_OK) return poisson_fail(c, s, "guess");
+        const int solved = poisson_band_solve_device(band.b, b, chi_c, p->rel_residual, bp->max_iterations, chi, &res0, &res, &its, nullptr, c->stream);
+        if (solved < 0) return poisson_fail(c, solved, "band solve");
+        if ((s = poisson_band_iso_device(band.b, d_xyz, d_nrm, n, counts[0], chi, grid, &iso, c->stream)) != RSM_OK) return poisson_fail(c, s, "iso-value");
+        int64_t un[2];
+        if ((s = poisson_band_extract_device(band.b, chi, iso, grid, occ, p->trim_cells, &c->pmesh, un, c->stream)) != RSM_OK) return poisson_fail(c, s, "extraction");
+        mesh_replaced(c);
+        st[2] = res;
+        st[3] = (double)its;
+        st[4] = iso;
+        for (int a = 0; a < 4; a++) st[5 + a] = grid[a];
+        st[10] = (double)un[0];
+        st[11] = (double)un[1];
+        st[12] = (double)band.b.n_active;
+        st[13] = (double)band.b.n_occupied;
+        st[14] = (double)ccycles;
+        st[15] = cres;
+        st[16] = res0;
+        if (solved == RSM_W_NOT_CONVERGED) set_err(c, solved, "poisson: band residual %g after %d iterations (rel_residual %g)", res, its, p->rel_residual);
+        else if (csolved == RSM_W_NOT_CONVERGED) set_err(c, csolved, "poisson: coarse residual %g after %d cycles (rel_residual %g)", cres, ccycles, p->rel_residual);
+        status = (solved == RSM_W_NOT_CONVERGED || csolved == RSM_W_NOT_CONVERGED) ? RSM_W_NOT_CONVERGED : RSM_OK;
+    }
+    *n_vertices = c->pmesh.nv;
+    *n_faces = c->pmesh.nf;
+    if (stats) memcpy(stats, st, sizeof st);
+    return status;
+}
+
+extern "C" int rsm_poisson_mesh_banded_device(rsm_ctx *c, const float *d_xyz, const float *d_normals4, int64_t n, const rsm_poisson_params *p,
+                                              const rsm_poisson_band_params *bp, int64_t *n_vertices, int64_t *n_faces, double *stats) {
+    if (!c) return RSM_E_INVALID;
+    rsm_poisson_params coarse;
+    int s = poisson_band_params_ok(c, p, bp, &coarse);
+    if (s != RSM_OK || (s = poisson_n_ok(c, n)) != RSM_OK) return s;
+    if (!n_vertices || !n_faces || (n > 0 && (!d_xyz || !d_normals4))) return set_err(c, RSM_E_INVALID, "poisson: a NULL pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    return poisson_run_banded(c, d_xyz, d_normals4, n, p, bp, &coarse, n_vertices, n_faces, stats);
+}
+
+extern "C" int rsm_poisson_mesh_banded(rsm_ctx *c, const float *xyz, const float *normals4, int64_t n, const rsm_poisson_params *p,
+                                       const rsm_poisson_band_params *bp, int64_t *n_vertices, int64_t *n_faces, double *stats) {
+    if (!c) return RSM_E_INVALID;
+    rsm_poisson_params coarse;
+    int s = poisson_band_params_ok(c, p, bp, &coarse);
+    if (s != RSM_OK || (s = poisson_n_ok(c, n)) != RSM_OK) return s;
+    if (!n_vertices || !n_faces || (n > 0 && (!xyz || !normals4))) return set_err(c, RSM_E_INVALID, "poisson: a NULL pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    Tmp T(c);
+    float *dx = T.up(xyz, 3 * (size_t)n), *dn = T.up(normals4, 4 * (size_t)n);
+    if (!dx || !dn) return set_err(c, RSM_E_NOMEM, "poisson: no device memory for %lld samples", (long long)n);
+    if (n > 0 && (s = finish(c, T)) != RSM_OK) return s;
+    return poisson_run_banded(c, dx, dn, n, p, bp, &coarse, n_vertices, n_faces, stats);
+}
+
+extern "C" int rsm_stage_poisson_band_rhs(rsm_ctx *c, const float *xyz, const float *normals4, int64_t n, const rsm_poisson_params *p,
+                                          const rsm_poisson_band_params *bp, const float *chi_c, int64_t max_bricks, int64_t brick_room, double grid[4],
+                                          int32_t *bricks, double *b, uint8_t *occ, float *g, int64_t counts[4]) {
+    if (!c) return RSM_E_INVALID;
+    rsm_poisson_params coarse;
+    int s = poisson_band_params_ok(c, p, bp, &coarse);
+    if (s != RSM_OK || (s = poisson_n_ok(c, n)) != RSM_OK) return s;
+    if (max_bricks < 0 || max_bricks > RSM_POISSON_BAND_MAX_BRICKS) return set_err(c, RSM_E_INVALID, "poisson: max_bricks %lld outside 0..2^20", (long long)max_bricks);
+    if (brick_room < 0) return set_err(c, RSM_E_INVALID, "poisson: brick_room %lld < 0", (long long)brick_room);
+    if (!grid || !bricks || !b || !occ || !g || !counts || (n > 0 && (!xyz || !normals4))) return set_err(c, RSM_E_INVALID, "poisson: a NULL pointer");
+    if (max_bricks == 0) max_bricks = RSM_POISSON_BAND_MAX_BRICKS;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t C3 = (size_t)1 << (3 * coarse.depth);
+    Tmp T(c);
+    float *dx = T.up(xyz, 3 * (size_t)n), *dn = T.up(normals4, 4 * (size_t)n);
+    float *dchic = chi_c ? T.up(chi_c, C3) : T.alloc<float>(C3);
+    if (!dx || !dn || !dchic) return set_err(c, RSM_E_NOMEM, "poisson: no device memory");
+    if ((s = finish(c, T)) != RSM_OK) return s;
+    int64_t vc[2];
+    if ((s = poisson_grid_device(dx, dn, n, p->depth, p->scale, grid, vc, c->stream)) != RSM_OK) return poisson_fail(c, s, "bounding box");
+    counts[0] = vc[0];
+    counts[1] = vc[1];
+    counts[2] = counts[3] = 0;
+    if (!(grid[3] > 0.0)) return RSM_OK;
+    BandOwner band;
+    if ((s = poisson_band_bricks_device(dx, dn, n, p->depth, grid, bp->band_bricks, max_bricks, &band.b, c->stream)) != RSM_OK) return poisson_fail(c, s, "bricks");
+    if ((s = poisson_band_cap(c, band.b, max_bricks)) != RSM_OK) return s;
+    if (band.b.n_active > brick_room)
+        return set_err(c, RSM_E_INVALID, "poisson: %lld active bricks, brick_room %lld", (long long)band.b.n_active, (long long)brick_room);
+    counts[2] = band.b.n_active;
+    counts[3] = band.b.n_occupied;
+    const size_t S = (size_t)band.b.n_active, nodes = S * 512;
+    double *db = T.alloc<double>(nodes);
+    uint8_t *docc = T.alloc<uint8_t>(nodes);
+    float *dg = T.alloc<float>(nodes);
+    if (!db || !docc || !dg) return set_err(c, RSM_E_NOMEM, "poisson: no device memory");
+    int solved = RSM_OK;
+    if (!chi_c) {
+        double cres;
+        int ccycles;
+        if ((solved = poisson_band_coarse(c, dx, dn, n, &coarse, grid, dchic, &cres, &ccycles)) < 0) return solved;
+    }
+    if ((s = poisson_band_rhs_device(band.b, dx, dn, n, grid, nullptr, db, docc, c->stream)) != RSM_OK) return poisson_fail(c, s, "band right-hand side");
+    if ((s = poisson_band_guess_device(band.b, dchic, dg, c->stream)) != RSM_OK) return poisson_fail(c, s, "guess");
+    T.later(bricks, (const int32_t *)band.b.d_active, S).later(b, (const double *)db, nodes).later(occ, (const uint8_t *)docc, nodes).later(g, (const float *)dg, nodes);
+    s = finish(c, T);
+    return s != RSM_OK ? s : solved;
+}
+
+// a caller's brick list: ascending, each in [0, B^3)
+static int poisson_band_list_ok(rsm_ctx *c, const int32_t *bricks, int64_t n_bricks, int depth) {
+    if (depth < 6 || depth > 10) return set_err(c, RSM_E_INVALID, "poisson: banded depth %d outside 6..10", depth);
+    const int64_t B3 = (int64_t)1 << (3 * (depth - 3));
+    if (n_bricks < 0 || n_bricks > B3 || n_bricks > RSM_POISSON_BAND_MAX_BRICKS)
+        return set_err(c, RSM_E_INVALID, "poisson: n_bricks %lld outside 0..min(B^3, 2^20)", (long long)n_bricks);
+    if (n_bricks > 0 && !bricks) return set_err(c, RSM_E_INVALID, "poisson: a NULL pointer");
+    for (int64_t i = 0; i < n_bricks; i++)
+        if (bricks[i] < 0 || bricks[i] >= B3 || (i > 0 && bricks[i] <= bricks[i - 1]))
+            return set_err(c, RSM_E_INVALID, "poisson: bricks[%lld] = %d out of range or not ascending", (long long)i, bricks[i]);
+    return RSM_OK;
+}
+
+extern "C" int rsm_stage_poisson_band_solve(rsm_ctx *c, const int32_t *bricks, int64_t n_bricks, int depth, const float *b, const float *g, const float *chi_c,
+                                            double rel_residual, int max_iterations, float *chi, double *residual, int *iterations, double *residual0,
+                                            double *history) {
+    if (!c) return RSM_E_INVALID;
+    int s = poisson_band_list_ok(c, bricks, n_bricks, depth);
+    if (s != RSM_OK) return s;
+    if (!(rel_residual > 0.0 && rel_residual < 1.0)) return set_err(c, RSM_E_INVALID, "poisson: rel_residual %g not in (0, 1)", rel_residual);
+    if (max_iterations < 1) return set_err(c, RSM_E_INVALID, "poisson: max_iterations %d < 1", max_iterations);
+    if (!residual || !iterations || !residual0 || (n_bricks > 0 && (!b || !g || !chi))) return set_err(c, RSM_E_INVALID, "poisson: a NULL pointer");
+    *residual = *residual0 = 0.0;
+    *iterations = 0;
+    if (n_bricks == 0) return RSM_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t nodes = (size_t)n_bricks * 512;
+    Tmp T(c);
+    float *db = T.up(b, nodes), *dchi = T.up(g, nodes), *dchic = chi_c ? T.up(chi_c, (size_t)1 << (3 * (depth - 1))) : nullptr;
+    if (!db || !dchi || (chi_c && !dchic)) return set_err(c, RSM_E_NOMEM, "poisson: no device memory");
+    if ((s = finish(c, T)) != RSM_OK) return s;
+    BandOwner band;
+    if ((s = poisson_band_of_list_device(bricks, n_bricks, depth, &band.b, c->stream)) != RSM_OK) return poisson_fail(c, s, "bricks");
+    s = poisson_band_solve_device(band.b, db, dchic, rel_residual, max_iterations, dchi, residual0, residual, iterations, history, c->stream);
+    if (s < 0) return poisson_fail(c, s, "band solve");
+    T.later(chi, (const float *)dchi, nodes);
+    const int d = finish(c, T);
+    return d != RSM_OK ? d : s;
+}
+
+extern "C" int rsm_stage_band_iso_mesh(rsm_ctx *c, const int32_t *bricks, int64_t n_bricks, int depth, const float *chi, double iso, const double grid[4],
+                                       const uint8_t *occ, int trim_cells, int64_t *n_vertices, int64_t *n_faces) {
+    if (!c) return RSM_E_INVALID;
+    int s = poisson_band_list_ok(c, bricks, n_bricks, depth);
+    if (s != RSM_OK) return s;
+    if (trim_cells < 0) return set_err(c, RSM_E_INVALID, "poisson: trim_cells %d < 0", trim_cells);
+    if (!grid || !n_vertices || !n_faces || (n_bricks > 0 && !chi) || (trim_cells > 0 && !occ)) return set_err(c, RSM_E_INVALID, "poisson: a NULL pointer");
+    if (!std::isfinite(iso) || !std::isfinite(grid[0]) || !std::isfinite(grid[1]) || !std::isfinite(grid[2]) || !(grid[3] > 0.0) || !std::isfinite(grid[3]))
+        return set_err(c, RSM_E_INVALID, "poisson: iso or grid not finite, or h <= 0");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t nodes = (size_t)n_bricks * 512;
+    Tmp T(c);
+    float *dchi = T.up(chi, nodes);
+    uint8_t *docc = occ ? T.up(occ, nodes) : nullptr;
+    if (!dchi || (occ && !docc)) return set_err(c, RSM_E_NOMEM, "poisson: no device memory");
+    if ((s = finish(c, T)) != RSM_OK) return s;
+    BandOwner band;
+    if ((s = poisson_band_of_list_device(bricks, n_bricks, depth, &band.b, c->stream)) != RSM_OK) return poisson_fail(c, s, "bricks");
+    int64_t un[2];
+    s = poisson_band_extract_device(band.b, dchi, iso, grid, docc, trim_cells, &c->pmesh, un, c->stream);
+    mesh_replaced(c); // (also when it failed: the extraction frees the mesh before anything else)
+    if (s != RSM_OK) return poisson_fail(c, s, "extraction");
+    *n_vertices = c->pmesh.nv;
+    *n_faces = c->pmesh.nf;
+    return RSM_OK;
+}
+
 // ---- the mesh-to-mesh stages: clean, trim, close_holes, decimate, subdivide (how the back end's units are laid out) -------------------------
 static int mesh_counts_ok(rsm_ctx *c, const char *who, int64_t nv, int64_t nf) { // who: "mesh_clean" / "mesh_trim" / "mesh_color" ...
     if (nv < 0 || nv > (int64_t)INT32_MAX) return set_err(c, RSM_E_INVALID, "%s: nv %lld outside 0..INT32_MAX", who, (long long)nv);
