@@ -636,6 +636,32 @@ int rsm_stage_poisson_band_solve(rsm_ctx *ctx, const int32_t *bricks, int64_t n_
                                  double *residual0, double *history);
 int rsm_stage_band_iso_mesh(rsm_ctx *ctx, const int32_t *bricks, int64_t n_bricks, int depth, const float *chi, double iso,
                             const double grid[4], const uint8_t *occ, int trim_cells, int64_t *n_vertices, int64_t *n_faces);
+/* ---- the banded call with the density-adaptive splat (script1.mlx: OctDepth 10 and SamplesPerNode 3 together) -----------------------------
+ * Opt-in; the three calls above keep their behaviour and their bits.  p->depth is the finest depth D, 6..10, and bp is the banded call's.  Every
+ * sample's rho, w and d = min(D, max(3, value)) are the density-adaptive call's at depth D, computed once; kernel_depth is 0 (D - 2) or 3..D - 1,
+ * since the density grid exists in the coarse problem too.  The coarse problem is the density-adaptive one at D - 1 on the same box with the same
+ * w and d clamped to D - 1.  On the fine grid the levels 3..D - 1 of the splat are dense and cascaded to level D - 1; the level D lives on the
+ * bricks; the right-hand side on the band is that of the level-D sums plus the trilinear prolongation of the coarser levels, which also
+ * stands for the field next to the band.  Guess, band solve, extraction and trim are the banded call's; the iso-value is the w-weighted mean of
+ * chi at the samples.  Not a bit-parity port of PoissonRecon: the rules as DESIGN.md 9 (f17) defines them. */
+/* stats: [0..16] as RSM_POISSON_BAND_STATS, [17] the kernel depth used, [18] the least d over the valid samples, [19] the number of samples
+ * with d < D, [20] the sum of w */
+#define RSM_POISSON_BAND_WEIGHTED_STATS 21
+/* as rsm_poisson_mesh_banded[_device].  RSM_E_INVALID (rsm_last_error names the parameter) for everything that call refuses, for dp = NULL,
+ * kernel_depth neither 0 nor in 3..D - 1 and samples_per_node not finite or <= 0. */
+int rsm_poisson_mesh_banded_weighted(rsm_ctx *ctx, const float *xyz, const float *normals4, int64_t n, const rsm_poisson_params *p,
+                                     const rsm_poisson_band_params *bp, const rsm_poisson_density_params *dp, int64_t *n_vertices, int64_t *n_faces,
+                                     double *stats);
+int rsm_poisson_mesh_banded_weighted_device(rsm_ctx *ctx, const float *d_xyz, const float *d_normals4, int64_t n, const rsm_poisson_params *p,
+                                            const rsm_poisson_band_params *bp, const rsm_poisson_density_params *dp, int64_t *n_vertices,
+                                            int64_t *n_faces, double *stats);
+/* stage entry point (host buffers) for the tests: rsm_stage_poisson_band_rhs with this splat.  depth_in (n doubles, may be NULL; RSM_E_INVALID
+ * when one is not finite): each sample's d from the caller, clamped to 3..D.  The coarse field, when chi_c is NULL, is that of the coarse
+ * problem above.  rho, w, d (n doubles each, may be NULL): per sample, 0 where it takes no part. */
+int rsm_stage_poisson_band_rhs_weighted(rsm_ctx *ctx, const float *xyz, const float *normals4, int64_t n, const rsm_poisson_params *p,
+                                        const rsm_poisson_band_params *bp, const rsm_poisson_density_params *dp, const double *depth_in,
+                                        const float *chi_c, int64_t max_bricks, int64_t brick_room, double grid[4], int32_t *bricks, double *b,
+                                        uint8_t *occ, float *g, int64_t counts[4], double *rho, double *w, double *d);
 /* binary little-endian PLY mesh: vertex float x, y, z; face list uchar int vertex_indices (what MeshLab and TextureStitcher read).  Host only. */
 int rsm_write_ply_mesh(const char *path, const float *xyz, int64_t n_vertices, const int32_t *faces, int64_t n_faces);
 

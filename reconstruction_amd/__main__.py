@@ -1,5 +1,5 @@
 """python -m reconstruction_amd <config.yml> [--device N] [--out cloud.ply] [--filter] [--mls [--isdelete] [--mls-out bigcloud.ply]]
-                              [--mesh [--mesh-depth 9] [--mesh-trim 4] [--mesh-band [B]] [--mesh-out bigmesh.ply]
+                              [--mesh [--mesh-depth 9] [--mesh-trim 4] [--mesh-band [B] [--mesh-band-samples-per-node [3]]] [--mesh-out bigmesh.ply]
                                [--mesh-samples-per-node [2] [--mesh-kernel-depth 0]]
                                [--mesh-density-trim [7] [--mesh-density-smooth 100] [--mesh-island-ratio 0.01]]
                                [--mesh-clean [--mesh-smooth 5] [--mesh-min-piece 10%]] [--mesh-close-holes [30]] [--mesh-decimate [100000]]
@@ -20,6 +20,8 @@ With --mesh-samples-per-node (implies --mesh) the Poisson call spreads every sam
 --samplesPerNode does (2 when given bare, mesh.bat's value; script1.mlx uses 3), so that thinly sampled parts hold their place.
 With --mesh-band (implies --mesh) the surface is one level finer than the dense grid reaches: --mesh-depth 6..10 is then the finest depth, a level
 that exists only on a band of bricks around the points, on top of the dense solve one depth coarser (script1.mlx's OctDepth 10).
+With --mesh-band-samples-per-node (implies --mesh-band 1) the banded call uses the density-adaptive splat: script1.mlx's OctDepth 10 and
+SamplesPerNode 3 together.  --mesh-band with --mesh-samples-per-node stays refused, which is why this switch is its own.
 With --mesh-density-trim (implies --mesh) the Poisson call runs without its occupancy trim and the surface is trimmed as mesh.bat's
 SurfaceTrimmer does, on the GPU: cut along the iso-line of the smoothed sample density, small islands moved across.
 With --mesh-clean (implies --mesh) bigmesh.ply is that surface after meshlab.bat's other filters, on the GPU: Laplacian smoothing
@@ -98,8 +100,13 @@ def main(argv=None) -> int:
                          "the bricks of 8^3 nodes within B (1..4; 1 when given bare) of a brick that holds a point, on top of the dense solve one depth "
                          "coarser; --mesh-trim is then at most 8 B - 1 (script1.mlx at depth 10 corresponds to --mesh-trim 8 --mesh-band 2); not with "
                          "--mesh-samples-per-node or --mesh-density-trim at depth 10")
+    ap.add_argument("--mesh-band-samples-per-node", type=float, nargs="?", const=3.0, default=None, metavar="S",
+                    help="the banded surface (--mesh-band 1 implied when that is absent) with the density-adaptive splat of --mesh-samples-per-node: the "
+                         "levels below the finest are dense, the finest lives on the bricks (3 when given bare as in script1.mlx).  A switch of its own "
+                         "because --mesh-band with --mesh-samples-per-node stays refused; honours --mesh-kernel-depth (0 or 3..depth - 1)")
     ap.add_argument("--mesh-kernel-depth", type=int, default=0, metavar="K",
-                    help="with --mesh-samples-per-node: the density is estimated on 2^K grid nodes per axis, 3..depth (0 = depth - 2)")
+                    help="with --mesh-samples-per-node or --mesh-band-samples-per-node: the density is estimated on 2^K grid nodes per axis, 3..depth "
+                         "(on the band 3..depth - 1; 0 = depth - 2)")
     ap.add_argument("--mesh-density-trim", type=float, nargs="?", const=7.0, default=None, metavar="T",
                     help="after the surface (implied; --mesh-trim is then not applied): cut it where the smoothed sample-density value falls below T "
                          "(mesh.bat's SurfaceTrimmer --trim 7; 7 when given bare) on the GPU, before --mesh-clean")
@@ -147,6 +154,8 @@ def main(argv=None) -> int:
         args.mesh_color = True
     if args.mesh_color:
         args.mesh = True
+    if args.mesh_band_samples_per_node is not None and args.mesh_band is None:
+        args.mesh_band = 1
     if args.mesh_density_trim is not None or args.mesh_close_holes is not None or args.mesh_decimate is not None or args.mesh_samples_per_node is not None or \
             args.mesh_subdivide is not None or args.mesh_band is not None:
         args.mesh = True
@@ -227,7 +236,8 @@ def main(argv=None) -> int:
         t2 = time.perf_counter()
         try:
             mv, mf, mst = sink.mesh(depth=args.mesh_depth, trim_cells=args.mesh_trim if args.mesh_density_trim is None else 0,
-                                    samples_per_node=args.mesh_samples_per_node, kernel_depth=args.mesh_kernel_depth, band_bricks=args.mesh_band)
+                                    samples_per_node=args.mesh_samples_per_node, kernel_depth=args.mesh_kernel_depth, band_bricks=args.mesh_band,
+                                    band_samples_per_node=args.mesh_band_samples_per_node)
         except (RsmError, ValueError) as e:                        # e.g. --mesh-depth outside 5..9, --mesh-samples-per-node 0, --mesh-band with it
             print(e)
             return 1
@@ -271,9 +281,10 @@ def main(argv=None) -> int:
         else:
             print("Mesh time: %.3f s (%d cycles, residual %.2e%s)" % (time.perf_counter() - t2, mst["cycles"], mst["residual"],
                                                                       "" if mst["converged"] else ", NOT converged"))
-        if args.mesh_samples_per_node is not None:
+        spn = args.mesh_samples_per_node if args.mesh_band_samples_per_node is None else args.mesh_band_samples_per_node
+        if spn is not None:
             print("Mesh samples per node %g: density on 2^%d nodes, %d of %d samples spread below depth %d (least depth %.2f)"
-                  % (args.mesh_samples_per_node, mst["kernel_depth"], mst["n_below_depth"], mst["n_valid"], args.mesh_depth, mst["min_sample_depth"]))
+                  % (spn, mst["kernel_depth"], mst["n_below_depth"], mst["n_valid"], args.mesh_depth, mst["min_sample_depth"]))
         if tst is not None:
             print("Mesh density trim: %d faces from %d (%d split along %d cut edges); values %.2f .. %.2f; %d pieces moved to the kept side, %d to the dropped"
                   % (tst["n_faces"], tst["n_faces_in"], tst["faces_split"], tst["cut_edges"], tst["value_min"], tst["value_max"], tst["moved_to_kept"],

@@ -89,6 +89,7 @@ class PoissonBandParams(C.Structure):
 
 POISSON_BAND_STATS = 17
 POISSON_BAND_MAX_BRICKS = 1 << 20
+POISSON_BAND_WEIGHTED_STATS = 21   # RSM_POISSON_BAND_WEIGHTED_STATS
 
 
 class MeshCleanParams(C.Structure):
@@ -270,6 +271,9 @@ PROTOTYPES = {
     "rsm_poisson_mesh_banded": (_I, [_V, _V, _V, _L, _PSN, _PBD, _pL, _pL, _V]),
     "rsm_poisson_mesh_banded_device": (_I, [_V, _V, _V, _L, _PSN, _PBD, _pL, _pL, _V]),
     "rsm_stage_poisson_band_rhs": (_I, [_V, _V, _V, _L, _PSN, _PBD, _V, _L, _L, _V, _V, _V, _V, _V, _V]),
+    "rsm_poisson_mesh_banded_weighted": (_I, [_V, _V, _V, _L, _PSN, _PBD, _PDN, _pL, _pL, _V]),
+    "rsm_poisson_mesh_banded_weighted_device": (_I, [_V, _V, _V, _L, _PSN, _PBD, _PDN, _pL, _pL, _V]),
+    "rsm_stage_poisson_band_rhs_weighted": (_I, [_V, _V, _V, _L, _PSN, _PBD, _PDN, _V, _V, _L, _L, _V, _V, _V, _V, _V, _V, _V, _V, _V]),
     "rsm_stage_poisson_band_solve": (_I, [_V, _V, _L, _I, _V, _V, _V, _D, _I, _V, _pD, _pI, _pD, _V]),
     "rsm_stage_band_iso_mesh": (_I, [_V, _V, _L, _I, _V, _D, _V, _V, _I, _pL, _pL]),
     "rsm_write_ply_mesh": (_I, [_S, _V, _L, _V, _L]),

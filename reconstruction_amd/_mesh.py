@@ -194,6 +194,75 @@ class MeshPart(ContextBase):
         S = int(counts[2])
         return dict(grid=grid, bricks=bricks[:S].copy(), b=b[:S].copy(), occ=occ[:S].copy(), g=g[:S].copy(), counts=tuple(int(v) for v in counts), status=int(status))
 
+    # ---- the banded call with the density-adaptive splat: script1.mlx's OctDepth 10 and SamplesPerNode 3 (csrc/k_poisson_band_density.hip) ----
+    def _poisson_banded_weighted(self, fn, xyz, nrm, n, depth, scale, trim_cells, rel_residual, max_cycles, band_bricks, max_iterations, samples_per_node, kernel_depth):
+        nv, nf = C.c_int64(), C.c_int64()
+        st = (C.c_double * _lib.POISSON_BAND_WEIGHTED_STATS)()
+        prm = PoissonParams(int(depth), float(scale), float(rel_residual), int(max_cycles), int(trim_cells))
+        bpr = PoissonBandParams(int(band_bricks), int(max_iterations))
+        dpr = PoissonDensityParams(int(kernel_depth), float(samples_per_node))
+        status = fn(self._h, xyz, nrm, n, C.byref(prm), C.byref(bpr), C.byref(dpr), C.byref(nv), C.byref(nf), st)
+        if status < 0:
+            self._chk(status)
+        stats = dict(n_valid=int(st[0]), n_invalid=int(st[1]), residual=float(st[2]), iterations=int(st[3]), iso=float(st[4]),
+                     origin=(float(st[5]), float(st[6]), float(st[7])), h=float(st[8]), N=int(st[9]), n_vertices_untrimmed=int(st[10]),
+                     n_faces_untrimmed=int(st[11]), active_bricks=int(st[12]), occupied_bricks=int(st[13]), coarse_cycles=int(st[14]),
+                     coarse_residual=float(st[15]), residual_before=float(st[16]), kernel_depth=int(st[17]), min_sample_depth=float(st[18]),
+                     n_below_depth=int(st[19]), sum_w=float(st[20]), status=int(status), converged=status == 0)
+        return int(nv.value), int(nf.value), stats
+
+    def poisson_mesh_banded_weighted(self, xyz, normals, depth=10, scale=1.1, trim_cells=7, rel_residual=POISSON_REL_RESIDUAL, max_cycles=POISSON_MAX_CYCLES,
+                                     band_bricks=1, max_iterations=POISSON_BAND_MAX_ITERATIONS, samples_per_node=3.0, kernel_depth=0):
+        """poisson_mesh_banded with poisson_mesh_weighted's density-adaptive splat (script1.mlx: OctDepth 10 with SamplesPerNode 3): every
+        sample's density, weight and depth are the weighted call's at the finest depth; the levels below the finest are dense and reach the
+        band through their trilinear prolongation, the finest lives on the bricks, and the dense solve at depth - 1 is the weighted one.
+        kernel_depth is 0 (depth - 2) or 3..depth - 1.  Returns (vertices, faces, stats dict): poisson_mesh_banded's keys and kernel_depth,
+        min_sample_depth, n_below_depth (samples spread below the finest level) and sum_w."""
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        nrm = _normals4(normals, len(xyz))
+        nv, nf, stats = self._poisson_banded_weighted(self._lib.rsm_poisson_mesh_banded_weighted, _p(xyz), _p(nrm), len(xyz), depth, scale, trim_cells, rel_residual,
+                                                      max_cycles, band_bricks, max_iterations, samples_per_node, kernel_depth)
+        return self.poisson_last_mesh(nv, nf) + (stats,)
+
+    def poisson_mesh_banded_weighted_device(self, xyz_ptr, normals_ptr, n, depth=10, scale=1.1, trim_cells=7, rel_residual=POISSON_REL_RESIDUAL,
+                                            max_cycles=POISSON_MAX_CYCLES, band_bricks=1, max_iterations=POISSON_BAND_MAX_ITERATIONS, samples_per_node=3.0,
+                                            kernel_depth=0):
+        """rsm_poisson_mesh_banded_weighted_device on device buffers (addresses), as poisson_mesh_device: (n_vertices, n_faces, stats)."""
+        return self._poisson_banded_weighted(self._lib.rsm_poisson_mesh_banded_weighted_device, xyz_ptr, normals_ptr, n, depth, scale, trim_cells, rel_residual,
+                                             max_cycles, band_bricks, max_iterations, samples_per_node, kernel_depth)
+
+    def poisson_band_rhs_weighted(self, xyz, normals, depth, scale=1.1, band_bricks=1, samples_per_node=3.0, kernel_depth=0, depth_in=None, chi_c=None,
+                                  max_bricks=0, rel_residual=POISSON_REL_RESIDUAL, max_cycles=POISSON_MAX_CYCLES):
+        """Stage: poisson_band_rhs with the density-adaptive splat -> its dict (grid, bricks, b float64 [S,512], occ, g, counts, status) and
+        rho, w, d float64 [n].  depth_in (float64 [n]): every sample's depth from the caller.  chi_c None: the weighted dense solve at depth - 1."""
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        n = len(xyz)
+        nrm = _normals4(normals, n)
+        room = ((1 << int(depth)) >> 3) ** 3 if 6 <= int(depth) <= 10 else 1
+        room = min(room, _lib.POISSON_BAND_MAX_BRICKS if not max_bricks else int(max_bricks))
+        grid = np.zeros(4, np.float64)
+        bricks = np.zeros(max(room, 1), np.int32)
+        b = np.zeros((max(room, 1), 512), np.float64)
+        occ = np.zeros((max(room, 1), 512), np.uint8)
+        g = np.zeros((max(room, 1), 512), np.float32)
+        counts = np.zeros(4, np.int64)
+        rho, w, d = (np.zeros(max(n, 1), np.float64) for _ in range(3))
+        din = None if depth_in is None else np.ascontiguousarray(depth_in, np.float64).reshape(-1)
+        assert din is None or len(din) == n
+        cc = None if chi_c is None else np.ascontiguousarray(chi_c, np.float32)
+        assert cc is None or cc.shape == ((1 << int(depth)) >> 1,) * 3
+        prm = PoissonParams(int(depth), float(scale), float(rel_residual), int(max_cycles), 0)
+        bpr = PoissonBandParams(int(band_bricks), 1)
+        dpr = PoissonDensityParams(int(kernel_depth), float(samples_per_node))
+        status = self._lib.rsm_stage_poisson_band_rhs_weighted(self._h, _p(xyz), _p(nrm), n, C.byref(prm), C.byref(bpr), C.byref(dpr), None if din is None else _p(din),
+                                                               None if cc is None else _p(cc), int(max_bricks), room, _p(grid), _p(bricks), _p(b), _p(occ), _p(g),
+                                                               _p(counts), _p(rho), _p(w), _p(d))
+        if status < 0:
+            self._chk(status)
+        S = int(counts[2])
+        return dict(grid=grid, bricks=bricks[:S].copy(), b=b[:S].copy(), occ=occ[:S].copy(), g=g[:S].copy(), counts=tuple(int(v) for v in counts), status=int(status),
+                    rho=rho[:n].copy(), w=w[:n].copy(), d=d[:n].copy())
+
     def poisson_band_solve(self, bricks, depth, b, g, chi_c=None, rel_residual=POISSON_REL_RESIDUAL, max_iterations=POISSON_BAND_MAX_ITERATIONS):
         """Stage: b and g (brick-major [S,512], rounded to float32) on the bricks -> (chi float32 [S,512], residual reached, iterations, status
         0 / 1, residual per iteration, residual before the first).  chi_c (float32 [N/2]^3): gives the guess next to the band; None: 0 there."""

@@ -317,20 +317,27 @@ class CloudOptimization:
         return self.cloud_ms_normals
 
     def mesh(self, depth=9, scale=1.1, trim_cells=4, rel_residual=POISSON_REL_RESIDUAL, max_cycles=POISSON_MAX_CYCLES, samples_per_node=None,
-             kernel_depth=0, band_bricks=None, band_max_iterations=POISSON_BAND_MAX_ITERATIONS):
+             kernel_depth=0, band_bricks=None, band_max_iterations=POISSON_BAND_MAX_ITERATIONS, band_samples_per_node=None):
         """Where CCloudOptimization::run hands bigcloud.ply to the Poisson mesher (after :389): the surface of cloud_ms_normals, run()'s
         result, by the dense-grid Poisson reconstruction and trim on the GPU (Context.poisson_mesh).  run() keeps its result on the
         host, so the host entry point is used.  samples_per_node (mesh.bat: 2, script1.mlx: 3) selects the density-adaptive splat
         (Context.poisson_mesh_weighted; kernel_depth as there); None is the plain call.  band_bricks (1..4) selects the banded call
         (Context.poisson_mesh_banded; script1.mlx's OctDepth 10): depth is then the finest depth, 6..10, and trim_cells at most
-        8 band_bricks - 1; it does not combine with samples_per_node (ValueError).  Stores and returns (vertices float32 [nv,3],
-        faces int32 [nf,3], stats)."""
+        8 band_bricks - 1; it does not combine with samples_per_node (ValueError).  The density-adaptive splat on the band has a switch of its
+        own because that refusal stays as it is: band_samples_per_node (script1.mlx: 3) with band_bricks selects
+        Context.poisson_mesh_banded_weighted, with kernel_depth (0 or 3..depth - 1) passed through; without band_bricks it is a ValueError.
+        Stores and returns (vertices float32 [nv,3], faces int32 [nf,3], stats)."""
         if getattr(self, "cloud_ms_normals", None) is None:
             raise ValueError("CloudOptimization.mesh: run() first (it meshes run()'s smoothed, oriented cloud)")
         if band_bricks is not None and samples_per_node is not None:
             raise ValueError("CloudOptimization.mesh: band_bricks and samples_per_node do not combine (the density-adaptive splat is not built on the band)")
+        if band_samples_per_node is not None and band_bricks is None:
+            raise ValueError("CloudOptimization.mesh: band_samples_per_node needs band_bricks (without the band, samples_per_node selects the density-adaptive splat)")
         xyz, nrm = self.cloud_ms_normals[0], self.cloud_ms_normals[1]
-        if band_bricks is not None:
+        if band_bricks is not None and band_samples_per_node is not None:
+            self.mesh_result = self._ctx.poisson_mesh_banded_weighted(xyz, nrm, depth, scale, trim_cells, rel_residual, max_cycles, band_bricks, band_max_iterations,
+                                                                      band_samples_per_node, kernel_depth)
+        elif band_bricks is not None:
             self.mesh_result = self._ctx.poisson_mesh_banded(xyz, nrm, depth, scale, trim_cells, rel_residual, max_cycles, band_bricks, band_max_iterations)
         elif samples_per_node is None:
             self.mesh_result = self._ctx.poisson_mesh(xyz, nrm, depth, scale, trim_cells, rel_residual, max_cycles)

@@ -18,44 +18,15 @@
 #include "rsm_dev.h"
 #include "mesh_common.h"
 #include "poisson_common.h"
+#include "poisson_band_common.h"
 
 #include <math.h>
 
-#define PB_NODES 512 // nodes of a brick
 // the band solve ends after this many iterations in a row without a new best residual (twice the longest such run of the
 // restatement's float32 histories before their floor)
 #define PB_STALL 20
 
 namespace {
-
-struct PbBand { // what a kernel needs of a PoissonBand
-    const int32_t *slot, *active, *nbr;
-    int sh, bsh, N; // N = 1 << sh nodes, 1 << bsh bricks per axis
-};
-
-// the slot of the brick that holds node (i, j, k): -1 inactive, -2 outside the grid
-__device__ __forceinline__ int pb_slot_of(const PbBand &B, int i, int j, int k) {
-    if ((unsigned)i >= (unsigned)B.N || (unsigned)j >= (unsigned)B.N || (unsigned)k >= (unsigned)B.N) return -2;
-    return B.slot[(size_t)(i >> 3) + (((size_t)(j >> 3) + ((size_t)(k >> 3) << B.bsh)) << B.bsh)];
-}
-__device__ __forceinline__ int pb_local(int i, int j, int k) { return (i & 7) + 8 * ((j & 7) + 8 * (k & 7)); }
-// ... and the node's element, or the negative slot
-__device__ __forceinline__ long long pb_elem_of(const PbBand &B, int i, int j, int k) {
-    const int s = pb_slot_of(B, i, j, k);
-    return s < 0 ? (long long)s : (long long)s * PB_NODES + pb_local(i, j, k);
-}
-// from a slot's 27 neighbour slots nb[(cx + 1) + 3 ((cy + 1) + 3 (cz + 1))]: the element of its node at local (x, y, z), each in -1 .. 8
-__device__ __forceinline__ long long pb_node(const int32_t *nb, int x, int y, int z) {
-    const int s = nb[((x >> 3) + 1) + 3 * (((y >> 3) + 1) + 3 * ((z >> 3) + 1))];
-    return s < 0 ? (long long)s : (long long)s * PB_NODES + pb_local(x, y, z);
-}
-// the grid coordinates of a slot's node 0
-__device__ __forceinline__ void pb_origin(const PbBand &B, int slot, int o[3]) {
-    const int b = B.active[slot], m = (1 << B.bsh) - 1;
-    o[0] = (b & m) << 3;
-    o[1] = ((b >> B.bsh) & m) << 3;
-    o[2] = (b >> (2 * B.bsh)) << 3;
-}
 
 // ---- bricks ---------------------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_pb_mark(const float *__restrict__ xyz, const float *__restrict__ nrm, int64_t n, PvGrid g, int bsh,
@@ -454,10 +425,6 @@ __global__ __launch_bounds__(256) void k_pb_dilate_cells(const uint8_t *__restri
     out[a] = m;
 }
 
-static PvGrid pb_grid(const double grid[4], int depth) { return PvGrid{grid[0], grid[1], grid[2], grid[3], depth, 1 << depth}; }
-static PbBand pb_band(const PoissonBand &b) { return PbBand{b.d_slot, b.d_active, b.d_nbr, b.depth, b.depth - 3, 1 << b.depth}; }
-static inline size_t pb_nodes(const PoissonBand &b) { return (size_t)b.n_active * PB_NODES; }
-
 } // namespace
 
 void poisson_band_free(PoissonBand *b) {
@@ -610,6 +577,11 @@ int poisson_band_solve_device(const PoissonBand &band, const float *d_b, const f
     return *residual <= rel_residual ? RSM_OK : RSM_W_NOT_CONVERGED;
 }
 
+void poisson_band_chi_at_samples(const PoissonBand &band, const float *d_xyz, const float *d_nrm4, int64_t n, const float *d_chi, const double grid[4], double *d_val,
+                                 hipStream_t st) {
+    hipLaunchKernelGGL(k_pb_chi_at_samples, blocks_for((size_t)n), dim3(256), 0, st, d_xyz, d_nrm4, n, pb_grid(grid, band.depth), pb_band(band), d_chi, d_val);
+}
+
 int poisson_band_iso_device(const PoissonBand &band, const float *d_xyz, const float *d_nrm4, int64_t n, int64_t n_valid, const float *d_chi,
                             const double grid[4], double *iso, hipStream_t st) {
     *iso = 0.0;
@@ -617,7 +589,7 @@ int poisson_band_iso_device(const PoissonBand &band, const float *d_xyz, const f
     DevMem M;
     double *val = M.get<double>((size_t)n), *part = M.get<double>(POISSON_SUM_PARTIALS), *scal = M.get<double>(1);
     if (!M.ok) return RSM_E_NOMEM;
-    hipLaunchKernelGGL(k_pb_chi_at_samples, blocks_for((size_t)n), dim3(256), 0, st, d_xyz, d_nrm4, n, pb_grid(grid, band.depth), pb_band(band), d_chi, val);
+    poisson_band_chi_at_samples(band, d_xyz, d_nrm4, n, d_chi, grid, val, st);
     poisson_tree_sum(val, n, part, scal, st);
     double sum = 0.0;
     DEVCHK(hipMemcpyAsync(&sum, scal, sizeof sum, hipMemcpyDeviceToHost, st));

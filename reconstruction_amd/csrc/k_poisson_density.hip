@@ -14,25 +14,24 @@
 //                prolongation, x then y then z, 0.75 near + 0.25 far, 0 outside                                         k_pd_cascade
 //   rhs          f7's central differences of U_depth in fp64, rounded once to float for the solver                     k_pd_rhs
 //   iso          sum w_s chi(p_s) / sum w_s: f7's chi at the samples (poisson_chi_at_samples) times w_s, both sums in f7's tree   k_pd_mul
-// The levels share one buffer of 64-bit words: level L's three components start at word 3 (8^L - 8^3) / 7.
+// The levels share one buffer of 64-bit words: level L's three components start at word 3 (8^L - 8^3) / 7.  The buffer's top level and the
+// finest depth are two numbers: the banded call (k_poisson_band_density.hip; f17) keeps the levels 3..depth - 1 here and the finest on its bricks.
 // No float atomics.  Built with -ffp-contract=off (csrc/Makefile): every fp64 expression below is evaluated as written.
 #include "../../include/rsm.h"
 #include "rsm_dev.h"
 #include "mesh_common.h"
+#include "poisson_density_common.h"
 
 #include <math.h>
 #include <string.h>
-
-#define PD_FIX 4294967296.0 // 2^32: the splat's fixed-point scale, f7's
-#define PD_LMIN 3           // the coarsest level a sample is spread on
 
 namespace {
 
 typedef unsigned long long u64;
 
-struct PdBox { // f7's box: the origin, the finest step, the finest level
+struct PdBox { // f7's box: the origin, the finest step, the finest level, the buffer's top level (<= depth)
     double ox, oy, oz, h;
-    int depth;
+    int depth, top;
 };
 __host__ __device__ __forceinline__ size_t pd_level_nodes(int L) { return (size_t)1 << (3 * L); }
 __host__ __device__ __forceinline__ size_t pd_level_word(int L) { return 3 * ((pd_level_nodes(L) - pd_level_nodes(PD_LMIN)) / 7); }
@@ -77,7 +76,7 @@ __global__ __launch_bounds__(256) void k_pd_sample(const float *__restrict__ xyz
     }
 }
 
-// ---- 4: the level splat ---------------------------------------------------------------------------------------------------------------
+// ---- 4: the level splat on the levels 3..box.top (occ may be NULL) -------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_pd_splat(const float *__restrict__ xyz, const float *__restrict__ nrm, int64_t n, PdBox box,
                                                   const double *__restrict__ w, const double *__restrict__ d, u64 *__restrict__ V,
                                                   uint8_t *__restrict__ occ) {
@@ -86,7 +85,7 @@ __global__ __launch_bounds__(256) void k_pd_splat(const float *__restrict__ xyz,
     double p[3], nh[3];
     if (!pv_valid(xyz, nrm, s, p, nh)) return;
     const int depth = box.depth;
-    { // occ: f7's cell on the finest level, clamped to the grid
+    if (occ) { // occ: f7's cell on the finest level, clamped to the grid
         const double o[3] = {box.ox, box.oy, box.oz};
         const int N = 1 << depth;
         size_t c[3];
@@ -96,15 +95,13 @@ __global__ __launch_bounds__(256) void k_pd_splat(const float *__restrict__ xyz,
         }
         occ[c[0] + (size_t)N * (c[1] + (size_t)N * c[2])] = 1;
     }
-    const double ws = w[s], ds = d[s];
-    const double fld = floor(ds);
-    int lo = ds >= (double)PD_LMIN ? (int)fld : PD_LMIN; // (k_pd_sample clamped d_s; the tests here keep the level inside the buffer whatever d holds)
-    lo = lo > depth ? depth : lo;
-    const double fr = ds - fld;
+    const double ws = w[s];
+    int lo;
+    const double fr = pd_split(d[s], depth, &lo);
     for (int t = 0; t < 2; t++) {
         const int L = lo + t;
-        if (L > depth) break;
-        const double alpha = t ? fr * ws : (1.0 - fr) * ws;
+        if (L > box.top) break; // (top <= depth: the levels above the buffer's top are another unit's)
+        const double alpha = pd_alpha(fr, ws, t);
         const MtGrid g = pd_level_grid(box, L);
         double fl[3], f[3];
         int i0[3];
@@ -181,30 +178,19 @@ __global__ __launch_bounds__(256) void k_pd_mul(double *__restrict__ x, const do
 
 } // namespace
 
-int poisson_density_rhs_device(const float *d_xyz, const float *d_nrm4, int64_t n, int depth, const double grid[4], int kernel_depth, double samples_per_node,
-                               const double *d_depth_in, float *d_b32, double *d_b64, uint8_t *d_occ, double *d_rho, double *d_w, double *d_d,
-                               double sample_stats[3], hipStream_t st) {
+int poisson_density_samples_device(const float *d_xyz, const float *d_nrm4, int64_t n, int depth, const double grid[4], int kernel_depth, double samples_per_node,
+                                   const double *d_depth_in, double *d_rho, double *d_w, double *d_d, double sample_stats[3], hipStream_t st) {
     sample_stats[0] = sample_stats[1] = sample_stats[2] = 0.0;
-    const size_t N3 = pd_level_nodes(depth), words = pd_level_word(depth + 1);
     DevMem M;
-    u64 *V = M.get<u64>(words), *ctr = M.get<u64>(2);
+    u64 *ctr = M.get<u64>(2);
     double *val = M.get<double>((size_t)n), *part = M.get<double>(POISSON_SUM_PARTIALS), *scal = M.get<double>(1);
     if (!M.ok) return RSM_E_NOMEM;
     const u64 init[2] = {~0ull, 0ull};
     DEVCHK(hipMemcpyAsync(ctr, init, sizeof init, hipMemcpyHostToDevice, st));
-    DEVCHK(hipMemsetAsync(V, 0, words * sizeof(u64), st));
-    DEVCHK(hipMemsetAsync(d_occ, 0, N3, st));
     // the density at the samples' own positions: they are float xyz of stride 3, as a mesh's vertices are
     int s = density_at_points_device(M, d_xyz, d_nrm4, n, depth, grid, kernel_depth, samples_per_node, d_xyz, n, d_rho, val, st);
     if (s != RSM_OK) return s;
     hipLaunchKernelGGL(k_pd_sample, blocks_for((size_t)n), dim3(256), 0, st, d_xyz, d_nrm4, n, depth, d_depth_in, (const double *)val, d_rho, d_w, d_d, ctr);
-    const PdBox box{grid[0], grid[1], grid[2], grid[3], depth};
-    hipLaunchKernelGGL(k_pd_splat, blocks_for((size_t)n), dim3(256), 0, st, d_xyz, d_nrm4, n, box, (const double *)d_w, (const double *)d_d, V, d_occ);
-    for (int L = PD_LMIN; L <= depth; L++) {
-        const double *coarse = L > PD_LMIN ? (const double *)(V + pd_level_word(L - 1)) : nullptr;
-        hipLaunchKernelGGL(k_pd_cascade, dim3(blocks_for(pd_level_nodes(L)).x, 3), dim3(256), 0, st, V + pd_level_word(L), coarse, L, ldexp(1.0, 3 * (L - depth)));
-    }
-    hipLaunchKernelGGL(k_pd_rhs, blocks_for(N3), dim3(256), 0, st, (const double *)(V + pd_level_word(depth)), depth, d_b32, d_b64);
     poisson_tree_sum(d_w, n, part, scal, st);
     u64 h[2] = {0, 0};
     double sum_w = 0.0;
@@ -218,20 +204,62 @@ int poisson_density_rhs_device(const float *d_xyz, const float *d_nrm4, int64_t 
     return RSM_OK;
 }
 
+size_t poisson_density_level_words(int top) { return pd_level_word(top + 1); }
+
+int poisson_density_levels_device(const float *d_xyz, const float *d_nrm4, int64_t n, int depth, int top, const double grid[4], const double *d_w, const double *d_d,
+                                  unsigned long long *d_V, uint8_t *d_occ, const double **d_U_top, hipStream_t st) {
+    DEVCHK(hipMemsetAsync(d_V, 0, pd_level_word(top + 1) * sizeof(u64), st));
+    if (d_occ) DEVCHK(hipMemsetAsync(d_occ, 0, pd_level_nodes(depth), st));
+    const PdBox box{grid[0], grid[1], grid[2], grid[3], depth, top};
+    hipLaunchKernelGGL(k_pd_splat, blocks_for((size_t)n), dim3(256), 0, st, d_xyz, d_nrm4, n, box, d_w, d_d, d_V, d_occ);
+    for (int L = PD_LMIN; L <= top; L++) {
+        const double *coarse = L > PD_LMIN ? (const double *)(d_V + pd_level_word(L - 1)) : nullptr;
+        hipLaunchKernelGGL(k_pd_cascade, dim3(blocks_for(pd_level_nodes(L)).x, 3), dim3(256), 0, st, d_V + pd_level_word(L), coarse, L, ldexp(1.0, 3 * (L - depth)));
+    }
+    *d_U_top = (const double *)(d_V + pd_level_word(top));
+    return RSM_OK;
+}
+
+void poisson_density_rhs_of_field(const double *d_U, int depth, float *d_b32, double *d_b64, hipStream_t st) {
+    hipLaunchKernelGGL(k_pd_rhs, blocks_for(pd_level_nodes(depth)), dim3(256), 0, st, d_U, depth, d_b32, d_b64);
+}
+
+int poisson_density_rhs_device(const float *d_xyz, const float *d_nrm4, int64_t n, int depth, const double grid[4], int kernel_depth, double samples_per_node,
+                               const double *d_depth_in, float *d_b32, double *d_b64, uint8_t *d_occ, double *d_rho, double *d_w, double *d_d,
+                               double sample_stats[3], hipStream_t st) {
+    sample_stats[0] = sample_stats[1] = sample_stats[2] = 0.0;
+    DevMem M; // (all of the call's level buffer before its first launch)
+    u64 *V = M.get<u64>(pd_level_word(depth + 1));
+    if (!M.ok) return RSM_E_NOMEM;
+    int s = poisson_density_samples_device(d_xyz, d_nrm4, n, depth, grid, kernel_depth, samples_per_node, d_depth_in, d_rho, d_w, d_d, sample_stats, st);
+    if (s != RSM_OK) return s;
+    const double *U = nullptr;
+    if ((s = poisson_density_levels_device(d_xyz, d_nrm4, n, depth, depth, grid, d_w, d_d, V, d_occ, &U, st)) != RSM_OK) return s;
+    poisson_density_rhs_of_field(U, depth, d_b32, d_b64, st);
+    return mesh_finish(st);
+}
+
+int poisson_weighted_mean_device(double *d_val, const double *d_w, int64_t n, double sum_w, double *mean, hipStream_t st) {
+    DevMem M;
+    double *part = M.get<double>(POISSON_SUM_PARTIALS), *scal = M.get<double>(1);
+    if (!M.ok) return RSM_E_NOMEM;
+    hipLaunchKernelGGL(k_pd_mul, blocks_for((size_t)n), dim3(256), 0, st, d_val, d_w, n);
+    poisson_tree_sum(d_val, n, part, scal, st);
+    double sum = 0.0;
+    DEVCHK(hipMemcpyAsync(&sum, scal, sizeof sum, hipMemcpyDeviceToHost, st));
+    DEVCHK(hipStreamSynchronize(st));
+    DEVCHK(hipGetLastError());
+    *mean = sum / sum_w;
+    return RSM_OK;
+}
+
 int poisson_iso_weighted_device(const float *d_xyz, const float *d_nrm4, int64_t n, const double *d_w, double sum_w, const float *d_chi, int depth,
                                 const double grid[4], double *iso, hipStream_t st) {
     *iso = 0.0;
     if (n <= 0 || !(sum_w > 0.0)) return RSM_OK;
     DevMem M;
-    double *val = M.get<double>((size_t)n), *part = M.get<double>(POISSON_SUM_PARTIALS), *scal = M.get<double>(1);
+    double *val = M.get<double>((size_t)n);
     if (!M.ok) return RSM_E_NOMEM;
     poisson_chi_at_samples(d_xyz, d_nrm4, n, d_chi, depth, grid, val, st);
-    hipLaunchKernelGGL(k_pd_mul, blocks_for((size_t)n), dim3(256), 0, st, val, d_w, n);
-    poisson_tree_sum(val, n, part, scal, st);
-    double sum = 0.0;
-    DEVCHK(hipMemcpyAsync(&sum, scal, sizeof sum, hipMemcpyDeviceToHost, st));
-    DEVCHK(hipStreamSynchronize(st));
-    DEVCHK(hipGetLastError());
-    *iso = sum / sum_w;
-    return RSM_OK;
+    return poisson_weighted_mean_device(val, d_w, n, sum_w, iso, st);
 }

@@ -296,6 +296,21 @@ int poisson_extract_device(const float *d_chi, int depth, double iso, const doub
 int poisson_density_rhs_device(const float *d_xyz, const float *d_nrm4, int64_t n, int depth, const double grid[4], int kernel_depth, double samples_per_node,
                                const double *d_depth_in, float *d_b32, double *d_b64, uint8_t *d_occ, double *d_rho, double *d_w, double *d_d,
                                double sample_stats[3], hipStream_t st);
+// ... in its parts, for the banded call with this splat (k_poisson_band_density.hip; f17), which keeps the finest level on its bricks:
+// items 2 and 3 alone: d_rho, d_w, d_d and sample_stats as above
+int poisson_density_samples_device(const float *d_xyz, const float *d_nrm4, int64_t n, int depth, const double grid[4], int kernel_depth, double samples_per_node,
+                                   const double *d_depth_in, double *d_rho, double *d_w, double *d_d, double sample_stats[3], hipStream_t st);
+// the 64-bit words of a level buffer whose top level is `top`
+size_t poisson_density_level_words(int top);
+// items 4 and 5 on the levels 3..top (top <= depth) of the grid whose finest level is `depth` with step grid[3]: d_d is clamped to depth, what
+// falls on a level above top is left out, the scales are 8^(L - depth).  d_V: poisson_density_level_words(top) words, zeroed here; *d_U_top:
+// the top level's three components in it, fp64.  d_occ (2^(3 depth) bytes) may be NULL.  Enqueues only.
+int poisson_density_levels_device(const float *d_xyz, const float *d_nrm4, int64_t n, int depth, int top, const double grid[4], const double *d_w, const double *d_d,
+                                  unsigned long long *d_V, uint8_t *d_occ, const double **d_U_top, hipStream_t st);
+// item 6 of a field d_U of three components on 2^depth nodes per axis.  Enqueues only.
+void poisson_density_rhs_of_field(const double *d_U, int depth, float *d_b32, double *d_b64, hipStream_t st);
+// sum w_s val_s / sum_w in f7's tree; d_val (n doubles) is overwritten
+int poisson_weighted_mean_device(double *d_val, const double *d_w, int64_t n, double sum_w, double *mean, hipStream_t st);
 // iso = sum w_s chi(p_s) / sum_w over the samples (sum_w = sample_stats[2])
 int poisson_iso_weighted_device(const float *d_xyz, const float *d_nrm4, int64_t n, const double *d_w, double sum_w, const float *d_chi, int depth,
                                 const double grid[4], double *iso, hipStream_t st);
@@ -329,6 +344,18 @@ int poisson_band_iso_device(const PoissonBand &band, const float *d_xyz, const f
                             const double grid[4], double *iso, hipStream_t st);
 int poisson_band_extract_device(const PoissonBand &band, const float *d_chi, double iso, const double grid[4], const uint8_t *d_occ, int trim_cells,
                                 PoissonMesh *out, int64_t untrimmed[2], hipStream_t st);
+// chi's trilinear interpolation at the n samples on the band (0 at the samples that take no part) -> d_val, n doubles.  Enqueues only.
+void poisson_band_chi_at_samples(const PoissonBand &band, const float *d_xyz, const float *d_nrm4, int64_t n, const float *d_chi, const double grid[4], double *d_val,
+                                 hipStream_t st);
+
+// the banded finest level with the density-adaptive splat (k_poisson_band_density.hip).  d_w, d_d: poisson_density_samples_device's
+// at the finest depth.  d_levels: poisson_density_level_words(band.depth - 1) words of scratch (the levels 3..depth - 1, dense).  d_b32 / d_b64
+// (either may be NULL) and d_occ (per fine cell), brick-major
+int poisson_band_density_rhs_device(const PoissonBand &band, const float *d_xyz, const float *d_nrm4, int64_t n, const double grid[4], const double *d_w,
+                                    const double *d_d, unsigned long long *d_levels, float *d_b32, double *d_b64, uint8_t *d_occ, hipStream_t st);
+// iso = sum w_s chi(p_s) / sum_w with chi on the band
+int poisson_band_iso_weighted_device(const PoissonBand &band, const float *d_xyz, const float *d_nrm4, int64_t n, const double *d_w, double sum_w, const float *d_chi,
+                                     const double grid[4], double *iso, hipStream_t st);
 
 // smoothing and clean-up of a triangle mesh (k_meshclean.hip).  Device buffers: nv float xyz, nf int32 x 3.  RSM_E_INVALID
 // comes with *invalid = 1 (a face index outside [0, nv)) or 2 (a coordinate that is not finite); parameters are the caller's to check.
