@@ -973,6 +973,47 @@ int rsm_stage_mesh_stitch_rhs(rsm_ctx *ctx, const float *xyz, int64_t nv, const 
 int rsm_stage_mesh_stitch_solve(rsm_ctx *ctx, const int32_t *faces, int64_t nv, int64_t nf, const int32_t *best_view, const uint8_t *rgb, const double *G,
                                 double lambda, int iterations, double *x, double *rel_residual);
 
+/* ---- the vertices no view sees filled from the colours around them (TextureStitcher's mesh is coloured everywhere) --------
+ * Run after rsm_mesh_color or rsm_mesh_stitch, on their rgb and best_view.  A vertex is known when best_view >= 0 (the sign alone counts),
+ * else unknown.  The incidences of a vertex are its corner list's, as in rsm_mesh_stitch, but to every neighbour, known or not.
+ * Front: round r = 1, 2, ... gives every unknown vertex without a level that has incidences to vertices of level < r (known: 0) the mean of
+ * their values, in order, and the level r; it stops after the first round that reaches nothing, or after max_rounds rounds.  L = the largest
+ * level.  The vertices it reached are the filled ones; the others (a component without a known vertex, or beyond max_rounds) keep their
+ * bytes.  System, per channel over the filled vertices: sum_j (x_i - x_j) = 0 over the incidences to known (fixed) and filled neighbours.
+ * Solver: rsm_mesh_stitch's Chebyshev iteration from the front's values on the interval [lmin, 2], lmin = 1 / (2 (L + 1))^2: `iterations`
+ * steps, or with iterations = 0 the least k with T_k(sigma) >= 1 / reduction.  Filled bytes = clamp(floor(x + 0.5), 0, 255); known bytes
+ * and best_view are untouched (a filled vertex keeps best_view -1).
+ * The rounds go out RSM_MESH_FILL_ROUND_BATCH at a time; between two batches the largest level is read back.  A round that reaches nothing
+ * is a no-op, so the result does not depend on that number (the front stage takes another one to show it). */
+typedef struct rsm_mesh_fill_params {
+    int max_rounds;     /* >= 0; 0 = until a round reaches nothing */
+    int iterations;     /* 0 .. 1000000; 0 = from reduction */
+    double reduction;   /* in (0, 1), used when iterations = 0 (1e-4) */
+} rsm_mesh_fill_params;
+#define RSM_MESH_FILL_MAX_ITERATIONS 1000000
+#define RSM_MESH_FILL_ROUND_BATCH 16
+/* stats: [0] vertices, [1] known, [2] filled, [3] unreached, [4] rounds L, [5] kept incidences of the filled vertices, [6] the largest of
+ * their counts, [7] steps run, [8] values clamped, [9] the largest |x - x_front| over the filled vertices */
+#define RSM_MESH_FILL_STATS 10
+/* host buffers: faces nf*3 int32, rgb nv*3 bytes in and out, best_view nv int32 in, level nv int32 out (may be NULL): 0 known, 1 .. L filled,
+ * -1 unreached.  An empty mesh, no unknown vertex, no known vertex: the input's bytes, RSM_OK.  RSM_E_INVALID (rsm_last_error names the
+ * cause): a NULL pointer, a face index outside [0, nv), 3 nf >= 2^31, nv above INT32_MAX, a negative count, max_rounds < 0, iterations
+ * outside 0 .. 1000000, reduction outside (0, 1) when it is used (or one that needs more than 1000000 steps). */
+int rsm_mesh_fill_colors(rsm_ctx *ctx, const int32_t *faces, int64_t nv, int64_t nf, uint8_t *rgb, const int32_t *best_view, int32_t *level,
+                         const rsm_mesh_fill_params *p, double *stats);
+/* the same on DEVICE buffers (faces, rgb, best_view, level) */
+int rsm_mesh_fill_colors_device(rsm_ctx *ctx, const int32_t *d_faces, int64_t nv, int64_t nf, uint8_t *d_rgb, const int32_t *d_best_view, int32_t *d_level,
+                                const rsm_mesh_fill_params *p, double *stats);
+/* the same on the context's last mesh and the colours rsm_mesh_color_last / rsm_mesh_stitch_last left with it (RSM_E_STATE when it has
+ * none); rsm_mesh_last_colors then copies out the filled bytes and the unchanged best views */
+int rsm_mesh_fill_colors_last(rsm_ctx *ctx, const rsm_mesh_fill_params *p, double *stats);
+/* stage entry points (host buffers) for the tests.  front: rgb, best_view -> x nv*3 doubles (the bytes as doubles where the front wrote
+ * nothing), level nv int32 (as above), *rounds = L; round_batch: 0 (RSM_MESH_FILL_ROUND_BATCH) or 1 .. 1024 rounds between two read-backs.  solve: `iterations` (0 .. 1000000, taken as given) steps from a caller's x, level
+ * (0 known, 1 .. L filled, anything else unreached) and L >= 0 -> x (in and out; only filled rows change). */
+int rsm_stage_mesh_fill_front(rsm_ctx *ctx, const int32_t *faces, int64_t nv, int64_t nf, const uint8_t *rgb, const int32_t *best_view, int max_rounds, int round_batch,
+                              double *x, int32_t *level, int *rounds);
+int rsm_stage_mesh_fill_solve(rsm_ctx *ctx, const int32_t *faces, int64_t nv, int64_t nf, const int32_t *level, int L, int iterations, double *x);
+
 /* ---- kernel microbenchmark (MDE/s: pixel x candidate NCC evaluations) -------------------- */
 /* Runs the NCC interval-argmax kernel `iters` times on a resident level-sized problem with
  * `cands` candidates per pixel and returns average milliseconds per launch. */

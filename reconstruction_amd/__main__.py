@@ -5,7 +5,7 @@
                                [--mesh-clean [--mesh-smooth 5] [--mesh-min-piece 10%]] [--mesh-close-holes [30]] [--mesh-decimate [100000]]
                                [--mesh-subdivide [3] [--mesh-subdivide-threshold 1]]
                                [--mesh-color [--mesh-color-mode blend] [--mesh-color-min-cos 0.2] [--mesh-color-eps LENGTH]]
-                               [--mesh-stitch [--mesh-stitch-lambda 0.01] [--mesh-stitch-iterations 0]]]
+                               [--mesh-stitch [--mesh-stitch-lambda 0.01] [--mesh-stitch-iterations 0]] [--mesh-color-fill [ROUNDS]]]
 
 The command-line shape of the reference's main() (reconstruction/main.cpp:5-23) for the part this package covers:
 CReconstrction::Init (configuration + calibration, CReconstruction.cpp:5-19) -> CStereoMatching::MatchAllLayer
@@ -39,6 +39,9 @@ CCloudOptimization::run calls TextureStitcher (visibility by a depth buffer per 
 f9): the coloured mesh goes to the configuration's outfilename, where TextureStitcher's --out goes, and the cloud PLY to <name>_cloud.ply.
 With --mesh-stitch (implies --mesh-color) the vertices take their best view's colour and the views' exposure seams are levelled on the
 GPU by a screened gradient-domain solve on the mesh graph, TextureStitcher's seam removal; the same PLY at outfilename.
+With --mesh-color-fill (implies --mesh-color) the vertices no view sees, grey after the colouring, are filled on the GPU with the harmonic
+extension of the colours around them on the mesh graph, after --mesh-stitch when both are given: all of them that are
+connected to a coloured vertex, or with ROUNDS those within that many edges of one; the same PLY at outfilename.
 The rest of CCloudOptimization::run (main.cpp:19) is outside this package: feed bigcloud.ply or bigmesh.ply to it.
 Needs an MI355X; there is no CPU path.
 """
@@ -149,8 +152,12 @@ def main(argv=None) -> int:
                     help="with --mesh-stitch: the pull towards the views' colours; a view's offset decays over about 1/sqrt(lambda) edges")
     ap.add_argument("--mesh-stitch-iterations", type=int, default=0,
                     help="with --mesh-stitch: Chebyshev steps (0: as many as reduce the error to 1e-4 of the start's)")
+    ap.add_argument("--mesh-color-fill", type=int, nargs="?", const=0, default=None, metavar="ROUNDS",
+                    help="implies --mesh-color (after --mesh-stitch when given): fill the vertices no view sees from the colours around them on the "
+                         "GPU (the harmonic extension on the mesh graph): every one connected to a coloured vertex when given bare, else those within "
+                         "ROUNDS edges of one.  The same PLY at outfilename")
     args = ap.parse_args(argv)
-    if args.mesh_stitch:
+    if args.mesh_stitch or args.mesh_color_fill is not None:
         args.mesh_color = True
     if args.mesh_color:
         args.mesh = True
@@ -316,7 +323,9 @@ def main(argv=None) -> int:
                 else:
                     rgb, _, kst = sink.color_mesh(mode=1 if args.mesh_color_mode == "blend" else 0, min_cos=args.mesh_color_min_cos,
                                                   depth_eps=args.mesh_color_eps)
-            except (RsmError, ValueError) as e:                    # pre-rectified input (no P), --mesh-color-min-cos outside [-1, 1), a lambda <= 0
+                if args.mesh_color_fill is not None:
+                    rgb, _, fst = sink.fill_mesh_colors(max_rounds=args.mesh_color_fill)
+            except (RsmError, ValueError) as e:                    # pre-rectified input (no P), --mesh-color-min-cos outside [-1, 1), a lambda <= 0, ROUNDS < 0
                 print(e)
                 return 1
             write_ply_mesh(color_out, mv, mf, rgb)
@@ -324,9 +333,13 @@ def main(argv=None) -> int:
                 print("Mesh stitch: %d of %d vertices coloured from %d views, %d of %d incidences across a seam, %d steps (residual %.2e), largest "
                       "change %.2f levels -> %s" % (sst["coloured"], sst["n_vertices"], 2 * len(data.cam), sst["seam_incidences"], sst["incidences"],
                                                     sst["steps"], sst["rel_residual"], sst["max_change"], color_out))
-                return 0
-            print("Mesh colour: %d of %d vertices coloured from %d views (%d without a normal) -> %s"
-                  % (kst["coloured"], kst["n_vertices"], 2 * len(data.cam), kst["no_normal"], color_out))
+            else:
+                print("Mesh colour: %d of %d vertices coloured from %d views (%d without a normal) -> %s"
+                      % (kst["coloured"], kst["n_vertices"], 2 * len(data.cam), kst["no_normal"], color_out))
+            if args.mesh_color_fill is not None:
+                print("Mesh colour fill: %d of %d uncoloured vertices filled in %d rounds, %d left as they were, %d steps, largest change from the "
+                      "front's means %.2f levels -> %s" % (fst["filled"], fst["filled"] + fst["unreached"], fst["rounds"], fst["unreached"], fst["steps"],
+                                                           fst["max_change"], color_out))
     return 0
 
 

@@ -154,6 +154,14 @@ class MeshStitchParams(C.Structure):
 MESH_STITCH_STATS = 12
 
 
+class MeshFillParams(C.Structure):
+    """rsm_mesh_fill_params (include/rsm.h)."""
+    _fields_ = [("max_rounds", C.c_int), ("iterations", C.c_int), ("reduction", C.c_double)]
+
+
+MESH_FILL_STATS = 10
+
+
 class DedupView(C.Structure):
     """rsm_dedup_view (include/rsm.h): one pair of the rig for the duplicate deletion (host pointers)."""
     _fields_ = [("P", (C.c_double * 12) * 2), ("cam_center", C.c_float * 3), ("bound0", Boundary), ("width", C.c_int),
@@ -180,7 +188,7 @@ _pI, _pL, _pD = C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_double)
 _PIN, _POUT, _BND, _RIN, _ROUT, _FLT = (C.POINTER(t) for t in (PairIn, PairOut, Boundary, RectifyIn, RectifyOut, FilterParams))
 _MLS, _VIEW, _PSN, _CLN, _COL, _STI = (C.POINTER(t) for t in (MlsParams, DedupView, PoissonParams, MeshCleanParams, MeshColorParams, MeshStitchParams))
 _TRM, _CLO, _DEC, _PDN = C.POINTER(MeshTrimParams), C.POINTER(MeshCloseParams), C.POINTER(MeshDecimateParams), C.POINTER(PoissonDensityParams)
-_SUB, _PBD = C.POINTER(MeshSubdivideParams), C.POINTER(PoissonBandParams)
+_SUB, _PBD, _FIL = C.POINTER(MeshSubdivideParams), C.POINTER(PoissonBandParams), C.POINTER(MeshFillParams)
 PROTOTYPES = {
     "rsm_create": (_I, [_V, _I]),
     "rsm_destroy": (None, [_V]),
@@ -316,6 +324,11 @@ PROTOTYPES = {
     "rsm_stage_mesh_visibility": (_I, [_V, _V, _L, _V, _L, _VIEW, _I, _COL, _V]),
     "rsm_stage_mesh_stitch_rhs": (_I, [_V, _V, _L, _V, _L, _VIEW, _I, _V, _V, _V, _I, _V, _V, _V]),
     "rsm_stage_mesh_stitch_solve": (_I, [_V, _V, _L, _L, _V, _V, _V, _D, _I, _V, _pD]),
+    "rsm_mesh_fill_colors": (_I, [_V, _V, _L, _L, _V, _V, _V, _FIL, _V]),
+    "rsm_mesh_fill_colors_device": (_I, [_V, _V, _L, _L, _V, _V, _V, _FIL, _V]),
+    "rsm_mesh_fill_colors_last": (_I, [_V, _FIL, _V]),
+    "rsm_stage_mesh_fill_front": (_I, [_V, _V, _L, _L, _V, _V, _I, _I, _V, _V, _pI]),
+    "rsm_stage_mesh_fill_solve": (_I, [_V, _V, _L, _L, _V, _I, _I, _V]),
     "rsm_bench_ncc": (_I, [_V, _I, _I, _I, _I, _I, _V]),
 }
 EXPORTS = list(PROTOTYPES)   # every symbol include/rsm.h declares

@@ -6,7 +6,7 @@ import numpy as np
 
 from . import _lib
 from ._context import ContextBase, _normals4, _p, _u8, _views
-from ._lib import MeshCleanParams, MeshCloseParams, MeshColorParams, MeshDecimateParams, MeshStitchParams, MeshSubdivideParams, MeshTrimParams, PoissonBandParams, PoissonDensityParams, PoissonParams
+from ._lib import MeshCleanParams, MeshCloseParams, MeshColorParams, MeshDecimateParams, MeshFillParams, MeshStitchParams, MeshSubdivideParams, MeshTrimParams, PoissonBandParams, PoissonDensityParams, PoissonParams
 
 # the solve's default stopping residual: one decade above the 4.2e-6 the float32 solver reaches at depth 9
 POISSON_REL_RESIDUAL = 4e-5
@@ -787,6 +787,77 @@ class MeshPart(ContextBase):
         rel = C.c_double()
         self._chk(self._lib.rsm_stage_mesh_stitch_solve(self._h, _p(f), n, len(f), _p(b), _p(c), _p(g), float(lam), int(iterations), _p(x), C.byref(rel)))
         return x[:n].copy(), float(rel.value)
+
+    # ---- the vertices no view sees filled from the colours around them (csrc/k_meshfill.hip) ----
+    _FILL_KEYS = ("n_vertices", "known", "filled", "unreached", "rounds", "incidences", "dmax", "steps", "clamped")
+
+    def _mesh_fill(self, fn, args, max_rounds, iterations, reduction):
+        """One of the three rsm_mesh_fill_colors* entries: the stats."""
+        st = (C.c_double * _lib.MESH_FILL_STATS)()
+        prm = MeshFillParams(int(max_rounds), int(iterations), float(reduction))
+        self._chk(fn(self._h, *args, C.byref(prm), st))
+        stats = {k: int(st[i]) for i, k in enumerate(self._FILL_KEYS)}
+        stats.update(max_change=float(st[9]))
+        return stats
+
+    def mesh_fill_colors(self, faces, rgb, best_view, max_rounds=0, iterations=0, reduction=1e-4):
+        """The colours of a mesh (mesh_color's or mesh_stitch's rgb uint8 [nv,3] and best_view int32 [nv]) with every uncoloured vertex
+        (best_view < 0) that is connected to a coloured one filled by the harmonic extension of the colours around it on the mesh graph
+        (DESIGN.md 9 f18): a front of means gives the start and each vertex's level (its distance in edges from the coloured ones, at most
+        max_rounds when that is > 0), `iterations` Chebyshev steps -- or with 0 as many as bring the error down to `reduction` of the
+        start's -- solve the system.  Coloured vertices keep their bytes.  Returns (rgb uint8 [nv,3], level int32 [nv]: 0 coloured,
+        1 .. rounds filled, -1 left as it was; stats dict)."""
+        f = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+        b = np.ascontiguousarray(best_view, np.int32).reshape(-1)
+        n = len(b)
+        c = np.array(rgb, np.uint8).reshape(-1, 3)
+        assert len(c) == n
+        c = np.ascontiguousarray(np.concatenate([c, np.zeros((1, 3), np.uint8)]))
+        level = np.zeros(max(n, 1), np.int32)
+        stats = self._mesh_fill(self._lib.rsm_mesh_fill_colors, (_p(f), n, len(f), _p(c), _p(b), _p(level)), max_rounds, iterations, reduction)
+        return c[:n].copy(), level[:n].copy(), stats
+
+    def mesh_fill_colors_device(self, faces_ptr, n_vertices, n_faces, rgb_ptr, best_view_ptr, level_ptr=0, max_rounds=0, iterations=0, reduction=1e-4):
+        """rsm_mesh_fill_colors_device on device buffers (addresses; rgb in and out; level_ptr may be 0).  Returns stats."""
+        return self._mesh_fill(self._lib.rsm_mesh_fill_colors_device, (faces_ptr, n_vertices, n_faces, rgb_ptr, best_view_ptr, level_ptr or None), max_rounds,
+                               iterations, reduction)
+
+    def mesh_fill_colors_last(self, max_rounds=0, iterations=0, reduction=1e-4):
+        """mesh_fill_colors of the context's last mesh and the colours mesh_color_last / mesh_stitch_last left with it, where they lie on
+        the device (RsmError RSM_E_STATE when it has none).  Returns (rgb, best_view, stats): best_view is unchanged, a filled vertex
+        keeps -1."""
+        stats = self._mesh_fill(self._lib.rsm_mesh_fill_colors_last, (), max_rounds, iterations, reduction)
+        nv = stats["n_vertices"]
+        rgb = np.zeros((max(nv, 1), 3), np.uint8)
+        best = np.zeros(max(nv, 1), np.int32)
+        self._chk(self._lib.rsm_mesh_last_colors(self._h, _p(rgb), _p(best)))
+        return rgb[:nv].copy(), best[:nv].copy(), stats
+
+    def mesh_fill_front(self, faces, rgb, best_view, max_rounds=0, round_batch=0):
+        """Stage: the front alone -> (x float64 [nv,3]: the bytes as doubles where it wrote nothing, level int32 [nv]: -1 unreached, L).
+        round_batch: the rounds launched between two read-backs of the largest level (0: the library's 16); the result does not depend on it."""
+        f = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+        b = np.ascontiguousarray(best_view, np.int32).reshape(-1)
+        n = len(b)
+        c = np.ascontiguousarray(rgb, np.uint8).reshape(-1, 3)
+        assert len(c) == n
+        x = np.zeros((max(n, 1), 3), np.float64)
+        level = np.zeros(max(n, 1), np.int32)
+        L = C.c_int()
+        self._chk(self._lib.rsm_stage_mesh_fill_front(self._h, _p(f), n, len(f), _p(c), _p(b), int(max_rounds), int(round_batch), _p(x), _p(level), C.byref(L)))
+        return x[:n].copy(), level[:n].copy(), int(L.value)
+
+    def mesh_fill_solve(self, faces, x, level, L, iterations):
+        """Stage: `iterations` Chebyshev steps from a caller's x float64 [nv,3], level (0 known, 1 .. L filled, anything else unreached)
+        and L -> x float64 [nv,3]; only filled rows change."""
+        f = np.ascontiguousarray(faces, np.int32).reshape(-1, 3)
+        lv = np.ascontiguousarray(level, np.int32).reshape(-1)
+        n = len(lv)
+        xx = np.array(x, np.float64).reshape(-1, 3)
+        assert len(xx) == n
+        xx = np.ascontiguousarray(np.concatenate([xx, np.zeros((1, 3))]))
+        self._chk(self._lib.rsm_stage_mesh_fill_solve(self._h, _p(f), n, len(f), _p(lv), int(L), int(iterations), _p(xx)))
+        return xx[:n].copy()
 
     def texture_color(self, xyz, P, image):
         """Stage: texture_color (CCloudOptimization.cpp:400-421) of xyz [n,3] float32 against one view (P 3x4, image BGR uint8 [H,W,3]):

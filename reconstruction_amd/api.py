@@ -255,7 +255,7 @@ class CloudOptimization:
     decimate_mesh() (decimation.mlx: the mesh thinned to a face count by quadric edge collapses, on the GPU),
     subdivide_mesh() (subdiv.mlx: the mesh refined by Loop subdivision, Loop's own weights, on the GPU),
     color_mesh() (where run() ends with TextureStitcher: the mesh's vertices coloured from every camera's rectified image, on the
-    GPU), stitch_mesh() (the tool's seam removal: the views' exposure seams levelled in those colours, on the GPU).  `cloud_normals` accumulates what the
+    GPU), stitch_mesh() (the tool's seam removal: the views' exposure seams levelled in those colours, on the GPU), fill_mesh_colors() (the vertices no view saw filled from the colours around them, on the GPU).  `cloud_normals` accumulates what the
     reference's global `*cloud_normals += *cloud_normal` (:123) does: per pair (xyz float32 [m,3], normals float32 [m,4])."""
 
     def __init__(self, ctx: Context | None = None, device: int = 0):
@@ -436,4 +436,15 @@ class CloudOptimization:
         if depth_eps is None:
             depth_eps = 2.0 * self.mesh_grid_step
         self.mesh_colors = self._ctx.mesh_stitch_last(cams, depth_eps, min_cos, lam, iterations, reduction, seam_gradient)
+        return self.mesh_colors
+
+    def fill_mesh_colors(self, max_rounds=0, iterations=0, reduction=1e-4):
+        """After color_mesh() or stitch_mesh(): TextureStitcher hands back a mesh that is coloured everywhere, so every vertex no view saw
+        ((127, 127, 127), best_view -1) that is connected to a coloured one takes the harmonic extension of the colours around it on the
+        mesh graph (Context.mesh_fill_colors_last on the colours left with the context).  max_rounds > 0 fills only the
+        vertices within that many edges of a coloured one.  Coloured vertices keep their bytes and best_view is unchanged: a filled
+        vertex keeps -1.  Stores and returns mesh_colors = (rgb uint8 [nv,3], best_view int32 [nv], stats)."""
+        if getattr(self, "mesh_colors", None) is None:
+            raise ValueError("CloudOptimization.fill_mesh_colors: color_mesh() or stitch_mesh() first (it fills their uncoloured vertices)")
+        self.mesh_colors = self._ctx.mesh_fill_colors_last(max_rounds, iterations, reduction)
         return self.mesh_colors

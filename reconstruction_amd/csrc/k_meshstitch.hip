@@ -281,17 +281,10 @@ int solve(DevMem &M, size_t nv, const int32_t *d_best, const uint8_t *d_rgb, con
     if (!M.ok) return RSM_E_NOMEM;
     hipLaunchKernelGGL(k_mst_init, blocks_for(3 * nv), dim3(256), 0, st, nv, d_best, d_rgb, d_G, lambda, xa, d, b);
     // the eigenvalues of M^-1 A lie in [lmin, 2]
-    const double lmin = lambda / ((double)dmax + lambda);
-    const double theta = (2.0 + lmin) / 2.0, delta = (2.0 - lmin) / 2.0, sigma = theta / delta;
-    double rho = 1.0 / sigma;
+    ChebSchedule cheb(lambda / ((double)dmax + lambda));
     for (int k = 0; k < steps; k++) {
-        double alpha = 0.0, beta = 1.0 / theta;
-        if (k >= 1) {
-            const double rn = 1.0 / (2.0 * sigma - rho);
-            alpha = rn * rho;
-            beta = (2.0 * rn) / delta;
-            rho = rn;
-        }
+        double alpha, beta;
+        cheb.step(k, &alpha, &beta);
         hipLaunchKernelGGL(k_mst_step, blocks_for(nv), dim3(256), 0, st, nv, row, (const uint32_t *)c.deg, (const uint32_t *)c.nbr, (const double *)xa,
                            (const double *)b, d, xb, lambda, alpha, beta);
         double *t = xa;
@@ -317,19 +310,7 @@ int solve(DevMem &M, size_t nv, const int32_t *d_best, const uint8_t *d_rgb, con
 } // namespace
 
 int mesh_stitch_steps(double lambda, unsigned long long dmax, double reduction) {
-    const double lmin = lambda / ((double)dmax + lambda);
-    const double theta = (2.0 + lmin) / 2.0, delta = (2.0 - lmin) / 2.0, sigma = theta / delta;
-    const double target = 1.0 / reduction;
-    double t0 = 1.0, t1 = sigma; // T_0, T_1; T_k+1 = 2 sigma T_k - T_k-1
-    int k = 1;
-    while (t1 < target) {
-        if (k == RSM_MESH_STITCH_MAX_ITERATIONS) return -1;
-        const double t2 = (2.0 * sigma) * t1 - t0;
-        t0 = t1;
-        t1 = t2;
-        k++;
-    }
-    return k;
+    return cheb_steps(lambda / ((double)dmax + lambda), reduction, RSM_MESH_STITCH_MAX_ITERATIONS);
 }
 
 int mesh_visibility_device(const float *d_v, int64_t nv, const int32_t *d_f, int64_t nf, const rsm_dedup_view *views, int n_pairs, const rsm_mesh_color_params *p,

@@ -7,7 +7,7 @@
 //   value         rho = the same weights times C 2^-32, eight fp64 terms in the corner order dz, dy, dx; value = max(0, kernel_depth +
 //                 1/2 log2(rho / samples_per_node))                                                                  k_mt_value
 //   smoothing     neighbour CSR in the order of mesh_common.h's corner lists (as k_mst_csr), one gather launch per step, values ping-pong, no host
-//                 synchronisation inside the loop                                                                   k_mt_csr, k_mt_step
+//                 synchronisation inside the loop                                                                   k_mesh_nbr_csr, k_mt_step
 //   split         the first entry of a run of mesh_common.h's sorted edge table whose ends lie on different sides of `trim` is a cut edge; its rank
 //                 among them (a scan) numbers its vertex; faces count 0 / 1 / 3 triangles, scan, emit               k_mt_cut_flags .. k_mt_face_emit
 //   islands       the edge table of the split mesh, union-find per side, areas as 64-bit fixed point (llrint(area 2^32 / D^2) <= 2^31 per
@@ -92,19 +92,7 @@ __global__ __launch_bounds__(256) void k_mt_value(const float *__restrict__ v, s
 }
 
 // ---- 4: smoothing of the values ---------------------------------------------------------------------------------------------------------
-// row i of the neighbour CSR starts at 2 row[i] (a corner gives two) and holds deg[i] = 2 (row[i + 1] - row[i]) entries
-__global__ __launch_bounds__(256) void k_mt_csr(size_t nv, const int32_t *__restrict__ f, const uint32_t *__restrict__ row, const uint32_t *__restrict__ corner,
-                                                uint32_t *__restrict__ nbr) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= nv) return;
-    for (uint32_t r = row[i]; r < row[i + 1]; r++) {
-        const uint32_t c = corner[r];
-        const size_t fi = c / 3;
-        const uint32_t j = c % 3;
-        nbr[2 * (size_t)r] = (uint32_t)f[3 * fi + (j + 1) % 3];
-        nbr[2 * (size_t)r + 1] = (uint32_t)f[3 * fi + (j + 2) % 3];
-    }
-}
+// the neighbour CSR is mesh_common.h's (k_mesh_nbr_csr): row i starts at 2 row[i] and holds deg[i] = 2 (row[i + 1] - row[i]) entries
 __global__ __launch_bounds__(256) void k_mt_step(const double *__restrict__ in, double *__restrict__ out, size_t nv, const uint32_t *__restrict__ row,
                                                  const uint32_t *__restrict__ nbr) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -396,7 +384,7 @@ static int smooth_values(DevMem &M, const int32_t *d_f, size_t nv, size_t nf, co
     uint32_t *nbr = M.get<uint32_t>(6 * nf);
     double *buf[2] = {M.get<double>(nv), M.get<double>(nv)};
     if (!M.ok) return RSM_E_NOMEM;
-    hipLaunchKernelGGL(k_mt_csr, blocks_for(nv), dim3(256), 0, st, nv, d_f, (const uint32_t *)row, (const uint32_t *)corner, nbr);
+    hipLaunchKernelGGL(k_mesh_nbr_csr<>, blocks_for(nv), dim3(256), 0, st, nv, d_f, (const uint32_t *)row, (const uint32_t *)corner, nbr);
     const double *src = d_in;
     for (int it = 0; it < steps; it++) {
         double *dst = buf[it & 1];

@@ -1,7 +1,7 @@
 // mesh_common.h -- the mesh units' topology layer, beyond dev_prims.h: what the surface (k_poisson.hip), its smoothing / clean-up
 // (k_meshclean.hip), its density trim (k_meshtrim.hip), the closing of its holes (k_meshclose.hip), its decimation (k_meshdecimate.hip), its subdivision
-// (k_meshsubdivide.hip) and its colours (k_meshcolor.hip, k_meshstitch.hip) share.  The scratch of one call; the sorted edge table and the corner lists of a mesh,
-// built from any allocator (dev_prims.h: DevMem and Pool here); the union-find over the table; the vertex box and its
+// (k_meshsubdivide.hip) and its colours (k_meshcolor.hip, k_meshstitch.hip, k_meshfill.hip) share.  The scratch of one call; the sorted edge table and the corner lists of a mesh,
+// built from any allocator (dev_prims.h: DevMem and Pool here); the neighbour CSR over the corner lists; the Chebyshev schedule; the union-find over the table; the vertex box and its
 // diagonal; a point in fp64; the end of a call that replaces a mesh.  What a stage does with the table's runs stays in its own unit.
 // The kernels are templates for the reason dev_prims.h gives: only a unit that launches one (k_mesh_edge_keys<>) holds a copy.
 #pragma once
@@ -187,6 +187,58 @@ static int mesh_corner_lists(Alloc &M, const int32_t *d_f, size_t nv, size_t nf,
     }
     hipLaunchKernelGGL(k_mesh_row_starts<>, blocks_for(nv + 1), dim3(256), 0, st, (const uint32_t *)k1, n, nv, *row);
     return RSM_OK;
+}
+
+// ---- the neighbour CSR over the corner lists (k_meshtrim.hip's value smoothing, k_meshfill.hip) -----------------------------------------------
+// row i starts at 2 row[i] (a corner gives two: f[(j+1)%3] then f[(j+2)%3]) and holds 2 (row[i + 1] - row[i]) entries: every neighbour,
+// an interior edge twice, a border edge once
+template <int = 0>
+__global__ __launch_bounds__(256) void k_mesh_nbr_csr(size_t nv, const int32_t *__restrict__ f, const uint32_t *__restrict__ row, const uint32_t *__restrict__ corner,
+                                                      uint32_t *__restrict__ nbr) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= nv) return;
+    for (uint32_t r = row[i]; r < row[i + 1]; r++) {
+        const uint32_t c = corner[r];
+        const size_t fi = c / 3;
+        const uint32_t j = c % 3;
+        nbr[2 * (size_t)r] = (uint32_t)f[3 * fi + (j + 1) % 3];
+        nbr[2 * (size_t)r + 1] = (uint32_t)f[3 * fi + (j + 2) % 3];
+    }
+}
+
+// ---- the Chebyshev iteration's schedule on the host (k_meshstitch.hip, k_meshfill.hip) ---------------------------------------
+// the eigenvalues of the Jacobi-preconditioned matrix lie in [lmin, 2]; step k = 0, 1, ... in order: d = alpha d + beta z
+struct ChebSchedule {
+    double theta, delta, sigma, rho;
+    explicit ChebSchedule(double lmin) : theta((2.0 + lmin) / 2.0), delta((2.0 - lmin) / 2.0) {
+        sigma = theta / delta;
+        rho = 1.0 / sigma;
+    }
+    void step(int k, double *alpha, double *beta) {
+        *alpha = 0.0;
+        *beta = 1.0 / theta;
+        if (k >= 1) {
+            const double rn = 1.0 / (2.0 * sigma - rho);
+            *alpha = rn * rho;
+            *beta = (2.0 * rn) / delta;
+            rho = rn;
+        }
+    }
+};
+// the least k >= 1 with T_k(sigma) >= 1 / reduction, T_k+1 = 2 sigma T_k - T_k-1; -1: more than max_steps
+static inline int cheb_steps(double lmin, double reduction, int max_steps) {
+    const double sigma = ChebSchedule(lmin).sigma;
+    const double target = 1.0 / reduction;
+    double t0 = 1.0, t1 = sigma;
+    int k = 1;
+    while (t1 < target) {
+        if (k == max_steps) return -1;
+        const double t2 = (2.0 * sigma) * t1 - t0;
+        t0 = t1;
+        t1 = t2;
+        k++;
+    }
+    return k;
 }
 
 // ---- the box of the vertices: mm[0 .. 5] = min x, y, z, max x, y, z as ordered uints (dev_prims.h), preset to ~0 / 0 ---------------------------

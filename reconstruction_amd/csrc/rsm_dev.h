@@ -457,3 +457,17 @@ int mesh_stitch_rhs_device(const float *d_v, int64_t nv, const int32_t *d_f, int
                            hipStream_t st);
 int mesh_stitch_solve_device(const int32_t *d_f, int64_t nv, int64_t nf, const int32_t *d_best, const uint8_t *d_rgb, const double *d_G, double lambda,
                              int iterations, double *d_x, double *rel_residual, int *invalid, hipStream_t st);
+
+// the vertices no view sees filled from the colours around them (k_meshfill.hip).  Device buffers: d_rgb nv x 3 bytes in
+// and out, d_best nv int32, d_level nv int32 out (-1 unreached; may be NULL in mesh_fill_device); batch = the rounds between two read-backs;
+// stats = RSM_MESH_FILL_STATS doubles (may be NULL).  RSM_E_INVALID comes with *invalid = 1 (a face index outside [0, nv)) or 4 (the
+// reduction needs more than RSM_MESH_FILL_MAX_ITERATIONS steps); the parameters are the caller's to check.
+struct rsm_mesh_fill_params;
+int mesh_fill_device(const int32_t *d_f, int64_t nv, int64_t nf, const int32_t *d_best, uint8_t *d_rgb, int32_t *d_level, const rsm_mesh_fill_params *p, int batch,
+                     double *stats, int *invalid, hipStream_t st);
+// the least k with T_k(sigma) >= 1 / reduction at lmin = 1 / (2 (L + 1))^2; -1: more than RSM_MESH_FILL_MAX_ITERATIONS
+int mesh_fill_steps(int L, double reduction);
+// the stages: the front alone -> d_x nv x 3 doubles, d_level, *L; `iterations` steps from a caller's d_x (in and out), d_level and L
+int mesh_fill_front_device(const int32_t *d_f, int64_t nv, int64_t nf, const int32_t *d_best, const uint8_t *d_rgb, int max_rounds, int batch, double *d_x,
+                           int32_t *d_level, int *L, int *invalid, hipStream_t st);
+int mesh_fill_solve_device(const int32_t *d_f, int64_t nv, int64_t nf, const int32_t *d_level, int L, int iterations, double *d_x, int *invalid, hipStream_t st);

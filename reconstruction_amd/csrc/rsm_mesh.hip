@@ -1,6 +1,6 @@
 // rsm_mesh.hip -- the mesh back end's host side: the dense-grid Poisson surface, its smoothing and clean-up, its density trim, the closing of
-// its holes, its decimation, its subdivision, and its colours from the rig's views with their seams levelled (k_poisson.hip, k_poisson_density.hip, k_poisson_band.hip, k_poisson_band_density.hip, k_meshclean.hip, k_meshtrim.hip,
-// k_meshclose.hip, k_meshdecimate.hip, k_meshsubdivide.hip, k_meshcolor.hip, k_meshstitch.hip).
+// its holes, its decimation, its subdivision, and its colours from the rig's views with their seams levelled and their gaps filled (k_poisson.hip, k_poisson_density.hip, k_poisson_band.hip, k_poisson_band_density.hip, k_meshclean.hip, k_meshtrim.hip,
+// k_meshclose.hip, k_meshdecimate.hip, k_meshsubdivide.hip, k_meshcolor.hip, k_meshstitch.hip, k_meshfill.hip).
 #include "rsm_ctx.h"
 
 #include <cmath>
@@ -1501,5 +1501,106 @@ extern "C" int rsm_stage_mesh_stitch_solve(rsm_ctx *c, const int32_t *faces, int
     int invalid = 0;
     if ((s = mesh_stitch_solve_device(df, nv, nf, db, dc, dG, lambda, iterations, dx, rel_residual, &invalid, c->stream)) != RSM_OK) return meshcolor_fail(c, s, invalid);
     T.later(x, dx, 3 * (size_t)nv);
+    return finish(c, T);
+}
+
+// ---- the vertices no view sees filled from the colours around them (k_meshfill.hip) -------------------------------------
+static int meshfill_params_ok(rsm_ctx *c, const rsm_mesh_fill_params *p) {
+    if (!p) return set_err(c, RSM_E_INVALID, "mesh_fill: params is NULL");
+    if (p->max_rounds < 0) return set_err(c, RSM_E_INVALID, "mesh_fill: max_rounds %d < 0", p->max_rounds);
+    if (p->iterations < 0 || p->iterations > RSM_MESH_FILL_MAX_ITERATIONS)
+        return set_err(c, RSM_E_INVALID, "mesh_fill: iterations %d outside 0..%d", p->iterations, RSM_MESH_FILL_MAX_ITERATIONS);
+    if (p->iterations == 0 && !(p->reduction > 0.0 && p->reduction < 1.0)) return set_err(c, RSM_E_INVALID, "mesh_fill: reduction %g not in (0, 1)", p->reduction);
+    return RSM_OK;
+}
+static int meshfill_fail(rsm_ctx *c, int s, int invalid) {
+    if (s == RSM_E_INVALID && invalid == 4)
+        return set_err(c, s, "mesh_fill: reduction needs more than %d steps on a front this deep (give iterations)", RSM_MESH_FILL_MAX_ITERATIONS);
+    if (s == RSM_E_INVALID) return set_err(c, s, "mesh_fill: a face index outside [0, nv)");
+    return set_err(c, s, "mesh_fill: failed%s", hip_tail(s).c_str());
+}
+
+extern "C" int rsm_mesh_fill_colors_device(rsm_ctx *c, const int32_t *d_faces, int64_t nv, int64_t nf, uint8_t *d_rgb, const int32_t *d_best_view, int32_t *d_level,
+                                           const rsm_mesh_fill_params *p, double *stats) {
+    if (!c) return RSM_E_INVALID;
+    int s = meshfill_params_ok(c, p);
+    if (s != RSM_OK || (s = mesh_counts_ok(c, "mesh_fill", nv, nf)) != RSM_OK) return s;
+    if ((nv > 0 && (!d_rgb || !d_best_view)) || (nf > 0 && !d_faces)) return set_err(c, RSM_E_INVALID, "mesh_fill: a NULL pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    int invalid = 0;
+    s = mesh_fill_device(d_faces, nv, nf, d_best_view, d_rgb, d_level, p, RSM_MESH_FILL_ROUND_BATCH, stats, &invalid, c->stream);
+    return s == RSM_OK ? RSM_OK : meshfill_fail(c, s, invalid);
+}
+
+extern "C" int rsm_mesh_fill_colors(rsm_ctx *c, const int32_t *faces, int64_t nv, int64_t nf, uint8_t *rgb, const int32_t *best_view, int32_t *level,
+                                    const rsm_mesh_fill_params *p, double *stats) {
+    if (!c) return RSM_E_INVALID;
+    int s = meshfill_params_ok(c, p);
+    if (s != RSM_OK || (s = mesh_counts_ok(c, "mesh_fill", nv, nf)) != RSM_OK) return s;
+    if ((nv > 0 && (!rgb || !best_view)) || (nf > 0 && !faces)) return set_err(c, RSM_E_INVALID, "mesh_fill: a NULL pointer");
+    HIPCHK(c, hipSetDevice(c->device));
+    Tmp T(c);
+    int32_t *df = T.up(faces, 3 * (size_t)nf), *db = T.up(best_view, (size_t)nv), *dl = T.alloc<int32_t>((size_t)nv);
+    uint8_t *dc = T.up((const uint8_t *)rgb, 3 * (size_t)nv);
+    if (!df || !db || !dl || !dc) return set_err(c, RSM_E_NOMEM, "mesh_fill: no device memory for %lld vertices, %lld faces", (long long)nv, (long long)nf);
+    if ((s = finish(c, T)) != RSM_OK) return s;
+    int invalid = 0;
+    s = mesh_fill_device(df, nv, nf, db, dc, dl, p, RSM_MESH_FILL_ROUND_BATCH, stats, &invalid, c->stream);
+    if (s != RSM_OK) return meshfill_fail(c, s, invalid);
+    T.later(rgb, (const uint8_t *)dc, 3 * (size_t)nv).later(level, (const int32_t *)dl, (size_t)nv);
+    return finish(c, T);
+}
+
+extern "C" int rsm_mesh_fill_colors_last(rsm_ctx *c, const rsm_mesh_fill_params *p, double *stats) {
+    if (!c) return RSM_E_INVALID;
+    int s = meshfill_params_ok(c, p);
+    if (s != RSM_OK) return s;
+    if (!c->mcol_rgb || !c->mcol_best || !c->mcol_valid)
+        return set_err(c, RSM_E_STATE, "mesh_fill: the context's last mesh has no colours (rsm_mesh_color_last or rsm_mesh_stitch_last first)");
+    HIPCHK(c, hipSetDevice(c->device));
+    int invalid = 0;
+    s = mesh_fill_device(c->pmesh.d_f, c->pmesh.nv, c->pmesh.nf, c->mcol_best, c->mcol_rgb, nullptr, p, RSM_MESH_FILL_ROUND_BATCH, stats, &invalid, c->stream);
+    return s == RSM_OK ? RSM_OK : meshfill_fail(c, s, invalid);
+}
+
+extern "C" int rsm_stage_mesh_fill_front(rsm_ctx *c, const int32_t *faces, int64_t nv, int64_t nf, const uint8_t *rgb, const int32_t *best_view, int max_rounds,
+                                         int round_batch, double *x, int32_t *level, int *rounds) {
+    if (!c) return RSM_E_INVALID;
+    int s = mesh_counts_ok(c, "mesh_fill", nv, nf);
+    if (s != RSM_OK) return s;
+    if (!rounds || (nv > 0 && (!rgb || !best_view || !x || !level)) || (nf > 0 && !faces)) return set_err(c, RSM_E_INVALID, "mesh_fill: a NULL pointer");
+    if (max_rounds < 0) return set_err(c, RSM_E_INVALID, "mesh_fill: max_rounds %d < 0", max_rounds);
+    if (round_batch < 0 || round_batch > 1024) return set_err(c, RSM_E_INVALID, "mesh_fill: round_batch %d outside 0..1024", round_batch);
+    HIPCHK(c, hipSetDevice(c->device));
+    Tmp T(c);
+    int32_t *df = T.up(faces, 3 * (size_t)nf), *db = T.up(best_view, (size_t)nv), *dl = T.alloc<int32_t>((size_t)nv);
+    uint8_t *dc = T.up(rgb, 3 * (size_t)nv);
+    double *dx = T.alloc<double>(3 * (size_t)nv);
+    if (!df || !db || !dl || !dc || !dx) return set_err(c, RSM_E_NOMEM, "mesh_fill: no device memory");
+    if ((s = finish(c, T)) != RSM_OK) return s;
+    int invalid = 0;
+    if ((s = mesh_fill_front_device(df, nv, nf, db, dc, max_rounds, round_batch ? round_batch : RSM_MESH_FILL_ROUND_BATCH, dx, dl, rounds, &invalid, c->stream)) != RSM_OK)
+        return meshfill_fail(c, s, invalid);
+    T.later(x, (const double *)dx, 3 * (size_t)nv).later(level, (const int32_t *)dl, (size_t)nv);
+    return finish(c, T);
+}
+
+extern "C" int rsm_stage_mesh_fill_solve(rsm_ctx *c, const int32_t *faces, int64_t nv, int64_t nf, const int32_t *level, int L, int iterations, double *x) {
+    if (!c) return RSM_E_INVALID;
+    int s = mesh_counts_ok(c, "mesh_fill", nv, nf);
+    if (s != RSM_OK) return s;
+    if ((nv > 0 && (!level || !x)) || (nf > 0 && !faces)) return set_err(c, RSM_E_INVALID, "mesh_fill: a NULL pointer");
+    if (L < 0) return set_err(c, RSM_E_INVALID, "mesh_fill: L %d < 0", L);
+    if (iterations < 0 || iterations > RSM_MESH_FILL_MAX_ITERATIONS)
+        return set_err(c, RSM_E_INVALID, "mesh_fill: iterations %d outside 0..%d", iterations, RSM_MESH_FILL_MAX_ITERATIONS);
+    HIPCHK(c, hipSetDevice(c->device));
+    Tmp T(c);
+    int32_t *df = T.up(faces, 3 * (size_t)nf), *dl = T.up(level, (size_t)nv);
+    double *dx = T.up((const double *)x, 3 * (size_t)nv);
+    if (!df || !dl || !dx) return set_err(c, RSM_E_NOMEM, "mesh_fill: no device memory");
+    if ((s = finish(c, T)) != RSM_OK) return s;
+    int invalid = 0;
+    if ((s = mesh_fill_solve_device(df, nv, nf, dl, L, iterations, dx, &invalid, c->stream)) != RSM_OK) return meshfill_fail(c, s, invalid);
+    T.later(x, (const double *)dx, 3 * (size_t)nv);
     return finish(c, T);
 }
