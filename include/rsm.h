@@ -484,6 +484,33 @@ int rsm_stage_filter_depth_map(rsm_ctx *ctx, const double *disp, const uint8_t *
  * the surviving points and their oriented normals (the reference's cloud_normal, :110-121).  h_normals may be NULL. */
 int rsm_filter_last_cloud_host(rsm_ctx *ctx, const rsm_filter_params *params, rsm_point16 *h_points, float *h_normals,
                                int64_t max_points, int64_t *n_kept, double *stats);
+/* The radius outlier pass of CCloudOptimization::filter, pcl::RadiusOutlierRemoval between cloud_after_1step and cloud_filtered
+ * (CCloudOptimization.cpp:90-96; the shipped reference has the block commented out, its Init and its tunings carry the two values).
+ * rsm_filter_params cannot grow, so the pass is a setting of the context: it applies to rsm_filter_cloud, rsm_filter_last_cloud[_host]
+ * and rsm_stage_filter_depth_map alike until it is changed.  p = NULL switches it off (the default: every entry then returns what it
+ * returned without this function).  With S = the survivors of the StatisticalOutlierRemoval in their order and S_f its finite points,
+ *   count(p) = #{ q in S_f : (dx dx + dy dy) + dz dz < r2 } in float32,  r2 = (float)(radius * radius);
+ * the point itself counts (radiusSearch returns the query), coincident points count once each, a non-finite p has count 0; p stays iff
+ * count(p) > min_neighbors (PCL 1.7.2's applyFilterIndices as published; parity unpinned).  min_neighbors = 0 removes exactly the
+ * non-finite points.  kept_index, the points and *n_kept are then the survivors of both passes, the normals are computed on that cloud,
+ * stats stay the first pass's, rsm_filter_last_info's info[3] is the final count; everything removed is n_kept = 0 and RSM_OK.
+ * RSM_E_INVALID (rsm_last_error names the cause): min_neighbors < 0; a radius that is not finite or not positive, whose float32 square
+ * is 0 or infinite, or whose float32 value is 0 (the search grid's cell edge). */
+typedef struct rsm_outrem_params {
+    int min_neighbors;     /* m_outrem_neighbor (CReconstruction.cpp:18: 50) */
+    double radius;         /* m_outrem_radius (2) */
+} rsm_outrem_params;
+int rsm_filter_set_outrem(rsm_ctx *ctx, const rsm_outrem_params *p);
+/* What that pass did in the last filter call of this context: info[0] = points in (the first pass's survivors), -1 when the pass was
+ * off; info[1] = points removed; info[2] = the pixel window (radius) the count ran over on the cloud's pixel lattice, 0 when it ran on
+ * a grid of radius-cells (the lattice serves while the k-nearest pass's copy is still there, "filter_normals_window" allows windows and
+ * no point needs a wider one for the larger of this radius and normal_radius; the normals then take the same route); info[3] = the
+ * non-finite points among the removed. */
+int rsm_filter_last_outrem(rsm_ctx *ctx, int64_t info[4]);
+/* Stage entry for the tests: the pass's count alone, on host buffers, over the whole cloud as S, by the grid route's kernel with its
+ * early stop made visible: count[i] = min(count(p_i), cap), cap >= 1 (INT32_MAX: the full count).  n = 0 is RSM_OK.  The radius is
+ * held to the setter's rules. */
+int rsm_stage_radius_count(rsm_ctx *ctx, const float *xyz, int64_t n, double radius, int cap, int32_t *count);
 
 /* ---- moving-least-squares smoothing (CCloudOptimization::run, CCloudOptimization.cpp:348-389) ----------- */
 typedef struct rsm_mls_params {

@@ -1,4 +1,5 @@
-"""python -m reconstruction_amd <config.yml> [--device N] [--out cloud.ply] [--filter] [--mls [--isdelete] [--mls-out bigcloud.ply]]
+"""python -m reconstruction_amd <config.yml> [--device N] [--out cloud.ply] [--filter] [--outrem [NEIGHBOURS RADIUS]]
+                              [--mls [--isdelete] [--mls-out bigcloud.ply]]
                               [--mesh [--mesh-depth 9] [--mesh-trim 4] [--mesh-band [B] [--mesh-band-samples-per-node [3]]] [--mesh-out bigmesh.ply]
                                [--mesh-samples-per-node [2] [--mesh-kernel-depth 0]]
                                [--mesh-density-trim [7] [--mesh-density-smooth 100] [--mesh-island-ratio 0.01]]
@@ -14,6 +15,9 @@ and normals (--filter; CCloudOptimization.cpp:82-121, on the GPU) -> the merged 
 (implies --filter) the moving-least-squares block of CCloudOptimization::run (CCloudOptimization.cpp:348-389, on the GPU):
 the smoothed, oriented cloud as bigcloud.ply (pcl::PointNormal, savePLYFileBinary), what the mesher reads; --isdelete runs the
 multi-view duplicate deletion before it (CCloudOptimization.cpp:152-346, on the GPU).
+With --outrem (implies --filter) the filter also runs the pcl::RadiusOutlierRemoval the reference has, commented out, between its outlier removal
+and its normals (CCloudOptimization.cpp:90-96, on the GPU): a survivor stays only with more than NEIGHBOURS survivors within RADIUS of it (50 and 2
+when given bare, CReconstruction.cpp:18's values).
 With --mesh (implies --mls) the surface of that cloud: unscreened Poisson reconstruction on a dense grid and a trim, on the GPU,
 where CCloudOptimization::run calls meshlab.bat's Poisson filter -> bigmesh.ply (not a bit-parity port of that tool: DESIGN.md 9 f7).
 With --mesh-samples-per-node (implies --mesh) the Poisson call spreads every sample by the density of the cloud around it, as PoissonRecon's
@@ -78,6 +82,9 @@ def main(argv=None) -> int:
     ap.add_argument("--ws", type=float, default=0.03, help="smoothness weight (CReconstruction.cpp:17: 0.03)")
     ap.add_argument("--filter", action="store_true",
                     help="per-pair StatisticalOutlierRemoval (k=100, 1 sigma) as CCloudOptimization::filter (CReconstruction.cpp:18)")
+    ap.add_argument("--outrem", nargs="*", default=None, metavar="N",
+                    help="the filter (implied) with the RadiusOutlierRemoval of CCloudOptimization.cpp:90-96 behind its outlier removal: no value "
+                         "(50 neighbours within radius 2, CReconstruction.cpp:18) or two, NEIGHBOURS RADIUS; give it after the configuration file")
     ap.add_argument("--mls-radius", type=float, default=2.5,
                     help="search radius of the per-pair normals and of the MLS, in scene units (m_mls_radius; CReconstruction.cpp:18 passes 2.5)")
     ap.add_argument("--mls", action="store_true",
@@ -157,6 +164,16 @@ def main(argv=None) -> int:
                          "GPU (the harmonic extension on the mesh graph): every one connected to a coloured vertex when given bare, else those within "
                          "ROUNDS edges of one.  The same PLY at outfilename")
     args = ap.parse_args(argv)
+    outrem = None
+    if args.outrem is not None:
+        try:
+            if len(args.outrem) not in (0, 2):
+                raise ValueError("%d given" % len(args.outrem))
+            outrem = (int(args.outrem[0]), float(args.outrem[1])) if args.outrem else (50, 2.0)
+        except ValueError as e:
+            print("--outrem takes no value or two, NEIGHBOURS (an integer) and RADIUS (a number): %s" % e)
+            return 1
+        args.filter = True
     if args.mesh_stitch or args.mesh_color_fill is not None:
         args.mesh_color = True
     if args.mesh_color:
@@ -192,7 +209,15 @@ def main(argv=None) -> int:
     if args.filter:
         from . import CloudOptimization
         sink = CloudOptimization(sm._ctx)
-        sink.Init(100, 1, 50, 2, args.mls_radius, data, args.isdelete)    # CReconstruction.cpp:18 (isdelete false there)
+        sink.Init(100, 1, outrem[0] if outrem else 50, outrem[1] if outrem else 2, args.mls_radius, data, args.isdelete)    # CReconstruction.cpp:18 (isdelete false there)
+        if outrem:
+            from . import RsmError
+            try:
+                sm._ctx.set_filter_outrem(*outrem)
+            except RsmError as e:             # --outrem -1 2, --outrem 50 0: what rsm_filter_set_outrem refuses
+                print(e)
+                return 1
+            sink.use_outrem = True
     else:
         sink = CloudSink()
     sm.Init(data, sink, args.radius, args.ws)
@@ -205,6 +230,11 @@ def main(argv=None) -> int:
         xyz = np.concatenate([c[0] for c in sink.cloud_normals]).astype(np.float64)
         bgr = np.concatenate(sink.cloud_bgr)
         normals = np.concatenate([c[1] for c in sink.cloud_normals])
+        if outrem:
+            rep = [st["outrem"] for st in sink.stats]
+            print("Radius outlier removal (more than %d within %g): %d points in, %d removed, %s"
+                  % (outrem[0], outrem[1], sum(r["points_in"] for r in rep), sum(r["removed"] for r in rep),
+                     "grid of radius-cells" if not any(r["window"] for r in rep) else "pixel window %d" % max(r["window"] for r in rep)))
     else:
         if not sink.xyz:
             print("no points")

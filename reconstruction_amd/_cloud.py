@@ -4,7 +4,7 @@ import ctypes as C
 import numpy as np
 
 from ._context import ContextBase, _bd, _normals4, _p, _u8, _views
-from ._lib import FilterParams, MlsParams
+from ._lib import FilterParams, MlsParams, OutremParams
 
 
 class CloudPart(ContextBase):
@@ -90,6 +90,36 @@ class CloudPart(ContextBase):
         self._chk(self._lib.rsm_filter_last_grid(self._h, g, v))
         return dict(h=np.float32(g[0]), origin=np.array(g[1:4], np.float32), cells=[int(v[a]) for a in range(3)], levels=int(v[3]),
                     kind0=int(v[4]), kinds=sorted(t for t in range(3) if (v[5] >> t) & 1))
+
+    # ---- the radius outlier pass behind the outlier removal (pcl::RadiusOutlierRemoval, CCloudOptimization.cpp:90-96) ----
+    def set_filter_outrem(self, min_neighbors=None, radius=None):
+        """rsm_filter_set_outrem: from now on every filter_* entry of this context removes, after the StatisticalOutlierRemoval, the
+        survivors with at most min_neighbors finite survivors (themselves included) within radius, and computes the normals on what is
+        left.  Both None: off (the default).  RsmError names what the library refuses (a negative count, a radius that is not positive and
+        finite in float32)."""
+        if min_neighbors is None and radius is None:
+            self._chk(self._lib.rsm_filter_set_outrem(self._h, None))
+            return
+        if min_neighbors is None or radius is None:
+            raise ValueError("set_filter_outrem: min_neighbors and radius go together (both None switches the pass off)")
+        prm = OutremParams(int(min_neighbors), float(radius))
+        self._chk(self._lib.rsm_filter_set_outrem(self._h, C.byref(prm)))
+
+    def filter_last_outrem(self) -> dict:
+        """What that pass did in the last filter call (rsm_filter_last_outrem): points_in (-1: the pass was off), removed, window (the
+        pixel window of the lattice route, 0 = the grid route), nonfinite (non-finite points among the removed)."""
+        v = (C.c_int64 * 4)()
+        self._chk(self._lib.rsm_filter_last_outrem(self._h, v))
+        return dict(points_in=int(v[0]), removed=int(v[1]), window=int(v[2]), nonfinite=int(v[3]))
+
+    def radius_count(self, xyz, radius, cap=None):
+        """rsm_stage_radius_count: per point of a host cloud (n x 3, float32) the finite points with float32 squared distance below
+        (float)(radius * radius), itself included, counted up to cap (None: the full count).  Returns int32 [n]."""
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        n = len(xyz)
+        cnt = np.zeros(max(n, 1), np.int32)
+        self._chk(self._lib.rsm_stage_radius_count(self._h, _p(xyz), n, float(radius), 2 ** 31 - 1 if cap is None else int(cap), _p(cnt)))
+        return cnt[:n].copy()
 
     # ---- moving-least-squares smoothing (CCloudOptimization::run, CloudOptimization/CCloudOptimization.cpp:348-389) ----
     def mls_cloud(self, xyz, radius=2.5, order=1, ref_normals=None):

@@ -61,6 +61,11 @@ class FilterParams(C.Structure):
     _fields_ = [("sor_mean_k", C.c_int), ("sor_std_mul", C.c_double), ("normal_radius", C.c_double), ("cam_center", C.c_float * 3)]
 
 
+class OutremParams(C.Structure):
+    """rsm_outrem_params (include/rsm.h)."""
+    _fields_ = [("min_neighbors", C.c_int), ("radius", C.c_double)]
+
+
 class MlsParams(C.Structure):
     """rsm_mls_params (include/rsm.h)."""
     _fields_ = [("search_radius", C.c_double), ("polynomial_order", C.c_int)]
@@ -189,6 +194,7 @@ _PIN, _POUT, _BND, _RIN, _ROUT, _FLT = (C.POINTER(t) for t in (PairIn, PairOut, 
 _MLS, _VIEW, _PSN, _CLN, _COL, _STI = (C.POINTER(t) for t in (MlsParams, DedupView, PoissonParams, MeshCleanParams, MeshColorParams, MeshStitchParams))
 _TRM, _CLO, _DEC, _PDN = C.POINTER(MeshTrimParams), C.POINTER(MeshCloseParams), C.POINTER(MeshDecimateParams), C.POINTER(PoissonDensityParams)
 _SUB, _PBD, _FIL = C.POINTER(MeshSubdivideParams), C.POINTER(PoissonBandParams), C.POINTER(MeshFillParams)
+_ORM = C.POINTER(OutremParams)
 PROTOTYPES = {
     "rsm_create": (_I, [_V, _I]),
     "rsm_destroy": (None, [_V]),
@@ -262,6 +268,9 @@ PROTOTYPES = {
     "rsm_filter_last_passes": (_I, [_V, _V, _V, _L, _V]),
     "rsm_stage_filter_depth_map": (_I, [_V, _V, _V, _V, _I, _I, _V, _D, _V, _V, _BND, _FLT, _V, _V, _V, _L, _V, _V, _V]),
     "rsm_filter_last_cloud_host": (_I, [_V, _FLT, _V, _V, _L, _V, _V]),
+    "rsm_filter_set_outrem": (_I, [_V, _ORM]),
+    "rsm_filter_last_outrem": (_I, [_V, _V]),
+    "rsm_stage_radius_count": (_I, [_V, _V, _L, _D, _I, _V]),
     "rsm_mls_cloud": (_I, [_V, _V, _L, _V, _MLS, _V, _V, _V, _pL]),
     "rsm_mls_cloud_device": (_I, [_V, _V, _L, _V, _MLS, _V, _V, _V, _pL]),
     "rsm_dedup_cloud": (_I, [_V, _V, _V, _L, _VIEW, _I, _V, _pL, _pL]),

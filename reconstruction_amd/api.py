@@ -246,7 +246,8 @@ class StereoMatching:
 class CloudOptimization:
     """The part of CCloudOptimization (CloudOptimization/CCloudOptimization.cpp) that sits on the stereo path:
     Init (:40-57: only the per-pair filter's parameters are used), InsertPoint (:59-62), filter(idx) (:64-147: the
-    StatisticalOutlierRemoval + NormalEstimation + normal flip of :82-121 on the GPU; the mesh / texture tooling
+    StatisticalOutlierRemoval + NormalEstimation + normal flip of :82-121 on the GPU, with `use_outrem` the RadiusOutlierRemoval of
+    :90-96 between them, which the shipped reference has commented out; the mesh / texture tooling
     after :123 is Windows executables and out of scope), run() (:348-389: MLS over the merged cloud + the normal flip
     on the GPU), mesh() (where run() calls the external Poisson mesher after :389: the dense-grid Poisson surface and trim on the GPU),
     trim_mesh() (mesh.bat's SurfaceTrimmer: the surface cut where the samples' density falls below a depth, on the GPU),
@@ -265,9 +266,11 @@ class CloudOptimization:
         self.cloud_normals = []
         self.cloud_bgr = []      # colours of the surviving points, per pair (imagePyrm[top][0], .cpp:756)
         self.stats = []
+        self.use_outrem = False  # the RadiusOutlierRemoval of :90-96, commented out in the shipped reference: True runs it with Init's two values
 
     def Init(self, sor_meank, sor_stdThres, outrem_neighbor, outrem_radius, mls_radius, ImageData, isdelete_=False):
         self.m_sor_meank, self.m_sor_stdThres, self.m_mls_radius = sor_meank, sor_stdThres, mls_radius
+        self.m_outrem_neighbor, self.m_outrem_radius = outrem_neighbor, outrem_radius   # :43-44
         self.isdelete = bool(isdelete_)
         self.m_ImageData = ImageData
         self.CamCenter = [np.asarray(c[0].CamCenter if c[0].CamCenter is not None else np.zeros(3), np.float32).ravel()
@@ -282,7 +285,12 @@ class CloudOptimization:
 
     def filter(self, idx):
         xyz = (np.concatenate([np.atleast_2d(p) for p in self._pts]) if self._pts else np.zeros((0, 3))).astype(np.float32)
+        if self.use_outrem:   # (set on every call, on or off: the setting is the context's, and other users of it may have changed it)
+            self._ctx.set_filter_outrem(self.m_outrem_neighbor, self.m_outrem_radius)
+        else:
+            self._ctx.set_filter_outrem(None, None)
         kept, nrm, st = self._ctx.filter_cloud(xyz, self.m_sor_meank, self.m_sor_stdThres, self.m_mls_radius, self.CamCenter[idx])
+        st["outrem"] = self._ctx.filter_last_outrem()
         self.cloud_normals.append((xyz[kept], nrm))
         self.cloud_bgr.append(self._bgr[kept] if self._bgr is not None and len(self._bgr) == len(xyz)
                               else np.zeros((len(kept), 3), np.uint8))

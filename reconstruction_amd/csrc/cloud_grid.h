@@ -60,22 +60,24 @@ __device__ __forceinline__ int lower_bound_key(const unsigned long long *__restr
 
 // the 9 contiguous ranges of the sorted array that hold the 27 cells around p (binary search on the keys; used by the
 // normals and by the k-nearest search when the grid has too many cells for a table)
+// range t of 9 around the cell (ix, iy, iz): the up to 3 x-adjacent cells of the row of cells (iy + t % 3 - 1, iz + t / 3 - 1)
+__device__ __forceinline__ void range_of9(const unsigned long long *__restrict__ keys, int n, const FGrid &g, int ix, int iy, int iz, int t, int &rs, int &re) {
+    const int x0 = max(ix - 1, 0), x1 = min(ix + 1, g.nx - 1);
+    const int yy = iy + t % 3 - 1, zz = iz + t / 3 - 1;
+    if (yy < 0 || yy >= g.ny || zz < 0 || zz >= g.nz) {
+        rs = re = 0;
+        return;
+    }
+    const unsigned long long base = ((unsigned long long)zz * g.ny + yy) * g.nx;
+    rs = lower_bound_key(keys, n, base + x0);
+    re = lower_bound_key(keys, n, base + x1 + 1);
+}
 __device__ __forceinline__ void ranges9(const unsigned long long *__restrict__ keys, int n, const FGrid &g, float px, float py,
                                         float pz, int (&rs)[9], int (&re)[9]) {
     int ix, iy, iz;
     grid_cell(g, px, py, pz, ix, iy, iz);
-    const int x0 = max(ix - 1, 0), x1 = min(ix + 1, g.nx - 1);
 #pragma unroll
-    for (int t = 0; t < 9; t++) {
-        const int yy = iy + t % 3 - 1, zz = iz + t / 3 - 1;
-        if (yy < 0 || yy >= g.ny || zz < 0 || zz >= g.nz) {
-            rs[t] = re[t] = 0;
-            continue;
-        }
-        const unsigned long long base = ((unsigned long long)zz * g.ny + yy) * g.nx;
-        rs[t] = lower_bound_key(keys, n, base + x0);
-        re[t] = lower_bound_key(keys, n, base + x1 + 1);
-    }
+    for (int t = 0; t < 9; t++) range_of9(keys, n, g, ix, iy, iz, t, rs[t], re[t]);
 }
 
 // ---- eigen33 / computeRoots of PCL's common/impl/eigen.hpp (smallest eigenvalue and its vector), in double

@@ -21,6 +21,16 @@ void launch_sor_window_list(const float4 *lat, const unsigned int *cell_of, cons
 void launch_sor_window_wave(const float4 *lat, const unsigned int *cell_of, const WinGeom &g, int mean_k, int radius, const unsigned int *list, int nq, float *dist,
                             unsigned int *undecided, hipStream_t st, int wg_max);
 
+// ---- k_filter_outrem.hip: the radius outlier pass's neighbour count on either structure, and its verdict
+// the nv finite points of grid G (cell edge = the search radius): count[position in the gridded cloud] = min(#{fdist2 < r2}, cap)
+void launch_radius_count_grid(const FilterGridDev &G, int nv, float r2, int cap, int32_t *count, hipStream_t st);
+// the m points kept_index lists, on the lattice copy (which holds exactly the finite ones of them): count[o] likewise; points without a
+// lattice entry are left as they are
+void launch_radius_count_lattice(const float4 *lat, const unsigned int *cell_of, const int32_t *kept_index, int64_t m, const WinGeom &g, double r, float r2,
+                                 int cap, int32_t *count, hipStream_t st);
+// flag[i] (1 = point i is the pos[i]-th of the counted cloud) &= count[pos[i]] > min_neighbors
+void launch_outrem_flags(const int32_t *count, const unsigned int *pos, int64_t n, int min_neighbors, unsigned int *flag, hipStream_t st);
+
 // ---- k_filter_knn.hip: a grid level's search and the whole-cloud search
 // nq queries against the 27 cells of grid G (search radius h): d_dist (per point) / undecided (per query: 1 = retry on a coarser grid)
 void launch_knn(const float *d_xyz, const FilterGridDev &G, int nv, float h, int mean_k, const unsigned int *queries, int nq, float *d_dist,

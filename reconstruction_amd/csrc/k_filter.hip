@@ -25,6 +25,9 @@
 // This unit: the host steps (FilterRun, filter_cloud_device), the per-point kernels and the normals.  The k-nearest searches are units of
 // their own, reached through filter_units.h's launchers: k_filter_win.hip (the pixel windows) and k_filter_knn.hip (the grid cells, the
 // whole cloud); what they share on the device is knn_select.h (the selection, the exact-sum rules), and win_bound.h with the normals here.
+// Between the outlier removal and the normals sits, when the caller switches it on (FilterRoute::outrem), the radius outlier pass of :90-96
+// (pcl::RadiusOutlierRemoval, commented out in the shipped reference): its kernels and its definition are k_filter_outrem.hip's, its host
+// step is outrem_pass here.
 #include "../../include/rsm.h"
 #include "filter_units.h"
 #include "knn_select.h"
@@ -295,6 +298,8 @@ struct FilterRun {
     bool prepassed = false, wave_done = false; // the tile pass ran / the wave passes ran
     float h_floor = 0.0f;                     // the ladder need not start below this search radius
     ScanTmp win_scan;                         // the tile pass's scan temporary, which the list and wave passes use again
+    ScanTmp keep_scan;                        // the compaction's, which the radius outlier pass's compaction uses again
+    int64_t nonfinite_kept = 0;               // non-finite points in the filtered cloud: they sort behind the finite ones in a grid over it
     FilterGridDev G;                          // the last grid level
     int64_t lat_cells() const { return prepassed ? (int64_t)wg.gw * (int64_t)wg.gh : 0; }
     void rewind() { A->off = lat_kept ? mark_lat : mark; }
@@ -550,14 +555,61 @@ int distance_threshold(FilterRun &R, double std_mul, double need_r, double stats
 }
 
 // Step 9: d_flag = kept, the kept points and their indices in order, *m = their number (one host round trip)
-int keep_compact(FilterRun &R, double thr, float *d_fxyz, int32_t *d_kept_index, int64_t *m) {
-    hipLaunchKernelGGL(k_keep_flags, blocks_for(R.n), dim3(256), 0, R.st, R.d_dist, R.n, thr, R.d_flag);
-    int s = scan_u32(*R.A, R.d_flag, R.d_pos, (size_t)R.n, R.st);
+int compact_kept(FilterRun &R, float *d_fxyz, int32_t *d_kept_index, int64_t *m) {
+    int s = scan_u32(*R.A, R.d_flag, R.d_pos, (size_t)R.n, R.st, &R.keep_scan);
     if (s != RSM_OK) return s;
     hipLaunchKernelGGL(k_compact_kept, blocks_for(R.n), dim3(256), 0, R.st, R.d_xyz, R.d_flag, R.d_pos, R.n, d_fxyz, d_kept_index);
     uint64_t total = 0;
     if ((s = scan_total(R.d_flag, R.d_pos, (size_t)R.n, R.st, &total, (unsigned int *)R.A->pin->cnt)) != RSM_OK) return s;
     *m = (int64_t)total;
+    return RSM_OK;
+}
+int keep_compact(FilterRun &R, double thr, float *d_fxyz, int32_t *d_kept_index, int64_t *m) {
+    hipLaunchKernelGGL(k_keep_flags, blocks_for(R.n), dim3(256), 0, R.st, R.d_dist, R.n, thr, R.d_flag);
+    return compact_kept(R, d_fxyz, d_kept_index, m);
+}
+
+// the radius outlier pass's count on the grid route: the n points of d_xyz (nv of them finite, inside [lo, hi]) sorted into a grid with cell
+// edge = the search radius, d_count[i] = min(count(p_i), cap); the non-finite points sort behind the finite ones and keep count 0
+int radius_count_on_grid(FilterArena *A, const float *d_xyz, int64_t n, int64_t nv, const float lo[3], const float hi[3], double radius, int cap,
+                         int32_t *d_count, hipStream_t st) {
+    DEVCHK(hipMemsetAsync(d_count, 0, sizeof(int32_t) * (size_t)n, st));
+    if (nv <= 0) return RSM_OK;
+    FilterGridDev G;
+    const int s = build_grid(A, d_xyz, n, 0 /* no table: the count walks its ranges by binary search, as the normals do */, (float)radius, lo, hi, st, G);
+    if (s != RSM_OK) return s;
+    launch_radius_count_grid(G, (int)nv, (float)(radius * radius), cap, d_count, st);
+    return RSM_OK;
+}
+
+// Step 9b, the radius outlier pass (k_filter_outrem.hip) on the m points step 9 kept: their counts -- on the lattice copy, with the points
+// step 9 removed blanked, or on a grid of radius-cells over d_fxyz --, d_flag = survives both passes, and step 9's compaction again.
+// The counts take d_redo (the searches' query lists are done), so the pass adds no buffer to the arena.
+int outrem_pass(FilterRun &R, FilterOutrem &O, double thr, int lattice_window, float *d_fxyz, int32_t *d_kept_index, int64_t *m) {
+    const int64_t m0 = *m;
+    const int64_t nonfinite = (0.0 > thr) ? 0 : R.n - R.nv; // step 9 keeps a non-finite point (distance 0) unless the threshold is negative
+    const int cap = O.min_neighbors < 0x7fffffff ? O.min_neighbors + 1 : 0x7fffffff;
+    int32_t *d_count = (int32_t *)R.d_redo;
+    if (lattice_window > 0) {
+        DEVCHK(hipMemsetAsync(d_count, 0, sizeof(int32_t) * (size_t)m0, R.st));
+        hipLaunchKernelGGL(k_lattice_drop, blocks_for(R.n), dim3(256), 0, R.st, R.d_flag, R.cell_of, R.n, R.lat);
+        launch_radius_count_lattice(R.lat, R.cell_of, d_kept_index, m0, R.wg, O.radius, (float)(O.radius * O.radius), cap, d_count, R.st);
+    } else {
+        R.A->off = R.mark; // (the grid takes the lattice copy's arena space, and the compaction's scan temporary's)
+        R.lat_kept = false;
+        R.keep_scan = ScanTmp{};
+        const int s = radius_count_on_grid(R.A, d_fxyz, m0, m0 - nonfinite, R.flo, R.fhi, O.radius, cap, d_count, R.st);
+        if (s != RSM_OK) return s;
+        R.A->off = R.mark;
+    }
+    launch_outrem_flags(d_count, R.d_pos, R.n, O.min_neighbors, R.d_flag, R.st);
+    const int s = compact_kept(R, d_fxyz, d_kept_index, m);
+    if (s != RSM_OK) return s;
+    R.nonfinite_kept = 0; // (count 0: every one of them went)
+    O.points_in = m0;
+    O.removed = m0 - *m;
+    O.nonfinite = nonfinite;
+    O.window = lattice_window;
     return RSM_OK;
 }
 
@@ -575,7 +627,7 @@ int normals_on_lattice(FilterRun &R, int64_t m, const int32_t *d_kept_index, dou
 // the NaN normal the buffer is filled with
 int normals_on_grid(FilterRun &R, int64_t m, const float *d_fxyz, double normal_radius, const float cam_center[3], float4 *d_normals) {
     FilterGridDev G2;
-    const int64_t mv = m - (R.n - R.nv);
+    const int64_t mv = m - R.nonfinite_kept;
     const int s = build_grid(R.A, d_fxyz, m, 0 /* no table: the normals walk their ranges by binary search */, (float)normal_radius, R.flo, R.fhi, R.st, G2);
     if (s != RSM_OK) return s;
     const float r2 = (float)(normal_radius * normal_radius);
@@ -598,10 +650,13 @@ int filter_cloud_device(FilterArena *A, const float *d_xyz, int64_t n, int mean_
                         double stats[4], hipStream_t st, const FilterLattice *pre, FilterRoute *route) {
     *n_kept = 0;
     if (route) {
-        const float h0 = route->h0;
+        const FilterRoute in = *route;
         *route = FilterRoute{};
-        route->h0 = h0;
+        route->h0 = in.h0;
+        route->outrem.on = in.outrem.on, route->outrem.min_neighbors = in.outrem.min_neighbors, route->outrem.radius = in.outrem.radius;
+        if (in.outrem.on) route->outrem.points_in = 0;
     }
+    FilterOutrem *const outrem = route && route->outrem.on ? &route->outrem : nullptr;
     if (pre && pre->passes_out) *pre->passes_out = FilterPasses{};
     if (n <= 0) return RSM_OK;
     if (n >= (1ll << 31) || mean_k < 1 || !A) return RSM_E_INVALID;
@@ -617,6 +672,7 @@ int filter_cloud_device(FilterArena *A, const float *d_xyz, int64_t n, int mean_
     if (A->failed) return RSM_E_NOMEM;
     DEVCHK(hipMemsetAsync(R.d_dist, 0, sizeof(float) * (size_t)n, st)); // non-finite points: distance 0, as PCL
     R.nq = (int)R.nv;
+    R.nonfinite_kept = n - R.nv; // (all kept: distance 0)
     R.mark = R.mark_lat = A->off;
     if (pre && mean_k <= 128 && R.nv > 0) { // the pixel-window passes: what they cannot decide becomes the ladder's first query list
         R.wg = win_geom(*pre);
@@ -639,10 +695,17 @@ int filter_cloud_device(FilterArena *A, const float *d_xyz, int64_t n, int mean_
     R.rewind();
     double thr = 0.0;
     // (the normals' window is asked for while the lattice copy is still there and the caller lets them use it)
-    const bool ask = R.lat_kept && d_normals && pre->normals_wmax > 0;
-    if ((s = distance_threshold(R, std_mul, ask ? normal_radius : 0.0, stats, &thr)) != RSM_OK) return s;
+    // (... and the radius outlier pass's: a window that covers the larger of the two radii covers the smaller)
+    const bool ask = R.lat_kept && (d_normals || outrem) && pre->normals_wmax > 0;
+    const double need_r = std::max(d_normals ? normal_radius : 0.0, outrem ? outrem->radius : 0.0);
+    if ((s = distance_threshold(R, std_mul, ask ? need_r : 0.0, stats, &thr)) != RSM_OK) return s;
     int64_t m = 0;
     if ((s = keep_compact(R, thr, d_fxyz, d_kept_index, &m)) != RSM_OK) return s;
+    if (outrem && m > 0) { // on the lattice copy under the normals' rule below, else on a grid
+        const int need = A->pin->cnt[3];
+        const bool on_lattice = R.lat_kept && need <= pre->normals_wmax;
+        if ((s = outrem_pass(R, *outrem, thr, on_lattice ? std::max(need, 1) : 0, d_fxyz, d_kept_index, &m)) != RSM_OK) return s;
+    }
     *n_kept = m;
     if (m > 0 && d_normals) {
         // normals of the filtered cloud.  On the lattice copy when it is still there and a window of at most pre->normals_wmax pixels holds every
@@ -662,6 +725,21 @@ int filter_cloud_device(FilterArena *A, const float *d_xyz, int64_t n, int mean_
         if (s != RSM_OK) return s;
     }
     A->off = R.mark;
+    return RSM_OK;
+}
+
+int radius_count_device(FilterArena *A, const float *d_xyz, int64_t n, double radius, int cap, int32_t *d_count, hipStream_t st) {
+    if (n <= 0) return RSM_OK;
+    if (n >= (1ll << 31) || cap < 1 || !A) return RSM_E_INVALID;
+    const size_t mark = A->off;
+    float lo[3], hi[3];
+    int64_t nv = 0;
+    int s = cloud_bbox(A, d_xyz, n, st, lo, hi, &nv);
+    if (s == RSM_OK) s = radius_count_on_grid(A, d_xyz, n, nv, lo, hi, radius, cap, d_count, st);
+    if (s != RSM_OK) return s;
+    DEVCHK(hipStreamSynchronize(st));
+    DEVCHK(hipGetLastError());
+    A->off = mark;
     return RSM_OK;
 }
 

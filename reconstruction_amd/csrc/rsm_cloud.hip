@@ -27,12 +27,78 @@ static int filter_buffers(rsm_ctx *c, int64_t n, bool want_normals, float **dx, 
     return RSM_OK;
 }
 
+// ---- the radius outlier pass (CCloudOptimization.cpp:90-96; k_filter_outrem.hip): a setting of the context, because rsm_filter_params
+// travels by pointer through four entries and cannot grow
+// nullptr, or why the grid cannot take this search radius
+static const char *outrem_radius_fault(double radius) {
+    if (!std::isfinite(radius)) return "the radius is not finite";
+    if (!(radius > 0.0)) return "the radius is not positive";
+    if (!((float)radius > 0.0f)) return "the radius is 0 in float32"; // (the grid's cell edge)
+    const float r2 = (float)(radius * radius);
+    if (!(r2 > 0.0f)) return "the radius' square is 0 in float32";
+    if (!std::isfinite(r2)) return "the radius' square is infinite in float32";
+    return nullptr;
+}
+extern "C" int rsm_filter_set_outrem(rsm_ctx *c, const rsm_outrem_params *p) {
+    if (!c) return RSM_E_INVALID;
+    FilterOutrem &o = c->filt_route.outrem;
+    if (!p) {
+        o.on = false;
+        return RSM_OK;
+    }
+    if (p->min_neighbors < 0) return set_err(c, RSM_E_INVALID, "rsm_filter_set_outrem: min_neighbors %d is negative", p->min_neighbors);
+    if (const char *why = outrem_radius_fault(p->radius)) return set_err(c, RSM_E_INVALID, "rsm_filter_set_outrem: %s (%g)", why, p->radius);
+    o.on = true;
+    o.min_neighbors = p->min_neighbors;
+    o.radius = p->radius;
+    return RSM_OK;
+}
+extern "C" int rsm_filter_last_outrem(rsm_ctx *c, int64_t info[4]) {
+    if (!c || !info) return RSM_E_INVALID;
+    const FilterOutrem &o = c->filt_route.outrem;
+    info[0] = o.points_in;
+    info[1] = o.removed;
+    info[2] = o.window;
+    info[3] = o.nonfinite;
+    return RSM_OK;
+}
+// a filter call that ends before filter_cloud_device (an empty cloud) leaves the report of a pass that had nothing to do
+static void outrem_report_empty(rsm_ctx *c) {
+    FilterOutrem &o = c->filt_route.outrem;
+    o.points_in = o.on ? 0 : -1;
+    o.removed = o.nonfinite = 0;
+    o.window = 0;
+}
+
+extern "C" int rsm_stage_radius_count(rsm_ctx *c, const float *xyz, int64_t n, double radius, int cap, int32_t *count) {
+    if (!c || n < 0 || n > (int64_t)INT32_MAX || (n > 0 && (!xyz || !count))) return RSM_E_INVALID;
+    if (cap < 1) return set_err(c, RSM_E_INVALID, "rsm_stage_radius_count: cap %d is below 1", cap);
+    if (const char *why = outrem_radius_fault(radius)) return set_err(c, RSM_E_INVALID, "rsm_stage_radius_count: %s (%g)", why, radius);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (n == 0) return RSM_OK;
+    Tmp t(c);
+    if (!c->filt_arena) c->filt_arena = filter_arena_create();
+    if (filter_arena_reserve(c->filt_arena, (size_t)n * 16 + 4096 + filter_arena_bytes(n)) != RSM_OK)
+        return set_err(c, RSM_E_NOMEM, "rsm_stage_radius_count: no device memory for %lld points", (long long)n);
+    float *dx = (float *)filter_arena_alloc(c->filt_arena, sizeof(float) * 3 * (size_t)n);
+    int32_t *dc = (int32_t *)filter_arena_alloc(c->filt_arena, sizeof(int32_t) * (size_t)n);
+    if (!dx || !dc) return set_err(c, RSM_E_NOMEM, "rsm_stage_radius_count: arena too small");
+    HIPCHK(c, hipMemcpyAsync(dx, xyz, sizeof(float) * 3 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    const int s = radius_count_device(c->filt_arena, dx, n, radius, cap, dc, c->stream);
+    if (s != RSM_OK) return set_err(c, s, "rsm_stage_radius_count failed");
+    t.down(count, (const int32_t *)dc, (size_t)n);
+    return finish(c, t);
+}
+
 extern "C" int rsm_filter_cloud(rsm_ctx *c, const float *xyz, int64_t n, const rsm_filter_params *prm, int32_t *kept_index,
                                 float *normals, int64_t *n_kept, double *stats) {
     if (!c || n < 0 || (n > 0 && (!xyz || !kept_index)) || !n_kept || !filter_params_ok(prm)) return RSM_E_INVALID;
     HIPCHK(c, hipSetDevice(c->device));
     *n_kept = 0;
-    if (n == 0) return RSM_OK;
+    if (n == 0) {
+        outrem_report_empty(c);
+        return RSM_OK;
+    }
     Tmp t(c);
     float *dx, *df;
     int32_t *dk;
@@ -175,7 +241,10 @@ extern "C" int rsm_filter_last_cloud(rsm_ctx *c, const rsm_filter_params *prm, r
     HIPCHK(c, hipSetDevice(c->device));
     *n_kept = 0;
     const int64_t n = c->n_points;
-    if (n == 0) return RSM_OK;
+    if (n == 0) {
+        outrem_report_empty(c);
+        return RSM_OK;
+    }
     Tmp t(c);
     // the cloud is the depth map this context just made
     const int k = c->N - 1;
@@ -234,7 +303,10 @@ extern "C" int rsm_stage_filter_depth_map(rsm_ctx *c, const double *disp, const 
     if (!t.ok) return finish(c, t);
     *n_points = n;
     if (n > max_points) return set_err(c, RSM_E_INVALID, "rsm_stage_filter_depth_map: %lld points, capacity %lld", (long long)n, (long long)max_points);
-    if (n == 0) return finish(c, t);
+    if (n == 0) {
+        outrem_report_empty(c);
+        return finish(c, t);
+    }
     const DepthCloud dc{fl, ro, W, H, box, dx, n, Q[11] * scale, R_final, T_final};
     FilteredCloud f{};
     const int s = filter_depth_cloud(c, prm, dc, normals != nullptr, &f, stats);

@@ -117,7 +117,8 @@ struct rsm_ctx {
     int64_t filt_tile_left = 0;        // ... queries the tile pass alone left over
     int64_t filt_info[4]{};            // last rsm_filter_last_cloud: window pass used, queries it left to the ladder, points in, points kept
     FilterPasses filt_passes;          // last rsm_filter_last_cloud / rsm_stage_filter_depth_map: the wave passes, the ladder, the whole-cloud search (rsm_filter_last_passes)
-    FilterRoute filt_route;            // the grid ladder: option "filter_ladder_h" in, what the last rsm_filter_cloud / rsm_filter_last_cloud did out
+    FilterRoute filt_route;            // the grid ladder: option "filter_ladder_h" in, what the last rsm_filter_cloud / rsm_filter_last_cloud did out;
+                                       // .outrem: the radius outlier pass's setting (rsm_filter_set_outrem) in, its report (rsm_filter_last_outrem) out
 
     // results
     double *res_disp[2]{};

@@ -220,7 +220,19 @@ struct FilterLattice {
     int *normals_out;   // optional, 2 ints: the window the normals used (0: the grid), the widest window a point needed
     FilterPasses *passes_out; // optional: what the wave passes, the ladder and the whole-cloud search were given
 };
-// The k-nearest grid ladder's route (option "filter_ladder_h", rsm_filter_last_grid): which levels decide a query, never its result.
+// The radius outlier pass between the outlier removal and the normals (k_filter_outrem.hip; rsm_filter_set_outrem, rsm_filter_last_outrem):
+// a survivor of the first pass stays iff more than min_neighbors finite survivors (itself included) lie within radius of it.
+struct FilterOutrem {
+    bool on = false;          // in
+    int min_neighbors = 0;    // in: >= 0
+    double radius = 0.0;      // in: positive, finite, with a positive finite float32 square and a positive float32 value (the setter checks)
+    int64_t points_in = -1;   // out: the first pass's survivors (-1: the pass was off)
+    int64_t removed = 0;      // out: of them, removed here
+    int64_t nonfinite = 0;    // out: non-finite points among the removed
+    int window = 0;           // out: the pixel window the count ran over on the lattice copy (0: the grid of radius-cells)
+};
+// The k-nearest grid ladder's route (option "filter_ladder_h", rsm_filter_last_grid): which levels decide a query, never its result --
+// and the radius outlier pass's setting and report, which travel with it through every filter entry.
 struct FilterRoute {
     float h0 = 0.0f;        // in: > 0 pins the first level's search radius (0: from the sample's extent, as without a route)
     float h = 0.0f;         // out: the first level's search radius (0: no level ran)
@@ -229,11 +241,15 @@ struct FilterRoute {
     int levels = 0;         // out: levels run
     int kind0 = -1;         // out: the first level's cell table kind (-1: no level ran)
     int kinds = 0;          // out: bit t set when a level searched with table kind t (k_sor_knn<t>)
+    FilterOutrem outrem;    // in: the radius outlier pass (off by default); out: what it did
 };
 size_t cloud_lattice_bytes(int XL, int XR, int YL, int YR); // k_filter_win.hip
 int filter_cloud_device(FilterArena *a, const float *d_xyz, int64_t n, int mean_k, double std_mul, double normal_radius,
                         const float cam_center[3], int32_t *d_kept_index, float *d_fxyz, float4 *d_normals, int64_t *n_kept,
                         double stats[4], hipStream_t st, const FilterLattice *pre = nullptr, FilterRoute *route = nullptr);
+// the radius outlier pass's count alone, on the grid route (rsm_stage_radius_count): d_count[i] = min(count(p_i), cap) over the whole cloud
+// as S (k_filter_outrem.hip's definition); A as above
+int radius_count_device(FilterArena *a, const float *d_xyz, int64_t n, double radius, int cap, int32_t *d_count, hipStream_t st);
 void launch_f64_to_f32x3(const double *src, int64_t n, float *dst, hipStream_t st);
 void launch_pack_filtered16(const double *xyz, const uint8_t *bgr, const int32_t *kept, int64_t m, void *dst16, hipStream_t st);
 
