@@ -68,10 +68,10 @@ def dedup(xyz, normals, views):
     """Returns (indicesptr int32, dict(s1, s2, count0, visited))."""
     xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
     n = len(xyz)
-    nrm = np.asarray(normals, np.float32).reshape(n, -1)[:, :3].copy()
     st = dict(s1=0, s2=0, count0=0, visited=0)
-    if n == 0:
+    if n == 0:      # (before the normals: an empty array has no row length to infer)
         return np.zeros(0, np.int32), st
+    nrm = np.asarray(normals, np.float32).reshape(n, -1)[:, :3].copy()
     RT = [(_RT(v["P"][0]), _RT(v["P"][1])) for v in views]
     C = [np.asarray(v["C"], np.float32).ravel()[:3] for v in views]
     # loop 1 (:160-192): best pair, projection, buckets
