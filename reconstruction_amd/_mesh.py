@@ -1,4 +1,4 @@
-"""The surface stages (csrc/rsm_mesh.hip): dense-grid Poisson surface and trim, smoothing and clean-up, the closing of small holes, the
+"""The surface stages (csrc/rsm_poisson.hip, csrc/rsm_mesh.hip): dense-grid Poisson surface and trim, smoothing and clean-up, the closing of small holes, the
 decimation, colours from the rig's views and the levelling of their seams."""
 import ctypes as C
 

@@ -5,18 +5,18 @@
 // the eight steps are defined in DESIGN.md 9 (f7) and restated in numpy in tests/poisson_restatement.py:
 //   1 valid samples (finite point and normal, normal != 0, normalised in fp64)       k_pv_bbox
 //   2 grid: o, h from the fp64 bounding box (host)
-//   3 splat V = sum w n^ (trilinear, 8 nodes) into 64-bit fixed point, occ(cell)     k_pv_splat
-//   4 b = 1/2 central differences of V (V = 0 outside)                               k_pv_rhs
+//   3 splat V = sum w n^ (trilinear, 8 nodes) into 64-bit fixed point, occ(cell)     k_pv_splat (pv_splat8)
+//   4 b = 1/2 central differences of V (V = 0 outside)                               k_pv_rhs<DenseSpace, long long>
 //   5 L chi = b, 7-point Laplacian, chi = 0 outside: conjugate gradients preconditioned by one cell-centred multigrid V-cycle
 //     (red-black Gauss-Seidel, 8-cell mean restriction, piecewise-constant prolongation, rediscretised coarse operators down to 2^3)
-//   6 iso = mean of chi at the samples (fp64, fixed summation tree)                  k_pv_iso + k_pv_sum
+//   6 iso = mean of chi at the samples (fp64, fixed summation tree)                  k_pv_chi_at_samples<DenseSpace> + k_pv_sum
 //   7 marching tetrahedra on the node lattice (six Kuhn tetrahedra per cell), indexed by lattice edge: flag -> scan -> emit
 //   8 trim by the dilated occupancy, compaction of faces and vertices
 // Reproducibility: the splat adds llrint(w n^ 2^32) with 64-bit integer atomics -- integer sums do not depend on arrival order.  |w n^| <= 1
 // and a sample meets a node at most once, so INT32_MAX samples sum to at most (2^31 - 1) 2^32 < 2^63.  Every floating-point reduction
 // (dot products, the iso-value) runs over a grid that depends on the problem size only, block trees in LDS, then one block over the partials.
-// The density-adaptive form of steps 3, 4 and 6 (PoissonRecon's --samplesPerNode) is k_poisson_density.hip; it calls this
-// file's solver, extraction, chi at the samples (poisson_chi_at_samples) and summation tree (poisson_tree_sum).
+// Steps 3, 4, 6 and 7 are the rules DESIGN.md 9 f42 states once for this grid, the density-adaptive splat and the band of bricks
+// (poisson_space.h, poisson_common.h), here on the DenseSpace; what is this file's own is the box, the multigrid solver and the summation tree.
 #include "../../include/rsm.h"
 #include "rsm_dev.h"
 #include "mesh_common.h"
@@ -65,57 +65,17 @@ __global__ __launch_bounds__(256) void k_pv_bbox_points(const float *__restrict_
     pv_bbox_body<false>(xyz, nullptr, n, mm, cnt);
 }
 
-// ---- 3: splat -----------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_pv_splat(const float *__restrict__ xyz, const float *__restrict__ nrm, int64_t n, PvGrid g,
+// ---- 3: splat (step 4, the right-hand side, is poisson_space.h's k_pv_rhs) ---------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_pv_splat(const float *__restrict__ xyz, const float *__restrict__ nrm, int64_t n, MtGrid g, DenseSpace S,
                                                   unsigned long long *__restrict__ V /* [3][N^3] */, uint8_t *__restrict__ occ) {
     const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= n) return;
     double p[3], nh[3];
     if (!pv_valid(xyz, nrm, s, p, nh)) return;
-    const double o[3] = {g.ox, g.oy, g.oz};
-    const int N = g.N;
-    const size_t N3 = (size_t)N * N * N;
-    int i0[3], c[3];
-    double f[3];
-    for (int a = 0; a < 3; a++) {
-        const double u = (p[a] - o[a]) / g.h;
-        const double gq = u - 0.5;
-        const double fl = floor(gq);
-        i0[a] = (int)fl;
-        f[a] = gq - fl;
-        int cc = (int)floor(u);
-        c[a] = cc < 0 ? 0 : (cc > N - 1 ? N - 1 : cc);
-    }
-    occ[(size_t)c[0] + (size_t)N * ((size_t)c[1] + (size_t)N * c[2])] = 1;
-    for (int dz = 0; dz < 2; dz++)
-        for (int dy = 0; dy < 2; dy++)
-            for (int dx = 0; dx < 2; dx++) {
-                const int i = i0[0] + dx, j = i0[1] + dy, k = i0[2] + dz;
-                if (i < 0 || j < 0 || k < 0 || i >= N || j >= N || k >= N) continue;
-                const double w = ((dx ? f[0] : 1.0 - f[0]) * (dy ? f[1] : 1.0 - f[1])) * (dz ? f[2] : 1.0 - f[2]);
-                const size_t node = (size_t)i + (size_t)N * ((size_t)j + (size_t)N * k);
-                for (int a = 0; a < 3; a++) {
-                    const long long q = __double2ll_rn((w * nh[a]) * PV_FIX);
-                    if (q) atomicAdd(&V[a * N3 + node], (unsigned long long)q);
-                }
-            }
-}
-
-// ---- 4: right-hand side (exact in integers, then one conversion) ------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_pv_rhs(const long long *__restrict__ V, int sh, float *__restrict__ b32, double *__restrict__ b64) {
-    const int N = 1 << sh;
-    const size_t N3 = (size_t)1 << (3 * sh);
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= N3) return;
-    const int i = (int)(idx & (N - 1)), j = (int)((idx >> sh) & (N - 1)), k = (int)(idx >> (2 * sh));
-    const size_t sy = (size_t)N, sz = (size_t)N * N;
-    const long long *Vx = V, *Vy = V + N3, *Vz = V + 2 * N3;
-    const long long dx = (i + 1 < N ? Vx[idx + 1] : 0) - (i > 0 ? Vx[idx - 1] : 0);
-    const long long dy = (j + 1 < N ? Vy[idx + sy] : 0) - (j > 0 ? Vy[idx - sy] : 0);
-    const long long dz = (k + 1 < N ? Vz[idx + sz] : 0) - (k > 0 ? Vz[idx - sz] : 0);
-    const double b = (0.5 * (((double)dx + (double)dy) + (double)dz)) / PV_FIX;
-    if (b32) b32[idx] = (float)b;
-    if (b64) b64[idx] = b;
+    int c[3];
+    pv_occ_cell3(p, g, c);
+    occ[S.elem(c[0], c[1], c[2])] = 1;
+    pv_splat8(S, p, g, nh, V, S.nodes());
 }
 
 // ---- reductions ---------------------------------------------------------------------------------------------------------------
@@ -207,169 +167,6 @@ __global__ __launch_bounds__(256) void k_pv_prolong_add(float *__restrict__ xf, 
     const int nc = nf >> 1;
     xf[t] += xc[(size_t)(i >> 1) + (size_t)nc * ((size_t)(j >> 1) + (size_t)nc * (k >> 1))];
 }
-__global__ __launch_bounds__(256) void k_pv_axpy(float *__restrict__ y, const float *__restrict__ x, float a, size_t n) { // y += a x
-    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (t < n) y[t] = y[t] + a * x[t];
-}
-__global__ __launch_bounds__(256) void k_pv_xpay(float *__restrict__ y, const float *__restrict__ x, float a, size_t n) { // y = x + a y
-    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (t < n) y[t] = x[t] + a * y[t];
-}
-
-// ---- 6: chi at the samples (0 for the samples that take no part) -------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_pv_iso(const float *__restrict__ xyz, const float *__restrict__ nrm, int64_t n, PvGrid g,
-                                                const float *__restrict__ chi, double *__restrict__ val) {
-    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= n) return;
-    double p[3], nh[3], acc = 0.0;
-    if (pv_valid(xyz, nrm, s, p, nh)) {
-        const double o[3] = {g.ox, g.oy, g.oz};
-        const int N = g.N;
-        int i0[3];
-        double f[3];
-        for (int a = 0; a < 3; a++) {
-            const double gq = (p[a] - o[a]) / g.h - 0.5;
-            const double fl = floor(gq);
-            i0[a] = (int)fl;
-            f[a] = gq - fl;
-        }
-        for (int dz = 0; dz < 2; dz++)
-            for (int dy = 0; dy < 2; dy++)
-                for (int dx = 0; dx < 2; dx++) {
-                    const int i = i0[0] + dx, j = i0[1] + dy, k = i0[2] + dz;
-                    if (i < 0 || j < 0 || k < 0 || i >= N || j >= N || k >= N) continue;
-                    const double w = ((dx ? f[0] : 1.0 - f[0]) * (dy ? f[1] : 1.0 - f[1])) * (dz ? f[2] : 1.0 - f[2]);
-                    acc += w * (double)chi[(size_t)i + (size_t)N * ((size_t)j + (size_t)N * k)];
-                }
-    }
-    val[s] = acc;
-}
-
-// ---- 7: marching tetrahedra ---------------------------------------------------------------------------------------------------------
-// flag[8 a + d] = the edge (a, d) crosses the surface; the 8th byte of a node stays 0 (one 8-byte store per node)
-__global__ __launch_bounds__(256) void k_pv_edge_flags(const float *__restrict__ chi, float iso, int sh, unsigned long long *__restrict__ flag8) {
-    const int N = 1 << sh;
-    const size_t N3 = (size_t)1 << (3 * sh);
-    const size_t a = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (a >= N3) return;
-    const int i = (int)(a & (N - 1)), j = (int)((a >> sh) & (N - 1)), k = (int)(a >> (2 * sh));
-    const bool ia = chi[a] < iso;
-    unsigned long long w = 0;
-    for (int d = 0; d < 7; d++) {
-        const int x = i + c_dir[d][0], y = j + c_dir[d][1], z = k + c_dir[d][2];
-        if (x >= N || y >= N || z >= N) continue;
-        const bool ib = chi[(size_t)x + (size_t)N * ((size_t)y + (size_t)N * z)] < iso;
-        if (ia != ib) w |= 1ull << (8 * d);
-    }
-    flag8[a] = w;
-}
-
-struct U8ToU32 {
-    __host__ __device__ unsigned int operator()(uint8_t v) const { return v; }
-};
-
-// one vertex per flagged edge, at its rank among the flagged edges (= ascending (a, d)); vkeep (optional) = its cell lies in the mask
-__global__ __launch_bounds__(256) void k_pv_emit_vertices(const float *__restrict__ chi, float iso, PvGrid g, const uint8_t *__restrict__ flag,
-                                                          const unsigned int *__restrict__ pos, float *__restrict__ verts,
-                                                          const uint8_t *__restrict__ mask, uint8_t *__restrict__ vkeep) {
-    const int N = g.N, sh = g.sh;
-    const size_t N3 = (size_t)1 << (3 * sh);
-    const size_t a = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (a >= N3) return;
-    if (((const unsigned long long *)flag)[a] == 0) return;
-    const int ijk[3] = {(int)(a & (N - 1)), (int)((a >> sh) & (N - 1)), (int)(a >> (2 * sh))};
-    const double o[3] = {g.ox, g.oy, g.oz};
-    const float ca = chi[a];
-    for (int d = 0; d < 7; d++) {
-        if (!flag[8 * a + d]) continue;
-        const size_t b = a + (size_t)c_dir[d][0] + (size_t)N * ((size_t)c_dir[d][1] + (size_t)N * c_dir[d][2]);
-        const float cb = chi[b];
-        const float t = (iso - ca) / (cb - ca);
-        const size_t v = pos[8 * a + d];
-        int cell[3];
-        for (int c = 0; c < 3; c++) {
-            const float pa = (float)(o[c] + ((double)ijk[c] + 0.5) * g.h);
-            const float pb = (float)(o[c] + ((double)(ijk[c] + c_dir[d][c]) + 0.5) * g.h);
-            const float p = pa + t * (pb - pa);
-            verts[3 * v + c] = p;
-            const int q = (int)floor(((double)p - o[c]) / g.h);
-            cell[c] = q < 0 ? 0 : (q > N - 1 ? N - 1 : q);
-        }
-        if (vkeep) vkeep[v] = mask[(size_t)cell[0] + (size_t)N * ((size_t)cell[1] + (size_t)N * cell[2])];
-    }
-}
-
-// faces of a cell (its 000 node is `a`): EMIT = false counts them, true writes them at foff[a] in (tetrahedron, triangle) order
-template <bool EMIT>
-__global__ __launch_bounds__(256) void k_pv_cell_faces(const float *__restrict__ chi, float iso, int sh, TetTable tab, unsigned int *__restrict__ cnt,
-                                                       const unsigned int *__restrict__ foff, const unsigned int *__restrict__ pos,
-                                                       int32_t *__restrict__ faces) {
-    const int N = 1 << sh;
-    const size_t N3 = (size_t)1 << (3 * sh);
-    const size_t a = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (a >= N3) return;
-    const int i = (int)(a & (N - 1)), j = (int)((a >> sh) & (N - 1)), k = (int)(a >> (2 * sh));
-    if (i >= N - 1 || j >= N - 1 || k >= N - 1) {
-        if (!EMIT) cnt[a] = 0;
-        return;
-    }
-    const size_t st[3] = {1, (size_t)N, (size_t)N * N};
-    unsigned int cube = 0; // bit (dx | dy << 1 | dz << 2) = that corner is inside
-    for (int c = 0; c < 8; c++)
-        if (chi[a + (c & 1) * st[0] + ((c >> 1) & 1) * st[1] + ((c >> 2) & 1) * st[2]] < iso) cube |= 1u << c;
-    if (cube == 0 || cube == 255) {
-        if (!EMIT) cnt[a] = 0;
-        return;
-    }
-    unsigned int nf = 0;
-    size_t o = EMIT ? (size_t)foff[a] : 0;
-    for (int t = 0; t < 6; t++) {
-        const int pa = c_perm[t][0], pb = c_perm[t][1];
-        const int corner[4] = {0, 1 << pa, (1 << pa) | (1 << pb), 7};
-        int m = 0;
-        for (int v = 0; v < 4; v++) m |= ((cube >> corner[v]) & 1) << v;
-        const int nt = tab.ntri[m];
-        if (!EMIT) {
-            nf += nt;
-            continue;
-        }
-        for (int q = 0; q < nt; q++) {
-            int32_t vi[3];
-            for (int c = 0; c < 3; c++) {
-                const int e = tab.e[m][q][c];
-                const int cu = corner[e >> 2], cv = corner[e & 3]; // cu is a subset of cv: the lower node is cu's
-                const int d = cv & ~cu;
-                const size_t na = a + (cu & 1) * st[0] + ((cu >> 1) & 1) * st[1] + ((cu >> 2) & 1) * st[2];
-                vi[c] = (int32_t)pos[8 * na + pv_dir_code(d & 1, (d >> 1) & 1, (d >> 2) & 1)];
-            }
-            if (c_perm_sign[t] < 0) {
-                const int32_t w = vi[1];
-                vi[1] = vi[2];
-                vi[2] = w;
-            }
-            faces[3 * o] = vi[0];
-            faces[3 * o + 1] = vi[1];
-            faces[3 * o + 2] = vi[2];
-            o++;
-        }
-    }
-    if (!EMIT) cnt[a] = nf;
-}
-
-// ---- 8: trim ------------------------------------------------------------------------------------------------------------------------
-// one axis of the Chebyshev dilation: out = max of in over [-r, r] along the axis of stride 1 << (axis * sh)
-__global__ __launch_bounds__(256) void k_pv_dilate(const uint8_t *__restrict__ in, uint8_t *__restrict__ out, int sh, int axis, int r) {
-    const int N = 1 << sh;
-    const size_t N3 = (size_t)1 << (3 * sh);
-    const size_t a = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (a >= N3) return;
-    const int c = (int)((a >> (axis * sh)) & (N - 1));
-    const size_t st = (size_t)1 << (axis * sh);
-    const int lo = c - r < 0 ? 0 : c - r, hi = c + r > N - 1 ? N - 1 : c + r;
-    uint8_t m = 0;
-    for (int q = lo; q <= hi && !m; q++) m = in[a + (size_t)(q - c) * st] ? 1 : 0; // (q - c may be negative: size_t wraps back, a + ... stays in range)
-    out[a] = m;
-}
 // ---- host ---------------------------------------------------------------------------------------------------------------------------
 static inline unsigned red_blocks(size_t n) { return (unsigned)std::min<size_t>(PV_RED_BLOCKS, (n + 255) / 256); }
 
@@ -421,8 +218,6 @@ int poisson_grid_device(const float *d_xyz, const float *d_nrm4, int64_t n, int 
     return RSM_OK;
 }
 
-static PvGrid make_grid(const double grid[4], int depth) { return PvGrid{grid[0], grid[1], grid[2], grid[3], depth, 1 << depth}; }
-
 int poisson_rhs_device(const float *d_xyz, const float *d_nrm4, int64_t n, int depth, const double grid[4], float *d_b32, double *d_b64,
                        uint8_t *d_occ, hipStream_t st) {
     const size_t N3 = (size_t)1 << (3 * depth);
@@ -431,9 +226,9 @@ int poisson_rhs_device(const float *d_xyz, const float *d_nrm4, int64_t n, int d
     if (!M.ok) return RSM_E_NOMEM;
     DEVCHK(hipMemsetAsync(V, 0, 3 * N3 * sizeof(unsigned long long), st));
     DEVCHK(hipMemsetAsync(d_occ, 0, N3, st));
-    const PvGrid g = make_grid(grid, depth);
-    hipLaunchKernelGGL(k_pv_splat, blocks_for((size_t)n), dim3(256), 0, st, d_xyz, d_nrm4, n, g, V, d_occ);
-    hipLaunchKernelGGL(k_pv_rhs, blocks_for(N3), dim3(256), 0, st, (const long long *)V, depth, d_b32, d_b64);
+    const DenseSpace S{depth};
+    hipLaunchKernelGGL(k_pv_splat, blocks_for((size_t)n), dim3(256), 0, st, d_xyz, d_nrm4, n, pv_grid(grid, depth), S, V, d_occ);
+    hipLaunchKernelGGL((k_pv_rhs<DenseSpace, long long>), blocks_for(N3), dim3(256), 0, st, (const long long *)V, S, d_b32, d_b64);
     DEVCHK(hipStreamSynchronize(st));
     DEVCHK(hipGetLastError());
     return RSM_OK;
@@ -441,10 +236,15 @@ int poisson_rhs_device(const float *d_xyz, const float *d_nrm4, int64_t n, int d
 
 namespace {
 struct Solver {
-    int depth;
-    hipStream_t st;
+    int depth = 0;
+    hipStream_t st = nullptr;
     std::vector<float *> x, b, r; // per level; level 0: x = z, b = the CG residual
-    double *part, *scal;
+    double *part = nullptr, *scal = nullptr;
+    // what poisson_pcg's Ops read: the elements, the blocks of a reduction, the right-hand side, z = x[0]
+    size_t n = 0;
+    unsigned rb = 0;
+    const float *rhs = nullptr;
+    float *z = nullptr;
     int vcycle(int l) {
         const int sh = depth - l;
         const size_t n3 = (size_t)1 << (3 * sh);
@@ -470,6 +270,21 @@ struct Solver {
         DEVCHK(hipStreamSynchronize(st));
         return RSM_OK;
     }
+    // poisson_pcg's Ops: one V-cycle as the preconditioner; r = b[0], z = x[0]
+    int precondition(double *rho) {
+        const int s = vcycle(0);
+        if (s != RSM_OK) return s;
+        hipLaunchKernelGGL(k_pv_dot, dim3(rb), dim3(256), 0, st, (const float *)b[0], (const float *)z, n, part);
+        return fetch((int)rb, rho);
+    }
+    int apply(const float *p, float *q, double *pq) {
+        hipLaunchKernelGGL(k_pv_stencil<0>, dim3(rb), dim3(256), 0, st, p, (const float *)nullptr, q, depth, part);
+        return fetch((int)rb, pq);
+    }
+    int residual(const float *chi, double *rr) {
+        hipLaunchKernelGGL(k_pv_stencil<1>, dim3(rb), dim3(256), 0, st, chi, rhs, b[0], depth, part);
+        return fetch((int)rb, rr);
+    }
 };
 } // namespace
 
@@ -492,8 +307,11 @@ int poisson_solve_device(const float *d_b, int depth, double rel_residual, int m
     S.part = M.get<double>(PV_RED_BLOCKS);
     S.scal = M.get<double>(1);
     if (!M.ok) return RSM_E_NOMEM;
-    float *z = S.x[0], *r = S.b[0];
-    const unsigned rb = red_blocks(N3);
+    S.n = N3;
+    S.rhs = d_b;
+    S.z = S.x[0];
+    float *r = S.b[0];
+    const unsigned rb = S.rb = red_blocks(N3);
     DEVCHK(hipMemsetAsync(d_chi, 0, N3 * sizeof(float), st));
     DEVCHK(hipMemcpyAsync(r, d_b, N3 * sizeof(float), hipMemcpyDeviceToDevice, st));
     double bb = 0.0;
@@ -501,43 +319,9 @@ int poisson_solve_device(const float *d_b, int depth, double rel_residual, int m
     int s = S.fetch((int)rb, &bb);
     if (s != RSM_OK) return s;
     if (!(bb > 0.0)) return RSM_OK; // b = 0: chi = 0
-    const double bnorm = sqrt(bb);
-    double rho_old = 0.0;
-    int worse = 0;
-    bool have_best = true; // (chi = 0, residual 1)
-    DEVCHK(hipMemsetAsync(best, 0, N3 * sizeof(float), st));
+    DEVCHK(hipMemsetAsync(best, 0, N3 * sizeof(float), st)); // (chi = 0, residual 1)
     *residual = 1.0;
-    for (int it = 1; it <= max_cycles; it++) {
-        s = S.vcycle(0); // z = M^-1 r
-        if (s != RSM_OK) return s;
-        double rho = 0.0, pq = 0.0, rr = 0.0;
-        hipLaunchKernelGGL(k_pv_dot, dim3(rb), dim3(256), 0, st, r, z, N3, S.part);
-        if ((s = S.fetch((int)rb, &rho)) != RSM_OK) return s;
-        if (it == 1) DEVCHK(hipMemcpyAsync(p, z, N3 * sizeof(float), hipMemcpyDeviceToDevice, st));
-        else hipLaunchKernelGGL(k_pv_xpay, blocks_for(N3), dim3(256), 0, st, p, z, (float)(rho / rho_old), N3);
-        hipLaunchKernelGGL(k_pv_stencil<0>, dim3(rb), dim3(256), 0, st, p, (const float *)nullptr, q, depth, S.part);
-        if ((s = S.fetch((int)rb, &pq)) != RSM_OK) return s;
-        if (pq == 0.0 || !std::isfinite(rho / pq)) break; // nothing left to correct in float32
-        hipLaunchKernelGGL(k_pv_axpy, blocks_for(N3), dim3(256), 0, st, d_chi, p, (float)(rho / pq), N3);
-        // the residual is recomputed from chi, not updated by recurrence: what is reported is what chi reaches
-        hipLaunchKernelGGL(k_pv_stencil<1>, dim3(rb), dim3(256), 0, st, d_chi, d_b, r, depth, S.part);
-        if ((s = S.fetch((int)rb, &rr)) != RSM_OK) return s;
-        rho_old = rho;
-        *cycles = it;
-        const double res = sqrt(rr) / bnorm;
-        if (history) history[it - 1] = res;
-        // float32 conjugate gradients reach a floor (a few 1e-6) and drift away from it afterwards: the best chi is kept, and two cycles
-        // in a row without a new best end the solve
-        if (res < *residual) {
-            *residual = res;
-            worse = 0;
-            if (res <= rel_residual) break; // (chi is the best iterate)
-            DEVCHK(hipMemcpyAsync(best, d_chi, N3 * sizeof(float), hipMemcpyDeviceToDevice, st));
-            have_best = true;
-        } else if (++worse >= 2)
-            break;
-    }
-    if (*residual > rel_residual && have_best) DEVCHK(hipMemcpyAsync(d_chi, best, N3 * sizeof(float), hipMemcpyDeviceToDevice, st));
+    if ((s = poisson_pcg(S, sqrt(bb), rel_residual, max_cycles, 2, d_chi, p, q, best, residual, cycles, history, st)) != RSM_OK) return s;
     DEVCHK(hipStreamSynchronize(st));
     DEVCHK(hipGetLastError());
     return *residual <= rel_residual ? RSM_OK : RSM_W_NOT_CONVERGED;
@@ -545,7 +329,7 @@ int poisson_solve_device(const float *d_b, int depth, double rel_residual, int m
 
 void poisson_chi_at_samples(const float *d_xyz, const float *d_nrm4, int64_t n, const float *d_chi, int depth, const double grid[4], double *d_val,
                             hipStream_t st) {
-    hipLaunchKernelGGL(k_pv_iso, blocks_for((size_t)n), dim3(256), 0, st, d_xyz, d_nrm4, n, make_grid(grid, depth), d_chi, d_val);
+    hipLaunchKernelGGL(k_pv_chi_at_samples<DenseSpace>, blocks_for((size_t)n), dim3(256), 0, st, d_xyz, d_nrm4, n, pv_grid(grid, depth), DenseSpace{depth}, d_chi, d_val);
 }
 
 void poisson_tree_sum(const double *d_v, int64_t n, double *d_part, double *d_sum, hipStream_t st) {
@@ -556,22 +340,11 @@ void poisson_tree_sum(const double *d_v, int64_t n, double *d_part, double *d_su
 
 int poisson_iso_device(const float *d_xyz, const float *d_nrm4, int64_t n, int64_t n_valid, const float *d_chi, int depth, const double grid[4],
                        double *iso, hipStream_t st) {
-    *iso = 0.0;
-    if (n <= 0 || n_valid <= 0) return RSM_OK;
-    DevMem M;
-    double *val = M.get<double>((size_t)n), *part = M.get<double>(PV_RED_BLOCKS), *scal = M.get<double>(1);
-    if (!M.ok) return RSM_E_NOMEM;
-    poisson_chi_at_samples(d_xyz, d_nrm4, n, d_chi, depth, grid, val, st);
-    poisson_tree_sum(val, n, part, scal, st);
-    double sum = 0.0;
-    DEVCHK(hipMemcpyAsync(&sum, scal, sizeof sum, hipMemcpyDeviceToHost, st));
-    DEVCHK(hipStreamSynchronize(st));
-    DEVCHK(hipGetLastError());
-    *iso = sum / (double)n_valid;
-    return RSM_OK;
+    auto chi_at = [&](double *val) { poisson_chi_at_samples(d_xyz, d_nrm4, n, d_chi, depth, grid, val, st); };
+    return poisson_mean_of_chi_at_samples(chi_at, n, nullptr, (double)n_valid, iso, st);
 }
 
-// step 8's second half, for the dense extraction and the banded one (k_poisson_band.hip): of `full` (its vertices flagged by vkeep) the faces whose
+// step 8's second half, for poisson_common.h's extraction: of `full` (its vertices flagged by vkeep) the faces whose
 // three vertices are kept, the vertices they use, both renumbered in order -> *out; `full` is freed
 int poisson_trim_commit(DevMem &M, PoissonMesh &full, const uint8_t *vkeep, PoissonMesh *out, hipStream_t st) {
     const uint64_t nv = (uint64_t)full.nv, nf = (uint64_t)full.nf;
@@ -611,69 +384,9 @@ int poisson_trim_commit(DevMem &M, PoissonMesh &full, const uint8_t *vkeep, Pois
 
 int poisson_extract_device(const float *d_chi, int depth, double iso, const double grid[4], const uint8_t *d_occ, int trim_cells,
                            PoissonMesh *out, int64_t untrimmed[2], hipStream_t st) {
-    poisson_mesh_free(out);
-    untrimmed[0] = untrimmed[1] = 0;
-    const size_t N3 = (size_t)1 << (3 * depth);
-    const PvGrid g = make_grid(grid, depth);
-    const float iso32 = (float)iso;
-    const TetTable tab = make_tet_table();
-    DevMem M;
-    uint8_t *flag = (uint8_t *)M.get<unsigned long long>(N3);
-    unsigned int *pos = M.get<unsigned int>(8 * N3);
-    unsigned int *cnt = M.get<unsigned int>(N3), *foff = M.get<unsigned int>(N3);
-    if (!M.ok) return RSM_E_NOMEM;
-    hipLaunchKernelGGL(k_pv_edge_flags, blocks_for(N3), dim3(256), 0, st, d_chi, iso32, depth, (unsigned long long *)flag);
-    int s = scan_u32(M, rocprim::make_transform_iterator((const uint8_t *)flag, U8ToU32()), pos, 8 * N3, st);
-    if (s != RSM_OK) return s;
-    hipLaunchKernelGGL(k_pv_cell_faces<false>, blocks_for(N3), dim3(256), 0, st, d_chi, iso32, depth, tab, cnt, (const unsigned int *)nullptr,
-                       (const unsigned int *)nullptr, (int32_t *)nullptr);
-    if ((s = scan_u32(M, (const unsigned int *)cnt, foff, N3, st)) != RSM_OK) return s;
-    uint64_t nv = 0, nf = 0;
-    // (the last node has no edge toward higher indices and is no cell: both last flags are 0, the totals are the last positions)
-    if ((s = scan_total(flag + 8 * N3 - 1, pos + 8 * N3 - 1, 1, st, &nv)) != RSM_OK) return s;
-    if ((s = scan_total(cnt + N3 - 1, foff + N3 - 1, 1, st, &nf)) != RSM_OK) return s;
-    DEVCHK(hipGetLastError());
-    untrimmed[0] = (int64_t)nv;
-    untrimmed[1] = (int64_t)nf;
-    if (nv == 0 || nf == 0) return RSM_OK;
-    if (nv > (uint64_t)INT32_MAX || nf > (uint64_t)INT32_MAX / 3) return RSM_E_NOMEM;
-    float *verts = nullptr;
-    int32_t *faces = nullptr;
-    if (hipMalloc((void **)&verts, nv * 3 * sizeof(float)) != hipSuccess) return RSM_E_NOMEM;
-    if (hipMalloc((void **)&faces, nf * 3 * sizeof(int32_t)) != hipSuccess) {
-        (void)hipFree(verts);
-        return RSM_E_NOMEM;
-    }
-    PoissonMesh full;
-    full.d_v = verts;
-    full.d_f = faces;
-    full.nv = (int64_t)nv;
-    full.nf = (int64_t)nf;
-    const bool trim = trim_cells > 0 && d_occ;
-    uint8_t *mask = nullptr, *vkeep = nullptr;
-    if (trim) {
-        uint8_t *t0 = M.get<uint8_t>(N3), *t1 = M.get<uint8_t>(N3);
-        vkeep = M.get<uint8_t>(nv);
-        if (!M.ok) {
-            poisson_mesh_free(&full);
-            return RSM_E_NOMEM;
-        }
-        hipLaunchKernelGGL(k_pv_dilate, blocks_for(N3), dim3(256), 0, st, d_occ, t0, depth, 0, trim_cells);
-        hipLaunchKernelGGL(k_pv_dilate, blocks_for(N3), dim3(256), 0, st, (const uint8_t *)t0, t1, depth, 1, trim_cells);
-        hipLaunchKernelGGL(k_pv_dilate, blocks_for(N3), dim3(256), 0, st, (const uint8_t *)t1, t0, depth, 2, trim_cells);
-        mask = t0;
-    }
-    hipLaunchKernelGGL(k_pv_emit_vertices, blocks_for(N3), dim3(256), 0, st, d_chi, iso32, g, (const uint8_t *)flag, (const unsigned int *)pos, verts,
-                       (const uint8_t *)mask, vkeep);
-    hipLaunchKernelGGL(k_pv_cell_faces<true>, blocks_for(N3), dim3(256), 0, st, d_chi, iso32, depth, tab, (unsigned int *)nullptr,
-                       (const unsigned int *)foff, (const unsigned int *)pos, faces);
-    if (!trim) {
-        if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) {
-            poisson_mesh_free(&full);
-            return RSM_E_HIP;
-        }
-        *out = full;
-        return RSM_OK;
-    }
-    return poisson_trim_commit(M, full, vkeep, out, st);
+    const DenseSpace S{depth};
+    auto dilate = [&](const uint8_t *in, uint8_t *to, int axis) {
+        hipLaunchKernelGGL(k_pv_dilate<>, blocks_for(S.nodes()), dim3(256), 0, st, in, to, depth, axis, trim_cells);
+    };
+    return poisson_extract(S, pv_grid(grid, depth), d_chi, iso, d_occ, trim_cells, dilate, out, untrimmed, st);
 }

@@ -2,23 +2,20 @@
 // level of N = 2^depth nodes per axis that exists only near the samples, on top of k_poisson.hip's dense solve at depth - 1.  The fine grid
 // is cut into bricks of 8^3 nodes; a brick is occupied when a sample's cell lies in it and active within band_bricks (Chebyshev) of an
 // occupied one.  The active bricks are listed in ascending linear index, a brick's slot is its place in the list, a dense B^3 table maps
-// brick -> slot (-1: inactive), and every field lives brick-major: element slot * 512 + lx + 8 (ly + 8 lz).  The steps (restated in numpy in
-// tests/poisson_band_restatement.py):
+// brick -> slot (-1: inactive), and every field lives brick-major: element slot * 512 + lx + 8 (ly + 8 lz).  Splat, right-hand side, chi at
+// the samples and the extraction are the rules DESIGN.md 9 f42 states once (poisson_space.h, poisson_common.h), here on the
+// BandSpace; what is this file's own (restated in numpy in tests/poisson_band_restatement.py):
 //   bricks   occupied -> dilated -> scan -> slot table, list, the 27 neighbour slots of every slot     k_pb_mark .. k_pb_nbr
-//   splat    f7's fixed-point splat and occ on the active nodes, b = 1/2 central differences           k_pb_splat, k_pb_rhs
 //   guess    g = (float)(1/4 trilinear prolongation of the coarse chi), fp64, corner order dz, dy, dx  k_pb_guess
 //   solve    L chi = b on the active nodes, chi = g on the inactive ones, 0 outside the grid: float32 conjugate gradients from chi = g,
 //            preconditioned by one symmetric red-black Gauss-Seidel sweep from zero on the band        k_pb_rbgs, k_pb_stencil
-//   iso      f7's mean of chi at the samples in f7's summation tree                                    k_pb_chi_at_samples
-//   mesh     f7's marching tetrahedra on the cells whose eight corners are active: flags -> scan -> emit, then f7's trim with the occupancy
-//            dilated inside the band                                                                   k_pb_edge_flags .. k_pb_dilate_cells
+//   trim     f7's trim with the occupancy dilated inside the band                                      k_pb_dilate_cells
 // One workgroup per brick in the solver: a 10^3 tile of the field in LDS, filled through the slot's neighbour table.  Every reduction has a fixed
 // shape: an LDS tree over a brick's 512 products, the per-slot partials through f7's tree (poisson_tree_sum).  No float atomics.
 #include "../../include/rsm.h"
 #include "rsm_dev.h"
 #include "mesh_common.h"
 #include "poisson_common.h"
-#include "poisson_band_common.h"
 
 #include <math.h>
 
@@ -29,7 +26,7 @@
 namespace {
 
 // ---- bricks ---------------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_pb_mark(const float *__restrict__ xyz, const float *__restrict__ nrm, int64_t n, PvGrid g, int bsh,
+__global__ __launch_bounds__(256) void k_pb_mark(const float *__restrict__ xyz, const float *__restrict__ nrm, int64_t n, MtGrid g, int bsh,
                                                  uint8_t *__restrict__ occb) {
     const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= n) return;
@@ -42,19 +39,6 @@ __global__ __launch_bounds__(256) void k_pb_mark(const float *__restrict__ xyz, 
         c[a] = (cc < 0 ? 0 : (cc > g.N - 1 ? g.N - 1 : cc)) >> 3;
     }
     occb[(size_t)c[0] + (((size_t)c[1] + ((size_t)c[2] << bsh)) << bsh)] = 1;
-}
-// one axis of the Chebyshev dilation over the B^3 bricks
-__global__ __launch_bounds__(256) void k_pb_dilate_bricks(const uint8_t *__restrict__ in, uint8_t *__restrict__ out, int bsh, int axis, int r) {
-    const int B = 1 << bsh;
-    const size_t B3 = (size_t)1 << (3 * bsh);
-    const size_t a = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (a >= B3) return;
-    const int c = (int)((a >> (axis * bsh)) & (B - 1));
-    const long long st = (long long)1 << (axis * bsh);
-    const int lo = c - r < 0 ? 0 : c - r, hi = c + r > B - 1 ? B - 1 : c + r;
-    uint8_t m = 0;
-    for (int q = lo; q <= hi && !m; q++) m = in[(long long)a + (q - c) * st] ? 1 : 0;
-    out[a] = m;
 }
 struct PbU8ToU32 {
     __host__ __device__ unsigned int operator()(uint8_t v) const { return v ? 1u : 0u; }
@@ -80,54 +64,18 @@ __global__ __launch_bounds__(256) void k_pb_nbr(const int32_t *__restrict__ acti
     nbr[t] = (x < 0 || y < 0 || z < 0 || x >= B || y >= B || z >= B) ? -2 : slot[(size_t)x + (((size_t)y + ((size_t)z << bsh)) << bsh)];
 }
 
-// ---- splat and right-hand side (f7's steps 3 and 4 on the active nodes) ----------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_pb_splat(const float *__restrict__ xyz, const float *__restrict__ nrm, int64_t n, PvGrid g, PbBand B,
-                                                  unsigned long long *__restrict__ V /* [3][S 512] */, size_t nodes, uint8_t *__restrict__ occ) {
+// ---- splat (f7's step 3 on the active nodes; the right-hand side is poisson_space.h's k_pv_rhs) ------------------------------------------------
+__global__ __launch_bounds__(256) void k_pb_splat(const float *__restrict__ xyz, const float *__restrict__ nrm, int64_t n, MtGrid g, BandSpace S,
+                                                  unsigned long long *__restrict__ V /* [3][S 512] */, uint8_t *__restrict__ occ) {
     const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= n) return;
     double p[3], nh[3];
     if (!pv_valid(xyz, nrm, s, p, nh)) return;
-    const double o[3] = {g.ox, g.oy, g.oz};
-    const int N = g.N;
-    int i0[3], c[3];
-    double f[3];
-    for (int a = 0; a < 3; a++) {
-        const double u = (p[a] - o[a]) / g.h;
-        const double gq = u - 0.5;
-        const double fl = floor(gq);
-        i0[a] = (int)fl;
-        f[a] = gq - fl;
-        int cc = (int)floor(u);
-        c[a] = cc < 0 ? 0 : (cc > N - 1 ? N - 1 : cc);
-    }
-    const long long ce = pb_elem_of(B, c[0], c[1], c[2]);
+    int c[3];
+    pv_occ_cell3(p, g, c);
+    const long long ce = S.elem(c[0], c[1], c[2]);
     if (ce >= 0) occ[ce] = 1; // (the cell's brick is occupied, so active)
-    for (int dz = 0; dz < 2; dz++)
-        for (int dy = 0; dy < 2; dy++)
-            for (int dx = 0; dx < 2; dx++) {
-                const long long node = pb_elem_of(B, i0[0] + dx, i0[1] + dy, i0[2] + dz);
-                if (node < 0) continue; // outside the grid; (inactive cannot happen with band_bricks >= 1)
-                const double w = ((dx ? f[0] : 1.0 - f[0]) * (dy ? f[1] : 1.0 - f[1])) * (dz ? f[2] : 1.0 - f[2]);
-                for (int a = 0; a < 3; a++) {
-                    const long long q = __double2ll_rn((w * nh[a]) * PV_FIX);
-                    if (q) atomicAdd(&V[a * nodes + (size_t)node], (unsigned long long)q);
-                }
-            }
-}
-__device__ __forceinline__ long long pb_v(const long long *__restrict__ V, long long e) { return e < 0 ? 0 : V[e]; }
-__global__ __launch_bounds__(256) void k_pb_rhs(const long long *__restrict__ V, size_t nodes, const int32_t *__restrict__ nbr, float *__restrict__ b32,
-                                                double *__restrict__ b64) {
-    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (t >= nodes) return;
-    const int32_t *nb = nbr + (t >> 9) * 27;
-    const int l = (int)(t & 511), x = l & 7, y = (l >> 3) & 7, z = l >> 6;
-    const long long *Vx = V, *Vy = V + nodes, *Vz = V + 2 * nodes;
-    const long long dx = pb_v(Vx, pb_node(nb, x + 1, y, z)) - pb_v(Vx, pb_node(nb, x - 1, y, z));
-    const long long dy = pb_v(Vy, pb_node(nb, x, y + 1, z)) - pb_v(Vy, pb_node(nb, x, y - 1, z));
-    const long long dz = pb_v(Vz, pb_node(nb, x, y, z + 1)) - pb_v(Vz, pb_node(nb, x, y, z - 1));
-    const double b = (0.5 * (((double)dx + (double)dy) + (double)dz)) / PV_FIX;
-    if (b32) b32[t] = (float)b;
-    if (b64) b64[t] = b;
+    pv_splat8(S, p, g, nh, V, S.nodes());
 }
 
 // ---- guess: a quarter of the cell-centred trilinear prolongation of the coarse field (chi_c = 0 outside its grid) -------------------------------
@@ -247,163 +195,6 @@ __global__ __launch_bounds__(256) void k_pb_dot(const float *__restrict__ x, con
     const size_t e = (size_t)blockIdx.x * PB_NODES + threadIdx.x;
     pb_brick_sum_to((double)x[e] * (double)y[e], (double)x[e + 256] * (double)y[e + 256], &part[blockIdx.x]);
 }
-__global__ __launch_bounds__(256) void k_pb_axpy(float *__restrict__ y, const float *__restrict__ x, float a, size_t n) { // y += a x
-    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (t < n) y[t] = y[t] + a * x[t];
-}
-__global__ __launch_bounds__(256) void k_pb_xpay(float *__restrict__ y, const float *__restrict__ x, float a, size_t n) { // y = x + a y
-    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (t < n) y[t] = x[t] + a * y[t];
-}
-
-// ---- iso: chi at the samples (0 for those that take no part) ----------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_pb_chi_at_samples(const float *__restrict__ xyz, const float *__restrict__ nrm, int64_t n, PvGrid g, PbBand B,
-                                                           const float *__restrict__ chi, double *__restrict__ val) {
-    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= n) return;
-    double p[3], nh[3], acc = 0.0;
-    if (pv_valid(xyz, nrm, s, p, nh)) {
-        const double o[3] = {g.ox, g.oy, g.oz};
-        int i0[3];
-        double f[3];
-        for (int a = 0; a < 3; a++) {
-            const double gq = (p[a] - o[a]) / g.h - 0.5;
-            const double fl = floor(gq);
-            i0[a] = (int)fl;
-            f[a] = gq - fl;
-        }
-        for (int dz = 0; dz < 2; dz++)
-            for (int dy = 0; dy < 2; dy++)
-                for (int dx = 0; dx < 2; dx++) {
-                    const long long e = pb_elem_of(B, i0[0] + dx, i0[1] + dy, i0[2] + dz);
-                    if (e < 0) continue;
-                    const double w = ((dx ? f[0] : 1.0 - f[0]) * (dy ? f[1] : 1.0 - f[1])) * (dz ? f[2] : 1.0 - f[2]);
-                    acc += w * (double)chi[e];
-                }
-    }
-    val[s] = acc;
-}
-
-// ---- extraction: f7's marching tetrahedra over the band ----------------------------------------------------------------------------------------
-// flag8[a]: byte d = the edge (a, d) has both ends active and crosses the surface; cnt[a] = how many of them
-__global__ __launch_bounds__(256) void k_pb_edge_flags(const float *__restrict__ chi, float iso, const int32_t *__restrict__ nbr, size_t nodes,
-                                                       unsigned long long *__restrict__ flag8, unsigned int *__restrict__ cnt) {
-    const size_t a = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (a >= nodes) return;
-    const int32_t *nb = nbr + (a >> 9) * 27;
-    const int l = (int)(a & 511), x = l & 7, y = (l >> 3) & 7, z = l >> 6;
-    const bool ia = chi[a] < iso;
-    unsigned long long w = 0;
-    unsigned int m = 0;
-    for (int d = 0; d < 7; d++) {
-        const long long e = pb_node(nb, x + c_dir[d][0], y + c_dir[d][1], z + c_dir[d][2]);
-        if (e < 0) continue;
-        if (ia != (chi[e] < iso)) {
-            w |= 1ull << (8 * d);
-            m++;
-        }
-    }
-    flag8[a] = w;
-    cnt[a] = m;
-}
-// the vertex of edge (a, d): a's first vertex plus the flagged directions below d
-__device__ __forceinline__ unsigned int pb_vertex(const unsigned long long *__restrict__ flag8, const unsigned int *__restrict__ vpos, size_t a, int d) {
-    return vpos[a] + (unsigned int)__popcll(flag8[a] & ((1ull << (8 * d)) - 1ull));
-}
-__global__ __launch_bounds__(256) void k_pb_emit_vertices(const float *__restrict__ chi, float iso, PvGrid g, PbBand B, size_t nodes,
-                                                          const unsigned long long *__restrict__ flag8, const unsigned int *__restrict__ vpos,
-                                                          float *__restrict__ verts, const uint8_t *__restrict__ mask, uint8_t *__restrict__ vkeep) {
-    const size_t a = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (a >= nodes) return;
-    const unsigned long long w = flag8[a];
-    if (w == 0) return;
-    const int32_t *nb = B.nbr + (a >> 9) * 27;
-    int org[3];
-    pb_origin(B, (int)(a >> 9), org);
-    const int l = (int)(a & 511), lc[3] = {l & 7, (l >> 3) & 7, l >> 6};
-    const int ijk[3] = {org[0] + lc[0], org[1] + lc[1], org[2] + lc[2]};
-    const double o[3] = {g.ox, g.oy, g.oz};
-    const float ca = chi[a];
-    size_t v = vpos[a];
-    for (int d = 0; d < 7; d++) {
-        if (!((w >> (8 * d)) & 1)) continue;
-        const float cb = chi[pb_node(nb, lc[0] + c_dir[d][0], lc[1] + c_dir[d][1], lc[2] + c_dir[d][2])];
-        const float t = (iso - ca) / (cb - ca);
-        int cell[3];
-        for (int c = 0; c < 3; c++) {
-            const float pa = (float)(o[c] + ((double)ijk[c] + 0.5) * g.h);
-            const float pb = (float)(o[c] + ((double)(ijk[c] + c_dir[d][c]) + 0.5) * g.h);
-            const float p = pa + t * (pb - pa);
-            verts[3 * v + c] = p;
-            const int q = (int)floor(((double)p - o[c]) / g.h);
-            cell[c] = q < 0 ? 0 : (q > g.N - 1 ? g.N - 1 : q);
-        }
-        if (vkeep) {
-            const long long e = pb_elem_of(B, cell[0], cell[1], cell[2]);
-            vkeep[v] = e < 0 ? 0 : mask[e];
-        }
-        v++;
-    }
-}
-// faces of a cell whose eight corners are active (its 000 node is `a`): EMIT = false counts them, true writes them at foff[a]
-template <bool EMIT>
-__global__ __launch_bounds__(256) void k_pb_cell_faces(const float *__restrict__ chi, float iso, const int32_t *__restrict__ nbr, size_t nodes, TetTable tab,
-                                                       unsigned int *__restrict__ cnt, const unsigned int *__restrict__ foff,
-                                                       const unsigned long long *__restrict__ flag8, const unsigned int *__restrict__ vpos,
-                                                       int32_t *__restrict__ faces) {
-    const size_t a = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (a >= nodes) return;
-    const int32_t *nb = nbr + (a >> 9) * 27;
-    const int l = (int)(a & 511), x = l & 7, y = (l >> 3) & 7, z = l >> 6;
-    long long ce[8];
-    bool whole = true;
-    for (int c = 0; c < 8; c++) {
-        ce[c] = pb_node(nb, x + (c & 1), y + ((c >> 1) & 1), z + ((c >> 2) & 1));
-        whole = whole && ce[c] >= 0;
-    }
-    unsigned int cube = 0; // bit (dx | dy << 1 | dz << 2) = that corner is inside
-    if (whole)
-        for (int c = 0; c < 8; c++)
-            if (chi[ce[c]] < iso) cube |= 1u << c;
-    if (!whole || cube == 0 || cube == 255) {
-        if (!EMIT) cnt[a] = 0;
-        return;
-    }
-    unsigned int nf = 0;
-    size_t o = EMIT ? (size_t)foff[a] : 0;
-    for (int t = 0; t < 6; t++) {
-        const int pa = c_perm[t][0], pb = c_perm[t][1];
-        const int corner[4] = {0, 1 << pa, (1 << pa) | (1 << pb), 7};
-        int m = 0;
-        for (int v = 0; v < 4; v++) m |= ((cube >> corner[v]) & 1) << v;
-        const int nt = tab.ntri[m];
-        if (!EMIT) {
-            nf += nt;
-            continue;
-        }
-        for (int q = 0; q < nt; q++) {
-            int32_t vi[3];
-            for (int c = 0; c < 3; c++) {
-                const int e = tab.e[m][q][c];
-                const int cu = corner[e >> 2], cv = corner[e & 3]; // cu is a subset of cv: the lower node is cu's
-                const int d = cv & ~cu;
-                long long na = ce[0];
-                for (int k = 1; k < 8; k++) na = k == cu ? ce[k] : na; // (no dynamic index into ce: it stays in registers)
-                vi[c] = (int32_t)pb_vertex(flag8, vpos, (size_t)na, pv_dir_code(d & 1, (d >> 1) & 1, (d >> 2) & 1));
-            }
-            if (c_perm_sign[t] < 0) {
-                const int32_t w = vi[1];
-                vi[1] = vi[2];
-                vi[2] = w;
-            }
-            faces[3 * o] = vi[0];
-            faces[3 * o + 1] = vi[1];
-            faces[3 * o + 2] = vi[2];
-            o++;
-        }
-    }
-    if (!EMIT) cnt[a] = nf;
-}
 // one axis of the Chebyshev dilation of the cells' occupancy inside the band (0 off it)
 __global__ __launch_bounds__(256) void k_pb_dilate_cells(const uint8_t *__restrict__ in, uint8_t *__restrict__ out, PbBand B, size_t nodes, int axis, int r) {
     const size_t a = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -456,14 +247,14 @@ int poisson_band_bricks_device(const float *d_xyz, const float *d_nrm4, int64_t 
     unsigned int *pos = M.get<unsigned int>(B3), *opos = M.get<unsigned int>(B3);
     if (!M.ok || hipMalloc((void **)&out->d_slot, B3 * sizeof(int32_t)) != hipSuccess) return RSM_E_NOMEM;
     DEVCHK(hipMemsetAsync(t0, 0, B3, st));
-    hipLaunchKernelGGL(k_pb_mark, blocks_for((size_t)n), dim3(256), 0, st, d_xyz, d_nrm4, n, pb_grid(grid, depth), bsh, t0);
+    hipLaunchKernelGGL(k_pb_mark, blocks_for((size_t)n), dim3(256), 0, st, d_xyz, d_nrm4, n, pv_grid(grid, depth), bsh, t0);
     int s = scan_u32(M, rocprim::make_transform_iterator((const uint8_t *)t0, PbU8ToU32()), opos, B3, st);
     if (s != RSM_OK) return s;
     uint64_t nocc = 0, nact = 0;
     if ((s = scan_total(t0, opos, B3, st, &nocc)) != RSM_OK) return s;
-    hipLaunchKernelGGL(k_pb_dilate_bricks, blocks_for(B3), dim3(256), 0, st, (const uint8_t *)t0, t1, bsh, 0, band_bricks);
-    hipLaunchKernelGGL(k_pb_dilate_bricks, blocks_for(B3), dim3(256), 0, st, (const uint8_t *)t1, t0, bsh, 1, band_bricks);
-    hipLaunchKernelGGL(k_pb_dilate_bricks, blocks_for(B3), dim3(256), 0, st, (const uint8_t *)t0, t1, bsh, 2, band_bricks);
+    hipLaunchKernelGGL(k_pv_dilate<>, blocks_for(B3), dim3(256), 0, st, (const uint8_t *)t0, t1, bsh, 0, band_bricks);
+    hipLaunchKernelGGL(k_pv_dilate<>, blocks_for(B3), dim3(256), 0, st, (const uint8_t *)t1, t0, bsh, 1, band_bricks);
+    hipLaunchKernelGGL(k_pv_dilate<>, blocks_for(B3), dim3(256), 0, st, (const uint8_t *)t0, t1, bsh, 2, band_bricks);
     if ((s = scan_u32(M, rocprim::make_transform_iterator((const uint8_t *)t1, PbU8ToU32()), pos, B3, st)) != RSM_OK) return s;
     if ((s = scan_total(t1, pos, B3, st, &nact)) != RSM_OK) return s;
     DEVCHK(hipGetLastError());
@@ -500,8 +291,9 @@ int poisson_band_rhs_device(const PoissonBand &band, const float *d_xyz, const f
     if (!M.ok) return RSM_E_NOMEM;
     DEVCHK(hipMemsetAsync(V, 0, 3 * nodes * sizeof(unsigned long long), st));
     DEVCHK(hipMemsetAsync(d_occ, 0, nodes, st));
-    hipLaunchKernelGGL(k_pb_splat, blocks_for((size_t)n), dim3(256), 0, st, d_xyz, d_nrm4, n, pb_grid(grid, band.depth), pb_band(band), V, nodes, d_occ);
-    hipLaunchKernelGGL(k_pb_rhs, blocks_for(nodes), dim3(256), 0, st, (const long long *)V, nodes, (const int32_t *)band.d_nbr, d_b32, d_b64);
+    const BandSpace S = pb_space(band);
+    hipLaunchKernelGGL(k_pb_splat, blocks_for((size_t)n), dim3(256), 0, st, d_xyz, d_nrm4, n, pv_grid(grid, band.depth), S, V, d_occ);
+    hipLaunchKernelGGL((k_pv_rhs<BandSpace, long long>), blocks_for(nodes), dim3(256), 0, st, (const long long *)V, S, d_b32, d_b64);
     return mesh_finish(st);
 }
 
@@ -511,66 +303,62 @@ int poisson_band_guess_device(const PoissonBand &band, const float *d_chi_c, flo
     return mesh_finish(st);
 }
 
-int poisson_band_solve_device(const PoissonBand &band, const float *d_b, const float *d_chi_c, double rel_residual, int max_iterations, float *d_chi,
-                              double *residual0, double *residual, int *iterations, double *history, hipStream_t st) {
-    const size_t nodes = pb_nodes(band);
-    const unsigned S = (unsigned)band.n_active;
-    const PbBand B = pb_band(band);
-    *residual0 = *residual = 0.0;
-    *iterations = 0;
-    DevMem M; // (all of the solve's scratch before its first launch)
-    float *r = M.get<float>(nodes), *z = M.get<float>(nodes), *p = M.get<float>(nodes), *q = M.get<float>(nodes), *best = M.get<float>(nodes);
-    double *part = M.get<double>(S), *part2 = M.get<double>(POISSON_SUM_PARTIALS), *scal = M.get<double>(1);
-    if (!M.ok) return RSM_E_NOMEM;
-    auto fetch = [&](double *out) -> int { // the sum of the per-slot partials, in slot order through f7's tree
+namespace {
+// poisson_pcg's Ops on the band: one symmetric red-black Gauss-Seidel sweep from zero as the preconditioner
+struct BandSolver {
+    PbBand B;
+    unsigned S; // the active bricks
+    size_t n;
+    const float *rhs, *chi_c;
+    float *r, *z;
+    double *part, *part2, *scal;
+    hipStream_t st;
+    int fetch(double *out) { // the sum of the per-slot partials, in slot order through f7's tree
         poisson_tree_sum(part, (int64_t)S, part2, scal, st);
         DEVCHK(hipMemcpyAsync(out, scal, sizeof(double), hipMemcpyDeviceToHost, st));
         DEVCHK(hipStreamSynchronize(st));
         return RSM_OK;
-    };
-    auto residual_of_chi = [&](double *rr) -> int { // r = b - L chi
-        hipLaunchKernelGGL(k_pb_stencil<1>, dim3(S), dim3(256), 0, st, (const float *)d_chi, d_b, r, B, d_chi_c, part);
+    }
+    int precondition(double *rho) { // red, black, (black again would recompute the same values from the same red ones), red; the last pass gives r . z
+        hipLaunchKernelGGL(k_pb_rbgs<true>, dim3(S), dim3(256), 0, st, z, (const float *)r, B, 0, (double *)nullptr);
+        hipLaunchKernelGGL(k_pb_rbgs<false>, dim3(S), dim3(256), 0, st, z, (const float *)r, B, 1, (double *)nullptr);
+        hipLaunchKernelGGL(k_pb_rbgs<false>, dim3(S), dim3(256), 0, st, z, (const float *)r, B, 0, part);
+        return fetch(rho);
+    }
+    int apply(const float *p, float *q, double *pq) {
+        hipLaunchKernelGGL(k_pb_stencil<0>, dim3(S), dim3(256), 0, st, p, (const float *)nullptr, q, B, (const float *)nullptr, part);
+        return fetch(pq);
+    }
+    int residual(const float *chi, double *rr) {
+        hipLaunchKernelGGL(k_pb_stencil<1>, dim3(S), dim3(256), 0, st, chi, rhs, r, B, chi_c, part);
         return fetch(rr);
-    };
+    }
+};
+} // namespace
+
+int poisson_band_solve_device(const PoissonBand &band, const float *d_b, const float *d_chi_c, double rel_residual, int max_iterations, float *d_chi,
+                              double *residual0, double *residual, int *iterations, double *history, hipStream_t st) {
+    const size_t nodes = pb_nodes(band);
+    *residual0 = *residual = 0.0;
+    *iterations = 0;
+    DevMem M; // (all of the solve's scratch before its first launch)
+    BandSolver A{pb_band(band), (unsigned)band.n_active, nodes, d_b, d_chi_c};
+    A.r = M.get<float>(nodes), A.z = M.get<float>(nodes);
+    float *p = M.get<float>(nodes), *q = M.get<float>(nodes), *best = M.get<float>(nodes);
+    A.part = M.get<double>(A.S), A.part2 = M.get<double>(POISSON_SUM_PARTIALS), A.scal = M.get<double>(1);
+    A.st = st;
+    if (!M.ok) return RSM_E_NOMEM;
     double bb = 0.0, rr = 0.0;
-    hipLaunchKernelGGL(k_pb_dot, dim3(S), dim3(256), 0, st, d_b, d_b, part);
-    int s = fetch(&bb);
+    hipLaunchKernelGGL(k_pb_dot, dim3(A.S), dim3(256), 0, st, d_b, d_b, A.part);
+    int s = A.fetch(&bb);
     if (s != RSM_OK) return s;
     if (!(bb > 0.0)) return mesh_finish(st); // b = 0 on the band: chi stays the guess
     const double bnorm = sqrt(bb);
-    if ((s = residual_of_chi(&rr)) != RSM_OK) return s;
+    if ((s = A.residual(d_chi, &rr)) != RSM_OK) return s;
     *residual0 = *residual = sqrt(rr) / bnorm;
     if (*residual > rel_residual) {
         DEVCHK(hipMemcpyAsync(best, d_chi, nodes * sizeof(float), hipMemcpyDeviceToDevice, st));
-        double rho_old = 0.0;
-        int worse = 0;
-        for (int it = 1; it <= max_iterations; it++) {
-            // z = M^-1 r: red, black, (black again would recompute the same values from the same red ones), red
-            hipLaunchKernelGGL(k_pb_rbgs<true>, dim3(S), dim3(256), 0, st, z, (const float *)r, B, 0, (double *)nullptr);
-            hipLaunchKernelGGL(k_pb_rbgs<false>, dim3(S), dim3(256), 0, st, z, (const float *)r, B, 1, (double *)nullptr);
-            hipLaunchKernelGGL(k_pb_rbgs<false>, dim3(S), dim3(256), 0, st, z, (const float *)r, B, 0, part);
-            double rho = 0.0, pq = 0.0;
-            if ((s = fetch(&rho)) != RSM_OK) return s;
-            if (it == 1) DEVCHK(hipMemcpyAsync(p, z, nodes * sizeof(float), hipMemcpyDeviceToDevice, st));
-            else hipLaunchKernelGGL(k_pb_xpay, blocks_for(nodes), dim3(256), 0, st, p, (const float *)z, (float)(rho / rho_old), nodes);
-            hipLaunchKernelGGL(k_pb_stencil<0>, dim3(S), dim3(256), 0, st, (const float *)p, (const float *)nullptr, q, B, (const float *)nullptr, part);
-            if ((s = fetch(&pq)) != RSM_OK) return s;
-            if (pq == 0.0 || !std::isfinite(rho / pq)) break; // nothing left to correct in float32
-            hipLaunchKernelGGL(k_pb_axpy, blocks_for(nodes), dim3(256), 0, st, d_chi, (const float *)p, (float)(rho / pq), nodes);
-            if ((s = residual_of_chi(&rr)) != RSM_OK) return s; // recomputed from chi: what is reported is what chi reaches
-            rho_old = rho;
-            *iterations = it;
-            const double res = sqrt(rr) / bnorm;
-            if (history) history[it - 1] = res;
-            if (res < *residual) {
-                *residual = res;
-                worse = 0;
-                if (res <= rel_residual) break; // (chi is the best iterate)
-                DEVCHK(hipMemcpyAsync(best, d_chi, nodes * sizeof(float), hipMemcpyDeviceToDevice, st));
-            } else if (++worse >= PB_STALL)
-                break;
-        }
-        if (*residual > rel_residual) DEVCHK(hipMemcpyAsync(d_chi, best, nodes * sizeof(float), hipMemcpyDeviceToDevice, st));
+        if ((s = poisson_pcg(A, bnorm, rel_residual, max_iterations, PB_STALL, d_chi, p, q, best, residual, iterations, history, st)) != RSM_OK) return s;
     }
     DEVCHK(hipStreamSynchronize(st));
     DEVCHK(hipGetLastError());
@@ -579,79 +367,20 @@ int poisson_band_solve_device(const PoissonBand &band, const float *d_b, const f
 
 void poisson_band_chi_at_samples(const PoissonBand &band, const float *d_xyz, const float *d_nrm4, int64_t n, const float *d_chi, const double grid[4], double *d_val,
                                  hipStream_t st) {
-    hipLaunchKernelGGL(k_pb_chi_at_samples, blocks_for((size_t)n), dim3(256), 0, st, d_xyz, d_nrm4, n, pb_grid(grid, band.depth), pb_band(band), d_chi, d_val);
+    hipLaunchKernelGGL(k_pv_chi_at_samples<BandSpace>, blocks_for((size_t)n), dim3(256), 0, st, d_xyz, d_nrm4, n, pv_grid(grid, band.depth), pb_space(band), d_chi, d_val);
 }
 
 int poisson_band_iso_device(const PoissonBand &band, const float *d_xyz, const float *d_nrm4, int64_t n, int64_t n_valid, const float *d_chi,
                             const double grid[4], double *iso, hipStream_t st) {
-    *iso = 0.0;
-    if (n <= 0 || n_valid <= 0) return RSM_OK;
-    DevMem M;
-    double *val = M.get<double>((size_t)n), *part = M.get<double>(POISSON_SUM_PARTIALS), *scal = M.get<double>(1);
-    if (!M.ok) return RSM_E_NOMEM;
-    poisson_band_chi_at_samples(band, d_xyz, d_nrm4, n, d_chi, grid, val, st);
-    poisson_tree_sum(val, n, part, scal, st);
-    double sum = 0.0;
-    DEVCHK(hipMemcpyAsync(&sum, scal, sizeof sum, hipMemcpyDeviceToHost, st));
-    DEVCHK(hipStreamSynchronize(st));
-    DEVCHK(hipGetLastError());
-    *iso = sum / (double)n_valid;
-    return RSM_OK;
+    auto chi_at = [&](double *val) { poisson_band_chi_at_samples(band, d_xyz, d_nrm4, n, d_chi, grid, val, st); };
+    return poisson_mean_of_chi_at_samples(chi_at, n, nullptr, (double)n_valid, iso, st);
 }
 
 int poisson_band_extract_device(const PoissonBand &band, const float *d_chi, double iso, const double grid[4], const uint8_t *d_occ, int trim_cells,
                                 PoissonMesh *out, int64_t untrimmed[2], hipStream_t st) {
-    poisson_mesh_free(out);
-    untrimmed[0] = untrimmed[1] = 0;
-    const size_t nodes = pb_nodes(band);
-    if (nodes == 0) return RSM_OK;
-    const PvGrid g = pb_grid(grid, band.depth);
-    const PbBand B = pb_band(band);
-    const float iso32 = (float)iso;
-    const TetTable tab = make_tet_table();
-    const bool trim = trim_cells > 0 && d_occ;
-    DevMem M;
-    unsigned long long *flag8 = M.get<unsigned long long>(nodes);
-    unsigned int *vcnt = M.get<unsigned int>(nodes), *vpos = M.get<unsigned int>(nodes), *cnt = M.get<unsigned int>(nodes), *foff = M.get<unsigned int>(nodes);
-    uint8_t *t0 = trim ? M.get<uint8_t>(nodes) : nullptr, *t1 = trim ? M.get<uint8_t>(nodes) : nullptr;
-    if (!M.ok) return RSM_E_NOMEM;
-    hipLaunchKernelGGL(k_pb_edge_flags, blocks_for(nodes), dim3(256), 0, st, d_chi, iso32, (const int32_t *)band.d_nbr, nodes, flag8, vcnt);
-    int s = scan_u32(M, (const unsigned int *)vcnt, vpos, nodes, st);
-    if (s != RSM_OK) return s;
-    hipLaunchKernelGGL(k_pb_cell_faces<false>, blocks_for(nodes), dim3(256), 0, st, d_chi, iso32, (const int32_t *)band.d_nbr, nodes, tab, cnt,
-                       (const unsigned int *)nullptr, (const unsigned long long *)nullptr, (const unsigned int *)nullptr, (int32_t *)nullptr);
-    if ((s = scan_u32(M, (const unsigned int *)cnt, foff, nodes, st)) != RSM_OK) return s;
-    if (trim) {
-        hipLaunchKernelGGL(k_pb_dilate_cells, blocks_for(nodes), dim3(256), 0, st, d_occ, t0, B, nodes, 0, trim_cells);
-        hipLaunchKernelGGL(k_pb_dilate_cells, blocks_for(nodes), dim3(256), 0, st, (const uint8_t *)t0, t1, B, nodes, 1, trim_cells);
-        hipLaunchKernelGGL(k_pb_dilate_cells, blocks_for(nodes), dim3(256), 0, st, (const uint8_t *)t1, t0, B, nodes, 2, trim_cells);
-    }
-    uint64_t nv = 0, nf = 0;
-    if ((s = scan_total(vcnt, vpos, nodes, st, &nv)) != RSM_OK) return s;
-    if ((s = scan_total(cnt, foff, nodes, st, &nf)) != RSM_OK) return s;
-    DEVCHK(hipGetLastError());
-    untrimmed[0] = (int64_t)nv;
-    untrimmed[1] = (int64_t)nf;
-    if (nv == 0 || nf == 0) return RSM_OK;
-    if (nv > (uint64_t)INT32_MAX || nf > (uint64_t)INT32_MAX / 3) return RSM_E_NOMEM;
-    PoissonMesh full;
-    if ((s = mesh_result_alloc(full, nv, nf)) != RSM_OK) return s;
-    uint8_t *vkeep = trim ? M.get<uint8_t>(nv) : nullptr;
-    if (!M.ok) {
-        poisson_mesh_free(&full);
-        return RSM_E_NOMEM;
-    }
-    hipLaunchKernelGGL(k_pb_emit_vertices, blocks_for(nodes), dim3(256), 0, st, d_chi, iso32, g, B, nodes, (const unsigned long long *)flag8,
-                       (const unsigned int *)vpos, full.d_v, (const uint8_t *)t0, vkeep);
-    hipLaunchKernelGGL(k_pb_cell_faces<true>, blocks_for(nodes), dim3(256), 0, st, d_chi, iso32, (const int32_t *)band.d_nbr, nodes, tab, (unsigned int *)nullptr,
-                       (const unsigned int *)foff, (const unsigned long long *)flag8, (const unsigned int *)vpos, full.d_f);
-    if (!trim) {
-        if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) {
-            poisson_mesh_free(&full);
-            return RSM_E_HIP;
-        }
-        *out = full;
-        return RSM_OK;
-    }
-    return poisson_trim_commit(M, full, vkeep, out, st);
+    const BandSpace S = pb_space(band);
+    auto dilate = [&](const uint8_t *in, uint8_t *to, int axis) {
+        hipLaunchKernelGGL(k_pb_dilate_cells, blocks_for(S.nodes()), dim3(256), 0, st, in, to, S.B, S.nodes(), axis, trim_cells);
+    };
+    return poisson_extract(S, pv_grid(grid, band.depth), d_chi, iso, d_occ, trim_cells, dilate, out, untrimmed, st);
 }

@@ -7,8 +7,8 @@
 //   level D         a sample with d_s > D - 1 puts alpha = fr w_s (d_s = D: w_s) at its eight level-D nodes: f14's fixed-point terms
 //                   llrint((wt (alpha n^_a)) 2^32) into brick-major V_D[3][S 512] through the slot table; 64-bit integer atomics.  With
 //                   band_bricks >= 1 every such node is active; nodes outside the grid are dropped.  occ is f16's      k_pbd_splat
-//   right-hand side U_D(node) = V_D(node) 2^-32 + P(W)(node); P = f14's prolongation at one node, in k_pd_cascade's expression and order (x, then
-//                   y, for the near and the far z-plane; 0.75 near + 0.25 far; 0 outside the coarse grid); V_D = 0 at an inactive node, U_D = 0
+//   right-hand side U_D(node) = V_D(node) 2^-32 + P(W)(node); P = f14's prolongation at one node (poisson_space.h's pd_prolong_at, which
+//                   k_pd_cascade evaluates too; 0 outside the coarse grid); V_D = 0 at an inactive node, U_D = 0
 //                   outside the fine grid.  b_f = 0.5 ((dx U_x + dy U_y) + dz U_z) in fp64 on every active node, rounded once to float for the
 //                   band solver.  One workgroup per brick: the 6^3 coarse nodes under the brick and its halo of one fine node go to LDS per
 //                   component, then each component's slab of U (10 x 8 x 8 along its own axis), then the differences.  The bits depend on
@@ -18,7 +18,7 @@
 #include "../../include/rsm.h"
 #include "rsm_dev.h"
 #include "mesh_common.h"
-#include "poisson_band_common.h"
+#include "poisson_space.h"
 #include "poisson_density_common.h"
 
 #include <math.h>
@@ -28,44 +28,24 @@ namespace {
 typedef unsigned long long u64;
 
 // ---- level D of the splat, on the bricks ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_pbd_splat(const float *__restrict__ xyz, const float *__restrict__ nrm, int64_t n, PvGrid g, PbBand B,
+__global__ __launch_bounds__(256) void k_pbd_splat(const float *__restrict__ xyz, const float *__restrict__ nrm, int64_t n, MtGrid g, BandSpace S,
                                                    const double *__restrict__ w, const double *__restrict__ d, u64 *__restrict__ V /* [3][S 512] */,
-                                                   size_t nodes, uint8_t *__restrict__ occ) {
+                                                   uint8_t *__restrict__ occ) {
     const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= n) return;
     double p[3], nh[3];
     if (!pv_valid(xyz, nrm, s, p, nh)) return;
-    const double o[3] = {g.ox, g.oy, g.oz};
-    const int N = g.N;
     int c[3];
-    for (int a = 0; a < 3; a++) { // occ: f16's cell, clamped to the grid
-        const int cc = (int)floor((p[a] - o[a]) / g.h);
-        c[a] = cc < 0 ? 0 : (cc > N - 1 ? N - 1 : cc);
-    }
-    const long long ce = pb_elem_of(B, c[0], c[1], c[2]);
+    pv_occ_cell3(p, g, c); // occ: f16's cell, clamped to the grid
+    const long long ce = S.elem(c[0], c[1], c[2]);
     if (ce >= 0) occ[ce] = 1; // (the cell's brick is occupied, so active)
     int lo;
-    const double fr = pd_split(d[s], g.sh, &lo);
-    const int t = g.sh - lo; // level D is lo (t = 0) or lo + 1 (t = 1)
+    const double fr = pd_split(d[s], S.B.sh, &lo);
+    const int t = S.B.sh - lo; // level D is lo (t = 0) or lo + 1 (t = 1)
     if (t > 1) return;
     const double alpha = pd_alpha(fr, w[s], t);
-    const MtGrid mg{g.ox, g.oy, g.oz, g.h, N};
-    double fl[3], f[3];
-    int i0[3];
-    mt_cell(p, mg, fl, f);
-    if (!mt_cell_index(fl, N, i0)) return;
     const double an[3] = {alpha * nh[0], alpha * nh[1], alpha * nh[2]};
-    for (int dz = 0; dz < 2; dz++)
-        for (int dy = 0; dy < 2; dy++)
-            for (int dx = 0; dx < 2; dx++) {
-                const long long node = pb_elem_of(B, i0[0] + dx, i0[1] + dy, i0[2] + dz);
-                if (node < 0) continue; // outside the grid; (inactive cannot happen with band_bricks >= 1)
-                const double wt = mt_weight(f, dx, dy, dz);
-                for (int a = 0; a < 3; a++) {
-                    const long long q = __double2ll_rn((wt * an[a]) * PD_FIX);
-                    if (q) atomicAdd(&V[a * nodes + (size_t)node], (u64)q);
-                }
-            }
+    pv_splat8(S, p, g, an, V, S.nodes());
 }
 
 // ---- the right-hand side: one workgroup of 256 threads per brick --------------------------------------------------------------------------
@@ -101,19 +81,13 @@ __global__ __launch_bounds__(256) void k_pbd_rhs(const long long *__restrict__ V
         const long long e = pb_node(nb, l[0], l[1], l[2]);
         double U = 0.0; // outside the fine grid
         if (e != -2) {
-            const double own = e >= 0 ? (double)V[a * nodes + (size_t)e] / PD_FIX : 0.0; // (k_pd_cascade's scale is 8^0 here)
+            const double own = e >= 0 ? (double)V[a * nodes + (size_t)e] / PV_FIX : 0.0; // (k_pd_cascade's scale is 8^0 here)
             const double *A = sW[a];
             int ci[2], cj[2], ck[2];
             pbd_near_far(l[0], ci[0], ci[1]);
             pbd_near_far(l[1], cj[0], cj[1]);
             pbd_near_far(l[2], ck[0], ck[1]);
-            double y[2];
-            for (int c = 0; c < 2; c++) { // x, then y, for the near and the far plane
-                const double x0 = 0.75 * A[ci[0] + PBD_CW * (cj[0] + PBD_CW * ck[c])] + 0.25 * A[ci[1] + PBD_CW * (cj[0] + PBD_CW * ck[c])];
-                const double x1 = 0.75 * A[ci[0] + PBD_CW * (cj[1] + PBD_CW * ck[c])] + 0.25 * A[ci[1] + PBD_CW * (cj[1] + PBD_CW * ck[c])];
-                y[c] = 0.75 * x0 + 0.25 * x1;
-            }
-            U = own + (0.75 * y[0] + 0.25 * y[1]);
+            U = own + pd_prolong_at([=](int x, int y, int z) { return A[x + PBD_CW * (y + PBD_CW * z)]; }, ci, cj, ck);
         }
         sU[a][r] = U;
     }
@@ -144,18 +118,13 @@ int poisson_band_density_rhs_device(const PoissonBand &band, const float *d_xyz,
     const double *W = nullptr;
     const int s = poisson_density_levels_device(d_xyz, d_nrm4, n, band.depth, band.depth - 1, grid, d_w, d_d, d_levels, nullptr, &W, st);
     if (s != RSM_OK) return s;
-    hipLaunchKernelGGL(k_pbd_splat, blocks_for((size_t)n), dim3(256), 0, st, d_xyz, d_nrm4, n, pb_grid(grid, band.depth), pb_band(band), d_w, d_d, V, nodes, d_occ);
+    hipLaunchKernelGGL(k_pbd_splat, blocks_for((size_t)n), dim3(256), 0, st, d_xyz, d_nrm4, n, pv_grid(grid, band.depth), pb_space(band), d_w, d_d, V, d_occ);
     hipLaunchKernelGGL(k_pbd_rhs, dim3((unsigned)band.n_active), dim3(256), 0, st, (const long long *)V, nodes, pb_band(band), W, d_b32, d_b64);
     return mesh_finish(st);
 }
 
 int poisson_band_iso_weighted_device(const PoissonBand &band, const float *d_xyz, const float *d_nrm4, int64_t n, const double *d_w, double sum_w, const float *d_chi,
                                      const double grid[4], double *iso, hipStream_t st) {
-    *iso = 0.0;
-    if (n <= 0 || !(sum_w > 0.0)) return RSM_OK;
-    DevMem M;
-    double *val = M.get<double>((size_t)n);
-    if (!M.ok) return RSM_E_NOMEM;
-    poisson_band_chi_at_samples(band, d_xyz, d_nrm4, n, d_chi, grid, val, st);
-    return poisson_weighted_mean_device(val, d_w, n, sum_w, iso, st);
+    auto chi_at = [&](double *val) { poisson_band_chi_at_samples(band, d_xyz, d_nrm4, n, d_chi, grid, val, st); };
+    return poisson_mean_of_chi_at_samples(chi_at, n, d_w, sum_w, iso, st);
 }

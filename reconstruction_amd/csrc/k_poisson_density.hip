@@ -12,7 +12,7 @@
 //                level.  occ is f7's, on the finest level                                                                k_pd_splat
 //   cascade      U_3 = V_3 2^-32 8^(3 - depth); U_L = V_L 2^-32 8^(L - depth) + P(U_{L-1}) in fp64, in place of V_L; P = cell-centred trilinear
 //                prolongation, x then y then z, 0.75 near + 0.25 far, 0 outside                                         k_pd_cascade
-//   rhs          f7's central differences of U_depth in fp64, rounded once to float for the solver                     k_pd_rhs
+//   rhs          f7's central differences of U_depth in fp64, rounded once to float for the solver                     k_pv_rhs<DenseSpace, double>
 //   iso          sum w_s chi(p_s) / sum w_s: f7's chi at the samples (poisson_chi_at_samples) times w_s, both sums in f7's tree   k_pd_mul
 // The levels share one buffer of 64-bit words: level L's three components start at word 3 (8^L - 8^3) / 7.  The buffer's top level and the
 // finest depth are two numbers: the banded call (k_poisson_band_density.hip; f17) keeps the levels 3..depth - 1 here and the finest on its bricks.
@@ -21,6 +21,7 @@
 #include "rsm_dev.h"
 #include "mesh_common.h"
 #include "poisson_density_common.h"
+#include "poisson_space.h"
 
 #include <math.h>
 #include <string.h>
@@ -29,14 +30,14 @@ namespace {
 
 typedef unsigned long long u64;
 
-struct PdBox { // f7's box: the origin, the finest step, the finest level, the buffer's top level (<= depth)
-    double ox, oy, oz, h;
+struct PdBox { // f7's grid at the finest level `depth`, and the buffer's top level (<= depth)
+    MtGrid g;
     int depth, top;
 };
 __host__ __device__ __forceinline__ size_t pd_level_nodes(int L) { return (size_t)1 << (3 * L); }
 __host__ __device__ __forceinline__ size_t pd_level_word(int L) { return 3 * ((pd_level_nodes(L) - pd_level_nodes(PD_LMIN)) / 7); }
 // level L's grid: h_L = side / 2^L = h 2^(depth - L), exact
-__device__ __forceinline__ MtGrid pd_level_grid(const PdBox &b, int L) { return MtGrid{b.ox, b.oy, b.oz, b.h * (double)(1 << (b.depth - L)), 1 << L}; }
+__device__ __forceinline__ MtGrid pd_level_grid(const PdBox &b, int L) { return MtGrid{b.g.ox, b.g.oy, b.g.oz, b.g.h * (double)(1 << (b.depth - L)), 1 << L}; }
 
 // ---- 3: weight and depth of a sample; ctr[0] = the least d_s as its bit pattern (d_s > 0: the order of the doubles), ctr[1] = samples below depth
 __global__ __launch_bounds__(256) void k_pd_sample(const float *__restrict__ xyz, const float *__restrict__ nrm, int64_t n, int depth,
@@ -86,14 +87,9 @@ __global__ __launch_bounds__(256) void k_pd_splat(const float *__restrict__ xyz,
     if (!pv_valid(xyz, nrm, s, p, nh)) return;
     const int depth = box.depth;
     if (occ) { // occ: f7's cell on the finest level, clamped to the grid
-        const double o[3] = {box.ox, box.oy, box.oz};
-        const int N = 1 << depth;
-        size_t c[3];
-        for (int a = 0; a < 3; a++) {
-            const double u = floor((p[a] - o[a]) / box.h);
-            c[a] = u >= 0.0 ? (u < (double)N ? (size_t)u : (size_t)(N - 1)) : 0; // (NaN lands on 0)
-        }
-        occ[c[0] + (size_t)N * (c[1] + (size_t)N * c[2])] = 1;
+        int c[3];
+        pv_occ_cell3(p, box.g, c);
+        occ[DenseSpace{depth}.elem(c[0], c[1], c[2])] = 1;
     }
     const double ws = w[s];
     int lo;
@@ -102,27 +98,8 @@ __global__ __launch_bounds__(256) void k_pd_splat(const float *__restrict__ xyz,
         const int L = lo + t;
         if (L > box.top) break; // (top <= depth: the levels above the buffer's top are another unit's)
         const double alpha = pd_alpha(fr, ws, t);
-        const MtGrid g = pd_level_grid(box, L);
-        double fl[3], f[3];
-        int i0[3];
-        mt_cell(p, g, fl, f);
-        if (!mt_cell_index(fl, g.N, i0)) continue;
-        const int N = g.N;
-        const size_t N3 = pd_level_nodes(L);
-        u64 *VL = V + pd_level_word(L);
         const double an[3] = {alpha * nh[0], alpha * nh[1], alpha * nh[2]};
-        for (int dz = 0; dz < 2; dz++)
-            for (int dy = 0; dy < 2; dy++)
-                for (int dx = 0; dx < 2; dx++) {
-                    const int i = i0[0] + dx, j = i0[1] + dy, k = i0[2] + dz;
-                    if (i < 0 || j < 0 || k < 0 || i >= N || j >= N || k >= N) continue;
-                    const double wt = mt_weight(f, dx, dy, dz);
-                    const size_t node = (size_t)i + (size_t)N * ((size_t)j + (size_t)N * k);
-                    for (int a = 0; a < 3; a++) {
-                        const long long q = __double2ll_rn((wt * an[a]) * PD_FIX);
-                        if (q) atomicAdd(&VL[a * N3 + node], (u64)q);
-                    }
-                }
+        pv_splat8(DenseSpace{L}, p, pd_level_grid(box, L), an, V + pd_level_word(L), pd_level_nodes(L));
     }
 }
 
@@ -137,37 +114,14 @@ __global__ __launch_bounds__(256) void k_pd_cascade(u64 *fine, const double *__r
     const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (t >= n3) return;
     u64 *word = fine + (size_t)blockIdx.y * n3 + t;
-    double u = ((double)(long long)*word / PD_FIX) * scale;
+    double u = ((double)(long long)*word / PV_FIX) * scale;
     if (coarse) {
         const double *A = coarse + (size_t)blockIdx.y * (n3 >> 3);
         const int i = (int)(t & (nf - 1)), j = (int)((t >> shf) & (nf - 1)), k = (int)(t >> (2 * shf));
         const int ci[2] = {i >> 1, (i >> 1) + ((i & 1) ? 1 : -1)}, cj[2] = {j >> 1, (j >> 1) + ((j & 1) ? 1 : -1)}, ck[2] = {k >> 1, (k >> 1) + ((k & 1) ? 1 : -1)};
-        double y[2];
-        for (int c = 0; c < 2; c++) { // x, then y, for the near and the far plane
-            const double x0 = 0.75 * pd_coarse(A, nc, ci[0], cj[0], ck[c]) + 0.25 * pd_coarse(A, nc, ci[1], cj[0], ck[c]);
-            const double x1 = 0.75 * pd_coarse(A, nc, ci[0], cj[1], ck[c]) + 0.25 * pd_coarse(A, nc, ci[1], cj[1], ck[c]);
-            y[c] = 0.75 * x0 + 0.25 * x1;
-        }
-        u = u + (0.75 * y[0] + 0.25 * y[1]);
+        u = u + pd_prolong_at([=](int x, int y, int z) { return pd_coarse(A, nc, x, y, z); }, ci, cj, ck);
     }
     __builtin_memcpy(word, &u, 8);
-}
-
-// ---- 6: the right-hand side from U_depth ---------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_pd_rhs(const double *__restrict__ U, int sh, float *__restrict__ b32, double *__restrict__ b64) {
-    const int N = 1 << sh;
-    const size_t N3 = (size_t)1 << (3 * sh);
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= N3) return;
-    const int i = (int)(idx & (N - 1)), j = (int)((idx >> sh) & (N - 1)), k = (int)(idx >> (2 * sh));
-    const size_t sy = (size_t)N, sz = (size_t)N * N;
-    const double *Ux = U, *Uy = U + N3, *Uz = U + 2 * N3;
-    const double dx = (i + 1 < N ? Ux[idx + 1] : 0.0) - (i > 0 ? Ux[idx - 1] : 0.0);
-    const double dy = (j + 1 < N ? Uy[idx + sy] : 0.0) - (j > 0 ? Uy[idx - sy] : 0.0);
-    const double dz = (k + 1 < N ? Uz[idx + sz] : 0.0) - (k > 0 ? Uz[idx - sz] : 0.0);
-    const double b = 0.5 * ((dx + dy) + dz);
-    if (b32) b32[idx] = (float)b;
-    if (b64) b64[idx] = b;
 }
 
 // ---- 7: w_s chi(p_s) ---------------------------------------------------------------------------------------------------------------------------
@@ -210,7 +164,7 @@ int poisson_density_levels_device(const float *d_xyz, const float *d_nrm4, int64
                                   unsigned long long *d_V, uint8_t *d_occ, const double **d_U_top, hipStream_t st) {
     DEVCHK(hipMemsetAsync(d_V, 0, pd_level_word(top + 1) * sizeof(u64), st));
     if (d_occ) DEVCHK(hipMemsetAsync(d_occ, 0, pd_level_nodes(depth), st));
-    const PdBox box{grid[0], grid[1], grid[2], grid[3], depth, top};
+    const PdBox box{pv_grid(grid, depth), depth, top};
     hipLaunchKernelGGL(k_pd_splat, blocks_for((size_t)n), dim3(256), 0, st, d_xyz, d_nrm4, n, box, d_w, d_d, d_V, d_occ);
     for (int L = PD_LMIN; L <= top; L++) {
         const double *coarse = L > PD_LMIN ? (const double *)(d_V + pd_level_word(L - 1)) : nullptr;
@@ -221,7 +175,7 @@ int poisson_density_levels_device(const float *d_xyz, const float *d_nrm4, int64
 }
 
 void poisson_density_rhs_of_field(const double *d_U, int depth, float *d_b32, double *d_b64, hipStream_t st) {
-    hipLaunchKernelGGL(k_pd_rhs, blocks_for(pd_level_nodes(depth)), dim3(256), 0, st, d_U, depth, d_b32, d_b64);
+    hipLaunchKernelGGL((k_pv_rhs<DenseSpace, double>), blocks_for(pd_level_nodes(depth)), dim3(256), 0, st, d_U, DenseSpace{depth}, d_b32, d_b64);
 }
 
 int poisson_density_rhs_device(const float *d_xyz, const float *d_nrm4, int64_t n, int depth, const double grid[4], int kernel_depth, double samples_per_node,
@@ -255,11 +209,6 @@ int poisson_weighted_mean_device(double *d_val, const double *d_w, int64_t n, do
 
 int poisson_iso_weighted_device(const float *d_xyz, const float *d_nrm4, int64_t n, const double *d_w, double sum_w, const float *d_chi, int depth,
                                 const double grid[4], double *iso, hipStream_t st) {
-    *iso = 0.0;
-    if (n <= 0 || !(sum_w > 0.0)) return RSM_OK;
-    DevMem M;
-    double *val = M.get<double>((size_t)n);
-    if (!M.ok) return RSM_E_NOMEM;
-    poisson_chi_at_samples(d_xyz, d_nrm4, n, d_chi, depth, grid, val, st);
-    return poisson_weighted_mean_device(val, d_w, n, sum_w, iso, st);
+    auto chi_at = [&](double *val) { poisson_chi_at_samples(d_xyz, d_nrm4, n, d_chi, depth, grid, val, st); };
+    return poisson_mean_of_chi_at_samples(chi_at, n, d_w, sum_w, iso, st);
 }

@@ -1,10 +1,9 @@
 // poisson_density_common.h -- what the units that splat a sample at the two levels around its depth share (k_poisson_density.hip,
-// k_poisson_band_density.hip): the fixed-point scale, the coarsest level, and how a depth splits.
+// k_poisson_band_density.hip): the coarsest level, and how a depth splits.
 #pragma once
 
 #include <math.h>
 
-#define PD_FIX 4294967296.0 // 2^32: the splat's fixed-point scale, f7's
 #define PD_LMIN 3           // the coarsest level a sample is spread on
 
 // d_s on a grid whose finest level is `depth`: *lo = floor(d_s) in PD_LMIN..depth, returns fr = d_s - lo.  (k_pd_sample clamped d_s to

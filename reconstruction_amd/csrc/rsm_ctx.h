@@ -105,7 +105,7 @@ struct rsm_ctx {
     PoissonMesh pmesh;                 // the last mesh of rsm_poisson_mesh / rsm_stage_iso_mesh (rsm_poisson_last_mesh copies it out)
     uint8_t *mcol_rgb = nullptr;       // rsm_mesh_color_last's colours of that mesh (rsm_mesh_last_colors copies them out) ...
     int32_t *mcol_best = nullptr;      // ... and best views
-    bool mcol_valid = false;           // they are the colours of pmesh as it is now: a later mesh has none (mesh_replaced(), rsm_mesh.hip)
+    bool mcol_valid = false;           // they are the colours of pmesh as it is now: a later mesh has none (mesh_replaced())
     long long opt_meshcolor_big_box = 4096; // rsm_mesh_color: a (face, view) bounding box of more pixels is strided by a block, not walked by one thread
     int opt_filter_wg_max = 2048;      // rsm_filter_last_cloud: the wave passes' workgroup form while at most this many queries are left (0: never)
     int opt_filter_normals_window = 8; // rsm_filter_last_cloud: the normals' radius search on the pixel lattice while no point needs a wider window than this (0: grid)
@@ -279,6 +279,13 @@ static inline int finish(rsm_ctx *c, Tmp &t) {
     if (!t.ok) return set_err(c, RSM_E_HIP, "stage alloc/copy failed");
     return RSM_OK;
 }
+// ---- what the mesh units' entries share (rsm_poisson.hip, rsm_mesh.hip) ---------------------------------------------------------------------
+// the end of the *_fail texts: after a HIP failure ": " and the runtime's last error, else nothing
+static inline std::string hip_tail(int s) { return s == RSM_E_HIP ? std::string(": ") + hipGetErrorString(hipGetLastError()) : std::string(); }
+// The colours of rsm_mesh_color_last / rsm_mesh_stitch_last are those of the mesh they were computed on.  Whoever hands &c->pmesh to a producer
+// calls this once the producer has replaced (or freed) that mesh; nothing else decides whether the colours still hold.
+static inline void mesh_replaced(rsm_ctx *c) { c->mcol_valid = false; }
+
 static inline bool stage_ok(rsm_ctx *c, int W, int H) { return c && W > 0 && H > 0 && hipSetDevice(c->device) == hipSuccess; }
 
 // the arguments of a one-direction stage call on host buffers (the parity entry points)

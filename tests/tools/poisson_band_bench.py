@@ -23,6 +23,9 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from poisson_bench import digest_line  # noqa: E402
 
 
 def analyze(path):
@@ -129,9 +132,11 @@ def main():
         print("dense depth 9 trim 4: %d samples -> %d vertices, %d faces (%d / %d before the trim); h %.6g; %d cycles, residual %.2e, status %d; "
               "hipEvent %.2f ms (wall %.2f ms; all %s)" % (k, nv, nf, st["n_vertices_untrimmed"], st["n_faces_untrimmed"], st["h"], st["cycles"], st["residual"],
                                                            st["status"], best[0], best[1], ["%.2f" % t[0] for t in times]), flush=True)
+        print(digest_line(ctx, nv, nf, st), flush=True)
         dv, _ = ctx.poisson_last_mesh(nv, nf)
         (nv, nf, st), times = timed(torch, lambda: ctx.poisson_mesh_banded_device(ox.data_ptr(), on.data_ptr(), k, 9, trim_cells=4, band_bricks=1), args.reps)
         print(band_line("banded depth 9 band_bricks 1 trim 4", k, nv, nf, st, times), flush=True)
+        print(digest_line(ctx, nv, nf, st), flush=True)
         bv, _ = ctx.poisson_last_mesh(nv, nf)
         from scipy.spatial import cKDTree
         d = cKDTree(dv.astype(np.float64)).query(bv.astype(np.float64), workers=8)[0] / st["h"]
@@ -140,6 +145,7 @@ def main():
         call = lambda: ctx.poisson_mesh_banded_device(ox.data_ptr(), on.data_ptr(), k, 10, trim_cells=8, band_bricks=2)
         (nv, nf, st), times = timed(torch, call, args.reps, warm=args.reps > 1)
         print(band_line("banded depth 10 band_bricks 2 trim 8", k, nv, nf, st, times), flush=True)
+        print(digest_line(ctx, nv, nf, st), flush=True)
         _, before, peak = with_memory_peak(torch, call)
         print("  device memory in use: %.2f GB before the call, %.2f GB at its peak (sampled every 2 ms)" % (before / 1e9, peak / 1e9), flush=True)
     return 0

@@ -22,6 +22,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, HERE)
 
 from poisson_band_bench import band_line, timed, with_memory_peak  # noqa: E402
+from poisson_bench import digest_line  # noqa: E402
 
 
 def analyze(path):
@@ -93,12 +94,14 @@ def main():
         plain = lambda: ctx.poisson_mesh_banded_device(ox.data_ptr(), on.data_ptr(), k, args.depth, trim_cells=args.trim, band_bricks=args.band)
         (nv, nf, st), times = timed(torch, plain, args.reps, warm=args.reps > 1)
         print(band_line("banded " + tag, k, nv, nf, st, times), flush=True)
+        print(digest_line(ctx, nv, nf, st), flush=True)
     call = lambda: ctx.poisson_mesh_banded_weighted_device(ox.data_ptr(), on.data_ptr(), k, args.depth, trim_cells=args.trim, band_bricks=args.band,
                                                            samples_per_node=args.samples_per_node)
     (nv, nf, st), times = timed(torch, call, args.reps, warm=args.reps > 1)
     print(band_line("banded weighted %s samples_per_node %g" % (tag, args.samples_per_node), k, nv, nf, st, times), flush=True)
     print("  density on 2^%d nodes; %d of %d samples below depth %d, least depth %.3f; sum of w %.6g; iso %.6g"
           % (st["kernel_depth"], st["n_below_depth"], st["n_valid"], args.depth, st["min_sample_depth"], st["sum_w"], st["iso"]), flush=True)
+    print(digest_line(ctx, nv, nf, st), flush=True)
     if not args.only_weighted:
         _, before, peak = with_memory_peak(torch, call)
         print("  device memory in use: %.2f GB before the call, %.2f GB at its peak (sampled every 2 ms)" % (before / 1e9, peak / 1e9), flush=True)

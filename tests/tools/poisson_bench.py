@@ -68,6 +68,17 @@ def curve():
     return 0
 
 
+def digest_line(ctx, nv, nf, st):
+    """SHA-256 of the last mesh's vertex bytes, of its face bytes and of the stats (the values in key order as float64): two libraries give
+    the same three on the same input or they differ somewhere"""
+    import hashlib
+
+    import numpy as np
+    v, f = ctx.poisson_last_mesh(nv, nf)
+    vec = np.concatenate([np.atleast_1d(np.asarray(st[key], np.float64)).ravel() for key in sorted(st)])
+    return "  sha256: vertices %s faces %s stats %s" % tuple(hashlib.sha256(np.ascontiguousarray(a).tobytes()).hexdigest() for a in (v, f, vec))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pairs", type=int, default=10)
@@ -124,6 +135,7 @@ def main():
           "status %d; hipEvent %.2f ms (wall %.2f ms; all %s)"
           % (args.depth, args.trim, k, st["n_invalid"], nv, nf, st["n_vertices_untrimmed"], st["n_faces_untrimmed"], st["cycles"], st["residual"],
              st["status"], best[0], best[1], ["%.2f" % t[0] for t in times]), flush=True)
+    print(digest_line(ctx, nv, nf, st), flush=True)
     return 0
 
 

@@ -19,6 +19,9 @@ import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from poisson_bench import digest_line  # noqa: E402
 
 
 def analyze(path):
@@ -97,6 +100,7 @@ def main():
           "status %d; hipEvent %.2f ms (wall %.2f ms; all %s)"
           % (args.depth, args.trim, k, st["n_invalid"], nv, nf, st["n_vertices_untrimmed"], st["n_faces_untrimmed"], st["cycles"], st["residual"],
              st["status"], best[0], best[1], ["%.2f" % t[0] for t in times]), flush=True)
+    print(digest_line(ctx, nv, nf, st), flush=True)
     (nv, nf, st), times = timed(torch, lambda: ctx.poisson_mesh_weighted_device(ox.data_ptr(), on.data_ptr(), k, args.depth, trim_cells=args.trim,
                                                                                  samples_per_node=args.samples_per_node, kernel_depth=args.kernel_depth), args.reps)
     best = min(times)
@@ -105,6 +109,7 @@ def main():
           % (args.depth, args.trim, args.samples_per_node, st["kernel_depth"], st["n_below_depth"], st["n_valid"], st["min_sample_depth"], nv, nf,
              st["n_vertices_untrimmed"], st["n_faces_untrimmed"], st["cycles"], st["residual"], st["status"], best[0], best[1], ["%.2f" % t[0] for t in times]),
           flush=True)
+    print(digest_line(ctx, nv, nf, st), flush=True)
     return 0
 
 
